@@ -136,6 +136,26 @@ static inline mtr_status mtr_pack_read(const uint8_t *codes, int32_t len, uint32
 mtr_status mtr_upload_batch_packed(mtr_ctx *ctx, const uint32_t *packed, int64_t n_words, const int64_t *woff,
                                    const int32_t *lens, int32_t n_reads);
 
+/* ---- reads already in device memory -------------------------------------------------------------------------------
+ * mtr_upload_batch_device takes the reads as text in DEVICE memory on the context's GPU (a basecaller's output, a torch
+ * tensor) and packs them on the device, by a kernel, into exactly the image mtr_upload_batch builds on the host.
+ *   d_text       text_bytes bytes of device memory on the context's device, one byte per base:
+ *                MTR_TEXT_ASCII 'A','C','G','T' or 'a','c','g','t'; MTR_TEXT_CODES 0..3 = A C G T (what mtr_upload_batch takes)
+ *   offsets      n_reads HOST int64 start offsets into d_text;  lens  n_reads HOST lengths (1..MTR_MAX_READ_LENGTH)
+ *   wait_stream  the hipStream_t the caller wrote d_text on (NULL = the null stream): the library records an event there and
+ *                its own stream waits for that event (no device-wide synchronisation)
+ * Returns after the packing has finished: d_text may then be reused.  Bytes of d_text outside every read are never looked at;
+ * a byte inside a read that is not a base of the kind (e.g. 'N', '
+', a code > 3) is MTR_ERR_BAD_ARG, and mtr_last_error names
+ * the first such read.  So are d_text that is not device memory of the context's GPU, a read outside text_bytes, an unknown
+ * text_kind.  A refused upload leaves no batch uploaded, as a refused mtr_upload_batch does; run / fetch / export / alignments
+ * work after a device upload as after a host one.  File-order mode (mtr_upload_batch_in_file) needs the bases on the host:
+ * there is no device variant of it. */
+#define MTR_TEXT_ASCII 0
+#define MTR_TEXT_CODES 1
+mtr_status mtr_upload_batch_device(mtr_ctx *ctx, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
+                                   const int32_t *lens, int32_t n_reads, int32_t text_kind, void *wait_stream);
+
 /* ---- wire form of the record table -------------------------------------------------------------------------------
  * A mtr_record is 2560 bytes because unit[] and unit_score[] are sized for MAX_PERIOD; a typical record uses 600.  The
  * wire form keeps what insert_an_alignment_into_set receives and nothing else, record after record:

@@ -1,6 +1,7 @@
 """mtr_amd — MI355X (gfx950) implementation of reference mTR's per-read hot path.
 
-Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointers, no torch types).
+Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointers).  Only the device-input methods
+(Engine.upload_device / process_device / export_tensor) take or return torch tensors; they import torch when called.
 The product path is libmtr_hip.so only: importing works without a GPU, but creating an Engine
 without the library or without a HIP device raises — there is no CPU fallback.
 """
@@ -15,6 +16,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MTR_LIB", os.path.join(HERE, "libmtr_hip.so"))   # MTR_LIB: A/B another build of the library
 MAX_PERIOD = 500
+MAX_READ_LENGTH = 833333                     # MTR_MAX_READ_LENGTH
+TEXT_ASCII, TEXT_CODES = 0, 1                # MTR_TEXT_ASCII, MTR_TEXT_CODES
 
 STATUS = {0: "MTR_OK", 1: "MTR_ERR_NO_DEVICE", 2: "MTR_ERR_BAD_ARG", 3: "MTR_ERR_OOM", 4: "MTR_ERR_HIP",
           5: "MTR_ERR_OVERFLOW", 6: "MTR_ERR_DP_TOO_LARGE"}
@@ -35,7 +38,7 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_run_resident_async", "mtr_wait", "mtr_alignments",
            "mtr_file_state_create", "mtr_file_state_destroy", "mtr_upload_batch_in_file", "mtr_file_state_skip",
            "mtr_get_bases_after_read", "mtr_upload_batch_packed", "mtr_fetch_results_packed", "mtr_export_packed_device",
-           "mtr_unpack_records", "mtr_pack_records", "mtr_get_first_failed_read"]
+           "mtr_unpack_records", "mtr_pack_records", "mtr_get_first_failed_read", "mtr_upload_batch_device"]
 
 
 class MtrError(RuntimeError):
@@ -157,6 +160,8 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_test_wrap_dp.restype = C.c_int
     lib.mtr_upload_batch_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]
     lib.mtr_upload_batch_packed.restype = C.c_int
+    lib.mtr_upload_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.mtr_upload_batch_device.restype = C.c_int
     lib.mtr_fetch_results_packed.argtypes = [C.c_void_p, C.c_int32, P(C.c_void_p), P(C.c_int64), P(C.c_void_p), P(C.c_int64)]
     lib.mtr_fetch_results_packed.restype = C.c_int
     lib.mtr_export_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(C.c_int64), P(C.c_int64)]
@@ -188,8 +193,56 @@ def _flatten(reads: Sequence[np.ndarray]):
     return np.ascontiguousarray(bases), offs, lens
 
 
+def _host_ints(a, dtype, what: str) -> np.ndarray:
+    if hasattr(a, "detach"):                   # a torch tensor: it must be on the CPU
+        if a.device.type != "cpu":
+            raise MtrError(f"{what} must be a host array, got a tensor on {a.device}")
+        a = a.detach().numpy()
+    a = np.asarray(a)
+    if a.ndim != 1 or not (np.issubdtype(a.dtype, np.integer) or a.size == 0):
+        raise MtrError(f"{what} must be a 1-D integer array, got shape {a.shape} dtype {a.dtype}")
+    out = np.ascontiguousarray(a, dtype=dtype)
+    if not np.array_equal(out, a):
+        raise MtrError(f"{what} does not fit {np.dtype(dtype).name}")
+    return out
+
+
+def device_input_args(text, offsets, lens, device: int):
+    """The checks of Engine.upload_device, made before the library is called: text a contiguous 1-D torch.uint8 tensor on
+    cuda:device, offsets / lens host integer arrays of one length, every read 1..MAX_READ_LENGTH bytes inside text.
+    Returns (offsets int64, lens int32) as contiguous numpy arrays; raises MtrError."""
+    import torch
+
+    if not isinstance(text, torch.Tensor):
+        raise MtrError(f"text must be a torch.Tensor, got {type(text).__name__}")
+    if text.dtype != torch.uint8:
+        raise MtrError(f"text must have dtype torch.uint8, got {text.dtype}")
+    if text.dim() != 1 or not text.is_contiguous():
+        raise MtrError(f"text must be a contiguous 1-D tensor, got shape {tuple(text.shape)} strides {text.stride()}")
+    offs = _host_ints(offsets, np.int64, "offsets")
+    ln = _host_ints(lens, np.int32, "lens")
+    if len(offs) != len(ln) or len(ln) == 0:
+        raise MtrError(f"offsets ({len(offs)}) and lens ({len(ln)}) must have the same, non-zero length")
+    if (ln <= 0).any() or (ln > MAX_READ_LENGTH).any():
+        i = int(np.argmax((ln <= 0) | (ln > MAX_READ_LENGTH)))
+        raise MtrError(f"read {i}: length {int(ln[i])} outside 1..{MAX_READ_LENGTH}")
+    past = (offs < 0) | (offs > text.numel() - ln.astype(np.int64))
+    if past.any():
+        i = int(np.argmax(past))
+        raise MtrError(f"read {i}: bytes {int(offs[i])} .. +{int(ln[i])} outside the text of {text.numel()} bytes")
+    if text.device.type != "cuda":
+        raise MtrError(f"text must be a GPU tensor, got a tensor on {text.device}")
+    if text.device.index != device:
+        raise MtrError(f"text is on {text.device}, the engine on cuda:{device}")
+    return offs, ln
+
+
 class Engine:
-    """One context per GPU (mtr_create).  manhattan=False is the reference's -p; min_match_ratio its -m."""
+    """One context per GPU (mtr_create).  manhattan=False is the reference's -p; min_match_ratio its -m.
+
+    The device-input methods (upload_device, process_device, export_tensor) use torch: import torch BEFORE the first Engine
+    is created.  torch ships its own HIP runtime under the same soname as the one libmtr_hip.so links, and whichever loads
+    first serves both; loaded second, torch finds no GPU."""
 
     def __init__(self, device: int = 0, manhattan: bool = True, min_match_ratio: float = 0.6):
         self.lib = load_library()
@@ -198,6 +251,7 @@ class Engine:
         if st != 0:
             raise MtrError(f"mtr_create failed: {STATUS.get(st, st)} (a HIP device is required; there is no CPU fallback)")
         self.h = h
+        self.device = device
         self._keep = None
 
     def close(self):
@@ -233,6 +287,44 @@ class Engine:
         self._keep = (bases, offs, lens)
         self._check(self.lib.mtr_upload_batch(self.h, bases.ctypes.data, offs.ctypes.data, lens.ctypes.data, len(lens)), "mtr_upload_batch")
         self.n_reads = len(lens)
+
+    def upload_device(self, text, offsets, lens, codes: bool = False):
+        """mtr_upload_batch_device: reads as text already on the GPU, packed there by a kernel.
+        text: contiguous 1-D torch.uint8 tensor on this engine's device, one byte per base - 'ACGT'/'acgt' (codes=False) or
+        0..3 (codes=True); offsets / lens: host int64 / int32 arrays (numpy or CPU tensors).  The library waits for torch's
+        current stream (where text was written) by an event; text may be reused once this returns."""
+        import torch
+
+        offs, ln = device_input_args(text, offsets, lens, self.device)
+        stream = torch.cuda.current_stream(text.device).cuda_stream
+        self.n_reads = 0
+        self._check(self.lib.mtr_upload_batch_device(self.h, C.c_void_p(text.data_ptr()), text.numel(), offs.ctypes.data, ln.ctypes.data, len(ln),
+                                                     TEXT_CODES if codes else TEXT_ASCII, C.c_void_p(stream)), "mtr_upload_batch_device")
+        self.n_reads = len(ln)
+
+    def process_device(self, text, offsets, lens, codes: bool = False) -> List[List[Record]]:
+        """upload_device + run + fetch: per read its records in insertion order, as process() returns them"""
+        self.upload_device(text, offsets, lens, codes)
+        self.run()
+        return self.fetch()
+
+    def export_tensor(self):
+        """The wire-form record table of the last run (mtr_export_packed_device) in a fresh torch.uint8 tensor on this engine's
+        device, and the records per read: returns (blob, counts int32 CPU tensor)."""
+        import torch
+
+        counts = np.zeros(self.n_reads, np.int32)
+        total, nbytes = C.c_int64(), C.c_int64()
+        st = self.lib.mtr_export_packed_device(self.h, None, 0, counts.ctypes.data, C.byref(total), C.byref(nbytes))   # capacity 0: the size
+        if st not in (0, 5):                                                                                      # (MTR_ERR_OVERFLOW: size known)
+            self._check(st, "mtr_export_packed_device")
+        dev = torch.device("cuda", self.device)
+        blob = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()            # the library writes blob on its own stream: torch's earlier use of the memory is done
+        if nbytes.value:
+            self._check(self.lib.mtr_export_packed_device(self.h, C.c_void_p(blob.data_ptr()), blob.numel(), counts.ctypes.data, C.byref(total),
+                                                          C.byref(nbytes)), "mtr_export_packed_device")
+        return blob[:int(nbytes.value)], torch.from_numpy(counts)
 
     def process_in_file(self, reads: Sequence[np.ndarray], file_state: "FileState") -> List[List[Record]]:
         """the next reads of a file under the reference's whole-file behaviour (include/mtr_hip.h, file-order mode)"""

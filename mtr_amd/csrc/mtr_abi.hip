@@ -30,6 +30,7 @@
 #include "k1_ranges.hip.inc"
 #include "k2_units.hip.inc"
 #include "k3_staged.hip.inc"
+#include "pack.hip.inc"
 
 static_assert(sizeof(DevRecord) == sizeof(mtr_record), "device and ABI record layouts must agree");
 static_assert(MTR_N_COUNTERS == CNT_N, "counter count");
@@ -117,6 +118,8 @@ struct mtr_ctx {
     void *h_counts = nullptr, *h_sizes = nullptr, *h_blob = nullptr; size_t h_counts_cap = 0, h_sizes_cap = 0, h_blob_cap = 0;
     // -a: task buffers of mtr_alignments (grow-only, like the batch buffers)
     int32_t *d_al_i32 = nullptr, *d_al_len = nullptr, *d_al_ends = nullptr; uint8_t *d_al_units = nullptr, *d_al_ops = nullptr; int64_t *d_al_off = nullptr;
+    // device input (mtr_upload_batch_device): per read its text offset, the first read with a byte that is no base, the caller's stream's event
+    int64_t *d_toff = nullptr; int32_t *d_pack_bad = nullptr; hipEvent_t ev_text = nullptr;
     // test entry points
     int32_t *d_t_i32 = nullptr, *d_t_out = nullptr; uint8_t *d_t_units = nullptr;
 };
@@ -261,6 +264,7 @@ static void release_batch_buffers(mtr_ctx *ctx)
     dfree(ctx->d_ovf_records); dfree(ctx->d_rec_base); dfree(ctx->d_ovf_order); dfree(ctx->d_src);
     dfree(ctx->d_item_read); dfree(ctx->d_item_idx); dfree(ctx->d_item_off); ctx->item_cap = 0;
     dfree(ctx->d_tail); dfree(ctx->d_tail_off);
+    dfree(ctx->d_toff); dfree(ctx->d_pack_bad);
     dfree(ctx->d_st_arena); dfree(ctx->d_st_kc); dfree(ctx->d_st_dp); dfree(ctx->d_st_bincnt); dfree(ctx->d_st_dpbin); dfree(ctx->d_st_dprank);
     dfree(ctx->d_st_binstart); dfree(ctx->d_st_sorted); dfree(ctx->d_st_classwave); dfree(ctx->d_st_cand); dfree(ctx->d_st_flag); dfree(ctx->d_st_scalars); dfree(ctx->d_st_wv); dfree(ctx->d_st_res); dfree(ctx->d_st_items); dfree(ctx->d_st_cont); dfree(ctx->d_st_rev);
     dfree(ctx->d_st_ipass); dfree(ctx->d_st_plist0); dfree(ctx->d_st_plist1); dfree(ctx->d_st_re2);
@@ -355,6 +359,7 @@ extern "C" void mtr_destroy(mtr_ctx *ctx)
     dfree(ctx->d_status); dfree(ctx->d_work); dfree(ctx->d_counters); dfree(ctx->d_scratch);
     dfree(ctx->d_trace); dfree(ctx->d_trace_n); dfree(ctx->d_fail_read);
     for (int i = 0; i < 4; i++) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
+    if (ctx->ev_text) (void)hipEventDestroy(ctx->ev_text);
     for (int i = 0; i < MTR_N_PHASE_TIMES; i++) { if (ctx->ev_ph[i]) (void)hipEventDestroy(ctx->ev_ph[i]); if (ctx->ev_ph2[i]) (void)hipEventDestroy(ctx->ev_ph2[i]); }
     for (int i = 0; i < 8; i++) if (ctx->ev_dom[i >> 2][(i >> 1) & 1][i & 1]) (void)hipEventDestroy(ctx->ev_dom[i >> 2][(i >> 1) & 1][i & 1]);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -410,8 +415,10 @@ static int pick_waves(mtr_ctx *ctx, int n_items, int per_cu, size_t per_wave, si
     return (int)waves;
 }
 
+// reads given as text in device memory (mtr_upload_batch_device)
+struct DeviceText { const uint8_t *d; int64_t bytes; int32_t kind; hipStream_t wait; };
 static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t *packed_in, int64_t n_words_in, const int64_t *woff_in,
-                               const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n);
+                               const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n, const DeviceText *dt = nullptr);
 extern "C" mtr_status mtr_upload_batch(mtr_ctx *ctx, const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n)
 {
     if (ctx && (!bases || !offsets)) { ctx->err = "null input"; return MTR_ERR_BAD_ARG; }
@@ -428,8 +435,47 @@ extern "C" mtr_status mtr_upload_batch_packed(mtr_ctx *ctx, const uint32_t *pack
     if (ctx && (!packed || !woff || n_words <= 0)) { ctx->err = "null input"; return MTR_ERR_BAD_ARG; }
     return upload_batch(ctx, nullptr, packed, n_words, woff, nullptr, nullptr, lens, n);
 }
+extern "C" mtr_status mtr_upload_batch_device(mtr_ctx *ctx, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
+                                              const int32_t *lens, int32_t n, int32_t text_kind, void *wait_stream)
+{
+    const DeviceText dt = { d_text, text_bytes, text_kind, (hipStream_t)wait_stream };
+    const mtr_status st = upload_batch(ctx, nullptr, nullptr, 0, nullptr, nullptr, offsets, lens, n, &dt);
+    if (st != MTR_OK && ctx && !ctx->pending) free_batch(ctx);          // a refused device upload leaves no batch behind
+    return st;
+}
+
+// the arguments of a device upload that the host can check (after free_batch: a refused upload leaves no batch behind)
+static mtr_status check_device_text(mtr_ctx *ctx, const DeviceText &dt, const int64_t *offsets, const int32_t *lens, int32_t n)
+{
+    if (!dt.d || !offsets) { ctx->err = "null input"; return MTR_ERR_BAD_ARG; }
+    if (dt.bytes <= 0) { ctx->err = "text_bytes " + std::to_string(dt.bytes) + " <= 0"; return MTR_ERR_BAD_ARG; }
+    if (dt.kind != MTR_TEXT_ASCII && dt.kind != MTR_TEXT_CODES) { ctx->err = "unknown text_kind " + std::to_string(dt.kind); return MTR_ERR_BAD_ARG; }
+    for (int i = 0; i < n; i++)
+        if (offsets[i] < 0 || offsets[i] > dt.bytes - lens[i]) {
+            ctx->err = "read " + std::to_string(i) + ": bytes " + std::to_string(offsets[i]) + " .. +" + std::to_string(lens[i]) + " outside the text of " +
+                       std::to_string(dt.bytes) + " bytes";
+            return MTR_ERR_BAD_ARG;
+        }
+    hipPointerAttribute_t a;
+    const bool dev = hipPointerGetAttributes(&a, dt.d) == hipSuccess && a.type == hipMemoryTypeDevice;
+    (void)hipGetLastError();                                             // (host memory unknown to HIP fails the query: not a sticky error)
+    if (!dev || a.device != ctx->device) {
+        ctx->err = dev ? "d_text is device memory of GPU " + std::to_string(a.device) + ", the context is on GPU " + std::to_string(ctx->device)
+                       : std::string("d_text is not device memory");
+        return MTR_ERR_BAD_ARG;
+    }
+    hipDeviceptr_t base = nullptr; size_t size = 0;                       // the text must lie inside one allocation
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)dt.d) == hipSuccess && base &&
+        (const uint8_t *)dt.d + dt.bytes > (const uint8_t *)base + size) {
+        ctx->err = "text_bytes " + std::to_string(dt.bytes) + " runs past the end of d_text's allocation";
+        return MTR_ERR_BAD_ARG;
+    }
+    (void)hipGetLastError();
+    return MTR_OK;
+}
+
 static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t *packed_in, int64_t n_words_in, const int64_t *woff_in,
-                               const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n)
+                               const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n, const DeviceText *dt)
 {
     if (!ctx) return MTR_ERR_BAD_ARG;
     if (!lens || n <= 0) { ctx->err = "null input or n_reads <= 0"; return MTR_ERR_BAD_ARG; }
@@ -444,6 +490,7 @@ static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t 
         if (lens[i] <= 0 || lens[i] > MTRC_MAX_SUPPORTED_LENGTH) { ctx->err = "read " + std::to_string(i) + ": length " + std::to_string(lens[i]) + " outside 1.." + std::to_string(MTRC_MAX_SUPPORTED_LENGTH); return MTR_ERR_BAD_ARG; }
         Lmax = std::max(Lmax, (int)lens[i]);
     }
+    if (dt) { mtr_status st = check_device_text(ctx, *dt, offsets, lens, n); if (st != MTR_OK) return st; }
     if (packed_in) {
         for (int i = 0; i < n; i++)
             if (woff_in[i] < 0 || woff_in[i] + mtr_packed_words(lens[i]) > n_words_in) { ctx->err = "read " + std::to_string(i) + ": words outside the packed image"; return MTR_ERR_BAD_ARG; }
@@ -451,8 +498,8 @@ static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t 
     } else {
         woff_own.resize((size_t)n);
         for (int i = 0; i < n; i++) { woff_own[(size_t)i] = words; words += mtr_packed_words(lens[i]); }
-        packed_own.assign((size_t)words, 0u);
-        for (int i = 0; i < n; i++)
+        if (!dt) packed_own.assign((size_t)words, 0u);
+        for (int i = 0; i < n && !dt; i++)
             if (mtr_pack_read(bases + offsets[i], lens[i], packed_own.data() + woff_own[(size_t)i]) != MTR_OK) { ctx->err = "read " + std::to_string(i) + ": base code > 3"; return MTR_ERR_BAD_ARG; }
         woff = woff_own.data(); packed = packed_own.data();
     }
@@ -493,11 +540,28 @@ static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t 
     HIPCHK(ensure_dev(ctx, ctx->d_recoff, ((size_t)n + 1) * 8));
     HIPCHK(ensure_dev(ctx, ctx->d_item_off, ((size_t)n + 1) * 8));
     DBG("upload_batch: batch buffers ready");
-    HIPCHK(hipMemcpyAsync(ctx->d_packed, packed, (size_t)words * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (!dt) HIPCHK(hipMemcpyAsync(ctx->d_packed, packed, (size_t)words * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_packed + words, 0, 80 * 4, ctx->stream));
     ctx->packed_words = (long long)words + 80;
     HIPCHK(hipMemcpyAsync(ctx->d_woff, woff, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_lens, lens, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    int32_t first_bad = n;
+    if (dt) {   // the text comes from the caller's stream: the packing kernel waits for it there, not for the whole device
+        if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
+        HIPCHK(ensure_dev(ctx, ctx->d_toff, (size_t)n * 8)); HIPCHK(ensure_dev(ctx, ctx->d_pack_bad, 4));
+        HIPCHK(hipMemcpyAsync(ctx->d_toff, offsets, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemsetAsync(ctx->d_pack_bad, 0x7f, 4, ctx->stream));
+        HIPCHK(hipEventRecord(ctx->ev_text, dt->wait));
+        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
+        const int64_t blocks = std::min<int64_t>((words + MTR_PACK_BLOCK - 1) / MTR_PACK_BLOCK, (int64_t)ctx->n_cu * 8);
+        if (dt->kind == MTR_TEXT_ASCII)
+            hipLaunchKernelGGL(mtr_k_pack_text<true>, dim3((unsigned)blocks), dim3(MTR_PACK_BLOCK), 0, ctx->stream, dt->d, ctx->d_toff, ctx->d_lens,
+                               ctx->d_woff, n, words, ctx->d_packed, ctx->d_pack_bad);
+        else
+            hipLaunchKernelGGL(mtr_k_pack_text<false>, dim3((unsigned)blocks), dim3(MTR_PACK_BLOCK), 0, ctx->stream, dt->d, ctx->d_toff, ctx->d_lens,
+                               ctx->d_woff, n, words, ctx->d_packed, ctx->d_pack_bad);
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(hipMemcpyAsync(ctx->d_order, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_roff, ctx->roff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     if (fs) {
@@ -505,8 +569,19 @@ static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t 
         if (!tail.empty()) HIPCHK(hipMemcpyAsync(ctx->d_tail, tail.data(), tail.size() * 2, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(ctx->d_tail_off, tail_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     }
+    if (dt) {   // (enqueued last, right before the synchronise: no early return leaves this copy pending)
+        hipError_t e = hipMemcpyAsync(&first_bad, ctx->d_pack_bad, 4, hipMemcpyDeviceToHost, ctx->stream);
+        hipError_t e2 = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) { ctx->err = std::string("device upload: ") + hipGetErrorString(e); return MTR_ERR_HIP; }
+    }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     DBG("upload_batch: copies done");
+    if (first_bad < n) {
+        free_batch(ctx);
+        ctx->err = "read " + std::to_string(first_bad) + (dt->kind == MTR_TEXT_ASCII ? ": a byte that is not A, C, G, T, a, c, g or t" : ": base code > 3");
+        return MTR_ERR_BAD_ARG;
+    }
     return MTR_OK;
 }
 

@@ -3,6 +3,8 @@ a stand-in for libmtr_hip.so that answers with the reference's recorded records)
 golden G4 captures.  Test infrastructure only."""
 from __future__ import annotations
 
+import hashlib
+import json
 import os
 import struct
 import subprocess
@@ -94,6 +96,78 @@ def wire_record(t) -> bytes:
     assert len(unit) == per and len(score) >= per, (per, len(unit), len(score))
     head = struct.pack("<14i", *t[:13], 0)
     return head + unit.encode() + b"\0" * ((-per) % 4) + struct.pack(f"<{per}i", *score[:per])
+
+
+def wire_split(blob: bytes, counts) -> list:
+    """a record table in the wire form (read after read) -> per read its bytes; counts = records per read"""
+    out, p = [], 0
+    for c in counts:
+        q = p
+        for _ in range(int(c)):
+            per = struct.unpack_from("<i", blob, q + 12)[0]
+            if not 0 <= per <= 500:
+                raise ValueError(f"record at byte {q}: rep_period {per}")
+            q += 56 + ((per + 3) & ~3) + 4 * per
+        out.append(blob[p:q])
+        p = q
+    if p != len(blob):
+        raise ValueError(f"{len(blob)} bytes, the counts describe {p}")
+    return out
+
+
+def wire_tuples(b: bytes) -> list:
+    """one read's records in the wire form -> tuples in tests.golden_util.g4_tuple order (the inverse of wire_record)"""
+    out, p = [], 0
+    while p < len(b):
+        head = struct.unpack_from("<13i", b, p)
+        per = head[3]
+        p += 56
+        unit = b[p:p + per].decode(errors="replace")
+        p += (per + 3) & ~3
+        out.append(head + (unit, struct.unpack_from(f"<{per}i", b, p)))
+        p += 4 * per
+    return out
+
+
+def load_known(name: str) -> dict:
+    with open(os.path.join(gu.GOLDEN, name)) as fh:
+        return json.load(fh)
+
+
+def known_wire_mismatch(blob: bytes, counts, reads, known: dict, diff_msg, manhattan: bool = True):
+    """None when `blob` (the wire form of the records of `reads`, read after read in input order) is the known answer `known`
+    (tests/golden/make_c4_wire_hash.py); otherwise a message.  On a mismatch the known answer's chunk_sha256 names the first bad
+    chunk, the CPU oracle runs on that chunk alone, and diff_msg(i, want, got) describes its first differing read."""
+    n = len(reads)
+    if len(counts) != n or known["n_reads"] != n:
+        return f"{len(counts)} reads fetched, {n} uploaded, the known answer has {known['n_reads']}"
+    if hashlib.sha256(blob).hexdigest() == known["sha256"]:
+        if len(blob) != known["wire_bytes"] or int(np.sum(counts)) != known["records"]:
+            return f"sha256 matches but {len(blob)} bytes / {int(np.sum(counts))} records against {known['wire_bytes']} / {known['records']}"
+        return None
+    head = (f"record stream differs from the known answer: {int(np.sum(counts))} records / {len(blob)} bytes, "
+            f"want {known['records']} / {known['wire_bytes']}")
+    try:
+        per_read = wire_split(blob, counts)
+    except (ValueError, struct.error) as e:
+        return f"{head}; the stream does not parse: {e}"
+    step = known["chunk_reads"]
+    for k, want_h in enumerate(known["chunk_sha256"]):
+        lo, hi = k * step, min(n, (k + 1) * step)
+        if hashlib.sha256(b"".join(per_read[lo:hi])).hexdigest() != want_h:
+            break
+    else:
+        return f"{head}; yet every chunk matches (inconsistent known answer?)"
+    from tests.oracle_binding import Oracle
+    orc = Oracle(manhattan=manhattan)
+    try:
+        for i in range(lo, hi):
+            want = orc.process(reads[i])
+            if b"".join(wire_record(r) for r in want) != per_read[i]:
+                return f"{head}; first bad chunk {k} (reads {lo}..{hi - 1}), " + diff_msg(i, want, wire_tuples(per_read[i]))
+    finally:
+        orc.close()
+    return f"{head}; chunk {k} (reads {lo}..{hi - 1}) differs but the oracle agrees with each of its reads"
 
 
 def write_table(path, cases):

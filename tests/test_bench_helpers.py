@@ -24,13 +24,100 @@ def test_committed_profiles_belong_to_their_workloads():
 
 
 def test_known_answers_of_the_command_line_legs_exist():
-    for f in ("c2_1000_stdout.json", "c4_100000_stdout.json", "c2_1000_wire.json", "c3_100_wire.json", "c4_100k_wire.json"):
+    for f in ("c2_1000_stdout.json", "c4_100000_stdout.json", "c2_1000_wire.json", "c3_100_wire.json", "c4_100k_wire.json",
+              "headline2k_10000_wire.json", "headline2k_10000_p_wire.json", "headline2k_10000_stdout.json", "headline2k_10000_p_stdout.json",
+              "c4_10000_stdout.json"):
         with open(os.path.join(gu.GOLDEN, f)) as fh:
             k = json.load(fh)
         assert len(k["sha256"]) == 64
     assert len(bench.C5_FILES) == 15
     for n in bench.C5_FILES:
         assert os.path.exists(gu.input_path(n)) and os.path.exists(os.path.join(gu.GOLDEN, f"{n}.p.stdout"))
+
+
+def _known_answers_with_inputs():
+    out = []
+    for f in sorted(os.listdir(gu.GOLDEN)):
+        if f.endswith(("_wire.json", "_stdout.json")):
+            with open(os.path.join(gu.GOLDEN, f)) as fh:
+                k = json.load(fh)
+            if "input_sha256" in k:
+                out.append((f, k))
+    return out
+
+
+def test_known_answers_still_describe_the_reads_synth_makes():
+    """A known answer is the answer for the reads mtr_amd.synth made when it was written: regenerate the inputs of every fixture that
+    records their hash (input_sha256 = sha256 of the concatenated base codes) and check it - a change to synth must come with new fixtures."""
+    import hashlib
+
+    from mtr_amd import synth
+    known = _known_answers_with_inputs()
+    names = {f for f, _ in known}
+    assert {"headline2k_10000_wire.json", "headline2k_10000_p_wire.json", "headline2k_10000_stdout.json", "headline2k_10000_p_stdout.json",
+            "c4_10000_stdout.json"} <= names, names
+    made = {}
+    for f, k in known:
+        key = (k["config"], k["n_reads"], k["seed"])
+        if key not in made:
+            reads = synth.make_reads(*key)
+            h = hashlib.sha256()
+            for _, codes in reads:
+                h.update(codes.astype("uint8").tobytes())
+            made[key] = (h.hexdigest(), sum(len(c) for _, c in reads))
+        assert k["seed"] == synth.CONFIGS[k["config"]][4], f
+        assert made[key][0] == k["input_sha256"], f"{f}: mtr_amd.synth no longer makes the reads this known answer describes"
+        if "sum_len" in k:
+            assert made[key][1] == k["sum_len"], f
+        if "chunk_sha256" in k:
+            assert len(k["chunk_sha256"]) == -(-k["n_reads"] // k["chunk_reads"]), f
+
+
+def test_headline_known_answers_agree_with_the_oracle_on_their_first_chunk():
+    """the first chunk_sha256 of each headline wire fixture is the CPU oracle's wire form of reads 0..499 as it stands (the whole fixture takes
+    ~130 core-seconds; tests/golden/make_c4_wire_hash.py)"""
+    import hashlib
+
+    from mtr_amd import synth
+    from tests.host_util import load_known, wire_record
+    from tests.oracle_binding import Oracle
+    reads = [c for _, c in synth.make_reads("headline2k", 500, 2)]
+    for name, manhattan in (("headline2k_10000_wire.json", True), ("headline2k_10000_p_wire.json", False)):
+        k = load_known(name)
+        orc = Oracle(manhattan=manhattan)
+        blob = b"".join(wire_record(r) for c in reads for r in orc.process(c))
+        orc.close()
+        assert k["chunk_reads"] == 500 and hashlib.sha256(blob).hexdigest() == k["chunk_sha256"][0], name
+
+
+def test_known_wire_mismatch_names_the_first_bad_chunk_and_read():
+    """the GPU tests' diagnosis of a failing whole-stream comparison (tests/host_util.known_wire_mismatch), on oracle records with one
+    field of one read changed"""
+    import hashlib
+
+    from mtr_amd import synth
+    from tests import host_util as hu
+    from tests.oracle_binding import Oracle
+    reads = [c for _, c in synth.make_reads("c2", 40, 5)]
+    orc = Oracle()
+    recs = [orc.process(c) for c in reads]
+    orc.close()
+    per_read = [b"".join(hu.wire_record(r) for r in rs) for rs in recs]
+    assert [hu.wire_tuples(b) for b in per_read] == recs
+    counts = [len(rs) for rs in recs]
+    blob = b"".join(per_read)
+    assert hu.wire_split(blob, counts) == per_read
+    known = {"n_reads": 40, "records": sum(counts), "wire_bytes": len(blob), "sha256": hashlib.sha256(blob).hexdigest(), "chunk_reads": 10,
+             "chunk_sha256": [hashlib.sha256(b"".join(per_read[i:i + 10])).hexdigest() for i in range(0, 40, 10)]}
+    msg = lambda i, want, got: f"read {i}: {want == got}"          # noqa: E731
+    assert hu.known_wire_mismatch(blob, counts, reads, known, msg) is None
+    bad = next(i for i in range(23, 40) if counts[i])
+    rec = list(recs[bad][0])
+    rec[6] += 1                                                     # num_mismatches
+    blob2 = b"".join(per_read[:bad]) + hu.wire_record(rec) + per_read[bad][len(hu.wire_record(rec)):] + b"".join(per_read[bad + 1:])
+    got = hu.known_wire_mismatch(blob2, counts, reads, known, msg)
+    assert got is not None and f"first bad chunk {bad // 10} " in got and got.endswith(f"read {bad}: False"), got
+    assert "does not parse" in hu.known_wire_mismatch(blob[:-4], counts, reads, known, msg)
 
 
 def _wire_of_golden_records(name="synth_c2", mode="default"):

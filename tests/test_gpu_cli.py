@@ -133,3 +133,44 @@ def test_cli_reports_the_engine_library_it_bound(cli):
     assert "Computation time" in err
     line = [ln for ln in err.splitlines() if ln.endswith("engine library")]
     assert len(line) == 1 and os.path.realpath(line[0].split("\t")[0]) == os.path.realpath(os.path.join(ROOT, "mtr_amd", "libmtr_hip.so")), err
+
+
+# ---- whole BASELINE configs against the known answers of the command line (tests/golden/make_stdout_hash.py) -------------------------
+KNOWN_RUNS = [("c2", 1000, False), ("c4", 100000, False), ("headline2k", 10000, False), ("headline2k", 10000, True)]
+
+
+@pytest.fixture(scope="module")
+def config_fastas(tmp_path_factory):
+    """the FASTAs exactly as bench.py writes them: synth.write_fasta(fa, synth.make_reads(cfg, n, seed of the config)) (IDs = read index);
+    made once - the 100 000 config-4 reads take ~20 s"""
+    from mtr_amd import synth
+    d = tmp_path_factory.mktemp("configs")
+    out = {}
+    for cfg, n in sorted({(c, n) for c, n, _ in KNOWN_RUNS}):
+        fa = str(d / f"{cfg}_{n}.fa")
+        synth.write_fasta(fa, synth.make_reads(cfg, n, synth.CONFIGS[cfg][4]))
+        out[(cfg, n)] = fa
+    return out
+
+
+def _visible_gpus():
+    import torch
+    return torch.cuda.device_count()
+
+
+@pytest.mark.timeout(1800)
+@pytest.mark.parametrize("cfg,n,pearson", KNOWN_RUNS, ids=[f"{c}_{n}{'_p' if p else ''}" for c, n, p in KNOWN_RUNS])
+def test_cli_whole_configs_match_their_known_answers(cli, config_fastas, cfg, n, pearson):
+    """mTR and mTR -g <visible GPUs> on whole BASELINE configs: stdout's sha256 and line count are the CPU oracle's command line's on the same
+    FASTA (tests/golden/<cfg>_<n>[_p]_stdout.json; the oracle prints what the reference prints run one read per process)"""
+    import hashlib
+    from tests import host_util as hu
+    known = hu.load_known(f"{cfg}_{n}{'_p' if pearson else ''}_stdout.json")
+    assert known["n_reads"] == n and known["pearson"] == pearson
+    env = {k: v for k, v in os.environ.items() if k not in ("MTR_LIB", "MTR_REPLAY_TABLE", "RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    flags = ["-p"] if pearson else []
+    for extra in ([], ["-g", str(_visible_gpus())]):
+        p = subprocess.run([cli, *flags, *extra, config_fastas[(cfg, n)]], capture_output=True, env=env, timeout=900)
+        assert p.returncode == 0, (extra, p.stderr.decode()[-800:])
+        got = (hashlib.sha256(p.stdout).hexdigest(), p.stdout.count(b"\n"), len(p.stdout))
+        assert got == (known["sha256"], known["stdout_lines"], known["stdout_bytes"]), (extra, got)

@@ -93,6 +93,20 @@ def test_headline_shaped_reads(eng, kw):
     assert sum(len(w) for w in want) > 2000
 
 
+@pytest.mark.timeout(900)
+def test_full_size_headline_batch_matches_the_known_answer(eng):
+    """The whole headline batch (10 000 reads, 20.5 M bases) as ASCII text in a torch tensor: the packing kernel's image feeds the
+    default selection at full size, and the record stream is the CPU oracle's (tests/golden/headline2k_10000_wire.json)"""
+    from tests import host_util as hu
+    from tests.test_gpu_parity import _diff_msg
+    reads = [c for _, c in synth.make_reads("headline2k", 10000, synth.CONFIGS["headline2k"][4])]
+    got, (blob, counts) = _device(eng, reads)
+    assert eng.last_mode() == "staged chain" and eng.counters()["reads_sent_back"] == 0
+    assert counts.tolist() == [len(g) for g in got]
+    bad = hu.known_wire_mismatch(blob, counts, reads, hu.load_known("headline2k_10000_wire.json"), _diff_msg)
+    assert bad is None, bad
+
+
 def test_config3_shaped_reads(eng):
     reads = [c for _, c in synth.make_reads("c3", 3)]
     _same(eng, reads, lower=1.0, junk=True, seed=5)

@@ -201,16 +201,21 @@ def test_c_host_over_gpus_alignments_file_order_and_a_failing_read(tmp_path):
 
 @pytest.mark.timeout(1800)
 def test_c_host_rccl_config4_ten_thousand_reads_against_the_oracles_hash(tmp_path):
-    """10 000 config-4 reads through mTR -g <GPUs> with the RCCL gather: the record stream is not visible on stdout, so the check is the report itself -
-    identical to the single-GPU command line's (whose records are checked read by read elsewhere) - plus several rounds of real size (3 MB each)"""
+    """10 000 config-4 reads (seed 4) through mTR -g <GPUs> with the RCCL gather: the report is the CPU oracle's command line's on the same FASTA
+    (tests/golden/c4_10000_stdout.json: sha256 and line count), identical to the single-GPU command line's, over several rounds of real size (3 MB each)"""
+    import hashlib
+
     import torch
+    from tests import host_util as hu
     n = torch.cuda.device_count()
+    known = hu.load_known("c4_10000_stdout.json")
     fa = tmp_path / "c4_10k.fa"
-    synth.write_fasta(str(fa), [(str(i), c) for i, c in enumerate(c for _, c in synth.make_reads("c4", 10000, 44))])
+    synth.write_fasta(str(fa), synth.make_reads("c4", 10000, 4))
     one = _mtr_g([str(fa)])
     assert one.returncode == 0 and one.stdout.count(b"\n") > 10000
     p = _mtr_g(["-c", "-g", str(n), str(fa)], {"MTR_GATHER": "rccl", "MTR_GATHER_SELF": "1", "MTR_CHUNK_BYTES": str(4 << 20)})
     assert p.returncode == 0, p.stderr.decode()[-800:]
+    assert (hashlib.sha256(p.stdout).hexdigest(), p.stdout.count(b"\n")) == (known["sha256"], known["stdout_lines"])
     assert p.stdout == one.stdout
     line = _gather_line(p)
     assert "gather rccl" in line and int(line.split(" exchange")[0].split()[-1]) >= 4 // n and "+ 0 straight to the host" in line, line

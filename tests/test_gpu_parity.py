@@ -1,6 +1,6 @@
 """Parity of the HIP path (through the C-ABI of include/mtr_hip.h) — run on the MI355X box with -m gpu.
 
-Three kinds of evidence:
+Four kinds of evidence:
   1. against the golden vectors recorded from the unmodified reference (tests/golden): candidate ranges
      (G1), wrap-around DP calls (G3) and the inserted records (G4 = the 17 arguments of
      insert_an_alignment_into_set), in Manhattan and Pearson (-p) mode — bit-exact;
@@ -9,6 +9,8 @@ Three kinds of evidence:
   3. at BASELINE.json's full size (10 000 reads of ~2 kb) through size-independent properties: batch
      independence (a read's records do not depend on which reads share its batch, nor on their order),
      run-to-run determinism, and a random sample against the oracle.
+  4. at that full size, the whole record stream against the CPU oracle's known answer (tests/golden/headline2k_10000*_wire.json)
+     in every arrangement of the kernels, with three contexts in flight, and in Pearson mode.
 """
 import os
 import subprocess
@@ -19,6 +21,7 @@ import pytest
 import mtr_amd
 from mtr_amd import synth
 from tests import golden_util as gu
+from tests import host_util as hu
 
 pytestmark = pytest.mark.gpu
 
@@ -164,12 +167,18 @@ def test_mixed_length_batch(eng, oracle):
 
 
 # ---- 3. full size: properties -----------------------------------------------------------------------------------
+@pytest.mark.timeout(900)
 def test_full_size_batch_independence_and_sample(eng, oracle):
     reads = [c for _, c in synth.make_reads("headline2k", 10000, 2)]
     eng.upload(reads)
     eng.run()
     full = eng.fetch()
     cnt = eng.counters()
+    # the whole record stream of the first run is the CPU oracle's (tests/golden/headline2k_10000_wire.json)
+    data, counts = eng.fetch_packed()
+    assert counts.tolist() == [len(r) for r in full]
+    bad = hu.known_wire_mismatch(data, counts, reads, hu.load_known("headline2k_10000_wire.json"), _diff_msg)
+    assert bad is None, bad
     assert cnt["records"] == sum(len(r) for r in full)
     # the DEFAULT selection for a batch of 20 M bases (no MTR_* override in this test): the chain in two passes with every wide range first
     # (k3_staged.hip.inc: mtr_k_pass_mark).  The mark pass's list of ranges is not provably a superset of what the reference's loop reaches; a miss
@@ -202,6 +211,92 @@ def test_full_size_batch_independence_and_sample(eng, oracle):
             assert np.float32(r.num_matches) / np.float32(tot) >= np.float32(0.6)
             assert r.num_freq_unit > 5 and 2 <= r.rep_period < 500 and len(r.unit) == r.rep_period
             assert r.repeat_len == r.num_matches + r.num_mismatches + r.num_insertions
+
+
+# ---- 4. full size: the whole stream against the known answer -----------------------------------------------------------
+@pytest.fixture(scope="module")
+def headline():
+    """the bench's headline batch: 10 000 reads of ~2 kb, 20.5 M bases (synth config headline2k, seed 2)"""
+    return [c for _, c in synth.make_reads("headline2k", 10000, synth.CONFIGS["headline2k"][4])]
+
+
+MODE_VARS = ("MTR_STAGED", "MTR_QUAD_MIN", "MTR_TWO_PASS", "MTR_TEST_STAGED_CAPS", "MTR_TEST_STAGED_FLAGS")
+# at 20.5 M bases the default selection is the chain with every wide range in the first pass (MTR_TWO_PASS=2) and the alignments of units of
+# up to 128 bases four per wavefront (MTR_QUAD_MIN=1024 alignments); each arrangement below moves one of those off its default
+FULL_SIZE_ARRANGEMENTS = {"default": {}, "one_pass": {"MTR_TWO_PASS": "0"}, "two_pass_uncontained_wide_first": {"MTR_TWO_PASS": "1"},
+                          "no_quads": {"MTR_QUAD_MIN": "0"}, "per_read": {"MTR_STAGED": "0"}}
+
+
+def _clear_mode_vars(monkeypatch):
+    for k in MODE_VARS:
+        monkeypatch.delenv(k, raising=False)
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("arrangement", list(FULL_SIZE_ARRANGEMENTS))
+def test_full_size_batch_every_arrangement_matches_the_known_answer(monkeypatch, headline, arrangement):
+    """The headline batch, read by read through its sha256 (tests/golden/headline2k_10000_wire.json), in the library's default selection
+    and with each of its choices forced the other way: the paths the 80-read mode tests force run here at the size that selects them -
+    2.44 rounds of 4 096 wavefront slots in the range kernel, the work lists split into sub-lists."""
+    _clear_mode_vars(monkeypatch)
+    for k, v in FULL_SIZE_ARRANGEMENTS[arrangement].items():
+        monkeypatch.setenv(k, v)
+    e = mtr_amd.Engine()
+    try:
+        e.upload(headline)
+        e.run()
+        cnt = e.counters()
+        if arrangement == "per_read":
+            assert e.last_mode() == "per-read kernel"
+        else:
+            assert e.last_mode() == "staged chain"
+            assert cnt["reads_sent_back"] == 0, cnt["reads_sent_back"]
+        data, counts = e.fetch_packed()
+        assert int(counts.sum()) == cnt["records"]
+        bad = hu.known_wire_mismatch(data, counts, headline, hu.load_known("headline2k_10000_wire.json"), _diff_msg)
+        assert bad is None, f"[{arrangement}] {bad}"
+    finally:
+        e.close()
+
+
+@pytest.mark.timeout(900)
+def test_full_size_batch_three_contexts_in_flight(monkeypatch, headline):
+    """As the bench runs the headline: three contexts hold the batch, all three launches are enqueued before the first is waited for.
+    Every context's stream is the known answer."""
+    _clear_mode_vars(monkeypatch)
+    known = hu.load_known("headline2k_10000_wire.json")
+    engines = [mtr_amd.Engine() for _ in range(3)]
+    try:
+        for e in engines:
+            e.upload(headline)
+        for e in engines:
+            e.run_async()
+        for e in engines:
+            e.wait()
+        for k, e in enumerate(engines):
+            assert e.last_mode() == "staged chain" and e.counters()["reads_sent_back"] == 0, k
+            data, counts = e.fetch_packed()
+            bad = hu.known_wire_mismatch(data, counts, headline, known, _diff_msg)
+            assert bad is None, f"context {k}: {bad}"
+    finally:
+        for e in engines:
+            e.close()
+
+
+@pytest.mark.timeout(900)
+def test_full_size_batch_pearson_matches_the_known_answer(monkeypatch, headline):
+    """-p (Pearson distance) on the headline batch in the default selection: tests/golden/headline2k_10000_p_wire.json"""
+    _clear_mode_vars(monkeypatch)
+    e = mtr_amd.Engine(manhattan=False)
+    try:
+        e.upload(headline)
+        e.run()
+        assert e.last_mode() == "staged chain" and e.counters()["reads_sent_back"] == 0
+        data, counts = e.fetch_packed()
+        bad = hu.known_wire_mismatch(data, counts, headline, hu.load_known("headline2k_10000_p_wire.json"), _diff_msg, manhattan=False)
+        assert bad is None, bad
+    finally:
+        e.close()
 
 
 # ---- error behaviour of the boundary -------------------------------------------------------------------------------

@@ -3,6 +3,11 @@
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
   python bench.py --gpus N --strong c4 ...               (strong scaling: ONE set of 100 000 config-4 reads split over the ranks)
+  python bench.py ... --full                             (also every other leg and check below: roofline, value_kernel, CPU baseline, command line, other configs)
+
+A run without --full does what its headline figure needs and nothing else: it makes the reads, sets up the contexts (each runs once), runs the warm-up and
+the timed steps, writes --dump-outputs and prints the line - value, ms_per_step, the kernel times of the warm-up and timed launches, the counters of the last
+launch and chain_health.  Everything else in this docstring is measured or checked with --full only.
 
 A "step" is one pass of the hot path over one batch of synthetic reads that is already resident in HBM (2 bit/base):
 the per-read kernels (candidate ranges, unit search, wrap-around DPs, revision; mtr_run_resident) AND the hand-over at
@@ -25,7 +30,7 @@ wire-form tables go device-to-device to rank 0 over RCCL (mtr_export_packed_devi
 config 4 — one set of 100 000 mixed-unit reads, contiguous blocks balanced by sum of lengths; rank 0 checks the sha256 of
 the gathered stream against the known answer of the CPU oracle (tests/golden/c4_100k_wire.json) and reports ranks_seen.
 
-Round 6: every BASELINE config is in the default line, each with its own evidence - `secondary.c2` / `secondary.c3` (configs 2 and 3 as resident-batch steps in child
+With --full every BASELINE config is in the line (round 6), each with its own evidence - `secondary.c2` / `secondary.c3` (configs 2 and 3 as resident-batch steps in child
 processes, record streams against the oracle's known answers), `baseline_configs_cli` (configs 2, 4 and 5 as jobs of `mTR -c -g N`, fresh child processes, stdout
 against committed known answers), `host_ceiling` (the host pipeline alone behind eight null GPUs), `cpu_baseline.ms_per_read_p50` (the reference, one read per
 process); `roofline.issue` by the lone launch and by the step, `roofline.slot_time` = wavefront-slot time per kernel, `roofline.traffic` - all three from the
@@ -451,6 +456,77 @@ def dump_outputs(out_dir, blobs, records, counts=None, cap_bytes=DUMP_CAP_BYTES)
             "sampled": None if keep is None else ("reads" if counts is not None else "records")}
 
 
+def roofline_of(reads, cnt, ref_cnt, k2_ms, sync_k2, step_s, config):
+    """--full: the roofline object of the line (the module's docstring) from what the run measured anyway - the HIP-event times of the warm-up and timed
+    launches, the counters of the last launch and of the per-read kernel's launch (the reference's work) - and the committed PMC profile of the workload"""
+    # algorithmic bytes of one launch (this rank's batch): the reference's DP cells = computed + answered from the memo
+    sumL4 = sum((len(r) + 3) // 4 for r in reads)
+    cells = ref_cnt["dp_cells"] + ref_cnt["revise_dp_cells"] + ref_cnt["memo_cells"]
+    b_alg = sumL4 + 576 * ref_cnt["records"] + (cells + 1) // 2
+    k2_avg_s = float(np.mean([k["k2_units"] for k in k2_ms])) / 1e3
+    achieved_gbs = b_alg / k2_avg_s / 1e9
+    valu_ops = cells * OPS_PER_CELL / k2_avg_s
+    prof, prof_tag = profiled_counters(config)
+    traffic = prof.get("k2_hbm_bytes_per_launch_fetch_x2") if prof else None
+    valu_insts = prof.get("SQ_INSTS_VALU_per_launch") if prof else None
+    # ---- roofline of the DOMINANT kernel (mtr_k_revise_quads: four revisions per wavefront), by its own duration: HIP events around its launches
+    # on the launch stream (mtr_get_kernel_times id 8), (i) in the warm-up launches, which have the GPU to themselves - the figure
+    # `rocprofv3 --kernel-trace --stats` of a lone launch reproduces (profiles/) and the one `frac` uses -, (ii) in the pipelined timed region,
+    # where a launch shares the chip with its neighbour (reported, not used).  Its algorithmic work: the cells (rows x unit) of the vote DPs and
+    # re-alignments it ran (no padding: what a pass computes beyond them shows as bytes per cell in quad_passes) x 7 integer operations
+    def kavg(ks, name):
+        v = [k[name] for k in ks if name in k]
+        return float(np.mean(v)) if v else None
+    dom = "mtr_k_revise_quads"
+    dom_lone_ms, dom_timed_ms = kavg(sync_k2, "kernel_" + dom), kavg(k2_ms, "kernel_" + dom)
+    dp2_lone_ms = kavg(sync_k2, "kernel_mtr_k_dp2_quads")
+    dom_cells = cnt["qpass_cells_rev"]
+    launch_lone_s = (float(np.mean([k["k2_units"] for k in sync_k2])) / 1e3) if sync_k2 else None
+    computed_cells = cnt["dp_cells"] + cnt["revise_dp_cells"]
+    if dom_lone_ms or dom_timed_ms:
+        dms = dom_lone_ms or dom_timed_ms
+        dom_ops = dom_cells * OPS_PER_CELL / (dms / 1e3)
+        roofline = {"bound": "valu-issue", "kernel": dom,
+                    "achieved": dom_ops / 1e12, "peak": VALU_PEAK_LANE_OPS / 1e12, "unit": "T lane-op/s", "frac": dom_ops / VALU_PEAK_LANE_OPS,
+                    "duration_ms": dms, "duration_source": ("HIP events around the kernel's launches, warm-up launches that have the GPU to themselves" if dom_lone_ms
+                                                            else "HIP events around the kernel's launches in the timed region (no warm-up launch ran)"),
+                    "duration_ms_in_timed_region": dom_timed_ms,
+                    "cells_per_launch": dom_cells, "ops_per_cell": OPS_PER_CELL,
+                    "frac_definition": "rounds 5-6: the dominant kernel's own cells x 7 / its lone duration / VALU peak (VERDICT r4's definition); the whole-launch "
+                                       "figure that rounds 1-4 called frac is whole_launch.frac_lone_launch / frac_by_step (ADVICE r5: not comparable across that change)",
+                    "cells_note": "cells (rows x unit) of the vote DPs and re-alignments the kernel ran in its passes of up to eight DPs per wavefront"}
+    else:       # a batch whose chain runs one DP per wavefront (small batches) or the per-read kernel: no kernel of its own to name - the launch
+        roofline = {"bound": "valu-issue", "kernel": "one launch (the chain ran one DP per wavefront: no dominant several-DPs-per-wavefront kernel)",
+                    "achieved": valu_ops / 1e12, "peak": VALU_PEAK_LANE_OPS / 1e12, "unit": "T lane-op/s", "frac": valu_ops / VALU_PEAK_LANE_OPS,
+                    "duration_ms": k2_avg_s * 1e3, "cells_per_launch": cells, "ops_per_cell": OPS_PER_CELL}
+    roofline.update({
+        "second_kernel": ({"kernel": "mtr_k_dp2_quads", "duration_ms": dp2_lone_ms, "cell_pairs_per_launch": cnt["qpass_cells_dp2"],
+                           "frac": 2 * cnt["qpass_cells_dp2"] * OPS_PER_CELL / (dp2_lone_ms / 1e3) / VALU_PEAK_LANE_OPS,
+                           "note": "two-parameter alignments: a cell pair = the cell of both parameter sets, 2 x 7 operations"} if dp2_lone_ms else None),
+        "whole_launch": {"kernel": "the staged chain (mtr_k1_ranges; per pass mtr_k_walks, mtr_k_walks_k, mtr_k_gather, mtr_k_dp2_quads, mtr_k_select, mtr_k_polish, "
+                                   "mtr_k_rev_share, mtr_k_revise_quads, mtr_k_finish; mtr_k_pass_mark between the passes; mtr_k_replay)",
+                         "cells_reference": cells, "cells_computed": computed_cells,
+                         "frac_by_step": cells * OPS_PER_CELL / step_s / VALU_PEAK_LANE_OPS,
+                         "frac_lone_launch": (cells * OPS_PER_CELL / launch_lone_s / VALU_PEAK_LANE_OPS) if launch_lone_s else None,
+                         "frac_computed_cells": computed_cells * OPS_PER_CELL / step_s / VALU_PEAK_LANE_OPS,
+                         "note": "cells_reference = the reference's DP cells of the launch (memo_cells of them answered without a DP); by the host-visible step, by a "
+                                 "launch that has the GPU to itself, and the cells the kernels computed by the step"},
+        "issue": ({"by_lone_launch": (valu_insts * 2 / (1024 * launch_lone_s * 2.4e9)) if launch_lone_s else None,
+                   "by_step": valu_insts * 2 / (1024 * step_s * 2.4e9),
+                   "SQ_INSTS_VALU_per_launch": valu_insts,
+                   "note": "VALU issue utilisation = SQ_INSTS_VALU of one launch (committed PMC pass of THIS workload) x 2 cycles / (1 024 SIMDs x duration x 2.4 GHz), by the "
+                           "duration of a launch that has the GPU to itself and by the host-visible step - not by the profiler's serialised launches (round 5's 0.170)"}
+                  if valu_insts else None),
+        "slot_time": slot_time(prof),
+        "hbm": {"achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved_gbs / HBM_PEAK_GBS,
+                "frac_by_step": b_alg / step_s / 1e9 / HBM_PEAK_GBS,
+                "algorithmic_bytes_per_launch": b_alg, "spilled": "every DP of the reference is counted as spilled (SURVEY.md 8d's upper figure)"},
+        "traffic": traffic, "traffic_source": prof_tag,
+        "note": "bound by VALU instruction issue: row-serial integer max-plus recurrence; issue, slot_time and traffic (HBM bytes per launch of the whole chain, "
+                "FETCH_SIZE x 2 + WRITE_SIZE, separate PMC passes) come from the committed profile of THIS workload and are null without one"})
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -459,12 +535,14 @@ def main():
     ap.add_argument("--reads", type=int, default=READS_PER_GPU, help="reads per GPU (default = the headline workload)")
     ap.add_argument("--strong", default=None, choices=["c4"], help="strong scaling: one fixed read set split over the ranks")
     ap.add_argument("--strong-reads", type=int, default=100000)
-    ap.add_argument("--cpu-sample", type=int, default=2000, help="reads timed on the CPU baseline (0 = skip); 2000 reads ~ 15 s on one core")
+    ap.add_argument("--full", action="store_true", help="also every leg and check beyond the timed steps (the module's docstring); the --no-* options and --cpu-sample "
+                                                         "trim this line")
+    ap.add_argument("--cpu-sample", type=int, default=2000, help="--full: reads timed on the CPU baseline (0 = skip); 2000 reads ~ 15 s on one core")
     ap.add_argument("--config", default=None, choices=["c2", "c3"], help="a secondary line for another BASELINE config: c2 = 1 000 reads of unit 100 x 10 copies (L ~ 1.25 kb); c3 = 100 reads of unit 200 x 200 copies (L ~ 42 kb), -a on in the command-line leg")
-    ap.add_argument("--no-secondary", action="store_true", help="the default line without its secondary objects (BASELINE configs 2 and 3 measured in child processes, configs 2 / 4 / 5 through the command line, the host's ceiling)")
-    ap.add_argument("--no-latency", action="store_true")
-    ap.add_argument("--no-cli", action="store_true")
-    ap.add_argument("--no-upload-leg", action="store_true", help="skip value_with_upload (profiling passes: only launches of the resident headline batch)")
+    ap.add_argument("--no-secondary", action="store_true", help="the --full line without its secondary objects (BASELINE configs 2 and 3 measured in child processes, configs 2 / 4 / 5 through the command line, the host's ceiling)")
+    ap.add_argument("--no-latency", action="store_true", help="the --full line without latency_ms_per_read_p50")
+    ap.add_argument("--no-cli", action="store_true", help="the --full line without the command-line legs")
+    ap.add_argument("--no-upload-leg", action="store_true", help="the --full line without value_with_upload (profiling passes: only launches of the resident headline batch)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the record tables of the last timed step to DIR/<name>.npy (rank 0; see dump_outputs) to compare two builds output for output")
     a = ap.parse_args()
@@ -490,7 +568,7 @@ def main():
     launcher_pre = None
     pre = {}
     t_start = time.time()
-    if world > 1 and not a.no_cli and not a.strong and a.config is None:
+    if world > 1 and a.full and not a.no_cli and not a.strong and a.config is None:
         # (the marker: named after the launcher's process and port, and only believed when it was written AFTER this process started - a stale one from a run that
         #  died would let the other ranks initialise their GPUs while rank 0 is still timing)
         marker = os.path.join(tempfile.gettempdir(), f"mtr_bench_launcher_{os.getppid()}_{os.environ.get('MASTER_PORT', '0')}.done")
@@ -699,7 +777,9 @@ def main():
         return dt, k2
 
     # the REFERENCE's work on this batch (its DP calls and cells, what it answers from a repeated call included): one launch of the
-    # per-read kernel, which runs the reference's own sequential range loop (the chain also searches ranges that loop removes)
+    # per-read kernel, which runs the reference's own sequential range loop (the chain also searches ranges that loop removes).  It is
+    # the first launch of engs[0] in every run, --full or not, so that the warm-up and the timed steps always start from the same state
+    # (engs[0]'s chain buffers are allocated by its first staged launch); only --full reports its counters (roofline)
     staged_before = os.environ.get("MTR_STAGED")
     os.environ["MTR_STAGED"] = "0"
     try:
@@ -730,7 +810,7 @@ def main():
             dumped = dump_outputs(a.dump_outputs, [data], [int(counts.sum())], counts)
     dt_kernel = None
     dt_upload = None
-    if world == 1:
+    if world == 1 and a.full:
         dt_kernel, _ = timed(a.steps, fetch=False)      # round 1's figure: the kernels alone, results left on the device
         if not a.strong and a.config is None and not a.no_upload_leg and NCTX >= 2:
             # the boundary handing over HOST buffers: every step takes a FRESH batch (three different read sets in turn) as concatenated base
@@ -759,21 +839,10 @@ def main():
         cnt = eng.counters()
         n_local = len(reads)
         value = n_job * a.steps / dt
-        # algorithmic bytes of one launch (this rank's batch): the reference's DP cells = computed + answered from the memo
-        sumL4 = sum((len(r) + 3) // 4 for r in reads)
-        cells = ref_cnt["dp_cells"] + ref_cnt["revise_dp_cells"] + ref_cnt["memo_cells"]
-        b_alg = sumL4 + 576 * ref_cnt["records"] + (cells + 1) // 2
         k2_avg_s = float(np.mean([k["k2_units"] for k in k2_ms])) / 1e3
-        achieved_gbs = b_alg / k2_avg_s / 1e9
-        valu_ops = cells * OPS_PER_CELL / k2_avg_s
-        step_s = dt / a.steps
         phases = sorted({p for k in k2_ms for p in k if p.startswith("chain_")})
         phase_ms = {p[6:]: float(np.mean([k.get(p, 0.0) for k in k2_ms])) for p in phases}
         phase_ms_alone = {p[6:]: float(np.mean([k.get(p, 0.0) for k in sync_k2])) for p in phases} if sync_k2 else None
-        prof, prof_tag = profiled_counters(a.config)
-        traffic = prof.get("k2_hbm_bytes_per_launch_fetch_x2") if prof else None
-        valu_insts = prof.get("SQ_INSTS_VALU_per_launch") if prof else None
-        wire_bytes = len(eng.fetch_packed()[0]) if world == 1 else None
         if a.strong:
             workload = (f"{a.strong}: ONE set of {n_job} synthetic Nanopore reads (unit 50-200 x 10 copies, L ~ 2 kb), contiguous blocks of equal "
                         f"read count over {world} GPU(s)")
@@ -786,61 +855,6 @@ def main():
         else:
             workload = (f"{WORKLOAD}: {n_local} synthetic Nanopore reads per GPU, unit 100 x 10 copies, 500-base flanks, "
                         f"mean L {np.mean([len(r) for r in reads]):.0f}, error profile sub 1.6/ins 9.0/del 3.8 %")
-        # ---- roofline of the DOMINANT kernel (mtr_k_revise_quads: four revisions per wavefront), by its own duration: HIP events around its launches
-        # on the launch stream (mtr_get_kernel_times id 8), (i) in the warm-up launches, which have the GPU to themselves - the figure
-        # `rocprofv3 --kernel-trace --stats` of a lone launch reproduces (profiles/) and the one `frac` uses -, (ii) in the pipelined timed region,
-        # where a launch shares the chip with its neighbour (reported, not used).  Its algorithmic work: the cells (rows x unit) of the vote DPs and
-        # re-alignments it ran (no padding: what a pass computes beyond them shows as bytes per cell in quad_passes) x 7 integer operations
-        def kavg(ks, name):
-            v = [k[name] for k in ks if name in k]
-            return float(np.mean(v)) if v else None
-        dom = "mtr_k_revise_quads"
-        dom_lone_ms, dom_timed_ms = kavg(sync_k2, "kernel_" + dom), kavg(k2_ms, "kernel_" + dom)
-        dp2_lone_ms = kavg(sync_k2, "kernel_mtr_k_dp2_quads")
-        dom_cells = cnt["qpass_cells_rev"]
-        launch_lone_s = (float(np.mean([k["k2_units"] for k in sync_k2])) / 1e3) if sync_k2 else None
-        computed_cells = cnt["dp_cells"] + cnt["revise_dp_cells"]
-        if dom_lone_ms or dom_timed_ms:
-            dms = dom_lone_ms or dom_timed_ms
-            dom_ops = dom_cells * OPS_PER_CELL / (dms / 1e3)
-            roofline = {"bound": "valu-issue", "kernel": dom,
-                        "achieved": dom_ops / 1e12, "peak": VALU_PEAK_LANE_OPS / 1e12, "unit": "T lane-op/s", "frac": dom_ops / VALU_PEAK_LANE_OPS,
-                        "duration_ms": dms, "duration_source": ("HIP events around the kernel's launches, warm-up launches that have the GPU to themselves" if dom_lone_ms
-                                                                else "HIP events around the kernel's launches in the timed region (no warm-up launch ran)"),
-                        "duration_ms_in_timed_region": dom_timed_ms,
-                        "cells_per_launch": dom_cells, "ops_per_cell": OPS_PER_CELL,
-                        "frac_definition": "rounds 5-6: the dominant kernel's own cells x 7 / its lone duration / VALU peak (VERDICT r4's definition); the whole-launch "
-                                           "figure that rounds 1-4 called frac is whole_launch.frac_lone_launch / frac_by_step (ADVICE r5: not comparable across that change)",
-                        "cells_note": "cells (rows x unit) of the vote DPs and re-alignments the kernel ran in its passes of up to eight DPs per wavefront"}
-        else:       # a batch whose chain runs one DP per wavefront (small batches) or the per-read kernel: no kernel of its own to name - the launch
-            roofline = {"bound": "valu-issue", "kernel": "one launch (the chain ran one DP per wavefront: no dominant several-DPs-per-wavefront kernel)",
-                        "achieved": valu_ops / 1e12, "peak": VALU_PEAK_LANE_OPS / 1e12, "unit": "T lane-op/s", "frac": valu_ops / VALU_PEAK_LANE_OPS,
-                        "duration_ms": k2_avg_s * 1e3, "cells_per_launch": cells, "ops_per_cell": OPS_PER_CELL}
-        roofline.update({
-            "second_kernel": ({"kernel": "mtr_k_dp2_quads", "duration_ms": dp2_lone_ms, "cell_pairs_per_launch": cnt["qpass_cells_dp2"],
-                               "frac": 2 * cnt["qpass_cells_dp2"] * OPS_PER_CELL / (dp2_lone_ms / 1e3) / VALU_PEAK_LANE_OPS,
-                               "note": "two-parameter alignments: a cell pair = the cell of both parameter sets, 2 x 7 operations"} if dp2_lone_ms else None),
-            "whole_launch": {"kernel": "the staged chain (mtr_k1_ranges; per pass mtr_k_walks, mtr_k_walks_k, mtr_k_gather, mtr_k_dp2_quads, mtr_k_select, mtr_k_polish, "
-                                       "mtr_k_rev_share, mtr_k_revise_quads, mtr_k_finish; mtr_k_pass_mark between the passes; mtr_k_replay)",
-                             "cells_reference": cells, "cells_computed": computed_cells,
-                             "frac_by_step": cells * OPS_PER_CELL / step_s / VALU_PEAK_LANE_OPS,
-                             "frac_lone_launch": (cells * OPS_PER_CELL / launch_lone_s / VALU_PEAK_LANE_OPS) if launch_lone_s else None,
-                             "frac_computed_cells": computed_cells * OPS_PER_CELL / step_s / VALU_PEAK_LANE_OPS,
-                             "note": "cells_reference = the reference's DP cells of the launch (memo_cells of them answered without a DP); by the driver-visible step, by a "
-                                     "launch that has the GPU to itself, and the cells the kernels computed by the step"},
-            "issue": ({"by_lone_launch": (valu_insts * 2 / (1024 * launch_lone_s * 2.4e9)) if launch_lone_s else None,
-                       "by_step": valu_insts * 2 / (1024 * step_s * 2.4e9),
-                       "SQ_INSTS_VALU_per_launch": valu_insts,
-                       "note": "VALU issue utilisation = SQ_INSTS_VALU of one launch (committed PMC pass of THIS workload) x 2 cycles / (1 024 SIMDs x duration x 2.4 GHz), by the "
-                               "duration of a launch that has the GPU to itself and by the driver-visible step - not by the profiler's serialised launches (round 5's 0.170)"}
-                      if valu_insts else None),
-            "slot_time": slot_time(prof),
-            "hbm": {"achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved_gbs / HBM_PEAK_GBS,
-                    "frac_by_step": b_alg / step_s / 1e9 / HBM_PEAK_GBS,
-                    "algorithmic_bytes_per_launch": b_alg, "spilled": "every DP of the reference is counted as spilled (SURVEY.md 8d's upper figure)"},
-            "traffic": traffic, "traffic_source": prof_tag,
-            "note": "bound by VALU instruction issue: row-serial integer max-plus recurrence; issue, slot_time and traffic (HBM bytes per launch of the whole chain, "
-                    "FETCH_SIZE x 2 + WRITE_SIZE, separate PMC passes) come from the committed profile of THIS workload and are null without one"})
         out = {
             "metric": "reads/sec, 2 kb Nanopore synthetic" if a.config is None else "reads/sec, config 3 (unit 200 x 200 copies, L ~ 42 kb; secondary line)" if a.config == "c3"
                       else "reads/sec, config 2 (1 000 reads, unit 100 x 10 copies, L ~ 1.25 kb; secondary line)",
@@ -877,150 +891,155 @@ def main():
                             "alignments_bytes_per_cell_pair": (cnt["qpass_bytes_dp2"] / cnt["qpass_cells_dp2"]) if cnt["qpass_cells_dp2"] else None,
                             "revisions_bytes_per_cell": (cnt["qpass_bytes_rev"] / cnt["qpass_cells_rev"]) if cnt["qpass_cells_rev"] else None,
                             "alignments_bytes": cnt["qpass_bytes_dp2"], "revisions_bytes": cnt["qpass_bytes_rev"]},
-            "reference_work_per_launch": {k: ref_cnt[k] for k in ("dp_calls", "dp_cells", "revise_dp_calls", "revise_dp_cells", "memo_hits", "memo_cells", "ranges_executed", "records")},
-            "roofline": roofline,
         }
+        if a.full:
+            out["reference_work_per_launch"] = {k: ref_cnt[k] for k in ("dp_calls", "dp_cells", "revise_dp_calls", "revise_dp_cells", "memo_hits", "memo_cells",
+                                                                        "ranges_executed", "records")}
+            out["roofline"] = roofline_of(reads, cnt, ref_cnt, k2_ms, sync_k2, dt / a.steps, a.config)
         if dumped is not None:
             out["dumped_outputs"] = dumped
         out["chain_health"] = {"reads_sent_back": cnt["reads_sent_back"], "ok": cnt["reads_sent_back"] == 0,
                                "note": "reads the two-pass chain had to send back to the per-read kernel (its mark pass missed a range the reference's loop reaches): must be 0"}
         if cnt["reads_sent_back"] != 0:
             print(f"bench.py: WARNING: the chain sent {cnt['reads_sent_back']} reads back to the per-read kernel on the default path", file=sys.stderr)
-        if world == 1:
-            out["value_kernel"] = n_job * a.steps / dt_kernel
-            if dt_upload:
-                out["value_with_upload"] = n_job * a.steps / dt_upload
-                out["value_with_upload_definition"] = ("every step takes a fresh batch as host buffers (base codes, offsets, lengths): 2-bit packing on the calling thread + "
-                                                       "copy to the device (mtr_upload_batch) + kernels + tables fetched to pinned host memory; PCIe-inclusive, never `value`")
-            out["boundary"] = {"wire_bytes_per_step": wire_bytes, "record_struct_bytes_per_step": 2560 * cnt["records"],
-                               "fetch_cost_ms_per_step": (dt - dt_kernel) / a.steps * 1e3}
-        if a.strong and "blobs" in gathered:
-            h = hashlib.sha256()
-            for bl in gathered["blobs"]:
-                h.update(bl)
-            known = None
-            try:
-                with open(os.path.join(ROOT, "tests", "golden", f"c4_{'100k' if n_job == 100000 else n_job}_wire.json")) as fh:
-                    known = json.load(fh)
-            except Exception:
-                pass
-            out["strong"] = {"ranks_seen": sum(1 for n in gathered["reads"] if n > 0), "reads_per_rank": gathered["reads"],
-                             "records": sum(gathered["records"]), "sha256": h.hexdigest(),
-                             "matches_oracle": (known is not None and known["sha256"] == h.hexdigest() and known["records"] == sum(gathered["records"]))
-                                               if known else None,
-                             "known_answer": "tests/golden/c4_100k_wire.json (CPU oracle)" if known else None}
-        elif a.strong and world == 1:
-            data, counts = eng.fetch_packed()
-            known = None
-            try:
-                with open(os.path.join(ROOT, "tests", "golden", f"c4_{'100k' if n_job == 100000 else n_job}_wire.json")) as fh:
-                    known = json.load(fh)
-            except Exception:
-                pass
-            hx = hashlib.sha256(data).hexdigest()
-            out["strong"] = {"ranks_seen": 1, "reads_per_rank": [n_local], "records": int(counts.sum()), "sha256": hx,
-                             "matches_oracle": (known["sha256"] == hx) if known else None,
-                             "known_answer": "tests/golden/c4_100k_wire.json (CPU oracle)" if known else None}
-        if a.config is not None and world == 1:
-            # the launch's record stream against the CPU oracle's known answer (tests/golden/make_c4_wire_hash.py --config c3 -n 100 / --config c2 -n 1000)
-            data, counts = eng.fetch_packed()
-            known = None
-            try:
-                with open(os.path.join(ROOT, "tests", "golden", f"{a.config}_{n_local}_wire.json")) as fh:
-                    known = json.load(fh)
-            except Exception:
-                pass
-            hx = hashlib.sha256(data).hexdigest()
-            out["matches_oracle"] = (known["sha256"] == hx and known["records"] == int(counts.sum())) if known else None
-            out["record_stream"] = {"records": int(counts.sum()), "wire_bytes": len(data), "sha256": hx,
-                                    "known_answer": f"tests/golden/{a.config}_{n_local}_wire.json (CPU oracle, pinned to the reference)" if known else None}
-        if world == 1 and not a.no_latency:
-            lat = []
-            e2 = mtr_amd.Engine(device=local_rank)
-            for i in range(33):
-                t1 = time.perf_counter()
-                e2.process([reads[i]])
-                lat.append((time.perf_counter() - t1) * 1e3)
-            e2.close()
-            out["latency_ms_per_read_p50"] = float(np.median(lat[1:]))
-        if world == 1 and not a.no_cli and not a.strong and a.config == "c3":
-            for e in engs:
-                e.close()
-            engs.clear()
-            torch.cuda.empty_cache()
-            ca = cli_rate(reads, len(reads), ["-a"])
-            out["value_cli"] = ca.get("reads_per_s")
-            out["cli"] = {"note": "mtr_amd/host/mTR -a <fasta> > /dev/null (alignment of every reported repeat on), wall clock incl. process start and HIP initialisation; best of 3",
-                          "with_alignments": ca}
-        elif world == 1 and not a.no_cli and not a.strong and a.config == "c2":
-            for e in engs:
-                e.close()
-            engs.clear()
-            torch.cuda.empty_cache()
-            ca = cli_rate(reads, len(reads))
-            out["value_cli"] = ca.get("reads_per_s")
-            out["cli"] = {"note": "mtr_amd/host/mTR <fasta> > /dev/null, wall clock incl. process start and HIP initialisation; best of 3", "one_batch": ca}
-        elif world == 1 and not a.no_cli and not a.strong:
-            for e in engs:                              # the command line brings its own contexts: free this process's memory first
-                e.close()
-            engs.clear()
-            torch.cuda.empty_cache()
-            # this process has just given ~50 GB of device memory back: the driver reclaims it in the background, and a child that allocates meanwhile waits
-            # for it (measured: the second context's first launch of a run 0.64 s instead of 0.01 s, all three runs of the leg).  A pause and one untimed run first.
-            time.sleep(2.0)
-            cli_rate(reads, 2000)
-            c1 = cli_rate(reads, len(reads))
-            c10 = cli_rate(reads, 10 * len(reads))
-            out["value_cli"] = c10.get("reads_per_s")
-            out["cli"] = {"note": "mtr_amd/host/mTR <fasta> > /dev/null, wall clock incl. process start and HIP initialisation; best of 3",
-                          "one_batch": c1, "ten_batches": c10, "empty_hip_program": empty_hip_program()}
-            lr = launcher_rate(reads, 10 * len(reads), 1)
-            out["launcher"] = lr
-            out["value_launcher"] = lr.get("reads_per_s")
-            out["launcher_rccl_forced"] = launcher_rate(reads, 10 * len(reads), 1, force_rccl=True)
-            if not a.no_secondary:
-                # BASELINE configs 2, 4 and 5 as jobs of the command line (fresh child processes), and the host pipeline's ceiling behind eight GPUs (no GPU touched)
+        if a.full:                                      # every other leg and check of the line: none of them runs without --full
+            if world == 1:
+                wire_bytes = len(eng.fetch_packed()[0])
+                out["value_kernel"] = n_job * a.steps / dt_kernel
+                if dt_upload:
+                    out["value_with_upload"] = n_job * a.steps / dt_upload
+                    out["value_with_upload_definition"] = ("every step takes a fresh batch as host buffers (base codes, offsets, lengths): 2-bit packing on the calling thread + "
+                                                           "copy to the device (mtr_upload_batch) + kernels + tables fetched to pinned host memory; PCIe-inclusive, never `value`")
+                out["boundary"] = {"wire_bytes_per_step": wire_bytes, "record_struct_bytes_per_step": 2560 * cnt["records"],
+                                   "fetch_cost_ms_per_step": (dt - dt_kernel) / a.steps * 1e3}
+            if a.strong and "blobs" in gathered:
+                h = hashlib.sha256()
+                for bl in gathered["blobs"]:
+                    h.update(bl)
+                known = None
                 try:
-                    out["baseline_configs_cli"] = baseline_configs_through_the_command_line(1)
-                except Exception as ex:
-                    out["baseline_configs_cli"] = {"error": repr(ex)[:300]}
-                out["host_ceiling"] = host_ceiling_leg()
-            try:        # the command line's own part: from the first device context (the runtime is up) to the end of the run
-                st = c10["stamps_s"]
-                own = st.get("run stopped", st["everything printed"]) - st["first device context created"]
-                out["cli"]["ten_batches_after_runtime_start"] = {"seconds": own, "reads_per_s": c10["reads"] / own}
-            except Exception:
-                pass
-        if world == 1 and a.cpu_sample > 0 and not a.strong:
-            out["cpu_baseline"] = cpu_baseline(reads, a.cpu_sample if a.config is None else min(a.cpu_sample, 6 if a.config == "c3" else 1000))     # (a config-3 read is ~2.6 s of CPU)
-            if out["cpu_baseline"].get("ms_per_read_p50") and out.get("latency_ms_per_read_p50"):
-                out["latency_p50_vs_cpu"] = out["cpu_baseline"]["ms_per_read_p50"] / out["latency_ms_per_read_p50"]
-            out["speedup_vs_cpu_1core"] = value / out["cpu_baseline"]["value"]
-            if "all_cores" in out["cpu_baseline"]:
-                out["speedup_vs_cpu_all_cores"] = value / out["cpu_baseline"]["all_cores"]["value"]
-            if out.get("value_cli"):
-                out["speedup_cli_vs_cpu_1core"] = out["value_cli"] / out["cpu_baseline"]["value"]
-        if world == 1 and not dist_on and not a.strong and a.config is None and not a.no_secondary:
-            # BASELINE config 3 (unit 200 x 200 copies, L ~ 42 kb, -a on in its command-line leg) in the driver-run line: measured by a
-            # child process after this one has given its contexts back, its whole JSON line kept under secondary.c3
-            for e in engs:
-                e.close()
-            engs.clear()
-            torch.cuda.empty_cache()
-            out["secondary"] = {}
-            for cfg, steps in (("c2", "40"), ("c3", "24")):
-                t0 = time.perf_counter()
+                    with open(os.path.join(ROOT, "tests", "golden", f"c4_{'100k' if n_job == 100000 else n_job}_wire.json")) as fh:
+                        known = json.load(fh)
+                except Exception:
+                    pass
+                out["strong"] = {"ranks_seen": sum(1 for n in gathered["reads"] if n > 0), "reads_per_rank": gathered["reads"],
+                                 "records": sum(gathered["records"]), "sha256": h.hexdigest(),
+                                 "matches_oracle": (known is not None and known["sha256"] == h.hexdigest() and known["records"] == sum(gathered["records"]))
+                                                   if known else None,
+                                 "known_answer": "tests/golden/c4_100k_wire.json (CPU oracle)" if known else None}
+            elif a.strong and world == 1:
+                data, counts = eng.fetch_packed()
+                known = None
                 try:
-                    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", steps, "--warmup", "3", "--cpu-sample", str(min(a.cpu_sample, 6 if cfg == "c3" else 1000))]
-                                       + (["--no-cli"] if a.no_cli else []), capture_output=True, text=True, cwd=ROOT, timeout=420)
+                    with open(os.path.join(ROOT, "tests", "golden", f"c4_{'100k' if n_job == 100000 else n_job}_wire.json")) as fh:
+                        known = json.load(fh)
+                except Exception:
+                    pass
+                hx = hashlib.sha256(data).hexdigest()
+                out["strong"] = {"ranks_seen": 1, "reads_per_rank": [n_local], "records": int(counts.sum()), "sha256": hx,
+                                 "matches_oracle": (known["sha256"] == hx) if known else None,
+                                 "known_answer": "tests/golden/c4_100k_wire.json (CPU oracle)" if known else None}
+            if a.config is not None and world == 1:
+                # the launch's record stream against the CPU oracle's known answer (tests/golden/make_c4_wire_hash.py --config c3 -n 100 / --config c2 -n 1000)
+                data, counts = eng.fetch_packed()
+                known = None
+                try:
+                    with open(os.path.join(ROOT, "tests", "golden", f"{a.config}_{n_local}_wire.json")) as fh:
+                        known = json.load(fh)
+                except Exception:
+                    pass
+                hx = hashlib.sha256(data).hexdigest()
+                out["matches_oracle"] = (known["sha256"] == hx and known["records"] == int(counts.sum())) if known else None
+                out["record_stream"] = {"records": int(counts.sum()), "wire_bytes": len(data), "sha256": hx,
+                                        "known_answer": f"tests/golden/{a.config}_{n_local}_wire.json (CPU oracle, pinned to the reference)" if known else None}
+            if world == 1 and not a.no_latency:
+                lat = []
+                e2 = mtr_amd.Engine(device=local_rank)
+                for i in range(33):
+                    t1 = time.perf_counter()
+                    e2.process([reads[i]])
+                    lat.append((time.perf_counter() - t1) * 1e3)
+                e2.close()
+                out["latency_ms_per_read_p50"] = float(np.median(lat[1:]))
+            if world == 1 and not a.no_cli and not a.strong and a.config == "c3":
+                for e in engs:
+                    e.close()
+                engs.clear()
+                torch.cuda.empty_cache()
+                ca = cli_rate(reads, len(reads), ["-a"])
+                out["value_cli"] = ca.get("reads_per_s")
+                out["cli"] = {"note": "mtr_amd/host/mTR -a <fasta> > /dev/null (alignment of every reported repeat on), wall clock incl. process start and HIP initialisation; best of 3",
+                              "with_alignments": ca}
+            elif world == 1 and not a.no_cli and not a.strong and a.config == "c2":
+                for e in engs:
+                    e.close()
+                engs.clear()
+                torch.cuda.empty_cache()
+                ca = cli_rate(reads, len(reads))
+                out["value_cli"] = ca.get("reads_per_s")
+                out["cli"] = {"note": "mtr_amd/host/mTR <fasta> > /dev/null, wall clock incl. process start and HIP initialisation; best of 3", "one_batch": ca}
+            elif world == 1 and not a.no_cli and not a.strong:
+                for e in engs:                              # the command line brings its own contexts: free this process's memory first
+                    e.close()
+                engs.clear()
+                torch.cuda.empty_cache()
+                # this process has just given ~50 GB of device memory back: the driver reclaims it in the background, and a child that allocates meanwhile waits
+                # for it (measured: the second context's first launch of a run 0.64 s instead of 0.01 s, all three runs of the leg).  A pause and one untimed run first.
+                time.sleep(2.0)
+                cli_rate(reads, 2000)
+                c1 = cli_rate(reads, len(reads))
+                c10 = cli_rate(reads, 10 * len(reads))
+                out["value_cli"] = c10.get("reads_per_s")
+                out["cli"] = {"note": "mtr_amd/host/mTR <fasta> > /dev/null, wall clock incl. process start and HIP initialisation; best of 3",
+                              "one_batch": c1, "ten_batches": c10, "empty_hip_program": empty_hip_program()}
+                lr = launcher_rate(reads, 10 * len(reads), 1)
+                out["launcher"] = lr
+                out["value_launcher"] = lr.get("reads_per_s")
+                out["launcher_rccl_forced"] = launcher_rate(reads, 10 * len(reads), 1, force_rccl=True)
+                if not a.no_secondary:
+                    # BASELINE configs 2, 4 and 5 as jobs of the command line (fresh child processes), and the host pipeline's ceiling behind eight GPUs (no GPU touched)
                     try:
-                        sec = json.loads(p.stdout.strip().splitlines()[-1])
-                    except Exception:
-                        sec = {"error": (p.stderr or p.stdout)[-400:], "returncode": p.returncode}
-                except subprocess.TimeoutExpired as ex:         # a stuck child must not take the driver-run line with it
-                    sec = {"error": "timeout after 420 s: " + ((ex.stderr or b"")[-300:].decode(errors="replace") if isinstance(ex.stderr, bytes) else str(ex.stderr or "")[-300:])}
-                sec["wall_s"] = time.perf_counter() - t0
-                out["secondary"][cfg] = sec
+                        out["baseline_configs_cli"] = baseline_configs_through_the_command_line(1)
+                    except Exception as ex:
+                        out["baseline_configs_cli"] = {"error": repr(ex)[:300]}
+                    out["host_ceiling"] = host_ceiling_leg()
+                try:        # the command line's own part: from the first device context (the runtime is up) to the end of the run
+                    st = c10["stamps_s"]
+                    own = st.get("run stopped", st["everything printed"]) - st["first device context created"]
+                    out["cli"]["ten_batches_after_runtime_start"] = {"seconds": own, "reads_per_s": c10["reads"] / own}
+                except Exception:
+                    pass
+            if world == 1 and a.cpu_sample > 0 and not a.strong:
+                out["cpu_baseline"] = cpu_baseline(reads, a.cpu_sample if a.config is None else min(a.cpu_sample, 6 if a.config == "c3" else 1000))     # (a config-3 read is ~2.6 s of CPU)
+                if out["cpu_baseline"].get("ms_per_read_p50") and out.get("latency_ms_per_read_p50"):
+                    out["latency_p50_vs_cpu"] = out["cpu_baseline"]["ms_per_read_p50"] / out["latency_ms_per_read_p50"]
+                out["speedup_vs_cpu_1core"] = value / out["cpu_baseline"]["value"]
+                if "all_cores" in out["cpu_baseline"]:
+                    out["speedup_vs_cpu_all_cores"] = value / out["cpu_baseline"]["all_cores"]["value"]
+                if out.get("value_cli"):
+                    out["speedup_cli_vs_cpu_1core"] = out["value_cli"] / out["cpu_baseline"]["value"]
+            if world == 1 and not dist_on and not a.strong and a.config is None and not a.no_secondary:
+                # BASELINE configs 2 and 3 (config 3: unit 200 x 200 copies, L ~ 42 kb, -a on in its command-line leg) in the line: each measured by a
+                # --full child process after this one has given its contexts back, its whole JSON line kept under secondary.<config>
+                for e in engs:
+                    e.close()
+                engs.clear()
+                torch.cuda.empty_cache()
+                out["secondary"] = {}
+                for cfg, steps in (("c2", "40"), ("c3", "24")):
+                    t0 = time.perf_counter()
+                    try:
+                        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--config", cfg, "--steps", steps, "--warmup", "3",
+                                            "--cpu-sample", str(min(a.cpu_sample, 6 if cfg == "c3" else 1000))]
+                                           + (["--no-cli"] if a.no_cli else []), capture_output=True, text=True, cwd=ROOT, timeout=420)
+                        try:
+                            sec = json.loads(p.stdout.strip().splitlines()[-1])
+                        except Exception:
+                            sec = {"error": (p.stderr or p.stdout)[-400:], "returncode": p.returncode}
+                    except subprocess.TimeoutExpired as ex:         # a stuck child must not take the --full line with it
+                        sec = {"error": "timeout after 420 s: " + ((ex.stderr or b"")[-300:].decode(errors="replace") if isinstance(ex.stderr, bytes) else str(ex.stderr or "")[-300:])}
+                    sec["wall_s"] = time.perf_counter() - t0
+                    out["secondary"][cfg] = sec
     for e in engs:
         e.close()
     engs.clear()

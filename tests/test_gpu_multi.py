@@ -325,7 +325,7 @@ def test_bench_strong_scaling_gathers_the_oracles_record_stream():
     env = {k: v for k, v in os.environ.items() if k not in ("MTR_LIB", "RANK", "WORLD_SIZE", "LOCAL_RANK")}
     if n == 1:
         env["MTR_BENCH_BACKEND"] = "gloo"
-    p = _torchrun(world, [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--strong", "c4", "--steps", "1", "--warmup", "1"], env, 800)
+    p = _torchrun(world, [os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--strong", "c4", "--steps", "1", "--warmup", "1"], env, 800)
     assert p.returncode == 0, p.stderr.decode()[-800:]
     line = json.loads(p.stdout.decode().strip().splitlines()[-1])
     assert line["n_gpus"] == world and line["scaling"] == "strong"
@@ -358,7 +358,7 @@ def test_rccl_strong_c4_10000_reads_match_the_oracles_hash():
     """bench.py --strong c4 --strong-reads 10000 through RCCL with one rank: the gathered record stream's sha256 is the CPU oracle's
     (tests/golden/c4_10000_wire.json, made by tests/golden/make_c4_wire_hash.py -n 10000)."""
     import json
-    p = _torchrun_one_rank([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--strong", "c4", "--strong-reads", "10000", "--steps", "1", "--warmup", "1"],
+    p = _torchrun_one_rank([os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--strong", "c4", "--strong-reads", "10000", "--steps", "1", "--warmup", "1"],
                            {"MTR_BENCH_FORCE_DIST": "1"})
     assert p.returncode == 0, p.stderr.decode()[-800:]
     line = json.loads(p.stdout.decode().strip().splitlines()[-1])

@@ -136,17 +136,37 @@ def test_config3_shape_16_reads_against_the_oracle():
 
 @pytest.mark.timeout(900)
 def test_config3_at_full_size_record_stream_is_the_oracles():
-    """BASELINE config 3 as bench.py measures it (its default line's secondary.c3 runs the same child): 100 reads of unit 200 x 200 copies,
+    """BASELINE config 3 as bench.py measures it (its --full line's secondary.c3 runs the same child): 100 reads of unit 200 x 200 copies,
     the launch's record stream in wire form against the CPU oracle's known answer (tests/golden/c3_100_wire.json)."""
     import json
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("MTR_LIB", "RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c3", "--steps", "1", "--warmup", "1", "--no-cli", "--no-latency", "--cpu-sample", "0"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "c3", "--steps", "1", "--warmup", "1", "--no-cli", "--no-latency", "--cpu-sample", "0"],
                        capture_output=True, env=env, timeout=800, cwd=ROOT)
     assert p.returncode == 0, p.stderr.decode()[-800:]
     line = json.loads(p.stdout.decode().strip().splitlines()[-1])
     assert line["matches_oracle"] is True and line["record_stream"]["records"] == 1724, line.get("record_stream")
     assert "config 3" in line["metric"] and line["config"]["reads_per_gpu"] == 100
+
+
+@pytest.mark.timeout(900)
+def test_bench_without_full_runs_only_the_headline(tmp_path):
+    """bench.py without --full: set-up, warm-up, timed steps, --dump-outputs and the line - none of the legs or checks --full adds"""
+    env = {k: v for k, v in os.environ.items() if k not in ("MTR_LIB", "RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    dump = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--reads", "2000", "--dump-outputs", str(dump)],
+                       capture_output=True, env=env, timeout=800, cwd=ROOT)
+    assert p.returncode == 0, p.stderr.decode()[-800:]
+    line = json.loads(p.stdout.decode().strip().splitlines()[-1])
+    assert line["unit"] == "reads/s" and line["higher_is_better"] is True and line["dtype"] == "int32" and line["steps"] == 3 and line["warmup"] == 1
+    assert abs(line["value"] - 2000 / (line["ms_per_step"] / 1e3)) < 1e-6 * line["value"]          # reads per second of the timed steps
+    full_only = {"reference_work_per_launch", "roofline", "value_kernel", "value_with_upload", "boundary", "latency_ms_per_read_p50", "value_cli", "cli",
+                 "launcher", "value_launcher", "launcher_rccl_forced", "baseline_configs_cli", "host_ceiling", "cpu_baseline", "secondary"}
+    assert not full_only & set(line), sorted(full_only & set(line))
+    assert line["chain_health"]["ok"] is True
+    recs = np.load(dump / "records.npy")
+    assert recs.shape == (line["dumped_outputs"]["records"], 13) and len(recs) > 0
+    assert np.load(dump / "records_per_read.npy").shape == (2000,)
 
 
 @pytest.mark.timeout(900)

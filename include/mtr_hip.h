@@ -15,8 +15,9 @@
  * mtr_process_batch() is the batch form of that edge: it takes N reads as integer base codes
  * (what handle_one_file.c:284-285 copies into orgInputString) and returns, per read and in the
  * reference's insertion order, exactly the 17 arguments of insert_an_alignment_into_set (readID and
- * inputLen are the caller's own).  Chaining + printing (chaining.cpp) stay on the host side of the
- * boundary (mtr_amd/host/).
+ * inputLen are the caller's own).  Printing (chaining.cpp) stays on the host side of the boundary
+ * (mtr_amd/host/).  Chaining is done there too for the command line; mtr_report_device() makes the same chains on the
+ * device for a caller that wants mTR's report without a host round trip.
  *
  * Semantics = the reference run one read per process ("isolated semantics"): the
  * results do not depend on which other reads share the batch.
@@ -180,6 +181,25 @@ mtr_status mtr_export_packed_device(mtr_ctx *ctx, void *d_dst, int64_t capacity_
 mtr_status mtr_unpack_records(const uint8_t *blob, int64_t bytes, int64_t n_records, mtr_record *out);
 /* returns the number of bytes written, or -1 if capacity is too small */
 int64_t    mtr_pack_records(const mtr_record *records, int64_t n_records, uint8_t *out, int64_t capacity);
+
+/* ---- mTR's report on the device ------------------------------------------------------------------------------------------
+ * mTR's report on the device: per read the maximum-score chain of its records (chaining.cpp:243-363, ties in insertion order,
+ * exactly mtr_amd/host/chain.c), reads in input order, each read's repeats in print order.  The columns are caller-owned DEVICE
+ * memory on the context's GPU. */
+typedef struct mtr_report_dst {
+    int32_t *read;        /* [R]    read index                                                               */
+    int32_t *record;      /* [R]    index of the repeat among its read's records (insertion order, as fetch) */
+    int32_t *fields;      /* [R*14] the 14 header ints of mtr_record (0-origin positions)                    */
+    float   *ratio;       /* [R]    (float)num_matches / repeat_len - the printed "match ratio"              */
+    int64_t *unit_off;    /* [R+1]  units[unit_off[k] .. unit_off[k+1]) = repeat k's unit, ASCII             */
+    uint8_t *units;       /* [U]                                                                             */
+    int64_t  cap_repeats, cap_unit_bytes;
+} mtr_report_dst;
+/* As mtr_export_packed_device: the chains are made on the first call after a run (and kept until the next upload or run);
+ * counts_host[i] = repeats of read i, *out_repeats = R, *out_unit_bytes = U.  dst == NULL: MTR_OK with the sizes only; capacities
+ * below R / U: MTR_ERR_OVERFLOW with the sizes; else the columns are written and the context's stream synchronised before the
+ * call returns.  Before any run MTR_ERR_BAD_ARG; after a failed run the status that run latched. */
+mtr_status mtr_report_device(mtr_ctx *ctx, const mtr_report_dst *dst, int32_t *counts_host, int64_t *out_repeats, int64_t *out_unit_bytes);
 
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left

@@ -35,6 +35,12 @@ int32_t mtr_test_last_mode(const mtr_ctx *ctx);
 mtr_status mtr_set_trace(mtr_ctx *ctx, int32_t max_events);
 mtr_status mtr_get_trace(mtr_ctx *ctx, int32_t **out_events, int64_t *out_n);
 
+/* The chain kernel of mtr_report_device on caller-given records: set k is (start, end, matches)[set_off[k] .. set_off[k+1])
+ * (set_off has n_sets + 1 entries, set_off[0] = 0).  (*out_len)[k] = its chain's length, the chain (indices within the set, print
+ * order) at (*out_idx)[set_off[k] ..].  Both arrays are malloc'ed; free() them. */
+mtr_status mtr_test_chain(mtr_ctx *ctx, int32_t n_sets, const int64_t *set_off, const int32_t *start, const int32_t *end,
+                          const int32_t *matches, int32_t **out_len, int32_t **out_idx);
+
 #ifdef __cplusplus
 }
 #endif

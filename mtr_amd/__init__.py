@@ -38,7 +38,8 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_run_resident_async", "mtr_wait", "mtr_alignments",
            "mtr_file_state_create", "mtr_file_state_destroy", "mtr_upload_batch_in_file", "mtr_file_state_skip",
            "mtr_get_bases_after_read", "mtr_upload_batch_packed", "mtr_fetch_results_packed", "mtr_export_packed_device",
-           "mtr_unpack_records", "mtr_pack_records", "mtr_get_first_failed_read", "mtr_upload_batch_device"]
+           "mtr_unpack_records", "mtr_pack_records", "mtr_get_first_failed_read", "mtr_upload_batch_device",
+           "mtr_report_device", "mtr_test_chain"]
 
 
 class MtrError(RuntimeError):
@@ -80,6 +81,24 @@ class CRecord(C.Structure):
                 ("num_insertions", C.c_int32), ("num_deletions", C.c_int32), ("kmer", C.c_int32), ("match_gain", C.c_int32),
                 ("mismatch_penalty", C.c_int32), ("indel_penalty", C.c_int32), ("reserved", C.c_int32),
                 ("unit", C.c_char * (MAX_PERIOD + 4)), ("unit_score", C.c_int32 * MAX_PERIOD)]
+
+
+class CReportDst(C.Structure):
+    """mtr_report_dst: device pointers of the report's columns and their capacities"""
+    _fields_ = [("read", C.c_void_p), ("record", C.c_void_p), ("fields", C.c_void_p), ("ratio", C.c_void_p), ("unit_off", C.c_void_p),
+                ("units", C.c_void_p), ("cap_repeats", C.c_int64), ("cap_unit_bytes", C.c_int64)]
+
+
+class Report(NamedTuple):
+    """mTR's report of a batch (Engine.report_tensors): R repeats, the chains of the reads in input order, each in print order.
+    counts is on the CPU, every other column on the engine's device."""
+    counts: "object"      # int32 [n_reads]: repeats per read
+    read: "object"        # int32 [R]
+    record: "object"      # int32 [R]: index among the read's records (insertion order, as fetch())
+    fields: "object"      # int32 [R, 14]: rep_start .. reserved of mtr_record (0-origin positions)
+    ratio: "object"       # float32 [R]: (float)num_matches / repeat_len
+    unit_off: "object"    # int64 [R + 1]
+    units: "object"       # uint8 [U]: repeat k's unit is units[unit_off[k]:unit_off[k + 1]], ASCII
 
 
 class CKernelTime(C.Structure):
@@ -166,6 +185,10 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_fetch_results_packed.restype = C.c_int
     lib.mtr_export_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(C.c_int64), P(C.c_int64)]
     lib.mtr_export_packed_device.restype = C.c_int
+    lib.mtr_report_device.argtypes = [C.c_void_p, P(CReportDst), C.c_void_p, P(C.c_int64), P(C.c_int64)]
+    lib.mtr_report_device.restype = C.c_int
+    lib.mtr_test_chain.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(P(C.c_int32)), P(P(C.c_int32))]
+    lib.mtr_test_chain.restype = C.c_int
     lib.mtr_unpack_records.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
     lib.mtr_unpack_records.restype = C.c_int
     lib.mtr_pack_records.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
@@ -325,6 +348,45 @@ class Engine:
             self._check(self.lib.mtr_export_packed_device(self.h, C.c_void_p(blob.data_ptr()), blob.numel(), counts.ctypes.data, C.byref(total),
                                                           C.byref(nbytes)), "mtr_export_packed_device")
         return blob[:int(nbytes.value)], torch.from_numpy(counts)
+
+    def report_tensors(self) -> Report:
+        """mTR's report of the last run (mtr_report_device), chained on the device: a Report of fresh tensors on this engine's device
+        (counts on the CPU).  Follows export_tensor's stream handling."""
+        import torch
+
+        n = getattr(self, "n_reads", 0)                          # (nothing uploaded yet: the library answers MTR_ERR_BAD_ARG)
+        counts = np.zeros(max(n, 1), np.int32)
+        nrep, nub = C.c_int64(), C.c_int64()
+        self._check(self.lib.mtr_report_device(self.h, None, counts.ctypes.data, C.byref(nrep), C.byref(nub)), "mtr_report_device")
+        R, U = int(nrep.value), int(nub.value)
+        dev = torch.device("cuda", self.device)
+        read = torch.empty(R, dtype=torch.int32, device=dev)
+        record = torch.empty(R, dtype=torch.int32, device=dev)
+        fields = torch.empty((R, 14), dtype=torch.int32, device=dev)
+        ratio = torch.empty(R, dtype=torch.float32, device=dev)
+        unit_off = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        units = torch.empty(U, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        ptr = lambda t: t.data_ptr() if t.numel() else None     # noqa: E731
+        dst = CReportDst(ptr(read), ptr(record), ptr(fields), ptr(ratio), unit_off.data_ptr(), ptr(units), R, U)
+        self._check(self.lib.mtr_report_device(self.h, C.byref(dst), counts.ctypes.data, C.byref(nrep), C.byref(nub)), "mtr_report_device")
+        return Report(torch.from_numpy(counts[:n]), read, record, fields, ratio, unit_off, units)
+
+    def test_chain(self, sets):
+        """mtr_test_chain: the report's chain kernel on caller-given records; sets = list of (start, end, matches) sequences.
+        Returns per set its chain (indices within the set, print order)."""
+        off = np.zeros(len(sets) + 1, np.int64)
+        off[1:] = np.cumsum([len(s[0]) for s in sets])
+        cols = [np.ascontiguousarray(np.concatenate([np.asarray(s[c], np.int32) for s in sets]) if len(sets) else np.zeros(0, np.int32), np.int32)
+                for c in range(3)]
+        pl, pi = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+        self._check(self.lib.mtr_test_chain(self.h, len(sets), off.ctypes.data, cols[0].ctypes.data, cols[1].ctypes.data, cols[2].ctypes.data,
+                                            C.byref(pl), C.byref(pi)), "mtr_test_chain")
+        try:
+            return [[pi[int(off[k]) + t] for t in range(pl[k])] for k in range(len(sets))]
+        finally:
+            _libc.free(C.cast(pl, C.c_void_p))
+            _libc.free(C.cast(pi, C.c_void_p))
 
     def process_in_file(self, reads: Sequence[np.ndarray], file_state: "FileState") -> List[List[Record]]:
         """the next reads of a file under the reference's whole-file behaviour (include/mtr_hip.h, file-order mode)"""
@@ -502,6 +564,37 @@ class Engine:
         arr = np.ctypeslib.as_array(ev, shape=(max(n.value, 1), 16))[: n.value].copy()
         _libc.free(C.cast(ev, C.c_void_p))
         return arr
+
+
+def _c_float_text(x) -> str:
+    """printf("%f", (double)x) as glibc prints it: Python's "%f" is the same correctly rounded conversion, except for the
+    spelling of infinities and NaNs (glibc keeps the sign of a NaN: an x86 host's 0.0f / 0 prints "-nan")"""
+    x = float(x)
+    if x != x:
+        return "-nan" if np.signbit(x) else "nan"
+    if x in (float("inf"), float("-inf")):
+        return "inf" if x > 0 else "-inf"
+    return "%f" % x
+
+
+def format_report(ids, lens, report: Report) -> bytes:
+    """mTR's report lines (mtr_amd/host/print.c: report_line) from a Report: per repeat ID, L, start+1, end+1, repeat_len, period,
+    copies, matches, ratio (%f of the float), mismatches, insertions, deletions, unit, tab-separated.
+    ids: per read its ID (str or bytes, what the FASTA header line holds after '>'), lens: per read its length."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    read, fields, ratio = host(report.read), host(report.fields).reshape(-1, 14), host(report.ratio).astype(np.float32)
+    unit_off, units = host(report.unit_off), host(report.units).tobytes()
+    out = []
+    bid = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+    for k in range(len(read)):
+        r = int(read[k])
+        f = [int(v) for v in fields[k]]
+        cols = [str(int(lens[r])), str(f[0] + 1), str(f[1] + 1), str(f[2]), str(f[3]), str(f[4]), str(f[5]), _c_float_text(ratio[k]),
+                str(f[6]), str(f[7]), str(f[8])]
+        out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + units[int(unit_off[k]):int(unit_off[k + 1])] + b"\n")
+    return b"".join(out)
 
 
 def pack_read(codes: np.ndarray) -> np.ndarray:

@@ -32,6 +32,7 @@
 #include "k2_units.hip.inc"
 #include "k3_staged.hip.inc"
 #include "pack.hip.inc"
+#include "chain.hip.inc"
 
 static_assert(sizeof(DevRecord) == sizeof(mtr_record), "device and ABI record layouts must agree");
 static_assert(MTR_N_COUNTERS == CNT_N, "counter count");
@@ -195,8 +196,13 @@ struct mtr_ctx {
     DevBuf<int32_t> d_al_i32, d_al_len, d_al_ends; DevBuf<uint8_t> d_al_units, d_al_ops; DevBuf<int64_t> d_al_off;
     // device input (mtr_upload_batch_device): per read its text offset, the first read with a byte that is no base, the caller's stream's event
     DevBuf<int64_t> d_toff; DevBuf<int32_t> d_pack_bad; hipEvent_t ev_text = nullptr;
+    // mTR's report on the device (mtr_report_device): the chains of the resident batch, made once per batch (rep_ready), and
+    // their column layout: per read the chain length, its units' bytes, and the offsets of its records / chain / scratch / columns
+    bool rep_ready = false; int64_t rep_total = 0, rep_unit_bytes = 0;
+    DevBuf<int32_t> d_ch_idx, d_ch_len, d_ch_scr; DevBuf<int64_t> d_ch_off;
+    PinnedBuf<int32_t> h_ch; std::vector<int64_t> ch_off;
     // test entry points
-    DevBuf<int32_t> d_t_i32, d_t_out; DevBuf<uint8_t> d_t_units;
+    DevBuf<int32_t> d_t_i32, d_t_out; DevBuf<uint8_t> d_t_units; DevBuf<int64_t> d_t_i64;
 };
 
 // The MT19937 base stream is the same for every read and every context: one device copy per GPU, shared by the
@@ -312,7 +318,7 @@ static hipError_t copy_sync(mtr_ctx *ctx, void *dst, const void *src, size_t byt
 }
 
 // forget the resident batch (its buffers stay allocated for the next one)
-static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
+static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
 
 extern "C" int mtr_abi_version(void) { return MTR_ABI_VERSION; }
 
@@ -1110,7 +1116,7 @@ extern "C" mtr_status mtr_run_resident_async(mtr_ctx *ctx)
     if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
     HIPCHK(hipSetDevice(ctx->device));
     { mtr_status w = mtr_wait(ctx); if (w != MTR_OK && ctx->pending) return w; }
-    ctx->run_status = MTR_OK; ctx->ran = false; ctx->first_failed = -1; ctx->ovf_reads.clear();
+    ctx->run_status = MTR_OK; ctx->ran = false; ctx->first_failed = -1; ctx->ovf_reads.clear(); ctx->rep_ready = false;
     read_switches(ctx->sw);
     { mtr_status r = reset_run_state(ctx); if (r != MTR_OK) return r; }
     // [measured, round 3] the chain is the faster arrangement for every batch: a single 2 kb read 3.0 against 19 ms, 2 000 reads 19
@@ -1459,6 +1465,115 @@ extern "C" mtr_status mtr_export_packed_device(mtr_ctx *ctx, void *d_dst, int64_
     hipLaunchKernelGGL(mtr_k_wire_pack, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d_records, srcs, ctx->d_reccount, ctx->d_wire_off, ctx->max_rec, n, (uint8_t *)d_dst);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- mTR's report on the device (chain.hip.inc) ----------------------------------------------------------------------------
+// ch_off (host, and the same on the device in d_ch_off): [0, n] record offsets | [n+1, 2n] scratch offsets (-1: LDS) |
+// [2n+1, 3n+1] offsets of the reads' repeats | [3n+2, 4n+2] offsets of their unit bytes.  h_ch: counts | chain lengths | unit bytes.
+static mtr_status report_chains(mtr_ctx *ctx)
+{
+    if (ctx->rep_ready) return MTR_OK;
+    const int n = ctx->n_reads;
+    const DevRecord *const *srcs = nullptr;
+    { mtr_status st = record_sources(ctx, &srcs); if (st != MTR_OK) return st; }
+    HIPCHK(ctx->h_ch.ensure((size_t)n * 12));
+    int32_t *h = ctx->h_ch;
+    HIPCHK(copy_sync(ctx, h, ctx->d_reccount, (size_t)n * 4, hipMemcpyDeviceToHost));
+    ctx->ch_off.assign(4 * (size_t)n + 3, 0);
+    int64_t *rec_off = ctx->ch_off.data(), *scr_off = rec_off + n + 1, *rep_off = scr_off + n, *ubase = rep_off + n + 1;
+    int64_t scr = 0;
+    for (int i = 0; i < n; i++) {
+        int c = h[i];
+        if (!srcs && c > ctx->max_rec) c = ctx->max_rec;            // as the compaction reads them
+        rec_off[i + 1] = rec_off[i] + c;
+        scr_off[i] = c > MTR_CHAIN_LDS_RECS ? scr : -1;
+        if (c > MTR_CHAIN_LDS_RECS) scr += MTR_CHAIN_INTS(c);
+    }
+    HIPCHK(ctx->d_ch_off.ensure(ctx->ch_off.size() * 8));
+    HIPCHK(ctx->d_ch_idx.ensure((size_t)std::max<int64_t>(rec_off[n], 1) * 4));
+    HIPCHK(ctx->d_ch_len.ensure((size_t)n * 8));
+    HIPCHK(ctx->d_ch_scr.ensure((size_t)std::max<int64_t>(scr, 1) * 4));
+    HIPCHK(copy_sync(ctx, ctx->d_ch_off, rec_off, (2 * (size_t)n + 1) * 8, hipMemcpyHostToDevice));
+    int64_t *d_off = ctx->d_ch_off;
+    hipLaunchKernelGGL(mtr_k_chain, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d_records, srcs, ctx->d_reccount, ctx->max_rec, n,
+                       d_off, d_off + n + 1, ctx->d_ch_scr, ctx->d_ch_idx, ctx->d_ch_len, ctx->d_ch_len + n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(ctx, h + n, ctx->d_ch_len, (size_t)n * 8, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) { rep_off[i + 1] = rep_off[i] + h[n + i]; ubase[i + 1] = ubase[i] + h[2 * n + i]; }
+    HIPCHK(copy_sync(ctx, d_off + 2 * n + 1, rep_off, (2 * (size_t)n + 2) * 8, hipMemcpyHostToDevice));
+    ctx->rep_total = rep_off[n]; ctx->rep_unit_bytes = ubase[n];
+    ctx->rep_ready = true;
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_report_device(mtr_ctx *ctx, const mtr_report_dst *dst, int32_t *counts_host, int64_t *out_repeats, int64_t *out_unit_bytes)
+{
+    if (!ctx || !counts_host || !out_repeats || !out_unit_bytes) return MTR_ERR_BAD_ARG;
+    { mtr_status r = results_ready(ctx, false); if (r != MTR_OK) return r; }
+    HIPCHK(hipSetDevice(ctx->device));
+    { mtr_status st = report_chains(ctx); if (st != MTR_OK) return st; }
+    const int n = ctx->n_reads;
+    const int64_t R = ctx->rep_total, U = ctx->rep_unit_bytes;
+    memcpy(counts_host, (int32_t *)ctx->h_ch + n, (size_t)n * 4);
+    *out_repeats = R; *out_unit_bytes = U;
+    if (!dst) return MTR_OK;
+    if (dst->cap_repeats < R || dst->cap_unit_bytes < U) {
+        ctx->err = "destination holds " + std::to_string(dst->cap_repeats) + " repeats / " + std::to_string(dst->cap_unit_bytes) + " unit bytes, " +
+                   std::to_string(R) + " / " + std::to_string(U) + " needed";
+        return MTR_ERR_OVERFLOW;
+    }
+    if (!dst->unit_off || (R > 0 && (!dst->read || !dst->record || !dst->fields || !dst->ratio)) || (U > 0 && !dst->units)) {
+        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
+    }
+    const DevRecord *const *srcs = nullptr;
+    { mtr_status st = record_sources(ctx, &srcs); if (st != MTR_OK) return st; }
+    const int64_t *d_off = ctx->d_ch_off;
+    hipLaunchKernelGGL(mtr_k_report_pack, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d_records, srcs, ctx->max_rec, n, d_off,
+                       ctx->d_ch_idx, ctx->d_ch_len, d_off + 2 * n + 1, d_off + 3 * n + 2, R, U,
+                       dst->read, dst->record, dst->fields, dst->ratio, dst->unit_off, dst->units);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_test_chain(mtr_ctx *ctx, int32_t n_sets, const int64_t *set_off, const int32_t *start, const int32_t *end,
+                                     const int32_t *matches, int32_t **out_len, int32_t **out_idx)
+{
+    if (!ctx || n_sets < 0 || !set_off || !out_len || !out_idx) return MTR_ERR_BAD_ARG;
+    if (set_off[0] != 0) { ctx->err = "set_off[0] must be 0"; return MTR_ERR_BAD_ARG; }
+    for (int k = 0; k < n_sets; k++)
+        if (set_off[k + 1] < set_off[k] || set_off[k + 1] - set_off[k] > (1 << 24)) { ctx->err = "bad set " + std::to_string(k); return MTR_ERR_BAD_ARG; }
+    const int64_t total = set_off[n_sets];
+    if (total > 0 && (!start || !end || !matches)) return MTR_ERR_BAD_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    HostArray<int32_t> len = host_array<int32_t>((size_t)std::max(n_sets, 1)), idx = host_array<int32_t>((size_t)std::max<int64_t>(total, 1));
+    if (!len || !idx) return MTR_ERR_OOM;
+    if (n_sets > 0) {
+        std::vector<int64_t> off((size_t)2 * n_sets + 1);              // set offsets | scratch offsets
+        int64_t scr = 0;
+        for (int k = 0; k <= n_sets; k++) off[(size_t)k] = set_off[k];
+        for (int k = 0; k < n_sets; k++) {
+            const int64_t c = set_off[k + 1] - set_off[k];
+            off[(size_t)n_sets + 1 + k] = c > MTR_CHAIN_LDS_RECS ? scr : -1;
+            if (c > MTR_CHAIN_LDS_RECS) scr += MTR_CHAIN_INTS(c);
+        }
+        const size_t t = (size_t)total;
+        HIPCHK(ctx->d_t_i32.ensure((3 * t + 1) * 4)); HIPCHK(ctx->d_t_out.ensure((t + (size_t)n_sets) * 4));
+        HIPCHK(ctx->d_ch_scr.ensure((size_t)std::max<int64_t>(scr, 1) * 4)); HIPCHK(ctx->d_t_i64.ensure(off.size() * 8));
+        int32_t *d_in = ctx->d_t_i32, *d_out = ctx->d_t_out;
+        if (t > 0) {
+            HIPCHK(copy_sync(ctx, d_in, start, t * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_in + t, end, t * 4, hipMemcpyHostToDevice));
+            HIPCHK(copy_sync(ctx, d_in + 2 * t, matches, t * 4, hipMemcpyHostToDevice));
+        }
+        HIPCHK(copy_sync(ctx, ctx->d_t_i64, off.data(), off.size() * 8, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(mtr_k_chain_sets, dim3((unsigned)n_sets), dim3(64), 0, ctx->stream, d_in, d_in + t, d_in + 2 * t, ctx->d_t_i64, n_sets,
+                           ctx->d_t_i64 + n_sets + 1, ctx->d_ch_scr, d_out, d_out + t);
+        HIPCHK(hipGetLastError());
+        HIPCHK(copy_sync(ctx, len.get(), d_out + t, (size_t)n_sets * 4, hipMemcpyDeviceToHost));
+        if (t > 0) HIPCHK(copy_sync(ctx, idx.get(), d_out, t * 4, hipMemcpyDeviceToHost));
+    }
+    *out_len = len.release(); *out_idx = idx.release();
     return MTR_OK;
 }
 

@@ -201,6 +201,30 @@ typedef struct mtr_report_dst {
  * call returns.  Before any run MTR_ERR_BAD_ARG; after a failed run the status that run latched. */
 mtr_status mtr_report_device(mtr_ctx *ctx, const mtr_report_dst *dst, int32_t *counts_host, int64_t *out_repeats, int64_t *out_unit_bytes);
 
+/* ---- the -a alignments of the report's repeats, on the device ------------------------------------------------------------------
+ * The alignment between the read and the predicted tandem repeat (the reference's -a: wrap_around_DP.c:57-213, chaining.cpp:164-167)
+ * of every repeat of mtr_report_device, in its order: repeat k here is repeat k there, R the same.  The reads' 2-bit image, the
+ * records and the chains are resident after a run, so no base, unit, record or path byte crosses to the host: device kernels make the
+ * tasks, mtr_alignments' kernel aligns them, and a kernel renders each path into caller-owned DEVICE memory on the context's GPU -
+ * in FORWARD (print) order, the order in which print.c's alignment_block prints the columns, 50 to a block.
+ *   column c of repeat k (col_off[k] <= c < col_off[k+1]):  ops[c] = 1 match, 2 mismatch, 3 gap in the read, 4 gap in the unit;
+ *   text[c] = the read's base or '-', text[C + c] = '|' for a match, else ' ', text[2C + c] = the unit's base or '-'   (C = *out_columns);
+ *   first[2k] = 0-origin read position, first[2k+1] = 1-origin unit column at repeat k's FIRST column (0, 0 for a repeat without columns).
+ * A repeat with rep_period <= 0 or an empty path has zero columns (alignment_block prints only its scores line).  A read position one
+ * or two past the read's end shows what mtr_get_bases_after_read reports ('A' under isolated semantics).
+ * Protocol as mtr_report_device: the alignments are made on the first call after a run (which makes the chains too if mtr_report_device
+ * has not been called) and kept until the next upload or run; *out_repeats = R, *out_columns = C.  dst == NULL: MTR_OK with the sizes
+ * only; capacities below R / C: MTR_ERR_OVERFLOW with the sizes, nothing written; else the columns are written and the context's stream
+ * synchronised before the call returns.  Before any run MTR_ERR_BAD_ARG; after a failed run the status that run latched. */
+typedef struct mtr_report_align_dst {
+    int64_t *col_off;     /* [R+1]  columns of repeat k = col_off[k] .. col_off[k+1]                              */
+    uint8_t *ops;         /* [C]                                                                                  */
+    uint8_t *text;        /* [3*C]  row r at text + r*C                                                           */
+    int32_t *first;       /* [R*2]                                                                                */
+    int64_t  cap_repeats, cap_columns;
+} mtr_report_align_dst;
+mtr_status mtr_report_alignments_device(mtr_ctx *ctx, const mtr_report_align_dst *dst, int64_t *out_repeats, int64_t *out_columns);
+
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left
  * of handle_one_file.c:281-287's loop across GPUs is ONE exchange: the record tables travel to the process that chains and

@@ -1,7 +1,8 @@
 """mtr_amd — MI355X (gfx950) implementation of reference mTR's per-read hot path.
 
-Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointers).  Only the device-input methods
-(Engine.upload_device / process_device / export_tensor) take or return torch tensors; they import torch when called.
+Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointers).  Only the device-input and report methods
+(Engine.upload_device / process_device / export_tensor / report_tensors / report_alignment_tensors) take or return torch tensors;
+they import torch when called.
 The product path is libmtr_hip.so only: importing works without a GPU, but creating an Engine
 without the library or without a HIP device raises — there is no CPU fallback.
 """
@@ -39,7 +40,8 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_file_state_create", "mtr_file_state_destroy", "mtr_upload_batch_in_file", "mtr_file_state_skip",
            "mtr_get_bases_after_read", "mtr_upload_batch_packed", "mtr_fetch_results_packed", "mtr_export_packed_device",
            "mtr_unpack_records", "mtr_pack_records", "mtr_get_first_failed_read", "mtr_upload_batch_device",
-           "mtr_report_device", "mtr_test_chain"]
+           "mtr_report_device", "mtr_test_chain", "mtr_report_alignments_device"]
+ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
 
 class MtrError(RuntimeError):
@@ -99,6 +101,20 @@ class Report(NamedTuple):
     ratio: "object"       # float32 [R]: (float)num_matches / repeat_len
     unit_off: "object"    # int64 [R + 1]
     units: "object"       # uint8 [U]: repeat k's unit is units[unit_off[k]:unit_off[k + 1]], ASCII
+
+
+class CReportAlignDst(C.Structure):
+    """mtr_report_align_dst: device pointers of the alignment columns and their capacities"""
+    _fields_ = [("col_off", C.c_void_p), ("ops", C.c_void_p), ("text", C.c_void_p), ("first", C.c_void_p),
+                ("cap_repeats", C.c_int64), ("cap_columns", C.c_int64)]
+
+
+class ReportAlignments(NamedTuple):
+    """The -a alignments of a Report's repeats (Engine.report_alignment_tensors): C columns in print order, all on the engine's device."""
+    col_off: "object"     # int64 [R + 1]: repeat k's columns are col_off[k]:col_off[k + 1]
+    ops: "object"         # uint8 [C]: 1 match, 2 mismatch, 3 gap in the read, 4 gap in the unit
+    text: "object"        # uint8 [3, C]: the read's bases or '-', '|' or ' ', the unit's bases or '-'
+    first: "object"       # int32 [R, 2]: 0-origin read position and 1-origin unit column of the repeat's first column
 
 
 class CKernelTime(C.Structure):
@@ -187,6 +203,8 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_export_packed_device.restype = C.c_int
     lib.mtr_report_device.argtypes = [C.c_void_p, P(CReportDst), C.c_void_p, P(C.c_int64), P(C.c_int64)]
     lib.mtr_report_device.restype = C.c_int
+    lib.mtr_report_alignments_device.argtypes = [C.c_void_p, P(CReportAlignDst), P(C.c_int64), P(C.c_int64)]
+    lib.mtr_report_alignments_device.restype = C.c_int
     lib.mtr_test_chain.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(P(C.c_int32)), P(P(C.c_int32))]
     lib.mtr_test_chain.restype = C.c_int
     lib.mtr_unpack_records.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
@@ -371,6 +389,25 @@ class Engine:
         dst = CReportDst(ptr(read), ptr(record), ptr(fields), ptr(ratio), unit_off.data_ptr(), ptr(units), R, U)
         self._check(self.lib.mtr_report_device(self.h, C.byref(dst), counts.ctypes.data, C.byref(nrep), C.byref(nub)), "mtr_report_device")
         return Report(torch.from_numpy(counts[:n]), read, record, fields, ratio, unit_off, units)
+
+    def report_alignment_tensors(self) -> ReportAlignments:
+        """The -a alignments of report_tensors()' repeats (mtr_report_alignments_device), aligned and rendered on the device: a
+        ReportAlignments of fresh tensors on this engine's device.  Follows report_tensors' stream handling."""
+        import torch
+
+        nrep, ncol = C.c_int64(), C.c_int64()
+        self._check(self.lib.mtr_report_alignments_device(self.h, None, C.byref(nrep), C.byref(ncol)), "mtr_report_alignments_device")
+        R, Cn = int(nrep.value), int(ncol.value)
+        dev = torch.device("cuda", self.device)
+        col_off = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        ops = torch.empty(Cn, dtype=torch.uint8, device=dev)
+        text = torch.empty((3, Cn), dtype=torch.uint8, device=dev)
+        first = torch.empty((R, 2), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        ptr = lambda t: t.data_ptr() if t.numel() else None     # noqa: E731
+        dst = CReportAlignDst(col_off.data_ptr(), ptr(ops), ptr(text), ptr(first), R, Cn)
+        self._check(self.lib.mtr_report_alignments_device(self.h, C.byref(dst), C.byref(nrep), C.byref(ncol)), "mtr_report_alignments_device")
+        return ReportAlignments(col_off, ops, text, first)
 
     def test_chain(self, sets):
         """mtr_test_chain: the report's chain kernel on caller-given records; sets = list of (start, end, matches) sequences.
@@ -577,15 +614,23 @@ def _c_float_text(x) -> str:
     return "%f" % x
 
 
-def format_report(ids, lens, report: Report) -> bytes:
+def format_report(ids, lens, report: Report, alignments: "ReportAlignments | None" = None) -> bytes:
     """mTR's report lines (mtr_amd/host/print.c: report_line) from a Report: per repeat ID, L, start+1, end+1, repeat_len, period,
     copies, matches, ratio (%f of the float), mismatches, insertions, deletions, unit, tab-separated.
-    ids: per read its ID (str or bytes, what the FASTA header line holds after '>'), lens: per read its length."""
+    ids: per read its ID (str or bytes, what the FASTA header line holds after '>'), lens: per read its length.
+    alignments (Engine.report_alignment_tensors of the same run): mTR -a's output - after each repeat's line the block print.c's
+    alignment_block prints: an empty line, the scores line, an empty line, then per ALIGN_WIDTH columns the three rows and an empty line."""
     def host(t):
         return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
 
     read, fields, ratio = host(report.read), host(report.fields).reshape(-1, 14), host(report.ratio).astype(np.float32)
     unit_off, units = host(report.unit_off), host(report.units).tobytes()
+    if alignments is not None:
+        col_off, text = host(alignments.col_off), np.ascontiguousarray(host(alignments.text), np.uint8)
+        text = text.reshape(3, text.size // 3)
+        rows = [text[0].tobytes(), text[1].tobytes(), text[2].tobytes()]
+        if len(col_off) != len(read) + 1:
+            raise MtrError(f"alignments of {len(col_off) - 1} repeats for a report of {len(read)}")
     out = []
     bid = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
     for k in range(len(read)):
@@ -594,6 +639,12 @@ def format_report(ids, lens, report: Report) -> bytes:
         cols = [str(int(lens[r])), str(f[0] + 1), str(f[1] + 1), str(f[2]), str(f[3]), str(f[4]), str(f[5]), _c_float_text(ratio[k]),
                 str(f[6]), str(f[7]), str(f[8])]
         out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + units[int(unit_off[k]):int(unit_off[k + 1])] + b"\n")
+        if alignments is not None:
+            out.append(f"\nmatch gain = {f[10]}, mismatch penalty = {f[11]}, indel penalty = {f[12]}\n\n".encode())
+            c1 = int(col_off[k + 1])
+            for c in range(int(col_off[k]), c1, ALIGN_WIDTH):
+                e = min(c + ALIGN_WIDTH, c1)
+                out.append(rows[0][c:e] + b"\n" + rows[1][c:e] + b"\n" + rows[2][c:e] + b"\n\n")
     return b"".join(out)
 
 

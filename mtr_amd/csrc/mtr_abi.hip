@@ -33,6 +33,7 @@
 #include "k3_staged.hip.inc"
 #include "pack.hip.inc"
 #include "chain.hip.inc"
+#include "report_align.hip.inc"
 
 static_assert(sizeof(DevRecord) == sizeof(mtr_record), "device and ABI record layouts must agree");
 static_assert(MTR_N_COUNTERS == CNT_N, "counter count");
@@ -201,6 +202,11 @@ struct mtr_ctx {
     bool rep_ready = false; int64_t rep_total = 0, rep_unit_bytes = 0;
     DevBuf<int32_t> d_ch_idx, d_ch_len, d_ch_scr; DevBuf<int64_t> d_ch_off;
     PinnedBuf<int32_t> h_ch; std::vector<int64_t> ch_off;
+    // the -a alignments of those repeats (mtr_report_alignments_device): made once per batch (ra_ready) - the tasks, the paths in traceback
+    // order as mtr_k_align leaves them, and the offsets of the repeats' columns; the rendering into the caller's columns is per call
+    bool ra_ready = false; int64_t ra_columns = 0;
+    DevBuf<int64_t> d_ra_sizes, d_ra_off, d_ra_coloff; DevBuf<int32_t> d_ra_i32, d_ra_len, d_ra_ends; DevBuf<uint8_t> d_ra_units, d_ra_ops;
+    DevBuf<const DevRecord *> d_ra_rec;
     // test entry points
     DevBuf<int32_t> d_t_i32, d_t_out; DevBuf<uint8_t> d_t_units; DevBuf<int64_t> d_t_i64;
 };
@@ -318,7 +324,7 @@ static hipError_t copy_sync(mtr_ctx *ctx, void *dst, const void *src, size_t byt
 }
 
 // forget the resident batch (its buffers stay allocated for the next one)
-static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
+static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
 
 extern "C" int mtr_abi_version(void) { return MTR_ABI_VERSION; }
 
@@ -1116,7 +1122,7 @@ extern "C" mtr_status mtr_run_resident_async(mtr_ctx *ctx)
     if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
     HIPCHK(hipSetDevice(ctx->device));
     { mtr_status w = mtr_wait(ctx); if (w != MTR_OK && ctx->pending) return w; }
-    ctx->run_status = MTR_OK; ctx->ran = false; ctx->first_failed = -1; ctx->ovf_reads.clear(); ctx->rep_ready = false;
+    ctx->run_status = MTR_OK; ctx->ran = false; ctx->first_failed = -1; ctx->ovf_reads.clear(); ctx->rep_ready = false; ctx->ra_ready = false;
     read_switches(ctx->sw);
     { mtr_status r = reset_run_state(ctx); if (r != MTR_OK) return r; }
     // [measured, round 3] the chain is the faster arrangement for every batch: a single 2 kb read 3.0 against 19 ms, 2 000 reads 19
@@ -1533,6 +1539,111 @@ extern "C" mtr_status mtr_report_device(mtr_ctx *ctx, const mtr_report_dst *dst,
                        ctx->d_ch_idx, ctx->d_ch_len, d_off + 2 * n + 1, d_off + 3 * n + 2, R, U,
                        dst->read, dst->record, dst->fields, dst->ratio, dst->unit_off, dst->units);
     HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- the -a alignments of the report's repeats (report_align.hip.inc) -------------------------------------------------------
+// d_ra_sizes: [0, n) path bytes per read | [n, 2n) unit bytes per read | [2n, 3n] offsets of the reads' units | [3n+1, 4n+1] offsets of
+// their paths | [4n+2] cells of the largest DP.  Only those closing scalars and the number of columns come to the host.
+static mtr_status report_alignments(mtr_ctx *ctx)
+{
+    if (ctx->ra_ready) return MTR_OK;
+    { mtr_status st = report_chains(ctx); if (st != MTR_OK) return st; }
+    const int n = ctx->n_reads;
+    const int64_t R = ctx->rep_total;
+    HIPCHK(ctx->d_ra_coloff.ensure(((size_t)R + 1) * 8));
+    if (R == 0) {
+        HIPCHK(hipMemsetAsync(ctx->d_ra_coloff, 0, 8, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        ctx->ra_columns = 0; ctx->ra_ready = true;
+        return MTR_OK;
+    }
+    if (R > (int64_t)INT32_MAX) { ctx->err = "more reported repeats than one alignment launch takes"; return MTR_ERR_OVERFLOW; }
+    read_switches(ctx->sw);
+    const DevRecord *const *srcs = nullptr;
+    { mtr_status st = record_sources(ctx, &srcs); if (st != MTR_OK) return st; }
+    HIPCHK(ctx->d_ra_sizes.ensure((4 * (size_t)n + 3) * 8));
+    int64_t *d_sz = ctx->d_ra_sizes, *d_ubase = d_sz + 2 * (size_t)n, *d_cbase = d_ubase + n + 1, *d_cells = d_cbase + n + 1;
+    const int64_t *d_off = ctx->d_ch_off;
+    HIPCHK(hipMemsetAsync(d_cells, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(mtr_k_align_sizes, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d_records, srcs, ctx->max_rec, n, d_off,
+                       ctx->d_ch_idx, ctx->d_ch_len, ctx->d_lens, d_sz, d_sz + n, (unsigned long long *)d_cells);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int64_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)d_sz, (int64_t)n, d_cbase);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int64_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)(d_sz + n), (int64_t)n, d_ubase);
+    HIPCHK(hipGetLastError());
+    int64_t unit_bytes = 0, tail[2] = { 0, 0 };                           // tail: the paths' bytes, the largest DP's cells
+    HIPCHK(hipMemcpyAsync(&unit_bytes, d_ubase + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(tail, d_cbase + n, 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const size_t ops_bytes = (size_t)tail[0], cells = (size_t)std::max<int64_t>(tail[1], 1);
+    if (unit_bytes > (int64_t)INT32_MAX) { ctx->err = "the units of the reported repeats exceed 2 GB"; return MTR_ERR_OVERFLOW; }
+    const size_t per_wave = mtrc_align(cells + 256, 256);             // + slack: the traceback's dword loads read a few bytes past a row
+    size_t total = 0;
+    const int waves = pick_waves(ctx, (int)R, 8, per_wave, &total);
+    DBG("report_alignments: %lld repeats, cells %zu, waves %d, scratch %zu, paths %zu bytes", (long long)R, cells, waves, total, ops_bytes);
+    { mtr_status s = ensure_scratch(ctx, total); if (s != MTR_OK) return s; }
+    const size_t nt = (size_t)R;
+    HIPCHK(ctx->d_ra_i32.ensure((nt * 7 + 1) * 4)); HIPCHK(ctx->d_ra_len.ensure(nt * 4)); HIPCHK(ctx->d_ra_ends.ensure(nt * 8));
+    HIPCHK(ctx->d_ra_units.ensure((size_t)unit_bytes + 16)); HIPCHK(ctx->d_ra_ops.ensure(ops_bytes + 16));
+    HIPCHK(ctx->d_ra_off.ensure((nt + 1) * 8)); HIPCHK(ctx->d_ra_rec.ensure(nt * sizeof(void *)));
+    int32_t *d_i32 = ctx->d_ra_i32;
+    AlignTaskDst t{};
+    t.read_idx = d_i32; t.rep_start = d_i32 + nt; t.rep_end = d_i32 + 2 * nt; t.gain = d_i32 + 3 * nt; t.mism = d_i32 + 4 * nt; t.indel = d_i32 + 5 * nt;
+    t.unit_off = d_i32 + 6 * nt; t.ops_off = ctx->d_ra_off; t.units = ctx->d_ra_units; t.rec_of = ctx->d_ra_rec;
+    hipLaunchKernelGGL(mtr_k_align_tasks, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d_records, srcs, ctx->max_rec, n, d_off,
+                       ctx->d_ch_idx, ctx->d_ch_len, d_off + 2 * n + 1, ctx->d_lens, (const int64_t *)d_cbase, (const int64_t *)d_ubase, R, t);
+    HIPCHK(hipGetLastError());
+    AlignArgs a{};
+    a.b = view(ctx); a.n_tasks = (int32_t)R;
+    a.read_idx = t.read_idx; a.rep_start = t.rep_start; a.rep_end = t.rep_end; a.gain = t.gain; a.mism = t.mism; a.indel = t.indel;
+    a.unit_off = t.unit_off; a.units = ctx->d_ra_units;
+    a.ops = ctx->d_ra_ops; a.ops_off = ctx->d_ra_off; a.ops_len = ctx->d_ra_len; a.ends = ctx->d_ra_ends;
+    a.scratch = ctx->d_scratch; a.scratch_per_wave = per_wave; a.cells_cap = cells;
+    a.status = ctx->d_status; a.work_counter = ctx->d_work; a.counters = ctx->d_counters; a.dp16_max_rows = ctx->sw.dp16_max_rows;
+    HIPCHK(hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned), ctx->stream));
+    hipLaunchKernelGGL(mtr_k_align, dim3((unsigned)waves), dim3(64), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)ctx->d_ra_len, R, (int64_t *)ctx->d_ra_coloff);
+    HIPCHK(hipGetLastError());
+    int64_t columns = 0;
+    HIPCHK(copy_sync(ctx, &columns, ctx->d_ra_coloff + R, 8, hipMemcpyDeviceToHost));
+    { mtr_status st = check_status(ctx); if (st != MTR_OK) return st; }
+    ctx->ra_columns = columns; ctx->ra_ready = true;
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_report_alignments_device(mtr_ctx *ctx, const mtr_report_align_dst *dst, int64_t *out_repeats, int64_t *out_columns)
+{
+    if (!ctx || !out_repeats || !out_columns) return MTR_ERR_BAD_ARG;
+    { mtr_status r = results_ready(ctx, false); if (r != MTR_OK) return r; }
+    HIPCHK(hipSetDevice(ctx->device));
+    { mtr_status st = report_alignments(ctx); if (st != MTR_OK) return st; }
+    const int64_t R = ctx->rep_total, Cn = ctx->ra_columns;
+    *out_repeats = R; *out_columns = Cn;
+    if (!dst) return MTR_OK;
+    if (dst->cap_repeats < R || dst->cap_columns < Cn) {
+        ctx->err = "destination holds " + std::to_string(dst->cap_repeats) + " repeats / " + std::to_string(dst->cap_columns) + " columns, " +
+                   std::to_string(R) + " / " + std::to_string(Cn) + " needed";
+        return MTR_ERR_OVERFLOW;
+    }
+    if (!dst->col_off || (R > 0 && !dst->first) || (Cn > 0 && (!dst->ops || !dst->text))) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipMemcpyAsync(dst->col_off, ctx->d_ra_coloff, ((size_t)R + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    if (R > 0) {
+        const size_t nt = (size_t)R;
+        AlignRenderArgs a{};
+        a.b = view(ctx); a.n_repeats = (int32_t)R;
+        a.read_idx = ctx->d_ra_i32; a.rep_start = ctx->d_ra_i32 + nt; a.ops_len = ctx->d_ra_len; a.ends = ctx->d_ra_ends;
+        a.path = ctx->d_ra_ops; a.path_off = ctx->d_ra_off; a.rec_of = ctx->d_ra_rec;
+        a.col_off = ctx->d_ra_coloff; a.n_columns = Cn;
+        a.ops = dst->ops; a.text = dst->text; a.first = dst->first; a.work_counter = ctx->d_work;
+        HIPCHK(hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned), ctx->stream));
+        const unsigned waves = (unsigned)std::min<int64_t>(R, (int64_t)ctx->n_cu * 16);
+        hipLaunchKernelGGL(mtr_k_align_render, dim3(waves), dim3(64), 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
 }

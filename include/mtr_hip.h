@@ -225,6 +225,30 @@ typedef struct mtr_report_align_dst {
 } mtr_report_align_dst;
 mtr_status mtr_report_alignments_device(mtr_ctx *ctx, const mtr_report_align_dst *dst, int64_t *out_repeats, int64_t *out_columns);
 
+/* ---- the report as text, on the device ---------------------------------------------------------------------------------------------
+ * The bytes mTR writes to stdout for the resident batch, formatted by device kernels into caller-owned DEVICE memory on the context's
+ * GPU: per repeat of mtr_report_device the line of mtr_amd/host/print.c's report_line (ID, L, start+1, end+1, repeat_len, period,
+ * copies, matches, the ratio as printf("%f") of (float)num_matches / repeat_len, mismatches, insertions, deletions, unit; tabs between,
+ * a line feed behind) and, with_alignments != 0, the block of alignment_block behind it (mTR -a: an empty line, the scores line, an
+ * empty line, then per 50 columns of the repeat's alignment its three rows and an empty line).  No byte of a record, unit or path
+ * crosses to the host.  The ratio's float is the ratio column of mtr_report_device bit for bit; 0 / 0 prints "-nan", as print.c on an
+ * x86 host (no record the library makes has repeat_len 0).
+ * ids / id_off are HOST arrays, the only caller data the report needs that the context does not have: read i's ID is the bytes
+ * ids[id_off[i] .. id_off[i+1]) - what the FASTA header holds behind '>' -, written verbatim; id_off has n_reads + 1 non-decreasing
+ * entries.  They are copied to the device per call and free again when it returns.
+ * Protocol as mtr_report_device: the chains, and for with_alignments the alignments, are made on first use after a run and kept until
+ * the next upload or run, so this call, mtr_report_device and mtr_report_alignments_device may come in any order and any mix, and both
+ * modes one after the other.  *out_bytes = B.  dst == NULL: MTR_OK with B only; cap_bytes below B: MTR_ERR_OVERFLOW with B, nothing
+ * written; else text and read_off are written and the context's stream synchronised before the call returns.  Before any run
+ * MTR_ERR_BAD_ARG; after a failed run the status that run latched; NULL ids / id_off or a decreasing id_off MTR_ERR_BAD_ARG. */
+typedef struct mtr_report_text_dst {
+    uint8_t *text;        /* [B]  mTR's stdout for the resident batch: reads in input order, each read's repeats in print order */
+    int64_t *read_off;    /* [n_reads+1] or NULL: read i's bytes are text[read_off[i] .. read_off[i+1]) */
+    int64_t  cap_bytes;
+} mtr_report_text_dst;
+mtr_status mtr_report_text_device(mtr_ctx *ctx, const char *ids, const int64_t *id_off, int32_t with_alignments,
+                                  const mtr_report_text_dst *dst, int64_t *out_bytes);
+
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left
  * of handle_one_file.c:281-287's loop across GPUs is ONE exchange: the record tables travel to the process that chains and

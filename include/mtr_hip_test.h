@@ -41,6 +41,13 @@ mtr_status mtr_get_trace(mtr_ctx *ctx, int32_t **out_events, int64_t *out_n);
 mtr_status mtr_test_chain(mtr_ctx *ctx, int32_t n_sets, const int64_t *set_off, const int32_t *start, const int32_t *end,
                           const int32_t *matches, int32_t **out_len, int32_t **out_idx);
 
+/* The line function of mtr_report_text_device on caller-given rows (the counterpart of mtr_test_chain).  Row k: the 14 header ints
+ * fields[14k ..], its read's length read_len[k], the unit bytes units[unit_off[k] .. unit_off[k+1]) printed as they are, and the ID
+ * ids[id_off[k] .. id_off[k+1]); unit_off and id_off have n_rows + 1 entries and start at 0.  Row k's line is
+ * (*out_text)[(*out_off)[k] .. (*out_off)[k+1]).  Both arrays are malloc'ed; free() them. */
+mtr_status mtr_test_report_lines(mtr_ctx *ctx, int32_t n_rows, const int32_t *fields, const int32_t *read_len, const uint8_t *units,
+                                 const int64_t *unit_off, const char *ids, const int64_t *id_off, uint8_t **out_text, int64_t **out_off);
+
 #ifdef __cplusplus
 }
 #endif

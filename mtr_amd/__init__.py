@@ -1,7 +1,8 @@
 """mtr_amd — MI355X (gfx950) implementation of reference mTR's per-read hot path.
 
 Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointers).  Only the device-input and report methods
-(Engine.upload_device / process_device / export_tensor / report_tensors / report_alignment_tensors) take or return torch tensors;
+(Engine.upload_device / process_device / export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes) take
+or return torch tensors;
 they import torch when called.
 The product path is libmtr_hip.so only: importing works without a GPU, but creating an Engine
 without the library or without a HIP device raises — there is no CPU fallback.
@@ -40,7 +41,7 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_file_state_create", "mtr_file_state_destroy", "mtr_upload_batch_in_file", "mtr_file_state_skip",
            "mtr_get_bases_after_read", "mtr_upload_batch_packed", "mtr_fetch_results_packed", "mtr_export_packed_device",
            "mtr_unpack_records", "mtr_pack_records", "mtr_get_first_failed_read", "mtr_upload_batch_device",
-           "mtr_report_device", "mtr_test_chain", "mtr_report_alignments_device"]
+           "mtr_report_device", "mtr_test_chain", "mtr_report_alignments_device", "mtr_report_text_device", "mtr_test_report_lines"]
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
 
@@ -115,6 +116,17 @@ class ReportAlignments(NamedTuple):
     ops: "object"         # uint8 [C]: 1 match, 2 mismatch, 3 gap in the read, 4 gap in the unit
     text: "object"        # uint8 [3, C]: the read's bases or '-', '|' or ' ', the unit's bases or '-'
     first: "object"       # int32 [R, 2]: 0-origin read position and 1-origin unit column of the repeat's first column
+
+
+class CReportTextDst(C.Structure):
+    """mtr_report_text_dst: device pointers of the text and the reads' offsets, and the text's capacity"""
+    _fields_ = [("text", C.c_void_p), ("read_off", C.c_void_p), ("cap_bytes", C.c_int64)]
+
+
+class ReportText(NamedTuple):
+    """mTR's stdout for a batch (Engine.report_text): B bytes, reads in input order, both tensors on the engine's device."""
+    text: "object"        # uint8 [B]
+    read_off: "object"    # int64 [n_reads + 1]: read i's bytes are text[read_off[i]:read_off[i + 1]]
 
 
 class CKernelTime(C.Structure):
@@ -205,6 +217,10 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_report_device.restype = C.c_int
     lib.mtr_report_alignments_device.argtypes = [C.c_void_p, P(CReportAlignDst), P(C.c_int64), P(C.c_int64)]
     lib.mtr_report_alignments_device.restype = C.c_int
+    lib.mtr_report_text_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, P(CReportTextDst), P(C.c_int64)]
+    lib.mtr_report_text_device.restype = C.c_int
+    lib.mtr_test_report_lines.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [P(P(C.c_uint8)), P(P(C.c_int64))]
+    lib.mtr_test_report_lines.restype = C.c_int
     lib.mtr_test_chain.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(P(C.c_int32)), P(P(C.c_int32))]
     lib.mtr_test_chain.restype = C.c_int
     lib.mtr_unpack_records.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
@@ -276,6 +292,29 @@ def device_input_args(text, offsets, lens, device: int):
     if text.device.index != device:
         raise MtrError(f"text is on {text.device}, the engine on cuda:{device}")
     return offs, ln
+
+
+def pack_ids(ids, n_reads: "int | None" = None):
+    """The IDs of a batch as mtr_report_text_device takes them: (bytes uint8 [>= 1], id_off int64 [n + 1]) as contiguous numpy arrays,
+    ID i = bytes[id_off[i]:id_off[i + 1]].  ids: one str (encoded as UTF-8) or bytes per read - what the FASTA header holds after '>'.
+    n_reads: the number of reads they must name.  Raises MtrError."""
+    if isinstance(ids, (str, bytes, bytearray)) or not hasattr(ids, "__len__"):
+        raise MtrError(f"ids must be a sequence of str or bytes, one per read, got {type(ids).__name__}")
+    if n_reads is not None and len(ids) != n_reads:
+        raise MtrError(f"{len(ids)} ids for {n_reads} uploaded reads")
+    raw = []
+    for i, v in enumerate(ids):
+        if isinstance(v, str):
+            raw.append(v.encode())
+        elif isinstance(v, (bytes, bytearray)):
+            raw.append(bytes(v))
+        else:
+            raise MtrError(f"id {i} must be str or bytes, got {type(v).__name__}")
+    off = np.zeros(len(raw) + 1, np.int64)
+    if raw:
+        off[1:] = np.cumsum([len(b) for b in raw], dtype=np.int64)
+    data = np.frombuffer(b"".join(raw) + b"\0", np.uint8)                # (never empty: the library takes no NULL ids)
+    return np.ascontiguousarray(data), off
 
 
 class Engine:
@@ -408,6 +447,50 @@ class Engine:
         dst = CReportAlignDst(col_off.data_ptr(), ptr(ops), ptr(text), ptr(first), R, Cn)
         self._check(self.lib.mtr_report_alignments_device(self.h, C.byref(dst), C.byref(nrep), C.byref(ncol)), "mtr_report_alignments_device")
         return ReportAlignments(col_off, ops, text, first)
+
+    def report_text(self, ids, alignments: bool = False) -> ReportText:
+        """mTR's stdout for the last run (mtr_report_text_device), formatted on the device: the report lines, with alignments=True
+        mTR -a's alignment blocks behind them - byte for byte format_report's result, as a ReportText of fresh tensors on this
+        engine's device.  ids: one str or bytes per uploaded read.  Follows report_tensors' stream handling."""
+        import torch
+
+        n = getattr(self, "n_reads", 0)                          # (nothing uploaded yet: the library answers MTR_ERR_BAD_ARG)
+        data, off = pack_ids(ids, n)
+        mode = 1 if alignments else 0
+        nb = C.c_int64()
+        self._check(self.lib.mtr_report_text_device(self.h, data.ctypes.data, off.ctypes.data, mode, None, C.byref(nb)), "mtr_report_text_device")
+        B = int(nb.value)
+        dev = torch.device("cuda", self.device)
+        text = torch.empty(B, dtype=torch.uint8, device=dev)
+        read_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the tensors on its own stream: torch's earlier use of the memory is done
+        dst = CReportTextDst(text.data_ptr() if B else None, read_off.data_ptr(), B)
+        self._check(self.lib.mtr_report_text_device(self.h, data.ctypes.data, off.ctypes.data, mode, C.byref(dst), C.byref(nb)), "mtr_report_text_device")
+        return ReportText(text, read_off)
+
+    def report_bytes(self, ids, alignments: bool = False) -> bytes:
+        """report_text(ids, alignments).text on the host: one device-to-host copy of the finished text"""
+        return self.report_text(ids, alignments).text.cpu().numpy().tobytes()
+
+    def test_report_lines(self, fields, read_len, units, ids) -> List[bytes]:
+        """mtr_test_report_lines: the line function of report_text on caller-given rows - fields int32 [n, 14], read_len [n], units
+        and ids one bytes (or str) per row.  Returns per row its line."""
+        f = np.ascontiguousarray(np.asarray(fields, np.int32).reshape(-1, 14))
+        ln = np.ascontiguousarray(read_len, np.int32)
+        udata, uoff = pack_ids(units, len(f))
+        idata, ioff = pack_ids(ids, len(f))
+        if len(ln) != len(f):
+            raise MtrError(f"{len(ln)} read lengths for {len(f)} rows")
+        pt, po = C.POINTER(C.c_uint8)(), C.POINTER(C.c_int64)()
+        self._check(self.lib.mtr_test_report_lines(self.h, len(f), f.ctypes.data, ln.ctypes.data, udata.ctypes.data, uoff.ctypes.data,
+                                                   idata.ctypes.data, ioff.ctypes.data, C.byref(pt), C.byref(po)), "mtr_test_report_lines")
+        try:
+            off = np.ctypeslib.as_array(po, shape=(len(f) + 1,)).copy()
+            text = C.string_at(pt, int(off[-1]))
+            return [text[int(off[k]):int(off[k + 1])] for k in range(len(f))]
+        finally:
+            _libc.free(C.cast(pt, C.c_void_p))
+            _libc.free(C.cast(po, C.c_void_p))
 
     def test_chain(self, sets):
         """mtr_test_chain: the report's chain kernel on caller-given records; sets = list of (start, end, matches) sequences.

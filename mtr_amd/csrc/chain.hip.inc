@@ -35,6 +35,14 @@ __device__ __forceinline__ int chain_unit_len(const DevRecord *r)
     return n;
 }
 
+// the printed "match ratio": (float)num_matches / repeat_len, the ratio column of mtr_report_device and the float mtr_report_text_device prints
+__device__ __forceinline__ float report_ratio(int matches, int repeat_len)
+{
+    float ratio = (float)matches / (float)repeat_len;                // correctly rounded (build.py), as the host's float division
+    if (ratio != ratio) ratio = __int_as_float((int)0xffc00000u);    // 0 / 0: the NaN an x86 host makes (printed "-nan")
+    return ratio;
+}
+
 // the records of a read: DevRecord slots (the product) or caller-given triples (mtr_test_chain)
 struct ChainRecs {
     const DevRecord *rec;                                      // non-null: f[0] start, f[1] end, f[5] matches
@@ -222,9 +230,7 @@ __global__ void __launch_bounds__(64) mtr_k_report_pack(const DevRecord *in, con
             const DevRecord *r = src + i;
             ul = chain_unit_len(r);
             o_read[k0 + t] = rd; o_record[k0 + t] = i;
-            float ratio = (float)r->f[5] / (float)r->f[2];                   // correctly rounded (build.py), as the host's float division
-            if (ratio != ratio) ratio = __int_as_float((int)0xffc00000u);    // 0 / 0: the NaN an x86 host makes (printed "-nan")
-            o_ratio[k0 + t] = ratio;
+            o_ratio[k0 + t] = report_ratio(r->f[5], r->f[2]);
         }
         int incl = ul;                                                       // inclusive scan of the unit lengths over the 64 lanes
         for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d); if (lane >= d) incl += v; }

@@ -34,6 +34,7 @@
 #include "pack.hip.inc"
 #include "chain.hip.inc"
 #include "report_align.hip.inc"
+#include "report_text.hip.inc"
 
 static_assert(sizeof(DevRecord) == sizeof(mtr_record), "device and ABI record layouts must agree");
 static_assert(MTR_N_COUNTERS == CNT_N, "counter count");
@@ -207,8 +208,12 @@ struct mtr_ctx {
     bool ra_ready = false; int64_t ra_columns = 0;
     DevBuf<int64_t> d_ra_sizes, d_ra_off, d_ra_coloff; DevBuf<int32_t> d_ra_i32, d_ra_len, d_ra_ends; DevBuf<uint8_t> d_ra_units, d_ra_ops;
     DevBuf<const DevRecord *> d_ra_rec;
+    // the report as text (mtr_report_text_device), per call: the caller's IDs, the repeats' byte counts / offsets, where their alignment rows begin
+    DevBuf<uint8_t> d_rt_ids; DevBuf<int64_t> d_rt_idoff, d_rt_bytes, d_rt_off, d_rt_rows;
+    // the sizes of the last call (rt_ready; for rt_mode and the ID lengths rt_idoff): a sizes-only call followed by the writing call sizes once
+    bool rt_ready = false; int32_t rt_mode = 0; int64_t rt_bytes = 0; std::vector<int64_t> rt_idoff;
     // test entry points
-    DevBuf<int32_t> d_t_i32, d_t_out; DevBuf<uint8_t> d_t_units; DevBuf<int64_t> d_t_i64;
+    DevBuf<int32_t> d_t_i32, d_t_out; DevBuf<uint8_t> d_t_units, d_t_text; DevBuf<int64_t> d_t_i64;
 };
 
 // The MT19937 base stream is the same for every read and every context: one device copy per GPU, shared by the
@@ -324,7 +329,7 @@ static hipError_t copy_sync(mtr_ctx *ctx, void *dst, const void *src, size_t byt
 }
 
 // forget the resident batch (its buffers stay allocated for the next one)
-static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
+static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
 
 extern "C" int mtr_abi_version(void) { return MTR_ABI_VERSION; }
 
@@ -1122,7 +1127,7 @@ extern "C" mtr_status mtr_run_resident_async(mtr_ctx *ctx)
     if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
     HIPCHK(hipSetDevice(ctx->device));
     { mtr_status w = mtr_wait(ctx); if (w != MTR_OK && ctx->pending) return w; }
-    ctx->run_status = MTR_OK; ctx->ran = false; ctx->first_failed = -1; ctx->ovf_reads.clear(); ctx->rep_ready = false; ctx->ra_ready = false;
+    ctx->run_status = MTR_OK; ctx->ran = false; ctx->first_failed = -1; ctx->ovf_reads.clear(); ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false;
     read_switches(ctx->sw);
     { mtr_status r = reset_run_state(ctx); if (r != MTR_OK) return r; }
     // [measured, round 3] the chain is the faster arrangement for every batch: a single 2 kb read 3.0 against 19 ms, 2 000 reads 19
@@ -1645,6 +1650,120 @@ extern "C" mtr_status mtr_report_alignments_device(mtr_ctx *ctx, const mtr_repor
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- the report as text (report_text.hip.inc) ----------------------------------------------------------------------------------
+// Only the IDs go to the device and only the byte count comes back.
+extern "C" mtr_status mtr_report_text_device(mtr_ctx *ctx, const char *ids, const int64_t *id_off, int32_t with_alignments,
+                                             const mtr_report_text_dst *dst, int64_t *out_bytes)
+{
+    if (!ctx || !out_bytes) return MTR_ERR_BAD_ARG;
+    if (!ids || !id_off) { ctx->err = "ids / id_off is NULL"; return MTR_ERR_BAD_ARG; }
+    { mtr_status r = results_ready(ctx, false); if (r != MTR_OK) return r; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const int n = ctx->n_reads;
+    if (id_off[0] < 0) { ctx->err = "id_off[0] is negative"; return MTR_ERR_BAD_ARG; }
+    for (int i = 0; i < n; i++)
+        if (id_off[i + 1] < id_off[i]) { ctx->err = "id_off decreases at read " + std::to_string(i); return MTR_ERR_BAD_ARG; }
+    { mtr_status st = with_alignments ? report_alignments(ctx) : report_chains(ctx); if (st != MTR_OK) return st; }
+    const int64_t R = ctx->rep_total;
+    const DevRecord *const *srcs = nullptr;
+    { mtr_status st = record_sources(ctx, &srcs); if (st != MTR_OK) return st; }
+    const size_t nr = (size_t)std::max<int64_t>(R, 1);
+    HIPCHK(ctx->d_rt_ids.ensure((size_t)id_off[n] + 16)); HIPCHK(ctx->d_rt_idoff.ensure(((size_t)n + 1) * 8));
+    HIPCHK(ctx->d_rt_bytes.ensure(nr * 8)); HIPCHK(ctx->d_rt_off.ensure((nr + 1) * 8)); HIPCHK(ctx->d_rt_rows.ensure(nr * 8));
+    const int64_t *d_off = ctx->d_ch_off;
+    TextArgs t{};
+    t.in = ctx->d_records; t.src_of = srcs; t.max_rec = ctx->max_rec; t.n_reads = n;
+    t.rec_off = d_off; t.chain_idx = ctx->d_ch_idx; t.chain_len = ctx->d_ch_len; t.rep_off = d_off + 2 * n + 1; t.lens = ctx->d_lens;
+    t.total_repeats = R; t.ids = ctx->d_rt_ids; t.id_off = ctx->d_rt_idoff;
+    t.ops_len = with_alignments && R > 0 ? (const int32_t *)ctx->d_ra_len : nullptr;
+    t.bytes = ctx->d_rt_bytes; t.byte_off = ctx->d_rt_off; t.rows_off = ctx->d_rt_rows;
+    const int32_t mode = with_alignments ? 1 : 0;
+    // the sizes depend on the mode and on the IDs' lengths alone: kept from the call before (the sizes-only call of a caller that allocates between the two)
+    const bool sized = ctx->rt_ready && ctx->rt_mode == mode && ctx->rt_idoff.size() == (size_t)n + 1 && memcmp(ctx->rt_idoff.data(), id_off, ((size_t)n + 1) * 8) == 0;
+    int64_t B = ctx->rt_bytes;
+    if (!sized) {
+        ctx->rt_ready = false;
+        HIPCHK(hipMemcpyAsync(ctx->d_rt_idoff, id_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(mtr_k_text_lines<false>, dim3((unsigned)n), dim3(64), 0, ctx->stream, t);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(mtr_k_scan_offsets<int64_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)ctx->d_rt_bytes, R, (int64_t *)ctx->d_rt_off);
+        HIPCHK(hipGetLastError());
+        HIPCHK(copy_sync(ctx, &B, ctx->d_rt_off + R, 8, hipMemcpyDeviceToHost));
+        ctx->rt_idoff.assign(id_off, id_off + n + 1); ctx->rt_mode = mode; ctx->rt_bytes = B; ctx->rt_ready = true;
+    }
+    *out_bytes = B;
+    if (!dst) return MTR_OK;
+    if (dst->cap_bytes < B) {
+        ctx->err = "destination holds " + std::to_string(dst->cap_bytes) + " bytes, " + std::to_string(B) + " needed";
+        return MTR_ERR_OVERFLOW;
+    }
+    if (B > 0 && !dst->text) { ctx->err = "the destination text is NULL"; return MTR_ERR_BAD_ARG; }
+    t.text = dst->text; t.read_off = dst->read_off;
+    // the sizes need the IDs' lengths alone (copied above, and waited for by copy_sync): the ID bytes go to the device only where they are written
+    if (id_off[n] > 0) HIPCHK(hipMemcpyAsync(ctx->d_rt_ids, ids, (size_t)id_off[n], hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(mtr_k_text_lines<true>, dim3((unsigned)n), dim3(64), 0, ctx->stream, t);
+    HIPCHK(hipGetLastError());
+    if (with_alignments && ctx->ra_columns > 0) {
+        const size_t nt = (size_t)R;
+        AlignRenderArgs a{};
+        a.b = view(ctx); a.n_repeats = (int32_t)R;
+        a.read_idx = ctx->d_ra_i32; a.rep_start = ctx->d_ra_i32 + nt; a.ops_len = ctx->d_ra_len; a.ends = ctx->d_ra_ends;
+        a.path = ctx->d_ra_ops; a.path_off = ctx->d_ra_off; a.rec_of = ctx->d_ra_rec;
+        a.work_counter = ctx->d_work;
+        HIPCHK(hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned), ctx->stream));
+        const unsigned waves = (unsigned)std::min<int64_t>(R, (int64_t)ctx->n_cu * 16);
+        hipLaunchKernelGGL(mtr_k_text_align, dim3(waves), dim3(64), 0, ctx->stream, a, (const int64_t *)ctx->d_rt_rows, dst->text);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_test_report_lines(mtr_ctx *ctx, int32_t n_rows, const int32_t *fields, const int32_t *read_len, const uint8_t *units,
+                                            const int64_t *unit_off, const char *ids, const int64_t *id_off, uint8_t **out_text, int64_t **out_off)
+{
+    if (!ctx || n_rows < 0 || !unit_off || !id_off || !out_text || !out_off) return MTR_ERR_BAD_ARG;
+    if (n_rows > 0 && (!fields || !read_len)) return MTR_ERR_BAD_ARG;
+    if (unit_off[0] != 0 || id_off[0] != 0) { ctx->err = "unit_off[0] and id_off[0] must be 0"; return MTR_ERR_BAD_ARG; }
+    for (int k = 0; k < n_rows; k++)
+        if (unit_off[k + 1] < unit_off[k] || unit_off[k + 1] - unit_off[k] > (1 << 24) || id_off[k + 1] < id_off[k]) { ctx->err = "bad row " + std::to_string(k); return MTR_ERR_BAD_ARG; }
+    const size_t nr = (size_t)n_rows, ub = (size_t)unit_off[nr], ib = (size_t)id_off[nr];
+    if ((ub > 0 && !units) || (ib > 0 && !ids)) return MTR_ERR_BAD_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    HostArray<int64_t> off = host_array<int64_t>(nr + 1);
+    if (!off) return MTR_ERR_OOM;
+    off[0] = 0;
+    int64_t B = 0;
+    if (n_rows > 0) {
+        // d_t_i32: fields | read_len;  d_t_units: units | ids;  d_t_i64: unit_off | id_off | bytes | byte_off
+        HIPCHK(ctx->d_t_i32.ensure(nr * 15 * 4)); HIPCHK(ctx->d_t_units.ensure(ub + ib + 16)); HIPCHK(ctx->d_t_i64.ensure((4 * nr + 3) * 8));
+        int32_t *d_f = ctx->d_t_i32, *d_len = d_f + 14 * nr;
+        uint8_t *d_units = ctx->d_t_units, *d_ids = d_units + ub;
+        int64_t *d_uoff = ctx->d_t_i64, *d_ioff = d_uoff + nr + 1, *d_bytes = d_ioff + nr + 1, *d_boff = d_bytes + nr;
+        HIPCHK(copy_sync(ctx, d_f, fields, nr * 14 * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_len, read_len, nr * 4, hipMemcpyHostToDevice));
+        if (ub > 0) HIPCHK(copy_sync(ctx, d_units, units, ub, hipMemcpyHostToDevice));
+        if (ib > 0) HIPCHK(copy_sync(ctx, d_ids, ids, ib, hipMemcpyHostToDevice));
+        HIPCHK(copy_sync(ctx, d_uoff, unit_off, (nr + 1) * 8, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_ioff, id_off, (nr + 1) * 8, hipMemcpyHostToDevice));
+        const unsigned blocks = (unsigned)((nr + 63) / 64);
+        hipLaunchKernelGGL(mtr_k_text_rows<false>, dim3(blocks), dim3(64), 0, ctx->stream, n_rows, (const int32_t *)d_f, (const int32_t *)d_len, (const uint8_t *)d_units,
+                           (const int64_t *)d_uoff, (const uint8_t *)d_ids, (const int64_t *)d_ioff, d_bytes, (const int64_t *)d_boff, (uint8_t *)nullptr);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(mtr_k_scan_offsets<int64_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)d_bytes, (int64_t)n_rows, d_boff);
+        HIPCHK(hipGetLastError());
+        HIPCHK(copy_sync(ctx, off.get(), d_boff, (nr + 1) * 8, hipMemcpyDeviceToHost));
+        B = off[nr];
+        HIPCHK(ctx->d_t_text.ensure((size_t)B + 16));
+        hipLaunchKernelGGL(mtr_k_text_rows<true>, dim3(blocks), dim3(64), 0, ctx->stream, n_rows, (const int32_t *)d_f, (const int32_t *)d_len, (const uint8_t *)d_units,
+                           (const int64_t *)d_uoff, (const uint8_t *)d_ids, (const int64_t *)d_ioff, d_bytes, (const int64_t *)d_boff, (uint8_t *)ctx->d_t_text);
+        HIPCHK(hipGetLastError());
+    }
+    HostArray<uint8_t> text = host_array<uint8_t>((size_t)std::max<int64_t>(B, 1));
+    if (!text) return MTR_ERR_OOM;
+    if (B > 0) HIPCHK(copy_sync(ctx, text.get(), ctx->d_t_text, (size_t)B, hipMemcpyDeviceToHost));
+    *out_text = text.release(); *out_off = off.release();
     return MTR_OK;
 }
 

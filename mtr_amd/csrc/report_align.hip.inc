@@ -131,50 +131,78 @@ struct AlignRenderArgs {
     unsigned int *work_counter;
 };
 
-// One wavefront per repeat, 64 columns a step.  Column q of the path (q = 0: the LAST printed column) shows read position
+// One alignment as the kernels that print it see it: repeat k's path in traceback order and what its columns are read from.
+struct AlignCols {
+    const uint8_t *path; const uint32_t *pk; const DevRecord *r;
+    int n, U, L, end_pos, end_col;
+    int used_p, used_j;                                              // read bases / unit columns the steps before this one consumed
+};
+// false: alignment_block prints only the scores line (no columns, or no unit).  Wave-uniform.
+__device__ __forceinline__ bool align_cols_begin(AlignCols &s, const AlignRenderArgs &a, int k)
+{
+    s.n = uni(a.ops_len[k]);
+    s.r = (const DevRecord *)uni64((long long)a.rec_of[k]);
+    s.U = uni(s.r->f[3]);
+    if (s.n <= 0 || s.U <= 0) return false;
+    const int rd = uni(a.read_idx[k]);
+    s.pk = a.b.packed + uni64(a.b.woff[rd]);
+    s.L = uni(a.b.lens[rd]);
+    s.end_pos = uni(a.rep_start[k]) - 1 + uni(a.ends[2 * k]); s.end_col = uni(a.ends[2 * k + 1]);
+    s.path = a.path + uni64(a.path_off[k]);
+    s.used_p = 0; s.used_j = 0;
+    return true;
+}
+// One step of 64 columns.  Column q = c + lane of the path (q = 0: the LAST printed column) shows read position
 // p(q) = end_pos - #{q' < q : no gap in the read} and unit column j(q) = ((end_col - 1 - #{q' < q : no gap in the unit}) mod U) + 1:
-// two ballots and the count of the lanes below per step, the steps' totals carried in scalars.  Lane q writes index n - 1 - q.
+// two ballots and the count of the lanes below per step, the steps' totals carried in s.  Returns q < n; then op is the column's
+// operation, p its read position, x its 0-origin unit column and row[0 .. 3) the three characters alignment_block prints for it.
+__device__ __forceinline__ bool align_cols_step(AlignCols &s, int c, int &op, int &p, int &x, uint8_t row[3])
+{
+    const int q = c + lane_id();
+    const bool in = q < s.n;
+    op = in ? (int)s.path[q] : 0;
+    const unsigned long long mp = __ballot(in && op != 3), mj = __ballot(in && op != 4);
+    p = s.end_pos - s.used_p - mbcnt(mp);
+    x = (s.end_col - 1 - s.used_j - mbcnt(mj)) % s.U;
+    if (x < 0) x += s.U;
+    if (in) {
+        // positions L and L + 1 read what the image holds there (zero, or in file-order mode the bases an earlier read left): the bits the DP saw
+        const int code = (p >= 0 && p < s.L + 2) ? base_at(s.pk, p) : 0;
+        const uint8_t xb = (uint8_t)(0x54474341u >> (8 * code)), ub = (uint8_t)s.r->unit[x];      // "ACGT"
+        row[0] = op == 3 ? (uint8_t)'-' : xb;
+        row[1] = op == 1 ? (uint8_t)'|' : (uint8_t)' ';
+        row[2] = op == 4 ? (uint8_t)'-' : ub;
+    }
+    s.used_p += __popcll(mp); s.used_j += __popcll(mj);
+    return in;
+}
+
+// One wavefront per repeat, 64 columns a step (align_cols_step).  Lane q writes index n - 1 - q: the path mirrored into print order.
 __global__ void __launch_bounds__(64) mtr_k_align_render(AlignRenderArgs a)
 {
     const int lane = lane_id();
     for (;;) {
         const int k = next_work_item(a.work_counter);
         if (k >= a.n_repeats) break;                                  // every wave reaches this exit
-        const int n = uni(a.ops_len[k]);
-        const DevRecord *r = (const DevRecord *)uni64((long long)a.rec_of[k]);
-        const int U = uni(r->f[3]);
-        if (n <= 0 || U <= 0) {                                      // alignment_block prints only the scores line
+        AlignCols s;
+        if (!align_cols_begin(s, a, k)) {                             // alignment_block prints only the scores line
             if (lane == 0) { a.first[2 * k] = 0; a.first[2 * k + 1] = 0; }
             loop_join();
             continue;
         }
-        const int rd = uni(a.read_idx[k]);
-        const uint32_t *pk = a.b.packed + uni64(a.b.woff[rd]);
-        const int L = uni(a.b.lens[rd]);
-        const int end_pos = uni(a.rep_start[k]) - 1 + uni(a.ends[2 * k]), end_col = uni(a.ends[2 * k + 1]);
-        const uint8_t *path = a.path + uni64(a.path_off[k]);
+        const int n = s.n;
         const int64_t o0 = uni64(a.col_off[k]) + (int64_t)(n - 1), C = a.n_columns;
-        int used_p = 0, used_j = 0;                                   // read bases / unit columns the steps before this one consumed
         for (int c = 0; c < n; c += 64) {
-            const int q = c + lane;
-            const bool in = q < n;
-            const int op = in ? (int)path[q] : 0;
-            const unsigned long long mp = __ballot(in && op != 3), mj = __ballot(in && op != 4);
-            const int p = end_pos - used_p - mbcnt(mp);
-            int x = (end_col - 1 - used_j - mbcnt(mj)) % U;
-            if (x < 0) x += U;
-            if (in) {
-                // positions L and L + 1 read what the image holds there (zero, or in file-order mode the bases an earlier read left): the bits the DP saw
-                const int code = (p >= 0 && p < L + 2) ? base_at(pk, p) : 0;
-                const uint8_t xb = (uint8_t)(0x54474341u >> (8 * code)), ub = (uint8_t)r->unit[x];      // "ACGT"
+            int op, p, x; uint8_t row[3];
+            if (align_cols_step(s, c, op, p, x, row)) {
+                const int q = c + lane;
                 const int64_t o = o0 - q;
                 a.ops[o] = (uint8_t)op;
-                a.text[o] = op == 3 ? (uint8_t)'-' : xb;
-                a.text[C + o] = op == 1 ? (uint8_t)'|' : (uint8_t)' ';
-                a.text[2 * C + o] = op == 4 ? (uint8_t)'-' : ub;
+                a.text[o] = row[0];
+                a.text[C + o] = row[1];
+                a.text[2 * C + o] = row[2];
                 if (q == n - 1) { a.first[2 * k] = p; a.first[2 * k + 1] = x + 1; }
             }
-            used_p += __popcll(mp); used_j += __popcll(mj);
         }
         loop_join();
     }

@@ -157,6 +157,51 @@ mtr_status mtr_upload_batch_packed(mtr_ctx *ctx, const uint32_t *packed, int64_t
 mtr_status mtr_upload_batch_device(mtr_ctx *ctx, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
                                    const int32_t *lens, int32_t n_reads, int32_t text_kind, void *wait_stream);
 
+/* ---- a FASTA file in device memory ---------------------------------------------------------------------------------------
+ * The step in front of mtr_upload_batch_device: the bytes of a FASTA file in DEVICE memory on the context's GPU (read there
+ * directly, or copied raw) are parsed by device kernels with the rules of the reference's reader (handle_one_file.c:169-269,
+ * restated in mtr_amd/host/fasta.c and in mtr_amd/csrc/fasta.hip.inc): fgets windows of 4095 characters, a window that begins
+ * with '>' is a header whose ID runs to the first NUL, LF or CR, such a character hides the rest of a sequence window, bases in
+ * front of the first header join the first record.  The input stops at the first of: a character that is none of ACGTacgt
+ * (MTR_FASTA_END_BADCHAR), a header that closes a record without bases (MTR_FASTA_END_EMPTY), a record's MTR_MAX_INPUT_LENGTH-th
+ * base (MTR_FASTA_END_TOOLONG); the reads are the records closed before it.  Without such a stop the end of the file closes the
+ * last record: MTR_FASTA_END_EOF, or MTR_FASTA_END_EMPTY if that record has no bases.  The values mean what MTRH_END_* of
+ * mtr_amd/host/mtr_host.h mean.
+ *   info      n_reads reads of n_bases bases in all, their IDs id_bytes bytes; end = why the input ended, end_pos = the position of
+ *             the stop in d_fasta (n_bytes when the file ended), bad_char = the character of MTR_FASTA_END_BADCHAR
+ *   dst       caller-owned DEVICE memory: text = the reads' bases, read after read, the file's own bytes (what
+ *             mtr_upload_batch_device takes as MTR_TEXT_ASCII); read i = text[offsets[i] .. offsets[i] + lens[i]); its ID =
+ *             ids[id_off[i] .. id_off[i + 1]), what the header holds behind '>'; id_off has n_reads + 1 entries
+ * mtr_parse_fasta_device follows mtr_report_device's protocol: dst == NULL: MTR_OK with info only; a capacity below info's:
+ * MTR_ERR_OVERFLOW with info filled, nothing written; else the columns are written and the context's stream synchronised before
+ * the call returns.  A stop is no error: the status is MTR_OK and info->end tells.  n_bytes == 0: MTR_OK, no reads,
+ * MTR_FASTA_END_EMPTY.  wait_stream as in mtr_upload_batch_device.  d_fasta that is NULL, not device memory of the context's GPU or
+ * runs past its allocation, and n_bytes < 0 or > INT32_MAX are MTR_ERR_BAD_ARG.  The resident batch is not touched.
+ * mtr_upload_fasta_device parses into buffers of the context and makes the reads the resident batch as mtr_upload_batch_device
+ * does.  A stop does not refuse the upload: the reads before it are uploaded, as the command line prints the reads before a bad
+ * record.  No reads: MTR_OK and no batch uploaded.  A read longer than MTR_MAX_READ_LENGTH: MTR_ERR_BAD_ARG naming the read, no
+ * batch uploaded.  run / fetch / export / alignments / report work afterwards as after any upload.  File-order mode needs the
+ * bases on the host: there is no FASTA variant of it.
+ * mtr_fasta_index: HOST copies of the last mtr_upload_fasta_device's index - lens[n_reads], id_off[n_reads + 1], ids[id_bytes] (what
+ * mtr_report_text_device takes); a NULL array is skipped.  MTR_ERR_BAD_ARG before any such upload. */
+#define MTR_FASTA_END_EOF 0
+#define MTR_FASTA_END_EMPTY 1
+#define MTR_FASTA_END_BADCHAR 2
+#define MTR_FASTA_END_TOOLONG 3
+typedef struct mtr_fasta_info { int32_t n_reads, end, bad_char, reserved; int64_t end_pos, n_bases, id_bytes; } mtr_fasta_info;
+typedef struct mtr_fasta_dst {
+    uint8_t *text;        /* [n_bases]                                        */
+    int64_t *offsets;     /* [n_reads]                                        */
+    int32_t *lens;        /* [n_reads]                                        */
+    uint8_t *ids;         /* [id_bytes]                                       */
+    int64_t *id_off;      /* [n_reads + 1]                                    */
+    int64_t  cap_text, cap_reads, cap_id_bytes;
+} mtr_fasta_dst;
+mtr_status mtr_parse_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream,
+                                  const mtr_fasta_dst *dst, mtr_fasta_info *info);
+mtr_status mtr_upload_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info);
+mtr_status mtr_fasta_index(const mtr_ctx *ctx, int32_t *lens, int64_t *id_off, char *ids);
+
 /* ---- wire form of the record table -------------------------------------------------------------------------------
  * A mtr_record is 2560 bytes because unit[] and unit_score[] are sized for MAX_PERIOD; a typical record uses 600.  The
  * wire form keeps what insert_an_alignment_into_set receives and nothing else, record after record:

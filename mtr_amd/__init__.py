@@ -1,8 +1,8 @@
 """mtr_amd — MI355X (gfx950) implementation of reference mTR's per-read hot path.
 
 Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointers).  Only the device-input and report methods
-(Engine.upload_device / process_device / export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes) take
-or return torch tensors;
+(Engine.upload_device / process_device / parse_fasta_device / upload_fasta_device / export_tensor / report_tensors /
+report_alignment_tensors / report_text / report_bytes) take or return torch tensors;
 they import torch when called.
 The product path is libmtr_hip.so only: importing works without a GPU, but creating an Engine
 without the library or without a HIP device raises — there is no CPU fallback.
@@ -20,6 +20,8 @@ LIB_PATH = os.environ.get("MTR_LIB", os.path.join(HERE, "libmtr_hip.so"))   # MT
 MAX_PERIOD = 500
 MAX_READ_LENGTH = 833333                     # MTR_MAX_READ_LENGTH
 TEXT_ASCII, TEXT_CODES = 0, 1                # MTR_TEXT_ASCII, MTR_TEXT_CODES
+FASTA_TILE_BYTES = 4096                      # MTR_FASTA_TILE_BYTES (mtr_amd/csrc/fasta.hip.inc): the bytes of a FASTA file one workgroup scans
+FASTA_END = {0: "eof", 1: "empty", 2: "bad", 3: "toolong"}        # MTR_FASTA_END_*
 
 STATUS = {0: "MTR_OK", 1: "MTR_ERR_NO_DEVICE", 2: "MTR_ERR_BAD_ARG", 3: "MTR_ERR_OOM", 4: "MTR_ERR_HIP",
           5: "MTR_ERR_OVERFLOW", 6: "MTR_ERR_DP_TOO_LARGE"}
@@ -41,7 +43,8 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_file_state_create", "mtr_file_state_destroy", "mtr_upload_batch_in_file", "mtr_file_state_skip",
            "mtr_get_bases_after_read", "mtr_upload_batch_packed", "mtr_fetch_results_packed", "mtr_export_packed_device",
            "mtr_unpack_records", "mtr_pack_records", "mtr_get_first_failed_read", "mtr_upload_batch_device",
-           "mtr_report_device", "mtr_test_chain", "mtr_report_alignments_device", "mtr_report_text_device", "mtr_test_report_lines"]
+           "mtr_report_device", "mtr_test_chain", "mtr_report_alignments_device", "mtr_report_text_device", "mtr_test_report_lines",
+           "mtr_parse_fasta_device", "mtr_upload_fasta_device", "mtr_fasta_index"]
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
 
@@ -127,6 +130,29 @@ class ReportText(NamedTuple):
     """mTR's stdout for a batch (Engine.report_text): B bytes, reads in input order, both tensors on the engine's device."""
     text: "object"        # uint8 [B]
     read_off: "object"    # int64 [n_reads + 1]: read i's bytes are text[read_off[i]:read_off[i + 1]]
+
+
+class CFastaInfo(C.Structure):
+    """mtr_fasta_info: what a FASTA file in device memory holds"""
+    _fields_ = [("n_reads", C.c_int32), ("end", C.c_int32), ("bad_char", C.c_int32), ("reserved", C.c_int32),
+                ("end_pos", C.c_int64), ("n_bases", C.c_int64), ("id_bytes", C.c_int64)]
+
+
+class CFastaDst(C.Structure):
+    """mtr_fasta_dst: device pointers of the parsed reads' columns and their capacities"""
+    _fields_ = [("text", C.c_void_p), ("offsets", C.c_void_p), ("lens", C.c_void_p), ("ids", C.c_void_p), ("id_off", C.c_void_p),
+                ("cap_text", C.c_int64), ("cap_reads", C.c_int64), ("cap_id_bytes", C.c_int64)]
+
+
+class Fasta(NamedTuple):
+    """The reads of a FASTA file parsed on the device (Engine.parse_fasta_device / upload_fasta_device): those before the stop."""
+    text: "object"        # uint8 [n_bases] on the engine's device: the reads' bases, the file's own bytes (None after upload_fasta_device)
+    offsets: "object"     # int64 numpy [n_reads]: read i is text[offsets[i]:offsets[i] + lens[i]]
+    lens: "object"        # int32 numpy [n_reads]
+    ids: list             # bytes per read: what its header holds behind '>'
+    end: str              # why the input ended: "eof", "empty" (a record without bases), "bad" (character), "toolong" (a record of 1 000 000 bases)
+    bad_char: "object"    # the character of end == "bad" as bytes, else None
+    end_pos: int          # the stop's position in the file (its length when the file ended)
 
 
 class CKernelTime(C.Structure):
@@ -219,6 +245,12 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_report_alignments_device.restype = C.c_int
     lib.mtr_report_text_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, P(CReportTextDst), P(C.c_int64)]
     lib.mtr_report_text_device.restype = C.c_int
+    lib.mtr_parse_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaDst), P(CFastaInfo)]
+    lib.mtr_parse_fasta_device.restype = C.c_int
+    lib.mtr_upload_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaInfo)]
+    lib.mtr_upload_fasta_device.restype = C.c_int
+    lib.mtr_fasta_index.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mtr_fasta_index.restype = C.c_int
     lib.mtr_test_report_lines.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [P(P(C.c_uint8)), P(P(C.c_int64))]
     lib.mtr_test_report_lines.restype = C.c_int
     lib.mtr_test_chain.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(P(C.c_int32)), P(P(C.c_int32))]
@@ -292,6 +324,28 @@ def device_input_args(text, offsets, lens, device: int):
     if text.device.index != device:
         raise MtrError(f"text is on {text.device}, the engine on cuda:{device}")
     return offs, ln
+
+
+def fasta_input_args(buf, device: int) -> None:
+    """The checks of Engine.parse_fasta_device / upload_fasta_device, made before the library is called: buf a contiguous 1-D
+    torch.uint8 tensor on cuda:device (the bytes of a FASTA file; it may be empty).  Raises MtrError."""
+    import torch
+
+    if not isinstance(buf, torch.Tensor):
+        raise MtrError(f"buf must be a torch.Tensor, got {type(buf).__name__}")
+    if buf.dtype != torch.uint8:
+        raise MtrError(f"buf must have dtype torch.uint8, got {buf.dtype}")
+    if buf.dim() != 1 or not buf.is_contiguous():
+        raise MtrError(f"buf must be a contiguous 1-D tensor, got shape {tuple(buf.shape)} strides {buf.stride()}")
+    if buf.device.type != "cuda":
+        raise MtrError(f"buf must be a GPU tensor, got a tensor on {buf.device}")
+    if buf.device.index != device:
+        raise MtrError(f"buf is on {buf.device}, the engine on cuda:{device}")
+
+
+def _fasta(info: CFastaInfo, text, offsets, lens, id_off, ids: bytes) -> Fasta:
+    return Fasta(text, offsets, lens, [ids[int(id_off[i]):int(id_off[i + 1])] for i in range(info.n_reads)], FASTA_END[info.end],
+                 bytes([info.bad_char & 0xFF]) if info.end == 2 else None, int(info.end_pos))
 
 
 def pack_ids(ids, n_reads: "int | None" = None):
@@ -381,6 +435,53 @@ class Engine:
         self._check(self.lib.mtr_upload_batch_device(self.h, C.c_void_p(text.data_ptr()), text.numel(), offs.ctypes.data, ln.ctypes.data, len(ln),
                                                      TEXT_CODES if codes else TEXT_ASCII, C.c_void_p(stream)), "mtr_upload_batch_device")
         self.n_reads = len(ln)
+
+    def parse_fasta_device(self, buf) -> Fasta:
+        """mtr_parse_fasta_device: the bytes of a FASTA file on the GPU parsed there, by the reference reader's rules.
+        buf: contiguous 1-D torch.uint8 tensor on this engine's device.  Returns a Fasta whose text is a fresh tensor on that
+        device (what upload_device takes) and whose index is on the host; the resident batch is not touched.  The library
+        waits for torch's current stream (where buf was written) by an event."""
+        import torch
+
+        fasta_input_args(buf, self.device)
+        dev = torch.device("cuda", self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        src = C.c_void_p(buf.data_ptr()) if buf.numel() else None
+        info = CFastaInfo()
+        self._check(self.lib.mtr_parse_fasta_device(self.h, src, buf.numel(), stream, None, C.byref(info)), "mtr_parse_fasta_device")
+        n, nb, ni = info.n_reads, int(info.n_bases), int(info.id_bytes)
+        text = torch.empty(nb, dtype=torch.uint8, device=dev)
+        offsets = torch.empty(n, dtype=torch.int64, device=dev)
+        lens = torch.empty(n, dtype=torch.int32, device=dev)
+        ids = torch.empty(ni, dtype=torch.uint8, device=dev)
+        id_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the tensors on its own stream: torch's earlier use of the memory is done
+        ptr = lambda t: t.data_ptr() if t.numel() else None     # noqa: E731
+        dst = CFastaDst(ptr(text), ptr(offsets), ptr(lens), ptr(ids), id_off.data_ptr(), nb, n, ni)
+        self._check(self.lib.mtr_parse_fasta_device(self.h, src, buf.numel(), stream, C.byref(dst), C.byref(info)), "mtr_parse_fasta_device")
+        return _fasta(info, text, offsets.cpu().numpy(), lens.cpu().numpy(), id_off.cpu().numpy(), ids.cpu().numpy().tobytes())
+
+    def upload_fasta_device(self, buf) -> Fasta:
+        """mtr_upload_fasta_device + mtr_fasta_index: the reads of a FASTA file on the GPU become the resident batch without a
+        host parser; run / fetch / report_* follow as after any upload, and the returned Fasta (text None) carries the ids
+        report_text takes.  A stop (end != "eof") does not refuse the upload: the reads before it are uploaded.  No reads: no
+        batch is uploaded."""
+        import torch
+
+        fasta_input_args(buf, self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+        info = CFastaInfo()
+        self.n_reads = 0
+        self._check(self.lib.mtr_upload_fasta_device(self.h, C.c_void_p(buf.data_ptr()) if buf.numel() else None, buf.numel(), stream, C.byref(info)),
+                    "mtr_upload_fasta_device")
+        n = info.n_reads
+        lens, id_off, ids = np.zeros(n, np.int32), np.zeros(n + 1, np.int64), np.zeros(max(int(info.id_bytes), 1), np.uint8)
+        self._check(self.lib.mtr_fasta_index(self.h, lens.ctypes.data, id_off.ctypes.data, ids.ctypes.data), "mtr_fasta_index")
+        offsets = np.zeros(n, np.int64)
+        if n > 1:
+            offsets[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+        self.n_reads = n
+        return _fasta(info, None, offsets, lens, id_off, ids.tobytes()[:int(info.id_bytes)])
 
     def process_device(self, text, offsets, lens, codes: bool = False) -> List[List[Record]]:
         """upload_device + run + fetch: per read its records in insertion order, as process() returns them"""

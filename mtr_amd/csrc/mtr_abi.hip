@@ -35,6 +35,7 @@
 #include "chain.hip.inc"
 #include "report_align.hip.inc"
 #include "report_text.hip.inc"
+#include "fasta.hip.inc"
 
 static_assert(sizeof(DevRecord) == sizeof(mtr_record), "device and ABI record layouts must agree");
 static_assert(MTR_N_COUNTERS == CNT_N, "counter count");
@@ -212,6 +213,12 @@ struct mtr_ctx {
     DevBuf<uint8_t> d_rt_ids; DevBuf<int64_t> d_rt_idoff, d_rt_bytes, d_rt_off, d_rt_rows;
     // the sizes of the last call (rt_ready; for rt_mode and the ID lengths rt_idoff): a sizes-only call followed by the writing call sizes once
     bool rt_ready = false; int32_t rt_mode = 0; int64_t rt_bytes = 0; std::vector<int64_t> rt_idoff;
+    // a FASTA file in device memory (fasta.hip.inc), per call: the tiles' columns, the header windows' columns, the IDs' offsets, the stop, the sizes
+    DevBuf<uint32_t> d_fa_tiles, d_fa_hbase; DevBuf<int32_t> d_fa_hpos, d_fa_hidlen; DevBuf<int64_t> d_fa_idoff;
+    DevBuf<unsigned long long> d_fa_event; DevBuf<mtr_fasta_info> d_fa_info;
+    // mtr_upload_fasta_device: the parsed reads on the device, and the host copies of their index (mtr_fasta_index)
+    DevBuf<uint8_t> d_fa_text, d_fa_ids; DevBuf<int64_t> d_fa_off; DevBuf<int32_t> d_fa_lens;
+    bool fa_indexed = false; std::vector<int32_t> fa_lens; std::vector<int64_t> fa_idoff; std::vector<char> fa_ids;
     // test entry points
     DevBuf<int32_t> d_t_i32, d_t_out; DevBuf<uint8_t> d_t_units, d_t_text; DevBuf<int64_t> d_t_i64;
 };
@@ -477,6 +484,27 @@ extern "C" mtr_status mtr_upload_batch_device(mtr_ctx *ctx, const uint8_t *d_tex
     return st;
 }
 
+// bytes .. of d must be device memory of the context's GPU, inside one allocation (what / what_bytes: the arguments' names in the reason)
+static mtr_status check_device_ptr(mtr_ctx *ctx, const uint8_t *d, int64_t bytes, const char *what, const char *what_bytes)
+{
+    hipPointerAttribute_t a;
+    const bool dev = hipPointerGetAttributes(&a, d) == hipSuccess && a.type == hipMemoryTypeDevice;
+    (void)hipGetLastError();                                             // (host memory unknown to HIP fails the query: not a sticky error)
+    if (!dev || a.device != ctx->device) {
+        ctx->err = dev ? std::string(what) + " is device memory of GPU " + std::to_string(a.device) + ", the context is on GPU " + std::to_string(ctx->device)
+                       : std::string(what) + " is not device memory";
+        return MTR_ERR_BAD_ARG;
+    }
+    hipDeviceptr_t base = nullptr; size_t size = 0;                       // the bytes must lie inside one allocation
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d) == hipSuccess && base &&
+        d + bytes > (const uint8_t *)base + size) {
+        ctx->err = std::string(what_bytes) + " " + std::to_string(bytes) + " runs past the end of " + what + "'s allocation";
+        return MTR_ERR_BAD_ARG;
+    }
+    (void)hipGetLastError();
+    return MTR_OK;
+}
+
 // the arguments of a device upload that the host can check (after free_batch: a refused upload leaves no batch behind)
 static mtr_status check_device_text(mtr_ctx *ctx, const DeviceText &dt, const int64_t *offsets, const int32_t *lens, int32_t n)
 {
@@ -489,22 +517,7 @@ static mtr_status check_device_text(mtr_ctx *ctx, const DeviceText &dt, const in
                        std::to_string(dt.bytes) + " bytes";
             return MTR_ERR_BAD_ARG;
         }
-    hipPointerAttribute_t a;
-    const bool dev = hipPointerGetAttributes(&a, dt.d) == hipSuccess && a.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();                                             // (host memory unknown to HIP fails the query: not a sticky error)
-    if (!dev || a.device != ctx->device) {
-        ctx->err = dev ? "d_text is device memory of GPU " + std::to_string(a.device) + ", the context is on GPU " + std::to_string(ctx->device)
-                       : std::string("d_text is not device memory");
-        return MTR_ERR_BAD_ARG;
-    }
-    hipDeviceptr_t base = nullptr; size_t size = 0;                       // the text must lie inside one allocation
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)dt.d) == hipSuccess && base &&
-        (const uint8_t *)dt.d + dt.bytes > (const uint8_t *)base + size) {
-        ctx->err = "text_bytes " + std::to_string(dt.bytes) + " runs past the end of d_text's allocation";
-        return MTR_ERR_BAD_ARG;
-    }
-    (void)hipGetLastError();
-    return MTR_OK;
+    return check_device_ptr(ctx, dt.d, dt.bytes, "d_text", "text_bytes");
 }
 
 static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t *packed_in, int64_t n_words_in, const int64_t *woff_in,
@@ -1719,6 +1732,148 @@ extern "C" mtr_status mtr_report_text_device(mtr_ctx *ctx, const char *ids, cons
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- a FASTA file in device memory (fasta.hip.inc) -----------------------------------------------------------------------------
+// Only the header count, the sizes and - for an upload - the reads' lengths, offsets and IDs come back to the host.
+struct FastaParse { FastaArgs a; int32_t n_heads; mtr_fasta_info info; };
+
+static void fasta_no_reads(mtr_fasta_info *info) { memset(info, 0, sizeof *info); info->end = MTR_FASTA_END_EMPTY; }
+
+// the arguments' checks and the scans, up to the sizes (p.info) and the header windows' columns on the device
+static mtr_status fasta_index(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, FastaParse &p)
+{
+    if (!d_fasta) { ctx->err = "d_fasta is NULL"; return MTR_ERR_BAD_ARG; }
+    if (n_bytes < 0 || n_bytes > (int64_t)INT32_MAX) {
+        ctx->err = "n_bytes " + std::to_string(n_bytes) + " outside 0.." + std::to_string(INT32_MAX) + " (a larger file goes in parts cut at record starts)";
+        return MTR_ERR_BAD_ARG;
+    }
+    { mtr_status st = check_device_ptr(ctx, d_fasta, n_bytes, "d_fasta", "n_bytes"); if (st != MTR_OK) return st; }
+    const int32_t n_tiles = (int32_t)((n_bytes + MTR_FASTA_TILE_BYTES - 1) / MTR_FASTA_TILE_BYTES);
+    const size_t nt = (size_t)n_tiles;
+    HIPCHK(ctx->d_fa_tiles.ensure((7 * nt + 2) * 4)); HIPCHK(ctx->d_fa_event.ensure(8)); HIPCHK(ctx->d_fa_info.ensure(sizeof(mtr_fasta_info)));
+    FastaArgs &a = p.a;
+    a = FastaArgs{};
+    a.fa = d_fasta; a.n = (int32_t)n_bytes; a.n_tiles = n_tiles;
+    uint32_t *t = ctx->d_fa_tiles;
+    a.t_nl = t; a.t_term = t + nt; a.t_cnt = t + 2 * nt; a.t_last = t + 3 * nt; a.t_base = t + 4 * nt; a.t_hdr = t + 5 * nt; a.t_rs = t + 6 * nt;
+    a.totals = t + 7 * nt; a.event = ctx->d_fa_event;
+    // the file comes from the caller's stream: the kernels wait for it there, not for the whole device
+    if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ctx->ev_text, (hipStream_t)wait_stream));
+    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
+    HIPCHK(hipMemsetAsync(ctx->d_fa_event, 0xff, 8, ctx->stream));
+    hipLaunchKernelGGL(mtr_k_fasta_lines, dim3((unsigned)n_tiles), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, a);
+    hipLaunchKernelGGL(mtr_k_fasta_scan_lines, dim3(1), dim3(MTR_FASTA_SCAN_BLOCK), 0, ctx->stream, a);
+    hipLaunchKernelGGL(mtr_k_fasta_tile<0>, dim3((unsigned)n_tiles), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, a);
+    hipLaunchKernelGGL(mtr_k_fasta_scan_counts, dim3(1), dim3(MTR_FASTA_SCAN_BLOCK), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    uint32_t totals[2] = { 0, 0 };
+    HIPCHK(copy_sync(ctx, totals, a.totals, 8, hipMemcpyDeviceToHost));
+    p.n_heads = (int32_t)std::max<uint32_t>(totals[1], 1u);       // a file without a header has one record, its ID ""
+    const size_t nh = (size_t)p.n_heads;
+    HIPCHK(ctx->d_fa_hpos.ensure(nh * 4)); HIPCHK(ctx->d_fa_hbase.ensure(nh * 4)); HIPCHK(ctx->d_fa_hidlen.ensure(nh * 4)); HIPCHK(ctx->d_fa_idoff.ensure((nh + 1) * 8));
+    a.h_pos = ctx->d_fa_hpos; a.h_base = ctx->d_fa_hbase; a.h_idlen = ctx->d_fa_hidlen; a.n_heads = (uint32_t)p.n_heads;
+    HIPCHK(hipMemsetAsync(a.h_pos, 0, nh * 4, ctx->stream)); HIPCHK(hipMemsetAsync(a.h_base, 0, nh * 4, ctx->stream)); HIPCHK(hipMemsetAsync(a.h_idlen, 0, nh * 4, ctx->stream));
+    hipLaunchKernelGGL(mtr_k_fasta_tile<1>, dim3((unsigned)n_tiles), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, a);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.h_idlen, (int64_t)p.n_heads, (int64_t *)ctx->d_fa_idoff);
+    hipLaunchKernelGGL(mtr_k_fasta_finish, dim3(1), dim3(64), 0, ctx->stream, a, p.n_heads, (const int64_t *)ctx->d_fa_idoff, (mtr_fasta_info *)ctx->d_fa_info);
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(ctx, &p.info, ctx->d_fa_info, sizeof(mtr_fasta_info), hipMemcpyDeviceToHost));
+    return MTR_OK;
+}
+
+// the columns of the reads before the stop into dst (capacities checked by the caller; dst.id_off may be NULL); enqueues only
+static mtr_status fasta_write(mtr_ctx *ctx, const FastaParse &p, const mtr_fasta_dst &dst)
+{
+    const mtr_fasta_info &f = p.info;
+    if (dst.id_off) HIPCHK(hipMemcpyAsync(dst.id_off, ctx->d_fa_idoff, ((size_t)f.n_reads + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    if (f.n_reads <= 0) return MTR_OK;
+    FastaArgs a = p.a;
+    a.text = dst.text; a.n_bases = (uint32_t)f.n_bases;
+    const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)f.n_reads + 255) / 256, (int64_t)ctx->n_cu * 8);
+    hipLaunchKernelGGL(mtr_k_fasta_reads, dim3(blocks), dim3(256), 0, ctx->stream, a, p.n_heads, f.n_reads, dst.offsets, dst.lens);
+    if (f.id_bytes > 0)
+        hipLaunchKernelGGL(mtr_k_fasta_ids, dim3((unsigned)std::min<int64_t>(f.n_reads, (int64_t)ctx->n_cu * 32)), dim3(64), 0, ctx->stream, a, f.n_reads,
+                           (const int64_t *)ctx->d_fa_idoff, dst.ids);
+    // every base of a reported read lies before the stop: the tiles behind it hold none
+    const int64_t upto = std::min<int64_t>(f.end_pos, (int64_t)a.n);
+    const unsigned tiles = (unsigned)((upto + MTR_FASTA_TILE_BYTES - 1) / MTR_FASTA_TILE_BYTES);
+    if (tiles > 0) hipLaunchKernelGGL(mtr_k_fasta_tile<2>, dim3(tiles), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_parse_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, const mtr_fasta_dst *dst,
+                                             mtr_fasta_info *info)
+{
+    if (!ctx || !info) return MTR_ERR_BAD_ARG;
+    fasta_no_reads(info);
+    HIPCHK(hipSetDevice(ctx->device));
+    if (n_bytes == 0) {                                           // an empty file: no reads, and no byte to look at
+        if (dst && dst->id_off) { HIPCHK(hipMemsetAsync(dst->id_off, 0, 8, ctx->stream)); HIPCHK(hipStreamSynchronize(ctx->stream)); }
+        return MTR_OK;
+    }
+    FastaParse p;
+    { mtr_status st = fasta_index(ctx, d_fasta, n_bytes, wait_stream, p); if (st != MTR_OK) return st; }
+    *info = p.info;
+    if (!dst) return MTR_OK;
+    const mtr_fasta_info &f = p.info;
+    if (dst->cap_text < f.n_bases || dst->cap_reads < f.n_reads || dst->cap_id_bytes < f.id_bytes) {
+        ctx->err = "destination holds " + std::to_string(dst->cap_text) + " bases, " + std::to_string(dst->cap_reads) + " reads, " + std::to_string(dst->cap_id_bytes) +
+                   " ID bytes; " + std::to_string(f.n_bases) + ", " + std::to_string(f.n_reads) + ", " + std::to_string(f.id_bytes) + " needed";
+        return MTR_ERR_OVERFLOW;
+    }
+    if (!dst->id_off || (f.n_reads > 0 && (!dst->text || !dst->offsets || !dst->lens)) || (f.id_bytes > 0 && !dst->ids)) {
+        ctx->err = "a destination column is NULL";
+        return MTR_ERR_BAD_ARG;
+    }
+    { mtr_status st = fasta_write(ctx, p, *dst); if (st != MTR_OK) return st; }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_upload_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info)
+{
+    if (!ctx || !info) return MTR_ERR_BAD_ARG;
+    fasta_no_reads(info);
+    HIPCHK(hipSetDevice(ctx->device));
+    { mtr_status w = mtr_wait(ctx); if (w != MTR_OK && w != MTR_ERR_OVERFLOW && w != MTR_ERR_DP_TOO_LARGE) return w; }
+    free_batch(ctx);                                              // whatever happens below, the batch before this call is gone
+    ctx->fa_indexed = false;
+    FastaParse p; p.info = *info;
+    if (n_bytes != 0) { mtr_status st = fasta_index(ctx, d_fasta, n_bytes, wait_stream, p); if (st != MTR_OK) return st; }
+    *info = p.info;
+    const mtr_fasta_info &f = p.info;
+    const size_t n = (size_t)f.n_reads;
+    std::vector<int64_t> offs(n);
+    ctx->fa_lens.assign(n, 0); ctx->fa_idoff.assign(n + 1, 0); ctx->fa_ids.assign((size_t)f.id_bytes, 0);
+    if (n > 0) {
+        HIPCHK(ctx->d_fa_text.ensure((size_t)f.n_bases + 16)); HIPCHK(ctx->d_fa_off.ensure(n * 8)); HIPCHK(ctx->d_fa_lens.ensure(n * 4));
+        HIPCHK(ctx->d_fa_ids.ensure((size_t)f.id_bytes + 16));
+        mtr_fasta_dst dst = { ctx->d_fa_text, ctx->d_fa_off, ctx->d_fa_lens, ctx->d_fa_ids, nullptr, f.n_bases, f.n_reads, f.id_bytes };
+        { mtr_status st = fasta_write(ctx, p, dst); if (st != MTR_OK) return st; }
+        HIPCHK(hipMemcpyAsync(offs.data(), ctx->d_fa_off, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->fa_lens.data(), ctx->d_fa_lens, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->fa_idoff.data(), ctx->d_fa_idoff, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (f.id_bytes > 0) HIPCHK(hipMemcpyAsync(ctx->fa_ids.data(), ctx->d_fa_ids, (size_t)f.id_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    ctx->fa_indexed = true;
+    if (n == 0) return MTR_OK;                                    // no reads: nothing to upload
+    const DeviceText dt = { ctx->d_fa_text, f.n_bases, MTR_TEXT_ASCII, ctx->stream };
+    const mtr_status st = upload_batch(ctx, nullptr, nullptr, 0, nullptr, nullptr, offs.data(), ctx->fa_lens.data(), f.n_reads, &dt);
+    if (st != MTR_OK) { ctx->fa_indexed = false; if (!ctx->pending) free_batch(ctx); }       // as a refused mtr_upload_batch_device: no batch is left
+    return st;
+}
+
+extern "C" mtr_status mtr_fasta_index(const mtr_ctx *ctx, int32_t *lens, int64_t *id_off, char *ids)
+{
+    if (!ctx || !ctx->fa_indexed) return MTR_ERR_BAD_ARG;
+    if (lens && !ctx->fa_lens.empty()) memcpy(lens, ctx->fa_lens.data(), ctx->fa_lens.size() * 4);
+    if (id_off) memcpy(id_off, ctx->fa_idoff.data(), ctx->fa_idoff.size() * 8);
+    if (ids && !ctx->fa_ids.empty()) memcpy(ids, ctx->fa_ids.data(), ctx->fa_ids.size());
     return MTR_OK;
 }
 

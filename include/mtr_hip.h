@@ -150,8 +150,8 @@ mtr_status mtr_upload_batch_packed(mtr_ctx *ctx, const uint32_t *packed, int64_t
 ', a code > 3) is MTR_ERR_BAD_ARG, and mtr_last_error names
  * the first such read.  So are d_text that is not device memory of the context's GPU, a read outside text_bytes, an unknown
  * text_kind.  A refused upload leaves no batch uploaded, as a refused mtr_upload_batch does; run / fetch / export / alignments
- * work after a device upload as after a host one.  File-order mode (mtr_upload_batch_in_file) needs the bases on the host:
- * there is no device variant of it. */
+ * work after a device upload as after a host one.  File-order mode for reads in device memory: mtr_upload_batch_device_in_file
+ * (below, with mtr_file_state). */
 #define MTR_TEXT_ASCII 0
 #define MTR_TEXT_CODES 1
 mtr_status mtr_upload_batch_device(mtr_ctx *ctx, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
@@ -180,8 +180,8 @@ mtr_status mtr_upload_batch_device(mtr_ctx *ctx, const uint8_t *d_text, int64_t 
  * mtr_upload_fasta_device parses into buffers of the context and makes the reads the resident batch as mtr_upload_batch_device
  * does.  A stop does not refuse the upload: the reads before it are uploaded, as the command line prints the reads before a bad
  * record.  No reads: MTR_OK and no batch uploaded.  A read longer than MTR_MAX_READ_LENGTH: MTR_ERR_BAD_ARG naming the read, no
- * batch uploaded.  run / fetch / export / alignments / report work afterwards as after any upload.  File-order mode needs the
- * bases on the host: there is no FASTA variant of it.
+ * batch uploaded.  run / fetch / export / alignments / report work afterwards as after any upload.  File-order mode for a file in device
+ * memory: mtr_upload_fasta_device_in_file (below, with mtr_file_state).
  * mtr_fasta_index: HOST copies of the last mtr_upload_fasta_device's index - lens[n_reads], id_off[n_reads + 1], ids[id_bytes] (what
  * mtr_report_text_device takes); a NULL array is skipped.  MTR_ERR_BAD_ARG before any such upload. */
 #define MTR_FASTA_END_EOF 0
@@ -330,7 +330,7 @@ mtr_status mtr_gather_get_stats(const mtr_gather *g, int64_t *out, int32_t n);
  * isolated semantics.  The reference's inputString_w_rand and orgInputString live for the whole file
  * (handle_one_file.c:85, mTR.h:65-67): the window look-ahead of a read (fill_directional_index.c:232) and the one-past
  * reads of its DPs (wrap_around_DP.c:243-245) see what the most recent LONGER read left beyond the part the current
- * read rewrites.  A mtr_file_state is the host shadow of that state for ONE file; give it the batches of the file in
+ * read rewrites.  A mtr_file_state is the shadow of that state for ONE file; give it the batches of the file in
  * file order (any context, any batch size — the state carries over) through mtr_upload_batch_in_file instead of
  * mtr_upload_batch, then run / fetch as usual.  Results then equal the reference run on the whole file at the lower
  * edge (the arguments of insert_an_alignment_into_set, read after read); the printed chain can still differ where two
@@ -345,6 +345,25 @@ mtr_status mtr_upload_batch_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint
                                     const int32_t *lens, int32_t n_reads);
 /* advance the state over reads that another context / GPU processes (same arguments as an upload, no device work) */
 mtr_status mtr_file_state_skip(mtr_file_state *fs, const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n_reads);
+
+/* File-order mode for reads that are already in DEVICE memory: the same state fed from the device.  The arguments, the checks and
+ * the stream protocol are those of mtr_upload_batch_device / mtr_upload_fasta_device; fs == NULL is MTR_ERR_BAD_ARG.  The stale
+ * tails and the two bases after each read are made by kernels (mtr_amd/csrc/file_order.hip.inc) from the packed words of the reads
+ * that left them; the results equal those of mtr_upload_batch_in_file on the same reads, and no base crosses to the host.
+ * A state fed this way keeps the lengths of its stairs on the host and their 2-bit words in device memory that it owns, on the
+ * GPU of the first context that fed it (mtr_file_state_destroy frees it there).  A state is host-fed or device-fed, fixed by its
+ * first feed: the other kind of call on it, or a context on another GPU, is MTR_ERR_BAD_ARG with the reason in mtr_last_error
+ * (mtr_file_state_skip has no context: the status alone).  A refused upload - a byte that is no base, a bad argument, a FASTA read
+ * longer than MTR_MAX_READ_LENGTH - leaves no batch uploaded and the state exactly as it was.  A FASTA stop uploads the reads before
+ * it and the state advances over those; no reads: no batch, the state unchanged.
+ * mtr_file_state_skip_device advances the state over reads in device memory that another GPU processes: they are packed and checked
+ * into the state's storage; no batch is uploaded and the context's resident batch stays as it is.  n_reads == 0 is MTR_OK. */
+mtr_status mtr_upload_batch_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
+                                           const int32_t *lens, int32_t n_reads, int32_t text_kind, void *wait_stream);
+mtr_status mtr_upload_fasta_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream,
+                                           mtr_fasta_info *info);
+mtr_status mtr_file_state_skip_device(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
+                                      const int32_t *lens, int32_t n_reads, int32_t text_kind, void *wait_stream);
 
 /* orgInputString[L] and [L+1] as read i of the resident batch found them: 0 under isolated semantics, in file-order mode
  * the bases an earlier, longer read left there.  A repeat can end on them (wrap_around_DP.c:243-245), and a printer of

@@ -48,6 +48,13 @@ mtr_status mtr_test_chain(mtr_ctx *ctx, int32_t n_sets, const int64_t *set_off, 
 mtr_status mtr_test_report_lines(mtr_ctx *ctx, int32_t n_rows, const int32_t *fields, const int32_t *read_len, const uint8_t *units,
                                  const int64_t *unit_off, const char *ids, const int64_t *id_off, uint8_t **out_text, int64_t **out_off);
 
+/* What file-order mode gave the resident batch, after a host (mtr_upload_batch_in_file) or a device (mtr_upload_batch_device_in_file,
+ * mtr_upload_fasta_device_in_file) upload: read i's stale entries of inputString_w_rand are (*out_tail)[(*out_tail_off)[i] ..
+ * (*out_tail_off)[i + 1]) (out_tail_off has n_reads + 1 entries), its orgInputString[L], [L + 1] are (*out_after)[2i], [2i + 1].
+ * After an isolated upload: empty tails and zeros.  The arrays are malloc'ed; free() them.  Afterwards id 0 of
+ * mtr_get_kernel_times is the tail kernel (mtr_k_file_tail) of that upload: launches = 0 after a host upload or with no entry. */
+mtr_status mtr_test_file_tail(mtr_ctx *ctx, uint16_t **out_tail, int64_t **out_tail_off, uint8_t **out_after);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,7 +44,8 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_get_bases_after_read", "mtr_upload_batch_packed", "mtr_fetch_results_packed", "mtr_export_packed_device",
            "mtr_unpack_records", "mtr_pack_records", "mtr_get_first_failed_read", "mtr_upload_batch_device",
            "mtr_report_device", "mtr_test_chain", "mtr_report_alignments_device", "mtr_report_text_device", "mtr_test_report_lines",
-           "mtr_parse_fasta_device", "mtr_upload_fasta_device", "mtr_fasta_index"]
+           "mtr_parse_fasta_device", "mtr_upload_fasta_device", "mtr_fasta_index",
+           "mtr_upload_batch_device_in_file", "mtr_upload_fasta_device_in_file", "mtr_file_state_skip_device", "mtr_test_file_tail"]
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
 
@@ -53,7 +54,9 @@ class MtrError(RuntimeError):
 
 
 class FileState:
-    """mtr_file_state: host shadow of what the reads of ONE file leave behind for the reads after them (file-order mode)."""
+    """mtr_file_state: what the reads of ONE file leave behind for the reads after them (file-order mode).  Its first feed fixes
+    its kind: host reads (Engine.upload / skip) or reads in device memory (Engine.upload_device / upload_fasta_device /
+    skip_device), whose bases it keeps on that GPU."""
 
     def __init__(self):
         self.lib = load_library()
@@ -68,6 +71,16 @@ class FileState:
         st = self.lib.mtr_file_state_skip(self.h, bases.ctypes.data, offs.ctypes.data, lens.ctypes.data, len(reads))
         if st != 0:
             raise MtrError(f"mtr_file_state_skip: {STATUS.get(st, st)}")
+
+    def skip_device(self, engine: "Engine", text, offsets, lens, codes: bool = False):
+        """mtr_file_state_skip_device: the state advances over reads in device memory (text, offsets, lens, codes as
+        Engine.upload_device takes them) that another GPU processes; engine's resident batch is not touched."""
+        import torch
+
+        offs, ln = device_input_args(text, offsets, lens, engine.device)
+        stream = torch.cuda.current_stream(text.device).cuda_stream
+        engine._check(self.lib.mtr_file_state_skip_device(engine.h, self.h, C.c_void_p(text.data_ptr()), text.numel(), offs.ctypes.data, ln.ctypes.data,
+                                                          len(ln), TEXT_CODES if codes else TEXT_ASCII, C.c_void_p(stream)), "mtr_file_state_skip_device")
 
     def close(self):
         if self.h:
@@ -249,6 +262,14 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_parse_fasta_device.restype = C.c_int
     lib.mtr_upload_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaInfo)]
     lib.mtr_upload_fasta_device.restype = C.c_int
+    lib.mtr_upload_batch_device_in_file.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.mtr_upload_batch_device_in_file.restype = C.c_int
+    lib.mtr_upload_fasta_device_in_file.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaInfo)]
+    lib.mtr_upload_fasta_device_in_file.restype = C.c_int
+    lib.mtr_file_state_skip_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.mtr_file_state_skip_device.restype = C.c_int
+    lib.mtr_test_file_tail.argtypes = [C.c_void_p, P(P(C.c_uint16)), P(P(C.c_int64)), P(P(C.c_uint8))]
+    lib.mtr_test_file_tail.restype = C.c_int
     lib.mtr_fasta_index.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mtr_fasta_index.restype = C.c_int
     lib.mtr_test_report_lines.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [P(P(C.c_uint8)), P(P(C.c_int64))]
@@ -422,18 +443,25 @@ class Engine:
         self._check(self.lib.mtr_upload_batch(self.h, bases.ctypes.data, offs.ctypes.data, lens.ctypes.data, len(lens)), "mtr_upload_batch")
         self.n_reads = len(lens)
 
-    def upload_device(self, text, offsets, lens, codes: bool = False):
+    def upload_device(self, text, offsets, lens, codes: bool = False, file_state: "FileState | None" = None):
         """mtr_upload_batch_device: reads as text already on the GPU, packed there by a kernel.
         text: contiguous 1-D torch.uint8 tensor on this engine's device, one byte per base - 'ACGT'/'acgt' (codes=False) or
         0..3 (codes=True); offsets / lens: host int64 / int32 arrays (numpy or CPU tensors).  The library waits for torch's
-        current stream (where text was written) by an event; text may be reused once this returns."""
+        current stream (where text was written) by an event; text may be reused once this returns.
+        file_state: the reads are the next reads of that file (file-order mode, mtr_upload_batch_device_in_file): the state is
+        fed from device memory and keeps its bases there."""
         import torch
 
         offs, ln = device_input_args(text, offsets, lens, self.device)
         stream = torch.cuda.current_stream(text.device).cuda_stream
         self.n_reads = 0
-        self._check(self.lib.mtr_upload_batch_device(self.h, C.c_void_p(text.data_ptr()), text.numel(), offs.ctypes.data, ln.ctypes.data, len(ln),
-                                                     TEXT_CODES if codes else TEXT_ASCII, C.c_void_p(stream)), "mtr_upload_batch_device")
+        if file_state is None:
+            self._check(self.lib.mtr_upload_batch_device(self.h, C.c_void_p(text.data_ptr()), text.numel(), offs.ctypes.data, ln.ctypes.data, len(ln),
+                                                         TEXT_CODES if codes else TEXT_ASCII, C.c_void_p(stream)), "mtr_upload_batch_device")
+        else:
+            self._check(self.lib.mtr_upload_batch_device_in_file(self.h, file_state.h, C.c_void_p(text.data_ptr()), text.numel(), offs.ctypes.data,
+                                                                 ln.ctypes.data, len(ln), TEXT_CODES if codes else TEXT_ASCII, C.c_void_p(stream)),
+                        "mtr_upload_batch_device_in_file")
         self.n_reads = len(ln)
 
     def parse_fasta_device(self, buf) -> Fasta:
@@ -461,19 +489,24 @@ class Engine:
         self._check(self.lib.mtr_parse_fasta_device(self.h, src, buf.numel(), stream, C.byref(dst), C.byref(info)), "mtr_parse_fasta_device")
         return _fasta(info, text, offsets.cpu().numpy(), lens.cpu().numpy(), id_off.cpu().numpy(), ids.cpu().numpy().tobytes())
 
-    def upload_fasta_device(self, buf) -> Fasta:
+    def upload_fasta_device(self, buf, file_state: "FileState | None" = None) -> Fasta:
         """mtr_upload_fasta_device + mtr_fasta_index: the reads of a FASTA file on the GPU become the resident batch without a
         host parser; run / fetch / report_* follow as after any upload, and the returned Fasta (text None) carries the ids
         report_text takes.  A stop (end != "eof") does not refuse the upload: the reads before it are uploaded.  No reads: no
-        batch is uploaded."""
+        batch is uploaded.  file_state: the reads are the next reads of that file (file-order mode,
+        mtr_upload_fasta_device_in_file); the state advances over the uploaded reads."""
         import torch
 
         fasta_input_args(buf, self.device)
         stream = C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
         info = CFastaInfo()
         self.n_reads = 0
-        self._check(self.lib.mtr_upload_fasta_device(self.h, C.c_void_p(buf.data_ptr()) if buf.numel() else None, buf.numel(), stream, C.byref(info)),
-                    "mtr_upload_fasta_device")
+        src = C.c_void_p(buf.data_ptr()) if buf.numel() else None
+        if file_state is None:
+            self._check(self.lib.mtr_upload_fasta_device(self.h, src, buf.numel(), stream, C.byref(info)), "mtr_upload_fasta_device")
+        else:
+            self._check(self.lib.mtr_upload_fasta_device_in_file(self.h, file_state.h, src, buf.numel(), stream, C.byref(info)),
+                        "mtr_upload_fasta_device_in_file")
         n = info.n_reads
         lens, id_off, ids = np.zeros(n, np.int32), np.zeros(n + 1, np.int64), np.zeros(max(int(info.id_bytes), 1), np.uint8)
         self._check(self.lib.mtr_fasta_index(self.h, lens.ctypes.data, id_off.ctypes.data, ids.ctypes.data), "mtr_fasta_index")
@@ -483,9 +516,9 @@ class Engine:
         self.n_reads = n
         return _fasta(info, None, offsets, lens, id_off, ids.tobytes()[:int(info.id_bytes)])
 
-    def process_device(self, text, offsets, lens, codes: bool = False) -> List[List[Record]]:
-        """upload_device + run + fetch: per read its records in insertion order, as process() returns them"""
-        self.upload_device(text, offsets, lens, codes)
+    def process_device(self, text, offsets, lens, codes: bool = False, file_state: "FileState | None" = None) -> List[List[Record]]:
+        """upload_device + run + fetch: per read its records in insertion order, as process() (file_state: process_in_file()) returns them"""
+        self.upload_device(text, offsets, lens, codes, file_state)
         self.run()
         return self.fetch()
 
@@ -757,6 +790,24 @@ class Engine:
         for ptr in (pc, ps, pe, pw, pd):
             _libc.free(C.cast(ptr, C.c_void_p))
         return out
+
+    def test_file_tail(self):
+        """mtr_test_file_tail: what file-order mode gave the resident batch - (tail uint16, tail_off int64 [n + 1], after uint8 [n, 2]):
+        read i's stale entries of inputString_w_rand are tail[tail_off[i]:tail_off[i + 1]], after[i] its orgInputString[L], [L + 1].
+        Empty tails and zeros after an isolated upload."""
+        P = C.POINTER
+        tl, to, af = P(C.c_uint16)(), P(C.c_int64)(), P(C.c_uint8)()
+        self._check(self.lib.mtr_test_file_tail(self.h, C.byref(tl), C.byref(to), C.byref(af)), "mtr_test_file_tail")
+        n = self.n_reads
+        try:
+            tail_off = np.ctypeslib.as_array(to, shape=(n + 1,)).copy()
+            m = int(tail_off[n])
+            tail = np.ctypeslib.as_array(tl, shape=(m,)).copy() if m else np.zeros(0, np.uint16)
+            after = np.ctypeslib.as_array(af, shape=(n, 2)).copy()
+        finally:
+            for a in (tl, to, af):
+                _libc.free(C.cast(a, C.c_void_p))
+        return tail, tail_off, after
 
     def test_wrap_dp(self, tasks):
         """tasks: list of (read_idx, qs, qe, unit codes, G, MM, D) -> int32 [n,8] as wrap_around_DP_sub returns."""

@@ -36,6 +36,7 @@
 #include "report_align.hip.inc"
 #include "report_text.hip.inc"
 #include "fasta.hip.inc"
+#include "file_order.hip.inc"
 
 static_assert(sizeof(DevRecord) == sizeof(mtr_record), "device and ABI record layouts must agree");
 static_assert(MTR_N_COUNTERS == CNT_N, "counter count");
@@ -186,6 +187,7 @@ struct mtr_ctx {
     bool sub_active = false;                           // launch_reads works on ovf_reads with the overflow buffers
     // file-order mode (mtr_upload_batch_in_file): per read the stale tail of the reference's inputString_w_rand
     bool file_order = false; DevBuf<uint16_t> d_tail; DevBuf<int64_t> d_tail_off;
+    int64_t tail_entries = 0; float fo_tail_ms = 0; int fo_tail_launches = 0;    // of the resident batch; mtr_k_file_tail's device time (mtr_test_file_tail)
     std::vector<uint8_t> after;                        // 2 per read: orgInputString[L], [L+1] (zeros unless file-order)
     mtr_kernel_time kt[MTR_N_KERNEL_TIMES] = {};
     unsigned long long counters[CNT_N] = { 0 };
@@ -199,6 +201,9 @@ struct mtr_ctx {
     DevBuf<int32_t> d_al_i32, d_al_len, d_al_ends; DevBuf<uint8_t> d_al_units, d_al_ops; DevBuf<int64_t> d_al_off;
     // device input (mtr_upload_batch_device): per read its text offset, the first read with a byte that is no base, the caller's stream's event
     DevBuf<int64_t> d_toff; DevBuf<int32_t> d_pack_bad; hipEvent_t ev_text = nullptr;
+    // file-order mode for device input (file_order.hip.inc): the tails' segments, the owners of the two bases after each read, those bases;
+    // mtr_file_state_skip_device: the skipped reads' lengths and word offsets (the resident batch keeps its own)
+    DevBuf<FoSeg> d_fo_segs; DevBuf<FoAfter> d_fo_own; DevBuf<uint8_t> d_after; DevBuf<int32_t> d_fo_lens; DevBuf<int64_t> d_fo_woff;
     // mTR's report on the device (mtr_report_device): the chains of the resident batch, made once per batch (rep_ready), and
     // their column layout: per read the chain length, its units' bytes, and the offsets of its records / chain / scratch / columns
     bool rep_ready = false; int64_t rep_total = 0, rep_unit_bytes = 0;
@@ -240,11 +245,21 @@ static const std::vector<uint8_t> &mt_host()
 // k = 1, 3, 5, so it LEAVES the k = 5 encoding) and [0, L) of the second; the passes of the next read look up to
 // L + r + 2w - k (:232) and its DPs up to org[L + 1], i.e. into what the most recent LONGER read left there.
 // That state is a staircase: of all earlier reads only those longer than every read after them still show.
+//
+// A state is fed either from the host (mtr_upload_batch_in_file, mtr_file_state_skip: every stair keeps its base codes here) or from
+// device memory (mtr_upload_batch_device_in_file, mtr_upload_fasta_device_in_file, mtr_file_state_skip_device).  A device-fed state
+// keeps the stairs' geometry here - lengths only - and their 2-bit words in device memory of its own (d_store): a stack like the
+// staircase itself, stair k at words [woff, woff + mtr_packed_words(L)), so the survivors of a batch are a prefix of it and the
+// new stairs are appended, device to device, from the batch's packed image.  Its bases never reach the host.
 struct mtr_file_state {
-    struct Entry { int32_t L = 0, r = 0; int64_t N = 0, n = 0, E = 0; std::vector<uint8_t> codes; };
+    struct Entry { int32_t L = 0, r = 0; int64_t N = 0, n = 0, E = 0; std::vector<uint8_t> codes; int64_t woff = 0; };
+    enum Kind { UNFED = 0, HOST_FED = 1, DEVICE_FED = 2 };
     std::vector<Entry> stairs;               // E (and L) strictly increasing from back() = most recent to front()
     std::vector<uint8_t> mt;                 // the MT19937 base stream (same as the device's)
     int64_t reads_seen = 0;
+    int kind = UNFED, device = -1;           // fixed by the first feed; device: the GPU of the context that fed it
+    uint32_t *d_store = nullptr; int64_t store_cap = 0;      // device-fed: the stairs' words, capacity in words
+    int64_t store_top() const { return stairs.empty() ? 0 : stairs.back().woff + mtr_packed_words(stairs.back().L); }
     int raw(const Entry &e, int64_t q) const
     {   // the buffer before the rolling encode, as k1_raw (k1_ranges.hip.inc)
         if (q < e.r) return mt[(size_t)(e.N + q)];
@@ -290,7 +305,7 @@ struct mtr_file_state {
         while (!stairs.empty() && stairs.back().L <= L) stairs.pop_back();
         e.codes.assign(codes, codes + L);
         stairs.push_back(std::move(e));
-        reads_seen++;
+        reads_seen++; kind = HOST_FED;
     }
 };
 
@@ -303,10 +318,15 @@ extern "C" mtr_status mtr_file_state_create(mtr_file_state **out)
     *out = fs;
     return MTR_OK;
 }
-extern "C" void mtr_file_state_destroy(mtr_file_state *fs) { delete fs; }
+extern "C" void mtr_file_state_destroy(mtr_file_state *fs)
+{
+    if (fs && fs->d_store) { (void)hipSetDevice(fs->device); (void)hipFree(fs->d_store); }
+    delete fs;
+}
 extern "C" mtr_status mtr_file_state_skip(mtr_file_state *fs, const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n)
 {
     if (!fs || !bases || !offsets || !lens || n < 0) return MTR_ERR_BAD_ARG;
+    if (fs->kind == mtr_file_state::DEVICE_FED) return MTR_ERR_BAD_ARG;          // (no context to leave a reason in)
     for (int i = 0; i < n; i++) {
         if (lens[i] <= 0 || lens[i] > MTRC_MAX_SUPPORTED_LENGTH) return MTR_ERR_BAD_ARG;
         fs->push(bases + offsets[i], lens[i]);
@@ -484,6 +504,16 @@ extern "C" mtr_status mtr_upload_batch_device(mtr_ctx *ctx, const uint8_t *d_tex
     return st;
 }
 
+extern "C" mtr_status mtr_upload_batch_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
+                                                      const int32_t *lens, int32_t n, int32_t text_kind, void *wait_stream)
+{
+    if (!fs) { if (ctx) ctx->err = "null file state"; return MTR_ERR_BAD_ARG; }
+    const DeviceText dt = { d_text, text_bytes, text_kind, (hipStream_t)wait_stream };
+    const mtr_status st = upload_batch(ctx, fs, nullptr, 0, nullptr, nullptr, offsets, lens, n, &dt);
+    if (st != MTR_OK && ctx && !ctx->pending) free_batch(ctx);          // a refused device upload leaves no batch behind, and the state as it was
+    return st;
+}
+
 // bytes .. of d must be device memory of the context's GPU, inside one allocation (what / what_bytes: the arguments' names in the reason)
 static mtr_status check_device_ptr(mtr_ctx *ctx, const uint8_t *d, int64_t bytes, const char *what, const char *what_bytes)
 {
@@ -520,11 +550,147 @@ static mtr_status check_device_text(mtr_ctx *ctx, const DeviceText &dt, const in
     return check_device_ptr(ctx, dt.d, dt.bytes, "d_text", "text_bytes");
 }
 
+
+// ---- file-order mode for device input (file_order.hip.inc): the staircase search over lengths, the launches, the state's storage ----
+// One step of the working staircase of a batch: a stair of the state as the batch found it (owner = ~its index) or a read of the batch (owner = its index)
+struct FoWork { int32_t L, r; int64_t N, n, E; int32_t owner; };
+struct FoPlan { std::vector<FoWork> work; std::vector<FoSeg> segs; std::vector<int64_t> tail_off; std::vector<FoAfter> own; };
+
+// may this context continue fs with a feed of kind `want`?
+static mtr_status fo_check_kind(mtr_ctx *ctx, const mtr_file_state *fs, int want)
+{
+    if (fs->kind != mtr_file_state::UNFED && fs->kind != want) {
+        ctx->err = want == mtr_file_state::DEVICE_FED ? "the file state is fed from the host: reads in device memory cannot continue it"
+                                                      : "the file state is fed from device memory: reads on the host cannot continue it";
+        return MTR_ERR_BAD_ARG;
+    }
+    if (want == mtr_file_state::DEVICE_FED && fs->device >= 0 && fs->device != ctx->device) {
+        ctx->err = "the file state lives on GPU " + std::to_string(fs->device) + ", the context is on GPU " + std::to_string(ctx->device);
+        return MTR_ERR_BAD_ARG;
+    }
+    return MTR_OK;
+}
+
+// What upload_batch's host loop does with the bases, over lengths only: the reads of the batch in file order against the state's stairs and
+// each other.  p.work ends as the staircase after the batch.  tails: also each read's tail as segments by owner (mtr_file_state::tail_for)
+// and the owners of its positions L, L + 1 (org_at); an owner's words are in `batch` at woff[owner] or in the state's storage.
+static void fo_plan(const mtr_file_state *fs, const uint32_t *batch, const int64_t *woff, const int32_t *lens, int32_t n, bool tails, FoPlan &p)
+{
+    p.work.clear(); p.segs.clear();
+    for (size_t k = 0; k < fs->stairs.size(); k++) {
+        const mtr_file_state::Entry &e = fs->stairs[k];
+        p.work.push_back(FoWork{ e.L, e.r, e.N, e.n, e.E, ~(int32_t)k });
+    }
+    auto words = [&](const FoWork &o) { return o.owner < 0 ? fs->d_store + fs->stairs[(size_t)~o.owner].woff : batch + woff[o.owner]; };
+    if (tails) { p.tail_off.assign((size_t)n + 1, 0); p.own.assign((size_t)n, FoAfter{ { nullptr, nullptr } }); }
+    int64_t t = 0;
+    for (int32_t i = 0; i < n; i++) {
+        const int32_t L = lens[i];
+        mtr_file_state::Entry me; mtr_file_state::geometry(L, me);
+        if (tails) {
+            int wtop = 0;
+            for (int w = MTRC_MIN_WINDOW; w <= MTRC_MAX_WINDOW && w < L / 2; w *= 2) wtop = w;
+            const int64_t reach = std::max<int64_t>((int64_t)L + me.r + 2 * wtop + 8, me.E);
+            int64_t cur = me.E;
+            for (size_t k = p.work.size(); k-- > 0 && cur < reach; ) {
+                const FoWork &o = p.work[k];
+                if (o.E <= cur) continue;
+                const int64_t end = std::min(o.E, reach);
+                p.segs.push_back(FoSeg{ words(o), t, (int32_t)cur, o.L, o.r, (int32_t)o.N });
+                t += end - cur; cur = end;
+            }
+            p.tail_off[(size_t)i + 1] = t;
+            for (int d = 0; d < 2; d++)
+                for (size_t k = p.work.size(); k-- > 0; )
+                    if (p.work[k].L > L + d) { p.own[(size_t)i].w[d] = words(p.work[k]); break; }
+        }
+        while (!p.work.empty() && p.work.back().L <= L) p.work.pop_back();
+        p.work.push_back(FoWork{ me.L, me.r, me.N, me.n, me.E, i });
+    }
+}
+
+// the tails and the after-bases of the batch whose packing kernel has just been enqueued: plan, copies and the two kernels, enqueued only
+static mtr_status fo_launch(mtr_ctx *ctx, const mtr_file_state *fs, const int64_t *woff, const int32_t *lens, int32_t n, FoPlan &p)
+{
+    fo_plan(fs, ctx->d_packed, woff, lens, n, true, p);
+    const int64_t entries = p.tail_off[(size_t)n];
+    const size_t n_segs = p.segs.size();
+    HIPCHK(ctx->d_tail.ensure((size_t)std::max<int64_t>(entries, 1) * 2)); HIPCHK(ctx->d_tail_off.ensure(((size_t)n + 1) * 8));
+    HIPCHK(ctx->d_fo_segs.ensure(std::max<size_t>(n_segs, 1) * sizeof(FoSeg))); HIPCHK(ctx->d_fo_own.ensure((size_t)n * sizeof(FoAfter)));
+    HIPCHK(ctx->d_after.ensure((size_t)n * 2));
+    HIPCHK(hipMemcpyAsync(ctx->d_tail_off, p.tail_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_fo_own, p.own.data(), (size_t)n * sizeof(FoAfter), hipMemcpyHostToDevice, ctx->stream));
+    ctx->fo_tail_launches = 0; ctx->fo_tail_ms = 0;
+    if (entries > 0) {
+        HIPCHK(hipMemcpyAsync(ctx->d_fo_segs, p.segs.data(), n_segs * sizeof(FoSeg), hipMemcpyHostToDevice, ctx->stream));
+        const int64_t blocks = std::min<int64_t>((entries + MTR_FO_BLOCK - 1) / MTR_FO_BLOCK, (int64_t)ctx->n_cu * 8);
+        HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+        hipLaunchKernelGGL(mtr_k_file_tail, dim3((unsigned)blocks), dim3(MTR_FO_BLOCK), 0, ctx->stream, (const FoSeg *)ctx->d_fo_segs, (int32_t)n_segs, entries,
+                           (const uint8_t *)ctx->d_mt, (uint16_t *)ctx->d_tail);
+        HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+        ctx->fo_tail_launches = 1;
+    }
+    hipLaunchKernelGGL(mtr_k_file_after, dim3((unsigned)((n + MTR_FO_BLOCK - 1) / MTR_FO_BLOCK)), dim3(MTR_FO_BLOCK), 0, ctx->stream, (const FoAfter *)ctx->d_fo_own,
+                       (const int64_t *)ctx->d_woff, (const int32_t *)ctx->d_lens, n, (uint32_t *)ctx->d_packed, (uint8_t *)ctx->d_after);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ctx->after.data(), ctx->d_after, (size_t)n * 2, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->tail_entries = entries;
+    return MTR_OK;
+}
+
+// room for `need` words in the state's storage; its first `live` words are kept
+static mtr_status fo_reserve(mtr_ctx *ctx, mtr_file_state *fs, int64_t need, int64_t live)
+{
+    if (need <= fs->store_cap) return MTR_OK;
+    const int64_t cap = need + need / 4 + 64;
+    uint32_t *fresh = nullptr;
+    if (hipMalloc((void **)&fresh, (size_t)cap * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->err = "file state: allocation of " + std::to_string(cap * 4) + " bytes failed";
+        return MTR_ERR_OOM;
+    }
+    if (live > 0) {
+        const hipError_t e = copy_sync(ctx, fresh, fs->d_store, (size_t)live * 4, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) { (void)hipFree(fresh); ctx->err = std::string("file state: ") + hipGetErrorString(e); return MTR_ERR_HIP; }
+    }
+    if (fs->d_store) (void)hipFree(fs->d_store);
+    fs->d_store = fresh; fs->store_cap = cap; fs->device = ctx->device;
+    return MTR_OK;
+}
+
+// The staircase after the batch (work) becomes the state's.  The stairs that survived are a prefix of the storage and stay; the new ones are
+// copied behind them from `batch`, device to device.  The state's stairs change after the last step that can fail.
+static mtr_status fo_commit(mtr_ctx *ctx, mtr_file_state *fs, const std::vector<FoWork> &work, const uint32_t *batch, const int64_t *woff, int32_t n)
+{
+    size_t kept = 0;
+    while (kept < work.size() && work[kept].owner < 0) kept++;
+    const int64_t top = kept ? fs->stairs[kept - 1].woff + mtr_packed_words(fs->stairs[kept - 1].L) : 0;
+    int64_t need = top;
+    for (size_t k = kept; k < work.size(); k++) need += mtr_packed_words(work[k].L);
+    // (batch may be the storage's own staging area, mtr_file_state_skip_device: it was reserved by the caller, so nothing moves here)
+    { mtr_status st = fo_reserve(ctx, fs, need, top); if (st != MTR_OK) return st; }
+    std::vector<mtr_file_state::Entry> fresh;
+    int64_t at = top;
+    for (size_t k = kept; k < work.size(); k++) {
+        const FoWork &o = work[k];
+        HIPCHK(hipMemcpyAsync(fs->d_store + at, batch + woff[o.owner], (size_t)mtr_packed_words(o.L) * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        mtr_file_state::Entry e; e.L = o.L; e.r = o.r; e.N = o.N; e.n = o.n; e.E = o.E; e.woff = at;
+        fresh.push_back(std::move(e));
+        at += mtr_packed_words(o.L);
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    fs->stairs.resize(kept);
+    for (auto &e : fresh) fs->stairs.push_back(std::move(e));
+    fs->reads_seen += n; fs->kind = mtr_file_state::DEVICE_FED; fs->device = ctx->device;
+    return MTR_OK;
+}
+
 static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t *packed_in, int64_t n_words_in, const int64_t *woff_in,
                                const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n, const DeviceText *dt)
 {
     if (!ctx) return MTR_ERR_BAD_ARG;
     if (!lens || n <= 0) { ctx->err = "null input or n_reads <= 0"; return MTR_ERR_BAD_ARG; }
+    if (fs) { mtr_status st = fo_check_kind(ctx, fs, dt ? mtr_file_state::DEVICE_FED : mtr_file_state::HOST_FED); if (st != MTR_OK) return st; }
     HIPCHK(hipSetDevice(ctx->device));
     { mtr_status w = mtr_wait(ctx); if (w != MTR_OK && w != MTR_ERR_OVERFLOW && w != MTR_ERR_DP_TOO_LARGE) return w; }
     free_batch(ctx);
@@ -551,8 +717,9 @@ static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t 
     }
     // file-order mode: in file order, what each read finds beyond its own part of the reference's two buffers
     std::vector<uint16_t> tail; std::vector<int64_t> tail_off;
+    FoPlan fo;                                                   // reads in device memory: file_order.hip.inc does it, behind the packing kernel
     ctx->after.assign((size_t)n * 2, 0);
-    if (fs) {
+    if (fs && !dt) {
         tail_off.assign((size_t)n + 1, 0);
         for (int i = 0; i < n; i++) {
             fs->tail_for(lens[i], tail);
@@ -566,7 +733,7 @@ static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t 
             fs->push(bases + offsets[i], lens[i]);
         }
     }
-    ctx->file_order = fs != nullptr;
+    ctx->file_order = fs != nullptr; ctx->tail_entries = (int64_t)tail.size(); ctx->fo_tail_launches = 0; ctx->fo_tail_ms = 0;
     std::vector<int32_t> order((size_t)n); std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lens[a] > lens[b]; });
     ctx->roff.assign((size_t)n + 1, 0);
@@ -607,10 +774,11 @@ static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t 
             hipLaunchKernelGGL(mtr_k_pack_text<false>, dim3((unsigned)blocks), dim3(MTR_PACK_BLOCK), 0, ctx->stream, dt->d, ctx->d_toff, ctx->d_lens,
                                ctx->d_woff, n, words, ctx->d_packed, ctx->d_pack_bad);
         HIPCHK(hipGetLastError());
+        if (fs) { mtr_status st = fo_launch(ctx, fs, woff, lens, n, fo); if (st != MTR_OK) return st; }
     }
     HIPCHK(hipMemcpyAsync(ctx->d_order, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_roff, ctx->roff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (fs) {
+    if (fs && !dt) {
         HIPCHK(ctx->d_tail.ensure(std::max<size_t>(tail.size(), 1) * 2)); HIPCHK(ctx->d_tail_off.ensure(((size_t)n + 1) * 8));
         if (!tail.empty()) HIPCHK(hipMemcpyAsync(ctx->d_tail, tail.data(), tail.size() * 2, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(ctx->d_tail_off, tail_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -628,7 +796,68 @@ static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t 
         ctx->err = "read " + std::to_string(first_bad) + (dt->kind == MTR_TEXT_ASCII ? ": a byte that is not A, C, G, T, a, c, g or t" : ": base code > 3");
         return MTR_ERR_BAD_ARG;
     }
+    if (fs && dt) {   // every refusal is behind us: the state advances over the batch
+        if (ctx->fo_tail_launches) HIPCHK(hipEventElapsedTime(&ctx->fo_tail_ms, ctx->ev[0], ctx->ev[1]));
+        mtr_status st = fo_commit(ctx, fs, fo.work, ctx->d_packed, woff, n);
+        if (st != MTR_OK) return st;
+    }
     return MTR_OK;
+}
+
+// The state advances over reads that another GPU processes: all of them are packed (and checked) into the storage's free end, the ones that
+// survive as stairs are then copied down behind the stairs that stay.  The resident batch and its buffers are not touched.
+extern "C" mtr_status mtr_file_state_skip_device(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
+                                                 const int32_t *lens, int32_t n, int32_t text_kind, void *wait_stream)
+{
+    if (!ctx) return MTR_ERR_BAD_ARG;
+    if (!fs) { ctx->err = "null file state"; return MTR_ERR_BAD_ARG; }
+    if (n < 0 || (n > 0 && !lens)) { ctx->err = "null input or n_reads < 0"; return MTR_ERR_BAD_ARG; }
+    { mtr_status st = fo_check_kind(ctx, fs, mtr_file_state::DEVICE_FED); if (st != MTR_OK) return st; }
+    if (n == 0) return MTR_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    std::vector<int64_t> woff((size_t)n);
+    int64_t words = 0;
+    for (int i = 0; i < n; i++) {
+        if (lens[i] <= 0 || lens[i] > MTRC_MAX_SUPPORTED_LENGTH) { ctx->err = "read " + std::to_string(i) + ": length " + std::to_string(lens[i]) + " outside 1.." + std::to_string(MTRC_MAX_SUPPORTED_LENGTH); return MTR_ERR_BAD_ARG; }
+        woff[(size_t)i] = words; words += mtr_packed_words(lens[i]);
+    }
+    const DeviceText dt = { d_text, text_bytes, text_kind, (hipStream_t)wait_stream };
+    { mtr_status st = check_device_text(ctx, dt, offsets, lens, n); if (st != MTR_OK) return st; }
+    FoPlan fo;
+    fo_plan(fs, nullptr, woff.data(), lens, n, false, fo);
+    size_t kept = 0;
+    while (kept < fo.work.size() && fo.work[kept].owner < 0) kept++;
+    const int64_t top = kept ? fs->stairs[kept - 1].woff + mtr_packed_words(fs->stairs[kept - 1].L) : 0;
+    int64_t fresh = 0;
+    for (size_t k = kept; k < fo.work.size(); k++) fresh += mtr_packed_words(fo.work[k].L);
+    // (the stairs that this call pops are still live until it commits: the staging area starts behind all of them too)
+    const int64_t stage = std::max(top + fresh, fs->store_top());
+    { mtr_status st = fo_reserve(ctx, fs, stage + words, fs->store_top()); if (st != MTR_OK) return st; }
+    uint32_t *d_stage = fs->d_store + stage;
+    if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
+    HIPCHK(ctx->d_toff.ensure((size_t)n * 8)); HIPCHK(ctx->d_pack_bad.ensure(4));
+    HIPCHK(ctx->d_fo_lens.ensure((size_t)n * 4)); HIPCHK(ctx->d_fo_woff.ensure((size_t)n * 8));
+    HIPCHK(hipMemcpyAsync(ctx->d_toff, offsets, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_fo_lens, lens, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_fo_woff, woff.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_pack_bad, 0x7f, 4, ctx->stream));
+    HIPCHK(hipEventRecord(ctx->ev_text, dt.wait));
+    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
+    const int64_t blocks = std::min<int64_t>((words + MTR_PACK_BLOCK - 1) / MTR_PACK_BLOCK, (int64_t)ctx->n_cu * 8);
+    if (dt.kind == MTR_TEXT_ASCII)
+        hipLaunchKernelGGL(mtr_k_pack_text<true>, dim3((unsigned)blocks), dim3(MTR_PACK_BLOCK), 0, ctx->stream, dt.d, ctx->d_toff, ctx->d_fo_lens,
+                           ctx->d_fo_woff, n, words, d_stage, ctx->d_pack_bad);
+    else
+        hipLaunchKernelGGL(mtr_k_pack_text<false>, dim3((unsigned)blocks), dim3(MTR_PACK_BLOCK), 0, ctx->stream, dt.d, ctx->d_toff, ctx->d_fo_lens,
+                           ctx->d_fo_woff, n, words, d_stage, ctx->d_pack_bad);
+    HIPCHK(hipGetLastError());
+    int32_t first_bad = n;
+    HIPCHK(copy_sync(ctx, &first_bad, ctx->d_pack_bad, 4, hipMemcpyDeviceToHost));
+    if (first_bad < n) {
+        ctx->err = "read " + std::to_string(first_bad) + (dt.kind == MTR_TEXT_ASCII ? ": a byte that is not A, C, G, T, a, c, g or t" : ": base code > 3");
+        return MTR_ERR_BAD_ARG;
+    }
+    return fo_commit(ctx, fs, fo.work, d_stage, woff.data(), n);
 }
 
 static BatchView view(const mtr_ctx *ctx)
@@ -1834,7 +2063,7 @@ extern "C" mtr_status mtr_parse_fasta_device(mtr_ctx *ctx, const uint8_t *d_fast
     return MTR_OK;
 }
 
-extern "C" mtr_status mtr_upload_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info)
+static mtr_status upload_fasta(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info)
 {
     if (!ctx || !info) return MTR_ERR_BAD_ARG;
     fasta_no_reads(info);
@@ -1863,9 +2092,19 @@ extern "C" mtr_status mtr_upload_fasta_device(mtr_ctx *ctx, const uint8_t *d_fas
     ctx->fa_indexed = true;
     if (n == 0) return MTR_OK;                                    // no reads: nothing to upload
     const DeviceText dt = { ctx->d_fa_text, f.n_bases, MTR_TEXT_ASCII, ctx->stream };
-    const mtr_status st = upload_batch(ctx, nullptr, nullptr, 0, nullptr, nullptr, offs.data(), ctx->fa_lens.data(), f.n_reads, &dt);
+    const mtr_status st = upload_batch(ctx, fs, nullptr, 0, nullptr, nullptr, offs.data(), ctx->fa_lens.data(), f.n_reads, &dt);
     if (st != MTR_OK) { ctx->fa_indexed = false; if (!ctx->pending) free_batch(ctx); }       // as a refused mtr_upload_batch_device: no batch is left
     return st;
+}
+extern "C" mtr_status mtr_upload_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info)
+{
+    return upload_fasta(ctx, nullptr, d_fasta, n_bytes, wait_stream, info);
+}
+extern "C" mtr_status mtr_upload_fasta_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream,
+                                                      mtr_fasta_info *info)
+{
+    if (!fs) { if (ctx) ctx->err = "null file state"; return MTR_ERR_BAD_ARG; }
+    return upload_fasta(ctx, fs, d_fasta, n_bytes, wait_stream, info);
 }
 
 extern "C" mtr_status mtr_fasta_index(const mtr_ctx *ctx, int32_t *lens, int64_t *id_off, char *ids)
@@ -2068,6 +2307,29 @@ extern "C" mtr_status mtr_test_ranges(mtr_ctx *ctx, int32_t **out_counts, int32_
         }
     }
     *out_counts = oc.release(); *out_start = os.release(); *out_end = oe.release(); *out_w = ow.release(); *out_di_bits = od.release(); if (out_total) *out_total = total;
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_test_file_tail(mtr_ctx *ctx, uint16_t **out_tail, int64_t **out_tail_off, uint8_t **out_after)
+{
+    if (!ctx || !out_tail || !out_tail_off || !out_after) return MTR_ERR_BAD_ARG;
+    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)ctx->n_reads;
+    const int64_t entries = ctx->file_order ? ctx->tail_entries : 0;
+    HostArray<uint16_t> tl = host_array<uint16_t>((size_t)std::max<int64_t>(entries, 1));
+    HostArray<int64_t> to = host_array<int64_t>(n + 1);
+    HostArray<uint8_t> af = host_array<uint8_t>(n * 2);
+    if (!tl || !to || !af) return MTR_ERR_OOM;
+    tl[0] = 0; memset(to.get(), 0, (n + 1) * 8); memset(af.get(), 0, n * 2);
+    if (ctx->file_order) {
+        HIPCHK(copy_sync(ctx, to.get(), ctx->d_tail_off, (n + 1) * 8, hipMemcpyDeviceToHost));
+        if (entries > 0) HIPCHK(copy_sync(ctx, tl.get(), ctx->d_tail, (size_t)entries * 2, hipMemcpyDeviceToHost));
+        if (ctx->after.size() >= n * 2) memcpy(af.get(), ctx->after.data(), n * 2);
+    }
+    // id 0 of mtr_get_kernel_times: mtr_k_file_tail of this batch's upload (launches = 0: a host upload, or no tail entry)
+    ctx->kt[0].ms = ctx->file_order ? ctx->fo_tail_ms : 0; ctx->kt[0].launches = ctx->file_order ? ctx->fo_tail_launches : 0;
+    *out_tail = tl.release(); *out_tail_off = to.release(); *out_after = af.release();
     return MTR_OK;
 }
 

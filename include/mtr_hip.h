@@ -202,6 +202,37 @@ mtr_status mtr_parse_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t 
 mtr_status mtr_upload_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info);
 mtr_status mtr_fasta_index(const mtr_ctx *ctx, int32_t *lens, int64_t *id_off, char *ids);
 
+/* ---- a FASTQ file in device memory ---------------------------------------------------------------------------------------
+ * What the long-read basecallers write, parsed by device kernels (mtr_amd/csrc/fastq.hip.inc).  The reference has no FASTQ reader;
+ * the rules are this library's: strict four-line FASTQ.
+ *   lines      line 0 starts at byte 0; line l + 1 starts behind the l-th LF, if a byte exists there (no fgets windows)
+ *   content    a line's content is its bytes in front of its first NUL, LF or CR, the FASTA rules' terminators; a terminator
+ *              hides the rest of its line
+ *   record r   is lines 4r .. 4r + 3 - header: content begins with '@', the ID is the content behind it, spaces included, and may
+ *              be empty; sequence: every content byte is one of ACGTacgt; separator: content begins with '+', the rest is
+ *              ignored; quality: content as long as the sequence's content, its bytes are not looked at otherwise ('@', '>' and
+ *              '+' are legal first quality characters and are not taken for a header)
+ *   stop       the input stops at the first of these in file order:
+ *                MTR_FASTA_END_BADCHAR  a sequence content byte outside ACGTacgt, 'N' included: end_pos at that byte, bad_char
+ *                                       holds it
+ *                MTR_FASTA_END_TOOLONG  the MTR_MAX_INPUT_LENGTH-th base of a sequence line: end_pos at that base
+ *                MTR_FASTA_END_EMPTY    a sequence line with empty content: end_pos = the line's first byte
+ *                MTR_FASTA_END_FORMAT   a header line not beginning with '@' or a separator line not beginning with '+': end_pos =
+ *                                       the line's first byte; a quality line whose content length differs from the sequence's:
+ *                                       end_pos = the line's first byte; the file ends inside a record, so fewer than four lines
+ *                                       of it begin: end_pos = n_bytes.  A blank line behind the last record is a header line
+ *                                       without '@'
+ *   reads      the records whose four lines are complete and correct before the stop; a last quality line without LF is complete
+ *   no stop    MTR_FASTA_END_EOF.  n_bytes == 0: MTR_OK, no reads, MTR_FASTA_END_EMPTY, as for FASTA
+ * Protocol, argument checks and stream handling are those of the FASTA entry points above, and info, dst, mtr_fasta_index mean
+ * what they mean there: text = the reads' bases read after read, offsets their exclusive sum.  mtr_upload_fastq_device compacts
+ * nothing: a sequence line is contiguous in the file, and the packing kernel of mtr_upload_batch_device reads the reads out of
+ * d_fastq itself.  Multi-line FASTQ and the qualities as output are not supported. */
+#define MTR_FASTA_END_FORMAT 4
+mtr_status mtr_parse_fastq_device(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_bytes, void *wait_stream,
+                                  const mtr_fasta_dst *dst, mtr_fasta_info *info);
+mtr_status mtr_upload_fastq_device(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info);
+
 /* ---- wire form of the record table -------------------------------------------------------------------------------
  * A mtr_record is 2560 bytes because unit[] and unit_score[] are sized for MAX_PERIOD; a typical record uses 600.  The
  * wire form keeps what insert_an_alignment_into_set receives and nothing else, record after record:
@@ -361,6 +392,9 @@ mtr_status mtr_file_state_skip(mtr_file_state *fs, const uint8_t *bases, const i
 mtr_status mtr_upload_batch_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
                                            const int32_t *lens, int32_t n_reads, int32_t text_kind, void *wait_stream);
 mtr_status mtr_upload_fasta_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream,
+                                           mtr_fasta_info *info);
+/* a FASTQ file's reads as the next reads of the file: feeds and advances a device-fed state exactly as mtr_upload_fasta_device_in_file */
+mtr_status mtr_upload_fastq_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fastq, int64_t n_bytes, void *wait_stream,
                                            mtr_fasta_info *info);
 mtr_status mtr_file_state_skip_device(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
                                       const int32_t *lens, int32_t n_reads, int32_t text_kind, void *wait_stream);

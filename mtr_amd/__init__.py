@@ -1,8 +1,8 @@
 """mtr_amd — MI355X (gfx950) implementation of reference mTR's per-read hot path.
 
 Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointers).  Only the device-input and report methods
-(Engine.upload_device / process_device / parse_fasta_device / upload_fasta_device / export_tensor / report_tensors /
-report_alignment_tensors / report_text / report_bytes) take or return torch tensors;
+(Engine.upload_device / process_device / parse_fasta_device / upload_fasta_device / parse_fastq_device / upload_fastq_device /
+export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes) take or return torch tensors;
 they import torch when called.
 The product path is libmtr_hip.so only: importing works without a GPU, but creating an Engine
 without the library or without a HIP device raises — there is no CPU fallback.
@@ -21,7 +21,8 @@ MAX_PERIOD = 500
 MAX_READ_LENGTH = 833333                     # MTR_MAX_READ_LENGTH
 TEXT_ASCII, TEXT_CODES = 0, 1                # MTR_TEXT_ASCII, MTR_TEXT_CODES
 FASTA_TILE_BYTES = 4096                      # MTR_FASTA_TILE_BYTES (mtr_amd/csrc/fasta.hip.inc): the bytes of a FASTA file one workgroup scans
-FASTA_END = {0: "eof", 1: "empty", 2: "bad", 3: "toolong"}        # MTR_FASTA_END_*
+FASTA_END = {0: "eof", 1: "empty", 2: "bad", 3: "toolong"}        # MTR_FASTA_END_* of a FASTA file
+FASTQ_END = {**FASTA_END, 4: "format"}       # ... and of a FASTQ file: MTR_FASTA_END_FORMAT too
 
 STATUS = {0: "MTR_OK", 1: "MTR_ERR_NO_DEVICE", 2: "MTR_ERR_BAD_ARG", 3: "MTR_ERR_OOM", 4: "MTR_ERR_HIP",
           5: "MTR_ERR_OVERFLOW", 6: "MTR_ERR_DP_TOO_LARGE"}
@@ -45,6 +46,7 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_unpack_records", "mtr_pack_records", "mtr_get_first_failed_read", "mtr_upload_batch_device",
            "mtr_report_device", "mtr_test_chain", "mtr_report_alignments_device", "mtr_report_text_device", "mtr_test_report_lines",
            "mtr_parse_fasta_device", "mtr_upload_fasta_device", "mtr_fasta_index",
+           "mtr_parse_fastq_device", "mtr_upload_fastq_device", "mtr_upload_fastq_device_in_file",
            "mtr_upload_batch_device_in_file", "mtr_upload_fasta_device_in_file", "mtr_file_state_skip_device", "mtr_test_file_tail"]
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
@@ -270,6 +272,9 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_file_state_skip_device.restype = C.c_int
     lib.mtr_test_file_tail.argtypes = [C.c_void_p, P(P(C.c_uint16)), P(P(C.c_int64)), P(P(C.c_uint8))]
     lib.mtr_test_file_tail.restype = C.c_int
+    for name in ("mtr_parse_fastq_device", "mtr_upload_fastq_device", "mtr_upload_fastq_device_in_file"):       # as their FASTA twins
+        twin = getattr(lib, name.replace("fastq", "fasta"))
+        getattr(lib, name).argtypes, getattr(lib, name).restype = twin.argtypes, twin.restype
     lib.mtr_fasta_index.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mtr_fasta_index.restype = C.c_int
     lib.mtr_test_report_lines.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [P(P(C.c_uint8)), P(P(C.c_int64))]
@@ -348,8 +353,8 @@ def device_input_args(text, offsets, lens, device: int):
 
 
 def fasta_input_args(buf, device: int) -> None:
-    """The checks of Engine.parse_fasta_device / upload_fasta_device, made before the library is called: buf a contiguous 1-D
-    torch.uint8 tensor on cuda:device (the bytes of a FASTA file; it may be empty).  Raises MtrError."""
+    """The checks of Engine.parse_fasta_device / upload_fasta_device and their FASTQ twins, made before the library is called: buf
+    a contiguous 1-D torch.uint8 tensor on cuda:device (the bytes of a FASTA or FASTQ file; it may be empty).  Raises MtrError."""
     import torch
 
     if not isinstance(buf, torch.Tensor):
@@ -365,7 +370,7 @@ def fasta_input_args(buf, device: int) -> None:
 
 
 def _fasta(info: CFastaInfo, text, offsets, lens, id_off, ids: bytes) -> Fasta:
-    return Fasta(text, offsets, lens, [ids[int(id_off[i]):int(id_off[i + 1])] for i in range(info.n_reads)], FASTA_END[info.end],
+    return Fasta(text, offsets, lens, [ids[int(id_off[i]):int(id_off[i + 1])] for i in range(info.n_reads)], FASTQ_END[info.end],
                  bytes([info.bad_char & 0xFF]) if info.end == 2 else None, int(info.end_pos))
 
 
@@ -469,6 +474,14 @@ class Engine:
         buf: contiguous 1-D torch.uint8 tensor on this engine's device.  Returns a Fasta whose text is a fresh tensor on that
         device (what upload_device takes) and whose index is on the host; the resident batch is not touched.  The library
         waits for torch's current stream (where buf was written) by an event."""
+        return self._parse_file_device("mtr_parse_fasta_device", buf)
+
+    def parse_fastq_device(self, buf) -> Fasta:
+        """mtr_parse_fastq_device: parse_fasta_device for the bytes of a FASTQ file - strict four-line records, the rules in
+        include/mtr_hip.h.  The qualities are checked for their length and dropped; end may be "format" too."""
+        return self._parse_file_device("mtr_parse_fastq_device", buf)
+
+    def _parse_file_device(self, entry: str, buf) -> Fasta:
         import torch
 
         fasta_input_args(buf, self.device)
@@ -476,7 +489,8 @@ class Engine:
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         src = C.c_void_p(buf.data_ptr()) if buf.numel() else None
         info = CFastaInfo()
-        self._check(self.lib.mtr_parse_fasta_device(self.h, src, buf.numel(), stream, None, C.byref(info)), "mtr_parse_fasta_device")
+        call = getattr(self.lib, entry)
+        self._check(call(self.h, src, buf.numel(), stream, None, C.byref(info)), entry)
         n, nb, ni = info.n_reads, int(info.n_bases), int(info.id_bytes)
         text = torch.empty(nb, dtype=torch.uint8, device=dev)
         offsets = torch.empty(n, dtype=torch.int64, device=dev)
@@ -486,7 +500,7 @@ class Engine:
         torch.cuda.current_stream(dev).synchronize()            # the library writes the tensors on its own stream: torch's earlier use of the memory is done
         ptr = lambda t: t.data_ptr() if t.numel() else None     # noqa: E731
         dst = CFastaDst(ptr(text), ptr(offsets), ptr(lens), ptr(ids), id_off.data_ptr(), nb, n, ni)
-        self._check(self.lib.mtr_parse_fasta_device(self.h, src, buf.numel(), stream, C.byref(dst), C.byref(info)), "mtr_parse_fasta_device")
+        self._check(call(self.h, src, buf.numel(), stream, C.byref(dst), C.byref(info)), entry)
         return _fasta(info, text, offsets.cpu().numpy(), lens.cpu().numpy(), id_off.cpu().numpy(), ids.cpu().numpy().tobytes())
 
     def upload_fasta_device(self, buf, file_state: "FileState | None" = None) -> Fasta:
@@ -495,6 +509,14 @@ class Engine:
         report_text takes.  A stop (end != "eof") does not refuse the upload: the reads before it are uploaded.  No reads: no
         batch is uploaded.  file_state: the reads are the next reads of that file (file-order mode,
         mtr_upload_fasta_device_in_file); the state advances over the uploaded reads."""
+        return self._upload_file_device("mtr_upload_fasta_device", buf, file_state)
+
+    def upload_fastq_device(self, buf, file_state: "FileState | None" = None) -> Fasta:
+        """mtr_upload_fastq_device(_in_file) + mtr_fasta_index: upload_fasta_device for the bytes of a FASTQ file.  Nothing is
+        copied or compacted: the reads are packed out of buf itself, where each is one contiguous sequence line."""
+        return self._upload_file_device("mtr_upload_fastq_device", buf, file_state)
+
+    def _upload_file_device(self, entry: str, buf, file_state) -> Fasta:
         import torch
 
         fasta_input_args(buf, self.device)
@@ -503,10 +525,9 @@ class Engine:
         self.n_reads = 0
         src = C.c_void_p(buf.data_ptr()) if buf.numel() else None
         if file_state is None:
-            self._check(self.lib.mtr_upload_fasta_device(self.h, src, buf.numel(), stream, C.byref(info)), "mtr_upload_fasta_device")
+            self._check(getattr(self.lib, entry)(self.h, src, buf.numel(), stream, C.byref(info)), entry)
         else:
-            self._check(self.lib.mtr_upload_fasta_device_in_file(self.h, file_state.h, src, buf.numel(), stream, C.byref(info)),
-                        "mtr_upload_fasta_device_in_file")
+            self._check(getattr(self.lib, entry + "_in_file")(self.h, file_state.h, src, buf.numel(), stream, C.byref(info)), entry + "_in_file")
         n = info.n_reads
         lens, id_off, ids = np.zeros(n, np.int32), np.zeros(n + 1, np.int64), np.zeros(max(int(info.id_bytes), 1), np.uint8)
         self._check(self.lib.mtr_fasta_index(self.h, lens.ctypes.data, id_off.ctypes.data, ids.ctypes.data), "mtr_fasta_index")

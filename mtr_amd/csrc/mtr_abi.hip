@@ -36,6 +36,7 @@
 #include "report_align.hip.inc"
 #include "report_text.hip.inc"
 #include "fasta.hip.inc"
+#include "fastq.hip.inc"
 #include "file_order.hip.inc"
 
 static_assert(sizeof(DevRecord) == sizeof(mtr_record), "device and ABI record layouts must agree");
@@ -221,6 +222,8 @@ struct mtr_ctx {
     // a FASTA file in device memory (fasta.hip.inc), per call: the tiles' columns, the header windows' columns, the IDs' offsets, the stop, the sizes
     DevBuf<uint32_t> d_fa_tiles, d_fa_hbase; DevBuf<int32_t> d_fa_hpos, d_fa_hidlen; DevBuf<int64_t> d_fa_idoff;
     DevBuf<unsigned long long> d_fa_event; DevBuf<mtr_fasta_info> d_fa_info;
+    // a FASTQ file in device memory (fastq.hip.inc) uses those too, and per call: the line table, the records' sequence lengths and their offsets
+    DevBuf<uint32_t> d_fq_lines; DevBuf<int32_t> d_fq_len; DevBuf<int64_t> d_fq_boff;
     // mtr_upload_fasta_device: the parsed reads on the device, and the host copies of their index (mtr_fasta_index)
     DevBuf<uint8_t> d_fa_text, d_fa_ids; DevBuf<int64_t> d_fa_off; DevBuf<int32_t> d_fa_lens;
     bool fa_indexed = false; std::vector<int32_t> fa_lens; std::vector<int64_t> fa_idoff; std::vector<char> fa_ids;
@@ -1966,33 +1969,43 @@ extern "C" mtr_status mtr_report_text_device(mtr_ctx *ctx, const char *ids, cons
 
 // ---- a FASTA file in device memory (fasta.hip.inc) -----------------------------------------------------------------------------
 // Only the header count, the sizes and - for an upload - the reads' lengths, offsets and IDs come back to the host.
-struct FastaParse { FastaArgs a; int32_t n_heads; mtr_fasta_info info; };
+// fastq: the file is FASTQ (fastq.hip.inc) and q holds its columns; the entry points share everything but the kernels
+struct FastaParse { FastaArgs a; int32_t n_heads; mtr_fasta_info info; bool fastq; FastqArgs q; };
 
 static void fasta_no_reads(mtr_fasta_info *info) { memset(info, 0, sizeof *info); info->end = MTR_FASTA_END_EMPTY; }
 
-// the arguments' checks and the scans, up to the sizes (p.info) and the header windows' columns on the device
-static mtr_status fasta_index(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, FastaParse &p)
+// the checks of a file in device memory (what: the argument's name), and the context's stream made to wait for the caller's
+static mtr_status fasta_input(mtr_ctx *ctx, const uint8_t *d_file, int64_t n_bytes, void *wait_stream, const char *what)
 {
-    if (!d_fasta) { ctx->err = "d_fasta is NULL"; return MTR_ERR_BAD_ARG; }
+    if (!d_file) { ctx->err = std::string(what) + " is NULL"; return MTR_ERR_BAD_ARG; }
     if (n_bytes < 0 || n_bytes > (int64_t)INT32_MAX) {
         ctx->err = "n_bytes " + std::to_string(n_bytes) + " outside 0.." + std::to_string(INT32_MAX) + " (a larger file goes in parts cut at record starts)";
         return MTR_ERR_BAD_ARG;
     }
-    { mtr_status st = check_device_ptr(ctx, d_fasta, n_bytes, "d_fasta", "n_bytes"); if (st != MTR_OK) return st; }
-    const int32_t n_tiles = (int32_t)((n_bytes + MTR_FASTA_TILE_BYTES - 1) / MTR_FASTA_TILE_BYTES);
-    const size_t nt = (size_t)n_tiles;
-    HIPCHK(ctx->d_fa_tiles.ensure((7 * nt + 2) * 4)); HIPCHK(ctx->d_fa_event.ensure(8)); HIPCHK(ctx->d_fa_info.ensure(sizeof(mtr_fasta_info)));
-    FastaArgs &a = p.a;
-    a = FastaArgs{};
-    a.fa = d_fasta; a.n = (int32_t)n_bytes; a.n_tiles = n_tiles;
-    uint32_t *t = ctx->d_fa_tiles;
-    a.t_nl = t; a.t_term = t + nt; a.t_cnt = t + 2 * nt; a.t_last = t + 3 * nt; a.t_base = t + 4 * nt; a.t_hdr = t + 5 * nt; a.t_rs = t + 6 * nt;
-    a.totals = t + 7 * nt; a.event = ctx->d_fa_event;
+    { mtr_status st = check_device_ptr(ctx, d_file, n_bytes, what, "n_bytes"); if (st != MTR_OK) return st; }
+    HIPCHK(ctx->d_fa_event.ensure(8)); HIPCHK(ctx->d_fa_info.ensure(sizeof(mtr_fasta_info)));
     // the file comes from the caller's stream: the kernels wait for it there, not for the whole device
     if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
     HIPCHK(hipEventRecord(ctx->ev_text, (hipStream_t)wait_stream));
     HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
     HIPCHK(hipMemsetAsync(ctx->d_fa_event, 0xff, 8, ctx->stream));
+    return MTR_OK;
+}
+
+// the arguments' checks and the scans, up to the sizes (p.info) and the header windows' columns on the device
+static mtr_status fasta_index(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, FastaParse &p)
+{
+    { mtr_status st = fasta_input(ctx, d_fasta, n_bytes, wait_stream, "d_fasta"); if (st != MTR_OK) return st; }
+    const int32_t n_tiles = (int32_t)((n_bytes + MTR_FASTA_TILE_BYTES - 1) / MTR_FASTA_TILE_BYTES);
+    const size_t nt = (size_t)n_tiles;
+    HIPCHK(ctx->d_fa_tiles.ensure((7 * nt + 2) * 4));
+    FastaArgs &a = p.a;
+    a = FastaArgs{};
+    p.fastq = false;
+    a.fa = d_fasta; a.n = (int32_t)n_bytes; a.n_tiles = n_tiles;
+    uint32_t *t = ctx->d_fa_tiles;
+    a.t_nl = t; a.t_term = t + nt; a.t_cnt = t + 2 * nt; a.t_last = t + 3 * nt; a.t_base = t + 4 * nt; a.t_hdr = t + 5 * nt; a.t_rs = t + 6 * nt;
+    a.totals = t + 7 * nt; a.event = ctx->d_fa_event;
     hipLaunchKernelGGL(mtr_k_fasta_lines, dim3((unsigned)n_tiles), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, a);
     hipLaunchKernelGGL(mtr_k_fasta_scan_lines, dim3(1), dim3(MTR_FASTA_SCAN_BLOCK), 0, ctx->stream, a);
     hipLaunchKernelGGL(mtr_k_fasta_tile<0>, dim3((unsigned)n_tiles), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, a);
@@ -2013,10 +2026,62 @@ static mtr_status fasta_index(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_by
     return MTR_OK;
 }
 
-// the columns of the reads before the stop into dst (capacities checked by the caller; dst.id_off may be NULL); enqueues only
+// fasta_index for a FASTQ file: the line table, the records' columns, the sizes.  Only the line count and the sizes come to the host.
+static mtr_status fastq_index(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_bytes, void *wait_stream, FastaParse &p)
+{
+    { mtr_status st = fasta_input(ctx, d_fastq, n_bytes, wait_stream, "d_fastq"); if (st != MTR_OK) return st; }
+    const int32_t n_tiles = (int32_t)((n_bytes + MTR_FASTA_TILE_BYTES - 1) / MTR_FASTA_TILE_BYTES);
+    const size_t nt = (size_t)n_tiles;
+    HIPCHK(ctx->d_fa_tiles.ensure((3 * nt + 1) * 4));
+    FastqArgs &a = p.q;
+    a = FastqArgs{};
+    p.a = FastaArgs{}; p.n_heads = 0; p.fastq = true;
+    a.fq = d_fastq; a.n = (int32_t)n_bytes; a.n_tiles = n_tiles;
+    uint32_t *t = ctx->d_fa_tiles;
+    a.t_cnt = t; a.t_nl = t + nt; a.t_term = t + 2 * nt; a.totals = t + 3 * nt; a.event = ctx->d_fa_event;
+    hipLaunchKernelGGL(mtr_k_fastq_lines, dim3((unsigned)n_tiles), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, a);
+    hipLaunchKernelGGL(mtr_k_fastq_scan_lines, dim3(1), dim3(MTR_FASTA_SCAN_BLOCK), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    uint32_t n_lines = 0;
+    HIPCHK(copy_sync(ctx, &n_lines, a.totals, 4, hipMemcpyDeviceToHost));
+    const size_t nl = (size_t)n_lines, nr = (nl + 3) / 4;         // (a file of one byte or more has a line, and so a record that begins)
+    HIPCHK(ctx->d_fq_lines.ensure(2 * nl * 4)); HIPCHK(ctx->d_fq_len.ensure(nr * 4)); HIPCHK(ctx->d_fq_boff.ensure((nr + 1) * 8));
+    HIPCHK(ctx->d_fa_hpos.ensure(nr * 4)); HIPCHK(ctx->d_fa_hidlen.ensure(nr * 4)); HIPCHK(ctx->d_fa_idoff.ensure((nr + 1) * 8));
+    a.l_start = ctx->d_fq_lines; a.l_end = a.l_start + nl; a.n_lines = n_lines;
+    a.r_pos = ctx->d_fa_hpos; a.r_idlen = ctx->d_fa_hidlen; a.r_len = ctx->d_fq_len; a.n_recs = (uint32_t)nr; a.b_off = ctx->d_fq_boff;
+    p.a.fa = d_fastq; p.a.h_pos = a.r_pos;                        // what mtr_k_fasta_ids reads: a header is a position there too
+    hipLaunchKernelGGL(mtr_k_fastq_tile<0>, dim3((unsigned)n_tiles), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, a);
+    const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)nr + 255) / 256, (int64_t)ctx->n_cu * 8);
+    hipLaunchKernelGGL(mtr_k_fastq_records, dim3(blocks), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.r_idlen, (int64_t)nr, (int64_t *)ctx->d_fa_idoff);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.r_len, (int64_t)nr, (int64_t *)ctx->d_fq_boff);
+    hipLaunchKernelGGL(mtr_k_fastq_finish, dim3(1), dim3(64), 0, ctx->stream, a, (const int64_t *)ctx->d_fa_idoff, (mtr_fasta_info *)ctx->d_fa_info);
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(ctx, &p.info, ctx->d_fa_info, sizeof(mtr_fasta_info), hipMemcpyDeviceToHost));
+    return MTR_OK;
+}
+
+// the columns of the reads before the stop into dst (capacities checked by the caller; dst.id_off may be NULL); enqueues only.
+// A FASTQ file with dst.text == NULL (mtr_upload_fastq_device): nothing is compacted, dst.offsets = the sequence lines' starts in the file.
 static mtr_status fasta_write(mtr_ctx *ctx, const FastaParse &p, const mtr_fasta_dst &dst)
 {
     const mtr_fasta_info &f = p.info;
+    if (p.fastq) {
+        if (dst.id_off) HIPCHK(hipMemcpyAsync(dst.id_off, ctx->d_fa_idoff, ((size_t)f.n_reads + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        if (f.n_reads <= 0) return MTR_OK;
+        FastqArgs q = p.q;
+        q.text = dst.text; q.n_reads = (uint32_t)f.n_reads;
+        const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)f.n_reads + 255) / 256, (int64_t)ctx->n_cu * 8);
+        hipLaunchKernelGGL(mtr_k_fastq_reads, dim3(blocks), dim3(256), 0, ctx->stream, q, f.n_reads, dst.text ? 0 : 1, dst.offsets, dst.lens);
+        if (f.id_bytes > 0)
+            hipLaunchKernelGGL(mtr_k_fasta_ids, dim3((unsigned)std::min<int64_t>(f.n_reads, (int64_t)ctx->n_cu * 32)), dim3(64), 0, ctx->stream, p.a, f.n_reads,
+                               (const int64_t *)ctx->d_fa_idoff, dst.ids);
+        // every base of a reported read lies before the stop: the tiles behind it hold none
+        const unsigned tiles = (unsigned)((std::min<int64_t>(f.end_pos, (int64_t)q.n) + MTR_FASTA_TILE_BYTES - 1) / MTR_FASTA_TILE_BYTES);
+        if (dst.text && tiles > 0) hipLaunchKernelGGL(mtr_k_fastq_tile<1>, dim3(tiles), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, q);
+        HIPCHK(hipGetLastError());
+        return MTR_OK;
+    }
     if (dst.id_off) HIPCHK(hipMemcpyAsync(dst.id_off, ctx->d_fa_idoff, ((size_t)f.n_reads + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
     if (f.n_reads <= 0) return MTR_OK;
     FastaArgs a = p.a;
@@ -2034,8 +2099,8 @@ static mtr_status fasta_write(mtr_ctx *ctx, const FastaParse &p, const mtr_fasta
     return MTR_OK;
 }
 
-extern "C" mtr_status mtr_parse_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, const mtr_fasta_dst *dst,
-                                             mtr_fasta_info *info)
+static mtr_status parse_fasta(mtr_ctx *ctx, bool fastq, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, const mtr_fasta_dst *dst,
+                              mtr_fasta_info *info)
 {
     if (!ctx || !info) return MTR_ERR_BAD_ARG;
     fasta_no_reads(info);
@@ -2045,7 +2110,7 @@ extern "C" mtr_status mtr_parse_fasta_device(mtr_ctx *ctx, const uint8_t *d_fast
         return MTR_OK;
     }
     FastaParse p;
-    { mtr_status st = fasta_index(ctx, d_fasta, n_bytes, wait_stream, p); if (st != MTR_OK) return st; }
+    { mtr_status st = (fastq ? fastq_index : fasta_index)(ctx, d_fasta, n_bytes, wait_stream, p); if (st != MTR_OK) return st; }
     *info = p.info;
     if (!dst) return MTR_OK;
     const mtr_fasta_info &f = p.info;
@@ -2062,8 +2127,19 @@ extern "C" mtr_status mtr_parse_fasta_device(mtr_ctx *ctx, const uint8_t *d_fast
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
 }
+extern "C" mtr_status mtr_parse_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, const mtr_fasta_dst *dst,
+                                             mtr_fasta_info *info)
+{
+    return parse_fasta(ctx, false, d_fasta, n_bytes, wait_stream, dst, info);
+}
+extern "C" mtr_status mtr_parse_fastq_device(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_bytes, void *wait_stream, const mtr_fasta_dst *dst,
+                                             mtr_fasta_info *info)
+{
+    return parse_fasta(ctx, true, d_fastq, n_bytes, wait_stream, dst, info);
+}
 
-static mtr_status upload_fasta(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info)
+// fastq: the reads stay where they are, in the file - a sequence line is contiguous there -, and the packing kernel reads them from it
+static mtr_status upload_fasta(mtr_ctx *ctx, mtr_file_state *fs, bool fastq, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info)
 {
     if (!ctx || !info) return MTR_ERR_BAD_ARG;
     fasta_no_reads(info);
@@ -2072,16 +2148,17 @@ static mtr_status upload_fasta(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *
     free_batch(ctx);                                              // whatever happens below, the batch before this call is gone
     ctx->fa_indexed = false;
     FastaParse p; p.info = *info;
-    if (n_bytes != 0) { mtr_status st = fasta_index(ctx, d_fasta, n_bytes, wait_stream, p); if (st != MTR_OK) return st; }
+    if (n_bytes != 0) { mtr_status st = (fastq ? fastq_index : fasta_index)(ctx, d_fasta, n_bytes, wait_stream, p); if (st != MTR_OK) return st; }
     *info = p.info;
     const mtr_fasta_info &f = p.info;
     const size_t n = (size_t)f.n_reads;
     std::vector<int64_t> offs(n);
     ctx->fa_lens.assign(n, 0); ctx->fa_idoff.assign(n + 1, 0); ctx->fa_ids.assign((size_t)f.id_bytes, 0);
     if (n > 0) {
-        HIPCHK(ctx->d_fa_text.ensure((size_t)f.n_bases + 16)); HIPCHK(ctx->d_fa_off.ensure(n * 8)); HIPCHK(ctx->d_fa_lens.ensure(n * 4));
+        if (!fastq) HIPCHK(ctx->d_fa_text.ensure((size_t)f.n_bases + 16));
+        HIPCHK(ctx->d_fa_off.ensure(n * 8)); HIPCHK(ctx->d_fa_lens.ensure(n * 4));
         HIPCHK(ctx->d_fa_ids.ensure((size_t)f.id_bytes + 16));
-        mtr_fasta_dst dst = { ctx->d_fa_text, ctx->d_fa_off, ctx->d_fa_lens, ctx->d_fa_ids, nullptr, f.n_bases, f.n_reads, f.id_bytes };
+        mtr_fasta_dst dst = { fastq ? nullptr : (uint8_t *)ctx->d_fa_text, ctx->d_fa_off, ctx->d_fa_lens, ctx->d_fa_ids, nullptr, f.n_bases, f.n_reads, f.id_bytes };
         { mtr_status st = fasta_write(ctx, p, dst); if (st != MTR_OK) return st; }
         HIPCHK(hipMemcpyAsync(offs.data(), ctx->d_fa_off, n * 8, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(ctx->fa_lens.data(), ctx->d_fa_lens, n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2091,20 +2168,30 @@ static mtr_status upload_fasta(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *
     }
     ctx->fa_indexed = true;
     if (n == 0) return MTR_OK;                                    // no reads: nothing to upload
-    const DeviceText dt = { ctx->d_fa_text, f.n_bases, MTR_TEXT_ASCII, ctx->stream };
+    const DeviceText dt = { fastq ? d_fasta : (const uint8_t *)ctx->d_fa_text, fastq ? n_bytes : f.n_bases, MTR_TEXT_ASCII, ctx->stream };
     const mtr_status st = upload_batch(ctx, fs, nullptr, 0, nullptr, nullptr, offs.data(), ctx->fa_lens.data(), f.n_reads, &dt);
     if (st != MTR_OK) { ctx->fa_indexed = false; if (!ctx->pending) free_batch(ctx); }       // as a refused mtr_upload_batch_device: no batch is left
     return st;
 }
 extern "C" mtr_status mtr_upload_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info)
 {
-    return upload_fasta(ctx, nullptr, d_fasta, n_bytes, wait_stream, info);
+    return upload_fasta(ctx, nullptr, false, d_fasta, n_bytes, wait_stream, info);
 }
 extern "C" mtr_status mtr_upload_fasta_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream,
                                                       mtr_fasta_info *info)
 {
     if (!fs) { if (ctx) ctx->err = "null file state"; return MTR_ERR_BAD_ARG; }
-    return upload_fasta(ctx, fs, d_fasta, n_bytes, wait_stream, info);
+    return upload_fasta(ctx, fs, false, d_fasta, n_bytes, wait_stream, info);
+}
+extern "C" mtr_status mtr_upload_fastq_device(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info)
+{
+    return upload_fasta(ctx, nullptr, true, d_fastq, n_bytes, wait_stream, info);
+}
+extern "C" mtr_status mtr_upload_fastq_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fastq, int64_t n_bytes, void *wait_stream,
+                                                      mtr_fasta_info *info)
+{
+    if (!fs) { if (ctx) ctx->err = "null file state"; return MTR_ERR_BAD_ARG; }
+    return upload_fasta(ctx, fs, true, d_fastq, n_bytes, wait_stream, info);
 }
 
 extern "C" mtr_status mtr_fasta_index(const mtr_ctx *ctx, int32_t *lens, int64_t *id_off, char *ids)

@@ -1813,7 +1813,11 @@ DEVINL void k2_range_walks(K2Ctx &c, int qs, int qe, int w, RangeP1 &st, int k_f
     for (int k = k0; k <= k1; k++) {
         const int lim = qe < c.L - k + 1 ? qe : c.L - k + 1;
         const int n_raw = qe - lim + 1;
-        if (freq_bound + n_raw <= MTRC_MIN_NUM_FREQ_UNIT) { wc_add(c.wc, CNT_TABLES_SKIPPED, 1); continue; }
+        if (freq_bound + n_raw <= MTRC_MIN_NUM_FREQ_UNIT) {
+            wc_add(c.wc, CNT_TABLES_SKIPPED, 1);
+            trace_ev(c, 2, qs, qe, k, 0, 0, -1, -1, -1, -1, -1, -1, -1, -1, -1);      // the search's answer all the same: no walk, the cleared record
+            continue;
+        }
         const int ki = k - min_k;
         int max_freq, e_of[2];
         const int found = search_walks(c, qs, qe, k, max_freq, n_ent, e_of);

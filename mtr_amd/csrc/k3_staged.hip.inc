@@ -431,8 +431,12 @@ __global__ __launch_bounds__(64, MTR_WAVES_PER_SIMD) void mtr_k_walks(K2Args a, 
         for (int k = k_last + 1; k <= max_k; k++) {
             const int lim = qe < c.L - k + 1 ? qe : c.L - k + 1;
             if (bound + (qe - lim + 1) > MTRC_MIN_NUM_FREQ_UNIT) alive |= 1u << (k - min_k);
-            else wc_add(c.wc, CNT_TABLES_SKIPPED, 1);
+            else { wc_add(c.wc, CNT_TABLES_SKIPPED, 1); trace_ev(c, 2, qs, qe, k, 0, 0, -1, -1, -1, -1, -1, -1, -1, -1, -1); }
         }
+        // the trace's event 2 of a range WITH a block comes from mtr_k_select; a range without one has no candidate at any k: the cleared record for each k searched
+        if (st.n_ent == 0 && alive == 0u && trace_on(c, 2))
+            for (int k = min_k; k <= k_last; k++) if ((st.run_mask >> (k - min_k)) & 1u)
+                trace_ev(c, 2, qs, qe, k, (int)((st.found_mask >> (k - min_k)) & 1u), 0, -1, -1, -1, -1, -1, -1, -1, -1, -1);
         if (st.n_ent > 0 || alive != 0u) {
             const int n_slots = 2 * (max_k - min_k + 1), maxU = st_max_unit(qs, qe);
             const int stride = (int)(st_pad16(maxU) + st_pad16(4ll * maxU));

@@ -63,6 +63,7 @@ struct mtro_ctx {
     int tab_k;
     int *direct;        /* 4^6 counts */
     int *hkey, *hval; size_t hcap, hmask;
+    int last_max_freq, last_n_seeds; int last_seeds[MAX_SEEDS];   /* of the latest search_unit (mtro_search_unit reports them) */
     /* DP matrix */
     int *dp; size_t dp_cap;
     char *al_in, *al_sym, *al_rep; size_t al_cap;
@@ -561,6 +562,7 @@ static int search_unit(mtro_ctx *c, int qs, int qe, rr_t *r)
     tab_build(c, k, qs, qe);
     int seeds[MAX_SEEDS], max_freq;
     int ns = tab_seeds(c, width, seeds, MAX_SEEDS, &max_freq);
+    c->last_max_freq = max_freq; c->last_n_seeds = ns; memcpy(c->last_seeds, seeds, (size_t)ns * sizeof(int));
     rr_t best, t; rr_clear(&best);
     float best_ratio = -1;
     int found = 0;
@@ -855,6 +857,43 @@ int mtro_wrap_dp(const uint8_t *codes, int L, int qs, int qe, const uint8_t *uni
     }
     mtro_destroy(c);
     return rc;
+}
+
+/* search_De_Bruijn_graph for one (window, k) of a read, as find_tandem_repeat_sub calls it: the record is what the G2
+ * capture line shows (NOT yet cleared where found = 0, handle_one_read.c:84) */
+int mtro_search_unit(mtro_ctx *c, const uint8_t *codes, int L, int qs, int qe, int k, mtro_search_result *out)
+{
+    if (c->file_order || L <= 0 || L > MTRO_MAX_INPUT_LENGTH || qs < 0 || qe < qs || qe >= L || k < 1 || k > MAX_KMER) return -1;
+    FILE *cap = c->cap; c->cap = NULL;                     /* a stand-alone call leaves no capture line */
+    load_read(c, codes, L);
+    rr_t t; rr_clear(&t); t.kmer = k;
+    int found = search_unit(c, qs, qe, &t);
+    c->cap = cap;
+    memset(out, 0, sizeof(*out));
+    out->found = found; out->period = t.rep_period; out->rep_start = t.rep_start; out->rep_end = t.rep_end;
+    out->repeat_len = t.repeat_len; out->copies = t.copies; out->mat = t.mat; out->mis = t.mis; out->ins = t.ins; out->del = t.del;
+    out->max_freq = c->last_max_freq; out->n_seeds = c->last_n_seeds;
+    memcpy(out->seeds, c->last_seeds, (size_t)c->last_n_seeds * sizeof(int));
+    if (t.rep_period > 0 && t.rep_period < MAX_PERIOD) strcpy(out->unit, t.str);      /* as cap_rr prints it */
+    return found;
+}
+
+/* one walk() on the table of (window, k) as search_De_Bruijn_graph leaves it for its walks: built, then every listed seed
+ * counted down once (consensus.c:160,209).  out_unit: room for MTRO_MAX_PERIOD + 1 characters. */
+int mtro_walk(mtro_ctx *c, const uint8_t *codes, int L, int qs, int qe, int k, int backward, int seed, int *out_period, char *out_unit)
+{
+    if (c->file_order || L <= 0 || L > MTRO_MAX_INPUT_LENGTH || qs < 0 || qe < qs || qe >= L || k < 1 || k > MAX_KMER ||
+        seed < 0 || seed >= POW4[k]) return -1;
+    load_read(c, codes, L);
+    tab_build(c, k, qs, qe);
+    int seeds[MAX_SEEDS], max_freq;
+    (void)tab_seeds(c, qe - qs + 1, seeds, MAX_SEEDS, &max_freq);
+    rr_t t; rr_clear(&t); t.kmer = k;
+    int found = walk(c, backward ? 1 : 0, qs, qe, k, seed, &t);
+    *out_period = t.rep_period;
+    out_unit[0] = 0;
+    if (found) strcpy(out_unit, t.str);
+    return found;
 }
 
 /* ================================================================================================

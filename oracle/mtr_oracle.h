@@ -80,6 +80,22 @@ typedef struct {
 /* wrap_around_DP_sub (wrap_around_DP.c:222-354) on codes[] with org[p>=L]=0 */
 int mtro_wrap_dp(const uint8_t *codes, int L, int query_start, int query_end, const uint8_t *unit, int unit_len,
                  int G, int MM, int D, mtro_dp_result *res);
+/* search_De_Bruijn_graph (consensus.c:507-582) for ONE (window, k) of a read under isolated semantics: the found flag
+ * (that of the last walk) and the record as capture point G2 shows it - every field -1 where no walk's unit
+ * passed the selection; unit = "" unless 0 < period < MTRO_MAX_PERIOD.  Also what the search started from: the window's
+ * maximum node count (no walk is made unless it exceeds 5, :532) and the seeds in the order they are tried.
+ * Returns found, or <0 on bad arguments (or a file-order context). */
+typedef struct {
+    int32_t found, period, rep_start, rep_end, repeat_len, copies, mat, mis, ins, del;
+    int32_t max_freq, n_seeds, seeds[100];
+    char    unit[MTRO_MAX_PERIOD + 4];
+} mtro_search_result;
+int mtro_search_unit(mtro_ctx *, const uint8_t *codes, int L, int query_start, int query_end, int k, mtro_search_result *out);
+/* one greedy walk (consensus.c:269-505) from `seed` on the same table, forward or backward: *out_period = the unit's
+ * length, 0 if the walk does not return to the seed (or only after MTRO_MAX_PERIOD steps); out_unit (MTRO_MAX_PERIOD + 1
+ * characters) = the unit, "" if none.  Returns 1 if the walk closed, 0 if not, <0 on bad arguments. */
+int mtro_walk(mtro_ctx *, const uint8_t *codes, int L, int query_start, int query_end, int k, int backward, int seed,
+              int *out_period, char *out_unit);
 /* fill_directional_index_with_end (+ de-dup); arrays of length L; returns number of usable ranges */
 int mtro_ranges(mtro_ctx *, const uint8_t *codes, int L, double *di, int32_t *end, int32_t *w);
 /* the MT19937 stream (MT.h) after init_genrand(0): out[i] = genrand_int32() % 4 */

@@ -35,6 +35,11 @@ class ODpResult(C.Structure):
                                          "num_mismatches", "num_insertions", "num_deletions")]
 
 
+class OSearchResult(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("found", "period", "rep_start", "rep_end", "repeat_len", "copies", "mat", "mis", "ins", "del_",
+                                         "max_freq", "n_seeds")] + [("seeds", C.c_int32 * 100), ("unit", C.c_char * (MAX_PERIOD + 4))]
+
+
 _lib = None
 _libc = C.CDLL(None)
 _libc.free.argtypes = [C.c_void_p]
@@ -61,6 +66,10 @@ def load(build: bool = True):
     lib.mtro_ranges.restype = C.c_int
     lib.mtro_wrap_dp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ODpResult)]
     lib.mtro_wrap_dp.restype = C.c_int
+    lib.mtro_search_unit.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OSearchResult)]
+    lib.mtro_search_unit.restype = C.c_int
+    lib.mtro_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_char_p]
+    lib.mtro_walk.restype = C.c_int
     lib.mtro_mt_bases.argtypes = [C.c_void_p, C.c_int]
     lib.mtro_chain.argtypes = [C.POINTER(ORecord), C.c_int, C.c_void_p]
     lib.mtro_chain.restype = C.c_int
@@ -115,6 +124,28 @@ class Oracle:
         bits = di.view(np.uint64)
         idx = np.nonzero((end > -1) & (end < L) & (di != -1.0))[0]
         return [(int(i), int(end[i]), int(w[i]), int(bits[i])) for i in idx]
+
+    def search_unit(self, codes: np.ndarray, qs: int, qe: int, k: int):
+        """search_De_Bruijn_graph for one (window, k) -> dict: found, the nine fields of capture point G2 (period, rep_start, rep_end,
+        repeat_len, copies, mat, mis, ins, del), unit, and what the search started from (max_freq, seeds in the order they are tried)"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        r = OSearchResult()
+        rc = self.lib.mtro_search_unit(self.h, codes.ctypes.data, len(codes), qs, qe, k, C.byref(r))
+        if rc < 0:
+            raise ValueError("mtro_search_unit: bad arguments")
+        return {"found": r.found, "period": r.period, "rep_start": r.rep_start, "rep_end": r.rep_end, "repeat_len": r.repeat_len,
+                "copies": r.copies, "mat": r.mat, "mis": r.mis, "ins": r.ins, "del": r.del_, "unit": r.unit.decode(),
+                "max_freq": r.max_freq, "seeds": list(r.seeds[:r.n_seeds])}
+
+    def walk(self, codes: np.ndarray, qs: int, qe: int, k: int, backward: bool, seed: int):
+        """one greedy walk from `seed` on the table of (window, k) -> (period, unit); period 0 = the walk did not close"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        period = C.c_int(0)
+        unit = C.create_string_buffer(MAX_PERIOD + 4)
+        rc = self.lib.mtro_walk(self.h, codes.ctypes.data, len(codes), qs, qe, k, 1 if backward else 0, seed, C.byref(period), unit)
+        if rc < 0:
+            raise ValueError("mtro_walk: bad arguments")
+        return period.value, unit.value.decode()
 
     def wrap_dp(self, codes: np.ndarray, qs: int, qe: int, unit: np.ndarray, G: int, MM: int, D: int):
         codes = np.ascontiguousarray(codes, dtype=np.uint8)

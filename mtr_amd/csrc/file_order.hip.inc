@@ -2,7 +2,8 @@
 // mtr_upload_fasta_device_in_file): what a read finds beyond its own part of the reference's two whole-file buffers, made
 // on the device from the packed words of the reads that left it there.  No base crosses to the host.
 //
-// The host keeps the staircase over lengths only (mtr_file_state, mtr_abi.hip) and hands the kernels
+// The host keeps the staircase over lengths only and plans a batch with the same walk over it as the host feed (mtr_file_state::walk,
+// plan_device, file_state.h); fo_launch (mtr_abi.hip) hands the kernels
 //   segments   the stale tails of the batch, cut where their owner changes: FoSeg = (owner's words, owner's geometry, first
 //              entry, first position), in entry order.  An owner is an earlier read of this batch (its words in the batch's
 //              packed image) or a stair of the state (its words in the state's storage).

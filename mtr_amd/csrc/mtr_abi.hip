@@ -28,6 +28,7 @@
 #include "../../include/mtr_hip.h"
 #include "../../include/mtr_hip_test.h"
 #include "mtr_common.h"
+#include "file_state.h"
 #include "k1_ranges.hip.inc"
 #include "k2_units.hip.inc"
 #include "k3_staged.hip.inc"
@@ -42,28 +43,6 @@
 static_assert(sizeof(DevRecord) == sizeof(mtr_record), "device and ABI record layouts must agree");
 static_assert(MTR_N_COUNTERS == CNT_N, "counter count");
 static_assert(MTR_MAX_READ_LENGTH == MTRC_MAX_SUPPORTED_LENGTH, "read length limit");
-
-// ---- MT19937 (reference MT.h = stock mt19937ar), host-precomputed base stream -------------------------
-static void mt_bases(std::vector<uint8_t> &out, size_t n)
-{
-    uint32_t s[624];
-    s[0] = 0u;                                                   // init_genrand(0), fill_directional_index.c:140
-    for (int i = 1; i < 624; i++) s[i] = 1812433253u * (s[i - 1] ^ (s[i - 1] >> 30)) + (uint32_t)i;
-    int idx = 624;
-    out.resize(n);
-    for (size_t t = 0; t < n; t++) {
-        if (idx >= 624) {
-            for (int i = 0; i < 624; i++) {
-                uint32_t y = (s[i] & 0x80000000u) | (s[(i + 1) % 624] & 0x7fffffffu);
-                s[i] = s[(i + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-            }
-            idx = 0;
-        }
-        uint32_t y = s[idx++];
-        y ^= y >> 11; y ^= (y << 7) & 0x9d2c5680u; y ^= (y << 15) & 0xefc60000u; y ^= y >> 18;
-        out[t] = (uint8_t)(y % 4u);                              // random_base(), fill_directional_index.c:131
-    }
-}
 
 // A buffer of the context: grow-only (hipMalloc / hipFree cost ~0.1-0.5 ms each; a dozen of them per batch were a third of a single
 // read's latency), freed with the context.  It converts to its raw pointer, which is what the kernels and the copies are given.
@@ -160,7 +139,7 @@ struct mtr_ctx {
     RunSwitches sw = {};                             // of the current launch
     // resident batch
     int n_reads = 0, Lmax = 0;
-    std::vector<int32_t> lens; std::vector<int64_t> roff;
+    std::vector<int32_t> lens, order; std::vector<int64_t> roff;      // order: longest first (work balance)
     long long packed_words = 0;
     long long st_last_arena_cap = 0;
     int32_t st_cand_cap = 0;
@@ -179,7 +158,7 @@ struct mtr_ctx {
     DevBuf<int32_t> d_item_read, d_item_idx; DevBuf<int64_t> d_item_off;
     bool last_staged = false;
     StagedBufs st;                     // staged mode (k3_staged.hip.inc)
-    // cost-ordered queue of the per-read unit kernel
+    // cost-ordered queue of the file-order path (launch_two_kernels)
     DevBuf<unsigned> d_lpt_count; DevBuf<int32_t> d_lpt_start, d_lpt_bin, d_lpt_rank, d_lpt_order;
     // reads that found more records than their max_rec slots are run again with room for all of them (resolve_overflow)
     std::vector<int32_t> ovf_reads; int ovf_cap = 0;
@@ -238,80 +217,11 @@ static struct { uint8_t *d = nullptr; int refs = 0; } g_mt[64];
 static std::vector<uint8_t> g_mt_host;
 static const std::vector<uint8_t> &mt_host()
 {   // callers hold g_mt_mu
-    if (g_mt_host.empty()) mt_bases(g_mt_host, (size_t)MTRC_MAX_INPUT_LENGTH + 2 * 100000 + 64);
+    if (g_mt_host.empty()) mt_bases(g_mt_host, MTR_MT_BASES);
     return g_mt_host;
 }
 
-// ---- file-order mode: the host shadow of the reference's process-wide buffers ---------------------------------------
-// The reference keeps inputString_w_rand and orgInputString for the whole file (handle_one_file.c:85, mTR.h:65-67).  A
-// read rewrites [0, E) of the first (E = max(L + 2r, min(L + 4r, 1e6)), fill_directional_index.c:137-169, three times:
-// k = 1, 3, 5, so it LEAVES the k = 5 encoding) and [0, L) of the second; the passes of the next read look up to
-// L + r + 2w - k (:232) and its DPs up to org[L + 1], i.e. into what the most recent LONGER read left there.
-// That state is a staircase: of all earlier reads only those longer than every read after them still show.
-//
-// A state is fed either from the host (mtr_upload_batch_in_file, mtr_file_state_skip: every stair keeps its base codes here) or from
-// device memory (mtr_upload_batch_device_in_file, mtr_upload_fasta_device_in_file, mtr_file_state_skip_device).  A device-fed state
-// keeps the stairs' geometry here - lengths only - and their 2-bit words in device memory of its own (d_store): a stack like the
-// staircase itself, stair k at words [woff, woff + mtr_packed_words(L)), so the survivors of a batch are a prefix of it and the
-// new stairs are appended, device to device, from the batch's packed image.  Its bases never reach the host.
-struct mtr_file_state {
-    struct Entry { int32_t L = 0, r = 0; int64_t N = 0, n = 0, E = 0; std::vector<uint8_t> codes; int64_t woff = 0; };
-    enum Kind { UNFED = 0, HOST_FED = 1, DEVICE_FED = 2 };
-    std::vector<Entry> stairs;               // E (and L) strictly increasing from back() = most recent to front()
-    std::vector<uint8_t> mt;                 // the MT19937 base stream (same as the device's)
-    int64_t reads_seen = 0;
-    int kind = UNFED, device = -1;           // fixed by the first feed; device: the GPU of the context that fed it
-    uint32_t *d_store = nullptr; int64_t store_cap = 0;      // device-fed: the stairs' words, capacity in words
-    int64_t store_top() const { return stairs.empty() ? 0 : stairs.back().woff + mtr_packed_words(stairs.back().L); }
-    int raw(const Entry &e, int64_t q) const
-    {   // the buffer before the rolling encode, as k1_raw (k1_ranges.hip.inc)
-        if (q < e.r) return mt[(size_t)(e.N + q)];
-        if (q < e.r + e.L) return e.codes[(size_t)(q - e.r)];
-        if (q < e.n) return mt[(size_t)(e.N + e.r + (q - e.r - e.L))];
-        return mt[(size_t)q];                // q < N
-    }
-    int left_at(const Entry &e, int64_t p) const
-    {   // what the read left at p < E: the 5-mer code where one was formed (:162-168), else the raw entry
-        if (p < e.n - 4) { int v = 0; for (int t = 0; t < 5; t++) v = 4 * v + raw(e, p + t); return v; }
-        return raw(e, p);
-    }
-    static void geometry(int32_t L, Entry &e)
-    {
-        e.L = L; e.r = mtrc_rand_len(L); e.n = (int64_t)L + 2 * e.r;
-        e.N = std::min<int64_t>((int64_t)L + 4 * (int64_t)e.r, MTRC_MAX_INPUT_LENGTH);
-        e.E = std::max(e.N, e.n);
-    }
-    // the entries [E, reach) of inputString_w_rand as the NEXT read of length L finds them
-    void tail_for(int32_t L, std::vector<uint16_t> &out) const
-    {
-        Entry me; geometry(L, me);
-        int wtop = 0;
-        for (int w = MTRC_MIN_WINDOW; w <= MTRC_MAX_WINDOW && w < L / 2; w *= 2) wtop = w;
-        const int64_t reach = std::max<int64_t>((int64_t)L + me.r + 2 * wtop + 8, me.E);      // = ncode of k1_read
-        int64_t cur = me.E;
-        for (size_t k = stairs.size(); k-- > 0 && cur < reach; ) {
-            const Entry &e = stairs[k];
-            if (e.E <= cur) continue;
-            const int64_t end = std::min(e.E, reach);
-            for (int64_t p = cur; p < end; p++) out.push_back((uint16_t)left_at(e, p));
-            cur = end;
-        }
-    }
-    int org_at(int64_t p) const
-    {   // orgInputString[p] for p >= the length of the next read
-        for (size_t k = stairs.size(); k-- > 0; ) if (stairs[k].L > p) return stairs[k].codes[(size_t)p];
-        return 0;
-    }
-    void push(const uint8_t *codes, int32_t L)
-    {
-        Entry e; geometry(L, e);
-        while (!stairs.empty() && stairs.back().L <= L) stairs.pop_back();
-        e.codes.assign(codes, codes + L);
-        stairs.push_back(std::move(e));
-        reads_seen++; kind = HOST_FED;
-    }
-};
-
+// ---- file-order mode: the state itself is file_state.h; here its entry points and, with the uploads below, its device storage ----
 extern "C" mtr_status mtr_file_state_create(mtr_file_state **out)
 {
     if (!out) return MTR_ERR_BAD_ARG;
@@ -326,14 +236,23 @@ extern "C" void mtr_file_state_destroy(mtr_file_state *fs)
     if (fs && fs->d_store) { (void)hipSetDevice(fs->device); (void)hipFree(fs->d_store); }
     delete fs;
 }
+// every length inside 1..MTRC_MAX_SUPPORTED_LENGTH?  err (may be NULL): the reason
+static bool check_lengths(const int32_t *lens, int32_t n, std::string *err)
+{
+    for (int i = 0; i < n; i++)
+        if (lens[i] <= 0 || lens[i] > MTRC_MAX_SUPPORTED_LENGTH) {
+            if (err) *err = "read " + std::to_string(i) + ": length " + std::to_string(lens[i]) + " outside 1.." + std::to_string(MTRC_MAX_SUPPORTED_LENGTH);
+            return false;
+        }
+    return true;
+}
 extern "C" mtr_status mtr_file_state_skip(mtr_file_state *fs, const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n)
 {
     if (!fs || !bases || !offsets || !lens || n < 0) return MTR_ERR_BAD_ARG;
     if (fs->kind == mtr_file_state::DEVICE_FED) return MTR_ERR_BAD_ARG;          // (no context to leave a reason in)
-    for (int i = 0; i < n; i++) {
-        if (lens[i] <= 0 || lens[i] > MTRC_MAX_SUPPORTED_LENGTH) return MTR_ERR_BAD_ARG;
-        fs->push(bases + offsets[i], lens[i]);
-    }
+    if (!check_lengths(lens, n, nullptr)) return MTR_ERR_BAD_ARG;
+    if (n == 0) return MTR_OK;
+    fs->adopt_host(mtr_file_state::skipped(fs->stairs, lens, n), bases, offsets, n);
     return MTR_OK;
 }
 
@@ -478,44 +397,13 @@ static int pick_waves(mtr_ctx *ctx, int n_items, int per_cu, size_t per_wave, si
     return (int)waves;
 }
 
-// reads given as text in device memory (mtr_upload_batch_device)
-struct DeviceText { const uint8_t *d; int64_t bytes; int32_t kind; hipStream_t wait; };
-static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t *packed_in, int64_t n_words_in, const int64_t *woff_in,
-                               const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n, const DeviceText *dt = nullptr);
-extern "C" mtr_status mtr_upload_batch(mtr_ctx *ctx, const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n)
-{
-    if (ctx && (!bases || !offsets)) { ctx->err = "null input"; return MTR_ERR_BAD_ARG; }
-    return upload_batch(ctx, nullptr, nullptr, 0, nullptr, bases, offsets, lens, n);
-}
-extern "C" mtr_status mtr_upload_batch_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n)
-{
-    if (!fs) { if (ctx) ctx->err = "null file state"; return MTR_ERR_BAD_ARG; }
-    if (ctx && (!bases || !offsets)) { ctx->err = "null input"; return MTR_ERR_BAD_ARG; }
-    return upload_batch(ctx, fs, nullptr, 0, nullptr, bases, offsets, lens, n);
-}
-extern "C" mtr_status mtr_upload_batch_packed(mtr_ctx *ctx, const uint32_t *packed, int64_t n_words, const int64_t *woff, const int32_t *lens, int32_t n)
-{
-    if (ctx && (!packed || !woff || n_words <= 0)) { ctx->err = "null input"; return MTR_ERR_BAD_ARG; }
-    return upload_batch(ctx, nullptr, packed, n_words, woff, nullptr, nullptr, lens, n);
-}
-extern "C" mtr_status mtr_upload_batch_device(mtr_ctx *ctx, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
-                                              const int32_t *lens, int32_t n, int32_t text_kind, void *wait_stream)
-{
-    const DeviceText dt = { d_text, text_bytes, text_kind, (hipStream_t)wait_stream };
-    const mtr_status st = upload_batch(ctx, nullptr, nullptr, 0, nullptr, nullptr, offsets, lens, n, &dt);
-    if (st != MTR_OK && ctx && !ctx->pending) free_batch(ctx);          // a refused device upload leaves no batch behind
-    return st;
-}
-
-extern "C" mtr_status mtr_upload_batch_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
-                                                      const int32_t *lens, int32_t n, int32_t text_kind, void *wait_stream)
-{
-    if (!fs) { if (ctx) ctx->err = "null file state"; return MTR_ERR_BAD_ARG; }
-    const DeviceText dt = { d_text, text_bytes, text_kind, (hipStream_t)wait_stream };
-    const mtr_status st = upload_batch(ctx, fs, nullptr, 0, nullptr, nullptr, offsets, lens, n, &dt);
-    if (st != MTR_OK && ctx && !ctx->pending) free_batch(ctx);          // a refused device upload leaves no batch behind, and the state as it was
-    return st;
-}
+// ---- upload: reads become the resident batch ------------------------------------------------------------------------------------------
+// They come from one of three sources, each with a function of its own made of the steps below: base codes on the host (upload_codes), a
+// packed image on the host (upload_packed), text in device memory (upload_text).  File-order mode (fs) is a mode of the first and the last.
+struct HostCodes { const uint8_t *bases; const int64_t *offsets; };                       // read i = bases[offsets[i] .. + lens[i]), codes 0..3
+struct HostPacked { const uint32_t *words; int64_t n_words; const int64_t *woff; };        // the device layout, made by the caller (mtr_pack_read)
+// read i = d[offsets[i] .. + lens[i]) in device memory (mtr_upload_batch_device); wait: the stream that wrote it
+struct DeviceText { const uint8_t *d; int64_t bytes; const int64_t *offsets; int32_t kind; hipStream_t wait; };
 
 // bytes .. of d must be device memory of the context's GPU, inside one allocation (what / what_bytes: the arguments' names in the reason)
 static mtr_status check_device_ptr(mtr_ctx *ctx, const uint8_t *d, int64_t bytes, const char *what, const char *what_bytes)
@@ -539,25 +427,19 @@ static mtr_status check_device_ptr(mtr_ctx *ctx, const uint8_t *d, int64_t bytes
 }
 
 // the arguments of a device upload that the host can check (after free_batch: a refused upload leaves no batch behind)
-static mtr_status check_device_text(mtr_ctx *ctx, const DeviceText &dt, const int64_t *offsets, const int32_t *lens, int32_t n)
+static mtr_status check_device_text(mtr_ctx *ctx, const DeviceText &dt, const int32_t *lens, int32_t n)
 {
-    if (!dt.d || !offsets) { ctx->err = "null input"; return MTR_ERR_BAD_ARG; }
+    if (!dt.d || !dt.offsets) { ctx->err = "null input"; return MTR_ERR_BAD_ARG; }
     if (dt.bytes <= 0) { ctx->err = "text_bytes " + std::to_string(dt.bytes) + " <= 0"; return MTR_ERR_BAD_ARG; }
     if (dt.kind != MTR_TEXT_ASCII && dt.kind != MTR_TEXT_CODES) { ctx->err = "unknown text_kind " + std::to_string(dt.kind); return MTR_ERR_BAD_ARG; }
     for (int i = 0; i < n; i++)
-        if (offsets[i] < 0 || offsets[i] > dt.bytes - lens[i]) {
-            ctx->err = "read " + std::to_string(i) + ": bytes " + std::to_string(offsets[i]) + " .. +" + std::to_string(lens[i]) + " outside the text of " +
+        if (dt.offsets[i] < 0 || dt.offsets[i] > dt.bytes - lens[i]) {
+            ctx->err = "read " + std::to_string(i) + ": bytes " + std::to_string(dt.offsets[i]) + " .. +" + std::to_string(lens[i]) + " outside the text of " +
                        std::to_string(dt.bytes) + " bytes";
             return MTR_ERR_BAD_ARG;
         }
     return check_device_ptr(ctx, dt.d, dt.bytes, "d_text", "text_bytes");
 }
-
-
-// ---- file-order mode for device input (file_order.hip.inc): the staircase search over lengths, the launches, the state's storage ----
-// One step of the working staircase of a batch: a stair of the state as the batch found it (owner = ~its index) or a read of the batch (owner = its index)
-struct FoWork { int32_t L, r; int64_t N, n, E; int32_t owner; };
-struct FoPlan { std::vector<FoWork> work; std::vector<FoSeg> segs; std::vector<int64_t> tail_off; std::vector<FoAfter> own; };
 
 // may this context continue fs with a feed of kind `want`?
 static mtr_status fo_check_kind(mtr_ctx *ctx, const mtr_file_state *fs, int want)
@@ -574,48 +456,131 @@ static mtr_status fo_check_kind(mtr_ctx *ctx, const mtr_file_state *fs, int want
     return MTR_OK;
 }
 
-// What upload_batch's host loop does with the bases, over lengths only: the reads of the batch in file order against the state's stairs and
-// each other.  p.work ends as the staircase after the batch.  tails: also each read's tail as segments by owner (mtr_file_state::tail_for)
-// and the owners of its positions L, L + 1 (org_at); an owner's words are in `batch` at woff[owner] or in the state's storage.
-static void fo_plan(const mtr_file_state *fs, const uint32_t *batch, const int64_t *woff, const int32_t *lens, int32_t n, bool tails, FoPlan &p)
+// what every upload begins with: the arguments all sources share, a state of the right kind, and the batch before this one gone
+static mtr_status upload_begin(mtr_ctx *ctx, const mtr_file_state *fs, int feed, const int32_t *lens, int32_t n)
 {
-    p.work.clear(); p.segs.clear();
-    for (size_t k = 0; k < fs->stairs.size(); k++) {
-        const mtr_file_state::Entry &e = fs->stairs[k];
-        p.work.push_back(FoWork{ e.L, e.r, e.N, e.n, e.E, ~(int32_t)k });
-    }
-    auto words = [&](const FoWork &o) { return o.owner < 0 ? fs->d_store + fs->stairs[(size_t)~o.owner].woff : batch + woff[o.owner]; };
-    if (tails) { p.tail_off.assign((size_t)n + 1, 0); p.own.assign((size_t)n, FoAfter{ { nullptr, nullptr } }); }
-    int64_t t = 0;
-    for (int32_t i = 0; i < n; i++) {
-        const int32_t L = lens[i];
-        mtr_file_state::Entry me; mtr_file_state::geometry(L, me);
-        if (tails) {
-            int wtop = 0;
-            for (int w = MTRC_MIN_WINDOW; w <= MTRC_MAX_WINDOW && w < L / 2; w *= 2) wtop = w;
-            const int64_t reach = std::max<int64_t>((int64_t)L + me.r + 2 * wtop + 8, me.E);
-            int64_t cur = me.E;
-            for (size_t k = p.work.size(); k-- > 0 && cur < reach; ) {
-                const FoWork &o = p.work[k];
-                if (o.E <= cur) continue;
-                const int64_t end = std::min(o.E, reach);
-                p.segs.push_back(FoSeg{ words(o), t, (int32_t)cur, o.L, o.r, (int32_t)o.N });
-                t += end - cur; cur = end;
-            }
-            p.tail_off[(size_t)i + 1] = t;
-            for (int d = 0; d < 2; d++)
-                for (size_t k = p.work.size(); k-- > 0; )
-                    if (p.work[k].L > L + d) { p.own[(size_t)i].w[d] = words(p.work[k]); break; }
-        }
-        while (!p.work.empty() && p.work.back().L <= L) p.work.pop_back();
-        p.work.push_back(FoWork{ me.L, me.r, me.N, me.n, me.E, i });
-    }
+    if (!ctx) return MTR_ERR_BAD_ARG;
+    if (!lens || n <= 0) { ctx->err = "null input or n_reads <= 0"; return MTR_ERR_BAD_ARG; }
+    if (fs) { mtr_status st = fo_check_kind(ctx, fs, feed); if (st != MTR_OK) return st; }
+    HIPCHK(hipSetDevice(ctx->device));
+    { mtr_status w = mtr_wait(ctx); if (w != MTR_OK && w != MTR_ERR_OVERFLOW && w != MTR_ERR_DP_TOO_LARGE) return w; }
+    free_batch(ctx);
+    return check_lengths(lens, n, &ctx->err) ? MTR_OK : MTR_ERR_BAD_ARG;
 }
+
+// the packed layout of reads stored one after the other: their word offsets; returns the words of all
+static int64_t word_layout(const int32_t *lens, int32_t n, std::vector<int64_t> &woff)
+{
+    woff.resize((size_t)n);
+    int64_t words = 0;
+    for (int i = 0; i < n; i++) { woff[(size_t)i] = words; words += mtr_packed_words(lens[i]); }
+    return words;
+}
+
+// the resident batch's host side and its buffers, sized for n reads in `words` words; nothing is enqueued
+static mtr_status size_batch(mtr_ctx *ctx, const int32_t *lens, int32_t n, int64_t words, bool file_order)
+{
+    ctx->file_order = file_order; ctx->tail_entries = 0; ctx->fo_tail_launches = 0; ctx->fo_tail_ms = 0;
+    ctx->after.assign((size_t)n * 2, 0);
+    ctx->roff.assign((size_t)n + 1, 0);
+    for (int i = 0; i < n; i++) ctx->roff[(size_t)i + 1] = ctx->roff[(size_t)i] + mtrc_range_cap(lens[i]);
+    ctx->total_rcap = ctx->roff[(size_t)n];
+    ctx->lens.assign(lens, lens + n);
+    ctx->order.resize((size_t)n); std::iota(ctx->order.begin(), ctx->order.end(), 0);
+    std::stable_sort(ctx->order.begin(), ctx->order.end(), [&](int a, int b) { return lens[a] > lens[b]; });
+    ctx->n_reads = n; ctx->Lmax = *std::max_element(lens, lens + n);
+    ctx->max_rec = 16 + ctx->Lmax / 100;
+    DBG("upload: %d reads checked and ordered", n);
+    HIPCHK(ctx->d_packed.ensure(((size_t)words + 80) * 4));      // + 80: the DP stages 64-word blocks, the last block must stay readable
+    HIPCHK(ctx->d_woff.ensure((size_t)n * 8)); HIPCHK(ctx->d_lens.ensure((size_t)n * 4)); HIPCHK(ctx->d_order.ensure((size_t)n * 4));
+    HIPCHK(ctx->d_roff.ensure(((size_t)n + 1) * 8)); HIPCHK(ctx->d_rcount.ensure((size_t)n * 4));
+    HIPCHK(ctx->d_rstart.ensure((size_t)ctx->total_rcap * 4)); HIPCHK(ctx->d_rend.ensure((size_t)ctx->total_rcap * 4));
+    HIPCHK(ctx->d_rw.ensure((size_t)ctx->total_rcap * 4)); HIPCHK(ctx->d_rdi.ensure((size_t)ctx->total_rcap * 8));
+    HIPCHK(ctx->d_records.ensure((size_t)n * (size_t)ctx->max_rec * sizeof(DevRecord)));
+    HIPCHK(ctx->d_reccount.ensure((size_t)n * 4)); HIPCHK(ctx->d_recoff.ensure(((size_t)n + 1) * 8)); HIPCHK(ctx->d_item_off.ensure(((size_t)n + 1) * 8));
+    DBG("upload: batch buffers ready");
+    return MTR_OK;
+}
+
+// enqueues: the zero words behind the image, the reads' word offsets and lengths
+static mtr_status enqueue_layout(mtr_ctx *ctx, const int32_t *lens, int32_t n, const int64_t *woff, int64_t words)
+{
+    HIPCHK(hipMemsetAsync(ctx->d_packed + words, 0, 80 * 4, ctx->stream));
+    ctx->packed_words = (long long)words + 80;
+    HIPCHK(hipMemcpyAsync(ctx->d_woff, woff, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_lens, lens, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    return MTR_OK;
+}
+
+// enqueues: the processing order and the reads' range slices, as size_batch left them in the context
+static mtr_status enqueue_order(mtr_ctx *ctx)
+{
+    HIPCHK(hipMemcpyAsync(ctx->d_order, ctx->order.data(), (size_t)ctx->n_reads * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_roff, ctx->roff.data(), ((size_t)ctx->n_reads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    return MTR_OK;
+}
+
+// Packs the reads of a device text into 2-bit words at dst, laid out by d_lens / d_woff (enqueued by the caller), with the kernel of
+// pack.hip.inc.  The text comes from the caller's stream: the kernel waits for it there, not for the whole device.  pack_text_result,
+// once everything else of the call is enqueued, synchronises and refuses the first read with a byte that is no base.
+static mtr_status pack_text_enqueue(mtr_ctx *ctx, const DeviceText &dt, int32_t n, int64_t words, const int32_t *d_lens, const int64_t *d_woff, uint32_t *dst)
+{
+    if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
+    HIPCHK(ctx->d_toff.ensure((size_t)n * 8)); HIPCHK(ctx->d_pack_bad.ensure(4));
+    HIPCHK(hipMemcpyAsync(ctx->d_toff, dt.offsets, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_pack_bad, 0x7f, 4, ctx->stream));
+    HIPCHK(hipEventRecord(ctx->ev_text, dt.wait));
+    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
+    const int64_t blocks = std::min<int64_t>((words + MTR_PACK_BLOCK - 1) / MTR_PACK_BLOCK, (int64_t)ctx->n_cu * 8);
+    hipLaunchKernelGGL(dt.kind == MTR_TEXT_ASCII ? mtr_k_pack_text<true> : mtr_k_pack_text<false>, dim3((unsigned)blocks), dim3(MTR_PACK_BLOCK), 0, ctx->stream,
+                       dt.d, (const int64_t *)ctx->d_toff, d_lens, d_woff, n, words, dst, (int32_t *)ctx->d_pack_bad);
+    HIPCHK(hipGetLastError());
+    return MTR_OK;
+}
+static mtr_status pack_text_result(mtr_ctx *ctx, const DeviceText &dt, int32_t n)
+{
+    int32_t first_bad = n;
+    hipError_t e = hipMemcpyAsync(&first_bad, ctx->d_pack_bad, 4, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);     // (whatever the copy said: nothing of this call stays pending)
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) { ctx->err = std::string("device upload: ") + hipGetErrorString(e); return MTR_ERR_HIP; }
+    if (first_bad < n) {
+        ctx->err = "read " + std::to_string(first_bad) + (dt.kind == MTR_TEXT_ASCII ? ": a byte that is not A, C, G, T, a, c, g or t" : ": base code > 3");
+        return MTR_ERR_BAD_ARG;
+    }
+    return MTR_OK;
+}
+
+// ---- file-order mode, host feed: what each read finds beyond its own part of the reference's two buffers, planned on the host ----
+// the plan; the two bases after each read go into its own words of the image, which are zero there
+static void fo_host_plan(const mtr_file_state *fs, const HostCodes &src, const int32_t *lens, int32_t n, const int64_t *woff, uint32_t *packed,
+                         mtr_file_state::HostPlan &p)
+{
+    fs->plan_host(src.bases, src.offsets, lens, n, p);
+    for (int i = 0; i < n; i++)
+        for (int64_t q = lens[i]; q < (int64_t)lens[i] + 2; q++)
+            packed[woff[i] + (q >> 4)] |= (uint32_t)p.after[(size_t)i * 2 + (size_t)(q - lens[i])] << (30 - 2 * (int)(q & 15));
+}
+// enqueues the tails of the sized batch
+static mtr_status fo_host_enqueue(mtr_ctx *ctx, const mtr_file_state::HostPlan &p)
+{
+    const size_t n = (size_t)ctx->n_reads;
+    ctx->after = p.after; ctx->tail_entries = (int64_t)p.tail.size();
+    HIPCHK(ctx->d_tail.ensure(std::max<size_t>(p.tail.size(), 1) * 2)); HIPCHK(ctx->d_tail_off.ensure((n + 1) * 8));
+    if (!p.tail.empty()) HIPCHK(hipMemcpyAsync(ctx->d_tail, p.tail.data(), p.tail.size() * 2, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_tail_off, p.tail_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    return MTR_OK;
+}
+
+// ---- file-order mode, device feed (file_order.hip.inc): the plan over lengths, the launches, the state's storage ----
+struct FoPlan { std::vector<FileStair> work; std::vector<FoSeg> segs; std::vector<int64_t> tail_off; std::vector<FoAfter> own; };
 
 // the tails and the after-bases of the batch whose packing kernel has just been enqueued: plan, copies and the two kernels, enqueued only
 static mtr_status fo_launch(mtr_ctx *ctx, const mtr_file_state *fs, const int64_t *woff, const int32_t *lens, int32_t n, FoPlan &p)
 {
-    fo_plan(fs, ctx->d_packed, woff, lens, n, true, p);
+    // an owner's words: a stair's in the state's storage, a read's of this batch in its packed image
+    fs->plan_device(lens, n, [&](const FileStair &o) -> const uint32_t * { return o.read < 0 ? fs->d_store + o.woff : ctx->d_packed + woff[o.read]; },
+                    p.work, p.segs, p.tail_off, p.own);
     const int64_t entries = p.tail_off[(size_t)n];
     const size_t n_segs = p.segs.size();
     HIPCHK(ctx->d_tail.ensure((size_t)std::max<int64_t>(entries, 1) * 2)); HIPCHK(ctx->d_tail_off.ensure(((size_t)n + 1) * 8));
@@ -661,150 +626,116 @@ static mtr_status fo_reserve(mtr_ctx *ctx, mtr_file_state *fs, int64_t need, int
     return MTR_OK;
 }
 
-// The staircase after the batch (work) becomes the state's.  The stairs that survived are a prefix of the storage and stay; the new ones are
+// The planned staircase (work) becomes the state's.  The stairs that survived are a prefix of the storage and stay; the new ones are
 // copied behind them from `batch`, device to device.  The state's stairs change after the last step that can fail.
-static mtr_status fo_commit(mtr_ctx *ctx, mtr_file_state *fs, const std::vector<FoWork> &work, const uint32_t *batch, const int64_t *woff, int32_t n)
+static mtr_status fo_commit(mtr_ctx *ctx, mtr_file_state *fs, std::vector<FileStair> &&work, const uint32_t *batch, const int64_t *woff, int32_t n)
 {
-    size_t kept = 0;
-    while (kept < work.size() && work[kept].owner < 0) kept++;
-    const int64_t top = kept ? fs->stairs[kept - 1].woff + mtr_packed_words(fs->stairs[kept - 1].L) : 0;
-    int64_t need = top;
-    for (size_t k = kept; k < work.size(); k++) need += mtr_packed_words(work[k].L);
+    const mtr_file_state::Survivors s = mtr_file_state::survivors(work);
     // (batch may be the storage's own staging area, mtr_file_state_skip_device: it was reserved by the caller, so nothing moves here)
-    { mtr_status st = fo_reserve(ctx, fs, need, top); if (st != MTR_OK) return st; }
-    std::vector<mtr_file_state::Entry> fresh;
-    int64_t at = top;
-    for (size_t k = kept; k < work.size(); k++) {
-        const FoWork &o = work[k];
-        HIPCHK(hipMemcpyAsync(fs->d_store + at, batch + woff[o.owner], (size_t)mtr_packed_words(o.L) * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        mtr_file_state::Entry e; e.L = o.L; e.r = o.r; e.N = o.N; e.n = o.n; e.E = o.E; e.woff = at;
-        fresh.push_back(std::move(e));
+    { mtr_status st = fo_reserve(ctx, fs, s.top + s.fresh, s.top); if (st != MTR_OK) return st; }
+    int64_t at = s.top;
+    for (size_t k = s.kept; k < work.size(); k++) {
+        FileStair &o = work[k];
+        HIPCHK(hipMemcpyAsync(fs->d_store + at, batch + woff[o.read], (size_t)mtr_packed_words(o.L) * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        o.woff = at; o.read = -1;
         at += mtr_packed_words(o.L);
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    fs->stairs.resize(kept);
-    for (auto &e : fresh) fs->stairs.push_back(std::move(e));
+    fs->stairs = std::move(work);
     fs->reads_seen += n; fs->kind = mtr_file_state::DEVICE_FED; fs->device = ctx->device;
     return MTR_OK;
 }
 
-static mtr_status upload_batch(mtr_ctx *ctx, mtr_file_state *fs, const uint32_t *packed_in, int64_t n_words_in, const int64_t *woff_in,
-                               const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n, const DeviceText *dt)
+// ---- the three sources ----
+// an image on the host, the caller's or made from codes, becomes the batch; fo: the host feed's plan in file-order mode
+static mtr_status upload_host_image(mtr_ctx *ctx, const uint32_t *packed, const int64_t *woff, int64_t words, const int32_t *lens, int32_t n,
+                                    const mtr_file_state::HostPlan *fo)
 {
-    if (!ctx) return MTR_ERR_BAD_ARG;
-    if (!lens || n <= 0) { ctx->err = "null input or n_reads <= 0"; return MTR_ERR_BAD_ARG; }
-    if (fs) { mtr_status st = fo_check_kind(ctx, fs, dt ? mtr_file_state::DEVICE_FED : mtr_file_state::HOST_FED); if (st != MTR_OK) return st; }
-    HIPCHK(hipSetDevice(ctx->device));
-    { mtr_status w = mtr_wait(ctx); if (w != MTR_OK && w != MTR_ERR_OVERFLOW && w != MTR_ERR_DP_TOO_LARGE) return w; }
-    free_batch(ctx);
-    std::vector<int64_t> woff_own;
-    std::vector<uint32_t> packed_own;
-    const int64_t *woff = woff_in; const uint32_t *packed = packed_in;
-    int64_t words = 0; int Lmax = 0;
-    for (int i = 0; i < n; i++) {
-        if (lens[i] <= 0 || lens[i] > MTRC_MAX_SUPPORTED_LENGTH) { ctx->err = "read " + std::to_string(i) + ": length " + std::to_string(lens[i]) + " outside 1.." + std::to_string(MTRC_MAX_SUPPORTED_LENGTH); return MTR_ERR_BAD_ARG; }
-        Lmax = std::max(Lmax, (int)lens[i]);
-    }
-    if (dt) { mtr_status st = check_device_text(ctx, *dt, offsets, lens, n); if (st != MTR_OK) return st; }
-    if (packed_in) {
-        for (int i = 0; i < n; i++)
-            if (woff_in[i] < 0 || woff_in[i] + mtr_packed_words(lens[i]) > n_words_in) { ctx->err = "read " + std::to_string(i) + ": words outside the packed image"; return MTR_ERR_BAD_ARG; }
-        words = n_words_in;
-    } else {
-        woff_own.resize((size_t)n);
-        for (int i = 0; i < n; i++) { woff_own[(size_t)i] = words; words += mtr_packed_words(lens[i]); }
-        if (!dt) packed_own.assign((size_t)words, 0u);
-        for (int i = 0; i < n && !dt; i++)
-            if (mtr_pack_read(bases + offsets[i], lens[i], packed_own.data() + woff_own[(size_t)i]) != MTR_OK) { ctx->err = "read " + std::to_string(i) + ": base code > 3"; return MTR_ERR_BAD_ARG; }
-        woff = woff_own.data(); packed = packed_own.data();
-    }
-    // file-order mode: in file order, what each read finds beyond its own part of the reference's two buffers
-    std::vector<uint16_t> tail; std::vector<int64_t> tail_off;
-    FoPlan fo;                                                   // reads in device memory: file_order.hip.inc does it, behind the packing kernel
-    ctx->after.assign((size_t)n * 2, 0);
-    if (fs && !dt) {
-        tail_off.assign((size_t)n + 1, 0);
-        for (int i = 0; i < n; i++) {
-            fs->tail_for(lens[i], tail);
-            tail_off[(size_t)i + 1] = (int64_t)tail.size();
-            uint32_t *w = packed_own.data() + woff_own[(size_t)i];
-            for (int64_t p = lens[i]; p < (int64_t)lens[i] + 2; p++) {
-                const int b = fs->org_at(p);
-                ctx->after[(size_t)i * 2 + (size_t)(p - lens[i])] = (uint8_t)b;
-                w[p >> 4] |= (uint32_t)b << (30 - 2 * (int)(p & 15));
-            }
-            fs->push(bases + offsets[i], lens[i]);
-        }
-    }
-    ctx->file_order = fs != nullptr; ctx->tail_entries = (int64_t)tail.size(); ctx->fo_tail_launches = 0; ctx->fo_tail_ms = 0;
-    std::vector<int32_t> order((size_t)n); std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lens[a] > lens[b]; });
-    ctx->roff.assign((size_t)n + 1, 0);
-    for (int i = 0; i < n; i++) ctx->roff[(size_t)i + 1] = ctx->roff[(size_t)i] + mtrc_range_cap(lens[i]);
-    ctx->total_rcap = ctx->roff[(size_t)n];
-    ctx->lens.assign(lens, lens + n);
-    ctx->n_reads = n; ctx->Lmax = Lmax;
-    ctx->max_rec = 16 + Lmax / 100;
-    DBG("upload_batch: %d reads checked and ordered", n);
-    HIPCHK(ctx->d_packed.ensure(((size_t)words + 80) * 4));      // + 80: the DP stages 64-word blocks, the last block must stay readable
-    HIPCHK(ctx->d_woff.ensure((size_t)n * 8)); HIPCHK(ctx->d_lens.ensure((size_t)n * 4)); HIPCHK(ctx->d_order.ensure((size_t)n * 4));
-    HIPCHK(ctx->d_roff.ensure(((size_t)n + 1) * 8)); HIPCHK(ctx->d_rcount.ensure((size_t)n * 4));
-    HIPCHK(ctx->d_rstart.ensure((size_t)ctx->total_rcap * 4)); HIPCHK(ctx->d_rend.ensure((size_t)ctx->total_rcap * 4));
-    HIPCHK(ctx->d_rw.ensure((size_t)ctx->total_rcap * 4)); HIPCHK(ctx->d_rdi.ensure((size_t)ctx->total_rcap * 8));
-    HIPCHK(ctx->d_records.ensure((size_t)n * (size_t)ctx->max_rec * sizeof(DevRecord)));
-    HIPCHK(ctx->d_reccount.ensure((size_t)n * 4));
-    HIPCHK(ctx->d_recoff.ensure(((size_t)n + 1) * 8));
-    HIPCHK(ctx->d_item_off.ensure(((size_t)n + 1) * 8));
-    DBG("upload_batch: batch buffers ready");
-    if (!dt) HIPCHK(hipMemcpyAsync(ctx->d_packed, packed, (size_t)words * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_packed + words, 0, 80 * 4, ctx->stream));
-    ctx->packed_words = (long long)words + 80;
-    HIPCHK(hipMemcpyAsync(ctx->d_woff, woff, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->d_lens, lens, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    int32_t first_bad = n;
-    if (dt) {   // the text comes from the caller's stream: the packing kernel waits for it there, not for the whole device
-        if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
-        HIPCHK(ctx->d_toff.ensure((size_t)n * 8)); HIPCHK(ctx->d_pack_bad.ensure(4));
-        HIPCHK(hipMemcpyAsync(ctx->d_toff, offsets, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemsetAsync(ctx->d_pack_bad, 0x7f, 4, ctx->stream));
-        HIPCHK(hipEventRecord(ctx->ev_text, dt->wait));
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
-        const int64_t blocks = std::min<int64_t>((words + MTR_PACK_BLOCK - 1) / MTR_PACK_BLOCK, (int64_t)ctx->n_cu * 8);
-        if (dt->kind == MTR_TEXT_ASCII)
-            hipLaunchKernelGGL(mtr_k_pack_text<true>, dim3((unsigned)blocks), dim3(MTR_PACK_BLOCK), 0, ctx->stream, dt->d, ctx->d_toff, ctx->d_lens,
-                               ctx->d_woff, n, words, ctx->d_packed, ctx->d_pack_bad);
-        else
-            hipLaunchKernelGGL(mtr_k_pack_text<false>, dim3((unsigned)blocks), dim3(MTR_PACK_BLOCK), 0, ctx->stream, dt->d, ctx->d_toff, ctx->d_lens,
-                               ctx->d_woff, n, words, ctx->d_packed, ctx->d_pack_bad);
-        HIPCHK(hipGetLastError());
-        if (fs) { mtr_status st = fo_launch(ctx, fs, woff, lens, n, fo); if (st != MTR_OK) return st; }
-    }
-    HIPCHK(hipMemcpyAsync(ctx->d_order, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->d_roff, ctx->roff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (fs && !dt) {
-        HIPCHK(ctx->d_tail.ensure(std::max<size_t>(tail.size(), 1) * 2)); HIPCHK(ctx->d_tail_off.ensure(((size_t)n + 1) * 8));
-        if (!tail.empty()) HIPCHK(hipMemcpyAsync(ctx->d_tail, tail.data(), tail.size() * 2, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->d_tail_off, tail_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (dt) {   // (enqueued last, right before the synchronise: no early return leaves this copy pending)
-        hipError_t e = hipMemcpyAsync(&first_bad, ctx->d_pack_bad, 4, hipMemcpyDeviceToHost, ctx->stream);
-        hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess) { ctx->err = std::string("device upload: ") + hipGetErrorString(e); return MTR_ERR_HIP; }
-    }
+    { mtr_status st = size_batch(ctx, lens, n, words, fo != nullptr); if (st != MTR_OK) return st; }
+    HIPCHK(hipMemcpyAsync(ctx->d_packed, packed, (size_t)words * 4, hipMemcpyHostToDevice, ctx->stream));
+    { mtr_status st = enqueue_layout(ctx, lens, n, woff, words); if (st != MTR_OK) return st; }
+    { mtr_status st = enqueue_order(ctx); if (st != MTR_OK) return st; }
+    if (fo) { mtr_status st = fo_host_enqueue(ctx, *fo); if (st != MTR_OK) return st; }
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    DBG("upload_batch: copies done");
-    if (first_bad < n) {
-        free_batch(ctx);
-        ctx->err = "read " + std::to_string(first_bad) + (dt->kind == MTR_TEXT_ASCII ? ": a byte that is not A, C, G, T, a, c, g or t" : ": base code > 3");
-        return MTR_ERR_BAD_ARG;
-    }
-    if (fs && dt) {   // every refusal is behind us: the state advances over the batch
-        if (ctx->fo_tail_launches) HIPCHK(hipEventElapsedTime(&ctx->fo_tail_ms, ctx->ev[0], ctx->ev[1]));
-        mtr_status st = fo_commit(ctx, fs, fo.work, ctx->d_packed, woff, n);
-        if (st != MTR_OK) return st;
-    }
+    DBG("upload: copies done");
     return MTR_OK;
+}
+
+static mtr_status upload_codes(mtr_ctx *ctx, mtr_file_state *fs, const HostCodes &src, const int32_t *lens, int32_t n)
+{
+    if (ctx && (!src.bases || !src.offsets)) { ctx->err = "null input"; return MTR_ERR_BAD_ARG; }
+    { mtr_status st = upload_begin(ctx, fs, mtr_file_state::HOST_FED, lens, n); if (st != MTR_OK) return st; }
+    std::vector<int64_t> woff;
+    const int64_t words = word_layout(lens, n, woff);
+    std::vector<uint32_t> packed((size_t)words, 0u);
+    for (int i = 0; i < n; i++)
+        if (mtr_pack_read(src.bases + src.offsets[i], lens[i], packed.data() + woff[(size_t)i]) != MTR_OK) { ctx->err = "read " + std::to_string(i) + ": base code > 3"; return MTR_ERR_BAD_ARG; }
+    mtr_file_state::HostPlan fo;
+    if (fs) fo_host_plan(fs, src, lens, n, woff.data(), packed.data(), fo);
+    { mtr_status st = upload_host_image(ctx, packed.data(), woff.data(), words, lens, n, fs ? &fo : nullptr); if (st != MTR_OK) return st; }
+    if (fs) fs->adopt_host(std::move(fo.work), src.bases, src.offsets, n);          // every refusal is behind us: the state advances over the batch
+    return MTR_OK;
+}
+
+static mtr_status upload_packed(mtr_ctx *ctx, const HostPacked &src, const int32_t *lens, int32_t n)
+{
+    { mtr_status st = upload_begin(ctx, nullptr, mtr_file_state::HOST_FED, lens, n); if (st != MTR_OK) return st; }
+    for (int i = 0; i < n; i++)
+        if (src.woff[i] < 0 || src.woff[i] + mtr_packed_words(lens[i]) > src.n_words) { ctx->err = "read " + std::to_string(i) + ": words outside the packed image"; return MTR_ERR_BAD_ARG; }
+    return upload_host_image(ctx, src.words, src.woff, src.n_words, lens, n, nullptr);
+}
+
+static mtr_status text_to_batch(mtr_ctx *ctx, mtr_file_state *fs, const DeviceText &dt, const int32_t *lens, int32_t n)
+{
+    { mtr_status st = upload_begin(ctx, fs, mtr_file_state::DEVICE_FED, lens, n); if (st != MTR_OK) return st; }
+    { mtr_status st = check_device_text(ctx, dt, lens, n); if (st != MTR_OK) return st; }
+    std::vector<int64_t> woff;
+    const int64_t words = word_layout(lens, n, woff);
+    FoPlan fo;
+    { mtr_status st = size_batch(ctx, lens, n, words, fs != nullptr); if (st != MTR_OK) return st; }
+    { mtr_status st = enqueue_layout(ctx, lens, n, woff.data(), words); if (st != MTR_OK) return st; }
+    { mtr_status st = pack_text_enqueue(ctx, dt, n, words, ctx->d_lens, ctx->d_woff, ctx->d_packed); if (st != MTR_OK) return st; }
+    if (fs) { mtr_status st = fo_launch(ctx, fs, woff.data(), lens, n, fo); if (st != MTR_OK) return st; }
+    { mtr_status st = enqueue_order(ctx); if (st != MTR_OK) return st; }
+    { mtr_status st = pack_text_result(ctx, dt, n); if (st != MTR_OK) return st; }
+    DBG("upload: copies done");
+    if (!fs) return MTR_OK;
+    // every refusal is behind us: the state advances over the batch
+    if (ctx->fo_tail_launches) HIPCHK(hipEventElapsedTime(&ctx->fo_tail_ms, ctx->ev[0], ctx->ev[1]));
+    return fo_commit(ctx, fs, std::move(fo.work), ctx->d_packed, woff.data(), n);
+}
+// a refused device upload leaves no batch behind, and the state as it was
+static mtr_status upload_text(mtr_ctx *ctx, mtr_file_state *fs, const DeviceText &dt, const int32_t *lens, int32_t n)
+{
+    const mtr_status st = text_to_batch(ctx, fs, dt, lens, n);
+    if (st != MTR_OK && ctx && !ctx->pending) free_batch(ctx);
+    return st;
+}
+
+extern "C" mtr_status mtr_upload_batch(mtr_ctx *ctx, const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n)
+{
+    return upload_codes(ctx, nullptr, HostCodes{ bases, offsets }, lens, n);
+}
+extern "C" mtr_status mtr_upload_batch_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *bases, const int64_t *offsets, const int32_t *lens, int32_t n)
+{
+    if (!fs) { if (ctx) ctx->err = "null file state"; return MTR_ERR_BAD_ARG; }
+    return upload_codes(ctx, fs, HostCodes{ bases, offsets }, lens, n);
+}
+extern "C" mtr_status mtr_upload_batch_packed(mtr_ctx *ctx, const uint32_t *packed, int64_t n_words, const int64_t *woff, const int32_t *lens, int32_t n)
+{
+    if (ctx && (!packed || !woff || n_words <= 0)) { ctx->err = "null input"; return MTR_ERR_BAD_ARG; }
+    return upload_packed(ctx, HostPacked{ packed, n_words, woff }, lens, n);
+}
+extern "C" mtr_status mtr_upload_batch_device(mtr_ctx *ctx, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
+                                              const int32_t *lens, int32_t n, int32_t text_kind, void *wait_stream)
+{
+    return upload_text(ctx, nullptr, DeviceText{ d_text, text_bytes, offsets, text_kind, (hipStream_t)wait_stream }, lens, n);
+}
+extern "C" mtr_status mtr_upload_batch_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
+                                                      const int32_t *lens, int32_t n, int32_t text_kind, void *wait_stream)
+{
+    if (!fs) { if (ctx) ctx->err = "null file state"; return MTR_ERR_BAD_ARG; }
+    return upload_text(ctx, fs, DeviceText{ d_text, text_bytes, offsets, text_kind, (hipStream_t)wait_stream }, lens, n);
 }
 
 // The state advances over reads that another GPU processes: all of them are packed (and checked) into the storage's free end, the ones that
@@ -818,49 +749,23 @@ extern "C" mtr_status mtr_file_state_skip_device(mtr_ctx *ctx, mtr_file_state *f
     { mtr_status st = fo_check_kind(ctx, fs, mtr_file_state::DEVICE_FED); if (st != MTR_OK) return st; }
     if (n == 0) return MTR_OK;
     HIPCHK(hipSetDevice(ctx->device));
-    std::vector<int64_t> woff((size_t)n);
-    int64_t words = 0;
-    for (int i = 0; i < n; i++) {
-        if (lens[i] <= 0 || lens[i] > MTRC_MAX_SUPPORTED_LENGTH) { ctx->err = "read " + std::to_string(i) + ": length " + std::to_string(lens[i]) + " outside 1.." + std::to_string(MTRC_MAX_SUPPORTED_LENGTH); return MTR_ERR_BAD_ARG; }
-        woff[(size_t)i] = words; words += mtr_packed_words(lens[i]);
-    }
-    const DeviceText dt = { d_text, text_bytes, text_kind, (hipStream_t)wait_stream };
-    { mtr_status st = check_device_text(ctx, dt, offsets, lens, n); if (st != MTR_OK) return st; }
-    FoPlan fo;
-    fo_plan(fs, nullptr, woff.data(), lens, n, false, fo);
-    size_t kept = 0;
-    while (kept < fo.work.size() && fo.work[kept].owner < 0) kept++;
-    const int64_t top = kept ? fs->stairs[kept - 1].woff + mtr_packed_words(fs->stairs[kept - 1].L) : 0;
-    int64_t fresh = 0;
-    for (size_t k = kept; k < fo.work.size(); k++) fresh += mtr_packed_words(fo.work[k].L);
+    if (!check_lengths(lens, n, &ctx->err)) return MTR_ERR_BAD_ARG;
+    const DeviceText dt = { d_text, text_bytes, offsets, text_kind, (hipStream_t)wait_stream };
+    { mtr_status st = check_device_text(ctx, dt, lens, n); if (st != MTR_OK) return st; }
+    std::vector<int64_t> woff;
+    const int64_t words = word_layout(lens, n, woff);
+    std::vector<FileStair> work = mtr_file_state::skipped(fs->stairs, lens, n);
+    const mtr_file_state::Survivors s = mtr_file_state::survivors(work);
     // (the stairs that this call pops are still live until it commits: the staging area starts behind all of them too)
-    const int64_t stage = std::max(top + fresh, fs->store_top());
+    const int64_t stage = std::max(s.top + s.fresh, fs->store_top());
     { mtr_status st = fo_reserve(ctx, fs, stage + words, fs->store_top()); if (st != MTR_OK) return st; }
     uint32_t *d_stage = fs->d_store + stage;
-    if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
-    HIPCHK(ctx->d_toff.ensure((size_t)n * 8)); HIPCHK(ctx->d_pack_bad.ensure(4));
     HIPCHK(ctx->d_fo_lens.ensure((size_t)n * 4)); HIPCHK(ctx->d_fo_woff.ensure((size_t)n * 8));
-    HIPCHK(hipMemcpyAsync(ctx->d_toff, offsets, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_fo_lens, lens, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_fo_woff, woff.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_pack_bad, 0x7f, 4, ctx->stream));
-    HIPCHK(hipEventRecord(ctx->ev_text, dt.wait));
-    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
-    const int64_t blocks = std::min<int64_t>((words + MTR_PACK_BLOCK - 1) / MTR_PACK_BLOCK, (int64_t)ctx->n_cu * 8);
-    if (dt.kind == MTR_TEXT_ASCII)
-        hipLaunchKernelGGL(mtr_k_pack_text<true>, dim3((unsigned)blocks), dim3(MTR_PACK_BLOCK), 0, ctx->stream, dt.d, ctx->d_toff, ctx->d_fo_lens,
-                           ctx->d_fo_woff, n, words, d_stage, ctx->d_pack_bad);
-    else
-        hipLaunchKernelGGL(mtr_k_pack_text<false>, dim3((unsigned)blocks), dim3(MTR_PACK_BLOCK), 0, ctx->stream, dt.d, ctx->d_toff, ctx->d_fo_lens,
-                           ctx->d_fo_woff, n, words, d_stage, ctx->d_pack_bad);
-    HIPCHK(hipGetLastError());
-    int32_t first_bad = n;
-    HIPCHK(copy_sync(ctx, &first_bad, ctx->d_pack_bad, 4, hipMemcpyDeviceToHost));
-    if (first_bad < n) {
-        ctx->err = "read " + std::to_string(first_bad) + (dt.kind == MTR_TEXT_ASCII ? ": a byte that is not A, C, G, T, a, c, g or t" : ": base code > 3");
-        return MTR_ERR_BAD_ARG;
-    }
-    return fo_commit(ctx, fs, fo.work, d_stage, woff.data(), n);
+    { mtr_status st = pack_text_enqueue(ctx, dt, n, words, ctx->d_fo_lens, ctx->d_fo_woff, d_stage); if (st != MTR_OK) return st; }
+    { mtr_status st = pack_text_result(ctx, dt, n); if (st != MTR_OK) return st; }
+    return fo_commit(ctx, fs, std::move(work), d_stage, woff.data(), n);
 }
 
 static BatchView view(const mtr_ctx *ctx)
@@ -2066,35 +1971,29 @@ static mtr_status fastq_index(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_by
 static mtr_status fasta_write(mtr_ctx *ctx, const FastaParse &p, const mtr_fasta_dst &dst)
 {
     const mtr_fasta_info &f = p.info;
-    if (p.fastq) {
-        if (dst.id_off) HIPCHK(hipMemcpyAsync(dst.id_off, ctx->d_fa_idoff, ((size_t)f.n_reads + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        if (f.n_reads <= 0) return MTR_OK;
-        FastqArgs q = p.q;
-        q.text = dst.text; q.n_reads = (uint32_t)f.n_reads;
-        const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)f.n_reads + 255) / 256, (int64_t)ctx->n_cu * 8);
-        hipLaunchKernelGGL(mtr_k_fastq_reads, dim3(blocks), dim3(256), 0, ctx->stream, q, f.n_reads, dst.text ? 0 : 1, dst.offsets, dst.lens);
-        if (f.id_bytes > 0)
-            hipLaunchKernelGGL(mtr_k_fasta_ids, dim3((unsigned)std::min<int64_t>(f.n_reads, (int64_t)ctx->n_cu * 32)), dim3(64), 0, ctx->stream, p.a, f.n_reads,
-                               (const int64_t *)ctx->d_fa_idoff, dst.ids);
-        // every base of a reported read lies before the stop: the tiles behind it hold none
-        const unsigned tiles = (unsigned)((std::min<int64_t>(f.end_pos, (int64_t)q.n) + MTR_FASTA_TILE_BYTES - 1) / MTR_FASTA_TILE_BYTES);
-        if (dst.text && tiles > 0) hipLaunchKernelGGL(mtr_k_fastq_tile<1>, dim3(tiles), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, q);
-        HIPCHK(hipGetLastError());
-        return MTR_OK;
-    }
     if (dst.id_off) HIPCHK(hipMemcpyAsync(dst.id_off, ctx->d_fa_idoff, ((size_t)f.n_reads + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
     if (f.n_reads <= 0) return MTR_OK;
-    FastaArgs a = p.a;
-    a.text = dst.text; a.n_bases = (uint32_t)f.n_bases;
     const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)f.n_reads + 255) / 256, (int64_t)ctx->n_cu * 8);
-    hipLaunchKernelGGL(mtr_k_fasta_reads, dim3(blocks), dim3(256), 0, ctx->stream, a, p.n_heads, f.n_reads, dst.offsets, dst.lens);
-    if (f.id_bytes > 0)
-        hipLaunchKernelGGL(mtr_k_fasta_ids, dim3((unsigned)std::min<int64_t>(f.n_reads, (int64_t)ctx->n_cu * 32)), dim3(64), 0, ctx->stream, a, f.n_reads,
-                           (const int64_t *)ctx->d_fa_idoff, dst.ids);
+    auto ids = [&](const FastaArgs &a) {     // between the format's two launches
+        if (f.id_bytes > 0)
+            hipLaunchKernelGGL(mtr_k_fasta_ids, dim3((unsigned)std::min<int64_t>(f.n_reads, (int64_t)ctx->n_cu * 32)), dim3(64), 0, ctx->stream, a, f.n_reads,
+                               (const int64_t *)ctx->d_fa_idoff, dst.ids);
+    };
     // every base of a reported read lies before the stop: the tiles behind it hold none
-    const int64_t upto = std::min<int64_t>(f.end_pos, (int64_t)a.n);
-    const unsigned tiles = (unsigned)((upto + MTR_FASTA_TILE_BYTES - 1) / MTR_FASTA_TILE_BYTES);
-    if (tiles > 0) hipLaunchKernelGGL(mtr_k_fasta_tile<2>, dim3(tiles), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, a);
+    auto tiles = [&](int64_t n) { return (unsigned)((std::min<int64_t>(f.end_pos, n) + MTR_FASTA_TILE_BYTES - 1) / MTR_FASTA_TILE_BYTES); };
+    if (p.fastq) {
+        FastqArgs q = p.q;
+        q.text = dst.text; q.n_reads = (uint32_t)f.n_reads;
+        hipLaunchKernelGGL(mtr_k_fastq_reads, dim3(blocks), dim3(256), 0, ctx->stream, q, f.n_reads, dst.text ? 0 : 1, dst.offsets, dst.lens);
+        ids(p.a);
+        if (dst.text && tiles(q.n) > 0) hipLaunchKernelGGL(mtr_k_fastq_tile<1>, dim3(tiles(q.n)), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, q);
+    } else {
+        FastaArgs a = p.a;
+        a.text = dst.text; a.n_bases = (uint32_t)f.n_bases;
+        hipLaunchKernelGGL(mtr_k_fasta_reads, dim3(blocks), dim3(256), 0, ctx->stream, a, p.n_heads, f.n_reads, dst.offsets, dst.lens);
+        ids(a);
+        if (tiles(a.n) > 0) hipLaunchKernelGGL(mtr_k_fasta_tile<2>, dim3(tiles(a.n)), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, a);
+    }
     HIPCHK(hipGetLastError());
     return MTR_OK;
 }
@@ -2168,9 +2067,9 @@ static mtr_status upload_fasta(mtr_ctx *ctx, mtr_file_state *fs, bool fastq, con
     }
     ctx->fa_indexed = true;
     if (n == 0) return MTR_OK;                                    // no reads: nothing to upload
-    const DeviceText dt = { fastq ? d_fasta : (const uint8_t *)ctx->d_fa_text, fastq ? n_bytes : f.n_bases, MTR_TEXT_ASCII, ctx->stream };
-    const mtr_status st = upload_batch(ctx, fs, nullptr, 0, nullptr, nullptr, offs.data(), ctx->fa_lens.data(), f.n_reads, &dt);
-    if (st != MTR_OK) { ctx->fa_indexed = false; if (!ctx->pending) free_batch(ctx); }       // as a refused mtr_upload_batch_device: no batch is left
+    const DeviceText dt = { fastq ? d_fasta : (const uint8_t *)ctx->d_fa_text, fastq ? n_bytes : f.n_bases, offs.data(), MTR_TEXT_ASCII, ctx->stream };
+    const mtr_status st = upload_text(ctx, fs, dt, ctx->fa_lens.data(), f.n_reads);
+    if (st != MTR_OK) ctx->fa_indexed = false;                    // as a refused mtr_upload_batch_device: no batch is left
     return st;
 }
 extern "C" mtr_status mtr_upload_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info)

@@ -6,6 +6,11 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#if !defined(__HIPCC__) && !defined(__host__)      // a plain C++ build of the host's own parts (file_state.h)
+#define __host__
+#define __device__
+#endif
+
 #define MTR_WAVE 64
 
 #define MTRC_MAX_PERIOD 500

@@ -50,7 +50,7 @@ def _rec(per_read):
 
 
 # ---- 1: the tail kernel and the after-bases kernel alone (upload only, no run) -----------------------------------------------------
-# One file; by mtr_file_state::tail_for a reader of 600 has E = 1000 and reach = 1028.  Behind 12000 its tail is that read's leading
+# One file; by mtr_file_state::walk a reader of 600 has E = 1000 and reach = 1028.  Behind 12000 its tail is that read's leading
 # flank, behind 10100 it straddles r_e = 1010, behind 2000 it is own bases, behind 910 own bases run into the trailing flank inside a
 # 5-mer, behind 820 it crosses the n_e - 4 switch from 5-mer to raw, behind 610 (E = 1010) it is mt[q] beyond n_e and then 900's
 # entries: two owners.  999 / 1000: r = 100 / L/10.  720000: N capped at 1e6, owner of 60000's tail and of later leading flanks, and

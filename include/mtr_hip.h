@@ -399,6 +399,53 @@ mtr_status mtr_upload_fastq_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, con
 mtr_status mtr_file_state_skip_device(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_text, int64_t text_bytes, const int64_t *offsets,
                                       const int32_t *lens, int32_t n_reads, int32_t text_kind, void *wait_stream);
 
+/* ---- a FASTA or FASTQ file in device memory, batch by batch ----------------------------------------------------------------
+ * The entry points above make ONE batch of the whole buffer.  A caller who wants batches of a chosen size cannot cut the file
+ * by looking at it: a FASTA record ends where the next header window - an fgets window of 4095 bytes that starts with '>' - begins, which
+ * is a result of the parse and not of a search for "\n>".  The _window entry points take the FIRST n_bytes of a longer input:
+ *   more_follows == 0  the buffer is the whole (rest of the) input: exactly the entry point of the same kind without _window -
+ *                      same code path, same results
+ *   more_follows == 1  bytes follow behind the buffer, and nothing is known about them
+ *   any other value    MTR_ERR_BAD_ARG
+ * fs == NULL is isolated mode (mtr_upload_fasta_device); otherwise file-order mode (mtr_upload_fasta_device_in_file): the state
+ * advances over the uploaded reads only.  Protocol, argument checks, stream handling and mtr_fasta_index are those of the entry
+ * points above.  With more_follows == 1:
+ *   a stop     found in the window is a stop of the whole input: line starts, fgets windows, hidden bytes, base counts and header
+ *              windows are functions of the bytes before a position.  It is reported as ever, with the reads closed before it.
+ *              Not raised are the two FASTQ stops that only the end of the input or a complete line decides: "the file ends
+ *              inside a record", and the length of a quality line whose LF is not in the window
+ *   FASTA      without a stop: the reads are the records closed by a header window that begins inside the window.  The last
+ *              record is open and is not returned.  end = MTR_FASTA_END_MORE, end_pos = the position of the open record's header
+ *              '>' - or 0 if the open record is the window's first, because that record owns the bases in front of its header too;
+ *              no header window at all: no reads, end_pos 0.  A header window starts an fgets window, so a parse that begins at
+ *              end_pos puts every later window where the parse of the whole input puts it: resuming there is exact
+ *   FASTQ      without a stop: the reads are the records whose quality line's LF lies inside the window.  end =
+ *              MTR_FASTA_END_MORE, end_pos = the byte behind the last such LF: the open record's header line, or n_bytes if the
+ *              window ends exactly behind a record
+ *   n_bytes == 0   MTR_OK, no reads, MTR_FASTA_END_MORE, end_pos 0
+ *   n_reads == 0 with MTR_FASTA_END_MORE   the window is smaller than its first record: the caller widens it
+ *   info.n_bases, id_bytes, the compaction, the IDs, and mtr_upload_fastq_device's packing out of the file itself cover the
+ *   returned reads only.  The parser's buffers in the context are sized by n_bytes, so a walk keeps them at window size.
+ * The walk of an input of any length - only a window is limited to INT32_MAX bytes:
+ *   pos = 0;
+ *   do { n = min(w, len - pos);
+ *        mtr_upload_fasta_device_window(ctx, fs, d + pos, n, pos + n < len, stream, &info);
+ *        if (info.end == MTR_FASTA_END_MORE && info.n_reads == 0) { w *= 2; continue; }
+ *        if (info.n_reads > 0) { run; report; }            // info.end_pos + pos is the position in the input
+ *        pos += info.end_pos;
+ *   } while (info.end == MTR_FASTA_END_MORE);
+ * The reads of all batches together, and the last call's end, bad_char and pos + end_pos, are those of one call on the whole
+ * input, whatever the windows. */
+#define MTR_FASTA_END_MORE 5
+mtr_status mtr_parse_fasta_device_window(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, int32_t more_follows,
+                                         void *wait_stream, const mtr_fasta_dst *dst, mtr_fasta_info *info);
+mtr_status mtr_upload_fasta_device_window(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fasta, int64_t n_bytes,
+                                          int32_t more_follows, void *wait_stream, mtr_fasta_info *info);
+mtr_status mtr_parse_fastq_device_window(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_bytes, int32_t more_follows,
+                                         void *wait_stream, const mtr_fasta_dst *dst, mtr_fasta_info *info);
+mtr_status mtr_upload_fastq_device_window(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fastq, int64_t n_bytes,
+                                          int32_t more_follows, void *wait_stream, mtr_fasta_info *info);
+
 /* orgInputString[L] and [L+1] as read i of the resident batch found them: 0 under isolated semantics, in file-order mode
  * the bases an earlier, longer read left there.  A repeat can end on them (wrap_around_DP.c:243-245), and a printer of
  * the -a alignments (mtr_alignments) needs them for its top row. */

@@ -2,6 +2,7 @@
 
 Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointers).  Only the device-input and report methods
 (Engine.upload_device / process_device / parse_fasta_device / upload_fasta_device / parse_fastq_device / upload_fastq_device /
+walk_fasta_device / walk_fastq_device /
 export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes) take or return torch tensors;
 they import torch when called.
 The product path is libmtr_hip.so only: importing works without a GPU, but creating an Engine
@@ -22,7 +23,7 @@ MAX_READ_LENGTH = 833333                     # MTR_MAX_READ_LENGTH
 TEXT_ASCII, TEXT_CODES = 0, 1                # MTR_TEXT_ASCII, MTR_TEXT_CODES
 FASTA_TILE_BYTES = 4096                      # MTR_FASTA_TILE_BYTES (mtr_amd/csrc/fasta.hip.inc): the bytes of a FASTA file one workgroup scans
 FASTA_END = {0: "eof", 1: "empty", 2: "bad", 3: "toolong"}        # MTR_FASTA_END_* of a FASTA file
-FASTQ_END = {**FASTA_END, 4: "format"}       # ... and of a FASTQ file: MTR_FASTA_END_FORMAT too
+FASTQ_END = {**FASTA_END, 4: "format", 5: "more"}        # ... of a FASTQ file: MTR_FASTA_END_FORMAT too; of a window: MTR_FASTA_END_MORE
 
 STATUS = {0: "MTR_OK", 1: "MTR_ERR_NO_DEVICE", 2: "MTR_ERR_BAD_ARG", 3: "MTR_ERR_OOM", 4: "MTR_ERR_HIP",
           5: "MTR_ERR_OVERFLOW", 6: "MTR_ERR_DP_TOO_LARGE"}
@@ -47,7 +48,8 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_report_device", "mtr_test_chain", "mtr_report_alignments_device", "mtr_report_text_device", "mtr_test_report_lines",
            "mtr_parse_fasta_device", "mtr_upload_fasta_device", "mtr_fasta_index",
            "mtr_parse_fastq_device", "mtr_upload_fastq_device", "mtr_upload_fastq_device_in_file",
-           "mtr_upload_batch_device_in_file", "mtr_upload_fasta_device_in_file", "mtr_file_state_skip_device", "mtr_test_file_tail"]
+           "mtr_upload_batch_device_in_file", "mtr_upload_fasta_device_in_file", "mtr_file_state_skip_device", "mtr_test_file_tail",
+           "mtr_parse_fasta_device_window", "mtr_upload_fasta_device_window", "mtr_parse_fastq_device_window", "mtr_upload_fastq_device_window"]
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
 
@@ -165,9 +167,10 @@ class Fasta(NamedTuple):
     offsets: "object"     # int64 numpy [n_reads]: read i is text[offsets[i]:offsets[i] + lens[i]]
     lens: "object"        # int32 numpy [n_reads]
     ids: list             # bytes per read: what its header holds behind '>'
-    end: str              # why the input ended: "eof", "empty" (a record without bases), "bad" (character), "toolong" (a record of 1 000 000 bases)
+    end: str              # why the input ended: "eof", "empty" (a record without bases), "bad" (character), "toolong" (a record of 1 000 000 bases);
+                          # FASTQ: "format" too; a window with more behind it (more=True) that holds no stop: "more"
     bad_char: "object"    # the character of end == "bad" as bytes, else None
-    end_pos: int          # the stop's position in the file (its length when the file ended)
+    end_pos: int          # the stop's position in the file (its length when the file ended); "more": where the next window starts
 
 
 class CKernelTime(C.Structure):
@@ -275,6 +278,11 @@ def load_library(path: str = LIB_PATH):
     for name in ("mtr_parse_fastq_device", "mtr_upload_fastq_device", "mtr_upload_fastq_device_in_file"):       # as their FASTA twins
         twin = getattr(lib, name.replace("fastq", "fasta"))
         getattr(lib, name).argtypes, getattr(lib, name).restype = twin.argtypes, twin.restype
+    for fmt in ("fasta", "fastq"):                              # more_follows behind n_bytes; the upload takes the file state, NULL or not
+        parse, upload = getattr(lib, f"mtr_parse_{fmt}_device_window"), getattr(lib, f"mtr_upload_{fmt}_device_window")
+        parse.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, P(CFastaDst), P(CFastaInfo)]
+        upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, P(CFastaInfo)]
+        parse.restype = upload.restype = C.c_int
     lib.mtr_fasta_index.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mtr_fasta_index.restype = C.c_int
     lib.mtr_test_report_lines.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [P(P(C.c_uint8)), P(P(C.c_int64))]
@@ -469,19 +477,23 @@ class Engine:
                         "mtr_upload_batch_device_in_file")
         self.n_reads = len(ln)
 
-    def parse_fasta_device(self, buf) -> Fasta:
+    def parse_fasta_device(self, buf, more: bool = False) -> Fasta:
         """mtr_parse_fasta_device: the bytes of a FASTA file on the GPU parsed there, by the reference reader's rules.
         buf: contiguous 1-D torch.uint8 tensor on this engine's device.  Returns a Fasta whose text is a fresh tensor on that
         device (what upload_device takes) and whose index is on the host; the resident batch is not touched.  The library
-        waits for torch's current stream (where buf was written) by an event."""
-        return self._parse_file_device("mtr_parse_fasta_device", buf)
+        waits for torch's current stream (where buf was written) by an event.
+        more=True (mtr_parse_fasta_device_window): buf is the beginning of a longer input.  Without a stop in it the reads are the
+        records that a later header closes, end is "more" and end_pos is where the next window starts - the open record's '>'."""
+        return self._parse_file_device("mtr_parse_fasta_device", buf, more)
 
-    def parse_fastq_device(self, buf) -> Fasta:
+    def parse_fastq_device(self, buf, more: bool = False) -> Fasta:
         """mtr_parse_fastq_device: parse_fasta_device for the bytes of a FASTQ file - strict four-line records, the rules in
-        include/mtr_hip.h.  The qualities are checked for their length and dropped; end may be "format" too."""
-        return self._parse_file_device("mtr_parse_fastq_device", buf)
+        include/mtr_hip.h.  The qualities are checked for their length and dropped; end may be "format" too.
+        more=True (mtr_parse_fastq_device_window): the reads are the records whose quality line's LF is in buf; end_pos is the byte
+        behind the last of them."""
+        return self._parse_file_device("mtr_parse_fastq_device", buf, more)
 
-    def _parse_file_device(self, entry: str, buf) -> Fasta:
+    def _parse_file_device(self, entry: str, buf, more: bool = False) -> Fasta:
         import torch
 
         fasta_input_args(buf, self.device)
@@ -489,7 +501,12 @@ class Engine:
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         src = C.c_void_p(buf.data_ptr()) if buf.numel() else None
         info = CFastaInfo()
-        call = getattr(self.lib, entry)
+        if more:
+            entry += "_window"
+            window = getattr(self.lib, entry)
+            call = lambda h, src, n, stream, dst, info: window(h, src, n, 1, stream, dst, info)     # noqa: E731
+        else:
+            call = getattr(self.lib, entry)
         self._check(call(self.h, src, buf.numel(), stream, None, C.byref(info)), entry)
         n, nb, ni = info.n_reads, int(info.n_bases), int(info.id_bytes)
         text = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -503,20 +520,23 @@ class Engine:
         self._check(call(self.h, src, buf.numel(), stream, C.byref(dst), C.byref(info)), entry)
         return _fasta(info, text, offsets.cpu().numpy(), lens.cpu().numpy(), id_off.cpu().numpy(), ids.cpu().numpy().tobytes())
 
-    def upload_fasta_device(self, buf, file_state: "FileState | None" = None) -> Fasta:
+    def upload_fasta_device(self, buf, file_state: "FileState | None" = None, more: bool = False) -> Fasta:
         """mtr_upload_fasta_device + mtr_fasta_index: the reads of a FASTA file on the GPU become the resident batch without a
         host parser; run / fetch / report_* follow as after any upload, and the returned Fasta (text None) carries the ids
         report_text takes.  A stop (end != "eof") does not refuse the upload: the reads before it are uploaded.  No reads: no
         batch is uploaded.  file_state: the reads are the next reads of that file (file-order mode,
-        mtr_upload_fasta_device_in_file); the state advances over the uploaded reads."""
-        return self._upload_file_device("mtr_upload_fasta_device", buf, file_state)
+        mtr_upload_fasta_device_in_file); the state advances over the uploaded reads.
+        more=True (mtr_upload_fasta_device_window): buf is the beginning of a longer input, as in parse_fasta_device; the reads in
+        front of end_pos are uploaded.  walk_fasta_device is the loop over a whole file."""
+        return self._upload_file_device("mtr_upload_fasta_device", buf, file_state, more)
 
-    def upload_fastq_device(self, buf, file_state: "FileState | None" = None) -> Fasta:
+    def upload_fastq_device(self, buf, file_state: "FileState | None" = None, more: bool = False) -> Fasta:
         """mtr_upload_fastq_device(_in_file) + mtr_fasta_index: upload_fasta_device for the bytes of a FASTQ file.  Nothing is
-        copied or compacted: the reads are packed out of buf itself, where each is one contiguous sequence line."""
-        return self._upload_file_device("mtr_upload_fastq_device", buf, file_state)
+        copied or compacted: the reads are packed out of buf itself, where each is one contiguous sequence line.
+        more=True (mtr_upload_fastq_device_window): buf is the beginning of a longer input, as in parse_fastq_device."""
+        return self._upload_file_device("mtr_upload_fastq_device", buf, file_state, more)
 
-    def _upload_file_device(self, entry: str, buf, file_state) -> Fasta:
+    def _upload_file_device(self, entry: str, buf, file_state, more: bool = False) -> Fasta:
         import torch
 
         fasta_input_args(buf, self.device)
@@ -524,7 +544,10 @@ class Engine:
         info = CFastaInfo()
         self.n_reads = 0
         src = C.c_void_p(buf.data_ptr()) if buf.numel() else None
-        if file_state is None:
+        if more:
+            self._check(getattr(self.lib, entry + "_window")(self.h, file_state.h if file_state is not None else None, src, buf.numel(), 1, stream,
+                                                             C.byref(info)), entry + "_window")
+        elif file_state is None:
             self._check(getattr(self.lib, entry)(self.h, src, buf.numel(), stream, C.byref(info)), entry)
         else:
             self._check(getattr(self.lib, entry + "_in_file")(self.h, file_state.h, src, buf.numel(), stream, C.byref(info)), entry + "_in_file")
@@ -536,6 +559,52 @@ class Engine:
             offsets[1:] = np.cumsum(lens[:-1], dtype=np.int64)
         self.n_reads = n
         return _fasta(info, None, offsets, lens, id_off, ids.tobytes()[:int(info.id_bytes)])
+
+    def walk_fasta_device(self, buf, window_bytes: int, file_state: "FileState | None" = None):
+        """A FASTA file on the GPU batch by batch: a generator over upload_fasta_device(buf[pos:pos + w], file_state, more), where
+        w starts as window_bytes and more = pos + w < len(buf).  The slices are views: nothing is copied, and a window may start at
+        any byte.  Yields one Fasta per call that uploaded reads - its reads are the resident batch: the caller runs and reports
+        before taking the next item - and one last item whose end is not "more": the end of the whole file, with end_pos and
+        bad_char as one upload_fasta_device(buf) would give them (end_pos of every item is absolute in buf).  That last item may
+        have no reads; then nothing is resident and there is nothing to run.  A window smaller than its first record (no reads,
+        "more") doubles w for the rest of the walk and is retried at the same pos; w is cut to what is left of buf, so the walk
+        ends.  The reads of all items together are those of upload_fasta_device(buf), whatever window_bytes: a window ends on
+        the header of its open record, which starts an fgets window of the reference's reader, so the next window is read as the
+        whole file would be.  window_bytes < 1 raises MtrError before the library is called.
+        Only a window is limited to INT32_MAX bytes: a buf of any length can be walked.  The loop of a C caller:
+            pos = 0;
+            do { n = min(w, len - pos);
+                 mtr_upload_fasta_device_window(ctx, fs, d + pos, n, pos + n < len, stream, &info);
+                 if (info.end == MTR_FASTA_END_MORE && info.n_reads == 0) { w *= 2; continue; }
+                 if (info.n_reads > 0) { run; report; }
+                 pos += info.end_pos;
+            } while (info.end == MTR_FASTA_END_MORE);"""
+        return self._walk_file_device(self.upload_fasta_device, buf, window_bytes, file_state)
+
+    def walk_fastq_device(self, buf, window_bytes: int, file_state: "FileState | None" = None):
+        """walk_fasta_device for the bytes of a FASTQ file (upload_fastq_device, mtr_upload_fastq_device_window): a window's reads
+        are the records whose quality line's LF lies in it, and the next window starts behind the last such LF."""
+        return self._walk_file_device(self.upload_fastq_device, buf, window_bytes, file_state)
+
+    def _walk_file_device(self, upload, buf, window_bytes, file_state):
+        if isinstance(window_bytes, bool) or not isinstance(window_bytes, (int, np.integer)) or window_bytes < 1:
+            raise MtrError(f"window_bytes must be an integer of at least 1, got {window_bytes!r}")
+        fasta_input_args(buf, self.device)
+        return self._walk(upload, buf, int(window_bytes), file_state)
+
+    @staticmethod
+    def _walk(upload, buf, w, file_state):
+        n, pos = buf.numel(), 0
+        while True:
+            k = min(w, n - pos)
+            f = upload(buf[pos:pos + k], file_state, pos + k < n)
+            if f.end == "more" and len(f.lens) == 0:
+                w *= 2
+                continue
+            yield f._replace(end_pos=pos + f.end_pos)
+            if f.end != "more":
+                return
+            pos += f.end_pos
 
     def process_device(self, text, offsets, lens, codes: bool = False, file_state: "FileState | None" = None) -> List[List[Record]]:
         """upload_device + run + fetch: per read its records in insertion order, as process() (file_state: process_in_file()) returns them"""

@@ -21,13 +21,20 @@
 //   mtr_k_fasta_tile<1>      the same walk with global counts: per header its position, the bases before it, its ID's length; the stop events,
 //                            atomicMin'ed as position * 4 + kind into one 64-bit word;
 //   mtr_k_scan_offsets       (report_align.hip.inc) the IDs' offsets;
-//   mtr_k_fasta_finish       one thread: the reads before the stop (a binary search over the header positions) and the sizes;
+//   mtr_k_fasta_finish       one thread: the reads before the stop (a binary search over the header positions) and the sizes; for a
+//                            window of a longer input (more, below) the records that a header window closed;
 //   mtr_k_fasta_reads / mtr_k_fasta_ids / mtr_k_fasta_tile<2>   the reads' offsets and lengths, their IDs gathered, the bases compacted (through
 //                            LDS, so that a tile's bases leave as one run of neighbouring bytes) - the file's own bytes, which
 //                            mtr_k_pack_text takes as MTR_TEXT_ASCII.
 // The file is read with aligned dword loads as mtr_k_pack_text reads its text: every dword loaded holds at least one byte of the file; the
 // bytes past the end of the last 16-byte span are loaded one by one.  Positions and counts are 32-bit: the entry points refuse more than
 // INT32_MAX bytes.  Every result is written with ordinary vector stores.
+// A WINDOW of a longer input (mtr_parse_fasta_device_window, more = 1): the buffer is the input's first n bytes and what follows is
+// unknown.  All of the above is a function of the bytes before a position, so a stop found in the window is a stop of the input and is
+// reported as ever.  Without one only the end of the file is missing: the last record stays open and is not a read, end =
+// MTR_FASTA_END_MORE, end_pos = where its header window starts (0 for the window's first record, which owns the bases in front of its
+// header as well).  A header window starts an fgets window, so a parse that begins there puts every later window where this one would.
+// Only mtr_k_fasta_finish knows the mode.
 
 #define MTR_FASTA_TILE_BYTES 4096
 #define MTR_FASTA_BLOCK 256                                    // x 16 bytes a thread = one tile
@@ -280,13 +287,18 @@ __global__ __launch_bounds__(MTR_FASTA_SCAN_BLOCK) void mtr_k_fasta_scan_counts(
 // The reads before the stop and the sizes.  n_heads = the header windows, or 1 for a file without one: its only record has the ID ""
 // (the host zeroes that header's columns).  Record r has the ID of header r, begins at base h_base[r] (record 0 at base 0: the bases
 // in front of the first header join it) and is closed by header r + 1 or by the end of the file.
-__global__ __launch_bounds__(64) void mtr_k_fasta_finish(FastaArgs a, int32_t n_heads, const int64_t *id_off, mtr_fasta_info *info)
+// more: the input goes on behind the buffer - without a stop the last record is open: not a read, and the next window starts on its header.
+__global__ __launch_bounds__(64) void mtr_k_fasta_finish(FastaArgs a, int32_t n_heads, int32_t more, const int64_t *id_off, mtr_fasta_info *info)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const unsigned long long ev = *a.event;
     const uint32_t total = a.totals[0];
     int32_t n_reads, end, bad = 0; int64_t end_pos;
-    if (ev == MTR_FASTA_NO_EVENT) {
+    if (ev == MTR_FASTA_NO_EVENT && more) {
+        n_reads = n_heads - 1;
+        end = MTR_FASTA_END_MORE;
+        end_pos = n_reads > 0 ? (int64_t)a.h_pos[n_reads] : 0;
+    } else if (ev == MTR_FASTA_NO_EVENT) {
         const uint32_t last = total - (n_heads > 1 ? a.h_base[n_heads - 1] : 0u);
         n_reads = n_heads - 1 + (last > 0u ? 1 : 0);
         end = last > 0u ? MTR_FASTA_END_EOF : MTR_FASTA_END_EMPTY;

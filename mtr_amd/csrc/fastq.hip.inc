@@ -37,6 +37,11 @@
 //                            does.
 // A sequence line is contiguous in the file, so mtr_upload_fastq_device compacts nothing: mtr_k_fastq_reads gives it the sequence lines'
 // starts and mtr_k_pack_text packs the file's own bytes from there.
+// A WINDOW of a longer input (mtr_parse_fastq_device_window, more = 1): the buffer is the input's first n bytes.  A stop that the bytes
+// before it decide is a stop of the input and is reported as ever.  Two stops need more than that and are not raised: "the file ends
+// inside a record", and the length of a quality line whose LF is not in the window.  Without a stop the reads are the records whose
+// quality line's LF is in the window, end = MTR_FASTA_END_MORE, end_pos = the byte behind the last such LF.  mtr_k_fastq_records and
+// mtr_k_fastq_finish know the mode.
 // Loads are fa_load16's aligned dwords (the file's last partial span bytewise); positions and counts are 32-bit; every result is written
 // with ordinary vector stores.
 
@@ -189,9 +194,12 @@ __global__ __launch_bounds__(MTR_FASTA_BLOCK) void mtr_k_fastq_tile(FastqArgs a)
 
 // One thread a record: its four lines against the rules that need the whole line - the stops other than those inside a sequence line -
 // and its columns.  A line that does not begin (the file ended) has no entry in the table.
-__global__ __launch_bounds__(256) void mtr_k_fastq_records(FastqArgs a)
+// more: the input goes on behind the buffer - a quality line is checked only if its LF is in the buffer (a line begins behind it, or it
+// is the buffer's last byte), and the buffer's end cuts no record.
+__global__ __launch_bounds__(256) void mtr_k_fastq_records(FastqArgs a, int32_t more)
 {
     unsigned long long ev = MTR_FASTA_NO_EVENT;
+    const bool ends_with_lf = more && a.fq[a.n - 1] == (uint8_t)10;
     for (uint32_t r = blockIdx.x * 256u + threadIdx.x; r < a.n_recs; r += gridDim.x * 256u) {
         const uint32_t l = 4u * r;
         unsigned long long e = MTR_FASTA_NO_EVENT, o;
@@ -210,8 +218,9 @@ __global__ __launch_bounds__(256) void mtr_k_fastq_records(FastqArgs a)
         }
         if (l + 3u < a.n_lines) {
             const uint32_t s3 = a.l_start[l + 3u];
-            if (a.l_end[l + 3u] - s3 != len) { o = fq_event(s3, MTR_FASTA_END_FORMAT); e = o < e ? o : e; }
-        } else {
+            const bool whole = !more || l + 4u < a.n_lines || ends_with_lf;
+            if (whole && a.l_end[l + 3u] - s3 != len) { o = fq_event(s3, MTR_FASTA_END_FORMAT); e = o < e ? o : e; }
+        } else if (!more) {
             o = fq_event((uint32_t)a.n, MTR_FASTA_END_FORMAT); e = o < e ? o : e;        // the file ends inside the record
         }
         a.r_pos[r] = (int32_t)s0; a.r_idlen[r] = at ? (int32_t)(e0 - s0 - 1u) : 0; a.r_len[r] = (int32_t)len;
@@ -222,12 +231,18 @@ __global__ __launch_bounds__(256) void mtr_k_fastq_records(FastqArgs a)
 
 // The reads before the stop and the sizes.  The stop lies in the record of the line it is on (the end of the file: in the record that
 // the file cuts); every record before that one is complete and correct, or the stop would be an earlier one.
-__global__ __launch_bounds__(64) void mtr_k_fastq_finish(FastqArgs a, const int64_t *id_off, mtr_fasta_info *info)
+// more: the input goes on behind the buffer - without a stop the reads are the records whose fourth LF is in the buffer, and the next
+// window starts behind that LF.
+__global__ __launch_bounds__(64) void mtr_k_fastq_finish(FastqArgs a, int32_t more, const int64_t *id_off, mtr_fasta_info *info)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const unsigned long long ev = *a.event;
     int32_t n_reads = (int32_t)(a.n_lines >> 2), end = MTR_FASTA_END_EOF, bad = 0; int64_t end_pos = a.n;
-    if (ev != MTR_FASTA_NO_EVENT) {
+    if (ev == MTR_FASTA_NO_EVENT && more) {
+        const uint32_t n_lf = a.n_lines - (a.fq[a.n - 1] == (uint8_t)10 ? 0u : 1u);       // (the last line has no LF yet)
+        n_reads = (int32_t)(n_lf >> 2); end = MTR_FASTA_END_MORE;
+        end_pos = 4u * (uint32_t)n_reads < a.n_lines ? (int64_t)a.l_start[4u * (uint32_t)n_reads] : (int64_t)a.n;
+    } else if (ev != MTR_FASTA_NO_EVENT) {
         end = (int32_t)(ev & 7ull); end_pos = (int64_t)(ev >> 3);
         if (end == MTR_FASTA_END_BADCHAR) bad = a.fq[end_pos];
         if (end_pos < (int64_t)a.n) {

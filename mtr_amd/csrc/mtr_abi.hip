@@ -1875,9 +1875,22 @@ extern "C" mtr_status mtr_report_text_device(mtr_ctx *ctx, const char *ids, cons
 // ---- a FASTA file in device memory (fasta.hip.inc) -----------------------------------------------------------------------------
 // Only the header count, the sizes and - for an upload - the reads' lengths, offsets and IDs come back to the host.
 // fastq: the file is FASTQ (fastq.hip.inc) and q holds its columns; the entry points share everything but the kernels
+// more (an argument of the functions below): the buffer is a window of a longer input, as the _window entry points say; 0 is the whole
+// file.  The finishing kernels alone read it: every launch, buffer and copy is the same in both modes.
 struct FastaParse { FastaArgs a; int32_t n_heads; mtr_fasta_info info; bool fastq; FastqArgs q; };
 
-static void fasta_no_reads(mtr_fasta_info *info) { memset(info, 0, sizeof *info); info->end = MTR_FASTA_END_EMPTY; }
+static void fasta_no_reads(mtr_fasta_info *info, int32_t more)
+{
+    memset(info, 0, sizeof *info);
+    info->end = more ? MTR_FASTA_END_MORE : MTR_FASTA_END_EMPTY;
+}
+
+static mtr_status fasta_more_arg(mtr_ctx *ctx, int32_t more_follows)
+{
+    if (more_follows == 0 || more_follows == 1) return MTR_OK;
+    ctx->err = "more_follows " + std::to_string(more_follows) + " is neither 0 nor 1";
+    return MTR_ERR_BAD_ARG;
+}
 
 // the checks of a file in device memory (what: the argument's name), and the context's stream made to wait for the caller's
 static mtr_status fasta_input(mtr_ctx *ctx, const uint8_t *d_file, int64_t n_bytes, void *wait_stream, const char *what)
@@ -1898,7 +1911,7 @@ static mtr_status fasta_input(mtr_ctx *ctx, const uint8_t *d_file, int64_t n_byt
 }
 
 // the arguments' checks and the scans, up to the sizes (p.info) and the header windows' columns on the device
-static mtr_status fasta_index(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, FastaParse &p)
+static mtr_status fasta_index(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, int32_t more, void *wait_stream, FastaParse &p)
 {
     { mtr_status st = fasta_input(ctx, d_fasta, n_bytes, wait_stream, "d_fasta"); if (st != MTR_OK) return st; }
     const int32_t n_tiles = (int32_t)((n_bytes + MTR_FASTA_TILE_BYTES - 1) / MTR_FASTA_TILE_BYTES);
@@ -1925,14 +1938,15 @@ static mtr_status fasta_index(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_by
     HIPCHK(hipMemsetAsync(a.h_pos, 0, nh * 4, ctx->stream)); HIPCHK(hipMemsetAsync(a.h_base, 0, nh * 4, ctx->stream)); HIPCHK(hipMemsetAsync(a.h_idlen, 0, nh * 4, ctx->stream));
     hipLaunchKernelGGL(mtr_k_fasta_tile<1>, dim3((unsigned)n_tiles), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, a);
     hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.h_idlen, (int64_t)p.n_heads, (int64_t *)ctx->d_fa_idoff);
-    hipLaunchKernelGGL(mtr_k_fasta_finish, dim3(1), dim3(64), 0, ctx->stream, a, p.n_heads, (const int64_t *)ctx->d_fa_idoff, (mtr_fasta_info *)ctx->d_fa_info);
+    hipLaunchKernelGGL(mtr_k_fasta_finish, dim3(1), dim3(64), 0, ctx->stream, a, p.n_heads, more, (const int64_t *)ctx->d_fa_idoff,
+                       (mtr_fasta_info *)ctx->d_fa_info);
     HIPCHK(hipGetLastError());
     HIPCHK(copy_sync(ctx, &p.info, ctx->d_fa_info, sizeof(mtr_fasta_info), hipMemcpyDeviceToHost));
     return MTR_OK;
 }
 
 // fasta_index for a FASTQ file: the line table, the records' columns, the sizes.  Only the line count and the sizes come to the host.
-static mtr_status fastq_index(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_bytes, void *wait_stream, FastaParse &p)
+static mtr_status fastq_index(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_bytes, int32_t more, void *wait_stream, FastaParse &p)
 {
     { mtr_status st = fasta_input(ctx, d_fastq, n_bytes, wait_stream, "d_fastq"); if (st != MTR_OK) return st; }
     const int32_t n_tiles = (int32_t)((n_bytes + MTR_FASTA_TILE_BYTES - 1) / MTR_FASTA_TILE_BYTES);
@@ -1957,10 +1971,10 @@ static mtr_status fastq_index(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_by
     p.a.fa = d_fastq; p.a.h_pos = a.r_pos;                        // what mtr_k_fasta_ids reads: a header is a position there too
     hipLaunchKernelGGL(mtr_k_fastq_tile<0>, dim3((unsigned)n_tiles), dim3(MTR_FASTA_BLOCK), 0, ctx->stream, a);
     const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)nr + 255) / 256, (int64_t)ctx->n_cu * 8);
-    hipLaunchKernelGGL(mtr_k_fastq_records, dim3(blocks), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(mtr_k_fastq_records, dim3(blocks), dim3(256), 0, ctx->stream, a, more);
     hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.r_idlen, (int64_t)nr, (int64_t *)ctx->d_fa_idoff);
     hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.r_len, (int64_t)nr, (int64_t *)ctx->d_fq_boff);
-    hipLaunchKernelGGL(mtr_k_fastq_finish, dim3(1), dim3(64), 0, ctx->stream, a, (const int64_t *)ctx->d_fa_idoff, (mtr_fasta_info *)ctx->d_fa_info);
+    hipLaunchKernelGGL(mtr_k_fastq_finish, dim3(1), dim3(64), 0, ctx->stream, a, more, (const int64_t *)ctx->d_fa_idoff, (mtr_fasta_info *)ctx->d_fa_info);
     HIPCHK(hipGetLastError());
     HIPCHK(copy_sync(ctx, &p.info, ctx->d_fa_info, sizeof(mtr_fasta_info), hipMemcpyDeviceToHost));
     return MTR_OK;
@@ -1998,18 +2012,19 @@ static mtr_status fasta_write(mtr_ctx *ctx, const FastaParse &p, const mtr_fasta
     return MTR_OK;
 }
 
-static mtr_status parse_fasta(mtr_ctx *ctx, bool fastq, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, const mtr_fasta_dst *dst,
-                              mtr_fasta_info *info)
+static mtr_status parse_fasta(mtr_ctx *ctx, bool fastq, const uint8_t *d_fasta, int64_t n_bytes, int32_t more, void *wait_stream,
+                              const mtr_fasta_dst *dst, mtr_fasta_info *info)
 {
     if (!ctx || !info) return MTR_ERR_BAD_ARG;
-    fasta_no_reads(info);
+    { mtr_status st = fasta_more_arg(ctx, more); if (st != MTR_OK) return st; }
+    fasta_no_reads(info, more);
     HIPCHK(hipSetDevice(ctx->device));
-    if (n_bytes == 0) {                                           // an empty file: no reads, and no byte to look at
+    if (n_bytes == 0) {                                           // an empty file (or window): no reads, and no byte to look at
         if (dst && dst->id_off) { HIPCHK(hipMemsetAsync(dst->id_off, 0, 8, ctx->stream)); HIPCHK(hipStreamSynchronize(ctx->stream)); }
         return MTR_OK;
     }
     FastaParse p;
-    { mtr_status st = (fastq ? fastq_index : fasta_index)(ctx, d_fasta, n_bytes, wait_stream, p); if (st != MTR_OK) return st; }
+    { mtr_status st = (fastq ? fastq_index : fasta_index)(ctx, d_fasta, n_bytes, more, wait_stream, p); if (st != MTR_OK) return st; }
     *info = p.info;
     if (!dst) return MTR_OK;
     const mtr_fasta_info &f = p.info;
@@ -2029,25 +2044,37 @@ static mtr_status parse_fasta(mtr_ctx *ctx, bool fastq, const uint8_t *d_fasta, 
 extern "C" mtr_status mtr_parse_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, const mtr_fasta_dst *dst,
                                              mtr_fasta_info *info)
 {
-    return parse_fasta(ctx, false, d_fasta, n_bytes, wait_stream, dst, info);
+    return parse_fasta(ctx, false, d_fasta, n_bytes, 0, wait_stream, dst, info);
+}
+extern "C" mtr_status mtr_parse_fasta_device_window(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, int32_t more_follows, void *wait_stream,
+                                                    const mtr_fasta_dst *dst, mtr_fasta_info *info)
+{
+    return parse_fasta(ctx, false, d_fasta, n_bytes, more_follows, wait_stream, dst, info);
 }
 extern "C" mtr_status mtr_parse_fastq_device(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_bytes, void *wait_stream, const mtr_fasta_dst *dst,
                                              mtr_fasta_info *info)
 {
-    return parse_fasta(ctx, true, d_fastq, n_bytes, wait_stream, dst, info);
+    return parse_fasta(ctx, true, d_fastq, n_bytes, 0, wait_stream, dst, info);
+}
+extern "C" mtr_status mtr_parse_fastq_device_window(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_bytes, int32_t more_follows, void *wait_stream,
+                                                    const mtr_fasta_dst *dst, mtr_fasta_info *info)
+{
+    return parse_fasta(ctx, true, d_fastq, n_bytes, more_follows, wait_stream, dst, info);
 }
 
 // fastq: the reads stay where they are, in the file - a sequence line is contiguous there -, and the packing kernel reads them from it
-static mtr_status upload_fasta(mtr_ctx *ctx, mtr_file_state *fs, bool fastq, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info)
+static mtr_status upload_fasta(mtr_ctx *ctx, mtr_file_state *fs, bool fastq, const uint8_t *d_fasta, int64_t n_bytes, int32_t more, void *wait_stream,
+                               mtr_fasta_info *info)
 {
     if (!ctx || !info) return MTR_ERR_BAD_ARG;
-    fasta_no_reads(info);
+    { mtr_status st = fasta_more_arg(ctx, more); if (st != MTR_OK) return st; }
+    fasta_no_reads(info, more);
     HIPCHK(hipSetDevice(ctx->device));
     { mtr_status w = mtr_wait(ctx); if (w != MTR_OK && w != MTR_ERR_OVERFLOW && w != MTR_ERR_DP_TOO_LARGE) return w; }
     free_batch(ctx);                                              // whatever happens below, the batch before this call is gone
     ctx->fa_indexed = false;
     FastaParse p; p.info = *info;
-    if (n_bytes != 0) { mtr_status st = (fastq ? fastq_index : fasta_index)(ctx, d_fasta, n_bytes, wait_stream, p); if (st != MTR_OK) return st; }
+    if (n_bytes != 0) { mtr_status st = (fastq ? fastq_index : fasta_index)(ctx, d_fasta, n_bytes, more, wait_stream, p); if (st != MTR_OK) return st; }
     *info = p.info;
     const mtr_fasta_info &f = p.info;
     const size_t n = (size_t)f.n_reads;
@@ -2074,23 +2101,34 @@ static mtr_status upload_fasta(mtr_ctx *ctx, mtr_file_state *fs, bool fastq, con
 }
 extern "C" mtr_status mtr_upload_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info)
 {
-    return upload_fasta(ctx, nullptr, false, d_fasta, n_bytes, wait_stream, info);
+    return upload_fasta(ctx, nullptr, false, d_fasta, n_bytes, 0, wait_stream, info);
 }
 extern "C" mtr_status mtr_upload_fasta_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream,
                                                       mtr_fasta_info *info)
 {
     if (!fs) { if (ctx) ctx->err = "null file state"; return MTR_ERR_BAD_ARG; }
-    return upload_fasta(ctx, fs, false, d_fasta, n_bytes, wait_stream, info);
+    return upload_fasta(ctx, fs, false, d_fasta, n_bytes, 0, wait_stream, info);
+}
+// fs == NULL: isolated mode
+extern "C" mtr_status mtr_upload_fasta_device_window(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fasta, int64_t n_bytes, int32_t more_follows,
+                                                     void *wait_stream, mtr_fasta_info *info)
+{
+    return upload_fasta(ctx, fs, false, d_fasta, n_bytes, more_follows, wait_stream, info);
 }
 extern "C" mtr_status mtr_upload_fastq_device(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info)
 {
-    return upload_fasta(ctx, nullptr, true, d_fastq, n_bytes, wait_stream, info);
+    return upload_fasta(ctx, nullptr, true, d_fastq, n_bytes, 0, wait_stream, info);
 }
 extern "C" mtr_status mtr_upload_fastq_device_in_file(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fastq, int64_t n_bytes, void *wait_stream,
                                                       mtr_fasta_info *info)
 {
     if (!fs) { if (ctx) ctx->err = "null file state"; return MTR_ERR_BAD_ARG; }
-    return upload_fasta(ctx, fs, true, d_fastq, n_bytes, wait_stream, info);
+    return upload_fasta(ctx, fs, true, d_fastq, n_bytes, 0, wait_stream, info);
+}
+extern "C" mtr_status mtr_upload_fastq_device_window(mtr_ctx *ctx, mtr_file_state *fs, const uint8_t *d_fastq, int64_t n_bytes, int32_t more_follows,
+                                                     void *wait_stream, mtr_fasta_info *info)
+{
+    return upload_fasta(ctx, fs, true, d_fastq, n_bytes, more_follows, wait_stream, info);
 }
 
 extern "C" mtr_status mtr_fasta_index(const mtr_ctx *ctx, int32_t *lens, int64_t *id_off, char *ids)

@@ -15,6 +15,8 @@
 //   Working arrays: 12 n + 6 ints for n records.  Reads of up to MTR_CHAIN_LDS_RECS records (nearly all: config 4 averages
 //   2.7) keep them in LDS; longer reads in per-read global scratch the host lays out (any count).
 // mtr_k_report_pack: one wavefront per read writes its chained repeats at the read's offset into the caller's columns.
+// The records come through a RecordView (records.hip.inc); what mtr_k_chain found, every later kernel of the report reads through
+// a ChainView: the chain of read rd and the number of its first repeat.
 //
 // Every result is written with ordinary vector stores.
 
@@ -166,16 +168,13 @@ __device__ int chain_one_read(const ChainRecs &src, int n, int *mem, int32_t *ou
 
 // per read: chain_idx[rec_off[rd] ..] = the chain (record indices, print order), chain_len[rd], unit_bytes[rd] = the bytes of
 // its repeats' units.  scr_off[rd] >= 0: the read's working arrays are scratch + scr_off[rd] (more than MTR_CHAIN_LDS_RECS records).
-__global__ void __launch_bounds__(64) mtr_k_chain(const DevRecord *in, const DevRecord *const *src_of, const int32_t *cnt, int max_rec, int n_reads,
-                                                   const int64_t *rec_off, const int64_t *scr_off, int32_t *scratch, int32_t *chain_idx,
+__global__ void __launch_bounds__(64) mtr_k_chain(RecordView v, const int64_t *rec_off, const int64_t *scr_off, int32_t *scratch, int32_t *chain_idx,
                                                    int32_t *chain_len, int32_t *unit_bytes)
 {
     __shared__ int lds[MTR_CHAIN_INTS(MTR_CHAIN_LDS_RECS)];
     const int rd = blockIdx.x;
-    if (rd >= n_reads) return;
-    int c = cnt[rd];
-    if (!src_of && c > max_rec) c = max_rec;
-    const DevRecord *src = src_of ? src_of[rd] : in + (size_t)rd * (size_t)max_rec;
+    if (rd >= v.n_reads) return;
+    const auto [src, c] = v.read(rd);
     int *mem = c <= MTR_CHAIN_LDS_RECS ? lds : scratch + scr_off[rd];
     ChainRecs r = { src, nullptr, nullptr, nullptr };
     int32_t *out = chain_idx + rec_off[rd];
@@ -202,21 +201,24 @@ __global__ void __launch_bounds__(64) mtr_k_chain_sets(const int32_t *start, con
     if (threadIdx.x == 0) chain_len[k] = len;
 }
 
-// Columns of mtr_report_dst for read rd: its repeats k = rep_off[rd] .. + chain_len[rd], their units from unit_base[rd] on.
+// What mtr_k_chain left: read rd's chain is chain_idx[rec_off[rd] .. + chain_len[rd]), its repeats are k = rep_off[rd] .. + chain_len[rd]
+struct ReadChain { const int32_t *idx; int len; int64_t k0; };
+struct ChainView {
+    const int64_t *rec_off; const int32_t *chain_idx, *chain_len; const int64_t *rep_off;
+    __device__ __forceinline__ ReadChain read(int rd) const { return { chain_idx + rec_off[rd], chain_len[rd], rep_off[rd] }; }
+};
+
+// Columns of mtr_report_dst for read rd: its repeats (ChainView), their units from unit_base[rd] on.
 // Lane 0 of read 0 also writes unit_off[total_repeats] = total_unit_bytes.
-__global__ void __launch_bounds__(64) mtr_k_report_pack(const DevRecord *in, const DevRecord *const *src_of, int max_rec, int n_reads,
-                                                         const int64_t *rec_off, const int32_t *chain_idx, const int32_t *chain_len,
-                                                         const int64_t *rep_off, const int64_t *unit_base, int64_t total_repeats, int64_t total_unit_bytes,
+__global__ void __launch_bounds__(64) mtr_k_report_pack(RecordView v, ChainView ch, const int64_t *unit_base, int64_t total_repeats, int64_t total_unit_bytes,
                                                          int32_t *o_read, int32_t *o_record, int32_t *o_fields, float *o_ratio, int64_t *o_unit_off, uint8_t *o_units)
 {
     const int rd = blockIdx.x, lane = threadIdx.x;
-    if (rd >= n_reads) return;
+    if (rd >= v.n_reads) return;
     if (rd == 0 && lane == 0) o_unit_off[total_repeats] = total_unit_bytes;
-    const int len = chain_len[rd];
+    const auto [idx, len, k0] = ch.read(rd);
     if (len <= 0) return;
-    const DevRecord *src = src_of ? src_of[rd] : in + (size_t)rd * (size_t)max_rec;
-    const int32_t *idx = chain_idx + rec_off[rd];
-    const int64_t k0 = rep_off[rd];
+    const DevRecord *src = v.read(rd).rec;
     for (int q = lane; q < 14 * len; q += 64) {
         const int t = q / 14, f = q - 14 * t;
         o_fields[(k0 + t) * 14 + f] = src[idx[t]].f[f];

@@ -144,7 +144,7 @@ extern "C" mtr_status mtr_gather_get_stats(const mtr_gather *g, int64_t *out, in
     return MTR_OK;
 }
 
-// wire_layout / mtr_k_wire_pack of mtr_abi.hip: the finished batch of `ctx` -> a staging buffer on the same device
+// wire_form of mtr_abi.hip: the finished batch of `ctx` -> a staging buffer on the same device
 extern "C" mtr_status mtr_gather_stage(mtr_gather *g, int32_t rank, mtr_ctx *ctx, int32_t *counts_host, int64_t *out_total_records,
                                        int64_t *out_bytes, int32_t *out_ticket)
 {
@@ -152,40 +152,37 @@ extern "C" mtr_status mtr_gather_stage(mtr_gather *g, int32_t rank, mtr_ctx *ctx
     if (ctx->device != g->ranks[(size_t)rank].device) { ctx->err = "the context lives on device " + std::to_string(ctx->device) + ", rank " + std::to_string(rank) + " of the gather on " + std::to_string(g->ranks[(size_t)rank].device); return MTR_ERR_BAD_ARG; }
     { mtr_status r = results_ready(ctx, false); if (r != MTR_OK) return r; }
     HIPCHK(hipSetDevice(ctx->device));
-    const int n = ctx->n_reads;
-    const DevRecord *const *srcs = nullptr; int64_t recs = 0, bytes = 0;
-    { mtr_status st = wire_layout(ctx, n, &srcs, &recs, &bytes); if (st != MTR_OK) return st; }
-    memcpy(counts_host, ctx->h_counts, (size_t)n * 4);
-    *out_total_records = recs; *out_bytes = bytes;
-    // a free slot of this rank that is large enough, else the smallest free one grown, else a new one
     GatherRank &gr = g->ranks[(size_t)rank];
     int slot = -1;
-    void *old = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g->mu);
-        for (size_t i = 0; i < gr.slots.size(); i++) if (!gr.slots[i].busy && gr.slots[i].cap >= (size_t)bytes && (slot < 0 || gr.slots[i].cap < gr.slots[(size_t)slot].cap)) slot = (int)i;
-        if (slot < 0) for (size_t i = 0; i < gr.slots.size(); i++) if (!gr.slots[i].busy) { slot = (int)i; break; }
-        if (slot < 0) {
-            if (gr.slots.size() >= GATHER_SLOTS_PER_RANK) { ctx->err = "too many staged tables wait for an exchange"; return MTR_ERR_OVERFLOW; }
-            gr.slots.emplace_back(); slot = (int)gr.slots.size() - 1;
-        }
-        gr.slots[(size_t)slot].busy = true; gr.slots[(size_t)slot].bytes = bytes;
-        if (gr.slots[(size_t)slot].cap < (size_t)bytes) { old = gr.slots[(size_t)slot].d; gr.slots[(size_t)slot].d = nullptr; gr.slots[(size_t)slot].cap = 0; }
-    }
     auto release = [&]() { std::lock_guard<std::mutex> lk(g->mu); gr.slots[(size_t)slot].busy = false; };
-    if (old) (void)hipFree(old);
-    void *d = nullptr; size_t cap = 0;
-    { std::lock_guard<std::mutex> lk(g->mu); d = gr.slots[(size_t)slot].d; cap = gr.slots[(size_t)slot].cap; }
-    if (cap < (size_t)bytes || !d) {
-        const size_t want = std::max<size_t>((size_t)bytes * 5 / 4, (size_t)1 << 20);
-        if (hipMalloc(&d, want) != hipSuccess) { release(); ctx->err = "cannot allocate a staging buffer of " + std::to_string(want) + " bytes"; return MTR_ERR_OOM; }
-        std::lock_guard<std::mutex> lk(g->mu);
-        gr.slots[(size_t)slot].d = d; gr.slots[(size_t)slot].cap = want;
-    }
-    if (bytes > 0) {
-        hipLaunchKernelGGL(mtr_k_wire_pack, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d_records, srcs, ctx->d_reccount, ctx->d_wire_off, ctx->max_rec, n, (uint8_t *)d);
-        if (hipGetLastError() != hipSuccess) { release(); ctx->err = "mtr_k_wire_pack could not be launched"; return MTR_ERR_HIP; }
-    }
+    // a free slot of this rank that is large enough, else the smallest free one grown, else a new one
+    auto take_slot = [&](int64_t bytes, uint8_t **out) {
+        void *old = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(g->mu);
+            for (size_t i = 0; i < gr.slots.size(); i++) if (!gr.slots[i].busy && gr.slots[i].cap >= (size_t)bytes && (slot < 0 || gr.slots[i].cap < gr.slots[(size_t)slot].cap)) slot = (int)i;
+            if (slot < 0) for (size_t i = 0; i < gr.slots.size(); i++) if (!gr.slots[i].busy) { slot = (int)i; break; }
+            if (slot < 0) {
+                if (gr.slots.size() >= GATHER_SLOTS_PER_RANK) { ctx->err = "too many staged tables wait for an exchange"; return MTR_ERR_OVERFLOW; }
+                gr.slots.emplace_back(); slot = (int)gr.slots.size() - 1;
+            }
+            gr.slots[(size_t)slot].busy = true; gr.slots[(size_t)slot].bytes = bytes;
+            if (gr.slots[(size_t)slot].cap < (size_t)bytes) { old = gr.slots[(size_t)slot].d; gr.slots[(size_t)slot].d = nullptr; gr.slots[(size_t)slot].cap = 0; }
+        }
+        if (old) (void)hipFree(old);
+        void *d = nullptr; size_t cap = 0;
+        { std::lock_guard<std::mutex> lk(g->mu); d = gr.slots[(size_t)slot].d; cap = gr.slots[(size_t)slot].cap; }
+        if (cap < (size_t)bytes || !d) {
+            const size_t want = std::max<size_t>((size_t)bytes * 5 / 4, (size_t)1 << 20);
+            if (hipMalloc(&d, want) != hipSuccess) { ctx->err = "cannot allocate a staging buffer of " + std::to_string(want) + " bytes"; return MTR_ERR_OOM; }
+            std::lock_guard<std::mutex> lk(g->mu);
+            gr.slots[(size_t)slot].d = d; gr.slots[(size_t)slot].cap = want;
+        }
+        *out = (uint8_t *)d;
+        return MTR_OK;
+    };
+    const mtr_status st = wire_form(ctx, ctx->n_reads, counts_host, out_total_records, out_bytes, take_slot);
+    if (st != MTR_OK) { if (slot >= 0) release(); return st; }
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { release(); ctx->err = "the wire form could not be staged"; return MTR_ERR_HIP; }
     *out_ticket = rank * GATHER_SLOTS_PER_RANK + slot;
     return MTR_OK;

@@ -33,6 +33,7 @@
 #include "k2_units.hip.inc"
 #include "k3_staged.hip.inc"
 #include "pack.hip.inc"
+#include "records.hip.inc"
 #include "chain.hip.inc"
 #include "report_align.hip.inc"
 #include "report_text.hip.inc"
@@ -163,7 +164,7 @@ struct mtr_ctx {
     // reads that found more records than their max_rec slots are run again with room for all of them (resolve_overflow)
     std::vector<int32_t> ovf_reads; int ovf_cap = 0;
     DevBuf<DevRecord> d_ovf_records; DevBuf<int64_t> d_rec_base; DevBuf<int32_t> d_ovf_order;
-    DevBuf<const DevRecord *> d_src;                   // per read: where its records are (compaction)
+    DevBuf<const DevRecord *> d_src;                   // per read: where its records are, while ovf_reads is not empty (publish_record_sources)
     bool sub_active = false;                           // launch_reads works on ovf_reads with the overflow buffers
     // file-order mode (mtr_upload_batch_in_file): per read the stale tail of the reference's inputString_w_rand
     bool file_order = false; DevBuf<uint16_t> d_tail; DevBuf<int64_t> d_tail_off;
@@ -775,6 +776,9 @@ static BatchView view(const mtr_ctx *ctx)
     return b;
 }
 
+// the records of the finished batch: the pointer table exists while reads of it have their records in the overflow buffer
+static RecordView record_view(const mtr_ctx *ctx) { return { ctx->d_records, ctx->ovf_reads.empty() ? nullptr : ctx->d_src.p, ctx->d_reccount, ctx->max_rec, ctx->n_reads }; }
+
 static mtr_status check_status(mtr_ctx *ctx)
 {
     int32_t st = 0;
@@ -1262,6 +1266,20 @@ static mtr_status resolve_overflow(mtr_ctx *ctx)
     }
 }
 
+// The pointer table of record_view, made once when a run ends with such reads (whatever became of their second run: after a DP
+// failure the reads before the failing one are still read through it).
+static mtr_status publish_record_sources(mtr_ctx *ctx)
+{
+    if (ctx->ovf_reads.empty()) return MTR_OK;
+    const int n = ctx->n_reads;
+    std::vector<const DevRecord *> src((size_t)n);
+    for (int i = 0; i < n; i++) src[(size_t)i] = ctx->d_records + (size_t)i * (size_t)ctx->max_rec;
+    for (size_t k = 0; k < ctx->ovf_reads.size(); k++) src[(size_t)ctx->ovf_reads[k]] = ctx->d_ovf_records + k * (size_t)ctx->ovf_cap;
+    HIPCHK(ctx->d_src.ensure((size_t)n * sizeof(void *)));
+    HIPCHK(copy_sync(ctx, ctx->d_src, src.data(), (size_t)n * sizeof(void *), hipMemcpyHostToDevice));
+    return MTR_OK;
+}
+
 // status, first failed read and counters start from zero for a launch of the resident batch
 static mtr_status reset_run_state(mtr_ctx *ctx)
 {
@@ -1432,8 +1450,9 @@ extern "C" mtr_status mtr_wait(mtr_ctx *ctx)
     if (st == MTR_OK || st == MTR_ERR_DP_TOO_LARGE) {
         // reads that found more records than their slots are run again (also after a DP failure: the reads before the
         // failing one are still reported, as the reference has printed them when it exits)
-        const mtr_status so = resolve_overflow(ctx);
-        if (so != MTR_OK && so != MTR_ERR_DP_TOO_LARGE) st = so;
+        mtr_status so = resolve_overflow(ctx);
+        if (so == MTR_OK || so == MTR_ERR_DP_TOO_LARGE) so = publish_record_sources(ctx);
+        if (so != MTR_OK) st = so;
     }
     ctx->run_status = st;
     ctx->ran = (st == MTR_OK);
@@ -1444,75 +1463,6 @@ extern "C" mtr_status mtr_run_resident(mtr_ctx *ctx)
 {
     mtr_status s = mtr_run_resident_async(ctx); if (s != MTR_OK) return s;
     return mtr_wait(ctx);
-}
-
-// device array of per-read record sources for the compaction, or nullptr when every read's records are in its own slots
-static mtr_status record_sources(mtr_ctx *ctx, const DevRecord *const **out)
-{
-    *out = nullptr;
-    if (ctx->ovf_reads.empty()) return MTR_OK;
-    const int n = ctx->n_reads;
-    std::vector<const DevRecord *> src((size_t)n);
-    for (int i = 0; i < n; i++) src[(size_t)i] = ctx->d_records + (size_t)i * (size_t)ctx->max_rec;
-    for (size_t k = 0; k < ctx->ovf_reads.size(); k++) src[(size_t)ctx->ovf_reads[k]] = ctx->d_ovf_records + k * (size_t)ctx->ovf_cap;
-    HIPCHK(ctx->d_src.ensure((size_t)n * sizeof(void *)));
-    HIPCHK(copy_sync(ctx, ctx->d_src, src.data(), (size_t)n * sizeof(void *), hipMemcpyHostToDevice));
-    *out = ctx->d_src;
-    return MTR_OK;
-}
-
-__global__ void mtr_k_compact(const DevRecord *in, const DevRecord *const *src_of, const int32_t *cnt, const int64_t *off, int max_rec, int n_reads, DevRecord *out)
-{
-    // one block per read; records are copied as 16-byte words.  src_of (optional) = where each read's records are
-    // (reads that were run again with more slots have theirs in the overflow buffer; every other read has at most max_rec)
-    int rd = blockIdx.x;
-    if (rd >= n_reads) return;
-    int c = cnt[rd];
-    if (!src_of && c > max_rec) c = max_rec;
-    const uint4 *src = (const uint4 *)(src_of ? src_of[rd] : in + (size_t)rd * (size_t)max_rec);
-    uint4 *dst = (uint4 *)(out + off[rd]);
-    size_t words = (size_t)c * sizeof(DevRecord) / 16;
-    for (size_t t = threadIdx.x; t < words; t += blockDim.x) dst[t] = src[t];
-}
-
-// ---- wire form (include/mtr_hip.h): 14 int32 | rep_period unit bytes padded to 4 | rep_period int32 scores ---------
-__device__ __forceinline__ int wire_period(const DevRecord *r) { int p = r->f[3]; return p < 0 ? 0 : (p > MTRC_MAX_PERIOD ? MTRC_MAX_PERIOD : p); }
-__global__ void mtr_k_wire_sizes(const DevRecord *in, const DevRecord *const *src_of, const int32_t *cnt, int max_rec, int n_reads, int64_t *bytes)
-{
-    const int rd = blockIdx.x * blockDim.x + threadIdx.x;
-    if (rd >= n_reads) return;
-    int c = cnt[rd];
-    if (!src_of && c > max_rec) c = max_rec;
-    const DevRecord *src = src_of ? src_of[rd] : in + (size_t)rd * (size_t)max_rec;
-    int64_t b = 0;
-    for (int t = 0; t < c; t++) { const int p = wire_period(src + t); b += 56 + ((p + 3) & ~3) + 4 * p; }
-    bytes[rd] = b;
-}
-__global__ void mtr_k_wire_pack(const DevRecord *in, const DevRecord *const *src_of, const int32_t *cnt, const int64_t *off, int max_rec, int n_reads, uint8_t *out)
-{
-    // one wavefront per read; every piece of a wire record is a whole number of dwords at a dword-aligned offset
-    const int rd = blockIdx.x;
-    if (rd >= n_reads) return;
-    int c = cnt[rd];
-    if (!src_of && c > max_rec) c = max_rec;
-    const DevRecord *src = src_of ? src_of[rd] : in + (size_t)rd * (size_t)max_rec;
-    uint32_t *dst = (uint32_t *)(out + off[rd]);
-    for (int t = 0; t < c; t++) {
-        const DevRecord *r = src + t;
-        const int p = wire_period(r), uw = (p + 3) >> 2;
-        const uint32_t *h = (const uint32_t *)r->f, *u = (const uint32_t *)r->unit, *sc = (const uint32_t *)r->unit_score;
-        for (int q = threadIdx.x; q < 14 + uw + p; q += blockDim.x) {
-            uint32_t v;
-            if (q < 14) v = h[q];
-            else if (q < 14 + uw) {
-                v = u[q - 14];
-                const int keep = p - 4 * (q - 14);                       // bytes of this word that belong to the unit
-                if (keep < 4) v &= (1u << (8 * keep)) - 1u;
-            } else v = sc[q - 14 - uw];
-            dst[q] = v;
-        }
-        dst += 14 + uw + p;
-    }
 }
 
 // status of the resident batch for the calls that read its results
@@ -1550,9 +1500,7 @@ extern "C" mtr_status mtr_fetch_results(mtr_ctx *ctx, mtr_record **out_records, 
     if (total > 0) {
         HIPCHK(ctx->d_out.ensure((size_t)total * sizeof(DevRecord)));
         HIPCHK(hipMemcpyAsync(ctx->d_recoff, off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        const DevRecord *const *srcs = nullptr;
-        { mtr_status st = record_sources(ctx, &srcs); if (st != MTR_OK) return st; }
-        hipLaunchKernelGGL(mtr_k_compact, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d_records, srcs, ctx->d_reccount, ctx->d_recoff, ctx->max_rec, n, ctx->d_out);
+        hipLaunchKernelGGL(mtr_k_compact, dim3((unsigned)n), dim3(64), 0, ctx->stream, record_view(ctx), (const int64_t *)ctx->d_recoff, (DevRecord *)ctx->d_out);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(recs.get(), ctx->d_out, (size_t)total * sizeof(DevRecord), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1561,16 +1509,16 @@ extern "C" mtr_status mtr_fetch_results(mtr_ctx *ctx, mtr_record **out_records, 
     return MTR_OK;
 }
 
-// sizes + offsets of the wire form of reads [0, n): counts and per-read byte sizes come to pinned host memory
-static mtr_status wire_layout(mtr_ctx *ctx, int n, const DevRecord *const **srcs_out, int64_t *total_records, int64_t *total_bytes)
+// The wire form of reads [0, n) of the finished batch into device memory the caller chooses once its size is known (dest(bytes, &d); an empty
+// form writes nothing there).  The counts come to ctx->h_counts, and to counts_host if that is given; the packing is enqueued, not waited for.
+template <typename Dest>
+static mtr_status wire_form(mtr_ctx *ctx, int n, int32_t *counts_host, int64_t *total_records, int64_t *total_bytes, Dest dest)
 {
     HIPCHK(ctx->h_counts.ensure((size_t)n * 4));
     HIPCHK(ctx->h_sizes.ensure(((size_t)n + 1) * 8));
     HIPCHK(ctx->d_wire_bytes.ensure((size_t)n * 8)); HIPCHK(ctx->d_wire_off.ensure(((size_t)n + 1) * 8));
-    const DevRecord *const *srcs = nullptr;
-    { mtr_status st = record_sources(ctx, &srcs); if (st != MTR_OK) return st; }
-    *srcs_out = srcs;
-    hipLaunchKernelGGL(mtr_k_wire_sizes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_records, srcs, ctx->d_reccount, ctx->max_rec, n, ctx->d_wire_bytes);
+    RecordView v = record_view(ctx); v.n_reads = n;
+    hipLaunchKernelGGL(mtr_k_wire_sizes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, v, (int64_t *)ctx->d_wire_bytes);
     HIPCHK(hipGetLastError());
     int32_t *counts = (int32_t *)ctx->h_counts; int64_t *sizes = (int64_t *)ctx->h_sizes;
     HIPCHK(hipMemcpyAsync(counts, ctx->d_reccount, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1579,8 +1527,13 @@ static mtr_status wire_layout(mtr_ctx *ctx, int n, const DevRecord *const **srcs
     int64_t recs = 0, off = 0;
     for (int i = 0; i < n; i++) { recs += counts[i]; const int64_t b = sizes[i]; sizes[i] = off; off += b; }   // in place: sizes -> offsets
     sizes[n] = off;
+    if (counts_host) memcpy(counts_host, counts, (size_t)n * 4);
     *total_records = recs; *total_bytes = off;
     HIPCHK(hipMemcpyAsync(ctx->d_wire_off, sizes, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    uint8_t *d = nullptr;
+    { mtr_status st = dest(off, &d); if (st != MTR_OK) return st; }
+    if (off > 0) hipLaunchKernelGGL(mtr_k_wire_pack, dim3((unsigned)n), dim3(64), 0, ctx->stream, v, (const int64_t *)ctx->d_wire_off, d);
+    HIPCHK(hipGetLastError());
     return MTR_OK;
 }
 
@@ -1595,15 +1548,11 @@ extern "C" mtr_status mtr_fetch_results_packed(mtr_ctx *ctx, int32_t n_reads_lim
     if (ctx->run_status == MTR_ERR_DP_TOO_LARGE && (ctx->first_failed < 0 || n > ctx->first_failed)) { ctx->err = "only the reads before the first failed one can be fetched"; return MTR_ERR_DP_TOO_LARGE; }
     *out_blob = nullptr; *out_bytes = 0; *out_counts = nullptr; if (out_total_records) *out_total_records = 0;
     if (n == 0) return MTR_OK;
-    const DevRecord *const *srcs = nullptr; int64_t recs = 0, bytes = 0;
-    { mtr_status st = wire_layout(ctx, n, &srcs, &recs, &bytes); if (st != MTR_OK) return st; }
+    int64_t recs = 0, bytes = 0;
+    { mtr_status st = wire_form(ctx, n, nullptr, &recs, &bytes, [&](int64_t b, uint8_t **d) { if (b > 0) HIPCHK(ctx->d_wire.ensure((size_t)b)); *d = ctx->d_wire; return MTR_OK; });
+      if (st != MTR_OK) return st; }
     HIPCHK(ctx->h_blob.ensure((size_t)std::max<int64_t>(bytes, 4)));
-    if (bytes > 0) {
-        HIPCHK(ctx->d_wire.ensure((size_t)bytes));
-        hipLaunchKernelGGL(mtr_k_wire_pack, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d_records, srcs, ctx->d_reccount, ctx->d_wire_off, ctx->max_rec, n, ctx->d_wire);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(ctx->h_blob, ctx->d_wire, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    if (bytes > 0) HIPCHK(hipMemcpyAsync(ctx->h_blob, ctx->d_wire, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     *out_blob = (const uint8_t *)ctx->h_blob; *out_bytes = bytes; *out_counts = (const int32_t *)ctx->h_counts;
     if (out_total_records) *out_total_records = recs;
@@ -1616,54 +1565,57 @@ extern "C" mtr_status mtr_export_packed_device(mtr_ctx *ctx, void *d_dst, int64_
     if (!ctx || !counts_host || !out_total_records || !out_bytes) return MTR_ERR_BAD_ARG;
     { mtr_status r = results_ready(ctx, false); if (r != MTR_OK) return r; }
     HIPCHK(hipSetDevice(ctx->device));
-    const int n = ctx->n_reads;
-    const DevRecord *const *srcs = nullptr; int64_t recs = 0, bytes = 0;
-    { mtr_status st = wire_layout(ctx, n, &srcs, &recs, &bytes); if (st != MTR_OK) return st; }
-    memcpy(counts_host, ctx->h_counts, (size_t)n * 4);
-    *out_total_records = recs; *out_bytes = bytes;
-    if (bytes == 0) { HIPCHK(hipStreamSynchronize(ctx->stream)); return MTR_OK; }
-    if (!d_dst || bytes > capacity_bytes) { (void)hipStreamSynchronize(ctx->stream); ctx->err = "destination holds " + std::to_string(capacity_bytes) + " bytes, " + std::to_string(bytes) + " needed"; return MTR_ERR_OVERFLOW; }
-    hipLaunchKernelGGL(mtr_k_wire_pack, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d_records, srcs, ctx->d_reccount, ctx->d_wire_off, ctx->max_rec, n, (uint8_t *)d_dst);
-    HIPCHK(hipGetLastError());
+    const mtr_status st = wire_form(ctx, ctx->n_reads, counts_host, out_total_records, out_bytes, [&](int64_t bytes, uint8_t **d) {
+        *d = (uint8_t *)d_dst;
+        if (bytes == 0 || (d_dst && bytes <= capacity_bytes)) return MTR_OK;
+        (void)hipStreamSynchronize(ctx->stream);
+        ctx->err = "destination holds " + std::to_string(capacity_bytes) + " bytes, " + std::to_string(bytes) + " needed";
+        return MTR_ERR_OVERFLOW;
+    });
+    if (st != MTR_OK) return st;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
 }
 
 // ---- mTR's report on the device (chain.hip.inc) ----------------------------------------------------------------------------
+#define MTR_OFFSETS_LEN(n) (4 * (size_t)(n) + 3)              // int64 entries of ch_off / d_ch_off, and of d_ra_sizes
 // ch_off (host, and the same on the device in d_ch_off): [0, n] record offsets | [n+1, 2n] scratch offsets (-1: LDS) |
 // [2n+1, 3n+1] offsets of the reads' repeats | [3n+2, 4n+2] offsets of their unit bytes.  h_ch: counts | chain lengths | unit bytes.
+struct ChainOffsets { int64_t *rec_off, *scr_off, *rep_off, *unit_base; };
+static ChainOffsets chain_offsets(int64_t *base, int n) { return { base, base + n + 1, base + 2 * n + 1, base + 3 * n + 2 }; }
+static ChainView chain_view(const mtr_ctx *ctx) { const ChainOffsets d = chain_offsets(ctx->d_ch_off, ctx->n_reads); return { d.rec_off, ctx->d_ch_idx, ctx->d_ch_len, d.rep_off }; }
+
 static mtr_status report_chains(mtr_ctx *ctx)
 {
     if (ctx->rep_ready) return MTR_OK;
     const int n = ctx->n_reads;
-    const DevRecord *const *srcs = nullptr;
-    { mtr_status st = record_sources(ctx, &srcs); if (st != MTR_OK) return st; }
+    const RecordView v = record_view(ctx);
     HIPCHK(ctx->h_ch.ensure((size_t)n * 12));
     int32_t *h = ctx->h_ch;
     HIPCHK(copy_sync(ctx, h, ctx->d_reccount, (size_t)n * 4, hipMemcpyDeviceToHost));
-    ctx->ch_off.assign(4 * (size_t)n + 3, 0);
-    int64_t *rec_off = ctx->ch_off.data(), *scr_off = rec_off + n + 1, *rep_off = scr_off + n, *ubase = rep_off + n + 1;
+    ctx->ch_off.assign(MTR_OFFSETS_LEN(n), 0);
+    const ChainOffsets o = chain_offsets(ctx->ch_off.data(), n);
     int64_t scr = 0;
     for (int i = 0; i < n; i++) {
-        int c = h[i];
-        if (!srcs && c > ctx->max_rec) c = ctx->max_rec;            // as the compaction reads them
-        rec_off[i + 1] = rec_off[i] + c;
-        scr_off[i] = c > MTR_CHAIN_LDS_RECS ? scr : -1;
+        const int c = v.usable(h[i]);
+        o.rec_off[i + 1] = o.rec_off[i] + c;
+        o.scr_off[i] = c > MTR_CHAIN_LDS_RECS ? scr : -1;
         if (c > MTR_CHAIN_LDS_RECS) scr += MTR_CHAIN_INTS(c);
     }
-    HIPCHK(ctx->d_ch_off.ensure(ctx->ch_off.size() * 8));
-    HIPCHK(ctx->d_ch_idx.ensure((size_t)std::max<int64_t>(rec_off[n], 1) * 4));
+    HIPCHK(ctx->d_ch_off.ensure(MTR_OFFSETS_LEN(n) * 8));
+    HIPCHK(ctx->d_ch_idx.ensure((size_t)std::max<int64_t>(o.rec_off[n], 1) * 4));
     HIPCHK(ctx->d_ch_len.ensure((size_t)n * 8));
     HIPCHK(ctx->d_ch_scr.ensure((size_t)std::max<int64_t>(scr, 1) * 4));
-    HIPCHK(copy_sync(ctx, ctx->d_ch_off, rec_off, (2 * (size_t)n + 1) * 8, hipMemcpyHostToDevice));
-    int64_t *d_off = ctx->d_ch_off;
-    hipLaunchKernelGGL(mtr_k_chain, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d_records, srcs, ctx->d_reccount, ctx->max_rec, n,
-                       d_off, d_off + n + 1, ctx->d_ch_scr, ctx->d_ch_idx, ctx->d_ch_len, ctx->d_ch_len + n);
+    const ChainOffsets d = chain_offsets(ctx->d_ch_off, n);
+    const size_t before_chain = (size_t)(o.rep_off - o.rec_off);          // the record and scratch offsets: what mtr_k_chain reads
+    HIPCHK(copy_sync(ctx, d.rec_off, o.rec_off, before_chain * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(mtr_k_chain, dim3((unsigned)n), dim3(64), 0, ctx->stream, v, (const int64_t *)d.rec_off, (const int64_t *)d.scr_off,
+                       (int32_t *)ctx->d_ch_scr, (int32_t *)ctx->d_ch_idx, (int32_t *)ctx->d_ch_len, ctx->d_ch_len + n);
     HIPCHK(hipGetLastError());
     HIPCHK(copy_sync(ctx, h + n, ctx->d_ch_len, (size_t)n * 8, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; i++) { rep_off[i + 1] = rep_off[i] + h[n + i]; ubase[i + 1] = ubase[i] + h[2 * n + i]; }
-    HIPCHK(copy_sync(ctx, d_off + 2 * n + 1, rep_off, (2 * (size_t)n + 2) * 8, hipMemcpyHostToDevice));
-    ctx->rep_total = rep_off[n]; ctx->rep_unit_bytes = ubase[n];
+    for (int i = 0; i < n; i++) { o.rep_off[i + 1] = o.rep_off[i] + h[n + i]; o.unit_base[i + 1] = o.unit_base[i] + h[2 * n + i]; }
+    HIPCHK(copy_sync(ctx, d.rep_off, o.rep_off, (MTR_OFFSETS_LEN(n) - before_chain) * 8, hipMemcpyHostToDevice));
+    ctx->rep_total = o.rep_off[n]; ctx->rep_unit_bytes = o.unit_base[n];
     ctx->rep_ready = true;
     return MTR_OK;
 }
@@ -1687,11 +1639,8 @@ extern "C" mtr_status mtr_report_device(mtr_ctx *ctx, const mtr_report_dst *dst,
     if (!dst->unit_off || (R > 0 && (!dst->read || !dst->record || !dst->fields || !dst->ratio)) || (U > 0 && !dst->units)) {
         ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
     }
-    const DevRecord *const *srcs = nullptr;
-    { mtr_status st = record_sources(ctx, &srcs); if (st != MTR_OK) return st; }
-    const int64_t *d_off = ctx->d_ch_off;
-    hipLaunchKernelGGL(mtr_k_report_pack, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d_records, srcs, ctx->max_rec, n, d_off,
-                       ctx->d_ch_idx, ctx->d_ch_len, d_off + 2 * n + 1, d_off + 3 * n + 2, R, U,
+    hipLaunchKernelGGL(mtr_k_report_pack, dim3((unsigned)n), dim3(64), 0, ctx->stream, record_view(ctx), chain_view(ctx),
+                       (const int64_t *)chain_offsets(ctx->d_ch_off, n).unit_base, R, U,
                        dst->read, dst->record, dst->fields, dst->ratio, dst->unit_off, dst->units);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1701,6 +1650,18 @@ extern "C" mtr_status mtr_report_device(mtr_ctx *ctx, const mtr_report_dst *dst,
 // ---- the -a alignments of the report's repeats (report_align.hip.inc) -------------------------------------------------------
 // d_ra_sizes: [0, n) path bytes per read | [n, 2n) unit bytes per read | [2n, 3n] offsets of the reads' units | [3n+1, 4n+1] offsets of
 // their paths | [4n+2] cells of the largest DP.  Only those closing scalars and the number of columns come to the host.
+struct AlignSizes { int64_t *read_cap, *read_units, *unit_base, *cap_base, *max_cells; };
+static AlignSizes align_sizes(int64_t *base, int n) { return { base, base + n, base + 2 * n, base + 3 * n + 1, base + 4 * n + 2 }; }
+
+// what mtr_k_align and mtr_k_scan_offsets left of the report's repeats, for the kernels that print them
+static AlignRenderArgs render_args(const mtr_ctx *ctx)
+{
+    AlignRenderArgs a{};
+    a.b = view(ctx); a.n_repeats = (int32_t)ctx->rep_total;
+    a.read_idx = ctx->d_ra_i32; a.rep_start = ctx->d_ra_i32 + (size_t)ctx->rep_total; a.ops_len = ctx->d_ra_len; a.ends = ctx->d_ra_ends;
+    a.path = ctx->d_ra_ops; a.path_off = ctx->d_ra_off; a.rec_of = ctx->d_ra_rec; a.work_counter = ctx->d_work;
+    return a;
+}
 static mtr_status report_alignments(mtr_ctx *ctx)
 {
     if (ctx->ra_ready) return MTR_OK;
@@ -1716,21 +1677,19 @@ static mtr_status report_alignments(mtr_ctx *ctx)
     }
     if (R > (int64_t)INT32_MAX) { ctx->err = "more reported repeats than one alignment launch takes"; return MTR_ERR_OVERFLOW; }
     read_switches(ctx->sw);
-    const DevRecord *const *srcs = nullptr;
-    { mtr_status st = record_sources(ctx, &srcs); if (st != MTR_OK) return st; }
-    HIPCHK(ctx->d_ra_sizes.ensure((4 * (size_t)n + 3) * 8));
-    int64_t *d_sz = ctx->d_ra_sizes, *d_ubase = d_sz + 2 * (size_t)n, *d_cbase = d_ubase + n + 1, *d_cells = d_cbase + n + 1;
-    const int64_t *d_off = ctx->d_ch_off;
-    HIPCHK(hipMemsetAsync(d_cells, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(mtr_k_align_sizes, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d_records, srcs, ctx->max_rec, n, d_off,
-                       ctx->d_ch_idx, ctx->d_ch_len, ctx->d_lens, d_sz, d_sz + n, (unsigned long long *)d_cells);
+    const RecordView v = record_view(ctx); const ChainView ch = chain_view(ctx);
+    HIPCHK(ctx->d_ra_sizes.ensure(MTR_OFFSETS_LEN(n) * 8));
+    const AlignSizes z = align_sizes(ctx->d_ra_sizes, n);
+    HIPCHK(hipMemsetAsync(z.max_cells, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(mtr_k_align_sizes, dim3((unsigned)n), dim3(64), 0, ctx->stream, v, ch, (const int32_t *)ctx->d_lens,
+                       z.read_cap, z.read_units, (unsigned long long *)z.max_cells);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int64_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)d_sz, (int64_t)n, d_cbase);
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int64_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)(d_sz + n), (int64_t)n, d_ubase);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int64_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)z.read_cap, (int64_t)n, z.cap_base);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int64_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)z.read_units, (int64_t)n, z.unit_base);
     HIPCHK(hipGetLastError());
-    int64_t unit_bytes = 0, tail[2] = { 0, 0 };                           // tail: the paths' bytes, the largest DP's cells
-    HIPCHK(hipMemcpyAsync(&unit_bytes, d_ubase + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(tail, d_cbase + n, 16, hipMemcpyDeviceToHost, ctx->stream));
+    int64_t unit_bytes = 0, tail[2] = { 0, 0 };                           // tail: the paths' bytes (cap_base[n]), the largest DP's cells behind them
+    HIPCHK(hipMemcpyAsync(&unit_bytes, z.unit_base + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(tail, z.cap_base + n, 16, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     const size_t ops_bytes = (size_t)tail[0], cells = (size_t)std::max<int64_t>(tail[1], 1);
     if (unit_bytes > (int64_t)INT32_MAX) { ctx->err = "the units of the reported repeats exceed 2 GB"; return MTR_ERR_OVERFLOW; }
@@ -1747,8 +1706,8 @@ static mtr_status report_alignments(mtr_ctx *ctx)
     AlignTaskDst t{};
     t.read_idx = d_i32; t.rep_start = d_i32 + nt; t.rep_end = d_i32 + 2 * nt; t.gain = d_i32 + 3 * nt; t.mism = d_i32 + 4 * nt; t.indel = d_i32 + 5 * nt;
     t.unit_off = d_i32 + 6 * nt; t.ops_off = ctx->d_ra_off; t.units = ctx->d_ra_units; t.rec_of = ctx->d_ra_rec;
-    hipLaunchKernelGGL(mtr_k_align_tasks, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d_records, srcs, ctx->max_rec, n, d_off,
-                       ctx->d_ch_idx, ctx->d_ch_len, d_off + 2 * n + 1, ctx->d_lens, (const int64_t *)d_cbase, (const int64_t *)d_ubase, R, t);
+    hipLaunchKernelGGL(mtr_k_align_tasks, dim3((unsigned)n), dim3(64), 0, ctx->stream, v, ch, (const int32_t *)ctx->d_lens,
+                       (const int64_t *)z.cap_base, (const int64_t *)z.unit_base, R, t);
     HIPCHK(hipGetLastError());
     AlignArgs a{};
     a.b = view(ctx); a.n_tasks = (int32_t)R;
@@ -1787,13 +1746,9 @@ extern "C" mtr_status mtr_report_alignments_device(mtr_ctx *ctx, const mtr_repor
     if (!dst->col_off || (R > 0 && !dst->first) || (Cn > 0 && (!dst->ops || !dst->text))) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
     HIPCHK(hipMemcpyAsync(dst->col_off, ctx->d_ra_coloff, ((size_t)R + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
     if (R > 0) {
-        const size_t nt = (size_t)R;
-        AlignRenderArgs a{};
-        a.b = view(ctx); a.n_repeats = (int32_t)R;
-        a.read_idx = ctx->d_ra_i32; a.rep_start = ctx->d_ra_i32 + nt; a.ops_len = ctx->d_ra_len; a.ends = ctx->d_ra_ends;
-        a.path = ctx->d_ra_ops; a.path_off = ctx->d_ra_off; a.rec_of = ctx->d_ra_rec;
+        AlignRenderArgs a = render_args(ctx);
         a.col_off = ctx->d_ra_coloff; a.n_columns = Cn;
-        a.ops = dst->ops; a.text = dst->text; a.first = dst->first; a.work_counter = ctx->d_work;
+        a.ops = dst->ops; a.text = dst->text; a.first = dst->first;
         HIPCHK(hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned), ctx->stream));
         const unsigned waves = (unsigned)std::min<int64_t>(R, (int64_t)ctx->n_cu * 16);
         hipLaunchKernelGGL(mtr_k_align_render, dim3(waves), dim3(64), 0, ctx->stream, a);
@@ -1818,15 +1773,11 @@ extern "C" mtr_status mtr_report_text_device(mtr_ctx *ctx, const char *ids, cons
         if (id_off[i + 1] < id_off[i]) { ctx->err = "id_off decreases at read " + std::to_string(i); return MTR_ERR_BAD_ARG; }
     { mtr_status st = with_alignments ? report_alignments(ctx) : report_chains(ctx); if (st != MTR_OK) return st; }
     const int64_t R = ctx->rep_total;
-    const DevRecord *const *srcs = nullptr;
-    { mtr_status st = record_sources(ctx, &srcs); if (st != MTR_OK) return st; }
     const size_t nr = (size_t)std::max<int64_t>(R, 1);
     HIPCHK(ctx->d_rt_ids.ensure((size_t)id_off[n] + 16)); HIPCHK(ctx->d_rt_idoff.ensure(((size_t)n + 1) * 8));
     HIPCHK(ctx->d_rt_bytes.ensure(nr * 8)); HIPCHK(ctx->d_rt_off.ensure((nr + 1) * 8)); HIPCHK(ctx->d_rt_rows.ensure(nr * 8));
-    const int64_t *d_off = ctx->d_ch_off;
     TextArgs t{};
-    t.in = ctx->d_records; t.src_of = srcs; t.max_rec = ctx->max_rec; t.n_reads = n;
-    t.rec_off = d_off; t.chain_idx = ctx->d_ch_idx; t.chain_len = ctx->d_ch_len; t.rep_off = d_off + 2 * n + 1; t.lens = ctx->d_lens;
+    t.v = record_view(ctx); t.ch = chain_view(ctx); t.lens = ctx->d_lens;
     t.total_repeats = R; t.ids = ctx->d_rt_ids; t.id_off = ctx->d_rt_idoff;
     t.ops_len = with_alignments && R > 0 ? (const int32_t *)ctx->d_ra_len : nullptr;
     t.bytes = ctx->d_rt_bytes; t.byte_off = ctx->d_rt_off; t.rows_off = ctx->d_rt_rows;
@@ -1857,15 +1808,9 @@ extern "C" mtr_status mtr_report_text_device(mtr_ctx *ctx, const char *ids, cons
     hipLaunchKernelGGL(mtr_k_text_lines<true>, dim3((unsigned)n), dim3(64), 0, ctx->stream, t);
     HIPCHK(hipGetLastError());
     if (with_alignments && ctx->ra_columns > 0) {
-        const size_t nt = (size_t)R;
-        AlignRenderArgs a{};
-        a.b = view(ctx); a.n_repeats = (int32_t)R;
-        a.read_idx = ctx->d_ra_i32; a.rep_start = ctx->d_ra_i32 + nt; a.ops_len = ctx->d_ra_len; a.ends = ctx->d_ra_ends;
-        a.path = ctx->d_ra_ops; a.path_off = ctx->d_ra_off; a.rec_of = ctx->d_ra_rec;
-        a.work_counter = ctx->d_work;
         HIPCHK(hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned), ctx->stream));
         const unsigned waves = (unsigned)std::min<int64_t>(R, (int64_t)ctx->n_cu * 16);
-        hipLaunchKernelGGL(mtr_k_text_align, dim3(waves), dim3(64), 0, ctx->stream, a, (const int64_t *)ctx->d_rt_rows, dst->text);
+        hipLaunchKernelGGL(mtr_k_text_align, dim3(waves), dim3(64), 0, ctx->stream, render_args(ctx), (const int64_t *)ctx->d_rt_rows, dst->text);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));

@@ -1,6 +1,7 @@
 // report_align.hip.inc — mtr_report_alignments_device: mTR's -a alignments of the reported repeats, made and rendered on the device.
 //
-// The repeats are those of mtr_report_device (chain.hip.inc), repeat k here = repeat k there.  Per call after a run:
+// The repeats are those of mtr_report_device (chain.hip.inc), repeat k here = repeat k there: the kernels that walk the reads take
+// the same RecordView and ChainView.  Per call after a run:
 //   mtr_k_align_sizes    one wavefront per read: the path capacity, unit bytes and DP cells its chained repeats need (sums per read,
 //                        the largest DP of the batch by one atomic maximum per read);
 //   mtr_k_scan_offsets   one workgroup: exclusive prefix sums (per-read capacities and unit bytes; later the path lengths);
@@ -28,15 +29,13 @@ __device__ __forceinline__ void ra_task(const DevRecord *r, int L, int &rs, int 
 }
 
 // per read: read_cap[rd] / read_units[rd] = path bytes / unit bytes of its chained repeats; *max_cells = the largest DP of the batch
-__global__ void __launch_bounds__(64) mtr_k_align_sizes(const DevRecord *in, const DevRecord *const *src_of, int max_rec, int n_reads,
-                                                         const int64_t *rec_off, const int32_t *chain_idx, const int32_t *chain_len, const int32_t *lens,
+__global__ void __launch_bounds__(64) mtr_k_align_sizes(RecordView v, ChainView ch, const int32_t *lens,
                                                          int64_t *read_cap, int64_t *read_units, unsigned long long *max_cells)
 {
     const int rd = blockIdx.x, lane = threadIdx.x;
-    if (rd >= n_reads) return;
-    const int len = chain_len[rd];
-    const DevRecord *src = src_of ? src_of[rd] : in + (size_t)rd * (size_t)max_rec;
-    const int32_t *idx = chain_idx + rec_off[rd];
+    if (rd >= v.n_reads) return;
+    const auto [idx, len, k0] = ch.read(rd);
+    const DevRecord *src = v.read(rd).rec;
     const int L = lens[rd];
     int64_t cap_sum = 0, unit_sum = 0, cell_max = 0;
     for (int t = lane; t < len; t += 64) {
@@ -78,26 +77,22 @@ __global__ void __launch_bounds__(1024) mtr_k_scan_offsets(const T *in, int64_t 
     if (tid == 0) out[n] = carry;
 }
 
-// the columns of AlignArgs for the repeats of read rd (k = rep_off[rd] .. + chain_len[rd]): their paths from cap_base[rd] on, their
-// units from unit_base[rd] on.  Lane 0 of read 0 also writes the closing offsets.
+// the columns of AlignArgs for the repeats of read rd (ChainView): their paths from cap_base[rd] on, their units from unit_base[rd] on.
+// Lane 0 of read 0 also writes the closing offsets.
 struct AlignTaskDst {
     int32_t *read_idx, *rep_start, *rep_end, *gain, *mism, *indel, *unit_off;
     int64_t *ops_off; uint8_t *units; const DevRecord **rec_of;
 };
-__global__ void __launch_bounds__(64) mtr_k_align_tasks(const DevRecord *in, const DevRecord *const *src_of, int max_rec, int n_reads,
-                                                         const int64_t *rec_off, const int32_t *chain_idx, const int32_t *chain_len, const int64_t *rep_off,
-                                                         const int32_t *lens, const int64_t *cap_base, const int64_t *unit_base, int64_t total_repeats,
-                                                         AlignTaskDst o)
+__global__ void __launch_bounds__(64) mtr_k_align_tasks(RecordView v, ChainView ch, const int32_t *lens, const int64_t *cap_base, const int64_t *unit_base,
+                                                         int64_t total_repeats, AlignTaskDst o)
 {
     const int rd = blockIdx.x, lane = threadIdx.x;
-    if (rd >= n_reads) return;
-    if (rd == 0 && lane == 0) { o.ops_off[total_repeats] = cap_base[n_reads]; o.unit_off[total_repeats] = (int32_t)unit_base[n_reads]; }
-    const int len = chain_len[rd];
+    if (rd >= v.n_reads) return;
+    if (rd == 0 && lane == 0) { o.ops_off[total_repeats] = cap_base[v.n_reads]; o.unit_off[total_repeats] = (int32_t)unit_base[v.n_reads]; }
+    const auto [idx, len, k0] = ch.read(rd);
     if (len <= 0) return;
-    const DevRecord *src = src_of ? src_of[rd] : in + (size_t)rd * (size_t)max_rec;
-    const int32_t *idx = chain_idx + rec_off[rd];
+    const DevRecord *src = v.read(rd).rec;
     const int L = lens[rd];
-    const int64_t k0 = rep_off[rd];
     int64_t cbase = cap_base[rd], ubase = unit_base[rd];
     for (int c = 0; c < len; c += 64) {
         const int t = c + lane;

@@ -1,7 +1,7 @@
 // report_text.hip.inc — mtr_report_text_device: the bytes mTR writes to stdout for the resident batch, -a too, formatted on the device.
 //
 // The repeats are those of mtr_report_device (chain.hip.inc) and, with alignments, the paths mtr_report_alignments_device keeps
-// (report_align.hip.inc).  Per call:
+// (report_align.hip.inc); TextArgs carries the same RecordView and ChainView.  Per call:
 //   mtr_k_text_lines<false>  one wavefront per read, a lane per repeat: the exact byte count of each repeat's output;
 //   mtr_k_scan_offsets       (report_align.hip.inc) the repeats' byte offsets; read i's section starts at the offset of its first repeat;
 //   mtr_k_text_lines<true>   the same walk again, writing: the report line of print.c's report_line, with alignments the scores line of
@@ -140,8 +140,7 @@ __device__ __forceinline__ int64_t rt_rows_bytes(int n, int U)
 }
 
 struct TextArgs {
-    const DevRecord *in; const DevRecord *const *src_of; int max_rec, n_reads;
-    const int64_t *rec_off; const int32_t *chain_idx, *chain_len; const int64_t *rep_off; const int32_t *lens;     // the chains (mtr_k_report_pack's view)
+    RecordView v; ChainView ch; const int32_t *lens;            // the records, the chains, the reads' lengths
     int64_t total_repeats;
     const uint8_t *ids; const int64_t *id_off;                  // read i's ID = ids[id_off[i] .. id_off[i + 1])
     const int32_t *ops_len;                                     // with alignments: the columns of every repeat; else null
@@ -155,16 +154,14 @@ template <bool WRITE>
 __global__ void __launch_bounds__(64) mtr_k_text_lines(TextArgs a)
 {
     const int rd = blockIdx.x, lane = threadIdx.x;
-    if (rd >= a.n_reads) return;
-    const int64_t k0 = a.rep_off[rd];
+    if (rd >= a.v.n_reads) return;
+    const auto [idx, len, k0] = a.ch.read(rd);
     if (WRITE && a.read_off && lane == 0) {
         a.read_off[rd] = a.byte_off[k0];
-        if (rd == 0) a.read_off[a.n_reads] = a.byte_off[a.total_repeats];
+        if (rd == 0) a.read_off[a.v.n_reads] = a.byte_off[a.total_repeats];
     }
-    const int len = a.chain_len[rd];
     if (len <= 0) return;
-    const DevRecord *src = a.src_of ? a.src_of[rd] : a.in + (size_t)rd * (size_t)a.max_rec;
-    const int32_t *idx = a.chain_idx + a.rec_off[rd];
+    const DevRecord *src = a.v.read(rd).rec;
     const int L = a.lens[rd];
     const int64_t i0 = a.id_off[rd], id_len = a.id_off[rd + 1] - i0;
     for (int t = lane; t < len; t += 64) {

@@ -15,6 +15,7 @@ import pytest
 import mtr_amd
 from mtr_amd import synth
 from tests import golden_util as gu
+from tests.test_gpu_parity import CROWDED_AT, crowded_batch, slots_of
 from tests.test_run_gloo import BUNDLED, golden
 
 pytestmark = pytest.mark.gpu
@@ -43,6 +44,27 @@ def test_wire_form_carries_the_records(eng):
     # a prefix of the batch (what the host fetches after a device-side failure)
     part, pc = eng.fetch_packed(limit=57)
     assert pc.tolist() == counts[:57].tolist() and data.startswith(part)
+
+
+@pytest.mark.parametrize("where", list(CROWDED_AT))
+def test_wire_form_of_a_read_with_more_records_than_slots(eng, where):
+    """the crowded read's records are read through the pointer table (resolve_overflow), as the first, a middle and the last read"""
+    import torch
+    reads, i = crowded_batch(where)
+    want = eng.process(reads)
+    assert len(want[i]) > slots_of(reads)
+    assert eng.fetch_via_wire() == want
+    data, counts = eng.fetch_packed()
+    assert counts.tolist() == [len(r) for r in want]
+    assert len(data) == sum(56 + ((r.rep_period + 3) & ~3) + 4 * r.rep_period for per in want for r in per)
+    for k in (i, i + 1):                                         # just before the crowded read, and just behind it
+        part, pc = eng.fetch_packed(limit=k)
+        assert pc.tolist() == counts[:k].tolist() and data.startswith(part)
+        assert len(part) == sum(56 + ((r.rep_period + 3) & ~3) + 4 * r.rep_period for per in want[:k] for r in per)
+    buf = torch.zeros(len(data) + 64, dtype=torch.uint8, device="cuda")
+    c2, total, nbytes = eng.export_packed_device(buf.data_ptr(), buf.numel())
+    assert c2.tolist() == counts.tolist() and total == sum(len(r) for r in want) and nbytes == len(data)
+    assert buf[:nbytes].cpu().numpy().tobytes() == data
 
 
 def test_wire_form_on_device_memory_for_the_gather(eng):

@@ -497,15 +497,38 @@ def test_kernel_modes_golden(monkeypatch, mode):
         e.close()
 
 
-def test_more_records_than_slots(eng, oracle):
-    """A read made of many short distinct repeats reports more records than its 16 + Lmax/100 slots: the library runs
-    such reads again with room for all of them (resolve_overflow) - the reference has no limit."""
-    rng = np.random.RandomState(31)
+def _crowded(seed):
+    """a read of about 4 kb made of 70 short distinct repeats: more records than the 16 + Lmax/100 slots of a batch of such lengths"""
+    rng = np.random.RandomState(seed)
     parts = []
     for _ in range(70):
         u = rng.randint(0, 4, size=int(rng.randint(3, 9))).astype(np.uint8)
         parts.append(np.tile(u, 9)); parts.append(rng.randint(0, 4, size=6).astype(np.uint8))
-    crowded = np.concatenate(parts)
+    return np.concatenate(parts)
+
+
+CROWDED_AT = {"first": 0, "middle": 5, "last": 10}
+
+
+def crowded_batch(where):
+    """(reads, i): the eleven reads of test_more_records_than_slots with the crowded one as read i = CROWDED_AT[where].  Read 0 writes
+    the closing offsets of the report kernels and the last read closes the prefix sums, so the read that goes through the pointer
+    table is tried in both places."""
+    reads = [c for _, c in synth.make_reads("c2", 5, 77)] + [c for _, c in synth.make_reads("c2", 5, 78)]
+    i = CROWDED_AT[where]
+    reads.insert(i, _crowded(31))
+    return reads, i
+
+
+def slots_of(reads):
+    """the record slots of every read of a batch; a read that reports more was run again and is read through the pointer table"""
+    return 16 + max(len(r) for r in reads) // 100
+
+
+def test_more_records_than_slots(eng, oracle):
+    """A read made of many short distinct repeats reports more records than its 16 + Lmax/100 slots: the library runs
+    such reads again with room for all of them (resolve_overflow) - the reference has no limit."""
+    crowded = _crowded(31)
     reads = [c for _, c in synth.make_reads("c2", 5, 77)] + [crowded] + [c for _, c in synth.make_reads("c2", 5, 78)]
     got = eng.process(reads)
     want = [oracle.process(c) for c in reads]
@@ -520,12 +543,7 @@ def test_a_read_sent_back_that_also_has_more_records_than_slots(monkeypatch, ora
     about its count); when its true count is larger, resolve_overflow runs it once more with room for all of them."""
     for k, v in MODES["staged_sent_back"].items():
         monkeypatch.setenv(k, v)
-    rng = np.random.RandomState(32)
-    parts = []
-    for _ in range(70):
-        u = rng.randint(0, 4, size=int(rng.randint(3, 9))).astype(np.uint8)
-        parts.append(np.tile(u, 9)); parts.append(rng.randint(0, 4, size=6).astype(np.uint8))
-    crowded = np.concatenate(parts)
+    crowded = _crowded(32)
     reads = [c for _, c in synth.make_reads("headline2k", 20, 79)] + [crowded] + [c for _, c in synth.make_reads("c2", 10, 80)]
     e = mtr_amd.Engine()
     got = e.process(reads)

@@ -14,6 +14,7 @@ import mtr_amd
 from mtr_amd import synth
 from tests import golden_util as gu
 from tests import host_util as hu
+from tests.test_gpu_parity import _crowded
 
 torch = pytest.importorskip("torch")
 
@@ -144,15 +145,6 @@ def test_whole_batches_match_their_known_answers(eng, eng_p, cfg, n, pearson):
     rep = e.report_tensors()
     out = mtr_amd.format_report([str(i) for i in range(n)], [len(r) for r in reads], rep)
     assert (hashlib.sha256(out).hexdigest(), out.count(b"\n"), len(out)) == (known["sha256"], known["stdout_lines"], known["stdout_bytes"])
-
-
-def _crowded(seed):
-    rng = np.random.RandomState(seed)
-    parts = []
-    for _ in range(70):
-        u = rng.randint(0, 4, size=int(rng.randint(3, 9))).astype(np.uint8)
-        parts.append(np.tile(u, 9)); parts.append(rng.randint(0, 4, size=6).astype(np.uint8))
-    return np.concatenate(parts)
 
 
 def test_a_read_with_more_records_than_slots(host, eng):

@@ -15,6 +15,7 @@ import mtr_amd
 from mtr_amd import synth
 from tests import golden_util as gu
 from tests import host_util as hu
+from tests.test_gpu_parity import CROWDED_AT, crowded_batch, slots_of
 from tests.test_report_text_format import INT_MAX, INT_MIN, PINNED, fuzz_report, fuzz_rows
 
 torch = pytest.importorskip("torch")
@@ -183,6 +184,46 @@ def test_whole_batches_with_alignments_equal_format_report(eng, cfg, n):
     off = eng.report_text(ids, alignments=True).read_off.cpu().numpy()
     counts = rep.counts.numpy()
     assert off[0] == 0 and off[-1] == len(out) and (np.diff(off) > 0).tolist() == (counts > 0).tolist()
+
+
+@pytest.mark.parametrize("where", list(CROWDED_AT))
+def test_a_read_with_more_records_than_slots(eng, where):
+    """the crowded read's records are read through the pointer table (resolve_overflow), as the first, a middle and the last read"""
+    reads, i = crowded_batch(where)
+    ids = [f"read{k}" for k in range(len(reads))]
+    eng.upload(reads)
+    eng.run()
+    assert len(eng.fetch()[i]) > slots_of(reads)
+    rep = eng.report_tensors()
+    assert int(rep.counts[i]) > 0
+    lens = [len(r) for r in reads]
+    _check_text(eng, ids, reads, False, mtr_amd.format_report(ids, lens, rep))
+    _check_text(eng, ids, reads, True, mtr_amd.format_report(ids, lens, rep, alignments=eng.report_alignment_tensors()))
+
+
+def _every_answer(e, ids):
+    """what every call that reads the finished batch returns, as comparable values"""
+    texts = [e.report_text(ids, alignments=True) for _ in range(2)]
+    rep = e.report_tensors()
+    data, counts = e.fetch_packed()
+    return ([(t.text.cpu().numpy().tobytes(), t.read_off.cpu().tolist()) for t in texts],
+            [rep.counts.tolist()] + [c.cpu().numpy().tobytes() for c in rep[1:]], data, counts.tolist(), e.fetch())
+
+
+@pytest.mark.parametrize("where", list(CROWDED_AT))
+def test_the_pointer_table_is_made_once_per_run(eng, where):
+    """the table of the crowded batch is made when its run ends: every reading call after it, in any order and repeated, and the same
+    calls after the resident batch ran once more, give the same bytes (a stale or dangling table would not)"""
+    reads, i = crowded_batch(where)
+    ids = [f"read{k}" for k in range(len(reads))]
+    eng.upload(reads)
+    eng.run()
+    first = _every_answer(eng, ids)
+    assert len(first[4][i]) > slots_of(reads)
+    assert first[0][0] == first[0][1]
+    assert first[0][0][0] == mtr_amd.format_report(ids, [len(r) for r in reads], eng.report_tensors(), alignments=eng.report_alignment_tensors())
+    eng.run()
+    assert _every_answer(eng, ids) == first
 
 
 def test_formatter_fuzz(eng):

@@ -55,6 +55,12 @@ mtr_status mtr_test_report_lines(mtr_ctx *ctx, int32_t n_rows, const int32_t *fi
  * mtr_get_kernel_times is the tail kernel (mtr_k_file_tail) of that upload: launches = 0 after a host upload or with no entry. */
 mtr_status mtr_test_file_tail(mtr_ctx *ctx, uint16_t **out_tail, int64_t **out_tail_off, uint8_t **out_after);
 
+/* Environment switches for tests, read once per launch next to MTR_TEST_STAGED_CAPS and MTR_TEST_STAGED_FLAGS (read_switches, mtr_abi.hip):
+ *   MTR_TEST_WALK_SCREEN=0   the staged chain without its dead-range screen (mtr_k_walk_screen): every candidate range is an item of mtr_k_walks,
+ *                            as before the screen existed.  Records and counters do not depend on it.  (A traced run, mtr_set_trace, never screens.)
+ *   MTR_TEST_STAGED_CAPS     also takes walk=<n>: the capacity of the list of ranges the screen leaves to mtr_k_walks (overflow: the per-read kernel
+ *                            takes the batch, like any other list of the chain). */
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mtr_common.h"
+#include "walk_screen.h"
 
 #define DEVINL __device__ __forceinline__
 
@@ -34,15 +35,7 @@ DEVINL int mbcnt(unsigned long long m)
 }
 DEVINL int first_lane(unsigned long long m) { return __ffsll((long long)m) - 1; }
 
-// ---- 2-bit packed reads: base i lives in word i>>4 at bit 30-2*(i&15) (MSB first) -----------------
-DEVINL int base_at(const uint32_t *pk, int i) { return (int)((pk[i >> 4] >> (30 - 2 * (i & 15))) & 3u); }
-// value of the k-mer starting at i, first base most significant (consensus.c:46-57), k <= 15
-DEVINL int kmer_at(const uint32_t *pk, int i, int k)
-{
-    unsigned long long x = ((unsigned long long)pk[i >> 4] << 32) | (unsigned long long)pk[(i >> 4) + 1];
-    int sh = 64 - 2 * (i & 15) - 2 * k;
-    return (int)((x >> sh) & ((1ull << (2 * k)) - 1ull));
-}
+// (2-bit packed reads: base_at, kmer_at - walk_screen.h, shared with the host)
 
 DEVINL unsigned scan_max_u32(unsigned v);
 // ---- wave reductions / scans ---------------------------------------------------------------------------

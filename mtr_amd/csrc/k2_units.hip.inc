@@ -283,13 +283,7 @@ DEVINL void tab_dec(K2Ctx &c, int key)
     }
 }
 
-// node of window position i: the k-mer at i while i < min(qe, L-k+1), else the raw base code
-// (init_inputString, consensus.c:37-60; SURVEY H5)
-DEVINL int win_node(const uint32_t *pk, int L, int k, int qe, int i)
-{
-    int lim = qe < L - k + 1 ? qe : L - k + 1;
-    return i < lim ? kmer_at(pk, i, k) : base_at(pk, i);
-}
+// (node of window position i: win_node, walk_screen.h)
 
 // build the table of window [qs,qe] for k; returns the maximum frequency (consensus.c:138-146/172-196)
 DEVINL int tab_build(K2Ctx &c, int k, int qs, int qe)
@@ -1786,13 +1780,7 @@ DEVINL void emit_record(K2Ctx &c, const RR &r, int nrec)
 struct RangeP1 { int min_k, max_k, n_ent; unsigned run_mask, found_mask; unsigned long long ent[2]; };
 
 // ---- phase 1: tables, seeds and walks of every k of the range; the units found go to pool slots -----------------------
-// k range of a window (handle_one_read.c:106-118)
-DEVINL void k2_k_range(int w, int &min_k, int &max_k)
-{
-    if (w < 100) { min_k = MTRC_MIN_KMER - 3; max_k = MTRC_MAX_KMER - 5; }
-    else if (w < 1000) { min_k = MTRC_MIN_KMER - 3; max_k = MTRC_MAX_KMER - 3; }
-    else { min_k = MTRC_MIN_KMER; max_k = MTRC_MAX_KMER; }
-}
+// (k range of a window: k2_k_range, walk_screen.h)
 // [k_from, k_to] restricts the search to some of the window's k (the staged mode spreads them over work items); bound_in =
 // the smallest maximum frequency seen at smaller k (an upper bound for every larger k, below), bound_out = the same after.
 DEVINL void k2_range_walks(K2Ctx &c, int qs, int qe, int w, RangeP1 &st, int k_from = 0, int k_to = 0x7fffffff,

@@ -77,6 +77,9 @@ struct StagedArgs {
     int32_t test_flags;                                         // tests: bit 0 = mtr_k_pass_mark lists nothing (every read with a range left for pass 1 then goes back to the per-read kernel)
     int8_t *item_pass; int32_t *pass_list[2]; unsigned *n_pass[2];
     int32_t *re2;                                               // mtr_k_pass_mark: its own copy of the ranges' ends (the replay prunes in place)
+    // the dead-range screen in front of the walks (mtr_k_walk_screen): walk_screen = 1: mtr_k_walks takes its items from walk_list (indices into item_tab,
+    // *n_walk of them, at most walk_cap), the ranges the screen could not answer; 0: from item_tab / pass_list as before
+    int32_t walk_screen; int32_t *walk_list; int32_t walk_cap; unsigned *n_walk;
 };
 
 // The long work items first: the lists of the alignments, of the (range, k) searches and of the revisions are kept per COST CLASS
@@ -372,6 +375,66 @@ DEVINL void st_park_entries(K2Ctx &c, const StagedArgs &s, long long base, const
     wave_sync_mem();
 }
 
+// The screen in front of the walks.  Four ranges in five of a batch of 2 kb reads are dead: windows of ~15 bases in which no 2-mer node is seen more than
+// MIN_NUM_FREQ_UNIT times, so that k = 2 finds no seed and the frequency bound skips every larger k.  As items of mtr_k_walks each of them took a queue pull,
+// a table in LDS (clear, fence, an atomic per position, a maximum) and a wavefront to learn that; here a LANE counts a range's 16 possible nodes in two
+// registers (walk_screen.h: ws_range_dead, the same win_node as tab_build), 64 ranges per wavefront and WS_PER_LANE of them in a row per lane.  A dead range
+// gets what mtr_k_walks gave it - cand_flag = 0, one range searched, one table, one skipped table per larger k (counted from the ballots, once per wavefront
+// at the kernel's end) -, every other one (wider than 64 bases, w >= 1000, or not dead) goes to walk_list: a ballot, mbcnt, ONE reservation per wavefront and
+// round.  The order inside the list is free, as the order of mtr_k_walks' pulls is.  No LDS, no scratch: the kernel holds none of the DP kernels' slots.
+#define WS_PER_LANE 4
+__global__ __launch_bounds__(64) void mtr_k_walk_screen(K2Args a, StagedArgs s)
+{
+    const int lane = lane_id();
+    const int n_items = s.two_pass ? (int)uni((int)*s.n_pass[s.pass]) : uni(*s.n_items);
+    const int32_t *src = s.two_pass ? s.pass_list[s.pass] : nullptr;
+    int n_dead = 0, n_skipped = 0;                         // of this wavefront (uniform)
+    for (long long base = (long long)blockIdx.x * (64 * WS_PER_LANE); base < (long long)n_items; base += (long long)gridDim.x * (64 * WS_PER_LANE)) {
+        int it_l[WS_PER_LANE]; bool keep[WS_PER_LANE]; int n_keep = 0;
+        int4 rec[WS_PER_LANE]; int L_l[WS_PER_LANE]; long long woff_l[WS_PER_LANE];
+        // (the loads of the round's ranges side by side: list entry, item record, the read's length and words)
+#pragma unroll
+        for (int r = 0; r < WS_PER_LANE; r++) {
+            const long long q = base + 64 * r + lane;
+            it_l[r] = q < (long long)n_items ? (src ? src[q] : (int)q) : -1;
+        }
+#pragma unroll
+        for (int r = 0; r < WS_PER_LANE; r++) rec[r] = it_l[r] >= 0 ? s.item_tab[it_l[r]] : make_int4(0, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < WS_PER_LANE; r++) { L_l[r] = it_l[r] >= 0 ? a.b.lens[rec[r].x] : 0; woff_l[r] = it_l[r] >= 0 ? a.b.woff[rec[r].x] : 0; }
+#pragma unroll
+        for (int r = 0; r < WS_PER_LANE; r++) {
+            const int qs = rec[r].y, qe = rec[r].z, w = rec[r].w;
+            const bool have = it_l[r] >= 0;
+            bool dead = false;
+            if (have && ws_applies(qs, qe, w)) dead = ws_range_dead(a.b.packed + woff_l[r], L_l[r], qs, qe, w, nullptr);
+            if (dead) s.cand_flag[it_l[r]] = 0;
+            keep[r] = have && !dead;
+            const unsigned long long dm = __ballot(dead), d100 = __ballot(dead && w >= 100);
+            int mk_lo, mk_hi, mk0;
+            k2_k_range(0, mk0, mk_lo); k2_k_range(100, mk0, mk_hi);
+            n_dead += __popcll(dm);
+            n_skipped += (__popcll(dm) - __popcll(d100)) * (mk_lo - mk0) + __popcll(d100) * (mk_hi - mk0);       // the k behind the window's first
+            n_keep += __popcll(__ballot(keep[r]));
+        }
+        if (n_keep == 0) continue;
+        unsigned got = 0;
+        if (lane == 0) got = atomicAdd(s.n_walk, (unsigned)n_keep);
+        got = (unsigned)uni((int)got);
+        if ((long long)got + (long long)n_keep > (long long)s.walk_cap) { set_status(a.status, DEV_ERR_STAGED_OVERFLOW); break; }
+#pragma unroll
+        for (int r = 0; r < WS_PER_LANE; r++) {
+            const unsigned long long m = __ballot(keep[r]);
+            if (keep[r]) s.walk_list[got + (unsigned)mbcnt(m)] = it_l[r];
+            got += (unsigned)__popcll(m);
+        }
+    }
+    if (n_dead > 0 && lane < 3) {
+        const int which = lane == 0 ? CNT_SPARE54 : lane == 1 ? CNT_TABLES : CNT_TABLES_SKIPPED;
+        atomicAdd(&a.counters[which], (unsigned long long)(lane == 2 ? n_skipped : n_dead));
+    }
+}
+
 // One work item per candidate range: the first k of the window (s.k_first of them).  92 % of the ranges end there: the
 // frequency bound says no larger k can have a node seen more than five times.  A range that found a candidate, or whose
 // larger k may still, gets its block; every remaining k becomes a work item of mtr_k_walks_k.
@@ -388,7 +451,9 @@ __global__ __launch_bounds__(64, MTR_WAVES_PER_SIMD) void mtr_k_walks(K2Args a, 
     c.y = k2_layout(a.Lmax, a.cells_cap);
     c.lds_keys = (lds_int *)s_keys; c.seeds = (lds_int *)s_seeds; c.stage = (lds_int *)s_stage;
     c.ties = (int *)(c.sc + c.y.ties); c.fresh = c.ties + MTRC_MAX_TIEBREAKS;
-    const int n_items = s.two_pass ? (int)uni((int)*s.n_pass[s.pass]) : uni(*s.n_items);
+    if (s.walk_screen && st_staged_overflowed(a)) return;  // the screen's list is half written: the host reruns the batch
+    const int32_t *src = s.walk_screen ? s.walk_list : s.two_pass ? s.pass_list[s.pass] : nullptr;
+    const int n_items = s.walk_screen ? (int)uni((int)*s.n_walk) : s.two_pass ? (int)uni((int)*s.n_pass[s.pass]) : uni(*s.n_items);
     Wq wq; wq_init(wq, (unsigned)n_items);
     constexpr int WB = 4;                                  // items per pull: lane b fetches what item b starts with, side by side with the others'
     for (;;) {
@@ -398,7 +463,7 @@ __global__ __launch_bounds__(64, MTR_WAVES_PER_SIMD) void mtr_k_walks(K2Args a, 
         const bool have = lane < WB && myq < (long long)n_items;
         int it_l = 0, L_l = 0; int4 rec_l = make_int4(0, 0, 0, 0); long long ioff_l = 0, woff_l = 0;
         if (have) {
-            it_l = s.two_pass ? s.pass_list[s.pass][myq] : (int)myq;
+            it_l = src ? src[myq] : (int)myq;
             rec_l = s.item_tab[it_l];
             ioff_l = s.item_off[rec_l.x]; L_l = a.b.lens[rec_l.x]; woff_l = a.b.woff[rec_l.x];
         }

@@ -73,7 +73,7 @@ template <typename T> using PinnedBuf = GrowBuf<T, true>;
 // Every environment switch of the run path.  read_switches() reads them once per launch (mtr_run_resident_async) and in the entry points
 // that size scratch or run DPs of their own; MTR_DEBUG (dbg) and MTR_TEST_WRAP_DP_SIZE (mtr_create) are read where they act.
 struct RunSwitches {
-    bool staged, two_pass_set, test_caps_set;
+    bool staged, two_pass_set, test_caps_set, walk_screen;
     int two_pass, pass_shuffle, service_wpc, select_wpc, polish_wpc, rev_wpc, waves_per_cu, dp16_max_rows, test_flags;
     int32_t trace_mask; long quad_min; long long two_pass_long_min; double scratch_max_gb;
     std::string test_caps;
@@ -99,6 +99,7 @@ static void read_switches(RunSwitches &w)
     w.test_caps_set = (e = getenv("MTR_TEST_STAGED_CAPS")) != nullptr;              // tests: shrunk capacities of the chain (staged_plan), no arena retry (mtr_wait)
     w.test_caps = e ? e : "";
     w.test_flags = (e = getenv("MTR_TEST_STAGED_FLAGS")) ? atoi(e) : 0;             // tests: StagedArgs::test_flags
+    w.walk_screen = (e = getenv("MTR_TEST_WALK_SCREEN")) ? atoi(e) != 0 : true;     // tests: 0 = no dead-range screen, every range is an item of mtr_k_walks
 }
 
 // The staged chain's buffers: fixed capacities per batch (staged_plan), grow-only like the others
@@ -108,6 +109,7 @@ struct StagedBufs {
     DevBuf<DevRecord> cand; DevBuf<int32_t> flag; DevBuf<unsigned long long> scalars;
     DevBuf<int32_t> wv, res; DevBuf<int4> items, cont; DevBuf<int64_t> rev;
     DevBuf<int8_t> ipass; DevBuf<int32_t> plist0, plist1, re2;          // the chain's two passes
+    DevBuf<int32_t> wlist;                                              // the ranges the dead-range screen leaves to mtr_k_walks
 };
 
 // The chain's device scalars, each on a 256-byte line of its own (same-line atomics complete one after the other), then its work queues
@@ -117,6 +119,7 @@ struct StagedBufs {
 #define ST_LINE_CAND 5                      // n_cand
 #define ST_LINE_PASS 6                      // n_pass[0], n_pass[1]
 #define ST_LINES_KEPT 8                     // lines [0, 8) live across the two passes (items, candidates, the two pass lists); the rest starts again
+#define ST_LINE_WALK 8                      // n_walk (per pass)
 #define ST_LINE_REV 32                      // n_rev: ST_NCLS counters, a line apart
 #define ST_LINE_WORK 64                     // the work queues
 #define ST_WORK_OFFSET ((size_t)ST_LINE_WORK * ST_LINE_BYTES)
@@ -988,9 +991,9 @@ static void staged_plan(mtr_ctx *ctx, int64_t sumL, size_t free_b, StagedArgs &s
     s.cand_cap = (int32_t)std::min<int64_t>(0x7fffff00, (int64_t)n * 8 + sumL / 256 + 1024);
     // lists in 64 sub-lists with a counter each from 4 M bases (k3_staged.hip.inc: one counter completes 88 M appends a second)
     s.nsub = sumL >= (4 << 20) ? 64 : 1;
-    long test_rev_cap = -1, test_cont_cap = -1;
+    long test_rev_cap = -1, test_cont_cap = -1, test_walk_cap = -1;
     if (ctx->sw.test_caps_set) {
-        // tests only: "arena=<bytes>,kc=<n>,dp=<n>,cand=<n>,cont=<n>,rev=<n>" shrinks capacities so that every overflow path of the
+        // tests only: "arena=<bytes>,kc=<n>,dp=<n>,cand=<n>,cont=<n>,rev=<n>,walk=<n>" shrinks capacities so that every overflow path of the
         // chain is taken (the batch must then come out of the per-read kernel with the same records)
         const char *e = ctx->sw.test_caps.c_str();
         auto cap = [&](const char *key) -> long { const char *q = strstr(e, key); return q ? atol(q + strlen(key)) : -1; };
@@ -998,13 +1001,17 @@ static void staged_plan(mtr_ctx *ctx, int64_t sumL, size_t free_b, StagedArgs &s
         if (cap("kc=") >= 0) s.kc_cap = (int32_t)cap("kc=");
         if (cap("dp=") >= 0) s.dp_cap = (int32_t)cap("dp=");
         if (cap("cand=") >= 0) s.cand_cap = (int32_t)cap("cand=");
-        test_cont_cap = cap("cont="); test_rev_cap = cap("rev=");
+        test_cont_cap = cap("cont="); test_rev_cap = cap("rev="); test_walk_cap = cap("walk=");
         if (cap("nsub=") == 1 || cap("nsub=") == 64) s.nsub = (int32_t)cap("nsub=");
         s.sorted_cap = s.dp_cap + 4 * ST_QCLASSES;
     }
     s.item_cap = (int32_t)std::min<int64_t>(0x7fffff00, ctx->total_rcap);
     s.cont_cap = test_cont_cap >= 0 ? (int32_t)test_cont_cap : (int32_t)std::min<int64_t>(0x7fffff00, 2 * (int64_t)s.kc_cap);
     s.rev_cap = test_rev_cap >= 0 ? (int32_t)test_rev_cap : s.kc_cap;
+    // the dead-range screen in front of the walks (k3_staged.hip.inc: mtr_k_walk_screen); a traced run keeps every range in mtr_k_walks, where the
+    // trace's event 2 of a range without a candidate comes from
+    s.walk_screen = ctx->sw.walk_screen && ctx->trace_cap == 0;
+    s.walk_cap = test_walk_cap >= 0 ? (int32_t)test_walk_cap : s.item_cap;
     s.k_first = 3;
     s.quad_min = staged_quad_min(sumL, ctx->sw);
     // wide windows first (k3_staged.hip.inc): the chain in two passes.  MTR_TWO_PASS=0 / 1 overrides
@@ -1040,6 +1047,7 @@ static bool staged_alloc(mtr_ctx *ctx, StagedArgs &s)
         need(b.ipass, items); need(b.plist0, items * 4);
         need(b.plist1, items * 4); need(b.re2, ranges * 4);
     }
+    if (s.walk_screen) need(b.wlist, items * 4);
     if (!ok) return false;
     unsigned long long *sc = b.scalars;
     s.item_off = ctx->d_item_off; s.n_items = (int32_t *)st_line(sc, ST_LINE_ITEMS);
@@ -1054,6 +1062,7 @@ static bool staged_alloc(mtr_ctx *ctx, StagedArgs &s)
     s.work = st_line(sc, ST_LINE_WORK);
     s.item_pass = b.ipass; s.pass_list[0] = b.plist0; s.pass_list[1] = b.plist1; s.re2 = b.re2;
     s.n_pass[0] = st_line(sc, ST_LINE_PASS); s.n_pass[1] = st_line(sc, ST_LINE_PASS + 1);
+    s.walk_list = b.wlist; s.n_walk = st_line(sc, ST_LINE_WALK);
     return true;
 }
 
@@ -1089,6 +1098,10 @@ static mtr_status enqueue_staged_pass(mtr_ctx *ctx, StagedArgs &s, const K2Args 
     s.pass = pass;
     K2Args an{};
     const int ww = narrow_scratch(ctx, a, g, an);
+    if (s.walk_screen) {                                    // (a round of a wavefront is 64 * WS_PER_LANE ranges; ~0.11 ranges per base)
+        hipLaunchKernelGGL(mtr_k_walk_screen, dim3((unsigned)g.capped(ctx->n_cu * 4, 8 * 64 * WS_PER_LANE)), dim3(64), 0, ctx->stream, a, s);
+        HIPCHK(hipGetLastError());
+    }
     hipLaunchKernelGGL(mtr_k_walks, dim3((unsigned)g.capped(ww, 8)), dim3(64), 0, ctx->stream, an, s);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(mtr_k_walks_k, dim3((unsigned)g.capped(ww, 32)), dim3(64), 0, ctx->stream, an, s);

@@ -325,6 +325,37 @@ typedef struct mtr_report_text_dst {
 mtr_status mtr_report_text_device(mtr_ctx *ctx, const char *ids, const int64_t *id_off, int32_t with_alignments,
                                   const mtr_report_text_dst *dst, int64_t *out_bytes);
 
+/* ---- the motif catalogue of the report's repeats, on the device -------------------------------------------------------------------------
+ * "Which repeats are the same repeat?"  mTR prints a unit in whatever phase and strand the read had: CAG, AGC, GCA and CTG (the other
+ * strand) are one motif.  For every repeat of mtr_report_device, in its order (repeat k here is repeat k there, R the same), device kernels
+ * find the canonical motif and the strand and rotation that lead to it, and group the repeats of the resident batch by motif; no unit
+ * crosses to the host.  The reference has no such output; this is its definition:
+ *   unit u      what mtr_report_device writes for the repeat: strnlen(unit, rep_period) bytes over ACGT, 0 <= p <= 500 of them
+ *   rc(u)       the reverse complement;  rot(s, r)[i] = s[(i + r) mod p];  strings compare bytewise, so A < C < G < T
+ *   canon(u)    the smallest string among the 2p strings rot(u, r) and rot(rc(u), r);  strand = 0 if some rot(u, r) attains it (the forward
+ *               strand wins a tie), else 1;  rotation = the smallest r on that strand that attains it
+ *   motif_len   d = the smallest divisor of p with rot(canon, d) == canon;  the motif is canon[0 .. d): ACAC, CA and GT all have motif AC
+ *               (and rotation < d always);  p == 0: strand = rotation = motif_len = 0 and the empty motif
+ *   group       two repeats are in one group iff their motifs are equal as strings (compared byte for byte, never by hash alone); groups are
+ *               numbered 0 .. G-1 by the report index of their first repeat
+ *   per group   g_first = that first repeat's k;  g_repeats = its members;  g_reads = the distinct reads with a member;  g_copies = the sum
+ *               over the members of num_freq_unit * (p / d) (0 for a member with p == 0);  g_bases = the sum of their repeat_len
+ * The sums are integer sums: the catalogue of a batch does not depend on how the device scheduled the work.
+ * The columns are caller-owned DEVICE memory on the context's GPU.  Protocol as mtr_report_device: the catalogue is made on first use after
+ * a run (which makes the chains too if nobody has asked for them yet) and kept until the next upload or run, so this call and the three
+ * other report calls may come in any order and any mix; *out_repeats = R, *out_groups = G, *out_motif_bytes = M.  dst == NULL: MTR_OK with
+ * the sizes only; a capacity below its size: MTR_ERR_OVERFLOW with the sizes, nothing written; a NULL column that would be written:
+ * MTR_ERR_BAD_ARG (motif_off is always written: motif_off[G] = M, also for R == 0); else the columns are written and the context's stream
+ * synchronised before the call returns.  Before any run MTR_ERR_BAD_ARG; after a failed run the status that run latched. */
+typedef struct mtr_report_motif_dst {
+    uint8_t *strand;  int32_t *rotation, *motif_len, *group;                 /* [R] */
+    int64_t *motif_off;  uint8_t *motifs;                                    /* [G+1], [M]: group g's motif = motifs[motif_off[g] .. motif_off[g+1]) */
+    int32_t *g_first, *g_repeats, *g_reads;  int64_t *g_copies, *g_bases;    /* [G] */
+    int64_t  cap_repeats, cap_groups, cap_motif_bytes;
+} mtr_report_motif_dst;
+mtr_status mtr_report_motifs_device(mtr_ctx *ctx, const mtr_report_motif_dst *dst,
+                                    int64_t *out_repeats, int64_t *out_groups, int64_t *out_motif_bytes);
+
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left
  * of handle_one_file.c:281-287's loop across GPUs is ONE exchange: the record tables travel to the process that chains and

@@ -48,6 +48,17 @@ mtr_status mtr_test_chain(mtr_ctx *ctx, int32_t n_sets, const int64_t *set_off, 
 mtr_status mtr_test_report_lines(mtr_ctx *ctx, int32_t n_rows, const int32_t *fields, const int32_t *read_len, const uint8_t *units,
                                  const int64_t *unit_off, const char *ids, const int64_t *id_off, uint8_t **out_text, int64_t **out_off);
 
+/* The kernels of mtr_report_motifs_device on caller-given units (the counterpart of mtr_test_chain).  Unit k is units[unit_off[k] ..
+ * unit_off[k+1]) (unit_off has n + 1 entries and starts at 0), a repeat of read read[k] with num_freq_unit copies[k] and repeat_len[k].
+ * A byte outside ACGT, a unit longer than 500, a decreasing read: MTR_ERR_BAD_ARG.  table_slots sizes the grouping's table so that a small
+ * input can fill it (n = 1000 units with table_slots = 1024 walk long probe sequences).  The per-unit arrays have n entries, the per-group
+ * arrays *out_groups, motif_off one more; all are malloc'ed, free() them.  A resident batch's catalogue is made again on its next use. */
+mtr_status mtr_test_unit_motifs(mtr_ctx *ctx, int32_t n, const char *units, const int64_t *unit_off, const int32_t *read /* non-decreasing */,
+                                const int32_t *copies, const int32_t *repeat_len, int64_t table_slots /* 0: the product's choice; else a power of two > n */,
+                                /* malloc'ed, free() them: */ uint8_t **strand, int32_t **rotation, int32_t **motif_len, int32_t **group,
+                                int64_t *out_groups, int64_t **motif_off, uint8_t **motifs, int32_t **g_first, int32_t **g_repeats, int32_t **g_reads,
+                                int64_t **g_copies, int64_t **g_bases);
+
 /* What file-order mode gave the resident batch, after a host (mtr_upload_batch_in_file) or a device (mtr_upload_batch_device_in_file,
  * mtr_upload_fasta_device_in_file) upload: read i's stale entries of inputString_w_rand are (*out_tail)[(*out_tail_off)[i] ..
  * (*out_tail_off)[i + 1]) (out_tail_off has n_reads + 1 entries), its orgInputString[L], [L + 1] are (*out_after)[2i], [2i + 1].

@@ -3,7 +3,7 @@
 Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointers).  Only the device-input and report methods
 (Engine.upload_device / process_device / parse_fasta_device / upload_fasta_device / parse_fastq_device / upload_fastq_device /
 walk_fasta_device / walk_fastq_device /
-export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes) take or return torch tensors;
+export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes / report_motif_tensors) take or return torch tensors;
 they import torch when called.
 The product path is libmtr_hip.so only: importing works without a GPU, but creating an Engine
 without the library or without a HIP device raises — there is no CPU fallback.
@@ -49,7 +49,8 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_parse_fasta_device", "mtr_upload_fasta_device", "mtr_fasta_index",
            "mtr_parse_fastq_device", "mtr_upload_fastq_device", "mtr_upload_fastq_device_in_file",
            "mtr_upload_batch_device_in_file", "mtr_upload_fasta_device_in_file", "mtr_file_state_skip_device", "mtr_test_file_tail",
-           "mtr_parse_fasta_device_window", "mtr_upload_fasta_device_window", "mtr_parse_fastq_device_window", "mtr_upload_fastq_device_window"]
+           "mtr_parse_fasta_device_window", "mtr_upload_fasta_device_window", "mtr_parse_fastq_device_window", "mtr_upload_fastq_device_window",
+           "mtr_report_motifs_device", "mtr_test_unit_motifs"]
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
 
@@ -147,6 +148,30 @@ class ReportText(NamedTuple):
     """mTR's stdout for a batch (Engine.report_text): B bytes, reads in input order, both tensors on the engine's device."""
     text: "object"        # uint8 [B]
     read_off: "object"    # int64 [n_reads + 1]: read i's bytes are text[read_off[i]:read_off[i + 1]]
+
+
+class CReportMotifDst(C.Structure):
+    """mtr_report_motif_dst: device pointers of the motif catalogue's columns and their capacities"""
+    _fields_ = [("strand", C.c_void_p), ("rotation", C.c_void_p), ("motif_len", C.c_void_p), ("group", C.c_void_p),
+                ("motif_off", C.c_void_p), ("motifs", C.c_void_p),
+                ("g_first", C.c_void_p), ("g_repeats", C.c_void_p), ("g_reads", C.c_void_p), ("g_copies", C.c_void_p), ("g_bases", C.c_void_p),
+                ("cap_repeats", C.c_int64), ("cap_groups", C.c_int64), ("cap_motif_bytes", C.c_int64)]
+
+
+class ReportMotifs(NamedTuple):
+    """The motif catalogue of a Report's repeats (Engine.report_motif_tensors): the R repeats' units grouped over rotation and strand
+    into G motifs, all on the engine's device.  include/mtr_hip.h defines every column."""
+    strand: "object"      # uint8 [R]: 0 = a rotation of the unit is the canonical string, 1 = only one of its reverse complement
+    rotation: "object"    # int32 [R]: the smallest such rotation
+    motif_len: "object"   # int32 [R]: the primitive period of the unit
+    group: "object"       # int32 [R]: the repeat's group
+    motif_off: "object"   # int64 [G + 1]
+    motifs: "object"      # uint8 [M]: group g's motif is motifs[motif_off[g]:motif_off[g + 1]], ASCII
+    g_first: "object"     # int32 [G]: the group's first repeat; groups are numbered in the order of these
+    g_repeats: "object"   # int32 [G]: its members
+    g_reads: "object"     # int32 [G]: the distinct reads with a member
+    g_copies: "object"    # int64 [G]: the sum of num_freq_unit * (unit length / motif_len) over the members
+    g_bases: "object"     # int64 [G]: the sum of repeat_len over the members
 
 
 class CFastaInfo(C.Structure):
@@ -263,6 +288,11 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_report_alignments_device.restype = C.c_int
     lib.mtr_report_text_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, P(CReportTextDst), P(C.c_int64)]
     lib.mtr_report_text_device.restype = C.c_int
+    lib.mtr_report_motifs_device.argtypes = [C.c_void_p, P(CReportMotifDst), P(C.c_int64), P(C.c_int64), P(C.c_int64)]
+    lib.mtr_report_motifs_device.restype = C.c_int
+    lib.mtr_test_unit_motifs.argtypes = ([C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, P(P(C.c_uint8))] + [P(P(C.c_int32))] * 3 +
+                                         [P(C.c_int64), P(P(C.c_int64)), P(P(C.c_uint8))] + [P(P(C.c_int32))] * 3 + [P(P(C.c_int64))] * 2)
+    lib.mtr_test_unit_motifs.restype = C.c_int
     lib.mtr_parse_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaDst), P(CFastaInfo)]
     lib.mtr_parse_fasta_device.restype = C.c_int
     lib.mtr_upload_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaInfo)]
@@ -696,6 +726,60 @@ class Engine:
         """report_text(ids, alignments).text on the host: one device-to-host copy of the finished text"""
         return self.report_text(ids, alignments).text.cpu().numpy().tobytes()
 
+    def report_motif_tensors(self) -> ReportMotifs:
+        """The motif catalogue of report_tensors()' repeats (mtr_report_motifs_device), made on the device: a ReportMotifs of fresh tensors
+        on this engine's device.  Follows report_tensors' stream handling."""
+        import torch
+
+        nrep, ngrp, nmb = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self.lib.mtr_report_motifs_device(self.h, None, C.byref(nrep), C.byref(ngrp), C.byref(nmb)), "mtr_report_motifs_device")
+        R, G, M = int(nrep.value), int(ngrp.value), int(nmb.value)
+        dev = torch.device("cuda", self.device)
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)     # noqa: E731
+        i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)     # noqa: E731
+        u8 = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)      # noqa: E731
+        mot = ReportMotifs(u8(R), i32(R), i32(R), i32(R), i64(G + 1), u8(M), i32(G), i32(G), i32(G), i64(G), i64(G))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        ptr = lambda t: t.data_ptr() if t.numel() else None     # noqa: E731
+        dst = CReportMotifDst(*[ptr(t) for t in mot], R, G, M)
+        self._check(self.lib.mtr_report_motifs_device(self.h, C.byref(dst), C.byref(nrep), C.byref(ngrp), C.byref(nmb)), "mtr_report_motifs_device")
+        return mot
+
+    def test_unit_motifs(self, units, read=None, copies=None, repeat_len=None, table_slots: int = 0) -> ReportMotifs:
+        """mtr_test_unit_motifs: the kernels of report_motif_tensors on caller-given units, one bytes (or str) per unit.  read: the read of
+        each unit, non-decreasing (default: every unit a read of its own); copies: num_freq_unit (default 1); repeat_len (default: the
+        unit's length); table_slots: 0 or a power of two above len(units), the size of the grouping's table.  Returns a ReportMotifs of
+        numpy arrays."""
+        n = len(units)
+        udata, uoff = pack_ids(units, n)
+
+        def col(a, default):
+            a = np.ascontiguousarray(default if a is None else a, np.int32)
+            if a.shape != (n,):
+                raise MtrError(f"{a.shape} values for {n} units")
+            return a
+        rd = col(read, np.arange(n))
+        cp = col(copies, np.ones(n))
+        ln = col(repeat_len, np.diff(uoff))
+        p8, p32, p64 = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        strand, rotation, motif_len, group, motif_off, motifs = p8(), p32(), p32(), p32(), p64(), p8()
+        g_first, g_repeats, g_reads, g_copies, g_bases = p32(), p32(), p32(), p64(), p64()
+        ng = C.c_int64()
+        outs = [strand, rotation, motif_len, group, motif_off, motifs, g_first, g_repeats, g_reads, g_copies, g_bases]
+        self._check(self.lib.mtr_test_unit_motifs(self.h, n, udata.ctypes.data, uoff.ctypes.data, rd.ctypes.data, cp.ctypes.data, ln.ctypes.data, int(table_slots),
+                                                  C.byref(strand), C.byref(rotation), C.byref(motif_len), C.byref(group), C.byref(ng), C.byref(motif_off),
+                                                  C.byref(motifs), C.byref(g_first), C.byref(g_repeats), C.byref(g_reads), C.byref(g_copies), C.byref(g_bases)),
+                    "mtr_test_unit_motifs")
+        try:
+            G = int(ng.value)
+            take = lambda p, k: np.ctypeslib.as_array(p, shape=(max(k, 1),))[:k].copy()   # noqa: E731  (every array has room for one entry)
+            off = take(motif_off, G + 1)
+            return ReportMotifs(take(strand, n), take(rotation, n), take(motif_len, n), take(group, n), off, take(motifs, int(off[-1])),
+                                take(g_first, G), take(g_repeats, G), take(g_reads, G), take(g_copies, G), take(g_bases, G))
+        finally:
+            for p in outs:
+                _libc.free(C.cast(p, C.c_void_p))
+
     def test_report_lines(self, fields, read_len, units, ids) -> List[bytes]:
         """mtr_test_report_lines: the line function of report_text on caller-given rows - fields int32 [n, 14], read_len [n], units
         and ids one bytes (or str) per row.  Returns per row its line."""
@@ -971,6 +1055,79 @@ def format_report(ids, lens, report: Report, alignments: "ReportAlignments | Non
                 e = min(c + ALIGN_WIDTH, c1)
                 out.append(rows[0][c:e] + b"\n" + rows[1][c:e] + b"\n" + rows[2][c:e] + b"\n\n")
     return b"".join(out)
+
+
+_COMPLEMENT = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+def canonical_motif(unit):
+    """(motif, strand, rotation) of one unit (str or bytes over ACGT) as include/mtr_hip.h defines them: the least string among the
+    rotations of the unit and of its reverse complement, cut to its primitive period; strand 0 if a rotation of the unit itself is
+    that string, rotation the smallest one on that strand.  Pure Python; the motif comes back in the type the unit came in."""
+    u = unit.encode() if isinstance(unit, str) else bytes(unit)
+    p = len(u)
+    if p == 0:
+        return unit[:0], 0, 0
+    best = None
+    for strand, s in enumerate((u, u.translate(_COMPLEMENT)[::-1])):
+        d = s + s
+        r = min(range(p), key=lambda r: (d[r:r + p], r))
+        cand = (d[r:r + p], strand, r)
+        if best is None or cand[0] < best[0]:
+            best = cand
+    canon, strand, rotation = best
+    d = next(d for d in range(1, p + 1) if p % d == 0 and canon[d:] + canon[:d] == canon)
+    motif = canon[:d]
+    return (motif.decode() if isinstance(unit, str) else motif), strand, rotation
+
+
+def _motif_rows(mot: ReportMotifs):
+    """the group table of a ReportMotifs (tensors or numpy) as host rows (motif bytes, motif_len, repeats, reads, copies, bases)"""
+    def host(t):
+        return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    off, motifs = host(mot.motif_off), host(mot.motifs).tobytes()
+    cols = [host(c).tolist() for c in (mot.g_repeats, mot.g_reads, mot.g_copies, mot.g_bases)]
+    return [(motifs[int(off[g]):int(off[g + 1])], int(off[g + 1] - off[g]), *(int(c[g]) for c in cols)) for g in range(len(off) - 1)]
+
+
+def _format_motif_rows(rows) -> bytes:
+    return b"".join(b"%s\t%d\t%d\t%d\t%d\t%d\n" % r for r in rows)
+
+
+def format_motifs(mot: ReportMotifs) -> bytes:
+    """The catalogue as text: one line per group in group order, motif TAB motif_len TAB repeats TAB reads TAB copies TAB bases LF."""
+    return _format_motif_rows(_motif_rows(mot))
+
+
+class MotifCatalog:
+    """A running motif catalogue over the batches of a walk, on the host (it is small: one row per motif).  add(mot) merges the group
+    table of a batch's ReportMotifs into it, keyed by motif; the batches of a walk hold disjoint reads, so every column adds.  The
+    order is that of first appearance.
+        cat = MotifCatalog()
+        for fa in eng.walk_fasta_device(buf, w):
+            if len(fa.lens):
+                eng.run(); cat.add(eng.report_motif_tensors())"""
+
+    def __init__(self):
+        self._rows = {}                                      # motif -> [repeats, reads, copies, bases], in insertion order
+
+    def add(self, mot: ReportMotifs) -> "MotifCatalog":
+        for motif, _, *cols in _motif_rows(mot):
+            have = self._rows.setdefault(motif, [0, 0, 0, 0])
+            for c, v in enumerate(cols):
+                have[c] += v
+        return self
+
+    def rows(self):
+        """[(motif bytes, motif_len, repeats, reads, copies, bases)] in the order of first appearance"""
+        return [(m, len(m), *cols) for m, cols in self._rows.items()]
+
+    def format(self) -> bytes:
+        """rows() as format_motifs prints a batch's"""
+        return _format_motif_rows(self.rows())
+
+    def __len__(self):
+        return len(self._rows)
 
 
 def pack_read(codes: np.ndarray) -> np.ndarray:

@@ -37,6 +37,7 @@
 #include "chain.hip.inc"
 #include "report_align.hip.inc"
 #include "report_text.hip.inc"
+#include "report_motif.hip.inc"
 #include "fasta.hip.inc"
 #include "fastq.hip.inc"
 #include "file_order.hip.inc"
@@ -202,6 +203,10 @@ struct mtr_ctx {
     DevBuf<uint8_t> d_rt_ids; DevBuf<int64_t> d_rt_idoff, d_rt_bytes, d_rt_off, d_rt_rows;
     // the sizes of the last call (rt_ready; for rt_mode and the ID lengths rt_idoff): a sizes-only call followed by the writing call sizes once
     bool rt_ready = false; int32_t rt_mode = 0; int64_t rt_bytes = 0; std::vector<int64_t> rt_idoff;
+    // the motif catalogue of those repeats (mtr_report_motifs_device): made once per batch (mo_ready) - per repeat its motif values and what the
+    // grouping needs (motif_work lays the three buffers out), the table, and per group the catalogue's columns; mtr_test_unit_motifs uses them too
+    bool mo_ready = false; int64_t mo_groups = 0, mo_motif_bytes = 0;
+    DevBuf<int32_t> d_mo_i32, d_mo_g32; DevBuf<int64_t> d_mo_i64, d_mo_g64; DevBuf<uint8_t> d_mo_u8, d_mo_motifs; DevBuf<unsigned> d_mo_table;
     // a FASTA file in device memory (fasta.hip.inc), per call: the tiles' columns, the header windows' columns, the IDs' offsets, the stop, the sizes
     DevBuf<uint32_t> d_fa_tiles, d_fa_hbase; DevBuf<int32_t> d_fa_hpos, d_fa_hidlen; DevBuf<int64_t> d_fa_idoff;
     DevBuf<unsigned long long> d_fa_event; DevBuf<mtr_fasta_info> d_fa_info;
@@ -282,7 +287,7 @@ static hipError_t copy_sync(mtr_ctx *ctx, void *dst, const void *src, size_t byt
 }
 
 // forget the resident batch (its buffers stay allocated for the next one)
-static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
+static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->mo_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
 
 extern "C" int mtr_abi_version(void) { return MTR_ABI_VERSION; }
 
@@ -1308,7 +1313,7 @@ extern "C" mtr_status mtr_run_resident_async(mtr_ctx *ctx)
     if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
     HIPCHK(hipSetDevice(ctx->device));
     { mtr_status w = mtr_wait(ctx); if (w != MTR_OK && ctx->pending) return w; }
-    ctx->run_status = MTR_OK; ctx->ran = false; ctx->first_failed = -1; ctx->ovf_reads.clear(); ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false;
+    ctx->run_status = MTR_OK; ctx->ran = false; ctx->first_failed = -1; ctx->ovf_reads.clear(); ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->mo_ready = false;
     read_switches(ctx->sw);
     { mtr_status r = reset_run_state(ctx); if (r != MTR_OK) return r; }
     // [measured, round 3] the chain is the faster arrangement for every batch: a single 2 kb read 3.0 against 19 ms, 2 000 reads 19
@@ -1830,6 +1835,128 @@ extern "C" mtr_status mtr_report_text_device(mtr_ctx *ctx, const char *ids, cons
     return MTR_OK;
 }
 
+// ---- the motif catalogue of the report's repeats (report_motif.hip.inc) -----------------------------------------------------------
+// Only the number of groups and of motif bytes come to the host.
+// The rows' working arrays in three buffers of the context: d_mo_i32 = rotation | motif_len | read | bases | slot_of | leader | first | lead_len | group,
+// d_mo_i64 = hash | copies | unit_off (n + 1) | group_of (n + 1) | len_off (n + 1), d_mo_u8 = strand | the motifs' bytes in the units' layout
+struct MotifWork { MotifRows rows; unsigned *slot_of; int32_t *leader, *first, *lead_len, *group; int64_t *group_of, *len_off; };
+static mtr_status motif_work(mtr_ctx *ctx, int64_t n, int64_t unit_bytes, MotifWork &w)
+{
+    const size_t nr = (size_t)n;
+    HIPCHK(ctx->d_mo_i32.ensure((9 * nr + 1) * 4)); HIPCHK(ctx->d_mo_i64.ensure((5 * nr + 3) * 8)); HIPCHK(ctx->d_mo_u8.ensure(nr + (size_t)unit_bytes + 16));
+    int32_t *i = ctx->d_mo_i32; int64_t *l = ctx->d_mo_i64; uint8_t *b = ctx->d_mo_u8;
+    w.rows.rotation = i; w.rows.motif_len = i + nr; w.rows.read = i + 2 * nr; w.rows.bases = i + 3 * nr;
+    w.slot_of = (unsigned *)(i + 4 * nr); w.leader = i + 5 * nr; w.first = i + 6 * nr; w.lead_len = i + 7 * nr; w.group = i + 8 * nr;
+    w.rows.hash = (unsigned long long *)l; w.rows.copies = l + nr; w.rows.unit_off = l + 2 * nr; w.group_of = l + 3 * nr + 1; w.len_off = l + 4 * nr + 2;
+    w.rows.strand = b; w.rows.motif = b + nr;
+    return MTR_OK;
+}
+// the columns per group in d_mo_g32 = first | repeats | reads, d_mo_g64 = motif_off (G + 1) | copies | bases, and d_mo_motifs
+static MotifGroups motif_groups(const mtr_ctx *ctx, const MotifWork &w)
+{
+    const size_t G = (size_t)ctx->mo_groups;
+    int32_t *i = ctx->d_mo_g32; int64_t *l = ctx->d_mo_g64;
+    return { w.group, l, ctx->d_mo_motifs, i, i + G, i + 2 * G, l + G + 1, l + 2 * G + 1 };
+}
+// The rows are in place (mtr_k_unit_motif or mtr_k_unit_motif_rows is enqueued): group them.  table_slots: 0 = twice the rows, rounded up to a
+// power of two; else the caller's power of two above n (mtr_test_unit_motifs).  Leaves mo_groups / mo_motif_bytes and the stream synchronised.
+static mtr_status motif_group(mtr_ctx *ctx, int64_t n, int64_t table_slots, const MotifWork &w)
+{
+    ctx->mo_groups = 0; ctx->mo_motif_bytes = 0;
+    if (n == 0) {
+        HIPCHK(ctx->d_mo_g64.ensure(8));
+        HIPCHK(hipMemsetAsync(ctx->d_mo_g64, 0, 8, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return MTR_OK;
+    }
+    int64_t slots = table_slots;
+    if (slots == 0) for (slots = 64; slots < 2 * n; slots <<= 1) { }
+    HIPCHK(ctx->d_mo_table.ensure((size_t)slots * 4));
+    HIPCHK(hipMemsetAsync(ctx->d_mo_table, 0xff, (size_t)slots * 4, ctx->stream));
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(mtr_k_motif_insert, dim3(blocks), dim3(256), 0, ctx->stream, (int32_t)n, w.rows, (unsigned *)ctx->d_mo_table, (unsigned)(slots - 1), w.slot_of);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(mtr_k_motif_leader, dim3(blocks), dim3(256), 0, ctx->stream, (int32_t)n, (const int32_t *)w.rows.motif_len, (const unsigned *)ctx->d_mo_table,
+                       (const unsigned *)w.slot_of, w.leader, w.first, w.lead_len);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)w.first, n, w.group_of);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)w.lead_len, n, w.len_off);
+    HIPCHK(hipGetLastError());
+    int64_t G = 0, M = 0;
+    HIPCHK(hipMemcpyAsync(&G, w.group_of + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&M, w.len_off + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (G < 1 || G > n || M < 0) { ctx->err = "the motif table is inconsistent"; return MTR_ERR_HIP; }
+    ctx->mo_groups = G; ctx->mo_motif_bytes = M;
+    const size_t g = (size_t)G;
+    HIPCHK(ctx->d_mo_g32.ensure(3 * g * 4)); HIPCHK(ctx->d_mo_g64.ensure((3 * g + 1) * 8)); HIPCHK(ctx->d_mo_motifs.ensure((size_t)M + 16));
+    const MotifGroups mg = motif_groups(ctx, w);
+    HIPCHK(hipMemsetAsync(mg.repeats, 0, 2 * g * 4, ctx->stream));             // repeats | reads
+    HIPCHK(hipMemsetAsync(mg.copies, 0, 2 * g * 8, ctx->stream));              // copies | bases
+    hipLaunchKernelGGL(mtr_k_motif_groups, dim3(blocks), dim3(256), 0, ctx->stream, (int32_t)n, w.rows, (const int32_t *)w.leader, (const int64_t *)w.group_of,
+                       (const int64_t *)w.len_off, mg);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+static mtr_status report_motifs(mtr_ctx *ctx)
+{
+    if (ctx->mo_ready) return MTR_OK;
+    { mtr_status st = report_chains(ctx); if (st != MTR_OK) return st; }
+    const int64_t R = ctx->rep_total;
+    if (R > (int64_t)INT32_MAX / 2) { ctx->err = "more reported repeats than the motif table takes"; return MTR_ERR_OVERFLOW; }
+    MotifWork w{};
+    { mtr_status st = motif_work(ctx, R, ctx->rep_unit_bytes, w); if (st != MTR_OK) return st; }
+    if (R > 0) {
+        const int n = ctx->n_reads;
+        hipLaunchKernelGGL(mtr_k_unit_motif, dim3((unsigned)n), dim3(64), 0, ctx->stream, record_view(ctx), chain_view(ctx),
+                           (const int64_t *)chain_offsets(ctx->d_ch_off, n).unit_base, R, ctx->rep_unit_bytes, w.rows);
+        HIPCHK(hipGetLastError());
+    }
+    { mtr_status st = motif_group(ctx, R, 0, w); if (st != MTR_OK) return st; }
+    ctx->mo_ready = true;
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_report_motifs_device(mtr_ctx *ctx, const mtr_report_motif_dst *dst, int64_t *out_repeats, int64_t *out_groups, int64_t *out_motif_bytes)
+{
+    if (!ctx || !out_repeats || !out_groups || !out_motif_bytes) return MTR_ERR_BAD_ARG;
+    { mtr_status r = results_ready(ctx, false); if (r != MTR_OK) return r; }
+    HIPCHK(hipSetDevice(ctx->device));
+    { mtr_status st = report_motifs(ctx); if (st != MTR_OK) return st; }
+    const int64_t R = ctx->rep_total, G = ctx->mo_groups, M = ctx->mo_motif_bytes;
+    *out_repeats = R; *out_groups = G; *out_motif_bytes = M;
+    if (!dst) return MTR_OK;
+    if (dst->cap_repeats < R || dst->cap_groups < G || dst->cap_motif_bytes < M) {
+        ctx->err = "destination holds " + std::to_string(dst->cap_repeats) + " repeats / " + std::to_string(dst->cap_groups) + " groups / " +
+                   std::to_string(dst->cap_motif_bytes) + " motif bytes, " + std::to_string(R) + " / " + std::to_string(G) + " / " + std::to_string(M) + " needed";
+        return MTR_ERR_OVERFLOW;
+    }
+    if (!dst->motif_off || (R > 0 && (!dst->strand || !dst->rotation || !dst->motif_len || !dst->group)) || (M > 0 && !dst->motifs) ||
+        (G > 0 && (!dst->g_first || !dst->g_repeats || !dst->g_reads || !dst->g_copies || !dst->g_bases))) {
+        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
+    }
+    MotifWork w{};
+    { mtr_status st = motif_work(ctx, R, ctx->rep_unit_bytes, w); if (st != MTR_OK) return st; }      // (the buffers are there: the layout alone)
+    const MotifGroups mg = motif_groups(ctx, w);
+    const size_t r = (size_t)R, g = (size_t)G;
+    const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
+    HIPCHK(hipMemcpyAsync(dst->motif_off, mg.motif_off, (g + 1) * 8, dd, ctx->stream));
+    if (R > 0) {
+        HIPCHK(hipMemcpyAsync(dst->strand, w.rows.strand, r, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->rotation, w.rows.rotation, r * 4, dd, ctx->stream));
+        HIPCHK(hipMemcpyAsync(dst->motif_len, w.rows.motif_len, r * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->group, mg.group, r * 4, dd, ctx->stream));
+    }
+    if (M > 0) HIPCHK(hipMemcpyAsync(dst->motifs, mg.motifs, (size_t)M, dd, ctx->stream));
+    if (G > 0) {
+        HIPCHK(hipMemcpyAsync(dst->g_first, mg.first, g * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->g_repeats, mg.repeats, g * 4, dd, ctx->stream));
+        HIPCHK(hipMemcpyAsync(dst->g_reads, mg.reads, g * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->g_copies, mg.copies, g * 8, dd, ctx->stream));
+        HIPCHK(hipMemcpyAsync(dst->g_bases, mg.bases, g * 8, dd, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
 // ---- a FASTA file in device memory (fasta.hip.inc) -----------------------------------------------------------------------------
 // Only the header count, the sizes and - for an upload - the reads' lengths, offsets and IDs come back to the host.
 // fastq: the file is FASTQ (fastq.hip.inc) and q holds its columns; the entry points share everything but the kernels
@@ -2180,6 +2307,68 @@ extern "C" mtr_status mtr_test_chain(mtr_ctx *ctx, int32_t n_sets, const int64_t
         if (t > 0) HIPCHK(copy_sync(ctx, idx.get(), d_out, t * 4, hipMemcpyDeviceToHost));
     }
     *out_len = len.release(); *out_idx = idx.release();
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_test_unit_motifs(mtr_ctx *ctx, int32_t n, const char *units, const int64_t *unit_off, const int32_t *read, const int32_t *copies,
+                                           const int32_t *repeat_len, int64_t table_slots, uint8_t **strand, int32_t **rotation, int32_t **motif_len, int32_t **group,
+                                           int64_t *out_groups, int64_t **motif_off, uint8_t **motifs, int32_t **g_first, int32_t **g_repeats, int32_t **g_reads,
+                                           int64_t **g_copies, int64_t **g_bases)
+{
+    if (!ctx || n < 0 || !unit_off || !strand || !rotation || !motif_len || !group || !out_groups || !motif_off || !motifs || !g_first || !g_repeats || !g_reads ||
+        !g_copies || !g_bases) return MTR_ERR_BAD_ARG;
+    if (n > 0 && (!read || !copies || !repeat_len)) return MTR_ERR_BAD_ARG;
+    if (n > INT32_MAX / 2) { ctx->err = "too many units"; return MTR_ERR_BAD_ARG; }
+    if (unit_off[0] != 0) { ctx->err = "unit_off[0] must be 0"; return MTR_ERR_BAD_ARG; }
+    if (table_slots != 0 && (table_slots <= n || table_slots > ((int64_t)1 << 31) || (table_slots & (table_slots - 1)) != 0)) {
+        ctx->err = "table_slots must be 0 or a power of two above the number of units"; return MTR_ERR_BAD_ARG;
+    }
+    for (int k = 0; k < n; k++) {
+        if (unit_off[k + 1] < unit_off[k] || unit_off[k + 1] - unit_off[k] > MTR_MAX_PERIOD) { ctx->err = "unit " + std::to_string(k) + ": length outside 0..500"; return MTR_ERR_BAD_ARG; }
+        if (k > 0 && read[k] < read[k - 1]) { ctx->err = "read decreases at unit " + std::to_string(k); return MTR_ERR_BAD_ARG; }
+    }
+    const size_t nr = (size_t)n, ub = (size_t)unit_off[nr];
+    if (ub > 0 && !units) return MTR_ERR_BAD_ARG;
+    for (size_t b = 0; b < ub; b++)
+        if (units[b] != 'A' && units[b] != 'C' && units[b] != 'G' && units[b] != 'T') { ctx->err = "byte " + std::to_string(b) + " of the units is none of ACGT"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->mo_ready = false;                                        // the catalogue's buffers are used: a resident batch makes its own again
+    MotifWork w{};
+    { mtr_status st = motif_work(ctx, n, (int64_t)ub, w); if (st != MTR_OK) return st; }
+    if (n > 0) {
+        // d_t_units: units;  d_t_i64: unit_off;  d_t_i32: read | copies | repeat_len
+        HIPCHK(ctx->d_t_units.ensure(ub + 16)); HIPCHK(ctx->d_t_i64.ensure((nr + 1) * 8)); HIPCHK(ctx->d_t_i32.ensure(3 * nr * 4));
+        int32_t *d_in = ctx->d_t_i32;
+        if (ub > 0) HIPCHK(copy_sync(ctx, ctx->d_t_units, units, ub, hipMemcpyHostToDevice));
+        HIPCHK(copy_sync(ctx, ctx->d_t_i64, unit_off, (nr + 1) * 8, hipMemcpyHostToDevice));
+        HIPCHK(copy_sync(ctx, d_in, read, nr * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_in + nr, copies, nr * 4, hipMemcpyHostToDevice));
+        HIPCHK(copy_sync(ctx, d_in + 2 * nr, repeat_len, nr * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(mtr_k_unit_motif_rows, dim3((unsigned)((nr + MOTIF_TILE - 1) / MOTIF_TILE)), dim3(64), 0, ctx->stream, n, (const uint8_t *)ctx->d_t_units,
+                           (const int64_t *)ctx->d_t_i64, (const int32_t *)d_in, (const int32_t *)(d_in + nr), (const int32_t *)(d_in + 2 * nr), w.rows);
+        HIPCHK(hipGetLastError());
+    }
+    { mtr_status st = motif_group(ctx, n, table_slots, w); if (st != MTR_OK) return st; }
+    const size_t g = (size_t)ctx->mo_groups, mb = (size_t)ctx->mo_motif_bytes, n1 = std::max<size_t>(nr, 1), g1 = std::max<size_t>(g, 1);
+    const MotifGroups mg = motif_groups(ctx, w);
+    HostArray<uint8_t> h_strand = host_array<uint8_t>(n1), h_motifs = host_array<uint8_t>(std::max<size_t>(mb, 1));
+    HostArray<int32_t> h_rot = host_array<int32_t>(n1), h_len = host_array<int32_t>(n1), h_group = host_array<int32_t>(n1);
+    HostArray<int32_t> h_first = host_array<int32_t>(g1), h_repeats = host_array<int32_t>(g1), h_reads = host_array<int32_t>(g1);
+    HostArray<int64_t> h_off = host_array<int64_t>(g + 1), h_copies = host_array<int64_t>(g1), h_bases = host_array<int64_t>(g1);
+    if (!h_strand || !h_motifs || !h_rot || !h_len || !h_group || !h_first || !h_repeats || !h_reads || !h_off || !h_copies || !h_bases) return MTR_ERR_OOM;
+    const hipMemcpyKind dh = hipMemcpyDeviceToHost;
+    HIPCHK(copy_sync(ctx, h_off.get(), mg.motif_off, (g + 1) * 8, dh));
+    if (n > 0) {
+        HIPCHK(copy_sync(ctx, h_strand.get(), w.rows.strand, nr, dh)); HIPCHK(copy_sync(ctx, h_rot.get(), w.rows.rotation, nr * 4, dh));
+        HIPCHK(copy_sync(ctx, h_len.get(), w.rows.motif_len, nr * 4, dh)); HIPCHK(copy_sync(ctx, h_group.get(), mg.group, nr * 4, dh));
+        HIPCHK(copy_sync(ctx, h_first.get(), mg.first, g * 4, dh)); HIPCHK(copy_sync(ctx, h_repeats.get(), mg.repeats, g * 4, dh));
+        HIPCHK(copy_sync(ctx, h_reads.get(), mg.reads, g * 4, dh)); HIPCHK(copy_sync(ctx, h_copies.get(), mg.copies, g * 8, dh));
+        HIPCHK(copy_sync(ctx, h_bases.get(), mg.bases, g * 8, dh));
+        if (mb > 0) HIPCHK(copy_sync(ctx, h_motifs.get(), mg.motifs, mb, dh));
+    }
+    *out_groups = (int64_t)g;
+    *strand = h_strand.release(); *rotation = h_rot.release(); *motif_len = h_len.release(); *group = h_group.release();
+    *motif_off = h_off.release(); *motifs = h_motifs.release(); *g_first = h_first.release(); *g_repeats = h_repeats.release(); *g_reads = h_reads.release();
+    *g_copies = h_copies.release(); *g_bases = h_bases.release();
     return MTR_OK;
 }
 

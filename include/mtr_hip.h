@@ -356,6 +356,50 @@ typedef struct mtr_report_motif_dst {
 mtr_status mtr_report_motifs_device(mtr_ctx *ctx, const mtr_report_motif_dst *dst,
                                     int64_t *out_repeats, int64_t *out_groups, int64_t *out_motif_bytes);
 
+/* ---- known-motif search: given motifs aligned to every read, on the device ----------------------------------------------------------------
+ * "I know the motif (CAG, GGGGCC, a 33-base VNTR unit): where is it in every read, and with how many copies?"  The report answers for the units
+ * the search infers; this call aligns the caller's motifs to every read of the resident batch by the wrap-around DP itself and returns one hit
+ * per (read, motif).  It needs an uploaded batch and no run: it may come before or after one (a run in flight ends first), it reads the reads
+ * alone - no after-base, so file-order mode does not change a hit - and the records, chains, kept reports and motif catalogue of the batch stay
+ * as they are.  This is its definition, in clean coordinates:
+ *   read x[0 .. L), motif m[0 .. U) over ACGT with 1 <= U <= 499, scores G (gain), MM (mismatch), D (indel)
+ *   a hit       the result of the reference's wrap_around_DP_sub (wrap_around_DP.c:222-354) with DP row i (1 .. L) standing for read base x[i - 1]:
+ *               every base of the read is aligned and nothing past its end is read (the reference's own callers read org[query_start + i]; this
+ *               entry does not copy that off-by-one)
+ *   recurrence  (:258-285) H(0, j) = 0;  a match gives H(i, j) = H(i-1, j-1) + G;  otherwise H(i, j) = max(0, H(i-1, j-1) - MM, H(i-1, j) - D,
+ *               H(i, j-1) - D), without the last term in column 1;  the wrap is H(i, 0) = H(i, U)
+ *   best cell   the first strict maximum in row-major order (max_i, max_j)
+ *   traceback   (:298-333) from the best cell while i > 0 and H > 0, in the fixed priority order match, mismatch, deletion (j - 1, from column 1 to
+ *               column U of the same row), insertion (i - 1)
+ *   columns     start = 0-origin index of the first aligned base = the traceback's final i;  end = 0-origin, inclusive = max_i - 1;
+ *               repeat_len = end - start + 1;  copies = (matches + mismatches + deletions) / U;  matches, mismatches, insertions, deletions;
+ *               score = the best cell's value (= G * matches - MM * mismatches - D * (insertions + deletions));
+ *               ratio = (float)matches / repeat_len, 0 when repeat_len == 0
+ *   no hit      a read with no positive cell: start = 0, end = -1 and zeros everywhere else
+ *   strands     both_strands != 0: the reverse complement of the motif is aligned as well, the hit is the alignment with the higher score, the forward
+ *               motif wins a tie; strand = 0 or 1 says which won (a palindromic motif such as AT is always strand 0).  both_strands == 0: strand = 0
+ *   as given    the motif is not reduced to a primitive period and not rotated: ACAC counts copies of four bases
+ * This equals the oracle's wrap_around_DP_sub on the read shifted by one base (window 0 .. L - 1 of [any base] + x) with rep_start and rep_end each
+ * lowered by one.
+ * motifs / motif_off are HOST arrays, as ids / id_off of mtr_report_text_device: motif k is motifs[motif_off[k] .. motif_off[k + 1]), upper-case ACGT.
+ * The columns are caller-owned DEVICE memory on the context's GPU; hit h = read * n_motifs + motif, H = n_reads * n_motifs of them.
+ * Checked in this order: MTR_ERR_BAD_ARG (mtr_last_error names the offender) without an uploaded batch, for n_motifs <= 0, gain outside 1..5, mismatch
+ * or indel outside 1..3 (the ranges the forward passes are written and tested for), a decreasing motif_off, a motif of length 0 or over 499, a byte
+ * outside ACGT, more than 2^30 - 1 motifs or motif bases, H over 2^31 - 1;  MTR_ERR_DP_TOO_LARGE, decided on the host before any launch, if for any (read, motif) (U + 1) * L + U reaches the
+ * WrapDPsize the kernels use (the message names the read and the motif);  then *out_hits = H and, as the report calls: dst == NULL: MTR_OK with the
+ * size only;  cap_hits < H: MTR_ERR_OVERFLOW, nothing written;  a NULL column: MTR_ERR_BAD_ARG;  else the columns are written and the context's
+ * stream synchronised before the call returns. */
+typedef struct mtr_motif_hits_dst {
+    int32_t *fields;   /* [H*8] start, end, repeat_len, copies, matches, mismatches, insertions, deletions */
+    int32_t *score;    /* [H] */
+    float   *ratio;    /* [H] */
+    uint8_t *strand;   /* [H] */
+    int64_t  cap_hits;
+} mtr_motif_hits_dst;   /* caller-owned DEVICE memory; hit h = read * n_motifs + motif */
+mtr_status mtr_search_motifs_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs,
+                                    int32_t gain, int32_t mismatch, int32_t indel, int32_t both_strands,
+                                    const mtr_motif_hits_dst *dst, int64_t *out_hits);
+
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left
  * of handle_one_file.c:281-287's loop across GPUs is ONE exchange: the record tables travel to the process that chains and

@@ -70,7 +70,11 @@ mtr_status mtr_test_file_tail(mtr_ctx *ctx, uint16_t **out_tail, int64_t **out_t
  *   MTR_TEST_WALK_SCREEN=0   the staged chain without its dead-range screen (mtr_k_walk_screen): every candidate range is an item of mtr_k_walks,
  *                            as before the screen existed.  Records and counters do not depend on it.  (A traced run, mtr_set_trace, never screens.)
  *   MTR_TEST_STAGED_CAPS     also takes walk=<n>: the capacity of the list of ranges the screen leaves to mtr_k_walks (overflow: the per-read kernel
- *                            takes the batch, like any other list of the chain). */
+ *                            takes the batch, like any other list of the chain).
+ *   MTR_TEST_MOTIF_LANE_MAX=<u>   mtr_search_motifs_device, read per call: the longest motif its lane path (one DP per lane, mtr_k_motif_lanes) takes,
+ *                            0 .. 32; 0 sends every alignment through the wave path (mtr_k_motif_waves, one DP per wavefront).  The hits do not depend on it.
+ *   MTR_TEST_MOTIF_LANE_ROWS=<n>  the longest read the lane path takes (at most its built-in bound of 16384 rows); longer reads take the wave path,
+ *                            reads either side of the bound come from different kernels in one call.  The hits do not depend on it. */
 
 #ifdef __cplusplus
 }

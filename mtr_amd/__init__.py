@@ -3,7 +3,7 @@
 Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointers).  Only the device-input and report methods
 (Engine.upload_device / process_device / parse_fasta_device / upload_fasta_device / parse_fastq_device / upload_fastq_device /
 walk_fasta_device / walk_fastq_device /
-export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes / report_motif_tensors) take or return torch tensors;
+export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes / report_motif_tensors / search_motifs) take or return torch tensors;
 they import torch when called.
 The product path is libmtr_hip.so only: importing works without a GPU, but creating an Engine
 without the library or without a HIP device raises — there is no CPU fallback.
@@ -50,7 +50,7 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_parse_fastq_device", "mtr_upload_fastq_device", "mtr_upload_fastq_device_in_file",
            "mtr_upload_batch_device_in_file", "mtr_upload_fasta_device_in_file", "mtr_file_state_skip_device", "mtr_test_file_tail",
            "mtr_parse_fasta_device_window", "mtr_upload_fasta_device_window", "mtr_parse_fastq_device_window", "mtr_upload_fastq_device_window",
-           "mtr_report_motifs_device", "mtr_test_unit_motifs"]
+           "mtr_report_motifs_device", "mtr_test_unit_motifs", "mtr_search_motifs_device"]
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
 
@@ -174,6 +174,20 @@ class ReportMotifs(NamedTuple):
     g_bases: "object"     # int64 [G]: the sum of repeat_len over the members
 
 
+class CMotifHitsDst(C.Structure):
+    """mtr_motif_hits_dst: device pointers of the known-motif search's columns and their capacity"""
+    _fields_ = [("fields", C.c_void_p), ("score", C.c_void_p), ("ratio", C.c_void_p), ("strand", C.c_void_p), ("cap_hits", C.c_int64)]
+
+
+class MotifHits(NamedTuple):
+    """What Engine.search_motifs found: one hit per (read, motif) of n reads and m motifs, all on the engine's device.  include/mtr_hip.h
+    defines every column."""
+    fields: "object"      # int32 [n, m, 8]: start, end (0-origin, inclusive), repeat_len, copies, matches, mismatches, insertions, deletions
+    score: "object"       # int32 [n, m]: the best cell's value; 0 = the motif is nowhere in the read (start 0, end -1)
+    ratio: "object"       # float32 [n, m]: matches / repeat_len
+    strand: "object"      # uint8 [n, m]: 0 = the motif as given, 1 = its reverse complement aligned better
+
+
 class CFastaInfo(C.Structure):
     """mtr_fasta_info: what a FASTA file in device memory holds"""
     _fields_ = [("n_reads", C.c_int32), ("end", C.c_int32), ("bad_char", C.c_int32), ("reserved", C.c_int32),
@@ -293,6 +307,8 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_test_unit_motifs.argtypes = ([C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, P(P(C.c_uint8))] + [P(P(C.c_int32))] * 3 +
                                          [P(C.c_int64), P(P(C.c_int64)), P(P(C.c_uint8))] + [P(P(C.c_int32))] * 3 + [P(P(C.c_int64))] * 2)
     lib.mtr_test_unit_motifs.restype = C.c_int
+    lib.mtr_search_motifs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [P(CMotifHitsDst), P(C.c_int64)]
+    lib.mtr_search_motifs_device.restype = C.c_int
     lib.mtr_parse_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaDst), P(CFastaInfo)]
     lib.mtr_parse_fasta_device.restype = C.c_int
     lib.mtr_upload_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaInfo)]
@@ -745,6 +761,30 @@ class Engine:
         self._check(self.lib.mtr_report_motifs_device(self.h, C.byref(dst), C.byref(nrep), C.byref(ngrp), C.byref(nmb)), "mtr_report_motifs_device")
         return mot
 
+    def search_motifs(self, motifs, gain: int = 1, mismatch: int = 1, indel: int = 1, both_strands: bool = True) -> MotifHits:
+        """Known-motif search (mtr_search_motifs_device): every motif - a sequence of str or bytes over upper-case ACGT, 1..499 bases each -
+        aligned to every read of the uploaded batch by the wrap-around DP with the given scores, on both strands unless both_strands is false.
+        Needs no run and changes nothing a run left.  Returns a MotifHits of fresh tensors on this engine's device; follows report_tensors'
+        stream handling."""
+        import torch
+
+        if isinstance(motifs, (str, bytes, bytearray)) or not hasattr(motifs, "__len__"):
+            raise MtrError(f"motifs must be a sequence of str or bytes, got {type(motifs).__name__}")
+        data, off = pack_ids(motifs)
+        m = len(motifs)
+        args = (self.h, data.ctypes.data, off.ctypes.data, m, int(gain), int(mismatch), int(indel), 1 if both_strands else 0)
+        nh = C.c_int64()
+        self._check(self.lib.mtr_search_motifs_device(*args, None, C.byref(nh)), "mtr_search_motifs_device")
+        H = int(nh.value)
+        n = H // m
+        dev = torch.device("cuda", self.device)
+        hits = MotifHits(torch.empty((n, m, 8), dtype=torch.int32, device=dev), torch.empty((n, m), dtype=torch.int32, device=dev),
+                         torch.empty((n, m), dtype=torch.float32, device=dev), torch.empty((n, m), dtype=torch.uint8, device=dev))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CMotifHitsDst(*[t.data_ptr() for t in hits], H)
+        self._check(self.lib.mtr_search_motifs_device(*args, C.byref(dst), C.byref(nh)), "mtr_search_motifs_device")
+        return hits
+
     def test_unit_motifs(self, units, read=None, copies=None, repeat_len=None, table_slots: int = 0) -> ReportMotifs:
         """mtr_test_unit_motifs: the kernels of report_motif_tensors on caller-given units, one bytes (or str) per unit.  read: the read of
         each unit, non-decreasing (default: every unit a read of its own); copies: num_freq_unit (default 1); repeat_len (default: the
@@ -1079,6 +1119,32 @@ def canonical_motif(unit):
     d = next(d for d in range(1, p + 1) if p % d == 0 and canon[d:] + canon[:d] == canon)
     motif = canon[:d]
     return (motif.decode() if isinstance(unit, str) else motif), strand, rotation
+
+
+def format_motif_hits(ids, lens, motifs, hits: MotifHits, min_ratio: float = 0.0, min_copies: int = 1) -> bytes:
+    """The hits of Engine.search_motifs as text, one line per kept hit in the thirteen columns of mTR's report line (format_report), so that
+    what parses the report parses this: ID, L, start+1, end+1, repeat_len, U, copies, matches, ratio (%f of the float), mismatches,
+    insertions, deletions, and the motif as aligned - its reverse complement for strand 1.  Reads in input order, motifs in the given order
+    within a read.  Kept: score > 0 (always), ratio >= min_ratio and copies >= min_copies.
+    ids, lens: per read its ID (str or bytes) and length; motifs: what search_motifs was given; hits: its result (tensors or numpy)."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    bmot = [v.encode() if isinstance(v, str) else bytes(v) for v in motifs]
+    bid = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+    n, m = len(bid), len(bmot)
+    fields, score = host(hits.fields).reshape(n, m, 8), host(hits.score).reshape(n, m)
+    ratio, strand = host(hits.ratio).astype(np.float32).reshape(n, m), host(hits.strand).reshape(n, m)
+    if len(lens) != n:
+        raise MtrError(f"{len(lens)} lengths for {n} ids")
+    shown = [(b, b.translate(_COMPLEMENT)[::-1]) for b in bmot]
+    out = []
+    for r, k in zip(*np.nonzero((score > 0) & (ratio >= np.float32(min_ratio)) & (fields[:, :, 3] >= min_copies))):
+        f = [int(v) for v in fields[r, k]]
+        cols = [str(int(lens[r])), str(f[0] + 1), str(f[1] + 1), str(f[2]), str(len(bmot[k])), str(f[3]), str(f[4]), _c_float_text(ratio[r, k]),
+                str(f[5]), str(f[6]), str(f[7])]
+        out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + shown[k][int(strand[r, k])] + b"\n")
+    return b"".join(out)
 
 
 def _motif_rows(mot: ReportMotifs):

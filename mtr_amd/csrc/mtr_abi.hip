@@ -38,6 +38,7 @@
 #include "report_align.hip.inc"
 #include "report_text.hip.inc"
 #include "report_motif.hip.inc"
+#include "motif_search.hip.inc"
 #include "fasta.hip.inc"
 #include "fastq.hip.inc"
 #include "file_order.hip.inc"
@@ -75,7 +76,7 @@ template <typename T> using PinnedBuf = GrowBuf<T, true>;
 // that size scratch or run DPs of their own; MTR_DEBUG (dbg) and MTR_TEST_WRAP_DP_SIZE (mtr_create) are read where they act.
 struct RunSwitches {
     bool staged, two_pass_set, test_caps_set, walk_screen;
-    int two_pass, pass_shuffle, service_wpc, select_wpc, polish_wpc, rev_wpc, waves_per_cu, dp16_max_rows, test_flags;
+    int two_pass, pass_shuffle, service_wpc, select_wpc, polish_wpc, rev_wpc, waves_per_cu, dp16_max_rows, test_flags, motif_lane_max, motif_lane_rows;
     int32_t trace_mask; long quad_min; long long two_pass_long_min; double scratch_max_gb;
     std::string test_caps;
 };
@@ -101,6 +102,8 @@ static void read_switches(RunSwitches &w)
     w.test_caps = e ? e : "";
     w.test_flags = (e = getenv("MTR_TEST_STAGED_FLAGS")) ? atoi(e) : 0;             // tests: StagedArgs::test_flags
     w.walk_screen = (e = getenv("MTR_TEST_WALK_SCREEN")) ? atoi(e) != 0 : true;     // tests: 0 = no dead-range screen, every range is an item of mtr_k_walks
+    w.motif_lane_max = (e = getenv("MTR_TEST_MOTIF_LANE_MAX")) ? std::min(std::max(atoi(e), 0), MDP_MAX_U) : MS_LANE_MAX_U;   // tests: the longest motif of the search's lane path (0: none)
+    w.motif_lane_rows = (e = getenv("MTR_TEST_MOTIF_LANE_ROWS")) ? std::min(std::max(atoi(e), 0), MS_LANE_ROWS) : MS_LANE_ROWS;   // tests: the longest read of it
 }
 
 // The staged chain's buffers: fixed capacities per batch (staged_plan), grow-only like the others
@@ -207,6 +210,10 @@ struct mtr_ctx {
     // grouping needs (motif_work lays the three buffers out), the table, and per group the catalogue's columns; mtr_test_unit_motifs uses them too
     bool mo_ready = false; int64_t mo_groups = 0, mo_motif_bytes = 0;
     DevBuf<int32_t> d_mo_i32, d_mo_g32; DevBuf<int64_t> d_mo_i64, d_mo_g64; DevBuf<uint8_t> d_mo_u8, d_mo_motifs; DevBuf<unsigned> d_mo_table;
+    // known-motif search (mtr_search_motifs_device), per call: the order and the slots' tables, the work lists, the slots' codes, the tasks' results,
+    // its own status word and item counters (the run's d_status / d_work / d_counters are not touched: a search may come between a run and its fetch)
+    DevBuf<int32_t> d_ms_i32, d_ms_res, d_ms_status; DevBuf<int64_t> d_ms_i64; DevBuf<uint8_t> d_ms_units; DevBuf<unsigned long long> d_ms_counter;
+    long long wrap_dp_size = MTRC_WRAP_DP_SIZE;          // the WrapDPsize the kernels of this context's device test (MTR_TEST_WRAP_DP_SIZE)
     // a FASTA file in device memory (fasta.hip.inc), per call: the tiles' columns, the header windows' columns, the IDs' offsets, the stop, the sizes
     DevBuf<uint32_t> d_fa_tiles, d_fa_hbase; DevBuf<int32_t> d_fa_hpos, d_fa_hidlen; DevBuf<int64_t> d_fa_idoff;
     DevBuf<unsigned long long> d_fa_event; DevBuf<mtr_fasta_info> d_fa_info;
@@ -333,6 +340,7 @@ extern "C" mtr_status mtr_create(int device, int manhattan, float min_match_rati
         static long long wrap_set[64];                           // what this process last wrote on the device (0 = the built-in 2e8)
         const char *e = getenv("MTR_TEST_WRAP_DP_SIZE");
         const long long want = e && atoll(e) > 0 ? atoll(e) : 0;
+        ctx->wrap_dp_size = want ? want : (long long)MTRC_WRAP_DP_SIZE;
         std::lock_guard<std::mutex> lk(g_mt_mu);
         if (want != wrap_set[device]) {
             const long long v = want ? want : (long long)MTRC_WRAP_DP_SIZE;
@@ -1953,6 +1961,159 @@ extern "C" mtr_status mtr_report_motifs_device(mtr_ctx *ctx, const mtr_report_mo
         HIPCHK(hipMemcpyAsync(dst->g_reads, mg.reads, g * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->g_copies, mg.copies, g * 8, dd, ctx->stream));
         HIPCHK(hipMemcpyAsync(dst->g_bases, mg.bases, g * 8, dd, ctx->stream));
     }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- known-motif search (motif_search.hip.inc) -------------------------------------------------------------------------------------
+// Only the lengths (already on the host) decide the work: one argsort per call, the slots' tables and at most five work lists go up, nothing
+// comes back but the status word.  Nothing kept lives in d_scratch (every user sizes and fills it per launch), so growing it here is safe.
+static mtr_status search_motifs_check(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs, int32_t gain, int32_t mismatch, int32_t indel)
+{
+    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    if (n_motifs <= 0) { ctx->err = "n_motifs = " + std::to_string(n_motifs) + ": at least one motif is needed"; return MTR_ERR_BAD_ARG; }
+    if (!motifs || !motif_off) { ctx->err = "motifs or motif_off is NULL"; return MTR_ERR_BAD_ARG; }
+    if (gain < 1 || gain > 5) { ctx->err = "gain = " + std::to_string(gain) + " outside 1..5"; return MTR_ERR_BAD_ARG; }
+    if (mismatch < 1 || mismatch > 3) { ctx->err = "mismatch = " + std::to_string(mismatch) + " outside 1..3"; return MTR_ERR_BAD_ARG; }
+    if (indel < 1 || indel > 3) { ctx->err = "indel = " + std::to_string(indel) + " outside 1..3"; return MTR_ERR_BAD_ARG; }
+    if (n_motifs > INT32_MAX / 2 || motif_off[n_motifs] - motif_off[0] > INT32_MAX / 2) {     // (the slots and their codes are indexed with 32 bits on the two strands)
+        ctx->err = "more than 2^30 - 1 motifs or motif bases"; return MTR_ERR_BAD_ARG;
+    }
+    for (int32_t m = 0; m < n_motifs; m++) {
+        const int64_t U = motif_off[m + 1] - motif_off[m];
+        if (U < 0) { ctx->err = "motif_off decreases at motif " + std::to_string(m); return MTR_ERR_BAD_ARG; }
+        if (U < 1 || U >= MTRC_MAX_PERIOD) { ctx->err = "motif " + std::to_string(m) + ": length " + std::to_string(U) + " outside 1.." + std::to_string(MTRC_MAX_PERIOD - 1); return MTR_ERR_BAD_ARG; }
+        for (int64_t t = motif_off[m]; t < motif_off[m + 1]; t++)
+            if (motifs[t] != 'A' && motifs[t] != 'C' && motifs[t] != 'G' && motifs[t] != 'T') {
+                ctx->err = "motif " + std::to_string(m) + ": byte " + std::to_string((int)(unsigned char)motifs[t]) + " at " + std::to_string(t - motif_off[m]) + " is none of ACGT";
+                return MTR_ERR_BAD_ARG;
+            }
+    }
+    if ((int64_t)ctx->n_reads * (int64_t)n_motifs > (int64_t)INT32_MAX) {
+        ctx->err = std::to_string(ctx->n_reads) + " reads x " + std::to_string(n_motifs) + " motifs are more than 2^31 - 1 hits"; return MTR_ERR_BAD_ARG;
+    }
+    // the reference's WrapDPsize test (wrap_around_DP.c:260) for the longest read first, then for the read it names
+    for (int32_t m = 0; m < n_motifs; m++) {
+        const long long U = motif_off[m + 1] - motif_off[m];
+        if ((U + 1) * (long long)ctx->Lmax + U < ctx->wrap_dp_size) continue;
+        for (int i = 0; i < ctx->n_reads; i++)
+            if ((U + 1) * (long long)ctx->lens[(size_t)i] + U >= ctx->wrap_dp_size) {
+                ctx->err = "You need to increse the value of WrapDPsize. (read " + std::to_string(i) + " of " + std::to_string(ctx->lens[(size_t)i]) + " bases against motif " +
+                           std::to_string(m) + " of " + std::to_string(U) + " bases exceeds " + std::to_string(ctx->wrap_dp_size) + " cells)";
+                return MTR_ERR_DP_TOO_LARGE;
+            }
+    }
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_search_motifs_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs, int32_t gain, int32_t mismatch,
+                                               int32_t indel, int32_t both_strands, const mtr_motif_hits_dst *dst, int64_t *out_hits)
+{
+    if (!ctx || !out_hits) return MTR_ERR_BAD_ARG;
+    *out_hits = 0;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    { mtr_status st = search_motifs_check(ctx, motifs, motif_off, n_motifs, gain, mismatch, indel); if (st != MTR_OK) return st; }
+    const int n = ctx->n_reads;
+    const int64_t H = (int64_t)n * n_motifs;
+    *out_hits = H;
+    if (!dst) return MTR_OK;
+    if (dst->cap_hits < H) { ctx->err = "destination holds " + std::to_string(dst->cap_hits) + " hits, " + std::to_string(H) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (!dst->fields || !dst->score || !dst->ratio || !dst->strand) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    const int lane_max = ctx->sw.motif_lane_max, lane_rows = ctx->sw.motif_lane_rows;
+    const int ns = both_strands ? 2 : 1, S = n_motifs * ns;
+    // the reads by descending length (ties in input order), the first n_long of them beyond the lane path
+    std::vector<int32_t> order((size_t)n);
+    for (int i = 0; i < n; i++) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return ctx->lens[(size_t)x] > ctx->lens[(size_t)y]; });
+    int n_long = 0;
+    while (n_long < n && ctx->lens[(size_t)order[(size_t)n_long]] > lane_rows) n_long++;
+    const long long L_first = ctx->lens[(size_t)order[0]], L_lane = n_long < n ? ctx->lens[(size_t)order[(size_t)n_long]] : 0;
+    // the slots: codes 0..3 of the motif, then of its reverse complement
+    std::vector<uint8_t> units; std::vector<int32_t> unit_off((size_t)S + 1, 0); std::vector<uint64_t> bits((size_t)S, 0);
+    for (int32_t m = 0; m < n_motifs; m++) {
+        const int U = (int)(motif_off[m + 1] - motif_off[m]);
+        for (int s = 0; s < ns; s++) {
+            const size_t at = units.size();
+            for (int t = 0; t < U; t++) {
+                const char c = motifs[motif_off[m] + (s ? U - 1 - t : t)];
+                const int code = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : 3;
+                units.push_back((uint8_t)(s ? 3 - code : code));
+            }
+            unit_off[(size_t)(m * ns + s) + 1] = (int32_t)units.size();
+            bits[(size_t)(m * ns + s)] = mdp_motif_bits(units.data() + at, U);
+        }
+    }
+    // the work lists: one per bucket of the lane path (groups of 64 reads of the order from n_long on), one of the wave path (reads)
+    enum { N_LISTS = 5 };
+    static const int bucket_ub[4] = { 4, 8, 16, 32 };
+    std::vector<int32_t> l_slot[N_LISTS]; std::vector<int64_t> l_first[N_LISTS]; int l_umax[N_LISTS] = { 0, 0, 0, 0, 0 };
+    const int64_t groups = ((int64_t)(n - n_long) + 63) / 64;
+    for (int k = 0; k < N_LISTS; k++) l_first[k].push_back(0);
+    for (int slot = 0; slot < S; slot++) {
+        const int U = unit_off[(size_t)slot + 1] - unit_off[(size_t)slot];
+        const bool lane = U <= lane_max && groups > 0;
+        if (lane) {
+            int k = 0; while (bucket_ub[k] < U) k++;
+            l_slot[k].push_back(slot); l_first[k].push_back(l_first[k].back() + groups); l_umax[k] = std::max(l_umax[k], U);
+        }
+        const int64_t by_wave = U <= lane_max ? n_long : n;
+        if (by_wave > 0) { l_slot[4].push_back(slot); l_first[4].push_back(l_first[4].back() + by_wave); l_umax[4] = std::max(l_umax[4], U); }
+    }
+    // device copies: d_ms_i32 = order | unit_off | the lists' slots, d_ms_i64 = bits | the lists' firsts
+    const size_t nr = (size_t)n, sS = (size_t)S;
+    HIPCHK(ctx->d_ms_i32.ensure((nr + sS + 1 + N_LISTS * sS) * 4)); HIPCHK(ctx->d_ms_i64.ensure((sS + N_LISTS * (sS + 1)) * 8));
+    HIPCHK(ctx->d_ms_units.ensure(units.size() + 16)); HIPCHK(ctx->d_ms_res.ensure((size_t)H * (size_t)ns * MS_RES * 4));
+    HIPCHK(ctx->d_ms_status.ensure(4)); HIPCHK(ctx->d_ms_counter.ensure(N_LISTS * 8));
+    int32_t *d_order = ctx->d_ms_i32, *d_uoff = d_order + nr, *d_slots = d_uoff + sS + 1;
+    int64_t *d_bits = ctx->d_ms_i64, *d_firsts = d_bits + sS;
+    HIPCHK(copy_sync(ctx, d_order, order.data(), nr * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_uoff, unit_off.data(), (sS + 1) * 4, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, d_bits, bits.data(), sS * 8, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_ms_units, units.data(), units.size(), hipMemcpyHostToDevice));
+    for (int k = 0; k < N_LISTS; k++) {
+        if (l_slot[k].empty()) continue;
+        HIPCHK(copy_sync(ctx, d_slots + (size_t)k * sS, l_slot[k].data(), l_slot[k].size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(copy_sync(ctx, d_firsts + (size_t)k * (sS + 1), l_first[k].data(), l_first[k].size() * 8, hipMemcpyHostToDevice));
+    }
+    // the launches' wavefronts and scratch: a lane wavefront holds rows x dwords x 64 lanes of cells, a wave wavefront one code matrix as mtr_test_wrap_dp's
+    size_t per_wave[N_LISTS] = { 0 }, scratch = 0; int waves[N_LISTS] = { 0 };
+    const size_t wave_cells = (size_t)L_first * (size_t)(l_umax[4] + 1);
+    for (int k = 0; k < N_LISTS; k++) {
+        if (l_slot[k].empty()) continue;
+        per_wave[k] = k < 4 ? mtrc_align((size_t)L_lane * (size_t)mdp_dwords(l_umax[k]) * 256, 256) : mtrc_align(wave_cells + 256, 256);
+        size_t total = 0;
+        waves[k] = pick_waves(ctx, (int)std::min<int64_t>(l_first[k].back(), INT32_MAX), k < 4 ? 16 : 8, per_wave[k], &total);
+        scratch = std::max(scratch, total);
+    }
+    { mtr_status s = ensure_scratch(ctx, scratch); if (s != MTR_OK) return s; }
+    HIPCHK(hipMemsetAsync(ctx->d_ms_status, 0, 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_ms_counter, 0, N_LISTS * 8, ctx->stream));
+    MotifSearchArgs a{};
+    a.b.packed = ctx->d_packed; a.b.woff = ctx->d_woff; a.b.lens = ctx->d_lens; a.b.order = d_order; a.b.n_reads = n;
+    a.order = d_order; a.n_reads = n; a.n_long = n_long; a.units = ctx->d_ms_units; a.unit_off = d_uoff; a.bits = (const uint64_t *)d_bits;
+    a.n_motifs = n_motifs; a.n_strands = ns; a.G = gain; a.MM = mismatch; a.D = indel; a.res = ctx->d_ms_res;
+    a.scratch = ctx->d_scratch; a.status = ctx->d_ms_status; a.dp16_max_rows = ctx->sw.dp16_max_rows;
+    for (int k = 0; k < N_LISTS; k++) {
+        if (l_slot[k].empty()) continue;
+        a.work = { d_slots + (size_t)k * sS, d_firsts + (size_t)k * (sS + 1), (int32_t)l_slot[k].size(), l_first[k].back() };
+        a.counter = (unsigned long long *)ctx->d_ms_counter + k; a.scratch_per_wave = per_wave[k]; a.cells_cap = k < 4 ? 0 : wave_cells;
+        DBG("search_motifs: list %d: %zu slots, %lld items, %d wavefronts of %zu bytes", k, l_slot[k].size(), (long long)l_first[k].back(), waves[k], per_wave[k]);
+        const dim3 grid((unsigned)waves[k]), block(64);
+        if (k == 0) hipLaunchKernelGGL(mtr_k_motif_lanes<4>, grid, block, 0, ctx->stream, a);
+        else if (k == 1) hipLaunchKernelGGL(mtr_k_motif_lanes<8>, grid, block, 0, ctx->stream, a);
+        else if (k == 2) hipLaunchKernelGGL(mtr_k_motif_lanes<16>, grid, block, 0, ctx->stream, a);
+        else if (k == 3) hipLaunchKernelGGL(mtr_k_motif_lanes<32>, grid, block, 0, ctx->stream, a);
+        else hipLaunchKernelGGL(mtr_k_motif_waves, grid, block, 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    // the status before the columns: a failed search writes nothing
+    int32_t dev = 0;
+    HIPCHK(copy_sync(ctx, &dev, ctx->d_ms_status, 4, hipMemcpyDeviceToHost));
+    if (dev == DEV_ERR_DP_TOO_LARGE) { ctx->err = "You need to increse the value of WrapDPsize. (a DP of the motif search exceeded it or its scratch)"; return MTR_ERR_DP_TOO_LARGE; }
+    if (dev != DEV_OK) { ctx->err = "the motif search failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
+    const MotifHitsOut out = { dst->fields, dst->score, dst->ratio, dst->strand };
+    hipLaunchKernelGGL(mtr_k_motif_pack, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t *)ctx->d_ms_res, (int32_t)ns, H, out);
+    HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
 }

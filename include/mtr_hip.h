@@ -400,6 +400,52 @@ mtr_status mtr_search_motifs_device(mtr_ctx *ctx, const char *motifs, const int6
                                     int32_t gain, int32_t mismatch, int32_t indel, int32_t both_strands,
                                     const mtr_motif_hits_dst *dst, int64_t *out_hits);
 
+/* ---- known-motif search: every locus of a motif in a read, not only the best -----------------------------------------------------------------
+ * mtr_search_motifs_device answers with ONE hit per (read, motif), the best local alignment; a long read or a contig holds a motif at several
+ * places.  This call reports all of them that reach a score, by aligning what lies left and right of a hit again.  The definition, for a read
+ * x[0 .. L), a motif m, the scores G, MM, D and both_strands of the search, a threshold min_score = S >= 1 and max_rounds = R in 1..32, with
+ * minlen = ceil(S / G) (a locus of score S holds at least that many read bases):
+ *   loci(lo, hi, depth):                          the half-open window x[lo .. hi)
+ *       if hi - lo < minlen: return
+ *       if depth == R: open = 1; return           the pair's "open" flag: something may be left
+ *       (hit, strand) = the hit of mtr_search_motifs_device's definition above, verbatim, for the read x[lo .. hi): both strands, the higher
+ *                       score wins, the forward motif on a tie
+ *       if hit.score < S: return
+ *       emit the hit with start and end raised by lo, and its strand
+ *       loci(lo, lo + hit.start, depth + 1);  loci(lo + hit.end + 1, hi, depth + 1)
+ *   the loci of (read, motif) = loci(0, L, 0), reported in ascending start
+ * A reported hit has repeat_len >= 1, so both children are strictly shorter and the recursion ends; the loci of a pair never overlap; with R = 1
+ * the result is mtr_search_motifs_device's hit where its score reaches S and nothing otherwise; skipping a window shorter than minlen never
+ * changes a result.
+ * The number of loci T is known only after the work, so there are two entry points: the search keeps its result in buffers of the context, the
+ * copy hands it out.
+ * mtr_search_motif_loci_device: the protocol of mtr_search_motifs_device - a run in flight ends first, an uploaded batch is needed and no run is,
+ * nothing a run left is touched, its own status word and counters.  The checks are the search's in the search's order, with MTR_ERR_BAD_ARG for
+ * min_score < 1 and for max_rounds outside 1..32 after the other arguments' and before MTR_ERR_DP_TOO_LARGE, which is decided from the whole reads
+ * before any launch, as there.  MTR_ERR_OVERFLOW if one round holds more than 2^31 - 1 alignments or the loci exceed 2^31 - 1.  On MTR_OK
+ * *out_pairs = P = n_reads * n_motifs, *out_loci = T and the result is kept; a failed call keeps nothing.  An upload of any kind and the next locus
+ * search (whatever its outcome) discard what is kept; a run does not.
+ * mtr_motif_loci_copy_device copies the kept result, device to device, into caller-owned DEVICE memory of the context's GPU:
+ *   loci_off   [P + 1]   the loci of pair p = read * n_motifs + motif are rows loci_off[p] .. loci_off[p + 1], in ascending start
+ *   fields     [T * 8]   the search's eight columns, in read coordinates;  score [T];  ratio [T], the search's formula;  strand [T]
+ *   open       [P]       1: the recursion reached depth R on a window of at least minlen bases - a larger max_rounds may find more
+ * MTR_ERR_BAD_ARG if nothing is kept or dst is NULL; MTR_ERR_OVERFLOW if cap_pairs < P or cap_loci < T, and then nothing is written;
+ * MTR_ERR_BAD_ARG if loci_off or open is NULL, or with T > 0 any other column; else the columns are written and the context's stream is
+ * synchronised before the call returns.  Two searches with the same arguments give byte-identical columns. */
+typedef struct mtr_motif_loci_dst {
+    int64_t *loci_off; /* [P+1] */
+    int32_t *fields;   /* [T*8] start, end, repeat_len, copies, matches, mismatches, insertions, deletions */
+    int32_t *score;    /* [T] */
+    float   *ratio;    /* [T] */
+    uint8_t *strand;   /* [T] */
+    uint8_t *open;     /* [P] */
+    int64_t  cap_pairs, cap_loci;
+} mtr_motif_loci_dst;   /* caller-owned DEVICE memory */
+mtr_status mtr_search_motif_loci_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs,
+                                        int32_t gain, int32_t mismatch, int32_t indel, int32_t both_strands,
+                                        int32_t min_score, int32_t max_rounds, int64_t *out_pairs, int64_t *out_loci);
+mtr_status mtr_motif_loci_copy_device(mtr_ctx *ctx, const mtr_motif_loci_dst *dst);
+
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left
  * of handle_one_file.c:281-287's loop across GPUs is ONE exchange: the record tables travel to the process that chains and

@@ -74,7 +74,9 @@ mtr_status mtr_test_file_tail(mtr_ctx *ctx, uint16_t **out_tail, int64_t **out_t
  *   MTR_TEST_MOTIF_LANE_MAX=<u>   mtr_search_motifs_device, read per call: the longest motif its lane path (one DP per lane, mtr_k_motif_lanes) takes,
  *                            0 .. 32; 0 sends every alignment through the wave path (mtr_k_motif_waves, one DP per wavefront).  The hits do not depend on it.
  *   MTR_TEST_MOTIF_LANE_ROWS=<n>  the longest read the lane path takes (at most its built-in bound of 16384 rows); longer reads take the wave path,
- *                            reads either side of the bound come from different kernels in one call.  The hits do not depend on it. */
+ *                            reads either side of the bound come from different kernels in one call.  The hits do not depend on it.
+ *                            mtr_search_motif_loci_device reads both per call as well; there the bound on the rows is on the WINDOW's length, so the
+ *                            short children of a long read are lanes' work.  The loci do not depend on either. */
 
 #ifdef __cplusplus
 }

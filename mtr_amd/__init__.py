@@ -3,7 +3,7 @@
 Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointers).  Only the device-input and report methods
 (Engine.upload_device / process_device / parse_fasta_device / upload_fasta_device / parse_fastq_device / upload_fastq_device /
 walk_fasta_device / walk_fastq_device /
-export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes / report_motif_tensors / search_motifs) take or return torch tensors;
+export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes / report_motif_tensors / search_motifs / search_motif_loci) take or return torch tensors;
 they import torch when called.
 The product path is libmtr_hip.so only: importing works without a GPU, but creating an Engine
 without the library or without a HIP device raises — there is no CPU fallback.
@@ -50,7 +50,8 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_parse_fastq_device", "mtr_upload_fastq_device", "mtr_upload_fastq_device_in_file",
            "mtr_upload_batch_device_in_file", "mtr_upload_fasta_device_in_file", "mtr_file_state_skip_device", "mtr_test_file_tail",
            "mtr_parse_fasta_device_window", "mtr_upload_fasta_device_window", "mtr_parse_fastq_device_window", "mtr_upload_fastq_device_window",
-           "mtr_report_motifs_device", "mtr_test_unit_motifs", "mtr_search_motifs_device"]
+           "mtr_report_motifs_device", "mtr_test_unit_motifs", "mtr_search_motifs_device",
+           "mtr_search_motif_loci_device", "mtr_motif_loci_copy_device"]
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
 
@@ -188,6 +189,23 @@ class MotifHits(NamedTuple):
     strand: "object"      # uint8 [n, m]: 0 = the motif as given, 1 = its reverse complement aligned better
 
 
+class CMotifLociDst(C.Structure):
+    """mtr_motif_loci_dst: device pointers of the locus search's columns and their capacities"""
+    _fields_ = [("loci_off", C.c_void_p), ("fields", C.c_void_p), ("score", C.c_void_p), ("ratio", C.c_void_p), ("strand", C.c_void_p),
+                ("open", C.c_void_p), ("cap_pairs", C.c_int64), ("cap_loci", C.c_int64)]
+
+
+class MotifLoci(NamedTuple):
+    """What Engine.search_motif_loci found: every locus of every motif in every read, T in all for n reads and m motifs, all on the engine's
+    device.  include/mtr_hip.h defines every column."""
+    loci_off: "object"    # int64 [n * m + 1]: the loci of (read r, motif k) are rows loci_off[r * m + k] .. loci_off[r * m + k + 1], ascending start
+    fields: "object"      # int32 [T, 8]: MotifHits' columns, in read coordinates
+    score: "object"       # int32 [T]: at least min_score
+    ratio: "object"       # float32 [T]: matches / repeat_len
+    strand: "object"      # uint8 [T]
+    open: "object"        # uint8 [n, m]: 1 = max_rounds ended the search of this pair with a window left that could still hold a locus
+
+
 class CFastaInfo(C.Structure):
     """mtr_fasta_info: what a FASTA file in device memory holds"""
     _fields_ = [("n_reads", C.c_int32), ("end", C.c_int32), ("bad_char", C.c_int32), ("reserved", C.c_int32),
@@ -309,6 +327,10 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_test_unit_motifs.restype = C.c_int
     lib.mtr_search_motifs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [P(CMotifHitsDst), P(C.c_int64)]
     lib.mtr_search_motifs_device.restype = C.c_int
+    lib.mtr_search_motif_loci_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [P(C.c_int64), P(C.c_int64)]
+    lib.mtr_search_motif_loci_device.restype = C.c_int
+    lib.mtr_motif_loci_copy_device.argtypes = [C.c_void_p, P(CMotifLociDst)]
+    lib.mtr_motif_loci_copy_device.restype = C.c_int
     lib.mtr_parse_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaDst), P(CFastaInfo)]
     lib.mtr_parse_fasta_device.restype = C.c_int
     lib.mtr_upload_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaInfo)]
@@ -785,6 +807,33 @@ class Engine:
         self._check(self.lib.mtr_search_motifs_device(*args, C.byref(dst), C.byref(nh)), "mtr_search_motifs_device")
         return hits
 
+    def search_motif_loci(self, motifs, min_score: int, gain: int = 1, mismatch: int = 1, indel: int = 1, both_strands: bool = True,
+                          max_rounds: int = 16) -> MotifLoci:
+        """Known-motif locus search (mtr_search_motif_loci_device, mtr_motif_loci_copy_device): EVERY place of every motif in every read of the
+        uploaded batch whose alignment scores at least min_score, not only the best one of search_motifs - what lies left and right of a hit
+        is aligned again, at most max_rounds (1..32) levels deep; `open` marks the pairs where that bound ended the search.  Needs no run and
+        changes nothing a run left.  Returns a MotifLoci of fresh tensors on this engine's device; follows search_motifs' stream handling."""
+        import torch
+
+        if isinstance(motifs, (str, bytes, bytearray)) or not hasattr(motifs, "__len__"):
+            raise MtrError(f"motifs must be a sequence of str or bytes, got {type(motifs).__name__}")
+        data, off = pack_ids(motifs)
+        m = len(motifs)
+        npairs, nloci = C.c_int64(), C.c_int64()
+        self._check(self.lib.mtr_search_motif_loci_device(self.h, data.ctypes.data, off.ctypes.data, m, int(gain), int(mismatch), int(indel),
+                                                          1 if both_strands else 0, int(min_score), int(max_rounds), C.byref(npairs), C.byref(nloci)),
+                    "mtr_search_motif_loci_device")
+        Pn, T = int(npairs.value), int(nloci.value)
+        n = Pn // m
+        dev = torch.device("cuda", self.device)
+        loci = MotifLoci(torch.empty((Pn + 1,), dtype=torch.int64, device=dev), torch.empty((T, 8), dtype=torch.int32, device=dev),
+                         torch.empty((T,), dtype=torch.int32, device=dev), torch.empty((T,), dtype=torch.float32, device=dev),
+                         torch.empty((T,), dtype=torch.uint8, device=dev), torch.empty((n, m), dtype=torch.uint8, device=dev))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CMotifLociDst(*[t.data_ptr() if t.numel() else None for t in loci], Pn, T)
+        self._check(self.lib.mtr_motif_loci_copy_device(self.h, C.byref(dst)), "mtr_motif_loci_copy_device")
+        return loci
+
     def test_unit_motifs(self, units, read=None, copies=None, repeat_len=None, table_slots: int = 0) -> ReportMotifs:
         """mtr_test_unit_motifs: the kernels of report_motif_tensors on caller-given units, one bytes (or str) per unit.  read: the read of
         each unit, non-decreasing (default: every unit a read of its own); copies: num_freq_unit (default 1); repeat_len (default: the
@@ -1144,6 +1193,41 @@ def format_motif_hits(ids, lens, motifs, hits: MotifHits, min_ratio: float = 0.0
         cols = [str(int(lens[r])), str(f[0] + 1), str(f[1] + 1), str(f[2]), str(len(bmot[k])), str(f[3]), str(f[4]), _c_float_text(ratio[r, k]),
                 str(f[5]), str(f[6]), str(f[7])]
         out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + shown[k][int(strand[r, k])] + b"\n")
+    return b"".join(out)
+
+
+def format_motif_loci(ids, lens, motifs, loci: MotifLoci, min_ratio: float = 0.0, min_copies: int = 1) -> bytes:
+    """The loci of Engine.search_motif_loci as text: format_motif_hits' thirteen columns, one line per kept locus, ordered by read, then motif
+    (in the given order), then start.  Strand 1 prints the motif's reverse complement.  Kept: ratio >= min_ratio and copies >= min_copies.
+    ids, lens: per read its ID (str or bytes) and length; motifs: what search_motif_loci was given; loci: its result (tensors or numpy)."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    bmot = [v.encode() if isinstance(v, str) else bytes(v) for v in motifs]
+    bid = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+    n, m = len(bid), len(bmot)
+    off, fields = host(loci.loci_off).reshape(-1), host(loci.fields).reshape(-1, 8)
+    score, ratio, strand = host(loci.score).reshape(-1), host(loci.ratio).astype(np.float32).reshape(-1), host(loci.strand).reshape(-1)
+    if len(lens) != n:
+        raise MtrError(f"{len(lens)} lengths for {n} ids")
+    if len(off) != n * m + 1:
+        raise MtrError(f"{len(off)} offsets for {n} ids and {m} motifs: {n * m + 1} needed")
+    T = int(off[-1]) if len(off) else 0
+    if not (len(fields) == len(score) == len(ratio) == len(strand) == T):
+        raise MtrError(f"columns of {len(fields)}, {len(score)}, {len(ratio)} and {len(strand)} rows for {T} loci")
+    if int(off[0]) != 0 or (np.diff(off) < 0).any():
+        raise MtrError("loci_off does not ascend from 0")
+    shown = [(b, b.translate(_COMPLEMENT)[::-1]) for b in bmot]
+    out = []
+    for p in range(n * m):
+        r, k = divmod(p, m)
+        for t in range(int(off[p]), int(off[p + 1])):
+            f = [int(v) for v in fields[t]]
+            if not (ratio[t] >= np.float32(min_ratio) and f[3] >= min_copies):
+                continue
+            cols = [str(int(lens[r])), str(f[0] + 1), str(f[1] + 1), str(f[2]), str(len(bmot[k])), str(f[3]), str(f[4]), _c_float_text(ratio[t]),
+                    str(f[5]), str(f[6]), str(f[7])]
+            out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + shown[k][int(strand[t])] + b"\n")
     return b"".join(out)
 
 

@@ -18,6 +18,9 @@
 //   traceback   wrap_around_DP.c:298-333 on the flags: match, else stop at H == 0, else mismatch, deletion, insertion in that order.  One
 //               dword load per (row, dword) visited.  A walk of more than (bi + 1) * (U + 1) steps cannot come from a consistent matrix:
 //               score = -1 instead of spinning.
+//   window      the locus search (motif_loci.hip.inc) aligns a WINDOW x[lo .. lo + L) of the read: the last argument `lo` of the forward pass
+//               (default 0: the whole read) makes row i stand for base x[lo + i - 1], with the word and the phase of that position.  Nothing
+//               else changes - the rows, the cells and every output are the window's own, as if its bases had been copied out.
 #pragma once
 #include "mtr_common.h"
 
@@ -48,9 +51,10 @@ struct MdpCellsLane {
     MDP_MEMBER uint32_t load(int i, int d) const { return p[((size_t)(i - 1) * (size_t)nd + (size_t)d) * 64 + (size_t)lane]; }
 };
 
-// pk: the read in the device layout (2 bits per base, first base in the top bits of word 0); L >= 0 rows; 1 <= U <= UB
+// pk: the read in the device layout (2 bits per base, first base in the top bits of word 0); L >= 0 rows; 1 <= U <= UB; lo >= 0: the window's first base
 template <int UB, class Cells>
-MDP_HD void motif_dp_forward(const uint32_t *pk, int L, uint64_t mot, int U, int G, int MM, int D, const Cells &cells, int &best_v, int &best_i, int &best_j)
+MDP_HD void motif_dp_forward(const uint32_t *pk, int L, uint64_t mot, int U, int G, int MM, int D, const Cells &cells, int &best_v, int &best_i, int &best_j,
+                             int lo = 0)
 {
     static_assert(UB >= 1 && UB <= MDP_MAX_U, "bucket");
     int P[UB];
@@ -59,8 +63,8 @@ MDP_HD void motif_dp_forward(const uint32_t *pk, int L, uint64_t mot, int U, int
     int wrap = 0, bv = 0, bi = 0, bj = 0;                    // wrap = H(i - 1, U)
     uint32_t w = 0;
     for (int i = 1; i <= L; i++) {
-        const int b = (i - 1) & 15;
-        if (b == 0) w = pk[(i - 1) >> 4];
+        const int p = lo + i - 1, b = p & 15;
+        if (b == 0 || i == 1) w = pk[p >> 4];                   // (a window begins inside a word)
         const int xi = (int)((w >> (30 - 2 * b)) & 3u);
         int diag = wrap, left = 0;
         uint32_t acc = 0, first = 0;
@@ -120,9 +124,9 @@ MDP_HD MotifHit motif_dp_traceback(const Cells &cells, int U, int best_v, int be
 
 // the two in a row: the single definition of a lane's work
 template <int UB, class Cells>
-MDP_HD MotifHit motif_dp(const uint32_t *pk, int L, uint64_t mot, int U, int G, int MM, int D, const Cells &cells)
+MDP_HD MotifHit motif_dp(const uint32_t *pk, int L, uint64_t mot, int U, int G, int MM, int D, const Cells &cells, int lo = 0)
 {
     int bv, bi, bj;
-    motif_dp_forward<UB>(pk, L, mot, U, G, MM, D, cells, bv, bi, bj);
+    motif_dp_forward<UB>(pk, L, mot, U, G, MM, D, cells, bv, bi, bj, lo);
     return motif_dp_traceback(cells, U, bv, bi, bj);
 }

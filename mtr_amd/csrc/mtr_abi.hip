@@ -39,6 +39,7 @@
 #include "report_text.hip.inc"
 #include "report_motif.hip.inc"
 #include "motif_search.hip.inc"
+#include "motif_loci.hip.inc"
 #include "fasta.hip.inc"
 #include "fastq.hip.inc"
 #include "file_order.hip.inc"
@@ -213,6 +214,13 @@ struct mtr_ctx {
     // known-motif search (mtr_search_motifs_device), per call: the order and the slots' tables, the work lists, the slots' codes, the tasks' results,
     // its own status word and item counters (the run's d_status / d_work / d_counters are not touched: a search may come between a run and its fetch)
     DevBuf<int32_t> d_ms_i32, d_ms_res, d_ms_status; DevBuf<int64_t> d_ms_i64; DevBuf<uint8_t> d_ms_units; DevBuf<unsigned long long> d_ms_counter;
+    // known-motif locus search (mtr_search_motif_loci_device), per call: the slots' tables, the bins' and the tasks' arrays, the two interval lists, the
+    // tasks' results, the hit list, its state words and item counters; and what mtr_motif_loci_copy_device hands out (ml_ready: P pairs, T loci),
+    // kept until the next upload or locus search
+    bool ml_ready = false; int64_t ml_pairs = 0, ml_loci = 0;
+    DevBuf<int32_t> d_ml_i32, d_ml_bin32, d_ml_task32, d_ml_res, d_ml_hits, d_ml_state, d_ml_count, d_ml_starts; DevBuf<int64_t> d_ml_i64, d_ml_bin64;
+    DevBuf<LociIv> d_ml_iv[2]; DevBuf<uint8_t> d_ml_units; DevBuf<unsigned long long> d_ml_counter;
+    DevBuf<int64_t> d_ml_off; DevBuf<int32_t> d_ml_fields, d_ml_score; DevBuf<float> d_ml_ratio; DevBuf<uint8_t> d_ml_strand, d_ml_open;
     long long wrap_dp_size = MTRC_WRAP_DP_SIZE;          // the WrapDPsize the kernels of this context's device test (MTR_TEST_WRAP_DP_SIZE)
     // a FASTA file in device memory (fasta.hip.inc), per call: the tiles' columns, the header windows' columns, the IDs' offsets, the stop, the sizes
     DevBuf<uint32_t> d_fa_tiles, d_fa_hbase; DevBuf<int32_t> d_fa_hpos, d_fa_hidlen; DevBuf<int64_t> d_fa_idoff;
@@ -294,7 +302,7 @@ static hipError_t copy_sync(mtr_ctx *ctx, void *dst, const void *src, size_t byt
 }
 
 // forget the resident batch (its buffers stay allocated for the next one)
-static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->mo_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
+static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->mo_ready = false; ctx->ml_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
 
 extern "C" int mtr_abi_version(void) { return MTR_ABI_VERSION; }
 
@@ -1968,7 +1976,8 @@ extern "C" mtr_status mtr_report_motifs_device(mtr_ctx *ctx, const mtr_report_mo
 // ---- known-motif search (motif_search.hip.inc) -------------------------------------------------------------------------------------
 // Only the lengths (already on the host) decide the work: one argsort per call, the slots' tables and at most five work lists go up, nothing
 // comes back but the status word.  Nothing kept lives in d_scratch (every user sizes and fills it per launch), so growing it here is safe.
-static mtr_status search_motifs_check(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs, int32_t gain, int32_t mismatch, int32_t indel)
+// (the checks in two parts: the locus search has arguments of its own to refuse between them)
+static mtr_status search_motifs_check_args(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs, int32_t gain, int32_t mismatch, int32_t indel)
 {
     if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
     if (n_motifs <= 0) { ctx->err = "n_motifs = " + std::to_string(n_motifs) + ": at least one motif is needed"; return MTR_ERR_BAD_ARG; }
@@ -1992,7 +2001,11 @@ static mtr_status search_motifs_check(mtr_ctx *ctx, const char *motifs, const in
     if ((int64_t)ctx->n_reads * (int64_t)n_motifs > (int64_t)INT32_MAX) {
         ctx->err = std::to_string(ctx->n_reads) + " reads x " + std::to_string(n_motifs) + " motifs are more than 2^31 - 1 hits"; return MTR_ERR_BAD_ARG;
     }
-    // the reference's WrapDPsize test (wrap_around_DP.c:260) for the longest read first, then for the read it names
+    return MTR_OK;
+}
+// the reference's WrapDPsize test (wrap_around_DP.c:260) for the longest read first, then for the read it names
+static mtr_status search_motifs_check_size(mtr_ctx *ctx, const int64_t *motif_off, int32_t n_motifs)
+{
     for (int32_t m = 0; m < n_motifs; m++) {
         const long long U = motif_off[m + 1] - motif_off[m];
         if ((U + 1) * (long long)ctx->Lmax + U < ctx->wrap_dp_size) continue;
@@ -2006,13 +2019,35 @@ static mtr_status search_motifs_check(mtr_ctx *ctx, const char *motifs, const in
     return MTR_OK;
 }
 
+// the slots (slot = motif * ns + strand): codes 0..3 of the motif, then of its reverse complement; for U <= MDP_MAX_U the 2-bit form as well
+static void motif_slots(const char *motifs, const int64_t *motif_off, int32_t n_motifs, int ns, std::vector<uint8_t> &units, std::vector<int32_t> &unit_off,
+                        std::vector<uint64_t> &bits)
+{
+    const size_t S = (size_t)n_motifs * (size_t)ns;
+    units.clear(); unit_off.assign(S + 1, 0); bits.assign(S, 0);
+    for (int32_t m = 0; m < n_motifs; m++) {
+        const int U = (int)(motif_off[m + 1] - motif_off[m]);
+        for (int s = 0; s < ns; s++) {
+            const size_t at = units.size();
+            for (int t = 0; t < U; t++) {
+                const char c = motifs[motif_off[m] + (s ? U - 1 - t : t)];
+                const int code = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : 3;
+                units.push_back((uint8_t)(s ? 3 - code : code));
+            }
+            unit_off[(size_t)(m * ns + s) + 1] = (int32_t)units.size();
+            bits[(size_t)(m * ns + s)] = mdp_motif_bits(units.data() + at, U);
+        }
+    }
+}
+
 extern "C" mtr_status mtr_search_motifs_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs, int32_t gain, int32_t mismatch,
                                                int32_t indel, int32_t both_strands, const mtr_motif_hits_dst *dst, int64_t *out_hits)
 {
     if (!ctx || !out_hits) return MTR_ERR_BAD_ARG;
     *out_hits = 0;
     if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    { mtr_status st = search_motifs_check(ctx, motifs, motif_off, n_motifs, gain, mismatch, indel); if (st != MTR_OK) return st; }
+    { mtr_status st = search_motifs_check_args(ctx, motifs, motif_off, n_motifs, gain, mismatch, indel); if (st != MTR_OK) return st; }
+    { mtr_status st = search_motifs_check_size(ctx, motif_off, n_motifs); if (st != MTR_OK) return st; }
     const int n = ctx->n_reads;
     const int64_t H = (int64_t)n * n_motifs;
     *out_hits = H;
@@ -2030,21 +2065,8 @@ extern "C" mtr_status mtr_search_motifs_device(mtr_ctx *ctx, const char *motifs,
     int n_long = 0;
     while (n_long < n && ctx->lens[(size_t)order[(size_t)n_long]] > lane_rows) n_long++;
     const long long L_first = ctx->lens[(size_t)order[0]], L_lane = n_long < n ? ctx->lens[(size_t)order[(size_t)n_long]] : 0;
-    // the slots: codes 0..3 of the motif, then of its reverse complement
-    std::vector<uint8_t> units; std::vector<int32_t> unit_off((size_t)S + 1, 0); std::vector<uint64_t> bits((size_t)S, 0);
-    for (int32_t m = 0; m < n_motifs; m++) {
-        const int U = (int)(motif_off[m + 1] - motif_off[m]);
-        for (int s = 0; s < ns; s++) {
-            const size_t at = units.size();
-            for (int t = 0; t < U; t++) {
-                const char c = motifs[motif_off[m] + (s ? U - 1 - t : t)];
-                const int code = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : 3;
-                units.push_back((uint8_t)(s ? 3 - code : code));
-            }
-            unit_off[(size_t)(m * ns + s) + 1] = (int32_t)units.size();
-            bits[(size_t)(m * ns + s)] = mdp_motif_bits(units.data() + at, U);
-        }
-    }
+    std::vector<uint8_t> units; std::vector<int32_t> unit_off; std::vector<uint64_t> bits;
+    motif_slots(motifs, motif_off, n_motifs, ns, units, unit_off, bits);
     // the work lists: one per bucket of the lane path (groups of 64 reads of the order from n_long on), one of the wave path (reads)
     enum { N_LISTS = 5 };
     static const int bucket_ub[4] = { 4, 8, 16, 32 };
@@ -2114,6 +2136,194 @@ extern "C" mtr_status mtr_search_motifs_device(mtr_ctx *ctx, const char *motifs,
     const MotifHitsOut out = { dst->fields, dst->score, dst->ratio, dst->strand };
     hipLaunchKernelGGL(mtr_k_motif_pack, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t *)ctx->d_ms_res, (int32_t)ns, H, out);
     HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- known-motif locus search (motif_loci.hip.inc) ---------------------------------------------------------------------------------
+// Round by round: the host knows how many intervals a round has and their longest (LOCI_STATE, one small copy per round), sizes the round's
+// arrays and scratch from that, and enqueues its kernels; everything else - the bins, the work lists, the hits, the children - is made on the device.
+// at least `bytes`, with what the first `keep` bytes hold (the hit list grows from round to round)
+template <typename T>
+static hipError_t grow_keeping(mtr_ctx *ctx, DevBuf<T> &b, size_t keep, size_t bytes)
+{
+    if (b.p && bytes <= b.cap) return hipSuccess;
+    T *fresh = nullptr;
+    const size_t want = std::max<size_t>(bytes + bytes / 2, 256);
+    hipError_t e = hipMalloc((void **)&fresh, want);
+    if (e != hipSuccess) return e;
+    if (keep > 0 && b.p) e = copy_sync(ctx, fresh, b.p, keep, hipMemcpyDeviceToDevice);
+    b.release();
+    b.p = fresh; b.cap = want;
+    return e;
+}
+
+extern "C" mtr_status mtr_search_motif_loci_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs, int32_t gain, int32_t mismatch,
+                                                   int32_t indel, int32_t both_strands, int32_t min_score, int32_t max_rounds, int64_t *out_pairs, int64_t *out_loci)
+{
+    if (!ctx || !out_pairs || !out_loci) return MTR_ERR_BAD_ARG;
+    *out_pairs = 0; *out_loci = 0;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    ctx->ml_ready = false;                                                                             // whatever happens below, the loci kept before this call are gone
+    { mtr_status st = search_motifs_check_args(ctx, motifs, motif_off, n_motifs, gain, mismatch, indel); if (st != MTR_OK) return st; }
+    if (min_score < 1) { ctx->err = "min_score = " + std::to_string(min_score) + ": at least 1"; return MTR_ERR_BAD_ARG; }
+    if (max_rounds < 1 || max_rounds > MLO_MAX_ROUNDS) { ctx->err = "max_rounds = " + std::to_string(max_rounds) + " outside 1.." + std::to_string(MLO_MAX_ROUNDS); return MTR_ERR_BAD_ARG; }
+    { mtr_status st = search_motifs_check_size(ctx, motif_off, n_motifs); if (st != MTR_OK) return st; }
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    const int lane_max = ctx->sw.motif_lane_max, lane_rows = ctx->sw.motif_lane_rows;
+    const int n = ctx->n_reads, ns = both_strands ? 2 : 1, S = n_motifs * ns, minlen = mlo_minlen(min_score, gain);
+    const int64_t P = (int64_t)n * n_motifs;
+    std::vector<uint8_t> units; std::vector<int32_t> unit_off; std::vector<uint64_t> bits;
+    motif_slots(motifs, motif_off, n_motifs, ns, units, unit_off, bits);
+    // the lane slots, numbered bucket by bucket: bucket k's bins are q_first[k] * MLO_N_CLASSES .. q_first[k + 1] * MLO_N_CLASSES
+    static const int bucket_ub[4] = { 4, 8, 16, 32 };
+    std::vector<int32_t> slot_q((size_t)S, -1), q_slot;
+    int q_first[5] = { 0, 0, 0, 0, 0 }, l_umax[4] = { 0, 0, 0, 0 }, u_all = 0, u_wave = 0;      // u_wave: the longest motif no lane takes
+    for (int k = 0; k < 4; k++) {
+        q_first[k] = (int)q_slot.size();
+        for (int slot = 0; slot < S; slot++) {
+            const int U = unit_off[(size_t)slot + 1] - unit_off[(size_t)slot];
+            if (U > lane_max || mdp_bucket(U) != bucket_ub[k]) continue;
+            slot_q[(size_t)slot] = (int32_t)q_slot.size(); q_slot.push_back(slot); l_umax[k] = std::max(l_umax[k], U);
+        }
+    }
+    q_first[4] = (int)q_slot.size();
+    for (int slot = 0; slot < S; slot++) {
+        const int U = unit_off[(size_t)slot + 1] - unit_off[(size_t)slot];
+        u_all = std::max(u_all, U);
+        if (slot_q[(size_t)slot] < 0) u_wave = std::max(u_wave, U);
+    }
+    const size_t sS = (size_t)S, nq = q_slot.size();
+    if ((int64_t)nq * MLO_N_CLASSES > (int64_t)INT32_MAX) { ctx->err = std::to_string(nq) + " short motifs are more than the bins take"; return MTR_ERR_OVERFLOW; }
+    const size_t nb = nq * MLO_N_CLASSES;
+    // device copies: d_ml_i32 = unit_off | slot_q | q_slot, d_ml_i64 = bits; the bins: d_ml_bin32 = hist | groups, d_ml_bin64 = tfirst | gfirst
+    HIPCHK(ctx->d_ml_i32.ensure((2 * sS + 1 + nq + 1) * 4)); HIPCHK(ctx->d_ml_i64.ensure(sS * 8)); HIPCHK(ctx->d_ml_units.ensure(units.size() + 16));
+    HIPCHK(ctx->d_ml_bin32.ensure((2 * nb + 1) * 4)); HIPCHK(ctx->d_ml_bin64.ensure(2 * (nb + 1) * 8));
+    HIPCHK(ctx->d_ml_state.ensure(LOCI_STATE * 4)); HIPCHK(ctx->d_ml_counter.ensure(5 * 8)); HIPCHK(ctx->d_ml_open.ensure((size_t)P));
+    int32_t *d_uoff = ctx->d_ml_i32, *d_slot_q = d_uoff + sS + 1, *d_q_slot = d_slot_q + sS;
+    HIPCHK(copy_sync(ctx, d_uoff, unit_off.data(), (sS + 1) * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_slot_q, slot_q.data(), sS * 4, hipMemcpyHostToDevice));
+    if (nq > 0) HIPCHK(copy_sync(ctx, d_q_slot, q_slot.data(), nq * 4, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, ctx->d_ml_i64, bits.data(), sS * 8, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_ml_units, units.data(), units.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(ctx->d_ml_state, 0, LOCI_STATE * 4, ctx->stream)); HIPCHK(hipMemsetAsync(ctx->d_ml_open, 0, (size_t)P, ctx->stream));
+    LociArgs a{};
+    a.b.packed = ctx->d_packed; a.b.woff = ctx->d_woff; a.b.lens = ctx->d_lens; a.b.order = nullptr; a.b.n_reads = n;
+    a.n_motifs = n_motifs; a.n_strands = ns; a.G = gain; a.MM = mismatch; a.D = indel; a.lane_rows = lane_rows;
+    a.units = ctx->d_ml_units; a.unit_off = d_uoff; a.bits = (const uint64_t *)(int64_t *)ctx->d_ml_i64; a.slot_q = d_slot_q; a.q_slot = d_q_slot;
+    a.hist = ctx->d_ml_bin32; a.groups = a.hist + nb; a.tfirst = ctx->d_ml_bin64; a.gfirst = a.tfirst + nb + 1; a.n_bins = (int32_t)nb;
+    a.state = ctx->d_ml_state; a.dp16_max_rows = ctx->sw.dp16_max_rows;
+    // round 0: every pair's whole read
+    HIPCHK(ctx->d_ml_iv[0].ensure((size_t)P * sizeof(LociIv)));
+    hipLaunchKernelGGL(mtr_k_loci_init, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t *)ctx->d_lens, n_motifs, (int32_t)P, (LociIv *)ctx->d_ml_iv[0]);
+    HIPCHK(hipGetLastError());
+    int64_t N = P, T = 0;
+    int max_len = ctx->Lmax;
+    for (int d = 0; d < max_rounds && N > 0; d++) {
+        const int64_t tasks = N * ns;
+        if (tasks > (int64_t)INT32_MAX || T + N > (int64_t)INT32_MAX) {
+            ctx->err = "round " + std::to_string(d) + ": " + std::to_string(tasks) + " alignments after " + std::to_string(T) + " loci are more than 2^31 - 1"; return MTR_ERR_OVERFLOW;
+        }
+        const size_t nt = (size_t)tasks;
+        LociIv *next = nullptr;
+        {   // the round's arrays: d_ml_task32 = tbin | trank | sorted | wlist; the next round holds at most two intervals per interval, the hit list one more hit
+            DevBuf<LociIv> &nx = ctx->d_ml_iv[(d + 1) & 1];
+            HIPCHK(ctx->d_ml_task32.ensure(4 * nt * 4)); HIPCHK(ctx->d_ml_res.ensure(nt * MS_RES * 4)); HIPCHK(nx.ensure(2 * (size_t)N * sizeof(LociIv)));
+            HIPCHK(grow_keeping(ctx, ctx->d_ml_hits, (size_t)T * LOCI_HIT * 4, (size_t)(T + N) * LOCI_HIT * 4));
+            next = nx;
+        }
+        a.iv = ctx->d_ml_iv[d & 1]; a.n_iv = (int32_t)N;
+        a.tbin = ctx->d_ml_task32; a.trank = a.tbin + nt; a.sorted = a.trank + nt; a.wlist = a.sorted + nt; a.res = ctx->d_ml_res;
+        // the launches' wavefronts and scratch, as the search's: lanes hold rows x dwords x 64 lanes of cells, a wave wavefront one code matrix
+        const int lane_len = std::min(max_len, lane_rows);
+        const bool by_wave = u_wave > 0 || max_len > lane_rows;
+        const size_t wave_cells = (size_t)max_len * (size_t)((max_len > lane_rows ? u_all : u_wave) + 1);
+        size_t per_wave[5] = { 0 }, scratch = 0; int waves[5] = { 0 };
+        for (int k = 0; k < 5; k++) {
+            if (k < 4 ? q_first[k] == q_first[k + 1] : !by_wave) continue;
+            per_wave[k] = k < 4 ? mtrc_align((size_t)lane_len * (size_t)mdp_dwords(l_umax[k]) * 256, 256) : mtrc_align(wave_cells + 256, 256);
+            const int64_t items = k < 4 ? tasks / 64 + (int64_t)(q_first[k + 1] - q_first[k]) * MLO_N_CLASSES : tasks;      // (a bound: the groups are counted on the device)
+            size_t total = 0;
+            waves[k] = pick_waves(ctx, (int)std::min<int64_t>(items, INT32_MAX), k < 4 ? 16 : 8, per_wave[k], &total);
+            scratch = std::max(scratch, total);
+        }
+        { mtr_status s = ensure_scratch(ctx, scratch); if (s != MTR_OK) return s; }
+        a.scratch = ctx->d_scratch;
+        if (nb > 0) HIPCHK(hipMemsetAsync(a.hist, 0, nb * 4, ctx->stream));
+        HIPCHK(hipMemsetAsync(ctx->d_ml_counter, 0, 5 * 8, ctx->stream));
+        HIPCHK(hipMemsetAsync(a.state + LOCI_NEXT, 0, (LOCI_STATE - LOCI_NEXT) * 4, ctx->stream));
+        const dim3 per_task((unsigned)((nt + 255) / 256)), b256(256);
+        hipLaunchKernelGGL(mtr_k_loci_bin, per_task, b256, 0, ctx->stream, a);
+        if (nb > 0) {
+            hipLaunchKernelGGL(mtr_k_loci_groups, dim3((unsigned)((nb + 255) / 256)), b256, 0, ctx->stream, (const int32_t *)a.hist, (int32_t)nb, a.groups);
+            hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.hist, (int64_t)nb, a.tfirst);
+            hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.groups, (int64_t)nb, a.gfirst);
+            hipLaunchKernelGGL(mtr_k_loci_scatter, per_task, b256, 0, ctx->stream, a);
+        }
+        HIPCHK(hipGetLastError());
+        for (int k = 0; k < 5; k++) {
+            if (waves[k] == 0) continue;
+            a.counter = (unsigned long long *)ctx->d_ml_counter + k; a.scratch_per_wave = per_wave[k]; a.cells_cap = k < 4 ? 0 : wave_cells;
+            if (k < 4) { a.bin0 = q_first[k] * MLO_N_CLASSES; a.bin1 = q_first[k + 1] * MLO_N_CLASSES; }
+            DBG("search_motif_loci: round %d, %lld intervals of at most %d bases, launch %d: %d wavefronts of %zu bytes", d, (long long)N, max_len, k, waves[k], per_wave[k]);
+            const dim3 grid((unsigned)waves[k]), block(64);
+            if (k == 0) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<4>, grid, block, 0, ctx->stream, a);
+            else if (k == 1) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<8>, grid, block, 0, ctx->stream, a);
+            else if (k == 2) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<16>, grid, block, 0, ctx->stream, a);
+            else if (k == 3) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<32>, grid, block, 0, ctx->stream, a);
+            else hipLaunchKernelGGL(mtr_k_motif_loci_waves, grid, block, 0, ctx->stream, a);
+            HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(mtr_k_loci_split, dim3((unsigned)((N + 255) / 256)), b256, 0, ctx->stream, a, min_score, (int32_t)minlen, max_rounds, (int32_t)d,
+                           next, (int32_t)std::min<int64_t>(2 * N, INT32_MAX), (int32_t *)ctx->d_ml_hits, (int32_t)(T + N), (uint8_t *)ctx->d_ml_open);
+        HIPCHK(hipGetLastError());
+        // the round's one look at the device: its verdict, the loci so far, the next round's intervals and their longest
+        int32_t st[LOCI_STATE];
+        HIPCHK(copy_sync(ctx, st, ctx->d_ml_state, sizeof st, hipMemcpyDeviceToHost));
+        if (st[LOCI_STATUS] == DEV_ERR_DP_TOO_LARGE) { ctx->err = "You need to increse the value of WrapDPsize. (a DP of the locus search exceeded it or its scratch)"; return MTR_ERR_DP_TOO_LARGE; }
+        if (st[LOCI_STATUS] != DEV_OK) { ctx->err = "the locus search failed on the device (status " + std::to_string(st[LOCI_STATUS]) + ", round " + std::to_string(d) + ")"; return MTR_ERR_HIP; }
+        if (st[LOCI_HITS] < T || st[LOCI_HITS] > T + N || st[LOCI_NEXT] < 0 || st[LOCI_NEXT] > 2 * N || st[LOCI_MAXLEN] > max_len) { ctx->err = "the locus search's lists are inconsistent"; return MTR_ERR_HIP; }
+        T = st[LOCI_HITS]; N = st[LOCI_NEXT]; max_len = st[LOCI_MAXLEN];
+    }
+    // the finish: per pair its loci counted, the offsets, every locus at its rank by start
+    const size_t np = (size_t)P, nl = std::max<size_t>((size_t)T, 1);
+    HIPCHK(ctx->d_ml_count.ensure(np * 4)); HIPCHK(ctx->d_ml_off.ensure((np + 1) * 8)); HIPCHK(ctx->d_ml_starts.ensure(nl * 4));
+    HIPCHK(ctx->d_ml_fields.ensure(nl * 32)); HIPCHK(ctx->d_ml_score.ensure(nl * 4)); HIPCHK(ctx->d_ml_ratio.ensure(nl * 4)); HIPCHK(ctx->d_ml_strand.ensure(nl));
+    HIPCHK(hipMemsetAsync(ctx->d_ml_count, 0, np * 4, ctx->stream));
+    const dim3 per_hit((unsigned)((nl + 255) / 256)), b256(256);
+    if (T > 0) hipLaunchKernelGGL(mtr_k_loci_count, per_hit, b256, 0, ctx->stream, (int32_t *)ctx->d_ml_hits, (int32_t)T, (int32_t *)ctx->d_ml_count);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)ctx->d_ml_count, P, (int64_t *)ctx->d_ml_off);
+    if (T > 0) {
+        const MotifLociOut out = { ctx->d_ml_fields, ctx->d_ml_score, ctx->d_ml_ratio, ctx->d_ml_strand };
+        hipLaunchKernelGGL(mtr_k_loci_starts, per_hit, b256, 0, ctx->stream, (const int32_t *)ctx->d_ml_hits, (int32_t)T, (const int64_t *)ctx->d_ml_off, (int32_t *)ctx->d_ml_starts);
+        hipLaunchKernelGGL(mtr_k_loci_place, per_hit, b256, 0, ctx->stream, (const int32_t *)ctx->d_ml_hits, (int32_t)T, (const int64_t *)ctx->d_ml_off,
+                           (const int32_t *)ctx->d_ml_starts, out);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->ml_ready = true; ctx->ml_pairs = P; ctx->ml_loci = T;
+    *out_pairs = P; *out_loci = T;
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_motif_loci_copy_device(mtr_ctx *ctx, const mtr_motif_loci_dst *dst)
+{
+    if (!ctx) return MTR_ERR_BAD_ARG;
+    if (!ctx->ml_ready) { ctx->err = "no loci kept: mtr_search_motif_loci_device comes first (an upload discards what it kept)"; return MTR_ERR_BAD_ARG; }
+    if (!dst) { ctx->err = "dst is NULL"; return MTR_ERR_BAD_ARG; }
+    const int64_t P = ctx->ml_pairs, T = ctx->ml_loci;
+    if (dst->cap_pairs < P || dst->cap_loci < T) {
+        ctx->err = "destination holds " + std::to_string(dst->cap_pairs) + " pairs and " + std::to_string(dst->cap_loci) + " loci, " + std::to_string(P) + " and " + std::to_string(T) + " needed";
+        return MTR_ERR_OVERFLOW;
+    }
+    if (!dst->loci_off || !dst->open || (T > 0 && (!dst->fields || !dst->score || !dst->ratio || !dst->strand))) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
+    const size_t p = (size_t)P, t = (size_t)T;
+    HIPCHK(hipMemcpyAsync(dst->loci_off, ctx->d_ml_off, (p + 1) * 8, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->open, ctx->d_ml_open, p, dd, ctx->stream));
+    if (T > 0) {
+        HIPCHK(hipMemcpyAsync(dst->fields, ctx->d_ml_fields, t * 32, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->score, ctx->d_ml_score, t * 4, dd, ctx->stream));
+        HIPCHK(hipMemcpyAsync(dst->ratio, ctx->d_ml_ratio, t * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->strand, ctx->d_ml_strand, t, dd, ctx->stream));
+    }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
 }

@@ -446,6 +446,73 @@ mtr_status mtr_search_motif_loci_device(mtr_ctx *ctx, const char *motifs, const 
                                         int32_t min_score, int32_t max_rounds, int64_t *out_pairs, int64_t *out_loci);
 mtr_status mtr_motif_loci_copy_device(mtr_ctx *ctx, const mtr_motif_loci_dst *dst);
 
+/* ---- flank search: short patterns matched approximately against every read --------------------------------------------------------------------
+ * Reads carry no coordinates: a locus is named by the unique sequence either side of its repeat.  This call matches every given pattern (a flank,
+ * a primer, an adapter) approximately against every read of the resident batch and reports where it fits best.  The reference has nothing of this
+ * kind; the definition is this project's own.  For a read x[0 .. L) and a pattern p[0 .. m) over ACGT, 1 <= m <= 64, with the unit-cost edit
+ * distance ed (substitution, insertion and deletion cost 1 each):
+ *   d(e)     = min over 0 <= s <= e of ed(p, x[s .. e)), for e = 0 .. L; d(0) = m
+ *   dist     = min over e of d(e)
+ *   end      = the smallest e with d(e) = dist
+ *   start    = the largest s <= end with ed(p, x[s .. end)) = dist: the shortest such substring; end - start <= m + dist
+ *   strands  both_strands != 0: the reverse complement of p is searched as well, the smaller dist wins, the forward pattern wins a tie; strand = 0
+ *            or 1 says which won (a palindromic pattern is always strand 0).  both_strands == 0: strand = 0
+ *   always   a hit is reported for every (read, pattern), without a threshold: the pattern matches x[start .. end) - half-open, end exclusive -
+ *            with dist edits.  A read shorter than the pattern simply has a large dist; dist = m means start = end = 0 (nothing of the read
+ *            helps)
+ * The protocol is mtr_search_motifs_device's: an uploaded batch is needed and a run is not, a run in flight ends first, nothing kept of the batch
+ * is touched (the call has its own status word and counters), patterns / pattern_off are HOST arrays as motifs / motif_off, the columns are
+ * caller-owned DEVICE memory on the context's GPU, hit h = read * n_patterns + pattern, H = n_reads * n_patterns of them.
+ * Checked in this order: MTR_ERR_BAD_ARG (mtr_last_error names the offender) without an uploaded batch, for n_patterns <= 0, a decreasing
+ * pattern_off, a pattern of length 0 or over 64, a byte outside ACGT, H over 2^31 - 1;  then *out_hits = H and, as the report calls: dst == NULL:
+ * MTR_OK with the size only;  cap_hits < H: MTR_ERR_OVERFLOW, nothing written;  a NULL column: MTR_ERR_BAD_ARG;  else the columns are written and
+ * the context's stream synchronised before the call returns. */
+typedef struct mtr_flank_hits_dst {
+    int32_t *dist;     /* [H] */
+    int32_t *start;    /* [H] 0-origin */
+    int32_t *end;      /* [H] 0-origin, exclusive */
+    uint8_t *strand;   /* [H] */
+    int64_t  cap_hits;
+} mtr_flank_hits_dst;   /* caller-owned DEVICE memory; hit h = read * n_patterns + pattern */
+mtr_status mtr_search_flanks_device(mtr_ctx *ctx, const char *patterns, const int64_t *pattern_off, int32_t n_patterns,
+                                    int32_t both_strands, const mtr_flank_hits_dst *dst, int64_t *out_hits);
+
+/* ---- locus genotyping: the repeat between two flanks, counted -------------------------------------------------------------------------------------
+ * "How many copies does this read carry at this locus?"  The motif alone does not identify a locus (a read holds CAG tracts at several places), and
+ * a local alignment's ends do not delimit the allele (they are where the score happened to peak: an interrupted allele is cut short, an allele of 0
+ * or 1 copies is invisible).  A locus is (A, M, B): left flank, motif, right flank; flanks of 1..64 bases, a motif as the search's, 1..499 bases.
+ * The definition, for a read x, a locus (A, M, B), K = max_flank_dist >= 0, the scores G, MM, D of the search, rc = reverse complement, and F(p) =
+ * the flank search's hit of pattern p on ONE strand (both_strands = 0, above):
+ *   orientation 0   a = F(A), b = F(B); valid iff a.dist <= K, b.dist <= K and a.end <= b.start; the window is [a.end, b.start), the motif is M
+ *   orientation 1   a' = F(rc A), b' = F(rc B); valid iff a'.dist <= K, b'.dist <= K and b'.end <= a'.start; the window is [b'.end, a'.start), the
+ *                   motif is rc M
+ *   choice          the read spans the locus in the valid orientation; if both are valid, the one with the smaller sum of its two distances,
+ *                   orientation 0 on a tie; if neither is valid: spanning = 0 and every other column of the row is 0
+ *   flank_dist      (left, right) = (a.dist, b.dist), or (a'.dist, b'.dist): each named by the locus' flank, not by its place in the read
+ *   alignment       window [lo, hi) with lo < hi: the hit of mtr_search_motifs_device's definition, verbatim, for the read x[lo .. hi) against the
+ *                   orientation's motif as given (both_strands = 0), with start and end raised by lo (a window without a positive cell: start = lo,
+ *                   end = lo - 1, zeros elsewhere);  lo == hi, an allele of no copies: spanning = 1, eight zero fields, score 0, ratio 0, and no DP
+ * The allele is hi - lo bases and fields[3] copies.
+ * seqs / seq_off are HOST arrays as motifs / motif_off holding 3 * n_loci sequences: locus l is sequences 3l (left flank), 3l + 1 (motif), 3l + 2
+ * (right flank).  The columns are caller-owned DEVICE memory, row = read * n_loci + locus.  The protocol is the flank search's; the call keeps
+ * nothing and drops nothing the batch keeps.
+ * Checked in this order: MTR_ERR_BAD_ARG without an uploaded batch, for n_loci <= 0, a decreasing seq_off;  the search's checks of the scores and
+ * of the motifs (the message's "motif l" is locus l);  a flank of length 0 or over 64 or with a byte outside ACGT;  max_flank_dist < 0;  more than
+ * 2^30 - 1 rows;  MTR_ERR_DP_TOO_LARGE, decided on the host from the WHOLE reads as the search decides it;  then *out_rows = n_reads * n_loci and
+ * dst as above (cap_rows). */
+typedef struct mtr_genotypes_dst {
+    uint8_t *spanning;     /* [R] */
+    uint8_t *orientation;  /* [R] */
+    int32_t *flank_dist;   /* [R*2] left, right */
+    int32_t *window;       /* [R*2] lo, hi */
+    int32_t *fields;       /* [R*8] start, end, repeat_len, copies, matches, mismatches, insertions, deletions: read coordinates */
+    int32_t *score;        /* [R] */
+    float   *ratio;        /* [R] */
+    int64_t  cap_rows;
+} mtr_genotypes_dst;   /* caller-owned DEVICE memory; row = read * n_loci + locus */
+mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist,
+                                    int32_t gain, int32_t mismatch, int32_t indel, const mtr_genotypes_dst *dst, int64_t *out_rows);
+
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left
  * of handle_one_file.c:281-287's loop across GPUs is ONE exchange: the record tables travel to the process that chains and

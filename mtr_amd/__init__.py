@@ -3,7 +3,8 @@
 Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointers).  Only the device-input and report methods
 (Engine.upload_device / process_device / parse_fasta_device / upload_fasta_device / parse_fastq_device / upload_fastq_device /
 walk_fasta_device / walk_fastq_device /
-export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes / report_motif_tensors / search_motifs / search_motif_loci) take or return torch tensors;
+export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes / report_motif_tensors / search_motifs / search_motif_loci /
+search_flanks / genotype_loci) take or return torch tensors;
 they import torch when called.
 The product path is libmtr_hip.so only: importing works without a GPU, but creating an Engine
 without the library or without a HIP device raises — there is no CPU fallback.
@@ -51,7 +52,7 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_upload_batch_device_in_file", "mtr_upload_fasta_device_in_file", "mtr_file_state_skip_device", "mtr_test_file_tail",
            "mtr_parse_fasta_device_window", "mtr_upload_fasta_device_window", "mtr_parse_fastq_device_window", "mtr_upload_fastq_device_window",
            "mtr_report_motifs_device", "mtr_test_unit_motifs", "mtr_search_motifs_device",
-           "mtr_search_motif_loci_device", "mtr_motif_loci_copy_device"]
+           "mtr_search_motif_loci_device", "mtr_motif_loci_copy_device", "mtr_search_flanks_device", "mtr_genotype_loci_device"]
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
 
@@ -206,6 +207,38 @@ class MotifLoci(NamedTuple):
     open: "object"        # uint8 [n, m]: 1 = max_rounds ended the search of this pair with a window left that could still hold a locus
 
 
+class CFlankHitsDst(C.Structure):
+    """mtr_flank_hits_dst: device pointers of the flank search's columns and their capacity"""
+    _fields_ = [("dist", C.c_void_p), ("start", C.c_void_p), ("end", C.c_void_p), ("strand", C.c_void_p), ("cap_hits", C.c_int64)]
+
+
+class FlankHits(NamedTuple):
+    """What Engine.search_flanks found: one hit per (read, pattern) of n reads and m patterns, all on the engine's device.  include/mtr_hip.h
+    defines every column."""
+    dist: "object"        # int32 [n, m]: the edit distance of the pattern to read[start:end], the smallest over the read
+    start: "object"       # int32 [n, m]: 0-origin
+    end: "object"         # int32 [n, m]: 0-origin, exclusive
+    strand: "object"      # uint8 [n, m]: 0 = the pattern as given, 1 = its reverse complement is nearer
+
+
+class CGenotypesDst(C.Structure):
+    """mtr_genotypes_dst: device pointers of the genotype's columns and their capacity"""
+    _fields_ = [("spanning", C.c_void_p), ("orientation", C.c_void_p), ("flank_dist", C.c_void_p), ("window", C.c_void_p), ("fields", C.c_void_p),
+                ("score", C.c_void_p), ("ratio", C.c_void_p), ("cap_rows", C.c_int64)]
+
+
+class Genotypes(NamedTuple):
+    """What Engine.genotype_loci found: one row per (read, locus) of n reads and m loci, all on the engine's device.  include/mtr_hip.h defines
+    every column.  The allele of a spanning row is window[1] - window[0] bases and fields[3] copies."""
+    spanning: "object"    # uint8 [n, m]: 1 = both flanks found in order; 0 = every other column of the row is 0
+    orientation: "object" # uint8 [n, m]: 0 = the locus as given, 1 = the read is its reverse complement
+    flank_dist: "object"  # int32 [n, m, 2]: the left and the right flank's edit distance
+    window: "object"      # int32 [n, m, 2]: the repeat is read[lo:hi]
+    fields: "object"      # int32 [n, m, 8]: MotifHits' columns for the window against the motif, in read coordinates
+    score: "object"       # int32 [n, m]
+    ratio: "object"       # float32 [n, m]: matches / repeat_len
+
+
 class CFastaInfo(C.Structure):
     """mtr_fasta_info: what a FASTA file in device memory holds"""
     _fields_ = [("n_reads", C.c_int32), ("end", C.c_int32), ("bad_char", C.c_int32), ("reserved", C.c_int32),
@@ -331,6 +364,10 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_search_motif_loci_device.restype = C.c_int
     lib.mtr_motif_loci_copy_device.argtypes = [C.c_void_p, P(CMotifLociDst)]
     lib.mtr_motif_loci_copy_device.restype = C.c_int
+    lib.mtr_search_flanks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, P(CFlankHitsDst), P(C.c_int64)]
+    lib.mtr_search_flanks_device.restype = C.c_int
+    lib.mtr_genotype_loci_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [P(CGenotypesDst), P(C.c_int64)]
+    lib.mtr_genotype_loci_device.restype = C.c_int
     lib.mtr_parse_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaDst), P(CFastaInfo)]
     lib.mtr_parse_fasta_device.restype = C.c_int
     lib.mtr_upload_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaInfo)]
@@ -834,6 +871,58 @@ class Engine:
         self._check(self.lib.mtr_motif_loci_copy_device(self.h, C.byref(dst)), "mtr_motif_loci_copy_device")
         return loci
 
+    def search_flanks(self, patterns, both_strands: bool = True) -> FlankHits:
+        """Flank search (mtr_search_flanks_device): every pattern - a sequence of str or bytes over upper-case ACGT, 1..64 bases each - matched
+        approximately (unit-cost edit distance) against every read of the uploaded batch, on both strands unless both_strands is false: the
+        nearest substring of the read, the leftmost end and then the shortest on ties.  Needs no run and changes nothing a run left.  Returns
+        a FlankHits of fresh tensors on this engine's device; follows search_motifs' stream handling."""
+        import torch
+
+        if isinstance(patterns, (str, bytes, bytearray)) or not hasattr(patterns, "__len__"):
+            raise MtrError(f"patterns must be a sequence of str or bytes, got {type(patterns).__name__}")
+        data, off = pack_ids(patterns)
+        m = len(patterns)
+        args = (self.h, data.ctypes.data, off.ctypes.data, m, 1 if both_strands else 0)
+        nh = C.c_int64()
+        self._check(self.lib.mtr_search_flanks_device(*args, None, C.byref(nh)), "mtr_search_flanks_device")
+        H = int(nh.value)
+        n = H // m
+        dev = torch.device("cuda", self.device)
+        hits = FlankHits(*[torch.empty((n, m), dtype=torch.int32, device=dev) for _ in range(3)], torch.empty((n, m), dtype=torch.uint8, device=dev))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CFlankHitsDst(*[t.data_ptr() for t in hits], H)
+        self._check(self.lib.mtr_search_flanks_device(*args, C.byref(dst), C.byref(nh)), "mtr_search_flanks_device")
+        return hits
+
+    def genotype_loci(self, loci, max_flank_dist: int, gain: int = 1, mismatch: int = 1, indel: int = 1) -> Genotypes:
+        """Locus genotyping (mtr_genotype_loci_device): loci is a sequence of (left_flank, motif, right_flank), each str or bytes over upper-case
+        ACGT - flanks of 1..64 bases, a motif of 1..499.  A read spans a locus where both flanks are found within max_flank_dist edits and in
+        order, on either strand; the bases between them are aligned to the motif by search_motifs' DP with the given scores.  Needs no run and
+        changes nothing a run left.  Returns a Genotypes of fresh tensors on this engine's device; follows search_motifs' stream handling."""
+        import torch
+
+        if isinstance(loci, (str, bytes, bytearray)) or not hasattr(loci, "__len__"):
+            raise MtrError(f"loci must be a sequence of (left_flank, motif, right_flank), got {type(loci).__name__}")
+        flat = []
+        for k, locus in enumerate(loci):
+            if isinstance(locus, (str, bytes, bytearray)) or not hasattr(locus, "__len__") or len(locus) != 3:
+                raise MtrError(f"locus {k} must be (left_flank, motif, right_flank)")
+            flat.extend(locus)
+        data, off = pack_ids(flat)
+        m = len(loci)
+        args = (self.h, data.ctypes.data, off.ctypes.data, m, int(max_flank_dist), int(gain), int(mismatch), int(indel))
+        nr = C.c_int64()
+        self._check(self.lib.mtr_genotype_loci_device(*args, None, C.byref(nr)), "mtr_genotype_loci_device")
+        R = int(nr.value)
+        n = R // m
+        dev = torch.device("cuda", self.device)
+        new = lambda dtype, *tail: torch.empty((n, m) + tail, dtype=dtype, device=dev)     # noqa: E731
+        gt = Genotypes(new(torch.uint8), new(torch.uint8), new(torch.int32, 2), new(torch.int32, 2), new(torch.int32, 8), new(torch.int32), new(torch.float32))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CGenotypesDst(*[t.data_ptr() for t in gt], R)
+        self._check(self.lib.mtr_genotype_loci_device(*args, C.byref(dst), C.byref(nr)), "mtr_genotype_loci_device")
+        return gt
+
     def test_unit_motifs(self, units, read=None, copies=None, repeat_len=None, table_slots: int = 0) -> ReportMotifs:
         """mtr_test_unit_motifs: the kernels of report_motif_tensors on caller-given units, one bytes (or str) per unit.  read: the read of
         each unit, non-decreasing (default: every unit a read of its own); copies: num_freq_unit (default 1); repeat_len (default: the
@@ -1228,6 +1317,59 @@ def format_motif_loci(ids, lens, motifs, loci: MotifLoci, min_ratio: float = 0.0
             cols = [str(int(lens[r])), str(f[0] + 1), str(f[1] + 1), str(f[2]), str(len(bmot[k])), str(f[3]), str(f[4]), _c_float_text(ratio[t]),
                     str(f[5]), str(f[6]), str(f[7])]
             out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + shown[k][int(strand[t])] + b"\n")
+    return b"".join(out)
+
+
+def format_flank_hits(ids, lens, patterns, hits: FlankHits, max_dist: "int | None" = None) -> bytes:
+    """The hits of Engine.search_flanks as text, one tab-separated line per kept hit: ID, L, pattern index, strand, dist, start + 1 (1-origin),
+    end (1-origin, inclusive; an empty match prints start + 1 and end one below it), the pattern's length, and the pattern as matched - its
+    reverse complement for strand 1.  Reads in input order, patterns in the given order within a read.  Kept: dist <= max_dist (None: all).
+    ids, lens: per read its ID (str or bytes) and length; patterns: what search_flanks was given; hits: its result (tensors or numpy)."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    bpat = [v.encode() if isinstance(v, str) else bytes(v) for v in patterns]
+    bid = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+    n, m = len(bid), len(bpat)
+    dist, start, end, strand = (host(t).reshape(n, m) for t in hits)
+    if len(lens) != n:
+        raise MtrError(f"{len(lens)} lengths for {n} ids")
+    shown = [(b, b.translate(_COMPLEMENT)[::-1]) for b in bpat]
+    out = []
+    for r in range(n):
+        for k in range(m):
+            if max_dist is not None and int(dist[r, k]) > max_dist:
+                continue
+            cols = [str(int(lens[r])), str(k), str(int(strand[r, k])), str(int(dist[r, k])), str(int(start[r, k]) + 1), str(int(end[r, k])), str(len(bpat[k]))]
+            out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + shown[k][int(strand[r, k])] + b"\n")
+    return b"".join(out)
+
+
+def format_genotypes(ids, lens, loci, gt: Genotypes) -> bytes:
+    """The rows of Engine.genotype_loci as text, one tab-separated line per SPANNING (read, locus): ID, L, locus index, orientation, the left
+    and the right flank's distance, the window's start (1-origin) and end (inclusive), the allele's length in bases, copies, matches, ratio (%f
+    of the float), mismatches, insertions, deletions, and the motif as aligned - its reverse complement for orientation 1.  Reads in input
+    order, loci in the given order within a read.
+    ids, lens: per read its ID (str or bytes) and length; loci: what genotype_loci was given; gt: its result (tensors or numpy)."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    bmot = [v[1].encode() if isinstance(v[1], str) else bytes(v[1]) for v in loci]
+    bid = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+    n, m = len(bid), len(bmot)
+    spanning, orientation = host(gt.spanning).reshape(n, m), host(gt.orientation).reshape(n, m)
+    fdist, window, fields = host(gt.flank_dist).reshape(n, m, 2), host(gt.window).reshape(n, m, 2), host(gt.fields).reshape(n, m, 8)
+    ratio = host(gt.ratio).astype(np.float32).reshape(n, m)
+    if len(lens) != n:
+        raise MtrError(f"{len(lens)} lengths for {n} ids")
+    shown = [(b, b.translate(_COMPLEMENT)[::-1]) for b in bmot]
+    out = []
+    for r, k in zip(*np.nonzero(spanning)):
+        f = [int(v) for v in fields[r, k]]
+        lo, hi = int(window[r, k, 0]), int(window[r, k, 1])
+        cols = [str(int(lens[r])), str(k), str(int(orientation[r, k])), str(int(fdist[r, k, 0])), str(int(fdist[r, k, 1])), str(lo + 1), str(hi), str(hi - lo),
+                str(f[3]), str(f[4]), _c_float_text(ratio[r, k]), str(f[5]), str(f[6]), str(f[7])]
+        out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + shown[k][int(orientation[r, k])] + b"\n")
     return b"".join(out)
 
 

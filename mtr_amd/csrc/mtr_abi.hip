@@ -40,6 +40,8 @@
 #include "report_motif.hip.inc"
 #include "motif_search.hip.inc"
 #include "motif_loci.hip.inc"
+#include "flank_search.hip.inc"
+#include "genotype.hip.inc"
 #include "fasta.hip.inc"
 #include "fastq.hip.inc"
 #include "file_order.hip.inc"
@@ -77,7 +79,7 @@ template <typename T> using PinnedBuf = GrowBuf<T, true>;
 // that size scratch or run DPs of their own; MTR_DEBUG (dbg) and MTR_TEST_WRAP_DP_SIZE (mtr_create) are read where they act.
 struct RunSwitches {
     bool staged, two_pass_set, test_caps_set, walk_screen;
-    int two_pass, pass_shuffle, service_wpc, select_wpc, polish_wpc, rev_wpc, waves_per_cu, dp16_max_rows, test_flags, motif_lane_max, motif_lane_rows;
+    int two_pass, pass_shuffle, service_wpc, select_wpc, polish_wpc, rev_wpc, waves_per_cu, dp16_max_rows, test_flags, motif_lane_max, motif_lane_rows, flank_word;
     int32_t trace_mask; long quad_min; long long two_pass_long_min; double scratch_max_gb;
     std::string test_caps;
 };
@@ -105,6 +107,7 @@ static void read_switches(RunSwitches &w)
     w.walk_screen = (e = getenv("MTR_TEST_WALK_SCREEN")) ? atoi(e) != 0 : true;     // tests: 0 = no dead-range screen, every range is an item of mtr_k_walks
     w.motif_lane_max = (e = getenv("MTR_TEST_MOTIF_LANE_MAX")) ? std::min(std::max(atoi(e), 0), MDP_MAX_U) : MS_LANE_MAX_U;   // tests: the longest motif of the search's lane path (0: none)
     w.motif_lane_rows = (e = getenv("MTR_TEST_MOTIF_LANE_ROWS")) ? std::min(std::max(atoi(e), 0), MS_LANE_ROWS) : MS_LANE_ROWS;   // tests: the longest read of it
+    w.flank_word = (e = getenv("MTR_TEST_FLANK_WORD")) ? atoi(e) : 0;               // tests: 64 = every pattern of the flank search through the 64-bit scan
 }
 
 // The staged chain's buffers: fixed capacities per batch (staged_plan), grow-only like the others
@@ -221,6 +224,13 @@ struct mtr_ctx {
     DevBuf<int32_t> d_ml_i32, d_ml_bin32, d_ml_task32, d_ml_res, d_ml_hits, d_ml_state, d_ml_count, d_ml_starts; DevBuf<int64_t> d_ml_i64, d_ml_bin64;
     DevBuf<LociIv> d_ml_iv[2]; DevBuf<uint8_t> d_ml_units; DevBuf<unsigned long long> d_ml_counter;
     DevBuf<int64_t> d_ml_off; DevBuf<int32_t> d_ml_fields, d_ml_score; DevBuf<float> d_ml_ratio; DevBuf<uint8_t> d_ml_strand, d_ml_open;
+    // flank search (mtr_search_flanks_device), per call: the order, the slots' lengths and work lists, the slots' masks, the tasks' results (per
+    // slot: the genotype pairs them before a strand is picked), its own status word and item counters
+    DevBuf<int32_t> d_fl_i32, d_fl_res, d_fl_status; DevBuf<int64_t> d_fl_i64; DevBuf<unsigned long long> d_fl_counter;
+    // locus genotyping (mtr_genotype_loci_device), per call and nothing kept: the pairs, their intervals, and one round of the locus search's
+    // arrays - buffers of its own, so that what the locus search keeps (ml_ready) stays
+    DevBuf<int32_t> d_gt_pair, d_gt_i32, d_gt_bin32, d_gt_task32, d_gt_res, d_gt_state; DevBuf<int64_t> d_gt_i64, d_gt_bin64;
+    DevBuf<LociIv> d_gt_iv; DevBuf<uint8_t> d_gt_units; DevBuf<unsigned long long> d_gt_counter;
     long long wrap_dp_size = MTRC_WRAP_DP_SIZE;          // the WrapDPsize the kernels of this context's device test (MTR_TEST_WRAP_DP_SIZE)
     // a FASTA file in device memory (fasta.hip.inc), per call: the tiles' columns, the header windows' columns, the IDs' offsets, the stop, the sizes
     DevBuf<uint32_t> d_fa_tiles, d_fa_hbase; DevBuf<int32_t> d_fa_hpos, d_fa_hidlen; DevBuf<int64_t> d_fa_idoff;
@@ -2158,6 +2168,81 @@ static hipError_t grow_keeping(mtr_ctx *ctx, DevBuf<T> &b, size_t keep, size_t b
     return e;
 }
 
+// the lane slots of S slots, numbered bucket by bucket: bucket k's bins are q_first[k] * MLO_N_CLASSES .. q_first[k + 1] * MLO_N_CLASSES
+struct LaneSlots {
+    std::vector<int32_t> slot_q, q_slot;
+    int q_first[5] = { 0, 0, 0, 0, 0 }, l_umax[4] = { 0, 0, 0, 0 }, u_all = 0, u_wave = 0;      // u_wave: the longest motif no lane takes
+};
+static LaneSlots lane_slots(const std::vector<int32_t> &unit_off, int S, int lane_max)
+{
+    static const int bucket_ub[4] = { 4, 8, 16, 32 };
+    LaneSlots ls;
+    ls.slot_q.assign((size_t)S, -1);
+    for (int k = 0; k < 4; k++) {
+        ls.q_first[k] = (int)ls.q_slot.size();
+        for (int slot = 0; slot < S; slot++) {
+            const int U = unit_off[(size_t)slot + 1] - unit_off[(size_t)slot];
+            if (U > lane_max || mdp_bucket(U) != bucket_ub[k]) continue;
+            ls.slot_q[(size_t)slot] = (int32_t)ls.q_slot.size(); ls.q_slot.push_back(slot); ls.l_umax[k] = std::max(ls.l_umax[k], U);
+        }
+    }
+    ls.q_first[4] = (int)ls.q_slot.size();
+    for (int slot = 0; slot < S; slot++) {
+        const int U = unit_off[(size_t)slot + 1] - unit_off[(size_t)slot];
+        ls.u_all = std::max(ls.u_all, U);
+        if (ls.slot_q[(size_t)slot] < 0) ls.u_wave = std::max(ls.u_wave, U);
+    }
+    return ls;
+}
+
+// One round's alignments: `tasks` tasks over a.iv (a.n_iv intervals of at most max_len bases), everything of `a` set but what one launch has of
+// its own.  Sizes the launches' wavefronts and scratch as the search does - lanes hold rows x dwords x 64 lanes of cells, a wave wavefront one
+// code matrix - then bins the tasks and enqueues the up to five DP launches.  counters: five item counters.  who: the caller, for MTR_DEBUG.
+static mtr_status loci_round(mtr_ctx *ctx, LociArgs &a, const LaneSlots &ls, int64_t tasks, int max_len, unsigned long long *counters, const char *who, int round)
+{
+    const int lane_rows = a.lane_rows;
+    const size_t nb = (size_t)a.n_bins, nt = (size_t)tasks;
+    const int lane_len = std::min(max_len, lane_rows);
+    const bool by_wave = ls.u_wave > 0 || max_len > lane_rows;
+    const size_t wave_cells = (size_t)max_len * (size_t)((max_len > lane_rows ? ls.u_all : ls.u_wave) + 1);
+    size_t per_wave[5] = { 0 }, scratch = 0; int waves[5] = { 0 };
+    for (int k = 0; k < 5; k++) {
+        if (k < 4 ? ls.q_first[k] == ls.q_first[k + 1] : !by_wave) continue;
+        per_wave[k] = k < 4 ? mtrc_align((size_t)lane_len * (size_t)mdp_dwords(ls.l_umax[k]) * 256, 256) : mtrc_align(wave_cells + 256, 256);
+        const int64_t items = k < 4 ? tasks / 64 + (int64_t)(ls.q_first[k + 1] - ls.q_first[k]) * MLO_N_CLASSES : tasks;      // (a bound: the groups are counted on the device)
+        size_t total = 0;
+        waves[k] = pick_waves(ctx, (int)std::min<int64_t>(items, INT32_MAX), k < 4 ? 16 : 8, per_wave[k], &total);
+        scratch = std::max(scratch, total);
+    }
+    { mtr_status s = ensure_scratch(ctx, scratch); if (s != MTR_OK) return s; }
+    a.scratch = ctx->d_scratch;
+    if (nb > 0) HIPCHK(hipMemsetAsync(a.hist, 0, nb * 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(counters, 0, 5 * 8, ctx->stream));
+    const dim3 per_task((unsigned)((nt + 255) / 256)), b256(256);
+    hipLaunchKernelGGL(mtr_k_loci_bin, per_task, b256, 0, ctx->stream, a);
+    if (nb > 0) {
+        hipLaunchKernelGGL(mtr_k_loci_groups, dim3((unsigned)((nb + 255) / 256)), b256, 0, ctx->stream, (const int32_t *)a.hist, (int32_t)nb, a.groups);
+        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.hist, (int64_t)nb, a.tfirst);
+        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.groups, (int64_t)nb, a.gfirst);
+        hipLaunchKernelGGL(mtr_k_loci_scatter, per_task, b256, 0, ctx->stream, a);
+    }
+    HIPCHK(hipGetLastError());
+    for (int k = 0; k < 5; k++) {
+        if (waves[k] == 0) continue;
+        a.counter = counters + k; a.scratch_per_wave = per_wave[k]; a.cells_cap = k < 4 ? 0 : wave_cells;
+        if (k < 4) { a.bin0 = ls.q_first[k] * MLO_N_CLASSES; a.bin1 = ls.q_first[k + 1] * MLO_N_CLASSES; }
+        DBG("%s: round %d, %lld intervals of at most %d bases, launch %d: %d wavefronts of %zu bytes", who, round, (long long)a.n_iv, max_len, k, waves[k], per_wave[k]);
+        const dim3 grid((unsigned)waves[k]), block(64);
+        if (k == 0) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<4>, grid, block, 0, ctx->stream, a);
+        else if (k == 1) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<8>, grid, block, 0, ctx->stream, a);
+        else if (k == 2) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<16>, grid, block, 0, ctx->stream, a);
+        else if (k == 3) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<32>, grid, block, 0, ctx->stream, a);
+        else hipLaunchKernelGGL(mtr_k_motif_loci_waves, grid, block, 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    return MTR_OK;
+}
+
 extern "C" mtr_status mtr_search_motif_loci_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs, int32_t gain, int32_t mismatch,
                                                    int32_t indel, int32_t both_strands, int32_t min_score, int32_t max_rounds, int64_t *out_pairs, int64_t *out_loci)
 {
@@ -2176,24 +2261,8 @@ extern "C" mtr_status mtr_search_motif_loci_device(mtr_ctx *ctx, const char *mot
     const int64_t P = (int64_t)n * n_motifs;
     std::vector<uint8_t> units; std::vector<int32_t> unit_off; std::vector<uint64_t> bits;
     motif_slots(motifs, motif_off, n_motifs, ns, units, unit_off, bits);
-    // the lane slots, numbered bucket by bucket: bucket k's bins are q_first[k] * MLO_N_CLASSES .. q_first[k + 1] * MLO_N_CLASSES
-    static const int bucket_ub[4] = { 4, 8, 16, 32 };
-    std::vector<int32_t> slot_q((size_t)S, -1), q_slot;
-    int q_first[5] = { 0, 0, 0, 0, 0 }, l_umax[4] = { 0, 0, 0, 0 }, u_all = 0, u_wave = 0;      // u_wave: the longest motif no lane takes
-    for (int k = 0; k < 4; k++) {
-        q_first[k] = (int)q_slot.size();
-        for (int slot = 0; slot < S; slot++) {
-            const int U = unit_off[(size_t)slot + 1] - unit_off[(size_t)slot];
-            if (U > lane_max || mdp_bucket(U) != bucket_ub[k]) continue;
-            slot_q[(size_t)slot] = (int32_t)q_slot.size(); q_slot.push_back(slot); l_umax[k] = std::max(l_umax[k], U);
-        }
-    }
-    q_first[4] = (int)q_slot.size();
-    for (int slot = 0; slot < S; slot++) {
-        const int U = unit_off[(size_t)slot + 1] - unit_off[(size_t)slot];
-        u_all = std::max(u_all, U);
-        if (slot_q[(size_t)slot] < 0) u_wave = std::max(u_wave, U);
-    }
+    const LaneSlots ls = lane_slots(unit_off, S, lane_max);
+    const std::vector<int32_t> &slot_q = ls.slot_q, &q_slot = ls.q_slot;
     const size_t sS = (size_t)S, nq = q_slot.size();
     if ((int64_t)nq * MLO_N_CLASSES > (int64_t)INT32_MAX) { ctx->err = std::to_string(nq) + " short motifs are more than the bins take"; return MTR_ERR_OVERFLOW; }
     const size_t nb = nq * MLO_N_CLASSES;
@@ -2233,46 +2302,9 @@ extern "C" mtr_status mtr_search_motif_loci_device(mtr_ctx *ctx, const char *mot
         }
         a.iv = ctx->d_ml_iv[d & 1]; a.n_iv = (int32_t)N;
         a.tbin = ctx->d_ml_task32; a.trank = a.tbin + nt; a.sorted = a.trank + nt; a.wlist = a.sorted + nt; a.res = ctx->d_ml_res;
-        // the launches' wavefronts and scratch, as the search's: lanes hold rows x dwords x 64 lanes of cells, a wave wavefront one code matrix
-        const int lane_len = std::min(max_len, lane_rows);
-        const bool by_wave = u_wave > 0 || max_len > lane_rows;
-        const size_t wave_cells = (size_t)max_len * (size_t)((max_len > lane_rows ? u_all : u_wave) + 1);
-        size_t per_wave[5] = { 0 }, scratch = 0; int waves[5] = { 0 };
-        for (int k = 0; k < 5; k++) {
-            if (k < 4 ? q_first[k] == q_first[k + 1] : !by_wave) continue;
-            per_wave[k] = k < 4 ? mtrc_align((size_t)lane_len * (size_t)mdp_dwords(l_umax[k]) * 256, 256) : mtrc_align(wave_cells + 256, 256);
-            const int64_t items = k < 4 ? tasks / 64 + (int64_t)(q_first[k + 1] - q_first[k]) * MLO_N_CLASSES : tasks;      // (a bound: the groups are counted on the device)
-            size_t total = 0;
-            waves[k] = pick_waves(ctx, (int)std::min<int64_t>(items, INT32_MAX), k < 4 ? 16 : 8, per_wave[k], &total);
-            scratch = std::max(scratch, total);
-        }
-        { mtr_status s = ensure_scratch(ctx, scratch); if (s != MTR_OK) return s; }
-        a.scratch = ctx->d_scratch;
-        if (nb > 0) HIPCHK(hipMemsetAsync(a.hist, 0, nb * 4, ctx->stream));
-        HIPCHK(hipMemsetAsync(ctx->d_ml_counter, 0, 5 * 8, ctx->stream));
         HIPCHK(hipMemsetAsync(a.state + LOCI_NEXT, 0, (LOCI_STATE - LOCI_NEXT) * 4, ctx->stream));
-        const dim3 per_task((unsigned)((nt + 255) / 256)), b256(256);
-        hipLaunchKernelGGL(mtr_k_loci_bin, per_task, b256, 0, ctx->stream, a);
-        if (nb > 0) {
-            hipLaunchKernelGGL(mtr_k_loci_groups, dim3((unsigned)((nb + 255) / 256)), b256, 0, ctx->stream, (const int32_t *)a.hist, (int32_t)nb, a.groups);
-            hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.hist, (int64_t)nb, a.tfirst);
-            hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.groups, (int64_t)nb, a.gfirst);
-            hipLaunchKernelGGL(mtr_k_loci_scatter, per_task, b256, 0, ctx->stream, a);
-        }
-        HIPCHK(hipGetLastError());
-        for (int k = 0; k < 5; k++) {
-            if (waves[k] == 0) continue;
-            a.counter = (unsigned long long *)ctx->d_ml_counter + k; a.scratch_per_wave = per_wave[k]; a.cells_cap = k < 4 ? 0 : wave_cells;
-            if (k < 4) { a.bin0 = q_first[k] * MLO_N_CLASSES; a.bin1 = q_first[k + 1] * MLO_N_CLASSES; }
-            DBG("search_motif_loci: round %d, %lld intervals of at most %d bases, launch %d: %d wavefronts of %zu bytes", d, (long long)N, max_len, k, waves[k], per_wave[k]);
-            const dim3 grid((unsigned)waves[k]), block(64);
-            if (k == 0) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<4>, grid, block, 0, ctx->stream, a);
-            else if (k == 1) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<8>, grid, block, 0, ctx->stream, a);
-            else if (k == 2) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<16>, grid, block, 0, ctx->stream, a);
-            else if (k == 3) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<32>, grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL(mtr_k_motif_loci_waves, grid, block, 0, ctx->stream, a);
-            HIPCHK(hipGetLastError());
-        }
+        { mtr_status s = loci_round(ctx, a, ls, tasks, max_len, (unsigned long long *)ctx->d_ml_counter, "search_motif_loci", d); if (s != MTR_OK) return s; }
+        const dim3 b256(256);
         hipLaunchKernelGGL(mtr_k_loci_split, dim3((unsigned)((N + 255) / 256)), b256, 0, ctx->stream, a, min_score, (int32_t)minlen, max_rounds, (int32_t)d,
                            next, (int32_t)std::min<int64_t>(2 * N, INT32_MAX), (int32_t *)ctx->d_ml_hits, (int32_t)(T + N), (uint8_t *)ctx->d_ml_open);
         HIPCHK(hipGetLastError());
@@ -2324,6 +2356,220 @@ extern "C" mtr_status mtr_motif_loci_copy_device(mtr_ctx *ctx, const mtr_motif_l
         HIPCHK(hipMemcpyAsync(dst->fields, ctx->d_ml_fields, t * 32, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->score, ctx->d_ml_score, t * 4, dd, ctx->stream));
         HIPCHK(hipMemcpyAsync(dst->ratio, ctx->d_ml_ratio, t * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->strand, ctx->d_ml_strand, t, dd, ctx->stream));
     }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- flank search (flank_search.hip.inc) --------------------------------------------------------------------------------------------
+// As the known-motif search: only the lengths decide the work - one argsort per call, the slots' masks and at most two work lists go up (one per
+// word width), nothing comes back but the status word.  No scratch at all.
+// a pattern of 1 .. FBV_MAX_M bases over ACGT, as codes; what: how the reason names it
+static mtr_status flank_pattern(mtr_ctx *ctx, const char *s, int64_t len, const std::string &what, std::vector<uint8_t> &codes)
+{
+    if (len < 1 || len > FBV_MAX_M) { ctx->err = what + ": length " + std::to_string(len) + " outside 1.." + std::to_string(FBV_MAX_M); return MTR_ERR_BAD_ARG; }
+    codes.resize((size_t)len);
+    for (int64_t t = 0; t < len; t++) {
+        const char c = s[t];
+        if (c != 'A' && c != 'C' && c != 'G' && c != 'T') { ctx->err = what + ": byte " + std::to_string((int)(unsigned char)c) + " at " + std::to_string(t) + " is none of ACGT"; return MTR_ERR_BAD_ARG; }
+        codes[(size_t)t] = (uint8_t)(c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : 3);
+    }
+    return MTR_OK;
+}
+static std::vector<uint8_t> revcomp_codes(const std::vector<uint8_t> &c)
+{
+    std::vector<uint8_t> r(c.size());
+    for (size_t t = 0; t < c.size(); t++) r[t] = (uint8_t)(3 - c[c.size() - 1 - t]);
+    return r;
+}
+
+// every slot's pattern against every read: ctx->d_fl_res[read * S + slot][FL_RES], complete when this returns
+static mtr_status flank_scan(mtr_ctx *ctx, const std::vector<std::vector<uint8_t>> &pat)
+{
+    const int n = ctx->n_reads;
+    const size_t S = pat.size(), nr = (size_t)n;
+    std::vector<int32_t> order(nr);
+    for (int i = 0; i < n; i++) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return ctx->lens[(size_t)x] > ctx->lens[(size_t)y]; });
+    // the work lists: groups of 64 reads of the order per slot, the slots by the word their pattern needs
+    std::vector<uint64_t> masks(S * FL_MASKS); std::vector<int32_t> plen(S);
+    std::vector<int32_t> l_slot[2]; std::vector<int64_t> l_first[2];
+    const int64_t groups = ((int64_t)n + 63) / 64;
+    for (int k = 0; k < 2; k++) l_first[k].push_back(0);
+    for (size_t slot = 0; slot < S; slot++) {
+        const int m = (int)pat[slot].size();
+        const FbvMasks<uint64_t> eq = fbv_masks<uint64_t>(pat[slot].data(), m, 0), rev = fbv_masks<uint64_t>(pat[slot].data(), m, 1);     // (the 32-bit masks are their low halves)
+        const uint64_t v[FL_MASKS] = { eq.a, eq.c, eq.g, eq.t, rev.a, rev.c, rev.g, rev.t };
+        std::copy(v, v + FL_MASKS, masks.begin() + (ptrdiff_t)(slot * FL_MASKS));
+        plen[slot] = m;
+        const int k = m <= 32 && ctx->sw.flank_word != 64 ? 0 : 1;
+        l_slot[k].push_back((int32_t)slot); l_first[k].push_back(l_first[k].back() + groups);
+    }
+    // device copies: d_fl_i32 = order | plen | the lists' slots, d_fl_i64 = masks | the lists' firsts
+    HIPCHK(ctx->d_fl_i32.ensure((nr + 3 * S) * 4)); HIPCHK(ctx->d_fl_i64.ensure((S * FL_MASKS + 2 * (S + 1)) * 8));
+    HIPCHK(ctx->d_fl_res.ensure(nr * S * FL_RES * 4)); HIPCHK(ctx->d_fl_status.ensure(4)); HIPCHK(ctx->d_fl_counter.ensure(2 * 8));
+    int32_t *d_order = ctx->d_fl_i32, *d_plen = d_order + nr, *d_slots = d_plen + S;
+    int64_t *d_masks = ctx->d_fl_i64, *d_firsts = d_masks + S * FL_MASKS;
+    HIPCHK(copy_sync(ctx, d_order, order.data(), nr * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_plen, plen.data(), S * 4, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, d_masks, masks.data(), S * FL_MASKS * 8, hipMemcpyHostToDevice));
+    for (int k = 0; k < 2; k++) {
+        if (l_slot[k].empty()) continue;
+        HIPCHK(copy_sync(ctx, d_slots + (size_t)k * S, l_slot[k].data(), l_slot[k].size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(copy_sync(ctx, d_firsts + (size_t)k * (S + 1), l_first[k].data(), l_first[k].size() * 8, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemsetAsync(ctx->d_fl_status, 0, 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_fl_counter, 0, 2 * 8, ctx->stream));
+    FlankArgs a{};
+    a.b.packed = ctx->d_packed; a.b.woff = ctx->d_woff; a.b.lens = ctx->d_lens; a.b.order = d_order; a.b.n_reads = n;
+    a.order = d_order; a.n_reads = n; a.n_slots = (int32_t)S; a.masks = (const uint64_t *)d_masks; a.plen = d_plen; a.res = ctx->d_fl_res; a.status = ctx->d_fl_status;
+    for (int k = 0; k < 2; k++) {
+        if (l_slot[k].empty()) continue;
+        a.work = { d_slots + (size_t)k * S, d_firsts + (size_t)k * (S + 1), (int32_t)l_slot[k].size(), l_first[k].back() };
+        a.counter = (unsigned long long *)ctx->d_fl_counter + k;
+        size_t total = 0;
+        const int waves = pick_waves(ctx, (int)std::min<int64_t>(l_first[k].back(), INT32_MAX), 16, 0, &total);
+        DBG("flank scan: %d-bit word: %zu slots, %lld groups, %d wavefronts", k ? 64 : 32, l_slot[k].size(), (long long)l_first[k].back(), waves);
+        if (k == 0) hipLaunchKernelGGL(mtr_k_flank_lanes<uint32_t>, dim3((unsigned)waves), dim3(64), 0, ctx->stream, a);
+        else hipLaunchKernelGGL(mtr_k_flank_lanes<uint64_t>, dim3((unsigned)waves), dim3(64), 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    int32_t dev = 0;
+    HIPCHK(copy_sync(ctx, &dev, ctx->d_fl_status, 4, hipMemcpyDeviceToHost));
+    if (dev != DEV_OK) { ctx->err = "the flank search failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_search_flanks_device(mtr_ctx *ctx, const char *patterns, const int64_t *pattern_off, int32_t n_patterns, int32_t both_strands,
+                                               const mtr_flank_hits_dst *dst, int64_t *out_hits)
+{
+    if (!ctx || !out_hits) return MTR_ERR_BAD_ARG;
+    *out_hits = 0;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    if (n_patterns <= 0) { ctx->err = "n_patterns = " + std::to_string(n_patterns) + ": at least one pattern is needed"; return MTR_ERR_BAD_ARG; }
+    if (!patterns || !pattern_off) { ctx->err = "patterns or pattern_off is NULL"; return MTR_ERR_BAD_ARG; }
+    const int ns = both_strands ? 2 : 1;
+    for (int32_t k = 0; k < n_patterns; k++)
+        if (pattern_off[k + 1] < pattern_off[k]) { ctx->err = "pattern_off decreases at pattern " + std::to_string(k); return MTR_ERR_BAD_ARG; }
+    std::vector<std::vector<uint8_t>> pat;
+    for (int32_t k = 0; k < n_patterns; k++) {
+        std::vector<uint8_t> codes;
+        { mtr_status st = flank_pattern(ctx, patterns + pattern_off[k], pattern_off[k + 1] - pattern_off[k], "pattern " + std::to_string(k), codes); if (st != MTR_OK) return st; }
+        pat.push_back(codes);
+        if (ns == 2) pat.push_back(revcomp_codes(codes));
+    }
+    const int64_t H = (int64_t)ctx->n_reads * n_patterns;
+    if (H > (int64_t)INT32_MAX) { ctx->err = std::to_string(ctx->n_reads) + " reads x " + std::to_string(n_patterns) + " patterns are more than 2^31 - 1 hits"; return MTR_ERR_BAD_ARG; }
+    *out_hits = H;
+    if (!dst) return MTR_OK;
+    if (dst->cap_hits < H) { ctx->err = "destination holds " + std::to_string(dst->cap_hits) + " hits, " + std::to_string(H) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (!dst->dist || !dst->start || !dst->end || !dst->strand) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    { mtr_status st = flank_scan(ctx, pat); if (st != MTR_OK) return st; }
+    const FlankHitsOut out = { dst->dist, dst->start, dst->end, dst->strand };
+    hipLaunchKernelGGL(mtr_k_flank_pack, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t *)ctx->d_fl_res, (int32_t)ns, H, out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- locus genotyping (genotype.hip.inc) --------------------------------------------------------------------------------------------
+// The flank step over four slots per locus, the pairing, one look at the device (how many windows, their longest), one round of the locus
+// search's kernels over 2 * n_loci single-strand motifs (sized as mtr_search_motif_loci_device sizes a round), the columns.
+extern "C" mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist,
+                                               int32_t gain, int32_t mismatch, int32_t indel, const mtr_genotypes_dst *dst, int64_t *out_rows)
+{
+    if (!ctx || !out_rows) return MTR_ERR_BAD_ARG;
+    *out_rows = 0;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    if (n_loci <= 0) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
+    if (!seqs || !seq_off) { ctx->err = "seqs or seq_off is NULL"; return MTR_ERR_BAD_ARG; }
+    if (n_loci > INT32_MAX / 4) { ctx->err = "more than 2^29 - 1 loci"; return MTR_ERR_BAD_ARG; }
+    for (int32_t k = 0; k < 3 * n_loci; k++)
+        if (seq_off[k + 1] < seq_off[k]) { ctx->err = "seq_off decreases at locus " + std::to_string(k / 3) + " (sequence " + std::to_string(k % 3) + ")"; return MTR_ERR_BAD_ARG; }
+    // the motifs as the search takes them, for the search's own checks
+    std::string mot; std::vector<int64_t> mot_off(1, 0);
+    for (int32_t l = 0; l < n_loci; l++) { mot.append(seqs + seq_off[3 * l + 1], (size_t)(seq_off[3 * l + 2] - seq_off[3 * l + 1])); mot_off.push_back((int64_t)mot.size()); }
+    { mtr_status st = search_motifs_check_args(ctx, mot.data(), mot_off.data(), n_loci, gain, mismatch, indel); if (st != MTR_OK) return st; }
+    std::vector<std::vector<uint8_t>> pat((size_t)n_loci * GT_SLOTS);
+    for (int32_t l = 0; l < n_loci; l++)
+        for (int side = 0; side < 2; side++) {
+            const int64_t at = seq_off[3 * l + 2 * side], len = seq_off[3 * l + 2 * side + 1] - at;
+            std::vector<uint8_t> &c = pat[(size_t)l * GT_SLOTS + (size_t)side];
+            { mtr_status st = flank_pattern(ctx, seqs + at, len, "locus " + std::to_string(l) + ", " + (side ? "right" : "left") + " flank", c); if (st != MTR_OK) return st; }
+            pat[(size_t)l * GT_SLOTS + 2 + (size_t)side] = revcomp_codes(c);
+        }
+    if (max_flank_dist < 0) { ctx->err = "max_flank_dist = " + std::to_string(max_flank_dist) + ": at least 0"; return MTR_ERR_BAD_ARG; }
+    const int n = ctx->n_reads, M2 = 2 * n_loci;
+    const int64_t rows = (int64_t)n * n_loci;
+    if (2 * rows > (int64_t)INT32_MAX) { ctx->err = std::to_string(n) + " reads x " + std::to_string(n_loci) + " loci in two orientations are more than 2^31 - 1 pairs"; return MTR_ERR_BAD_ARG; }
+    { mtr_status st = search_motifs_check_size(ctx, mot_off.data(), n_loci); if (st != MTR_OK) return st; }
+    *out_rows = rows;
+    if (!dst) return MTR_OK;
+    if (dst->cap_rows < rows) { ctx->err = "destination holds " + std::to_string(dst->cap_rows) + " rows, " + std::to_string(rows) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (!dst->spanning || !dst->orientation || !dst->flank_dist || !dst->window || !dst->fields || !dst->score || !dst->ratio) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    { mtr_status st = flank_scan(ctx, pat); if (st != MTR_OK) return st; }
+    // the pairing
+    HIPCHK(ctx->d_gt_state.ensure(LOCI_STATE * 4)); HIPCHK(ctx->d_gt_pair.ensure((size_t)rows * GT_PAIR * 4)); HIPCHK(ctx->d_gt_iv.ensure((size_t)rows * sizeof(LociIv)));
+    HIPCHK(hipMemsetAsync(ctx->d_gt_state, 0, LOCI_STATE * 4, ctx->stream));
+    const dim3 per_row((unsigned)((rows + 255) / 256)), b256(256);
+    const GenoPairArgs ga = { ctx->d_fl_res, n_loci, max_flank_dist, rows, ctx->d_gt_pair, ctx->d_gt_iv, (int32_t)rows, ctx->d_gt_state };
+    hipLaunchKernelGGL(mtr_k_geno_pair, per_row, b256, 0, ctx->stream, ga);
+    HIPCHK(hipGetLastError());
+    int32_t st[LOCI_STATE];
+    HIPCHK(copy_sync(ctx, st, ctx->d_gt_state, sizeof st, hipMemcpyDeviceToHost));
+    const int64_t N = st[LOCI_NEXT];
+    const int max_len = st[LOCI_MAXLEN];
+    if (st[LOCI_STATUS] != DEV_OK || N < 0 || N > rows || max_len < 0 || max_len > ctx->Lmax || (N > 0) != (max_len > 0)) {
+        ctx->err = "the genotype's pairing failed on the device (status " + std::to_string(st[LOCI_STATUS]) + ")"; return MTR_ERR_HIP;
+    }
+    if (N > 0) {
+        // the slots: locus l as given (2 * l) and reverse-complemented (2 * l + 1), one strand each
+        const int lane_max = ctx->sw.motif_lane_max, lane_rows = ctx->sw.motif_lane_rows;
+        std::string both; std::vector<int64_t> both_off(1, 0);
+        static const char letters[4] = { 'A', 'C', 'G', 'T' };
+        for (int32_t l = 0; l < n_loci; l++) {
+            const std::string m = mot.substr((size_t)mot_off[(size_t)l], (size_t)(mot_off[(size_t)l + 1] - mot_off[(size_t)l]));
+            std::string rc(m.size(), 'A');
+            for (size_t t = 0; t < m.size(); t++) { const char c = m[m.size() - 1 - t]; rc[t] = letters[3 - (c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : 3)]; }
+            both += m; both_off.push_back((int64_t)both.size()); both += rc; both_off.push_back((int64_t)both.size());
+        }
+        std::vector<uint8_t> units; std::vector<int32_t> unit_off; std::vector<uint64_t> bits;
+        motif_slots(both.data(), both_off.data(), M2, 1, units, unit_off, bits);
+        const LaneSlots ls = lane_slots(unit_off, M2, lane_max);
+        const std::vector<int32_t> &slot_q = ls.slot_q, &q_slot = ls.q_slot;
+        const size_t sS = (size_t)M2, nq = q_slot.size(), nt = (size_t)N;
+        if ((int64_t)nq * MLO_N_CLASSES > (int64_t)INT32_MAX) { ctx->err = std::to_string(nq) + " short motifs are more than the bins take"; return MTR_ERR_OVERFLOW; }
+        const size_t nb = nq * MLO_N_CLASSES;
+        // device copies: d_gt_i32 = unit_off | slot_q | q_slot, d_gt_i64 = bits; the bins: d_gt_bin32 = hist | groups, d_gt_bin64 = tfirst | gfirst;
+        // the tasks: d_gt_task32 = tbin | trank | sorted | wlist
+        HIPCHK(ctx->d_gt_i32.ensure((2 * sS + 1 + nq + 1) * 4)); HIPCHK(ctx->d_gt_i64.ensure(sS * 8)); HIPCHK(ctx->d_gt_units.ensure(units.size() + 16));
+        HIPCHK(ctx->d_gt_bin32.ensure((2 * nb + 1) * 4)); HIPCHK(ctx->d_gt_bin64.ensure(2 * (nb + 1) * 8)); HIPCHK(ctx->d_gt_counter.ensure(5 * 8));
+        HIPCHK(ctx->d_gt_task32.ensure(4 * nt * 4)); HIPCHK(ctx->d_gt_res.ensure(nt * MS_RES * 4));
+        int32_t *d_uoff = ctx->d_gt_i32, *d_slot_q = d_uoff + sS + 1, *d_q_slot = d_slot_q + sS;
+        HIPCHK(copy_sync(ctx, d_uoff, unit_off.data(), (sS + 1) * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_slot_q, slot_q.data(), sS * 4, hipMemcpyHostToDevice));
+        if (nq > 0) HIPCHK(copy_sync(ctx, d_q_slot, q_slot.data(), nq * 4, hipMemcpyHostToDevice));
+        HIPCHK(copy_sync(ctx, ctx->d_gt_i64, bits.data(), sS * 8, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_gt_units, units.data(), units.size(), hipMemcpyHostToDevice));
+        LociArgs a{};
+        a.b.packed = ctx->d_packed; a.b.woff = ctx->d_woff; a.b.lens = ctx->d_lens; a.b.order = nullptr; a.b.n_reads = n;
+        a.iv = ctx->d_gt_iv; a.n_iv = (int32_t)N;
+        a.n_motifs = M2; a.n_strands = 1; a.G = gain; a.MM = mismatch; a.D = indel; a.lane_rows = lane_rows;
+        a.units = ctx->d_gt_units; a.unit_off = d_uoff; a.bits = (const uint64_t *)(int64_t *)ctx->d_gt_i64; a.slot_q = d_slot_q; a.q_slot = d_q_slot;
+        a.hist = ctx->d_gt_bin32; a.groups = a.hist + nb; a.tfirst = ctx->d_gt_bin64; a.gfirst = a.tfirst + nb + 1; a.n_bins = (int32_t)nb;
+        a.tbin = ctx->d_gt_task32; a.trank = a.tbin + nt; a.sorted = a.trank + nt; a.wlist = a.sorted + nt; a.res = ctx->d_gt_res;
+        a.state = ctx->d_gt_state; a.dp16_max_rows = ctx->sw.dp16_max_rows;
+        { mtr_status r = loci_round(ctx, a, ls, N, max_len, (unsigned long long *)ctx->d_gt_counter, "genotype_loci", 0); if (r != MTR_OK) return r; }
+        // the status before the columns: a failed genotype writes nothing
+        HIPCHK(copy_sync(ctx, st, ctx->d_gt_state, sizeof st, hipMemcpyDeviceToHost));
+        if (st[LOCI_STATUS] == DEV_ERR_DP_TOO_LARGE) { ctx->err = "You need to increse the value of WrapDPsize. (a DP of the genotype exceeded it or its scratch)"; return MTR_ERR_DP_TOO_LARGE; }
+        if (st[LOCI_STATUS] != DEV_OK) { ctx->err = "the genotype's alignments failed on the device (status " + std::to_string(st[LOCI_STATUS]) + ")"; return MTR_ERR_HIP; }
+    }
+    const GenotypesOut out = { dst->spanning, dst->orientation, dst->flank_dist, dst->window, dst->fields, dst->score, dst->ratio };
+    hipLaunchKernelGGL(mtr_k_geno_out, per_row, b256, 0, ctx->stream, (const int32_t *)ctx->d_gt_pair, (const int32_t *)ctx->d_gt_res, rows, out);
+    HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
 }

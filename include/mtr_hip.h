@@ -513,6 +513,63 @@ typedef struct mtr_genotypes_dst {
 mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist,
                                     int32_t gain, int32_t mismatch, int32_t indel, const mtr_genotypes_dst *dst, int64_t *out_rows);
 
+/* ---- allele calls: the genotype's rows of a locus ranked and split ---------------------------------------------------------------------------------
+ * "Which alleles does the sample carry at this locus?"  The genotype answers per read; this call reduces every read that spans a locus to one or
+ * two values.  The input is genotype rows in DEVICE memory, row = read * n_loci + locus, n_reads >= 1, n_loci >= 1, n_reads * n_loci <= 2^31 - 1:
+ * what one mtr_genotype_loci_device call wrote, or several calls' rows concatenated along the read axis (the batches of a file walk go in as one
+ * input; n_reads is an argument).  The call needs no uploaded batch and touches nothing the context keeps of one.
+ * The definition, for the parameters measure, min_ratio, min_support, min_percent, min_sep (mtr_allele_params):
+ *   supporting row   a row supports its locus iff spanning == 1 and (window[1] == window[0] or ratio >= min_ratio), the comparison made in float32;
+ *                    a row with spanning == 0 is skipped whatever its other columns hold
+ *   value            v = fields[3] (measure = MTR_ALLELE_COPIES) or window[1] - window[0] (MTR_ALLELE_BASES); v < 0 in a supporting row is
+ *                    MTR_ERR_BAD_ARG, the message names the row (the smallest such row), nothing is written
+ *   support list     the supporting rows of a locus sorted by (v, read) ascending; locus l has S_l of them, S = sum S_l; support_off[n_loci + 1]
+ *                    is the prefix of S_l, value[S] and read[S] hold the sorted lists, one locus after the other
+ *   med, sad         for the sorted values v[0 .. S_l) of one locus: med(i, j) = v[i + (j - i - 1) / 2], the lower median of the segment [i, j);
+ *                    sad(i, j) = sum over t in [i, j) of |v[t] - med(i, j)|, as int64; cost1 = sad(0, S_l)
+ *   admissible       a split k, 1 <= k < S_l, is admissible iff v[k - 1] < v[k] (reads of one value are never separated), min(k, S_l - k) >=
+ *                    min_support, min(k, S_l - k) * 100 >= min_percent * S_l (in int64), and med(k, S_l) - med(0, k) >= min_sep
+ *   cost2(k)         = sad(0, k) + sad(k, S_l)
+ *   S_l < min_support (S_l == 0 too)   zygosity 0, call (0, 0), call_support (0, 0), cost (0, 0), allele 0 for the locus' entries; value and read
+ *                                      are still written
+ *   no admissible k                    zygosity 1, call (med(0, S_l), med(0, S_l)), call_support (S_l, 0), cost (cost1, cost1), allele 0
+ *   an admissible k exists             zygosity 2, k = the admissible split of smallest cost2, the smallest such k on a tie: call (med(0, k),
+ *                                      med(k, S_l)), call_support (k, S_l - k), cost (cost1, cost2(k)), allele[t] = 0 for t < k and 1 from k on
+ * Every output is an exact integer and none depends on the order in which the device worked.
+ * rows is the genotype's own struct read as INPUT: cap_rows >= n_reads * n_loci; only spanning, window, fields and ratio are read, the other
+ * three pointers may be NULL.  wait_stream is the stream that wrote the rows, handled as mtr_upload_batch_device handles it.
+ * Checked in this order, each MTR_ERR_BAD_ARG with mtr_last_error naming the offender: NULL ctx, out_support, rows or prm;  n_reads < 1, n_loci < 1,
+ * more than 2^31 - 1 rows;  measure, min_ratio (0 <= min_ratio <= 1, not NaN), min_support (>= 1), min_percent (0..50), min_sep (>= 1) out of
+ * range, in this order;  a NULL needed input column or cap_rows too small;  a needed input column that is not device memory of the context's GPU
+ * or runs past its allocation.  Then the rows are counted: *out_support = S, and the negative value's error.  Then, as the report calls: dst ==
+ * NULL: MTR_OK with the size only;  cap_loci < n_loci or cap_support < S: MTR_ERR_OVERFLOW, nothing written;  a NULL destination column:
+ * MTR_ERR_BAD_ARG (value, read and allele may be NULL only when S == 0);  else the columns are written and the context's stream synchronised
+ * before the call returns.  A failed call writes nothing into dst. */
+#define MTR_ALLELE_COPIES 0
+#define MTR_ALLELE_BASES 1
+typedef struct mtr_allele_params {
+    int32_t measure;       /* MTR_ALLELE_COPIES or MTR_ALLELE_BASES */
+    float   min_ratio;     /* the smallest ratio a row with a non-empty window may have */
+    int32_t min_support;   /* the fewest reads an allele needs */
+    int32_t min_percent;   /* the smaller allele's least share of the locus' supporting reads, in percent */
+    int32_t min_sep;       /* the least distance between the two alleles' values */
+} mtr_allele_params;
+typedef struct mtr_allele_calls_dst {
+    int64_t *support_off;   /* [n_loci + 1] */
+    int32_t *value;         /* [S] */
+    int32_t *read;          /* [S] */
+    uint8_t *allele;        /* [S] */
+    uint8_t *zygosity;      /* [n_loci] */
+    int32_t *call;          /* [n_loci * 2] */
+    int32_t *call_support;  /* [n_loci * 2] */
+    int64_t *cost;          /* [n_loci * 2] cost1, cost2 */
+    int64_t  cap_loci;
+    int64_t  cap_support;
+} mtr_allele_calls_dst;   /* caller-owned DEVICE memory */
+mtr_status mtr_call_alleles_device(mtr_ctx *ctx, const mtr_genotypes_dst *rows, int64_t n_reads, int32_t n_loci,
+                                   const mtr_allele_params *prm, void *wait_stream,
+                                   const mtr_allele_calls_dst *dst, int64_t *out_support);
+
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left
  * of handle_one_file.c:281-287's loop across GPUs is ONE exchange: the record tables travel to the process that chains and

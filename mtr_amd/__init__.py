@@ -52,7 +52,9 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_upload_batch_device_in_file", "mtr_upload_fasta_device_in_file", "mtr_file_state_skip_device", "mtr_test_file_tail",
            "mtr_parse_fasta_device_window", "mtr_upload_fasta_device_window", "mtr_parse_fastq_device_window", "mtr_upload_fastq_device_window",
            "mtr_report_motifs_device", "mtr_test_unit_motifs", "mtr_search_motifs_device",
-           "mtr_search_motif_loci_device", "mtr_motif_loci_copy_device", "mtr_search_flanks_device", "mtr_genotype_loci_device"]
+           "mtr_search_motif_loci_device", "mtr_motif_loci_copy_device", "mtr_search_flanks_device", "mtr_genotype_loci_device",
+           "mtr_call_alleles_device"]
+ALLELE_COPIES, ALLELE_BASES = 0, 1           # MTR_ALLELE_COPIES, MTR_ALLELE_BASES: the measure of Engine.call_alleles
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
 
@@ -239,6 +241,30 @@ class Genotypes(NamedTuple):
     ratio: "object"       # float32 [n, m]: matches / repeat_len
 
 
+class CAlleleParams(C.Structure):
+    """mtr_allele_params: what supports a locus and which splits are admissible"""
+    _fields_ = [("measure", C.c_int32), ("min_ratio", C.c_float), ("min_support", C.c_int32), ("min_percent", C.c_int32), ("min_sep", C.c_int32)]
+
+
+class CAlleleCallsDst(C.Structure):
+    """mtr_allele_calls_dst: device pointers of the allele calls' columns and their capacities"""
+    _fields_ = [("support_off", C.c_void_p), ("value", C.c_void_p), ("read", C.c_void_p), ("allele", C.c_void_p), ("zygosity", C.c_void_p),
+                ("call", C.c_void_p), ("call_support", C.c_void_p), ("cost", C.c_void_p), ("cap_loci", C.c_int64), ("cap_support", C.c_int64)]
+
+
+class AlleleCalls(NamedTuple):
+    """What Engine.call_alleles made of the genotype rows of n reads and m loci: per locus its S_l supporting reads sorted by (value, read) -
+    S of them in all - and the one or two alleles they split into, all on the engine's device.  include/mtr_hip.h defines every column."""
+    support_off: "object"   # int64 [m + 1]: locus l's supporting reads are entries support_off[l] .. support_off[l + 1]
+    value: "object"         # int32 [S]: copies or bases, ascending within a locus
+    read: "object"          # int32 [S]: the read of each value, ascending among equal values
+    allele: "object"        # uint8 [S]: 0 = the entry belongs to the first (or only) allele, 1 = to the second
+    zygosity: "object"      # uint8 [m]: 0 = too little support for a call, 1 = one allele, 2 = two
+    call: "object"          # int32 [m, 2]: the alleles' values, the lower medians of their entries
+    call_support: "object"  # int32 [m, 2]: the alleles' numbers of reads
+    cost: "object"          # int64 [m, 2]: the sum of absolute deviations from the median(s) as one allele, and as called
+
+
 class CFastaInfo(C.Structure):
     """mtr_fasta_info: what a FASTA file in device memory holds"""
     _fields_ = [("n_reads", C.c_int32), ("end", C.c_int32), ("bad_char", C.c_int32), ("reserved", C.c_int32),
@@ -368,6 +394,8 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_search_flanks_device.restype = C.c_int
     lib.mtr_genotype_loci_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [P(CGenotypesDst), P(C.c_int64)]
     lib.mtr_genotype_loci_device.restype = C.c_int
+    lib.mtr_call_alleles_device.argtypes = [C.c_void_p, P(CGenotypesDst), C.c_int64, C.c_int32, P(CAlleleParams), C.c_void_p, P(CAlleleCallsDst), P(C.c_int64)]
+    lib.mtr_call_alleles_device.restype = C.c_int
     lib.mtr_parse_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaDst), P(CFastaInfo)]
     lib.mtr_parse_fasta_device.restype = C.c_int
     lib.mtr_upload_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaInfo)]
@@ -480,6 +508,43 @@ def fasta_input_args(buf, device: int) -> None:
         raise MtrError(f"buf must be a GPU tensor, got a tensor on {buf.device}")
     if buf.device.index != device:
         raise MtrError(f"buf is on {buf.device}, the engine on cuda:{device}")
+
+
+def genotype_rows_args(gt, device: int):
+    """The checks of Engine.call_alleles on its genotype rows, made before the library is called: gt.spanning a contiguous 2-D torch.uint8 tensor
+    [n, m] with n, m >= 1, gt.window [n, m, 2] int32, gt.fields [n, m, 8] int32, gt.ratio [n, m] float32, all contiguous and on cuda:device (a
+    Genotypes, or anything with these four attributes: the other columns are not read).  Returns (n, m); raises MtrError."""
+    import torch
+
+    sp = getattr(gt, "spanning", None)
+    if not isinstance(sp, torch.Tensor):
+        raise MtrError(f"gt.spanning must be a torch.Tensor, got {type(sp).__name__}")
+    if sp.dtype != torch.uint8:
+        raise MtrError(f"gt.spanning must have dtype torch.uint8, got {sp.dtype}")
+    if sp.dim() != 2 or sp.shape[0] < 1 or sp.shape[1] < 1:
+        raise MtrError(f"gt.spanning must be [n, m] with n, m >= 1, got shape {tuple(sp.shape)}")
+    n, m = int(sp.shape[0]), int(sp.shape[1])
+    cols = (("spanning", sp, torch.uint8, (n, m)), ("window", getattr(gt, "window", None), torch.int32, (n, m, 2)),
+            ("fields", getattr(gt, "fields", None), torch.int32, (n, m, 8)), ("ratio", getattr(gt, "ratio", None), torch.float32, (n, m)))
+    for name, t, dtype, shape in cols:
+        if not isinstance(t, torch.Tensor):
+            raise MtrError(f"gt.{name} must be a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != dtype:
+            raise MtrError(f"gt.{name} must have dtype {dtype}, got {t.dtype}")
+        if tuple(t.shape) != shape:
+            raise MtrError(f"gt.{name} must have shape {shape}, got shape {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise MtrError(f"gt.{name} must be contiguous, got strides {t.stride()}")
+    if n * m > 2 ** 31 - 1:
+        raise MtrError(f"{n} reads x {m} loci are more than 2^31 - 1 rows")
+    for name, t, _, _ in cols:
+        if t.device != sp.device:
+            raise MtrError(f"gt.{name} is on {t.device}, gt.spanning on {sp.device}: the columns must be on one device")
+    if sp.device.type != "cuda":
+        raise MtrError(f"the genotype rows must be GPU tensors, got tensors on {sp.device}")
+    if sp.device.index != device:
+        raise MtrError(f"the genotype rows are on {sp.device}, the engine on cuda:{device}")
+    return n, m
 
 
 def _fasta(info: CFastaInfo, text, offsets, lens, id_off, ids: bytes) -> Fasta:
@@ -922,6 +987,39 @@ class Engine:
         dst = CGenotypesDst(*[t.data_ptr() for t in gt], R)
         self._check(self.lib.mtr_genotype_loci_device(*args, C.byref(dst), C.byref(nr)), "mtr_genotype_loci_device")
         return gt
+
+    def call_alleles(self, gt, measure="copies", min_ratio: float = 0.0, min_support: int = 2, min_percent: int = 20, min_sep: int = 1) -> AlleleCalls:
+        """Allele calls (mtr_call_alleles_device): the rows of genotype_loci - one call's Genotypes, or several batches' joined with torch.cat(dim=0)
+        column by column - reduced per locus.  A row supports its locus when it spans it and its ratio is at least min_ratio (a row with an empty
+        window always does); its value is its copies (measure "copies" / ALLELE_COPIES) or its window's bases ("bases" / ALLELE_BASES).  Per locus
+        the supporting reads are sorted by (value, read) and split into two alleles where a split exists whose smaller side has min_support reads
+        and min_percent percent of them and whose medians lie min_sep apart - the split of least absolute deviation from the two medians.  Needs no
+        upload and no run and changes nothing either left.  Returns an AlleleCalls of fresh tensors on this engine's device; waits for torch's
+        current stream (where gt was written) by an event, and follows genotype_loci's stream handling for its results."""
+        import torch
+
+        if isinstance(measure, str) and measure in ("copies", "bases"):
+            code = ALLELE_COPIES if measure == "copies" else ALLELE_BASES
+        elif isinstance(measure, (int, np.integer)) and not isinstance(measure, bool) and int(measure) in (ALLELE_COPIES, ALLELE_BASES):
+            code = int(measure)
+        else:
+            raise MtrError(f"measure must be 'copies', 'bases', ALLELE_COPIES or ALLELE_BASES, got {measure!r}")
+        n, m = genotype_rows_args(gt, self.device)
+        dev = torch.device("cuda", self.device)
+        rows = CGenotypesDst(gt.spanning.data_ptr(), None, None, gt.window.data_ptr(), gt.fields.data_ptr(), None, gt.ratio.data_ptr(), n * m)
+        prm = CAlleleParams(code, float(min_ratio), int(min_support), int(min_percent), int(min_sep))
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        args = (self.h, C.byref(rows), n, m, C.byref(prm), stream)
+        ns = C.c_int64()
+        self._check(self.lib.mtr_call_alleles_device(*args, None, C.byref(ns)), "mtr_call_alleles_device")
+        S = int(ns.value)
+        new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)     # noqa: E731
+        calls = AlleleCalls(new(torch.int64, m + 1), new(torch.int32, S), new(torch.int32, S), new(torch.uint8, S), new(torch.uint8, m),
+                            new(torch.int32, m, 2), new(torch.int32, m, 2), new(torch.int64, m, 2))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CAlleleCallsDst(*[t.data_ptr() if t.numel() else None for t in calls], m, S)
+        self._check(self.lib.mtr_call_alleles_device(*args, C.byref(dst), C.byref(ns)), "mtr_call_alleles_device")
+        return calls
 
     def test_unit_motifs(self, units, read=None, copies=None, repeat_len=None, table_slots: int = 0) -> ReportMotifs:
         """mtr_test_unit_motifs: the kernels of report_motif_tensors on caller-given units, one bytes (or str) per unit.  read: the read of
@@ -1370,6 +1468,29 @@ def format_genotypes(ids, lens, loci, gt: Genotypes) -> bytes:
         cols = [str(int(lens[r])), str(k), str(int(orientation[r, k])), str(int(fdist[r, k, 0])), str(int(fdist[r, k, 1])), str(lo + 1), str(hi), str(hi - lo),
                 str(f[3]), str(f[4]), _c_float_text(ratio[r, k]), str(f[5]), str(f[6]), str(f[7])]
         out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + shown[k][int(orientation[r, k])] + b"\n")
+    return b"".join(out)
+
+
+def format_allele_calls(loci, calls: AlleleCalls) -> bytes:
+    """The calls of Engine.call_alleles as text, one tab-separated line per locus in the given order: locus index, S_l (its supporting reads),
+    zygosity, the two alleles' values, their supports, cost1 and cost2, the smallest and the largest supporting value (0 and 0 without
+    support), and the locus' motif as given.
+    loci: what genotype_loci was given, (left_flank, motif, right_flank) each; calls: call_alleles' result (tensors or numpy)."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    bmot = [v[1].encode() if isinstance(v[1], str) else bytes(v[1]) for v in loci]
+    m = len(bmot)
+    off, value, zyg = host(calls.support_off).reshape(-1), host(calls.value).reshape(-1), host(calls.zygosity).reshape(-1)
+    if len(off) != m + 1 or len(zyg) != m:
+        raise MtrError(f"{len(zyg)} calls for {m} loci")
+    call, sup, cost = host(calls.call).reshape(m, 2), host(calls.call_support).reshape(m, 2), host(calls.cost).reshape(m, 2)
+    out = []
+    for k in range(m):
+        lo, hi = int(off[k]), int(off[k + 1])
+        ends = (int(value[lo]), int(value[hi - 1])) if hi > lo else (0, 0)
+        cols = [k, hi - lo, int(zyg[k]), int(call[k, 0]), int(call[k, 1]), int(sup[k, 0]), int(sup[k, 1]), int(cost[k, 0]), int(cost[k, 1]), *ends]
+        out.append("\t".join(str(c) for c in cols).encode() + b"\t" + bmot[k] + b"\n")
     return b"".join(out)
 
 

@@ -2116,6 +2116,9 @@ DEVINL long long replay_ranges(int32_t *re, int nr, L &&flag_of, F &&on_record)
 __global__ __launch_bounds__(64) void mtr_k_replay(K2Args a, SplitArgs s)
 {
     const int lane = lane_id();
+    // A chain that outgrew a buffer left its flags half written - after a full list of the dead-range screen the walks did not run, and in one
+    // pass nothing else writes a kept range's flag: what the buffer held before would be taken for an index into cand.  The host reruns the batch.
+    if (uni(*(volatile int32_t *)a.status) == DEV_ERR_STAGED_OVERFLOW) return;
     for (int rd = blockIdx.x; rd < a.b.n_reads; rd += gridDim.x) {
         int hv = 0; long long ho = 0;
         if (lane == 0) { hv = a.r_count[rd]; ho = a.r_off[rd]; } else if (lane == 1) ho = s.item_off[rd];

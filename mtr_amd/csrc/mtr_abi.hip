@@ -42,6 +42,7 @@
 #include "motif_loci.hip.inc"
 #include "flank_search.hip.inc"
 #include "genotype.hip.inc"
+#include "allele_call.hip.inc"
 #include "fasta.hip.inc"
 #include "fastq.hip.inc"
 #include "file_order.hip.inc"
@@ -231,6 +232,9 @@ struct mtr_ctx {
     // arrays - buffers of its own, so that what the locus search keeps (ml_ready) stays
     DevBuf<int32_t> d_gt_pair, d_gt_i32, d_gt_bin32, d_gt_task32, d_gt_res, d_gt_state; DevBuf<int64_t> d_gt_i64, d_gt_bin64;
     DevBuf<LociIv> d_gt_iv; DevBuf<uint8_t> d_gt_units; DevBuf<unsigned long long> d_gt_counter;
+    // allele calls (mtr_call_alleles_device), per call and nothing kept, buffers of its own so that what the genotype and the locus search keep stays:
+    // d_ac_i32 = count | cursor (spread while the loci are few), d_ac_i64 = support_off | tile_off | state, the keys, the split's prefix sums
+    DevBuf<int32_t> d_ac_i32; DevBuf<int64_t> d_ac_i64, d_ac_prefix; DevBuf<unsigned long long> d_ac_keys;
     long long wrap_dp_size = MTRC_WRAP_DP_SIZE;          // the WrapDPsize the kernels of this context's device test (MTR_TEST_WRAP_DP_SIZE)
     // a FASTA file in device memory (fasta.hip.inc), per call: the tiles' columns, the header windows' columns, the IDs' offsets, the stop, the sizes
     DevBuf<uint32_t> d_fa_tiles, d_fa_hbase; DevBuf<int32_t> d_fa_hpos, d_fa_hidlen; DevBuf<int64_t> d_fa_idoff;
@@ -2570,6 +2574,82 @@ extern "C" mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, c
     const GenotypesOut out = { dst->spanning, dst->orientation, dst->flank_dist, dst->window, dst->fields, dst->score, dst->ratio };
     hipLaunchKernelGGL(mtr_k_geno_out, per_row, b256, 0, ctx->stream, (const int32_t *)ctx->d_gt_pair, (const int32_t *)ctx->d_gt_res, rows, out);
     HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- allele calls (allele_call.hip.inc) ------------------------------------------------------------------------------------------------
+// The arguments' checks, the count and the offsets, one look at the device (the status, S, the tiles), then the fill, the rank and the split
+// straight into the caller's columns.  No batch is needed and none is touched.
+extern "C" mtr_status mtr_call_alleles_device(mtr_ctx *ctx, const mtr_genotypes_dst *rows, int64_t n_reads, int32_t n_loci, const mtr_allele_params *prm,
+                                              void *wait_stream, const mtr_allele_calls_dst *dst, int64_t *out_support)
+{
+    if (!ctx || !out_support) return MTR_ERR_BAD_ARG;
+    *out_support = 0;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    if (!rows || !prm) { ctx->err = "rows or prm is NULL"; return MTR_ERR_BAD_ARG; }
+    if (n_reads < 1) { ctx->err = "n_reads = " + std::to_string(n_reads) + ": at least one read is needed"; return MTR_ERR_BAD_ARG; }
+    if (n_loci < 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
+    if (n_reads > (int64_t)INT32_MAX / n_loci) { ctx->err = std::to_string(n_reads) + " reads x " + std::to_string(n_loci) + " loci are more than 2^31 - 1 rows"; return MTR_ERR_BAD_ARG; }
+    if (prm->measure != MTR_ALLELE_COPIES && prm->measure != MTR_ALLELE_BASES) { ctx->err = "measure " + std::to_string(prm->measure) + " is neither MTR_ALLELE_COPIES nor MTR_ALLELE_BASES"; return MTR_ERR_BAD_ARG; }
+    if (!(prm->min_ratio >= 0.0f && prm->min_ratio <= 1.0f)) { ctx->err = "min_ratio " + std::to_string(prm->min_ratio) + " outside 0..1"; return MTR_ERR_BAD_ARG; }
+    if (prm->min_support < 1) { ctx->err = "min_support " + std::to_string(prm->min_support) + ": at least 1"; return MTR_ERR_BAD_ARG; }
+    if (prm->min_percent < 0 || prm->min_percent > 50) { ctx->err = "min_percent " + std::to_string(prm->min_percent) + " outside 0..50"; return MTR_ERR_BAD_ARG; }
+    if (prm->min_sep < 1) { ctx->err = "min_sep " + std::to_string(prm->min_sep) + ": at least 1"; return MTR_ERR_BAD_ARG; }
+    const int64_t R = n_reads * n_loci;
+    if (!rows->spanning || !rows->window || !rows->fields || !rows->ratio) { ctx->err = "an input column (spanning, window, fields, ratio) is NULL"; return MTR_ERR_BAD_ARG; }
+    if (rows->cap_rows < R) { ctx->err = "cap_rows " + std::to_string(rows->cap_rows) + " of the input is below " + std::to_string(R) + " rows"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    { mtr_status st = check_device_ptr(ctx, rows->spanning, R, "rows->spanning", "the rows' bytes"); if (st != MTR_OK) return st; }
+    { mtr_status st = check_device_ptr(ctx, (const uint8_t *)rows->window, R * 8, "rows->window", "the rows' bytes"); if (st != MTR_OK) return st; }
+    { mtr_status st = check_device_ptr(ctx, (const uint8_t *)rows->fields, R * 32, "rows->fields", "the rows' bytes"); if (st != MTR_OK) return st; }
+    { mtr_status st = check_device_ptr(ctx, (const uint8_t *)rows->ratio, R * 4, "rows->ratio", "the rows' bytes"); if (st != MTR_OK) return st; }
+    const size_t nl = (size_t)n_loci;
+    const size_t cstride = n_loci <= AL_SPREAD_LOCI ? AL_SPREAD : 1;
+    HIPCHK(ctx->d_ac_i32.ensure(2 * nl * cstride * 4)); HIPCHK(ctx->d_ac_i64.ensure((2 * (nl + 1) + AL_STATE) * 8));
+    AlleleArgs a{};
+    a.spanning = rows->spanning; a.window = rows->window; a.fields = rows->fields; a.ratio = rows->ratio;
+    a.rows = R; a.n_loci = n_loci; a.measure = prm->measure; a.min_ratio = prm->min_ratio; a.rule = { prm->min_support, prm->min_percent, prm->min_sep };
+    a.count = ctx->d_ac_i32; a.cursor = a.count + nl * cstride; a.cstride = (int32_t)cstride; a.off = ctx->d_ac_i64; a.tile_off = a.off + nl + 1; a.state = a.tile_off + nl + 1;
+    // the rows come from the caller's stream: the kernels wait for it there, not for the whole device
+    if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ctx->ev_text, (hipStream_t)wait_stream));
+    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
+    HIPCHK(hipMemsetAsync(ctx->d_ac_i32, 0, 2 * nl * cstride * 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(a.state, 0xff, 8, ctx->stream));
+    const dim3 per_row((unsigned)((R + AL_BLOCK - 1) / AL_BLOCK)), blk(AL_BLOCK);
+    hipLaunchKernelGGL(mtr_k_allele_count, per_row, blk, 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(mtr_k_allele_offsets, dim3(1), dim3(64), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    int64_t st[AL_STATE];
+    HIPCHK(copy_sync(ctx, st, a.state, 3 * 8, hipMemcpyDeviceToHost));
+    const int64_t S = st[AL_TOTAL], n_tiles = st[AL_TILES];
+    if (S < 0 || S > R || n_tiles < 0 || n_tiles > S) { ctx->err = "the allele calls' count failed on the device"; return MTR_ERR_HIP; }
+    *out_support = S;
+    if (st[AL_BAD] != -1) {
+        const int64_t p = st[AL_BAD];
+        ctx->err = "row " + std::to_string(p) + " (read " + std::to_string(p / n_loci) + ", locus " + std::to_string(p % n_loci) + ") supports its locus with a negative value";
+        return MTR_ERR_BAD_ARG;
+    }
+    if (!dst) return MTR_OK;
+    if (dst->cap_loci < n_loci) { ctx->err = "destination holds " + std::to_string(dst->cap_loci) + " loci, " + std::to_string(n_loci) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (dst->cap_support < S) { ctx->err = "destination holds " + std::to_string(dst->cap_support) + " supporting rows, " + std::to_string(S) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (!dst->support_off || !dst->zygosity || !dst->call || !dst->call_support || !dst->cost || (S > 0 && (!dst->value || !dst->read || !dst->allele))) {
+        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
+    }
+    HIPCHK(ctx->d_ac_keys.ensure((size_t)std::max<int64_t>(S, 1) * 8)); HIPCHK(ctx->d_ac_prefix.ensure(((size_t)S + nl) * 8));
+    a.keys = ctx->d_ac_keys; a.prefix = ctx->d_ac_prefix;
+    a.value = dst->value; a.read = dst->read; a.allele = dst->allele; a.zygosity = dst->zygosity; a.call = dst->call; a.call_support = dst->call_support; a.cost = dst->cost;
+    if (S > 0) {
+        hipLaunchKernelGGL(mtr_k_allele_fill, per_row, blk, 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(mtr_k_allele_rank, dim3((unsigned)std::min<int64_t>(n_tiles, AL_MAX_GRID)), dim3(AL_TILE), 0, ctx->stream, a, n_tiles);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(mtr_k_allele_split, dim3((unsigned)std::min<int64_t>(n_loci, AL_MAX_GRID)), blk, 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(dst->support_off, a.off, (nl + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
 }

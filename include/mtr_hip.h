@@ -513,6 +513,54 @@ typedef struct mtr_genotypes_dst {
 mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist,
                                     int32_t gain, int32_t mismatch, int32_t indel, const mtr_genotypes_dst *dst, int64_t *out_rows);
 
+/* ---- partial genotype: what a read that does not span a locus still proves ------------------------------------------------------------------------
+ * The genotype answers only for reads that span a locus; an expanded allele is the one a read is least likely to span.  A read that holds one
+ * flank and runs off its end inside the repeat proves "at least N copies"; a read whose repeat ends but whose far flank is too damaged to be found
+ * carries a count as well.  This call reports both.  The reference has nothing of this kind; the definition is this project's own.  For a read
+ * x[0 .. L), a locus (A, M, B) and K, G, MM, D as the genotype's, max_tail >= 0, and the four single-strand flank hits of the genotype's definition
+ * as slots: 0 = F(A), 1 = F(B), 2 = F(rc A), 3 = F(rc B):
+ *   partial row   iff the genotype's pairing rule finds neither orientation valid (it would say spanning = 0) and at least one slot has dist <= K.
+ *                 A spanning row, and a row with no flank within K, is all zeros
+ *   slot          the slot of smallest dist among those with dist <= K, the lowest slot number on a tie.  It fixes the window [lo, hi), the
+ *                 direction and the motif Mo:
+ *                   slot 0 (A)      [a.end, L)      forward from lo     M
+ *                   slot 1 (B)      [0, b.start)    backward from hi    M
+ *                   slot 2 (rc A)   [0, a'.start)   backward from hi    rc M
+ *                   slot 3 (rc B)   [b'.end, L)     forward from lo     rc M
+ *                 forward: y[t] = x[lo + t], m[j] = Mo[j];  backward: y[t] = x[hi - 1 - t], m[j] = Mo[U - 1 - j];  n = hi - lo
+ *   extension     of y[0 .. n) against m[0 .. U), 1 <= U <= 32: the search's wrap-around recurrence ANCHORED at the flank, that is, without the
+ *                 maximum with 0.  Row 0: H(0, j) = C(0, j) = T(0, j) = 0 for every j (the phase at the flank is free).  Rows i = 1 .. n, columns
+ *                 j = 1 .. U, with H(i - 1, 0) = H(i - 1, U) (C and T likewise):
+ *                   sub  = H(i - 1, j - 1) + (G if y[i - 1] == m[j - 1], else -MM)
+ *                   left = H(i, j - 1) - D, for j > 1 only (column 1 has no left term, as in the search's forward pass)
+ *                   up   = H(i - 1, j) - D
+ *                 H(i, j) is the largest of these; the predecessor is the first of sub, left, up that attains it (the traceback's order:
+ *                 diagonal, deletion, insertion).  C counts motif bases consumed: the predecessor's C, plus 1 for sub and for left.  T counts
+ *                 matches: the predecessor's T, plus 1 for a matching sub.
+ *   best cell     (bi, bj) = the first strict maximum of H in row-major order over the rows >= 1, if it is positive.  Without a positive cell, or
+ *                 with n = 0: bi = 0 and C = T = H = 0
+ *   columns       partial;  slot;  flank_dist = the slot's dist;  window = lo, hi;  ext = ext_len = bi, motif_bases = C(bi, bj), copies = C / U,
+ *                 matches = T(bi, bj), score = H(bi, bj), tail = n - bi (a window without a positive cell: tail = n);  ratio = matches / ext_len
+ *                 as float, 0 when ext_len is 0;  open = 1 iff the row is partial and tail <= max_tail
+ * The repeat is x[lo .. lo + ext_len) for a forward slot and x[hi - ext_len .. hi) for a backward one.  open = 1 says that the repeat runs off the
+ * read: copies is a LOWER BOUND.  An empty window (lo == hi) gives partial = 1, open = 1, zeros in ext, and no DP.
+ * seqs / seq_off, the rows and the protocol are mtr_genotype_loci_device's; the call keeps nothing and drops nothing the batch or a run keeps.
+ * Checked in the genotype's order up to its row limit; then MTR_ERR_BAD_ARG for a motif of more than 32 bases (the message names the locus: this
+ * call aligns one extension per lane and nothing else) and for max_tail < 0.  There is no MTR_ERR_DP_TOO_LARGE: nothing is stored per cell.  Then
+ * *out_rows = n_reads * n_loci and dst as there (cap_rows); a failed call writes nothing. */
+typedef struct mtr_partial_dst {
+    uint8_t *partial;      /* [R] */
+    uint8_t *slot;         /* [R] 0 .. 3 */
+    int32_t *flank_dist;   /* [R] */
+    int32_t *window;       /* [R*2] lo, hi */
+    int32_t *ext;          /* [R*6] ext_len, motif_bases, copies, matches, score, tail */
+    float   *ratio;        /* [R] */
+    uint8_t *open;         /* [R] */
+    int64_t  cap_rows;
+} mtr_partial_dst;   /* caller-owned DEVICE memory; row = read * n_loci + locus */
+mtr_status mtr_genotype_partial_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist,
+                                       int32_t gain, int32_t mismatch, int32_t indel, int32_t max_tail, const mtr_partial_dst *dst, int64_t *out_rows);
+
 /* ---- allele calls: the genotype's rows of a locus ranked and split ---------------------------------------------------------------------------------
  * "Which alleles does the sample carry at this locus?"  The genotype answers per read; this call reduces every read that spans a locus to one or
  * two values.  The input is genotype rows in DEVICE memory, row = read * n_loci + locus, n_reads >= 1, n_loci >= 1, n_reads * n_loci <= 2^31 - 1:

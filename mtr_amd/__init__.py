@@ -4,7 +4,7 @@ Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointer
 (Engine.upload_device / process_device / parse_fasta_device / upload_fasta_device / parse_fastq_device / upload_fastq_device /
 walk_fasta_device / walk_fastq_device /
 export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes / report_motif_tensors / search_motifs / search_motif_loci /
-search_flanks / genotype_loci) take or return torch tensors;
+search_flanks / genotype_loci / genotype_partial) take or return torch tensors;
 they import torch when called.
 The product path is libmtr_hip.so only: importing works without a GPU, but creating an Engine
 without the library or without a HIP device raises — there is no CPU fallback.
@@ -53,7 +53,7 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_parse_fasta_device_window", "mtr_upload_fasta_device_window", "mtr_parse_fastq_device_window", "mtr_upload_fastq_device_window",
            "mtr_report_motifs_device", "mtr_test_unit_motifs", "mtr_search_motifs_device",
            "mtr_search_motif_loci_device", "mtr_motif_loci_copy_device", "mtr_search_flanks_device", "mtr_genotype_loci_device",
-           "mtr_call_alleles_device"]
+           "mtr_call_alleles_device", "mtr_genotype_partial_device"]
 ALLELE_COPIES, ALLELE_BASES = 0, 1           # MTR_ALLELE_COPIES, MTR_ALLELE_BASES: the measure of Engine.call_alleles
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
@@ -241,6 +241,32 @@ class Genotypes(NamedTuple):
     ratio: "object"       # float32 [n, m]: matches / repeat_len
 
 
+class CPartialDst(C.Structure):
+    """mtr_partial_dst: device pointers of the partial genotype's columns and their capacity"""
+    _fields_ = [("partial", C.c_void_p), ("slot", C.c_void_p), ("flank_dist", C.c_void_p), ("window", C.c_void_p), ("ext", C.c_void_p),
+                ("ratio", C.c_void_p), ("open", C.c_void_p), ("cap_rows", C.c_int64)]
+
+
+class PartialGenotypes(NamedTuple):
+    """What Engine.genotype_partial found: one row per (read, locus) of n reads and m loci, all on the engine's device.  include/mtr_hip.h defines
+    every column.  A row with open set says "at least ext[2] copies": the repeat runs off the read."""
+    partial: "object"     # uint8 [n, m]: 1 = the read does not span the locus and holds one of its flanks; 0 = every other column of the row is 0
+    slot: "object"        # uint8 [n, m]: the flank the extension starts from: 0 = A, 1 = B, 2 = rc A, 3 = rc B
+    flank_dist: "object"  # int32 [n, m]: that flank's edit distance
+    window: "object"      # int32 [n, m, 2]: the extension runs in read[lo:hi], from lo for slots 0 and 3, from hi for slots 1 and 2
+    ext: "object"         # int32 [n, m, 6]: ext_len, motif_bases, copies, matches, score, tail
+    ratio: "object"       # float32 [n, m]: matches / ext_len
+    open: "object"        # uint8 [n, m]: 1 = partial and tail <= max_tail: copies is a lower bound
+
+
+class PartialSupport(NamedTuple):
+    """What partial_support makes of a PartialGenotypes, per locus"""
+    n_partial: "object"   # int64 [m]: partial rows
+    n_open: "object"      # int64 [m]: open rows
+    max_copies: "object"  # int32 [m]: the largest copies among the open rows with ratio >= min_ratio, 0 without one
+    n_beyond: "object"    # int64 [m], or None without calls: those rows whose copies exceed the larger called allele
+
+
 class CAlleleParams(C.Structure):
     """mtr_allele_params: what supports a locus and which splits are admissible"""
     _fields_ = [("measure", C.c_int32), ("min_ratio", C.c_float), ("min_support", C.c_int32), ("min_percent", C.c_int32), ("min_sep", C.c_int32)]
@@ -394,6 +420,8 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_search_flanks_device.restype = C.c_int
     lib.mtr_genotype_loci_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [P(CGenotypesDst), P(C.c_int64)]
     lib.mtr_genotype_loci_device.restype = C.c_int
+    lib.mtr_genotype_partial_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [P(CPartialDst), P(C.c_int64)]
+    lib.mtr_genotype_partial_device.restype = C.c_int
     lib.mtr_call_alleles_device.argtypes = [C.c_void_p, P(CGenotypesDst), C.c_int64, C.c_int32, P(CAlleleParams), C.c_void_p, P(CAlleleCallsDst), P(C.c_int64)]
     lib.mtr_call_alleles_device.restype = C.c_int
     lib.mtr_parse_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaDst), P(CFastaInfo)]
@@ -988,6 +1016,36 @@ class Engine:
         self._check(self.lib.mtr_genotype_loci_device(*args, C.byref(dst), C.byref(nr)), "mtr_genotype_loci_device")
         return gt
 
+    def genotype_partial(self, loci, max_flank_dist: int, gain: int = 1, mismatch: int = 1, indel: int = 1, max_tail: int = 10) -> PartialGenotypes:
+        """Partial genotype (mtr_genotype_partial_device): loci as genotype_loci takes them, motifs of at most 32 bases.  A read that does not
+        span a locus but holds one of its flanks within max_flank_dist edits is extended from that flank towards the read's end by the anchored
+        wrap-around DP with the given scores; where the extension ends within max_tail bases of the read's end the row is open: its copies are a
+        lower bound.  Needs no run and changes nothing a run left.  Returns a PartialGenotypes of fresh tensors on this engine's device; follows
+        genotype_loci's stream handling."""
+        import torch
+
+        if isinstance(loci, (str, bytes, bytearray)) or not hasattr(loci, "__len__"):
+            raise MtrError(f"loci must be a sequence of (left_flank, motif, right_flank), got {type(loci).__name__}")
+        flat = []
+        for k, locus in enumerate(loci):
+            if isinstance(locus, (str, bytes, bytearray)) or not hasattr(locus, "__len__") or len(locus) != 3:
+                raise MtrError(f"locus {k} must be (left_flank, motif, right_flank)")
+            flat.extend(locus)
+        data, off = pack_ids(flat)
+        m = len(loci)
+        args = (self.h, data.ctypes.data, off.ctypes.data, m, int(max_flank_dist), int(gain), int(mismatch), int(indel), int(max_tail))
+        nr = C.c_int64()
+        self._check(self.lib.mtr_genotype_partial_device(*args, None, C.byref(nr)), "mtr_genotype_partial_device")
+        R = int(nr.value)
+        n = R // m
+        dev = torch.device("cuda", self.device)
+        new = lambda dtype, *tail: torch.empty((n, m) + tail, dtype=dtype, device=dev)     # noqa: E731
+        pg = PartialGenotypes(new(torch.uint8), new(torch.uint8), new(torch.int32), new(torch.int32, 2), new(torch.int32, 6), new(torch.float32), new(torch.uint8))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CPartialDst(*[t.data_ptr() for t in pg], R)
+        self._check(self.lib.mtr_genotype_partial_device(*args, C.byref(dst), C.byref(nr)), "mtr_genotype_partial_device")
+        return pg
+
     def call_alleles(self, gt, measure="copies", min_ratio: float = 0.0, min_support: int = 2, min_percent: int = 20, min_sep: int = 1) -> AlleleCalls:
         """Allele calls (mtr_call_alleles_device): the rows of genotype_loci - one call's Genotypes, or several batches' joined with torch.cat(dim=0)
         column by column - reduced per locus.  A row supports its locus when it spans it and its ratio is at least min_ratio (a row with an empty
@@ -1469,6 +1527,56 @@ def format_genotypes(ids, lens, loci, gt: Genotypes) -> bytes:
                 str(f[3]), str(f[4]), _c_float_text(ratio[r, k]), str(f[5]), str(f[6]), str(f[7])]
         out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + shown[k][int(orientation[r, k])] + b"\n")
     return b"".join(out)
+
+
+def format_partial_genotypes(ids, lens, loci, pg: PartialGenotypes) -> bytes:
+    """The rows of Engine.genotype_partial as text, one tab-separated line per PARTIAL (read, locus): ID, L, locus index, slot, the flank's
+    distance, the repeat's start (1-origin) and end (inclusive) - the end is start - 1 where nothing extends -, its length in bases, copies -
+    with ">=" in front where the row is open -, matches, ratio (%f of the float), score, tail, and the motif as aligned - its reverse complement
+    for slots 2 and 3.  Reads in input order, loci in the given order within a read.
+    ids, lens: per read its ID (str or bytes) and length; loci: what genotype_partial was given; pg: its result (tensors or numpy)."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    bmot = [v[1].encode() if isinstance(v[1], str) else bytes(v[1]) for v in loci]
+    bid = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+    n, m = len(bid), len(bmot)
+    partial, slot, fdist = host(pg.partial).reshape(n, m), host(pg.slot).reshape(n, m), host(pg.flank_dist).reshape(n, m)
+    window, ext, is_open = host(pg.window).reshape(n, m, 2), host(pg.ext).reshape(n, m, 6), host(pg.open).reshape(n, m)
+    ratio = host(pg.ratio).astype(np.float32).reshape(n, m)
+    if len(lens) != n:
+        raise MtrError(f"{len(lens)} lengths for {n} ids")
+    shown = [(b, b.translate(_COMPLEMENT)[::-1]) for b in bmot]
+    out = []
+    for r, k in zip(*np.nonzero(partial)):
+        e = [int(v) for v in ext[r, k]]
+        s, lo, hi = int(slot[r, k]), int(window[r, k, 0]), int(window[r, k, 1])
+        start, end = (lo, lo + e[0]) if s in (0, 3) else (hi - e[0], hi)
+        cols = [str(int(lens[r])), str(k), str(s), str(int(fdist[r, k])), str(start + 1), str(end), str(e[0]), (">=" if is_open[r, k] else "") + str(e[2]),
+                str(e[3]), _c_float_text(ratio[r, k]), str(e[4]), str(e[5])]
+        out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + shown[k][s >> 1] + b"\n")
+    return b"".join(out)
+
+
+def partial_support(pg: PartialGenotypes, calls: "AlleleCalls | None" = None, min_ratio: float = 0.0) -> PartialSupport:
+    """Per locus, what the reads that do not span it say (plain torch on the tensors' own device, no kernel): the partial rows, the open rows,
+    the largest copies among the open rows with ratio >= min_ratio (float32) and, with the locus' calls given, n_beyond: how many of those rows
+    hold more copies than the larger called allele calls.call[:, 1] - evidence of an allele longer than the one called.  call_alleles itself
+    is unchanged: these rows are lower bounds, no values to rank."""
+    import torch
+
+    partial, is_open = pg.partial != 0, pg.open != 0
+    copies = pg.ext[:, :, 2]
+    good = is_open & (pg.ratio >= torch.tensor(min_ratio, dtype=torch.float32, device=pg.ratio.device))
+    zero = torch.zeros((), dtype=copies.dtype, device=copies.device)
+    top = torch.where(good, copies, zero).amax(dim=0) if copies.shape[0] else torch.zeros(copies.shape[1], dtype=copies.dtype, device=copies.device)
+    beyond = None
+    if calls is not None:
+        larger = calls.call[:, 1].to(copies.device)
+        if larger.shape[0] != copies.shape[1]:
+            raise MtrError(f"{larger.shape[0]} calls for {copies.shape[1]} loci")
+        beyond = (good & (copies > larger[None, :])).sum(dim=0)
+    return PartialSupport(partial.sum(dim=0), is_open.sum(dim=0), top, beyond)
 
 
 def format_allele_calls(loci, calls: AlleleCalls) -> bytes:

@@ -42,6 +42,7 @@
 #include "motif_loci.hip.inc"
 #include "flank_search.hip.inc"
 #include "genotype.hip.inc"
+#include "partial.hip.inc"
 #include "allele_call.hip.inc"
 #include "fasta.hip.inc"
 #include "fastq.hip.inc"
@@ -232,6 +233,9 @@ struct mtr_ctx {
     // arrays - buffers of its own, so that what the locus search keeps (ml_ready) stays
     DevBuf<int32_t> d_gt_pair, d_gt_i32, d_gt_bin32, d_gt_task32, d_gt_res, d_gt_state; DevBuf<int64_t> d_gt_i64, d_gt_bin64;
     DevBuf<LociIv> d_gt_iv; DevBuf<uint8_t> d_gt_units; DevBuf<unsigned long long> d_gt_counter;
+    // partial genotype (mtr_genotype_partial_device), per call and nothing kept: the rows, the variants' task lists, the tasks' results by row;
+    // d_pt_i32 = status | count | ulen | the work lists' variants, d_pt_i64 = bits | the work lists' firsts
+    DevBuf<int32_t> d_pt_row, d_pt_ext, d_pt_i32; DevBuf<int64_t> d_pt_i64; DevBuf<PtTask> d_pt_task;
     // allele calls (mtr_call_alleles_device), per call and nothing kept, buffers of its own so that what the genotype and the locus search keep stays:
     // d_ac_i32 = count | cursor (spread while the loci are few), d_ac_i64 = support_off | tile_off | state, the keys, the split's prefix sums
     DevBuf<int32_t> d_ac_i32; DevBuf<int64_t> d_ac_i64, d_ac_prefix; DevBuf<unsigned long long> d_ac_keys;
@@ -2477,6 +2481,36 @@ extern "C" mtr_status mtr_search_flanks_device(mtr_ctx *ctx, const char *pattern
     return MTR_OK;
 }
 
+// the genotype's checks of its arguments, in its order, up to the row limit; on MTR_OK: the motifs as the search takes them, the four flank
+// patterns of every locus (A, B, rc A, rc B) as codes
+static mtr_status genotype_check_args(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist, int32_t gain, int32_t mismatch,
+                                      int32_t indel, std::string &mot, std::vector<int64_t> &mot_off, std::vector<std::vector<uint8_t>> &pat)
+{
+    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    if (n_loci <= 0) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
+    if (!seqs || !seq_off) { ctx->err = "seqs or seq_off is NULL"; return MTR_ERR_BAD_ARG; }
+    if (n_loci > INT32_MAX / 4) { ctx->err = "more than 2^29 - 1 loci"; return MTR_ERR_BAD_ARG; }
+    for (int32_t k = 0; k < 3 * n_loci; k++)
+        if (seq_off[k + 1] < seq_off[k]) { ctx->err = "seq_off decreases at locus " + std::to_string(k / 3) + " (sequence " + std::to_string(k % 3) + ")"; return MTR_ERR_BAD_ARG; }
+    // the motifs as the search takes them, for the search's own checks
+    mot.clear(); mot_off.assign(1, 0);
+    for (int32_t l = 0; l < n_loci; l++) { mot.append(seqs + seq_off[3 * l + 1], (size_t)(seq_off[3 * l + 2] - seq_off[3 * l + 1])); mot_off.push_back((int64_t)mot.size()); }
+    { mtr_status st = search_motifs_check_args(ctx, mot.data(), mot_off.data(), n_loci, gain, mismatch, indel); if (st != MTR_OK) return st; }
+    pat.assign((size_t)n_loci * GT_SLOTS, std::vector<uint8_t>());
+    for (int32_t l = 0; l < n_loci; l++)
+        for (int side = 0; side < 2; side++) {
+            const int64_t at = seq_off[3 * l + 2 * side], len = seq_off[3 * l + 2 * side + 1] - at;
+            std::vector<uint8_t> &c = pat[(size_t)l * GT_SLOTS + (size_t)side];
+            { mtr_status st = flank_pattern(ctx, seqs + at, len, "locus " + std::to_string(l) + ", " + (side ? "right" : "left") + " flank", c); if (st != MTR_OK) return st; }
+            pat[(size_t)l * GT_SLOTS + 2 + (size_t)side] = revcomp_codes(c);
+        }
+    if (max_flank_dist < 0) { ctx->err = "max_flank_dist = " + std::to_string(max_flank_dist) + ": at least 0"; return MTR_ERR_BAD_ARG; }
+    const int n = ctx->n_reads;
+    const int64_t rows = (int64_t)n * n_loci;
+    if (2 * rows > (int64_t)INT32_MAX) { ctx->err = std::to_string(n) + " reads x " + std::to_string(n_loci) + " loci in two orientations are more than 2^31 - 1 pairs"; return MTR_ERR_BAD_ARG; }
+    return MTR_OK;
+}
+
 // ---- locus genotyping (genotype.hip.inc) --------------------------------------------------------------------------------------------
 // The flank step over four slots per locus, the pairing, one look at the device (how many windows, their longest), one round of the locus
 // search's kernels over 2 * n_loci single-strand motifs (sized as mtr_search_motif_loci_device sizes a round), the columns.
@@ -2486,28 +2520,10 @@ extern "C" mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, c
     if (!ctx || !out_rows) return MTR_ERR_BAD_ARG;
     *out_rows = 0;
     if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
-    if (n_loci <= 0) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
-    if (!seqs || !seq_off) { ctx->err = "seqs or seq_off is NULL"; return MTR_ERR_BAD_ARG; }
-    if (n_loci > INT32_MAX / 4) { ctx->err = "more than 2^29 - 1 loci"; return MTR_ERR_BAD_ARG; }
-    for (int32_t k = 0; k < 3 * n_loci; k++)
-        if (seq_off[k + 1] < seq_off[k]) { ctx->err = "seq_off decreases at locus " + std::to_string(k / 3) + " (sequence " + std::to_string(k % 3) + ")"; return MTR_ERR_BAD_ARG; }
-    // the motifs as the search takes them, for the search's own checks
-    std::string mot; std::vector<int64_t> mot_off(1, 0);
-    for (int32_t l = 0; l < n_loci; l++) { mot.append(seqs + seq_off[3 * l + 1], (size_t)(seq_off[3 * l + 2] - seq_off[3 * l + 1])); mot_off.push_back((int64_t)mot.size()); }
-    { mtr_status st = search_motifs_check_args(ctx, mot.data(), mot_off.data(), n_loci, gain, mismatch, indel); if (st != MTR_OK) return st; }
-    std::vector<std::vector<uint8_t>> pat((size_t)n_loci * GT_SLOTS);
-    for (int32_t l = 0; l < n_loci; l++)
-        for (int side = 0; side < 2; side++) {
-            const int64_t at = seq_off[3 * l + 2 * side], len = seq_off[3 * l + 2 * side + 1] - at;
-            std::vector<uint8_t> &c = pat[(size_t)l * GT_SLOTS + (size_t)side];
-            { mtr_status st = flank_pattern(ctx, seqs + at, len, "locus " + std::to_string(l) + ", " + (side ? "right" : "left") + " flank", c); if (st != MTR_OK) return st; }
-            pat[(size_t)l * GT_SLOTS + 2 + (size_t)side] = revcomp_codes(c);
-        }
-    if (max_flank_dist < 0) { ctx->err = "max_flank_dist = " + std::to_string(max_flank_dist) + ": at least 0"; return MTR_ERR_BAD_ARG; }
+    std::string mot; std::vector<int64_t> mot_off; std::vector<std::vector<uint8_t>> pat;
+    { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, mot, mot_off, pat); if (st != MTR_OK) return st; }
     const int n = ctx->n_reads, M2 = 2 * n_loci;
     const int64_t rows = (int64_t)n * n_loci;
-    if (2 * rows > (int64_t)INT32_MAX) { ctx->err = std::to_string(n) + " reads x " + std::to_string(n_loci) + " loci in two orientations are more than 2^31 - 1 pairs"; return MTR_ERR_BAD_ARG; }
     { mtr_status st = search_motifs_check_size(ctx, mot_off.data(), n_loci); if (st != MTR_OK) return st; }
     *out_rows = rows;
     if (!dst) return MTR_OK;
@@ -2573,6 +2589,100 @@ extern "C" mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, c
     }
     const GenotypesOut out = { dst->spanning, dst->orientation, dst->flank_dist, dst->window, dst->fields, dst->score, dst->ratio };
     hipLaunchKernelGGL(mtr_k_geno_out, per_row, b256, 0, ctx->stream, (const int32_t *)ctx->d_gt_pair, (const int32_t *)ctx->d_gt_res, rows, out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- partial genotype (partial.hip.inc) ------------------------------------------------------------------------------------------------
+// The genotype's checks and its flank step, the pairing and the choice of slot, one look at the device (the status and every variant's number
+// of tasks), one launch of the extension per bucket that has tasks, the columns.
+extern "C" mtr_status mtr_genotype_partial_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist,
+                                                  int32_t gain, int32_t mismatch, int32_t indel, int32_t max_tail, const mtr_partial_dst *dst, int64_t *out_rows)
+{
+    if (!ctx || !out_rows) return MTR_ERR_BAD_ARG;
+    *out_rows = 0;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    std::string mot; std::vector<int64_t> mot_off; std::vector<std::vector<uint8_t>> pat;
+    { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, mot, mot_off, pat); if (st != MTR_OK) return st; }
+    for (int32_t l = 0; l < n_loci; l++)
+        if (mot_off[(size_t)l + 1] - mot_off[(size_t)l] > MDP_MAX_U) {
+            ctx->err = "locus " + std::to_string(l) + ": a motif of " + std::to_string(mot_off[(size_t)l + 1] - mot_off[(size_t)l]) + " bases, the partial genotype takes at most " + std::to_string(MDP_MAX_U);
+            return MTR_ERR_BAD_ARG;
+        }
+    if (max_tail < 0) { ctx->err = "max_tail = " + std::to_string(max_tail) + ": at least 0"; return MTR_ERR_BAD_ARG; }
+    const int n = ctx->n_reads;
+    const int64_t rows = (int64_t)n * n_loci;
+    *out_rows = rows;
+    if (!dst) return MTR_OK;
+    if (dst->cap_rows < rows) { ctx->err = "destination holds " + std::to_string(dst->cap_rows) + " rows, " + std::to_string(rows) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (!dst->partial || !dst->slot || !dst->flank_dist || !dst->window || !dst->ext || !dst->ratio || !dst->open) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    { mtr_status st = flank_scan(ctx, pat); if (st != MTR_OK) return st; }
+    // the variants of every locus: M, reversed M, rc M, reversed rc M, as motif_ext takes them
+    const size_t V = (size_t)n_loci * 4, nl = (size_t)n_loci, nr = (size_t)n;
+    std::vector<uint64_t> bits(V); std::vector<int32_t> ulen(nl);
+    for (int32_t l = 0; l < n_loci; l++) {
+        const int U = (int)(mot_off[(size_t)l + 1] - mot_off[(size_t)l]);
+        std::vector<uint8_t> c((size_t)U);
+        for (int t = 0; t < U; t++) { const char ch = mot[(size_t)mot_off[(size_t)l] + (size_t)t]; c[(size_t)t] = (uint8_t)(ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : 3); }
+        const std::vector<uint8_t> rc = revcomp_codes(c), rev(c.rbegin(), c.rend()), rrc(rc.rbegin(), rc.rend());
+        const std::vector<uint8_t> *four[4] = { &c, &rev, &rc, &rrc };
+        for (int k = 0; k < 4; k++) bits[(size_t)l * 4 + (size_t)k] = mdp_motif_bits(four[k]->data(), U);
+        ulen[(size_t)l] = U;
+    }
+    // device copies: d_pt_i32 = status | count | ulen | the work lists' variants, d_pt_i64 = bits | the work lists' firsts (a list per bucket)
+    HIPCHK(ctx->d_pt_i32.ensure((1 + 2 * V + nl) * 4)); HIPCHK(ctx->d_pt_i64.ensure((2 * V + 4) * 8));
+    HIPCHK(ctx->d_pt_row.ensure((size_t)rows * PT_ROW * 4)); HIPCHK(ctx->d_pt_ext.ensure((size_t)rows * PT_EXT * 4)); HIPCHK(ctx->d_pt_task.ensure(V * nr * sizeof(PtTask)));
+    int32_t *d_status = ctx->d_pt_i32, *d_count = d_status + 1, *d_ulen = d_count + V, *d_wslot = d_ulen + nl;
+    int64_t *d_bits = ctx->d_pt_i64, *d_wfirst = d_bits + V;
+    HIPCHK(hipMemsetAsync(d_status, 0, (1 + V) * 4, ctx->stream));
+    HIPCHK(copy_sync(ctx, d_ulen, ulen.data(), nl * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_bits, bits.data(), V * 8, hipMemcpyHostToDevice));
+    const dim3 per_row((unsigned)((rows + 255) / 256)), b256(256);
+    const PartialPairArgs pa = { ctx->d_fl_res, ctx->d_lens, n_loci, max_flank_dist, n, rows, ctx->d_pt_row, ctx->d_pt_task, d_count, d_status };
+    hipLaunchKernelGGL(mtr_k_partial_pair, per_row, b256, 0, ctx->stream, pa);
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> head(1 + V);
+    HIPCHK(copy_sync(ctx, head.data(), d_status, (1 + V) * 4, hipMemcpyDeviceToHost));
+    bool sane = head[0] == DEV_OK;
+    for (size_t v = 0; v < V; v++) sane = sane && head[1 + v] >= 0 && head[1 + v] <= n;
+    if (!sane) { ctx->err = "the partial genotype's pairing failed on the device (status " + std::to_string(head[0]) + ")"; return MTR_ERR_HIP; }
+    // a work list per bucket: entries (variant, first group) of the variants that have tasks
+    std::vector<int32_t> wslot; std::vector<int64_t> wfirst;
+    struct Launch { int ub; size_t slot_at, first_at; int32_t entries; int64_t groups; } launches[4];
+    int n_launch = 0;
+    for (int ub = 4; ub <= MDP_MAX_U; ub *= 2) {
+        Launch la = { ub, wslot.size(), wfirst.size(), 0, 0 };
+        for (size_t v = 0; v < V; v++)
+            if (head[1 + v] > 0 && mdp_bucket(ulen[v >> 2]) == ub) { wslot.push_back((int32_t)v); wfirst.push_back(la.groups); la.entries++; la.groups += ((int64_t)head[1 + v] + 63) / 64; }
+        wfirst.push_back(la.groups);
+        if (la.entries > 0) launches[n_launch++] = la;
+    }
+    if (n_launch > 0) {
+        HIPCHK(copy_sync(ctx, d_wslot, wslot.data(), wslot.size() * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_wfirst, wfirst.data(), wfirst.size() * 8, hipMemcpyHostToDevice));
+        PartialExtArgs a{};
+        a.b.packed = ctx->d_packed; a.b.woff = ctx->d_woff; a.b.lens = ctx->d_lens; a.b.order = nullptr; a.b.n_reads = n;
+        a.tasks = ctx->d_pt_task; a.count = d_count; a.bits = (const uint64_t *)d_bits; a.ulen = d_ulen;
+        a.n_reads = n; a.n_loci = n_loci; a.G = gain; a.MM = mismatch; a.D = indel; a.ext = ctx->d_pt_ext; a.status = d_status;
+        for (int k = 0; k < n_launch; k++) {
+            const Launch &la = launches[k];
+            a.work = { d_wslot + la.slot_at, d_wfirst + la.first_at, la.entries, la.groups };
+            DBG("partial genotype: bucket %d: %d variants, %lld groups", la.ub, la.entries, (long long)la.groups);
+            const dim3 grid((unsigned)la.groups), b64(64);
+            if (la.ub == 4) hipLaunchKernelGGL(mtr_k_ext_lanes<4>, grid, b64, 0, ctx->stream, a);
+            else if (la.ub == 8) hipLaunchKernelGGL(mtr_k_ext_lanes<8>, grid, b64, 0, ctx->stream, a);
+            else if (la.ub == 16) hipLaunchKernelGGL(mtr_k_ext_lanes<16>, grid, b64, 0, ctx->stream, a);
+            else hipLaunchKernelGGL(mtr_k_ext_lanes<32>, grid, b64, 0, ctx->stream, a);
+            HIPCHK(hipGetLastError());
+        }
+        // the status before the columns: a failed call writes nothing
+        int32_t dev = 0;
+        HIPCHK(copy_sync(ctx, &dev, d_status, 4, hipMemcpyDeviceToHost));
+        if (dev != DEV_OK) { ctx->err = "the partial genotype's extensions failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
+    }
+    const PartialOut out = { dst->partial, dst->slot, dst->flank_dist, dst->window, dst->ext, dst->ratio, dst->open };
+    hipLaunchKernelGGL(mtr_k_partial_out, per_row, b256, 0, ctx->stream, (const int32_t *)ctx->d_pt_row, (const int32_t *)ctx->d_pt_ext, (const int32_t *)d_ulen, n_loci, max_tail, rows, out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;

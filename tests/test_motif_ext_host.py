@@ -1,0 +1,27 @@
+"""The per-lane anchored extension of the partial genotype on the CPU: mtr_amd/csrc/motif_ext.h (the function mtr_k_ext_lanes<UB> runs, one task per
+lane) is built by the plain host C++ compiler into tests/motif_ext_check.cpp, a program of its own that compares ext_len, motif_bases, matches
+and score with a full-matrix DP written there - both directions, every bucket with U at its edges, lo and hi at all 16 residues of a word,
+windows of 0, 1 and U - 1 bases, six score sets, the packed text sized to the window so that a load beyond it trips.  It is built twice: plain,
+and with the address and undefined-behaviour sanitizers (no library is loaded into Python under a sanitizer: the check is a program with its
+own main)."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "motif_ext_check.cpp")
+
+
+@pytest.mark.parametrize("flags", [["-O2"], ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]], ids=["plain", "sanitizers"])
+def test_the_lane_extension_against_a_full_matrix_dp(tmp_path, flags):
+    gxx = shutil.which("g++")
+    assert gxx, "no g++"
+    exe = str(tmp_path / "motif_ext_check")
+    subprocess.run([gxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", *flags, "-o", exe, SRC], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    print(r.stdout)
+    assert "cases checked" in r.stdout and r.stdout.rstrip().endswith(": ok") and r.stderr == ""
+    assert int(r.stdout.split()[0]) >= 10000

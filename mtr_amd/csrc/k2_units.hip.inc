@@ -27,6 +27,16 @@
 #ifndef MTR_WAVES_PER_SIMD
 #define MTR_WAVES_PER_SIMD 4       // 16 wavefronts per CU = 128 VGPRs each (an experiment build may lower it: fewer spills, less latency hiding)
 #endif
+// The walk and polish kernels wait on memory; their bound leaves each SIMD 128 of its 512 registers beside four of their wavefronts: one DP wavefront of another batch
+// in flight.  (Registers only.  LDS is handed out in granules of 1 280 bytes, tests/dev/coresidency_probe.hip: the 10 080-byte arena below takes eight of a CU's 128,
+// sixteen wavefronts take them all, and no wavefront that declares any LDS enters beside them until the arena kernels fit seven granules - DESIGN.md 4.11.)
+#ifndef MTR_LAT_WAVES_PER_SIMD
+#define MTR_LAT_WAVES_PER_SIMD 5
+#endif
+#define MTR_LDS_PER_CU (160 * 1024)
+#define MTR_LDS_GRANULE 1280
+#define MTR_LDS_ALLOC(bytes) (((bytes) + MTR_LDS_GRANULE - 1) / MTR_LDS_GRANULE * MTR_LDS_GRANULE)
+#define MTR_ARENA_CORESIDENT_BYTES (7 * MTR_LDS_GRANULE)     // what an arena kernel (arena + counters) may declare for four DP wavefronts to fit beside sixteen of its own
 #define K2_TAB_CAP 2048            // 32-bit words of the LDS table area (8 KB)
 #define K2_TAB_MAX_WIDTH 1400      // windows up to this many positions use the LDS table
 #define K2_EMPTY (-1)

@@ -438,7 +438,7 @@ __global__ __launch_bounds__(64) void mtr_k_walk_screen(K2Args a, StagedArgs s)
 // One work item per candidate range: the first k of the window (s.k_first of them).  92 % of the ranges end there: the
 // frequency bound says no larger k can have a node seen more than five times.  A range that found a candidate, or whose
 // larger k may still, gets its block; every remaining k becomes a work item of mtr_k_walks_k.
-__global__ __launch_bounds__(64, MTR_WAVES_PER_SIMD) void mtr_k_walks(K2Args a, StagedArgs s)
+__global__ __launch_bounds__(64, MTR_LAT_WAVES_PER_SIMD) void mtr_k_walks(K2Args a, StagedArgs s)
 {
     __shared__ __attribute__((aligned(16))) int s_arena[MTR_ARENA_INTS];
     __shared__ unsigned long long s_cnt[CNT_N];
@@ -1257,7 +1257,7 @@ DEVINL void st_member_ctx(K2Ctx &c, const K2Args &a, int rd) { c.rd = rd; c.L = 
 // polish_repeat (consensus.c:610-704) needs the k-mer table of the repeat for the record's k and is a serial walk over the unit: inside
 // mtr_k_revise_quads it held up the three other revisions of its wavefront.  Here every revision of the batch is a work item: the polished unit,
 // its length and the candidate's node frequencies go to the revision's record in the arena.
-__global__ __launch_bounds__(64, MTR_WAVES_PER_SIMD) void mtr_k_polish(K2Args a, StagedArgs s)
+__global__ __launch_bounds__(64, MTR_LAT_WAVES_PER_SIMD) void mtr_k_polish(K2Args a, StagedArgs s)
 {
     __shared__ __attribute__((aligned(16))) int s_arena[MTR_ARENA_INTS];
     __shared__ unsigned long long s_cnt[CNT_N];
@@ -1455,16 +1455,20 @@ DEVINL void st_fwd1p_any(int C, const DpOct &q, uint8_t *cells, int maxrows, int
     default: dp_forward1p_h8<8>(q, cells, maxrows, best); break;
     }
 }
+// LDS: the slots' state and the counters, nothing else (MTR_RQ_LDS_BYTES: one allocation granule).  The kernel used to declare the per-read kernel's 10 KB arena
+// and kept two things in it: the slots' state, and the votes of a vote traceback (9 (U + 1) words).  The votes go to the wavefront's global scratch, where those
+// of units above 226 bases always went (c.lds_keys = nullptr: revise_sub and the pass's own traceback take cons / miss); DESIGN.md 4.11.
+#define MTR_RQ_LDS_BYTES (RQ_SLOTS * 64 + CNT_N * 8)
+// the largest DP kernel's side of the sum: four of them beside sixteen arena wavefronts of seven granules.  (The arena kernels' side does not hold yet: eight granules.)
+static_assert(16 * MTR_ARENA_CORESIDENT_BYTES + 4 * MTR_LDS_ALLOC(MTR_RQ_LDS_BYTES) <= MTR_LDS_PER_CU, "four DP wavefronts beside sixteen arena wavefronts");
+static_assert(16 * MTR_LDS_ALLOC(MTR_ARENA_INTS * 4 + CNT_N * 8) <= MTR_LDS_PER_CU, "sixteen wavefronts of an arena kernel per CU");
 __global__ __launch_bounds__(64, MTR_WAVES_PER_SIMD) void mtr_k_revise_quads(K2Args a, StagedArgs s)
 {
-    __shared__ __attribute__((aligned(16))) int s_arena[MTR_ARENA_INTS];
-    __shared__ unsigned long long s_cnt[CNT_N];
-    // the slots' state lives in the staging rows of the look-ahead (1 KB, idle in this kernel): as an array of its own it took the workgroup over a sixteenth of
-    // the CU's LDS - 15 wavefronts per CU instead of 16
     typedef __attribute__((address_space(3))) StRevMember lds_StRevMember;
-    static_assert(sizeof(StRevMember) * RQ_SLOTS <= 4 * 256, "the slots' state fits the staging rows");
-    lds_StRevMember *s_mem = (lds_StRevMember *)(s_arena + K2_TAB_CAP + MTRC_MAX_SEEDS + 4);
-    int *s_keys = s_arena, *s_seeds = s_arena + K2_TAB_CAP, *s_stage = s_seeds + MTRC_MAX_SEEDS + 4;
+    __shared__ __attribute__((aligned(16))) StRevMember s_slots[RQ_SLOTS];
+    __shared__ unsigned long long s_cnt[CNT_N];
+    static_assert(sizeof(StRevMember) == 64 && sizeof(s_slots) + sizeof(s_cnt) == MTR_RQ_LDS_BYTES && MTR_RQ_LDS_BYTES <= 2048, "mtr_k_revise_quads: the LDS it uses, at most 2 KB");
+    lds_StRevMember *s_mem = (lds_StRevMember *)s_slots;
     const int lane = lane_id();
     if (lane < CNT_N) s_cnt[lane] = 0ull;
     if (lane < RQ_SLOTS) { s_mem[lane].state = RS_EMPTY; s_mem[lane].round = 0; s_mem[lane].id = -1; }
@@ -1473,7 +1477,7 @@ __global__ __launch_bounds__(64, MTR_WAVES_PER_SIMD) void mtr_k_revise_quads(K2A
     c.a = &a; c.wc = s_cnt;
     c.sc = a.scratch + (size_t)blockIdx.x * a.scratch_per_wave;
     c.y = k2_layout(a.Lmax, a.cells_cap);
-    c.lds_keys = (lds_int *)s_keys; c.seeds = (lds_int *)s_seeds; c.stage = (lds_int *)s_stage;
+    c.lds_keys = nullptr; c.seeds = nullptr; c.stage = nullptr;        // no table, no seeds, no look-ahead here (polish ran in mtr_k_polish)
     c.ties = (int *)(c.sc + c.y.ties); c.fresh = c.ties + MTRC_MAX_TIEBREAKS;
     c.memo_n = 0; c.memo_qs = c.memo_qe = -1; c.memo_U = 0; c.rmemo_n = 0;
     const unsigned n_slots = (unsigned)uni(s.quad_cls[ST_QCLASSES]);           // entries of `sorted` (a class's tail may hold -1)
@@ -1610,10 +1614,10 @@ __global__ __launch_bounds__(64, MTR_WAVES_PER_SIMD) void mtr_k_revise_quads(K2A
                     valid = revise_sub(c, t, G, MM, D, dp_in, unch, S3) ? 1 : 0; unchanged = unch ? 1 : 0;
                 } else if (in_pass) {
                     t.G = G; t.MM = MM; t.D = D;
-                    lds_int *lv = ((U + 1) * 9 <= K2_TAB_CAP) ? c.lds_keys : (lds_int *)nullptr;
+                    lds_int *lv = (lds_int *)nullptr;      // the votes: global scratch (no arena in this kernel)
                     const unsigned long long t_b = clk();
-                    if (lv) { for (int tt = lane; tt < (U + 1) * 9; tt += 64) lv[tt] = 0; }
-                    else { for (int tt = lane; tt < (U + 1) * 5; tt += 64) cons[tt] = 0; for (int tt = lane; tt < (U + 1) * 4; tt += 64) miss[tt] = 0; }
+                    for (int tt = lane; tt < (U + 1) * 5; tt += 64) cons[tt] = 0;
+                    for (int tt = lane; tt < (U + 1) * 4; tt += 64) miss[tt] = 0;
                     wave_sync_mem();
                     dp_in.stop_i = 0; dp_in.end_i = 0; dp_in.mat = dp_in.mis = dp_in.ins = dp_in.del = dp_in.scanned = 0; dp_in.end_j = bvg > 0 ? bjg : 0;
                     valid = 1;

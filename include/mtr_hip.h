@@ -513,6 +513,45 @@ typedef struct mtr_genotypes_dst {
 mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist,
                                     int32_t gain, int32_t mismatch, int32_t indel, const mtr_genotypes_dst *dst, int64_t *out_rows);
 
+/* ---- catalogue genotype: the genotype's spanning rows for a locus list of any length ---------------------------------------------------------------
+ * mtr_genotype_loci_device scans every read against every flank and writes a row per (read, locus): a catalogue of tens of thousands of loci, of
+ * which a read spans a handful, does not fit it.  This call returns exactly the rows that call would write with spanning = 1 - every column bit for
+ * bit - as a list sorted by (read, locus), and does no work sized reads x loci.  It is not an approximation:
+ *   seeds       a pattern p of m bases, K = max_flank_dist and q = seed_len with m >= (K + 1) * q has the K + 1 disjoint seeds p[i * q .. i * q + q),
+ *               i = 0 .. K.  A substring of the read within K edits of p leaves at least one seed untouched: that seed occurs in the read exactly.
+ *   candidate   (read, locus, orientation o) where the read holds a seed of BOTH patterns of o - A and B for o = 0, rc A and rc B for o = 1 (the
+ *               seeds of the reverse complement are taken from the reverse complement).  Every other orientation is invalid by the genotype's
+ *               definition, whatever its flank hits are.
+ *   rows        for a candidate the two flank hits F(.) are the genotype's own; the pairing rule runs with a non-candidate orientation counted
+ *               as invalid, and a spanning (read, locus) is a row: read, locus, and the seven columns as mtr_genotype_loci_device defines them.
+ * The number of rows R is known only after the work, so there are two entry points, as the locus search's: the context keeps the result, the copy
+ * hands it out.
+ * mtr_genotype_catalog_device: seqs / seq_off, the scores and the protocol are mtr_genotype_loci_device's, and so are the checks, in its order,
+ * including the limit of 2^30 - 1 (read, locus) pairs - the alignment path's pair ids are 32-bit (read * 2 * n_loci + 2 * locus + orientation), so a
+ * catalogue is limited by n_reads * n_loci although nothing of that size is allocated - and MTR_ERR_DP_TOO_LARGE, decided from the whole reads.
+ * Then MTR_ERR_BAD_ARG for seed_len outside 8..16 and for a flank shorter than (max_flank_dist + 1) * seed_len (mtr_last_error names the locus and
+ * the side).  MTR_ERR_OVERFLOW for more than 2^31 - 1 seed hits or 2^30 - 1 candidates.  On MTR_OK *out_rows = R, *out_candidates = the number of
+ * (read, locus, orientation) candidates verified (how selective the seeds were), and the rows are kept; a failed call keeps nothing.  An upload of
+ * any kind and the next catalogue call (whatever its outcome) discard what is kept; a run, the locus search and the other genotype calls do not.
+ * mtr_genotype_catalog_copy_device copies the kept rows, device to device, into caller-owned DEVICE memory of the context's GPU: read [R] and
+ * locus [R], ascending by (read, locus), and rows.* with R rows (spanning is 1 throughout).  MTR_ERR_BAD_ARG if nothing is kept or dst is NULL;
+ * MTR_ERR_OVERFLOW if rows.cap_rows < R, and then nothing is written; MTR_ERR_BAD_ARG if R > 0 and a column is NULL; else the columns are written
+ * and the context's stream is synchronised before the call returns.  Two calls with the same arguments give byte-identical columns.
+ * What the call is meant for: seeds that are rare in the reads.  A position's cost is one filter look; a seed hit costs a table probe and an entry
+ * per (locus, slot) that has the seed, and a read's hits are compared pairwise to find its candidates (quadratic in the read's hits).  With
+ * 4^seed_len well above the catalogue's 4 * (max_flank_dist + 1) * n_loci seeds - seed_len >= 12 for 100 000 loci - a 2 kb read has tens to
+ * hundreds of hits; at seed_len = 8 (65 536 codes) a catalogue of more than a few thousand loci makes every position a hit of several entries
+ * and the call slower than the dense one.  Choose the largest seed_len the flanks admit. */
+typedef struct mtr_catalog_dst {
+    int32_t *read;           /* [R] */
+    int32_t *locus;          /* [R] */
+    mtr_genotypes_dst rows;  /* the genotype's columns, R rows; cap_rows is the capacity of all nine */
+} mtr_catalog_dst;   /* caller-owned DEVICE memory */
+mtr_status mtr_genotype_catalog_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist,
+                                       int32_t seed_len, int32_t gain, int32_t mismatch, int32_t indel, int64_t *out_rows,
+                                       int64_t *out_candidates);
+mtr_status mtr_genotype_catalog_copy_device(mtr_ctx *ctx, const mtr_catalog_dst *dst);
+
 /* ---- partial genotype: what a read that does not span a locus still proves ------------------------------------------------------------------------
  * The genotype answers only for reads that span a locus; an expanded allele is the one a read is least likely to span.  A read that holds one
  * flank and runs off its end inside the repeat proves "at least N copies"; a read whose repeat ends but whose far flank is too damaged to be found
@@ -617,6 +656,17 @@ typedef struct mtr_allele_calls_dst {
 mtr_status mtr_call_alleles_device(mtr_ctx *ctx, const mtr_genotypes_dst *rows, int64_t n_reads, int32_t n_loci,
                                    const mtr_allele_params *prm, void *wait_stream,
                                    const mtr_allele_calls_dst *dst, int64_t *out_support);
+/* mtr_call_alleles_rows_device: the same call - the same definition, parameters, outputs and protocol - over a LIST of n_rows >= 0 genotype rows in
+ * any order, each naming its read and locus in two more DEVICE columns, row_read [n_rows] and row_locus [n_rows] (int32): what
+ * mtr_genotype_catalog_copy_device wrote, or several batches' rows concatenated column by column after the batch's first read's index was added to
+ * its read column.  A row's read and locus come from these columns instead of row / n_loci and row % n_loci; rows->cap_rows >= n_rows.  A (read,
+ * locus) without a row is a pair that does not span.  Checked as above with n_rows (0 .. 2^31 - 1) in place of the dense shape and NULL index
+ * columns refused when n_rows > 0; then, on the device and before any kernel is given dst, MTR_ERR_BAD_ARG for a row whose locus is outside
+ * 0 .. n_loci - 1 or whose read is negative, and for a (locus, read) that more than one row names - the rank's keys (value, read) are distinct
+ * only if it is unique (mtr_last_error names the row, or the pair); nothing is written then. */
+mtr_status mtr_call_alleles_rows_device(mtr_ctx *ctx, const mtr_genotypes_dst *rows, const int32_t *row_read, const int32_t *row_locus,
+                                        int64_t n_rows, int32_t n_loci, const mtr_allele_params *prm, void *wait_stream,
+                                        const mtr_allele_calls_dst *dst, int64_t *out_support);
 
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left

@@ -48,6 +48,11 @@ mtr_status mtr_test_chain(mtr_ctx *ctx, int32_t n_sets, const int64_t *set_off, 
 mtr_status mtr_test_report_lines(mtr_ctx *ctx, int32_t n_rows, const int32_t *fields, const int32_t *read_len, const uint8_t *units,
                                  const int64_t *unit_off, const char *ids, const int64_t *id_off, uint8_t **out_text, int64_t **out_off);
 
+/* What the last successful mtr_genotype_catalog_device call of the context saw: counts[4] = the reads' seed positions, those the filter let
+ * through, the seed hits, the candidates; ms[3] = host clock over the host's index build and upload, the first scan pass up to the look that ends
+ * it, and the rest of the call.  For tests/dev/gpu_catalog.py.  MTR_ERR_BAD_ARG without such a call. */
+mtr_status mtr_test_catalog_stats(mtr_ctx *ctx, int64_t *counts, double *ms);
+
 /* The kernels of mtr_report_motifs_device on caller-given units (the counterpart of mtr_test_chain).  Unit k is units[unit_off[k] ..
  * unit_off[k+1]) (unit_off has n + 1 entries and starts at 0), a repeat of read read[k] with num_freq_unit copies[k] and repeat_len[k].
  * A byte outside ACGT, a unit longer than 500, a decreasing read: MTR_ERR_BAD_ARG.  table_slots sizes the grouping's table so that a small

@@ -4,7 +4,7 @@ Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointer
 (Engine.upload_device / process_device / parse_fasta_device / upload_fasta_device / parse_fastq_device / upload_fastq_device /
 walk_fasta_device / walk_fastq_device /
 export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes / report_motif_tensors / search_motifs / search_motif_loci /
-search_flanks / genotype_loci / genotype_partial) take or return torch tensors;
+search_flanks / genotype_loci / genotype_catalog / genotype_partial) take or return torch tensors;
 they import torch when called.
 The product path is libmtr_hip.so only: importing works without a GPU, but creating an Engine
 without the library or without a HIP device raises — there is no CPU fallback.
@@ -53,7 +53,8 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_parse_fasta_device_window", "mtr_upload_fasta_device_window", "mtr_parse_fastq_device_window", "mtr_upload_fastq_device_window",
            "mtr_report_motifs_device", "mtr_test_unit_motifs", "mtr_search_motifs_device",
            "mtr_search_motif_loci_device", "mtr_motif_loci_copy_device", "mtr_search_flanks_device", "mtr_genotype_loci_device",
-           "mtr_call_alleles_device", "mtr_genotype_partial_device"]
+           "mtr_call_alleles_device", "mtr_genotype_partial_device", "mtr_genotype_catalog_device", "mtr_genotype_catalog_copy_device",
+           "mtr_call_alleles_rows_device", "mtr_test_catalog_stats"]
 ALLELE_COPIES, ALLELE_BASES = 0, 1           # MTR_ALLELE_COPIES, MTR_ALLELE_BASES: the measure of Engine.call_alleles
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
@@ -241,6 +242,42 @@ class Genotypes(NamedTuple):
     ratio: "object"       # float32 [n, m]: matches / repeat_len
 
 
+class CCatalogDst(C.Structure):
+    """mtr_catalog_dst: device pointers of the catalogue genotype's read and locus columns, and the genotype's columns"""
+    _fields_ = [("read", C.c_void_p), ("locus", C.c_void_p), ("rows", CGenotypesDst)]
+
+
+class SparseGenotypes(NamedTuple):
+    """What Engine.genotype_catalog found: the R rows of Genotypes with spanning = 1, as a list sorted by (read, locus), all on the engine's
+    device.  include/mtr_hip.h defines every column.  Several batches' results are joined with torch.cat per column after the batch's first
+    read's index has been added to `read` (and n_reads summed): the joined rows stay sorted."""
+    n_reads: int
+    n_loci: int
+    read: "object"        # int32 [R]
+    locus: "object"       # int32 [R]
+    spanning: "object"    # uint8 [R]: 1
+    orientation: "object" # uint8 [R]
+    flank_dist: "object"  # int32 [R, 2]
+    window: "object"      # int32 [R, 2]
+    fields: "object"      # int32 [R, 8]
+    score: "object"       # int32 [R]
+    ratio: "object"       # float32 [R]
+    candidates: int       # the (read, locus, orientation) candidates the seeds left to be verified
+
+    def to_dense(self) -> "Genotypes":
+        """the same rows as Engine.genotype_loci returns them, zeros where a read does not span a locus (n_reads x n_loci rows: small shapes)"""
+        import torch
+
+        n, m = self.n_reads, self.n_loci
+        at = self.read.long() * m + self.locus.long()
+        cols = []
+        for c in self[4:11]:
+            full = torch.zeros((n * m,) + tuple(c.shape[1:]), dtype=c.dtype, device=c.device)
+            full[at] = c
+            cols.append(full.reshape((n, m) + tuple(c.shape[1:])))
+        return Genotypes(*cols)
+
+
 class CPartialDst(C.Structure):
     """mtr_partial_dst: device pointers of the partial genotype's columns and their capacity"""
     _fields_ = [("partial", C.c_void_p), ("slot", C.c_void_p), ("flank_dist", C.c_void_p), ("window", C.c_void_p), ("ext", C.c_void_p),
@@ -420,10 +457,19 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_search_flanks_device.restype = C.c_int
     lib.mtr_genotype_loci_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [P(CGenotypesDst), P(C.c_int64)]
     lib.mtr_genotype_loci_device.restype = C.c_int
+    lib.mtr_genotype_catalog_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [P(C.c_int64), P(C.c_int64)]
+    lib.mtr_genotype_catalog_device.restype = C.c_int
+    lib.mtr_genotype_catalog_copy_device.argtypes = [C.c_void_p, P(CCatalogDst)]
+    lib.mtr_genotype_catalog_copy_device.restype = C.c_int
     lib.mtr_genotype_partial_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [P(CPartialDst), P(C.c_int64)]
     lib.mtr_genotype_partial_device.restype = C.c_int
     lib.mtr_call_alleles_device.argtypes = [C.c_void_p, P(CGenotypesDst), C.c_int64, C.c_int32, P(CAlleleParams), C.c_void_p, P(CAlleleCallsDst), P(C.c_int64)]
     lib.mtr_call_alleles_device.restype = C.c_int
+    lib.mtr_call_alleles_rows_device.argtypes = [C.c_void_p, P(CGenotypesDst), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(CAlleleParams), C.c_void_p, P(CAlleleCallsDst),
+                                                 P(C.c_int64)]
+    lib.mtr_call_alleles_rows_device.restype = C.c_int
+    lib.mtr_test_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
+    lib.mtr_test_catalog_stats.restype = C.c_int
     lib.mtr_parse_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaDst), P(CFastaInfo)]
     lib.mtr_parse_fasta_device.restype = C.c_int
     lib.mtr_upload_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaInfo)]
@@ -573,6 +619,32 @@ def genotype_rows_args(gt, device: int):
     if sp.device.index != device:
         raise MtrError(f"the genotype rows are on {sp.device}, the engine on cuda:{device}")
     return n, m
+
+
+def sparse_rows_args(sg, device: int):
+    """The checks of Engine.call_alleles on a SparseGenotypes, made before the library is called: read, locus (int32 [R]), spanning (uint8 [R]),
+    window (int32 [R, 2]), fields (int32 [R, 8]) and ratio (float32 [R]) contiguous torch tensors on the engine's GPU, n_loci >= 1.  Returns
+    (R, n_loci); raises MtrError."""
+    import torch
+
+    if isinstance(sg.n_loci, bool) or not isinstance(sg.n_loci, (int, np.integer)) or sg.n_loci < 1:
+        raise MtrError(f"n_loci must be an integer >= 1, got {sg.n_loci!r}")
+    if not isinstance(sg.read, torch.Tensor) or sg.read.dim() != 1:
+        raise MtrError("the rows' read column must be a 1-D torch tensor")
+    R = int(sg.read.numel())
+    want = (("read", torch.int32, (R,)), ("locus", torch.int32, (R,)), ("spanning", torch.uint8, (R,)), ("window", torch.int32, (R, 2)), ("fields", torch.int32, (R, 8)),
+            ("ratio", torch.float32, (R,)))
+    for name, dtype, shape in want:
+        t = getattr(sg, name)
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise MtrError(f"the rows' {name} must be a contiguous {dtype} tensor of shape {shape}")
+    for name, _, _ in want:
+        t = getattr(sg, name)
+        if not t.is_cuda:
+            raise MtrError(f"the genotype rows must be GPU tensors, got tensors on {t.device}")
+        if t.device.index != device:
+            raise MtrError(f"the genotype rows are on {t.device}, the engine on cuda:{device}")
+    return R, int(sg.n_loci)
 
 
 def _fasta(info: CFastaInfo, text, offsets, lens, id_off, ids: bytes) -> Fasta:
@@ -1016,6 +1088,39 @@ class Engine:
         self._check(self.lib.mtr_genotype_loci_device(*args, C.byref(dst), C.byref(nr)), "mtr_genotype_loci_device")
         return gt
 
+    def genotype_catalog(self, loci, max_flank_dist: int, seed_len: "int | None" = None, gain: int = 1, mismatch: int = 1, indel: int = 1) -> SparseGenotypes:
+        """Catalogue genotype (mtr_genotype_catalog_device, mtr_genotype_catalog_copy_device): loci and scores as genotype_loci takes them, any
+        number of loci.  Returns the rows genotype_loci would mark spanning, bit for bit, as a SparseGenotypes sorted by (read, locus): a read
+        is compared with a locus only where it holds an exact seed_len-mer of both flanks (exact: max_flank_dist edits cannot touch all of a
+        flank's max_flank_dist + 1 disjoint seeds), so every flank needs (max_flank_dist + 1) * seed_len bases, 8 <= seed_len <= 16.
+        seed_len = None picks the largest the flanks admit.  Needs no run and changes nothing a run left; follows genotype_loci's stream
+        handling."""
+        import torch
+
+        if isinstance(loci, (str, bytes, bytearray)) or not hasattr(loci, "__len__"):
+            raise MtrError(f"loci must be a sequence of (left_flank, motif, right_flank), got {type(loci).__name__}")
+        flat = []
+        for k, locus in enumerate(loci):
+            if isinstance(locus, (str, bytes, bytearray)) or not hasattr(locus, "__len__") or len(locus) != 3:
+                raise MtrError(f"locus {k} must be (left_flank, motif, right_flank)")
+            flat.extend(locus)
+        if seed_len is None:
+            seed_len = pick_seed_len(loci, max_flank_dist)
+        data, off = pack_ids(flat)
+        m = len(loci)
+        nr, nc = C.c_int64(), C.c_int64()
+        self._check(self.lib.mtr_genotype_catalog_device(self.h, data.ctypes.data, off.ctypes.data, m, int(max_flank_dist), int(seed_len), int(gain), int(mismatch),
+                                                         int(indel), C.byref(nr), C.byref(nc)), "mtr_genotype_catalog_device")
+        R = int(nr.value)
+        dev = torch.device("cuda", self.device)
+        new = lambda dtype, *tail: torch.empty((R,) + tail, dtype=dtype, device=dev)     # noqa: E731
+        cols = (new(torch.int32), new(torch.int32), new(torch.uint8), new(torch.uint8), new(torch.int32, 2), new(torch.int32, 2), new(torch.int32, 8), new(torch.int32),
+                new(torch.float32))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CCatalogDst(cols[0].data_ptr(), cols[1].data_ptr(), CGenotypesDst(*[t.data_ptr() for t in cols[2:]], R))
+        self._check(self.lib.mtr_genotype_catalog_copy_device(self.h, C.byref(dst)), "mtr_genotype_catalog_copy_device")
+        return SparseGenotypes(self.n_reads, m, *cols, int(nc.value))
+
     def genotype_partial(self, loci, max_flank_dist: int, gain: int = 1, mismatch: int = 1, indel: int = 1, max_tail: int = 10) -> PartialGenotypes:
         """Partial genotype (mtr_genotype_partial_device): loci as genotype_loci takes them, motifs of at most 32 bases.  A read that does not
         span a locus but holds one of its flanks within max_flank_dist edits is extended from that flank towards the read's end by the anchored
@@ -1048,7 +1153,9 @@ class Engine:
 
     def call_alleles(self, gt, measure="copies", min_ratio: float = 0.0, min_support: int = 2, min_percent: int = 20, min_sep: int = 1) -> AlleleCalls:
         """Allele calls (mtr_call_alleles_device): the rows of genotype_loci - one call's Genotypes, or several batches' joined with torch.cat(dim=0)
-        column by column - reduced per locus.  A row supports its locus when it spans it and its ratio is at least min_ratio (a row with an empty
+        column by column - reduced per locus.  gt may also be a SparseGenotypes (mtr_call_alleles_rows_device): genotype_catalog's result, or
+        several batches' - SparseGenotypes(n_reads summed, n_loci, then every column joined with torch.cat after the batch's first read's index
+        was added to its `read`) - with the same calls as the dense rows give; no (read, locus) may occur twice.  A row supports its locus when it spans it and its ratio is at least min_ratio (a row with an empty
         window always does); its value is its copies (measure "copies" / ALLELE_COPIES) or its window's bases ("bases" / ALLELE_BASES).  Per locus
         the supporting reads are sorted by (value, read) and split into two alleles where a split exists whose smaller side has min_support reads
         and min_percent percent of them and whose medians lie min_sep apart - the split of least absolute deviation from the two medians.  Needs no
@@ -1062,22 +1169,37 @@ class Engine:
             code = int(measure)
         else:
             raise MtrError(f"measure must be 'copies', 'bases', ALLELE_COPIES or ALLELE_BASES, got {measure!r}")
-        n, m = genotype_rows_args(gt, self.device)
         dev = torch.device("cuda", self.device)
-        rows = CGenotypesDst(gt.spanning.data_ptr(), None, None, gt.window.data_ptr(), gt.fields.data_ptr(), None, gt.ratio.data_ptr(), n * m)
         prm = CAlleleParams(code, float(min_ratio), int(min_support), int(min_percent), int(min_sep))
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        args = (self.h, C.byref(rows), n, m, C.byref(prm), stream)
+        if isinstance(gt, SparseGenotypes):
+            R, m = sparse_rows_args(gt, self.device)
+            ptr = lambda t: t.data_ptr() if R else None     # noqa: E731
+            rows = CGenotypesDst(ptr(gt.spanning), None, None, ptr(gt.window), ptr(gt.fields), None, ptr(gt.ratio), R)
+            call, name = self.lib.mtr_call_alleles_rows_device, "mtr_call_alleles_rows_device"
+            args = (self.h, C.byref(rows), ptr(gt.read), ptr(gt.locus), R, m, C.byref(prm), stream)
+        else:
+            n, m = genotype_rows_args(gt, self.device)
+            rows = CGenotypesDst(gt.spanning.data_ptr(), None, None, gt.window.data_ptr(), gt.fields.data_ptr(), None, gt.ratio.data_ptr(), n * m)
+            call, name = self.lib.mtr_call_alleles_device, "mtr_call_alleles_device"
+            args = (self.h, C.byref(rows), n, m, C.byref(prm), stream)
         ns = C.c_int64()
-        self._check(self.lib.mtr_call_alleles_device(*args, None, C.byref(ns)), "mtr_call_alleles_device")
+        self._check(call(*args, None, C.byref(ns)), name)
         S = int(ns.value)
         new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)     # noqa: E731
         calls = AlleleCalls(new(torch.int64, m + 1), new(torch.int32, S), new(torch.int32, S), new(torch.uint8, S), new(torch.uint8, m),
                             new(torch.int32, m, 2), new(torch.int32, m, 2), new(torch.int64, m, 2))
         torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
         dst = CAlleleCallsDst(*[t.data_ptr() if t.numel() else None for t in calls], m, S)
-        self._check(self.lib.mtr_call_alleles_device(*args, C.byref(dst), C.byref(ns)), "mtr_call_alleles_device")
+        self._check(call(*args, C.byref(dst), C.byref(ns)), name)
         return calls
+
+    def test_catalog_stats(self):
+        """mtr_test_catalog_stats: what the last genotype_catalog call saw - (positions, passed by the filter, seed hits, candidates) and the
+        host-clock ms of (index build and upload, first scan pass, the rest)"""
+        counts, ms = (C.c_int64 * 4)(), (C.c_double * 3)()
+        self._check(self.lib.mtr_test_catalog_stats(self.h, counts, ms), "mtr_test_catalog_stats")
+        return tuple(int(v) for v in counts), tuple(float(v) for v in ms)
 
     def test_unit_motifs(self, units, read=None, copies=None, repeat_len=None, table_slots: int = 0) -> ReportMotifs:
         """mtr_test_unit_motifs: the kernels of report_motif_tensors on caller-given units, one bytes (or str) per unit.  read: the read of
@@ -1526,6 +1648,47 @@ def format_genotypes(ids, lens, loci, gt: Genotypes) -> bytes:
         cols = [str(int(lens[r])), str(k), str(int(orientation[r, k])), str(int(fdist[r, k, 0])), str(int(fdist[r, k, 1])), str(lo + 1), str(hi), str(hi - lo),
                 str(f[3]), str(f[4]), _c_float_text(ratio[r, k]), str(f[5]), str(f[6]), str(f[7])]
         out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + shown[k][int(orientation[r, k])] + b"\n")
+    return b"".join(out)
+
+
+def pick_seed_len(loci, max_flank_dist: int) -> int:
+    """The seed length Engine.genotype_catalog takes by default: the largest q <= 16 with (max_flank_dist + 1) * q bases in every flank of loci
+    (a sequence of (left_flank, motif, right_flank)); raises MtrError where that is below 8 - the flanks are too short for an exact screen at
+    this distance."""
+    if isinstance(max_flank_dist, bool) or not isinstance(max_flank_dist, (int, np.integer)) or max_flank_dist < 0:
+        raise MtrError(f"max_flank_dist must be an integer >= 0, got {max_flank_dist!r}")
+    if len(loci) == 0:
+        raise MtrError("loci is empty: at least one locus is needed")
+    shortest, where = min((len(locus[2 * side]), (k, side)) for k, locus in enumerate(loci) for side in (0, 1))
+    q = min(16, shortest // (int(max_flank_dist) + 1))
+    if q < 8:
+        raise MtrError(f"locus {where[0]}, {'right' if where[1] else 'left'} flank: {shortest} bases admit seeds of {q} bases at max_flank_dist = {max_flank_dist}, "
+                       "fewer than 8")
+    return q
+
+
+def format_sparse_genotypes(ids, lens, loci, sg: SparseGenotypes) -> bytes:
+    """The rows of Engine.genotype_catalog as text: byte for byte format_genotypes of the dense result, without building it.
+    ids, lens: per read its ID (str or bytes) and length; loci: what genotype_catalog was given; sg: its result (tensors or numpy)."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    bmot = [v[1].encode() if isinstance(v[1], str) else bytes(v[1]) for v in loci]
+    bid = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+    if len(lens) != len(bid):
+        raise MtrError(f"{len(lens)} lengths for {len(bid)} ids")
+    if (len(bid), len(bmot)) != (sg.n_reads, sg.n_loci):
+        raise MtrError(f"{len(bid)} ids and {len(bmot)} loci for the rows of {sg.n_reads} reads and {sg.n_loci} loci")
+    read, locus, orientation = host(sg.read), host(sg.locus), host(sg.orientation)
+    fdist, window, fields, ratio = host(sg.flank_dist), host(sg.window), host(sg.fields), host(sg.ratio).astype(np.float32)
+    shown = [(b, b.translate(_COMPLEMENT)[::-1]) for b in bmot]
+    out = []
+    for i in range(len(read)):
+        r, k, f = int(read[i]), int(locus[i]), [int(v) for v in fields[i]]
+        lo, hi = int(window[i, 0]), int(window[i, 1])
+        cols = [str(int(lens[r])), str(k), str(int(orientation[i])), str(int(fdist[i, 0])), str(int(fdist[i, 1])), str(lo + 1), str(hi), str(hi - lo),
+                str(f[3]), str(f[4]), _c_float_text(ratio[i]), str(f[5]), str(f[6]), str(f[7])]
+        out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + shown[k][int(orientation[i])] + b"\n")
     return b"".join(out)
 
 

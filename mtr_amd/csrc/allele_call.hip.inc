@@ -1,4 +1,5 @@
-// allele_call.hip.inc — allele calls per locus (mtr_call_alleles_device): genotype rows [read][locus] in device memory reduced to one row per
+// allele_call.hip.inc — allele calls per locus (mtr_call_alleles_device; mtr_call_alleles_rows_device: the same over a list of rows that name
+// their read and locus): genotype rows [read][locus] in device memory reduced to one row per
 // locus - the supporting reads ranked by (value, read), and the ranked list split into one or two alleles.  The definition is
 // include/mtr_hip.h's ("allele calls"); the split itself is allele_split.h, shared with the host.  Five launches on the context's stream, no
 // waiting between workgroups, every output an exact integer:
@@ -33,6 +34,7 @@
 
 struct AlleleArgs {
     const uint8_t *spanning; const int32_t *window, *fields; const float *ratio;        // the genotype's columns, row = read * n_loci + locus
+    const int32_t *row_read, *row_locus;                                                // or NULL: rows in any order, each with its read and locus (mtr_call_alleles_rows_device)
     int64_t rows; int32_t n_loci, measure; float min_ratio; AlleleRule rule;
     int32_t *count, *cursor;        // [n_loci * cstride] each, zeroed by the host: locus l's at l * cstride
     int32_t cstride;                // AL_SPREAD up to AL_SPREAD_LOCI loci, else 1
@@ -52,6 +54,13 @@ DEVINL bool allele_row(const AlleleArgs &a, int64_t p, int32_t &v)
     if (hi != lo && !(a.ratio[p] >= a.min_ratio)) return false;
     v = a.measure == 0 ? a.fields[8 * p + 3] : hi - lo;
     return true;
+}
+
+// the read and the locus of row p < a.rows
+DEVINL void allele_where(const AlleleArgs &a, int64_t p, int64_t &rd, int &l)
+{
+    if (a.row_locus) { rd = a.row_read[p]; l = a.row_locus[p]; }
+    else { rd = p / a.n_loci; l = (int)(p - rd * a.n_loci); }
 }
 
 // counter[l] += 1 for every lane with take set; returns the counter's value before this lane's own add (what a cursor hands out).  Every lane
@@ -81,7 +90,8 @@ __global__ __launch_bounds__(AL_BLOCK) void mtr_k_allele_count(AlleleArgs a)
     const int64_t p = (int64_t)blockIdx.x * AL_BLOCK + threadIdx.x;
     int32_t v;
     const bool sup = allele_row(a, p, v);
-    const int l = p < a.rows ? (int)(p % a.n_loci) : 0;
+    int64_t rd = 0; int l = 0;
+    if (p < a.rows) allele_where(a, p, rd, l);
     if (sup && v < 0) atomicMin((unsigned long long *)&a.state[AL_BAD], (unsigned long long)p);
     (void)allele_take(a.count, l * a.cstride, sup, a.n_loci < 64);
 }
@@ -109,8 +119,8 @@ __global__ __launch_bounds__(AL_BLOCK) void mtr_k_allele_fill(AlleleArgs a)
     const int64_t p = (int64_t)blockIdx.x * AL_BLOCK + threadIdx.x;
     int32_t v;
     const bool sup = allele_row(a, p, v);
-    const int64_t rd = p < a.rows ? p / a.n_loci : 0;
-    const int l = p < a.rows ? (int)(p - rd * a.n_loci) : 0;
+    int64_t rd = 0; int l = 0;
+    if (p < a.rows) allele_where(a, p, rd, l);
     const int slot = allele_take(a.cursor, l * a.cstride, sup, a.n_loci < 64);
     if (!sup) return;
     const int64_t at = a.off[l] + slot;

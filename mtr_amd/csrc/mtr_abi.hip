@@ -42,6 +42,7 @@
 #include "motif_loci.hip.inc"
 #include "flank_search.hip.inc"
 #include "genotype.hip.inc"
+#include "catalog.hip.inc"
 #include "partial.hip.inc"
 #include "allele_call.hip.inc"
 #include "fasta.hip.inc"
@@ -233,6 +234,15 @@ struct mtr_ctx {
     // arrays - buffers of its own, so that what the locus search keeps (ml_ready) stays
     DevBuf<int32_t> d_gt_pair, d_gt_i32, d_gt_bin32, d_gt_task32, d_gt_res, d_gt_state; DevBuf<int64_t> d_gt_i64, d_gt_bin64;
     DevBuf<LociIv> d_gt_iv; DevBuf<uint8_t> d_gt_units; DevBuf<unsigned long long> d_gt_counter;
+    // catalogue genotype (mtr_genotype_catalog_device), per call: the seed index (d_ct_ix = filter | key | run | entries | the slots' lengths), the
+    // slots' masks, per read its hits' and candidates' counts and offsets, the hits and their head flags, the candidates (d_ct_cand = read | key |
+    // span), their flank hits, the status and the filter's count; the alignment goes through the genotype's own d_gt_* buffers.  What
+    // mtr_genotype_catalog_copy_device hands out (gc_ready: gc_rows rows) is kept until an upload or the next catalogue call.
+    bool gc_ready = false; int64_t gc_rows = 0;
+    int64_t gc_counts[4] = { 0, 0, 0, 0 }; double gc_ms[3] = { 0, 0, 0 };       // the last catalogue call, for mtr_test_catalog_stats
+    DevBuf<int32_t> d_ct_ix, d_ct_count, d_ct_hits, d_ct_cand, d_ct_flank, d_ct_status; DevBuf<int64_t> d_ct_off, d_ct_rowoff; DevBuf<uint64_t> d_ct_masks;
+    DevBuf<uint8_t> d_ct_head; DevBuf<unsigned long long> d_ct_passed;
+    DevBuf<int32_t> d_gc_read, d_gc_locus, d_gc_fdist, d_gc_window, d_gc_fields, d_gc_score; DevBuf<float> d_gc_ratio; DevBuf<uint8_t> d_gc_spanning, d_gc_orientation;
     // partial genotype (mtr_genotype_partial_device), per call and nothing kept: the rows, the variants' task lists, the tasks' results by row;
     // d_pt_i32 = status | count | ulen | the work lists' variants, d_pt_i64 = bits | the work lists' firsts
     DevBuf<int32_t> d_pt_row, d_pt_ext, d_pt_i32; DevBuf<int64_t> d_pt_i64; DevBuf<PtTask> d_pt_task;
@@ -320,7 +330,7 @@ static hipError_t copy_sync(mtr_ctx *ctx, void *dst, const void *src, size_t byt
 }
 
 // forget the resident batch (its buffers stay allocated for the next one)
-static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->mo_ready = false; ctx->ml_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
+static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->mo_ready = false; ctx->ml_ready = false; ctx->gc_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
 
 extern "C" int mtr_abi_version(void) { return MTR_ABI_VERSION; }
 
@@ -2390,6 +2400,16 @@ static std::vector<uint8_t> revcomp_codes(const std::vector<uint8_t> &c)
     return r;
 }
 
+// the eight masks (FL_MASKS) of a slot's pattern, as both flank kernels take them (the 32-bit masks are their low halves), and the word it runs in
+static void flank_slot_masks(const std::vector<uint8_t> &p, uint64_t *out)
+{
+    const int m = (int)p.size();
+    const FbvMasks<uint64_t> eq = fbv_masks<uint64_t>(p.data(), m, 0), rev = fbv_masks<uint64_t>(p.data(), m, 1);
+    const uint64_t v[FL_MASKS] = { eq.a, eq.c, eq.g, eq.t, rev.a, rev.c, rev.g, rev.t };
+    std::copy(v, v + FL_MASKS, out);
+}
+static bool flank_is_wide(const mtr_ctx *ctx, int m) { return !(m <= 32 && ctx->sw.flank_word != 64); }
+
 // every slot's pattern against every read: ctx->d_fl_res[read * S + slot][FL_RES], complete when this returns
 static mtr_status flank_scan(mtr_ctx *ctx, const std::vector<std::vector<uint8_t>> &pat)
 {
@@ -2405,11 +2425,9 @@ static mtr_status flank_scan(mtr_ctx *ctx, const std::vector<std::vector<uint8_t
     for (int k = 0; k < 2; k++) l_first[k].push_back(0);
     for (size_t slot = 0; slot < S; slot++) {
         const int m = (int)pat[slot].size();
-        const FbvMasks<uint64_t> eq = fbv_masks<uint64_t>(pat[slot].data(), m, 0), rev = fbv_masks<uint64_t>(pat[slot].data(), m, 1);     // (the 32-bit masks are their low halves)
-        const uint64_t v[FL_MASKS] = { eq.a, eq.c, eq.g, eq.t, rev.a, rev.c, rev.g, rev.t };
-        std::copy(v, v + FL_MASKS, masks.begin() + (ptrdiff_t)(slot * FL_MASKS));
+        flank_slot_masks(pat[slot], masks.data() + slot * FL_MASKS);
         plen[slot] = m;
-        const int k = m <= 32 && ctx->sw.flank_word != 64 ? 0 : 1;
+        const int k = flank_is_wide(ctx, m) ? 1 : 0;
         l_slot[k].push_back((int32_t)slot); l_first[k].push_back(l_first[k].back() + groups);
     }
     // device copies: d_fl_i32 = order | plen | the lists' slots, d_fl_i64 = masks | the lists' firsts
@@ -2511,6 +2529,9 @@ static mtr_status genotype_check_args(mtr_ctx *ctx, const char *seqs, const int6
     return MTR_OK;
 }
 
+static mtr_status genotype_align(mtr_ctx *ctx, const std::string &mot, const std::vector<int64_t> &mot_off, int32_t n_loci, int64_t N, int max_len,
+                                 int32_t gain, int32_t mismatch, int32_t indel, const char *who);      // (defined below the call)
+
 // ---- locus genotyping (genotype.hip.inc) --------------------------------------------------------------------------------------------
 // The flank step over four slots per locus, the pairing, one look at the device (how many windows, their longest), one round of the locus
 // search's kernels over 2 * n_loci single-strand motifs (sized as mtr_search_motif_loci_device sizes a round), the columns.
@@ -2522,7 +2543,7 @@ extern "C" mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, c
     if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
     std::string mot; std::vector<int64_t> mot_off; std::vector<std::vector<uint8_t>> pat;
     { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, mot, mot_off, pat); if (st != MTR_OK) return st; }
-    const int n = ctx->n_reads, M2 = 2 * n_loci;
+    const int n = ctx->n_reads;
     const int64_t rows = (int64_t)n * n_loci;
     { mtr_status st = search_motifs_check_size(ctx, mot_off.data(), n_loci); if (st != MTR_OK) return st; }
     *out_rows = rows;
@@ -2546,7 +2567,22 @@ extern "C" mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, c
     if (st[LOCI_STATUS] != DEV_OK || N < 0 || N > rows || max_len < 0 || max_len > ctx->Lmax || (N > 0) != (max_len > 0)) {
         ctx->err = "the genotype's pairing failed on the device (status " + std::to_string(st[LOCI_STATUS]) + ")"; return MTR_ERR_HIP;
     }
-    if (N > 0) {
+    if (N > 0) { mtr_status r = genotype_align(ctx, mot, mot_off, n_loci, N, max_len, gain, mismatch, indel, "genotype_loci"); if (r != MTR_OK) return r; }
+    const GenotypesOut out = { dst->spanning, dst->orientation, dst->flank_dist, dst->window, dst->fields, dst->score, dst->ratio };
+    hipLaunchKernelGGL(mtr_k_geno_out, per_row, b256, 0, ctx->stream, (const int32_t *)ctx->d_gt_pair, (const int32_t *)ctx->d_gt_res, rows, out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// The alignment step of the genotype and of the catalogue genotype: the N intervals in ctx->d_gt_iv (the longest of max_len bases, counted in
+// ctx->d_gt_state) through one round of the locus search's path over 2 * n_loci single-strand motifs; their hits are in ctx->d_gt_res on MTR_OK.
+static mtr_status genotype_align(mtr_ctx *ctx, const std::string &mot, const std::vector<int64_t> &mot_off, int32_t n_loci, int64_t N, int max_len,
+                                 int32_t gain, int32_t mismatch, int32_t indel, const char *who)
+{
+    const int n = ctx->n_reads, M2 = 2 * n_loci;
+    int32_t st[LOCI_STATE];
+    {
         // the slots: locus l as given (2 * l) and reverse-complemented (2 * l + 1), one strand each
         const int lane_max = ctx->sw.motif_lane_max, lane_rows = ctx->sw.motif_lane_rows;
         std::string both; std::vector<int64_t> both_off(1, 0);
@@ -2581,15 +2617,201 @@ extern "C" mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, c
         a.hist = ctx->d_gt_bin32; a.groups = a.hist + nb; a.tfirst = ctx->d_gt_bin64; a.gfirst = a.tfirst + nb + 1; a.n_bins = (int32_t)nb;
         a.tbin = ctx->d_gt_task32; a.trank = a.tbin + nt; a.sorted = a.trank + nt; a.wlist = a.sorted + nt; a.res = ctx->d_gt_res;
         a.state = ctx->d_gt_state; a.dp16_max_rows = ctx->sw.dp16_max_rows;
-        { mtr_status r = loci_round(ctx, a, ls, N, max_len, (unsigned long long *)ctx->d_gt_counter, "genotype_loci", 0); if (r != MTR_OK) return r; }
+        { mtr_status r = loci_round(ctx, a, ls, N, max_len, (unsigned long long *)ctx->d_gt_counter, who, 0); if (r != MTR_OK) return r; }
         // the status before the columns: a failed genotype writes nothing
         HIPCHK(copy_sync(ctx, st, ctx->d_gt_state, sizeof st, hipMemcpyDeviceToHost));
         if (st[LOCI_STATUS] == DEV_ERR_DP_TOO_LARGE) { ctx->err = "You need to increse the value of WrapDPsize. (a DP of the genotype exceeded it or its scratch)"; return MTR_ERR_DP_TOO_LARGE; }
         if (st[LOCI_STATUS] != DEV_OK) { ctx->err = "the genotype's alignments failed on the device (status " + std::to_string(st[LOCI_STATUS]) + ")"; return MTR_ERR_HIP; }
     }
-    const GenotypesOut out = { dst->spanning, dst->orientation, dst->flank_dist, dst->window, dst->fields, dst->score, dst->ratio };
-    hipLaunchKernelGGL(mtr_k_geno_out, per_row, b256, 0, ctx->stream, (const int32_t *)ctx->d_gt_pair, (const int32_t *)ctx->d_gt_res, rows, out);
+    return MTR_OK;
+}
+
+// ---- catalogue genotype (catalog.hip.inc) -------------------------------------------------------------------------------------------
+// The genotype's checks; the seed index built on the host (sorted entries, a table of the distinct codes, the filter bitmap) and sent up; the scan
+// in two passes around one look at the device (the hits), the candidates in two passes around another (the candidates); their flank scans, the
+// pairing, a third look (the windows, their longest, the rows), the genotype's alignment step, the rows into the context's buffers.  Every buffer
+// is sized by the reads, by the loci, or by what the scan found: none by reads x loci.
+extern "C" mtr_status mtr_genotype_catalog_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist, int32_t seed_len,
+                                                  int32_t gain, int32_t mismatch, int32_t indel, int64_t *out_rows, int64_t *out_candidates)
+{
+    if (!ctx || !out_rows || !out_candidates) return MTR_ERR_BAD_ARG;
+    *out_rows = 0; *out_candidates = 0;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    ctx->gc_ready = false;                                                                             // whatever happens below, the rows kept before this call are gone
+    std::string mot; std::vector<int64_t> mot_off; std::vector<std::vector<uint8_t>> pat;
+    { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, mot, mot_off, pat); if (st != MTR_OK) return st; }
+    { mtr_status st = search_motifs_check_size(ctx, mot_off.data(), n_loci); if (st != MTR_OK) return st; }
+    if (seed_len < SI_MIN_Q || seed_len > SI_MAX_Q) { ctx->err = "seed_len = " + std::to_string(seed_len) + " outside " + std::to_string(SI_MIN_Q) + ".." + std::to_string(SI_MAX_Q); return MTR_ERR_BAD_ARG; }
+    const int q = seed_len;
+    const int64_t need = ((int64_t)max_flank_dist + 1) * q;
+    for (int32_t l = 0; l < n_loci; l++)
+        for (int side = 0; side < 2; side++) {
+            const size_t m = pat[(size_t)l * GT_SLOTS + (size_t)side].size();
+            if ((int64_t)m < need) {
+                ctx->err = "locus " + std::to_string(l) + ", " + (side ? "right" : "left") + " flank: " + std::to_string(m) + " bases are fewer than (max_flank_dist + 1) * seed_len = " + std::to_string(need);
+                return MTR_ERR_BAD_ARG;
+            }
+        }
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    const auto t_start = std::chrono::steady_clock::now();
+    const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    const int n = ctx->n_reads, seeds = max_flank_dist + 1;
+    const size_t nr = (size_t)n, S = pat.size();
+    // the index: the entries (code, locus * 4 + slot) sorted and made distinct, a table slot per distinct code, the filter over the codes
+    std::vector<std::pair<uint32_t, int32_t>> ent;
+    ent.reserve(S * (size_t)seeds);
+    bool narrow = false, wide = false;
+    std::vector<uint64_t> masks(S * FL_MASKS); std::vector<int32_t> plen(S);
+    for (size_t slot = 0; slot < S; slot++) {
+        const int m = (int)pat[slot].size();
+        for (int i = 0; i < seeds; i++) ent.push_back({ si_seed_code(pat[slot].data() + si_seed_offset(i, q), q), (int32_t)slot });
+        flank_slot_masks(pat[slot], masks.data() + slot * FL_MASKS);
+        plen[slot] = m;
+        (flank_is_wide(ctx, m) ? wide : narrow) = true;
+    }
+    std::sort(ent.begin(), ent.end());
+    ent.erase(std::unique(ent.begin(), ent.end()), ent.end());
+    const size_t E = ent.size();
+    size_t distinct = 0;
+    for (size_t e = 0; e < E; e++) distinct += e == 0 || ent[e].first != ent[e - 1].first;
+    uint32_t cap = 64; while ((size_t)cap < 2 * distinct) cap <<= 1;
+    int fbits = CAT_FILTER_MIN_BITS; while (fbits < CAT_FILTER_MAX_BITS && ((size_t)1 << fbits) < 16 * distinct) fbits++;
+    const size_t fwords = ((size_t)1 << fbits) / 32;
+    std::vector<uint32_t> ix(fwords + 3 * (size_t)cap + E + S, 0);                                     // filter | key | run | entries | plen
+    uint32_t *h_filter = ix.data(), *h_key = h_filter + fwords; int32_t *h_run = (int32_t *)(h_key + cap), *h_ent = h_run + 2 * (size_t)cap, *h_plen = h_ent + E;
+    for (size_t e = 0, first = 0; e < E; e++) {
+        h_ent[e] = ent[e].second;
+        if (e + 1 < E && ent[e + 1].first == ent[e].first) continue;
+        si_filter_set(h_filter, fbits, ent[e].first);
+        if (!si_insert(h_key, h_run, cap, ent[e].first, (int32_t)first, (int32_t)(e + 1 - first))) { ctx->err = "the seed table is full"; return MTR_ERR_HIP; }
+        first = e + 1;
+    }
+    std::copy(plen.begin(), plen.end(), h_plen);
+    HIPCHK(ctx->d_ct_ix.ensure(ix.size() * 4)); HIPCHK(ctx->d_ct_masks.ensure(masks.size() * 8));
+    HIPCHK(ctx->d_ct_count.ensure(2 * nr * 4)); HIPCHK(ctx->d_ct_off.ensure(2 * (nr + 1) * 8)); HIPCHK(ctx->d_ct_status.ensure(4)); HIPCHK(ctx->d_ct_passed.ensure(8));
+    HIPCHK(copy_sync(ctx, ctx->d_ct_ix, ix.data(), ix.size() * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_ct_masks, masks.data(), masks.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(ctx->d_ct_status, 0, 4, ctx->stream)); HIPCHK(hipMemsetAsync(ctx->d_ct_passed, 0, 8, ctx->stream));
+    const uint32_t *d_filter = (const uint32_t *)(int32_t *)ctx->d_ct_ix, *d_key = d_filter + fwords;
+    const int32_t *d_run = (const int32_t *)(d_key + cap), *d_ent = d_run + 2 * (size_t)cap, *d_plen = d_ent + E;
+    int32_t *hit_count = ctx->d_ct_count, *cand_count = hit_count + nr;
+    int64_t *hit_off = ctx->d_ct_off, *cand_off = hit_off + nr + 1;
+    const dim3 per_read((unsigned)n), b64(64), b256(256), one(1), b1024(1024);
+    // the scan: the reads' hits counted, then written
+    const double ms_index = ms_since(t_start);                         // the host's index and its upload (the copies are synchronous)
+    const auto t_scan = std::chrono::steady_clock::now();
+    CatScanArgs sa{};
+    sa.b.packed = ctx->d_packed; sa.b.woff = ctx->d_woff; sa.b.lens = ctx->d_lens; sa.b.order = nullptr; sa.b.n_reads = n;
+    sa.ix = { d_filter, fbits, d_key, d_run, cap }; sa.ent = d_ent; sa.q = q; sa.fill = 0;
+    sa.hit_count = hit_count; sa.hit_off = hit_off; sa.hits = nullptr; sa.passed = ctx->d_ct_passed;
+    hipLaunchKernelGGL(mtr_k_cat_scan, per_read, b64, 0, ctx->stream, sa);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)hit_count, (int64_t)n, hit_off);
     HIPCHK(hipGetLastError());
+    int64_t H = 0, Cn = 0, R = 0;
+    HIPCHK(copy_sync(ctx, &H, hit_off + nr, 8, hipMemcpyDeviceToHost));
+    if (H < 0 || H >= (int64_t)INT32_MAX) { ctx->err = "2^31 - 1 seed hits or more (a read's count saturates there)"; return MTR_ERR_OVERFLOW; }
+    const double ms_scan = ms_since(t_scan);                           // the first scan pass and the offsets, up to the look that ends them
+    const auto t_rest = std::chrono::steady_clock::now();
+    unsigned long long passed = 0;
+    HIPCHK(copy_sync(ctx, &passed, ctx->d_ct_passed, 8, hipMemcpyDeviceToHost));
+    {
+        DBG("genotype_catalog: %zu entries of %zu codes, table of %u slots, filter of 2^%d bits; the filter passed %llu positions, %lld hits", E, distinct, cap, fbits, passed, (long long)H);
+    }
+    if (H > 0) {
+        HIPCHK(ctx->d_ct_hits.ensure((size_t)H * 4)); HIPCHK(ctx->d_ct_head.ensure((size_t)H));
+        sa.fill = 1; sa.hits = ctx->d_ct_hits;
+        hipLaunchKernelGGL(mtr_k_cat_scan, per_read, b64, 0, ctx->stream, sa);
+        CatCandArgs ca{};
+        ca.n_reads = n; ca.fill = 0; ca.hit_off = hit_off; ca.hits = ctx->d_ct_hits; ca.head = ctx->d_ct_head; ca.cand_count = cand_count; ca.cand_off = cand_off;
+        hipLaunchKernelGGL(mtr_k_cat_cands, per_read, b64, 0, ctx->stream, ca);
+        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)cand_count, (int64_t)n, cand_off);
+        HIPCHK(hipGetLastError());
+        HIPCHK(copy_sync(ctx, &Cn, cand_off + nr, 8, hipMemcpyDeviceToHost));
+        if (Cn < 0 || Cn > H) { ctx->err = "the catalogue's candidate lists are inconsistent"; return MTR_ERR_HIP; }
+        if (Cn > (int64_t)INT32_MAX / 2) { ctx->err = std::to_string(Cn) + " candidates are more than 2^30 - 1"; return MTR_ERR_OVERFLOW; }
+        if (Cn > 0) {
+            const size_t nc = (size_t)Cn;
+            HIPCHK(ctx->d_ct_cand.ensure(3 * nc * 4)); HIPCHK(ctx->d_ct_flank.ensure(2 * nc * FL_RES * 4)); HIPCHK(ctx->d_ct_rowoff.ensure((nc + 1) * 8));
+            int32_t *cand_read = ctx->d_ct_cand, *cand_key = cand_read + nc, *span = cand_key + nc;
+            int64_t *row_off = ctx->d_ct_rowoff;
+            ca.fill = 1; ca.cand_read = cand_read; ca.cand_key = cand_key;
+            hipLaunchKernelGGL(mtr_k_cat_cands, per_read, b64, 0, ctx->stream, ca);
+            // the candidates' two flank scans each
+            CatFlankArgs fa{};
+            fa.b = sa.b; fa.cand_read = cand_read; fa.cand_key = cand_key; fa.n_tasks = (int32_t)(2 * Cn);
+            fa.masks = ctx->d_ct_masks; fa.plen = d_plen; fa.all_wide = ctx->sw.flank_word == 64; fa.res = ctx->d_ct_flank; fa.status = ctx->d_ct_status;
+            const dim3 per_task((unsigned)((2 * nc + 63) / 64));
+            if (narrow) hipLaunchKernelGGL(mtr_k_cat_flank<uint32_t>, per_task, b64, 0, ctx->stream, fa);
+            if (wide) hipLaunchKernelGGL(mtr_k_cat_flank<uint64_t>, per_task, b64, 0, ctx->stream, fa);
+            // the pairing, and the rows' places
+            HIPCHK(ctx->d_gt_state.ensure(LOCI_STATE * 4)); HIPCHK(ctx->d_gt_pair.ensure(nc * GT_PAIR * 4)); HIPCHK(ctx->d_gt_iv.ensure(nc * sizeof(LociIv)));
+            HIPCHK(hipMemsetAsync(ctx->d_gt_state, 0, LOCI_STATE * 4, ctx->stream));
+            const dim3 per_cand((unsigned)((nc + 255) / 256));
+            const CatPairArgs pa = { cand_read, cand_key, (int32_t)Cn, ctx->d_ct_flank, n_loci, max_flank_dist, ctx->d_gt_pair, span, ctx->d_gt_iv, (int32_t)Cn, ctx->d_gt_state };
+            hipLaunchKernelGGL(mtr_k_cat_pair, per_cand, b256, 0, ctx->stream, pa);
+            hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)span, Cn, row_off);
+            HIPCHK(hipGetLastError());
+            int32_t st[LOCI_STATE], dev = 0;
+            HIPCHK(copy_sync(ctx, st, ctx->d_gt_state, sizeof st, hipMemcpyDeviceToHost));
+            HIPCHK(copy_sync(ctx, &dev, ctx->d_ct_status, 4, hipMemcpyDeviceToHost));
+            HIPCHK(copy_sync(ctx, &R, row_off + nc, 8, hipMemcpyDeviceToHost));
+            const int64_t N = st[LOCI_NEXT];
+            const int max_len = st[LOCI_MAXLEN];
+            if (dev != DEV_OK) { ctx->err = "the catalogue's flank scans failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
+            if (st[LOCI_STATUS] != DEV_OK || R < 0 || R > Cn || N < 0 || N > R || max_len < 0 || max_len > ctx->Lmax || (N > 0) != (max_len > 0)) {
+                ctx->err = "the catalogue's pairing failed on the device (status " + std::to_string(st[LOCI_STATUS]) + ")"; return MTR_ERR_HIP;
+            }
+            if (N > 0) { mtr_status r = genotype_align(ctx, mot, mot_off, n_loci, N, max_len, gain, mismatch, indel, "genotype_catalog"); if (r != MTR_OK) return r; }
+            if (R > 0) {
+                const size_t rr = (size_t)R;
+                HIPCHK(ctx->d_gc_read.ensure(rr * 4)); HIPCHK(ctx->d_gc_locus.ensure(rr * 4)); HIPCHK(ctx->d_gc_spanning.ensure(rr)); HIPCHK(ctx->d_gc_orientation.ensure(rr));
+                HIPCHK(ctx->d_gc_fdist.ensure(rr * 8)); HIPCHK(ctx->d_gc_window.ensure(rr * 8)); HIPCHK(ctx->d_gc_fields.ensure(rr * 32)); HIPCHK(ctx->d_gc_score.ensure(rr * 4));
+                HIPCHK(ctx->d_gc_ratio.ensure(rr * 4));
+                const CatRowsOut out = { ctx->d_gc_read, ctx->d_gc_locus, { ctx->d_gc_spanning, ctx->d_gc_orientation, ctx->d_gc_fdist, ctx->d_gc_window, ctx->d_gc_fields, ctx->d_gc_score, ctx->d_gc_ratio } };
+                hipLaunchKernelGGL(mtr_k_cat_out, per_cand, b256, 0, ctx->stream, (const int32_t *)cand_read, (const int32_t *)cand_key, (const int32_t *)ctx->d_gt_pair,
+                                   (const int32_t *)span, (const int64_t *)row_off, (const int32_t *)ctx->d_gt_res, (int32_t)Cn, out);
+                HIPCHK(hipGetLastError());
+            }
+        }
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->gc_ready = true; ctx->gc_rows = R;
+    int64_t positions = 0;
+    for (int i = 0; i < n; i++) positions += std::max(0, ctx->lens[(size_t)i] - q + 1);
+    ctx->gc_counts[0] = positions; ctx->gc_counts[1] = (int64_t)passed; ctx->gc_counts[2] = H; ctx->gc_counts[3] = Cn;
+    ctx->gc_ms[0] = ms_index; ctx->gc_ms[1] = ms_scan; ctx->gc_ms[2] = ms_since(t_rest);
+    *out_rows = R; *out_candidates = Cn;
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_test_catalog_stats(mtr_ctx *ctx, int64_t *counts, double *ms)
+{
+    if (!ctx || !counts || !ms) return MTR_ERR_BAD_ARG;
+    if (!ctx->gc_ready) { ctx->err = "no catalogue call to report on"; return MTR_ERR_BAD_ARG; }
+    std::copy(ctx->gc_counts, ctx->gc_counts + 4, counts); std::copy(ctx->gc_ms, ctx->gc_ms + 3, ms);
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_genotype_catalog_copy_device(mtr_ctx *ctx, const mtr_catalog_dst *dst)
+{
+    if (!ctx) return MTR_ERR_BAD_ARG;
+    if (!ctx->gc_ready) { ctx->err = "no rows kept: mtr_genotype_catalog_device comes first (an upload discards what it kept)"; return MTR_ERR_BAD_ARG; }
+    if (!dst) { ctx->err = "dst is NULL"; return MTR_ERR_BAD_ARG; }
+    const int64_t R = ctx->gc_rows;
+    const mtr_genotypes_dst &g = dst->rows;
+    if (g.cap_rows < R) { ctx->err = "destination holds " + std::to_string(g.cap_rows) + " rows, " + std::to_string(R) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (R > 0 && (!dst->read || !dst->locus || !g.spanning || !g.orientation || !g.flank_dist || !g.window || !g.fields || !g.score || !g.ratio)) {
+        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
+    }
+    if (R == 0) return MTR_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
+    const size_t r = (size_t)R;
+    HIPCHK(hipMemcpyAsync(dst->read, ctx->d_gc_read, r * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->locus, ctx->d_gc_locus, r * 4, dd, ctx->stream));
+    HIPCHK(hipMemcpyAsync(g.spanning, ctx->d_gc_spanning, r, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(g.orientation, ctx->d_gc_orientation, r, dd, ctx->stream));
+    HIPCHK(hipMemcpyAsync(g.flank_dist, ctx->d_gc_fdist, r * 8, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(g.window, ctx->d_gc_window, r * 8, dd, ctx->stream));
+    HIPCHK(hipMemcpyAsync(g.fields, ctx->d_gc_fields, r * 32, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(g.score, ctx->d_gc_score, r * 4, dd, ctx->stream));
+    HIPCHK(hipMemcpyAsync(g.ratio, ctx->d_gc_ratio, r * 4, dd, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
 }
@@ -2691,44 +2913,65 @@ extern "C" mtr_status mtr_genotype_partial_device(mtr_ctx *ctx, const char *seqs
 // ---- allele calls (allele_call.hip.inc) ------------------------------------------------------------------------------------------------
 // The arguments' checks, the count and the offsets, one look at the device (the status, S, the tiles), then the fill, the rank and the split
 // straight into the caller's columns.  No batch is needed and none is touched.
-extern "C" mtr_status mtr_call_alleles_device(mtr_ctx *ctx, const mtr_genotypes_dst *rows, int64_t n_reads, int32_t n_loci, const mtr_allele_params *prm,
-                                              void *wait_stream, const mtr_allele_calls_dst *dst, int64_t *out_support)
+// rows: the four input columns with R rows; row_read / row_locus: NULL for the dense layout (row = read * n_loci + locus), else the rows' own
+static mtr_status call_alleles_rows(mtr_ctx *ctx, const mtr_genotypes_dst *rows, int64_t R, int32_t n_loci, const int32_t *row_read, const int32_t *row_locus,
+                                    const mtr_allele_params *prm, void *wait_stream, const mtr_allele_calls_dst *dst, int64_t *out_support)
 {
-    if (!ctx || !out_support) return MTR_ERR_BAD_ARG;
-    *out_support = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    if (!rows || !prm) { ctx->err = "rows or prm is NULL"; return MTR_ERR_BAD_ARG; }
-    if (n_reads < 1) { ctx->err = "n_reads = " + std::to_string(n_reads) + ": at least one read is needed"; return MTR_ERR_BAD_ARG; }
-    if (n_loci < 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
-    if (n_reads > (int64_t)INT32_MAX / n_loci) { ctx->err = std::to_string(n_reads) + " reads x " + std::to_string(n_loci) + " loci are more than 2^31 - 1 rows"; return MTR_ERR_BAD_ARG; }
     if (prm->measure != MTR_ALLELE_COPIES && prm->measure != MTR_ALLELE_BASES) { ctx->err = "measure " + std::to_string(prm->measure) + " is neither MTR_ALLELE_COPIES nor MTR_ALLELE_BASES"; return MTR_ERR_BAD_ARG; }
     if (!(prm->min_ratio >= 0.0f && prm->min_ratio <= 1.0f)) { ctx->err = "min_ratio " + std::to_string(prm->min_ratio) + " outside 0..1"; return MTR_ERR_BAD_ARG; }
     if (prm->min_support < 1) { ctx->err = "min_support " + std::to_string(prm->min_support) + ": at least 1"; return MTR_ERR_BAD_ARG; }
     if (prm->min_percent < 0 || prm->min_percent > 50) { ctx->err = "min_percent " + std::to_string(prm->min_percent) + " outside 0..50"; return MTR_ERR_BAD_ARG; }
     if (prm->min_sep < 1) { ctx->err = "min_sep " + std::to_string(prm->min_sep) + ": at least 1"; return MTR_ERR_BAD_ARG; }
-    const int64_t R = n_reads * n_loci;
-    if (!rows->spanning || !rows->window || !rows->fields || !rows->ratio) { ctx->err = "an input column (spanning, window, fields, ratio) is NULL"; return MTR_ERR_BAD_ARG; }
+    if (R > 0 && (!rows->spanning || !rows->window || !rows->fields || !rows->ratio)) { ctx->err = "an input column (spanning, window, fields, ratio) is NULL"; return MTR_ERR_BAD_ARG; }
     if (rows->cap_rows < R) { ctx->err = "cap_rows " + std::to_string(rows->cap_rows) + " of the input is below " + std::to_string(R) + " rows"; return MTR_ERR_BAD_ARG; }
     HIPCHK(hipSetDevice(ctx->device));
-    { mtr_status st = check_device_ptr(ctx, rows->spanning, R, "rows->spanning", "the rows' bytes"); if (st != MTR_OK) return st; }
-    { mtr_status st = check_device_ptr(ctx, (const uint8_t *)rows->window, R * 8, "rows->window", "the rows' bytes"); if (st != MTR_OK) return st; }
-    { mtr_status st = check_device_ptr(ctx, (const uint8_t *)rows->fields, R * 32, "rows->fields", "the rows' bytes"); if (st != MTR_OK) return st; }
-    { mtr_status st = check_device_ptr(ctx, (const uint8_t *)rows->ratio, R * 4, "rows->ratio", "the rows' bytes"); if (st != MTR_OK) return st; }
+    if (R > 0) {
+        { mtr_status st = check_device_ptr(ctx, rows->spanning, R, "rows->spanning", "the rows' bytes"); if (st != MTR_OK) return st; }
+        { mtr_status st = check_device_ptr(ctx, (const uint8_t *)rows->window, R * 8, "rows->window", "the rows' bytes"); if (st != MTR_OK) return st; }
+        { mtr_status st = check_device_ptr(ctx, (const uint8_t *)rows->fields, R * 32, "rows->fields", "the rows' bytes"); if (st != MTR_OK) return st; }
+        { mtr_status st = check_device_ptr(ctx, (const uint8_t *)rows->ratio, R * 4, "rows->ratio", "the rows' bytes"); if (st != MTR_OK) return st; }
+        if (row_locus) {
+            { mtr_status st = check_device_ptr(ctx, (const uint8_t *)row_read, R * 4, "row_read", "the rows' bytes"); if (st != MTR_OK) return st; }
+            { mtr_status st = check_device_ptr(ctx, (const uint8_t *)row_locus, R * 4, "row_locus", "the rows' bytes"); if (st != MTR_OK) return st; }
+        }
+    }
     const size_t nl = (size_t)n_loci;
     const size_t cstride = n_loci <= AL_SPREAD_LOCI ? AL_SPREAD : 1;
     HIPCHK(ctx->d_ac_i32.ensure(2 * nl * cstride * 4)); HIPCHK(ctx->d_ac_i64.ensure((2 * (nl + 1) + AL_STATE) * 8));
     AlleleArgs a{};
     a.spanning = rows->spanning; a.window = rows->window; a.fields = rows->fields; a.ratio = rows->ratio;
+    a.row_read = R > 0 ? row_read : nullptr; a.row_locus = R > 0 ? row_locus : nullptr;
     a.rows = R; a.n_loci = n_loci; a.measure = prm->measure; a.min_ratio = prm->min_ratio; a.rule = { prm->min_support, prm->min_percent, prm->min_sep };
     a.count = ctx->d_ac_i32; a.cursor = a.count + nl * cstride; a.cstride = (int32_t)cstride; a.off = ctx->d_ac_i64; a.tile_off = a.off + nl + 1; a.state = a.tile_off + nl + 1;
     // the rows come from the caller's stream: the kernels wait for it there, not for the whole device
     if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
     HIPCHK(hipEventRecord(ctx->ev_text, (hipStream_t)wait_stream));
     HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
+    if (a.row_locus) {
+        // the index columns before anything else reads them: every locus in range, every (locus, read) once - the rank's keys are distinct by that
+        unsigned long long cap = 64; while (cap < 2 * (unsigned long long)R) cap <<= 1;
+        HIPCHK(ctx->d_ac_keys.ensure((size_t)(cap + 2) * 8));
+        unsigned long long *set = ctx->d_ac_keys, *bad = set + cap;
+        HIPCHK(hipMemsetAsync(set, 0xff, (size_t)(cap + 2) * 8, ctx->stream));
+        hipLaunchKernelGGL(mtr_k_cat_rows_check, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, ctx->stream, row_read, row_locus, R, n_loci, set, cap, bad);
+        HIPCHK(hipGetLastError());
+        unsigned long long found[2];
+        HIPCHK(copy_sync(ctx, found, bad, sizeof found, hipMemcpyDeviceToHost));
+        if (found[0] != ~0ull) {
+            int32_t rl[2] = { 0, 0 };
+            HIPCHK(copy_sync(ctx, &rl[0], row_read + found[0], 4, hipMemcpyDeviceToHost)); HIPCHK(copy_sync(ctx, &rl[1], row_locus + found[0], 4, hipMemcpyDeviceToHost));
+            ctx->err = "row " + std::to_string(found[0]) + ": read " + std::to_string(rl[0]) + " is negative or locus " + std::to_string(rl[1]) + " is outside 0.." + std::to_string(n_loci - 1);
+            return MTR_ERR_BAD_ARG;
+        }
+        if (found[1] != ~0ull) {
+            ctx->err = "(locus " + std::to_string(found[1] >> 32) + ", read " + std::to_string(found[1] & 0xffffffffull) + ") is given by more than one row";
+            return MTR_ERR_BAD_ARG;
+        }
+    }
     HIPCHK(hipMemsetAsync(ctx->d_ac_i32, 0, 2 * nl * cstride * 4, ctx->stream));
     HIPCHK(hipMemsetAsync(a.state, 0xff, 8, ctx->stream));
     const dim3 per_row((unsigned)((R + AL_BLOCK - 1) / AL_BLOCK)), blk(AL_BLOCK);
-    hipLaunchKernelGGL(mtr_k_allele_count, per_row, blk, 0, ctx->stream, a);
+    if (R > 0) hipLaunchKernelGGL(mtr_k_allele_count, per_row, blk, 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(mtr_k_allele_offsets, dim3(1), dim3(64), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
@@ -2739,7 +2982,13 @@ extern "C" mtr_status mtr_call_alleles_device(mtr_ctx *ctx, const mtr_genotypes_
     *out_support = S;
     if (st[AL_BAD] != -1) {
         const int64_t p = st[AL_BAD];
-        ctx->err = "row " + std::to_string(p) + " (read " + std::to_string(p / n_loci) + ", locus " + std::to_string(p % n_loci) + ") supports its locus with a negative value";
+        int64_t rd = p / n_loci, l = p % n_loci;
+        if (a.row_locus) {
+            int32_t rl[2] = { 0, 0 };
+            HIPCHK(copy_sync(ctx, &rl[0], row_read + p, 4, hipMemcpyDeviceToHost)); HIPCHK(copy_sync(ctx, &rl[1], row_locus + p, 4, hipMemcpyDeviceToHost));
+            rd = rl[0]; l = rl[1];
+        }
+        ctx->err = "row " + std::to_string(p) + " (read " + std::to_string(rd) + ", locus " + std::to_string(l) + ") supports its locus with a negative value";
         return MTR_ERR_BAD_ARG;
     }
     if (!dst) return MTR_OK;
@@ -2762,6 +3011,32 @@ extern "C" mtr_status mtr_call_alleles_device(mtr_ctx *ctx, const mtr_genotypes_
     HIPCHK(hipMemcpyAsync(dst->support_off, a.off, (nl + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
+}
+
+extern "C" mtr_status mtr_call_alleles_device(mtr_ctx *ctx, const mtr_genotypes_dst *rows, int64_t n_reads, int32_t n_loci, const mtr_allele_params *prm,
+                                              void *wait_stream, const mtr_allele_calls_dst *dst, int64_t *out_support)
+{
+    if (!ctx || !out_support) return MTR_ERR_BAD_ARG;
+    *out_support = 0;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    if (!rows || !prm) { ctx->err = "rows or prm is NULL"; return MTR_ERR_BAD_ARG; }
+    if (n_reads < 1) { ctx->err = "n_reads = " + std::to_string(n_reads) + ": at least one read is needed"; return MTR_ERR_BAD_ARG; }
+    if (n_loci < 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
+    if (n_reads > (int64_t)INT32_MAX / n_loci) { ctx->err = std::to_string(n_reads) + " reads x " + std::to_string(n_loci) + " loci are more than 2^31 - 1 rows"; return MTR_ERR_BAD_ARG; }
+    return call_alleles_rows(ctx, rows, n_reads * n_loci, n_loci, nullptr, nullptr, prm, wait_stream, dst, out_support);
+}
+
+extern "C" mtr_status mtr_call_alleles_rows_device(mtr_ctx *ctx, const mtr_genotypes_dst *rows, const int32_t *row_read, const int32_t *row_locus, int64_t n_rows,
+                                                   int32_t n_loci, const mtr_allele_params *prm, void *wait_stream, const mtr_allele_calls_dst *dst, int64_t *out_support)
+{
+    if (!ctx || !out_support) return MTR_ERR_BAD_ARG;
+    *out_support = 0;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    if (!rows || !prm) { ctx->err = "rows or prm is NULL"; return MTR_ERR_BAD_ARG; }
+    if (n_rows < 0 || n_rows > (int64_t)INT32_MAX) { ctx->err = "n_rows = " + std::to_string(n_rows) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (n_loci < 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
+    if (n_rows > 0 && (!row_read || !row_locus)) { ctx->err = "row_read or row_locus is NULL"; return MTR_ERR_BAD_ARG; }
+    return call_alleles_rows(ctx, rows, n_rows, n_loci, row_read, row_locus, prm, wait_stream, dst, out_support);
 }
 
 // ---- a FASTA file in device memory (fasta.hip.inc) -----------------------------------------------------------------------------

@@ -25,6 +25,26 @@ mtr_status mtr_test_wrap_dp(mtr_ctx *ctx, int32_t n_tasks, const int32_t *read_i
                             const int32_t *query_end, const uint8_t *units, const int32_t *unit_off,
                             const int32_t *gain, const int32_t *mismatch, const int32_t *indel, int32_t *out8);
 
+/* ONE chosen forward pass of the wrap-around DP, with its tracebacks, on groups the caller chose: group g = tasks group_off[g] .. group_off[g + 1]
+ * (group_off[0] = 0, group_off[n_groups] = the number of tasks), the DPs that share one forward pass.  The task arrays are mtr_test_wrap_dp's.
+ * out16[16 t + 8 p ..] = the eight integers of mtr_test_wrap_dp for task t and parameter set p, same window convention (row i is base
+ * query_start + i).  The two-parameter passes ignore gain / mismatch / indel: p = 0 is (1,1,3), p = 1 is (1,3,1).  The one-parameter passes
+ * take the task's own set, one of (1,1,3), (1,3,1), (5,1,1), and fill p = 0 only (p = 1: zeros).
+ *   MTR_TEST_PASS_WAVE2P  groups of 1 task: dp_wrap2 where dp_wrap2_fits, else dp_wrap twice (dp_two_params_unit's decision)
+ *   MTR_TEST_PASS_Q4      1-4 units of at most 16 bases over the same read and window: dp_forward2p_q4 + tracebacks, under dp_batch_fits
+ *   MTR_TEST_PASS_QUAD2P  1-4 tasks of one DPQ_COLS class: the forward pass and tracebacks of mtr_k_dp2_quads (units <= 128, DPQ_FITS(rows, U, 1, 3))
+ *   MTR_TEST_PASS_FOUR1P  1-4 tasks: a pass of mtr_k_revise_quads with one DP per 16 lanes, at the widest member's width, + counting tracebacks
+ *   MTR_TEST_PASS_OCT1P   1-8 tasks: the same with two DPs per 16 lanes; member d is half d & 1 of lane group d >> 1
+ * A task the batch path would never hand to the pass (the same bounds: units, rows, 16-bit scores, WrapDPsize), a group of another size, members of
+ * QUAD2P classes or Q4 windows that differ, a window outside its read: MTR_ERR_BAD_ARG, the reason names the task; nothing is launched.
+ * The entry sizes its own cell scratch from the passes' block macros, so the batch path's "the block fits this launch's cell budget" terms
+ * (dp_batch_fits' 4 x 16 x rows, DPQ_BLOCK_BYTES / DPQP_BLOCK_BYTES against the cells of a batch) are held against the context's scratch cap
+ * (MTR_SCRATCH_MAX_GB) instead: a group whose block exceeds it is refused in the same way. */
+enum { MTR_TEST_PASS_WAVE2P = 0, MTR_TEST_PASS_Q4 = 1, MTR_TEST_PASS_QUAD2P = 2, MTR_TEST_PASS_FOUR1P = 3, MTR_TEST_PASS_OCT1P = 4 };
+mtr_status mtr_test_wrap_dp_pass(mtr_ctx *ctx, int32_t pass, int32_t n_groups, const int32_t *group_off, const int32_t *read_idx,
+                                 const int32_t *query_start, const int32_t *query_end, const uint8_t *units, const int32_t *unit_off,
+                                 const int32_t *gain, const int32_t *mismatch, const int32_t *indel, int32_t *out16);
+
 /* How the last launch ran: 0 = one kernel, a wavefront per read; 1 = range-parallel; 2 = the staged chain of kernels.
  * (The records do not depend on it; tests pin the policy of mtr_hip.h's mtr_set_overlapped_launches with it.) */
 int32_t mtr_test_last_mode(const mtr_ctx *ctx);

@@ -41,7 +41,7 @@ COUNTER_NAMES = ["dp_calls", "dp_cells", "dp_rows", "revise_dp_calls", "revise_d
 # (per-read kernel: revisions / unchanged units / accepted rounds; walk kernels: cycles by window width; see the CNT_SPARE* uses in csrc)
 EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mtr_process_batch", "mtr_free_results",
            "mtr_upload_batch", "mtr_run_resident", "mtr_fetch_results", "mtr_get_kernel_times", "mtr_get_counters",
-           "mtr_test_ranges", "mtr_test_wrap_dp", "mtr_test_last_mode", "mtr_set_trace", "mtr_get_trace",
+           "mtr_test_ranges", "mtr_test_wrap_dp", "mtr_test_wrap_dp_pass", "mtr_test_last_mode", "mtr_set_trace", "mtr_get_trace",
            "mtr_run_resident_async", "mtr_wait", "mtr_alignments",
            "mtr_file_state_create", "mtr_file_state_destroy", "mtr_upload_batch_in_file", "mtr_file_state_skip",
            "mtr_get_bases_after_read", "mtr_upload_batch_packed", "mtr_fetch_results_packed", "mtr_export_packed_device",
@@ -428,6 +428,8 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_test_ranges.restype = C.c_int
     lib.mtr_test_wrap_dp.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
     lib.mtr_test_wrap_dp.restype = C.c_int
+    lib.mtr_test_wrap_dp_pass.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 10
+    lib.mtr_test_wrap_dp_pass.restype = C.c_int
     lib.mtr_upload_batch_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]
     lib.mtr_upload_batch_packed.restype = C.c_int
     lib.mtr_upload_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
@@ -1455,6 +1457,31 @@ class Engine:
         self._check(self.lib.mtr_test_wrap_dp(self.h, n, rd.ctypes.data, qs.ctypes.data, qe.ctypes.data, units.ctypes.data, uo.ctypes.data,
                                               g.ctypes.data, m.ctypes.data, d.ctypes.data, out.ctypes.data), "mtr_test_wrap_dp")
         return out
+
+    DP_PASSES = {"WAVE2P": 0, "Q4": 1, "QUAD2P": 2, "FOUR1P": 3, "OCT1P": 4}       # MTR_TEST_PASS_* of include/mtr_hip_test.h
+
+    def test_wrap_dp_pass(self, dp_pass: str, groups):
+        """mtr_test_wrap_dp_pass: one chosen forward pass of the wrap-around DP with its tracebacks.  groups: list of groups, a group a list of
+        test_wrap_dp's tasks (the DPs that share one forward pass) -> int32 [n tasks, 2, 8]: per task (in the order given) and parameter set what
+        wrap_around_DP_sub returns.  The two-parameter passes: set 0 = (1,1,3), set 1 = (1,3,1); the one-parameter passes fill set 0 with the task's own."""
+        tasks = [t for g in groups for t in g]
+        n = len(tasks)
+        go = np.zeros(len(groups) + 1, np.int32)
+        go[1:] = np.cumsum([len(g) for g in groups])
+        rd = np.array([t[0] for t in tasks], np.int32)
+        qs = np.array([t[1] for t in tasks], np.int32)
+        qe = np.array([t[2] for t in tasks], np.int32)
+        uo = np.zeros(n + 1, np.int32)
+        uo[1:] = np.cumsum([len(t[3]) for t in tasks])
+        units = np.ascontiguousarray(np.concatenate([np.asarray(t[3], np.uint8) for t in tasks] + [np.zeros(1, np.uint8)]))
+        g = np.array([t[4] for t in tasks], np.int32)
+        m = np.array([t[5] for t in tasks], np.int32)
+        d = np.array([t[6] for t in tasks], np.int32)
+        out = np.zeros((max(n, 1), 2, 8), np.int32)
+        self._check(self.lib.mtr_test_wrap_dp_pass(self.h, self.DP_PASSES[dp_pass], len(groups), go.ctypes.data, rd.ctypes.data, qs.ctypes.data, qe.ctypes.data,
+                                                   units.ctypes.data, uo.ctypes.data, g.ctypes.data, m.ctypes.data, d.ctypes.data, out.ctypes.data),
+                    "mtr_test_wrap_dp_pass")
+        return out[:n]
 
     def set_trace(self, max_events: int):
         self._check(self.lib.mtr_set_trace(self.h, max_events), "mtr_set_trace")

@@ -1351,6 +1351,8 @@ DEVINL bool dp_batch_fits(const K2Ctx &c, int rows)
 // The pass itself for up to four units (q.n, q.U, q.unit; kk = their k): forward pass, the two tracebacks of each and the
 // selection between the two parameter sets; store(g, record, ok) receives each result (ok = false: a traceback found the
 // matrix corrupt, the record is cleared).  Callers: the per-read kernel's pool (below), the staged chain's alignment kernel.
+// (The slot filling below - matrices one behind the other, a DP that is not there with one column and no cells - is written out once more in
+//  mtr_k_dp_test_waves, dp_test.hip.inc, which needs each parameter set's result: change both together.)
 template <typename F>
 DEVINL void dp_two_params_q4(K2Ctx &c, int qs, int qe, Dp4 &q, const int (&kk)[4], F &&store)
 {

@@ -968,8 +968,8 @@ __global__ __launch_bounds__(64, 4) void mtr_k_dp2_quads(K2Args a, StagedArgs s)
         const int wi = wq_next(ST_WQ(s, ST_Q_QUAD), nq, wq);
         if (wi < 0) break;                                 // every wave reaches this exit
         const int slot0 = (int)st_scatter_index((unsigned)wi, nq, q_stride) << 2;
-        DpQuad q; q.n = 0;
-        int items[4], kk[4];
+        DpQuad q; q.n = 0;                                  // (this slot filling - an empty slot repeats the first member with no rows, wlim from packed_words - is written out
+        int items[4], kk[4];                                //  once more in mtr_k_dp_test_quads, dp_test.hip.inc: change both together)
         int maxrows = 0;
 #pragma unroll
         for (int g = 0; g < 4; g++) {
@@ -1523,8 +1523,8 @@ __global__ __launch_bounds__(64, MTR_WAVES_PER_SIMD) void mtr_k_revise_quads(K2A
         if (n_active == 0) break;                          // the list is empty and every slot is through: every wave reaches this exit
         const unsigned long long t_prep = clk();
         // ---- 2. the next DP of every slot: into the pass if it fits, else by itself right away (it uses the cell scratch: before the pass)
-        DpOct q; q.n = RQ_SLOTS;
-        int maxrows = 0, maxU = 0, n_quad = 0;
+        DpOct q; q.n = RQ_SLOTS;                            // (the slots' default values, wlim and the width of the pass are written out once more in mtr_k_dp_test_rev,
+        int maxrows = 0, maxU = 0, n_quad = 0;              //  dp_test.hip.inc: change both together)
 #pragma unroll 1
         for (int g = 0; g < RQ_SLOTS; g++) { q.pk[g] = a.b.packed; q.wlim[g] = 1; q.base[g] = 0; q.rows[g] = 0; q.U[g] = 0; q.unit[g] = c.sc; q.G[g] = 1; q.MM[g] = 1; q.D[g] = 1; }
 #pragma unroll 1

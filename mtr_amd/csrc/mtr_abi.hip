@@ -32,6 +32,7 @@
 #include "k1_ranges.hip.inc"
 #include "k2_units.hip.inc"
 #include "k3_staged.hip.inc"
+#include "dp_test.hip.inc"
 #include "pack.hip.inc"
 #include "records.hip.inc"
 #include "chain.hip.inc"
@@ -3630,6 +3631,108 @@ extern "C" mtr_status mtr_test_wrap_dp(mtr_ctx *ctx, int32_t n_tasks, const int3
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3])); ctx->kt[1].ms = ms; ctx->kt[1].launches = 1;
     HIPCHK(copy_sync(ctx, ctx->counters, ctx->d_counters, sizeof(unsigned long long) * CNT_N, hipMemcpyDeviceToHost));
     HIPCHK(copy_sync(ctx, out8, d_out, nt * 8 * 4, hipMemcpyDeviceToHost));
+    return check_status(ctx);
+}
+
+// One chosen forward pass on chosen groups (dp_test.hip.inc).  The host holds every task to the bounds under which the batch path hands a DP to that
+// pass - the same macros, evaluated here - and refuses the rest before anything is launched.
+extern "C" mtr_status mtr_test_wrap_dp_pass(mtr_ctx *ctx, int32_t pass, int32_t n_groups, const int32_t *group_off, const int32_t *read_idx,
+                                            const int32_t *query_start, const int32_t *query_end, const uint8_t *units, const int32_t *unit_off,
+                                            const int32_t *gain, const int32_t *mismatch, const int32_t *indel, int32_t *out16)
+{
+    if (!ctx || pass < MTR_TEST_PASS_WAVE2P || pass > MTR_TEST_PASS_OCT1P || n_groups <= 0 || !group_off || !read_idx || !query_start || !query_end || !units || !unit_off ||
+        !gain || !mismatch || !indel || !out16) return MTR_ERR_BAD_ARG;
+    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    if (group_off[0] != 0) { ctx->err = "group_off[0] is not 0"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    const long long lim16 = ctx->sw.dp16_max_rows;
+    const bool one_param = pass == MTR_TEST_PASS_FOUR1P || pass == MTR_TEST_PASS_OCT1P;
+    const int max_members = pass == MTR_TEST_PASS_WAVE2P ? 1 : pass == MTR_TEST_PASS_OCT1P ? RQ_SLOTS : 4;
+    auto refuse = [&](int g, int t, const char *why) {
+        ctx->err = "bad DP pass task " + std::to_string(t) + " (group " + std::to_string(g) + "): " + why; return MTR_ERR_BAD_ARG;
+    };
+    auto size_ok = [&](long long U, long long rows) { return (U + 1) * rows + U < ctx->wrap_dp_size; };       // dp_size_ok (device_util.hip.inc)
+    size_t cells = 1;                                        // the largest cell block of a group
+    int quad_cols = 0;
+    for (int g = 0; g < n_groups; g++) {
+        const int t0 = group_off[g], n = group_off[g + 1] - t0;
+        if (t0 < 0 || n < 1 || n > max_members) return refuse(g, t0, "empty group, or more members than the pass takes");
+        long long maxrows = 0, maxU = 0, sumU = 0;
+        for (int t = t0; t < t0 + n; t++) {
+            const int rd = read_idx[t];
+            const long long U = (long long)unit_off[t + 1] - unit_off[t];
+            if (rd < 0 || rd >= ctx->n_reads || query_start[t] < 0 || query_end[t] < query_start[t] || query_end[t] >= ctx->lens[(size_t)rd]) return refuse(g, t, "window outside its read");
+            if (U <= 0 || U >= MTRC_MAX_PERIOD) return refuse(g, t, "unit length");
+            const long long rows = (long long)query_end[t] - query_start[t] + 1;
+            if (!size_ok(U, rows)) return refuse(g, t, "beyond WrapDPsize");
+            switch (pass) {
+            case MTR_TEST_PASS_WAVE2P: break;                // dp_two_params_unit takes every alignment
+            case MTR_TEST_PASS_Q4:                           // dp_batch_fits + the units the pool batches
+                if (U > 16) return refuse(g, t, "unit above 16 bases");
+                if (rows > DP2P_MAX_ROWS || rows > lim16 || !size_ok(16, rows)) return refuse(g, t, "rows beyond dp_batch_fits");
+                if (rd != read_idx[t0] || query_start[t] != query_start[t0] || query_end[t] != query_end[t0]) return refuse(g, t, "the units of a Q4 group share read and window");
+                break;
+            case MTR_TEST_PASS_QUAD2P:                       // mtr_k_gather's isq
+                if (U > ST_QUMAX) return refuse(g, t, "unit above ST_QUMAX");
+                if (rows > DP2P_MAX_ROWS || rows > lim16 || !DPQ_FITS(rows, U, 1, 3)) return refuse(g, t, "rows beyond DPQ_FITS");
+                if (quad_cols == 0) quad_cols = DPQ_COLS(U);
+                if (DPQ_COLS(U) != quad_cols) return refuse(g, t, "the tasks of a QUAD2P call are of one DPQ_COLS class");
+                break;
+            default: {                                       // mtr_k_revise_quads' fits
+                const int G = gain[t], MM = mismatch[t], D = indel[t];
+                if (!((G == 1 && MM == 1 && D == 3) || (G == 1 && MM == 3 && D == 1) || (G == 5 && MM == 1 && D == 1))) return refuse(g, t, "not one of the three parameter sets");
+                if (U > ST_QUMAX) return refuse(g, t, "unit above ST_QUMAX");
+                if (rows > lim16 || !DPQ_FITS(rows, U, G, D)) return refuse(g, t, "rows beyond DPQ_FITS");
+                break; }
+            }
+            maxrows = std::max(maxrows, rows); maxU = std::max(maxU, U); sumU += U;
+        }
+        size_t block;
+        switch (pass) {
+        case MTR_TEST_PASS_WAVE2P: block = 2 * (size_t)maxrows * (size_t)(maxU + 1) + 64; break;      // dp_forward2 writes two matrices; a wide row is at most 256 bytes
+        case MTR_TEST_PASS_Q4: block = (size_t)maxrows * (size_t)sumU; break;
+        case MTR_TEST_PASS_QUAD2P: block = DPQ_BLOCK_BYTES(DPQ_COLS(maxU), maxrows); break;
+        default: block = (RQ_SLOTS / 4) * DPQP_BLOCK_BYTES(DPQ_COLS(maxU), maxrows); break;
+        }
+        cells = std::max(cells, block);
+    }
+    const size_t per_wave = mtrc_align(cells + 256, 256);   // + slack: the traceback's dword loads read a few bytes past a row
+    if (per_wave > scratch_cap(ctx)) { ctx->err = "bad DP pass task: a group's cell block of " + std::to_string(cells) + " bytes exceeds the scratch cap"; return MTR_ERR_BAD_ARG; }
+    size_t total = 0;
+    const int waves = pick_waves(ctx, n_groups, 8, per_wave, &total);
+    mtr_status s = ensure_scratch(ctx, total); if (s != MTR_OK) return s;
+    const size_t nt = (size_t)group_off[n_groups], ng = (size_t)n_groups;
+    HIPCHK(ctx->d_t_i32.ensure((nt * 7 + 1 + ng + 1) * 4)); HIPCHK(ctx->d_t_units.ensure((size_t)unit_off[nt] + 16)); HIPCHK(ctx->d_t_out.ensure(nt * 16 * 4));
+    int32_t *d_i32 = ctx->d_t_i32; uint8_t *d_units = ctx->d_t_units; int32_t *d_out = ctx->d_t_out;
+    int32_t *d_rd = d_i32, *d_qs = d_i32 + nt, *d_qe = d_i32 + 2 * nt, *d_g = d_i32 + 3 * nt, *d_m = d_i32 + 4 * nt, *d_d = d_i32 + 5 * nt, *d_uo = d_i32 + 6 * nt, *d_go = d_i32 + 7 * nt + 1;
+    HIPCHK(copy_sync(ctx, d_rd, read_idx, nt * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_qs, query_start, nt * 4, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, d_qe, query_end, nt * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_g, gain, nt * 4, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, d_m, mismatch, nt * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_d, indel, nt * 4, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, d_uo, unit_off, (nt + 1) * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_units, units, (size_t)unit_off[nt], hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, d_go, group_off, (ng + 1) * 4, hipMemcpyHostToDevice));
+    DpPassArgs a{};
+    a.t.b = view(ctx); a.t.n_tasks = (int32_t)nt; a.t.read_idx = d_rd; a.t.qs = d_qs; a.t.qe = d_qe; a.t.units = d_units; a.t.unit_off = d_uo;
+    a.t.gain = d_g; a.t.mism = d_m; a.t.indel = d_d; a.t.out8 = d_out; a.t.scratch = ctx->d_scratch; a.t.scratch_per_wave = per_wave; a.t.cells_cap = cells;
+    a.t.status = ctx->d_status; a.t.work_counter = ctx->d_work; a.t.counters = ctx->d_counters; a.t.dp16_max_rows = ctx->sw.dp16_max_rows;
+    a.pass = pass; a.n_groups = n_groups; a.group_off = d_go; a.packed_words = ctx->packed_words;
+    HIPCHK(hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * CNT_N, ctx->stream));
+    HIPCHK(hipMemsetAsync(d_out, 0, nt * 16 * 4, ctx->stream));
+    const dim3 grid((unsigned)waves), block(64);
+    if (pass == MTR_TEST_PASS_WAVE2P || pass == MTR_TEST_PASS_Q4) hipLaunchKernelGGL(mtr_k_dp_test_waves, grid, block, 0, ctx->stream, a);
+    else if (one_param) hipLaunchKernelGGL(mtr_k_dp_test_rev, grid, block, 0, ctx->stream, a);
+    else {
+        typedef void (*quad_kernel)(DpPassArgs);
+        static const quad_kernel by_cols[8] = { mtr_k_dp_test_quads<1>, mtr_k_dp_test_quads<2>, mtr_k_dp_test_quads<3>, mtr_k_dp_test_quads<4>,
+                                                mtr_k_dp_test_quads<5>, mtr_k_dp_test_quads<6>, mtr_k_dp_test_quads<7>, mtr_k_dp_test_quads<8> };
+        hipLaunchKernelGGL(by_cols[quad_cols - 1], grid, block, 0, ctx->stream, a);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(copy_sync(ctx, ctx->counters, ctx->d_counters, sizeof(unsigned long long) * CNT_N, hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(ctx, out16, d_out, nt * 16 * 4, hipMemcpyDeviceToHost));
     return check_status(ctx);
 }
 

@@ -94,6 +94,7 @@ def test_no_scratch_memory_in_the_kernels_that_align_nothing(kernels, stem):
 
 
 def test_dp_kernels_spill_little(kernels):
-    for stem, limit in (("mtr_k_dp2_quads", 40), ("mtr_k_revise_quads", 48)):
+    """the build's spill counts (26 and 33 VGPRs) plus two"""
+    for stem, limit in (("mtr_k_dp2_quads", 28), ("mtr_k_revise_quads", 35)):
         for k in _find(kernels, stem):
             assert k["vgpr_spill_count"] <= limit, k

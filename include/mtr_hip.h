@@ -600,6 +600,42 @@ typedef struct mtr_partial_dst {
 mtr_status mtr_genotype_partial_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist,
                                        int32_t gain, int32_t mismatch, int32_t indel, int32_t max_tail, const mtr_partial_dst *dst, int64_t *out_rows);
 
+/* ---- partial genotype at catalogue scale: one seeded flank is a candidate ---------------------------------------------------------------------------
+ * mtr_genotype_partial_device scans every read against every flank and writes a row per (read, locus).  This call returns exactly the rows that
+ * call would write with partial = 1 - every column bit for bit - as a list sorted by (read, locus), and does no work and no allocation sized
+ * reads x loci.  It is not an approximation:
+ *   seeds       as the catalogue genotype defines them: K + 1 disjoint q-mers per pattern, m >= (K + 1) * q, q = seed_len in 8..16.
+ *   candidate   (read, locus) where the read holds a seed of AT LEAST ONE of the locus' four slots (A, B, rc A, rc B).  A slot within K edits
+ *               leaves one of its seeds in the read verbatim, so a pair that is no candidate has no slot within K and the dense call writes zeros
+ *               for it.  (The catalogue genotype asks for both flanks of an orientation; a partial row needs one flank.)
+ *   rows        for a candidate a seeded slot's hit F(.) is the flank search's own, over the whole read; an unseeded slot counts as dist > K.  On
+ *               these four the genotype's pairing rule decides "spanning" - such a pair is no row - and otherwise the partial genotype's choice of
+ *               slot, window, direction, motif, extension, tail, ratio and open apply verbatim.  A candidate with no slot within K is no row.
+ *   columns     read [R], locus [R], and mtr_partial_dst's seven columns with R rows; partial is 1 throughout.
+ * Two entry points, as the catalogue genotype's: the context keeps the result, the copy hands it out.
+ * mtr_genotype_partial_catalog_device: checked in this order - the genotype's checks, its limit of 2^30 - 1 (read, locus) pairs included; a motif
+ * of more than 32 bases, then max_tail < 0 (the partial genotype's); seed_len outside 8..16, then a flank shorter than (max_flank_dist + 1) *
+ * seed_len, naming locus and side (the catalogue's).  There is no MTR_ERR_DP_TOO_LARGE.  MTR_ERR_OVERFLOW for 2^31 - 1 seed hits or more, or more
+ * than 2^30 - 1 candidates.  On MTR_OK *out_rows = R, *out_candidates = the number of (read, locus) candidates verified, and the rows are kept; a
+ * failed call keeps nothing and writes nothing.  The kept rows are this call's own: an upload of any kind and the next call of this kind (whatever
+ * its outcome) discard them; mtr_genotype_catalog_device does not, and this call does not discard what that one kept.
+ * mtr_genotype_partial_catalog_copy_device follows mtr_genotype_catalog_copy_device's rules: MTR_ERR_BAD_ARG if nothing is kept or dst is NULL;
+ * MTR_ERR_OVERFLOW if rows.cap_rows < R, and then nothing is written; MTR_ERR_BAD_ARG if R > 0 and a column is NULL; else the columns are written
+ * and the context's stream is synchronised before the call returns.  Two calls with the same arguments give byte-identical columns.
+ * What the call is meant for is what the catalogue genotype is meant for: seeds that are rare in the reads.  A read's hits are compared pairwise to
+ * find its candidates (quadratic in the read's hits); with 4^seed_len well above the catalogue's 4 * (max_flank_dist + 1) * n_loci seeds -
+ * seed_len >= 12 for 100 000 loci - a 2 kb read has tens to hundreds of hits; at seed_len = 8 a catalogue of more than a few thousand loci makes
+ * every position a hit of several entries and the call slower than the dense one.  Choose the largest seed_len the flanks admit. */
+typedef struct mtr_partial_catalog_dst {
+    int32_t *read;           /* [R] */
+    int32_t *locus;          /* [R] */
+    mtr_partial_dst rows;    /* the partial genotype's columns, R rows; cap_rows is the capacity of all nine */
+} mtr_partial_catalog_dst;   /* caller-owned DEVICE memory */
+mtr_status mtr_genotype_partial_catalog_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist,
+                                               int32_t seed_len, int32_t gain, int32_t mismatch, int32_t indel, int32_t max_tail,
+                                               int64_t *out_rows, int64_t *out_candidates);
+mtr_status mtr_genotype_partial_catalog_copy_device(mtr_ctx *ctx, const mtr_partial_catalog_dst *dst);
+
 /* ---- allele calls: the genotype's rows of a locus ranked and split ---------------------------------------------------------------------------------
  * "Which alleles does the sample carry at this locus?"  The genotype answers per read; this call reduces every read that spans a locus to one or
  * two values.  The input is genotype rows in DEVICE memory, row = read * n_loci + locus, n_reads >= 1, n_loci >= 1, n_reads * n_loci <= 2^31 - 1:

@@ -73,6 +73,10 @@ mtr_status mtr_test_report_lines(mtr_ctx *ctx, int32_t n_rows, const int32_t *fi
  * it, and the rest of the call.  For tests/dev/gpu_catalog.py.  MTR_ERR_BAD_ARG without such a call. */
 mtr_status mtr_test_catalog_stats(mtr_ctx *ctx, int64_t *counts, double *ms);
 
+/* The same of the last successful mtr_genotype_partial_catalog_device call of the context (its candidates are (read, locus) pairs).  For
+ * tests/dev/gpu_partial_catalog.py.  MTR_ERR_BAD_ARG without such a call. */
+mtr_status mtr_test_partial_catalog_stats(mtr_ctx *ctx, int64_t *counts, double *ms);
+
 /* The kernels of mtr_report_motifs_device on caller-given units (the counterpart of mtr_test_chain).  Unit k is units[unit_off[k] ..
  * unit_off[k+1]) (unit_off has n + 1 entries and starts at 0), a repeat of read read[k] with num_freq_unit copies[k] and repeat_len[k].
  * A byte outside ACGT, a unit longer than 500, a decreasing read: MTR_ERR_BAD_ARG.  table_slots sizes the grouping's table so that a small

@@ -4,7 +4,7 @@ Python host-side mirror of the C-ABI in include/mtr_hip.h (ctypes; plain pointer
 (Engine.upload_device / process_device / parse_fasta_device / upload_fasta_device / parse_fastq_device / upload_fastq_device /
 walk_fasta_device / walk_fastq_device /
 export_tensor / report_tensors / report_alignment_tensors / report_text / report_bytes / report_motif_tensors / search_motifs / search_motif_loci /
-search_flanks / genotype_loci / genotype_catalog / genotype_partial) take or return torch tensors;
+search_flanks / genotype_loci / genotype_catalog / genotype_partial / genotype_partial_catalog) take or return torch tensors;
 they import torch when called.
 The product path is libmtr_hip.so only: importing works without a GPU, but creating an Engine
 without the library or without a HIP device raises — there is no CPU fallback.
@@ -54,7 +54,8 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_report_motifs_device", "mtr_test_unit_motifs", "mtr_search_motifs_device",
            "mtr_search_motif_loci_device", "mtr_motif_loci_copy_device", "mtr_search_flanks_device", "mtr_genotype_loci_device",
            "mtr_call_alleles_device", "mtr_genotype_partial_device", "mtr_genotype_catalog_device", "mtr_genotype_catalog_copy_device",
-           "mtr_call_alleles_rows_device", "mtr_test_catalog_stats"]
+           "mtr_call_alleles_rows_device", "mtr_test_catalog_stats", "mtr_genotype_partial_catalog_device", "mtr_genotype_partial_catalog_copy_device",
+           "mtr_test_partial_catalog_stats"]
 ALLELE_COPIES, ALLELE_BASES = 0, 1           # MTR_ALLELE_COPIES, MTR_ALLELE_BASES: the measure of Engine.call_alleles
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
@@ -296,6 +297,42 @@ class PartialGenotypes(NamedTuple):
     open: "object"        # uint8 [n, m]: 1 = partial and tail <= max_tail: copies is a lower bound
 
 
+class CPartialCatalogDst(C.Structure):
+    """mtr_partial_catalog_dst: device pointers of the partial catalogue genotype's read and locus columns, and the partial genotype's columns"""
+    _fields_ = [("read", C.c_void_p), ("locus", C.c_void_p), ("rows", CPartialDst)]
+
+
+class SparsePartialGenotypes(NamedTuple):
+    """What Engine.genotype_partial_catalog found: the R rows of PartialGenotypes with partial = 1, as a list sorted by (read, locus), all on the
+    engine's device.  include/mtr_hip.h defines every column.  Several batches' results are joined with torch.cat per column after the batch's
+    first read's index has been added to `read` (and n_reads summed): the joined rows stay sorted."""
+    n_reads: int
+    n_loci: int
+    read: "object"        # int32 [R]
+    locus: "object"       # int32 [R]
+    partial: "object"     # uint8 [R]: 1
+    slot: "object"        # uint8 [R]
+    flank_dist: "object"  # int32 [R]
+    window: "object"      # int32 [R, 2]
+    ext: "object"         # int32 [R, 6]
+    ratio: "object"       # float32 [R]
+    open: "object"        # uint8 [R]
+    candidates: int       # the (read, locus) candidates the seeds left to be verified
+
+    def to_dense(self) -> "PartialGenotypes":
+        """the same rows as Engine.genotype_partial returns them, zeros where a row is not partial (n_reads x n_loci rows: small shapes)"""
+        import torch
+
+        n, m = self.n_reads, self.n_loci
+        at = self.read.long() * m + self.locus.long()
+        cols = []
+        for c in self[4:11]:
+            full = torch.zeros((n * m,) + tuple(c.shape[1:]), dtype=c.dtype, device=c.device)
+            full[at] = c
+            cols.append(full.reshape((n, m) + tuple(c.shape[1:])))
+        return PartialGenotypes(*cols)
+
+
 class PartialSupport(NamedTuple):
     """What partial_support makes of a PartialGenotypes, per locus"""
     n_partial: "object"   # int64 [m]: partial rows
@@ -465,6 +502,10 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_genotype_catalog_copy_device.restype = C.c_int
     lib.mtr_genotype_partial_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [P(CPartialDst), P(C.c_int64)]
     lib.mtr_genotype_partial_device.restype = C.c_int
+    lib.mtr_genotype_partial_catalog_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [P(C.c_int64), P(C.c_int64)]
+    lib.mtr_genotype_partial_catalog_device.restype = C.c_int
+    lib.mtr_genotype_partial_catalog_copy_device.argtypes = [C.c_void_p, P(CPartialCatalogDst)]
+    lib.mtr_genotype_partial_catalog_copy_device.restype = C.c_int
     lib.mtr_call_alleles_device.argtypes = [C.c_void_p, P(CGenotypesDst), C.c_int64, C.c_int32, P(CAlleleParams), C.c_void_p, P(CAlleleCallsDst), P(C.c_int64)]
     lib.mtr_call_alleles_device.restype = C.c_int
     lib.mtr_call_alleles_rows_device.argtypes = [C.c_void_p, P(CGenotypesDst), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(CAlleleParams), C.c_void_p, P(CAlleleCallsDst),
@@ -472,6 +513,8 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_call_alleles_rows_device.restype = C.c_int
     lib.mtr_test_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
     lib.mtr_test_catalog_stats.restype = C.c_int
+    lib.mtr_test_partial_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
+    lib.mtr_test_partial_catalog_stats.restype = C.c_int
     lib.mtr_parse_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaDst), P(CFastaInfo)]
     lib.mtr_parse_fasta_device.restype = C.c_int
     lib.mtr_upload_fasta_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CFastaInfo)]
@@ -1099,17 +1142,7 @@ class Engine:
         handling."""
         import torch
 
-        if isinstance(loci, (str, bytes, bytearray)) or not hasattr(loci, "__len__"):
-            raise MtrError(f"loci must be a sequence of (left_flank, motif, right_flank), got {type(loci).__name__}")
-        flat = []
-        for k, locus in enumerate(loci):
-            if isinstance(locus, (str, bytes, bytearray)) or not hasattr(locus, "__len__") or len(locus) != 3:
-                raise MtrError(f"locus {k} must be (left_flank, motif, right_flank)")
-            flat.extend(locus)
-        if seed_len is None:
-            seed_len = pick_seed_len(loci, max_flank_dist)
-        data, off = pack_ids(flat)
-        m = len(loci)
+        data, off, m, seed_len = catalog_loci_args(loci, max_flank_dist, seed_len)
         nr, nc = C.c_int64(), C.c_int64()
         self._check(self.lib.mtr_genotype_catalog_device(self.h, data.ctypes.data, off.ctypes.data, m, int(max_flank_dist), int(seed_len), int(gain), int(mismatch),
                                                          int(indel), C.byref(nr), C.byref(nc)), "mtr_genotype_catalog_device")
@@ -1152,6 +1185,30 @@ class Engine:
         dst = CPartialDst(*[t.data_ptr() for t in pg], R)
         self._check(self.lib.mtr_genotype_partial_device(*args, C.byref(dst), C.byref(nr)), "mtr_genotype_partial_device")
         return pg
+
+    def genotype_partial_catalog(self, loci, max_flank_dist: int, seed_len: "int | None" = None, gain: int = 1, mismatch: int = 1, indel: int = 1,
+                                 max_tail: int = 10) -> SparsePartialGenotypes:
+        """Partial genotype at catalogue scale (mtr_genotype_partial_catalog_device, mtr_genotype_partial_catalog_copy_device): loci, scores and
+        max_tail as genotype_partial takes them, any number of loci.  Returns the rows genotype_partial would mark partial, bit for bit, as a
+        SparsePartialGenotypes sorted by (read, locus): a read is compared with a locus only where it holds an exact seed_len-mer of at least
+        one of its four flank patterns (exact: max_flank_dist edits cannot touch all of a flank's max_flank_dist + 1 disjoint seeds), and only
+        the seeded patterns are scanned; every flank needs (max_flank_dist + 1) * seed_len bases, 8 <= seed_len <= 16.  seed_len = None picks
+        the largest the flanks admit.  Needs no run and changes nothing a run or genotype_catalog left; follows genotype_loci's stream handling."""
+        import torch
+
+        data, off, m, seed_len = catalog_loci_args(loci, max_flank_dist, seed_len)
+        nr, nc = C.c_int64(), C.c_int64()
+        self._check(self.lib.mtr_genotype_partial_catalog_device(self.h, data.ctypes.data, off.ctypes.data, m, int(max_flank_dist), int(seed_len), int(gain), int(mismatch),
+                                                                 int(indel), int(max_tail), C.byref(nr), C.byref(nc)), "mtr_genotype_partial_catalog_device")
+        R = int(nr.value)
+        dev = torch.device("cuda", self.device)
+        new = lambda dtype, *tail: torch.empty((R,) + tail, dtype=dtype, device=dev)     # noqa: E731
+        cols = (new(torch.int32), new(torch.int32), new(torch.uint8), new(torch.uint8), new(torch.int32), new(torch.int32, 2), new(torch.int32, 6), new(torch.float32),
+                new(torch.uint8))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CPartialCatalogDst(cols[0].data_ptr(), cols[1].data_ptr(), CPartialDst(*[t.data_ptr() for t in cols[2:]], R))
+        self._check(self.lib.mtr_genotype_partial_catalog_copy_device(self.h, C.byref(dst)), "mtr_genotype_partial_catalog_copy_device")
+        return SparsePartialGenotypes(self.n_reads, m, *cols, int(nc.value))
 
     def call_alleles(self, gt, measure="copies", min_ratio: float = 0.0, min_support: int = 2, min_percent: int = 20, min_sep: int = 1) -> AlleleCalls:
         """Allele calls (mtr_call_alleles_device): the rows of genotype_loci - one call's Genotypes, or several batches' joined with torch.cat(dim=0)
@@ -1201,6 +1258,13 @@ class Engine:
         host-clock ms of (index build and upload, first scan pass, the rest)"""
         counts, ms = (C.c_int64 * 4)(), (C.c_double * 3)()
         self._check(self.lib.mtr_test_catalog_stats(self.h, counts, ms), "mtr_test_catalog_stats")
+        return tuple(int(v) for v in counts), tuple(float(v) for v in ms)
+
+    def test_partial_catalog_stats(self):
+        """mtr_test_partial_catalog_stats: what the last genotype_partial_catalog call saw - (positions, passed by the filter, seed hits,
+        candidates) and the host-clock ms of (index build and upload, first scan pass, the rest)"""
+        counts, ms = (C.c_int64 * 4)(), (C.c_double * 3)()
+        self._check(self.lib.mtr_test_partial_catalog_stats(self.h, counts, ms), "mtr_test_partial_catalog_stats")
         return tuple(int(v) for v in counts), tuple(float(v) for v in ms)
 
     def test_unit_motifs(self, units, read=None, copies=None, repeat_len=None, table_slots: int = 0) -> ReportMotifs:
@@ -1678,6 +1742,22 @@ def format_genotypes(ids, lens, loci, gt: Genotypes) -> bytes:
     return b"".join(out)
 
 
+def catalog_loci_args(loci, max_flank_dist: int, seed_len: "int | None"):
+    """What Engine.genotype_catalog and Engine.genotype_partial_catalog make of their loci: the checks of the list's shape, the sequences packed
+    as the C calls take them (seqs, seq_off), the number of loci, and the seed length - pick_seed_len's where none is given"""
+    if isinstance(loci, (str, bytes, bytearray)) or not hasattr(loci, "__len__"):
+        raise MtrError(f"loci must be a sequence of (left_flank, motif, right_flank), got {type(loci).__name__}")
+    flat = []
+    for k, locus in enumerate(loci):
+        if isinstance(locus, (str, bytes, bytearray)) or not hasattr(locus, "__len__") or len(locus) != 3:
+            raise MtrError(f"locus {k} must be (left_flank, motif, right_flank)")
+        flat.extend(locus)
+    if seed_len is None:
+        seed_len = pick_seed_len(loci, max_flank_dist)
+    data, off = pack_ids(flat)
+    return data, off, len(loci), seed_len
+
+
 def pick_seed_len(loci, max_flank_dist: int) -> int:
     """The seed length Engine.genotype_catalog takes by default: the largest q <= 16 with (max_flank_dist + 1) * q bases in every flank of loci
     (a sequence of (left_flank, motif, right_flank)); raises MtrError where that is below 8 - the flanks are too short for an exact screen at
@@ -1748,13 +1828,56 @@ def format_partial_genotypes(ids, lens, loci, pg: PartialGenotypes) -> bytes:
     return b"".join(out)
 
 
-def partial_support(pg: PartialGenotypes, calls: "AlleleCalls | None" = None, min_ratio: float = 0.0) -> PartialSupport:
+def format_sparse_partial_genotypes(ids, lens, loci, spg: "SparsePartialGenotypes") -> bytes:
+    """The rows of Engine.genotype_partial_catalog as text: byte for byte format_partial_genotypes of the dense result, without building it.
+    ids, lens: per read its ID (str or bytes) and length; loci: what genotype_partial_catalog was given; spg: its result (tensors or numpy)."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    bmot = [v[1].encode() if isinstance(v[1], str) else bytes(v[1]) for v in loci]
+    bid = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+    if len(lens) != len(bid):
+        raise MtrError(f"{len(lens)} lengths for {len(bid)} ids")
+    if (len(bid), len(bmot)) != (spg.n_reads, spg.n_loci):
+        raise MtrError(f"{len(bid)} ids and {len(bmot)} loci for the rows of {spg.n_reads} reads and {spg.n_loci} loci")
+    read, locus, slot, fdist = host(spg.read), host(spg.locus), host(spg.slot), host(spg.flank_dist)
+    window, ext, is_open, ratio = host(spg.window), host(spg.ext), host(spg.open), host(spg.ratio).astype(np.float32)
+    shown = [(b, b.translate(_COMPLEMENT)[::-1]) for b in bmot]
+    out = []
+    for i in range(len(read)):
+        r, k, e = int(read[i]), int(locus[i]), [int(v) for v in ext[i]]
+        s, lo, hi = int(slot[i]), int(window[i, 0]), int(window[i, 1])
+        start, end = (lo, lo + e[0]) if s in (0, 3) else (hi - e[0], hi)
+        cols = [str(int(lens[r])), str(k), str(s), str(int(fdist[i])), str(start + 1), str(end), str(e[0]), (">=" if is_open[i] else "") + str(e[2]),
+                str(e[3]), _c_float_text(ratio[i]), str(e[4]), str(e[5])]
+        out.append(bid[r] + b"\t" + "\t".join(cols).encode() + b"\t" + shown[k][s >> 1] + b"\n")
+    return b"".join(out)
+
+
+def partial_support(pg: "PartialGenotypes | SparsePartialGenotypes", calls: "AlleleCalls | None" = None, min_ratio: float = 0.0) -> PartialSupport:
     """Per locus, what the reads that do not span it say (plain torch on the tensors' own device, no kernel): the partial rows, the open rows,
     the largest copies among the open rows with ratio >= min_ratio (float32) and, with the locus' calls given, n_beyond: how many of those rows
     hold more copies than the larger called allele calls.call[:, 1] - evidence of an allele longer than the one called.  call_alleles itself
-    is unchanged: these rows are lower bounds, no values to rank."""
+    is unchanged: these rows are lower bounds, no values to rank.  pg may also be a SparsePartialGenotypes (genotype_partial_catalog's result, or
+    several batches' joined): the same per-locus results by scatter over its locus column, nothing sized reads x loci."""
     import torch
 
+    if isinstance(pg, SparsePartialGenotypes):
+        m, dev = pg.n_loci, pg.partial.device
+        at = pg.locus.long()
+        partial, is_open = pg.partial != 0, pg.open != 0
+        copies = pg.ext[:, 2]
+        good = is_open & (pg.ratio >= torch.tensor(min_ratio, dtype=torch.float32, device=dev))
+        count = lambda flag: torch.zeros(m, dtype=torch.int64, device=dev).index_add(0, at, flag.long())     # noqa: E731
+        zero = torch.zeros((), dtype=copies.dtype, device=dev)
+        top = torch.zeros(m, dtype=copies.dtype, device=dev).scatter_reduce(0, at, torch.where(good, copies, zero), "amax", include_self=True)
+        beyond = None
+        if calls is not None:
+            larger = calls.call[:, 1].to(dev)
+            if larger.shape[0] != m:
+                raise MtrError(f"{larger.shape[0]} calls for {m} loci")
+            beyond = count(good & (copies > larger[at]))
+        return PartialSupport(count(partial), count(is_open), top, beyond)
     partial, is_open = pg.partial != 0, pg.open != 0
     copies = pg.ext[:, :, 2]
     good = is_open & (pg.ratio >= torch.tensor(min_ratio, dtype=torch.float32, device=pg.ratio.device))

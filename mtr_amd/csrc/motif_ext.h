@@ -1,6 +1,7 @@
 // motif_ext.h — the ANCHORED EXTENSION of a read's window against ONE short motif as one sequential function: the form the partial genotype runs
-// one per lane (partial.hip.inc: 64 tasks per wavefront, the motif wave-uniform).  Plain C++, nothing of HIP: the same function compiles into the
-// gfx950 kernels and into a host program (tests/motif_ext_check.cpp).
+// one per lane (partial.hip.inc: 64 tasks of one variant per wavefront, the motif wave-uniform; partial_catalog.hip.inc: 64 tasks of any loci, the
+// motif, its length and the direction the lane's own, through motif_ext_rows<UB, false> directly).  Plain C++, nothing of HIP: the same function
+// compiles into the gfx950 kernels and into host programs (tests/motif_ext_check.cpp, tests/motif_ext_masked_check.cpp).
 //
 // The definition is include/mtr_hip.h's ("partial genotype"): motif_dp.h's wrap-around recurrence started at the flank's boundary and WITHOUT the
 // zero floor - a path begins in row 0 and nowhere else, so the best cell says how far the repeat runs from the flank - with what a traceback would
@@ -14,7 +15,8 @@
 //               plus 1 to C for sub and left, plus 1 to T for a matching sub.  The previous row of H, C and T is three arrays of UB registers
 //               (UB = the bucket: 4, 8, 16, 32); the loop over the columns is unrolled over UB, so every index is a constant, and cut at U
 //               WITHOUT a branch: a motif that fills its bucket (U == UB) runs rows compiled without a cut; a shorter one computes all UB columns
-//               and takes the best cell, the wrap (column U) and the row's maximum under the wave-uniform mask j < U.  Columns >= U read
+//               and takes the best cell, the wrap (column U) and the row's maximum under the mask j < U (wave-uniform in partial.hip.inc, per lane in
+//               partial_catalog.hip.inc: nothing here asks for either, and the masked rows are right for U == UB as well).  Columns >= U read
 //               columns < U and are read by none of them.  (Cut by branches - motif_dp_forward's way - the three arrays' registers were moved
 //               around at every cut: 67 instructions per cell built, about 40 of them moves.)  The motif is 2 bits per base in a 64-bit
 //               value, m[j] at bits 2j: the host hands the backward variants reversed.
@@ -47,7 +49,7 @@ MDP_HD MotifExt motif_ext_rows(const Load &ld, int lo, int hi, int back, uint64_
         int dH = wH, dC = wC, dT = wT, lH = 0, lC = 0, lT = 0;
     MDP_UNROLL
         for (int j = 0; j < UB; j++) {
-            const bool on = FULL || j < U;                       // (wave-uniform)
+            const bool on = FULL || j < U;                       // (wave-uniform where the wavefront shares a motif; a lane's own otherwise)
             const int mj = (int)((mot >> (2 * j)) & 3u);
             const bool m = xi == mj;
             const int uH = H[j], uC = Cn[j], uT = T[j];

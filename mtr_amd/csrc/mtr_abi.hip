@@ -45,6 +45,7 @@
 #include "genotype.hip.inc"
 #include "catalog.hip.inc"
 #include "partial.hip.inc"
+#include "partial_catalog.hip.inc"
 #include "allele_call.hip.inc"
 #include "fasta.hip.inc"
 #include "fastq.hip.inc"
@@ -247,6 +248,14 @@ struct mtr_ctx {
     // partial genotype (mtr_genotype_partial_device), per call and nothing kept: the rows, the variants' task lists, the tasks' results by row;
     // d_pt_i32 = status | count | ulen | the work lists' variants, d_pt_i64 = bits | the work lists' firsts
     DevBuf<int32_t> d_pt_row, d_pt_ext, d_pt_i32; DevBuf<int64_t> d_pt_i64; DevBuf<PtTask> d_pt_task;
+    // partial genotype at catalogue scale (mtr_genotype_partial_catalog_device), per call: the catalogue's d_ct_* working buffers (neither call keeps
+    // anything in them), and of its own the candidates (d_pc_cand = read | locus | mask | slots | is_row), the flank tasks and their offsets, the
+    // candidates' rows and results, the buckets' task lists, d_pc_i32 = status | count[4] | ulen, d_pc_i64 = bits.  What
+    // mtr_genotype_partial_catalog_copy_device hands out (pc_ready: pc_rows rows) is kept until an upload or the next call of this kind.
+    bool pc_ready = false; int64_t pc_rows = 0;
+    int64_t pc_counts[4] = { 0, 0, 0, 0 }; double pc_ms[3] = { 0, 0, 0 };       // the last such call, for mtr_test_partial_catalog_stats
+    DevBuf<int32_t> d_pc_cand, d_pc_row, d_pc_ext, d_pc_i32; DevBuf<uint32_t> d_pc_ftask; DevBuf<int64_t> d_pc_i64, d_pc_toff; DevBuf<PtTask> d_pc_task;
+    DevBuf<int32_t> d_pk_read, d_pk_locus, d_pk_fdist, d_pk_window, d_pk_ext; DevBuf<float> d_pk_ratio; DevBuf<uint8_t> d_pk_partial, d_pk_slot, d_pk_open;
     // allele calls (mtr_call_alleles_device), per call and nothing kept, buffers of its own so that what the genotype and the locus search keep stays:
     // d_ac_i32 = count | cursor (spread while the loci are few), d_ac_i64 = support_off | tile_off | state, the keys, the split's prefix sums
     DevBuf<int32_t> d_ac_i32; DevBuf<int64_t> d_ac_i64, d_ac_prefix; DevBuf<unsigned long long> d_ac_keys;
@@ -331,7 +340,7 @@ static hipError_t copy_sync(mtr_ctx *ctx, void *dst, const void *src, size_t byt
 }
 
 // forget the resident batch (its buffers stay allocated for the next one)
-static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->mo_ready = false; ctx->ml_ready = false; ctx->gc_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
+static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->mo_ready = false; ctx->ml_ready = false; ctx->gc_ready = false; ctx->pc_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
 
 extern "C" int mtr_abi_version(void) { return MTR_ABI_VERSION; }
 
@@ -2632,19 +2641,11 @@ static mtr_status genotype_align(mtr_ctx *ctx, const std::string &mot, const std
 // in two passes around one look at the device (the hits), the candidates in two passes around another (the candidates); their flank scans, the
 // pairing, a third look (the windows, their longest, the rows), the genotype's alignment step, the rows into the context's buffers.  Every buffer
 // is sized by the reads, by the loci, or by what the scan found: none by reads x loci.
-extern "C" mtr_status mtr_genotype_catalog_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist, int32_t seed_len,
-                                                  int32_t gain, int32_t mismatch, int32_t indel, int64_t *out_rows, int64_t *out_candidates)
+// The catalogue calls' checks of the seeds: seed_len, then every flank's length, naming locus and side
+static mtr_status catalog_check_seeds(mtr_ctx *ctx, const std::vector<std::vector<uint8_t>> &pat, int32_t n_loci, int32_t max_flank_dist, int32_t seed_len)
 {
-    if (!ctx || !out_rows || !out_candidates) return MTR_ERR_BAD_ARG;
-    *out_rows = 0; *out_candidates = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    ctx->gc_ready = false;                                                                             // whatever happens below, the rows kept before this call are gone
-    std::string mot; std::vector<int64_t> mot_off; std::vector<std::vector<uint8_t>> pat;
-    { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, mot, mot_off, pat); if (st != MTR_OK) return st; }
-    { mtr_status st = search_motifs_check_size(ctx, mot_off.data(), n_loci); if (st != MTR_OK) return st; }
     if (seed_len < SI_MIN_Q || seed_len > SI_MAX_Q) { ctx->err = "seed_len = " + std::to_string(seed_len) + " outside " + std::to_string(SI_MIN_Q) + ".." + std::to_string(SI_MAX_Q); return MTR_ERR_BAD_ARG; }
-    const int q = seed_len;
-    const int64_t need = ((int64_t)max_flank_dist + 1) * q;
+    const int64_t need = ((int64_t)max_flank_dist + 1) * seed_len;
     for (int32_t l = 0; l < n_loci; l++)
         for (int side = 0; side < 2; side++) {
             const size_t m = pat[(size_t)l * GT_SLOTS + (size_t)side].size();
@@ -2653,23 +2654,31 @@ extern "C" mtr_status mtr_genotype_catalog_device(mtr_ctx *ctx, const char *seqs
                 return MTR_ERR_BAD_ARG;
             }
         }
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    const auto t_start = std::chrono::steady_clock::now();
-    const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-    const int n = ctx->n_reads, seeds = max_flank_dist + 1;
-    const size_t nr = (size_t)n, S = pat.size();
-    // the index: the entries (code, locus * 4 + slot) sorted and made distinct, a table slot per distinct code, the filter over the codes
+    return MTR_OK;
+}
+
+// The seed index of a catalogue call, as it lies in ctx->d_ct_ix (filter | key | run | entries | the slots' lengths), and what the host knows of it
+struct CatIndex {
+    size_t E = 0, distinct = 0, fwords = 0; uint32_t cap = 0; int fbits = 0;
+    bool narrow = false, wide = false;                       // a slot of either flank word exists
+    const uint32_t *d_filter = nullptr, *d_key = nullptr; const int32_t *d_run = nullptr, *d_ent = nullptr, *d_plen = nullptr;
+};
+
+// The index built on the host and sent up: the entries (code, locus * 4 + slot) sorted and made distinct, a table slot per distinct code, the
+// filter over the codes, the slots' masks (ctx->d_ct_masks) and lengths; the reads' count and offset buffers sized, the status and the filter's
+// count zeroed.  The copies are synchronous.
+static mtr_status catalog_index(mtr_ctx *ctx, const std::vector<std::vector<uint8_t>> &pat, int seeds, int q, CatIndex &o)
+{
+    const size_t nr = (size_t)ctx->n_reads, S = pat.size();
     std::vector<std::pair<uint32_t, int32_t>> ent;
     ent.reserve(S * (size_t)seeds);
-    bool narrow = false, wide = false;
     std::vector<uint64_t> masks(S * FL_MASKS); std::vector<int32_t> plen(S);
     for (size_t slot = 0; slot < S; slot++) {
         const int m = (int)pat[slot].size();
         for (int i = 0; i < seeds; i++) ent.push_back({ si_seed_code(pat[slot].data() + si_seed_offset(i, q), q), (int32_t)slot });
         flank_slot_masks(pat[slot], masks.data() + slot * FL_MASKS);
         plen[slot] = m;
-        (flank_is_wide(ctx, m) ? wide : narrow) = true;
+        (flank_is_wide(ctx, m) ? o.wide : o.narrow) = true;
     }
     std::sort(ent.begin(), ent.end());
     ent.erase(std::unique(ent.begin(), ent.end()), ent.end());
@@ -2693,8 +2702,59 @@ extern "C" mtr_status mtr_genotype_catalog_device(mtr_ctx *ctx, const char *seqs
     HIPCHK(ctx->d_ct_count.ensure(2 * nr * 4)); HIPCHK(ctx->d_ct_off.ensure(2 * (nr + 1) * 8)); HIPCHK(ctx->d_ct_status.ensure(4)); HIPCHK(ctx->d_ct_passed.ensure(8));
     HIPCHK(copy_sync(ctx, ctx->d_ct_ix, ix.data(), ix.size() * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_ct_masks, masks.data(), masks.size() * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemsetAsync(ctx->d_ct_status, 0, 4, ctx->stream)); HIPCHK(hipMemsetAsync(ctx->d_ct_passed, 0, 8, ctx->stream));
-    const uint32_t *d_filter = (const uint32_t *)(int32_t *)ctx->d_ct_ix, *d_key = d_filter + fwords;
-    const int32_t *d_run = (const int32_t *)(d_key + cap), *d_ent = d_run + 2 * (size_t)cap, *d_plen = d_ent + E;
+    o.E = E; o.distinct = distinct; o.fwords = fwords; o.cap = cap; o.fbits = fbits;
+    o.d_filter = (const uint32_t *)(int32_t *)ctx->d_ct_ix; o.d_key = o.d_filter + fwords;
+    o.d_run = (const int32_t *)(o.d_key + cap); o.d_ent = o.d_run + 2 * (size_t)cap; o.d_plen = o.d_ent + E;
+    return MTR_OK;
+}
+
+// The scan's first pass: sa filled in, the reads' hits counted (d_ct_count's first half), their offsets (d_ct_off's), and one look at the device: *H
+static mtr_status catalog_scan_count(mtr_ctx *ctx, const CatIndex &ix, int q, CatScanArgs &sa, int64_t *H)
+{
+    const int n = ctx->n_reads;
+    int32_t *hit_count = ctx->d_ct_count; int64_t *hit_off = ctx->d_ct_off;
+    sa.b.packed = ctx->d_packed; sa.b.woff = ctx->d_woff; sa.b.lens = ctx->d_lens; sa.b.order = nullptr; sa.b.n_reads = n;
+    sa.ix = { ix.d_filter, ix.fbits, ix.d_key, ix.d_run, ix.cap }; sa.ent = ix.d_ent; sa.q = q; sa.fill = 0;
+    sa.hit_count = hit_count; sa.hit_off = hit_off; sa.hits = nullptr; sa.passed = ctx->d_ct_passed;
+    hipLaunchKernelGGL(mtr_k_cat_scan, dim3((unsigned)n), dim3(64), 0, ctx->stream, sa);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)hit_count, (int64_t)n, hit_off);
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(ctx, H, hit_off + (size_t)n, 8, hipMemcpyDeviceToHost));
+    if (*H < 0 || *H >= (int64_t)INT32_MAX) { ctx->err = "2^31 - 1 seed hits or more (a read's count saturates there)"; return MTR_ERR_OVERFLOW; }
+    return MTR_OK;
+}
+
+// The scan's second pass: the H > 0 hits into ctx->d_ct_hits (d_ct_head sized beside them), launched and not waited for
+static mtr_status catalog_scan_fill(mtr_ctx *ctx, CatScanArgs &sa, int64_t H)
+{
+    HIPCHK(ctx->d_ct_hits.ensure((size_t)H * 4)); HIPCHK(ctx->d_ct_head.ensure((size_t)H));
+    sa.fill = 1; sa.hits = ctx->d_ct_hits;
+    hipLaunchKernelGGL(mtr_k_cat_scan, dim3((unsigned)ctx->n_reads), dim3(64), 0, ctx->stream, sa);
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_genotype_catalog_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist, int32_t seed_len,
+                                                  int32_t gain, int32_t mismatch, int32_t indel, int64_t *out_rows, int64_t *out_candidates)
+{
+    if (!ctx || !out_rows || !out_candidates) return MTR_ERR_BAD_ARG;
+    *out_rows = 0; *out_candidates = 0;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    ctx->gc_ready = false;                                                                             // whatever happens below, the rows kept before this call are gone
+    std::string mot; std::vector<int64_t> mot_off; std::vector<std::vector<uint8_t>> pat;
+    { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, mot, mot_off, pat); if (st != MTR_OK) return st; }
+    { mtr_status st = search_motifs_check_size(ctx, mot_off.data(), n_loci); if (st != MTR_OK) return st; }
+    { mtr_status st = catalog_check_seeds(ctx, pat, n_loci, max_flank_dist, seed_len); if (st != MTR_OK) return st; }
+    const int q = seed_len;
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    const auto t_start = std::chrono::steady_clock::now();
+    const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    const int n = ctx->n_reads, seeds = max_flank_dist + 1;
+    const size_t nr = (size_t)n;
+    CatIndex ix;
+    { mtr_status st = catalog_index(ctx, pat, seeds, q, ix); if (st != MTR_OK) return st; }
+    const bool narrow = ix.narrow, wide = ix.wide;
+    const int32_t *d_plen = ix.d_plen;
     int32_t *hit_count = ctx->d_ct_count, *cand_count = hit_count + nr;
     int64_t *hit_off = ctx->d_ct_off, *cand_off = hit_off + nr + 1;
     const dim3 per_read((unsigned)n), b64(64), b256(256), one(1), b1024(1024);
@@ -2702,26 +2762,17 @@ extern "C" mtr_status mtr_genotype_catalog_device(mtr_ctx *ctx, const char *seqs
     const double ms_index = ms_since(t_start);                         // the host's index and its upload (the copies are synchronous)
     const auto t_scan = std::chrono::steady_clock::now();
     CatScanArgs sa{};
-    sa.b.packed = ctx->d_packed; sa.b.woff = ctx->d_woff; sa.b.lens = ctx->d_lens; sa.b.order = nullptr; sa.b.n_reads = n;
-    sa.ix = { d_filter, fbits, d_key, d_run, cap }; sa.ent = d_ent; sa.q = q; sa.fill = 0;
-    sa.hit_count = hit_count; sa.hit_off = hit_off; sa.hits = nullptr; sa.passed = ctx->d_ct_passed;
-    hipLaunchKernelGGL(mtr_k_cat_scan, per_read, b64, 0, ctx->stream, sa);
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)hit_count, (int64_t)n, hit_off);
-    HIPCHK(hipGetLastError());
     int64_t H = 0, Cn = 0, R = 0;
-    HIPCHK(copy_sync(ctx, &H, hit_off + nr, 8, hipMemcpyDeviceToHost));
-    if (H < 0 || H >= (int64_t)INT32_MAX) { ctx->err = "2^31 - 1 seed hits or more (a read's count saturates there)"; return MTR_ERR_OVERFLOW; }
+    { mtr_status st = catalog_scan_count(ctx, ix, q, sa, &H); if (st != MTR_OK) return st; }
     const double ms_scan = ms_since(t_scan);                           // the first scan pass and the offsets, up to the look that ends them
     const auto t_rest = std::chrono::steady_clock::now();
     unsigned long long passed = 0;
     HIPCHK(copy_sync(ctx, &passed, ctx->d_ct_passed, 8, hipMemcpyDeviceToHost));
     {
-        DBG("genotype_catalog: %zu entries of %zu codes, table of %u slots, filter of 2^%d bits; the filter passed %llu positions, %lld hits", E, distinct, cap, fbits, passed, (long long)H);
+        DBG("genotype_catalog: %zu entries of %zu codes, table of %u slots, filter of 2^%d bits; the filter passed %llu positions, %lld hits", ix.E, ix.distinct, ix.cap, ix.fbits, passed, (long long)H);
     }
     if (H > 0) {
-        HIPCHK(ctx->d_ct_hits.ensure((size_t)H * 4)); HIPCHK(ctx->d_ct_head.ensure((size_t)H));
-        sa.fill = 1; sa.hits = ctx->d_ct_hits;
-        hipLaunchKernelGGL(mtr_k_cat_scan, per_read, b64, 0, ctx->stream, sa);
+        { mtr_status st = catalog_scan_fill(ctx, sa, H); if (st != MTR_OK) return st; }
         CatCandArgs ca{};
         ca.n_reads = n; ca.fill = 0; ca.hit_off = hit_off; ca.hits = ctx->d_ct_hits; ca.head = ctx->d_ct_head; ca.cand_count = cand_count; ca.cand_off = cand_off;
         hipLaunchKernelGGL(mtr_k_cat_cands, per_read, b64, 0, ctx->stream, ca);
@@ -2820,6 +2871,33 @@ extern "C" mtr_status mtr_genotype_catalog_copy_device(mtr_ctx *ctx, const mtr_c
 // ---- partial genotype (partial.hip.inc) ------------------------------------------------------------------------------------------------
 // The genotype's checks and its flank step, the pairing and the choice of slot, one look at the device (the status and every variant's number
 // of tasks), one launch of the extension per bucket that has tasks, the columns.
+// the partial genotype's checks after the genotype's: a motif over 32 bases (naming the locus), then max_tail
+static mtr_status partial_check_args(mtr_ctx *ctx, const std::vector<int64_t> &mot_off, int32_t n_loci, int32_t max_tail)
+{
+    for (int32_t l = 0; l < n_loci; l++)
+        if (mot_off[(size_t)l + 1] - mot_off[(size_t)l] > MDP_MAX_U) {
+            ctx->err = "locus " + std::to_string(l) + ": a motif of " + std::to_string(mot_off[(size_t)l + 1] - mot_off[(size_t)l]) + " bases, the partial genotype takes at most " + std::to_string(MDP_MAX_U);
+            return MTR_ERR_BAD_ARG;
+        }
+    if (max_tail < 0) { ctx->err = "max_tail = " + std::to_string(max_tail) + ": at least 0"; return MTR_ERR_BAD_ARG; }
+    return MTR_OK;
+}
+
+// the variants of every locus: M, reversed M, rc M, reversed rc M at bits[4 * locus ..], as motif_ext takes them, and the motifs' lengths
+static void partial_variants(const std::string &mot, const std::vector<int64_t> &mot_off, int32_t n_loci, std::vector<uint64_t> &bits, std::vector<int32_t> &ulen)
+{
+    bits.assign((size_t)n_loci * 4, 0); ulen.assign((size_t)n_loci, 0);
+    for (int32_t l = 0; l < n_loci; l++) {
+        const int U = (int)(mot_off[(size_t)l + 1] - mot_off[(size_t)l]);
+        std::vector<uint8_t> c((size_t)U);
+        for (int t = 0; t < U; t++) { const char ch = mot[(size_t)mot_off[(size_t)l] + (size_t)t]; c[(size_t)t] = (uint8_t)(ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : 3); }
+        const std::vector<uint8_t> rc = revcomp_codes(c), rev(c.rbegin(), c.rend()), rrc(rc.rbegin(), rc.rend());
+        const std::vector<uint8_t> *four[4] = { &c, &rev, &rc, &rrc };
+        for (int k = 0; k < 4; k++) bits[(size_t)l * 4 + (size_t)k] = mdp_motif_bits(four[k]->data(), U);
+        ulen[(size_t)l] = U;
+    }
+}
+
 extern "C" mtr_status mtr_genotype_partial_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist,
                                                   int32_t gain, int32_t mismatch, int32_t indel, int32_t max_tail, const mtr_partial_dst *dst, int64_t *out_rows)
 {
@@ -2828,12 +2906,7 @@ extern "C" mtr_status mtr_genotype_partial_device(mtr_ctx *ctx, const char *seqs
     if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
     std::string mot; std::vector<int64_t> mot_off; std::vector<std::vector<uint8_t>> pat;
     { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, mot, mot_off, pat); if (st != MTR_OK) return st; }
-    for (int32_t l = 0; l < n_loci; l++)
-        if (mot_off[(size_t)l + 1] - mot_off[(size_t)l] > MDP_MAX_U) {
-            ctx->err = "locus " + std::to_string(l) + ": a motif of " + std::to_string(mot_off[(size_t)l + 1] - mot_off[(size_t)l]) + " bases, the partial genotype takes at most " + std::to_string(MDP_MAX_U);
-            return MTR_ERR_BAD_ARG;
-        }
-    if (max_tail < 0) { ctx->err = "max_tail = " + std::to_string(max_tail) + ": at least 0"; return MTR_ERR_BAD_ARG; }
+    { mtr_status st = partial_check_args(ctx, mot_off, n_loci, max_tail); if (st != MTR_OK) return st; }
     const int n = ctx->n_reads;
     const int64_t rows = (int64_t)n * n_loci;
     *out_rows = rows;
@@ -2845,16 +2918,8 @@ extern "C" mtr_status mtr_genotype_partial_device(mtr_ctx *ctx, const char *seqs
     { mtr_status st = flank_scan(ctx, pat); if (st != MTR_OK) return st; }
     // the variants of every locus: M, reversed M, rc M, reversed rc M, as motif_ext takes them
     const size_t V = (size_t)n_loci * 4, nl = (size_t)n_loci, nr = (size_t)n;
-    std::vector<uint64_t> bits(V); std::vector<int32_t> ulen(nl);
-    for (int32_t l = 0; l < n_loci; l++) {
-        const int U = (int)(mot_off[(size_t)l + 1] - mot_off[(size_t)l]);
-        std::vector<uint8_t> c((size_t)U);
-        for (int t = 0; t < U; t++) { const char ch = mot[(size_t)mot_off[(size_t)l] + (size_t)t]; c[(size_t)t] = (uint8_t)(ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : 3); }
-        const std::vector<uint8_t> rc = revcomp_codes(c), rev(c.rbegin(), c.rend()), rrc(rc.rbegin(), rc.rend());
-        const std::vector<uint8_t> *four[4] = { &c, &rev, &rc, &rrc };
-        for (int k = 0; k < 4; k++) bits[(size_t)l * 4 + (size_t)k] = mdp_motif_bits(four[k]->data(), U);
-        ulen[(size_t)l] = U;
-    }
+    std::vector<uint64_t> bits; std::vector<int32_t> ulen;
+    partial_variants(mot, mot_off, n_loci, bits, ulen);
     // device copies: d_pt_i32 = status | count | ulen | the work lists' variants, d_pt_i64 = bits | the work lists' firsts (a list per bucket)
     HIPCHK(ctx->d_pt_i32.ensure((1 + 2 * V + nl) * 4)); HIPCHK(ctx->d_pt_i64.ensure((2 * V + 4) * 8));
     HIPCHK(ctx->d_pt_row.ensure((size_t)rows * PT_ROW * 4)); HIPCHK(ctx->d_pt_ext.ensure((size_t)rows * PT_EXT * 4)); HIPCHK(ctx->d_pt_task.ensure(V * nr * sizeof(PtTask)));
@@ -2907,6 +2972,176 @@ extern "C" mtr_status mtr_genotype_partial_device(mtr_ctx *ctx, const char *seqs
     const PartialOut out = { dst->partial, dst->slot, dst->flank_dist, dst->window, dst->ext, dst->ratio, dst->open };
     hipLaunchKernelGGL(mtr_k_partial_out, per_row, b256, 0, ctx->stream, (const int32_t *)ctx->d_pt_row, (const int32_t *)ctx->d_pt_ext, (const int32_t *)d_ulen, n_loci, max_tail, rows, out);
     HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- partial genotype at catalogue scale (partial_catalog.hip.inc) -----------------------------------------------------------------------
+// The genotype's checks, the partial genotype's, the catalogue's; the catalogue's index and scan (catalog_index, catalog_scan_*: one look at the
+// device for the hits); the candidates in two passes around a second look; their seeded slots as flank tasks (a third look: the tasks), the
+// scans, the pairing, a fourth look (the status, the buckets' tasks, the rows); one launch of the extension per bucket that has tasks and the
+// status again; the rows into the context's buffers.  Every buffer is sized by the reads, by the loci, or by what the scan found.
+extern "C" mtr_status mtr_genotype_partial_catalog_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist, int32_t seed_len,
+                                                          int32_t gain, int32_t mismatch, int32_t indel, int32_t max_tail, int64_t *out_rows, int64_t *out_candidates)
+{
+    if (!ctx || !out_rows || !out_candidates) return MTR_ERR_BAD_ARG;
+    *out_rows = 0; *out_candidates = 0;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    ctx->pc_ready = false;                                                                             // whatever happens below, the rows kept before this call are gone
+    std::string mot; std::vector<int64_t> mot_off; std::vector<std::vector<uint8_t>> pat;
+    { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, mot, mot_off, pat); if (st != MTR_OK) return st; }
+    { mtr_status st = partial_check_args(ctx, mot_off, n_loci, max_tail); if (st != MTR_OK) return st; }
+    { mtr_status st = catalog_check_seeds(ctx, pat, n_loci, max_flank_dist, seed_len); if (st != MTR_OK) return st; }
+    const int q = seed_len;
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    const auto t_start = std::chrono::steady_clock::now();
+    const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    const int n = ctx->n_reads;
+    const size_t nr = (size_t)n, nl = (size_t)n_loci;
+    CatIndex ix;
+    { mtr_status st = catalog_index(ctx, pat, max_flank_dist + 1, q, ix); if (st != MTR_OK) return st; }
+    int32_t *cand_count = ctx->d_ct_count + nr;
+    int64_t *hit_off = ctx->d_ct_off, *cand_off = hit_off + nr + 1;
+    const dim3 per_read((unsigned)n), b64(64), b256(256), one(1), b1024(1024);
+    const double ms_index = ms_since(t_start);                         // the host's index and its upload (the copies are synchronous)
+    const auto t_scan = std::chrono::steady_clock::now();
+    CatScanArgs sa{};
+    int64_t H = 0, Cn = 0, R = 0;
+    { mtr_status st = catalog_scan_count(ctx, ix, q, sa, &H); if (st != MTR_OK) return st; }
+    const double ms_scan = ms_since(t_scan);                           // the first scan pass and the offsets, up to the look that ends them
+    const auto t_rest = std::chrono::steady_clock::now();
+    unsigned long long passed = 0;
+    HIPCHK(copy_sync(ctx, &passed, ctx->d_ct_passed, 8, hipMemcpyDeviceToHost));
+    DBG("genotype_partial_catalog: %zu entries of %zu codes, the filter passed %llu positions, %lld hits", ix.E, ix.distinct, passed, (long long)H);
+    if (H > 0) {
+        { mtr_status st = catalog_scan_fill(ctx, sa, H); if (st != MTR_OK) return st; }
+        PtcCandArgs ca{};
+        ca.n_reads = n; ca.fill = 0; ca.hit_off = hit_off; ca.hits = ctx->d_ct_hits; ca.head = ctx->d_ct_head; ca.cand_count = cand_count; ca.cand_off = cand_off;
+        hipLaunchKernelGGL(mtr_k_ptc_cands, per_read, b64, 0, ctx->stream, ca);
+        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)cand_count, (int64_t)n, cand_off);
+        HIPCHK(hipGetLastError());
+        HIPCHK(copy_sync(ctx, &Cn, cand_off + nr, 8, hipMemcpyDeviceToHost));
+        if (Cn < 0 || Cn > H) { ctx->err = "the partial catalogue's candidate lists are inconsistent"; return MTR_ERR_HIP; }
+        if (Cn > (int64_t)INT32_MAX / 2) { ctx->err = std::to_string(Cn) + " candidates are more than 2^30 - 1"; return MTR_ERR_OVERFLOW; }
+    }
+    if (Cn > 0) {
+        const size_t nc = (size_t)Cn;
+        // the candidates, their seeded slots as flank tasks
+        HIPCHK(ctx->d_pc_cand.ensure(5 * nc * 4)); HIPCHK(ctx->d_pc_toff.ensure((nc + 1) * 8)); HIPCHK(ctx->d_ct_flank.ensure(PT_SLOTS * nc * FL_RES * 4));
+        HIPCHK(ctx->d_ct_rowoff.ensure((nc + 1) * 8));
+        int32_t *cand_read = ctx->d_pc_cand, *cand_locus = cand_read + nc, *cand_mask = cand_locus + nc, *cand_slots = cand_mask + nc, *is_row = cand_slots + nc;
+        int64_t *task_off = ctx->d_pc_toff, *row_off = ctx->d_ct_rowoff;
+        PtcCandArgs ca{};
+        ca.n_reads = n; ca.fill = 1; ca.hit_off = hit_off; ca.hits = ctx->d_ct_hits; ca.head = ctx->d_ct_head; ca.cand_count = cand_count; ca.cand_off = cand_off;
+        ca.cand_read = cand_read; ca.cand_locus = cand_locus; ca.cand_mask = cand_mask; ca.cand_slots = cand_slots;
+        hipLaunchKernelGGL(mtr_k_ptc_cands, per_read, b64, 0, ctx->stream, ca);
+        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)cand_slots, Cn, task_off);
+        HIPCHK(hipGetLastError());
+        int64_t F = 0;
+        HIPCHK(copy_sync(ctx, &F, task_off + nc, 8, hipMemcpyDeviceToHost));
+        if (F < Cn || F > PT_SLOTS * Cn || F > H) { ctx->err = "the partial catalogue's flank tasks are inconsistent"; return MTR_ERR_HIP; }
+        HIPCHK(ctx->d_pc_ftask.ensure((size_t)F * 4));
+        const dim3 per_cand((unsigned)((nc + 255) / 256));
+        const PtcTaskArgs ta = { cand_mask, task_off, (int32_t)Cn, ctx->d_pc_ftask, ctx->d_ct_flank };
+        hipLaunchKernelGGL(mtr_k_ptc_tasks, per_cand, b256, 0, ctx->stream, ta);
+        PtcFlankArgs fa{};
+        fa.b = sa.b; fa.cand_read = cand_read; fa.cand_locus = cand_locus; fa.n_cand = (int32_t)Cn; fa.tasks = ctx->d_pc_ftask; fa.n_tasks = (int32_t)F;
+        fa.masks = ctx->d_ct_masks; fa.plen = ix.d_plen; fa.all_wide = ctx->sw.flank_word == 64; fa.res = ctx->d_ct_flank; fa.status = ctx->d_ct_status;
+        const dim3 per_task((unsigned)(((size_t)F + 63) / 64));
+        if (ix.narrow) hipLaunchKernelGGL(mtr_k_ptc_flank<uint32_t>, per_task, b64, 0, ctx->stream, fa);
+        if (ix.wide) hipLaunchKernelGGL(mtr_k_ptc_flank<uint64_t>, per_task, b64, 0, ctx->stream, fa);
+        // the variants; d_pc_i32 = status | count[4] | ulen, d_pc_i64 = bits
+        std::vector<uint64_t> bits; std::vector<int32_t> ulen;
+        partial_variants(mot, mot_off, n_loci, bits, ulen);
+        HIPCHK(ctx->d_pc_i32.ensure((1 + PTC_BUCKETS + nl) * 4)); HIPCHK(ctx->d_pc_i64.ensure(bits.size() * 8));
+        HIPCHK(ctx->d_pc_row.ensure(nc * PT_ROW * 4)); HIPCHK(ctx->d_pc_ext.ensure(nc * PT_EXT * 4)); HIPCHK(ctx->d_pc_task.ensure(PTC_BUCKETS * nc * sizeof(PtTask)));
+        int32_t *d_status = ctx->d_pc_i32, *d_count = d_status + 1, *d_ulen = d_count + PTC_BUCKETS;
+        HIPCHK(hipMemsetAsync(d_status, 0, (1 + PTC_BUCKETS) * 4, ctx->stream));
+        HIPCHK(copy_sync(ctx, d_ulen, ulen.data(), nl * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_pc_i64, bits.data(), bits.size() * 8, hipMemcpyHostToDevice));
+        // the pairing, and the rows' places
+        const PtcPairArgs pa = { cand_read, cand_locus, (int32_t)Cn, ctx->d_ct_flank, ctx->d_lens, d_ulen, max_flank_dist, ctx->d_pc_row, is_row, ctx->d_pc_task, d_count, d_status };
+        hipLaunchKernelGGL(mtr_k_ptc_pair, per_cand, b256, 0, ctx->stream, pa);
+        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)is_row, Cn, row_off);
+        HIPCHK(hipGetLastError());
+        int32_t head[1 + PTC_BUCKETS], dev = 0;
+        HIPCHK(copy_sync(ctx, head, d_status, sizeof head, hipMemcpyDeviceToHost));
+        HIPCHK(copy_sync(ctx, &dev, ctx->d_ct_status, 4, hipMemcpyDeviceToHost));
+        HIPCHK(copy_sync(ctx, &R, row_off + nc, 8, hipMemcpyDeviceToHost));
+        if (dev != DEV_OK) { ctx->err = "the partial catalogue's flank scans failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
+        bool sane = head[0] == DEV_OK && R >= 0 && R <= Cn;
+        int64_t tasks = 0;
+        for (int b = 0; b < PTC_BUCKETS; b++) { sane = sane && head[1 + b] >= 0 && head[1 + b] <= Cn; tasks += head[1 + b]; }
+        if (!sane || tasks > R) { ctx->err = "the partial catalogue's pairing failed on the device (status " + std::to_string(head[0]) + ")"; return MTR_ERR_HIP; }
+        if (tasks > 0) {
+            PtcExtArgs a{};
+            a.b = sa.b; a.cand_read = cand_read; a.tasks = ctx->d_pc_task; a.count = d_count; a.n_cand = (int32_t)Cn;
+            a.bits = (const uint64_t *)(int64_t *)ctx->d_pc_i64; a.ulen = d_ulen; a.G = gain; a.MM = mismatch; a.D = indel; a.ext = ctx->d_pc_ext; a.status = d_status;
+            for (int b = 0; b < PTC_BUCKETS; b++) {
+                if (head[1 + b] == 0) continue;
+                const dim3 grid((unsigned)((head[1 + b] + 63) / 64));
+                DBG("genotype_partial_catalog: bucket %d: %d tasks", 4 << b, head[1 + b]);
+                if (b == 0) hipLaunchKernelGGL(mtr_k_ptc_ext<4>, grid, b64, 0, ctx->stream, a);
+                else if (b == 1) hipLaunchKernelGGL(mtr_k_ptc_ext<8>, grid, b64, 0, ctx->stream, a);
+                else if (b == 2) hipLaunchKernelGGL(mtr_k_ptc_ext<16>, grid, b64, 0, ctx->stream, a);
+                else hipLaunchKernelGGL(mtr_k_ptc_ext<32>, grid, b64, 0, ctx->stream, a);
+                HIPCHK(hipGetLastError());
+            }
+            // the status before anything is kept
+            HIPCHK(copy_sync(ctx, &dev, d_status, 4, hipMemcpyDeviceToHost));
+            if (dev != DEV_OK) { ctx->err = "the partial catalogue's extensions failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
+        }
+        if (R > 0) {
+            const size_t rr = (size_t)R;
+            HIPCHK(ctx->d_pk_read.ensure(rr * 4)); HIPCHK(ctx->d_pk_locus.ensure(rr * 4)); HIPCHK(ctx->d_pk_partial.ensure(rr)); HIPCHK(ctx->d_pk_slot.ensure(rr));
+            HIPCHK(ctx->d_pk_fdist.ensure(rr * 4)); HIPCHK(ctx->d_pk_window.ensure(rr * 8)); HIPCHK(ctx->d_pk_ext.ensure(rr * 24)); HIPCHK(ctx->d_pk_ratio.ensure(rr * 4));
+            HIPCHK(ctx->d_pk_open.ensure(rr));
+            PtcOutArgs oa{};
+            oa.cand_read = cand_read; oa.cand_locus = cand_locus; oa.row = ctx->d_pc_row; oa.is_row = is_row; oa.row_off = row_off; oa.ext = ctx->d_pc_ext; oa.ulen = d_ulen;
+            oa.n_cand = (int32_t)Cn; oa.max_tail = max_tail;
+            oa.out = { ctx->d_pk_read, ctx->d_pk_locus, { ctx->d_pk_partial, ctx->d_pk_slot, ctx->d_pk_fdist, ctx->d_pk_window, ctx->d_pk_ext, ctx->d_pk_ratio, ctx->d_pk_open } };
+            hipLaunchKernelGGL(mtr_k_ptc_out, per_cand, b256, 0, ctx->stream, oa);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->pc_ready = true; ctx->pc_rows = R;
+    int64_t positions = 0;
+    for (int i = 0; i < n; i++) positions += std::max(0, ctx->lens[(size_t)i] - q + 1);
+    ctx->pc_counts[0] = positions; ctx->pc_counts[1] = (int64_t)passed; ctx->pc_counts[2] = H; ctx->pc_counts[3] = Cn;
+    ctx->pc_ms[0] = ms_index; ctx->pc_ms[1] = ms_scan; ctx->pc_ms[2] = ms_since(t_rest);
+    *out_rows = R; *out_candidates = Cn;
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_test_partial_catalog_stats(mtr_ctx *ctx, int64_t *counts, double *ms)
+{
+    if (!ctx || !counts || !ms) return MTR_ERR_BAD_ARG;
+    if (!ctx->pc_ready) { ctx->err = "no partial catalogue call to report on"; return MTR_ERR_BAD_ARG; }
+    std::copy(ctx->pc_counts, ctx->pc_counts + 4, counts); std::copy(ctx->pc_ms, ctx->pc_ms + 3, ms);
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_genotype_partial_catalog_copy_device(mtr_ctx *ctx, const mtr_partial_catalog_dst *dst)
+{
+    if (!ctx) return MTR_ERR_BAD_ARG;
+    if (!ctx->pc_ready) { ctx->err = "no rows kept: mtr_genotype_partial_catalog_device comes first (an upload discards what it kept)"; return MTR_ERR_BAD_ARG; }
+    if (!dst) { ctx->err = "dst is NULL"; return MTR_ERR_BAD_ARG; }
+    const int64_t R = ctx->pc_rows;
+    const mtr_partial_dst &g = dst->rows;
+    if (g.cap_rows < R) { ctx->err = "destination holds " + std::to_string(g.cap_rows) + " rows, " + std::to_string(R) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (R > 0 && (!dst->read || !dst->locus || !g.partial || !g.slot || !g.flank_dist || !g.window || !g.ext || !g.ratio || !g.open)) {
+        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
+    }
+    if (R == 0) return MTR_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
+    const size_t r = (size_t)R;
+    HIPCHK(hipMemcpyAsync(dst->read, ctx->d_pk_read, r * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->locus, ctx->d_pk_locus, r * 4, dd, ctx->stream));
+    HIPCHK(hipMemcpyAsync(g.partial, ctx->d_pk_partial, r, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(g.slot, ctx->d_pk_slot, r, dd, ctx->stream));
+    HIPCHK(hipMemcpyAsync(g.flank_dist, ctx->d_pk_fdist, r * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(g.window, ctx->d_pk_window, r * 8, dd, ctx->stream));
+    HIPCHK(hipMemcpyAsync(g.ext, ctx->d_pk_ext, r * 24, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(g.ratio, ctx->d_pk_ratio, r * 4, dd, ctx->stream));
+    HIPCHK(hipMemcpyAsync(g.open, ctx->d_pk_open, r, dd, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
 }

@@ -13,6 +13,8 @@
 //                        host made from the lists' counts (entries (variant, first group), the entry found by bisection on wave-uniform values,
 //                        as the search's); a bucket's variants are one launch.  No cross-lane operation after the group is found.
 //   mtr_k_partial_out    one lane per (read, locus): the caller's columns.
+// partial_choose, partial_variant, partial_row_store and partial_row_out are the pairing's and the output's single definitions: the call at
+// catalogue scale (partial_catalog.hip.inc) runs them per candidate.
 #pragma once
 #include "flank_search.hip.inc"
 #include "motif_search.hip.inc"
@@ -34,36 +36,49 @@ struct PartialPairArgs {
     int32_t *status;
 };
 
+// what the pairing makes of the four entries f = [slot][FL_RES] of one (read, locus) of a read of L bases: slot < 0 - spanning by the genotype's
+// rule, or no slot within K - or the chosen slot, its distance and its window.  The one definition: the catalogue call's pairing runs it too.
+struct PtChoice { int slot, dist, lo, hi; };
+DEVINL PtChoice partial_choose(const int32_t *f, int K, int L, int32_t *status)
+{
+    const int32_t *A = f, *B = f + FL_RES, *rA = f + 2 * FL_RES, *rB = f + 3 * FL_RES;
+    const bool v0 = A[0] <= K && B[0] <= K && A[2] <= B[1];
+    const bool v1 = rA[0] <= K && rB[0] <= K && rB[2] <= rA[1];
+    PtChoice c = { -1, 0, 0, 0 };
+    if (!(v0 || v1)) {
+        for (int s = 0; s < PT_SLOTS; s++) {
+            const int d = f[s * FL_RES];
+            if (d <= K && (c.slot < 0 || d < c.dist)) { c.slot = s; c.dist = d; }
+        }
+    }
+    if (c.slot >= 0) {
+        const int32_t *h = f + c.slot * FL_RES;
+        if (c.slot == 0 || c.slot == 3) { c.lo = h[2]; c.hi = L; } else { c.lo = 0; c.hi = h[1]; }
+        if (c.lo < 0 || c.hi > L || c.lo > c.hi) { atomicCAS(status, 0, DEV_ERR_INTERNAL); c.hi = c.lo = 0; }      // (a flank hit lies inside its read)
+    }
+    return c;
+}
+DEVINL int partial_variant(int l, int slot) { return 4 * l + (slot == 2 ? 3 : slot == 3 ? 2 : slot); }
+// q: the PT_ROW values of a (read, locus); at: its task's place in its list, -1 without one
+DEVINL void partial_row_store(int32_t *q, const PtChoice &c, int at)
+{
+    q[0] = c.slot >= 0 ? 1 : 0; q[1] = c.slot >= 0 ? c.slot : 0; q[2] = c.dist; q[3] = c.lo; q[4] = c.hi; q[5] = at; q[6] = 0; q[7] = 0;
+}
+
 __global__ __launch_bounds__(256) void mtr_k_partial_pair(PartialPairArgs a)
 {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= a.rows) return;
     const int rd = (int)(p / a.n_loci), l = (int)(p - (int64_t)rd * a.n_loci);
-    const int32_t *f = a.flank + (size_t)p * PT_SLOTS * FL_RES;
-    const int32_t *A = f, *B = f + FL_RES, *rA = f + 2 * FL_RES, *rB = f + 3 * FL_RES;
-    const bool v0 = A[0] <= a.K && B[0] <= a.K && A[2] <= B[1];
-    const bool v1 = rA[0] <= a.K && rB[0] <= a.K && rB[2] <= rA[1];
-    int32_t *q = a.row + (size_t)p * PT_ROW;
-    int slot = -1, dist = 0, lo = 0, hi = 0, at = -1;
-    if (!(v0 || v1)) {
-        for (int s = 0; s < PT_SLOTS; s++) {
-            const int d = f[s * FL_RES];
-            if (d <= a.K && (slot < 0 || d < dist)) { slot = s; dist = d; }
-        }
+    const PtChoice c = partial_choose(a.flank + (size_t)p * PT_SLOTS * FL_RES, a.K, a.lens[rd], a.status);
+    int at = -1;
+    if (c.slot >= 0 && c.hi > c.lo) {
+        const int variant = partial_variant(l, c.slot);
+        at = atomicAdd(&a.count[variant], 1);
+        if (at >= a.n_reads) { atomicCAS(a.status, 0, DEV_ERR_INTERNAL); at = -1; }
+        else a.tasks[(size_t)variant * (size_t)a.n_reads + (size_t)at] = { (int32_t)p, c.lo, c.hi, variant };
     }
-    if (slot >= 0) {
-        const int L = a.lens[rd];
-        const int32_t *h = f + slot * FL_RES;
-        if (slot == 0 || slot == 3) { lo = h[2]; hi = L; } else { lo = 0; hi = h[1]; }
-        if (lo < 0 || hi > L || lo > hi) { atomicCAS(a.status, 0, DEV_ERR_INTERNAL); hi = lo = 0; }      // (a flank hit lies inside its read)
-        if (hi > lo) {
-            const int variant = 4 * l + (slot == 2 ? 3 : slot == 3 ? 2 : slot);
-            at = atomicAdd(&a.count[variant], 1);
-            if (at >= a.n_reads) { atomicCAS(a.status, 0, DEV_ERR_INTERNAL); at = -1; }
-            else a.tasks[(size_t)variant * (size_t)a.n_reads + (size_t)at] = { (int32_t)p, lo, hi, variant };
-        }
-    }
-    q[0] = slot >= 0 ? 1 : 0; q[1] = slot >= 0 ? slot : 0; q[2] = dist; q[3] = lo; q[4] = hi; q[5] = at; q[6] = 0; q[7] = 0;
+    partial_row_store(a.row + (size_t)p * PT_ROW, c, at);
 }
 
 struct PartialExtArgs {
@@ -102,21 +117,27 @@ __global__ __launch_bounds__(64) void mtr_k_ext_lanes(PartialExtArgs a)
 }
 
 struct PartialOut { uint8_t *partial, *slot; int32_t *flank_dist, *window, *ext; float *ratio; uint8_t *open; };
-// ext: the tasks' results by row; a row without a task - not partial, or an empty window - has zeros
-__global__ __launch_bounds__(256) void mtr_k_partial_out(const int32_t *row, const int32_t *ext, const int32_t *ulen, int32_t n_loci, int32_t max_tail, int64_t rows,
-                                                         PartialOut out)
+// one row's columns at place p: q = its PT_ROW values, x = its PT_EXT values (read only where the row has a task), U = its locus' motif length.
+// The one definition of copies, tail, ratio and open: the catalogue call's output kernel runs it too.
+DEVINL void partial_row_out(const int32_t *q, const int32_t *x, int U, int max_tail, int64_t p, const PartialOut &out)
 {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= rows) return;
-    const int32_t *q = row + (size_t)p * PT_ROW;
     out.partial[p] = (uint8_t)q[0]; out.slot[p] = (uint8_t)q[1];
     out.flank_dist[p] = q[2];
     out.window[2 * p] = q[3]; out.window[2 * p + 1] = q[4];
     int32_t *o = out.ext + (size_t)p * 6;
     const int n = q[4] - q[3];
     int len = 0, C = 0, T = 0, H = 0;
-    if (q[5] >= 0) { const int32_t *x = ext + (size_t)p * PT_EXT; len = x[0]; C = x[1]; T = x[2]; H = x[3]; }
-    o[0] = len; o[1] = C; o[2] = C / ulen[(int)(p % n_loci)]; o[3] = T; o[4] = H; o[5] = n - len;
+    if (q[5] >= 0) { len = x[0]; C = x[1]; T = x[2]; H = x[3]; }
+    o[0] = len; o[1] = C; o[2] = C / U; o[3] = T; o[4] = H; o[5] = n - len;
     out.ratio[p] = len > 0 ? (float)T / (float)len : 0.0f;
     out.open[p] = (uint8_t)(q[0] && n - len <= max_tail ? 1 : 0);
+}
+
+// ext: the tasks' results by row; a row without a task - not partial, or an empty window - has zeros
+__global__ __launch_bounds__(256) void mtr_k_partial_out(const int32_t *row, const int32_t *ext, const int32_t *ulen, int32_t n_loci, int32_t max_tail, int64_t rows,
+                                                         PartialOut out)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= rows) return;
+    partial_row_out(row + (size_t)p * PT_ROW, ext + (size_t)p * PT_EXT, ulen[(int)(p % n_loci)], max_tail, p, out);
 }

@@ -636,6 +636,55 @@ mtr_status mtr_genotype_partial_catalog_device(mtr_ctx *ctx, const char *seqs, c
                                                int64_t *out_rows, int64_t *out_candidates);
 mtr_status mtr_genotype_partial_catalog_copy_device(mtr_ctx *ctx, const mtr_partial_catalog_dst *dst);
 
+/* ---- a prepared locus catalogue: what depends on the loci alone, built on the GPU once and used by every batch --------------------------------
+ * A locus list is fixed for a run while the reads come batch after batch; the two catalogue calls above rebuild per call everything that
+ * depends on the loci alone (the seed index, the slots' masks, the motif tables).  An mtr_catalog holds all of that in DEVICE memory, made once;
+ * the two prepared calls take it in place of the loci and return, bit for bit, what the text-taking calls return for the same loci, seed_len and
+ * max_flank_dist on the same batch.
+ * mtr_catalog_create: seqs / seq_off, n_loci, max_flank_dist, seed_len as mtr_genotype_catalog_device takes them.  It needs NO uploaded batch: ctx
+ * gives the device, the stream and the place of mtr_last_error.  A run in flight on ctx ends first.  It makes every check of the text-taking
+ * calls that does not depend on the reads or the scores, in their order and with their status and message for the same argument: n_loci < 1,
+ * seqs or seq_off NULL, more than 2^29 - 1 loci, a decreasing seq_off, more than 2^30 - 1 motifs or motif bases, a motif's length outside
+ * 1..499 or a byte of it outside ACGT, a flank's length outside 1..64 or a byte of it outside ACGT, max_flank_dist < 0, seed_len outside 8..16,
+ * a flank shorter than (max_flank_dist + 1) * seed_len.  A motif of more than 32 bases is legal here (mtr_catalog_info names the first);
+ * the prepared partial call refuses such a catalogue.  MTR_ERR_OVERFLOW if 4 * n_loci * (max_flank_dist + 1) seeds exceed 2^31 - 1; MTR_ERR_OOM /
+ * MTR_ERR_HIP as elsewhere ("the seed table is full" is MTR_ERR_HIP: the table's probes are bounded).  On anything but MTR_OK *out is NULL.
+ * The host reads only seq_off (lengths); every table that depends on a base is computed on the device from one upload of seqs: the slots'
+ * patterns, masks and seeds, the entries sorted by (code, slot) by a stable radix sort and made distinct, the runs, the filter, the table, the
+ * motif tables.  The entries, the filter and everything a probe of the table returns equal what the text-taking calls build on the host; the
+ * places of the codes in the table may differ.
+ * Lifetime and sharing: the catalogue is immutable once create returns, and the device is synchronised before it returns.  Any context on the
+ * same device may use it, several at once (each on its own stream), whether or not the creating context still exists; a context on another
+ * device gets MTR_ERR_BAD_ARG.  No upload, run or genotype call changes it.  mtr_catalog_destroy frees it (NULL: a no-op); no call may be using it.
+ * mtr_genotype_catalog_prepared_device / mtr_genotype_partial_catalog_prepared_device: checked in this order - ctx, cat, the out pointers; no
+ * batch uploaded; n_reads x n_loci beyond the text-taking calls' limits; (the catalogue genotype only) the WrapDPsize test, MTR_ERR_DP_TOO_LARGE;
+ * the scores; (the partial call only) a motif of more than 32 bases, naming the locus, then max_tail < 0 - each with the text-taking call's
+ * message.  Whatever the outcome, the rows the context kept of the same kind of call are discarded, as the text-taking calls discard them; on
+ * MTR_OK the rows are kept in the context exactly as mtr_genotype_catalog_device / mtr_genotype_partial_catalog_device keep them, and
+ * mtr_genotype_catalog_copy_device / mtr_genotype_partial_catalog_copy_device hand them out.  Nothing sized by the catalogue is built by these
+ * calls.  What the test switches of a call decide from the lengths - which motif slots run a lane each, which flank words are launched - goes into
+ * the context's own buffers: the lane-slot lists are derived and uploaded once per (catalogue, MTR_TEST_MOTIF_LANE_MAX) and kept in the context
+ * until another catalogue, another value or a text-taking genotype call takes their place, so batch after batch on one catalogue sends nothing
+ * sized by it.  MTR_ABI_VERSION is unchanged by these entries: look for them by symbol. */
+typedef struct mtr_catalog mtr_catalog;
+typedef struct mtr_catalog_info {
+    int32_t n_loci, max_flank_dist, seed_len;
+    int32_t filter_bits;          /* the filter has 2^filter_bits bits */
+    int64_t entries;              /* distinct (code, slot) pairs */
+    int64_t distinct_codes;
+    int64_t table_slots;          /* a power of two >= 2 * distinct_codes, at least 64 */
+    int64_t first_long_motif;     /* the first locus whose motif exceeds 32 bases, or -1 */
+    int64_t device_bytes;         /* what the catalogue holds in device memory */
+} mtr_catalog_info;
+mtr_status mtr_catalog_create(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist, int32_t seed_len,
+                              mtr_catalog **out);
+void mtr_catalog_destroy(mtr_catalog *cat);
+mtr_status mtr_catalog_info_get(const mtr_catalog *cat, mtr_catalog_info *info);
+mtr_status mtr_genotype_catalog_prepared_device(mtr_ctx *ctx, const mtr_catalog *cat, int32_t gain, int32_t mismatch, int32_t indel,
+                                                int64_t *out_rows, int64_t *out_candidates);
+mtr_status mtr_genotype_partial_catalog_prepared_device(mtr_ctx *ctx, const mtr_catalog *cat, int32_t gain, int32_t mismatch, int32_t indel,
+                                                        int32_t max_tail, int64_t *out_rows, int64_t *out_candidates);
+
 /* ---- allele calls: the genotype's rows of a locus ranked and split ---------------------------------------------------------------------------------
  * "Which alleles does the sample carry at this locus?"  The genotype answers per read; this call reduces every read that spans a locus to one or
  * two values.  The input is genotype rows in DEVICE memory, row = read * n_loci + locus, n_reads >= 1, n_loci >= 1, n_reads * n_loci <= 2^31 - 1:

@@ -77,6 +77,26 @@ mtr_status mtr_test_catalog_stats(mtr_ctx *ctx, int64_t *counts, double *ms);
  * tests/dev/gpu_partial_catalog.py.  MTR_ERR_BAD_ARG without such a call. */
 mtr_status mtr_test_partial_catalog_stats(mtr_ctx *ctx, int64_t *counts, double *ms);
 
+/* Host copies of everything a prepared catalogue holds on the device (tests/test_gpu_catalog_prepared.py).  ctx: a context on the catalogue's
+ * device (its stream makes the copies).  Every array is malloc'ed, free() them; on anything but MTR_OK none is.
+ *   filter [filter_words]   key [table_slots]   run [table_slots][2] (first, count; count = 0: empty)   ent [entries]
+ *   plen [n_slots]   masks [n_slots][8]   (n_slots = 4 * n_loci)
+ *   units [unit_bytes]   unit_off [2 * n_loci + 1]   unit_bits [2 * n_loci]   variant_bits [4 * n_loci]   ulen [n_loci] */
+typedef struct mtr_catalog_dump {
+    int64_t filter_words, table_slots, entries, n_slots, unit_bytes, n_loci;
+    uint32_t *filter, *key;
+    int32_t *run, *ent, *plen;
+    uint64_t *masks;
+    uint8_t *units;
+    int32_t *unit_off;
+    uint64_t *unit_bits, *variant_bits;
+    int32_t *ulen;
+} mtr_catalog_dump;
+mtr_status mtr_test_catalog_dump(mtr_ctx *ctx, const mtr_catalog *cat, mtr_catalog_dump *out);
+/* ms[3] of the last successful mtr_catalog_create on ctx, by the host clock: the host's pass over seq_off, the uploads (seqs and the length
+ * arrays), the device build up to the synchronisation that ends it.  For tests/dev/gpu_catalog_prepared.py.  MTR_ERR_BAD_ARG without one. */
+mtr_status mtr_test_catalog_build_stats(mtr_ctx *ctx, double *ms);
+
 /* The kernels of mtr_report_motifs_device on caller-given units (the counterpart of mtr_test_chain).  Unit k is units[unit_off[k] ..
  * unit_off[k+1]) (unit_off has n + 1 entries and starts at 0), a repeat of read read[k] with num_freq_unit copies[k] and repeat_len[k].
  * A byte outside ACGT, a unit longer than 500, a decreasing read: MTR_ERR_BAD_ARG.  table_slots sizes the grouping's table so that a small

@@ -55,7 +55,8 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_search_motif_loci_device", "mtr_motif_loci_copy_device", "mtr_search_flanks_device", "mtr_genotype_loci_device",
            "mtr_call_alleles_device", "mtr_genotype_partial_device", "mtr_genotype_catalog_device", "mtr_genotype_catalog_copy_device",
            "mtr_call_alleles_rows_device", "mtr_test_catalog_stats", "mtr_genotype_partial_catalog_device", "mtr_genotype_partial_catalog_copy_device",
-           "mtr_test_partial_catalog_stats"]
+           "mtr_test_partial_catalog_stats", "mtr_catalog_create", "mtr_catalog_destroy", "mtr_catalog_info_get", "mtr_genotype_catalog_prepared_device",
+           "mtr_genotype_partial_catalog_prepared_device", "mtr_test_catalog_dump", "mtr_test_catalog_build_stats"]
 ALLELE_COPIES, ALLELE_BASES = 0, 1           # MTR_ALLELE_COPIES, MTR_ALLELE_BASES: the measure of Engine.call_alleles
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
@@ -302,6 +303,65 @@ class CPartialCatalogDst(C.Structure):
     _fields_ = [("read", C.c_void_p), ("locus", C.c_void_p), ("rows", CPartialDst)]
 
 
+class CCatalogInfo(C.Structure):
+    """mtr_catalog_info"""
+    _fields_ = [("n_loci", C.c_int32), ("max_flank_dist", C.c_int32), ("seed_len", C.c_int32), ("filter_bits", C.c_int32), ("entries", C.c_int64),
+                ("distinct_codes", C.c_int64), ("table_slots", C.c_int64), ("first_long_motif", C.c_int64), ("device_bytes", C.c_int64)]
+
+
+class CCatalogDump(C.Structure):
+    """mtr_catalog_dump (include/mtr_hip_test.h): host copies of a prepared catalogue's device tables, malloc'ed by the library"""
+    _fields_ = [(k, C.c_int64) for k in ("filter_words", "table_slots", "entries", "n_slots", "unit_bytes", "n_loci")] + \
+               [(k, C.c_void_p) for k in ("filter", "key", "run", "ent", "plen", "masks", "units", "unit_off", "unit_bits", "variant_bits", "ulen")]
+
+
+class CatalogInfo(NamedTuple):
+    """mtr_catalog_info: what a prepared catalogue holds"""
+    n_loci: int
+    max_flank_dist: int
+    seed_len: int
+    filter_bits: int          # the filter has 2^filter_bits bits
+    entries: int              # distinct (code, slot) pairs
+    distinct_codes: int
+    table_slots: int
+    first_long_motif: int     # the first locus whose motif exceeds 32 bases (genotype_partial_prepared refuses the catalogue), or -1
+    device_bytes: int
+
+
+class Catalog:
+    """mtr_catalog: a locus list prepared once on the GPU (Engine.build_catalog) - the seed index, the flank masks and the motif tables that
+    Engine.genotype_catalog and Engine.genotype_partial_catalog rebuild per call.  Immutable; any Engine on the same device may use it, and it
+    outlives the Engine that built it.  close() frees its device memory (no call may be using it); it closes when collected, as FileState."""
+
+    def __init__(self, lib, handle, device: int):
+        self.lib, self.h, self.device = lib, handle, device
+        ci = CCatalogInfo()
+        st = lib.mtr_catalog_info_get(handle, C.byref(ci))
+        if st != 0:
+            raise MtrError(f"mtr_catalog_info_get: {STATUS.get(st, st)}")
+        self.info = CatalogInfo(*(int(getattr(ci, f[0])) for f in CCatalogInfo._fields_))
+
+    n_loci = property(lambda self: self.info.n_loci)
+    max_flank_dist = property(lambda self: self.info.max_flank_dist)
+    seed_len = property(lambda self: self.info.seed_len)
+
+    def _handle(self):
+        if not self.h:
+            raise MtrError("the catalogue is closed")
+        return self.h
+
+    def close(self):
+        if self.h:
+            self.lib.mtr_catalog_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SparsePartialGenotypes(NamedTuple):
     """What Engine.genotype_partial_catalog found: the R rows of PartialGenotypes with partial = 1, as a list sorted by (read, locus), all on the
     engine's device.  include/mtr_hip.h defines every column.  Several batches' results are joined with torch.cat per column after the batch's
@@ -506,6 +566,21 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_genotype_partial_catalog_device.restype = C.c_int
     lib.mtr_genotype_partial_catalog_copy_device.argtypes = [C.c_void_p, P(CPartialCatalogDst)]
     lib.mtr_genotype_partial_catalog_copy_device.restype = C.c_int
+    if hasattr(lib, "mtr_catalog_create"):      # (a build from before the prepared catalogue, A/B'd through MTR_LIB, has none of these: using one raises there)
+        lib.mtr_catalog_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p)]
+        lib.mtr_catalog_create.restype = C.c_int
+        lib.mtr_catalog_destroy.argtypes = [C.c_void_p]
+        lib.mtr_catalog_destroy.restype = None
+        lib.mtr_catalog_info_get.argtypes = [C.c_void_p, P(CCatalogInfo)]
+        lib.mtr_catalog_info_get.restype = C.c_int
+        lib.mtr_genotype_catalog_prepared_device.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [P(C.c_int64), P(C.c_int64)]
+        lib.mtr_genotype_catalog_prepared_device.restype = C.c_int
+        lib.mtr_genotype_partial_catalog_prepared_device.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [P(C.c_int64), P(C.c_int64)]
+        lib.mtr_genotype_partial_catalog_prepared_device.restype = C.c_int
+        lib.mtr_test_catalog_dump.argtypes = [C.c_void_p, C.c_void_p, P(CCatalogDump)]
+        lib.mtr_test_catalog_dump.restype = C.c_int
+        lib.mtr_test_catalog_build_stats.argtypes = [C.c_void_p, P(C.c_double)]
+        lib.mtr_test_catalog_build_stats.restype = C.c_int
     lib.mtr_call_alleles_device.argtypes = [C.c_void_p, P(CGenotypesDst), C.c_int64, C.c_int32, P(CAlleleParams), C.c_void_p, P(CAlleleCallsDst), P(C.c_int64)]
     lib.mtr_call_alleles_device.restype = C.c_int
     lib.mtr_call_alleles_rows_device.argtypes = [C.c_void_p, P(CGenotypesDst), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(CAlleleParams), C.c_void_p, P(CAlleleCallsDst),
@@ -1146,7 +1221,12 @@ class Engine:
         nr, nc = C.c_int64(), C.c_int64()
         self._check(self.lib.mtr_genotype_catalog_device(self.h, data.ctypes.data, off.ctypes.data, m, int(max_flank_dist), int(seed_len), int(gain), int(mismatch),
                                                          int(indel), C.byref(nr), C.byref(nc)), "mtr_genotype_catalog_device")
-        R = int(nr.value)
+        return self._catalog_rows(m, int(nr.value), int(nc.value))
+
+    def _catalog_rows(self, m: int, R: int, candidates: int) -> SparseGenotypes:
+        """the R rows a catalogue genotype call kept in the context, as fresh tensors (mtr_genotype_catalog_copy_device)"""
+        import torch
+
         dev = torch.device("cuda", self.device)
         new = lambda dtype, *tail: torch.empty((R,) + tail, dtype=dtype, device=dev)     # noqa: E731
         cols = (new(torch.int32), new(torch.int32), new(torch.uint8), new(torch.uint8), new(torch.int32, 2), new(torch.int32, 2), new(torch.int32, 8), new(torch.int32),
@@ -1154,7 +1234,45 @@ class Engine:
         torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
         dst = CCatalogDst(cols[0].data_ptr(), cols[1].data_ptr(), CGenotypesDst(*[t.data_ptr() for t in cols[2:]], R))
         self._check(self.lib.mtr_genotype_catalog_copy_device(self.h, C.byref(dst)), "mtr_genotype_catalog_copy_device")
-        return SparseGenotypes(self.n_reads, m, *cols, int(nc.value))
+        return SparseGenotypes(self.n_reads, m, *cols, candidates)
+
+    def build_catalog(self, loci, max_flank_dist: int, seed_len: "int | None" = None) -> Catalog:
+        """A prepared catalogue (mtr_catalog_create): loci, max_flank_dist and seed_len as genotype_catalog takes them, with its checks and its
+        choice of seed_len.  loci may also be the sequences already packed as the C call takes them - (uint8 array, int64 offsets with
+        3 * n_loci + 1 entries: left flank, motif, right flank per locus) - which skips the string packing; seed_len is then required.  Built on
+        this engine's device from one upload of the letters; needs no uploaded batch and changes nothing a batch or a run left.  The result
+        is for genotype_prepared / genotype_partial_prepared of any Engine on this device, batch after batch."""
+        if isinstance(loci, tuple) and len(loci) == 2 and isinstance(loci[0], np.ndarray) and isinstance(loci[1], np.ndarray):
+            data, off = np.ascontiguousarray(loci[0], dtype=np.uint8), np.ascontiguousarray(loci[1], dtype=np.int64)
+            if len(off) < 4 or (len(off) - 1) % 3 != 0:
+                raise MtrError(f"packed loci need 3 * n_loci + 1 offsets, got {len(off)}")
+            if seed_len is None:
+                raise MtrError("packed loci need a seed_len")
+            if int(off[0]) < 0 or int(off[-1]) > len(data):
+                raise MtrError(f"the offsets reach {int(off[-1])}, the sequences hold {len(data)} bytes")
+            m = (len(off) - 1) // 3
+        else:
+            data, off, m, seed_len = catalog_loci_args(loci, max_flank_dist, seed_len)
+        h = C.c_void_p()
+        self._check(self.lib.mtr_catalog_create(self.h, data.ctypes.data, off.ctypes.data, m, int(max_flank_dist), int(seed_len), C.byref(h)), "mtr_catalog_create")
+        return Catalog(self.lib, h, self.device)
+
+    def genotype_prepared(self, cat: Catalog, gain: int = 1, mismatch: int = 1, indel: int = 1) -> SparseGenotypes:
+        """genotype_catalog on a prepared catalogue (mtr_genotype_catalog_prepared_device): the same SparseGenotypes, bit for bit, as
+        genotype_catalog returns for the catalogue's loci, max_flank_dist and seed_len on the resident batch, without rebuilding anything that
+        depends on the loci alone."""
+        nr, nc = C.c_int64(), C.c_int64()
+        self._check(self.lib.mtr_genotype_catalog_prepared_device(self.h, cat._handle(), int(gain), int(mismatch), int(indel), C.byref(nr), C.byref(nc)),
+                    "mtr_genotype_catalog_prepared_device")
+        return self._catalog_rows(cat.n_loci, int(nr.value), int(nc.value))
+
+    def genotype_partial_prepared(self, cat: Catalog, gain: int = 1, mismatch: int = 1, indel: int = 1, max_tail: int = 10) -> SparsePartialGenotypes:
+        """genotype_partial_catalog on a prepared catalogue (mtr_genotype_partial_catalog_prepared_device): the same SparsePartialGenotypes, bit
+        for bit; a catalogue with a motif of more than 32 bases is refused as genotype_partial_catalog refuses such loci."""
+        nr, nc = C.c_int64(), C.c_int64()
+        self._check(self.lib.mtr_genotype_partial_catalog_prepared_device(self.h, cat._handle(), int(gain), int(mismatch), int(indel), int(max_tail), C.byref(nr),
+                                                                          C.byref(nc)), "mtr_genotype_partial_catalog_prepared_device")
+        return self._partial_catalog_rows(cat.n_loci, int(nr.value), int(nc.value))
 
     def genotype_partial(self, loci, max_flank_dist: int, gain: int = 1, mismatch: int = 1, indel: int = 1, max_tail: int = 10) -> PartialGenotypes:
         """Partial genotype (mtr_genotype_partial_device): loci as genotype_loci takes them, motifs of at most 32 bases.  A read that does not
@@ -1200,7 +1318,12 @@ class Engine:
         nr, nc = C.c_int64(), C.c_int64()
         self._check(self.lib.mtr_genotype_partial_catalog_device(self.h, data.ctypes.data, off.ctypes.data, m, int(max_flank_dist), int(seed_len), int(gain), int(mismatch),
                                                                  int(indel), int(max_tail), C.byref(nr), C.byref(nc)), "mtr_genotype_partial_catalog_device")
-        R = int(nr.value)
+        return self._partial_catalog_rows(m, int(nr.value), int(nc.value))
+
+    def _partial_catalog_rows(self, m: int, R: int, candidates: int) -> SparsePartialGenotypes:
+        """the R rows a partial catalogue call kept in the context, as fresh tensors (mtr_genotype_partial_catalog_copy_device)"""
+        import torch
+
         dev = torch.device("cuda", self.device)
         new = lambda dtype, *tail: torch.empty((R,) + tail, dtype=dtype, device=dev)     # noqa: E731
         cols = (new(torch.int32), new(torch.int32), new(torch.uint8), new(torch.uint8), new(torch.int32), new(torch.int32, 2), new(torch.int32, 6), new(torch.float32),
@@ -1208,7 +1331,7 @@ class Engine:
         torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
         dst = CPartialCatalogDst(cols[0].data_ptr(), cols[1].data_ptr(), CPartialDst(*[t.data_ptr() for t in cols[2:]], R))
         self._check(self.lib.mtr_genotype_partial_catalog_copy_device(self.h, C.byref(dst)), "mtr_genotype_partial_catalog_copy_device")
-        return SparsePartialGenotypes(self.n_reads, m, *cols, int(nc.value))
+        return SparsePartialGenotypes(self.n_reads, m, *cols, candidates)
 
     def call_alleles(self, gt, measure="copies", min_ratio: float = 0.0, min_support: int = 2, min_percent: int = 20, min_sep: int = 1) -> AlleleCalls:
         """Allele calls (mtr_call_alleles_device): the rows of genotype_loci - one call's Genotypes, or several batches' joined with torch.cat(dim=0)
@@ -1266,6 +1389,13 @@ class Engine:
         counts, ms = (C.c_int64 * 4)(), (C.c_double * 3)()
         self._check(self.lib.mtr_test_partial_catalog_stats(self.h, counts, ms), "mtr_test_partial_catalog_stats")
         return tuple(int(v) for v in counts), tuple(float(v) for v in ms)
+
+    def test_catalog_build_stats(self):
+        """mtr_test_catalog_build_stats: the host-clock ms of this engine's last build_catalog - (the host's pass over the lengths, the uploads,
+        the device build)"""
+        ms = (C.c_double * 3)()
+        self._check(self.lib.mtr_test_catalog_build_stats(self.h, ms), "mtr_test_catalog_build_stats")
+        return tuple(float(v) for v in ms)
 
     def test_unit_motifs(self, units, read=None, copies=None, repeat_len=None, table_slots: int = 0) -> ReportMotifs:
         """mtr_test_unit_motifs: the kernels of report_motif_tensors on caller-given units, one bytes (or str) per unit.  read: the read of

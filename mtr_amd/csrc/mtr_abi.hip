@@ -14,6 +14,7 @@
 // There is no CPU path: every entry point needs the HIP device the context was created on.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -46,6 +47,7 @@
 #include "catalog.hip.inc"
 #include "partial.hip.inc"
 #include "partial_catalog.hip.inc"
+#include "catalog_build.hip.inc"
 #include "allele_call.hip.inc"
 #include "fasta.hip.inc"
 #include "fastq.hip.inc"
@@ -140,6 +142,7 @@ struct StagedBufs {
 static unsigned *st_line(unsigned long long *sc, int line) { return (unsigned *)(sc + (size_t)line * (ST_LINE_BYTES / 8)); }
 static const int st_sl_cont_slots[ST_NCLS] = { 6, 7, 9, 11, 12, 13, 14, 15 };     // st_sl_cont(class): the continuation lists' sub-list counters
 
+struct LaneSlots;                                   // (defined with the locus search, below)
 #define MTR_N_PHASE_TIMES 8                         // ids 0..7 of mtr_get_kernel_times: the launch and the phases of the chain; 8, 9: the two dominant kernels
 struct mtr_ctx {
     int device = 0, manhattan = 1; float min_ratio = 0.6f;
@@ -256,6 +259,12 @@ struct mtr_ctx {
     int64_t pc_counts[4] = { 0, 0, 0, 0 }; double pc_ms[3] = { 0, 0, 0 };       // the last such call, for mtr_test_partial_catalog_stats
     DevBuf<int32_t> d_pc_cand, d_pc_row, d_pc_ext, d_pc_i32; DevBuf<uint32_t> d_pc_ftask; DevBuf<int64_t> d_pc_i64, d_pc_toff; DevBuf<PtTask> d_pc_task;
     DevBuf<int32_t> d_pk_read, d_pk_locus, d_pk_fdist, d_pk_window, d_pk_ext; DevBuf<float> d_pk_ratio; DevBuf<uint8_t> d_pk_partial, d_pk_slot, d_pk_open;
+    // mtr_catalog_create keeps nothing in the context but the host clock of its last success (mtr_test_catalog_build_stats); its working
+    // buffers live for the call
+    bool cb_ready = false; double cb_ms[3] = { 0, 0, 0 };
+    // the lane slots genotype_align_tables last derived and uploaded (slot_q | q_slot in d_gt_i32, at gt_ls_at): of prepared catalogue gt_ls_cat
+    // (0: of a text-taking call, never reused) under MTR_TEST_MOTIF_LANE_MAX = gt_ls_lane_max
+    std::shared_ptr<const LaneSlots> gt_ls; uint64_t gt_ls_cat = 0; int gt_ls_lane_max = 0; const int32_t *gt_ls_at = nullptr;
     // allele calls (mtr_call_alleles_device), per call and nothing kept, buffers of its own so that what the genotype and the locus search keep stays:
     // d_ac_i32 = count | cursor (spread while the loci are few), d_ac_i64 = support_off | tile_off | state, the keys, the split's prefix sums
     DevBuf<int32_t> d_ac_i32; DevBuf<int64_t> d_ac_i64, d_ac_prefix; DevBuf<unsigned long long> d_ac_keys;
@@ -2541,6 +2550,10 @@ static mtr_status genotype_check_args(mtr_ctx *ctx, const char *seqs, const int6
 
 static mtr_status genotype_align(mtr_ctx *ctx, const std::string &mot, const std::vector<int64_t> &mot_off, int32_t n_loci, int64_t N, int max_len,
                                  int32_t gain, int32_t mismatch, int32_t indel, const char *who);      // (defined below the call)
+// the 2 * n_loci single-strand motif slots on the device - the slots' codes, their offsets, their 2-bit forms - and the offsets on the host
+// cat_id: the prepared catalogue they belong to (mtr_catalog::id), 0 for tables a text-taking call made for itself
+struct GtTables { const uint8_t *d_units; const int32_t *d_uoff; const uint64_t *d_bits; const std::vector<int32_t> *unit_off; uint64_t cat_id; };
+static mtr_status genotype_align_tables(mtr_ctx *ctx, const GtTables &tb, int32_t n_loci, int64_t N, int max_len, int32_t gain, int32_t mismatch, int32_t indel, const char *who);
 
 // ---- locus genotyping (genotype.hip.inc) --------------------------------------------------------------------------------------------
 // The flank step over four slots per locus, the pairing, one look at the device (how many windows, their longest), one round of the locus
@@ -2590,11 +2603,9 @@ extern "C" mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, c
 static mtr_status genotype_align(mtr_ctx *ctx, const std::string &mot, const std::vector<int64_t> &mot_off, int32_t n_loci, int64_t N, int max_len,
                                  int32_t gain, int32_t mismatch, int32_t indel, const char *who)
 {
-    const int n = ctx->n_reads, M2 = 2 * n_loci;
-    int32_t st[LOCI_STATE];
+    const int M2 = 2 * n_loci;
     {
         // the slots: locus l as given (2 * l) and reverse-complemented (2 * l + 1), one strand each
-        const int lane_max = ctx->sw.motif_lane_max, lane_rows = ctx->sw.motif_lane_rows;
         std::string both; std::vector<int64_t> both_off(1, 0);
         static const char letters[4] = { 'A', 'C', 'G', 'T' };
         for (int32_t l = 0; l < n_loci; l++) {
@@ -2605,25 +2616,49 @@ static mtr_status genotype_align(mtr_ctx *ctx, const std::string &mot, const std
         }
         std::vector<uint8_t> units; std::vector<int32_t> unit_off; std::vector<uint64_t> bits;
         motif_slots(both.data(), both_off.data(), M2, 1, units, unit_off, bits);
-        const LaneSlots ls = lane_slots(unit_off, M2, lane_max);
-        const std::vector<int32_t> &slot_q = ls.slot_q, &q_slot = ls.q_slot;
-        const size_t sS = (size_t)M2, nq = q_slot.size(), nt = (size_t)N;
+        // device copies: d_gt_i32 = unit_off | slot_q | q_slot (the two lists are genotype_align_tables'), d_gt_i64 = bits
+        const size_t sS = (size_t)M2;
+        HIPCHK(ctx->d_gt_i32.ensure((3 * sS + 2) * 4)); HIPCHK(ctx->d_gt_i64.ensure(sS * 8)); HIPCHK(ctx->d_gt_units.ensure(units.size() + 16));
+        HIPCHK(copy_sync(ctx, ctx->d_gt_i32, unit_off.data(), (sS + 1) * 4, hipMemcpyHostToDevice));
+        HIPCHK(copy_sync(ctx, ctx->d_gt_i64, bits.data(), sS * 8, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_gt_units, units.data(), units.size(), hipMemcpyHostToDevice));
+        const GtTables tb = { ctx->d_gt_units, ctx->d_gt_i32, (const uint64_t *)(int64_t *)ctx->d_gt_i64, &unit_off, 0 };
+        return genotype_align_tables(ctx, tb, n_loci, N, max_len, gain, mismatch, indel, who);
+    }
+}
+
+// The alignment step from the device tables, whoever made them: the lane slots of this call's MTR_TEST_MOTIF_LANE_MAX from the units' lengths
+// (the context's d_gt_i32 behind the text-taking calls' unit_off: slot_q | q_slot - a prepared catalogue is never written to), the round.
+static mtr_status genotype_align_tables(mtr_ctx *ctx, const GtTables &tb, int32_t n_loci, int64_t N, int max_len, int32_t gain, int32_t mismatch, int32_t indel, const char *who)
+{
+    const int n = ctx->n_reads, M2 = 2 * n_loci;
+    int32_t st[LOCI_STATE];
+    {
+        const int lane_max = ctx->sw.motif_lane_max, lane_rows = ctx->sw.motif_lane_rows;
+        const size_t sS = (size_t)M2, nt = (size_t)N;
+        HIPCHK(ctx->d_gt_i32.ensure((3 * sS + 2) * 4));
+        const int32_t *d_uoff = tb.d_uoff;
+        int32_t *d_slot_q = (int32_t *)ctx->d_gt_i32 + sS + 1, *d_q_slot = d_slot_q + sS;
+        // the lane slots: a prepared catalogue's, once derived and uploaded for this lane_max, stay in the context (its d_gt_i32 at this address)
+        // until another catalogue, another lane_max or a text-taking call (cat_id = 0) takes their place; batch after batch sends nothing
+        if (!(tb.cat_id != 0 && ctx->gt_ls && ctx->gt_ls_cat == tb.cat_id && ctx->gt_ls_lane_max == lane_max && ctx->gt_ls_at == d_slot_q)) {
+            ctx->gt_ls_cat = 0;
+            const std::shared_ptr<const LaneSlots> fresh = std::make_shared<const LaneSlots>(lane_slots(*tb.unit_off, M2, lane_max));
+            HIPCHK(copy_sync(ctx, d_slot_q, fresh->slot_q.data(), sS * 4, hipMemcpyHostToDevice));
+            if (!fresh->q_slot.empty()) HIPCHK(copy_sync(ctx, d_q_slot, fresh->q_slot.data(), fresh->q_slot.size() * 4, hipMemcpyHostToDevice));
+            ctx->gt_ls = fresh; ctx->gt_ls_cat = tb.cat_id; ctx->gt_ls_lane_max = lane_max; ctx->gt_ls_at = d_slot_q;
+        }
+        const LaneSlots &ls = *ctx->gt_ls;
+        const size_t nq = ls.q_slot.size();
         if ((int64_t)nq * MLO_N_CLASSES > (int64_t)INT32_MAX) { ctx->err = std::to_string(nq) + " short motifs are more than the bins take"; return MTR_ERR_OVERFLOW; }
         const size_t nb = nq * MLO_N_CLASSES;
-        // device copies: d_gt_i32 = unit_off | slot_q | q_slot, d_gt_i64 = bits; the bins: d_gt_bin32 = hist | groups, d_gt_bin64 = tfirst | gfirst;
-        // the tasks: d_gt_task32 = tbin | trank | sorted | wlist
-        HIPCHK(ctx->d_gt_i32.ensure((2 * sS + 1 + nq + 1) * 4)); HIPCHK(ctx->d_gt_i64.ensure(sS * 8)); HIPCHK(ctx->d_gt_units.ensure(units.size() + 16));
+        // the bins: d_gt_bin32 = hist | groups, d_gt_bin64 = tfirst | gfirst; the tasks: d_gt_task32 = tbin | trank | sorted | wlist
         HIPCHK(ctx->d_gt_bin32.ensure((2 * nb + 1) * 4)); HIPCHK(ctx->d_gt_bin64.ensure(2 * (nb + 1) * 8)); HIPCHK(ctx->d_gt_counter.ensure(5 * 8));
         HIPCHK(ctx->d_gt_task32.ensure(4 * nt * 4)); HIPCHK(ctx->d_gt_res.ensure(nt * MS_RES * 4));
-        int32_t *d_uoff = ctx->d_gt_i32, *d_slot_q = d_uoff + sS + 1, *d_q_slot = d_slot_q + sS;
-        HIPCHK(copy_sync(ctx, d_uoff, unit_off.data(), (sS + 1) * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_slot_q, slot_q.data(), sS * 4, hipMemcpyHostToDevice));
-        if (nq > 0) HIPCHK(copy_sync(ctx, d_q_slot, q_slot.data(), nq * 4, hipMemcpyHostToDevice));
-        HIPCHK(copy_sync(ctx, ctx->d_gt_i64, bits.data(), sS * 8, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_gt_units, units.data(), units.size(), hipMemcpyHostToDevice));
         LociArgs a{};
         a.b.packed = ctx->d_packed; a.b.woff = ctx->d_woff; a.b.lens = ctx->d_lens; a.b.order = nullptr; a.b.n_reads = n;
         a.iv = ctx->d_gt_iv; a.n_iv = (int32_t)N;
         a.n_motifs = M2; a.n_strands = 1; a.G = gain; a.MM = mismatch; a.D = indel; a.lane_rows = lane_rows;
-        a.units = ctx->d_gt_units; a.unit_off = d_uoff; a.bits = (const uint64_t *)(int64_t *)ctx->d_gt_i64; a.slot_q = d_slot_q; a.q_slot = d_q_slot;
+        a.units = tb.d_units; a.unit_off = d_uoff; a.bits = tb.d_bits; a.slot_q = d_slot_q; a.q_slot = d_q_slot;
         a.hist = ctx->d_gt_bin32; a.groups = a.hist + nb; a.tfirst = ctx->d_gt_bin64; a.gfirst = a.tfirst + nb + 1; a.n_bins = (int32_t)nb;
         a.tbin = ctx->d_gt_task32; a.trank = a.tbin + nt; a.sorted = a.trank + nt; a.wlist = a.sorted + nt; a.res = ctx->d_gt_res;
         a.state = ctx->d_gt_state; a.dp16_max_rows = ctx->sw.dp16_max_rows;
@@ -2662,14 +2697,48 @@ struct CatIndex {
     size_t E = 0, distinct = 0, fwords = 0; uint32_t cap = 0; int fbits = 0;
     bool narrow = false, wide = false;                       // a slot of either flank word exists
     const uint32_t *d_filter = nullptr, *d_key = nullptr; const int32_t *d_run = nullptr, *d_ent = nullptr, *d_plen = nullptr;
+    const uint64_t *d_masks = nullptr;                       // the slots' masks: ctx->d_ct_masks, or a prepared catalogue's
 };
+
+// A prepared catalogue (mtr_catalog_create): what depends on the loci alone.  On the host what lengths decide; on the device, in buffers of its
+// own (no context owns them: any context of the device may read them, none writes), the index as CatIndex points into it, the slots' masks,
+// the genotype's 2 * n_loci single-strand motif slots (GtTables) and the partial genotype's variants (vbits, ulen).
+struct mtr_catalog {
+    uint64_t id = 0;                                        // never 0 and never given twice in a process: what a context remembers a catalogue by
+    int device = 0; int32_t n_loci = 0, max_flank_dist = 0, seed_len = 0;
+    size_t E = 0, distinct = 0, fwords = 0; uint32_t cap = 0; int fbits = 0;
+    int64_t n_short = 0, n_long = 0;                        // slots of at most / of more than 32 bases: which flank words a call launches
+    int64_t first_long_motif = -1;
+    std::vector<int64_t> mot_off;                           // [n_loci + 1]: the motifs' lengths as search_motifs_check_size takes them
+    std::vector<int32_t> unit_off;                          // [2 * n_loci + 1]: the motif slots' offsets (lane_slots)
+    DevBuf<uint32_t> d_filter, d_key; DevBuf<int32_t> d_run, d_ent, d_plen, d_uoff, d_ulen; DevBuf<uint64_t> d_masks, d_ubits, d_vbits; DevBuf<uint8_t> d_units;
+    size_t device_bytes() const { return d_filter.cap + d_key.cap + d_run.cap + d_ent.cap + d_plen.cap + d_uoff.cap + d_ulen.cap + d_masks.cap + d_ubits.cap + d_vbits.cap + d_units.cap; }
+};
+static GtTables catalog_gt_tables(const mtr_catalog *cat) { return { cat->d_units, cat->d_uoff, cat->d_ubits, &cat->unit_off, cat->id }; }
+
+// what a catalogue call runs on beside the index: the motifs as text (the text-taking calls), or a prepared catalogue's tables
+struct CatMotifs { const std::string *mot; const std::vector<int64_t> *mot_off; const mtr_catalog *cat; };
+static mtr_status genotype_catalog_run(mtr_ctx *ctx, const CatIndex &ix, const CatMotifs &cm, int32_t n_loci, int32_t max_flank_dist, int q, int32_t gain, int32_t mismatch,
+                                       int32_t indel, double ms_index, int64_t *out_rows, int64_t *out_candidates);
+static mtr_status genotype_partial_catalog_run(mtr_ctx *ctx, const CatIndex &ix, const CatMotifs &cm, int32_t n_loci, int32_t max_flank_dist, int q, int32_t gain,
+                                               int32_t mismatch, int32_t indel, int32_t max_tail, double ms_index, int64_t *out_rows, int64_t *out_candidates);
+
+// What every catalogue call needs beside an index, whichever made it: the reads' count and offset buffers sized, the status and the filter's
+// count zeroed
+static mtr_status catalog_scan_buffers(mtr_ctx *ctx)
+{
+    const size_t nr = (size_t)ctx->n_reads;
+    HIPCHK(ctx->d_ct_count.ensure(2 * nr * 4)); HIPCHK(ctx->d_ct_off.ensure(2 * (nr + 1) * 8)); HIPCHK(ctx->d_ct_status.ensure(4)); HIPCHK(ctx->d_ct_passed.ensure(8));
+    HIPCHK(hipMemsetAsync(ctx->d_ct_status, 0, 4, ctx->stream)); HIPCHK(hipMemsetAsync(ctx->d_ct_passed, 0, 8, ctx->stream));
+    return MTR_OK;
+}
 
 // The index built on the host and sent up: the entries (code, locus * 4 + slot) sorted and made distinct, a table slot per distinct code, the
 // filter over the codes, the slots' masks (ctx->d_ct_masks) and lengths; the reads' count and offset buffers sized, the status and the filter's
 // count zeroed.  The copies are synchronous.
 static mtr_status catalog_index(mtr_ctx *ctx, const std::vector<std::vector<uint8_t>> &pat, int seeds, int q, CatIndex &o)
 {
-    const size_t nr = (size_t)ctx->n_reads, S = pat.size();
+    const size_t S = pat.size();
     std::vector<std::pair<uint32_t, int32_t>> ent;
     ent.reserve(S * (size_t)seeds);
     std::vector<uint64_t> masks(S * FL_MASKS); std::vector<int32_t> plen(S);
@@ -2699,9 +2768,9 @@ static mtr_status catalog_index(mtr_ctx *ctx, const std::vector<std::vector<uint
     }
     std::copy(plen.begin(), plen.end(), h_plen);
     HIPCHK(ctx->d_ct_ix.ensure(ix.size() * 4)); HIPCHK(ctx->d_ct_masks.ensure(masks.size() * 8));
-    HIPCHK(ctx->d_ct_count.ensure(2 * nr * 4)); HIPCHK(ctx->d_ct_off.ensure(2 * (nr + 1) * 8)); HIPCHK(ctx->d_ct_status.ensure(4)); HIPCHK(ctx->d_ct_passed.ensure(8));
     HIPCHK(copy_sync(ctx, ctx->d_ct_ix, ix.data(), ix.size() * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_ct_masks, masks.data(), masks.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(ctx->d_ct_status, 0, 4, ctx->stream)); HIPCHK(hipMemsetAsync(ctx->d_ct_passed, 0, 8, ctx->stream));
+    { mtr_status st = catalog_scan_buffers(ctx); if (st != MTR_OK) return st; }
+    o.d_masks = ctx->d_ct_masks;
     o.E = E; o.distinct = distinct; o.fwords = fwords; o.cap = cap; o.fbits = fbits;
     o.d_filter = (const uint32_t *)(int32_t *)ctx->d_ct_ix; o.d_key = o.d_filter + fwords;
     o.d_run = (const int32_t *)(o.d_key + cap); o.d_ent = o.d_run + 2 * (size_t)cap; o.d_plen = o.d_ent + E;
@@ -2748,18 +2817,26 @@ extern "C" mtr_status mtr_genotype_catalog_device(mtr_ctx *ctx, const char *seqs
     HIPCHK(hipSetDevice(ctx->device));
     read_switches(ctx->sw);
     const auto t_start = std::chrono::steady_clock::now();
-    const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-    const int n = ctx->n_reads, seeds = max_flank_dist + 1;
-    const size_t nr = (size_t)n;
     CatIndex ix;
-    { mtr_status st = catalog_index(ctx, pat, seeds, q, ix); if (st != MTR_OK) return st; }
+    { mtr_status st = catalog_index(ctx, pat, max_flank_dist + 1, q, ix); if (st != MTR_OK) return st; }
+    const double ms_index = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();    // the host's index and its upload (the copies are synchronous)
+    const CatMotifs cm = { &mot, &mot_off, nullptr };
+    return genotype_catalog_run(ctx, ix, cm, n_loci, max_flank_dist, q, gain, mismatch, indel, ms_index, out_rows, out_candidates);
+}
+
+// The catalogue genotype from the index on, whoever made it (ix, cm): the scan, the candidates, the rows kept in the context, the statistics
+static mtr_status genotype_catalog_run(mtr_ctx *ctx, const CatIndex &ix, const CatMotifs &cm, int32_t n_loci, int32_t max_flank_dist, int q, int32_t gain, int32_t mismatch,
+                                       int32_t indel, double ms_index, int64_t *out_rows, int64_t *out_candidates)
+{
+    const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    const int n = ctx->n_reads;
+    const size_t nr = (size_t)n;
     const bool narrow = ix.narrow, wide = ix.wide;
     const int32_t *d_plen = ix.d_plen;
     int32_t *hit_count = ctx->d_ct_count, *cand_count = hit_count + nr;
     int64_t *hit_off = ctx->d_ct_off, *cand_off = hit_off + nr + 1;
     const dim3 per_read((unsigned)n), b64(64), b256(256), one(1), b1024(1024);
     // the scan: the reads' hits counted, then written
-    const double ms_index = ms_since(t_start);                         // the host's index and its upload (the copies are synchronous)
     const auto t_scan = std::chrono::steady_clock::now();
     CatScanArgs sa{};
     int64_t H = 0, Cn = 0, R = 0;
@@ -2791,7 +2868,7 @@ extern "C" mtr_status mtr_genotype_catalog_device(mtr_ctx *ctx, const char *seqs
             // the candidates' two flank scans each
             CatFlankArgs fa{};
             fa.b = sa.b; fa.cand_read = cand_read; fa.cand_key = cand_key; fa.n_tasks = (int32_t)(2 * Cn);
-            fa.masks = ctx->d_ct_masks; fa.plen = d_plen; fa.all_wide = ctx->sw.flank_word == 64; fa.res = ctx->d_ct_flank; fa.status = ctx->d_ct_status;
+            fa.masks = ix.d_masks; fa.plen = d_plen; fa.all_wide = ctx->sw.flank_word == 64; fa.res = ctx->d_ct_flank; fa.status = ctx->d_ct_status;
             const dim3 per_task((unsigned)((2 * nc + 63) / 64));
             if (narrow) hipLaunchKernelGGL(mtr_k_cat_flank<uint32_t>, per_task, b64, 0, ctx->stream, fa);
             if (wide) hipLaunchKernelGGL(mtr_k_cat_flank<uint64_t>, per_task, b64, 0, ctx->stream, fa);
@@ -2813,7 +2890,11 @@ extern "C" mtr_status mtr_genotype_catalog_device(mtr_ctx *ctx, const char *seqs
             if (st[LOCI_STATUS] != DEV_OK || R < 0 || R > Cn || N < 0 || N > R || max_len < 0 || max_len > ctx->Lmax || (N > 0) != (max_len > 0)) {
                 ctx->err = "the catalogue's pairing failed on the device (status " + std::to_string(st[LOCI_STATUS]) + ")"; return MTR_ERR_HIP;
             }
-            if (N > 0) { mtr_status r = genotype_align(ctx, mot, mot_off, n_loci, N, max_len, gain, mismatch, indel, "genotype_catalog"); if (r != MTR_OK) return r; }
+            if (N > 0) {
+                const mtr_status r = cm.cat ? genotype_align_tables(ctx, catalog_gt_tables(cm.cat), n_loci, N, max_len, gain, mismatch, indel, "genotype_catalog")
+                                            : genotype_align(ctx, *cm.mot, *cm.mot_off, n_loci, N, max_len, gain, mismatch, indel, "genotype_catalog");
+                if (r != MTR_OK) return r;
+            }
             if (R > 0) {
                 const size_t rr = (size_t)R;
                 HIPCHK(ctx->d_gc_read.ensure(rr * 4)); HIPCHK(ctx->d_gc_locus.ensure(rr * 4)); HIPCHK(ctx->d_gc_spanning.ensure(rr)); HIPCHK(ctx->d_gc_orientation.ensure(rr));
@@ -2996,15 +3077,23 @@ extern "C" mtr_status mtr_genotype_partial_catalog_device(mtr_ctx *ctx, const ch
     HIPCHK(hipSetDevice(ctx->device));
     read_switches(ctx->sw);
     const auto t_start = std::chrono::steady_clock::now();
+    CatIndex ix;
+    { mtr_status st = catalog_index(ctx, pat, max_flank_dist + 1, q, ix); if (st != MTR_OK) return st; }
+    const double ms_index = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();    // the host's index and its upload (the copies are synchronous)
+    const CatMotifs cm = { &mot, &mot_off, nullptr };
+    return genotype_partial_catalog_run(ctx, ix, cm, n_loci, max_flank_dist, q, gain, mismatch, indel, max_tail, ms_index, out_rows, out_candidates);
+}
+
+// The partial genotype at catalogue scale from the index on, whoever made it (ix, cm)
+static mtr_status genotype_partial_catalog_run(mtr_ctx *ctx, const CatIndex &ix, const CatMotifs &cm, int32_t n_loci, int32_t max_flank_dist, int q, int32_t gain,
+                                               int32_t mismatch, int32_t indel, int32_t max_tail, double ms_index, int64_t *out_rows, int64_t *out_candidates)
+{
     const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
     const int n = ctx->n_reads;
     const size_t nr = (size_t)n, nl = (size_t)n_loci;
-    CatIndex ix;
-    { mtr_status st = catalog_index(ctx, pat, max_flank_dist + 1, q, ix); if (st != MTR_OK) return st; }
     int32_t *cand_count = ctx->d_ct_count + nr;
     int64_t *hit_off = ctx->d_ct_off, *cand_off = hit_off + nr + 1;
     const dim3 per_read((unsigned)n), b64(64), b256(256), one(1), b1024(1024);
-    const double ms_index = ms_since(t_start);                         // the host's index and its upload (the copies are synchronous)
     const auto t_scan = std::chrono::steady_clock::now();
     CatScanArgs sa{};
     int64_t H = 0, Cn = 0, R = 0;
@@ -3047,18 +3136,25 @@ extern "C" mtr_status mtr_genotype_partial_catalog_device(mtr_ctx *ctx, const ch
         hipLaunchKernelGGL(mtr_k_ptc_tasks, per_cand, b256, 0, ctx->stream, ta);
         PtcFlankArgs fa{};
         fa.b = sa.b; fa.cand_read = cand_read; fa.cand_locus = cand_locus; fa.n_cand = (int32_t)Cn; fa.tasks = ctx->d_pc_ftask; fa.n_tasks = (int32_t)F;
-        fa.masks = ctx->d_ct_masks; fa.plen = ix.d_plen; fa.all_wide = ctx->sw.flank_word == 64; fa.res = ctx->d_ct_flank; fa.status = ctx->d_ct_status;
+        fa.masks = ix.d_masks; fa.plen = ix.d_plen; fa.all_wide = ctx->sw.flank_word == 64; fa.res = ctx->d_ct_flank; fa.status = ctx->d_ct_status;
         const dim3 per_task((unsigned)(((size_t)F + 63) / 64));
         if (ix.narrow) hipLaunchKernelGGL(mtr_k_ptc_flank<uint32_t>, per_task, b64, 0, ctx->stream, fa);
         if (ix.wide) hipLaunchKernelGGL(mtr_k_ptc_flank<uint64_t>, per_task, b64, 0, ctx->stream, fa);
         // the variants; d_pc_i32 = status | count[4] | ulen, d_pc_i64 = bits
-        std::vector<uint64_t> bits; std::vector<int32_t> ulen;
-        partial_variants(mot, mot_off, n_loci, bits, ulen);
-        HIPCHK(ctx->d_pc_i32.ensure((1 + PTC_BUCKETS + nl) * 4)); HIPCHK(ctx->d_pc_i64.ensure(bits.size() * 8));
+        // (a prepared catalogue brings its own bits and ulen; the text-taking call makes them here and keeps them behind its status words)
+        HIPCHK(ctx->d_pc_i32.ensure((1 + PTC_BUCKETS + nl) * 4));
         HIPCHK(ctx->d_pc_row.ensure(nc * PT_ROW * 4)); HIPCHK(ctx->d_pc_ext.ensure(nc * PT_EXT * 4)); HIPCHK(ctx->d_pc_task.ensure(PTC_BUCKETS * nc * sizeof(PtTask)));
-        int32_t *d_status = ctx->d_pc_i32, *d_count = d_status + 1, *d_ulen = d_count + PTC_BUCKETS;
+        int32_t *d_status = ctx->d_pc_i32, *d_count = d_status + 1;
+        const int32_t *d_ulen = d_count + PTC_BUCKETS; const uint64_t *d_vbits = nullptr;
         HIPCHK(hipMemsetAsync(d_status, 0, (1 + PTC_BUCKETS) * 4, ctx->stream));
-        HIPCHK(copy_sync(ctx, d_ulen, ulen.data(), nl * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_pc_i64, bits.data(), bits.size() * 8, hipMemcpyHostToDevice));
+        if (cm.cat) { d_ulen = cm.cat->d_ulen; d_vbits = cm.cat->d_vbits; }
+        else {
+            std::vector<uint64_t> bits; std::vector<int32_t> ulen;
+            partial_variants(*cm.mot, *cm.mot_off, n_loci, bits, ulen);
+            HIPCHK(ctx->d_pc_i64.ensure(bits.size() * 8));
+            HIPCHK(copy_sync(ctx, d_count + PTC_BUCKETS, ulen.data(), nl * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_pc_i64, bits.data(), bits.size() * 8, hipMemcpyHostToDevice));
+            d_vbits = (const uint64_t *)(int64_t *)ctx->d_pc_i64;
+        }
         // the pairing, and the rows' places
         const PtcPairArgs pa = { cand_read, cand_locus, (int32_t)Cn, ctx->d_ct_flank, ctx->d_lens, d_ulen, max_flank_dist, ctx->d_pc_row, is_row, ctx->d_pc_task, d_count, d_status };
         hipLaunchKernelGGL(mtr_k_ptc_pair, per_cand, b256, 0, ctx->stream, pa);
@@ -3076,7 +3172,7 @@ extern "C" mtr_status mtr_genotype_partial_catalog_device(mtr_ctx *ctx, const ch
         if (tasks > 0) {
             PtcExtArgs a{};
             a.b = sa.b; a.cand_read = cand_read; a.tasks = ctx->d_pc_task; a.count = d_count; a.n_cand = (int32_t)Cn;
-            a.bits = (const uint64_t *)(int64_t *)ctx->d_pc_i64; a.ulen = d_ulen; a.G = gain; a.MM = mismatch; a.D = indel; a.ext = ctx->d_pc_ext; a.status = d_status;
+            a.bits = d_vbits; a.ulen = d_ulen; a.G = gain; a.MM = mismatch; a.D = indel; a.ext = ctx->d_pc_ext; a.status = d_status;
             for (int b = 0; b < PTC_BUCKETS; b++) {
                 if (head[1 + b] == 0) continue;
                 const dim3 grid((unsigned)((head[1 + b] + 63) / 64));
@@ -3143,6 +3239,263 @@ extern "C" mtr_status mtr_genotype_partial_catalog_copy_device(mtr_ctx *ctx, con
     HIPCHK(hipMemcpyAsync(g.ext, ctx->d_pk_ext, r * 24, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(g.ratio, ctx->d_pk_ratio, r * 4, dd, ctx->stream));
     HIPCHK(hipMemcpyAsync(g.open, ctx->d_pk_open, r, dd, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- a prepared locus catalogue (catalog_build.hip.inc) ---------------------------------------------------------------------------------
+// mtr_catalog_create: one pass over seq_off on the host (the checks that lengths decide, the slots' and the motifs' lengths and offsets), one
+// upload of the letters and of those small arrays, the letters' check (a second look at the device: the first bad byte), then the build - the
+// slots, the sort's passes (count, scan, fill), the flags and their two scans, a third look (the entries, the distinct codes: they size the
+// catalogue's buffers), the compaction, the table, the motif tables - and the status.  The working buffers are freed when the call returns.
+// The two prepared calls are the text-taking calls from the index on (genotype_catalog_run, genotype_partial_catalog_run).
+static std::string catalog_flank_name(int64_t l, int side) { return "locus " + std::to_string(l) + ", " + (side ? "right" : "left") + " flank"; }
+
+extern "C" mtr_status mtr_catalog_create(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist, int32_t seed_len, mtr_catalog **out)
+{
+    if (!ctx || !out) return MTR_ERR_BAD_ARG;
+    *out = nullptr;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    const auto t_host = std::chrono::steady_clock::now();
+    // genotype_check_args' checks that need no batch, in its order
+    if (n_loci <= 0) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
+    if (!seqs || !seq_off) { ctx->err = "seqs or seq_off is NULL"; return MTR_ERR_BAD_ARG; }
+    if (n_loci > INT32_MAX / 4) { ctx->err = "more than 2^29 - 1 loci"; return MTR_ERR_BAD_ARG; }
+    for (int32_t k = 0; k < 3 * n_loci; k++)
+        if (seq_off[k + 1] < seq_off[k]) { ctx->err = "seq_off decreases at locus " + std::to_string(k / 3) + " (sequence " + std::to_string(k % 3) + ")"; return MTR_ERR_BAD_ARG; }
+    // the pass over the lengths: the first refusal of a length among the motifs and among the flanks, as keys in the checks' order (the device
+    // adds the first bad byte, catb_bad_key: all motifs come before the first flank); the arrays that lengths decide
+    const size_t nl = (size_t)n_loci, S = nl * GT_SLOTS;
+    std::unique_ptr<mtr_catalog> cat(new mtr_catalog);
+    static std::atomic<uint64_t> next_id{ 1 };
+    cat->id = next_id.fetch_add(1);
+    cat->device = ctx->device; cat->n_loci = n_loci; cat->max_flank_dist = max_flank_dist; cat->seed_len = seed_len;
+    cat->mot_off.assign(nl + 1, 0); cat->unit_off.assign(2 * nl + 1, 0);
+    std::vector<int32_t> plen(S), ulen(nl);
+    std::vector<int64_t> off(3 * nl + 1);
+    const auto host_key = [](int is_flank, int64_t index) { return ((unsigned long long)is_flank << 62) | ((unsigned long long)index << 10); };
+    unsigned long long first_bad = CATB_NO_BAD_BYTE;
+    int64_t motif_bases = 0, units_at = 0;
+    for (size_t l = 0; l < nl; l++) {
+        const int64_t U = seq_off[3 * l + 2] - seq_off[3 * l + 1];
+        motif_bases += U;
+        cat->mot_off[l + 1] = motif_bases;
+        if (U < 1 || U >= MTRC_MAX_PERIOD) first_bad = std::min(first_bad, host_key(0, (int64_t)l));
+        if (U > MDP_MAX_U && cat->first_long_motif < 0) cat->first_long_motif = (int64_t)l;
+        ulen[l] = (int32_t)std::min<int64_t>(U, INT32_MAX);
+        const int64_t u = std::min<int64_t>(std::max<int64_t>(U, 0), MTRC_MAX_PERIOD);          // (a refused length is never built: the offsets only stay 32-bit)
+        cat->unit_off[2 * l] = (int32_t)units_at; cat->unit_off[2 * l + 1] = (int32_t)(units_at + u); units_at += 2 * u;
+        for (int side = 0; side < 2; side++) {
+            const int64_t m = seq_off[3 * l + 2 * (size_t)side + 1] - seq_off[3 * l + 2 * (size_t)side];
+            if (m < 1 || m > FBV_MAX_M) first_bad = std::min(first_bad, host_key(1, 2 * (int64_t)l + side));
+            const int32_t mm = (int32_t)std::min<int64_t>(m, INT32_MAX);
+            plen[l * GT_SLOTS + (size_t)side] = mm; plen[l * GT_SLOTS + 2 + (size_t)side] = mm;
+            (m <= 32 ? cat->n_short : cat->n_long) += 2;
+        }
+        for (int k = 0; k < 3; k++) off[3 * l + (size_t)k] = seq_off[3 * l + (size_t)k] - seq_off[0];
+    }
+    cat->unit_off[2 * nl] = (int32_t)units_at;
+    off[3 * nl] = seq_off[3 * nl] - seq_off[0];
+    if (motif_bases > INT32_MAX / 2) { ctx->err = "more than 2^30 - 1 motifs or motif bases"; return MTR_ERR_BAD_ARG; }
+    const int64_t n_bytes = off[3 * nl];
+    const double ms_host = ms_since(t_host);
+    // the uploads, and the letters' check
+    HIPCHK(hipSetDevice(ctx->device));
+    const auto t_up = std::chrono::steady_clock::now();
+    DevBuf<char> w_seqs; DevBuf<int64_t> w_off; DevBuf<unsigned long long> w_bad; DevBuf<int32_t> w_status;
+    HIPCHK(w_seqs.alloc((size_t)n_bytes + 16)); HIPCHK(w_off.alloc((3 * nl + 1) * 8)); HIPCHK(w_bad.alloc(8)); HIPCHK(w_status.alloc(4));
+    HIPCHK(cat->d_plen.alloc(S * 4)); HIPCHK(cat->d_uoff.alloc((2 * nl + 1) * 4)); HIPCHK(cat->d_ulen.alloc(nl * 4));
+    if (n_bytes > 0) HIPCHK(copy_sync(ctx, w_seqs, seqs + seq_off[0], (size_t)n_bytes, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, w_off, off.data(), (3 * nl + 1) * 8, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, cat->d_plen, plen.data(), S * 4, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, cat->d_uoff, cat->unit_off.data(), (2 * nl + 1) * 4, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, cat->d_ulen, ulen.data(), nl * 4, hipMemcpyHostToDevice));
+    const double ms_upload = ms_since(t_up);
+    const auto t_build = std::chrono::steady_clock::now();
+    const CatbSrc src = { w_seqs, w_off, n_loci };
+    const dim3 b64(64), b256(256), one(1), b1024(1024);
+    HIPCHK(hipMemsetAsync(w_bad, 0xFF, 8, ctx->stream)); HIPCHK(hipMemsetAsync(w_status, 0, 4, ctx->stream));
+    hipLaunchKernelGGL(mtr_k_catb_check, dim3((unsigned)((3 * nl + 255) / 256)), b256, 0, ctx->stream, src, (unsigned long long *)w_bad);
+    HIPCHK(hipGetLastError());
+    unsigned long long dev_bad = CATB_NO_BAD_BYTE;
+    HIPCHK(copy_sync(ctx, &dev_bad, w_bad, 8, hipMemcpyDeviceToHost));
+    first_bad = std::min(first_bad, dev_bad);
+    if (first_bad != CATB_NO_BAD_BYTE) {
+        const bool is_flank = (first_bad >> 62) & 1;
+        const int64_t index = (int64_t)((first_bad >> 10) & (((unsigned long long)1 << 52) - 1)), t = (int64_t)(first_bad & 1023) - 1;
+        const size_t k = is_flank ? 3 * (size_t)(index / 2) + 2 * (size_t)(index % 2) : 3 * (size_t)index + 1;
+        const int64_t len = seq_off[k + 1] - seq_off[k];
+        const std::string what = is_flank ? catalog_flank_name(index / 2, (int)(index % 2)) : "motif " + std::to_string(index);
+        if (t < 0) ctx->err = what + ": length " + std::to_string(len) + " outside 1.." + std::to_string(is_flank ? FBV_MAX_M : MTRC_MAX_PERIOD - 1);
+        else if (t >= len) { ctx->err = "the catalogue's check of the letters failed on the device"; return MTR_ERR_HIP; }
+        else ctx->err = what + ": byte " + std::to_string((int)(unsigned char)seqs[seq_off[k] + t]) + " at " + std::to_string(t) + " is none of ACGT";
+        return MTR_ERR_BAD_ARG;
+    }
+    if (max_flank_dist < 0) { ctx->err = "max_flank_dist = " + std::to_string(max_flank_dist) + ": at least 0"; return MTR_ERR_BAD_ARG; }
+    // catalog_check_seeds, from the lengths
+    if (seed_len < SI_MIN_Q || seed_len > SI_MAX_Q) { ctx->err = "seed_len = " + std::to_string(seed_len) + " outside " + std::to_string(SI_MIN_Q) + ".." + std::to_string(SI_MAX_Q); return MTR_ERR_BAD_ARG; }
+    const int64_t need = ((int64_t)max_flank_dist + 1) * seed_len;
+    for (size_t l = 0; l < nl; l++)
+        for (int side = 0; side < 2; side++) {
+            const int32_t m = plen[l * GT_SLOTS + (size_t)side];
+            if ((int64_t)m < need) {
+                ctx->err = catalog_flank_name((int64_t)l, side) + ": " + std::to_string(m) + " bases are fewer than (max_flank_dist + 1) * seed_len = " + std::to_string(need);
+                return MTR_ERR_BAD_ARG;
+            }
+        }
+    // the build.  (need <= 64 from here on: every flank has at most 64 bases)
+    const int q = seed_len, seeds = max_flank_dist + 1;
+    const int64_t E0 = (int64_t)S * seeds;
+    if (E0 > (int64_t)INT32_MAX) { ctx->err = std::to_string(S) + " slots x " + std::to_string(seeds) + " seeds are more than 2^31 - 1 entries"; return MTR_ERR_OVERFLOW; }
+    const size_t e0 = (size_t)E0;
+    const int n_tiles = (int)((e0 + CB_TILE - 1) / CB_TILE);
+    const size_t nh = (size_t)CB_DIGITS * (size_t)n_tiles;
+    DevBuf<uint32_t> w_keys[2], w_rkey; DevBuf<int32_t> w_vals[2], w_hist, w_keep, w_head, w_rfirst; DevBuf<int64_t> w_first, w_keepoff, w_headoff;
+    for (int k = 0; k < 2; k++) { HIPCHK(w_keys[k].alloc(e0 * 4)); HIPCHK(w_vals[k].alloc(e0 * 4)); }
+    HIPCHK(w_hist.alloc(nh * 4)); HIPCHK(w_first.alloc((nh + 1) * 8)); HIPCHK(w_keep.alloc(e0 * 4)); HIPCHK(w_head.alloc(e0 * 4));
+    HIPCHK(w_keepoff.alloc((e0 + 1) * 8)); HIPCHK(w_headoff.alloc((e0 + 1) * 8));
+    HIPCHK(cat->d_masks.alloc(S * FL_MASKS * 8));
+    const CatbSlotArgs sl = { src, cat->d_plen, q, seeds, cat->d_masks, w_keys[0], w_vals[0], w_status };
+    hipLaunchKernelGGL(mtr_k_catb_slots, dim3((unsigned)((S + 63) / 64)), b64, 0, ctx->stream, sl);
+    const int passes = cb_passes(q);
+    for (int p = 0; p < passes; p++) {
+        const int from = p & 1, to = from ^ 1;
+        hipLaunchKernelGGL(mtr_k_catb_count, dim3((unsigned)n_tiles), b64, 0, ctx->stream, (const uint32_t *)w_keys[from], (long long)E0, p, n_tiles, (int32_t *)w_hist);
+        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)w_hist, (int64_t)nh, (int64_t *)w_first);
+        const CatbFillArgs fa = { w_keys[from], w_vals[from], (long long)E0, p, n_tiles, w_first, w_keys[to], w_vals[to], w_status };
+        hipLaunchKernelGGL(mtr_k_catb_fill, dim3((unsigned)n_tiles), b64, 0, ctx->stream, fa);
+    }
+    const uint32_t *s_keys = w_keys[passes & 1]; const int32_t *s_vals = w_vals[passes & 1];
+    const dim3 per_entry((unsigned)((e0 + 255) / 256));
+    hipLaunchKernelGGL(mtr_k_catb_flags, per_entry, b256, 0, ctx->stream, s_keys, s_vals, (long long)E0, (int32_t *)w_keep, (int32_t *)w_head);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)w_keep, E0, (int64_t *)w_keepoff);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)w_head, E0, (int64_t *)w_headoff);
+    HIPCHK(hipGetLastError());
+    int64_t E = 0, distinct = 0; int32_t dev = 0;
+    HIPCHK(copy_sync(ctx, &E, (int64_t *)w_keepoff + e0, 8, hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(ctx, &distinct, (int64_t *)w_headoff + e0, 8, hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(ctx, &dev, w_status, 4, hipMemcpyDeviceToHost));
+    if (dev != DEV_OK || distinct < 1 || distinct > E || E > E0) { ctx->err = "the catalogue's sort failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
+    cat->E = (size_t)E; cat->distinct = (size_t)distinct;
+    cat->cap = cb_table_cap((uint64_t)distinct); cat->fbits = cb_filter_bits((uint64_t)distinct); cat->fwords = ((size_t)1 << cat->fbits) / 32;
+    const size_t cap = cat->cap;
+    HIPCHK(cat->d_filter.alloc(cat->fwords * 4)); HIPCHK(cat->d_key.alloc(cap * 4)); HIPCHK(cat->d_run.alloc(2 * cap * 4)); HIPCHK(cat->d_ent.alloc(cat->E * 4));
+    HIPCHK(w_rkey.alloc(cat->distinct * 4)); HIPCHK(w_rfirst.alloc((cat->distinct + 1) * 4));
+    HIPCHK(hipMemsetAsync(cat->d_filter, 0, cat->fwords * 4, ctx->stream)); HIPCHK(hipMemsetAsync(cat->d_key, 0, cap * 4, ctx->stream)); HIPCHK(hipMemsetAsync(cat->d_run, 0, 2 * cap * 4, ctx->stream));
+    const CatbCompactArgs co = { s_keys, s_vals, (long long)E0, w_keep, w_head, w_keepoff, w_headoff, (long long)E, (long long)distinct, cat->d_ent, w_rkey, w_rfirst, w_status };
+    hipLaunchKernelGGL(mtr_k_catb_compact, per_entry, b256, 0, ctx->stream, co);
+    const CatbTableArgs ta = { w_rkey, w_rfirst, (long long)distinct, cat->d_filter, cat->fbits, cat->d_key, cat->d_run, cat->cap, w_status };
+    hipLaunchKernelGGL(mtr_k_catb_table, dim3((unsigned)((cat->distinct + 255) / 256)), b256, 0, ctx->stream, ta);
+    // the motif tables
+    HIPCHK(cat->d_units.alloc((size_t)units_at + 16)); HIPCHK(cat->d_ubits.alloc(2 * nl * 8)); HIPCHK(cat->d_vbits.alloc(4 * nl * 8));
+    const CatbMotifArgs ma = { src, cat->d_ulen, cat->d_uoff, cat->d_units, cat->d_ubits, cat->d_vbits, w_status };
+    hipLaunchKernelGGL(mtr_k_catb_motifs, dim3((unsigned)((nl + 255) / 256)), b256, 0, ctx->stream, ma);
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(ctx, &dev, w_status, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (dev == CATB_ERR_TABLE_FULL) { ctx->err = "the seed table is full"; return MTR_ERR_HIP; }
+    if (dev != DEV_OK) { ctx->err = "the catalogue's build failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
+    DBG("catalog_create: %zu entries of %zu codes, table of %u slots, filter of 2^%d bits, %zu device bytes", cat->E, cat->distinct, cat->cap, cat->fbits, cat->device_bytes());
+    ctx->cb_ready = true; ctx->cb_ms[0] = ms_host; ctx->cb_ms[1] = ms_upload; ctx->cb_ms[2] = ms_since(t_build);
+    *out = cat.release();
+    return MTR_OK;
+}
+
+extern "C" void mtr_catalog_destroy(mtr_catalog *cat)
+{
+    if (!cat) return;
+    (void)hipSetDevice(cat->device);
+    delete cat;
+}
+
+extern "C" mtr_status mtr_catalog_info_get(const mtr_catalog *cat, mtr_catalog_info *info)
+{
+    if (!cat || !info) return MTR_ERR_BAD_ARG;
+    info->n_loci = cat->n_loci; info->max_flank_dist = cat->max_flank_dist; info->seed_len = cat->seed_len; info->filter_bits = cat->fbits;
+    info->entries = (int64_t)cat->E; info->distinct_codes = (int64_t)cat->distinct; info->table_slots = (int64_t)cat->cap;
+    info->first_long_motif = cat->first_long_motif; info->device_bytes = (int64_t)cat->device_bytes();
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_test_catalog_build_stats(mtr_ctx *ctx, double *ms)
+{
+    if (!ctx || !ms) return MTR_ERR_BAD_ARG;
+    if (!ctx->cb_ready) { ctx->err = "no mtr_catalog_create to report on"; return MTR_ERR_BAD_ARG; }
+    std::copy(ctx->cb_ms, ctx->cb_ms + 3, ms);
+    return MTR_OK;
+}
+
+// the prepared calls' checks that depend on the batch or the call, in their order; on MTR_OK the switches are read and ix points into cat
+static mtr_status catalog_prepared_begin(mtr_ctx *ctx, const mtr_catalog *cat, bool partial, int32_t gain, int32_t mismatch, int32_t indel, int32_t max_tail, CatIndex &ix)
+{
+    if (ctx->device != cat->device) { ctx->err = "the catalogue was built on device " + std::to_string(cat->device) + ", the context runs on device " + std::to_string(ctx->device); return MTR_ERR_BAD_ARG; }
+    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    const int n = ctx->n_reads; const int32_t n_loci = cat->n_loci;
+    const int64_t rows = (int64_t)n * n_loci;
+    if (rows > (int64_t)INT32_MAX) { ctx->err = std::to_string(n) + " reads x " + std::to_string(n_loci) + " motifs are more than 2^31 - 1 hits"; return MTR_ERR_BAD_ARG; }
+    if (2 * rows > (int64_t)INT32_MAX) { ctx->err = std::to_string(n) + " reads x " + std::to_string(n_loci) + " loci in two orientations are more than 2^31 - 1 pairs"; return MTR_ERR_BAD_ARG; }
+    if (!partial) { mtr_status st = search_motifs_check_size(ctx, cat->mot_off.data(), n_loci); if (st != MTR_OK) return st; }
+    if (gain < 1 || gain > 5) { ctx->err = "gain = " + std::to_string(gain) + " outside 1..5"; return MTR_ERR_BAD_ARG; }
+    if (mismatch < 1 || mismatch > 3) { ctx->err = "mismatch = " + std::to_string(mismatch) + " outside 1..3"; return MTR_ERR_BAD_ARG; }
+    if (indel < 1 || indel > 3) { ctx->err = "indel = " + std::to_string(indel) + " outside 1..3"; return MTR_ERR_BAD_ARG; }
+    if (partial) { mtr_status st = partial_check_args(ctx, cat->mot_off, n_loci, max_tail); if (st != MTR_OK) return st; }
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    { mtr_status st = catalog_scan_buffers(ctx); if (st != MTR_OK) return st; }
+    ix.E = cat->E; ix.distinct = cat->distinct; ix.fwords = cat->fwords; ix.cap = cat->cap; ix.fbits = cat->fbits;
+    ix.narrow = ctx->sw.flank_word != 64 && cat->n_short > 0; ix.wide = ctx->sw.flank_word == 64 || cat->n_long > 0;      // flank_is_wide over the slots' lengths
+    ix.d_filter = cat->d_filter; ix.d_key = cat->d_key; ix.d_run = cat->d_run; ix.d_ent = cat->d_ent; ix.d_plen = cat->d_plen; ix.d_masks = cat->d_masks;
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_genotype_catalog_prepared_device(mtr_ctx *ctx, const mtr_catalog *cat, int32_t gain, int32_t mismatch, int32_t indel, int64_t *out_rows,
+                                                           int64_t *out_candidates)
+{
+    if (!ctx || !out_rows || !out_candidates) return MTR_ERR_BAD_ARG;
+    *out_rows = 0; *out_candidates = 0;
+    if (!cat) { ctx->err = "cat is NULL"; return MTR_ERR_BAD_ARG; }
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    ctx->gc_ready = false;                                                                             // whatever happens below, the rows kept before this call are gone
+    CatIndex ix;
+    { mtr_status st = catalog_prepared_begin(ctx, cat, false, gain, mismatch, indel, 0, ix); if (st != MTR_OK) return st; }
+    const CatMotifs cm = { nullptr, nullptr, cat };
+    return genotype_catalog_run(ctx, ix, cm, cat->n_loci, cat->max_flank_dist, cat->seed_len, gain, mismatch, indel, 0.0, out_rows, out_candidates);
+}
+
+extern "C" mtr_status mtr_genotype_partial_catalog_prepared_device(mtr_ctx *ctx, const mtr_catalog *cat, int32_t gain, int32_t mismatch, int32_t indel, int32_t max_tail,
+                                                                   int64_t *out_rows, int64_t *out_candidates)
+{
+    if (!ctx || !out_rows || !out_candidates) return MTR_ERR_BAD_ARG;
+    *out_rows = 0; *out_candidates = 0;
+    if (!cat) { ctx->err = "cat is NULL"; return MTR_ERR_BAD_ARG; }
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    ctx->pc_ready = false;                                                                             // whatever happens below, the rows kept before this call are gone
+    CatIndex ix;
+    { mtr_status st = catalog_prepared_begin(ctx, cat, true, gain, mismatch, indel, max_tail, ix); if (st != MTR_OK) return st; }
+    const CatMotifs cm = { nullptr, nullptr, cat };
+    return genotype_partial_catalog_run(ctx, ix, cm, cat->n_loci, cat->max_flank_dist, cat->seed_len, gain, mismatch, indel, max_tail, 0.0, out_rows, out_candidates);
+}
+
+extern "C" mtr_status mtr_test_catalog_dump(mtr_ctx *ctx, const mtr_catalog *cat, mtr_catalog_dump *out)
+{
+    if (!ctx || !cat || !out) return MTR_ERR_BAD_ARG;
+    if (ctx->device != cat->device) { ctx->err = "the catalogue was built on device " + std::to_string(cat->device) + ", the context runs on device " + std::to_string(ctx->device); return MTR_ERR_BAD_ARG; }
+    memset(out, 0, sizeof *out);
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t nl = (size_t)cat->n_loci, S = nl * GT_SLOTS, cap = cat->cap, ub = (size_t)cat->unit_off[2 * nl];
+    const struct { const void *d; size_t bytes; } src[11] = {
+        { cat->d_filter, cat->fwords * 4 }, { cat->d_key, cap * 4 }, { cat->d_run, 2 * cap * 4 }, { cat->d_ent, cat->E * 4 }, { cat->d_plen, S * 4 }, { cat->d_masks, S * FL_MASKS * 8 },
+        { cat->d_units, ub }, { cat->d_uoff, (2 * nl + 1) * 4 }, { cat->d_ubits, 2 * nl * 8 }, { cat->d_vbits, 4 * nl * 8 }, { cat->d_ulen, nl * 4 } };
+    std::unique_ptr<void, FreeDeleter> h[11];
+    for (int k = 0; k < 11; k++) {
+        h[k].reset(malloc(std::max<size_t>(src[k].bytes, 1)));
+        if (!h[k]) { ctx->err = "out of host memory"; return MTR_ERR_OOM; }
+        if (src[k].bytes > 0) HIPCHK(copy_sync(ctx, h[k].get(), src[k].d, src[k].bytes, hipMemcpyDeviceToHost));
+    }
+    out->filter_words = (int64_t)cat->fwords; out->table_slots = (int64_t)cap; out->entries = (int64_t)cat->E; out->n_slots = (int64_t)S; out->unit_bytes = (int64_t)ub; out->n_loci = cat->n_loci;
+    out->filter = (uint32_t *)h[0].release(); out->key = (uint32_t *)h[1].release(); out->run = (int32_t *)h[2].release(); out->ent = (int32_t *)h[3].release();
+    out->plen = (int32_t *)h[4].release(); out->masks = (uint64_t *)h[5].release(); out->units = (uint8_t *)h[6].release(); out->unit_off = (int32_t *)h[7].release();
+    out->unit_bits = (uint64_t *)h[8].release(); out->variant_bits = (uint64_t *)h[9].release(); out->ulen = (int32_t *)h[10].release();
     return MTR_OK;
 }
 

@@ -753,6 +753,96 @@ mtr_status mtr_call_alleles_rows_device(mtr_ctx *ctx, const mtr_genotypes_dst *r
                                         int64_t n_rows, int32_t n_loci, const mtr_allele_params *prm, void *wait_stream,
                                         const mtr_allele_calls_dst *dst, int64_t *out_support);
 
+/* ---- allele consensus: each called allele's sequence by vote --------------------------------------------------------------------------------------
+ * A call says "19 and 42 copies"; this says what those alleles are: the consensus of the reads that support an allele, interruptions included.
+ * The reference has nothing of this kind; the definition is this project's own.  Two calls.
+ *
+ * mtr_extract_windows_device: the oriented windows of n_rows >= 0 genotype rows out of the RESIDENT batch, before the next upload replaces it.
+ * row_read [n_rows] (indices into the resident batch: before a joining offset is added), orientation [n_rows] and window [n_rows * 2] are DEVICE
+ * columns as mtr_genotype_catalog_copy_device writes them.  Row r's oriented window is win_bases[win_off[r] .. win_off[r + 1]), codes 0..3: the
+ * read's bases [lo, hi) for orientation 0, their reverse complement for orientation 1 - every window reads in the locus' direction.
+ * *out_bases = T, the windows' bases in all.  Checked in this order, MTR_ERR_BAD_ARG with mtr_last_error naming the offender: NULL ctx or
+ * out_bases; no batch uploaded; n_rows outside 0..2^31 - 1; a NULL input column with n_rows > 0; an input column that is not device memory of the
+ * context's GPU or runs past its allocation; then, on the device and before any kernel is given dst, a row whose read is outside the batch or
+ * whose window is outside its read (the smallest such row).  Then dst == NULL: MTR_OK with T only; cap_rows < n_rows or cap_bases < T:
+ * MTR_ERR_OVERFLOW, nothing written; a NULL win_off, or a NULL win_bases with T > 0: MTR_ERR_BAD_ARG; else the columns are written and the
+ * context's stream synchronised before the call returns.  wait_stream is the stream that wrote the rows, handled as mtr_upload_batch_device
+ * handles it.  Several batches' windows are joined by concatenating win_bases and shifting each batch's win_off by the bases before it.
+ *
+ * mtr_allele_consensus_device: needs no uploaded batch and touches nothing a batch or a run left.  src, all DEVICE memory: the joined rows'
+ * row_read and row_locus [n_rows], ascending by (read, locus) and distinct - checked on the device, MTR_ERR_BAD_ARG names the first row out of
+ * order; their windows win_off [n_rows + 1], win_bases [n_bases]; of the allele calls over the same rows support_off [n_loci + 1], read
+ * [n_support], allele [n_support], zygosity [n_loci].  A support entry (locus l, read q) finds its row by bisection over (read, locus); an entry
+ * without a row is MTR_ERR_BAD_ARG naming the entry, nothing is written.  band_extra in 0..MTR_CONS_MAX_EXTRA.
+ * The definition:
+ *   alleles     allele index A = 2 * locus + a, a in {0, 1}.  Zygosity 0 has no alleles, zygosity 1 allele 0 only, zygosity 2 both.  The members of
+ *               an allele are the locus' support entries with allele == a, in list order (ascending (value, read)): n_A of them.  An allele
+ *               without a member is no allele
+ *   backbone    the member at position (n_A - 1) / 2 of that order - the entry whose value is the call; B is its oriented window, m = |B|
+ *   aligned     every other member, with window W, n = |W|, is aligned to B unless it is skipped: n > MTR_CONS_MAX_WINDOW, m >
+ *               MTR_CONS_MAX_WINDOW, or |m - n| + 2 * band_extra + 1 > MTR_CONS_MAX_BAND.  Skipped members are counted and vote nothing
+ *   banded D    cells (i, j), 0 <= i <= n, 0 <= j <= m, exist iff dlo <= j - i <= dhi, dlo = min(0, m - n) - band_extra, dhi = max(0, m - n) +
+ *               band_extra; other cells are infinite.  D(0, 0) = 0; else D(i, j) is the minimum of diag = D(i-1, j-1) + (W[i-1] != B[j-1]),
+ *               up = D(i-1, j) + 1, left = D(i, j-1) + 1, and the cell's direction is the first of diag, up, left that attains it.  The band is
+ *               part of the definition, not an approximation of something else
+ *   votes       the walk from (n, m) to (0, 0) by the directions: diag at (i, j): base[j][W[i-1]] += 1; left at (i, j): del[j] += 1; a maximal
+ *               run of up steps at column j is an insertion after backbone position j (j = 0: before the first base), whose bases vote in read
+ *               order, ins[j][k][W[i0 + k]] += 1 for k < MTR_CONS_INS_SLOTS; further bases of the run vote nothing.  The backbone votes
+ *               base[j][B[j-1]] += 1 for every j.  N = 1 + the aligned members
+ *   emission    for j = 0 .. m: if j >= 1, c* = the base of most votes in base[j] - among tied bases the backbone's if it is one of them, else
+ *               the lowest code - is emitted with votes = base[j][c*] unless del[j] > base[j][c*]; then the insertion slots k = 0, 1, .. after
+ *               j: with tot = sum over c of ins[j][k][c] and mx its maximum (lowest code on a tie) slot k is emitted with votes = mx iff mx > N -
+ *               tot; the first slot not emitted ends the junction.  Ties go to the backbone's state everywhere
+ * Every output is an exact integer and none depends on the order in which the device worked.
+ * Outputs, one group per allele index, G = 2 * n_loci: cons_off [G + 1] (an allele that is none has an empty span), bases [T] (codes), votes [T],
+ * backbone_read (-1 without an allele), backbone_len, members, aligned, skipped [G] each.  *out_bases = T.  Checked in this order, each
+ * MTR_ERR_BAD_ARG naming the offender: NULL ctx, out_bases or src; n_loci < 1 or above 2^30 - 1, n_rows, n_support or n_bases outside 0..2^31 - 1;
+ * band_extra; a NULL input column that would be read; an input column that is not device memory of the context's GPU or runs past its
+ * allocation; then on the device the rows' order, the offset columns (ascending from 0 to n_bases / n_support, no window above 2^30 bases), a
+ * zygosity above 2, an entry without a row, an allele column that is not 0 .. 0 1 .. 1 within a locus.  Then the votes and the emission lengths are
+ * computed, and as mtr_call_alleles_rows_device: dst == NULL: MTR_OK with T only; cap_alleles < G or cap_bases < T: MTR_ERR_OVERFLOW, nothing
+ * written; a NULL destination column (bases and votes may be NULL only when T == 0): MTR_ERR_BAD_ARG; else the columns are written and the
+ * context's stream synchronised before the call returns.  A failed call writes nothing into dst.  MTR_ABI_VERSION is unchanged by these
+ * entries: look for them by symbol. */
+#define MTR_CONS_MAX_WINDOW 16384
+#define MTR_CONS_MAX_BAND 256
+#define MTR_CONS_INS_SLOTS 4
+#define MTR_CONS_MAX_EXTRA 64
+typedef struct mtr_windows_dst {
+    int64_t *win_off;       /* [n_rows + 1] */
+    uint8_t *win_bases;     /* [T] */
+    int64_t  cap_rows;
+    int64_t  cap_bases;
+} mtr_windows_dst;   /* caller-owned DEVICE memory */
+mtr_status mtr_extract_windows_device(mtr_ctx *ctx, const int32_t *row_read, const uint8_t *orientation, const int32_t *window, int64_t n_rows,
+                                      void *wait_stream, const mtr_windows_dst *dst, int64_t *out_bases);
+typedef struct mtr_consensus_src {
+    const int32_t *row_read;     /* [n_rows] */
+    const int32_t *row_locus;    /* [n_rows] */
+    const int64_t *win_off;      /* [n_rows + 1] */
+    const uint8_t *win_bases;    /* [n_bases] */
+    const int64_t *support_off;  /* [n_loci + 1] */
+    const int32_t *read;         /* [n_support] */
+    const uint8_t *allele;       /* [n_support] */
+    const uint8_t *zygosity;     /* [n_loci] */
+    int64_t n_rows, n_bases, n_support;
+    int32_t n_loci;
+} mtr_consensus_src;   /* DEVICE memory, read only */
+typedef struct mtr_consensus_dst {
+    int64_t *cons_off;       /* [2 * n_loci + 1] */
+    uint8_t *bases;          /* [T] */
+    int32_t *votes;          /* [T] */
+    int32_t *backbone_read;  /* [2 * n_loci] */
+    int32_t *backbone_len;   /* [2 * n_loci] */
+    int32_t *members;        /* [2 * n_loci] */
+    int32_t *aligned;        /* [2 * n_loci] */
+    int32_t *skipped;        /* [2 * n_loci] */
+    int64_t  cap_alleles;
+    int64_t  cap_bases;
+} mtr_consensus_dst;   /* caller-owned DEVICE memory */
+mtr_status mtr_allele_consensus_device(mtr_ctx *ctx, const mtr_consensus_src *src, int32_t band_extra, void *wait_stream,
+                                       const mtr_consensus_dst *dst, int64_t *out_bases);
+
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left
  * of handle_one_file.c:281-287's loop across GPUs is ONE exchange: the record tables travel to the process that chains and

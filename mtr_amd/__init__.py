@@ -56,7 +56,9 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_call_alleles_device", "mtr_genotype_partial_device", "mtr_genotype_catalog_device", "mtr_genotype_catalog_copy_device",
            "mtr_call_alleles_rows_device", "mtr_test_catalog_stats", "mtr_genotype_partial_catalog_device", "mtr_genotype_partial_catalog_copy_device",
            "mtr_test_partial_catalog_stats", "mtr_catalog_create", "mtr_catalog_destroy", "mtr_catalog_info_get", "mtr_genotype_catalog_prepared_device",
-           "mtr_genotype_partial_catalog_prepared_device", "mtr_test_catalog_dump", "mtr_test_catalog_build_stats"]
+           "mtr_genotype_partial_catalog_prepared_device", "mtr_test_catalog_dump", "mtr_test_catalog_build_stats",
+           "mtr_extract_windows_device", "mtr_allele_consensus_device"]
+CONS_MAX_WINDOW, CONS_MAX_BAND, CONS_INS_SLOTS, CONS_MAX_EXTRA = 16384, 256, 4, 64      # MTR_CONS_*: the limits of Engine.allele_consensus
 ALLELE_COPIES, ALLELE_BASES = 0, 1           # MTR_ALLELE_COPIES, MTR_ALLELE_BASES: the measure of Engine.call_alleles
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
 
@@ -243,6 +245,22 @@ class Genotypes(NamedTuple):
     score: "object"       # int32 [n, m]
     ratio: "object"       # float32 [n, m]: matches / repeat_len
 
+    def to_sparse(self) -> "SparseGenotypes":
+        """the spanning rows as Engine.genotype_catalog returns them, sorted by (read, locus): dense results enter the paths that take a
+        SparseGenotypes (genotype_windows, join_sparse_genotypes, allele_consensus).  Plain torch (or numpy) over spanning.nonzero()."""
+        n, m = int(self.spanning.shape[0]), int(self.spanning.shape[1])
+        if hasattr(self.spanning, "detach"):
+            import torch
+
+            at = self.spanning.reshape(-1).nonzero().reshape(-1)                 # ascending: row = read * m + locus
+            read, locus = torch.div(at, m, rounding_mode="floor").to(torch.int32), (at % m).to(torch.int32)
+            cols = [c.reshape((n * m,) + tuple(c.shape[2:]))[at].contiguous() for c in self]
+        else:
+            at = np.flatnonzero(np.asarray(self.spanning).reshape(-1))
+            read, locus = (at // m).astype(np.int32), (at % m).astype(np.int32)
+            cols = [np.ascontiguousarray(np.asarray(c).reshape((n * m,) + tuple(np.asarray(c).shape[2:]))[at]) for c in self]
+        return SparseGenotypes(n, m, read, locus, *cols, int(len(at)))
+
 
 class CCatalogDst(C.Structure):
     """mtr_catalog_dst: device pointers of the catalogue genotype's read and locus columns, and the genotype's columns"""
@@ -425,6 +443,43 @@ class AlleleCalls(NamedTuple):
     cost: "object"          # int64 [m, 2]: the sum of absolute deviations from the median(s) as one allele, and as called
 
 
+class CWindowsDst(C.Structure):
+    """mtr_windows_dst: device pointers of the windows' two columns and their capacities"""
+    _fields_ = [("win_off", C.c_void_p), ("win_bases", C.c_void_p), ("cap_rows", C.c_int64), ("cap_bases", C.c_int64)]
+
+
+class GenotypeWindows(NamedTuple):
+    """What Engine.genotype_windows cut out of the resident batch: row r's oriented window is bases[off[r]:off[r + 1]], codes 0..3, the read's
+    window for orientation 0 and its reverse complement for orientation 1 - every window reads in the locus' direction."""
+    off: "object"     # int64 [R + 1]
+    bases: "object"   # uint8 [T]
+
+
+class CConsensusSrc(C.Structure):
+    """mtr_consensus_src: device pointers of the rows, their windows and the calls, and their sizes"""
+    _fields_ = [("row_read", C.c_void_p), ("row_locus", C.c_void_p), ("win_off", C.c_void_p), ("win_bases", C.c_void_p), ("support_off", C.c_void_p), ("read", C.c_void_p),
+                ("allele", C.c_void_p), ("zygosity", C.c_void_p), ("n_rows", C.c_int64), ("n_bases", C.c_int64), ("n_support", C.c_int64), ("n_loci", C.c_int32)]
+
+
+class CConsensusDst(C.Structure):
+    """mtr_consensus_dst: device pointers of the consensus' columns and their capacities"""
+    _fields_ = [("cons_off", C.c_void_p), ("bases", C.c_void_p), ("votes", C.c_void_p), ("backbone_read", C.c_void_p), ("backbone_len", C.c_void_p), ("members", C.c_void_p),
+                ("aligned", C.c_void_p), ("skipped", C.c_void_p), ("cap_alleles", C.c_int64), ("cap_bases", C.c_int64)]
+
+
+class AlleleConsensus(NamedTuple):
+    """What Engine.allele_consensus voted: one group per allele index 2 * locus + a of m loci, all on the engine's device.  include/mtr_hip.h
+    defines every column.  Allele A's sequence is bases[off[A]:off[A + 1]]; an allele that was not called has an empty span."""
+    off: "object"            # int64 [2m + 1]
+    bases: "object"          # uint8 [T]: codes 0..3
+    votes: "object"          # int32 [T]: the votes each emitted base had
+    backbone_read: "object"  # int32 [2m]: the read whose window the members were aligned to, -1 without an allele
+    backbone_len: "object"   # int32 [2m]
+    members: "object"        # int32 [2m]: the allele's supporting reads, the backbone among them
+    aligned: "object"        # int32 [2m]: the members aligned to the backbone
+    skipped: "object"        # int32 [2m]: the members left out (a window or a band beyond the limits)
+
+
 class CFastaInfo(C.Structure):
     """mtr_fasta_info: what a FASTA file in device memory holds"""
     _fields_ = [("n_reads", C.c_int32), ("end", C.c_int32), ("bad_char", C.c_int32), ("reserved", C.c_int32),
@@ -586,6 +641,11 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_call_alleles_rows_device.argtypes = [C.c_void_p, P(CGenotypesDst), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(CAlleleParams), C.c_void_p, P(CAlleleCallsDst),
                                                  P(C.c_int64)]
     lib.mtr_call_alleles_rows_device.restype = C.c_int
+    if hasattr(lib, "mtr_allele_consensus_device"):      # (a build from before the consensus, A/B'd through MTR_LIB, has neither: using one raises there)
+        lib.mtr_extract_windows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(CWindowsDst), P(C.c_int64)]
+        lib.mtr_extract_windows_device.restype = C.c_int
+        lib.mtr_allele_consensus_device.argtypes = [C.c_void_p, P(CConsensusSrc), C.c_int32, C.c_void_p, P(CConsensusDst), P(C.c_int64)]
+        lib.mtr_allele_consensus_device.restype = C.c_int
     lib.mtr_test_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
     lib.mtr_test_catalog_stats.restype = C.c_int
     lib.mtr_test_partial_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
@@ -1376,6 +1436,75 @@ class Engine:
         self._check(call(*args, C.byref(dst), C.byref(ns)), name)
         return calls
 
+    def _gpu_column(self, t, dtype, shape, what: str):
+        import torch
+
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise MtrError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)}")
+        if not t.is_cuda or t.device.index != self.device:
+            raise MtrError(f"{what} is on {t.device}, the engine on cuda:{self.device}")
+        return t.data_ptr() if t.numel() else None
+
+    def genotype_windows(self, sg) -> GenotypeWindows:
+        """The oriented windows of a SparseGenotypes' rows out of the RESIDENT batch (mtr_extract_windows_device): call it on the batch's own
+        result - genotype_catalog's or genotype_prepared's, or genotype_loci(...).to_sparse() - before the next upload and before
+        join_sparse_genotypes adds an offset to `read`.  Row r's window is bases[off[r]:off[r + 1]], reverse-complemented where orientation is 1.
+        Returns fresh tensors on this engine's device; stream handling as call_alleles'."""
+        import torch
+
+        R = int(sg.read.numel()) if isinstance(sg.read, torch.Tensor) and sg.read.dim() == 1 else -1
+        if R < 0:
+            raise MtrError("the rows' read column must be a 1-D torch tensor")
+        ptrs = [self._gpu_column(sg.read, torch.int32, (R,), "the rows' read"), self._gpu_column(sg.orientation, torch.uint8, (R,), "the rows' orientation"),
+                self._gpu_column(sg.window, torch.int32, (R, 2), "the rows' window")]
+        dev = torch.device("cuda", self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        nb = C.c_int64()
+        self._check(self.lib.mtr_extract_windows_device(self.h, *ptrs, R, stream, None, C.byref(nb)), "mtr_extract_windows_device")
+        T = int(nb.value)
+        win = GenotypeWindows(torch.empty(R + 1, dtype=torch.int64, device=dev), torch.empty(T, dtype=torch.uint8, device=dev))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CWindowsDst(win.off.data_ptr(), win.bases.data_ptr() if T else None, R, T)
+        self._check(self.lib.mtr_extract_windows_device(self.h, *ptrs, R, stream, C.byref(dst), C.byref(nb)), "mtr_extract_windows_device")
+        return win
+
+    def allele_consensus(self, sg, windows: GenotypeWindows, calls: AlleleCalls, band_extra: int = 16) -> AlleleConsensus:
+        """Allele consensus (mtr_allele_consensus_device): each called allele's sequence by vote.  sg: the SparseGenotypes the calls were made of
+        (one batch's, or join_sparse_genotypes'), sorted by (read, locus); windows: its rows' windows (genotype_windows, or join_windows'); calls:
+        call_alleles(sg, ...).  Per allele the member in the middle of its (value, read) order is the backbone; every other member is aligned to
+        it by a banded edit distance (the band is |length difference| + 2 * band_extra + 1 diagonals wide; a member whose band exceeds 256 or
+        whose window, or the backbone's, exceeds 16384 bases is counted as skipped) and votes per backbone position for a base, a deletion or up
+        to four inserted bases; the consensus is the plurality, ties to the backbone.  Needs no upload and no run and changes nothing either
+        left.  Returns an AlleleConsensus of fresh tensors on this engine's device; stream handling as call_alleles'."""
+        import torch
+
+        if isinstance(band_extra, bool) or not isinstance(band_extra, (int, np.integer)):
+            raise MtrError(f"band_extra must be an integer, got {band_extra!r}")
+        if isinstance(sg.n_loci, bool) or not isinstance(sg.n_loci, (int, np.integer)) or sg.n_loci < 1:
+            raise MtrError(f"n_loci must be an integer >= 1, got {sg.n_loci!r}")
+        if not isinstance(sg.read, torch.Tensor) or sg.read.dim() != 1 or not isinstance(calls.read, torch.Tensor) or calls.read.dim() != 1:
+            raise MtrError("the rows' and the calls' read columns must be 1-D torch tensors")
+        if not isinstance(windows.bases, torch.Tensor) or windows.bases.dim() != 1:
+            raise MtrError("the windows' bases must be a 1-D torch tensor")
+        R, S, T, m = int(sg.read.numel()), int(calls.read.numel()), int(windows.bases.numel()), int(sg.n_loci)
+        col = self._gpu_column
+        src = CConsensusSrc(col(sg.read, torch.int32, (R,), "the rows' read"), col(sg.locus, torch.int32, (R,), "the rows' locus"),
+                            col(windows.off, torch.int64, (R + 1,), "the windows' off"), col(windows.bases, torch.uint8, (T,), "the windows' bases"),
+                            col(calls.support_off, torch.int64, (m + 1,), "the calls' support_off"), col(calls.read, torch.int32, (S,), "the calls' read"),
+                            col(calls.allele, torch.uint8, (S,), "the calls' allele"), col(calls.zygosity, torch.uint8, (m,), "the calls' zygosity"), R, T, S, m)
+        dev = torch.device("cuda", self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        nb = C.c_int64()
+        call = self.lib.mtr_allele_consensus_device
+        self._check(call(self.h, C.byref(src), int(band_extra), stream, None, C.byref(nb)), "mtr_allele_consensus_device")
+        L = int(nb.value)
+        new = lambda dtype, n: torch.empty(n, dtype=dtype, device=dev)     # noqa: E731
+        cons = AlleleConsensus(new(torch.int64, 2 * m + 1), new(torch.uint8, L), new(torch.int32, L), *[new(torch.int32, 2 * m) for _ in range(5)])
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CConsensusDst(*[t.data_ptr() if t.numel() else None for t in cons], 2 * m, L)
+        self._check(call(self.h, C.byref(src), int(band_extra), stream, C.byref(dst), C.byref(nb)), "mtr_allele_consensus_device")
+        return cons
+
     def test_catalog_stats(self):
         """mtr_test_catalog_stats: what the last genotype_catalog call saw - (positions, passed by the filter, seed hits, candidates) and the
         host-clock ms of (index build and upload, first scan pass, the rest)"""
@@ -2042,6 +2171,70 @@ def format_allele_calls(loci, calls: AlleleCalls) -> bytes:
         ends = (int(value[lo]), int(value[hi - 1])) if hi > lo else (0, 0)
         cols = [k, hi - lo, int(zyg[k]), int(call[k, 0]), int(call[k, 1]), int(sup[k, 0]), int(sup[k, 1]), int(cost[k, 0]), int(cost[k, 1]), *ends]
         out.append("\t".join(str(c) for c in cols).encode() + b"\t" + bmot[k] + b"\n")
+    return b"".join(out)
+
+
+def _cat(parts):
+    if hasattr(parts[0], "detach"):
+        import torch
+
+        return torch.cat(list(parts))
+    return np.concatenate([np.asarray(p) for p in parts])
+
+
+def join_sparse_genotypes(parts) -> SparseGenotypes:
+    """Several batches' SparseGenotypes (in file order, the same loci) as one: n_reads summed, each batch's first read's index added to its `read`,
+    every column concatenated, candidates summed.  The joined rows stay sorted by (read, locus).  Tensors or numpy columns."""
+    parts = list(parts)
+    if not parts:
+        raise MtrError("nothing to join")
+    m = parts[0].n_loci
+    if any(p.n_loci != m for p in parts):
+        raise MtrError(f"the batches' n_loci differ: {[p.n_loci for p in parts]}")
+    first, reads = 0, []
+    for p in parts:
+        reads.append(p.read + first)
+        first += int(p.n_reads)
+    if first > 2 ** 31 - 1:
+        raise MtrError(f"{first} reads are more than 2^31 - 1")
+    return SparseGenotypes(first, m, _cat(reads), *[_cat([p[k] for p in parts]) for k in range(3, 11)], sum(int(p.candidates) for p in parts))
+
+
+def join_windows(parts) -> GenotypeWindows:
+    """Several batches' GenotypeWindows, in the order of join_sparse_genotypes' parts, as one: the bases concatenated, each batch's offsets shifted
+    by the bases before it.  Tensors or numpy columns."""
+    parts = list(parts)
+    if not parts:
+        raise MtrError("nothing to join")
+    before, offs = 0, []
+    for k, p in enumerate(parts):
+        offs.append((p.off if k == len(parts) - 1 else p.off[:-1]) + before)
+        before += int(p.off[-1])
+    return GenotypeWindows(_cat(offs), _cat([p.bases for p in parts]))
+
+
+def format_allele_consensus(loci, cons: AlleleConsensus) -> bytes:
+    """The consensus of Engine.allele_consensus as text, one tab-separated line per CALLED allele in allele order: locus index, allele (0 or 1),
+    members, aligned, skipped, the sequence's length, the sequence as letters ("." when it is empty), and the locus' motif as given.
+    loci: what the genotype call was given, (left_flank, motif, right_flank) each; cons: allele_consensus' result (tensors or numpy)."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    bmot = [v[1].encode() if isinstance(v[1], str) else bytes(v[1]) for v in loci]
+    m = len(bmot)
+    off, bases, bb = host(cons.off).reshape(-1), host(cons.bases).reshape(-1), host(cons.backbone_read).reshape(-1)
+    if len(off) != 2 * m + 1 or len(bb) != 2 * m:
+        raise MtrError(f"{len(bb)} alleles for {m} loci")
+    members, aligned, skipped = host(cons.members).reshape(-1), host(cons.aligned).reshape(-1), host(cons.skipped).reshape(-1)
+    letters = np.frombuffer(b"ACGT", np.uint8)
+    out = []
+    for A in range(2 * m):
+        if bb[A] < 0:
+            continue
+        lo, hi = int(off[A]), int(off[A + 1])
+        seq = letters[bases[lo:hi]].tobytes() if hi > lo else b"."
+        cols = [A // 2, A % 2, int(members[A]), int(aligned[A]), int(skipped[A]), hi - lo]
+        out.append("\t".join(str(c) for c in cols).encode() + b"\t" + seq + b"\t" + bmot[A // 2] + b"\n")
     return b"".join(out)
 
 

@@ -49,6 +49,7 @@
 #include "partial_catalog.hip.inc"
 #include "catalog_build.hip.inc"
 #include "allele_call.hip.inc"
+#include "consensus.hip.inc"
 #include "fasta.hip.inc"
 #include "fastq.hip.inc"
 #include "file_order.hip.inc"
@@ -268,6 +269,9 @@ struct mtr_ctx {
     // allele calls (mtr_call_alleles_device), per call and nothing kept, buffers of its own so that what the genotype and the locus search keep stays:
     // d_ac_i32 = count | cursor (spread while the loci are few), d_ac_i64 = support_off | tile_off | state, the keys, the split's prefix sums
     DevBuf<int32_t> d_ac_i32; DevBuf<int64_t> d_ac_i64, d_ac_prefix; DevBuf<unsigned long long> d_ac_keys;
+    // the windows and the allele consensus (consensus.hip.inc): d_co_i32 = the per-entry and per-allele int32 columns, d_co_i64 = tab_off | cons_off (or the
+    // windows' offsets), d_co_state = the bad-input words and the task counters, the tasks, the vote tables, the alignment's direction scratch
+    DevBuf<int32_t> d_co_i32, d_co_tab; DevBuf<int64_t> d_co_i64; DevBuf<unsigned long long> d_co_state; DevBuf<int4> d_co_tasks; DevBuf<uint32_t> d_co_dirs;
     long long wrap_dp_size = MTRC_WRAP_DP_SIZE;          // the WrapDPsize the kernels of this context's device test (MTR_TEST_WRAP_DP_SIZE)
     // a FASTA file in device memory (fasta.hip.inc), per call: the tiles' columns, the header windows' columns, the IDs' offsets, the stop, the sizes
     DevBuf<uint32_t> d_fa_tiles, d_fa_hbase; DevBuf<int32_t> d_fa_hpos, d_fa_hidlen; DevBuf<int64_t> d_fa_idoff;
@@ -3626,6 +3630,178 @@ extern "C" mtr_status mtr_call_alleles_rows_device(mtr_ctx *ctx, const mtr_genot
     if (n_loci < 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
     if (n_rows > 0 && (!row_read || !row_locus)) { ctx->err = "row_read or row_locus is NULL"; return MTR_ERR_BAD_ARG; }
     return call_alleles_rows(ctx, rows, n_rows, n_loci, row_read, row_locus, prm, wait_stream, dst, out_support);
+}
+
+// ---- windows and allele consensus (consensus.hip.inc) ------------------------------------------------------------------------------------
+// the caller's stream before the context's, and the bad-input words set to "none"
+static mtr_status cons_begin(mtr_ctx *ctx, void *wait_stream)
+{
+    HIPCHK(ctx->d_co_state.ensure((CO_BAD + CO_STATE) * 8));
+    if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ctx->ev_text, (hipStream_t)wait_stream));
+    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
+    HIPCHK(hipMemsetAsync(ctx->d_co_state, 0xff, CO_BAD * 8, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_co_state + CO_BAD, 0, CO_STATE * 8, ctx->stream));
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_extract_windows_device(mtr_ctx *ctx, const int32_t *row_read, const uint8_t *orientation, const int32_t *window, int64_t n_rows,
+                                                 void *wait_stream, const mtr_windows_dst *dst, int64_t *out_bases)
+{
+    if (!ctx || !out_bases) return MTR_ERR_BAD_ARG;
+    *out_bases = 0;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    const int64_t R = n_rows;
+    if (R < 0 || R > (int64_t)INT32_MAX) { ctx->err = "n_rows = " + std::to_string(R) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (R > 0 && (!row_read || !orientation || !window)) { ctx->err = "row_read, orientation or window is NULL"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    if (R > 0) {
+        { mtr_status st = check_device_ptr(ctx, (const uint8_t *)row_read, R * 4, "row_read", "the rows' bytes"); if (st != MTR_OK) return st; }
+        { mtr_status st = check_device_ptr(ctx, orientation, R, "orientation", "the rows' bytes"); if (st != MTR_OK) return st; }
+        { mtr_status st = check_device_ptr(ctx, (const uint8_t *)window, R * 8, "window", "the rows' bytes"); if (st != MTR_OK) return st; }
+    }
+    const size_t nr = (size_t)R;
+    HIPCHK(ctx->d_co_i32.ensure(std::max<size_t>(nr, 1) * 4)); HIPCHK(ctx->d_co_i64.ensure((nr + 1) * 8));
+    { mtr_status st = cons_begin(ctx, wait_stream); if (st != MTR_OK) return st; }
+    unsigned long long *bad = ctx->d_co_state;
+    int32_t *len = ctx->d_co_i32; int64_t *off = ctx->d_co_i64;
+    if (R > 0) hipLaunchKernelGGL(mtr_k_win_len, dim3((unsigned)((R + CO_BLOCK - 1) / CO_BLOCK)), dim3(CO_BLOCK), 0, ctx->stream, row_read, window, R,
+                                  (const int32_t *)ctx->d_lens, (int32_t)ctx->n_reads, len, bad);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)len, R, off);
+    HIPCHK(hipGetLastError());
+    unsigned long long found = 0; int64_t T = 0;
+    HIPCHK(hipMemcpyAsync(&T, off + R, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(copy_sync(ctx, &found, bad + 5, 8, hipMemcpyDeviceToHost));
+    if (found != ~0ull) {
+        int32_t v[3] = { 0, 0, 0 };
+        HIPCHK(copy_sync(ctx, &v[0], row_read + found, 4, hipMemcpyDeviceToHost)); HIPCHK(copy_sync(ctx, &v[1], window + 2 * found, 8, hipMemcpyDeviceToHost));
+        ctx->err = "row " + std::to_string(found) + ": read " + std::to_string(v[0]) + " is outside the batch of " + std::to_string(ctx->n_reads) + " reads, or its window " +
+                   std::to_string(v[1]) + ".." + std::to_string(v[2]) + " outside the read";
+        return MTR_ERR_BAD_ARG;
+    }
+    if (T < 0) { ctx->err = "the windows' scan failed on the device"; return MTR_ERR_HIP; }
+    *out_bases = T;
+    if (!dst) return MTR_OK;
+    if (dst->cap_rows < R) { ctx->err = "destination holds " + std::to_string(dst->cap_rows) + " rows, " + std::to_string(R) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (dst->cap_bases < T) { ctx->err = "destination holds " + std::to_string(dst->cap_bases) + " bases, " + std::to_string(T) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (!dst->win_off || (T > 0 && !dst->win_bases)) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
+    if (T > 0) {
+        hipLaunchKernelGGL(mtr_k_win_gather, dim3((unsigned)std::min<int64_t>(R, CO_MAX_GRID)), dim3(64), 0, ctx->stream, row_read, orientation, window, R,
+                           (const uint32_t *)ctx->d_packed, (const int64_t *)ctx->d_woff, (const int64_t *)off, dst->win_bases);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(dst->win_off, off, (nr + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// one bucket's alignments: the grid is bounded by the scratch it may take (each wavefront its own directions, sized by the bucket's longest task)
+template <int CPL>
+static mtr_status cons_align_bucket(mtr_ctx *ctx, const ConsArgs &a, int bucket, unsigned n_tasks, unsigned longest)
+{
+    if (n_tasks == 0) return MTR_OK;
+    const int64_t words = ((int64_t)(longest >> 4) + 1) * CPL * 64;
+    const int64_t cap_words = (int64_t)(std::min(ctx->sw.scratch_max_gb, 0.25) * (double)(1ll << 30) / 4.0);      // a quarter of a GB at the most, under the context's scratch cap
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_tasks, (int64_t)ctx->n_cu * 16), cap_words / words));
+    HIPCHK(ctx->d_co_dirs.ensure((size_t)(grid * words) * 4));
+    hipLaunchKernelGGL(mtr_k_cons_align<CPL>, dim3((unsigned)grid), dim3(64), 0, ctx->stream, a, bucket, n_tasks, (uint32_t *)ctx->d_co_dirs, words);
+    HIPCHK(hipGetLastError());
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_allele_consensus_device(mtr_ctx *ctx, const mtr_consensus_src *src, int32_t band_extra, void *wait_stream,
+                                                  const mtr_consensus_dst *dst, int64_t *out_bases)
+{
+    if (!ctx || !out_bases) return MTR_ERR_BAD_ARG;
+    *out_bases = 0;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    if (!src) { ctx->err = "src is NULL"; return MTR_ERR_BAD_ARG; }
+    const int64_t R = src->n_rows, S = src->n_support, NB = src->n_bases; const int32_t n_loci = src->n_loci;
+    if (n_loci < 1 || n_loci > (1 << 30) - 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + " outside 1..2^30 - 1"; return MTR_ERR_BAD_ARG; }
+    if (R < 0 || R > (int64_t)INT32_MAX) { ctx->err = "n_rows = " + std::to_string(R) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (S < 0 || S > (int64_t)INT32_MAX) { ctx->err = "n_support = " + std::to_string(S) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (NB < 0 || NB > (int64_t)INT32_MAX) { ctx->err = "n_bases = " + std::to_string(NB) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (band_extra < 0 || band_extra > MTR_CONS_MAX_EXTRA) { ctx->err = "band_extra = " + std::to_string(band_extra) + " outside 0.." + std::to_string(MTR_CONS_MAX_EXTRA); return MTR_ERR_BAD_ARG; }
+    if (!src->win_off || !src->support_off || !src->zygosity || (R > 0 && (!src->row_read || !src->row_locus)) || (NB > 0 && !src->win_bases) ||
+        (S > 0 && (!src->read || !src->allele))) { ctx->err = "an input column is NULL"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    {
+        const struct { const void *p; int64_t bytes; const char *what; } cols[8] = {
+            { src->row_read, R * 4, "src->row_read" }, { src->row_locus, R * 4, "src->row_locus" }, { src->win_off, (R + 1) * 8, "src->win_off" }, { src->win_bases, NB, "src->win_bases" },
+            { src->support_off, ((int64_t)n_loci + 1) * 8, "src->support_off" }, { src->read, S * 4, "src->read" }, { src->allele, S, "src->allele" }, { src->zygosity, n_loci, "src->zygosity" } };
+        for (const auto &c : cols)
+            if (c.bytes > 0) { mtr_status st = check_device_ptr(ctx, (const uint8_t *)c.p, c.bytes, c.what, "the column's bytes"); if (st != MTR_OK) return st; }
+    }
+    read_switches(ctx->sw);
+    const size_t G = 2 * (size_t)n_loci, ns = (size_t)S;
+    HIPCHK(ctx->d_co_i32.ensure((ns + 9 * G) * 4)); HIPCHK(ctx->d_co_i64.ensure(2 * (G + 1) * 8)); HIPCHK(ctx->d_co_tasks.ensure(std::max<size_t>(2 * ns, 1) * sizeof(int4)));
+    { mtr_status st = cons_begin(ctx, wait_stream); if (st != MTR_OK) return st; }
+    ConsArgs a{};
+    a.row_read = src->row_read; a.row_locus = src->row_locus; a.R = R; a.win_off = src->win_off; a.win_bases = src->win_bases; a.n_bases = NB;
+    a.support_off = src->support_off; a.sup_read = src->read; a.sup_allele = src->allele; a.zygosity = src->zygosity; a.S = S; a.n_loci = n_loci; a.band_extra = band_extra;
+    int32_t *i32 = ctx->d_co_i32;
+    a.ent_row = i32; a.bb_ent = i32 + ns; a.bb_row = a.bb_ent + G; a.bb_read = a.bb_row + G; a.bb_len = a.bb_read + G; a.members = a.bb_len + G; a.aligned = a.members + G;
+    a.skipped = a.aligned + G; a.tab_len = a.skipped + G; a.cons_len = a.tab_len + G;
+    a.tab_off = ctx->d_co_i64; a.cons_off = a.tab_off + G + 1; a.tasks = ctx->d_co_tasks;
+    a.bad = ctx->d_co_state; a.state = (unsigned *)(a.bad + CO_BAD);
+    const auto blocks = [](int64_t n) { return dim3((unsigned)((std::max<int64_t>(n, 1) + CO_BLOCK - 1) / CO_BLOCK)); };
+    const dim3 blk(CO_BLOCK);
+    unsigned long long bad[CO_BAD];
+    hipLaunchKernelGGL(mtr_k_cons_check, blocks(std::max<int64_t>(R, n_loci)), blk, 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(ctx, bad, a.bad, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad[0] != ~0ull) { ctx->err = "row " + std::to_string(bad[0]) + " is out of order: the rows must ascend by (read, locus), each pair once, none negative"; return MTR_ERR_BAD_ARG; }
+    if (bad[1] != ~0ull) { ctx->err = "win_off at row " + std::to_string(bad[1]) + " does not ascend from 0 to n_bases, or the window is above 2^30 bases"; return MTR_ERR_BAD_ARG; }
+    if (bad[2] != ~0ull) { ctx->err = "locus " + std::to_string(bad[2]) + ": support_off does not ascend from 0 to n_support, or the zygosity is above 2"; return MTR_ERR_BAD_ARG; }
+    if (S > 0) {
+        hipLaunchKernelGGL(mtr_k_cons_members, blocks(S), blk, 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        HIPCHK(copy_sync(ctx, bad, a.bad, sizeof bad, hipMemcpyDeviceToHost));
+        if (bad[3] != ~0ull) {
+            int32_t rd = 0;
+            HIPCHK(copy_sync(ctx, &rd, src->read + bad[3], 4, hipMemcpyDeviceToHost));
+            ctx->err = "support entry " + std::to_string(bad[3]) + " (read " + std::to_string(rd) + ") has no row of its (read, locus)";
+            return MTR_ERR_BAD_ARG;
+        }
+        if (bad[4] != ~0ull) { ctx->err = "support entry " + std::to_string(bad[4]) + ": the allele column is not 0 .. 0 1 .. 1 within its locus"; return MTR_ERR_BAD_ARG; }
+    }
+    HIPCHK(hipMemsetAsync(a.aligned, 0, 2 * G * 4, ctx->stream));                                      // aligned | skipped
+    hipLaunchKernelGGL(mtr_k_cons_alleles, blocks((int64_t)G), blk, 0, ctx->stream, a);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.tab_len, (int64_t)G, a.tab_off);
+    if (S > 0) hipLaunchKernelGGL(mtr_k_cons_tasks, blocks(S), blk, 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    unsigned state[CO_STATE]; int64_t tab_positions = 0;
+    HIPCHK(hipMemcpyAsync(&tab_positions, a.tab_off + G, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(copy_sync(ctx, state, a.state, sizeof state, hipMemcpyDeviceToHost));
+    if (tab_positions < 0 || (int64_t)state[0] + state[1] > S || state[2] > 2 * BA_MAX_WINDOW || state[3] > 2 * BA_MAX_WINDOW) { ctx->err = "the consensus' task lists failed on the device"; return MTR_ERR_HIP; }
+    HIPCHK(ctx->d_co_tab.ensure(std::max<size_t>((size_t)tab_positions * BA_TAB, 1) * 4));
+    a.tab = ctx->d_co_tab;
+    if (tab_positions > 0) HIPCHK(hipMemsetAsync(a.tab, 0, (size_t)tab_positions * BA_TAB * 4, ctx->stream));
+    { mtr_status st = cons_align_bucket<1>(ctx, a, 0, state[0], state[2]); if (st != MTR_OK) return st; }
+    { mtr_status st = cons_align_bucket<2>(ctx, a, 1, state[1], state[3]); if (st != MTR_OK) return st; }
+    const dim3 per_allele((unsigned)std::min<int64_t>((int64_t)G, CO_MAX_GRID));
+    hipLaunchKernelGGL(mtr_k_cons_emit<0>, per_allele, blk, 0, ctx->stream, a);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.cons_len, (int64_t)G, a.cons_off);
+    HIPCHK(hipGetLastError());
+    int64_t T = 0;
+    HIPCHK(copy_sync(ctx, &T, a.cons_off + G, 8, hipMemcpyDeviceToHost));
+    if (T < 0) { ctx->err = "the consensus' emission lengths failed on the device"; return MTR_ERR_HIP; }
+    *out_bases = T;
+    if (!dst) return MTR_OK;
+    if (dst->cap_alleles < (int64_t)G) { ctx->err = "destination holds " + std::to_string(dst->cap_alleles) + " alleles, " + std::to_string(G) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (dst->cap_bases < T) { ctx->err = "destination holds " + std::to_string(dst->cap_bases) + " bases, " + std::to_string(T) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (!dst->cons_off || !dst->backbone_read || !dst->backbone_len || !dst->members || !dst->aligned || !dst->skipped || (T > 0 && (!dst->bases || !dst->votes))) {
+        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
+    }
+    a.bases = dst->bases; a.votes = dst->votes;
+    if (T > 0) { hipLaunchKernelGGL(mtr_k_cons_emit<1>, per_allele, blk, 0, ctx->stream, a); HIPCHK(hipGetLastError()); }
+    HIPCHK(hipMemcpyAsync(dst->cons_off, a.cons_off, (G + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    const struct { int32_t *to; const int32_t *from; } cols[5] = { { dst->backbone_read, a.bb_read }, { dst->backbone_len, a.bb_len }, { dst->members, a.members }, { dst->aligned, a.aligned },
+                                                                   { dst->skipped, a.skipped } };
+    for (const auto &c : cols) HIPCHK(hipMemcpyAsync(c.to, c.from, G * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
 }
 
 // ---- a FASTA file in device memory (fasta.hip.inc) -----------------------------------------------------------------------------

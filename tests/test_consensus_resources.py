@@ -1,0 +1,42 @@
+"""The windows' and the allele consensus' kernels (mtr_amd/csrc/consensus.hip.inc) against the resources their launches assume (CPU; reads the
+gfx950 code object out of mtr_amd/libmtr_hip.so as tests/test_kernel_resources.py does).  No kernel spills and none takes private scratch memory
+- the alignment's directions go to a buffer the host sizes, not to the private segment; LDS appears only in the emission, at exactly the declared
+size (one int32 per wavefront of its workgroup of 256 lanes); the alignment, one wavefront per workgroup and up to 16 workgroups per CU, stays
+within 128 VGPRs (four wavefronts per SIMD), as every other kernel of the file does; and the file's kernels are exactly the ones listed."""
+import os
+import re
+
+import pytest
+
+from tests.test_kernel_resources import LIB, READELF, _find, _kernels
+
+LDS = {"mtr_k_win_len": 0, "mtr_k_win_gather": 0, "mtr_k_cons_check": 0, "mtr_k_cons_members": 0, "mtr_k_cons_alleles": 0, "mtr_k_cons_tasks": 0, "mtr_k_cons_align": 0,
+       "mtr_k_cons_emit": (256 // 64) * 4}
+INSTANCES = {"mtr_k_cons_align": 2, "mtr_k_cons_emit": 2}
+
+
+@pytest.fixture(scope="module")
+def kernels(tmp_path_factory):
+    if READELF is None:
+        pytest.skip("llvm-readelf not found")
+    if not os.path.exists(LIB):
+        import mtr_amd.build
+        mtr_amd.build.build()
+    return _kernels(tmp_path_factory.mktemp("co"))
+
+
+@pytest.mark.parametrize("stem", sorted(LDS))
+def test_no_scratch_no_spills_the_declared_lds_and_four_wavefronts_per_simd(kernels, stem):
+    found = _find(kernels, stem)
+    assert len(found) == INSTANCES.get(stem, 1), (stem, found)
+    for k in found:
+        print(f"{k['name']}: {k['vgpr_count']} VGPRs, {k.get('sgpr_count')} SGPRs, {k['group_segment_fixed_size']} bytes of LDS, {k['private_segment_fixed_size']} of scratch")
+        assert k["private_segment_fixed_size"] == 0, k
+        assert k.get("vgpr_spill_count", 0) == 0 and k.get("sgpr_spill_count", 0) == 0, k
+        assert k["group_segment_fixed_size"] == LDS[stem], k
+        assert k["vgpr_count"] <= 128, k
+
+
+def test_the_kernels_are_the_ones_listed():
+    src = open(os.path.join(os.path.dirname(LIB), "csrc", "consensus.hip.inc")).read()
+    assert sorted(set(re.findall(r"__global__[^\n]*\bvoid (mtr_k_\w+)\(", src))) == sorted(LDS)

@@ -35,12 +35,14 @@ mtr_status mtr_test_wrap_dp(mtr_ctx *ctx, int32_t n_tasks, const int32_t *read_i
  *   MTR_TEST_PASS_QUAD2P  1-4 tasks of one DPQ_COLS class: the forward pass and tracebacks of mtr_k_dp2_quads (units <= 128, DPQ_FITS(rows, U, 1, 3))
  *   MTR_TEST_PASS_FOUR1P  1-4 tasks: a pass of mtr_k_revise_quads with one DP per 16 lanes, at the widest member's width, + counting tracebacks
  *   MTR_TEST_PASS_OCT1P   1-8 tasks: the same with two DPs per 16 lanes; member d is half d & 1 of lane group d >> 1
+ *   MTR_TEST_PASS_OCT2P   1-8 tasks of units of at most 32 bases: the forward pass and tracebacks of mtr_k_dp2_quads' eight-per-wavefront part, at
+ *                         ceil(longest unit / 8) columns per lane (DPQ_FITS(rows, U, 1, 3)); member d is lanes 8 d .. 8 d + 7
  * A task the batch path would never hand to the pass (the same bounds: units, rows, 16-bit scores, WrapDPsize), a group of another size, members of
  * QUAD2P classes or Q4 windows that differ, a window outside its read: MTR_ERR_BAD_ARG, the reason names the task; nothing is launched.
  * The entry sizes its own cell scratch from the passes' block macros, so the batch path's "the block fits this launch's cell budget" terms
  * (dp_batch_fits' 4 x 16 x rows, DPQ_BLOCK_BYTES / DPQP_BLOCK_BYTES against the cells of a batch) are held against the context's scratch cap
  * (MTR_SCRATCH_MAX_GB) instead: a group whose block exceeds it is refused in the same way. */
-enum { MTR_TEST_PASS_WAVE2P = 0, MTR_TEST_PASS_Q4 = 1, MTR_TEST_PASS_QUAD2P = 2, MTR_TEST_PASS_FOUR1P = 3, MTR_TEST_PASS_OCT1P = 4 };
+enum { MTR_TEST_PASS_WAVE2P = 0, MTR_TEST_PASS_Q4 = 1, MTR_TEST_PASS_QUAD2P = 2, MTR_TEST_PASS_FOUR1P = 3, MTR_TEST_PASS_OCT1P = 4, MTR_TEST_PASS_OCT2P = 5 };
 mtr_status mtr_test_wrap_dp_pass(mtr_ctx *ctx, int32_t pass, int32_t n_groups, const int32_t *group_off, const int32_t *read_idx,
                                  const int32_t *query_start, const int32_t *query_end, const uint8_t *units, const int32_t *unit_off,
                                  const int32_t *gain, const int32_t *mismatch, const int32_t *indel, int32_t *out16);

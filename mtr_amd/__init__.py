@@ -38,7 +38,8 @@ COUNTER_NAMES = ["dp_calls", "dp_cells", "dp_rows", "revise_dp_calls", "revise_d
                  "walk_calls", "walk_closed", "cyc_walk_fast", "prof43", "prof44", "prof45", "prof46", "prof47",
                  "qpass_bytes_dp2", "qpass_cells_dp2", "qpass_bytes_rev", "qpass_cells_rev", "revisions_shared", "reads_sent_back", "ranges_searched", "prof55"]
 # prof43..47, prof55: scratch counters of the profiling builds (-DMTR_PROFILE...); what they count depends on the kernel that wrote them
-# (per-read kernel: revisions / unchanged units / accepted rounds; walk kernels: cycles by window width; see the CNT_SPARE* uses in csrc)
+# (per-read kernel: revisions / unchanged units / accepted rounds; walk kernels: cycles by window width; see the CNT_SPARE* uses in csrc).
+# In a product build (no -DMTR_PROFILE) mtr_k_dp2_quads counts its passes by kind: prof47 = four alignments per wavefront, prof55 = eight
 EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mtr_process_batch", "mtr_free_results",
            "mtr_upload_batch", "mtr_run_resident", "mtr_fetch_results", "mtr_get_kernel_times", "mtr_get_counters",
            "mtr_test_ranges", "mtr_test_wrap_dp", "mtr_test_wrap_dp_pass", "mtr_test_last_mode", "mtr_set_trace", "mtr_get_trace",
@@ -1781,7 +1782,7 @@ class Engine:
                                               g.ctypes.data, m.ctypes.data, d.ctypes.data, out.ctypes.data), "mtr_test_wrap_dp")
         return out
 
-    DP_PASSES = {"WAVE2P": 0, "Q4": 1, "QUAD2P": 2, "FOUR1P": 3, "OCT1P": 4}       # MTR_TEST_PASS_* of include/mtr_hip_test.h
+    DP_PASSES = {"WAVE2P": 0, "Q4": 1, "QUAD2P": 2, "FOUR1P": 3, "OCT1P": 4, "OCT2P": 5}       # MTR_TEST_PASS_* of include/mtr_hip_test.h
 
     def test_wrap_dp_pass(self, dp_pass: str, groups):
         """mtr_test_wrap_dp_pass: one chosen forward pass of the wrap-around DP with its tracebacks.  groups: list of groups, a group a list of

@@ -300,8 +300,9 @@ DEVINL void wc_time(unsigned long long *wc, int which, unsigned long long t0) { 
 DEVINL unsigned long long clk() { return 0ull; }
 DEVINL void wc_time(unsigned long long *, int, unsigned long long) {}
 #endif
-// timers that share a spare counter with a development build's own use of it (-DMTR_PROFILE_WALK_FMT: k2_units.hip.inc walk())
-#ifdef MTR_PROFILE_WALK_FMT
+// timers that share a spare counter with a development build's own use of it (-DMTR_PROFILE_WALK_FMT: k2_units.hip.inc walk();
+// -DMTR_PROFILE_DP2_CLASS: k3_staged.hip.inc st_quad_run())
+#if defined(MTR_PROFILE_WALK_FMT) || defined(MTR_PROFILE_DP2_CLASS)
 #define wc_time_aux(wc, which, t0) do { } while (0)
 #else
 #define wc_time_aux(wc, which, t0) wc_time(wc, which, t0)

@@ -53,12 +53,35 @@ struct DpQuad {
 // GL = lanes per DP: 16 (four DPs per wavefront) or 64 (ONE DP on the whole wavefront, C columns per lane: units of 129..256 bases,
 // which the chunked dp_forward2p<4> takes at ~250 instructions a row).  SC = what the scores are multiplied by: 4 (see above) or 1
 // (windows beyond DPQ_FITS: the flags then take two shifts more per column).
-template <int C, int GL = 16, int SC = DPQ_SCALE>
-DEVINL void dp_forward2p_g16(const DpQuad &q, int G0, int MM0, int D0, int G1, int MM1, int D1, uint8_t *cells, int maxrows, int (&best)[4][2][3])
+//
+// GL = 8 (units of up to 32 bases, C <= 4): EIGHT DPs per wavefront, two per DPP row - a unit of at most 16 bases has one column per lane of a 16-lane DP
+// and pays a quarter of the per-row work whatever its length.  The members come as DpLanes, every lane holding the values of ITS DP (no selects over
+// eight members), and the best cells go back the same way.  What differs in the row loop: a DP's first lane starts a scan segment of its own (a constant
+// lane mask joins the match lanes: the row's scan then carries nothing over from the DP before it), and it takes no incoming value and the wrap as its
+// diagonal, which the row's first lane gets from the DPP move itself; the scan has three steps.
+struct DpLanes {                // per lane: the DP of lanes 8 d .. 8 d + 7 (member d of the pass); rows = 0 and U = 0: no such member
+    const uint32_t *pk; long long wlim; int base, rows, U; const uint8_t *unit;
+};
+#define DPO_BLOCK_BYTES(C, maxrows) (8 * DPQ_DP_BYTES_G(8, C, maxrows))
+DEVINL void scan_max_u32_x2_row8(unsigned &a, unsigned &b)
+{   // scan_max_u32_x2_row16 without its last step: for keys that grow from one half of the row to the other
+    unsigned s, t;
+#define MTR_SCAN_STEP(ctrl) \
+    s = (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, ctrl, 0xf, 0xf, false); \
+    t = (unsigned)__builtin_amdgcn_update_dpp(0, (int)b, ctrl, 0xf, 0xf, false); \
+    a = s > a ? s : a; b = t > b ? t : b;
+    MTR_SCAN_STEP(0x111) MTR_SCAN_STEP(0x112) MTR_SCAN_STEP(0x114)
+#undef MTR_SCAN_STEP
+}
+template <int C, int GL = 16, int SC = DPQ_SCALE, class Q = DpQuad, class B = int[4][2][3]>
+DEVINL void dp_forward2p_g16(const Q &q, int G0, int MM0, int D0, int G1, int MM1, int D1, uint8_t *cells, int maxrows, B &best)
 {
-    static_assert(C >= 1 && C <= 8 && (GL == 16 || GL == 64) && (SC == 1 || SC == 4), "columns per lane, lanes per DP, score scale");
+    static_assert(C >= 1 && C <= 8 && (GL == 16 || GL == 64 || (GL == 8 && C <= 4 && SC == 4)) && (SC == 1 || SC == 4), "columns per lane, lanes per DP, score scale");
     constexpr int NG = 64 / GL;
-    const int lane = lane_id();
+    int lane = lane_id();
+    // (GL = 8: what a pass derives from the lane alone - its first cell's address, D l C, the crossbar addresses, for each C - is not to be formed at the top of
+    //  the calling kernel for all widths and kept there in registers that the kernel's widest passes then spill)
+    if (GL == 8) asm volatile("" : "+v"(lane));
     const int g = lane / GL, l = lane % GL;
     unsigned Gpk = SC * ((unsigned)G0 | ((unsigned)G1 << 16)), MMpk = SC * ((unsigned)MM0 | ((unsigned)MM1 << 16)), Dpk = SC * ((unsigned)D0 | ((unsigned)D1 << 16));
     unsigned ONE = 0x00010001u, TWO = 0x00020002u, FOUR = 0x00040004u, SEL_HI = 0x07060100u, C8 = 0x00080008u;
@@ -66,11 +89,17 @@ DEVINL void dp_forward2p_g16(const DpQuad &q, int G0, int MM0, int D0, int G1, i
     unsigned SEL_K0 = 0x0c040100u, SEL_K1 = 0x0c040302u, SEL_S = 0x05040100u, SEL_LO = 0x05040100u, SEL_P1 = 0x07060302u, K4N = ~0x00040004u;
     asm volatile("" : "+s"(MMpk), "+s"(Dpk), "+s"(SEL_K0), "+s"(SEL_K1), "+s"(SEL_S), "+s"(SEL_LO), "+s"(SEL_P1), "+s"(K4N));
     // ---- this lane's DP
-    int Ul = q.U[0], basel = q.base[0], rowsl = q.rows[0]; const uint8_t *up_ = q.unit[0]; const uint32_t *pkl = q.pk[0]; long long wl = q.wlim[0];
-    if (g == 1) { Ul = q.U[1]; basel = q.base[1]; rowsl = q.rows[1]; up_ = q.unit[1]; pkl = q.pk[1]; wl = q.wlim[1]; }
-    if (g == 2) { Ul = q.U[2]; basel = q.base[2]; rowsl = q.rows[2]; up_ = q.unit[2]; pkl = q.pk[2]; wl = q.wlim[2]; }
-    if (g == 3) { Ul = q.U[3]; basel = q.base[3]; rowsl = q.rows[3]; up_ = q.unit[3]; pkl = q.pk[3]; wl = q.wlim[3]; }
-    if (g >= q.n) { Ul = 0; rowsl = 0; }
+    int Ul, basel, rowsl; const uint8_t *up_; const uint32_t *pkl; long long wl;
+    if constexpr (GL == 8) {
+        Ul = q.U; basel = q.base; rowsl = q.rows; up_ = q.unit; pkl = q.pk; wl = q.wlim;
+        if (rowsl <= 0) { Ul = 0; rowsl = 0; }
+    } else {
+        Ul = q.U[0]; basel = q.base[0]; rowsl = q.rows[0]; up_ = q.unit[0]; pkl = q.pk[0]; wl = q.wlim[0];
+        if (g == 1) { Ul = q.U[1]; basel = q.base[1]; rowsl = q.rows[1]; up_ = q.unit[1]; pkl = q.pk[1]; wl = q.wlim[1]; }
+        if (g == 2) { Ul = q.U[2]; basel = q.base[2]; rowsl = q.rows[2]; up_ = q.unit[2]; pkl = q.pk[2]; wl = q.wlim[2]; }
+        if (g == 3) { Ul = q.U[3]; basel = q.base[3]; rowsl = q.rows[3]; up_ = q.unit[3]; pkl = q.pk[3]; wl = q.wlim[3]; }
+        if (g >= q.n) { Ul = 0; rowsl = 0; }
+    }
     // the unit's base of each of the lane's columns, one byte each (4 = no such column: no read base equals it).  A column's match is
     // ONE compare of its byte with the row's base (the byte picked by the instruction itself, SDWA), whose result is a scalar mask: "no
     // match so far in this lane" is then scalar arithmetic on masks.  (Before: a table of match bits per base, one v_perm per row and
@@ -122,8 +151,12 @@ DEVINL void dp_forward2p_g16(const DpQuad &q, int G0, int MM0, int D0, int G1, i
     unsigned wrapv = 0u;                                        // H(i-1, U) of this lane's DP (all lanes of the row hold it)
     // rows after which a DP is over: the next such row is a scalar, the test per row a scalar compare
     int next_done = maxrows + 1;
+    if constexpr (GL == 8) next_done = uni(-wave_max_i32(-rowsl));
+    else {
 #pragma unroll
-    for (int h = 0; h < NG; h++) { const int r = h < q.n ? q.rows[h] : 0; if (r < next_done) next_done = r; }
+        for (int h = 0; h < NG; h++) { const int r = h < q.n ? q.rows[h] : 0; if (r < next_done) next_done = r; }
+    }
+    const unsigned long long seg_heads = GL == 8 ? 0x0101010101010101ull : 0ull;     // GL = 8: every DP's first lane starts a scan segment
     if (rowsl <= 0) { ubw[0] = 0x04040404u; ubw[1] = 0x04040404u; }
     uint8_t *crow = cells + (size_t)g * DPQ_DP_BYTES_G(GL, C, maxrows) + (size_t)l * C;
     int i = 1;
@@ -154,8 +187,11 @@ DEVINL void dp_forward2p_g16(const DpQuad &q, int G0, int MM0, int D0, int G1, i
                 if (i > next_done) {                            // rare: some DP of the wavefront has had its last row
                     if (i > rowsl) { ubw[0] = 0x04040404u; ubw[1] = 0x04040404u; }
                     next_done = maxrows + 1;
+                    if constexpr (GL == 8) next_done = uni(-wave_max_i32(-(rowsl >= i ? rowsl : maxrows + 1)));
+                    else {
 #pragma unroll
-                    for (int h = 0; h < NG; h++) { const int r = h < q.n ? q.rows[h] : 0; if (r >= i && r < next_done) next_done = r; }
+                        for (int h = 0; h < NG; h++) { const int r = h < q.n ? q.rows[h] : 0; if (r >= i && r < next_done) next_done = r; }
+                    }
                 }
                 const unsigned xi = __builtin_amdgcn_ubfe(wcur, (unsigned)bsh, 2u);
                 const unsigned inv_i = 0xFFFFu - (unsigned)i;
@@ -164,7 +200,8 @@ DEVINL void dp_forward2p_g16(const DpQuad &q, int G0, int MM0, int D0, int G1, i
                 bool mt[C], nh[C];
                 unsigned sprev = 0u;
                 bool nhp = true;
-                const unsigned diag0 = GL == 16 ? (unsigned)row_shift_up1((int)P[C - 1], (int)wrapv) : (unsigned)shift_up1((int)P[C - 1], (int)wrapv);
+                unsigned diag0 = GL != 64 ? (unsigned)row_shift_up1((int)P[C - 1], (int)wrapv) : (unsigned)shift_up1((int)P[C - 1], (int)wrapv);
+                if (GL == 8) diag0 = lane0 ? wrapv : diag0;                         // (the DP in the row's second half: its first lane is no row's first)
 #pragma unroll
                 for (int c = 0; c < C; c++) {
                     const unsigned diag = c == 0 ? diag0 : P[c - 1];
@@ -180,16 +217,17 @@ DEVINL void dp_forward2p_g16(const DpQuad &q, int G0, int MM0, int D0, int G1, i
                     sprev = sc;
                 }
                 // ---- what arrives from the left: segmented prefix maximum over the row's 16 lanes of the value leaving each lane
-                const unsigned long long hm = __ballot(!nhp);
+                const unsigned long long hm = __ballot(!nhp) | seg_heads;
                 const unsigned seg = (unsigned)mbcnt(hm >> 1);
                 const unsigned sout = sprev + Dlane;                                // what leaves the lane, counted from column 1 of the DP
                 unsigned k0 = __builtin_amdgcn_perm(seg, sout, SEL_K0);
                 unsigned k1 = __builtin_amdgcn_perm(seg, sout, SEL_K1);
-                if (GL == 16) scan_max_u32_x2_row16(k0, k1); else scan_max_u32_x2(k0, k1);
+                if (GL == 8) scan_max_u32_x2_row8(k0, k1); else if (GL == 16) scan_max_u32_x2_row16(k0, k1); else scan_max_u32_x2(k0, k1);
                 const unsigned S = __builtin_amdgcn_perm(k1, k0, SEL_S);
                 // the DP's first lane (column 1): nothing comes in.  Every other lane: at least what left the lane before it, which is at least
                 // D l C in both halves (g >= D j) - the subtraction borrows nothing
-                const unsigned e = (GL == 16 ? (unsigned)row_shift_up1((int)S, 0) : (unsigned)shift_up1((int)S, 0)) - Dlane;
+                unsigned e = (GL != 64 ? (unsigned)row_shift_up1((int)S, 0) : (unsigned)shift_up1((int)S, 0)) - Dlane;
+                if (GL == 8) e = lane0 ? 0u : e;
                 // ---- phase B: the incoming value reaches the columns before the lane's first match
                 unsigned f[8];
 #pragma unroll
@@ -289,8 +327,11 @@ DEVINL void dp_forward2p_g16(const DpQuad &q, int G0, int MM0, int D0, int G1, i
             const bool take = (ov > v) || (ov == v && ov > 0 && (oi < vi || (oi == vi && oj < vj)));
             if (take) { v = ov; vi = oi; vj = oj; }
         }
+        if constexpr (GL == 8) { best[d][0] = v / SC; best[d][1] = vi; best[d][2] = vj; }       // (every lane of a DP holds its DP's)
+        else {
 #pragma unroll
-        for (int h = 0; h < NG; h++) { best[h][d][0] = lane_val(v, GL * h) / SC; best[h][d][1] = lane_val(vi, GL * h); best[h][d][2] = lane_val(vj, GL * h); }
+            for (int h = 0; h < NG; h++) { best[h][d][0] = lane_val(v, GL * h) / SC; best[h][d][1] = lane_val(vi, GL * h); best[h][d][2] = lane_val(vj, GL * h); }
+        }
     }
 }
 

@@ -3,7 +3,7 @@
 // search decides which windows, units, row counts and group compositions a pass sees; here a test does.
 //
 // Nothing of a pass is written here: the kernels call the device functions the batch path calls (dp_wrap2 / dp_wrap, dp_forward2p_q4,
-// dp_forward2p_g16<C>, st_fwd1p_four, st_fwd1p_any, dp_traceback<0, .>) with the geometry the batch path gives them (cell blocks by DPQ_DP_BYTES /
+// dp_forward2p_g16<C>, st_fwd2p_oct, st_fwd1p_four, st_fwd1p_any, dp_traceback<0, .>) with the geometry the batch path gives them (cell blocks by DPQ_DP_BYTES /
 // DPQP_DP_BYTES, wlim from the batch's packed words), under the launch bounds of the kernel they stand for.  What the batch path does AFTER a
 // traceback (apply_dp, the choice between the two parameter sets) is left out on purpose: a test sees each parameter set's eight integers.
 // The host refuses every task the batch path would not hand to the pass (mtr_abi.hip), so nothing below re-checks eligibility.
@@ -137,6 +137,53 @@ __global__ __launch_bounds__(64, 4) void mtr_k_dp_test_quads(DpPassArgs a)
                     loop_join();
                 }
             }
+        }
+        wave_sync_mem();
+        loop_join();
+    }
+    wc_flush(s_cnt, a.t.counters);
+}
+
+// MTR_TEST_PASS_OCT2P: st_oct_run's forward pass and tracebacks for groups of up to eight units of at most ST_OUMAX bases (every lane fills in ITS DP; an
+// empty slot repeats the first member with no rows, as st_oct_run fills it)
+__global__ __launch_bounds__(64, 4) void mtr_k_dp_test_octs(DpPassArgs a)
+{
+    __shared__ unsigned long long s_cnt[CNT_N];
+    const int lane = lane_id();
+    if (lane < CNT_N) s_cnt[lane] = 0ull;
+    uint8_t *cells = a.t.scratch + (size_t)blockIdx.x * a.t.scratch_per_wave;
+    for (;;) {
+        const int grp = next_work_item(a.t.work_counter);
+        if (grp >= a.n_groups) break;
+        const int t0 = uni(a.group_off[grp]), n = uni(a.group_off[grp + 1]) - t0;
+        DpLanes q;
+        {
+            const bool on = (lane >> 3) < n;
+            const int tg = t0 + (on ? (lane >> 3) : 0);
+            const int rd = a.t.read_idx[tg], uo = a.t.unit_off[tg];
+            const long long wo = a.t.b.woff[rd];
+            q.pk = a.t.b.packed + wo; q.wlim = a.packed_words - wo;
+            q.base = a.t.qs[tg]; q.rows = on ? a.t.qe[tg] - q.base + 1 : 0; q.U = on ? a.t.unit_off[tg + 1] - uo : 0;
+            q.unit = a.t.units + uo;
+        }
+        const int maxrows = uni(wave_max_i32(q.rows)), umax = uni(wave_max_i32(q.U));
+        const int C = (umax + 7) >> 3;
+        int best[2][3];
+        st_fwd2p_oct(C, q, cells, maxrows, best);
+        wave_sync_mem();
+        const int bestl = st_oct_best_lanes(best);
+#pragma unroll 1
+        for (int g = 0; g < n; g++) {
+            const int tg = t0 + g;
+            const int rd = uni(a.t.read_idx[tg]), qs = uni(a.t.qs[tg]), U = uni(a.t.unit_off[tg + 1]) - uni(a.t.unit_off[tg]);
+            for (int p = 0; p < 2; p++) {
+                const int bk[3] = { lane_val(bestl, 8 * g + 3 * p), lane_val(bestl, 8 * g + 3 * p + 1), lane_val(bestl, 8 * g + 3 * p + 2) };
+                DpRes o;
+                dpt_traceback<1>(a, a.t.b.packed + uni64(a.t.b.woff[rd]), qs, U, cells + (size_t)g * DPQ_DP_BYTES_G(8, C, maxrows), p, DPQ_ROW_BYTES_G(8, C), bk, o, s_cnt);
+                dpt_store(a, tg, p, qs, U, o);
+                loop_join();
+            }
+            loop_join();
         }
         wave_sync_mem();
         loop_join();

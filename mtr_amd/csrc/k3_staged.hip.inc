@@ -4,7 +4,8 @@
 // One wavefront per read (mtr_k_reads) runs everything a read needs on its own wavefront, one thing after the other; here every
 // (read, range) is searched first (tables + walks, the phase 1 of k2_range), the candidate units are parked in HBM, and then ALL
 // two-parameter alignments of the batch are work items: in a big batch units of up to 128 bases FOUR per wavefront (mtr_k_dp2_quads, dp_quad.hip.inc:
-// alignments of different reads share a wavefront; sorted by columns per lane and row count so that a wavefront's four are alike),
+// alignments of different reads share a wavefront; sorted by columns per lane and row count so that a wavefront's four are alike) and, among them,
+// units of up to 32 bases EIGHT per wavefront (st_oct_run),
 // the others one wavefront each (mtr_k_dp2_waves; up to four units of at most 16 bases over one window share a pass).  Selection
 // runs per range; the revisions of a big batch are polished as work items (mtr_k_polish), joined where a range's polished states are equal
 // (mtr_k_rev_share) and run EIGHT per wavefront (mtr_k_revise_quads: dp_forward1p_h8, two revision DPs in the 16-bit halves of every register), those of a
@@ -29,6 +30,11 @@
 #define ST_QSUB 8
 #define ST_NBINS (ST_QCLASSES * ST_QROWBINS * ST_QSUB)
 #define ST_QUMAX 128
+// Units of up to ST_OUMAX bases go EIGHT per wavefront (st_oct_run): they are the last two classes (two and one column per lane of a 16-lane DP), each
+// sorted by ceil(U / 8) first - the upper half of the unit lengths in the first half of its row bins, rows descending in steps of 8 inside a half (windows
+// beyond 8 (ST_QROWBINS / 2) rows share the half's first bin) - so that the eight of a pass have the same columns per lane of an 8-lane DP and nearly the same rows
+#define ST_OUMAX 32
+#define ST_OCLS0 (ST_QCLASSES - 2)             // first class of that part of `sorted`
 
 // A range that found candidates (or may still find some at larger k) owns a block in the arena: this header, then one StEnt per
 // (k, direction) SLOT (slot = 2 (k - min_k) + direction; period 0 = empty), then per slot `stride` bytes: the unit (padded to
@@ -688,6 +694,10 @@ __global__ __launch_bounds__(64) void mtr_k_gather(K2Args a, StagedArgs s)
             d->pad[0] = ke; d->pad[1] = cls;
             if (is_quad) {
                 int rb = ST_QROWBINS - 1 - (rows >> 3); if (rb < 0) rb = 0;
+                if (Ue <= ST_OUMAX) {                  // eight per wavefront: by ceil(U / 8) first (above)
+                    int r8 = rows >> 3; if (r8 > ST_QROWBINS / 2 - 1) r8 = ST_QROWBINS / 2 - 1;
+                    rb = ((((Ue - 1) >> 3) & 1) ? 0 : ST_QROWBINS / 2) + ST_QROWBINS / 2 - 1 - r8;
+                }
                 const int bin = ((8 - DPQ_COLS(Ue)) * ST_QROWBINS + rb) * ST_QSUB + (int)(blockIdx.x & (ST_QSUB - 1));   // the classes with the most columns per lane first
                 s.dp_bin[di] = bin; s.dp_rank[di] = (int32_t)atomicAdd(s.bin_count + bin, 1u);
             } else {
@@ -739,9 +749,13 @@ __global__ __launch_bounds__(1024) void mtr_k_qbins(StagedArgs s, int force)
         int off = 0;
         for (int c = 0; c < ST_QCLASSES; c++) {
             const int n = tot[(c + 1) * TPC - 1] - (c > 0 ? tot[c * TPC - 1] : 0);
+            // (the alignments' sort, force = 0: the part that goes eight per wavefront starts on a multiple of eight slots - the class before it is padded - and
+            //  ends on one; sorted_cap's 4 slots per class hold that: 5 x 3 + 7 + 3 + 7)
+            if (!force && c == ST_OCLS0) off = (off + 7) & ~7;
             cls_start[c] = off; cls_n[c] = n;
             off += (n + 3) & ~3;
         }
+        if (!force) off = (off + 7) & ~7;
         cls_start[ST_QCLASSES] = off;
         const bool use = s.quad_min > 0 && (force || tot[1023] >= s.quad_min) && off <= s.sorted_cap;
         for (int c = 0; c <= ST_QCLASSES; c++) s.quad_cls[c] = use ? cls_start[c] : 0;
@@ -888,11 +902,23 @@ DEVINL void st_quad_run(K2Ctx &c, const K2Args &a, const StagedArgs &s, const in
     dp_forward2p_g16<C>(q, 1, 1, 3, 1, 3, 1, cells, maxrows, best);
     wave_sync_mem();
     wc_time(c.wc, CYC_DP_FWD, t_f);
+#if defined(MTR_PROFILE) && defined(MTR_PROFILE_DP2_CLASS)
+    {   // development build (tests/dev/dp2_class.py): the forward passes by columns per lane - cycles in the low 44 bits of a spare counter, passes above them.
+        // Class 1 is split at units of 8 bases (what eight lanes per DP would run with one column per lane)
+        int umax = 0;
+        for (int g = 0; g < q.n; g++) umax = q.U[g] > umax ? q.U[g] : umax;
+        const int cls_ = C == 1 ? (umax <= 8 ? CNT_SPARE43 : CNT_SPARE44) : C == 2 ? CNT_SPARE45 : C <= 6 ? CNT_SPARE46 : CNT_SPARE47;
+        wc_add(c.wc, cls_, (long long)(clk() - t_f) + (1ll << 44));
+    }
+#endif
     if (lane == 0) {                                   // what the pass wrote against what it was run for (cell pairs: both parameter sets)
         unsigned long long served = 0ull;
         for (int g = 0; g < q.n; g++) served += (unsigned long long)q.rows[g] * (unsigned long long)q.U[g];
         c.wc[CNT_QPASS_BYTES_DP2] += 4ull * (unsigned long long)maxrows * (unsigned long long)DPQ_ROW_BYTES(C);
         c.wc[CNT_QPASS_CELLS_DP2] += served;
+#ifndef MTR_PROFILE
+        c.wc[CNT_SPARE47] += 1ull;                     // (product builds: the passes by kind, see st_oct_run)
+#endif
     }
     const unsigned long long t_b = clk();
 #pragma unroll
@@ -933,6 +959,109 @@ DEVINL void st_quad_run(K2Ctx &c, const K2Args &a, const StagedArgs &s, const in
     wc_time(c.wc, CYC_DP_TB, t_b);
     wave_sync_mem();                                   // the next quad's forward pass overwrites the cells the tracebacks have read
 }
+// ---- eight alignments per wavefront: units of up to ST_OUMAX bases (dp_forward2p_g16<C, 8>, C = ceil(longest unit / 8) columns per lane) ----
+// Eight consecutive slots of `sorted` behind quad_cls[ST_OCLS0] are one pass (mtr_k_qbins starts that part on a multiple of eight slots and ends it on one;
+// a slot may be empty anywhere in it: the padding between the two classes).  Every lane loads the item of ITS DP, so a pass is filled by one round of vector
+// loads; the tracebacks, one after the other as in st_quad_run, read their member's item again - one copy of dp_traceback for all four widths.
+// (This filling is written out once more in mtr_k_dp_test_octs, dp_test.hip.inc: change both together.)
+DEVINL void st_fwd2p_oct(int C, const DpLanes &q, uint8_t *cells, int maxrows, int (&best)[2][3])
+{
+    switch (C) {
+    case 1: dp_forward2p_g16<1, 8>(q, 1, 1, 3, 1, 3, 1, cells, maxrows, best); break;
+    case 2: dp_forward2p_g16<2, 8>(q, 1, 1, 3, 1, 3, 1, cells, maxrows, best); break;
+    case 3: dp_forward2p_g16<3, 8>(q, 1, 1, 3, 1, 3, 1, cells, maxrows, best); break;
+    default: dp_forward2p_g16<4, 8>(q, 1, 1, 3, 1, 3, 1, cells, maxrows, best); break;
+    }
+}
+DEVINL int st_oct_best_lanes(const int (&best)[2][3])
+{   // (every lane of a DP holds its DP's best cells: lane k of the eight picks value k)
+    const int k = lane_id() & 7;
+    return k == 0 ? best[0][0] : k == 1 ? best[0][1] : k == 2 ? best[0][2] : k == 3 ? best[1][0] : k == 4 ? best[1][1] : best[1][2];
+}
+// (false: the block of the eight does not fit this launch's cell scratch - the caller runs them one after the other)
+DEVINL bool st_oct_run(K2Ctx &c, const K2Args &a, const StagedArgs &s, int slot0)
+{
+    const int lane = lane_id();
+    const int di_l = s.sorted[slot0 + (lane >> 3)];
+    const unsigned long long present = __ballot(di_l >= 0);
+    if (present == 0ull) return true;
+    DpLanes q;
+    {   // (an empty slot repeats a member that is there, with no rows)
+        const StDpItem *d = s.dp + (di_l >= 0 ? di_l : lane_val(di_l, first_lane(present)));
+        const int rd = d->rd;
+        const long long wo = a.b.woff[rd];
+        q.pk = a.b.packed + wo; q.wlim = (long long)a.packed_words - wo;
+        q.base = d->qs; q.rows = di_l >= 0 ? d->rows : 0; q.U = di_l >= 0 ? d->U : 0;
+        q.unit = s.arena + d->unit_off;
+    }
+    const int maxrows = uni(wave_max_i32(q.rows)), umax = uni(wave_max_i32(q.U));
+    const int C = (umax + 7) >> 3;                                  // 1 .. 4 (mtr_k_gather's bins: units of at most ST_OUMAX bases)
+    if (DPO_BLOCK_BYTES(C, maxrows) > c.y.cells) return false;
+    uint8_t *cells = c.sc + c.y.codes;
+    int best[2][3];
+    const unsigned long long t_f = clk();
+    st_fwd2p_oct(C, q, cells, maxrows, best);
+    wave_sync_mem();
+    // lane 8 d + k keeps value k of member d (set 0's value, row and column, then set 1's): ONE register stays live across the tracebacks
+    const int bestl = st_oct_best_lanes(best);
+    wc_time(c.wc, CYC_DP_FWD, t_f);
+#if defined(MTR_PROFILE) && defined(MTR_PROFILE_DP2_CLASS)
+    wc_add(c.wc, C == 1 ? CNT_SPARE43 : C == 2 ? CNT_SPARE44 : CNT_SPARE45, (long long)(clk() - t_f) + (1ll << 44));      // (by units <= 8, <= 16, <= 32, as st_quad_run's)
+#endif
+    if (lane == 0) {                                   // what the pass wrote (against what it was run for: per member, below)
+        c.wc[CNT_QPASS_BYTES_DP2] += 8ull * (unsigned long long)maxrows * (unsigned long long)DPQ_ROW_BYTES_G(8, C);
+#ifndef MTR_PROFILE
+        c.wc[CNT_SPARE55] += 1ull;                     // (product builds: the passes by kind - CNT_SPARE47 four per wavefront, CNT_SPARE55 eight)
+#endif
+    }
+    const unsigned long long t_b = clk();
+    const int rstride = DPQ_ROW_BYTES_G(8, C);
+    const size_t mbytes = DPQ_DP_BYTES_G(8, C, maxrows);
+#pragma unroll 1
+    for (int g = 0; g < 8; g++) {
+        const int di = uni(s.sorted[slot0 + g]);
+        if (di >= 0) {
+            const StDpItem *d = s.dp + di;
+            const int U = uni(d->U), qs = uni(d->qs), rows = uni(d->rows);
+            c.rd = uni(d->rd);                                    // (dp_too_large names the read)
+            const uint32_t *pk = a.b.packed + uni64(a.b.woff[c.rd]);
+            const uint8_t *unit = s.arena + uni64(d->unit_off);
+            RR r; rr_clear(r); r.period = U; r.kmer = uni(d->pad[0]);
+            RR bestr; rr_clear(bestr);
+            float best_ratio = -1.0f;
+            long long tb = 0;
+            bool ok = true;
+            for (int p = 0; p < 2; p++) {
+                DpRes o; o.stop_i = 0; o.end_i = 0; o.mat = o.mis = o.ins = o.del = o.scanned = 0; o.end_j = 0;
+                const int bv = lane_val(bestl, 8 * g + 3 * p), bi = lane_val(bestl, 8 * g + 3 * p + 1), bj = lane_val(bestl, 8 * g + 3 * p + 2);
+                if (bv > 0) {
+                    dp_traceback<0, 1>(pk, qs, U, cells + (size_t)g * mbytes, p, rstride, bi, bj, nullptr, nullptr, nullptr, o, c.wc);
+                    if (o.stop_i < 0) { o.stop_i = 0; o.end_i = 0; o.mat = o.mis = o.ins = o.del = o.scanned = 0; ok = false; }
+                }
+                tb += (long long)(o.mat + o.mis + o.ins + o.del);
+                RR t = r;
+                apply_dp(t, qs, o, U, 1, p == 0 ? 1 : 3, p == 0 ? 3 : 1);
+                trace_ev(c, 3, qs, qs + rows - 1, U, trace_on(c, 3) ? unit_hash(unit, U) : 0, 1, p == 0 ? 1 : 3, p == 0 ? 3 : 1, t.rep_start, t.rep_end, t.repeat_len, t.copies, t.mat, t.mis, t.ins);
+                const float qq = rr_ratio(t);
+                if (best_ratio < qq) { bestr = t; best_ratio = qq; }
+                loop_join();
+            }
+            if (!ok) { dp_too_large(c); rr_clear(bestr); }
+            int *o = s.dp_res + (size_t)di * 16;
+            if (lane == 0) {
+                o[0] = bestr.rep_start; o[1] = bestr.rep_end; o[2] = bestr.repeat_len; o[3] = bestr.period; o[4] = bestr.copies; o[5] = bestr.mat; o[6] = bestr.mis;
+                o[7] = bestr.ins; o[8] = bestr.del; o[9] = bestr.kmer; o[10] = bestr.G; o[11] = bestr.MM; o[12] = bestr.D;
+                c.wc[CNT_DP_CALLS] += 2ull; c.wc[CNT_DP_CELLS] += 2ull * (unsigned long long)rows * (unsigned long long)U;
+                c.wc[CNT_DP_ROWS] += 2ull * (unsigned long long)rows; c.wc[CNT_TB_STEPS] += (unsigned long long)tb;
+                c.wc[CNT_QPASS_CELLS_DP2] += (unsigned long long)rows * (unsigned long long)U;
+            }
+        }
+        loop_join();
+    }
+    wc_time(c.wc, CYC_DP_TB, t_b);
+    wave_sync_mem();                                   // the next pass's forward pass overwrites the cells the tracebacks have read
+    return true;
+}
 // The passes of a sorted list in a scattered order: pass i of the queue is list entry (i * stride) mod n, stride ~ 0.618 n and coprime to n.  In list order every
 // wavefront of the chip runs passes of the same shape at the same time - long forward passes (vector instructions) together, then their tracebacks (scalar
 // instructions and memory waits) together.  Measured (mtr_abi.hip: pass_shuffle): the kernel alone does not gain, the pipelined step does.
@@ -960,14 +1089,21 @@ __global__ __launch_bounds__(64, 4) void mtr_k_dp2_quads(K2Args a, StagedArgs s)
     c.y = k2_layout(a.Lmax, a.cells_cap);
     c.lds_keys = nullptr; c.seeds = nullptr; c.stage = nullptr; c.ties = nullptr; c.fresh = nullptr;
     st_dp2_waves_body(c, a, s);                            // the alignments that go one per wavefront, longest first
-    const unsigned nq = (unsigned)(uni(s.quad_cls[ST_QCLASSES]) >> 2);
+    // the passes of the list: four slots each up to the classes that go eight per wavefront, eight slots each from there - one queue, one scattered order
+    const int oct0 = uni(s.quad_cls[ST_OCLS0]);
+    const unsigned nq4 = (unsigned)(oct0 >> 2), nq = nq4 + (unsigned)((uni(s.quad_cls[ST_QCLASSES]) - oct0) >> 3);
     if (nq == 0u) { wc_flush(s_cnt, a.counters); return; }
     Wq wq; wq_init(wq, nq);
     const unsigned q_stride = s.pass_shuffle ? st_scatter_stride(nq) : 1u;
     for (;;) {
         const int wi = wq_next(ST_WQ(s, ST_Q_QUAD), nq, wq);
         if (wi < 0) break;                                 // every wave reaches this exit
-        const int slot0 = (int)st_scatter_index((unsigned)wi, nq, q_stride) << 2;
+        const unsigned pi = st_scatter_index((unsigned)wi, nq, q_stride);
+        const bool oct = pi >= nq4;
+        const int slot0 = oct ? oct0 + (int)((pi - nq4) << 3) : (int)pi << 2;
+        bool fits = true;
+        if (oct) fits = st_oct_run(c, a, s, slot0);
+        else if (uni(s.sorted[slot0]) >= 0) {                   // (else: four slots of padding in front of the eight-per-wavefront part; a class's empty slots are its last)
         DpQuad q; q.n = 0;                                  // (this slot filling - an empty slot repeats the first member with no rows, wlim from packed_words - is written out
         int items[4], kk[4];                                //  once more in mtr_k_dp_test_quads, dp_test.hip.inc: change both together)
         int maxrows = 0;
@@ -984,33 +1120,37 @@ __global__ __launch_bounds__(64, 4) void mtr_k_dp2_quads(K2Args a, StagedArgs s)
             kk[g] = uni(d->pad[0]);
             if (di >= 0) { q.n = g + 1; maxrows = q.rows[g] > maxrows ? q.rows[g] : maxrows; }
         }
-        const int C = DPQ_COLS(q.U[0]);                     // the same for the four (mtr_k_gather's bins)
-        if (DPQ_BLOCK_BYTES(C, maxrows) > c.y.cells) {
-            // the block of the four does not fit this launch's cell scratch (short reads): one after the other
-            for (int g = 0; g < q.n; g++) {
-                const StDpItem *d = s.dp + items[g];
-                c.rd = uni(d->rd); c.L = uni(a.b.lens[c.rd]); c.pk = a.b.packed + uni64(a.b.woff[c.rd]);
-                RR r; rr_clear(r); r.period = q.U[g]; r.kmer = kk[g];
-                dp_two_params_unit(c, q.base[g], q.base[g] + q.rows[g] - 1, r, q.unit[g]);
-                int *o = s.dp_res + (size_t)items[g] * 16;
-                if (lane == 0) {
-                    o[0] = r.rep_start; o[1] = r.rep_end; o[2] = r.repeat_len; o[3] = r.period; o[4] = r.copies; o[5] = r.mat; o[6] = r.mis;
-                    o[7] = r.ins; o[8] = r.del; o[9] = r.kmer; o[10] = r.G; o[11] = r.MM; o[12] = r.D;
-                }
-                loop_join();
-            }
-            loop_join();
-            continue;
-        }
-        switch (C) {
-        case 1: st_quad_run<1>(c, a, s, items, q, kk, maxrows); break;
-        case 2: st_quad_run<2>(c, a, s, items, q, kk, maxrows); break;
+        // the same for the four (mtr_k_gather's bins); units of up to ST_OUMAX bases go eight per wavefront and never come here - a wider pass would serve them as well
+        const int C = DPQ_COLS(q.U[0]) < 3 ? 3 : DPQ_COLS(q.U[0]);
+        fits = DPQ_BLOCK_BYTES(C, maxrows) <= c.y.cells;
+        if (fits) switch (C) {
         case 3: st_quad_run<3>(c, a, s, items, q, kk, maxrows); break;
         case 4: st_quad_run<4>(c, a, s, items, q, kk, maxrows); break;
         case 5: st_quad_run<5>(c, a, s, items, q, kk, maxrows); break;
         case 6: st_quad_run<6>(c, a, s, items, q, kk, maxrows); break;
         case 7: st_quad_run<7>(c, a, s, items, q, kk, maxrows); break;
         default: st_quad_run<8>(c, a, s, items, q, kk, maxrows); break;
+        }
+        }
+        if (!fits) {
+            // the block of the pass does not fit this launch's cell scratch (short reads): its alignments one after the other
+#pragma unroll 1
+            for (int g = 0; g < (oct ? 8 : 4); g++) {
+                const int di = uni(s.sorted[slot0 + g]);
+                if (di >= 0) {
+                    const StDpItem *d = s.dp + di;
+                    c.rd = uni(d->rd); c.L = uni(a.b.lens[c.rd]); c.pk = a.b.packed + uni64(a.b.woff[c.rd]);
+                    const int qs = uni(d->qs), rows = uni(d->rows);
+                    RR r; rr_clear(r); r.period = uni(d->U); r.kmer = uni(d->pad[0]);
+                    dp_two_params_unit(c, qs, qs + rows - 1, r, s.arena + uni64(d->unit_off));
+                    int *o = s.dp_res + (size_t)di * 16;
+                    if (lane == 0) {
+                        o[0] = r.rep_start; o[1] = r.rep_end; o[2] = r.repeat_len; o[3] = r.period; o[4] = r.copies; o[5] = r.mat; o[6] = r.mis;
+                        o[7] = r.ins; o[8] = r.del; o[9] = r.kmer; o[10] = r.G; o[11] = r.MM; o[12] = r.D;
+                    }
+                }
+                loop_join();
+            }
         }
         loop_join();
     }

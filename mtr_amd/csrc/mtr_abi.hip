@@ -4404,7 +4404,7 @@ extern "C" mtr_status mtr_test_wrap_dp_pass(mtr_ctx *ctx, int32_t pass, int32_t 
                                             const int32_t *query_start, const int32_t *query_end, const uint8_t *units, const int32_t *unit_off,
                                             const int32_t *gain, const int32_t *mismatch, const int32_t *indel, int32_t *out16)
 {
-    if (!ctx || pass < MTR_TEST_PASS_WAVE2P || pass > MTR_TEST_PASS_OCT1P || n_groups <= 0 || !group_off || !read_idx || !query_start || !query_end || !units || !unit_off ||
+    if (!ctx || pass < MTR_TEST_PASS_WAVE2P || pass > MTR_TEST_PASS_OCT2P || n_groups <= 0 || !group_off || !read_idx || !query_start || !query_end || !units || !unit_off ||
         !gain || !mismatch || !indel || !out16) return MTR_ERR_BAD_ARG;
     if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
     if (group_off[0] != 0) { ctx->err = "group_off[0] is not 0"; return MTR_ERR_BAD_ARG; }
@@ -4412,7 +4412,7 @@ extern "C" mtr_status mtr_test_wrap_dp_pass(mtr_ctx *ctx, int32_t pass, int32_t 
     read_switches(ctx->sw);
     const long long lim16 = ctx->sw.dp16_max_rows;
     const bool one_param = pass == MTR_TEST_PASS_FOUR1P || pass == MTR_TEST_PASS_OCT1P;
-    const int max_members = pass == MTR_TEST_PASS_WAVE2P ? 1 : pass == MTR_TEST_PASS_OCT1P ? RQ_SLOTS : 4;
+    const int max_members = pass == MTR_TEST_PASS_WAVE2P ? 1 : pass == MTR_TEST_PASS_OCT1P ? RQ_SLOTS : pass == MTR_TEST_PASS_OCT2P ? 8 : 4;
     auto refuse = [&](int g, int t, const char *why) {
         ctx->err = "bad DP pass task " + std::to_string(t) + " (group " + std::to_string(g) + "): " + why; return MTR_ERR_BAD_ARG;
     };
@@ -4443,6 +4443,10 @@ extern "C" mtr_status mtr_test_wrap_dp_pass(mtr_ctx *ctx, int32_t pass, int32_t 
                 if (quad_cols == 0) quad_cols = DPQ_COLS(U);
                 if (DPQ_COLS(U) != quad_cols) return refuse(g, t, "the tasks of a QUAD2P call are of one DPQ_COLS class");
                 break;
+            case MTR_TEST_PASS_OCT2P:                        // mtr_k_gather's isq, and the units that go eight per wavefront
+                if (U > ST_OUMAX) return refuse(g, t, "unit above ST_OUMAX");
+                if (rows > DP2P_MAX_ROWS || rows > lim16 || !DPQ_FITS(rows, U, 1, 3)) return refuse(g, t, "rows beyond DPQ_FITS");
+                break;
             default: {                                       // mtr_k_revise_quads' fits
                 const int G = gain[t], MM = mismatch[t], D = indel[t];
                 if (!((G == 1 && MM == 1 && D == 3) || (G == 1 && MM == 3 && D == 1) || (G == 5 && MM == 1 && D == 1))) return refuse(g, t, "not one of the three parameter sets");
@@ -4457,6 +4461,7 @@ extern "C" mtr_status mtr_test_wrap_dp_pass(mtr_ctx *ctx, int32_t pass, int32_t 
         case MTR_TEST_PASS_WAVE2P: block = 2 * (size_t)maxrows * (size_t)(maxU + 1) + 64; break;      // dp_forward2 writes two matrices; a wide row is at most 256 bytes
         case MTR_TEST_PASS_Q4: block = (size_t)maxrows * (size_t)sumU; break;
         case MTR_TEST_PASS_QUAD2P: block = DPQ_BLOCK_BYTES(DPQ_COLS(maxU), maxrows); break;
+        case MTR_TEST_PASS_OCT2P: block = DPO_BLOCK_BYTES((maxU + 7) / 8, maxrows); break;
         default: block = (RQ_SLOTS / 4) * DPQP_BLOCK_BYTES(DPQ_COLS(maxU), maxrows); break;
         }
         cells = std::max(cells, block);
@@ -4487,6 +4492,7 @@ extern "C" mtr_status mtr_test_wrap_dp_pass(mtr_ctx *ctx, int32_t pass, int32_t 
     const dim3 grid((unsigned)waves), block(64);
     if (pass == MTR_TEST_PASS_WAVE2P || pass == MTR_TEST_PASS_Q4) hipLaunchKernelGGL(mtr_k_dp_test_waves, grid, block, 0, ctx->stream, a);
     else if (one_param) hipLaunchKernelGGL(mtr_k_dp_test_rev, grid, block, 0, ctx->stream, a);
+    else if (pass == MTR_TEST_PASS_OCT2P) hipLaunchKernelGGL(mtr_k_dp_test_octs, grid, block, 0, ctx->stream, a);
     else {
         typedef void (*quad_kernel)(DpPassArgs);
         static const quad_kernel by_cols[8] = { mtr_k_dp_test_quads<1>, mtr_k_dp_test_quads<2>, mtr_k_dp_test_quads<3>, mtr_k_dp_test_quads<4>,

@@ -30,6 +30,7 @@
 #include "../../include/mtr_hip_test.h"
 #include "mtr_common.h"
 #include "file_state.h"
+#include "loci_args.h"
 #include "k1_ranges.hip.inc"
 #include "k2_units.hip.inc"
 #include "k3_staged.hip.inc"
@@ -143,7 +144,14 @@ struct StagedBufs {
 static unsigned *st_line(unsigned long long *sc, int line) { return (unsigned *)(sc + (size_t)line * (ST_LINE_BYTES / 8)); }
 static const int st_sl_cont_slots[ST_NCLS] = { 6, 7, 9, 11, 12, 13, 14, 15 };     // st_sl_cont(class): the continuation lists' sub-list counters
 
-struct LaneSlots;                                   // (defined with the locus search, below)
+// the lane slots of S slots (lane_slots, with the locus search), numbered bucket by bucket: bucket k's bins are q_first[k] * MLO_N_CLASSES .. q_first[k + 1] * MLO_N_CLASSES
+struct LaneSlots {
+    std::vector<int32_t> slot_q, q_slot;
+    int q_first[5] = { 0, 0, 0, 0, 0 }, l_umax[4] = { 0, 0, 0, 0 }, u_all = 0, u_wave = 0;      // u_wave: the longest motif no lane takes
+};
+// what a catalogue call of either kind keeps for its copy and its statistics (genotype_host.hip.inc): the rows in CAT_ROW_COLS columns
+struct CatKept { bool ready = false; int64_t rows = 0; int64_t counts[4] = { 0, 0, 0, 0 }; double ms[3] = { 0, 0, 0 }; };
+#define CAT_ROW_COLS 9
 #define MTR_N_PHASE_TIMES 8                         // ids 0..7 of mtr_get_kernel_times: the launch and the phases of the chain; 8, 9: the two dominant kernels
 struct mtr_ctx {
     int device = 0, manhattan = 1; float min_ratio = 0.6f;
@@ -243,23 +251,21 @@ struct mtr_ctx {
     // catalogue genotype (mtr_genotype_catalog_device), per call: the seed index (d_ct_ix = filter | key | run | entries | the slots' lengths), the
     // slots' masks, per read its hits' and candidates' counts and offsets, the hits and their head flags, the candidates (d_ct_cand = read | key |
     // span), their flank hits, the status and the filter's count; the alignment goes through the genotype's own d_gt_* buffers.  What
-    // mtr_genotype_catalog_copy_device hands out (gc_ready: gc_rows rows) is kept until an upload or the next catalogue call.
-    bool gc_ready = false; int64_t gc_rows = 0;
-    int64_t gc_counts[4] = { 0, 0, 0, 0 }; double gc_ms[3] = { 0, 0, 0 };       // the last catalogue call, for mtr_test_catalog_stats
+    // mtr_genotype_catalog_copy_device hands out (gc: the columns d_gc, genotype_host.hip.inc's GC_*) is kept until an upload or the next catalogue call.
+    CatKept gc;
     DevBuf<int32_t> d_ct_ix, d_ct_count, d_ct_hits, d_ct_cand, d_ct_flank, d_ct_status; DevBuf<int64_t> d_ct_off, d_ct_rowoff; DevBuf<uint64_t> d_ct_masks;
     DevBuf<uint8_t> d_ct_head; DevBuf<unsigned long long> d_ct_passed;
-    DevBuf<int32_t> d_gc_read, d_gc_locus, d_gc_fdist, d_gc_window, d_gc_fields, d_gc_score; DevBuf<float> d_gc_ratio; DevBuf<uint8_t> d_gc_spanning, d_gc_orientation;
+    DevBuf<uint8_t> d_gc[CAT_ROW_COLS];
     // partial genotype (mtr_genotype_partial_device), per call and nothing kept: the rows, the variants' task lists, the tasks' results by row;
     // d_pt_i32 = status | count | ulen | the work lists' variants, d_pt_i64 = bits | the work lists' firsts
     DevBuf<int32_t> d_pt_row, d_pt_ext, d_pt_i32; DevBuf<int64_t> d_pt_i64; DevBuf<PtTask> d_pt_task;
     // partial genotype at catalogue scale (mtr_genotype_partial_catalog_device), per call: the catalogue's d_ct_* working buffers (neither call keeps
     // anything in them), and of its own the candidates (d_pc_cand = read | locus | mask | slots | is_row), the flank tasks and their offsets, the
     // candidates' rows and results, the buckets' task lists, d_pc_i32 = status | count[4] | ulen, d_pc_i64 = bits.  What
-    // mtr_genotype_partial_catalog_copy_device hands out (pc_ready: pc_rows rows) is kept until an upload or the next call of this kind.
-    bool pc_ready = false; int64_t pc_rows = 0;
-    int64_t pc_counts[4] = { 0, 0, 0, 0 }; double pc_ms[3] = { 0, 0, 0 };       // the last such call, for mtr_test_partial_catalog_stats
+    // mtr_genotype_partial_catalog_copy_device hands out (pc: the columns d_pk, PK_*) is kept until an upload or the next call of this kind.
+    CatKept pc;
     DevBuf<int32_t> d_pc_cand, d_pc_row, d_pc_ext, d_pc_i32; DevBuf<uint32_t> d_pc_ftask; DevBuf<int64_t> d_pc_i64, d_pc_toff; DevBuf<PtTask> d_pc_task;
-    DevBuf<int32_t> d_pk_read, d_pk_locus, d_pk_fdist, d_pk_window, d_pk_ext; DevBuf<float> d_pk_ratio; DevBuf<uint8_t> d_pk_partial, d_pk_slot, d_pk_open;
+    DevBuf<uint8_t> d_pk[CAT_ROW_COLS];
     // mtr_catalog_create keeps nothing in the context but the host clock of its last success (mtr_test_catalog_build_stats); its working
     // buffers live for the call
     bool cb_ready = false; double cb_ms[3] = { 0, 0, 0 };
@@ -338,6 +344,13 @@ static double dbg_ms() { static const auto t0 = std::chrono::steady_clock::now()
 #define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
     ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); return MTR_ERR_HIP; } } while (0)
 
+// the instantiation of a kernel template over the motif's bucket ub (4, 8, 16 or 32: mdp_bucket)
+#define LAUNCH_BY_BUCKET(kernel, ub, grid, block, stream, ...) do { \
+    if ((ub) == 4) hipLaunchKernelGGL(kernel<4>, grid, block, 0, stream, __VA_ARGS__); \
+    else if ((ub) == 8) hipLaunchKernelGGL(kernel<8>, grid, block, 0, stream, __VA_ARGS__); \
+    else if ((ub) == 16) hipLaunchKernelGGL(kernel<16>, grid, block, 0, stream, __VA_ARGS__); \
+    else hipLaunchKernelGGL(kernel<32>, grid, block, 0, stream, __VA_ARGS__); } while (0)
+
 // malloc'd arrays that the caller receives (and frees with free / mtr_free_results): freed on every early return, release()d on success
 struct FreeDeleter { void operator()(void *p) const { free(p); } };
 template <typename T> using HostArray = std::unique_ptr<T[], FreeDeleter>;
@@ -353,7 +366,7 @@ static hipError_t copy_sync(mtr_ctx *ctx, void *dst, const void *src, size_t byt
 }
 
 // forget the resident batch (its buffers stay allocated for the next one)
-static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->mo_ready = false; ctx->ml_ready = false; ctx->gc_ready = false; ctx->pc_ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
+static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->mo_ready = false; ctx->ml_ready = false; ctx->gc.ready = false; ctx->pc.ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
 
 extern "C" int mtr_abi_version(void) { return MTR_ABI_VERSION; }
 
@@ -2027,32 +2040,23 @@ extern "C" mtr_status mtr_report_motifs_device(mtr_ctx *ctx, const mtr_report_mo
 // ---- known-motif search (motif_search.hip.inc) -------------------------------------------------------------------------------------
 // Only the lengths (already on the host) decide the work: one argsort per call, the slots' tables and at most five work lists go up, nothing
 // comes back but the status word.  Nothing kept lives in d_scratch (every user sizes and fills it per launch), so growing it here is safe.
-// (the checks in two parts: the locus search has arguments of its own to refuse between them)
+// (the checks in two parts: the locus search has arguments of its own to refuse between them; the scores', the total's and a motif's own
+// checks and words are loci_args.h's, which the genotype calls reach for their loci's motifs too)
 static mtr_status search_motifs_check_args(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs, int32_t gain, int32_t mismatch, int32_t indel)
 {
     if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
     if (n_motifs <= 0) { ctx->err = "n_motifs = " + std::to_string(n_motifs) + ": at least one motif is needed"; return MTR_ERR_BAD_ARG; }
     if (!motifs || !motif_off) { ctx->err = "motifs or motif_off is NULL"; return MTR_ERR_BAD_ARG; }
-    if (gain < 1 || gain > 5) { ctx->err = "gain = " + std::to_string(gain) + " outside 1..5"; return MTR_ERR_BAD_ARG; }
-    if (mismatch < 1 || mismatch > 3) { ctx->err = "mismatch = " + std::to_string(mismatch) + " outside 1..3"; return MTR_ERR_BAD_ARG; }
-    if (indel < 1 || indel > 3) { ctx->err = "indel = " + std::to_string(indel) + " outside 1..3"; return MTR_ERR_BAD_ARG; }
-    if (n_motifs > INT32_MAX / 2 || motif_off[n_motifs] - motif_off[0] > INT32_MAX / 2) {     // (the slots and their codes are indexed with 32 bits on the two strands)
-        ctx->err = "more than 2^30 - 1 motifs or motif bases"; return MTR_ERR_BAD_ARG;
-    }
+    if (!la_check_scores(gain, mismatch, indel, ctx->err)) return MTR_ERR_BAD_ARG;
+    if (!la_check_motif_total(n_motifs, motif_off[n_motifs] - motif_off[0], ctx->err)) return MTR_ERR_BAD_ARG;
     for (int32_t m = 0; m < n_motifs; m++) {
+        const char *s = motifs + motif_off[m];
         const int64_t U = motif_off[m + 1] - motif_off[m];
         if (U < 0) { ctx->err = "motif_off decreases at motif " + std::to_string(m); return MTR_ERR_BAD_ARG; }
-        if (U < 1 || U >= MTRC_MAX_PERIOD) { ctx->err = "motif " + std::to_string(m) + ": length " + std::to_string(U) + " outside 1.." + std::to_string(MTRC_MAX_PERIOD - 1); return MTR_ERR_BAD_ARG; }
-        for (int64_t t = motif_off[m]; t < motif_off[m + 1]; t++)
-            if (motifs[t] != 'A' && motifs[t] != 'C' && motifs[t] != 'G' && motifs[t] != 'T') {
-                ctx->err = "motif " + std::to_string(m) + ": byte " + std::to_string((int)(unsigned char)motifs[t]) + " at " + std::to_string(t - motif_off[m]) + " is none of ACGT";
-                return MTR_ERR_BAD_ARG;
-            }
+        const int64_t t = la_seq_check(false, s, U);
+        if (t < U) { ctx->err = la_refusal(la_motif_name(m), false, t, s, U); return MTR_ERR_BAD_ARG; }
     }
-    if ((int64_t)ctx->n_reads * (int64_t)n_motifs > (int64_t)INT32_MAX) {
-        ctx->err = std::to_string(ctx->n_reads) + " reads x " + std::to_string(n_motifs) + " motifs are more than 2^31 - 1 hits"; return MTR_ERR_BAD_ARG;
-    }
-    return MTR_OK;
+    return la_check_hits(ctx->n_reads, n_motifs, ctx->err) ? MTR_OK : MTR_ERR_BAD_ARG;
 }
 // the reference's WrapDPsize test (wrap_around_DP.c:260) for the longest read first, then for the read it names
 static mtr_status search_motifs_check_size(mtr_ctx *ctx, const int64_t *motif_off, int32_t n_motifs)
@@ -2068,27 +2072,6 @@ static mtr_status search_motifs_check_size(mtr_ctx *ctx, const int64_t *motif_of
             }
     }
     return MTR_OK;
-}
-
-// the slots (slot = motif * ns + strand): codes 0..3 of the motif, then of its reverse complement; for U <= MDP_MAX_U the 2-bit form as well
-static void motif_slots(const char *motifs, const int64_t *motif_off, int32_t n_motifs, int ns, std::vector<uint8_t> &units, std::vector<int32_t> &unit_off,
-                        std::vector<uint64_t> &bits)
-{
-    const size_t S = (size_t)n_motifs * (size_t)ns;
-    units.clear(); unit_off.assign(S + 1, 0); bits.assign(S, 0);
-    for (int32_t m = 0; m < n_motifs; m++) {
-        const int U = (int)(motif_off[m + 1] - motif_off[m]);
-        for (int s = 0; s < ns; s++) {
-            const size_t at = units.size();
-            for (int t = 0; t < U; t++) {
-                const char c = motifs[motif_off[m] + (s ? U - 1 - t : t)];
-                const int code = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : 3;
-                units.push_back((uint8_t)(s ? 3 - code : code));
-            }
-            unit_off[(size_t)(m * ns + s) + 1] = (int32_t)units.size();
-            bits[(size_t)(m * ns + s)] = mdp_motif_bits(units.data() + at, U);
-        }
-    }
 }
 
 extern "C" mtr_status mtr_search_motifs_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs, int32_t gain, int32_t mismatch,
@@ -2172,10 +2155,7 @@ extern "C" mtr_status mtr_search_motifs_device(mtr_ctx *ctx, const char *motifs,
         a.counter = (unsigned long long *)ctx->d_ms_counter + k; a.scratch_per_wave = per_wave[k]; a.cells_cap = k < 4 ? 0 : wave_cells;
         DBG("search_motifs: list %d: %zu slots, %lld items, %d wavefronts of %zu bytes", k, l_slot[k].size(), (long long)l_first[k].back(), waves[k], per_wave[k]);
         const dim3 grid((unsigned)waves[k]), block(64);
-        if (k == 0) hipLaunchKernelGGL(mtr_k_motif_lanes<4>, grid, block, 0, ctx->stream, a);
-        else if (k == 1) hipLaunchKernelGGL(mtr_k_motif_lanes<8>, grid, block, 0, ctx->stream, a);
-        else if (k == 2) hipLaunchKernelGGL(mtr_k_motif_lanes<16>, grid, block, 0, ctx->stream, a);
-        else if (k == 3) hipLaunchKernelGGL(mtr_k_motif_lanes<32>, grid, block, 0, ctx->stream, a);
+        if (k < 4) LAUNCH_BY_BUCKET(mtr_k_motif_lanes, bucket_ub[k], grid, block, ctx->stream, a);
         else hipLaunchKernelGGL(mtr_k_motif_waves, grid, block, 0, ctx->stream, a);
         HIPCHK(hipGetLastError());
     }
@@ -2209,11 +2189,6 @@ static hipError_t grow_keeping(mtr_ctx *ctx, DevBuf<T> &b, size_t keep, size_t b
     return e;
 }
 
-// the lane slots of S slots, numbered bucket by bucket: bucket k's bins are q_first[k] * MLO_N_CLASSES .. q_first[k + 1] * MLO_N_CLASSES
-struct LaneSlots {
-    std::vector<int32_t> slot_q, q_slot;
-    int q_first[5] = { 0, 0, 0, 0, 0 }, l_umax[4] = { 0, 0, 0, 0 }, u_all = 0, u_wave = 0;      // u_wave: the longest motif no lane takes
-};
 static LaneSlots lane_slots(const std::vector<int32_t> &unit_off, int S, int lane_max)
 {
     static const int bucket_ub[4] = { 4, 8, 16, 32 };
@@ -2274,10 +2249,7 @@ static mtr_status loci_round(mtr_ctx *ctx, LociArgs &a, const LaneSlots &ls, int
         if (k < 4) { a.bin0 = ls.q_first[k] * MLO_N_CLASSES; a.bin1 = ls.q_first[k + 1] * MLO_N_CLASSES; }
         DBG("%s: round %d, %lld intervals of at most %d bases, launch %d: %d wavefronts of %zu bytes", who, round, (long long)a.n_iv, max_len, k, waves[k], per_wave[k]);
         const dim3 grid((unsigned)waves[k]), block(64);
-        if (k == 0) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<4>, grid, block, 0, ctx->stream, a);
-        else if (k == 1) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<8>, grid, block, 0, ctx->stream, a);
-        else if (k == 2) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<16>, grid, block, 0, ctx->stream, a);
-        else if (k == 3) hipLaunchKernelGGL(mtr_k_motif_loci_lanes<32>, grid, block, 0, ctx->stream, a);
+        if (k < 4) LAUNCH_BY_BUCKET(mtr_k_motif_loci_lanes, 4 << k, grid, block, ctx->stream, a);
         else hipLaunchKernelGGL(mtr_k_motif_loci_waves, grid, block, 0, ctx->stream, a);
         HIPCHK(hipGetLastError());
     }
@@ -2401,1107 +2373,7 @@ extern "C" mtr_status mtr_motif_loci_copy_device(mtr_ctx *ctx, const mtr_motif_l
     return MTR_OK;
 }
 
-// ---- flank search (flank_search.hip.inc) --------------------------------------------------------------------------------------------
-// As the known-motif search: only the lengths decide the work - one argsort per call, the slots' masks and at most two work lists go up (one per
-// word width), nothing comes back but the status word.  No scratch at all.
-// a pattern of 1 .. FBV_MAX_M bases over ACGT, as codes; what: how the reason names it
-static mtr_status flank_pattern(mtr_ctx *ctx, const char *s, int64_t len, const std::string &what, std::vector<uint8_t> &codes)
-{
-    if (len < 1 || len > FBV_MAX_M) { ctx->err = what + ": length " + std::to_string(len) + " outside 1.." + std::to_string(FBV_MAX_M); return MTR_ERR_BAD_ARG; }
-    codes.resize((size_t)len);
-    for (int64_t t = 0; t < len; t++) {
-        const char c = s[t];
-        if (c != 'A' && c != 'C' && c != 'G' && c != 'T') { ctx->err = what + ": byte " + std::to_string((int)(unsigned char)c) + " at " + std::to_string(t) + " is none of ACGT"; return MTR_ERR_BAD_ARG; }
-        codes[(size_t)t] = (uint8_t)(c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : 3);
-    }
-    return MTR_OK;
-}
-static std::vector<uint8_t> revcomp_codes(const std::vector<uint8_t> &c)
-{
-    std::vector<uint8_t> r(c.size());
-    for (size_t t = 0; t < c.size(); t++) r[t] = (uint8_t)(3 - c[c.size() - 1 - t]);
-    return r;
-}
-
-// the eight masks (FL_MASKS) of a slot's pattern, as both flank kernels take them (the 32-bit masks are their low halves), and the word it runs in
-static void flank_slot_masks(const std::vector<uint8_t> &p, uint64_t *out)
-{
-    const int m = (int)p.size();
-    const FbvMasks<uint64_t> eq = fbv_masks<uint64_t>(p.data(), m, 0), rev = fbv_masks<uint64_t>(p.data(), m, 1);
-    const uint64_t v[FL_MASKS] = { eq.a, eq.c, eq.g, eq.t, rev.a, rev.c, rev.g, rev.t };
-    std::copy(v, v + FL_MASKS, out);
-}
-static bool flank_is_wide(const mtr_ctx *ctx, int m) { return !(m <= 32 && ctx->sw.flank_word != 64); }
-
-// every slot's pattern against every read: ctx->d_fl_res[read * S + slot][FL_RES], complete when this returns
-static mtr_status flank_scan(mtr_ctx *ctx, const std::vector<std::vector<uint8_t>> &pat)
-{
-    const int n = ctx->n_reads;
-    const size_t S = pat.size(), nr = (size_t)n;
-    std::vector<int32_t> order(nr);
-    for (int i = 0; i < n; i++) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return ctx->lens[(size_t)x] > ctx->lens[(size_t)y]; });
-    // the work lists: groups of 64 reads of the order per slot, the slots by the word their pattern needs
-    std::vector<uint64_t> masks(S * FL_MASKS); std::vector<int32_t> plen(S);
-    std::vector<int32_t> l_slot[2]; std::vector<int64_t> l_first[2];
-    const int64_t groups = ((int64_t)n + 63) / 64;
-    for (int k = 0; k < 2; k++) l_first[k].push_back(0);
-    for (size_t slot = 0; slot < S; slot++) {
-        const int m = (int)pat[slot].size();
-        flank_slot_masks(pat[slot], masks.data() + slot * FL_MASKS);
-        plen[slot] = m;
-        const int k = flank_is_wide(ctx, m) ? 1 : 0;
-        l_slot[k].push_back((int32_t)slot); l_first[k].push_back(l_first[k].back() + groups);
-    }
-    // device copies: d_fl_i32 = order | plen | the lists' slots, d_fl_i64 = masks | the lists' firsts
-    HIPCHK(ctx->d_fl_i32.ensure((nr + 3 * S) * 4)); HIPCHK(ctx->d_fl_i64.ensure((S * FL_MASKS + 2 * (S + 1)) * 8));
-    HIPCHK(ctx->d_fl_res.ensure(nr * S * FL_RES * 4)); HIPCHK(ctx->d_fl_status.ensure(4)); HIPCHK(ctx->d_fl_counter.ensure(2 * 8));
-    int32_t *d_order = ctx->d_fl_i32, *d_plen = d_order + nr, *d_slots = d_plen + S;
-    int64_t *d_masks = ctx->d_fl_i64, *d_firsts = d_masks + S * FL_MASKS;
-    HIPCHK(copy_sync(ctx, d_order, order.data(), nr * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_plen, plen.data(), S * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, d_masks, masks.data(), S * FL_MASKS * 8, hipMemcpyHostToDevice));
-    for (int k = 0; k < 2; k++) {
-        if (l_slot[k].empty()) continue;
-        HIPCHK(copy_sync(ctx, d_slots + (size_t)k * S, l_slot[k].data(), l_slot[k].size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(copy_sync(ctx, d_firsts + (size_t)k * (S + 1), l_first[k].data(), l_first[k].size() * 8, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemsetAsync(ctx->d_fl_status, 0, 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_fl_counter, 0, 2 * 8, ctx->stream));
-    FlankArgs a{};
-    a.b.packed = ctx->d_packed; a.b.woff = ctx->d_woff; a.b.lens = ctx->d_lens; a.b.order = d_order; a.b.n_reads = n;
-    a.order = d_order; a.n_reads = n; a.n_slots = (int32_t)S; a.masks = (const uint64_t *)d_masks; a.plen = d_plen; a.res = ctx->d_fl_res; a.status = ctx->d_fl_status;
-    for (int k = 0; k < 2; k++) {
-        if (l_slot[k].empty()) continue;
-        a.work = { d_slots + (size_t)k * S, d_firsts + (size_t)k * (S + 1), (int32_t)l_slot[k].size(), l_first[k].back() };
-        a.counter = (unsigned long long *)ctx->d_fl_counter + k;
-        size_t total = 0;
-        const int waves = pick_waves(ctx, (int)std::min<int64_t>(l_first[k].back(), INT32_MAX), 16, 0, &total);
-        DBG("flank scan: %d-bit word: %zu slots, %lld groups, %d wavefronts", k ? 64 : 32, l_slot[k].size(), (long long)l_first[k].back(), waves);
-        if (k == 0) hipLaunchKernelGGL(mtr_k_flank_lanes<uint32_t>, dim3((unsigned)waves), dim3(64), 0, ctx->stream, a);
-        else hipLaunchKernelGGL(mtr_k_flank_lanes<uint64_t>, dim3((unsigned)waves), dim3(64), 0, ctx->stream, a);
-        HIPCHK(hipGetLastError());
-    }
-    int32_t dev = 0;
-    HIPCHK(copy_sync(ctx, &dev, ctx->d_fl_status, 4, hipMemcpyDeviceToHost));
-    if (dev != DEV_OK) { ctx->err = "the flank search failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_search_flanks_device(mtr_ctx *ctx, const char *patterns, const int64_t *pattern_off, int32_t n_patterns, int32_t both_strands,
-                                               const mtr_flank_hits_dst *dst, int64_t *out_hits)
-{
-    if (!ctx || !out_hits) return MTR_ERR_BAD_ARG;
-    *out_hits = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
-    if (n_patterns <= 0) { ctx->err = "n_patterns = " + std::to_string(n_patterns) + ": at least one pattern is needed"; return MTR_ERR_BAD_ARG; }
-    if (!patterns || !pattern_off) { ctx->err = "patterns or pattern_off is NULL"; return MTR_ERR_BAD_ARG; }
-    const int ns = both_strands ? 2 : 1;
-    for (int32_t k = 0; k < n_patterns; k++)
-        if (pattern_off[k + 1] < pattern_off[k]) { ctx->err = "pattern_off decreases at pattern " + std::to_string(k); return MTR_ERR_BAD_ARG; }
-    std::vector<std::vector<uint8_t>> pat;
-    for (int32_t k = 0; k < n_patterns; k++) {
-        std::vector<uint8_t> codes;
-        { mtr_status st = flank_pattern(ctx, patterns + pattern_off[k], pattern_off[k + 1] - pattern_off[k], "pattern " + std::to_string(k), codes); if (st != MTR_OK) return st; }
-        pat.push_back(codes);
-        if (ns == 2) pat.push_back(revcomp_codes(codes));
-    }
-    const int64_t H = (int64_t)ctx->n_reads * n_patterns;
-    if (H > (int64_t)INT32_MAX) { ctx->err = std::to_string(ctx->n_reads) + " reads x " + std::to_string(n_patterns) + " patterns are more than 2^31 - 1 hits"; return MTR_ERR_BAD_ARG; }
-    *out_hits = H;
-    if (!dst) return MTR_OK;
-    if (dst->cap_hits < H) { ctx->err = "destination holds " + std::to_string(dst->cap_hits) + " hits, " + std::to_string(H) + " needed"; return MTR_ERR_OVERFLOW; }
-    if (!dst->dist || !dst->start || !dst->end || !dst->strand) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    { mtr_status st = flank_scan(ctx, pat); if (st != MTR_OK) return st; }
-    const FlankHitsOut out = { dst->dist, dst->start, dst->end, dst->strand };
-    hipLaunchKernelGGL(mtr_k_flank_pack, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t *)ctx->d_fl_res, (int32_t)ns, H, out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
-
-// the genotype's checks of its arguments, in its order, up to the row limit; on MTR_OK: the motifs as the search takes them, the four flank
-// patterns of every locus (A, B, rc A, rc B) as codes
-static mtr_status genotype_check_args(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist, int32_t gain, int32_t mismatch,
-                                      int32_t indel, std::string &mot, std::vector<int64_t> &mot_off, std::vector<std::vector<uint8_t>> &pat)
-{
-    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
-    if (n_loci <= 0) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
-    if (!seqs || !seq_off) { ctx->err = "seqs or seq_off is NULL"; return MTR_ERR_BAD_ARG; }
-    if (n_loci > INT32_MAX / 4) { ctx->err = "more than 2^29 - 1 loci"; return MTR_ERR_BAD_ARG; }
-    for (int32_t k = 0; k < 3 * n_loci; k++)
-        if (seq_off[k + 1] < seq_off[k]) { ctx->err = "seq_off decreases at locus " + std::to_string(k / 3) + " (sequence " + std::to_string(k % 3) + ")"; return MTR_ERR_BAD_ARG; }
-    // the motifs as the search takes them, for the search's own checks
-    mot.clear(); mot_off.assign(1, 0);
-    for (int32_t l = 0; l < n_loci; l++) { mot.append(seqs + seq_off[3 * l + 1], (size_t)(seq_off[3 * l + 2] - seq_off[3 * l + 1])); mot_off.push_back((int64_t)mot.size()); }
-    { mtr_status st = search_motifs_check_args(ctx, mot.data(), mot_off.data(), n_loci, gain, mismatch, indel); if (st != MTR_OK) return st; }
-    pat.assign((size_t)n_loci * GT_SLOTS, std::vector<uint8_t>());
-    for (int32_t l = 0; l < n_loci; l++)
-        for (int side = 0; side < 2; side++) {
-            const int64_t at = seq_off[3 * l + 2 * side], len = seq_off[3 * l + 2 * side + 1] - at;
-            std::vector<uint8_t> &c = pat[(size_t)l * GT_SLOTS + (size_t)side];
-            { mtr_status st = flank_pattern(ctx, seqs + at, len, "locus " + std::to_string(l) + ", " + (side ? "right" : "left") + " flank", c); if (st != MTR_OK) return st; }
-            pat[(size_t)l * GT_SLOTS + 2 + (size_t)side] = revcomp_codes(c);
-        }
-    if (max_flank_dist < 0) { ctx->err = "max_flank_dist = " + std::to_string(max_flank_dist) + ": at least 0"; return MTR_ERR_BAD_ARG; }
-    const int n = ctx->n_reads;
-    const int64_t rows = (int64_t)n * n_loci;
-    if (2 * rows > (int64_t)INT32_MAX) { ctx->err = std::to_string(n) + " reads x " + std::to_string(n_loci) + " loci in two orientations are more than 2^31 - 1 pairs"; return MTR_ERR_BAD_ARG; }
-    return MTR_OK;
-}
-
-static mtr_status genotype_align(mtr_ctx *ctx, const std::string &mot, const std::vector<int64_t> &mot_off, int32_t n_loci, int64_t N, int max_len,
-                                 int32_t gain, int32_t mismatch, int32_t indel, const char *who);      // (defined below the call)
-// the 2 * n_loci single-strand motif slots on the device - the slots' codes, their offsets, their 2-bit forms - and the offsets on the host
-// cat_id: the prepared catalogue they belong to (mtr_catalog::id), 0 for tables a text-taking call made for itself
-struct GtTables { const uint8_t *d_units; const int32_t *d_uoff; const uint64_t *d_bits; const std::vector<int32_t> *unit_off; uint64_t cat_id; };
-static mtr_status genotype_align_tables(mtr_ctx *ctx, const GtTables &tb, int32_t n_loci, int64_t N, int max_len, int32_t gain, int32_t mismatch, int32_t indel, const char *who);
-
-// ---- locus genotyping (genotype.hip.inc) --------------------------------------------------------------------------------------------
-// The flank step over four slots per locus, the pairing, one look at the device (how many windows, their longest), one round of the locus
-// search's kernels over 2 * n_loci single-strand motifs (sized as mtr_search_motif_loci_device sizes a round), the columns.
-extern "C" mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist,
-                                               int32_t gain, int32_t mismatch, int32_t indel, const mtr_genotypes_dst *dst, int64_t *out_rows)
-{
-    if (!ctx || !out_rows) return MTR_ERR_BAD_ARG;
-    *out_rows = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    std::string mot; std::vector<int64_t> mot_off; std::vector<std::vector<uint8_t>> pat;
-    { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, mot, mot_off, pat); if (st != MTR_OK) return st; }
-    const int n = ctx->n_reads;
-    const int64_t rows = (int64_t)n * n_loci;
-    { mtr_status st = search_motifs_check_size(ctx, mot_off.data(), n_loci); if (st != MTR_OK) return st; }
-    *out_rows = rows;
-    if (!dst) return MTR_OK;
-    if (dst->cap_rows < rows) { ctx->err = "destination holds " + std::to_string(dst->cap_rows) + " rows, " + std::to_string(rows) + " needed"; return MTR_ERR_OVERFLOW; }
-    if (!dst->spanning || !dst->orientation || !dst->flank_dist || !dst->window || !dst->fields || !dst->score || !dst->ratio) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    { mtr_status st = flank_scan(ctx, pat); if (st != MTR_OK) return st; }
-    // the pairing
-    HIPCHK(ctx->d_gt_state.ensure(LOCI_STATE * 4)); HIPCHK(ctx->d_gt_pair.ensure((size_t)rows * GT_PAIR * 4)); HIPCHK(ctx->d_gt_iv.ensure((size_t)rows * sizeof(LociIv)));
-    HIPCHK(hipMemsetAsync(ctx->d_gt_state, 0, LOCI_STATE * 4, ctx->stream));
-    const dim3 per_row((unsigned)((rows + 255) / 256)), b256(256);
-    const GenoPairArgs ga = { ctx->d_fl_res, n_loci, max_flank_dist, rows, ctx->d_gt_pair, ctx->d_gt_iv, (int32_t)rows, ctx->d_gt_state };
-    hipLaunchKernelGGL(mtr_k_geno_pair, per_row, b256, 0, ctx->stream, ga);
-    HIPCHK(hipGetLastError());
-    int32_t st[LOCI_STATE];
-    HIPCHK(copy_sync(ctx, st, ctx->d_gt_state, sizeof st, hipMemcpyDeviceToHost));
-    const int64_t N = st[LOCI_NEXT];
-    const int max_len = st[LOCI_MAXLEN];
-    if (st[LOCI_STATUS] != DEV_OK || N < 0 || N > rows || max_len < 0 || max_len > ctx->Lmax || (N > 0) != (max_len > 0)) {
-        ctx->err = "the genotype's pairing failed on the device (status " + std::to_string(st[LOCI_STATUS]) + ")"; return MTR_ERR_HIP;
-    }
-    if (N > 0) { mtr_status r = genotype_align(ctx, mot, mot_off, n_loci, N, max_len, gain, mismatch, indel, "genotype_loci"); if (r != MTR_OK) return r; }
-    const GenotypesOut out = { dst->spanning, dst->orientation, dst->flank_dist, dst->window, dst->fields, dst->score, dst->ratio };
-    hipLaunchKernelGGL(mtr_k_geno_out, per_row, b256, 0, ctx->stream, (const int32_t *)ctx->d_gt_pair, (const int32_t *)ctx->d_gt_res, rows, out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
-
-// The alignment step of the genotype and of the catalogue genotype: the N intervals in ctx->d_gt_iv (the longest of max_len bases, counted in
-// ctx->d_gt_state) through one round of the locus search's path over 2 * n_loci single-strand motifs; their hits are in ctx->d_gt_res on MTR_OK.
-static mtr_status genotype_align(mtr_ctx *ctx, const std::string &mot, const std::vector<int64_t> &mot_off, int32_t n_loci, int64_t N, int max_len,
-                                 int32_t gain, int32_t mismatch, int32_t indel, const char *who)
-{
-    const int M2 = 2 * n_loci;
-    {
-        // the slots: locus l as given (2 * l) and reverse-complemented (2 * l + 1), one strand each
-        std::string both; std::vector<int64_t> both_off(1, 0);
-        static const char letters[4] = { 'A', 'C', 'G', 'T' };
-        for (int32_t l = 0; l < n_loci; l++) {
-            const std::string m = mot.substr((size_t)mot_off[(size_t)l], (size_t)(mot_off[(size_t)l + 1] - mot_off[(size_t)l]));
-            std::string rc(m.size(), 'A');
-            for (size_t t = 0; t < m.size(); t++) { const char c = m[m.size() - 1 - t]; rc[t] = letters[3 - (c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : 3)]; }
-            both += m; both_off.push_back((int64_t)both.size()); both += rc; both_off.push_back((int64_t)both.size());
-        }
-        std::vector<uint8_t> units; std::vector<int32_t> unit_off; std::vector<uint64_t> bits;
-        motif_slots(both.data(), both_off.data(), M2, 1, units, unit_off, bits);
-        // device copies: d_gt_i32 = unit_off | slot_q | q_slot (the two lists are genotype_align_tables'), d_gt_i64 = bits
-        const size_t sS = (size_t)M2;
-        HIPCHK(ctx->d_gt_i32.ensure((3 * sS + 2) * 4)); HIPCHK(ctx->d_gt_i64.ensure(sS * 8)); HIPCHK(ctx->d_gt_units.ensure(units.size() + 16));
-        HIPCHK(copy_sync(ctx, ctx->d_gt_i32, unit_off.data(), (sS + 1) * 4, hipMemcpyHostToDevice));
-        HIPCHK(copy_sync(ctx, ctx->d_gt_i64, bits.data(), sS * 8, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_gt_units, units.data(), units.size(), hipMemcpyHostToDevice));
-        const GtTables tb = { ctx->d_gt_units, ctx->d_gt_i32, (const uint64_t *)(int64_t *)ctx->d_gt_i64, &unit_off, 0 };
-        return genotype_align_tables(ctx, tb, n_loci, N, max_len, gain, mismatch, indel, who);
-    }
-}
-
-// The alignment step from the device tables, whoever made them: the lane slots of this call's MTR_TEST_MOTIF_LANE_MAX from the units' lengths
-// (the context's d_gt_i32 behind the text-taking calls' unit_off: slot_q | q_slot - a prepared catalogue is never written to), the round.
-static mtr_status genotype_align_tables(mtr_ctx *ctx, const GtTables &tb, int32_t n_loci, int64_t N, int max_len, int32_t gain, int32_t mismatch, int32_t indel, const char *who)
-{
-    const int n = ctx->n_reads, M2 = 2 * n_loci;
-    int32_t st[LOCI_STATE];
-    {
-        const int lane_max = ctx->sw.motif_lane_max, lane_rows = ctx->sw.motif_lane_rows;
-        const size_t sS = (size_t)M2, nt = (size_t)N;
-        HIPCHK(ctx->d_gt_i32.ensure((3 * sS + 2) * 4));
-        const int32_t *d_uoff = tb.d_uoff;
-        int32_t *d_slot_q = (int32_t *)ctx->d_gt_i32 + sS + 1, *d_q_slot = d_slot_q + sS;
-        // the lane slots: a prepared catalogue's, once derived and uploaded for this lane_max, stay in the context (its d_gt_i32 at this address)
-        // until another catalogue, another lane_max or a text-taking call (cat_id = 0) takes their place; batch after batch sends nothing
-        if (!(tb.cat_id != 0 && ctx->gt_ls && ctx->gt_ls_cat == tb.cat_id && ctx->gt_ls_lane_max == lane_max && ctx->gt_ls_at == d_slot_q)) {
-            ctx->gt_ls_cat = 0;
-            const std::shared_ptr<const LaneSlots> fresh = std::make_shared<const LaneSlots>(lane_slots(*tb.unit_off, M2, lane_max));
-            HIPCHK(copy_sync(ctx, d_slot_q, fresh->slot_q.data(), sS * 4, hipMemcpyHostToDevice));
-            if (!fresh->q_slot.empty()) HIPCHK(copy_sync(ctx, d_q_slot, fresh->q_slot.data(), fresh->q_slot.size() * 4, hipMemcpyHostToDevice));
-            ctx->gt_ls = fresh; ctx->gt_ls_cat = tb.cat_id; ctx->gt_ls_lane_max = lane_max; ctx->gt_ls_at = d_slot_q;
-        }
-        const LaneSlots &ls = *ctx->gt_ls;
-        const size_t nq = ls.q_slot.size();
-        if ((int64_t)nq * MLO_N_CLASSES > (int64_t)INT32_MAX) { ctx->err = std::to_string(nq) + " short motifs are more than the bins take"; return MTR_ERR_OVERFLOW; }
-        const size_t nb = nq * MLO_N_CLASSES;
-        // the bins: d_gt_bin32 = hist | groups, d_gt_bin64 = tfirst | gfirst; the tasks: d_gt_task32 = tbin | trank | sorted | wlist
-        HIPCHK(ctx->d_gt_bin32.ensure((2 * nb + 1) * 4)); HIPCHK(ctx->d_gt_bin64.ensure(2 * (nb + 1) * 8)); HIPCHK(ctx->d_gt_counter.ensure(5 * 8));
-        HIPCHK(ctx->d_gt_task32.ensure(4 * nt * 4)); HIPCHK(ctx->d_gt_res.ensure(nt * MS_RES * 4));
-        LociArgs a{};
-        a.b.packed = ctx->d_packed; a.b.woff = ctx->d_woff; a.b.lens = ctx->d_lens; a.b.order = nullptr; a.b.n_reads = n;
-        a.iv = ctx->d_gt_iv; a.n_iv = (int32_t)N;
-        a.n_motifs = M2; a.n_strands = 1; a.G = gain; a.MM = mismatch; a.D = indel; a.lane_rows = lane_rows;
-        a.units = tb.d_units; a.unit_off = d_uoff; a.bits = tb.d_bits; a.slot_q = d_slot_q; a.q_slot = d_q_slot;
-        a.hist = ctx->d_gt_bin32; a.groups = a.hist + nb; a.tfirst = ctx->d_gt_bin64; a.gfirst = a.tfirst + nb + 1; a.n_bins = (int32_t)nb;
-        a.tbin = ctx->d_gt_task32; a.trank = a.tbin + nt; a.sorted = a.trank + nt; a.wlist = a.sorted + nt; a.res = ctx->d_gt_res;
-        a.state = ctx->d_gt_state; a.dp16_max_rows = ctx->sw.dp16_max_rows;
-        { mtr_status r = loci_round(ctx, a, ls, N, max_len, (unsigned long long *)ctx->d_gt_counter, who, 0); if (r != MTR_OK) return r; }
-        // the status before the columns: a failed genotype writes nothing
-        HIPCHK(copy_sync(ctx, st, ctx->d_gt_state, sizeof st, hipMemcpyDeviceToHost));
-        if (st[LOCI_STATUS] == DEV_ERR_DP_TOO_LARGE) { ctx->err = "You need to increse the value of WrapDPsize. (a DP of the genotype exceeded it or its scratch)"; return MTR_ERR_DP_TOO_LARGE; }
-        if (st[LOCI_STATUS] != DEV_OK) { ctx->err = "the genotype's alignments failed on the device (status " + std::to_string(st[LOCI_STATUS]) + ")"; return MTR_ERR_HIP; }
-    }
-    return MTR_OK;
-}
-
-// ---- catalogue genotype (catalog.hip.inc) -------------------------------------------------------------------------------------------
-// The genotype's checks; the seed index built on the host (sorted entries, a table of the distinct codes, the filter bitmap) and sent up; the scan
-// in two passes around one look at the device (the hits), the candidates in two passes around another (the candidates); their flank scans, the
-// pairing, a third look (the windows, their longest, the rows), the genotype's alignment step, the rows into the context's buffers.  Every buffer
-// is sized by the reads, by the loci, or by what the scan found: none by reads x loci.
-// The catalogue calls' checks of the seeds: seed_len, then every flank's length, naming locus and side
-static mtr_status catalog_check_seeds(mtr_ctx *ctx, const std::vector<std::vector<uint8_t>> &pat, int32_t n_loci, int32_t max_flank_dist, int32_t seed_len)
-{
-    if (seed_len < SI_MIN_Q || seed_len > SI_MAX_Q) { ctx->err = "seed_len = " + std::to_string(seed_len) + " outside " + std::to_string(SI_MIN_Q) + ".." + std::to_string(SI_MAX_Q); return MTR_ERR_BAD_ARG; }
-    const int64_t need = ((int64_t)max_flank_dist + 1) * seed_len;
-    for (int32_t l = 0; l < n_loci; l++)
-        for (int side = 0; side < 2; side++) {
-            const size_t m = pat[(size_t)l * GT_SLOTS + (size_t)side].size();
-            if ((int64_t)m < need) {
-                ctx->err = "locus " + std::to_string(l) + ", " + (side ? "right" : "left") + " flank: " + std::to_string(m) + " bases are fewer than (max_flank_dist + 1) * seed_len = " + std::to_string(need);
-                return MTR_ERR_BAD_ARG;
-            }
-        }
-    return MTR_OK;
-}
-
-// The seed index of a catalogue call, as it lies in ctx->d_ct_ix (filter | key | run | entries | the slots' lengths), and what the host knows of it
-struct CatIndex {
-    size_t E = 0, distinct = 0, fwords = 0; uint32_t cap = 0; int fbits = 0;
-    bool narrow = false, wide = false;                       // a slot of either flank word exists
-    const uint32_t *d_filter = nullptr, *d_key = nullptr; const int32_t *d_run = nullptr, *d_ent = nullptr, *d_plen = nullptr;
-    const uint64_t *d_masks = nullptr;                       // the slots' masks: ctx->d_ct_masks, or a prepared catalogue's
-};
-
-// A prepared catalogue (mtr_catalog_create): what depends on the loci alone.  On the host what lengths decide; on the device, in buffers of its
-// own (no context owns them: any context of the device may read them, none writes), the index as CatIndex points into it, the slots' masks,
-// the genotype's 2 * n_loci single-strand motif slots (GtTables) and the partial genotype's variants (vbits, ulen).
-struct mtr_catalog {
-    uint64_t id = 0;                                        // never 0 and never given twice in a process: what a context remembers a catalogue by
-    int device = 0; int32_t n_loci = 0, max_flank_dist = 0, seed_len = 0;
-    size_t E = 0, distinct = 0, fwords = 0; uint32_t cap = 0; int fbits = 0;
-    int64_t n_short = 0, n_long = 0;                        // slots of at most / of more than 32 bases: which flank words a call launches
-    int64_t first_long_motif = -1;
-    std::vector<int64_t> mot_off;                           // [n_loci + 1]: the motifs' lengths as search_motifs_check_size takes them
-    std::vector<int32_t> unit_off;                          // [2 * n_loci + 1]: the motif slots' offsets (lane_slots)
-    DevBuf<uint32_t> d_filter, d_key; DevBuf<int32_t> d_run, d_ent, d_plen, d_uoff, d_ulen; DevBuf<uint64_t> d_masks, d_ubits, d_vbits; DevBuf<uint8_t> d_units;
-    size_t device_bytes() const { return d_filter.cap + d_key.cap + d_run.cap + d_ent.cap + d_plen.cap + d_uoff.cap + d_ulen.cap + d_masks.cap + d_ubits.cap + d_vbits.cap + d_units.cap; }
-};
-static GtTables catalog_gt_tables(const mtr_catalog *cat) { return { cat->d_units, cat->d_uoff, cat->d_ubits, &cat->unit_off, cat->id }; }
-
-// what a catalogue call runs on beside the index: the motifs as text (the text-taking calls), or a prepared catalogue's tables
-struct CatMotifs { const std::string *mot; const std::vector<int64_t> *mot_off; const mtr_catalog *cat; };
-static mtr_status genotype_catalog_run(mtr_ctx *ctx, const CatIndex &ix, const CatMotifs &cm, int32_t n_loci, int32_t max_flank_dist, int q, int32_t gain, int32_t mismatch,
-                                       int32_t indel, double ms_index, int64_t *out_rows, int64_t *out_candidates);
-static mtr_status genotype_partial_catalog_run(mtr_ctx *ctx, const CatIndex &ix, const CatMotifs &cm, int32_t n_loci, int32_t max_flank_dist, int q, int32_t gain,
-                                               int32_t mismatch, int32_t indel, int32_t max_tail, double ms_index, int64_t *out_rows, int64_t *out_candidates);
-
-// What every catalogue call needs beside an index, whichever made it: the reads' count and offset buffers sized, the status and the filter's
-// count zeroed
-static mtr_status catalog_scan_buffers(mtr_ctx *ctx)
-{
-    const size_t nr = (size_t)ctx->n_reads;
-    HIPCHK(ctx->d_ct_count.ensure(2 * nr * 4)); HIPCHK(ctx->d_ct_off.ensure(2 * (nr + 1) * 8)); HIPCHK(ctx->d_ct_status.ensure(4)); HIPCHK(ctx->d_ct_passed.ensure(8));
-    HIPCHK(hipMemsetAsync(ctx->d_ct_status, 0, 4, ctx->stream)); HIPCHK(hipMemsetAsync(ctx->d_ct_passed, 0, 8, ctx->stream));
-    return MTR_OK;
-}
-
-// The index built on the host and sent up: the entries (code, locus * 4 + slot) sorted and made distinct, a table slot per distinct code, the
-// filter over the codes, the slots' masks (ctx->d_ct_masks) and lengths; the reads' count and offset buffers sized, the status and the filter's
-// count zeroed.  The copies are synchronous.
-static mtr_status catalog_index(mtr_ctx *ctx, const std::vector<std::vector<uint8_t>> &pat, int seeds, int q, CatIndex &o)
-{
-    const size_t S = pat.size();
-    std::vector<std::pair<uint32_t, int32_t>> ent;
-    ent.reserve(S * (size_t)seeds);
-    std::vector<uint64_t> masks(S * FL_MASKS); std::vector<int32_t> plen(S);
-    for (size_t slot = 0; slot < S; slot++) {
-        const int m = (int)pat[slot].size();
-        for (int i = 0; i < seeds; i++) ent.push_back({ si_seed_code(pat[slot].data() + si_seed_offset(i, q), q), (int32_t)slot });
-        flank_slot_masks(pat[slot], masks.data() + slot * FL_MASKS);
-        plen[slot] = m;
-        (flank_is_wide(ctx, m) ? o.wide : o.narrow) = true;
-    }
-    std::sort(ent.begin(), ent.end());
-    ent.erase(std::unique(ent.begin(), ent.end()), ent.end());
-    const size_t E = ent.size();
-    size_t distinct = 0;
-    for (size_t e = 0; e < E; e++) distinct += e == 0 || ent[e].first != ent[e - 1].first;
-    uint32_t cap = 64; while ((size_t)cap < 2 * distinct) cap <<= 1;
-    int fbits = CAT_FILTER_MIN_BITS; while (fbits < CAT_FILTER_MAX_BITS && ((size_t)1 << fbits) < 16 * distinct) fbits++;
-    const size_t fwords = ((size_t)1 << fbits) / 32;
-    std::vector<uint32_t> ix(fwords + 3 * (size_t)cap + E + S, 0);                                     // filter | key | run | entries | plen
-    uint32_t *h_filter = ix.data(), *h_key = h_filter + fwords; int32_t *h_run = (int32_t *)(h_key + cap), *h_ent = h_run + 2 * (size_t)cap, *h_plen = h_ent + E;
-    for (size_t e = 0, first = 0; e < E; e++) {
-        h_ent[e] = ent[e].second;
-        if (e + 1 < E && ent[e + 1].first == ent[e].first) continue;
-        si_filter_set(h_filter, fbits, ent[e].first);
-        if (!si_insert(h_key, h_run, cap, ent[e].first, (int32_t)first, (int32_t)(e + 1 - first))) { ctx->err = "the seed table is full"; return MTR_ERR_HIP; }
-        first = e + 1;
-    }
-    std::copy(plen.begin(), plen.end(), h_plen);
-    HIPCHK(ctx->d_ct_ix.ensure(ix.size() * 4)); HIPCHK(ctx->d_ct_masks.ensure(masks.size() * 8));
-    HIPCHK(copy_sync(ctx, ctx->d_ct_ix, ix.data(), ix.size() * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_ct_masks, masks.data(), masks.size() * 8, hipMemcpyHostToDevice));
-    { mtr_status st = catalog_scan_buffers(ctx); if (st != MTR_OK) return st; }
-    o.d_masks = ctx->d_ct_masks;
-    o.E = E; o.distinct = distinct; o.fwords = fwords; o.cap = cap; o.fbits = fbits;
-    o.d_filter = (const uint32_t *)(int32_t *)ctx->d_ct_ix; o.d_key = o.d_filter + fwords;
-    o.d_run = (const int32_t *)(o.d_key + cap); o.d_ent = o.d_run + 2 * (size_t)cap; o.d_plen = o.d_ent + E;
-    return MTR_OK;
-}
-
-// The scan's first pass: sa filled in, the reads' hits counted (d_ct_count's first half), their offsets (d_ct_off's), and one look at the device: *H
-static mtr_status catalog_scan_count(mtr_ctx *ctx, const CatIndex &ix, int q, CatScanArgs &sa, int64_t *H)
-{
-    const int n = ctx->n_reads;
-    int32_t *hit_count = ctx->d_ct_count; int64_t *hit_off = ctx->d_ct_off;
-    sa.b.packed = ctx->d_packed; sa.b.woff = ctx->d_woff; sa.b.lens = ctx->d_lens; sa.b.order = nullptr; sa.b.n_reads = n;
-    sa.ix = { ix.d_filter, ix.fbits, ix.d_key, ix.d_run, ix.cap }; sa.ent = ix.d_ent; sa.q = q; sa.fill = 0;
-    sa.hit_count = hit_count; sa.hit_off = hit_off; sa.hits = nullptr; sa.passed = ctx->d_ct_passed;
-    hipLaunchKernelGGL(mtr_k_cat_scan, dim3((unsigned)n), dim3(64), 0, ctx->stream, sa);
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)hit_count, (int64_t)n, hit_off);
-    HIPCHK(hipGetLastError());
-    HIPCHK(copy_sync(ctx, H, hit_off + (size_t)n, 8, hipMemcpyDeviceToHost));
-    if (*H < 0 || *H >= (int64_t)INT32_MAX) { ctx->err = "2^31 - 1 seed hits or more (a read's count saturates there)"; return MTR_ERR_OVERFLOW; }
-    return MTR_OK;
-}
-
-// The scan's second pass: the H > 0 hits into ctx->d_ct_hits (d_ct_head sized beside them), launched and not waited for
-static mtr_status catalog_scan_fill(mtr_ctx *ctx, CatScanArgs &sa, int64_t H)
-{
-    HIPCHK(ctx->d_ct_hits.ensure((size_t)H * 4)); HIPCHK(ctx->d_ct_head.ensure((size_t)H));
-    sa.fill = 1; sa.hits = ctx->d_ct_hits;
-    hipLaunchKernelGGL(mtr_k_cat_scan, dim3((unsigned)ctx->n_reads), dim3(64), 0, ctx->stream, sa);
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_genotype_catalog_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist, int32_t seed_len,
-                                                  int32_t gain, int32_t mismatch, int32_t indel, int64_t *out_rows, int64_t *out_candidates)
-{
-    if (!ctx || !out_rows || !out_candidates) return MTR_ERR_BAD_ARG;
-    *out_rows = 0; *out_candidates = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    ctx->gc_ready = false;                                                                             // whatever happens below, the rows kept before this call are gone
-    std::string mot; std::vector<int64_t> mot_off; std::vector<std::vector<uint8_t>> pat;
-    { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, mot, mot_off, pat); if (st != MTR_OK) return st; }
-    { mtr_status st = search_motifs_check_size(ctx, mot_off.data(), n_loci); if (st != MTR_OK) return st; }
-    { mtr_status st = catalog_check_seeds(ctx, pat, n_loci, max_flank_dist, seed_len); if (st != MTR_OK) return st; }
-    const int q = seed_len;
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    const auto t_start = std::chrono::steady_clock::now();
-    CatIndex ix;
-    { mtr_status st = catalog_index(ctx, pat, max_flank_dist + 1, q, ix); if (st != MTR_OK) return st; }
-    const double ms_index = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();    // the host's index and its upload (the copies are synchronous)
-    const CatMotifs cm = { &mot, &mot_off, nullptr };
-    return genotype_catalog_run(ctx, ix, cm, n_loci, max_flank_dist, q, gain, mismatch, indel, ms_index, out_rows, out_candidates);
-}
-
-// The catalogue genotype from the index on, whoever made it (ix, cm): the scan, the candidates, the rows kept in the context, the statistics
-static mtr_status genotype_catalog_run(mtr_ctx *ctx, const CatIndex &ix, const CatMotifs &cm, int32_t n_loci, int32_t max_flank_dist, int q, int32_t gain, int32_t mismatch,
-                                       int32_t indel, double ms_index, int64_t *out_rows, int64_t *out_candidates)
-{
-    const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-    const int n = ctx->n_reads;
-    const size_t nr = (size_t)n;
-    const bool narrow = ix.narrow, wide = ix.wide;
-    const int32_t *d_plen = ix.d_plen;
-    int32_t *hit_count = ctx->d_ct_count, *cand_count = hit_count + nr;
-    int64_t *hit_off = ctx->d_ct_off, *cand_off = hit_off + nr + 1;
-    const dim3 per_read((unsigned)n), b64(64), b256(256), one(1), b1024(1024);
-    // the scan: the reads' hits counted, then written
-    const auto t_scan = std::chrono::steady_clock::now();
-    CatScanArgs sa{};
-    int64_t H = 0, Cn = 0, R = 0;
-    { mtr_status st = catalog_scan_count(ctx, ix, q, sa, &H); if (st != MTR_OK) return st; }
-    const double ms_scan = ms_since(t_scan);                           // the first scan pass and the offsets, up to the look that ends them
-    const auto t_rest = std::chrono::steady_clock::now();
-    unsigned long long passed = 0;
-    HIPCHK(copy_sync(ctx, &passed, ctx->d_ct_passed, 8, hipMemcpyDeviceToHost));
-    {
-        DBG("genotype_catalog: %zu entries of %zu codes, table of %u slots, filter of 2^%d bits; the filter passed %llu positions, %lld hits", ix.E, ix.distinct, ix.cap, ix.fbits, passed, (long long)H);
-    }
-    if (H > 0) {
-        { mtr_status st = catalog_scan_fill(ctx, sa, H); if (st != MTR_OK) return st; }
-        CatCandArgs ca{};
-        ca.n_reads = n; ca.fill = 0; ca.hit_off = hit_off; ca.hits = ctx->d_ct_hits; ca.head = ctx->d_ct_head; ca.cand_count = cand_count; ca.cand_off = cand_off;
-        hipLaunchKernelGGL(mtr_k_cat_cands, per_read, b64, 0, ctx->stream, ca);
-        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)cand_count, (int64_t)n, cand_off);
-        HIPCHK(hipGetLastError());
-        HIPCHK(copy_sync(ctx, &Cn, cand_off + nr, 8, hipMemcpyDeviceToHost));
-        if (Cn < 0 || Cn > H) { ctx->err = "the catalogue's candidate lists are inconsistent"; return MTR_ERR_HIP; }
-        if (Cn > (int64_t)INT32_MAX / 2) { ctx->err = std::to_string(Cn) + " candidates are more than 2^30 - 1"; return MTR_ERR_OVERFLOW; }
-        if (Cn > 0) {
-            const size_t nc = (size_t)Cn;
-            HIPCHK(ctx->d_ct_cand.ensure(3 * nc * 4)); HIPCHK(ctx->d_ct_flank.ensure(2 * nc * FL_RES * 4)); HIPCHK(ctx->d_ct_rowoff.ensure((nc + 1) * 8));
-            int32_t *cand_read = ctx->d_ct_cand, *cand_key = cand_read + nc, *span = cand_key + nc;
-            int64_t *row_off = ctx->d_ct_rowoff;
-            ca.fill = 1; ca.cand_read = cand_read; ca.cand_key = cand_key;
-            hipLaunchKernelGGL(mtr_k_cat_cands, per_read, b64, 0, ctx->stream, ca);
-            // the candidates' two flank scans each
-            CatFlankArgs fa{};
-            fa.b = sa.b; fa.cand_read = cand_read; fa.cand_key = cand_key; fa.n_tasks = (int32_t)(2 * Cn);
-            fa.masks = ix.d_masks; fa.plen = d_plen; fa.all_wide = ctx->sw.flank_word == 64; fa.res = ctx->d_ct_flank; fa.status = ctx->d_ct_status;
-            const dim3 per_task((unsigned)((2 * nc + 63) / 64));
-            if (narrow) hipLaunchKernelGGL(mtr_k_cat_flank<uint32_t>, per_task, b64, 0, ctx->stream, fa);
-            if (wide) hipLaunchKernelGGL(mtr_k_cat_flank<uint64_t>, per_task, b64, 0, ctx->stream, fa);
-            // the pairing, and the rows' places
-            HIPCHK(ctx->d_gt_state.ensure(LOCI_STATE * 4)); HIPCHK(ctx->d_gt_pair.ensure(nc * GT_PAIR * 4)); HIPCHK(ctx->d_gt_iv.ensure(nc * sizeof(LociIv)));
-            HIPCHK(hipMemsetAsync(ctx->d_gt_state, 0, LOCI_STATE * 4, ctx->stream));
-            const dim3 per_cand((unsigned)((nc + 255) / 256));
-            const CatPairArgs pa = { cand_read, cand_key, (int32_t)Cn, ctx->d_ct_flank, n_loci, max_flank_dist, ctx->d_gt_pair, span, ctx->d_gt_iv, (int32_t)Cn, ctx->d_gt_state };
-            hipLaunchKernelGGL(mtr_k_cat_pair, per_cand, b256, 0, ctx->stream, pa);
-            hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)span, Cn, row_off);
-            HIPCHK(hipGetLastError());
-            int32_t st[LOCI_STATE], dev = 0;
-            HIPCHK(copy_sync(ctx, st, ctx->d_gt_state, sizeof st, hipMemcpyDeviceToHost));
-            HIPCHK(copy_sync(ctx, &dev, ctx->d_ct_status, 4, hipMemcpyDeviceToHost));
-            HIPCHK(copy_sync(ctx, &R, row_off + nc, 8, hipMemcpyDeviceToHost));
-            const int64_t N = st[LOCI_NEXT];
-            const int max_len = st[LOCI_MAXLEN];
-            if (dev != DEV_OK) { ctx->err = "the catalogue's flank scans failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
-            if (st[LOCI_STATUS] != DEV_OK || R < 0 || R > Cn || N < 0 || N > R || max_len < 0 || max_len > ctx->Lmax || (N > 0) != (max_len > 0)) {
-                ctx->err = "the catalogue's pairing failed on the device (status " + std::to_string(st[LOCI_STATUS]) + ")"; return MTR_ERR_HIP;
-            }
-            if (N > 0) {
-                const mtr_status r = cm.cat ? genotype_align_tables(ctx, catalog_gt_tables(cm.cat), n_loci, N, max_len, gain, mismatch, indel, "genotype_catalog")
-                                            : genotype_align(ctx, *cm.mot, *cm.mot_off, n_loci, N, max_len, gain, mismatch, indel, "genotype_catalog");
-                if (r != MTR_OK) return r;
-            }
-            if (R > 0) {
-                const size_t rr = (size_t)R;
-                HIPCHK(ctx->d_gc_read.ensure(rr * 4)); HIPCHK(ctx->d_gc_locus.ensure(rr * 4)); HIPCHK(ctx->d_gc_spanning.ensure(rr)); HIPCHK(ctx->d_gc_orientation.ensure(rr));
-                HIPCHK(ctx->d_gc_fdist.ensure(rr * 8)); HIPCHK(ctx->d_gc_window.ensure(rr * 8)); HIPCHK(ctx->d_gc_fields.ensure(rr * 32)); HIPCHK(ctx->d_gc_score.ensure(rr * 4));
-                HIPCHK(ctx->d_gc_ratio.ensure(rr * 4));
-                const CatRowsOut out = { ctx->d_gc_read, ctx->d_gc_locus, { ctx->d_gc_spanning, ctx->d_gc_orientation, ctx->d_gc_fdist, ctx->d_gc_window, ctx->d_gc_fields, ctx->d_gc_score, ctx->d_gc_ratio } };
-                hipLaunchKernelGGL(mtr_k_cat_out, per_cand, b256, 0, ctx->stream, (const int32_t *)cand_read, (const int32_t *)cand_key, (const int32_t *)ctx->d_gt_pair,
-                                   (const int32_t *)span, (const int64_t *)row_off, (const int32_t *)ctx->d_gt_res, (int32_t)Cn, out);
-                HIPCHK(hipGetLastError());
-            }
-        }
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->gc_ready = true; ctx->gc_rows = R;
-    int64_t positions = 0;
-    for (int i = 0; i < n; i++) positions += std::max(0, ctx->lens[(size_t)i] - q + 1);
-    ctx->gc_counts[0] = positions; ctx->gc_counts[1] = (int64_t)passed; ctx->gc_counts[2] = H; ctx->gc_counts[3] = Cn;
-    ctx->gc_ms[0] = ms_index; ctx->gc_ms[1] = ms_scan; ctx->gc_ms[2] = ms_since(t_rest);
-    *out_rows = R; *out_candidates = Cn;
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_test_catalog_stats(mtr_ctx *ctx, int64_t *counts, double *ms)
-{
-    if (!ctx || !counts || !ms) return MTR_ERR_BAD_ARG;
-    if (!ctx->gc_ready) { ctx->err = "no catalogue call to report on"; return MTR_ERR_BAD_ARG; }
-    std::copy(ctx->gc_counts, ctx->gc_counts + 4, counts); std::copy(ctx->gc_ms, ctx->gc_ms + 3, ms);
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_genotype_catalog_copy_device(mtr_ctx *ctx, const mtr_catalog_dst *dst)
-{
-    if (!ctx) return MTR_ERR_BAD_ARG;
-    if (!ctx->gc_ready) { ctx->err = "no rows kept: mtr_genotype_catalog_device comes first (an upload discards what it kept)"; return MTR_ERR_BAD_ARG; }
-    if (!dst) { ctx->err = "dst is NULL"; return MTR_ERR_BAD_ARG; }
-    const int64_t R = ctx->gc_rows;
-    const mtr_genotypes_dst &g = dst->rows;
-    if (g.cap_rows < R) { ctx->err = "destination holds " + std::to_string(g.cap_rows) + " rows, " + std::to_string(R) + " needed"; return MTR_ERR_OVERFLOW; }
-    if (R > 0 && (!dst->read || !dst->locus || !g.spanning || !g.orientation || !g.flank_dist || !g.window || !g.fields || !g.score || !g.ratio)) {
-        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
-    }
-    if (R == 0) return MTR_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
-    const size_t r = (size_t)R;
-    HIPCHK(hipMemcpyAsync(dst->read, ctx->d_gc_read, r * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->locus, ctx->d_gc_locus, r * 4, dd, ctx->stream));
-    HIPCHK(hipMemcpyAsync(g.spanning, ctx->d_gc_spanning, r, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(g.orientation, ctx->d_gc_orientation, r, dd, ctx->stream));
-    HIPCHK(hipMemcpyAsync(g.flank_dist, ctx->d_gc_fdist, r * 8, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(g.window, ctx->d_gc_window, r * 8, dd, ctx->stream));
-    HIPCHK(hipMemcpyAsync(g.fields, ctx->d_gc_fields, r * 32, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(g.score, ctx->d_gc_score, r * 4, dd, ctx->stream));
-    HIPCHK(hipMemcpyAsync(g.ratio, ctx->d_gc_ratio, r * 4, dd, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
-
-// ---- partial genotype (partial.hip.inc) ------------------------------------------------------------------------------------------------
-// The genotype's checks and its flank step, the pairing and the choice of slot, one look at the device (the status and every variant's number
-// of tasks), one launch of the extension per bucket that has tasks, the columns.
-// the partial genotype's checks after the genotype's: a motif over 32 bases (naming the locus), then max_tail
-static mtr_status partial_check_args(mtr_ctx *ctx, const std::vector<int64_t> &mot_off, int32_t n_loci, int32_t max_tail)
-{
-    for (int32_t l = 0; l < n_loci; l++)
-        if (mot_off[(size_t)l + 1] - mot_off[(size_t)l] > MDP_MAX_U) {
-            ctx->err = "locus " + std::to_string(l) + ": a motif of " + std::to_string(mot_off[(size_t)l + 1] - mot_off[(size_t)l]) + " bases, the partial genotype takes at most " + std::to_string(MDP_MAX_U);
-            return MTR_ERR_BAD_ARG;
-        }
-    if (max_tail < 0) { ctx->err = "max_tail = " + std::to_string(max_tail) + ": at least 0"; return MTR_ERR_BAD_ARG; }
-    return MTR_OK;
-}
-
-// the variants of every locus: M, reversed M, rc M, reversed rc M at bits[4 * locus ..], as motif_ext takes them, and the motifs' lengths
-static void partial_variants(const std::string &mot, const std::vector<int64_t> &mot_off, int32_t n_loci, std::vector<uint64_t> &bits, std::vector<int32_t> &ulen)
-{
-    bits.assign((size_t)n_loci * 4, 0); ulen.assign((size_t)n_loci, 0);
-    for (int32_t l = 0; l < n_loci; l++) {
-        const int U = (int)(mot_off[(size_t)l + 1] - mot_off[(size_t)l]);
-        std::vector<uint8_t> c((size_t)U);
-        for (int t = 0; t < U; t++) { const char ch = mot[(size_t)mot_off[(size_t)l] + (size_t)t]; c[(size_t)t] = (uint8_t)(ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : 3); }
-        const std::vector<uint8_t> rc = revcomp_codes(c), rev(c.rbegin(), c.rend()), rrc(rc.rbegin(), rc.rend());
-        const std::vector<uint8_t> *four[4] = { &c, &rev, &rc, &rrc };
-        for (int k = 0; k < 4; k++) bits[(size_t)l * 4 + (size_t)k] = mdp_motif_bits(four[k]->data(), U);
-        ulen[(size_t)l] = U;
-    }
-}
-
-extern "C" mtr_status mtr_genotype_partial_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist,
-                                                  int32_t gain, int32_t mismatch, int32_t indel, int32_t max_tail, const mtr_partial_dst *dst, int64_t *out_rows)
-{
-    if (!ctx || !out_rows) return MTR_ERR_BAD_ARG;
-    *out_rows = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    std::string mot; std::vector<int64_t> mot_off; std::vector<std::vector<uint8_t>> pat;
-    { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, mot, mot_off, pat); if (st != MTR_OK) return st; }
-    { mtr_status st = partial_check_args(ctx, mot_off, n_loci, max_tail); if (st != MTR_OK) return st; }
-    const int n = ctx->n_reads;
-    const int64_t rows = (int64_t)n * n_loci;
-    *out_rows = rows;
-    if (!dst) return MTR_OK;
-    if (dst->cap_rows < rows) { ctx->err = "destination holds " + std::to_string(dst->cap_rows) + " rows, " + std::to_string(rows) + " needed"; return MTR_ERR_OVERFLOW; }
-    if (!dst->partial || !dst->slot || !dst->flank_dist || !dst->window || !dst->ext || !dst->ratio || !dst->open) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    { mtr_status st = flank_scan(ctx, pat); if (st != MTR_OK) return st; }
-    // the variants of every locus: M, reversed M, rc M, reversed rc M, as motif_ext takes them
-    const size_t V = (size_t)n_loci * 4, nl = (size_t)n_loci, nr = (size_t)n;
-    std::vector<uint64_t> bits; std::vector<int32_t> ulen;
-    partial_variants(mot, mot_off, n_loci, bits, ulen);
-    // device copies: d_pt_i32 = status | count | ulen | the work lists' variants, d_pt_i64 = bits | the work lists' firsts (a list per bucket)
-    HIPCHK(ctx->d_pt_i32.ensure((1 + 2 * V + nl) * 4)); HIPCHK(ctx->d_pt_i64.ensure((2 * V + 4) * 8));
-    HIPCHK(ctx->d_pt_row.ensure((size_t)rows * PT_ROW * 4)); HIPCHK(ctx->d_pt_ext.ensure((size_t)rows * PT_EXT * 4)); HIPCHK(ctx->d_pt_task.ensure(V * nr * sizeof(PtTask)));
-    int32_t *d_status = ctx->d_pt_i32, *d_count = d_status + 1, *d_ulen = d_count + V, *d_wslot = d_ulen + nl;
-    int64_t *d_bits = ctx->d_pt_i64, *d_wfirst = d_bits + V;
-    HIPCHK(hipMemsetAsync(d_status, 0, (1 + V) * 4, ctx->stream));
-    HIPCHK(copy_sync(ctx, d_ulen, ulen.data(), nl * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_bits, bits.data(), V * 8, hipMemcpyHostToDevice));
-    const dim3 per_row((unsigned)((rows + 255) / 256)), b256(256);
-    const PartialPairArgs pa = { ctx->d_fl_res, ctx->d_lens, n_loci, max_flank_dist, n, rows, ctx->d_pt_row, ctx->d_pt_task, d_count, d_status };
-    hipLaunchKernelGGL(mtr_k_partial_pair, per_row, b256, 0, ctx->stream, pa);
-    HIPCHK(hipGetLastError());
-    std::vector<int32_t> head(1 + V);
-    HIPCHK(copy_sync(ctx, head.data(), d_status, (1 + V) * 4, hipMemcpyDeviceToHost));
-    bool sane = head[0] == DEV_OK;
-    for (size_t v = 0; v < V; v++) sane = sane && head[1 + v] >= 0 && head[1 + v] <= n;
-    if (!sane) { ctx->err = "the partial genotype's pairing failed on the device (status " + std::to_string(head[0]) + ")"; return MTR_ERR_HIP; }
-    // a work list per bucket: entries (variant, first group) of the variants that have tasks
-    std::vector<int32_t> wslot; std::vector<int64_t> wfirst;
-    struct Launch { int ub; size_t slot_at, first_at; int32_t entries; int64_t groups; } launches[4];
-    int n_launch = 0;
-    for (int ub = 4; ub <= MDP_MAX_U; ub *= 2) {
-        Launch la = { ub, wslot.size(), wfirst.size(), 0, 0 };
-        for (size_t v = 0; v < V; v++)
-            if (head[1 + v] > 0 && mdp_bucket(ulen[v >> 2]) == ub) { wslot.push_back((int32_t)v); wfirst.push_back(la.groups); la.entries++; la.groups += ((int64_t)head[1 + v] + 63) / 64; }
-        wfirst.push_back(la.groups);
-        if (la.entries > 0) launches[n_launch++] = la;
-    }
-    if (n_launch > 0) {
-        HIPCHK(copy_sync(ctx, d_wslot, wslot.data(), wslot.size() * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_wfirst, wfirst.data(), wfirst.size() * 8, hipMemcpyHostToDevice));
-        PartialExtArgs a{};
-        a.b.packed = ctx->d_packed; a.b.woff = ctx->d_woff; a.b.lens = ctx->d_lens; a.b.order = nullptr; a.b.n_reads = n;
-        a.tasks = ctx->d_pt_task; a.count = d_count; a.bits = (const uint64_t *)d_bits; a.ulen = d_ulen;
-        a.n_reads = n; a.n_loci = n_loci; a.G = gain; a.MM = mismatch; a.D = indel; a.ext = ctx->d_pt_ext; a.status = d_status;
-        for (int k = 0; k < n_launch; k++) {
-            const Launch &la = launches[k];
-            a.work = { d_wslot + la.slot_at, d_wfirst + la.first_at, la.entries, la.groups };
-            DBG("partial genotype: bucket %d: %d variants, %lld groups", la.ub, la.entries, (long long)la.groups);
-            const dim3 grid((unsigned)la.groups), b64(64);
-            if (la.ub == 4) hipLaunchKernelGGL(mtr_k_ext_lanes<4>, grid, b64, 0, ctx->stream, a);
-            else if (la.ub == 8) hipLaunchKernelGGL(mtr_k_ext_lanes<8>, grid, b64, 0, ctx->stream, a);
-            else if (la.ub == 16) hipLaunchKernelGGL(mtr_k_ext_lanes<16>, grid, b64, 0, ctx->stream, a);
-            else hipLaunchKernelGGL(mtr_k_ext_lanes<32>, grid, b64, 0, ctx->stream, a);
-            HIPCHK(hipGetLastError());
-        }
-        // the status before the columns: a failed call writes nothing
-        int32_t dev = 0;
-        HIPCHK(copy_sync(ctx, &dev, d_status, 4, hipMemcpyDeviceToHost));
-        if (dev != DEV_OK) { ctx->err = "the partial genotype's extensions failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
-    }
-    const PartialOut out = { dst->partial, dst->slot, dst->flank_dist, dst->window, dst->ext, dst->ratio, dst->open };
-    hipLaunchKernelGGL(mtr_k_partial_out, per_row, b256, 0, ctx->stream, (const int32_t *)ctx->d_pt_row, (const int32_t *)ctx->d_pt_ext, (const int32_t *)d_ulen, n_loci, max_tail, rows, out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
-
-// ---- partial genotype at catalogue scale (partial_catalog.hip.inc) -----------------------------------------------------------------------
-// The genotype's checks, the partial genotype's, the catalogue's; the catalogue's index and scan (catalog_index, catalog_scan_*: one look at the
-// device for the hits); the candidates in two passes around a second look; their seeded slots as flank tasks (a third look: the tasks), the
-// scans, the pairing, a fourth look (the status, the buckets' tasks, the rows); one launch of the extension per bucket that has tasks and the
-// status again; the rows into the context's buffers.  Every buffer is sized by the reads, by the loci, or by what the scan found.
-extern "C" mtr_status mtr_genotype_partial_catalog_device(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist, int32_t seed_len,
-                                                          int32_t gain, int32_t mismatch, int32_t indel, int32_t max_tail, int64_t *out_rows, int64_t *out_candidates)
-{
-    if (!ctx || !out_rows || !out_candidates) return MTR_ERR_BAD_ARG;
-    *out_rows = 0; *out_candidates = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    ctx->pc_ready = false;                                                                             // whatever happens below, the rows kept before this call are gone
-    std::string mot; std::vector<int64_t> mot_off; std::vector<std::vector<uint8_t>> pat;
-    { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, mot, mot_off, pat); if (st != MTR_OK) return st; }
-    { mtr_status st = partial_check_args(ctx, mot_off, n_loci, max_tail); if (st != MTR_OK) return st; }
-    { mtr_status st = catalog_check_seeds(ctx, pat, n_loci, max_flank_dist, seed_len); if (st != MTR_OK) return st; }
-    const int q = seed_len;
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    const auto t_start = std::chrono::steady_clock::now();
-    CatIndex ix;
-    { mtr_status st = catalog_index(ctx, pat, max_flank_dist + 1, q, ix); if (st != MTR_OK) return st; }
-    const double ms_index = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();    // the host's index and its upload (the copies are synchronous)
-    const CatMotifs cm = { &mot, &mot_off, nullptr };
-    return genotype_partial_catalog_run(ctx, ix, cm, n_loci, max_flank_dist, q, gain, mismatch, indel, max_tail, ms_index, out_rows, out_candidates);
-}
-
-// The partial genotype at catalogue scale from the index on, whoever made it (ix, cm)
-static mtr_status genotype_partial_catalog_run(mtr_ctx *ctx, const CatIndex &ix, const CatMotifs &cm, int32_t n_loci, int32_t max_flank_dist, int q, int32_t gain,
-                                               int32_t mismatch, int32_t indel, int32_t max_tail, double ms_index, int64_t *out_rows, int64_t *out_candidates)
-{
-    const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-    const int n = ctx->n_reads;
-    const size_t nr = (size_t)n, nl = (size_t)n_loci;
-    int32_t *cand_count = ctx->d_ct_count + nr;
-    int64_t *hit_off = ctx->d_ct_off, *cand_off = hit_off + nr + 1;
-    const dim3 per_read((unsigned)n), b64(64), b256(256), one(1), b1024(1024);
-    const auto t_scan = std::chrono::steady_clock::now();
-    CatScanArgs sa{};
-    int64_t H = 0, Cn = 0, R = 0;
-    { mtr_status st = catalog_scan_count(ctx, ix, q, sa, &H); if (st != MTR_OK) return st; }
-    const double ms_scan = ms_since(t_scan);                           // the first scan pass and the offsets, up to the look that ends them
-    const auto t_rest = std::chrono::steady_clock::now();
-    unsigned long long passed = 0;
-    HIPCHK(copy_sync(ctx, &passed, ctx->d_ct_passed, 8, hipMemcpyDeviceToHost));
-    DBG("genotype_partial_catalog: %zu entries of %zu codes, the filter passed %llu positions, %lld hits", ix.E, ix.distinct, passed, (long long)H);
-    if (H > 0) {
-        { mtr_status st = catalog_scan_fill(ctx, sa, H); if (st != MTR_OK) return st; }
-        PtcCandArgs ca{};
-        ca.n_reads = n; ca.fill = 0; ca.hit_off = hit_off; ca.hits = ctx->d_ct_hits; ca.head = ctx->d_ct_head; ca.cand_count = cand_count; ca.cand_off = cand_off;
-        hipLaunchKernelGGL(mtr_k_ptc_cands, per_read, b64, 0, ctx->stream, ca);
-        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)cand_count, (int64_t)n, cand_off);
-        HIPCHK(hipGetLastError());
-        HIPCHK(copy_sync(ctx, &Cn, cand_off + nr, 8, hipMemcpyDeviceToHost));
-        if (Cn < 0 || Cn > H) { ctx->err = "the partial catalogue's candidate lists are inconsistent"; return MTR_ERR_HIP; }
-        if (Cn > (int64_t)INT32_MAX / 2) { ctx->err = std::to_string(Cn) + " candidates are more than 2^30 - 1"; return MTR_ERR_OVERFLOW; }
-    }
-    if (Cn > 0) {
-        const size_t nc = (size_t)Cn;
-        // the candidates, their seeded slots as flank tasks
-        HIPCHK(ctx->d_pc_cand.ensure(5 * nc * 4)); HIPCHK(ctx->d_pc_toff.ensure((nc + 1) * 8)); HIPCHK(ctx->d_ct_flank.ensure(PT_SLOTS * nc * FL_RES * 4));
-        HIPCHK(ctx->d_ct_rowoff.ensure((nc + 1) * 8));
-        int32_t *cand_read = ctx->d_pc_cand, *cand_locus = cand_read + nc, *cand_mask = cand_locus + nc, *cand_slots = cand_mask + nc, *is_row = cand_slots + nc;
-        int64_t *task_off = ctx->d_pc_toff, *row_off = ctx->d_ct_rowoff;
-        PtcCandArgs ca{};
-        ca.n_reads = n; ca.fill = 1; ca.hit_off = hit_off; ca.hits = ctx->d_ct_hits; ca.head = ctx->d_ct_head; ca.cand_count = cand_count; ca.cand_off = cand_off;
-        ca.cand_read = cand_read; ca.cand_locus = cand_locus; ca.cand_mask = cand_mask; ca.cand_slots = cand_slots;
-        hipLaunchKernelGGL(mtr_k_ptc_cands, per_read, b64, 0, ctx->stream, ca);
-        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)cand_slots, Cn, task_off);
-        HIPCHK(hipGetLastError());
-        int64_t F = 0;
-        HIPCHK(copy_sync(ctx, &F, task_off + nc, 8, hipMemcpyDeviceToHost));
-        if (F < Cn || F > PT_SLOTS * Cn || F > H) { ctx->err = "the partial catalogue's flank tasks are inconsistent"; return MTR_ERR_HIP; }
-        HIPCHK(ctx->d_pc_ftask.ensure((size_t)F * 4));
-        const dim3 per_cand((unsigned)((nc + 255) / 256));
-        const PtcTaskArgs ta = { cand_mask, task_off, (int32_t)Cn, ctx->d_pc_ftask, ctx->d_ct_flank };
-        hipLaunchKernelGGL(mtr_k_ptc_tasks, per_cand, b256, 0, ctx->stream, ta);
-        PtcFlankArgs fa{};
-        fa.b = sa.b; fa.cand_read = cand_read; fa.cand_locus = cand_locus; fa.n_cand = (int32_t)Cn; fa.tasks = ctx->d_pc_ftask; fa.n_tasks = (int32_t)F;
-        fa.masks = ix.d_masks; fa.plen = ix.d_plen; fa.all_wide = ctx->sw.flank_word == 64; fa.res = ctx->d_ct_flank; fa.status = ctx->d_ct_status;
-        const dim3 per_task((unsigned)(((size_t)F + 63) / 64));
-        if (ix.narrow) hipLaunchKernelGGL(mtr_k_ptc_flank<uint32_t>, per_task, b64, 0, ctx->stream, fa);
-        if (ix.wide) hipLaunchKernelGGL(mtr_k_ptc_flank<uint64_t>, per_task, b64, 0, ctx->stream, fa);
-        // the variants; d_pc_i32 = status | count[4] | ulen, d_pc_i64 = bits
-        // (a prepared catalogue brings its own bits and ulen; the text-taking call makes them here and keeps them behind its status words)
-        HIPCHK(ctx->d_pc_i32.ensure((1 + PTC_BUCKETS + nl) * 4));
-        HIPCHK(ctx->d_pc_row.ensure(nc * PT_ROW * 4)); HIPCHK(ctx->d_pc_ext.ensure(nc * PT_EXT * 4)); HIPCHK(ctx->d_pc_task.ensure(PTC_BUCKETS * nc * sizeof(PtTask)));
-        int32_t *d_status = ctx->d_pc_i32, *d_count = d_status + 1;
-        const int32_t *d_ulen = d_count + PTC_BUCKETS; const uint64_t *d_vbits = nullptr;
-        HIPCHK(hipMemsetAsync(d_status, 0, (1 + PTC_BUCKETS) * 4, ctx->stream));
-        if (cm.cat) { d_ulen = cm.cat->d_ulen; d_vbits = cm.cat->d_vbits; }
-        else {
-            std::vector<uint64_t> bits; std::vector<int32_t> ulen;
-            partial_variants(*cm.mot, *cm.mot_off, n_loci, bits, ulen);
-            HIPCHK(ctx->d_pc_i64.ensure(bits.size() * 8));
-            HIPCHK(copy_sync(ctx, d_count + PTC_BUCKETS, ulen.data(), nl * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_pc_i64, bits.data(), bits.size() * 8, hipMemcpyHostToDevice));
-            d_vbits = (const uint64_t *)(int64_t *)ctx->d_pc_i64;
-        }
-        // the pairing, and the rows' places
-        const PtcPairArgs pa = { cand_read, cand_locus, (int32_t)Cn, ctx->d_ct_flank, ctx->d_lens, d_ulen, max_flank_dist, ctx->d_pc_row, is_row, ctx->d_pc_task, d_count, d_status };
-        hipLaunchKernelGGL(mtr_k_ptc_pair, per_cand, b256, 0, ctx->stream, pa);
-        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)is_row, Cn, row_off);
-        HIPCHK(hipGetLastError());
-        int32_t head[1 + PTC_BUCKETS], dev = 0;
-        HIPCHK(copy_sync(ctx, head, d_status, sizeof head, hipMemcpyDeviceToHost));
-        HIPCHK(copy_sync(ctx, &dev, ctx->d_ct_status, 4, hipMemcpyDeviceToHost));
-        HIPCHK(copy_sync(ctx, &R, row_off + nc, 8, hipMemcpyDeviceToHost));
-        if (dev != DEV_OK) { ctx->err = "the partial catalogue's flank scans failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
-        bool sane = head[0] == DEV_OK && R >= 0 && R <= Cn;
-        int64_t tasks = 0;
-        for (int b = 0; b < PTC_BUCKETS; b++) { sane = sane && head[1 + b] >= 0 && head[1 + b] <= Cn; tasks += head[1 + b]; }
-        if (!sane || tasks > R) { ctx->err = "the partial catalogue's pairing failed on the device (status " + std::to_string(head[0]) + ")"; return MTR_ERR_HIP; }
-        if (tasks > 0) {
-            PtcExtArgs a{};
-            a.b = sa.b; a.cand_read = cand_read; a.tasks = ctx->d_pc_task; a.count = d_count; a.n_cand = (int32_t)Cn;
-            a.bits = d_vbits; a.ulen = d_ulen; a.G = gain; a.MM = mismatch; a.D = indel; a.ext = ctx->d_pc_ext; a.status = d_status;
-            for (int b = 0; b < PTC_BUCKETS; b++) {
-                if (head[1 + b] == 0) continue;
-                const dim3 grid((unsigned)((head[1 + b] + 63) / 64));
-                DBG("genotype_partial_catalog: bucket %d: %d tasks", 4 << b, head[1 + b]);
-                if (b == 0) hipLaunchKernelGGL(mtr_k_ptc_ext<4>, grid, b64, 0, ctx->stream, a);
-                else if (b == 1) hipLaunchKernelGGL(mtr_k_ptc_ext<8>, grid, b64, 0, ctx->stream, a);
-                else if (b == 2) hipLaunchKernelGGL(mtr_k_ptc_ext<16>, grid, b64, 0, ctx->stream, a);
-                else hipLaunchKernelGGL(mtr_k_ptc_ext<32>, grid, b64, 0, ctx->stream, a);
-                HIPCHK(hipGetLastError());
-            }
-            // the status before anything is kept
-            HIPCHK(copy_sync(ctx, &dev, d_status, 4, hipMemcpyDeviceToHost));
-            if (dev != DEV_OK) { ctx->err = "the partial catalogue's extensions failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
-        }
-        if (R > 0) {
-            const size_t rr = (size_t)R;
-            HIPCHK(ctx->d_pk_read.ensure(rr * 4)); HIPCHK(ctx->d_pk_locus.ensure(rr * 4)); HIPCHK(ctx->d_pk_partial.ensure(rr)); HIPCHK(ctx->d_pk_slot.ensure(rr));
-            HIPCHK(ctx->d_pk_fdist.ensure(rr * 4)); HIPCHK(ctx->d_pk_window.ensure(rr * 8)); HIPCHK(ctx->d_pk_ext.ensure(rr * 24)); HIPCHK(ctx->d_pk_ratio.ensure(rr * 4));
-            HIPCHK(ctx->d_pk_open.ensure(rr));
-            PtcOutArgs oa{};
-            oa.cand_read = cand_read; oa.cand_locus = cand_locus; oa.row = ctx->d_pc_row; oa.is_row = is_row; oa.row_off = row_off; oa.ext = ctx->d_pc_ext; oa.ulen = d_ulen;
-            oa.n_cand = (int32_t)Cn; oa.max_tail = max_tail;
-            oa.out = { ctx->d_pk_read, ctx->d_pk_locus, { ctx->d_pk_partial, ctx->d_pk_slot, ctx->d_pk_fdist, ctx->d_pk_window, ctx->d_pk_ext, ctx->d_pk_ratio, ctx->d_pk_open } };
-            hipLaunchKernelGGL(mtr_k_ptc_out, per_cand, b256, 0, ctx->stream, oa);
-            HIPCHK(hipGetLastError());
-        }
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->pc_ready = true; ctx->pc_rows = R;
-    int64_t positions = 0;
-    for (int i = 0; i < n; i++) positions += std::max(0, ctx->lens[(size_t)i] - q + 1);
-    ctx->pc_counts[0] = positions; ctx->pc_counts[1] = (int64_t)passed; ctx->pc_counts[2] = H; ctx->pc_counts[3] = Cn;
-    ctx->pc_ms[0] = ms_index; ctx->pc_ms[1] = ms_scan; ctx->pc_ms[2] = ms_since(t_rest);
-    *out_rows = R; *out_candidates = Cn;
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_test_partial_catalog_stats(mtr_ctx *ctx, int64_t *counts, double *ms)
-{
-    if (!ctx || !counts || !ms) return MTR_ERR_BAD_ARG;
-    if (!ctx->pc_ready) { ctx->err = "no partial catalogue call to report on"; return MTR_ERR_BAD_ARG; }
-    std::copy(ctx->pc_counts, ctx->pc_counts + 4, counts); std::copy(ctx->pc_ms, ctx->pc_ms + 3, ms);
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_genotype_partial_catalog_copy_device(mtr_ctx *ctx, const mtr_partial_catalog_dst *dst)
-{
-    if (!ctx) return MTR_ERR_BAD_ARG;
-    if (!ctx->pc_ready) { ctx->err = "no rows kept: mtr_genotype_partial_catalog_device comes first (an upload discards what it kept)"; return MTR_ERR_BAD_ARG; }
-    if (!dst) { ctx->err = "dst is NULL"; return MTR_ERR_BAD_ARG; }
-    const int64_t R = ctx->pc_rows;
-    const mtr_partial_dst &g = dst->rows;
-    if (g.cap_rows < R) { ctx->err = "destination holds " + std::to_string(g.cap_rows) + " rows, " + std::to_string(R) + " needed"; return MTR_ERR_OVERFLOW; }
-    if (R > 0 && (!dst->read || !dst->locus || !g.partial || !g.slot || !g.flank_dist || !g.window || !g.ext || !g.ratio || !g.open)) {
-        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
-    }
-    if (R == 0) return MTR_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
-    const size_t r = (size_t)R;
-    HIPCHK(hipMemcpyAsync(dst->read, ctx->d_pk_read, r * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->locus, ctx->d_pk_locus, r * 4, dd, ctx->stream));
-    HIPCHK(hipMemcpyAsync(g.partial, ctx->d_pk_partial, r, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(g.slot, ctx->d_pk_slot, r, dd, ctx->stream));
-    HIPCHK(hipMemcpyAsync(g.flank_dist, ctx->d_pk_fdist, r * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(g.window, ctx->d_pk_window, r * 8, dd, ctx->stream));
-    HIPCHK(hipMemcpyAsync(g.ext, ctx->d_pk_ext, r * 24, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(g.ratio, ctx->d_pk_ratio, r * 4, dd, ctx->stream));
-    HIPCHK(hipMemcpyAsync(g.open, ctx->d_pk_open, r, dd, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
-
-// ---- a prepared locus catalogue (catalog_build.hip.inc) ---------------------------------------------------------------------------------
-// mtr_catalog_create: one pass over seq_off on the host (the checks that lengths decide, the slots' and the motifs' lengths and offsets), one
-// upload of the letters and of those small arrays, the letters' check (a second look at the device: the first bad byte), then the build - the
-// slots, the sort's passes (count, scan, fill), the flags and their two scans, a third look (the entries, the distinct codes: they size the
-// catalogue's buffers), the compaction, the table, the motif tables - and the status.  The working buffers are freed when the call returns.
-// The two prepared calls are the text-taking calls from the index on (genotype_catalog_run, genotype_partial_catalog_run).
-static std::string catalog_flank_name(int64_t l, int side) { return "locus " + std::to_string(l) + ", " + (side ? "right" : "left") + " flank"; }
-
-extern "C" mtr_status mtr_catalog_create(mtr_ctx *ctx, const char *seqs, const int64_t *seq_off, int32_t n_loci, int32_t max_flank_dist, int32_t seed_len, mtr_catalog **out)
-{
-    if (!ctx || !out) return MTR_ERR_BAD_ARG;
-    *out = nullptr;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-    const auto t_host = std::chrono::steady_clock::now();
-    // genotype_check_args' checks that need no batch, in its order
-    if (n_loci <= 0) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
-    if (!seqs || !seq_off) { ctx->err = "seqs or seq_off is NULL"; return MTR_ERR_BAD_ARG; }
-    if (n_loci > INT32_MAX / 4) { ctx->err = "more than 2^29 - 1 loci"; return MTR_ERR_BAD_ARG; }
-    for (int32_t k = 0; k < 3 * n_loci; k++)
-        if (seq_off[k + 1] < seq_off[k]) { ctx->err = "seq_off decreases at locus " + std::to_string(k / 3) + " (sequence " + std::to_string(k % 3) + ")"; return MTR_ERR_BAD_ARG; }
-    // the pass over the lengths: the first refusal of a length among the motifs and among the flanks, as keys in the checks' order (the device
-    // adds the first bad byte, catb_bad_key: all motifs come before the first flank); the arrays that lengths decide
-    const size_t nl = (size_t)n_loci, S = nl * GT_SLOTS;
-    std::unique_ptr<mtr_catalog> cat(new mtr_catalog);
-    static std::atomic<uint64_t> next_id{ 1 };
-    cat->id = next_id.fetch_add(1);
-    cat->device = ctx->device; cat->n_loci = n_loci; cat->max_flank_dist = max_flank_dist; cat->seed_len = seed_len;
-    cat->mot_off.assign(nl + 1, 0); cat->unit_off.assign(2 * nl + 1, 0);
-    std::vector<int32_t> plen(S), ulen(nl);
-    std::vector<int64_t> off(3 * nl + 1);
-    const auto host_key = [](int is_flank, int64_t index) { return ((unsigned long long)is_flank << 62) | ((unsigned long long)index << 10); };
-    unsigned long long first_bad = CATB_NO_BAD_BYTE;
-    int64_t motif_bases = 0, units_at = 0;
-    for (size_t l = 0; l < nl; l++) {
-        const int64_t U = seq_off[3 * l + 2] - seq_off[3 * l + 1];
-        motif_bases += U;
-        cat->mot_off[l + 1] = motif_bases;
-        if (U < 1 || U >= MTRC_MAX_PERIOD) first_bad = std::min(first_bad, host_key(0, (int64_t)l));
-        if (U > MDP_MAX_U && cat->first_long_motif < 0) cat->first_long_motif = (int64_t)l;
-        ulen[l] = (int32_t)std::min<int64_t>(U, INT32_MAX);
-        const int64_t u = std::min<int64_t>(std::max<int64_t>(U, 0), MTRC_MAX_PERIOD);          // (a refused length is never built: the offsets only stay 32-bit)
-        cat->unit_off[2 * l] = (int32_t)units_at; cat->unit_off[2 * l + 1] = (int32_t)(units_at + u); units_at += 2 * u;
-        for (int side = 0; side < 2; side++) {
-            const int64_t m = seq_off[3 * l + 2 * (size_t)side + 1] - seq_off[3 * l + 2 * (size_t)side];
-            if (m < 1 || m > FBV_MAX_M) first_bad = std::min(first_bad, host_key(1, 2 * (int64_t)l + side));
-            const int32_t mm = (int32_t)std::min<int64_t>(m, INT32_MAX);
-            plen[l * GT_SLOTS + (size_t)side] = mm; plen[l * GT_SLOTS + 2 + (size_t)side] = mm;
-            (m <= 32 ? cat->n_short : cat->n_long) += 2;
-        }
-        for (int k = 0; k < 3; k++) off[3 * l + (size_t)k] = seq_off[3 * l + (size_t)k] - seq_off[0];
-    }
-    cat->unit_off[2 * nl] = (int32_t)units_at;
-    off[3 * nl] = seq_off[3 * nl] - seq_off[0];
-    if (motif_bases > INT32_MAX / 2) { ctx->err = "more than 2^30 - 1 motifs or motif bases"; return MTR_ERR_BAD_ARG; }
-    const int64_t n_bytes = off[3 * nl];
-    const double ms_host = ms_since(t_host);
-    // the uploads, and the letters' check
-    HIPCHK(hipSetDevice(ctx->device));
-    const auto t_up = std::chrono::steady_clock::now();
-    DevBuf<char> w_seqs; DevBuf<int64_t> w_off; DevBuf<unsigned long long> w_bad; DevBuf<int32_t> w_status;
-    HIPCHK(w_seqs.alloc((size_t)n_bytes + 16)); HIPCHK(w_off.alloc((3 * nl + 1) * 8)); HIPCHK(w_bad.alloc(8)); HIPCHK(w_status.alloc(4));
-    HIPCHK(cat->d_plen.alloc(S * 4)); HIPCHK(cat->d_uoff.alloc((2 * nl + 1) * 4)); HIPCHK(cat->d_ulen.alloc(nl * 4));
-    if (n_bytes > 0) HIPCHK(copy_sync(ctx, w_seqs, seqs + seq_off[0], (size_t)n_bytes, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, w_off, off.data(), (3 * nl + 1) * 8, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, cat->d_plen, plen.data(), S * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, cat->d_uoff, cat->unit_off.data(), (2 * nl + 1) * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, cat->d_ulen, ulen.data(), nl * 4, hipMemcpyHostToDevice));
-    const double ms_upload = ms_since(t_up);
-    const auto t_build = std::chrono::steady_clock::now();
-    const CatbSrc src = { w_seqs, w_off, n_loci };
-    const dim3 b64(64), b256(256), one(1), b1024(1024);
-    HIPCHK(hipMemsetAsync(w_bad, 0xFF, 8, ctx->stream)); HIPCHK(hipMemsetAsync(w_status, 0, 4, ctx->stream));
-    hipLaunchKernelGGL(mtr_k_catb_check, dim3((unsigned)((3 * nl + 255) / 256)), b256, 0, ctx->stream, src, (unsigned long long *)w_bad);
-    HIPCHK(hipGetLastError());
-    unsigned long long dev_bad = CATB_NO_BAD_BYTE;
-    HIPCHK(copy_sync(ctx, &dev_bad, w_bad, 8, hipMemcpyDeviceToHost));
-    first_bad = std::min(first_bad, dev_bad);
-    if (first_bad != CATB_NO_BAD_BYTE) {
-        const bool is_flank = (first_bad >> 62) & 1;
-        const int64_t index = (int64_t)((first_bad >> 10) & (((unsigned long long)1 << 52) - 1)), t = (int64_t)(first_bad & 1023) - 1;
-        const size_t k = is_flank ? 3 * (size_t)(index / 2) + 2 * (size_t)(index % 2) : 3 * (size_t)index + 1;
-        const int64_t len = seq_off[k + 1] - seq_off[k];
-        const std::string what = is_flank ? catalog_flank_name(index / 2, (int)(index % 2)) : "motif " + std::to_string(index);
-        if (t < 0) ctx->err = what + ": length " + std::to_string(len) + " outside 1.." + std::to_string(is_flank ? FBV_MAX_M : MTRC_MAX_PERIOD - 1);
-        else if (t >= len) { ctx->err = "the catalogue's check of the letters failed on the device"; return MTR_ERR_HIP; }
-        else ctx->err = what + ": byte " + std::to_string((int)(unsigned char)seqs[seq_off[k] + t]) + " at " + std::to_string(t) + " is none of ACGT";
-        return MTR_ERR_BAD_ARG;
-    }
-    if (max_flank_dist < 0) { ctx->err = "max_flank_dist = " + std::to_string(max_flank_dist) + ": at least 0"; return MTR_ERR_BAD_ARG; }
-    // catalog_check_seeds, from the lengths
-    if (seed_len < SI_MIN_Q || seed_len > SI_MAX_Q) { ctx->err = "seed_len = " + std::to_string(seed_len) + " outside " + std::to_string(SI_MIN_Q) + ".." + std::to_string(SI_MAX_Q); return MTR_ERR_BAD_ARG; }
-    const int64_t need = ((int64_t)max_flank_dist + 1) * seed_len;
-    for (size_t l = 0; l < nl; l++)
-        for (int side = 0; side < 2; side++) {
-            const int32_t m = plen[l * GT_SLOTS + (size_t)side];
-            if ((int64_t)m < need) {
-                ctx->err = catalog_flank_name((int64_t)l, side) + ": " + std::to_string(m) + " bases are fewer than (max_flank_dist + 1) * seed_len = " + std::to_string(need);
-                return MTR_ERR_BAD_ARG;
-            }
-        }
-    // the build.  (need <= 64 from here on: every flank has at most 64 bases)
-    const int q = seed_len, seeds = max_flank_dist + 1;
-    const int64_t E0 = (int64_t)S * seeds;
-    if (E0 > (int64_t)INT32_MAX) { ctx->err = std::to_string(S) + " slots x " + std::to_string(seeds) + " seeds are more than 2^31 - 1 entries"; return MTR_ERR_OVERFLOW; }
-    const size_t e0 = (size_t)E0;
-    const int n_tiles = (int)((e0 + CB_TILE - 1) / CB_TILE);
-    const size_t nh = (size_t)CB_DIGITS * (size_t)n_tiles;
-    DevBuf<uint32_t> w_keys[2], w_rkey; DevBuf<int32_t> w_vals[2], w_hist, w_keep, w_head, w_rfirst; DevBuf<int64_t> w_first, w_keepoff, w_headoff;
-    for (int k = 0; k < 2; k++) { HIPCHK(w_keys[k].alloc(e0 * 4)); HIPCHK(w_vals[k].alloc(e0 * 4)); }
-    HIPCHK(w_hist.alloc(nh * 4)); HIPCHK(w_first.alloc((nh + 1) * 8)); HIPCHK(w_keep.alloc(e0 * 4)); HIPCHK(w_head.alloc(e0 * 4));
-    HIPCHK(w_keepoff.alloc((e0 + 1) * 8)); HIPCHK(w_headoff.alloc((e0 + 1) * 8));
-    HIPCHK(cat->d_masks.alloc(S * FL_MASKS * 8));
-    const CatbSlotArgs sl = { src, cat->d_plen, q, seeds, cat->d_masks, w_keys[0], w_vals[0], w_status };
-    hipLaunchKernelGGL(mtr_k_catb_slots, dim3((unsigned)((S + 63) / 64)), b64, 0, ctx->stream, sl);
-    const int passes = cb_passes(q);
-    for (int p = 0; p < passes; p++) {
-        const int from = p & 1, to = from ^ 1;
-        hipLaunchKernelGGL(mtr_k_catb_count, dim3((unsigned)n_tiles), b64, 0, ctx->stream, (const uint32_t *)w_keys[from], (long long)E0, p, n_tiles, (int32_t *)w_hist);
-        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)w_hist, (int64_t)nh, (int64_t *)w_first);
-        const CatbFillArgs fa = { w_keys[from], w_vals[from], (long long)E0, p, n_tiles, w_first, w_keys[to], w_vals[to], w_status };
-        hipLaunchKernelGGL(mtr_k_catb_fill, dim3((unsigned)n_tiles), b64, 0, ctx->stream, fa);
-    }
-    const uint32_t *s_keys = w_keys[passes & 1]; const int32_t *s_vals = w_vals[passes & 1];
-    const dim3 per_entry((unsigned)((e0 + 255) / 256));
-    hipLaunchKernelGGL(mtr_k_catb_flags, per_entry, b256, 0, ctx->stream, s_keys, s_vals, (long long)E0, (int32_t *)w_keep, (int32_t *)w_head);
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)w_keep, E0, (int64_t *)w_keepoff);
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)w_head, E0, (int64_t *)w_headoff);
-    HIPCHK(hipGetLastError());
-    int64_t E = 0, distinct = 0; int32_t dev = 0;
-    HIPCHK(copy_sync(ctx, &E, (int64_t *)w_keepoff + e0, 8, hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(ctx, &distinct, (int64_t *)w_headoff + e0, 8, hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(ctx, &dev, w_status, 4, hipMemcpyDeviceToHost));
-    if (dev != DEV_OK || distinct < 1 || distinct > E || E > E0) { ctx->err = "the catalogue's sort failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
-    cat->E = (size_t)E; cat->distinct = (size_t)distinct;
-    cat->cap = cb_table_cap((uint64_t)distinct); cat->fbits = cb_filter_bits((uint64_t)distinct); cat->fwords = ((size_t)1 << cat->fbits) / 32;
-    const size_t cap = cat->cap;
-    HIPCHK(cat->d_filter.alloc(cat->fwords * 4)); HIPCHK(cat->d_key.alloc(cap * 4)); HIPCHK(cat->d_run.alloc(2 * cap * 4)); HIPCHK(cat->d_ent.alloc(cat->E * 4));
-    HIPCHK(w_rkey.alloc(cat->distinct * 4)); HIPCHK(w_rfirst.alloc((cat->distinct + 1) * 4));
-    HIPCHK(hipMemsetAsync(cat->d_filter, 0, cat->fwords * 4, ctx->stream)); HIPCHK(hipMemsetAsync(cat->d_key, 0, cap * 4, ctx->stream)); HIPCHK(hipMemsetAsync(cat->d_run, 0, 2 * cap * 4, ctx->stream));
-    const CatbCompactArgs co = { s_keys, s_vals, (long long)E0, w_keep, w_head, w_keepoff, w_headoff, (long long)E, (long long)distinct, cat->d_ent, w_rkey, w_rfirst, w_status };
-    hipLaunchKernelGGL(mtr_k_catb_compact, per_entry, b256, 0, ctx->stream, co);
-    const CatbTableArgs ta = { w_rkey, w_rfirst, (long long)distinct, cat->d_filter, cat->fbits, cat->d_key, cat->d_run, cat->cap, w_status };
-    hipLaunchKernelGGL(mtr_k_catb_table, dim3((unsigned)((cat->distinct + 255) / 256)), b256, 0, ctx->stream, ta);
-    // the motif tables
-    HIPCHK(cat->d_units.alloc((size_t)units_at + 16)); HIPCHK(cat->d_ubits.alloc(2 * nl * 8)); HIPCHK(cat->d_vbits.alloc(4 * nl * 8));
-    const CatbMotifArgs ma = { src, cat->d_ulen, cat->d_uoff, cat->d_units, cat->d_ubits, cat->d_vbits, w_status };
-    hipLaunchKernelGGL(mtr_k_catb_motifs, dim3((unsigned)((nl + 255) / 256)), b256, 0, ctx->stream, ma);
-    HIPCHK(hipGetLastError());
-    HIPCHK(copy_sync(ctx, &dev, w_status, 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (dev == CATB_ERR_TABLE_FULL) { ctx->err = "the seed table is full"; return MTR_ERR_HIP; }
-    if (dev != DEV_OK) { ctx->err = "the catalogue's build failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
-    DBG("catalog_create: %zu entries of %zu codes, table of %u slots, filter of 2^%d bits, %zu device bytes", cat->E, cat->distinct, cat->cap, cat->fbits, cat->device_bytes());
-    ctx->cb_ready = true; ctx->cb_ms[0] = ms_host; ctx->cb_ms[1] = ms_upload; ctx->cb_ms[2] = ms_since(t_build);
-    *out = cat.release();
-    return MTR_OK;
-}
-
-extern "C" void mtr_catalog_destroy(mtr_catalog *cat)
-{
-    if (!cat) return;
-    (void)hipSetDevice(cat->device);
-    delete cat;
-}
-
-extern "C" mtr_status mtr_catalog_info_get(const mtr_catalog *cat, mtr_catalog_info *info)
-{
-    if (!cat || !info) return MTR_ERR_BAD_ARG;
-    info->n_loci = cat->n_loci; info->max_flank_dist = cat->max_flank_dist; info->seed_len = cat->seed_len; info->filter_bits = cat->fbits;
-    info->entries = (int64_t)cat->E; info->distinct_codes = (int64_t)cat->distinct; info->table_slots = (int64_t)cat->cap;
-    info->first_long_motif = cat->first_long_motif; info->device_bytes = (int64_t)cat->device_bytes();
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_test_catalog_build_stats(mtr_ctx *ctx, double *ms)
-{
-    if (!ctx || !ms) return MTR_ERR_BAD_ARG;
-    if (!ctx->cb_ready) { ctx->err = "no mtr_catalog_create to report on"; return MTR_ERR_BAD_ARG; }
-    std::copy(ctx->cb_ms, ctx->cb_ms + 3, ms);
-    return MTR_OK;
-}
-
-// the prepared calls' checks that depend on the batch or the call, in their order; on MTR_OK the switches are read and ix points into cat
-static mtr_status catalog_prepared_begin(mtr_ctx *ctx, const mtr_catalog *cat, bool partial, int32_t gain, int32_t mismatch, int32_t indel, int32_t max_tail, CatIndex &ix)
-{
-    if (ctx->device != cat->device) { ctx->err = "the catalogue was built on device " + std::to_string(cat->device) + ", the context runs on device " + std::to_string(ctx->device); return MTR_ERR_BAD_ARG; }
-    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
-    const int n = ctx->n_reads; const int32_t n_loci = cat->n_loci;
-    const int64_t rows = (int64_t)n * n_loci;
-    if (rows > (int64_t)INT32_MAX) { ctx->err = std::to_string(n) + " reads x " + std::to_string(n_loci) + " motifs are more than 2^31 - 1 hits"; return MTR_ERR_BAD_ARG; }
-    if (2 * rows > (int64_t)INT32_MAX) { ctx->err = std::to_string(n) + " reads x " + std::to_string(n_loci) + " loci in two orientations are more than 2^31 - 1 pairs"; return MTR_ERR_BAD_ARG; }
-    if (!partial) { mtr_status st = search_motifs_check_size(ctx, cat->mot_off.data(), n_loci); if (st != MTR_OK) return st; }
-    if (gain < 1 || gain > 5) { ctx->err = "gain = " + std::to_string(gain) + " outside 1..5"; return MTR_ERR_BAD_ARG; }
-    if (mismatch < 1 || mismatch > 3) { ctx->err = "mismatch = " + std::to_string(mismatch) + " outside 1..3"; return MTR_ERR_BAD_ARG; }
-    if (indel < 1 || indel > 3) { ctx->err = "indel = " + std::to_string(indel) + " outside 1..3"; return MTR_ERR_BAD_ARG; }
-    if (partial) { mtr_status st = partial_check_args(ctx, cat->mot_off, n_loci, max_tail); if (st != MTR_OK) return st; }
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    { mtr_status st = catalog_scan_buffers(ctx); if (st != MTR_OK) return st; }
-    ix.E = cat->E; ix.distinct = cat->distinct; ix.fwords = cat->fwords; ix.cap = cat->cap; ix.fbits = cat->fbits;
-    ix.narrow = ctx->sw.flank_word != 64 && cat->n_short > 0; ix.wide = ctx->sw.flank_word == 64 || cat->n_long > 0;      // flank_is_wide over the slots' lengths
-    ix.d_filter = cat->d_filter; ix.d_key = cat->d_key; ix.d_run = cat->d_run; ix.d_ent = cat->d_ent; ix.d_plen = cat->d_plen; ix.d_masks = cat->d_masks;
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_genotype_catalog_prepared_device(mtr_ctx *ctx, const mtr_catalog *cat, int32_t gain, int32_t mismatch, int32_t indel, int64_t *out_rows,
-                                                           int64_t *out_candidates)
-{
-    if (!ctx || !out_rows || !out_candidates) return MTR_ERR_BAD_ARG;
-    *out_rows = 0; *out_candidates = 0;
-    if (!cat) { ctx->err = "cat is NULL"; return MTR_ERR_BAD_ARG; }
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    ctx->gc_ready = false;                                                                             // whatever happens below, the rows kept before this call are gone
-    CatIndex ix;
-    { mtr_status st = catalog_prepared_begin(ctx, cat, false, gain, mismatch, indel, 0, ix); if (st != MTR_OK) return st; }
-    const CatMotifs cm = { nullptr, nullptr, cat };
-    return genotype_catalog_run(ctx, ix, cm, cat->n_loci, cat->max_flank_dist, cat->seed_len, gain, mismatch, indel, 0.0, out_rows, out_candidates);
-}
-
-extern "C" mtr_status mtr_genotype_partial_catalog_prepared_device(mtr_ctx *ctx, const mtr_catalog *cat, int32_t gain, int32_t mismatch, int32_t indel, int32_t max_tail,
-                                                                   int64_t *out_rows, int64_t *out_candidates)
-{
-    if (!ctx || !out_rows || !out_candidates) return MTR_ERR_BAD_ARG;
-    *out_rows = 0; *out_candidates = 0;
-    if (!cat) { ctx->err = "cat is NULL"; return MTR_ERR_BAD_ARG; }
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    ctx->pc_ready = false;                                                                             // whatever happens below, the rows kept before this call are gone
-    CatIndex ix;
-    { mtr_status st = catalog_prepared_begin(ctx, cat, true, gain, mismatch, indel, max_tail, ix); if (st != MTR_OK) return st; }
-    const CatMotifs cm = { nullptr, nullptr, cat };
-    return genotype_partial_catalog_run(ctx, ix, cm, cat->n_loci, cat->max_flank_dist, cat->seed_len, gain, mismatch, indel, max_tail, 0.0, out_rows, out_candidates);
-}
-
-extern "C" mtr_status mtr_test_catalog_dump(mtr_ctx *ctx, const mtr_catalog *cat, mtr_catalog_dump *out)
-{
-    if (!ctx || !cat || !out) return MTR_ERR_BAD_ARG;
-    if (ctx->device != cat->device) { ctx->err = "the catalogue was built on device " + std::to_string(cat->device) + ", the context runs on device " + std::to_string(ctx->device); return MTR_ERR_BAD_ARG; }
-    memset(out, 0, sizeof *out);
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t nl = (size_t)cat->n_loci, S = nl * GT_SLOTS, cap = cat->cap, ub = (size_t)cat->unit_off[2 * nl];
-    const struct { const void *d; size_t bytes; } src[11] = {
-        { cat->d_filter, cat->fwords * 4 }, { cat->d_key, cap * 4 }, { cat->d_run, 2 * cap * 4 }, { cat->d_ent, cat->E * 4 }, { cat->d_plen, S * 4 }, { cat->d_masks, S * FL_MASKS * 8 },
-        { cat->d_units, ub }, { cat->d_uoff, (2 * nl + 1) * 4 }, { cat->d_ubits, 2 * nl * 8 }, { cat->d_vbits, 4 * nl * 8 }, { cat->d_ulen, nl * 4 } };
-    std::unique_ptr<void, FreeDeleter> h[11];
-    for (int k = 0; k < 11; k++) {
-        h[k].reset(malloc(std::max<size_t>(src[k].bytes, 1)));
-        if (!h[k]) { ctx->err = "out of host memory"; return MTR_ERR_OOM; }
-        if (src[k].bytes > 0) HIPCHK(copy_sync(ctx, h[k].get(), src[k].d, src[k].bytes, hipMemcpyDeviceToHost));
-    }
-    out->filter_words = (int64_t)cat->fwords; out->table_slots = (int64_t)cap; out->entries = (int64_t)cat->E; out->n_slots = (int64_t)S; out->unit_bytes = (int64_t)ub; out->n_loci = cat->n_loci;
-    out->filter = (uint32_t *)h[0].release(); out->key = (uint32_t *)h[1].release(); out->run = (int32_t *)h[2].release(); out->ent = (int32_t *)h[3].release();
-    out->plen = (int32_t *)h[4].release(); out->masks = (uint64_t *)h[5].release(); out->units = (uint8_t *)h[6].release(); out->unit_off = (int32_t *)h[7].release();
-    out->unit_bits = (uint64_t *)h[8].release(); out->variant_bits = (uint64_t *)h[9].release(); out->ulen = (int32_t *)h[10].release();
-    return MTR_OK;
-}
+#include "genotype_host.hip.inc"
 
 // ---- allele calls (allele_call.hip.inc) ------------------------------------------------------------------------------------------------
 // The arguments' checks, the count and the offsets, one look at the device (the status, S, the tiles), then the fill, the rank and the split

@@ -843,6 +843,64 @@ typedef struct mtr_consensus_dst {
 mtr_status mtr_allele_consensus_device(mtr_ctx *ctx, const mtr_consensus_src *src, int32_t band_extra, void *wait_stream,
                                        const mtr_consensus_dst *dst, int64_t *out_bases);
 
+/* ---- window structure: compound loci counted segment by segment ---------------------------------------------------------------------------------
+ * A genotype row's `copies` is one count for one motif, taken from a LOCAL alignment; a compound locus - HTT's (CAG)n CAACAG CCGCCA (CCG)m - and
+ * the interruptions a consensus carries need the GLOBAL alignment of an oriented window to an ORDERED LIST of motifs, each repeated zero or more
+ * whole times, reported per segment.  The reference has nothing of this kind; the definition is this project's own.  It applies unchanged to the
+ * windows of mtr_extract_windows_device and to the sequences of mtr_allele_consensus_device: both are off [N + 1], bases [T], codes 0..3.
+ * The definition:
+ *   structure   motifs M_0 .. M_{S-1} over ACGT, 1 <= S <= MTR_WS_MAX_SEGMENTS = 4, U_s = |M_s| >= 1, W = sum U_s.  Limit: S <= 2 and W <= 32, or
+ *               S <= 4 and W <= 16 (the per-segment counters are 16-bit fields: two fit one register, four a register pair, and a cell is
+ *               carried in registers, one DP per lane).  The columns are flat, c = 0 .. W-1; seg(c), first(s) and last(s) name a column's
+ *               segment and a segment's end columns; m[c] is the motif base of column c.  A state START stands for "no motif base consumed yet"
+ *   window      y[0 .. n), codes 0..3, n <= MTR_WS_MAX_WINDOW = 16384.  Scores G (gain), MM (mismatch), D (indel) in the search's ranges
+ *   predecessors of a column, in this order: for c != first(seg(c)): [c - 1]; for c = first(s): [last(s-1), last(s-2), .., last(0), START,
+ *               last(s)] - the segment's own wrap comes last
+ *   cells       rows i = 0 .. n.  H(i, START) = -D * i.  For a column c, H(i, c) is the largest of these candidates: sub (i >= 1), for each
+ *               predecessor p in order: H(i-1, p) + (G if y[i-1] == m[c] else -MM); up (i >= 1): H(i-1, c) - D; left, for each predecessor p in
+ *               order: H(i, p) - D.  Row 0 has left only.  The cell's predecessor is the FIRST candidate in that order (subs, then up, then
+ *               lefts) that attains the maximum.  A cell with no finite candidate is minus infinity
+ *   fixpoint    the lefts make a row cyclic through the wrap, and H is the fixpoint.  Two sweeps reach it: sweep 1 computes the row without the
+ *               wrap's left; sweep 2, per segment: if H(i, last(s)) - D is STRICTLY greater than H(i, first(s)) it replaces it, and the
+ *               improvement runs on by lefts while it stays strictly greater.  Once round a segment by lefts costs U_s * D > 0, so sweep 2 never
+ *               changes last(s) and needs no third sweep.  The wrap is the last left candidate and subs and up come before lefts, so "strictly
+ *               greater" is exactly the priority rule
+ *   carried     with a cell, from its predecessor: copies[s], plus 1 when a sub or left lands on last(s); matches[s], plus 1 on a matching sub
+ *               in segment s; entry[s], set when a step lands on first(s) from any predecessor other than last(s): to i - 1 for a sub, to i for
+ *               a left.  A copy made only of lefts strictly loses, so every count is at most n <= 16384 and fits 16 bits
+ *   end         the best of H(n, e) over e in [last(S-1), .., last(0), START], the first in that order that attains the maximum.  Only whole
+ *               copies exist: a segment is entered at first and left from last
+ * Columns per window w: seg [N * 4 * 4] = start, end, copies, matches per segment - going from s = S-1 down with nxt = n, a segment with copies >
+ * 0 spans [entry[s], nxt) and sets nxt = entry[s]; a segment with no copies is (nxt, nxt, 0, 0); segments >= S are zeros; bases before the first
+ * used segment belong to none.  score [N] = H of the end.  ratio [N] = float(sum matches) / n, or 0 for n == 0.  skipped [N] = 1 for n >
+ * MTR_WS_MAX_WINDOW; such a window is zeros elsewhere.  n == 0 is score 0, all zeros, and no DP.  Every output but ratio is an exact integer,
+ * and none depends on where or in which order the device worked.
+ *
+ * mtr_window_structure_device: motifs, motif_off and struct_off [n_structs + 1] are HOST arrays: structure k is motifs struct_off[k] ..
+ * struct_off[k + 1], motif j the bytes motifs[motif_off[j] .. motif_off[j + 1]).  win_off [n_windows + 1], win_bases [n_bases] and win_struct
+ * [n_windows] (int32, the window's structure) are DEVICE columns.  The call needs no uploaded batch and touches nothing a batch, a run or another
+ * call keeps; its buffers are its own.  Checked in this order, each MTR_ERR_BAD_ARG with mtr_last_error naming the offender: a NULL ctx; NULL
+ * motifs, motif_off or struct_off; a NULL device column that would be read, a NULL dst or destination column (with n_windows > 0); n_structs
+ * outside 1..2^24, n_windows outside 0..2^31 - 1, n_bases negative; the scores (gain 1..5, mismatch and indel 1..3); struct_off, then motif_off,
+ * decreasing; then, each over all structures before the next: a structure of 0 or more than 4 motifs, a motif of length 0, the column limit, a
+ * byte that is none of ACGT; a device column that is not memory of the context's GPU or runs past its allocation; then on the device, the
+ * smallest offender of each kind: win_off not ascending from 0 to n_bases, a win_struct outside 0 .. n_structs - 1, a base code above 3.  Then
+ * cap_windows < n_windows: MTR_ERR_OVERFLOW.  Else the columns are written and the context's stream synchronised before the call returns.  A
+ * failed call writes nothing into dst.  wait_stream is the stream that wrote the columns, handled as mtr_upload_batch_device handles it.
+ * MTR_ABI_VERSION is unchanged by this entry: look for it by symbol. */
+#define MTR_WS_MAX_SEGMENTS 4
+#define MTR_WS_MAX_WINDOW 16384
+typedef struct mtr_window_structure_dst {
+    int32_t *seg;           /* [n_windows * 4 * 4]: start, end, copies, matches per segment */
+    int32_t *score;         /* [n_windows] */
+    float   *ratio;         /* [n_windows] */
+    uint8_t *skipped;       /* [n_windows] */
+    int64_t  cap_windows;
+} mtr_window_structure_dst;   /* caller-owned DEVICE memory */
+mtr_status mtr_window_structure_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, const int32_t *struct_off, int32_t n_structs,
+                                       const int64_t *win_off, const uint8_t *win_bases, const int32_t *win_struct, int64_t n_windows, int64_t n_bases,
+                                       int32_t gain, int32_t mismatch, int32_t indel, void *wait_stream, const mtr_window_structure_dst *dst);
+
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left
  * of handle_one_file.c:281-287's loop across GPUs is ONE exchange: the record tables travel to the process that chains and

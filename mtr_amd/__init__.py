@@ -58,7 +58,8 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_call_alleles_rows_device", "mtr_test_catalog_stats", "mtr_genotype_partial_catalog_device", "mtr_genotype_partial_catalog_copy_device",
            "mtr_test_partial_catalog_stats", "mtr_catalog_create", "mtr_catalog_destroy", "mtr_catalog_info_get", "mtr_genotype_catalog_prepared_device",
            "mtr_genotype_partial_catalog_prepared_device", "mtr_test_catalog_dump", "mtr_test_catalog_build_stats",
-           "mtr_extract_windows_device", "mtr_allele_consensus_device"]
+           "mtr_extract_windows_device", "mtr_allele_consensus_device", "mtr_window_structure_device"]
+WS_MAX_SEGMENTS, WS_MAX_WINDOW = 4, 16384    # MTR_WS_*: the limits of Engine.window_structure
 CONS_MAX_WINDOW, CONS_MAX_BAND, CONS_INS_SLOTS, CONS_MAX_EXTRA = 16384, 256, 4, 64      # MTR_CONS_*: the limits of Engine.allele_consensus
 ALLELE_COPIES, ALLELE_BASES = 0, 1           # MTR_ALLELE_COPIES, MTR_ALLELE_BASES: the measure of Engine.call_alleles
 ALIGN_WIDTH = 50                             # MTRH_ALIGN_WIDTH: alignment columns per printed block
@@ -481,6 +482,19 @@ class AlleleConsensus(NamedTuple):
     skipped: "object"        # int32 [2m]: the members left out (a window or a band beyond the limits)
 
 
+class CWindowStructureDst(C.Structure):
+    """mtr_window_structure_dst: device pointers of the window structure's columns and their capacity"""
+    _fields_ = [("seg", C.c_void_p), ("score", C.c_void_p), ("ratio", C.c_void_p), ("skipped", C.c_void_p), ("cap_windows", C.c_int64)]
+
+
+class WindowStructure(NamedTuple):
+    """What Engine.window_structure found: one row per window, all on the engine's device.  include/mtr_hip.h defines every column."""
+    seg: "object"      # int32 [N, 4, 4]: per segment start, end, copies, matches; a segment without copies is empty at the next one's start
+    score: "object"    # int32 [N]
+    ratio: "object"    # float32 [N]: the matches of all segments over the window's length
+    skipped: "object"  # uint8 [N]: 1 = the window is longer than WS_MAX_WINDOW and every other column of the row is 0
+
+
 class CFastaInfo(C.Structure):
     """mtr_fasta_info: what a FASTA file in device memory holds"""
     _fields_ = [("n_reads", C.c_int32), ("end", C.c_int32), ("bad_char", C.c_int32), ("reserved", C.c_int32),
@@ -647,6 +661,10 @@ def load_library(path: str = LIB_PATH):
         lib.mtr_extract_windows_device.restype = C.c_int
         lib.mtr_allele_consensus_device.argtypes = [C.c_void_p, P(CConsensusSrc), C.c_int32, C.c_void_p, P(CConsensusDst), P(C.c_int64)]
         lib.mtr_allele_consensus_device.restype = C.c_int
+    if hasattr(lib, "mtr_window_structure_device"):      # (likewise a build from before the window structure)
+        lib.mtr_window_structure_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                    C.c_int32, C.c_int32, C.c_int32, C.c_void_p, P(CWindowStructureDst)]
+        lib.mtr_window_structure_device.restype = C.c_int
     lib.mtr_test_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
     lib.mtr_test_catalog_stats.restype = C.c_int
     lib.mtr_test_partial_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
@@ -1506,6 +1524,39 @@ class Engine:
         self._check(call(self.h, C.byref(src), int(band_extra), stream, C.byref(dst), C.byref(nb)), "mtr_allele_consensus_device")
         return cons
 
+    def window_structure(self, structures, off, bases, which, gain: int = 1, mismatch: int = 1, indel: int = 1) -> WindowStructure:
+        """The motif structure of windows (mtr_window_structure_device): window w = bases[off[w]:off[w + 1]] (codes 0..3) aligned globally to
+        structures[which[w]], an ordered list of motifs each repeated zero or more whole times; per segment its span, copies and matches.
+        structures: a sequence of structures, each a string (one motif) or a sequence of strings - at most 2 motifs of 32 bases in all, or 4 of
+        16.  off (int64 [N + 1]), bases (uint8 [T]) and which (int32 [N]) are tensors on this engine's device: genotype_windows' off and bases
+        with which = sg.locus, or allele_consensus' off and bases with which = arange(2 * n_loci) // 2.  A window above WS_MAX_WINDOW bases is
+        marked skipped.  Needs no upload and no run and changes nothing either left.  Returns a WindowStructure of fresh tensors on this
+        engine's device; stream handling as call_alleles'."""
+        import torch
+
+        for name, v in (("gain", gain), ("mismatch", mismatch), ("indel", indel)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise MtrError(f"{name} must be an integer, got {v!r}")
+        lists = [[st] if isinstance(st, (str, bytes)) else list(st) for st in structures]
+        motifs = [m.encode() if isinstance(m, str) else bytes(m) for st in lists for m in st]
+        data = np.frombuffer(b"".join(motifs) + b"\0", np.uint8).copy()
+        motif_off = np.concatenate([[0], np.cumsum([len(m) for m in motifs], dtype=np.int64)]).astype(np.int64)
+        struct_off = np.concatenate([[0], np.cumsum([len(st) for st in lists], dtype=np.int64)]).astype(np.int32)
+        if not isinstance(off, torch.Tensor) or off.dim() != 1 or off.numel() < 1 or not isinstance(bases, torch.Tensor) or bases.dim() != 1:
+            raise MtrError("off must be a 1-D torch tensor of N + 1 offsets and bases a 1-D torch tensor")
+        N, T = int(off.numel()) - 1, int(bases.numel())
+        col = self._gpu_column
+        ptrs = [col(off, torch.int64, (N + 1,), "the windows' off"), col(bases, torch.uint8, (T,), "the windows' bases"), col(which, torch.int32, (N,), "the windows' structure")]
+        dev = torch.device("cuda", self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ws = WindowStructure(torch.empty((N, 4, 4), dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
+                             torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.uint8, device=dev))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CWindowStructureDst(*[t.data_ptr() if t.numel() else None for t in ws], N)
+        self._check(self.lib.mtr_window_structure_device(self.h, data.ctypes.data, motif_off.ctypes.data, struct_off.ctypes.data, len(lists), *ptrs, N, T,
+                                                         int(gain), int(mismatch), int(indel), stream, C.byref(dst)), "mtr_window_structure_device")
+        return ws
+
     def test_catalog_stats(self):
         """mtr_test_catalog_stats: what the last genotype_catalog call saw - (positions, passed by the filter, seed hits, candidates) and the
         host-clock ms of (index build and upload, first scan pass, the rest)"""
@@ -2212,6 +2263,46 @@ def join_windows(parts) -> GenotypeWindows:
         offs.append((p.off if k == len(parts) - 1 else p.off[:-1]) + before)
         before += int(p.off[-1])
     return GenotypeWindows(_cat(offs), _cat([p.bases for p in parts]))
+
+
+def format_window_structure(structures, ws: WindowStructure, names=None) -> bytes:
+    """The result of Engine.window_structure as text, one tab-separated line per window: its name (names[w], or its index), score, ratio, and
+    per segment of its structure motif*copies[start,end)matches; a skipped window's line ends in "skipped".  structures: window w's structure
+    at structures[w] (the call's structures[which[w]]), or one structure for every window."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    lists = [[st] if isinstance(st, (str, bytes)) else list(st) for st in structures]
+    seg, score, ratio, skipped = host(ws.seg).reshape(-1, 4, 4), host(ws.score).reshape(-1), host(ws.ratio).reshape(-1), host(ws.skipped).reshape(-1)
+    if len(lists) == 1:
+        lists = lists * len(seg)
+    if not len(seg) == len(score) == len(ratio) == len(skipped) == len(lists):
+        raise MtrError(f"{len(lists)} structures for {len(seg)} windows")
+    out = []
+    for w in range(len(seg)):
+        head = f"{names[w] if names is not None else w}\t{int(score[w])}\t{float(ratio[w]):.4f}"
+        if skipped[w]:
+            out.append(head + "\tskipped\n")
+            continue
+        cols = []
+        for s, m in enumerate(lists[w]):
+            start, end, copies, matches = (int(v) for v in seg[w, s])
+            cols.append(f"{m.decode() if isinstance(m, bytes) else m}*{copies}[{start},{end}){matches}")
+        out.append(head + "\t" + "\t".join(cols) + "\n")
+    return "".join(out).encode()
+
+
+def with_segment_copies(sg: SparseGenotypes, ws: WindowStructure, segment: int) -> SparseGenotypes:
+    """sg with fields[:, 3] (copies) replaced by the copies of segment `segment` of ws (Engine.window_structure over genotype_windows(sg) with
+    which = sg.locus) and ratio by ws.ratio; everything else is sg's own.  Device operations only.  Engine.call_alleles(...) then calls that
+    segment of a compound locus as it calls a plain locus."""
+    if isinstance(segment, bool) or not isinstance(segment, (int, np.integer)) or not 0 <= segment < WS_MAX_SEGMENTS:
+        raise MtrError(f"segment must be an integer in 0..{WS_MAX_SEGMENTS - 1}, got {segment!r}")
+    if tuple(ws.seg.shape) != (int(sg.read.shape[0]), 4, 4):
+        raise MtrError(f"the structure has {tuple(ws.seg.shape)} segment columns for {int(sg.read.shape[0])} rows")
+    fields = sg.fields.clone()
+    fields[:, 3] = ws.seg[:, segment, 2]
+    return sg._replace(fields=fields, ratio=ws.ratio.clone())
 
 
 def format_allele_consensus(loci, cons: AlleleConsensus) -> bytes:

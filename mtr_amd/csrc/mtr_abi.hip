@@ -51,6 +51,8 @@
 #include "catalog_build.hip.inc"
 #include "allele_call.hip.inc"
 #include "consensus.hip.inc"
+#include "window_structure.hip.inc"
+#include "window_structure_args.h"
 #include "fasta.hip.inc"
 #include "fastq.hip.inc"
 #include "file_order.hip.inc"
@@ -58,6 +60,7 @@
 static_assert(sizeof(DevRecord) == sizeof(mtr_record), "device and ABI record layouts must agree");
 static_assert(MTR_N_COUNTERS == CNT_N, "counter count");
 static_assert(MTR_MAX_READ_LENGTH == MTRC_MAX_SUPPORTED_LENGTH, "read length limit");
+static_assert(MTR_WS_MAX_SEGMENTS == WS_MAX_SEGMENTS && MTR_WS_MAX_WINDOW == WS_MAX_WINDOW, "the window structure's limits");
 
 // A buffer of the context: grow-only (hipMalloc / hipFree cost ~0.1-0.5 ms each; a dozen of them per batch were a third of a single
 // read's latency), freed with the context.  It converts to its raw pointer, which is what the kernels and the copies are given.
@@ -278,6 +281,9 @@ struct mtr_ctx {
     // the windows and the allele consensus (consensus.hip.inc): d_co_i32 = the per-entry and per-allele int32 columns, d_co_i64 = tab_off | cons_off (or the
     // windows' offsets), d_co_state = the bad-input words and the task counters, the tasks, the vote tables, the alignment's direction scratch
     DevBuf<int32_t> d_co_i32, d_co_tab; DevBuf<int64_t> d_co_i64; DevBuf<unsigned long long> d_co_state; DevBuf<int4> d_co_tasks; DevBuf<uint32_t> d_co_dirs;
+    // the window structure (window_structure.hip.inc), per call and nothing kept, buffers of its own: the structures as the lanes carry them, d_ws_i32 =
+    // the windows' keys | the task list, the ends' carried fields, d_ws_state = the bad-input words | the keys' counts | their cursors
+    DevBuf<WsStruct> d_ws_structs; DevBuf<int32_t> d_ws_i32; DevBuf<WsRaw> d_ws_raw; DevBuf<unsigned long long> d_ws_state;
     long long wrap_dp_size = MTRC_WRAP_DP_SIZE;          // the WrapDPsize the kernels of this context's device test (MTR_TEST_WRAP_DP_SIZE)
     // a FASTA file in device memory (fasta.hip.inc), per call: the tiles' columns, the header windows' columns, the IDs' offsets, the stop, the sizes
     DevBuf<uint32_t> d_fa_tiles, d_fa_hbase; DevBuf<int32_t> d_fa_hpos, d_fa_hidlen; DevBuf<int64_t> d_fa_idoff;
@@ -2672,6 +2678,83 @@ extern "C" mtr_status mtr_allele_consensus_device(mtr_ctx *ctx, const mtr_consen
     const struct { int32_t *to; const int32_t *from; } cols[5] = { { dst->backbone_read, a.bb_read }, { dst->backbone_len, a.bb_len }, { dst->members, a.members }, { dst->aligned, a.aligned },
                                                                    { dst->skipped, a.skipped } };
     for (const auto &c : cols) HIPCHK(hipMemcpyAsync(c.to, c.from, G * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- the motif structure of windows (window_structure.hip.inc) ---------------------------------------------------------------------------
+template <int UB, bool WIDE>
+static void ws_launch_bin(mtr_ctx *ctx, const WsArgs &a, unsigned first, unsigned n_tasks)
+{
+    if (n_tasks > 0) hipLaunchKernelGGL((mtr_k_ws_lanes<UB, WIDE>), dim3((n_tasks + 63) / 64), dim3(64), 0, ctx->stream, a, first, n_tasks);
+}
+
+extern "C" mtr_status mtr_window_structure_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, const int32_t *struct_off, int32_t n_structs,
+                                                  const int64_t *win_off, const uint8_t *win_bases, const int32_t *win_struct, int64_t n_windows, int64_t n_bases,
+                                                  int32_t gain, int32_t mismatch, int32_t indel, void *wait_stream, const mtr_window_structure_dst *dst)
+{
+    if (!ctx) return MTR_ERR_BAD_ARG;
+    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    const int64_t N = n_windows;
+    const bool columns_null = !win_off || (N > 0 && !win_struct) || (n_bases > 0 && !win_bases) || !dst || (N > 0 && (!dst->seg || !dst->score || !dst->ratio || !dst->skipped));
+    if (!wsa_check(motifs, motif_off, struct_off, n_structs, columns_null, N, n_bases, gain, mismatch, indel, ctx->err)) return MTR_ERR_BAD_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    {
+        const struct { const void *p; int64_t bytes; const char *what; } cols[3] = { { win_off, (N + 1) * 8, "win_off" }, { win_bases, n_bases, "win_bases" }, { win_struct, N * 4, "win_struct" } };
+        for (const auto &c : cols)
+            if (c.bytes > 0) { mtr_status st = check_device_ptr(ctx, (const uint8_t *)c.p, c.bytes, c.what, "the column's bytes"); if (st != MTR_OK) return st; }
+    }
+    std::vector<WsStruct> structs((size_t)n_structs);
+    for (int32_t k = 0; k < n_structs; k++) structs[(size_t)k] = wsa_struct(motifs, motif_off, struct_off, k);
+    const size_t nw = std::max<size_t>((size_t)N, 1);
+    const size_t state_bytes = WS_BAD * 8 + 2 * WS_KEYS * 4;
+    HIPCHK(ctx->d_ws_structs.ensure(structs.size() * sizeof(WsStruct))); HIPCHK(ctx->d_ws_i32.ensure(2 * nw * 4)); HIPCHK(ctx->d_ws_raw.ensure(nw * sizeof(WsRaw)));
+    HIPCHK(ctx->d_ws_state.ensure(state_bytes));
+    if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ctx->ev_text, (hipStream_t)wait_stream));
+    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
+    HIPCHK(hipMemsetAsync(ctx->d_ws_state, 0xff, WS_BAD * 8, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_ws_state + WS_BAD, 0, 2 * WS_KEYS * 4, ctx->stream));
+    HIPCHK(copy_sync(ctx, ctx->d_ws_structs, structs.data(), structs.size() * sizeof(WsStruct), hipMemcpyHostToDevice));
+    WsArgs a{};
+    a.win_off = win_off; a.win_bases = win_bases; a.win_struct = win_struct; a.N = N; a.n_bases = n_bases; a.n_structs = n_structs; a.structs = ctx->d_ws_structs;
+    a.bad = ctx->d_ws_state; a.count = (unsigned *)(a.bad + WS_BAD); a.cursor = a.count + WS_KEYS;
+    a.key = ctx->d_ws_i32; a.tasks = a.key + nw; a.raw = ctx->d_ws_raw; a.G = gain; a.MM = mismatch; a.D = indel;
+    const dim3 per_window((unsigned)((nw + WS_BLOCK - 1) / WS_BLOCK)), blk(WS_BLOCK);
+    hipLaunchKernelGGL(mtr_k_ws_check, per_window, blk, 0, ctx->stream, a);
+    if (n_bases > 0) {
+        const int64_t words = (((int64_t)((uintptr_t)win_bases & 7) + n_bases - 1) >> 3) + 1;
+        hipLaunchKernelGGL(mtr_k_ws_bases, dim3((unsigned)std::min<int64_t>((words + WS_BLOCK - 1) / WS_BLOCK, 1 << 16)), blk, 0, ctx->stream, win_bases, n_bases, words, a.bad);
+    }
+    HIPCHK(hipGetLastError());
+    struct { unsigned long long bad[WS_BAD]; unsigned count[WS_KEYS]; } st;
+    static_assert(sizeof st == WS_BAD * 8 + WS_KEYS * 4, "the state's layout");
+    HIPCHK(copy_sync(ctx, &st, a.bad, sizeof st, hipMemcpyDeviceToHost));
+    if (st.bad[0] != ~0ull) { ctx->err = "win_off at window " + std::to_string(st.bad[0]) + " does not ascend from 0 to n_bases"; return MTR_ERR_BAD_ARG; }
+    if (st.bad[1] != ~0ull) {
+        int32_t k = 0;
+        HIPCHK(copy_sync(ctx, &k, win_struct + st.bad[1], 4, hipMemcpyDeviceToHost));
+        ctx->err = "window " + std::to_string(st.bad[1]) + ": win_struct " + std::to_string(k) + " outside 0.." + std::to_string(n_structs - 1); return MTR_ERR_BAD_ARG;
+    }
+    if (st.bad[2] != ~0ull) {
+        uint8_t c = 0;
+        HIPCHK(copy_sync(ctx, &c, win_bases + st.bad[2], 1, hipMemcpyDeviceToHost));
+        ctx->err = "win_bases at " + std::to_string(st.bad[2]) + ": code " + std::to_string((int)c) + " is above 3"; return MTR_ERR_BAD_ARG;
+    }
+    if (dst->cap_windows < N) { ctx->err = "destination holds " + std::to_string(dst->cap_windows) + " windows, " + std::to_string(N) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (N == 0) return MTR_OK;
+    unsigned bin_first[WS_BINS + 1] = { 0 };
+    for (int b = 0; b < WS_BINS; b++) { unsigned n = 0; for (int k = 0; k < WS_CLASSES; k++) n += st.count[b * WS_CLASSES + k]; bin_first[b + 1] = bin_first[b] + n; }
+    if ((int64_t)bin_first[WS_BINS] > N) { ctx->err = "the window structure's task counts failed on the device"; return MTR_ERR_HIP; }
+    hipLaunchKernelGGL(mtr_k_ws_tasks, per_window, blk, 0, ctx->stream, a);
+    ws_launch_bin<8, false>(ctx, a, bin_first[0], bin_first[1] - bin_first[0]);
+    ws_launch_bin<16, false>(ctx, a, bin_first[1], bin_first[2] - bin_first[1]);
+    ws_launch_bin<32, false>(ctx, a, bin_first[2], bin_first[3] - bin_first[2]);
+    ws_launch_bin<8, true>(ctx, a, bin_first[3], bin_first[4] - bin_first[3]);
+    ws_launch_bin<16, true>(ctx, a, bin_first[4], bin_first[5] - bin_first[4]);
+    a.seg = dst->seg; a.score = dst->score; a.ratio = dst->ratio; a.skipped = dst->skipped;
+    hipLaunchKernelGGL(mtr_k_ws_output, per_window, blk, 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
 }

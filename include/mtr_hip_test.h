@@ -47,6 +47,15 @@ mtr_status mtr_test_wrap_dp_pass(mtr_ctx *ctx, int32_t pass, int32_t n_groups, c
                                  const int32_t *query_start, const int32_t *query_end, const uint8_t *units, const int32_t *unit_off,
                                  const int32_t *gain, const int32_t *mismatch, const int32_t *indel, int32_t *out16);
 
+/* polish_repeat (consensus.c:610-704) alone, through the function the kernels run (polish(), k2_units.hip.inc), one wavefront per task, on the
+ * uploaded batch.  Task t: the repeat rep_start[t] .. rep_end[t] (0-origin, inclusive) of read read_idx[t], k[t] (2 .. 15), the unit
+ * units[unit_off[t] .. unit_off[t+1]) (codes 0..3, fewer than 500 bases) and its node frequencies scores[unit_off[t] ..] (unit_off has
+ * n_tasks + 1 entries and starts at 0).  out_len[t] = the polished unit's length, its codes at out_units[500 t ..] (the caller's
+ * 500 n_tasks bytes).  A task outside these bounds: MTR_ERR_BAD_ARG, the reason names it; nothing is launched. */
+mtr_status mtr_test_polish(mtr_ctx *ctx, int32_t n_tasks, const int32_t *read_idx, const int32_t *rep_start, const int32_t *rep_end,
+                           const int32_t *k, const uint8_t *units, const int32_t *scores, const int32_t *unit_off,
+                           uint8_t *out_units, int32_t *out_len);
+
 /* How the last launch ran: 0 = one kernel, a wavefront per read; 1 = range-parallel; 2 = the staged chain of kernels.
  * (The records do not depend on it; tests pin the policy of mtr_hip.h's mtr_set_overlapped_launches with it.) */
 int32_t mtr_test_last_mode(const mtr_ctx *ctx);

@@ -42,7 +42,7 @@ COUNTER_NAMES = ["dp_calls", "dp_cells", "dp_rows", "revise_dp_calls", "revise_d
 # In a product build (no -DMTR_PROFILE) mtr_k_dp2_quads counts its passes by kind: prof47 = four alignments per wavefront, prof55 = eight
 EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mtr_process_batch", "mtr_free_results",
            "mtr_upload_batch", "mtr_run_resident", "mtr_fetch_results", "mtr_get_kernel_times", "mtr_get_counters",
-           "mtr_test_ranges", "mtr_test_wrap_dp", "mtr_test_wrap_dp_pass", "mtr_test_last_mode", "mtr_set_trace", "mtr_get_trace",
+           "mtr_test_ranges", "mtr_test_wrap_dp", "mtr_test_wrap_dp_pass", "mtr_test_polish", "mtr_test_last_mode", "mtr_set_trace", "mtr_get_trace",
            "mtr_run_resident_async", "mtr_wait", "mtr_alignments",
            "mtr_file_state_create", "mtr_file_state_destroy", "mtr_upload_batch_in_file", "mtr_file_state_skip",
            "mtr_get_bases_after_read", "mtr_upload_batch_packed", "mtr_fetch_results_packed", "mtr_export_packed_device",
@@ -1832,6 +1832,22 @@ class Engine:
         self._check(self.lib.mtr_test_wrap_dp(self.h, n, rd.ctypes.data, qs.ctypes.data, qe.ctypes.data, units.ctypes.data, uo.ctypes.data,
                                               g.ctypes.data, m.ctypes.data, d.ctypes.data, out.ctypes.data), "mtr_test_wrap_dp")
         return out
+
+    def test_polish(self, tasks):
+        """mtr_test_polish: polish_repeat on one wavefront per task.  tasks: list of (read_idx, rep_start, rep_end, k, unit codes, node frequencies)
+        -> list of polished units (uint8 codes)."""
+        n = len(tasks)
+        rd, rs, re, kk = (np.array([t[i] for t in tasks], np.int32) for i in range(4))
+        uo = np.zeros(n + 1, np.int32)
+        uo[1:] = np.cumsum([len(t[4]) for t in tasks])
+        units = np.ascontiguousarray(np.concatenate([np.asarray(t[4], np.uint8) for t in tasks]))
+        scores = np.ascontiguousarray(np.concatenate([np.asarray(t[5], np.int32) for t in tasks]))
+        out_units, out_len = np.zeros((n, 500), np.uint8), np.zeros(n, np.int32)
+        self.lib.mtr_test_polish.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
+        self.lib.mtr_test_polish.restype = C.c_int
+        self._check(self.lib.mtr_test_polish(self.h, n, rd.ctypes.data, rs.ctypes.data, re.ctypes.data, kk.ctypes.data, units.ctypes.data,
+                                             scores.ctypes.data, uo.ctypes.data, out_units.ctypes.data, out_len.ctypes.data), "mtr_test_polish")
+        return [out_units[i, :out_len[i]].copy() for i in range(n)]
 
     DP_PASSES = {"WAVE2P": 0, "Q4": 1, "QUAD2P": 2, "FOUR1P": 3, "OCT1P": 4, "OCT2P": 5}       # MTR_TEST_PASS_* of include/mtr_hip_test.h
 

@@ -301,11 +301,18 @@ DEVINL unsigned long long clk() { return 0ull; }
 DEVINL void wc_time(unsigned long long *, int, unsigned long long) {}
 #endif
 // timers that share a spare counter with a development build's own use of it (-DMTR_PROFILE_WALK_FMT: k2_units.hip.inc walk();
-// -DMTR_PROFILE_DP2_CLASS: k3_staged.hip.inc st_quad_run())
-#if defined(MTR_PROFILE_WALK_FMT) || defined(MTR_PROFILE_DP2_CLASS)
+// -DMTR_PROFILE_DP2_CLASS: k3_staged.hip.inc st_quad_run(); -DMTR_PROFILE_POLISH: mtr_k_polish and polish(), k2_units.hip.inc)
+#if defined(MTR_PROFILE_WALK_FMT) || defined(MTR_PROFILE_DP2_CLASS) || defined(MTR_PROFILE_POLISH)
 #define wc_time_aux(wc, which, t0) do { } while (0)
 #else
 #define wc_time_aux(wc, which, t0) wc_time(wc, which, t0)
+#endif
+// -DMTR_PROFILE -DMTR_PROFILE_POLISH (tests/dev/polish_phases.py): the phases of a polish work item, each in a spare counter - 43 queue pull and
+// item loads, 44 candidate in, 45 staging and the flag test, 46 table build, 47 the walk, 55 result out
+#ifdef MTR_PROFILE_POLISH
+#define wc_time_pol(wc, which, t0) wc_time(wc, which, t0)
+#else
+#define wc_time_pol(wc, which, t0) do { } while (0)
 #endif
 DEVINL void wc_flush(unsigned long long *wc, unsigned long long *global)
 {

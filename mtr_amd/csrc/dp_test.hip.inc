@@ -237,3 +237,45 @@ __global__ __launch_bounds__(64, MTR_WAVES_PER_SIMD) void mtr_k_dp_test_rev(DpPa
     }
     wc_flush(s_cnt, a.t.counters);
 }
+
+// ---- polish_repeat alone (mtr_test_polish): a task per work item through polish(), as the per-read kernel calls it ------------------------
+struct PolishTestArgs {
+    K2Args a;                      // the batch, the narrow scratch layout (no cells), counters and status
+    int32_t n_tasks;
+    const int32_t *read_idx, *rep_start, *rep_end, *k;
+    const uint8_t *units; const int32_t *scores, *unit_off;      // unit codes 0..3 and node frequencies, concatenated
+    uint8_t *out_units; int32_t *out_len;                         // task t's polished unit at MTRC_MAX_PERIOD * t
+};
+__global__ __launch_bounds__(64, MTR_LAT_WAVES_PER_SIMD) void mtr_k_polish_test(PolishTestArgs p)
+{
+    __shared__ __attribute__((aligned(16))) int s_arena[MTR_ARENA_INTS];
+    __shared__ unsigned long long s_cnt[CNT_N];
+    int *s_keys = s_arena, *s_seeds = s_arena + K2_TAB_CAP, *s_stage = s_seeds + MTRC_MAX_SEEDS + 4;
+    const int lane = lane_id();
+    if (lane < CNT_N) s_cnt[lane] = 0ull;
+    K2Ctx c;
+    c.a = &p.a; c.wc = s_cnt;
+    c.sc = p.a.scratch + (size_t)blockIdx.x * p.a.scratch_per_wave;
+    c.y = k2_layout(p.a.Lmax, p.a.cells_cap);
+    c.lds_keys = (lds_int *)s_keys; c.seeds = (lds_int *)s_seeds; c.stage = (lds_int *)s_stage;
+    c.ties = (int *)(c.sc + c.y.ties); c.fresh = c.ties + MTRC_MAX_TIEBREAKS;
+    c.memo_n = 0; c.memo_qs = c.memo_qe = -1; c.memo_U = 0; c.rmemo_n = 0;
+    for (;;) {
+        const int t = next_work_item(p.a.work_counter);
+        if (t >= p.n_tasks) break;
+        st_member_ctx(c, p.a, uni(p.read_idx[t]));
+        const int uo = uni(p.unit_off[t]), U = uni(p.unit_off[t + 1]) - uo;
+        RR r; rr_clear(r);
+        r.rep_start = uni(p.rep_start[t]); r.rep_end = uni(p.rep_end[t]); r.kmer = uni(p.k[t]); r.period = U;
+        uint8_t *ub = slot_unit(c, 1);
+        slot_load_candidate(ub, slot_score(c, 1), p.units + uo, p.scores + uo, U);
+        wave_sync_mem();
+        polish(c, r, 1);
+#pragma unroll 1
+        for (int q = lane; q < r.period; q += 64) p.out_units[(size_t)t * MTRC_MAX_PERIOD + q] = ub[q];
+        if (lane == 0) p.out_len[t] = r.period;
+        wave_sync_mem();                                   // the next task loads over slot 1
+        loop_join();
+    }
+    wc_flush(s_cnt, p.a.counters);
+}

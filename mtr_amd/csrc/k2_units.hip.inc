@@ -23,6 +23,7 @@
 #include "device_util.hip.inc"
 #include "dp_wrap.hip.inc"
 #include "min_missing_table.h"
+#include "polish_plan.h"
 
 #ifndef MTR_WAVES_PER_SIMD
 #define MTR_WAVES_PER_SIMD 4       // 16 wavefronts per CU = 128 VGPRs each (an experiment build may lower it: fewer spills, less latency hiding)
@@ -1493,95 +1494,119 @@ DEVINL int search_walks(K2Ctx &c, int qs, int qe, int k, int &max_freq_out, int 
 // ---------------------------------------------------------------------------------------------------------
 // polish_repeat (consensus.c:610-704): operates on RR r / slot 1 in place
 // ---------------------------------------------------------------------------------------------------------
-// The unit and its node frequencies are staged in LDS for the serial loop below, one byte per position:
-// bits 0-1 = base, bits 2-3 = min(string_score, 3) (the loop only asks "== 1" and "< 2").  Read from global scratch
-// each of its ~2-10 look-ups per position was a dependent 1-2 us round trip.
-DEVINL int pol_base(const lds_u8 *st, int j) { return uni((int)st[j]) & 3; }
+// The unit and its node frequencies are staged in LDS, one byte per position (polish_plan.h: pp_stage_byte; bits 0-1 = base, bits 2-3 =
+// min(string_score, 3) - the walk only asks "== 1" and "< 2").  Read from global scratch each of a position's ~2-10 look-ups was a
+// dependent 1-2 us round trip.  The polished unit is written into the bytes behind them (out[jr], jr = MTRC_MAX_PERIOD - 1 downwards).
+// The walk itself is polish_plan.h's: every lane answers the flag predicate for its own positions, ballots make the flagged set, and the
+// walk visits the flagged positions only (pp_walk_plan) - the stretches between them are copies, 64 bases a store.
+// -DMTR_POLISH_WALK_ALL (a build of its own, for A/B runs; never a runtime switch): the reference's walk over every position (pp_walk_all).
+#define POL_OUT_OFF 512                      // the output's bytes within c.stage (1024 bytes, free here: no look-ahead runs during polish)
+static_assert(MTRC_MAX_PERIOD <= POL_OUT_OFF, "a staged unit and its polished form share the look-ahead's staging bytes");
+DEVINL int pol_base(const lds_u8 *st, int j) { return uni((int)st[j]) & 3; }               // everything in the walk is wave-uniform: say so (uni)
 DEVINL int pol_score(const lds_u8 *st, int j) { return (uni((int)st[j]) >> 2) & 3; }
-DEVINL int align_score(K2Ctx &c, int start, int k, int node, int period, const lds_u8 *st)
-{   // score_for_alignment, consensus.c:584-595
-    int sum = 0;
-    const int p4k1 = 1 << (2 * (k - 1));
-    for (int j = start; 0 <= j && start - k < j; j--) { node = pol_base(st, j % period) * p4k1 + node / 4; sum += uni(tab_get(c, node)); }
-    return sum;
+// this wavefront's LDS writes before its later LDS reads from other lanes (a wavefront's LDS operations run in order: the compiler must keep them so)
+DEVINL void wave_sync_lds()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
 }
-DEVINL bool suspicious(const lds_u8 *st, int kmer, int j)
-{   // consensus.c:597-608
-    int cnt = 0;
-    for (int i = 0; i < kmer - 1 && 0 <= j - i; i++) if (pol_score(st, j - i) < 2) cnt++;
-    return (double)(kmer - 1) * 0.8 < (double)cnt;
+struct PolMask {                             // polish_plan.h's flagged set on a wavefront: lane q holds word q
+    long long v;
+    DEVINL unsigned long long word(int q) const { return (unsigned long long)lane_val64(v, q); }
+};
+struct PolOps {                              // polish_plan.h's OPS on a wavefront
+    const K2Ctx *c; const lds_u8 *st; lds_u8 *out; int k, period;
+    DEVINL int base(int j) const { return pol_base(st, j); }
+    DEVINL int score(int j) const { return pol_score(st, j); }
+    DEVINL int get(int node) const { return uni(tab_get(*c, node)); }
+    // four look-ups side by side, lane l asks for the l-th node: one trip to the table instead of four in a row
+    DEVINL void get4(int a0, int a1, int a2, int a3, int &f0, int &f1, int &f2, int &f3) const
+    {
+#ifdef MTR_POLISH_WALK_ALL
+        f0 = get(a0); f1 = get(a1); f2 = get(a2); f3 = get(a3);
+#else
+        const int lane = lane_id();
+        const int key = lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? a2 : a3;
+        int v = 0;
+        if (lane < 4) v = tab_get(*c, key);
+        f0 = lane_val(v, 0); f1 = lane_val(v, 1); f2 = lane_val(v, 2); f3 = lane_val(v, 3);
+#endif
+    }
+    // the cyclic k-mer at j with one ballot: lane l answers bit l of the node, bit l & 1 of the base k - 1 - (l >> 1) places behind j
+    DEVINL int cyc(int j) const
+    {
+        const int lane = lane_id();
+        const bool on = lane < 2 * k;
+        int pos = j + (k - 1 - (lane >> 1)); if (pos >= period) pos -= period;                 // (period > k: one wrap at most)
+        const int b = on ? (int)st[pos] : 0;
+        return (int)(unsigned)__ballot(on && ((b >> (lane & 1)) & 1) != 0);
+    }
+    DEVINL void emit(int jr, int b) const { if (lane_id() == 0) out[jr] = (unsigned char)b; }
+    DEVINL void copy(int jr, int j, int n) const
+    {   // (not unrolled: at most eight rounds, and an unrolled copy took thirty-odd registers for its bytes in flight)
+#pragma unroll 1
+        for (int t = j - n + 1 + lane_id(); t <= j; t += 64) out[jr - j + t] = (unsigned char)(st[t] & 3);
+    }
+    DEVINL void undefined() const { wc_add(c->wc, CNT_UNDEFINED, 1); }
+    DEVINL void join() const { loop_join(); }
+};
+// polish_repeat on a staged unit (st[0 .. r.period), written by the caller and synchronised): true = the unit changed, its new form is
+// out[jr + 1 .. MTRC_MAX_PERIOD - 1]; false = it stays as it is (no flagged position, a walk that altered nothing, or an output beyond
+// MTRC_MAX_PERIOD, :645).  The k-mer table of the repeat (:617-619) is built only if a position is flagged.
+DEVINL bool polish_staged(K2Ctx &c, const RR &r, const lds_u8 *st, lds_u8 *out, int &jr, unsigned long long t_stage)
+{
+    const int lane = lane_id();
+    const int k = r.kmer, period = r.period;
+    // The walk only ever leaves the unit's own base and a step of one at a position whose node frequency is 1 AND that is suspicious
+    // (:629-631); everything else copies the unit.  If no position is flagged the unit comes out as it went in and neither the table nor
+    // the walk is needed (most revisions: SURVEY appendix B, 467 of 4 538 units change).
+    PolMask m; m.v = 0ll;
+    unsigned long long any = 0ull;
+#pragma unroll 1
+    for (int q = 0; q * 64 < period; q++) {
+        const int t = q * 64 + lane;
+        const unsigned long long w = __ballot(t < period && pp_flagged([&](int p) { return ((int)st[p] >> 2) & 3; }, k, t));
+        if (lane == q) m.v = (long long)w;
+        any |= w;
+    }
+    const bool none = any == 0ull;
+    wc_time_pol(c.wc, CNT_SPARE45, t_stage);
+    if (none) return false;
+    const unsigned long long t_tab = clk();
+    (void)tab_build(c, k, r.rep_start, r.rep_end);             // init_inputString + generate_freqNode_return_maxNode (:617-619)
+    wc_time_pol(c.wc, CNT_SPARE46, t_tab);
+    const unsigned long long t_walk = clk();
+    PolOps ops{&c, st, out, k, period};
+    bool altered = false;
+#ifdef MTR_POLISH_WALK_ALL
+    const bool ok = pp_walk_all(ops, k, period, jr, altered);
+#else
+    const bool ok = pp_walk_plan(ops, m, k, period, jr, altered);
+#endif
+    wave_sync_lds();
+    wc_time_pol(c.wc, CNT_SPARE47, t_walk);
+    return ok && altered;
 }
 
+// RR r / unit slot `slot` in place (the per-read kernel, mtr_k_revise)
 DEVINL void polish(K2Ctx &c, RR &r, int slot = 1)
 {
     const int lane = lane_id();
     const int k = r.kmer, period = r.period;
     if (period <= k) return;
     uint8_t *ub = slot_unit(c, slot); const int *score = slot_score(c, slot);
-    int *rev = (int *)(c.sc + c.y.pol_rev);
-    lds_u8 *st = (lds_u8 *)c.stage;                            // 1024 bytes, free here (no look-ahead runs during polish)
-    for (int t = lane; t < period; t += 64) {
-        const int sv = score[t];
-        st[t] = (unsigned char)((ub[t] & 3) | ((sv < 0 ? 0 : (sv > 3 ? 3 : sv)) << 2));
-    }
+    lds_u8 *st = (lds_u8 *)c.stage, *out = st + POL_OUT_OFF;
+    const unsigned long long t_stage = clk();
+#pragma unroll 1
+    for (int t = lane; t < period; t += 64) st[t] = pp_stage_byte((int)ub[t], score[t]);
+    wave_sync_lds();
+    int jr = 0;
+    if (!polish_staged(c, r, st, out, jr, t_stage)) return;
+    const int np = (MTRC_MAX_PERIOD - 1) - jr;
+#pragma unroll 1
+    for (int t = lane; t < np; t += 64) ub[t] = out[t + jr + 1];
     wave_sync_mem();
-    {   // The loop below only ever leaves the unit's own base and a step of one at a position whose node frequency is 1 AND that is
-        // suspicious (:629-631); everything else copies the unit.  Whether any such position exists is a question every position can answer
-        // for itself (the same window count as suspicious()): if none does, the unit comes out as it went in and neither the k-mer table of
-        // the repeat (:617-619) nor the walk over the unit is needed (most revisions: SURVEY appendix B, 467 of 4 538 units change).
-        bool any = false;
-        for (int t = lane; t < period; t += 64) {
-            if (((st[t] >> 2) & 3) != 1) continue;
-            int cnt = 0;
-            for (int i = 0; i < k - 1 && 0 <= t - i; i++) if (((st[t - i] >> 2) & 3) < 2) cnt++;
-            any = any || ((double)(k - 1) * 0.8 < (double)cnt);
-        }
-        if (__ballot(any) == 0ull) return;
-    }
-    (void)tab_build(c, k, r.rep_start, r.rep_end);             // init_inputString + generate_freqNode_return_maxNode (:617-619)
-    const int p4k1 = 1 << (2 * (k - 1)), p4k = 1 << (2 * k);
-    int jr = MTRC_MAX_PERIOD - 1;
-    int node = 0;
-    for (int i = 0; i < k; i++) node += pol_base(st, i) * (1 << (2 * (k - 1 - i)));
-    bool ok = true;
-    for (int j = period - 1; 0 <= j;) {
-        const int uj = pol_base(st, j);                           // everything here is wave-uniform: say so (uni)
-        int ref = uj * p4k1 + node / 4;
-        node = ref;
-        int emit, step;
-        if (pol_score(st, j) == 1 && suspicious(st, k, j)) {
-            int bestf = uni(tab_get(c, ref));                       // (only a suspicious position looks its node up)
-            for (int l = 0; l < 4; l++) {
-                int alt = (ref + (l - uj) * p4k1) % p4k;
-                int f = uni(tab_get(c, alt));
-                if (bestf < f) { bestf = f; node = alt; }
-            }
-            if (node == ref) { emit = uj; step = 1; }
-            else {
-                int sd = align_score(c, j, k, node, period, st);
-                int ss = align_score(c, j - 1, k, node, period, st);
-                int si = -1;
-                int prevb;
-                if (j == 0) { prevb = -1; wc_add(c.wc, CNT_UNDEFINED, 1); }   // int_unit[-1] in the reference (H10)
-                else prevb = pol_base(st, (j - 1) % period);
-                if (node / p4k1 == prevb) si = align_score(c, j - 2, k, node, period, st);
-                emit = node / p4k1;
-                int mx = sd > ss ? sd : ss; if (si > mx) mx = si;
-                step = (mx == sd) ? 0 : (mx == ss ? 1 : 2);
-            }
-        } else { emit = uj; step = 1; }
-        if (lane == 0) rev[jr] = emit;
-        jr--; j -= step;
-        loop_join();
-        if (jr < 0) { ok = false; break; }
-    }
-    wave_sync_mem();
-    if (ok) {
-        int np = (MTRC_MAX_PERIOD - 1) - jr;
-        for (int t = lane; t < np; t += 64) ub[t] = (uint8_t)rev[t + jr + 1];
-        wave_sync_mem();
-        r.period = np;
-    }
+    r.period = np;
 }
 
 DEVINL int min_missing(int period, double err, int coverage)

@@ -1414,6 +1414,7 @@ __global__ __launch_bounds__(64, MTR_LAT_WAVES_PER_SIMD) void mtr_k_polish(K2Arg
     c.memo_n = 0; c.memo_qs = c.memo_qe = -1; c.memo_U = 0; c.rmemo_n = 0;
     WqS wq; (void)wqs_init(wq, s, ST_SL_REV, s.rev_cap);
     for (;;) {
+        const unsigned long long t_pull = clk();
         const long long wi = wqs_next(s, ST_Q_POLISH, s.rev_cap, wq);
         if (wi < 0) break;                                 // every wave reaches this exit
         const long long ro = uni64(s.rev_items[wi]);
@@ -1424,25 +1425,46 @@ __global__ __launch_bounds__(64, MTR_LAT_WAVES_PER_SIMD) void mtr_k_polish(K2Arg
         st_member_ctx(c, a, uni(h->rd));
         const int e = uni(rv->slot), qs = uni(h->qs), qe = uni(h->qe);
         RR cur; st_rr_load(rv->rr, cur);
+        wc_time_pol(c.wc, CNT_SPARE43, t_pull);
+        const unsigned long long t_in = clk();
+        // The candidate's bases and node frequencies are loaded once, from its slot of the block: the frequencies (-1 behind them: clear_rr) go
+        // straight to the revision's record, bases and clamped frequencies into the staging bytes of the walk.  No unit slot of the wavefront's
+        // scratch in between (it cost a store, a fence and a load on the way in, and the same on the way out).
+        const int U = uni(en[e].period), maxU = st_max_unit(qs, qe);
+        uint8_t *du = s.arena + ro + sizeof(StRev); int *ds = (int *)(s.arena + ro + sizeof(StRev) + K2_SLOT_UNIT);
+        lds_u8 *st = (lds_u8 *)c.stage, *out = st + POL_OUT_OFF;
         {
-            const int U = uni(en[e].period), maxU = st_max_unit(qs, qe);
-            uint8_t *ub = slot_unit(c, 1); int *us = slot_score(c, 1);
             const uint8_t *su = st_slot_unit(s.arena, base, h, e); const int *ss = (const int *)(su + st_pad16(maxU));
-            slot_load_candidate(ub, us, su, ss, U);
-            wave_sync_mem();
+            int sv[K2_SLOT_SCORE / 64]; int bv[K2_SLOT_SCORE / 64];
+#pragma unroll
+            for (int q = 0; q < K2_SLOT_SCORE / 64; q++) { const int t = q * 64 + lane; sv[q] = t < U ? ss[t] : -1; bv[q] = t < U ? (int)su[t] : 0; }
+#pragma unroll
+            for (int q = 0; q < K2_SLOT_SCORE / 64; q++) { const int t = q * 64 + lane; ds[t] = sv[q]; if (t < POL_OUT_OFF) st[t] = pp_stage_byte(bv[q], sv[q]); }
         }
+        wave_sync_lds();
+        wc_time_pol(c.wc, CNT_SPARE44, t_in);
         const int in_period = cur.period;
         const unsigned long long t0 = clk();
-        polish(c, cur, 1);
+        int jr = 0;
+        const bool changed = cur.period > cur.kmer && polish_staged(c, cur, st, out, jr, t0);
         wc_time(c.wc, CYC_POLISH, t0);
-        trace_ev(c, 4, cur.rep_start, cur.rep_end, cur.kmer, in_period, cur.period, trace_on(c, 4) ? unit_hash(slot_unit(c, 1), cur.period) : 0, 0, 0, 0, 0, 0, 0, 0, 0);
-        st_rr_store(rv->rr, cur);
-        {
-            const uint32_t *su = (const uint32_t *)slot_unit(c, 1); uint32_t *du = (uint32_t *)(s.arena + ro + sizeof(StRev));
-            const int *ss = slot_score(c, 1); int *ds = (int *)(s.arena + ro + sizeof(StRev) + K2_SLOT_UNIT);
-            slot_copy_raw((uint8_t *)du, ds, (const uint8_t *)su, ss);
+        const unsigned long long t_out = clk();
+        if (changed) {                                     // the new unit from the walk's output to the record; its length is the one field that moves
+            const int np = (MTRC_MAX_PERIOD - 1) - jr;
+#pragma unroll 1
+            for (int t = lane; t < np; t += 64) du[t] = out[t + jr + 1];
+            cur.period = np;
+            st_rr_store(rv->rr, cur);
+        } else {                                           // as it went in: the record's copy from the staged bytes, the RR stays as it is
+#pragma unroll 1
+            for (int t = lane; t < U; t += 64) du[t] = (uint8_t)(st[t] & 3);
         }
-        wave_sync_mem();
+        if (trace_on(c, 4)) {
+            wave_sync_mem();
+            trace_ev(c, 4, cur.rep_start, cur.rep_end, cur.kmer, in_period, cur.period, unit_hash(du, cur.period), 0, 0, 0, 0, 0, 0, 0, 0);
+        }
+        wave_sync_lds();                                   // the next item stages over these bytes
+        wc_time_pol(c.wc, CNT_SPARE55, t_out);
         loop_join();
     }
     wc_flush(s_cnt, a.counters);

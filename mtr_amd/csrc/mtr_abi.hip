@@ -3353,6 +3353,50 @@ extern "C" mtr_status mtr_test_wrap_dp(mtr_ctx *ctx, int32_t n_tasks, const int3
     return check_status(ctx);
 }
 
+// polish_repeat alone, a task per wavefront turn (dp_test.hip.inc: mtr_k_polish_test), on the narrow scratch layout of the chain's polish kernel
+extern "C" mtr_status mtr_test_polish(mtr_ctx *ctx, int32_t n_tasks, const int32_t *read_idx, const int32_t *rep_start, const int32_t *rep_end,
+                                      const int32_t *k, const uint8_t *units, const int32_t *scores, const int32_t *unit_off,
+                                      uint8_t *out_units, int32_t *out_len)
+{
+    if (!ctx || n_tasks <= 0 || !read_idx || !rep_start || !rep_end || !k || !units || !scores || !unit_off || !out_units || !out_len) return MTR_ERR_BAD_ARG;
+    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    if (unit_off[0] != 0) { ctx->err = "unit_off[0] is not 0"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    for (int t = 0; t < n_tasks; t++) {
+        const int rd = read_idx[t], U = unit_off[t + 1] - unit_off[t];
+        if (rd < 0 || rd >= ctx->n_reads || rep_start[t] < 0 || rep_end[t] < rep_start[t] || rep_end[t] >= ctx->lens[(size_t)rd] || U <= 0 || U >= MTRC_MAX_PERIOD ||
+            k[t] < 2 || k[t] > MTRC_MAX_KMER) { ctx->err = "bad polish task " + std::to_string(t); return MTR_ERR_BAD_ARG; }
+    }
+    const size_t nt = (size_t)n_tasks, ub = (size_t)unit_off[n_tasks];
+    const size_t per_wave = k2_layout(ctx->Lmax, 256).total;
+    size_t total = 0;
+    const int waves = pick_waves(ctx, n_tasks, 8, per_wave, &total);
+    mtr_status s = ensure_scratch(ctx, total); if (s != MTR_OK) return s;
+    // d_t_i32: read | rep_start | rep_end | k | unit_off | scores;  d_t_out: lengths | units
+    HIPCHK(ctx->d_t_i32.ensure((nt * 5 + 1 + ub) * 4)); HIPCHK(ctx->d_t_units.ensure(ub + 16)); HIPCHK(ctx->d_t_out.ensure(nt * 4 + nt * MTRC_MAX_PERIOD + 16));
+    int32_t *d_i32 = ctx->d_t_i32; uint8_t *d_units = ctx->d_t_units; int32_t *d_len = ctx->d_t_out; uint8_t *d_out = (uint8_t *)(d_len + nt);
+    int32_t *d_rd = d_i32, *d_rs = d_i32 + nt, *d_re = d_i32 + 2 * nt, *d_k = d_i32 + 3 * nt, *d_uo = d_i32 + 4 * nt, *d_sc = d_i32 + 5 * nt + 1;
+    HIPCHK(copy_sync(ctx, d_rd, read_idx, nt * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_rs, rep_start, nt * 4, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, d_re, rep_end, nt * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_k, k, nt * 4, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, d_uo, unit_off, (nt + 1) * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_sc, scores, ub * 4, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, d_units, units, ub, hipMemcpyHostToDevice));
+    PolishTestArgs p{};
+    k2_args(ctx, p.a, per_wave); p.a.cells_cap = 256; p.a.trace_cap = 0;
+    p.n_tasks = n_tasks; p.read_idx = d_rd; p.rep_start = d_rs; p.rep_end = d_re; p.k = d_k; p.units = d_units; p.scores = d_sc; p.unit_off = d_uo;
+    p.out_units = d_out; p.out_len = d_len;
+    HIPCHK(hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * CNT_N, ctx->stream));
+    hipLaunchKernelGGL(mtr_k_polish_test, dim3((unsigned)waves), dim3(64), 0, ctx->stream, p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(copy_sync(ctx, ctx->counters, ctx->d_counters, sizeof(unsigned long long) * CNT_N, hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(ctx, out_len, d_len, nt * 4, hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(ctx, out_units, d_out, nt * MTRC_MAX_PERIOD, hipMemcpyDeviceToHost));
+    return check_status(ctx);
+}
+
 // One chosen forward pass on chosen groups (dp_test.hip.inc).  The host holds every task to the bounds under which the batch path hands a DP to that
 // pass - the same macros, evaluated here - and refuses the rest before anything is launched.
 extern "C" mtr_status mtr_test_wrap_dp_pass(mtr_ctx *ctx, int32_t pass, int32_t n_groups, const int32_t *group_off, const int32_t *read_idx,

@@ -597,6 +597,8 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_test_wrap_dp.restype = C.c_int
     lib.mtr_test_wrap_dp_pass.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 10
     lib.mtr_test_wrap_dp_pass.restype = C.c_int
+    lib.mtr_test_polish.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
+    lib.mtr_test_polish.restype = C.c_int
     lib.mtr_upload_batch_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]
     lib.mtr_upload_batch_packed.restype = C.c_int
     lib.mtr_upload_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
@@ -1816,21 +1818,27 @@ class Engine:
                 _libc.free(C.cast(a, C.c_void_p))
         return tail, tail_off, after
 
-    def test_wrap_dp(self, tasks):
-        """tasks: list of (read_idx, qs, qe, unit codes, G, MM, D) -> int32 [n,8] as wrap_around_DP_sub returns."""
-        n = len(tasks)
+    @staticmethod
+    def _dp_task_arrays(tasks, pad_units: bool):
+        """The seven arrays of mtr_test_wrap_dp's tasks (read_idx, qs, qe, unit codes, G, MM, D), in the order the two DP entry points take them.
+        pad_units: one byte behind the units, so that no task at all is still an array."""
         rd = np.array([t[0] for t in tasks], np.int32)
         qs = np.array([t[1] for t in tasks], np.int32)
         qe = np.array([t[2] for t in tasks], np.int32)
-        uo = np.zeros(n + 1, np.int32)
+        uo = np.zeros(len(tasks) + 1, np.int32)
         uo[1:] = np.cumsum([len(t[3]) for t in tasks])
-        units = np.ascontiguousarray(np.concatenate([np.asarray(t[3], np.uint8) for t in tasks]))
+        units = np.ascontiguousarray(np.concatenate([np.asarray(t[3], np.uint8) for t in tasks] + ([np.zeros(1, np.uint8)] if pad_units else [])))
         g = np.array([t[4] for t in tasks], np.int32)
         m = np.array([t[5] for t in tasks], np.int32)
         d = np.array([t[6] for t in tasks], np.int32)
+        return rd, qs, qe, units, uo, g, m, d
+
+    def test_wrap_dp(self, tasks):
+        """tasks: list of (read_idx, qs, qe, unit codes, G, MM, D) -> int32 [n,8] as wrap_around_DP_sub returns."""
+        n = len(tasks)
+        arrays = self._dp_task_arrays(tasks, pad_units=False)
         out = np.zeros((n, 8), np.int32)
-        self._check(self.lib.mtr_test_wrap_dp(self.h, n, rd.ctypes.data, qs.ctypes.data, qe.ctypes.data, units.ctypes.data, uo.ctypes.data,
-                                              g.ctypes.data, m.ctypes.data, d.ctypes.data, out.ctypes.data), "mtr_test_wrap_dp")
+        self._check(self.lib.mtr_test_wrap_dp(self.h, n, *(a.ctypes.data for a in arrays), out.ctypes.data), "mtr_test_wrap_dp")
         return out
 
     def test_polish(self, tasks):
@@ -1843,8 +1851,6 @@ class Engine:
         units = np.ascontiguousarray(np.concatenate([np.asarray(t[4], np.uint8) for t in tasks]))
         scores = np.ascontiguousarray(np.concatenate([np.asarray(t[5], np.int32) for t in tasks]))
         out_units, out_len = np.zeros((n, 500), np.uint8), np.zeros(n, np.int32)
-        self.lib.mtr_test_polish.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
-        self.lib.mtr_test_polish.restype = C.c_int
         self._check(self.lib.mtr_test_polish(self.h, n, rd.ctypes.data, rs.ctypes.data, re.ctypes.data, kk.ctypes.data, units.ctypes.data,
                                              scores.ctypes.data, uo.ctypes.data, out_units.ctypes.data, out_len.ctypes.data), "mtr_test_polish")
         return [out_units[i, :out_len[i]].copy() for i in range(n)]
@@ -1859,18 +1865,9 @@ class Engine:
         n = len(tasks)
         go = np.zeros(len(groups) + 1, np.int32)
         go[1:] = np.cumsum([len(g) for g in groups])
-        rd = np.array([t[0] for t in tasks], np.int32)
-        qs = np.array([t[1] for t in tasks], np.int32)
-        qe = np.array([t[2] for t in tasks], np.int32)
-        uo = np.zeros(n + 1, np.int32)
-        uo[1:] = np.cumsum([len(t[3]) for t in tasks])
-        units = np.ascontiguousarray(np.concatenate([np.asarray(t[3], np.uint8) for t in tasks] + [np.zeros(1, np.uint8)]))
-        g = np.array([t[4] for t in tasks], np.int32)
-        m = np.array([t[5] for t in tasks], np.int32)
-        d = np.array([t[6] for t in tasks], np.int32)
+        arrays = self._dp_task_arrays(tasks, pad_units=True)
         out = np.zeros((max(n, 1), 2, 8), np.int32)
-        self._check(self.lib.mtr_test_wrap_dp_pass(self.h, self.DP_PASSES[dp_pass], len(groups), go.ctypes.data, rd.ctypes.data, qs.ctypes.data, qe.ctypes.data,
-                                                   units.ctypes.data, uo.ctypes.data, g.ctypes.data, m.ctypes.data, d.ctypes.data, out.ctypes.data),
+        self._check(self.lib.mtr_test_wrap_dp_pass(self.h, self.DP_PASSES[dp_pass], len(groups), go.ctypes.data, *(a.ctypes.data for a in arrays), out.ctypes.data),
                     "mtr_test_wrap_dp_pass")
         return out[:n]
 

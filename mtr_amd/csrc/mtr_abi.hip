@@ -31,6 +31,7 @@
 #include "mtr_common.h"
 #include "file_state.h"
 #include "loci_args.h"
+#include "dp_task_plan.h"
 #include "k1_ranges.hip.inc"
 #include "k2_units.hip.inc"
 #include "k3_staged.hip.inc"
@@ -147,11 +148,6 @@ struct StagedBufs {
 static unsigned *st_line(unsigned long long *sc, int line) { return (unsigned *)(sc + (size_t)line * (ST_LINE_BYTES / 8)); }
 static const int st_sl_cont_slots[ST_NCLS] = { 6, 7, 9, 11, 12, 13, 14, 15 };     // st_sl_cont(class): the continuation lists' sub-list counters
 
-// the lane slots of S slots (lane_slots, with the locus search), numbered bucket by bucket: bucket k's bins are q_first[k] * MLO_N_CLASSES .. q_first[k + 1] * MLO_N_CLASSES
-struct LaneSlots {
-    std::vector<int32_t> slot_q, q_slot;
-    int q_first[5] = { 0, 0, 0, 0, 0 }, l_umax[4] = { 0, 0, 0, 0 }, u_all = 0, u_wave = 0;      // u_wave: the longest motif no lane takes
-};
 // what a catalogue call of either kind keeps for its copy and its statistics (genotype_host.hip.inc): the rows in CAT_ROW_COLS columns
 struct CatKept { bool ready = false; int64_t rows = 0; int64_t counts[4] = { 0, 0, 0, 0 }; double ms[3] = { 0, 0, 0 }; };
 #define CAT_ROW_COLS 9
@@ -1751,116 +1747,7 @@ extern "C" mtr_status mtr_report_device(mtr_ctx *ctx, const mtr_report_dst *dst,
     return MTR_OK;
 }
 
-// ---- the -a alignments of the report's repeats (report_align.hip.inc) -------------------------------------------------------
-// d_ra_sizes: [0, n) path bytes per read | [n, 2n) unit bytes per read | [2n, 3n] offsets of the reads' units | [3n+1, 4n+1] offsets of
-// their paths | [4n+2] cells of the largest DP.  Only those closing scalars and the number of columns come to the host.
-struct AlignSizes { int64_t *read_cap, *read_units, *unit_base, *cap_base, *max_cells; };
-static AlignSizes align_sizes(int64_t *base, int n) { return { base, base + n, base + 2 * n, base + 3 * n + 1, base + 4 * n + 2 }; }
-
-// what mtr_k_align and mtr_k_scan_offsets left of the report's repeats, for the kernels that print them
-static AlignRenderArgs render_args(const mtr_ctx *ctx)
-{
-    AlignRenderArgs a{};
-    a.b = view(ctx); a.n_repeats = (int32_t)ctx->rep_total;
-    a.read_idx = ctx->d_ra_i32; a.rep_start = ctx->d_ra_i32 + (size_t)ctx->rep_total; a.ops_len = ctx->d_ra_len; a.ends = ctx->d_ra_ends;
-    a.path = ctx->d_ra_ops; a.path_off = ctx->d_ra_off; a.rec_of = ctx->d_ra_rec; a.work_counter = ctx->d_work;
-    return a;
-}
-static mtr_status report_alignments(mtr_ctx *ctx)
-{
-    if (ctx->ra_ready) return MTR_OK;
-    { mtr_status st = report_chains(ctx); if (st != MTR_OK) return st; }
-    const int n = ctx->n_reads;
-    const int64_t R = ctx->rep_total;
-    HIPCHK(ctx->d_ra_coloff.ensure(((size_t)R + 1) * 8));
-    if (R == 0) {
-        HIPCHK(hipMemsetAsync(ctx->d_ra_coloff, 0, 8, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        ctx->ra_columns = 0; ctx->ra_ready = true;
-        return MTR_OK;
-    }
-    if (R > (int64_t)INT32_MAX) { ctx->err = "more reported repeats than one alignment launch takes"; return MTR_ERR_OVERFLOW; }
-    read_switches(ctx->sw);
-    const RecordView v = record_view(ctx); const ChainView ch = chain_view(ctx);
-    HIPCHK(ctx->d_ra_sizes.ensure(MTR_OFFSETS_LEN(n) * 8));
-    const AlignSizes z = align_sizes(ctx->d_ra_sizes, n);
-    HIPCHK(hipMemsetAsync(z.max_cells, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(mtr_k_align_sizes, dim3((unsigned)n), dim3(64), 0, ctx->stream, v, ch, (const int32_t *)ctx->d_lens,
-                       z.read_cap, z.read_units, (unsigned long long *)z.max_cells);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int64_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)z.read_cap, (int64_t)n, z.cap_base);
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int64_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)z.read_units, (int64_t)n, z.unit_base);
-    HIPCHK(hipGetLastError());
-    int64_t unit_bytes = 0, tail[2] = { 0, 0 };                           // tail: the paths' bytes (cap_base[n]), the largest DP's cells behind them
-    HIPCHK(hipMemcpyAsync(&unit_bytes, z.unit_base + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(tail, z.cap_base + n, 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    const size_t ops_bytes = (size_t)tail[0], cells = (size_t)std::max<int64_t>(tail[1], 1);
-    if (unit_bytes > (int64_t)INT32_MAX) { ctx->err = "the units of the reported repeats exceed 2 GB"; return MTR_ERR_OVERFLOW; }
-    const size_t per_wave = mtrc_align(cells + 256, 256);             // + slack: the traceback's dword loads read a few bytes past a row
-    size_t total = 0;
-    const int waves = pick_waves(ctx, (int)R, 8, per_wave, &total);
-    DBG("report_alignments: %lld repeats, cells %zu, waves %d, scratch %zu, paths %zu bytes", (long long)R, cells, waves, total, ops_bytes);
-    { mtr_status s = ensure_scratch(ctx, total); if (s != MTR_OK) return s; }
-    const size_t nt = (size_t)R;
-    HIPCHK(ctx->d_ra_i32.ensure((nt * 7 + 1) * 4)); HIPCHK(ctx->d_ra_len.ensure(nt * 4)); HIPCHK(ctx->d_ra_ends.ensure(nt * 8));
-    HIPCHK(ctx->d_ra_units.ensure((size_t)unit_bytes + 16)); HIPCHK(ctx->d_ra_ops.ensure(ops_bytes + 16));
-    HIPCHK(ctx->d_ra_off.ensure((nt + 1) * 8)); HIPCHK(ctx->d_ra_rec.ensure(nt * sizeof(void *)));
-    int32_t *d_i32 = ctx->d_ra_i32;
-    AlignTaskDst t{};
-    t.read_idx = d_i32; t.rep_start = d_i32 + nt; t.rep_end = d_i32 + 2 * nt; t.gain = d_i32 + 3 * nt; t.mism = d_i32 + 4 * nt; t.indel = d_i32 + 5 * nt;
-    t.unit_off = d_i32 + 6 * nt; t.ops_off = ctx->d_ra_off; t.units = ctx->d_ra_units; t.rec_of = ctx->d_ra_rec;
-    hipLaunchKernelGGL(mtr_k_align_tasks, dim3((unsigned)n), dim3(64), 0, ctx->stream, v, ch, (const int32_t *)ctx->d_lens,
-                       (const int64_t *)z.cap_base, (const int64_t *)z.unit_base, R, t);
-    HIPCHK(hipGetLastError());
-    AlignArgs a{};
-    a.b = view(ctx); a.n_tasks = (int32_t)R;
-    a.read_idx = t.read_idx; a.rep_start = t.rep_start; a.rep_end = t.rep_end; a.gain = t.gain; a.mism = t.mism; a.indel = t.indel;
-    a.unit_off = t.unit_off; a.units = ctx->d_ra_units;
-    a.ops = ctx->d_ra_ops; a.ops_off = ctx->d_ra_off; a.ops_len = ctx->d_ra_len; a.ends = ctx->d_ra_ends;
-    a.scratch = ctx->d_scratch; a.scratch_per_wave = per_wave; a.cells_cap = cells;
-    a.status = ctx->d_status; a.work_counter = ctx->d_work; a.counters = ctx->d_counters; a.dp16_max_rows = ctx->sw.dp16_max_rows;
-    HIPCHK(hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned), ctx->stream));
-    hipLaunchKernelGGL(mtr_k_align, dim3((unsigned)waves), dim3(64), 0, ctx->stream, a);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)ctx->d_ra_len, R, (int64_t *)ctx->d_ra_coloff);
-    HIPCHK(hipGetLastError());
-    int64_t columns = 0;
-    HIPCHK(copy_sync(ctx, &columns, ctx->d_ra_coloff + R, 8, hipMemcpyDeviceToHost));
-    { mtr_status st = check_status(ctx); if (st != MTR_OK) return st; }
-    ctx->ra_columns = columns; ctx->ra_ready = true;
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_report_alignments_device(mtr_ctx *ctx, const mtr_report_align_dst *dst, int64_t *out_repeats, int64_t *out_columns)
-{
-    if (!ctx || !out_repeats || !out_columns) return MTR_ERR_BAD_ARG;
-    { mtr_status r = results_ready(ctx, false); if (r != MTR_OK) return r; }
-    HIPCHK(hipSetDevice(ctx->device));
-    { mtr_status st = report_alignments(ctx); if (st != MTR_OK) return st; }
-    const int64_t R = ctx->rep_total, Cn = ctx->ra_columns;
-    *out_repeats = R; *out_columns = Cn;
-    if (!dst) return MTR_OK;
-    if (dst->cap_repeats < R || dst->cap_columns < Cn) {
-        ctx->err = "destination holds " + std::to_string(dst->cap_repeats) + " repeats / " + std::to_string(dst->cap_columns) + " columns, " +
-                   std::to_string(R) + " / " + std::to_string(Cn) + " needed";
-        return MTR_ERR_OVERFLOW;
-    }
-    if (!dst->col_off || (R > 0 && !dst->first) || (Cn > 0 && (!dst->ops || !dst->text))) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipMemcpyAsync(dst->col_off, ctx->d_ra_coloff, ((size_t)R + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    if (R > 0) {
-        AlignRenderArgs a = render_args(ctx);
-        a.col_off = ctx->d_ra_coloff; a.n_columns = Cn;
-        a.ops = dst->ops; a.text = dst->text; a.first = dst->first;
-        HIPCHK(hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned), ctx->stream));
-        const unsigned waves = (unsigned)std::min<int64_t>(R, (int64_t)ctx->n_cu * 16);
-        hipLaunchKernelGGL(mtr_k_align_render, dim3(waves), dim3(64), 0, ctx->stream, a);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
+#include "align_host.hip.inc"
 
 // ---- the report as text (report_text.hip.inc) ----------------------------------------------------------------------------------
 // Only the IDs go to the device and only the byte count comes back.
@@ -2108,8 +1995,7 @@ extern "C" mtr_status mtr_search_motifs_device(mtr_ctx *ctx, const char *motifs,
     std::vector<uint8_t> units; std::vector<int32_t> unit_off; std::vector<uint64_t> bits;
     motif_slots(motifs, motif_off, n_motifs, ns, units, unit_off, bits);
     // the work lists: one per bucket of the lane path (groups of 64 reads of the order from n_long on), one of the wave path (reads)
-    enum { N_LISTS = 5 };
-    static const int bucket_ub[4] = { 4, 8, 16, 32 };
+    enum { N_LISTS = DP_LAUNCHES };
     std::vector<int32_t> l_slot[N_LISTS]; std::vector<int64_t> l_first[N_LISTS]; int l_umax[N_LISTS] = { 0, 0, 0, 0, 0 };
     const int64_t groups = ((int64_t)(n - n_long) + 63) / 64;
     for (int k = 0; k < N_LISTS; k++) l_first[k].push_back(0);
@@ -2117,7 +2003,7 @@ extern "C" mtr_status mtr_search_motifs_device(mtr_ctx *ctx, const char *motifs,
         const int U = unit_off[(size_t)slot + 1] - unit_off[(size_t)slot];
         const bool lane = U <= lane_max && groups > 0;
         if (lane) {
-            int k = 0; while (bucket_ub[k] < U) k++;
+            int k = 0; while (dp_bucket_ub(k) < U) k++;
             l_slot[k].push_back(slot); l_first[k].push_back(l_first[k].back() + groups); l_umax[k] = std::max(l_umax[k], U);
         }
         const int64_t by_wave = U <= lane_max ? n_long : n;
@@ -2137,17 +2023,10 @@ extern "C" mtr_status mtr_search_motifs_device(mtr_ctx *ctx, const char *motifs,
         HIPCHK(copy_sync(ctx, d_slots + (size_t)k * sS, l_slot[k].data(), l_slot[k].size() * 4, hipMemcpyHostToDevice));
         HIPCHK(copy_sync(ctx, d_firsts + (size_t)k * (sS + 1), l_first[k].data(), l_first[k].size() * 8, hipMemcpyHostToDevice));
     }
-    // the launches' wavefronts and scratch: a lane wavefront holds rows x dwords x 64 lanes of cells, a wave wavefront one code matrix as mtr_test_wrap_dp's
-    size_t per_wave[N_LISTS] = { 0 }, scratch = 0; int waves[N_LISTS] = { 0 };
-    const size_t wave_cells = (size_t)L_first * (size_t)(l_umax[4] + 1);
-    for (int k = 0; k < N_LISTS; k++) {
-        if (l_slot[k].empty()) continue;
-        per_wave[k] = k < 4 ? mtrc_align((size_t)L_lane * (size_t)mdp_dwords(l_umax[k]) * 256, 256) : mtrc_align(wave_cells + 256, 256);
-        size_t total = 0;
-        waves[k] = pick_waves(ctx, (int)std::min<int64_t>(l_first[k].back(), INT32_MAX), k < 4 ? 16 : 8, per_wave[k], &total);
-        scratch = std::max(scratch, total);
-    }
-    { mtr_status s = ensure_scratch(ctx, scratch); if (s != MTR_OK) return s; }
+    // the launches' wavefronts and scratch (dp_task_plan.h: the five-launch plan)
+    const int64_t l_items[N_LISTS] = { l_first[0].back(), l_first[1].back(), l_first[2].back(), l_first[3].back(), l_first[4].back() };
+    const DpLaunchPlan plan = dp_search_plan(L_lane, L_first, l_umax, l_items, DpPick{ ctx });
+    { mtr_status s = ensure_scratch(ctx, plan.scratch); if (s != MTR_OK) return s; }
     HIPCHK(hipMemsetAsync(ctx->d_ms_status, 0, 4, ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_ms_counter, 0, N_LISTS * 8, ctx->stream));
     MotifSearchArgs a{};
@@ -2155,16 +2034,13 @@ extern "C" mtr_status mtr_search_motifs_device(mtr_ctx *ctx, const char *motifs,
     a.order = d_order; a.n_reads = n; a.n_long = n_long; a.units = ctx->d_ms_units; a.unit_off = d_uoff; a.bits = (const uint64_t *)d_bits;
     a.n_motifs = n_motifs; a.n_strands = ns; a.G = gain; a.MM = mismatch; a.D = indel; a.res = ctx->d_ms_res;
     a.scratch = ctx->d_scratch; a.status = ctx->d_ms_status; a.dp16_max_rows = ctx->sw.dp16_max_rows;
-    for (int k = 0; k < N_LISTS; k++) {
-        if (l_slot[k].empty()) continue;
+    const mtr_status launched = dp_plan_launches(ctx, plan, a, (unsigned long long *)ctx->d_ms_counter, [&](int k, dim3 grid, dim3 block) {
         a.work = { d_slots + (size_t)k * sS, d_firsts + (size_t)k * (sS + 1), (int32_t)l_slot[k].size(), l_first[k].back() };
-        a.counter = (unsigned long long *)ctx->d_ms_counter + k; a.scratch_per_wave = per_wave[k]; a.cells_cap = k < 4 ? 0 : wave_cells;
-        DBG("search_motifs: list %d: %zu slots, %lld items, %d wavefronts of %zu bytes", k, l_slot[k].size(), (long long)l_first[k].back(), waves[k], per_wave[k]);
-        const dim3 grid((unsigned)waves[k]), block(64);
-        if (k < 4) LAUNCH_BY_BUCKET(mtr_k_motif_lanes, bucket_ub[k], grid, block, ctx->stream, a);
+        DBG("search_motifs: list %d: %zu slots, %lld items, %d wavefronts of %zu bytes", k, l_slot[k].size(), (long long)l_first[k].back(), plan.waves[k], plan.per_wave[k]);
+        if (k < DP_LANE_BUCKETS) LAUNCH_BY_BUCKET(mtr_k_motif_lanes, dp_bucket_ub(k), grid, block, ctx->stream, a);
         else hipLaunchKernelGGL(mtr_k_motif_waves, grid, block, 0, ctx->stream, a);
-        HIPCHK(hipGetLastError());
-    }
+    });
+    if (launched != MTR_OK) return launched;
     // the status before the columns: a failed search writes nothing
     int32_t dev = 0;
     HIPCHK(copy_sync(ctx, &dev, ctx->d_ms_status, 4, hipMemcpyDeviceToHost));
@@ -2195,48 +2071,13 @@ static hipError_t grow_keeping(mtr_ctx *ctx, DevBuf<T> &b, size_t keep, size_t b
     return e;
 }
 
-static LaneSlots lane_slots(const std::vector<int32_t> &unit_off, int S, int lane_max)
-{
-    static const int bucket_ub[4] = { 4, 8, 16, 32 };
-    LaneSlots ls;
-    ls.slot_q.assign((size_t)S, -1);
-    for (int k = 0; k < 4; k++) {
-        ls.q_first[k] = (int)ls.q_slot.size();
-        for (int slot = 0; slot < S; slot++) {
-            const int U = unit_off[(size_t)slot + 1] - unit_off[(size_t)slot];
-            if (U > lane_max || mdp_bucket(U) != bucket_ub[k]) continue;
-            ls.slot_q[(size_t)slot] = (int32_t)ls.q_slot.size(); ls.q_slot.push_back(slot); ls.l_umax[k] = std::max(ls.l_umax[k], U);
-        }
-    }
-    ls.q_first[4] = (int)ls.q_slot.size();
-    for (int slot = 0; slot < S; slot++) {
-        const int U = unit_off[(size_t)slot + 1] - unit_off[(size_t)slot];
-        ls.u_all = std::max(ls.u_all, U);
-        if (ls.slot_q[(size_t)slot] < 0) ls.u_wave = std::max(ls.u_wave, U);
-    }
-    return ls;
-}
-
 // One round's alignments: `tasks` tasks over a.iv (a.n_iv intervals of at most max_len bases), everything of `a` set but what one launch has of
-// its own.  Sizes the launches' wavefronts and scratch as the search does - lanes hold rows x dwords x 64 lanes of cells, a wave wavefront one
-// code matrix - then bins the tasks and enqueues the up to five DP launches.  counters: five item counters.  who: the caller, for MTR_DEBUG.
+// its own.  Plans the launches as the search does, bins the tasks, enqueues the up to five DP launches.  counters: five item counters.  who: for MTR_DEBUG.
 static mtr_status loci_round(mtr_ctx *ctx, LociArgs &a, const LaneSlots &ls, int64_t tasks, int max_len, unsigned long long *counters, const char *who, int round)
 {
-    const int lane_rows = a.lane_rows;
     const size_t nb = (size_t)a.n_bins, nt = (size_t)tasks;
-    const int lane_len = std::min(max_len, lane_rows);
-    const bool by_wave = ls.u_wave > 0 || max_len > lane_rows;
-    const size_t wave_cells = (size_t)max_len * (size_t)((max_len > lane_rows ? ls.u_all : ls.u_wave) + 1);
-    size_t per_wave[5] = { 0 }, scratch = 0; int waves[5] = { 0 };
-    for (int k = 0; k < 5; k++) {
-        if (k < 4 ? ls.q_first[k] == ls.q_first[k + 1] : !by_wave) continue;
-        per_wave[k] = k < 4 ? mtrc_align((size_t)lane_len * (size_t)mdp_dwords(ls.l_umax[k]) * 256, 256) : mtrc_align(wave_cells + 256, 256);
-        const int64_t items = k < 4 ? tasks / 64 + (int64_t)(ls.q_first[k + 1] - ls.q_first[k]) * MLO_N_CLASSES : tasks;      // (a bound: the groups are counted on the device)
-        size_t total = 0;
-        waves[k] = pick_waves(ctx, (int)std::min<int64_t>(items, INT32_MAX), k < 4 ? 16 : 8, per_wave[k], &total);
-        scratch = std::max(scratch, total);
-    }
-    { mtr_status s = ensure_scratch(ctx, scratch); if (s != MTR_OK) return s; }
+    const DpLaunchPlan plan = dp_loci_plan(ls, tasks, max_len, a.lane_rows, DpPick{ ctx });
+    { mtr_status s = ensure_scratch(ctx, plan.scratch); if (s != MTR_OK) return s; }
     a.scratch = ctx->d_scratch;
     if (nb > 0) HIPCHK(hipMemsetAsync(a.hist, 0, nb * 4, ctx->stream));
     HIPCHK(hipMemsetAsync(counters, 0, 5 * 8, ctx->stream));
@@ -2249,17 +2090,12 @@ static mtr_status loci_round(mtr_ctx *ctx, LociArgs &a, const LaneSlots &ls, int
         hipLaunchKernelGGL(mtr_k_loci_scatter, per_task, b256, 0, ctx->stream, a);
     }
     HIPCHK(hipGetLastError());
-    for (int k = 0; k < 5; k++) {
-        if (waves[k] == 0) continue;
-        a.counter = counters + k; a.scratch_per_wave = per_wave[k]; a.cells_cap = k < 4 ? 0 : wave_cells;
-        if (k < 4) { a.bin0 = ls.q_first[k] * MLO_N_CLASSES; a.bin1 = ls.q_first[k + 1] * MLO_N_CLASSES; }
-        DBG("%s: round %d, %lld intervals of at most %d bases, launch %d: %d wavefronts of %zu bytes", who, round, (long long)a.n_iv, max_len, k, waves[k], per_wave[k]);
-        const dim3 grid((unsigned)waves[k]), block(64);
-        if (k < 4) LAUNCH_BY_BUCKET(mtr_k_motif_loci_lanes, 4 << k, grid, block, ctx->stream, a);
+    return dp_plan_launches(ctx, plan, a, counters, [&](int k, dim3 grid, dim3 block) {
+        if (k < DP_LANE_BUCKETS) { a.bin0 = ls.q_first[k] * MLO_N_CLASSES; a.bin1 = ls.q_first[k + 1] * MLO_N_CLASSES; }
+        DBG("%s: round %d, %lld intervals of at most %d bases, launch %d: %d wavefronts of %zu bytes", who, round, (long long)a.n_iv, max_len, k, plan.waves[k], plan.per_wave[k]);
+        if (k < DP_LANE_BUCKETS) LAUNCH_BY_BUCKET(mtr_k_motif_loci_lanes, dp_bucket_ub(k), grid, block, ctx->stream, a);
         else hipLaunchKernelGGL(mtr_k_motif_loci_waves, grid, block, 0, ctx->stream, a);
-        HIPCHK(hipGetLastError());
-    }
-    return MTR_OK;
+    });
 }
 
 extern "C" mtr_status mtr_search_motif_loci_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs, int32_t gain, int32_t mismatch,
@@ -3027,153 +2863,6 @@ extern "C" mtr_status mtr_fasta_index(const mtr_ctx *ctx, int32_t *lens, int64_t
     return MTR_OK;
 }
 
-extern "C" mtr_status mtr_test_report_lines(mtr_ctx *ctx, int32_t n_rows, const int32_t *fields, const int32_t *read_len, const uint8_t *units,
-                                            const int64_t *unit_off, const char *ids, const int64_t *id_off, uint8_t **out_text, int64_t **out_off)
-{
-    if (!ctx || n_rows < 0 || !unit_off || !id_off || !out_text || !out_off) return MTR_ERR_BAD_ARG;
-    if (n_rows > 0 && (!fields || !read_len)) return MTR_ERR_BAD_ARG;
-    if (unit_off[0] != 0 || id_off[0] != 0) { ctx->err = "unit_off[0] and id_off[0] must be 0"; return MTR_ERR_BAD_ARG; }
-    for (int k = 0; k < n_rows; k++)
-        if (unit_off[k + 1] < unit_off[k] || unit_off[k + 1] - unit_off[k] > (1 << 24) || id_off[k + 1] < id_off[k]) { ctx->err = "bad row " + std::to_string(k); return MTR_ERR_BAD_ARG; }
-    const size_t nr = (size_t)n_rows, ub = (size_t)unit_off[nr], ib = (size_t)id_off[nr];
-    if ((ub > 0 && !units) || (ib > 0 && !ids)) return MTR_ERR_BAD_ARG;
-    HIPCHK(hipSetDevice(ctx->device));
-    HostArray<int64_t> off = host_array<int64_t>(nr + 1);
-    if (!off) return MTR_ERR_OOM;
-    off[0] = 0;
-    int64_t B = 0;
-    if (n_rows > 0) {
-        // d_t_i32: fields | read_len;  d_t_units: units | ids;  d_t_i64: unit_off | id_off | bytes | byte_off
-        HIPCHK(ctx->d_t_i32.ensure(nr * 15 * 4)); HIPCHK(ctx->d_t_units.ensure(ub + ib + 16)); HIPCHK(ctx->d_t_i64.ensure((4 * nr + 3) * 8));
-        int32_t *d_f = ctx->d_t_i32, *d_len = d_f + 14 * nr;
-        uint8_t *d_units = ctx->d_t_units, *d_ids = d_units + ub;
-        int64_t *d_uoff = ctx->d_t_i64, *d_ioff = d_uoff + nr + 1, *d_bytes = d_ioff + nr + 1, *d_boff = d_bytes + nr;
-        HIPCHK(copy_sync(ctx, d_f, fields, nr * 14 * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_len, read_len, nr * 4, hipMemcpyHostToDevice));
-        if (ub > 0) HIPCHK(copy_sync(ctx, d_units, units, ub, hipMemcpyHostToDevice));
-        if (ib > 0) HIPCHK(copy_sync(ctx, d_ids, ids, ib, hipMemcpyHostToDevice));
-        HIPCHK(copy_sync(ctx, d_uoff, unit_off, (nr + 1) * 8, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_ioff, id_off, (nr + 1) * 8, hipMemcpyHostToDevice));
-        const unsigned blocks = (unsigned)((nr + 63) / 64);
-        hipLaunchKernelGGL(mtr_k_text_rows<false>, dim3(blocks), dim3(64), 0, ctx->stream, n_rows, (const int32_t *)d_f, (const int32_t *)d_len, (const uint8_t *)d_units,
-                           (const int64_t *)d_uoff, (const uint8_t *)d_ids, (const int64_t *)d_ioff, d_bytes, (const int64_t *)d_boff, (uint8_t *)nullptr);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(mtr_k_scan_offsets<int64_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int64_t *)d_bytes, (int64_t)n_rows, d_boff);
-        HIPCHK(hipGetLastError());
-        HIPCHK(copy_sync(ctx, off.get(), d_boff, (nr + 1) * 8, hipMemcpyDeviceToHost));
-        B = off[nr];
-        HIPCHK(ctx->d_t_text.ensure((size_t)B + 16));
-        hipLaunchKernelGGL(mtr_k_text_rows<true>, dim3(blocks), dim3(64), 0, ctx->stream, n_rows, (const int32_t *)d_f, (const int32_t *)d_len, (const uint8_t *)d_units,
-                           (const int64_t *)d_uoff, (const uint8_t *)d_ids, (const int64_t *)d_ioff, d_bytes, (const int64_t *)d_boff, (uint8_t *)ctx->d_t_text);
-        HIPCHK(hipGetLastError());
-    }
-    HostArray<uint8_t> text = host_array<uint8_t>((size_t)std::max<int64_t>(B, 1));
-    if (!text) return MTR_ERR_OOM;
-    if (B > 0) HIPCHK(copy_sync(ctx, text.get(), ctx->d_t_text, (size_t)B, hipMemcpyDeviceToHost));
-    *out_text = text.release(); *out_off = off.release();
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_test_chain(mtr_ctx *ctx, int32_t n_sets, const int64_t *set_off, const int32_t *start, const int32_t *end,
-                                     const int32_t *matches, int32_t **out_len, int32_t **out_idx)
-{
-    if (!ctx || n_sets < 0 || !set_off || !out_len || !out_idx) return MTR_ERR_BAD_ARG;
-    if (set_off[0] != 0) { ctx->err = "set_off[0] must be 0"; return MTR_ERR_BAD_ARG; }
-    for (int k = 0; k < n_sets; k++)
-        if (set_off[k + 1] < set_off[k] || set_off[k + 1] - set_off[k] > (1 << 24)) { ctx->err = "bad set " + std::to_string(k); return MTR_ERR_BAD_ARG; }
-    const int64_t total = set_off[n_sets];
-    if (total > 0 && (!start || !end || !matches)) return MTR_ERR_BAD_ARG;
-    HIPCHK(hipSetDevice(ctx->device));
-    HostArray<int32_t> len = host_array<int32_t>((size_t)std::max(n_sets, 1)), idx = host_array<int32_t>((size_t)std::max<int64_t>(total, 1));
-    if (!len || !idx) return MTR_ERR_OOM;
-    if (n_sets > 0) {
-        std::vector<int64_t> off((size_t)2 * n_sets + 1);              // set offsets | scratch offsets
-        int64_t scr = 0;
-        for (int k = 0; k <= n_sets; k++) off[(size_t)k] = set_off[k];
-        for (int k = 0; k < n_sets; k++) {
-            const int64_t c = set_off[k + 1] - set_off[k];
-            off[(size_t)n_sets + 1 + k] = c > MTR_CHAIN_LDS_RECS ? scr : -1;
-            if (c > MTR_CHAIN_LDS_RECS) scr += MTR_CHAIN_INTS(c);
-        }
-        const size_t t = (size_t)total;
-        HIPCHK(ctx->d_t_i32.ensure((3 * t + 1) * 4)); HIPCHK(ctx->d_t_out.ensure((t + (size_t)n_sets) * 4));
-        HIPCHK(ctx->d_ch_scr.ensure((size_t)std::max<int64_t>(scr, 1) * 4)); HIPCHK(ctx->d_t_i64.ensure(off.size() * 8));
-        int32_t *d_in = ctx->d_t_i32, *d_out = ctx->d_t_out;
-        if (t > 0) {
-            HIPCHK(copy_sync(ctx, d_in, start, t * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_in + t, end, t * 4, hipMemcpyHostToDevice));
-            HIPCHK(copy_sync(ctx, d_in + 2 * t, matches, t * 4, hipMemcpyHostToDevice));
-        }
-        HIPCHK(copy_sync(ctx, ctx->d_t_i64, off.data(), off.size() * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(mtr_k_chain_sets, dim3((unsigned)n_sets), dim3(64), 0, ctx->stream, d_in, d_in + t, d_in + 2 * t, ctx->d_t_i64, n_sets,
-                           ctx->d_t_i64 + n_sets + 1, ctx->d_ch_scr, d_out, d_out + t);
-        HIPCHK(hipGetLastError());
-        HIPCHK(copy_sync(ctx, len.get(), d_out + t, (size_t)n_sets * 4, hipMemcpyDeviceToHost));
-        if (t > 0) HIPCHK(copy_sync(ctx, idx.get(), d_out, t * 4, hipMemcpyDeviceToHost));
-    }
-    *out_len = len.release(); *out_idx = idx.release();
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_test_unit_motifs(mtr_ctx *ctx, int32_t n, const char *units, const int64_t *unit_off, const int32_t *read, const int32_t *copies,
-                                           const int32_t *repeat_len, int64_t table_slots, uint8_t **strand, int32_t **rotation, int32_t **motif_len, int32_t **group,
-                                           int64_t *out_groups, int64_t **motif_off, uint8_t **motifs, int32_t **g_first, int32_t **g_repeats, int32_t **g_reads,
-                                           int64_t **g_copies, int64_t **g_bases)
-{
-    if (!ctx || n < 0 || !unit_off || !strand || !rotation || !motif_len || !group || !out_groups || !motif_off || !motifs || !g_first || !g_repeats || !g_reads ||
-        !g_copies || !g_bases) return MTR_ERR_BAD_ARG;
-    if (n > 0 && (!read || !copies || !repeat_len)) return MTR_ERR_BAD_ARG;
-    if (n > INT32_MAX / 2) { ctx->err = "too many units"; return MTR_ERR_BAD_ARG; }
-    if (unit_off[0] != 0) { ctx->err = "unit_off[0] must be 0"; return MTR_ERR_BAD_ARG; }
-    if (table_slots != 0 && (table_slots <= n || table_slots > ((int64_t)1 << 31) || (table_slots & (table_slots - 1)) != 0)) {
-        ctx->err = "table_slots must be 0 or a power of two above the number of units"; return MTR_ERR_BAD_ARG;
-    }
-    for (int k = 0; k < n; k++) {
-        if (unit_off[k + 1] < unit_off[k] || unit_off[k + 1] - unit_off[k] > MTR_MAX_PERIOD) { ctx->err = "unit " + std::to_string(k) + ": length outside 0..500"; return MTR_ERR_BAD_ARG; }
-        if (k > 0 && read[k] < read[k - 1]) { ctx->err = "read decreases at unit " + std::to_string(k); return MTR_ERR_BAD_ARG; }
-    }
-    const size_t nr = (size_t)n, ub = (size_t)unit_off[nr];
-    if (ub > 0 && !units) return MTR_ERR_BAD_ARG;
-    for (size_t b = 0; b < ub; b++)
-        if (units[b] != 'A' && units[b] != 'C' && units[b] != 'G' && units[b] != 'T') { ctx->err = "byte " + std::to_string(b) + " of the units is none of ACGT"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->mo_ready = false;                                        // the catalogue's buffers are used: a resident batch makes its own again
-    MotifWork w{};
-    { mtr_status st = motif_work(ctx, n, (int64_t)ub, w); if (st != MTR_OK) return st; }
-    if (n > 0) {
-        // d_t_units: units;  d_t_i64: unit_off;  d_t_i32: read | copies | repeat_len
-        HIPCHK(ctx->d_t_units.ensure(ub + 16)); HIPCHK(ctx->d_t_i64.ensure((nr + 1) * 8)); HIPCHK(ctx->d_t_i32.ensure(3 * nr * 4));
-        int32_t *d_in = ctx->d_t_i32;
-        if (ub > 0) HIPCHK(copy_sync(ctx, ctx->d_t_units, units, ub, hipMemcpyHostToDevice));
-        HIPCHK(copy_sync(ctx, ctx->d_t_i64, unit_off, (nr + 1) * 8, hipMemcpyHostToDevice));
-        HIPCHK(copy_sync(ctx, d_in, read, nr * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_in + nr, copies, nr * 4, hipMemcpyHostToDevice));
-        HIPCHK(copy_sync(ctx, d_in + 2 * nr, repeat_len, nr * 4, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(mtr_k_unit_motif_rows, dim3((unsigned)((nr + MOTIF_TILE - 1) / MOTIF_TILE)), dim3(64), 0, ctx->stream, n, (const uint8_t *)ctx->d_t_units,
-                           (const int64_t *)ctx->d_t_i64, (const int32_t *)d_in, (const int32_t *)(d_in + nr), (const int32_t *)(d_in + 2 * nr), w.rows);
-        HIPCHK(hipGetLastError());
-    }
-    { mtr_status st = motif_group(ctx, n, table_slots, w); if (st != MTR_OK) return st; }
-    const size_t g = (size_t)ctx->mo_groups, mb = (size_t)ctx->mo_motif_bytes, n1 = std::max<size_t>(nr, 1), g1 = std::max<size_t>(g, 1);
-    const MotifGroups mg = motif_groups(ctx, w);
-    HostArray<uint8_t> h_strand = host_array<uint8_t>(n1), h_motifs = host_array<uint8_t>(std::max<size_t>(mb, 1));
-    HostArray<int32_t> h_rot = host_array<int32_t>(n1), h_len = host_array<int32_t>(n1), h_group = host_array<int32_t>(n1);
-    HostArray<int32_t> h_first = host_array<int32_t>(g1), h_repeats = host_array<int32_t>(g1), h_reads = host_array<int32_t>(g1);
-    HostArray<int64_t> h_off = host_array<int64_t>(g + 1), h_copies = host_array<int64_t>(g1), h_bases = host_array<int64_t>(g1);
-    if (!h_strand || !h_motifs || !h_rot || !h_len || !h_group || !h_first || !h_repeats || !h_reads || !h_off || !h_copies || !h_bases) return MTR_ERR_OOM;
-    const hipMemcpyKind dh = hipMemcpyDeviceToHost;
-    HIPCHK(copy_sync(ctx, h_off.get(), mg.motif_off, (g + 1) * 8, dh));
-    if (n > 0) {
-        HIPCHK(copy_sync(ctx, h_strand.get(), w.rows.strand, nr, dh)); HIPCHK(copy_sync(ctx, h_rot.get(), w.rows.rotation, nr * 4, dh));
-        HIPCHK(copy_sync(ctx, h_len.get(), w.rows.motif_len, nr * 4, dh)); HIPCHK(copy_sync(ctx, h_group.get(), mg.group, nr * 4, dh));
-        HIPCHK(copy_sync(ctx, h_first.get(), mg.first, g * 4, dh)); HIPCHK(copy_sync(ctx, h_repeats.get(), mg.repeats, g * 4, dh));
-        HIPCHK(copy_sync(ctx, h_reads.get(), mg.reads, g * 4, dh)); HIPCHK(copy_sync(ctx, h_copies.get(), mg.copies, g * 8, dh));
-        HIPCHK(copy_sync(ctx, h_bases.get(), mg.bases, g * 8, dh));
-        if (mb > 0) HIPCHK(copy_sync(ctx, h_motifs.get(), mg.motifs, mb, dh));
-    }
-    *out_groups = (int64_t)g;
-    *strand = h_strand.release(); *rotation = h_rot.release(); *motif_len = h_len.release(); *group = h_group.release();
-    *motif_off = h_off.release(); *motifs = h_motifs.release(); *g_first = h_first.release(); *g_repeats = h_repeats.release(); *g_reads = h_reads.release();
-    *g_copies = h_copies.release(); *g_bases = h_bases.release();
-    return MTR_OK;
-}
-
 // host-only conversions between the wire form and mtr_record
 extern "C" mtr_status mtr_unpack_records(const uint8_t *blob, int64_t bytes, int64_t n_records, mtr_record *out)
 {
@@ -3245,337 +2934,7 @@ extern "C" mtr_status mtr_get_counters(const mtr_ctx *ctx, int64_t *out, int32_t
     return MTR_OK;
 }
 
-extern "C" mtr_status mtr_test_ranges(mtr_ctx *ctx, int32_t **out_counts, int32_t **out_start, int32_t **out_end,
-                                      int32_t **out_w, uint64_t **out_di_bits, int64_t *out_total)
-{
-    if (!ctx || !out_counts || !out_start || !out_end || !out_w || !out_di_bits) return MTR_ERR_BAD_ARG;
-    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    HIPCHK(hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * CNT_N, ctx->stream));
-    mtr_status s = launch_k1(ctx); if (s != MTR_OK) return s;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1])); ctx->kt[0].ms = ms; ctx->kt[0].launches = 1;
-    s = check_status(ctx); if (s != MTR_OK) return s;
-    const int n = ctx->n_reads;
-    std::vector<int32_t> cnt((size_t)n), st((size_t)ctx->total_rcap), en((size_t)ctx->total_rcap), ww((size_t)ctx->total_rcap);
-    std::vector<uint64_t> di((size_t)ctx->total_rcap);
-    HIPCHK(copy_sync(ctx, cnt.data(), ctx->d_rcount, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(ctx, st.data(), ctx->d_rstart, st.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(ctx, en.data(), ctx->d_rend, en.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(ctx, ww.data(), ctx->d_rw, ww.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(ctx, di.data(), ctx->d_rdi, di.size() * 8, hipMemcpyDeviceToHost));
-    int64_t total = 0; for (int i = 0; i < n; i++) total += cnt[(size_t)i];
-    const size_t m = (size_t)std::max<int64_t>(total, 1);
-    HostArray<int32_t> oc = host_array<int32_t>((size_t)n), os = host_array<int32_t>(m), oe = host_array<int32_t>(m), ow = host_array<int32_t>(m);
-    HostArray<uint64_t> od = host_array<uint64_t>(m);
-    if (!oc || !os || !oe || !ow || !od) return MTR_ERR_OOM;
-    int64_t p = 0;
-    for (int i = 0; i < n; i++) {
-        oc[i] = cnt[(size_t)i];
-        for (int t = 0; t < cnt[(size_t)i]; t++, p++) {
-            size_t q = (size_t)ctx->roff[(size_t)i] + (size_t)t;
-            os[p] = st[q]; oe[p] = en[q]; ow[p] = ww[q]; od[p] = di[q];
-        }
-    }
-    *out_counts = oc.release(); *out_start = os.release(); *out_end = oe.release(); *out_w = ow.release(); *out_di_bits = od.release(); if (out_total) *out_total = total;
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_test_file_tail(mtr_ctx *ctx, uint16_t **out_tail, int64_t **out_tail_off, uint8_t **out_after)
-{
-    if (!ctx || !out_tail || !out_tail_off || !out_after) return MTR_ERR_BAD_ARG;
-    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)ctx->n_reads;
-    const int64_t entries = ctx->file_order ? ctx->tail_entries : 0;
-    HostArray<uint16_t> tl = host_array<uint16_t>((size_t)std::max<int64_t>(entries, 1));
-    HostArray<int64_t> to = host_array<int64_t>(n + 1);
-    HostArray<uint8_t> af = host_array<uint8_t>(n * 2);
-    if (!tl || !to || !af) return MTR_ERR_OOM;
-    tl[0] = 0; memset(to.get(), 0, (n + 1) * 8); memset(af.get(), 0, n * 2);
-    if (ctx->file_order) {
-        HIPCHK(copy_sync(ctx, to.get(), ctx->d_tail_off, (n + 1) * 8, hipMemcpyDeviceToHost));
-        if (entries > 0) HIPCHK(copy_sync(ctx, tl.get(), ctx->d_tail, (size_t)entries * 2, hipMemcpyDeviceToHost));
-        if (ctx->after.size() >= n * 2) memcpy(af.get(), ctx->after.data(), n * 2);
-    }
-    // id 0 of mtr_get_kernel_times: mtr_k_file_tail of this batch's upload (launches = 0: a host upload, or no tail entry)
-    ctx->kt[0].ms = ctx->file_order ? ctx->fo_tail_ms : 0; ctx->kt[0].launches = ctx->file_order ? ctx->fo_tail_launches : 0;
-    *out_tail = tl.release(); *out_tail_off = to.release(); *out_after = af.release();
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_test_wrap_dp(mtr_ctx *ctx, int32_t n_tasks, const int32_t *read_idx, const int32_t *query_start,
-                                       const int32_t *query_end, const uint8_t *units, const int32_t *unit_off,
-                                       const int32_t *gain, const int32_t *mismatch, const int32_t *indel, int32_t *out8)
-{
-    if (!ctx || n_tasks <= 0 || !read_idx || !query_start || !query_end || !units || !unit_off || !gain || !mismatch || !indel || !out8) return MTR_ERR_BAD_ARG;
-    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    size_t cells = 1;
-    for (int t = 0; t < n_tasks; t++) {
-        int rd = read_idx[t];
-        int U = unit_off[t + 1] - unit_off[t];
-        if (rd < 0 || rd >= ctx->n_reads || query_start[t] < 0 || query_end[t] < query_start[t] || query_end[t] >= ctx->lens[(size_t)rd] || U <= 0 || U >= MTRC_MAX_PERIOD) { ctx->err = "bad DP task " + std::to_string(t); return MTR_ERR_BAD_ARG; }
-        cells = std::max(cells, (size_t)(query_end[t] - query_start[t] + 1) * (size_t)(U + 1));   // rows may be padded to an even length
-    }
-    size_t per_wave = mtrc_align(cells + 256, 256), total = 0;   // + slack: the traceback's dword loads read a few bytes past a row
-    int waves = pick_waves(ctx, n_tasks, 8, per_wave, &total);
-    DBG("test_wrap_dp: %d tasks, cells %zu, waves %d, scratch %zu", n_tasks, cells, waves, total);
-    mtr_status s = ensure_scratch(ctx, total); if (s != MTR_OK) return s;
-    const size_t nt = (size_t)n_tasks;
-    HIPCHK(ctx->d_t_i32.ensure((nt * 7 + 1) * 4)); HIPCHK(ctx->d_t_units.ensure((size_t)unit_off[n_tasks] + 16)); HIPCHK(ctx->d_t_out.ensure(nt * 8 * 4));
-    int32_t *d_i32 = ctx->d_t_i32; uint8_t *d_units = ctx->d_t_units; int32_t *d_out = ctx->d_t_out;
-    int32_t *d_rd = d_i32, *d_qs = d_i32 + nt, *d_qe = d_i32 + 2 * nt, *d_g = d_i32 + 3 * nt, *d_m = d_i32 + 4 * nt, *d_d = d_i32 + 5 * nt, *d_uo = d_i32 + 6 * nt;
-    HIPCHK(copy_sync(ctx, d_rd, read_idx, nt * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_qs, query_start, nt * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, d_qe, query_end, nt * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_g, gain, nt * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, d_m, mismatch, nt * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_d, indel, nt * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, d_uo, unit_off, (nt + 1) * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_units, units, (size_t)unit_off[n_tasks], hipMemcpyHostToDevice));
-    DpTestArgs a{};
-    a.b = view(ctx); a.n_tasks = n_tasks; a.read_idx = d_rd; a.qs = d_qs; a.qe = d_qe; a.units = d_units; a.unit_off = d_uo;
-    a.gain = d_g; a.mism = d_m; a.indel = d_d; a.out8 = d_out; a.scratch = ctx->d_scratch; a.scratch_per_wave = per_wave; a.cells_cap = cells;
-    a.status = ctx->d_status; a.work_counter = ctx->d_work; a.counters = ctx->d_counters; a.dp16_max_rows = ctx->sw.dp16_max_rows;
-    HIPCHK(hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned), ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * CNT_N, ctx->stream));
-    HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
-    DBG("test_wrap_dp: launching");
-    hipLaunchKernelGGL(mtr_k_dp_test, dim3((unsigned)waves), dim3(64), 0, ctx->stream, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    DBG("test_wrap_dp: kernel done");
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3])); ctx->kt[1].ms = ms; ctx->kt[1].launches = 1;
-    HIPCHK(copy_sync(ctx, ctx->counters, ctx->d_counters, sizeof(unsigned long long) * CNT_N, hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(ctx, out8, d_out, nt * 8 * 4, hipMemcpyDeviceToHost));
-    return check_status(ctx);
-}
-
-// polish_repeat alone, a task per wavefront turn (dp_test.hip.inc: mtr_k_polish_test), on the narrow scratch layout of the chain's polish kernel
-extern "C" mtr_status mtr_test_polish(mtr_ctx *ctx, int32_t n_tasks, const int32_t *read_idx, const int32_t *rep_start, const int32_t *rep_end,
-                                      const int32_t *k, const uint8_t *units, const int32_t *scores, const int32_t *unit_off,
-                                      uint8_t *out_units, int32_t *out_len)
-{
-    if (!ctx || n_tasks <= 0 || !read_idx || !rep_start || !rep_end || !k || !units || !scores || !unit_off || !out_units || !out_len) return MTR_ERR_BAD_ARG;
-    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
-    if (unit_off[0] != 0) { ctx->err = "unit_off[0] is not 0"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    for (int t = 0; t < n_tasks; t++) {
-        const int rd = read_idx[t], U = unit_off[t + 1] - unit_off[t];
-        if (rd < 0 || rd >= ctx->n_reads || rep_start[t] < 0 || rep_end[t] < rep_start[t] || rep_end[t] >= ctx->lens[(size_t)rd] || U <= 0 || U >= MTRC_MAX_PERIOD ||
-            k[t] < 2 || k[t] > MTRC_MAX_KMER) { ctx->err = "bad polish task " + std::to_string(t); return MTR_ERR_BAD_ARG; }
-    }
-    const size_t nt = (size_t)n_tasks, ub = (size_t)unit_off[n_tasks];
-    const size_t per_wave = k2_layout(ctx->Lmax, 256).total;
-    size_t total = 0;
-    const int waves = pick_waves(ctx, n_tasks, 8, per_wave, &total);
-    mtr_status s = ensure_scratch(ctx, total); if (s != MTR_OK) return s;
-    // d_t_i32: read | rep_start | rep_end | k | unit_off | scores;  d_t_out: lengths | units
-    HIPCHK(ctx->d_t_i32.ensure((nt * 5 + 1 + ub) * 4)); HIPCHK(ctx->d_t_units.ensure(ub + 16)); HIPCHK(ctx->d_t_out.ensure(nt * 4 + nt * MTRC_MAX_PERIOD + 16));
-    int32_t *d_i32 = ctx->d_t_i32; uint8_t *d_units = ctx->d_t_units; int32_t *d_len = ctx->d_t_out; uint8_t *d_out = (uint8_t *)(d_len + nt);
-    int32_t *d_rd = d_i32, *d_rs = d_i32 + nt, *d_re = d_i32 + 2 * nt, *d_k = d_i32 + 3 * nt, *d_uo = d_i32 + 4 * nt, *d_sc = d_i32 + 5 * nt + 1;
-    HIPCHK(copy_sync(ctx, d_rd, read_idx, nt * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_rs, rep_start, nt * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, d_re, rep_end, nt * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_k, k, nt * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, d_uo, unit_off, (nt + 1) * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_sc, scores, ub * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, d_units, units, ub, hipMemcpyHostToDevice));
-    PolishTestArgs p{};
-    k2_args(ctx, p.a, per_wave); p.a.cells_cap = 256; p.a.trace_cap = 0;
-    p.n_tasks = n_tasks; p.read_idx = d_rd; p.rep_start = d_rs; p.rep_end = d_re; p.k = d_k; p.units = d_units; p.scores = d_sc; p.unit_off = d_uo;
-    p.out_units = d_out; p.out_len = d_len;
-    HIPCHK(hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned), ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * CNT_N, ctx->stream));
-    hipLaunchKernelGGL(mtr_k_polish_test, dim3((unsigned)waves), dim3(64), 0, ctx->stream, p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(copy_sync(ctx, ctx->counters, ctx->d_counters, sizeof(unsigned long long) * CNT_N, hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(ctx, out_len, d_len, nt * 4, hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(ctx, out_units, d_out, nt * MTRC_MAX_PERIOD, hipMemcpyDeviceToHost));
-    return check_status(ctx);
-}
-
-// One chosen forward pass on chosen groups (dp_test.hip.inc).  The host holds every task to the bounds under which the batch path hands a DP to that
-// pass - the same macros, evaluated here - and refuses the rest before anything is launched.
-extern "C" mtr_status mtr_test_wrap_dp_pass(mtr_ctx *ctx, int32_t pass, int32_t n_groups, const int32_t *group_off, const int32_t *read_idx,
-                                            const int32_t *query_start, const int32_t *query_end, const uint8_t *units, const int32_t *unit_off,
-                                            const int32_t *gain, const int32_t *mismatch, const int32_t *indel, int32_t *out16)
-{
-    if (!ctx || pass < MTR_TEST_PASS_WAVE2P || pass > MTR_TEST_PASS_OCT2P || n_groups <= 0 || !group_off || !read_idx || !query_start || !query_end || !units || !unit_off ||
-        !gain || !mismatch || !indel || !out16) return MTR_ERR_BAD_ARG;
-    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
-    if (group_off[0] != 0) { ctx->err = "group_off[0] is not 0"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    const long long lim16 = ctx->sw.dp16_max_rows;
-    const bool one_param = pass == MTR_TEST_PASS_FOUR1P || pass == MTR_TEST_PASS_OCT1P;
-    const int max_members = pass == MTR_TEST_PASS_WAVE2P ? 1 : pass == MTR_TEST_PASS_OCT1P ? RQ_SLOTS : pass == MTR_TEST_PASS_OCT2P ? 8 : 4;
-    auto refuse = [&](int g, int t, const char *why) {
-        ctx->err = "bad DP pass task " + std::to_string(t) + " (group " + std::to_string(g) + "): " + why; return MTR_ERR_BAD_ARG;
-    };
-    auto size_ok = [&](long long U, long long rows) { return (U + 1) * rows + U < ctx->wrap_dp_size; };       // dp_size_ok (device_util.hip.inc)
-    size_t cells = 1;                                        // the largest cell block of a group
-    int quad_cols = 0;
-    for (int g = 0; g < n_groups; g++) {
-        const int t0 = group_off[g], n = group_off[g + 1] - t0;
-        if (t0 < 0 || n < 1 || n > max_members) return refuse(g, t0, "empty group, or more members than the pass takes");
-        long long maxrows = 0, maxU = 0, sumU = 0;
-        for (int t = t0; t < t0 + n; t++) {
-            const int rd = read_idx[t];
-            const long long U = (long long)unit_off[t + 1] - unit_off[t];
-            if (rd < 0 || rd >= ctx->n_reads || query_start[t] < 0 || query_end[t] < query_start[t] || query_end[t] >= ctx->lens[(size_t)rd]) return refuse(g, t, "window outside its read");
-            if (U <= 0 || U >= MTRC_MAX_PERIOD) return refuse(g, t, "unit length");
-            const long long rows = (long long)query_end[t] - query_start[t] + 1;
-            if (!size_ok(U, rows)) return refuse(g, t, "beyond WrapDPsize");
-            switch (pass) {
-            case MTR_TEST_PASS_WAVE2P: break;                // dp_two_params_unit takes every alignment
-            case MTR_TEST_PASS_Q4:                           // dp_batch_fits + the units the pool batches
-                if (U > 16) return refuse(g, t, "unit above 16 bases");
-                if (rows > DP2P_MAX_ROWS || rows > lim16 || !size_ok(16, rows)) return refuse(g, t, "rows beyond dp_batch_fits");
-                if (rd != read_idx[t0] || query_start[t] != query_start[t0] || query_end[t] != query_end[t0]) return refuse(g, t, "the units of a Q4 group share read and window");
-                break;
-            case MTR_TEST_PASS_QUAD2P:                       // mtr_k_gather's isq
-                if (U > ST_QUMAX) return refuse(g, t, "unit above ST_QUMAX");
-                if (rows > DP2P_MAX_ROWS || rows > lim16 || !DPQ_FITS(rows, U, 1, 3)) return refuse(g, t, "rows beyond DPQ_FITS");
-                if (quad_cols == 0) quad_cols = DPQ_COLS(U);
-                if (DPQ_COLS(U) != quad_cols) return refuse(g, t, "the tasks of a QUAD2P call are of one DPQ_COLS class");
-                break;
-            case MTR_TEST_PASS_OCT2P:                        // mtr_k_gather's isq, and the units that go eight per wavefront
-                if (U > ST_OUMAX) return refuse(g, t, "unit above ST_OUMAX");
-                if (rows > DP2P_MAX_ROWS || rows > lim16 || !DPQ_FITS(rows, U, 1, 3)) return refuse(g, t, "rows beyond DPQ_FITS");
-                break;
-            default: {                                       // mtr_k_revise_quads' fits
-                const int G = gain[t], MM = mismatch[t], D = indel[t];
-                if (!((G == 1 && MM == 1 && D == 3) || (G == 1 && MM == 3 && D == 1) || (G == 5 && MM == 1 && D == 1))) return refuse(g, t, "not one of the three parameter sets");
-                if (U > ST_QUMAX) return refuse(g, t, "unit above ST_QUMAX");
-                if (rows > lim16 || !DPQ_FITS(rows, U, G, D)) return refuse(g, t, "rows beyond DPQ_FITS");
-                break; }
-            }
-            maxrows = std::max(maxrows, rows); maxU = std::max(maxU, U); sumU += U;
-        }
-        size_t block;
-        switch (pass) {
-        case MTR_TEST_PASS_WAVE2P: block = 2 * (size_t)maxrows * (size_t)(maxU + 1) + 64; break;      // dp_forward2 writes two matrices; a wide row is at most 256 bytes
-        case MTR_TEST_PASS_Q4: block = (size_t)maxrows * (size_t)sumU; break;
-        case MTR_TEST_PASS_QUAD2P: block = DPQ_BLOCK_BYTES(DPQ_COLS(maxU), maxrows); break;
-        case MTR_TEST_PASS_OCT2P: block = DPO_BLOCK_BYTES((maxU + 7) / 8, maxrows); break;
-        default: block = (RQ_SLOTS / 4) * DPQP_BLOCK_BYTES(DPQ_COLS(maxU), maxrows); break;
-        }
-        cells = std::max(cells, block);
-    }
-    const size_t per_wave = mtrc_align(cells + 256, 256);   // + slack: the traceback's dword loads read a few bytes past a row
-    if (per_wave > scratch_cap(ctx)) { ctx->err = "bad DP pass task: a group's cell block of " + std::to_string(cells) + " bytes exceeds the scratch cap"; return MTR_ERR_BAD_ARG; }
-    size_t total = 0;
-    const int waves = pick_waves(ctx, n_groups, 8, per_wave, &total);
-    mtr_status s = ensure_scratch(ctx, total); if (s != MTR_OK) return s;
-    const size_t nt = (size_t)group_off[n_groups], ng = (size_t)n_groups;
-    HIPCHK(ctx->d_t_i32.ensure((nt * 7 + 1 + ng + 1) * 4)); HIPCHK(ctx->d_t_units.ensure((size_t)unit_off[nt] + 16)); HIPCHK(ctx->d_t_out.ensure(nt * 16 * 4));
-    int32_t *d_i32 = ctx->d_t_i32; uint8_t *d_units = ctx->d_t_units; int32_t *d_out = ctx->d_t_out;
-    int32_t *d_rd = d_i32, *d_qs = d_i32 + nt, *d_qe = d_i32 + 2 * nt, *d_g = d_i32 + 3 * nt, *d_m = d_i32 + 4 * nt, *d_d = d_i32 + 5 * nt, *d_uo = d_i32 + 6 * nt, *d_go = d_i32 + 7 * nt + 1;
-    HIPCHK(copy_sync(ctx, d_rd, read_idx, nt * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_qs, query_start, nt * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, d_qe, query_end, nt * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_g, gain, nt * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, d_m, mismatch, nt * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_d, indel, nt * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, d_uo, unit_off, (nt + 1) * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_units, units, (size_t)unit_off[nt], hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, d_go, group_off, (ng + 1) * 4, hipMemcpyHostToDevice));
-    DpPassArgs a{};
-    a.t.b = view(ctx); a.t.n_tasks = (int32_t)nt; a.t.read_idx = d_rd; a.t.qs = d_qs; a.t.qe = d_qe; a.t.units = d_units; a.t.unit_off = d_uo;
-    a.t.gain = d_g; a.t.mism = d_m; a.t.indel = d_d; a.t.out8 = d_out; a.t.scratch = ctx->d_scratch; a.t.scratch_per_wave = per_wave; a.t.cells_cap = cells;
-    a.t.status = ctx->d_status; a.t.work_counter = ctx->d_work; a.t.counters = ctx->d_counters; a.t.dp16_max_rows = ctx->sw.dp16_max_rows;
-    a.pass = pass; a.n_groups = n_groups; a.group_off = d_go; a.packed_words = ctx->packed_words;
-    HIPCHK(hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned), ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * CNT_N, ctx->stream));
-    HIPCHK(hipMemsetAsync(d_out, 0, nt * 16 * 4, ctx->stream));
-    const dim3 grid((unsigned)waves), block(64);
-    if (pass == MTR_TEST_PASS_WAVE2P || pass == MTR_TEST_PASS_Q4) hipLaunchKernelGGL(mtr_k_dp_test_waves, grid, block, 0, ctx->stream, a);
-    else if (one_param) hipLaunchKernelGGL(mtr_k_dp_test_rev, grid, block, 0, ctx->stream, a);
-    else if (pass == MTR_TEST_PASS_OCT2P) hipLaunchKernelGGL(mtr_k_dp_test_octs, grid, block, 0, ctx->stream, a);
-    else {
-        typedef void (*quad_kernel)(DpPassArgs);
-        static const quad_kernel by_cols[8] = { mtr_k_dp_test_quads<1>, mtr_k_dp_test_quads<2>, mtr_k_dp_test_quads<3>, mtr_k_dp_test_quads<4>,
-                                                mtr_k_dp_test_quads<5>, mtr_k_dp_test_quads<6>, mtr_k_dp_test_quads<7>, mtr_k_dp_test_quads<8> };
-        hipLaunchKernelGGL(by_cols[quad_cols - 1], grid, block, 0, ctx->stream, a);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(copy_sync(ctx, ctx->counters, ctx->d_counters, sizeof(unsigned long long) * CNT_N, hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(ctx, out16, d_out, nt * 16 * 4, hipMemcpyDeviceToHost));
-    return check_status(ctx);
-}
-
-extern "C" mtr_status mtr_alignments(mtr_ctx *ctx, int32_t n, const int32_t *read_idx, const mtr_record *records,
-                                     uint8_t **out_ops, int64_t **out_off, int32_t **out_end)
-{
-    if (!ctx || n < 0 || (n > 0 && (!read_idx || !records)) || !out_ops || !out_off || !out_end) return MTR_ERR_BAD_ARG;
-    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
-    { mtr_status w = mtr_wait(ctx); if (w != MTR_OK && w != MTR_ERR_DP_TOO_LARGE) return w; }   // after a DP failure: the reads before it are still printed
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    HostArray<int64_t> off = host_array<int64_t>((size_t)n + 1);
-    if (!off) return MTR_ERR_OOM;
-    off[0] = 0;
-    if (n == 0) { *out_ops = host_array<uint8_t>(1).release(); *out_off = off.release(); *out_end = host_array<int32_t>(2).release(); return MTR_OK; }
-    const size_t nt = (size_t)n;
-    std::vector<int32_t> h((nt * 6) + nt + 1);
-    int32_t *h_rd = h.data(), *h_rs = h_rd + nt, *h_re = h_rs + nt, *h_g = h_re + nt, *h_m = h_g + nt, *h_d = h_m + nt, *h_uo = h_d + nt;
-    std::vector<uint8_t> units; std::vector<int64_t> cap_off(nt + 1, 0);
-    size_t cells = 1;
-    for (int t = 0; t < n; t++) {
-        const mtr_record &r = records[t];
-        const int rd = read_idx[t], U = r.rep_period, rows = r.rep_end - r.rep_start + 1;
-        if (rd < 0 || rd >= ctx->n_reads || U <= 0 || U >= MTRC_MAX_PERIOD || rows <= 0 || r.rep_start < 0 || r.rep_end > ctx->lens[(size_t)rd]) {
-            ctx->err = "bad alignment task " + std::to_string(t); return MTR_ERR_BAD_ARG;
-        }
-        h_rd[t] = rd; h_rs[t] = r.rep_start; h_re[t] = r.rep_end; h_g[t] = r.match_gain; h_m[t] = r.mismatch_penalty; h_d[t] = r.indel_penalty;
-        h_uo[t] = (int32_t)units.size();
-        for (int j = 0; j < U; j++) { const char ch = r.unit[j]; units.push_back(ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : 3); }
-        // columns = rows + deletions; every deletion costs indel_penalty out of a score of at most match_gain per row
-        const size_t max_del = (size_t)std::max(r.match_gain, 1) * (size_t)rows / (size_t)std::max(r.indel_penalty, 1);
-        cap_off[(size_t)t + 1] = cap_off[(size_t)t] + (int64_t)(((size_t)rows + max_del + (size_t)U + 64 + 3) & ~(size_t)3);
-        cells = std::max(cells, (size_t)rows * (size_t)(U + 1));
-    }
-    h_uo[n] = (int32_t)units.size();
-    const size_t per_wave = mtrc_align(cells + 256, 256);
-    size_t total = 0;
-    const int waves = pick_waves(ctx, n, 8, per_wave, &total);
-    mtr_status s = ensure_scratch(ctx, total); if (s != MTR_OK) return s;
-    const size_t ops_bytes = (size_t)cap_off[nt];
-    HIPCHK(ctx->d_al_i32.ensure(h.size() * 4)); HIPCHK(ctx->d_al_len.ensure(nt * 4)); HIPCHK(ctx->d_al_units.ensure(units.size() + 16));
-    HIPCHK(ctx->d_al_ops.ensure(ops_bytes + 16)); HIPCHK(ctx->d_al_off.ensure((nt + 1) * 8)); HIPCHK(ctx->d_al_ends.ensure(nt * 8));
-    int32_t *d_i32 = ctx->d_al_i32;
-    HIPCHK(hipMemcpyAsync(d_i32, h.data(), h.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->d_al_units, units.data(), units.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->d_al_off, cap_off.data(), (nt + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    AlignArgs a{};
-    a.b = view(ctx); a.n_tasks = n;
-    a.read_idx = d_i32; a.rep_start = d_i32 + nt; a.rep_end = d_i32 + 2 * nt; a.gain = d_i32 + 3 * nt; a.mism = d_i32 + 4 * nt; a.indel = d_i32 + 5 * nt;
-    a.unit_off = d_i32 + 6 * nt; a.units = ctx->d_al_units;
-    a.ops = ctx->d_al_ops; a.ops_off = ctx->d_al_off; a.ops_len = ctx->d_al_len; a.ends = ctx->d_al_ends;
-    a.scratch = ctx->d_scratch; a.scratch_per_wave = per_wave; a.cells_cap = cells;
-    a.status = ctx->d_status; a.work_counter = ctx->d_work; a.counters = ctx->d_counters; a.dp16_max_rows = ctx->sw.dp16_max_rows;
-    HIPCHK(hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_work, 0, sizeof(unsigned), ctx->stream));
-    hipLaunchKernelGGL(mtr_k_align, dim3((unsigned)waves), dim3(64), 0, ctx->stream, a);
-    HIPCHK(hipGetLastError());
-    std::vector<int32_t> len(nt);
-    std::vector<uint8_t> raw(ops_bytes);
-    HostArray<int32_t> ends = host_array<int32_t>(nt * 2);
-    if (!ends) return MTR_ERR_OOM;
-    HIPCHK(hipMemcpyAsync(ends.get(), ctx->d_al_ends, nt * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(len.data(), ctx->d_al_len, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(raw.data(), ctx->d_al_ops, ops_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    { mtr_status st = check_status(ctx); if (st != MTR_OK && !(st == MTR_ERR_DP_TOO_LARGE && ctx->run_status == MTR_ERR_DP_TOO_LARGE)) return st; }
-    for (int t = 0; t < n; t++) off[(size_t)t + 1] = off[(size_t)t] + len[(size_t)t];
-    HostArray<uint8_t> ops = host_array<uint8_t>((size_t)std::max<int64_t>(off[nt], 1));
-    if (!ops) return MTR_ERR_OOM;
-    for (int t = 0; t < n; t++) memcpy(ops.get() + off[(size_t)t], raw.data() + cap_off[(size_t)t], (size_t)len[(size_t)t]);
-    for (int t = 0; t < n; t++) ends[2 * t] = records[t].rep_start - 1 + ends[2 * t];       // window row -> read position
-    *out_ops = ops.release(); *out_off = off.release(); *out_end = ends.release();
-    return MTR_OK;
-}
+#include "test_entries.hip.inc"
 
 extern "C" mtr_status mtr_set_trace(mtr_ctx *ctx, int32_t max_events)
 {

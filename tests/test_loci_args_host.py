@@ -24,6 +24,7 @@ def test_loci_args_against_the_sequential_model(tmp_path):
 
 
 def test_the_header_is_free_of_hip():
-    for name in ("loci_args.h", "mtr_common.h", "catalog_build.h", "flank_bv.h", "motif_dp.h", "seed_index.h"):      # the header and all it includes
+    # the header and all it includes; dp_task_plan.h (tests/test_dp_task_plan_host.py) and what it adds to them
+    for name in ("loci_args.h", "mtr_common.h", "catalog_build.h", "flank_bv.h", "motif_dp.h", "seed_index.h", "dp_task_plan.h", "motif_loci.h"):
         src = open(os.path.join(ROOT, "mtr_amd", "csrc", name)).read()
         assert "hip_runtime" not in src and "hipMalloc" not in src and "__global__" not in src, name

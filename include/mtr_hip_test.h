@@ -18,6 +18,21 @@ extern "C" {
 mtr_status mtr_test_ranges(mtr_ctx *ctx, int32_t **out_counts, int32_t **out_start, int32_t **out_end,
                            int32_t **out_w, uint64_t **out_di_bits, int64_t *out_total);
 
+/* The same ranges from the range finder's OTHER arrangement: the three kernels the staged chain launches for a batch of few reads
+ * (launch_k1_parts: the code arrays; one work item per (read, pass, position segment); extraction as a pipeline of 16 wavefronts per
+ * read, compaction and de-duplication by the workgroup), run alone on the resident batch over per-read scratch of n_reads *
+ * k1_layout(Lmax).total bytes - exactly as launch_staged reaches them.  Outputs and malloc'ed arrays as mtr_test_ranges.
+ *   mode     follows the resident batch: uploaded with a file state (mtr_upload_batch_in_file and the device uploads in a file), the passes
+ *            run whole and the finish is one wavefront per read; any other batch has its passes cut into segments and the pipeline finish.
+ *            The context's DI (Manhattan / Pearson) selects the passes.
+ *   refused  with MTR_ERR_BAD_ARG and a reason, nothing launched: no resident batch; more than 256 reads; per-read scratch for every read
+ *            that does not fit the context's scratch budget (MTR_SCRATCH_MAX_GB, free memory) - the batches launch_staged hands to the
+ *            one-wavefront-per-read kernel instead.
+ * Status and counters are cleared first; afterwards id 0 of mtr_get_kernel_times is the time between two events of the entry's own
+ * around the launches (launches = 3, or 2 where no read has a pass), and the context runs the batch as before (mtr_run_resident). */
+mtr_status mtr_test_ranges_parts(mtr_ctx *ctx, int32_t **out_counts, int32_t **out_start, int32_t **out_end,
+                                 int32_t **out_w, uint64_t **out_di_bits, int64_t *out_total);
+
 /* wrap_around_DP_sub (wrap_around_DP.c:222-354) for n_tasks (read, window, unit, scores) tasks on the
  * uploaded batch.  unit codes 0..3, units concatenated, unit_off[n_tasks+1].  out8[8*t..] =
  * rep_start, rep_end, repeat_len, Num_freq_unit, matches, mismatches, insertions, deletions. */

@@ -42,7 +42,7 @@ COUNTER_NAMES = ["dp_calls", "dp_cells", "dp_rows", "revise_dp_calls", "revise_d
 # In a product build (no -DMTR_PROFILE) mtr_k_dp2_quads counts its passes by kind: prof47 = four alignments per wavefront, prof55 = eight
 EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mtr_process_batch", "mtr_free_results",
            "mtr_upload_batch", "mtr_run_resident", "mtr_fetch_results", "mtr_get_kernel_times", "mtr_get_counters",
-           "mtr_test_ranges", "mtr_test_wrap_dp", "mtr_test_wrap_dp_pass", "mtr_test_polish", "mtr_test_last_mode", "mtr_set_trace", "mtr_get_trace",
+           "mtr_test_ranges", "mtr_test_ranges_parts", "mtr_test_wrap_dp", "mtr_test_wrap_dp_pass", "mtr_test_polish", "mtr_test_last_mode", "mtr_set_trace", "mtr_get_trace",
            "mtr_run_resident_async", "mtr_wait", "mtr_alignments",
            "mtr_file_state_create", "mtr_file_state_destroy", "mtr_upload_batch_in_file", "mtr_file_state_skip",
            "mtr_get_bases_after_read", "mtr_upload_batch_packed", "mtr_fetch_results_packed", "mtr_export_packed_device",
@@ -593,6 +593,8 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_get_counters.restype = C.c_int
     lib.mtr_test_ranges.argtypes = [C.c_void_p, P(P(C.c_int32)), P(P(C.c_int32)), P(P(C.c_int32)), P(P(C.c_int32)), P(P(C.c_uint64)), P(C.c_int64)]
     lib.mtr_test_ranges.restype = C.c_int
+    lib.mtr_test_ranges_parts.argtypes = lib.mtr_test_ranges.argtypes
+    lib.mtr_test_ranges_parts.restype = C.c_int
     lib.mtr_test_wrap_dp.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
     lib.mtr_test_wrap_dp.restype = C.c_int
     lib.mtr_test_wrap_dp_pass.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 10
@@ -1787,17 +1789,28 @@ class Engine:
         return {n: int(c[i]) for i, n in enumerate(COUNTER_NAMES)}
 
     # ---- building blocks (parity tests) ----------------------------------------------------------------------
-    def test_ranges(self):
-        """K1 alone on the uploaded batch -> per read list of (start, end, w, di_bits)."""
+    def test_ranges(self, finder: str = "wave"):
+        """The range finder alone on the uploaded batch -> per read list of (start, end, w, di_bits).  finder="wave": one wavefront per
+        read (mtr_test_ranges); finder="parts": the three kernels the staged chain launches for a batch of at most 256 reads
+        (mtr_test_ranges_parts; a batch the chain would not run them on: MtrError)."""
+        if finder not in ("wave", "parts"):
+            raise ValueError("finder is 'wave' or 'parts'")
+        name = "mtr_test_ranges" if finder == "wave" else "mtr_test_ranges_parts"
         P = C.POINTER
         pc, ps, pe, pw, pd, tot = P(C.c_int32)(), P(C.c_int32)(), P(C.c_int32)(), P(C.c_int32)(), P(C.c_uint64)(), C.c_int64()
-        self._check(self.lib.mtr_test_ranges(self.h, C.byref(pc), C.byref(ps), C.byref(pe), C.byref(pw), C.byref(pd), C.byref(tot)), "mtr_test_ranges")
+        self._check(getattr(self.lib, name)(self.h, C.byref(pc), C.byref(ps), C.byref(pe), C.byref(pw), C.byref(pd), C.byref(tot)), name)
+        try:
+            n, m = self.n_reads, int(tot.value)
+            counts = np.ctypeslib.as_array(pc, shape=(n,)).tolist()
+            cols = [np.ctypeslib.as_array(q, shape=(m,)).tolist() if m else [] for q in (ps, pe, pw, pd)]
+        finally:
+            for ptr in (pc, ps, pe, pw, pd):
+                _libc.free(C.cast(ptr, C.c_void_p))
+        rows = list(zip(*cols))
         out, p = [], 0
-        for i in range(self.n_reads):
-            out.append([(ps[p + t], pe[p + t], pw[p + t], pd[p + t]) for t in range(pc[i])])
-            p += pc[i]
-        for ptr in (pc, ps, pe, pw, pd):
-            _libc.free(C.cast(ptr, C.c_void_p))
+        for c in counts:
+            out.append(rows[p:p + c])
+            p += c
         return out
 
     def test_file_tail(self):

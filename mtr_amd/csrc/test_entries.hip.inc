@@ -146,19 +146,9 @@ extern "C" mtr_status mtr_test_unit_motifs(mtr_ctx *ctx, int32_t n, const char *
     return MTR_OK;
 }
 
-extern "C" mtr_status mtr_test_ranges(mtr_ctx *ctx, int32_t **out_counts, int32_t **out_start, int32_t **out_end,
-                                      int32_t **out_w, uint64_t **out_di_bits, int64_t *out_total)
+// the range lists of the resident batch (d_rcount, d_rstart, d_rend, d_rw, d_rdi) as mtr_test_ranges' and mtr_test_ranges_parts' malloc'ed arrays
+static mtr_status ranges_to_host(mtr_ctx *ctx, int32_t **out_counts, int32_t **out_start, int32_t **out_end, int32_t **out_w, uint64_t **out_di_bits, int64_t *out_total)
 {
-    if (!ctx || !out_counts || !out_start || !out_end || !out_w || !out_di_bits) return MTR_ERR_BAD_ARG;
-    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    HIPCHK(hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * CNT_N, ctx->stream));
-    mtr_status s = launch_k1(ctx); if (s != MTR_OK) return s;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1])); ctx->kt[0].ms = ms; ctx->kt[0].launches = 1;
-    s = check_status(ctx); if (s != MTR_OK) return s;
     const int n = ctx->n_reads;
     std::vector<int32_t> cnt((size_t)n), st((size_t)ctx->total_rcap), en((size_t)ctx->total_rcap), ww((size_t)ctx->total_rcap);
     std::vector<uint64_t> di((size_t)ctx->total_rcap);
@@ -182,6 +172,55 @@ extern "C" mtr_status mtr_test_ranges(mtr_ctx *ctx, int32_t **out_counts, int32_
     }
     *out_counts = oc.release(); *out_start = os.release(); *out_end = oe.release(); *out_w = ow.release(); *out_di_bits = od.release(); if (out_total) *out_total = total;
     return MTR_OK;
+}
+
+extern "C" mtr_status mtr_test_ranges(mtr_ctx *ctx, int32_t **out_counts, int32_t **out_start, int32_t **out_end,
+                                      int32_t **out_w, uint64_t **out_di_bits, int64_t *out_total)
+{
+    if (!ctx || !out_counts || !out_start || !out_end || !out_w || !out_di_bits) return MTR_ERR_BAD_ARG;
+    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    HIPCHK(hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * CNT_N, ctx->stream));
+    mtr_status s = launch_k1(ctx); if (s != MTR_OK) return s;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1])); ctx->kt[0].ms = ms; ctx->kt[0].launches = 1;
+    s = check_status(ctx); if (s != MTR_OK) return s;
+    return ranges_to_host(ctx, out_counts, out_start, out_end, out_w, out_di_bits, out_total);
+}
+
+// The range finder as the staged chain runs it on a batch of few reads: launch_k1_parts alone, under launch_staged's own conditions for it
+extern "C" mtr_status mtr_test_ranges_parts(mtr_ctx *ctx, int32_t **out_counts, int32_t **out_start, int32_t **out_end,
+                                            int32_t **out_w, uint64_t **out_di_bits, int64_t *out_total)
+{
+    if (!ctx || !out_counts || !out_start || !out_end || !out_w || !out_di_bits) return MTR_ERR_BAD_ARG;
+    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    const int n = ctx->n_reads;
+    const int parts_max = 256;                               // launch_staged's parts_max
+    if (n > parts_max) {
+        ctx->err = "a batch of " + std::to_string(n) + " reads: the staged chain runs the three-kernel range finder on at most " + std::to_string(parts_max);
+        return MTR_ERR_BAD_ARG;
+    }
+    const K1Layout y1 = k1_layout(ctx->Lmax);
+    size_t tot = 0;
+    if (pick_waves(ctx, n, n, y1.total, &tot) != n) {
+        ctx->err = "per-read scratch of " + std::to_string(n) + " x " + std::to_string(y1.total) + " bytes does not fit: the staged chain would not run the three-kernel range finder on this batch";
+        return MTR_ERR_BAD_ARG;
+    }
+    HIPCHK(hipMemsetAsync(ctx->d_status, 0, 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * CNT_N, ctx->stream));
+    // launch_k1_parts records no events: the entry's own pair around everything it enqueues (the item lists' copies included)
+    HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+    mtr_status s = launch_k1_parts(ctx); if (s != MTR_OK) return s;
+    HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    int passes = 0; for (int i = 0; i < n; i++) passes += k1_num_passes(ctx->lens[(size_t)i]);
+    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1])); ctx->kt[0].ms = ms; ctx->kt[0].launches = passes > 0 ? 3 : 2;
+    s = check_status(ctx); if (s != MTR_OK) return s;
+    return ranges_to_host(ctx, out_counts, out_start, out_end, out_w, out_di_bits, out_total);
 }
 
 extern "C" mtr_status mtr_test_file_tail(mtr_ctx *ctx, uint16_t **out_tail, int64_t **out_tail_off, uint8_t **out_after)

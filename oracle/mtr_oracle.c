@@ -56,7 +56,7 @@ struct mtro_ctx {
     int L;
     int *org;           /* L+2 entries, org[L]=org[L+1]=0 (isolated semantics) */
     int *wrand; size_t wrand_cap;
-    double *di_tmp, *di; int *di_end, *di_w; size_t di_cap;
+    double *di_tmp, *di; int *di_end, *di_w, *di_k /* the k of the pass that wrote di_w */, cur_k; size_t di_cap;
     int *hist[3];
     /* k-mer table of the current (window,k) */
     int *node; size_t node_cap;
@@ -132,7 +132,7 @@ mtro_ctx *mtro_create(int manhattan, float min_match_ratio)
 void mtro_destroy(mtro_ctx *c)
 {
     if (!c) return;
-    free(c->org); free(c->wrand); free(c->di_tmp); free(c->di); free(c->di_end); free(c->di_w);
+    free(c->org); free(c->wrand); free(c->di_tmp); free(c->di); free(c->di_end); free(c->di_w); free(c->di_k);
     for (int v = 0; v < 3; v++) free(c->hist[v]);
     free(c->node); free(c->direct); free(c->hkey); free(c->hval); free(c->dp);
     free(c->al_in); free(c->al_sym); free(c->al_rep);
@@ -245,7 +245,7 @@ static void extract_ranges(mtro_ctx *c, int n, int w)
             for (int j = lmax_i; j < n; j++) {
                 if (lmin > tmp[j]) { lmin = tmp[j]; lmin_j = j; }
                 if (lmin_j + w < j) {
-                    c->di[lmax_i] = lmax; c->di_w[lmax_i] = w; c->di_end[lmax_i] = lmin_j + w;
+                    c->di[lmax_i] = lmax; c->di_w[lmax_i] = w; c->di_k[lmax_i] = c->cur_k; c->di_end[lmax_i] = lmin_j + w;
                     i = lmin_j + w;
                     break;
                 }
@@ -283,22 +283,25 @@ static void dedup_ranges(mtro_ctx *c, int L)
 }
 
 /* fill_directional_index_with_end (fill_directional_index.c:549-602) */
-static void fill_ranges(mtro_ctx *c, int L, int r)
+static void fill_ranges(mtro_ctx *c, int L, int r, int32_t *end_raw /* may be NULL: the shifted ends before the de-duplication */, int32_t *k_raw /* may be NULL: their passes' k */)
 {
     int n = L + 2 * r;
-    for (int i = 0; i < n; i++) { c->di[i] = -1; c->di_end[i] = -1; c->di_w[i] = -1; }
+    for (int i = 0; i < n; i++) { c->di[i] = -1; c->di_end[i] = -1; c->di_w[i] = -1; c->di_k[i] = -1; }
     for (int k = 1; k <= 5; k += 2) {
         int max_w = (k == 1) ? 20 : (k == 3) ? 80 : MAX_WINDOW;
         build_wrand(c, k, L, r);
+        c->cur_k = k;
         for (int w = MIN_WINDOW; w <= max_w && w < L / 2; w *= 2) {
             di_pass(c, n, w, k, r);
             extract_ranges(c, n, w);
         }
     }
     for (int i = 0; i < L; i++) {
-        c->di[i] = c->di[i + r]; c->di_end[i] = c->di_end[i + r] - r; c->di_w[i] = c->di_w[i + r];
+        c->di[i] = c->di[i + r]; c->di_end[i] = c->di_end[i + r] - r; c->di_w[i] = c->di_w[i + r]; c->di_k[i] = c->di_k[i + r];
     }
     for (int i = L; i < n; i++) { c->di[i] = -1; c->di_end[i] = -1; c->di_w[i] = -1; }
+    if (end_raw) for (int i = 0; i < L; i++) end_raw[i] = c->di[i] != -1 ? c->di_end[i] : -1;
+    if (k_raw) for (int i = 0; i < L; i++) k_raw[i] = c->di[i] != -1 ? c->di_k[i] : -1;
     dedup_ranges(c, L);
 }
 
@@ -754,6 +757,7 @@ static void ensure_read_buffers(mtro_ctx *c, int L, int r)
         c->di = (double *)xrealloc(c->di, c->di_cap * sizeof(double));
         c->di_end = (int *)xrealloc(c->di_end, c->di_cap * sizeof(int));
         c->di_w = (int *)xrealloc(c->di_w, c->di_cap * sizeof(int));
+        c->di_k = (int *)xrealloc(c->di_k, c->di_cap * sizeof(int));
     }
     size_t wn = (size_t)L * 2 + (size_t)r * 4 + 64;      /* reads reach L + r - k + 2w, w < L/2 */
     if (wn > c->wrand_cap) { c->wrand_cap = wn + wn / 4; c->wrand = (int *)xrealloc(c->wrand, c->wrand_cap * sizeof(int)); }
@@ -783,12 +787,14 @@ static void cap_g1(mtro_ctx *c, int L, int r)
     fprintf(c->cap, "]}\n");
 }
 
-int mtro_ranges(mtro_ctx *c, const uint8_t *codes, int L, double *di, int32_t *end, int32_t *w)
+int mtro_ranges(mtro_ctx *c, const uint8_t *codes, int L, double *di, int32_t *end, int32_t *w) { return mtro_ranges_raw(c, codes, L, di, end, w, NULL, NULL); }
+
+int mtro_ranges_raw(mtro_ctx *c, const uint8_t *codes, int L, double *di, int32_t *end, int32_t *w, int32_t *end_raw, int32_t *k_raw)
 {
     int r = rand_len(L);
     load_read(c, codes, L);
     ensure_read_buffers(c, L, r);
-    fill_ranges(c, L, r);
+    fill_ranges(c, L, r, end_raw, k_raw);
     int n = 0;
     for (int i = 0; i < L; i++) {
         di[i] = c->di[i]; end[i] = c->di_end[i]; w[i] = c->di_w[i];
@@ -804,7 +810,7 @@ int mtro_process_read(mtro_ctx *c, const char *read_id, const uint8_t *codes, in
     int r = rand_len(L);
     load_read(c, codes, L);
     ensure_read_buffers(c, L, r);
-    fill_ranges(c, L, r);
+    fill_ranges(c, L, r, NULL, NULL);
     if (c->cap && c->level >= 1) cap_g1(c, L, r);
     for (int i = 0; i < L; i++) if (-1 < c->di_end[i] && c->di_end[i] < L) c->st.ranges_candidate++;
 

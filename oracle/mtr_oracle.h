@@ -98,6 +98,9 @@ int mtro_walk(mtro_ctx *, const uint8_t *codes, int L, int query_start, int quer
               int *out_period, char *out_unit);
 /* fill_directional_index_with_end (+ de-dup); arrays of length L; returns number of usable ranges */
 int mtro_ranges(mtro_ctx *, const uint8_t *codes, int L, double *di, int32_t *end, int32_t *w);
+/* the same, and (either may be NULL) end_raw[i] = the end of the entry at i BEFORE the de-duplication, k_raw[i] = the k of the pass that
+ * recorded it (-1: no entry): the list the de-duplication chain walks and the pass (k, w) of every entry, for tests that choose reads by them */
+int mtro_ranges_raw(mtro_ctx *, const uint8_t *codes, int L, double *di, int32_t *end, int32_t *w, int32_t *end_raw, int32_t *k_raw);
 /* the MT19937 stream (MT.h) after init_genrand(0): out[i] = genrand_int32() % 4 */
 void mtro_mt_bases(uint8_t *out, int n);
 

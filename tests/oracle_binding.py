@@ -64,6 +64,8 @@ def load(build: bool = True):
     lib.mtro_reset_stats.argtypes = [C.c_void_p]
     lib.mtro_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mtro_ranges.restype = C.c_int
+    lib.mtro_ranges_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mtro_ranges_raw.restype = C.c_int
     lib.mtro_wrap_dp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ODpResult)]
     lib.mtro_wrap_dp.restype = C.c_int
     lib.mtro_search_unit.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OSearchResult)]
@@ -124,6 +126,19 @@ class Oracle:
         bits = di.view(np.uint64)
         idx = np.nonzero((end > -1) & (end < L) & (di != -1.0))[0]
         return [(int(i), int(end[i]), int(w[i]), int(bits[i])) for i in idx]
+
+    def ranges_raw(self, codes: np.ndarray):
+        """-> (ranges as ranges(), raw): raw = int64 array [m, 4] of (start, end, w, k), one row per position that held a DI entry BEFORE
+        the de-duplication, in position order - the list the de-duplication chain walks, with the pass (k, w) that recorded each entry"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        L = len(codes)
+        di, end, w, raw, kk = np.zeros(L, np.float64), np.zeros(L, np.int32), np.zeros(L, np.int32), np.zeros(L, np.int32), np.zeros(L, np.int32)
+        self.lib.mtro_ranges_raw(self.h, codes.ctypes.data, L, di.ctypes.data, end.ctypes.data, w.ctypes.data, raw.ctypes.data, kk.ctypes.data)
+        bits = di.view(np.uint64)
+        idx = np.nonzero((end > -1) & (end < L) & (di != -1.0))[0]
+        alive = np.nonzero(kk > -1)[0]
+        return ([(int(i), int(end[i]), int(w[i]), int(bits[i])) for i in idx],
+                np.stack([alive, raw[alive], w[alive], kk[alive]], axis=1).astype(np.int64).reshape(-1, 4))
 
     def search_unit(self, codes: np.ndarray, qs: int, qe: int, k: int):
         """search_De_Bruijn_graph for one (window, k) -> dict: found, the nine fields of capture point G2 (period, rep_start, rep_end,

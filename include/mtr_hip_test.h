@@ -71,6 +71,31 @@ mtr_status mtr_test_polish(mtr_ctx *ctx, int32_t n_tasks, const int32_t *read_id
                            const int32_t *k, const uint8_t *units, const int32_t *scores, const int32_t *unit_off,
                            uint8_t *out_units, int32_t *out_len);
 
+/* revise_representative_unit (consensus.c:1048-1087) on records and units of the caller's choosing, on the uploaded batch.  Task t: read read_idx[t], the 13
+ * scalar fields of its record rr[13 t ..] in the order of mtr_record (rep_start, rep_end, repeat_len, rep_period, num_freq_unit, matches, mismatches,
+ * insertions, deletions, kmer, match_gain, mismatch_penalty, indel_penalty), the unit units[unit_off[t] .. unit_off[t+1]) (codes 0..3; its length is the
+ * record's period) and its node frequencies scores[unit_off[t] ..].  Group g = tasks group_off[g] .. group_off[g + 1] (group_off[0] = unit_off[0] = 0).
+ * out_rr[13 t ..] = the record after the revision, out_units[500 t ..] its unit (rep_period codes; the caller's 500 x tasks bytes).
+ *   MTR_TEST_REVISE_WAVE   a test kernel with mtr_k_revise's arena and launch bounds: the tasks of a group go through revise() - polish_repeat first - one after
+ *                          the other on one wavefront, as the per-read path runs the k of a range; the round memo starts empty with the group and lives across
+ *                          its tasks.  waves: a bound on the grid (0: none).
+ *   MTR_TEST_REVISE_SLOTS  mtr_k_revise_quads ITSELF on `waves` wavefronts (0: one) over a work list built from the tasks in the order given (the groups only
+ *                          cut the list for the reasons' sake): which revisions share a wavefront's eight slots follows from that order, and with one wavefront
+ *                          from nothing else.  The unit given is the POLISHED one (the chain polishes in mtr_k_polish); the node frequencies travel along.
+ *                          MTR_DP16_MAX_ROWS applies as in a batch run.
+ * Scratch per wavefront and the cell budget are those launch_staged gives the kernels for the resident batch; *out_cells = that budget (k2_layout's cells:
+ * what decides whether a pass's block fits).  The context's counters are cleared first and describe this launch afterwards (mtr_get_counters).
+ * Refused with MTR_ERR_BAD_ARG, the reason naming task and group, nothing launched - what the batch path never hands to a revision (mtr_amd/csrc/revise_task.h):
+ * a period outside 6..499 or a unit of another length; repeat_len / period outside 5..20; a window outside 0 <= rep_start <= rep_end <= L (rep_end = L is
+ * taken: a repeat that runs to the end of its read); a negative count, matches + mismatches + insertions + deletions <= 0 or repeat_len <= 0; kmer outside
+ * 2..15; (2 period + 1) rows + 2 period >= WrapDPsize; a unit code above 3; no resident batch; no group or an empty one; more than 4096 tasks; WAVE: a
+ * group whose tasks lie in different reads (the round memo is a range's: its key does not hold the read).
+ * Afterwards the context runs the batch as before (mtr_run_resident). */
+enum { MTR_TEST_REVISE_WAVE = 0, MTR_TEST_REVISE_SLOTS = 1 };
+mtr_status mtr_test_revise(mtr_ctx *ctx, int32_t mode, int32_t n_groups, const int32_t *group_off, const int32_t *read_idx, const int32_t *rr,
+                           const uint8_t *units, const int32_t *scores, const int32_t *unit_off, int32_t waves, int32_t *out_rr, uint8_t *out_units,
+                           int64_t *out_cells);
+
 /* How the last launch ran: 0 = one kernel, a wavefront per read; 1 = range-parallel; 2 = the staged chain of kernels.
  * (The records do not depend on it; tests pin the policy of mtr_hip.h's mtr_set_overlapped_launches with it.) */
 int32_t mtr_test_last_mode(const mtr_ctx *ctx);

@@ -42,7 +42,7 @@ COUNTER_NAMES = ["dp_calls", "dp_cells", "dp_rows", "revise_dp_calls", "revise_d
 # In a product build (no -DMTR_PROFILE) mtr_k_dp2_quads counts its passes by kind: prof47 = four alignments per wavefront, prof55 = eight
 EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mtr_process_batch", "mtr_free_results",
            "mtr_upload_batch", "mtr_run_resident", "mtr_fetch_results", "mtr_get_kernel_times", "mtr_get_counters",
-           "mtr_test_ranges", "mtr_test_ranges_parts", "mtr_test_wrap_dp", "mtr_test_wrap_dp_pass", "mtr_test_polish", "mtr_test_last_mode", "mtr_set_trace", "mtr_get_trace",
+           "mtr_test_ranges", "mtr_test_ranges_parts", "mtr_test_wrap_dp", "mtr_test_wrap_dp_pass", "mtr_test_polish", "mtr_test_revise", "mtr_test_last_mode", "mtr_set_trace", "mtr_get_trace",
            "mtr_run_resident_async", "mtr_wait", "mtr_alignments",
            "mtr_file_state_create", "mtr_file_state_destroy", "mtr_upload_batch_in_file", "mtr_file_state_skip",
            "mtr_get_bases_after_read", "mtr_upload_batch_packed", "mtr_fetch_results_packed", "mtr_export_packed_device",
@@ -601,6 +601,8 @@ def load_library(path: str = LIB_PATH):
     lib.mtr_test_wrap_dp_pass.restype = C.c_int
     lib.mtr_test_polish.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
     lib.mtr_test_polish.restype = C.c_int
+    lib.mtr_test_revise.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 3
+    lib.mtr_test_revise.restype = C.c_int
     lib.mtr_upload_batch_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]
     lib.mtr_upload_batch_packed.restype = C.c_int
     lib.mtr_upload_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
@@ -1867,6 +1869,32 @@ class Engine:
         self._check(self.lib.mtr_test_polish(self.h, n, rd.ctypes.data, rs.ctypes.data, re.ctypes.data, kk.ctypes.data, units.ctypes.data,
                                              scores.ctypes.data, uo.ctypes.data, out_units.ctypes.data, out_len.ctypes.data), "mtr_test_polish")
         return [out_units[i, :out_len[i]].copy() for i in range(n)]
+
+    REVISE_MODES = {"WAVE": 0, "SLOTS": 1}                  # MTR_TEST_REVISE_* of include/mtr_hip_test.h
+
+    def test_revise(self, mode: str, groups, waves: int = 0):
+        """mtr_test_revise: revise_representative_unit on chosen records and units of the uploaded batch.  groups: list of groups, a group a list of tasks
+        (read_idx, rr, unit codes, node frequencies), rr = the record's 13 scalar fields (rep_start, rep_end, repeat_len, period, copies, mat, mis, ins, del,
+        k, G, MM, D).  mode "WAVE": revise() - polish first - on one wavefront per group, the round memo living across the group's tasks; "SLOTS":
+        mtr_k_revise_quads itself on `waves` wavefronts (0: one) over the tasks in the order given, the units being polished ones.
+        -> (list of (rr 13-tuple, unit uint8 codes) per task in the order given, the launch's cell budget per wavefront).  Engine.counters() describes the launch."""
+        tasks = [t for g in groups for t in g]
+        n = len(tasks)
+        go = np.zeros(len(groups) + 1, np.int32)
+        go[1:] = np.cumsum([len(g) for g in groups])
+        rd = np.array([t[0] for t in tasks] + [0], np.int32)
+        rr = np.ascontiguousarray(np.array([list(t[1]) for t in tasks] + [[0] * 13], np.int32).reshape(-1, 13))
+        uo = np.zeros(n + 1, np.int32)
+        uo[1:] = np.cumsum([len(t[2]) for t in tasks])
+        units = np.ascontiguousarray(np.concatenate([np.asarray(t[2], np.uint8) for t in tasks] + [np.zeros(1, np.uint8)]))
+        scores = np.ascontiguousarray(np.concatenate([np.asarray(t[3], np.int32) for t in tasks] + [np.zeros(1, np.int32)]))
+        if any(len(t[2]) != len(t[3]) for t in tasks):
+            raise ValueError("a task's node frequencies are one per unit base")
+        out_rr, out_units, cells = np.zeros((max(n, 1), 13), np.int32), np.zeros((max(n, 1), 500), np.uint8), C.c_int64(0)
+        self._check(self.lib.mtr_test_revise(self.h, self.REVISE_MODES[mode], len(groups), go.ctypes.data, rd.ctypes.data, rr.ctypes.data, units.ctypes.data,
+                                             scores.ctypes.data, uo.ctypes.data, int(waves), out_rr.ctypes.data, out_units.ctypes.data, C.byref(cells)),
+                    "mtr_test_revise")
+        return [(tuple(int(v) for v in out_rr[i]), out_units[i, :max(0, min(int(out_rr[i, 3]), 500))].copy()) for i in range(n)], int(cells.value)
 
     DP_PASSES = {"WAVE2P": 0, "Q4": 1, "QUAD2P": 2, "FOUR1P": 3, "OCT1P": 4, "OCT2P": 5}       # MTR_TEST_PASS_* of include/mtr_hip_test.h
 

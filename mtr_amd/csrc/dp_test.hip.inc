@@ -279,3 +279,55 @@ __global__ __launch_bounds__(64, MTR_LAT_WAVES_PER_SIMD) void mtr_k_polish_test(
     }
     wc_flush(s_cnt, p.a.counters);
 }
+
+// ---- revise_representative_unit alone (mtr_test_revise, MTR_TEST_REVISE_WAVE): a GROUP of tasks per work item through revise(), one after the other on one
+// wavefront, as k2_range_select runs the k of a range: the round memo starts empty with the group (c.rmemo_n = 0) and lives across its tasks.  The arena and
+// the launch bounds are mtr_k_revise's.  (MTR_TEST_REVISE_SLOTS has no kernel here: the host launches mtr_k_revise_quads itself, test_entries.hip.inc.)
+struct ReviseTestArgs {
+    K2Args a;                      // the batch, the full scratch layout (cells included), counters and status
+    int32_t n_groups;
+    const int32_t *group_off, *read_idx, *rr;                    // group g = tasks group_off[g] .. group_off[g + 1]; rr: 13 integers per task in RR's order
+    const uint8_t *units; const int32_t *scores, *unit_off;      // unit codes 0..3 and node frequencies, concatenated
+    int32_t *out_rr; uint8_t *out_units;                          // task t's record (13 integers) and unit (at MTRC_MAX_PERIOD * t)
+};
+__global__ __launch_bounds__(64, MTR_WAVES_PER_SIMD) void mtr_k_revise_test(ReviseTestArgs p)
+{
+    __shared__ __attribute__((aligned(16))) int s_arena[MTR_ARENA_INTS];
+    __shared__ unsigned long long s_cnt[CNT_N];
+    int *s_keys = s_arena, *s_seeds = s_arena + K2_TAB_CAP, *s_stage = s_seeds + MTRC_MAX_SEEDS + 4;
+    const int lane = lane_id();
+    if (lane < CNT_N) s_cnt[lane] = 0ull;
+    K2Ctx c;
+    c.a = &p.a; c.wc = s_cnt;
+    c.sc = p.a.scratch + (size_t)blockIdx.x * p.a.scratch_per_wave;
+    c.y = k2_layout(p.a.Lmax, p.a.cells_cap);
+    c.lds_keys = (lds_int *)s_keys; c.seeds = (lds_int *)s_seeds; c.stage = (lds_int *)s_stage;
+    c.ties = (int *)(c.sc + c.y.ties); c.fresh = c.ties + MTRC_MAX_TIEBREAKS;
+    for (;;) {
+        const int grp = next_work_item(p.a.work_counter);
+        if (grp >= p.n_groups) break;
+        const int t0 = uni(p.group_off[grp]), t1 = uni(p.group_off[grp + 1]);
+        c.memo_n = 0; c.memo_qs = c.memo_qe = -1; c.memo_U = 0; c.rmemo_n = 0;
+#pragma unroll 1
+        for (int t = t0; t < t1; t++) {
+            st_member_ctx(c, p.a, uni(p.read_idx[t]));
+            const int uo = uni(p.unit_off[t]), U = uni(p.unit_off[t + 1]) - uo;
+            RR cur; st_rr_load(p.rr + (size_t)t * 13, cur);
+            uint8_t *ub = slot_unit(c, 1);
+            slot_load_candidate(ub, slot_score(c, 1), p.units + uo, p.scores + uo, U);
+            wave_sync_mem();
+            revise(c, cur);
+            if (lane == 0) {
+                int32_t *o = p.out_rr + (size_t)t * 13;
+                o[0] = cur.rep_start; o[1] = cur.rep_end; o[2] = cur.repeat_len; o[3] = cur.period; o[4] = cur.copies; o[5] = cur.mat; o[6] = cur.mis;
+                o[7] = cur.ins; o[8] = cur.del; o[9] = cur.kmer; o[10] = cur.G; o[11] = cur.MM; o[12] = cur.D;
+            }
+#pragma unroll 1
+            for (int q = lane; q < cur.period && q < MTRC_MAX_PERIOD; q += 64) p.out_units[(size_t)t * MTRC_MAX_PERIOD + q] = ub[q];
+            wave_sync_mem();                               // the next task loads over slot 1
+            loop_join();
+        }
+        loop_join();
+    }
+    wc_flush(s_cnt, p.a.counters);
+}

@@ -1685,8 +1685,8 @@ __global__ __launch_bounds__(64, MTR_WAVES_PER_SIMD) void mtr_k_revise_quads(K2A
         if (n_active == 0) break;                          // the list is empty and every slot is through: every wave reaches this exit
         const unsigned long long t_prep = clk();
         // ---- 2. the next DP of every slot: into the pass if it fits, else by itself right away (it uses the cell scratch: before the pass)
-        DpOct q; q.n = RQ_SLOTS;                            // (the slots' default values, wlim and the width of the pass are written out once more in mtr_k_dp_test_rev,
-        int maxrows = 0, maxU = 0, n_quad = 0;              //  dp_test.hip.inc: change both together)
+        DpOct q; q.n = RQ_SLOTS;                            // (the slots' default values, wlim and the width of the pass: mtr_k_dp_test_rev, dp_test.hip.inc, writes them out once
+        int maxrows = 0, maxU = 0, n_quad = 0;              //  more for ITS passes; the check on this copy is this kernel run on chosen lists, tests/test_gpu_revise.py, SLOTS mode)
 #pragma unroll 1
         for (int g = 0; g < RQ_SLOTS; g++) { q.pk[g] = a.b.packed; q.wlim[g] = 1; q.base[g] = 0; q.rows[g] = 0; q.U[g] = 0; q.unit[g] = c.sc; q.G[g] = 1; q.MM[g] = 1; q.D[g] = 1; }
 #pragma unroll 1

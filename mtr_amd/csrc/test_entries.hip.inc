@@ -419,3 +419,103 @@ extern "C" mtr_status mtr_test_wrap_dp_pass(mtr_ctx *ctx, int32_t pass, int32_t 
     HIPCHK(copy_sync(ctx, out16, a.t.out8, nt * 16 * 4, hipMemcpyDeviceToHost));
     return check_status(ctx);
 }
+
+// revise_representative_unit on chosen records and units (include/mtr_hip_test.h).  WAVE: revise() on one wavefront per group (dp_test.hip.inc:
+// mtr_k_revise_test); SLOTS: mtr_k_revise_quads ITSELF over a work list made here in the shape mtr_k_select / mtr_k_polish / mtr_k_rscatter leave it - per task a
+// block header (the kernel reads its rd), a revision record with the polished unit and the node frequencies behind it, its arena offset in rev_items, and
+// `sorted` in the caller's order.  The host holds every task to the bounds under which the batch path hands a record to its revision (revise_task.h) and refuses
+// the rest before anything is launched.  Scratch per wavefront and the cell budget are launch_staged's for the resident batch.
+#include "revise_task.h"
+extern "C" mtr_status mtr_test_revise(mtr_ctx *ctx, int32_t mode, int32_t n_groups, const int32_t *group_off, const int32_t *read_idx, const int32_t *rr,
+                                      const uint8_t *units, const int32_t *scores, const int32_t *unit_off, int32_t waves, int32_t *out_rr, uint8_t *out_units,
+                                      int64_t *out_cells)
+{
+    if (!ctx || (mode != MTR_TEST_REVISE_WAVE && mode != MTR_TEST_REVISE_SLOTS) || waves < 0 || !group_off || !read_idx || !rr || !units || !scores || !unit_off ||
+        !out_rr || !out_units || !out_cells) return MTR_ERR_BAD_ARG;
+    if (ctx->n_reads <= 0) { ctx->err = "bad revision task: no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    if (n_groups <= 0) { ctx->err = "bad revision task: no group"; return MTR_ERR_BAD_ARG; }
+    if (group_off[0] != 0 || unit_off[0] != 0) { ctx->err = "bad revision task: group_off[0] or unit_off[0] is not 0"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    read_switches(ctx->sw);
+    for (int g = 0; g < n_groups; g++) {
+        if (group_off[g + 1] <= group_off[g]) { ctx->err = "bad revision task " + std::to_string(group_off[g]) + " (group " + std::to_string(g) + "): empty group"; return MTR_ERR_BAD_ARG; }
+        if (group_off[g + 1] > RVT_MAX_TASKS) { ctx->err = "bad revision task " + std::to_string(RVT_MAX_TASKS) + " (group " + std::to_string(g) + "): more tasks than the lists hold"; return MTR_ERR_BAD_ARG; }
+        for (int t = group_off[g]; t < group_off[g + 1]; t++) {
+            const int64_t U = (int64_t)unit_off[t + 1] - unit_off[t];
+            std::string why = rvt_refusal(read_idx[t], ctx->n_reads, ctx->lens.data(), rr + (size_t)t * 13, U, ctx->wrap_dp_size);
+            if (why.empty()) for (int64_t q = 0; q < U; q++) if (units[unit_off[t] + q] > 3) { why = "a unit code above 3"; break; }
+            // (the round memo is a range's, and a range lies in one read: its key does not hold the read)
+            if (why.empty() && mode == MTR_TEST_REVISE_WAVE && read_idx[t] != read_idx[group_off[g]]) why = "the tasks of a WAVE group share their read";
+            if (!why.empty()) { ctx->err = "bad revision task " + std::to_string(t) + " (group " + std::to_string(g) + "): " + why; return MTR_ERR_BAD_ARG; }
+        }
+    }
+    const size_t nt = (size_t)group_off[n_groups], ng = (size_t)n_groups, ub = (size_t)unit_off[nt];
+    // launch_staged's scratch per wavefront: the unit layout alone where the three-kernel range finder takes per-read scratch, else the larger of the two
+    const int n = ctx->n_reads;
+    const K1Layout y1 = k1_layout(ctx->Lmax); const K2Layout y2 = k2_layout(ctx->Lmax);
+    bool parts = n <= 256;
+    if (parts) { size_t tot = 0; parts = pick_waves(ctx, n, n, y1.total, &tot) == n; }
+    const size_t per_wave = parts ? y2.total : std::max(y1.total, y2.total);
+    *out_cells = (int64_t)y2.cells;
+    const bool slots = mode == MTR_TEST_REVISE_SLOTS;
+    const int want = waves > 0 ? waves : slots ? 1 : (int)std::min<size_t>(ng, 1u << 20);
+    size_t total = 0;
+    const int nw = pick_waves(ctx, slots ? want : std::min<int>(want, (int)ng), slots ? 32 : 8, per_wave, &total);
+    { mtr_status s = ensure_scratch(ctx, total); if (s != MTR_OK) return s; }
+    K2Args a{}; k2_args(ctx, a, per_wave); a.trace_cap = 0;
+    { mtr_status s = dp_launch_reset(ctx, a, per_wave, 0, DP_COUNTERS_OWN); if (s != MTR_OK) return s; }      // (cells_cap 0: the whole cell region, as the chain's DP kernels have it)
+    if (!slots) {
+        // d_t_i32: group_off | read_idx | rr | unit_off | scores;  d_t_out: records | units
+        HIPCHK(ctx->d_t_i32.ensure((ng + 1 + nt + 13 * nt + nt + 1 + ub) * 4)); HIPCHK(ctx->d_t_units.ensure(ub + 16)); HIPCHK(ctx->d_t_out.ensure(nt * 13 * 4 + nt * MTRC_MAX_PERIOD + 16));
+        int32_t *d_go = ctx->d_t_i32, *d_rd = d_go + ng + 1, *d_rr = d_rd + nt, *d_uo = d_rr + 13 * nt, *d_sc = d_uo + nt + 1;
+        int32_t *d_orr = ctx->d_t_out; uint8_t *d_ou = (uint8_t *)(d_orr + 13 * nt);
+        HIPCHK(copy_sync(ctx, d_go, group_off, (ng + 1) * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_rd, read_idx, nt * 4, hipMemcpyHostToDevice));
+        HIPCHK(copy_sync(ctx, d_rr, rr, nt * 13 * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_uo, unit_off, (nt + 1) * 4, hipMemcpyHostToDevice));
+        HIPCHK(copy_sync(ctx, d_sc, scores, ub * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_t_units, units, ub, hipMemcpyHostToDevice));
+        HIPCHK(hipMemsetAsync(d_orr, 0, nt * 13 * 4 + nt * MTRC_MAX_PERIOD, ctx->stream));
+        ReviseTestArgs p{}; p.a = a; p.n_groups = n_groups; p.group_off = d_go; p.read_idx = d_rd; p.rr = d_rr; p.units = ctx->d_t_units; p.scores = d_sc; p.unit_off = d_uo;
+        p.out_rr = d_orr; p.out_units = d_ou;
+        hipLaunchKernelGGL(mtr_k_revise_test, dim3((unsigned)nw), dim3(64), 0, ctx->stream, p);
+        { mtr_status s = dp_launch_wait(ctx, DP_COUNTERS_OWN); if (s != MTR_OK) return s; }
+        HIPCHK(copy_sync(ctx, out_rr, d_orr, nt * 13 * 4, hipMemcpyDeviceToHost)); HIPCHK(copy_sync(ctx, out_units, d_ou, nt * MTRC_MAX_PERIOD, hipMemcpyDeviceToHost));
+        return check_status(ctx);
+    }
+    // the work list of mtr_k_revise_quads.  d_t_units: the arena (per task: StItemHdr, StRev, unit, node frequencies);  d_t_i64: rev_items;
+    // d_t_i32: sorted | quad_cls;  d_t_out: the work queues
+    const size_t block = sizeof(StItemHdr) + (size_t)ST_REV_BYTES, qwords = (size_t)ST_N_QUEUES * WQ_WORDS;
+    std::vector<uint8_t> arena(nt * block, 0);
+    std::vector<long long> items(nt);
+    std::vector<int32_t> lists(nt + 16, 0);
+    for (size_t t = 0; t < nt; t++) {
+        const size_t base = t * block, ro = base + sizeof(StItemHdr);
+        const int U = unit_off[t + 1] - unit_off[t];
+        StItemHdr h{}; h.rd = read_idx[t];
+        StRev rv{}; rv.block = (long long)base; rv.k = rr[t * 13 + 9]; rv.slot = 0; rv.leader = -1; rv.ri = (int32_t)t;
+        for (int f = 0; f < 13; f++) rv.rr[f] = rr[t * 13 + (size_t)f];
+        memcpy(arena.data() + base, &h, sizeof h); memcpy(arena.data() + ro, &rv, sizeof rv);
+        memcpy(arena.data() + ro + sizeof(StRev), units + unit_off[t], (size_t)U);
+        int32_t *sc = (int32_t *)(arena.data() + ro + sizeof(StRev) + K2_SLOT_UNIT);
+        for (int q = 0; q < K2_SLOT_SCORE; q++) sc[q] = q < U ? scores[unit_off[t] + q] : -1;
+        items[t] = (long long)ro; lists[t] = (int32_t)t;
+    }
+    lists[nt + ST_QCLASSES] = (int32_t)nt; lists[nt + ST_QCLASSES + 1] = 1;
+    HIPCHK(ctx->d_t_units.ensure(arena.size() + 16)); HIPCHK(ctx->d_t_i64.ensure(nt * 8)); HIPCHK(ctx->d_t_i32.ensure(lists.size() * 4)); HIPCHK(ctx->d_t_out.ensure(qwords * 4));
+    HIPCHK(copy_sync(ctx, ctx->d_t_units, arena.data(), arena.size(), hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_t_i64, items.data(), nt * 8, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(ctx, ctx->d_t_i32, lists.data(), lists.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(ctx->d_t_out, 0, qwords * 4, ctx->stream));
+    StagedArgs s{};
+    s.n_reads = n; s.arena = ctx->d_t_units; s.arena_cap = (long long)arena.size(); s.rev_items = (long long *)ctx->d_t_i64.p; s.rev_cap = (int32_t)nt;
+    s.sorted = ctx->d_t_i32; s.sorted_cap = (int32_t)nt; s.quad_cls = s.sorted + nt; s.work = (unsigned *)ctx->d_t_out.p; s.nsub = 1; s.quad_min = 1;
+    hipLaunchKernelGGL(mtr_k_revise_quads, dim3((unsigned)nw), dim3(64), 0, ctx->stream, a, s);
+    { mtr_status st = dp_launch_wait(ctx, DP_COUNTERS_OWN); if (st != MTR_OK) return st; }
+    HIPCHK(copy_sync(ctx, arena.data(), ctx->d_t_units, arena.size(), hipMemcpyDeviceToHost));
+    memset(out_units, 0, nt * MTRC_MAX_PERIOD);
+    for (size_t t = 0; t < nt; t++) {
+        const size_t ro = t * block + sizeof(StItemHdr);
+        StRev rv; memcpy(&rv, arena.data() + ro, sizeof rv);
+        for (int f = 0; f < 13; f++) out_rr[t * 13 + (size_t)f] = rv.rr[f];
+        const int U = std::max(0, std::min(rv.rr[3], MTRC_MAX_PERIOD));
+        memcpy(out_units + t * MTRC_MAX_PERIOD, arena.data() + ro + sizeof(StRev), (size_t)U);
+    }
+    return check_status(ctx);
+}

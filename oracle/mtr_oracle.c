@@ -704,22 +704,42 @@ static void revise_sub(mtro_ctx *c, rr_t *r, int G, int MM, int D)
                 rs, re, r->repeat_len, r->mis, r->ins, r->del, G, MM, D, unit_in, n, r->str);
 }
 
-/* revise_representative_unit (consensus.c:1048-1087) */
-static void revise(mtro_ctx *c, rr_t *r)
+/* revise_representative_unit (consensus.c:1048-1087).  do_polish = 0 and info are mtro_revise's: the unit given is already polished (the
+ * staged chain polishes in a kernel of its own), and what each round met and made is written down */
+static void revise_rounds(mtro_ctx *c, rr_t *r, int do_polish, mtro_revise_out *info)
 {
     static const int P[2][3] = { { 5, 1, 1 }, { 1, 1, 3 } };
-    polish(c, r);
+    if (do_polish) polish(c, r);
+    if (info) info->polished_len = r->rep_period;
     float base_ratio = rr_ratio(r);               /* not refreshed between the rounds (H7) */
     for (int p = 0; p < 2; p++) {
         rr_t t = *r;
+        mtro_revise_round *w = info ? &info->round[p] : NULL;
+        if (w) {
+            int cov = t.rep_period > 0 ? t.repeat_len / t.rep_period : 0;
+            w->in_start = t.rep_start; w->in_end = t.rep_end; w->in_repeat_len = t.repeat_len; w->in_mis = t.mis; w->in_ins = t.ins; w->in_del = t.del;
+            w->in_len = t.rep_period;
+            for (int i = 0; i < t.rep_period; i++) w->in_unit[i] = (uint8_t)c2b(t.str[i]);
+            w->threshold = (5 <= cov && cov <= 20) ? min_missing(t.rep_period, (double)(t.mis + t.ins + t.del) / t.repeat_len, cov) : -1;
+        }
         revise_sub(c, &t, P[p][0], P[p][1], P[p][2]);
+        if (w) {
+            w->rev_len = t.rep_period;
+            w->unchanged = t.rep_period == r->rep_period && memcmp(t.str, r->str, (size_t)t.rep_period) == 0;
+            for (int i = 0; i < t.rep_period; i++) w->rev_unit[i] = (uint8_t)c2b(t.str[i]);
+        }
         if (t.rep_period < MAX_PERIOD) {
             if (t.rep_period <= 0) { c->undefined_hits++; continue; }   /* reference divides by zero */
             dp_sub(c, t.rep_start, t.rep_end, &t, P[p][0], P[p][1], P[p][2]);
-            if (base_ratio < rr_ratio(&t)) *r = t;
+            if (w) w->candidate = 1;
+            if (base_ratio < rr_ratio(&t)) {
+                if (w) { w->accepted = 1; w->moved = t.rep_start != r->rep_start || t.rep_end != r->rep_end; }
+                *r = t;
+            }
         }
     }
 }
+static void revise(mtro_ctx *c, rr_t *r) { revise_rounds(c, r, 1, NULL); }
 
 /* ================================================================================================
  * per range / per read: handle_one_read.c:77-261
@@ -900,6 +920,35 @@ int mtro_walk(mtro_ctx *c, const uint8_t *codes, int L, int qs, int qe, int k, i
     out_unit[0] = 0;
     if (found) strcpy(out_unit, t.str);
     return found;
+}
+
+/* revise_representative_unit for ONE record of a read under isolated semantics, as find_tandem_repeat_sub calls it (handle_one_read.c:95-97):
+ * polish (unless the unit given is already polished), then the two rounds through the statics above */
+int mtro_revise(mtro_ctx *c, const uint8_t *codes, int L, const mtro_revise_in *in, int do_polish, mtro_revise_out *out)
+{
+    if (!c || !codes || !in || !out || c->file_order || L <= 0 || L > MTRO_MAX_INPUT_LENGTH) return -1;
+    const int U = in->rep_period;
+    if (U < 1 || U >= MAX_PERIOD || in->unit_len != U) return -2;
+    if (in->rep_start < 0 || in->rep_end < in->rep_start || in->rep_end > L) return -3;       /* rep_end = L: a repeat that runs to the end of its read (H2) */
+    if (in->mat < 0 || in->mis < 0 || in->ins < 0 || in->del < 0 || (long long)in->mat + in->mis + in->ins + in->del <= 0 || in->repeat_len <= 0) return -4;
+    if (in->kmer < 1 || in->kmer > MAX_KMER) return -5;
+    /* a revised unit has up to 2 U bases: no DP of the rounds may reach the cell count at which revise_sub / dp_sub end the process */
+    if ((2LL * U + 1) * (long long)(in->rep_end - in->rep_start + 1) + 2LL * U >= WRAP_DP_SIZE) return -6;
+    for (int i = 0; i < U; i++) if (in->unit[i] > 3) return -7;
+    FILE *cap = c->cap; c->cap = NULL;                     /* a stand-alone call leaves no capture line */
+    load_read(c, codes, L);
+    rr_t r; rr_clear(&r);
+    r.rep_start = in->rep_start; r.rep_end = in->rep_end; r.repeat_len = in->repeat_len; r.rep_period = U; r.copies = in->copies;
+    r.mat = in->mat; r.mis = in->mis; r.ins = in->ins; r.del = in->del; r.kmer = in->kmer; r.G = in->G; r.MM = in->MM; r.D = in->D;
+    for (int i = 0; i < U; i++) { r.str[i] = B2C[in->unit[i]]; r.score[i] = in->score[i]; }
+    r.str[U] = 0;
+    memset(out, 0, sizeof(*out));
+    revise_rounds(c, &r, do_polish, out);
+    c->cap = cap;
+    out->rep_start = r.rep_start; out->rep_end = r.rep_end; out->repeat_len = r.repeat_len; out->rep_period = r.rep_period; out->copies = r.copies;
+    out->mat = r.mat; out->mis = r.mis; out->ins = r.ins; out->del = r.del; out->kmer = r.kmer; out->G = r.G; out->MM = r.MM; out->D = r.D;
+    for (int i = 0; i < r.rep_period && i < MAX_PERIOD * 2 + 4; i++) out->unit[i] = (uint8_t)c2b(r.str[i]);
+    return 0;
 }
 
 /* ================================================================================================

@@ -96,6 +96,35 @@ int mtro_search_unit(mtro_ctx *, const uint8_t *codes, int L, int query_start, i
  * characters) = the unit, "" if none.  Returns 1 if the walk closed, 0 if not, <0 on bad arguments. */
 int mtro_walk(mtro_ctx *, const uint8_t *codes, int L, int query_start, int query_end, int k, int backward, int seed,
               int *out_period, char *out_unit);
+/* revise_representative_unit (consensus.c:1048-1087) for ONE record of a read under isolated semantics: polish_repeat (do_polish != 0; 0: the unit
+ * given is already polished, as the staged chain hands it to its revision kernel), then the two rounds (vote DP (5,1,1) / (1,1,3), revised unit,
+ * re-alignment, acceptance against the ratio the revision started with) - through the statics mtro_process_read runs, so what a test
+ * learns here holds for a whole read.  in: the 13 scalar fields of the record, the unit's codes (0..3) and its node frequencies.  out: the final
+ * record and unit, the polished unit's length, and per round what revise_representative_unit_sub was given (the fields of capture point G3r), the
+ * threshold of the missing-base votes (min_missing; -1 where the coverage is outside 5..20), the revised unit, whether the votes left the unit as it
+ * was, whether a candidate was made (0 < revised length < MTRO_MAX_PERIOD), whether it was accepted and whether that moved rep_start or rep_end.
+ * Leaves no capture line.  Returns 0, or < 0 and nothing done: a file-order context or a bad read (-1); a period outside 1..499 or unit_len that
+ * differs from it (-2); a window outside 0 <= rep_start <= rep_end <= L (-3; rep_end = L is what a repeat that runs to the end of its read gives,
+ * org[L..L+3] = 0); mat + mis + ins + del <= 0, a negative count or repeat_len <= 0 (-4); k outside 1..15 (-5); (2 period + 1) rows + 2
+ * period >= WrapDPsize, where a round's DP of a revised unit could end the process (-6); a unit code above 3 (-7). */
+typedef struct {
+    int32_t rep_start, rep_end, repeat_len, rep_period, copies, mat, mis, ins, del, kmer, G, MM, D;
+    int32_t unit_len;
+    uint8_t unit[MTRO_MAX_PERIOD];
+    int32_t score[MTRO_MAX_PERIOD];
+} mtro_revise_in;
+typedef struct {
+    int32_t in_start, in_end, in_repeat_len, in_mis, in_ins, in_del, in_len, threshold;
+    int32_t rev_len, unchanged, candidate, accepted, moved;
+    uint8_t in_unit[MTRO_MAX_PERIOD], rev_unit[MTRO_MAX_PERIOD * 2 + 4];
+} mtro_revise_round;
+typedef struct {
+    int32_t rep_start, rep_end, repeat_len, rep_period, copies, mat, mis, ins, del, kmer, G, MM, D;
+    int32_t polished_len;
+    uint8_t unit[MTRO_MAX_PERIOD * 2 + 4];
+    mtro_revise_round round[2];
+} mtro_revise_out;
+int mtro_revise(mtro_ctx *, const uint8_t *codes, int L, const mtro_revise_in *in, int do_polish, mtro_revise_out *out);
 /* fill_directional_index_with_end (+ de-dup); arrays of length L; returns number of usable ranges */
 int mtro_ranges(mtro_ctx *, const uint8_t *codes, int L, double *di, int32_t *end, int32_t *w);
 /* the same, and (either may be NULL) end_raw[i] = the end of the entry at i BEFORE the de-duplication, k_raw[i] = the k of the pass that

@@ -40,8 +40,28 @@ class OSearchResult(C.Structure):
                                          "max_freq", "n_seeds")] + [("seeds", C.c_int32 * 100), ("unit", C.c_char * (MAX_PERIOD + 4))]
 
 
+class OReviseIn(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("rep_start", "rep_end", "repeat_len", "rep_period", "copies", "mat", "mis", "ins", "del_", "kmer", "G", "MM", "D",
+                                         "unit_len")] + [("unit", C.c_uint8 * MAX_PERIOD), ("score", C.c_int32 * MAX_PERIOD)]
+
+
+class OReviseRound(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("in_start", "in_end", "in_repeat_len", "in_mis", "in_ins", "in_del", "in_len", "threshold", "rev_len", "unchanged",
+                                         "candidate", "accepted", "moved")] + [("in_unit", C.c_uint8 * MAX_PERIOD), ("rev_unit", C.c_uint8 * (MAX_PERIOD * 2 + 4))]
+
+
+class OReviseOut(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("rep_start", "rep_end", "repeat_len", "rep_period", "copies", "mat", "mis", "ins", "del_", "kmer", "G", "MM", "D",
+                                         "polished_len")] + [("unit", C.c_uint8 * (MAX_PERIOD * 2 + 4)), ("round", OReviseRound * 2)]
+
+
+RR_FIELDS = ("rep_start", "rep_end", "repeat_len", "rep_period", "copies", "mat", "mis", "ins", "del_", "kmer", "G", "MM", "D")      # rr_t's scalars, in its order
+
 _lib = None
 _libc = C.CDLL(None)
+_libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
+_libc.fopen.restype = C.c_void_p
+_libc.fclose.argtypes = [C.c_void_p]
 _libc.free.argtypes = [C.c_void_p]
 
 
@@ -72,6 +92,10 @@ def load(build: bool = True):
     lib.mtro_search_unit.restype = C.c_int
     lib.mtro_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_char_p]
     lib.mtro_walk.restype = C.c_int
+    lib.mtro_revise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(OReviseIn), C.c_int, C.POINTER(OReviseOut)]
+    lib.mtro_revise.restype = C.c_int
+    lib.mtro_set_capture.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib.mtro_set_capture.restype = None
     lib.mtro_mt_bases.argtypes = [C.c_void_p, C.c_int]
     lib.mtro_chain.argtypes = [C.POINTER(ORecord), C.c_int, C.c_void_p]
     lib.mtro_chain.restype = C.c_int
@@ -161,6 +185,46 @@ class Oracle:
         if rc < 0:
             raise ValueError("mtro_walk: bad arguments")
         return period.value, unit.value.decode()
+
+    def capture(self, path: str, level: int = 1):
+        """the capture lines (G1 .. G4, oracle/ref_capture.c's format) of what follows go to `path`, until end_capture()"""
+        self._cap = _libc.fopen(path.encode(), b"w")
+        if not self._cap:
+            raise OSError(path)
+        self.lib.mtro_set_capture(self.h, self._cap, level)
+
+    def end_capture(self):
+        self.lib.mtro_set_capture(self.h, None, 0)
+        _libc.fclose(self._cap)
+        self._cap = None
+
+    def revise(self, codes: np.ndarray, rr, unit, score, polish: bool = True):
+        """mtro_revise: revise_representative_unit for one record.  rr: the 13 scalar fields in rr_t's order (rep_start, rep_end, repeat_len, period,
+        copies, mat, mis, ins, del, k, G, MM, D), unit: codes 0..3 (len = period), score: its node frequencies; polish=False: the unit is already
+        polished.  -> dict: rr (13-tuple), unit (uint8 codes), polished_len, rounds (two dicts: the G3r fields the round was given, threshold,
+        rev_len, rev_unit, unchanged, candidate, accepted, moved).  ValueError (the code in it) where the export refuses."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        a, o = OReviseIn(), OReviseOut()
+        for n, v in zip(RR_FIELDS, rr):
+            setattr(a, n, int(v))
+        unit, score = np.asarray(unit, np.uint8), np.asarray(score, np.int32)
+        a.unit_len = len(unit)
+        if len(unit) <= MAX_PERIOD and len(score) == len(unit):
+            C.memmove(a.unit, unit.ctypes.data, len(unit))
+            C.memmove(a.score, score.ctypes.data, 4 * len(unit))
+        else:
+            a.unit_len = -1
+        rc = self.lib.mtro_revise(self.h, codes.ctypes.data, len(codes), C.byref(a), 1 if polish else 0, C.byref(o))
+        if rc < 0:
+            raise ValueError(f"mtro_revise: refused ({rc})")
+        rounds = []
+        for w in o.round:
+            d = {n: int(getattr(w, n)) for n, _ in OReviseRound._fields_[:13]}
+            d["in_unit"] = bytes(w.in_unit[:max(0, w.in_len)])
+            d["rev_unit"] = bytes(w.rev_unit[:max(0, w.rev_len)])
+            rounds.append(d)
+        out_rr = tuple(int(getattr(o, n)) for n in RR_FIELDS)
+        return {"rr": out_rr, "unit": np.array(o.unit[:max(0, o.rep_period)], np.uint8), "polished_len": int(o.polished_len), "rounds": rounds}
 
     def wrap_dp(self, codes: np.ndarray, qs: int, qe: int, unit: np.ndarray, G: int, MM: int, D: int):
         codes = np.ascontiguousarray(codes, dtype=np.uint8)

@@ -1,0 +1,357 @@
+// allele_host.hip.inc — the hosts of what follows a genotype, included by mtr_abi.hip below genotype_host.hip.inc: the allele calls, the windows and
+// the allele consensus, the motif structure of windows.  Every one takes the caller's device columns: they are checked by check_device_cols, and
+// the context's stream waits for the caller's (wait_for_stream) before a kernel reads them.
+
+// ---- allele calls (allele_call.hip.inc) ------------------------------------------------------------------------------------------------
+// The arguments' checks, the count and the offsets, one look at the device (the status, S, the tiles), then the fill, the rank and the split
+// straight into the caller's columns.  No batch is needed and none is touched.
+// rows: the four input columns with R rows; row_read / row_locus: NULL for the dense layout (row = read * n_loci + locus), else the rows' own
+static mtr_status call_alleles_rows(mtr_ctx *ctx, const mtr_genotypes_dst *rows, int64_t R, int32_t n_loci, const int32_t *row_read, const int32_t *row_locus,
+                                    const mtr_allele_params *prm, void *wait_stream, const mtr_allele_calls_dst *dst, int64_t *out_support)
+{
+    if (prm->measure != MTR_ALLELE_COPIES && prm->measure != MTR_ALLELE_BASES) { ctx->err = "measure " + std::to_string(prm->measure) + " is neither MTR_ALLELE_COPIES nor MTR_ALLELE_BASES"; return MTR_ERR_BAD_ARG; }
+    if (!(prm->min_ratio >= 0.0f && prm->min_ratio <= 1.0f)) { ctx->err = "min_ratio " + std::to_string(prm->min_ratio) + " outside 0..1"; return MTR_ERR_BAD_ARG; }
+    if (prm->min_support < 1) { ctx->err = "min_support " + std::to_string(prm->min_support) + ": at least 1"; return MTR_ERR_BAD_ARG; }
+    if (prm->min_percent < 0 || prm->min_percent > 50) { ctx->err = "min_percent " + std::to_string(prm->min_percent) + " outside 0..50"; return MTR_ERR_BAD_ARG; }
+    if (prm->min_sep < 1) { ctx->err = "min_sep " + std::to_string(prm->min_sep) + ": at least 1"; return MTR_ERR_BAD_ARG; }
+    if (R > 0 && (!rows->spanning || !rows->window || !rows->fields || !rows->ratio)) { ctx->err = "an input column (spanning, window, fields, ratio) is NULL"; return MTR_ERR_BAD_ARG; }
+    if (rows->cap_rows < R) { ctx->err = "cap_rows " + std::to_string(rows->cap_rows) + " of the input is below " + std::to_string(R) + " rows"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t own = row_locus ? R * 4 : 0;                                                          // the dense layout has no index columns
+    const DeviceCol cols[6] = { { rows->spanning, R, "rows->spanning" }, { rows->window, R * 8, "rows->window" }, { rows->fields, R * 32, "rows->fields" },
+                                { rows->ratio, R * 4, "rows->ratio" }, { row_read, own, "row_read" }, { row_locus, own, "row_locus" } };
+    { mtr_status st = check_device_cols(ctx, cols, "the rows' bytes"); if (st != MTR_OK) return st; }
+    const size_t nl = (size_t)n_loci;
+    const size_t cstride = n_loci <= AL_SPREAD_LOCI ? AL_SPREAD : 1;
+    HIPCHK(ctx->d_ac_i32.ensure(2 * nl * cstride * 4)); HIPCHK(ctx->d_ac_i64.ensure((2 * (nl + 1) + AL_STATE) * 8));
+    AlleleArgs a{};
+    a.spanning = rows->spanning; a.window = rows->window; a.fields = rows->fields; a.ratio = rows->ratio;
+    a.row_read = R > 0 ? row_read : nullptr; a.row_locus = R > 0 ? row_locus : nullptr;
+    a.rows = R; a.n_loci = n_loci; a.measure = prm->measure; a.min_ratio = prm->min_ratio; a.rule = { prm->min_support, prm->min_percent, prm->min_sep };
+    a.count = ctx->d_ac_i32; a.cursor = a.count + nl * cstride; a.cstride = (int32_t)cstride; a.off = ctx->d_ac_i64; a.tile_off = a.off + nl + 1; a.state = a.tile_off + nl + 1;
+    { mtr_status st = wait_for_stream(ctx, wait_stream); if (st != MTR_OK) return st; }               // the rows come from the caller's stream
+    if (a.row_locus) {
+        // the index columns before anything else reads them: every locus in range, every (locus, read) once - the rank's keys are distinct by that
+        unsigned long long cap = 64; while (cap < 2 * (unsigned long long)R) cap <<= 1;
+        HIPCHK(ctx->d_ac_keys.ensure((size_t)(cap + 2) * 8));
+        unsigned long long *set = ctx->d_ac_keys, *bad = set + cap;
+        HIPCHK(hipMemsetAsync(set, 0xff, (size_t)(cap + 2) * 8, ctx->stream));
+        hipLaunchKernelGGL(mtr_k_cat_rows_check, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, ctx->stream, row_read, row_locus, R, n_loci, set, cap, bad);
+        HIPCHK(hipGetLastError());
+        unsigned long long found[2];
+        HIPCHK(copy_sync(ctx, found, bad, sizeof found, hipMemcpyDeviceToHost));
+        if (found[0] != ~0ull) {
+            int32_t rl[2] = { 0, 0 };
+            HIPCHK(copy_sync(ctx, &rl[0], row_read + found[0], 4, hipMemcpyDeviceToHost)); HIPCHK(copy_sync(ctx, &rl[1], row_locus + found[0], 4, hipMemcpyDeviceToHost));
+            ctx->err = "row " + std::to_string(found[0]) + ": read " + std::to_string(rl[0]) + " is negative or locus " + std::to_string(rl[1]) + " is outside 0.." + std::to_string(n_loci - 1);
+            return MTR_ERR_BAD_ARG;
+        }
+        if (found[1] != ~0ull) {
+            ctx->err = "(locus " + std::to_string(found[1] >> 32) + ", read " + std::to_string(found[1] & 0xffffffffull) + ") is given by more than one row";
+            return MTR_ERR_BAD_ARG;
+        }
+    }
+    HIPCHK(hipMemsetAsync(ctx->d_ac_i32, 0, 2 * nl * cstride * 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(a.state, 0xff, 8, ctx->stream));
+    const dim3 per_row((unsigned)((R + AL_BLOCK - 1) / AL_BLOCK)), blk(AL_BLOCK);
+    if (R > 0) hipLaunchKernelGGL(mtr_k_allele_count, per_row, blk, 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(mtr_k_allele_offsets, dim3(1), dim3(64), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    int64_t st[AL_STATE];
+    HIPCHK(copy_sync(ctx, st, a.state, 3 * 8, hipMemcpyDeviceToHost));
+    const int64_t S = st[AL_TOTAL], n_tiles = st[AL_TILES];
+    if (S < 0 || S > R || n_tiles < 0 || n_tiles > S) { ctx->err = "the allele calls' count failed on the device"; return MTR_ERR_HIP; }
+    *out_support = S;
+    if (st[AL_BAD] != -1) {
+        const int64_t p = st[AL_BAD];
+        int64_t rd = p / n_loci, l = p % n_loci;
+        if (a.row_locus) {
+            int32_t rl[2] = { 0, 0 };
+            HIPCHK(copy_sync(ctx, &rl[0], row_read + p, 4, hipMemcpyDeviceToHost)); HIPCHK(copy_sync(ctx, &rl[1], row_locus + p, 4, hipMemcpyDeviceToHost));
+            rd = rl[0]; l = rl[1];
+        }
+        ctx->err = "row " + std::to_string(p) + " (read " + std::to_string(rd) + ", locus " + std::to_string(l) + ") supports its locus with a negative value";
+        return MTR_ERR_BAD_ARG;
+    }
+    if (!dst) return MTR_OK;
+    if (dst->cap_loci < n_loci) { ctx->err = "destination holds " + std::to_string(dst->cap_loci) + " loci, " + std::to_string(n_loci) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (dst->cap_support < S) { ctx->err = "destination holds " + std::to_string(dst->cap_support) + " supporting rows, " + std::to_string(S) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (!dst->support_off || !dst->zygosity || !dst->call || !dst->call_support || !dst->cost || (S > 0 && (!dst->value || !dst->read || !dst->allele))) {
+        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
+    }
+    HIPCHK(ctx->d_ac_keys.ensure((size_t)std::max<int64_t>(S, 1) * 8)); HIPCHK(ctx->d_ac_prefix.ensure(((size_t)S + nl) * 8));
+    a.keys = ctx->d_ac_keys; a.prefix = ctx->d_ac_prefix;
+    a.value = dst->value; a.read = dst->read; a.allele = dst->allele; a.zygosity = dst->zygosity; a.call = dst->call; a.call_support = dst->call_support; a.cost = dst->cost;
+    if (S > 0) {
+        hipLaunchKernelGGL(mtr_k_allele_fill, per_row, blk, 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(mtr_k_allele_rank, dim3((unsigned)std::min<int64_t>(n_tiles, AL_MAX_GRID)), dim3(AL_TILE), 0, ctx->stream, a, n_tiles);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(mtr_k_allele_split, dim3((unsigned)std::min<int64_t>(n_loci, AL_MAX_GRID)), blk, 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(dst->support_off, a.off, (nl + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_call_alleles_device(mtr_ctx *ctx, const mtr_genotypes_dst *rows, int64_t n_reads, int32_t n_loci, const mtr_allele_params *prm,
+                                              void *wait_stream, const mtr_allele_calls_dst *dst, int64_t *out_support)
+{
+    if (!ctx || !out_support) return MTR_ERR_BAD_ARG;
+    *out_support = 0;
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
+    if (!rows || !prm) { ctx->err = "rows or prm is NULL"; return MTR_ERR_BAD_ARG; }
+    if (n_reads < 1) { ctx->err = "n_reads = " + std::to_string(n_reads) + ": at least one read is needed"; return MTR_ERR_BAD_ARG; }
+    if (n_loci < 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
+    if (n_reads > (int64_t)INT32_MAX / n_loci) { ctx->err = std::to_string(n_reads) + " reads x " + std::to_string(n_loci) + " loci are more than 2^31 - 1 rows"; return MTR_ERR_BAD_ARG; }
+    return call_alleles_rows(ctx, rows, n_reads * n_loci, n_loci, nullptr, nullptr, prm, wait_stream, dst, out_support);
+}
+
+extern "C" mtr_status mtr_call_alleles_rows_device(mtr_ctx *ctx, const mtr_genotypes_dst *rows, const int32_t *row_read, const int32_t *row_locus, int64_t n_rows,
+                                                   int32_t n_loci, const mtr_allele_params *prm, void *wait_stream, const mtr_allele_calls_dst *dst, int64_t *out_support)
+{
+    if (!ctx || !out_support) return MTR_ERR_BAD_ARG;
+    *out_support = 0;
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
+    if (!rows || !prm) { ctx->err = "rows or prm is NULL"; return MTR_ERR_BAD_ARG; }
+    if (n_rows < 0 || n_rows > (int64_t)INT32_MAX) { ctx->err = "n_rows = " + std::to_string(n_rows) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (n_loci < 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
+    if (n_rows > 0 && (!row_read || !row_locus)) { ctx->err = "row_read or row_locus is NULL"; return MTR_ERR_BAD_ARG; }
+    return call_alleles_rows(ctx, rows, n_rows, n_loci, row_read, row_locus, prm, wait_stream, dst, out_support);
+}
+
+// ---- windows and allele consensus (consensus.hip.inc) ------------------------------------------------------------------------------------
+// the caller's stream before the context's, and a call's state words: n_bad bad-input words set to "none", zero_bytes of counters behind them to 0
+static mtr_status columns_begin(mtr_ctx *ctx, void *wait_stream, DevBuf<unsigned long long> &state, size_t n_bad, size_t zero_bytes)
+{
+    HIPCHK(state.ensure(n_bad * 8 + zero_bytes));
+    { mtr_status st = wait_for_stream(ctx, wait_stream); if (st != MTR_OK) return st; }
+    HIPCHK(hipMemsetAsync(state, 0xff, n_bad * 8, ctx->stream));
+    HIPCHK(hipMemsetAsync(state + n_bad, 0, zero_bytes, ctx->stream));
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_extract_windows_device(mtr_ctx *ctx, const int32_t *row_read, const uint8_t *orientation, const int32_t *window, int64_t n_rows,
+                                                 void *wait_stream, const mtr_windows_dst *dst, int64_t *out_bases)
+{
+    if (!ctx || !out_bases) return MTR_ERR_BAD_ARG;
+    *out_bases = 0;
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
+    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    const int64_t R = n_rows;
+    if (R < 0 || R > (int64_t)INT32_MAX) { ctx->err = "n_rows = " + std::to_string(R) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (R > 0 && (!row_read || !orientation || !window)) { ctx->err = "row_read, orientation or window is NULL"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const DeviceCol cols[3] = { { row_read, R * 4, "row_read" }, { orientation, R, "orientation" }, { window, R * 8, "window" } };
+    { mtr_status st = check_device_cols(ctx, cols, "the rows' bytes"); if (st != MTR_OK) return st; }
+    const size_t nr = (size_t)R;
+    HIPCHK(ctx->d_co_i32.ensure(std::max<size_t>(nr, 1) * 4)); HIPCHK(ctx->d_co_i64.ensure((nr + 1) * 8));
+    { mtr_status st = columns_begin(ctx, wait_stream, ctx->d_co_state, CO_BAD, CO_STATE * 8); if (st != MTR_OK) return st; }
+    unsigned long long *bad = ctx->d_co_state;
+    int32_t *len = ctx->d_co_i32; int64_t *off = ctx->d_co_i64;
+    if (R > 0) hipLaunchKernelGGL(mtr_k_win_len, dim3((unsigned)((R + CO_BLOCK - 1) / CO_BLOCK)), dim3(CO_BLOCK), 0, ctx->stream, row_read, window, R,
+                                  (const int32_t *)ctx->d_lens, (int32_t)ctx->n_reads, len, bad);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)len, R, off);
+    HIPCHK(hipGetLastError());
+    unsigned long long found = 0; int64_t T = 0;
+    HIPCHK(hipMemcpyAsync(&T, off + R, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(copy_sync(ctx, &found, bad + 5, 8, hipMemcpyDeviceToHost));
+    if (found != ~0ull) {
+        int32_t v[3] = { 0, 0, 0 };
+        HIPCHK(copy_sync(ctx, &v[0], row_read + found, 4, hipMemcpyDeviceToHost)); HIPCHK(copy_sync(ctx, &v[1], window + 2 * found, 8, hipMemcpyDeviceToHost));
+        ctx->err = "row " + std::to_string(found) + ": read " + std::to_string(v[0]) + " is outside the batch of " + std::to_string(ctx->n_reads) + " reads, or its window " +
+                   std::to_string(v[1]) + ".." + std::to_string(v[2]) + " outside the read";
+        return MTR_ERR_BAD_ARG;
+    }
+    if (T < 0) { ctx->err = "the windows' scan failed on the device"; return MTR_ERR_HIP; }
+    *out_bases = T;
+    if (!dst) return MTR_OK;
+    if (dst->cap_rows < R) { ctx->err = "destination holds " + std::to_string(dst->cap_rows) + " rows, " + std::to_string(R) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (dst->cap_bases < T) { ctx->err = "destination holds " + std::to_string(dst->cap_bases) + " bases, " + std::to_string(T) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (!dst->win_off || (T > 0 && !dst->win_bases)) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
+    if (T > 0) {
+        hipLaunchKernelGGL(mtr_k_win_gather, dim3((unsigned)std::min<int64_t>(R, CO_MAX_GRID)), dim3(64), 0, ctx->stream, row_read, orientation, window, R,
+                           (const uint32_t *)ctx->d_packed, (const int64_t *)ctx->d_woff, (const int64_t *)off, dst->win_bases);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(dst->win_off, off, (nr + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// one bucket's alignments: the grid is bounded by the scratch it may take (each wavefront its own directions, sized by the bucket's longest task)
+template <int CPL>
+static mtr_status cons_align_bucket(mtr_ctx *ctx, const ConsArgs &a, int bucket, unsigned n_tasks, unsigned longest)
+{
+    if (n_tasks == 0) return MTR_OK;
+    const int64_t words = ((int64_t)(longest >> 4) + 1) * CPL * 64;
+    const int64_t cap_words = (int64_t)(std::min(ctx->sw.scratch_max_gb, 0.25) * (double)(1ll << 30) / 4.0);      // a quarter of a GB at the most, under the context's scratch cap
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_tasks, (int64_t)ctx->n_cu * 16), cap_words / words));
+    HIPCHK(ctx->d_co_dirs.ensure((size_t)(grid * words) * 4));
+    hipLaunchKernelGGL(mtr_k_cons_align<CPL>, dim3((unsigned)grid), dim3(64), 0, ctx->stream, a, bucket, n_tasks, (uint32_t *)ctx->d_co_dirs, words);
+    HIPCHK(hipGetLastError());
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_allele_consensus_device(mtr_ctx *ctx, const mtr_consensus_src *src, int32_t band_extra, void *wait_stream,
+                                                  const mtr_consensus_dst *dst, int64_t *out_bases)
+{
+    if (!ctx || !out_bases) return MTR_ERR_BAD_ARG;
+    *out_bases = 0;
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
+    if (!src) { ctx->err = "src is NULL"; return MTR_ERR_BAD_ARG; }
+    const int64_t R = src->n_rows, S = src->n_support, NB = src->n_bases; const int32_t n_loci = src->n_loci;
+    if (n_loci < 1 || n_loci > (1 << 30) - 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + " outside 1..2^30 - 1"; return MTR_ERR_BAD_ARG; }
+    if (R < 0 || R > (int64_t)INT32_MAX) { ctx->err = "n_rows = " + std::to_string(R) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (S < 0 || S > (int64_t)INT32_MAX) { ctx->err = "n_support = " + std::to_string(S) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (NB < 0 || NB > (int64_t)INT32_MAX) { ctx->err = "n_bases = " + std::to_string(NB) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (band_extra < 0 || band_extra > MTR_CONS_MAX_EXTRA) { ctx->err = "band_extra = " + std::to_string(band_extra) + " outside 0.." + std::to_string(MTR_CONS_MAX_EXTRA); return MTR_ERR_BAD_ARG; }
+    if (!src->win_off || !src->support_off || !src->zygosity || (R > 0 && (!src->row_read || !src->row_locus)) || (NB > 0 && !src->win_bases) ||
+        (S > 0 && (!src->read || !src->allele))) { ctx->err = "an input column is NULL"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    {
+        const DeviceCol cols[8] = {
+            { src->row_read, R * 4, "src->row_read" }, { src->row_locus, R * 4, "src->row_locus" }, { src->win_off, (R + 1) * 8, "src->win_off" }, { src->win_bases, NB, "src->win_bases" },
+            { src->support_off, ((int64_t)n_loci + 1) * 8, "src->support_off" }, { src->read, S * 4, "src->read" }, { src->allele, S, "src->allele" }, { src->zygosity, n_loci, "src->zygosity" } };
+        { mtr_status st = check_device_cols(ctx, cols, "the column's bytes"); if (st != MTR_OK) return st; }
+    }
+    read_switches(ctx->sw);
+    const size_t G = 2 * (size_t)n_loci, ns = (size_t)S;
+    HIPCHK(ctx->d_co_i32.ensure((ns + 9 * G) * 4)); HIPCHK(ctx->d_co_i64.ensure(2 * (G + 1) * 8)); HIPCHK(ctx->d_co_tasks.ensure(std::max<size_t>(2 * ns, 1) * sizeof(int4)));
+    { mtr_status st = columns_begin(ctx, wait_stream, ctx->d_co_state, CO_BAD, CO_STATE * 8); if (st != MTR_OK) return st; }
+    ConsArgs a{};
+    a.row_read = src->row_read; a.row_locus = src->row_locus; a.R = R; a.win_off = src->win_off; a.win_bases = src->win_bases; a.n_bases = NB;
+    a.support_off = src->support_off; a.sup_read = src->read; a.sup_allele = src->allele; a.zygosity = src->zygosity; a.S = S; a.n_loci = n_loci; a.band_extra = band_extra;
+    int32_t *i32 = ctx->d_co_i32;
+    a.ent_row = i32; a.bb_ent = i32 + ns; a.bb_row = a.bb_ent + G; a.bb_read = a.bb_row + G; a.bb_len = a.bb_read + G; a.members = a.bb_len + G; a.aligned = a.members + G;
+    a.skipped = a.aligned + G; a.tab_len = a.skipped + G; a.cons_len = a.tab_len + G;
+    a.tab_off = ctx->d_co_i64; a.cons_off = a.tab_off + G + 1; a.tasks = ctx->d_co_tasks;
+    a.bad = ctx->d_co_state; a.state = (unsigned *)(a.bad + CO_BAD);
+    const auto blocks = [](int64_t n) { return dim3((unsigned)((std::max<int64_t>(n, 1) + CO_BLOCK - 1) / CO_BLOCK)); };
+    const dim3 blk(CO_BLOCK);
+    unsigned long long bad[CO_BAD];
+    hipLaunchKernelGGL(mtr_k_cons_check, blocks(std::max<int64_t>(R, n_loci)), blk, 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(ctx, bad, a.bad, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad[0] != ~0ull) { ctx->err = "row " + std::to_string(bad[0]) + " is out of order: the rows must ascend by (read, locus), each pair once, none negative"; return MTR_ERR_BAD_ARG; }
+    if (bad[1] != ~0ull) { ctx->err = "win_off at row " + std::to_string(bad[1]) + " does not ascend from 0 to n_bases, or the window is above 2^30 bases"; return MTR_ERR_BAD_ARG; }
+    if (bad[2] != ~0ull) { ctx->err = "locus " + std::to_string(bad[2]) + ": support_off does not ascend from 0 to n_support, or the zygosity is above 2"; return MTR_ERR_BAD_ARG; }
+    if (S > 0) {
+        hipLaunchKernelGGL(mtr_k_cons_members, blocks(S), blk, 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        HIPCHK(copy_sync(ctx, bad, a.bad, sizeof bad, hipMemcpyDeviceToHost));
+        if (bad[3] != ~0ull) {
+            int32_t rd = 0;
+            HIPCHK(copy_sync(ctx, &rd, src->read + bad[3], 4, hipMemcpyDeviceToHost));
+            ctx->err = "support entry " + std::to_string(bad[3]) + " (read " + std::to_string(rd) + ") has no row of its (read, locus)";
+            return MTR_ERR_BAD_ARG;
+        }
+        if (bad[4] != ~0ull) { ctx->err = "support entry " + std::to_string(bad[4]) + ": the allele column is not 0 .. 0 1 .. 1 within its locus"; return MTR_ERR_BAD_ARG; }
+    }
+    HIPCHK(hipMemsetAsync(a.aligned, 0, 2 * G * 4, ctx->stream));                                      // aligned | skipped
+    hipLaunchKernelGGL(mtr_k_cons_alleles, blocks((int64_t)G), blk, 0, ctx->stream, a);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.tab_len, (int64_t)G, a.tab_off);
+    if (S > 0) hipLaunchKernelGGL(mtr_k_cons_tasks, blocks(S), blk, 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    unsigned state[CO_STATE]; int64_t tab_positions = 0;
+    HIPCHK(hipMemcpyAsync(&tab_positions, a.tab_off + G, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(copy_sync(ctx, state, a.state, sizeof state, hipMemcpyDeviceToHost));
+    if (tab_positions < 0 || (int64_t)state[0] + state[1] > S || state[2] > 2 * BA_MAX_WINDOW || state[3] > 2 * BA_MAX_WINDOW) { ctx->err = "the consensus' task lists failed on the device"; return MTR_ERR_HIP; }
+    HIPCHK(ctx->d_co_tab.ensure(std::max<size_t>((size_t)tab_positions * BA_TAB, 1) * 4));
+    a.tab = ctx->d_co_tab;
+    if (tab_positions > 0) HIPCHK(hipMemsetAsync(a.tab, 0, (size_t)tab_positions * BA_TAB * 4, ctx->stream));
+    { mtr_status st = cons_align_bucket<1>(ctx, a, 0, state[0], state[2]); if (st != MTR_OK) return st; }
+    { mtr_status st = cons_align_bucket<2>(ctx, a, 1, state[1], state[3]); if (st != MTR_OK) return st; }
+    const dim3 per_allele((unsigned)std::min<int64_t>((int64_t)G, CO_MAX_GRID));
+    hipLaunchKernelGGL(mtr_k_cons_emit<0>, per_allele, blk, 0, ctx->stream, a);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.cons_len, (int64_t)G, a.cons_off);
+    HIPCHK(hipGetLastError());
+    int64_t T = 0;
+    HIPCHK(copy_sync(ctx, &T, a.cons_off + G, 8, hipMemcpyDeviceToHost));
+    if (T < 0) { ctx->err = "the consensus' emission lengths failed on the device"; return MTR_ERR_HIP; }
+    *out_bases = T;
+    if (!dst) return MTR_OK;
+    if (dst->cap_alleles < (int64_t)G) { ctx->err = "destination holds " + std::to_string(dst->cap_alleles) + " alleles, " + std::to_string(G) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (dst->cap_bases < T) { ctx->err = "destination holds " + std::to_string(dst->cap_bases) + " bases, " + std::to_string(T) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (!dst->cons_off || !dst->backbone_read || !dst->backbone_len || !dst->members || !dst->aligned || !dst->skipped || (T > 0 && (!dst->bases || !dst->votes))) {
+        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
+    }
+    a.bases = dst->bases; a.votes = dst->votes;
+    if (T > 0) { hipLaunchKernelGGL(mtr_k_cons_emit<1>, per_allele, blk, 0, ctx->stream, a); HIPCHK(hipGetLastError()); }
+    HIPCHK(hipMemcpyAsync(dst->cons_off, a.cons_off, (G + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    const struct { int32_t *to; const int32_t *from; } cols[5] = { { dst->backbone_read, a.bb_read }, { dst->backbone_len, a.bb_len }, { dst->members, a.members }, { dst->aligned, a.aligned },
+                                                                   { dst->skipped, a.skipped } };
+    for (const auto &c : cols) HIPCHK(hipMemcpyAsync(c.to, c.from, G * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- the motif structure of windows (window_structure.hip.inc) ---------------------------------------------------------------------------
+template <int UB, bool WIDE>
+static void ws_launch_bin(mtr_ctx *ctx, const WsArgs &a, unsigned first, unsigned n_tasks)
+{
+    if (n_tasks > 0) hipLaunchKernelGGL((mtr_k_ws_lanes<UB, WIDE>), dim3((n_tasks + 63) / 64), dim3(64), 0, ctx->stream, a, first, n_tasks);
+}
+
+extern "C" mtr_status mtr_window_structure_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, const int32_t *struct_off, int32_t n_structs,
+                                                  const int64_t *win_off, const uint8_t *win_bases, const int32_t *win_struct, int64_t n_windows, int64_t n_bases,
+                                                  int32_t gain, int32_t mismatch, int32_t indel, void *wait_stream, const mtr_window_structure_dst *dst)
+{
+    if (!ctx) return MTR_ERR_BAD_ARG;
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
+    const int64_t N = n_windows;
+    const bool columns_null = !win_off || (N > 0 && !win_struct) || (n_bases > 0 && !win_bases) || !dst || (N > 0 && (!dst->seg || !dst->score || !dst->ratio || !dst->skipped));
+    if (!wsa_check(motifs, motif_off, struct_off, n_structs, columns_null, N, n_bases, gain, mismatch, indel, ctx->err)) return MTR_ERR_BAD_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    const DeviceCol cols[3] = { { win_off, (N + 1) * 8, "win_off" }, { win_bases, n_bases, "win_bases" }, { win_struct, N * 4, "win_struct" } };
+    { mtr_status st = check_device_cols(ctx, cols, "the column's bytes"); if (st != MTR_OK) return st; }
+    std::vector<WsStruct> structs((size_t)n_structs);
+    for (int32_t k = 0; k < n_structs; k++) structs[(size_t)k] = wsa_struct(motifs, motif_off, struct_off, k);
+    const size_t nw = std::max<size_t>((size_t)N, 1);
+    HIPCHK(ctx->d_ws_structs.ensure(structs.size() * sizeof(WsStruct))); HIPCHK(ctx->d_ws_i32.ensure(2 * nw * 4)); HIPCHK(ctx->d_ws_raw.ensure(nw * sizeof(WsRaw)));
+    { mtr_status st = columns_begin(ctx, wait_stream, ctx->d_ws_state, WS_BAD, 2 * WS_KEYS * 4); if (st != MTR_OK) return st; }
+    HIPCHK(copy_sync(ctx, ctx->d_ws_structs, structs.data(), structs.size() * sizeof(WsStruct), hipMemcpyHostToDevice));
+    WsArgs a{};
+    a.win_off = win_off; a.win_bases = win_bases; a.win_struct = win_struct; a.N = N; a.n_bases = n_bases; a.n_structs = n_structs; a.structs = ctx->d_ws_structs;
+    a.bad = ctx->d_ws_state; a.count = (unsigned *)(a.bad + WS_BAD); a.cursor = a.count + WS_KEYS;
+    a.key = ctx->d_ws_i32; a.tasks = a.key + nw; a.raw = ctx->d_ws_raw; a.G = gain; a.MM = mismatch; a.D = indel;
+    const dim3 per_window((unsigned)((nw + WS_BLOCK - 1) / WS_BLOCK)), blk(WS_BLOCK);
+    hipLaunchKernelGGL(mtr_k_ws_check, per_window, blk, 0, ctx->stream, a);
+    if (n_bases > 0) {
+        const int64_t words = (((int64_t)((uintptr_t)win_bases & 7) + n_bases - 1) >> 3) + 1;
+        hipLaunchKernelGGL(mtr_k_ws_bases, dim3((unsigned)std::min<int64_t>((words + WS_BLOCK - 1) / WS_BLOCK, 1 << 16)), blk, 0, ctx->stream, win_bases, n_bases, words, a.bad);
+    }
+    HIPCHK(hipGetLastError());
+    struct { unsigned long long bad[WS_BAD]; unsigned count[WS_KEYS]; } st;
+    static_assert(sizeof st == WS_BAD * 8 + WS_KEYS * 4, "the state's layout");
+    HIPCHK(copy_sync(ctx, &st, a.bad, sizeof st, hipMemcpyDeviceToHost));
+    if (st.bad[0] != ~0ull) { ctx->err = "win_off at window " + std::to_string(st.bad[0]) + " does not ascend from 0 to n_bases"; return MTR_ERR_BAD_ARG; }
+    if (st.bad[1] != ~0ull) {
+        int32_t k = 0;
+        HIPCHK(copy_sync(ctx, &k, win_struct + st.bad[1], 4, hipMemcpyDeviceToHost));
+        ctx->err = "window " + std::to_string(st.bad[1]) + ": win_struct " + std::to_string(k) + " outside 0.." + std::to_string(n_structs - 1); return MTR_ERR_BAD_ARG;
+    }
+    if (st.bad[2] != ~0ull) {
+        uint8_t c = 0;
+        HIPCHK(copy_sync(ctx, &c, win_bases + st.bad[2], 1, hipMemcpyDeviceToHost));
+        ctx->err = "win_bases at " + std::to_string(st.bad[2]) + ": code " + std::to_string((int)c) + " is above 3"; return MTR_ERR_BAD_ARG;
+    }
+    if (dst->cap_windows < N) { ctx->err = "destination holds " + std::to_string(dst->cap_windows) + " windows, " + std::to_string(N) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (N == 0) return MTR_OK;
+    unsigned bin_first[WS_BINS + 1] = { 0 };
+    for (int b = 0; b < WS_BINS; b++) { unsigned n = 0; for (int k = 0; k < WS_CLASSES; k++) n += st.count[b * WS_CLASSES + k]; bin_first[b + 1] = bin_first[b] + n; }
+    if ((int64_t)bin_first[WS_BINS] > N) { ctx->err = "the window structure's task counts failed on the device"; return MTR_ERR_HIP; }
+    hipLaunchKernelGGL(mtr_k_ws_tasks, per_window, blk, 0, ctx->stream, a);
+    ws_launch_bin<8, false>(ctx, a, bin_first[0], bin_first[1] - bin_first[0]);
+    ws_launch_bin<16, false>(ctx, a, bin_first[1], bin_first[2] - bin_first[1]);
+    ws_launch_bin<32, false>(ctx, a, bin_first[2], bin_first[3] - bin_first[2]);
+    ws_launch_bin<8, true>(ctx, a, bin_first[3], bin_first[4] - bin_first[3]);
+    ws_launch_bin<16, true>(ctx, a, bin_first[4], bin_first[5] - bin_first[4]);
+    a.seg = dst->seg; a.score = dst->score; a.ratio = dst->ratio; a.skipped = dst->skipped;
+    hipLaunchKernelGGL(mtr_k_ws_output, per_window, blk, 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}

@@ -2,6 +2,7 @@
 // HIP: a wrong figure here is an out-of-bounds access on the GPU, not a failing assertion, so tests/dp_task_plan_check.cpp holds them to the formulas one by one.
 #pragma once
 #include <algorithm>
+#include <string>
 #include <vector>
 #include "mtr_common.h"
 #include "motif_dp.h"
@@ -60,3 +61,22 @@ template <typename Pick> static inline DpLaunchPlan dp_loci_plan(const LaneSlots
     items[4] = ls.u_wave > 0 || max_len > lane_rows ? tasks : 0;
     return dp_launch_plan((size_t)std::min(max_len, lane_rows), ls.l_umax, (size_t)max_len * (size_t)((max_len > lane_rows ? ls.u_all : ls.u_wave) + 1), items, pick);
 }
+
+// One round of the locus search's kernels (loci_round) over S motif slots, nq of them lane slots, and nt tasks: every buffer's bytes and, counted in
+// the buffer's own elements, where each slice begins.  The locus search and the genotype both size and slice by this (LociRoundBufs).
+//   i32     unit_off (S + 1) | slot_q (S) | q_slot (nq, with room for S: the genotype keeps q_slot's address from before nq is known)         i64   bits (S)
+//   bin32   hist (nb) | groups (nb), one int over; nb = nq * MLO_N_CLASSES bins         bin64   tfirst (nb + 1) | gfirst (nb + 1)
+//   task32  tbin | trank | sorted | wlist, nt each       res   LOCI_RES_INTS a task       state   LOCI_STATE_INTS words       counter   8 bytes a launch
+#define LOCI_RES_INTS 9                                 // MS_RES (motif_search.hip.inc)
+#define LOCI_STATE_INTS 5                               // LOCI_STATE (motif_loci.hip.inc)
+struct LociRoundLayout { size_t nb, i32_bytes, i64_bytes, bin32_bytes, bin64_bytes, task32_bytes, res_bytes, state_bytes, counter_bytes, slot_q, q_slot, groups, gfirst, trank, sorted, wlist; };
+static inline bool loci_round_layout(size_t S, size_t nq, size_t nt, LociRoundLayout &l, std::string &err)
+{
+    if ((int64_t)nq * MLO_N_CLASSES > (int64_t)INT32_MAX) { err = std::to_string(nq) + " short motifs are more than the bins take"; return false; }
+    const size_t nb = nq * MLO_N_CLASSES;
+    l = { nb, (3 * S + 2) * 4, S * 8, (2 * nb + 1) * 4, 2 * (nb + 1) * 8, 4 * nt * 4, nt * LOCI_RES_INTS * 4, LOCI_STATE_INTS * 4, DP_LAUNCHES * 8,
+          S + 1, 2 * S + 1, nb, nb + 1, nt, 2 * nt, 3 * nt };
+    return true;
+}
+// what S alone decides, for a host that does not know nq yet: the slot ints' bound, slot_q's and q_slot's places, the bits
+static inline LociRoundLayout loci_slot_layout(size_t S) { LociRoundLayout l; std::string none; loci_round_layout(S, 0, 0, l, none); return l; }

@@ -1,4 +1,4 @@
-// genotype_host.hip.inc — the host driver of locus genotyping, included by mtr_abi.hip below its locus search (lane_slots, loci_round): the flank
+// genotype_host.hip.inc — the host driver of locus genotyping, included by mtr_abi.hip below motif_host.hip.inc (loci_round and its buffers, search_motifs_check_size): the flank
 // search, the genotype and the partial genotype, their catalogue forms, the prepared catalogue, in the order they depend on each other.  What the
 // loci's text and lengths decide - the checks and their words, the arrays of lengths, the codes - is loci_args.h; here the launches, the buffers
 // and the looks at the device.
@@ -79,7 +79,7 @@ extern "C" mtr_status mtr_search_flanks_device(mtr_ctx *ctx, const char *pattern
 {
     if (!ctx || !out_hits) return MTR_ERR_BAD_ARG;
     *out_hits = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
     if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
     if (n_patterns <= 0) { ctx->err = "n_patterns = " + std::to_string(n_patterns) + ": at least one pattern is needed"; return MTR_ERR_BAD_ARG; }
     if (!patterns || !pattern_off) { ctx->err = "patterns or pattern_off is NULL"; return MTR_ERR_BAD_ARG; }
@@ -141,67 +141,53 @@ static mtr_status partial_check_args(mtr_ctx *ctx, const std::vector<int64_t> &m
 }
 
 // ---- the alignment step of the genotype and of the catalogue genotype ---------------------------------------------------------------------
-// The N intervals in ctx->d_gt_iv (the longest of max_len bases, counted in ctx->d_gt_state) through one round of the locus search's path over
-// 2 * n_loci single-strand motifs; their hits are in ctx->d_gt_res on MTR_OK.
+// The N intervals in ctx->d_gt_iv (the longest of max_len bases, counted in ctx->gt.state) through one round of the locus search's path over
+// 2 * n_loci single-strand motifs; their hits are in ctx->gt.res on MTR_OK.
 // the 2 * n_loci single-strand motif slots on the device - the slots' codes, their offsets, their 2-bit forms - and the offsets on the host
 // cat_id: the prepared catalogue they belong to (mtr_catalog::id), 0 for tables a text-taking call made for itself
 struct GtTables { const uint8_t *d_units; const int32_t *d_uoff; const uint64_t *d_bits; const std::vector<int32_t> *unit_off; uint64_t cat_id; };
 
 // The alignment step from the device tables, whoever made them: the lane slots of this call's MTR_TEST_MOTIF_LANE_MAX from the units' lengths
-// (the context's d_gt_i32 behind the text-taking calls' unit_off: slot_q | q_slot - a prepared catalogue is never written to), the round, and
+// (the context's gt.i32 behind the text-taking calls' unit_off: slot_q | q_slot - a prepared catalogue is never written to), the round, and
 // one look at the device: the status.
 static mtr_status genotype_align_tables(mtr_ctx *ctx, const GtTables &tb, int32_t n_loci, int64_t N, int max_len, int32_t gain, int32_t mismatch, int32_t indel, const char *who)
 {
-    const int n = ctx->n_reads, M2 = 2 * n_loci;
-    const int lane_max = ctx->sw.motif_lane_max, lane_rows = ctx->sw.motif_lane_rows;
-    const size_t sS = (size_t)M2, nt = (size_t)N;
-    HIPCHK(ctx->d_gt_i32.ensure((3 * sS + 2) * 4));
-    int32_t *d_slot_q = (int32_t *)ctx->d_gt_i32 + sS + 1, *d_q_slot = d_slot_q + sS;
-    // the lane slots: a prepared catalogue's, once derived and uploaded for this lane_max, stay in the context (its d_gt_i32 at this address)
+    const int M2 = 2 * n_loci, lane_max = ctx->sw.motif_lane_max;
+    LociRoundBufs &gt = ctx->gt;
+    const LociRoundLayout at = loci_slot_layout((size_t)M2);                                // nq is not known yet
+    HIPCHK(gt.i32.ensure(at.i32_bytes));
+    int32_t *d_slot_q = gt.i32 + at.slot_q;
+    // the lane slots: a prepared catalogue's, once derived and uploaded for this lane_max, stay in the context (its gt.i32 at this address)
     // until another catalogue, another lane_max or a text-taking call (cat_id = 0) takes their place; batch after batch sends nothing
     if (!(tb.cat_id != 0 && ctx->gt_ls && ctx->gt_ls_cat == tb.cat_id && ctx->gt_ls_lane_max == lane_max && ctx->gt_ls_at == d_slot_q)) {
         ctx->gt_ls_cat = 0;
         const std::shared_ptr<const LaneSlots> fresh = std::make_shared<const LaneSlots>(lane_slots(*tb.unit_off, M2, lane_max));
-        HIPCHK(copy_sync(ctx, d_slot_q, fresh->slot_q.data(), sS * 4, hipMemcpyHostToDevice));
-        if (!fresh->q_slot.empty()) HIPCHK(copy_sync(ctx, d_q_slot, fresh->q_slot.data(), fresh->q_slot.size() * 4, hipMemcpyHostToDevice));
+        { mtr_status r = upload_lane_slots(ctx, *fresh, d_slot_q, gt.i32 + at.q_slot); if (r != MTR_OK) return r; }
         ctx->gt_ls = fresh; ctx->gt_ls_cat = tb.cat_id; ctx->gt_ls_lane_max = lane_max; ctx->gt_ls_at = d_slot_q;
     }
     const LaneSlots &ls = *ctx->gt_ls;
-    const size_t nq = ls.q_slot.size();
-    if ((int64_t)nq * MLO_N_CLASSES > (int64_t)INT32_MAX) { ctx->err = std::to_string(nq) + " short motifs are more than the bins take"; return MTR_ERR_OVERFLOW; }
-    const size_t nb = nq * MLO_N_CLASSES;
-    // the bins: d_gt_bin32 = hist | groups, d_gt_bin64 = tfirst | gfirst; the tasks: d_gt_task32 = tbin | trank | sorted | wlist
-    HIPCHK(ctx->d_gt_bin32.ensure((2 * nb + 1) * 4)); HIPCHK(ctx->d_gt_bin64.ensure(2 * (nb + 1) * 8)); HIPCHK(ctx->d_gt_counter.ensure(5 * 8));
-    HIPCHK(ctx->d_gt_task32.ensure(4 * nt * 4)); HIPCHK(ctx->d_gt_res.ensure(nt * MS_RES * 4));
     LociArgs a{};
-    a.b.packed = ctx->d_packed; a.b.woff = ctx->d_woff; a.b.lens = ctx->d_lens; a.b.order = nullptr; a.b.n_reads = n;
+    { mtr_status r = loci_round_bufs(ctx, gt, (size_t)M2, ls.q_slot.size(), (size_t)N, a); if (r != MTR_OK) return r; }
     a.iv = ctx->d_gt_iv; a.n_iv = (int32_t)N;
-    a.n_motifs = M2; a.n_strands = 1; a.G = gain; a.MM = mismatch; a.D = indel; a.lane_rows = lane_rows;
-    a.units = tb.d_units; a.unit_off = tb.d_uoff; a.bits = tb.d_bits; a.slot_q = d_slot_q; a.q_slot = d_q_slot;
-    a.hist = ctx->d_gt_bin32; a.groups = a.hist + nb; a.tfirst = ctx->d_gt_bin64; a.gfirst = a.tfirst + nb + 1; a.n_bins = (int32_t)nb;
-    a.tbin = ctx->d_gt_task32; a.trank = a.tbin + nt; a.sorted = a.trank + nt; a.wlist = a.sorted + nt; a.res = ctx->d_gt_res;
-    a.state = ctx->d_gt_state; a.dp16_max_rows = ctx->sw.dp16_max_rows;
-    { mtr_status r = loci_round(ctx, a, ls, N, max_len, (unsigned long long *)ctx->d_gt_counter, who, 0); if (r != MTR_OK) return r; }
+    a.n_motifs = M2; a.n_strands = 1; a.G = gain; a.MM = mismatch; a.D = indel;
+    a.units = tb.d_units; a.unit_off = tb.d_uoff; a.bits = tb.d_bits;
+    { mtr_status r = loci_round(ctx, a, ls, N, max_len, (unsigned long long *)gt.counter, who, 0); if (r != MTR_OK) return r; }
     // the status before the columns: a failed genotype writes nothing
     int32_t st[LOCI_STATE];
-    HIPCHK(copy_sync(ctx, st, ctx->d_gt_state, sizeof st, hipMemcpyDeviceToHost));
-    if (st[LOCI_STATUS] == DEV_ERR_DP_TOO_LARGE) { ctx->err = "You need to increse the value of WrapDPsize. (a DP of the genotype exceeded it or its scratch)"; return MTR_ERR_DP_TOO_LARGE; }
-    if (st[LOCI_STATUS] != DEV_OK) { ctx->err = "the genotype's alignments failed on the device (status " + std::to_string(st[LOCI_STATUS]) + ")"; return MTR_ERR_HIP; }
-    return MTR_OK;
+    return loci_round_status(ctx, gt, st, "genotype", "genotype's alignments", "");
 }
 
 // The alignment step of a text-taking call: the slots - locus l as given (2 * l) and reverse-complemented (2 * l + 1), one strand each - made
-// here and sent up.  Device copies: d_gt_i32 = unit_off | slot_q | q_slot (the two lists are genotype_align_tables'), d_gt_i64 = bits
+// here and sent up (gt.i32's unit_off, gt.i64, gt.units; the two lists behind unit_off are genotype_align_tables')
 static mtr_status genotype_align(mtr_ctx *ctx, const std::string &mot, const std::vector<int64_t> &mot_off, int32_t n_loci, int64_t N, int max_len,
                                  int32_t gain, int32_t mismatch, int32_t indel, const char *who)
 {
-    std::vector<uint8_t> units; std::vector<int32_t> unit_off; std::vector<uint64_t> bits;
-    motif_slots(mot.data(), mot_off.data(), n_loci, 2, units, unit_off, bits);
-    const size_t sS = 2 * (size_t)n_loci;
-    HIPCHK(ctx->d_gt_i32.ensure((3 * sS + 2) * 4)); HIPCHK(ctx->d_gt_i64.ensure(sS * 8)); HIPCHK(ctx->d_gt_units.ensure(units.size() + 16));
-    HIPCHK(copy_sync(ctx, ctx->d_gt_i32, unit_off.data(), (sS + 1) * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, ctx->d_gt_i64, bits.data(), sS * 8, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_gt_units, units.data(), units.size(), hipMemcpyHostToDevice));
-    const GtTables tb = { ctx->d_gt_units, ctx->d_gt_i32, (const uint64_t *)(int64_t *)ctx->d_gt_i64, &unit_off, 0 };
+    SlotTables t;
+    motif_slots(mot.data(), mot_off.data(), n_loci, 2, t.units, t.unit_off, t.bits);
+    LociRoundBufs &gt = ctx->gt;
+    HIPCHK(gt.i32.ensure(loci_slot_layout(t.bits.size()).i32_bytes));
+    { mtr_status r = upload_slot_tables(ctx, t, gt.i32, gt.i64, gt.units); if (r != MTR_OK) return r; }
+    const GtTables tb = { gt.units, gt.i32, (const uint64_t *)(int64_t *)gt.i64, &t.unit_off, 0 };
     return genotype_align_tables(ctx, tb, n_loci, N, max_len, gain, mismatch, indel, who);
 }
 
@@ -213,7 +199,7 @@ extern "C" mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, c
 {
     if (!ctx || !out_rows) return MTR_ERR_BAD_ARG;
     *out_rows = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
     LociText lt;
     { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, lt); if (st != MTR_OK) return st; }
     const int n = ctx->n_reads;
@@ -227,14 +213,14 @@ extern "C" mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, c
     read_switches(ctx->sw);
     { mtr_status st = flank_scan(ctx, lt.pat); if (st != MTR_OK) return st; }
     // the pairing
-    HIPCHK(ctx->d_gt_state.ensure(LOCI_STATE * 4)); HIPCHK(ctx->d_gt_pair.ensure((size_t)rows * GT_PAIR * 4)); HIPCHK(ctx->d_gt_iv.ensure((size_t)rows * sizeof(LociIv)));
-    HIPCHK(hipMemsetAsync(ctx->d_gt_state, 0, LOCI_STATE * 4, ctx->stream));
+    HIPCHK(ctx->gt.state.ensure(LOCI_STATE * 4)); HIPCHK(ctx->d_gt_pair.ensure((size_t)rows * GT_PAIR * 4)); HIPCHK(ctx->d_gt_iv.ensure((size_t)rows * sizeof(LociIv)));
+    HIPCHK(hipMemsetAsync(ctx->gt.state, 0, LOCI_STATE * 4, ctx->stream));
     const dim3 per_row((unsigned)((rows + 255) / 256)), b256(256);
-    const GenoPairArgs ga = { ctx->d_fl_res, n_loci, max_flank_dist, rows, ctx->d_gt_pair, ctx->d_gt_iv, (int32_t)rows, ctx->d_gt_state };
+    const GenoPairArgs ga = { ctx->d_fl_res, n_loci, max_flank_dist, rows, ctx->d_gt_pair, ctx->d_gt_iv, (int32_t)rows, ctx->gt.state };
     hipLaunchKernelGGL(mtr_k_geno_pair, per_row, b256, 0, ctx->stream, ga);
     HIPCHK(hipGetLastError());
     int32_t st[LOCI_STATE];
-    HIPCHK(copy_sync(ctx, st, ctx->d_gt_state, sizeof st, hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(ctx, st, ctx->gt.state, sizeof st, hipMemcpyDeviceToHost));
     const int64_t N = st[LOCI_NEXT];
     const int max_len = st[LOCI_MAXLEN];
     if (st[LOCI_STATUS] != DEV_OK || N < 0 || N > rows || max_len < 0 || max_len > ctx->Lmax || (N > 0) != (max_len > 0)) {
@@ -242,7 +228,7 @@ extern "C" mtr_status mtr_genotype_loci_device(mtr_ctx *ctx, const char *seqs, c
     }
     if (N > 0) { mtr_status r = genotype_align(ctx, lt.mot, lt.L.mot_off, n_loci, N, max_len, gain, mismatch, indel, "genotype_loci"); if (r != MTR_OK) return r; }
     const GenotypesOut out = { dst->spanning, dst->orientation, dst->flank_dist, dst->window, dst->fields, dst->score, dst->ratio };
-    hipLaunchKernelGGL(mtr_k_geno_out, per_row, b256, 0, ctx->stream, (const int32_t *)ctx->d_gt_pair, (const int32_t *)ctx->d_gt_res, rows, out);
+    hipLaunchKernelGGL(mtr_k_geno_out, per_row, b256, 0, ctx->stream, (const int32_t *)ctx->d_gt_pair, (const int32_t *)ctx->gt.res, rows, out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
@@ -434,16 +420,16 @@ static mtr_status genotype_catalog_rows(mtr_ctx *ctx, const CatIndex &ix, const 
     if (ix.narrow) hipLaunchKernelGGL(mtr_k_cat_flank<uint32_t>, per_task, b64, 0, ctx->stream, fa);
     if (ix.wide) hipLaunchKernelGGL(mtr_k_cat_flank<uint64_t>, per_task, b64, 0, ctx->stream, fa);
     // the pairing, and the rows' places
-    HIPCHK(ctx->d_gt_state.ensure(LOCI_STATE * 4)); HIPCHK(ctx->d_gt_pair.ensure(nc * GT_PAIR * 4)); HIPCHK(ctx->d_gt_iv.ensure(nc * sizeof(LociIv)));
-    HIPCHK(hipMemsetAsync(ctx->d_gt_state, 0, LOCI_STATE * 4, ctx->stream));
+    HIPCHK(ctx->gt.state.ensure(LOCI_STATE * 4)); HIPCHK(ctx->d_gt_pair.ensure(nc * GT_PAIR * 4)); HIPCHK(ctx->d_gt_iv.ensure(nc * sizeof(LociIv)));
+    HIPCHK(hipMemsetAsync(ctx->gt.state, 0, LOCI_STATE * 4, ctx->stream));
     const dim3 per_cand((unsigned)((nc + 255) / 256));
-    const CatPairArgs pa = { cand_read, cand_key, (int32_t)Cn, ctx->d_ct_flank, n_loci, max_flank_dist, ctx->d_gt_pair, span, ctx->d_gt_iv, (int32_t)Cn, ctx->d_gt_state };
+    const CatPairArgs pa = { cand_read, cand_key, (int32_t)Cn, ctx->d_ct_flank, n_loci, max_flank_dist, ctx->d_gt_pair, span, ctx->d_gt_iv, (int32_t)Cn, ctx->gt.state };
     hipLaunchKernelGGL(mtr_k_cat_pair, per_cand, b256, 0, ctx->stream, pa);
     hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, one, b1024, 0, ctx->stream, (const int32_t *)span, Cn, row_off);
     HIPCHK(hipGetLastError());
     int32_t st[LOCI_STATE], dev = 0;
     int64_t R = 0;
-    HIPCHK(copy_sync(ctx, st, ctx->d_gt_state, sizeof st, hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(ctx, st, ctx->gt.state, sizeof st, hipMemcpyDeviceToHost));
     HIPCHK(copy_sync(ctx, &dev, ctx->d_ct_status, 4, hipMemcpyDeviceToHost));
     HIPCHK(copy_sync(ctx, &R, row_off + nc, 8, hipMemcpyDeviceToHost));
     const int64_t N = st[LOCI_NEXT];
@@ -464,7 +450,7 @@ static mtr_status genotype_catalog_rows(mtr_ctx *ctx, const CatIndex &ix, const 
                                  { kept_col<uint8_t>(k, GC_SPANNING), kept_col<uint8_t>(k, GC_ORIENTATION), kept_col<int32_t>(k, GC_FDIST), kept_col<int32_t>(k, GC_WINDOW),
                                    kept_col<int32_t>(k, GC_FIELDS), kept_col<int32_t>(k, GC_SCORE), kept_col<float>(k, GC_RATIO) } };
         hipLaunchKernelGGL(mtr_k_cat_out, per_cand, b256, 0, ctx->stream, (const int32_t *)cand_read, (const int32_t *)cand_key, (const int32_t *)ctx->d_gt_pair,
-                           (const int32_t *)span, (const int64_t *)row_off, (const int32_t *)ctx->d_gt_res, (int32_t)Cn, out);
+                           (const int32_t *)span, (const int64_t *)row_off, (const int32_t *)ctx->gt.res, (int32_t)Cn, out);
         HIPCHK(hipGetLastError());
     }
     *out_R = R;
@@ -497,7 +483,7 @@ extern "C" mtr_status mtr_genotype_partial_device(mtr_ctx *ctx, const char *seqs
 {
     if (!ctx || !out_rows) return MTR_ERR_BAD_ARG;
     *out_rows = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
     LociText lt;
     { mtr_status st = genotype_check_args(ctx, seqs, seq_off, n_loci, max_flank_dist, gain, mismatch, indel, lt); if (st != MTR_OK) return st; }
     { mtr_status st = partial_check_args(ctx, lt.L.mot_off, n_loci, max_tail); if (st != MTR_OK) return st; }
@@ -684,7 +670,7 @@ static mtr_status catalog_call_begin(mtr_ctx *ctx, bool partial, bool no_cat, in
     if (!ctx || !out_rows || !out_candidates) return MTR_ERR_BAD_ARG;
     *out_rows = 0; *out_candidates = 0;
     if (no_cat) { ctx->err = "cat is NULL"; return MTR_ERR_BAD_ARG; }
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
     (partial ? ctx->pc : ctx->gc).ready = false;
     return MTR_OK;
 }
@@ -744,7 +730,7 @@ extern "C" mtr_status mtr_catalog_create(mtr_ctx *ctx, const char *seqs, const i
 {
     if (!ctx || !out) return MTR_ERR_BAD_ARG;
     *out = nullptr;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
     const auto t_host = HostClock::now();
     // genotype_check_args' checks that need no batch, in its order; the device adds the first bad byte to the first bad length (catb_bad_key)
     LA_CHK(la_check_offsets(seqs, seq_off, n_loci, ctx->err));

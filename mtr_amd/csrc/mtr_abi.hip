@@ -61,6 +61,7 @@
 static_assert(sizeof(DevRecord) == sizeof(mtr_record), "device and ABI record layouts must agree");
 static_assert(MTR_N_COUNTERS == CNT_N, "counter count");
 static_assert(MTR_MAX_READ_LENGTH == MTRC_MAX_SUPPORTED_LENGTH, "read length limit");
+static_assert(LOCI_RES_INTS == MS_RES && LOCI_STATE_INTS == LOCI_STATE, "the round layout's figures (dp_task_plan.h)");
 static_assert(MTR_WS_MAX_SEGMENTS == WS_MAX_SEGMENTS && MTR_WS_MAX_WINDOW == WS_MAX_WINDOW, "the window structure's limits");
 
 // A buffer of the context: grow-only (hipMalloc / hipFree cost ~0.1-0.5 ms each; a dozen of them per batch were a third of a single
@@ -148,6 +149,10 @@ struct StagedBufs {
 static unsigned *st_line(unsigned long long *sc, int line) { return (unsigned *)(sc + (size_t)line * (ST_LINE_BYTES / 8)); }
 static const int st_sl_cont_slots[ST_NCLS] = { 6, 7, 9, 11, 12, 13, 14, 15 };     // st_sl_cont(class): the continuation lists' sub-list counters
 
+// One round of the locus search's arrays, sized and sliced by dp_task_plan.h's LociRoundLayout (motif_host.hip.inc: loci_round_bufs); units: the
+// slots' codes, which like unit_off and bits a prepared catalogue brings itself
+struct LociRoundBufs { DevBuf<int32_t> i32, bin32, task32, res, state; DevBuf<int64_t> i64, bin64; DevBuf<uint8_t> units; DevBuf<unsigned long long> counter; };
+
 // what a catalogue call of either kind keeps for its copy and its statistics (genotype_host.hip.inc): the rows in CAT_ROW_COLS columns
 struct CatKept { bool ready = false; int64_t rows = 0; int64_t counts[4] = { 0, 0, 0, 0 }; double ms[3] = { 0, 0, 0 }; };
 #define CAT_ROW_COLS 9
@@ -233,23 +238,20 @@ struct mtr_ctx {
     // known-motif search (mtr_search_motifs_device), per call: the order and the slots' tables, the work lists, the slots' codes, the tasks' results,
     // its own status word and item counters (the run's d_status / d_work / d_counters are not touched: a search may come between a run and its fetch)
     DevBuf<int32_t> d_ms_i32, d_ms_res, d_ms_status; DevBuf<int64_t> d_ms_i64; DevBuf<uint8_t> d_ms_units; DevBuf<unsigned long long> d_ms_counter;
-    // known-motif locus search (mtr_search_motif_loci_device), per call: the slots' tables, the bins' and the tasks' arrays, the two interval lists, the
-    // tasks' results, the hit list, its state words and item counters; and what mtr_motif_loci_copy_device hands out (ml_ready: P pairs, T loci),
-    // kept until the next upload or locus search
+    // known-motif locus search (mtr_search_motif_loci_device), per call: a round's arrays (ml), the two interval lists, the hit list; and what
+    // mtr_motif_loci_copy_device hands out (ml_ready: P pairs, T loci), kept until the next upload or locus search
     bool ml_ready = false; int64_t ml_pairs = 0, ml_loci = 0;
-    DevBuf<int32_t> d_ml_i32, d_ml_bin32, d_ml_task32, d_ml_res, d_ml_hits, d_ml_state, d_ml_count, d_ml_starts; DevBuf<int64_t> d_ml_i64, d_ml_bin64;
-    DevBuf<LociIv> d_ml_iv[2]; DevBuf<uint8_t> d_ml_units; DevBuf<unsigned long long> d_ml_counter;
+    LociRoundBufs ml; DevBuf<int32_t> d_ml_hits, d_ml_count, d_ml_starts; DevBuf<LociIv> d_ml_iv[2];
     DevBuf<int64_t> d_ml_off; DevBuf<int32_t> d_ml_fields, d_ml_score; DevBuf<float> d_ml_ratio; DevBuf<uint8_t> d_ml_strand, d_ml_open;
     // flank search (mtr_search_flanks_device), per call: the order, the slots' lengths and work lists, the slots' masks, the tasks' results (per
     // slot: the genotype pairs them before a strand is picked), its own status word and item counters
     DevBuf<int32_t> d_fl_i32, d_fl_res, d_fl_status; DevBuf<int64_t> d_fl_i64; DevBuf<unsigned long long> d_fl_counter;
     // locus genotyping (mtr_genotype_loci_device), per call and nothing kept: the pairs, their intervals, and one round of the locus search's
-    // arrays - buffers of its own, so that what the locus search keeps (ml_ready) stays
-    DevBuf<int32_t> d_gt_pair, d_gt_i32, d_gt_bin32, d_gt_task32, d_gt_res, d_gt_state; DevBuf<int64_t> d_gt_i64, d_gt_bin64;
-    DevBuf<LociIv> d_gt_iv; DevBuf<uint8_t> d_gt_units; DevBuf<unsigned long long> d_gt_counter;
+    // arrays (gt) - buffers of its own, so that what the locus search keeps (ml_ready) stays
+    DevBuf<int32_t> d_gt_pair; DevBuf<LociIv> d_gt_iv; LociRoundBufs gt;
     // catalogue genotype (mtr_genotype_catalog_device), per call: the seed index (d_ct_ix = filter | key | run | entries | the slots' lengths), the
     // slots' masks, per read its hits' and candidates' counts and offsets, the hits and their head flags, the candidates (d_ct_cand = read | key |
-    // span), their flank hits, the status and the filter's count; the alignment goes through the genotype's own d_gt_* buffers.  What
+    // span), their flank hits, the status and the filter's count; the alignment goes through the genotype's own buffers (d_gt_*, gt).  What
     // mtr_genotype_catalog_copy_device hands out (gc: the columns d_gc, genotype_host.hip.inc's GC_*) is kept until an upload or the next catalogue call.
     CatKept gc;
     DevBuf<int32_t> d_ct_ix, d_ct_count, d_ct_hits, d_ct_cand, d_ct_flank, d_ct_status; DevBuf<int64_t> d_ct_off, d_ct_rowoff; DevBuf<uint64_t> d_ct_masks;
@@ -268,7 +270,7 @@ struct mtr_ctx {
     // mtr_catalog_create keeps nothing in the context but the host clock of its last success (mtr_test_catalog_build_stats); its working
     // buffers live for the call
     bool cb_ready = false; double cb_ms[3] = { 0, 0, 0 };
-    // the lane slots genotype_align_tables last derived and uploaded (slot_q | q_slot in d_gt_i32, at gt_ls_at): of prepared catalogue gt_ls_cat
+    // the lane slots genotype_align_tables last derived and uploaded (slot_q | q_slot in gt.i32, at gt_ls_at): of prepared catalogue gt_ls_cat
     // (0: of a text-taking call, never reused) under MTR_TEST_MOTIF_LANE_MAX = gt_ls_lane_max
     std::shared_ptr<const LaneSlots> gt_ls; uint64_t gt_ls_cat = 0; int gt_ls_lane_max = 0; const int32_t *gt_ls_at = nullptr;
     // allele calls (mtr_call_alleles_device), per call and nothing kept, buffers of its own so that what the genotype and the locus search keep stays:
@@ -516,6 +518,24 @@ static mtr_status check_device_ptr(mtr_ctx *ctx, const uint8_t *d, int64_t bytes
     (void)hipGetLastError();
     return MTR_OK;
 }
+// the caller's device columns, one after the other: every one that has bytes (what_bytes: what a column's bytes are called in the reason)
+struct DeviceCol { const void *p; int64_t bytes; const char *what; };
+template <size_t N> static mtr_status check_device_cols(mtr_ctx *ctx, const DeviceCol (&cols)[N], const char *what_bytes)
+{
+    for (const DeviceCol &c : cols)
+        if (c.bytes > 0) { mtr_status st = check_device_ptr(ctx, (const uint8_t *)c.p, c.bytes, c.what, what_bytes); if (st != MTR_OK) return st; }
+    return MTR_OK;
+}
+// what the caller's stream holds so far before anything the context's stream gets from here on: the kernels wait for it there, not for the whole device
+static mtr_status wait_for_stream(mtr_ctx *ctx, void *caller)
+{
+    if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ctx->ev_text, (hipStream_t)caller));
+    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
+    return MTR_OK;
+}
+// a run in flight ends first; its verdict is its own: MTR_ERR_HIP alone stops the caller
+static mtr_status end_pending_run(mtr_ctx *ctx) { return ctx->pending && mtr_wait(ctx) == MTR_ERR_HIP ? MTR_ERR_HIP : MTR_OK; }
 
 // the arguments of a device upload that the host can check (after free_batch: a refused upload leaves no batch behind)
 static mtr_status check_device_text(mtr_ctx *ctx, const DeviceText &dt, const int32_t *lens, int32_t n)
@@ -620,7 +640,7 @@ static mtr_status pack_text_enqueue(mtr_ctx *ctx, const DeviceText &dt, int32_t 
     HIPCHK(ctx->d_toff.ensure((size_t)n * 8)); HIPCHK(ctx->d_pack_bad.ensure(4));
     HIPCHK(hipMemcpyAsync(ctx->d_toff, dt.offsets, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_pack_bad, 0x7f, 4, ctx->stream));
-    HIPCHK(hipEventRecord(ctx->ev_text, dt.wait));
+    HIPCHK(hipEventRecord(ctx->ev_text, dt.wait));                        // (wait_for_stream's two steps, but behind this call's own copy and memset)
     HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
     const int64_t blocks = std::min<int64_t>((words + MTR_PACK_BLOCK - 1) / MTR_PACK_BLOCK, (int64_t)ctx->n_cu * 8);
     hipLaunchKernelGGL(dt.kind == MTR_TEXT_ASCII ? mtr_k_pack_text<true> : mtr_k_pack_text<false>, dim3((unsigned)blocks), dim3(MTR_PACK_BLOCK), 0, ctx->stream,
@@ -1808,792 +1828,11 @@ extern "C" mtr_status mtr_report_text_device(mtr_ctx *ctx, const char *ids, cons
     return MTR_OK;
 }
 
-// ---- the motif catalogue of the report's repeats (report_motif.hip.inc) -----------------------------------------------------------
-// Only the number of groups and of motif bytes come to the host.
-// The rows' working arrays in three buffers of the context: d_mo_i32 = rotation | motif_len | read | bases | slot_of | leader | first | lead_len | group,
-// d_mo_i64 = hash | copies | unit_off (n + 1) | group_of (n + 1) | len_off (n + 1), d_mo_u8 = strand | the motifs' bytes in the units' layout
-struct MotifWork { MotifRows rows; unsigned *slot_of; int32_t *leader, *first, *lead_len, *group; int64_t *group_of, *len_off; };
-static mtr_status motif_work(mtr_ctx *ctx, int64_t n, int64_t unit_bytes, MotifWork &w)
-{
-    const size_t nr = (size_t)n;
-    HIPCHK(ctx->d_mo_i32.ensure((9 * nr + 1) * 4)); HIPCHK(ctx->d_mo_i64.ensure((5 * nr + 3) * 8)); HIPCHK(ctx->d_mo_u8.ensure(nr + (size_t)unit_bytes + 16));
-    int32_t *i = ctx->d_mo_i32; int64_t *l = ctx->d_mo_i64; uint8_t *b = ctx->d_mo_u8;
-    w.rows.rotation = i; w.rows.motif_len = i + nr; w.rows.read = i + 2 * nr; w.rows.bases = i + 3 * nr;
-    w.slot_of = (unsigned *)(i + 4 * nr); w.leader = i + 5 * nr; w.first = i + 6 * nr; w.lead_len = i + 7 * nr; w.group = i + 8 * nr;
-    w.rows.hash = (unsigned long long *)l; w.rows.copies = l + nr; w.rows.unit_off = l + 2 * nr; w.group_of = l + 3 * nr + 1; w.len_off = l + 4 * nr + 2;
-    w.rows.strand = b; w.rows.motif = b + nr;
-    return MTR_OK;
-}
-// the columns per group in d_mo_g32 = first | repeats | reads, d_mo_g64 = motif_off (G + 1) | copies | bases, and d_mo_motifs
-static MotifGroups motif_groups(const mtr_ctx *ctx, const MotifWork &w)
-{
-    const size_t G = (size_t)ctx->mo_groups;
-    int32_t *i = ctx->d_mo_g32; int64_t *l = ctx->d_mo_g64;
-    return { w.group, l, ctx->d_mo_motifs, i, i + G, i + 2 * G, l + G + 1, l + 2 * G + 1 };
-}
-// The rows are in place (mtr_k_unit_motif or mtr_k_unit_motif_rows is enqueued): group them.  table_slots: 0 = twice the rows, rounded up to a
-// power of two; else the caller's power of two above n (mtr_test_unit_motifs).  Leaves mo_groups / mo_motif_bytes and the stream synchronised.
-static mtr_status motif_group(mtr_ctx *ctx, int64_t n, int64_t table_slots, const MotifWork &w)
-{
-    ctx->mo_groups = 0; ctx->mo_motif_bytes = 0;
-    if (n == 0) {
-        HIPCHK(ctx->d_mo_g64.ensure(8));
-        HIPCHK(hipMemsetAsync(ctx->d_mo_g64, 0, 8, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        return MTR_OK;
-    }
-    int64_t slots = table_slots;
-    if (slots == 0) for (slots = 64; slots < 2 * n; slots <<= 1) { }
-    HIPCHK(ctx->d_mo_table.ensure((size_t)slots * 4));
-    HIPCHK(hipMemsetAsync(ctx->d_mo_table, 0xff, (size_t)slots * 4, ctx->stream));
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(mtr_k_motif_insert, dim3(blocks), dim3(256), 0, ctx->stream, (int32_t)n, w.rows, (unsigned *)ctx->d_mo_table, (unsigned)(slots - 1), w.slot_of);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(mtr_k_motif_leader, dim3(blocks), dim3(256), 0, ctx->stream, (int32_t)n, (const int32_t *)w.rows.motif_len, (const unsigned *)ctx->d_mo_table,
-                       (const unsigned *)w.slot_of, w.leader, w.first, w.lead_len);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)w.first, n, w.group_of);
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)w.lead_len, n, w.len_off);
-    HIPCHK(hipGetLastError());
-    int64_t G = 0, M = 0;
-    HIPCHK(hipMemcpyAsync(&G, w.group_of + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(&M, w.len_off + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (G < 1 || G > n || M < 0) { ctx->err = "the motif table is inconsistent"; return MTR_ERR_HIP; }
-    ctx->mo_groups = G; ctx->mo_motif_bytes = M;
-    const size_t g = (size_t)G;
-    HIPCHK(ctx->d_mo_g32.ensure(3 * g * 4)); HIPCHK(ctx->d_mo_g64.ensure((3 * g + 1) * 8)); HIPCHK(ctx->d_mo_motifs.ensure((size_t)M + 16));
-    const MotifGroups mg = motif_groups(ctx, w);
-    HIPCHK(hipMemsetAsync(mg.repeats, 0, 2 * g * 4, ctx->stream));             // repeats | reads
-    HIPCHK(hipMemsetAsync(mg.copies, 0, 2 * g * 8, ctx->stream));              // copies | bases
-    hipLaunchKernelGGL(mtr_k_motif_groups, dim3(blocks), dim3(256), 0, ctx->stream, (int32_t)n, w.rows, (const int32_t *)w.leader, (const int64_t *)w.group_of,
-                       (const int64_t *)w.len_off, mg);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
-
-static mtr_status report_motifs(mtr_ctx *ctx)
-{
-    if (ctx->mo_ready) return MTR_OK;
-    { mtr_status st = report_chains(ctx); if (st != MTR_OK) return st; }
-    const int64_t R = ctx->rep_total;
-    if (R > (int64_t)INT32_MAX / 2) { ctx->err = "more reported repeats than the motif table takes"; return MTR_ERR_OVERFLOW; }
-    MotifWork w{};
-    { mtr_status st = motif_work(ctx, R, ctx->rep_unit_bytes, w); if (st != MTR_OK) return st; }
-    if (R > 0) {
-        const int n = ctx->n_reads;
-        hipLaunchKernelGGL(mtr_k_unit_motif, dim3((unsigned)n), dim3(64), 0, ctx->stream, record_view(ctx), chain_view(ctx),
-                           (const int64_t *)chain_offsets(ctx->d_ch_off, n).unit_base, R, ctx->rep_unit_bytes, w.rows);
-        HIPCHK(hipGetLastError());
-    }
-    { mtr_status st = motif_group(ctx, R, 0, w); if (st != MTR_OK) return st; }
-    ctx->mo_ready = true;
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_report_motifs_device(mtr_ctx *ctx, const mtr_report_motif_dst *dst, int64_t *out_repeats, int64_t *out_groups, int64_t *out_motif_bytes)
-{
-    if (!ctx || !out_repeats || !out_groups || !out_motif_bytes) return MTR_ERR_BAD_ARG;
-    { mtr_status r = results_ready(ctx, false); if (r != MTR_OK) return r; }
-    HIPCHK(hipSetDevice(ctx->device));
-    { mtr_status st = report_motifs(ctx); if (st != MTR_OK) return st; }
-    const int64_t R = ctx->rep_total, G = ctx->mo_groups, M = ctx->mo_motif_bytes;
-    *out_repeats = R; *out_groups = G; *out_motif_bytes = M;
-    if (!dst) return MTR_OK;
-    if (dst->cap_repeats < R || dst->cap_groups < G || dst->cap_motif_bytes < M) {
-        ctx->err = "destination holds " + std::to_string(dst->cap_repeats) + " repeats / " + std::to_string(dst->cap_groups) + " groups / " +
-                   std::to_string(dst->cap_motif_bytes) + " motif bytes, " + std::to_string(R) + " / " + std::to_string(G) + " / " + std::to_string(M) + " needed";
-        return MTR_ERR_OVERFLOW;
-    }
-    if (!dst->motif_off || (R > 0 && (!dst->strand || !dst->rotation || !dst->motif_len || !dst->group)) || (M > 0 && !dst->motifs) ||
-        (G > 0 && (!dst->g_first || !dst->g_repeats || !dst->g_reads || !dst->g_copies || !dst->g_bases))) {
-        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
-    }
-    MotifWork w{};
-    { mtr_status st = motif_work(ctx, R, ctx->rep_unit_bytes, w); if (st != MTR_OK) return st; }      // (the buffers are there: the layout alone)
-    const MotifGroups mg = motif_groups(ctx, w);
-    const size_t r = (size_t)R, g = (size_t)G;
-    const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
-    HIPCHK(hipMemcpyAsync(dst->motif_off, mg.motif_off, (g + 1) * 8, dd, ctx->stream));
-    if (R > 0) {
-        HIPCHK(hipMemcpyAsync(dst->strand, w.rows.strand, r, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->rotation, w.rows.rotation, r * 4, dd, ctx->stream));
-        HIPCHK(hipMemcpyAsync(dst->motif_len, w.rows.motif_len, r * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->group, mg.group, r * 4, dd, ctx->stream));
-    }
-    if (M > 0) HIPCHK(hipMemcpyAsync(dst->motifs, mg.motifs, (size_t)M, dd, ctx->stream));
-    if (G > 0) {
-        HIPCHK(hipMemcpyAsync(dst->g_first, mg.first, g * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->g_repeats, mg.repeats, g * 4, dd, ctx->stream));
-        HIPCHK(hipMemcpyAsync(dst->g_reads, mg.reads, g * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->g_copies, mg.copies, g * 8, dd, ctx->stream));
-        HIPCHK(hipMemcpyAsync(dst->g_bases, mg.bases, g * 8, dd, ctx->stream));
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
-
-// ---- known-motif search (motif_search.hip.inc) -------------------------------------------------------------------------------------
-// Only the lengths (already on the host) decide the work: one argsort per call, the slots' tables and at most five work lists go up, nothing
-// comes back but the status word.  Nothing kept lives in d_scratch (every user sizes and fills it per launch), so growing it here is safe.
-// (the checks in two parts: the locus search has arguments of its own to refuse between them; the scores', the total's and a motif's own
-// checks and words are loci_args.h's, which the genotype calls reach for their loci's motifs too)
-static mtr_status search_motifs_check_args(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs, int32_t gain, int32_t mismatch, int32_t indel)
-{
-    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
-    if (n_motifs <= 0) { ctx->err = "n_motifs = " + std::to_string(n_motifs) + ": at least one motif is needed"; return MTR_ERR_BAD_ARG; }
-    if (!motifs || !motif_off) { ctx->err = "motifs or motif_off is NULL"; return MTR_ERR_BAD_ARG; }
-    if (!la_check_scores(gain, mismatch, indel, ctx->err)) return MTR_ERR_BAD_ARG;
-    if (!la_check_motif_total(n_motifs, motif_off[n_motifs] - motif_off[0], ctx->err)) return MTR_ERR_BAD_ARG;
-    for (int32_t m = 0; m < n_motifs; m++) {
-        const char *s = motifs + motif_off[m];
-        const int64_t U = motif_off[m + 1] - motif_off[m];
-        if (U < 0) { ctx->err = "motif_off decreases at motif " + std::to_string(m); return MTR_ERR_BAD_ARG; }
-        const int64_t t = la_seq_check(false, s, U);
-        if (t < U) { ctx->err = la_refusal(la_motif_name(m), false, t, s, U); return MTR_ERR_BAD_ARG; }
-    }
-    return la_check_hits(ctx->n_reads, n_motifs, ctx->err) ? MTR_OK : MTR_ERR_BAD_ARG;
-}
-// the reference's WrapDPsize test (wrap_around_DP.c:260) for the longest read first, then for the read it names
-static mtr_status search_motifs_check_size(mtr_ctx *ctx, const int64_t *motif_off, int32_t n_motifs)
-{
-    for (int32_t m = 0; m < n_motifs; m++) {
-        const long long U = motif_off[m + 1] - motif_off[m];
-        if ((U + 1) * (long long)ctx->Lmax + U < ctx->wrap_dp_size) continue;
-        for (int i = 0; i < ctx->n_reads; i++)
-            if ((U + 1) * (long long)ctx->lens[(size_t)i] + U >= ctx->wrap_dp_size) {
-                ctx->err = "You need to increse the value of WrapDPsize. (read " + std::to_string(i) + " of " + std::to_string(ctx->lens[(size_t)i]) + " bases against motif " +
-                           std::to_string(m) + " of " + std::to_string(U) + " bases exceeds " + std::to_string(ctx->wrap_dp_size) + " cells)";
-                return MTR_ERR_DP_TOO_LARGE;
-            }
-    }
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_search_motifs_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs, int32_t gain, int32_t mismatch,
-                                               int32_t indel, int32_t both_strands, const mtr_motif_hits_dst *dst, int64_t *out_hits)
-{
-    if (!ctx || !out_hits) return MTR_ERR_BAD_ARG;
-    *out_hits = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    { mtr_status st = search_motifs_check_args(ctx, motifs, motif_off, n_motifs, gain, mismatch, indel); if (st != MTR_OK) return st; }
-    { mtr_status st = search_motifs_check_size(ctx, motif_off, n_motifs); if (st != MTR_OK) return st; }
-    const int n = ctx->n_reads;
-    const int64_t H = (int64_t)n * n_motifs;
-    *out_hits = H;
-    if (!dst) return MTR_OK;
-    if (dst->cap_hits < H) { ctx->err = "destination holds " + std::to_string(dst->cap_hits) + " hits, " + std::to_string(H) + " needed"; return MTR_ERR_OVERFLOW; }
-    if (!dst->fields || !dst->score || !dst->ratio || !dst->strand) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    const int lane_max = ctx->sw.motif_lane_max, lane_rows = ctx->sw.motif_lane_rows;
-    const int ns = both_strands ? 2 : 1, S = n_motifs * ns;
-    // the reads by descending length (ties in input order), the first n_long of them beyond the lane path
-    std::vector<int32_t> order((size_t)n);
-    for (int i = 0; i < n; i++) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return ctx->lens[(size_t)x] > ctx->lens[(size_t)y]; });
-    int n_long = 0;
-    while (n_long < n && ctx->lens[(size_t)order[(size_t)n_long]] > lane_rows) n_long++;
-    const long long L_first = ctx->lens[(size_t)order[0]], L_lane = n_long < n ? ctx->lens[(size_t)order[(size_t)n_long]] : 0;
-    std::vector<uint8_t> units; std::vector<int32_t> unit_off; std::vector<uint64_t> bits;
-    motif_slots(motifs, motif_off, n_motifs, ns, units, unit_off, bits);
-    // the work lists: one per bucket of the lane path (groups of 64 reads of the order from n_long on), one of the wave path (reads)
-    enum { N_LISTS = DP_LAUNCHES };
-    std::vector<int32_t> l_slot[N_LISTS]; std::vector<int64_t> l_first[N_LISTS]; int l_umax[N_LISTS] = { 0, 0, 0, 0, 0 };
-    const int64_t groups = ((int64_t)(n - n_long) + 63) / 64;
-    for (int k = 0; k < N_LISTS; k++) l_first[k].push_back(0);
-    for (int slot = 0; slot < S; slot++) {
-        const int U = unit_off[(size_t)slot + 1] - unit_off[(size_t)slot];
-        const bool lane = U <= lane_max && groups > 0;
-        if (lane) {
-            int k = 0; while (dp_bucket_ub(k) < U) k++;
-            l_slot[k].push_back(slot); l_first[k].push_back(l_first[k].back() + groups); l_umax[k] = std::max(l_umax[k], U);
-        }
-        const int64_t by_wave = U <= lane_max ? n_long : n;
-        if (by_wave > 0) { l_slot[4].push_back(slot); l_first[4].push_back(l_first[4].back() + by_wave); l_umax[4] = std::max(l_umax[4], U); }
-    }
-    // device copies: d_ms_i32 = order | unit_off | the lists' slots, d_ms_i64 = bits | the lists' firsts
-    const size_t nr = (size_t)n, sS = (size_t)S;
-    HIPCHK(ctx->d_ms_i32.ensure((nr + sS + 1 + N_LISTS * sS) * 4)); HIPCHK(ctx->d_ms_i64.ensure((sS + N_LISTS * (sS + 1)) * 8));
-    HIPCHK(ctx->d_ms_units.ensure(units.size() + 16)); HIPCHK(ctx->d_ms_res.ensure((size_t)H * (size_t)ns * MS_RES * 4));
-    HIPCHK(ctx->d_ms_status.ensure(4)); HIPCHK(ctx->d_ms_counter.ensure(N_LISTS * 8));
-    int32_t *d_order = ctx->d_ms_i32, *d_uoff = d_order + nr, *d_slots = d_uoff + sS + 1;
-    int64_t *d_bits = ctx->d_ms_i64, *d_firsts = d_bits + sS;
-    HIPCHK(copy_sync(ctx, d_order, order.data(), nr * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_uoff, unit_off.data(), (sS + 1) * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, d_bits, bits.data(), sS * 8, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_ms_units, units.data(), units.size(), hipMemcpyHostToDevice));
-    for (int k = 0; k < N_LISTS; k++) {
-        if (l_slot[k].empty()) continue;
-        HIPCHK(copy_sync(ctx, d_slots + (size_t)k * sS, l_slot[k].data(), l_slot[k].size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(copy_sync(ctx, d_firsts + (size_t)k * (sS + 1), l_first[k].data(), l_first[k].size() * 8, hipMemcpyHostToDevice));
-    }
-    // the launches' wavefronts and scratch (dp_task_plan.h: the five-launch plan)
-    const int64_t l_items[N_LISTS] = { l_first[0].back(), l_first[1].back(), l_first[2].back(), l_first[3].back(), l_first[4].back() };
-    const DpLaunchPlan plan = dp_search_plan(L_lane, L_first, l_umax, l_items, DpPick{ ctx });
-    { mtr_status s = ensure_scratch(ctx, plan.scratch); if (s != MTR_OK) return s; }
-    HIPCHK(hipMemsetAsync(ctx->d_ms_status, 0, 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_ms_counter, 0, N_LISTS * 8, ctx->stream));
-    MotifSearchArgs a{};
-    a.b.packed = ctx->d_packed; a.b.woff = ctx->d_woff; a.b.lens = ctx->d_lens; a.b.order = d_order; a.b.n_reads = n;
-    a.order = d_order; a.n_reads = n; a.n_long = n_long; a.units = ctx->d_ms_units; a.unit_off = d_uoff; a.bits = (const uint64_t *)d_bits;
-    a.n_motifs = n_motifs; a.n_strands = ns; a.G = gain; a.MM = mismatch; a.D = indel; a.res = ctx->d_ms_res;
-    a.scratch = ctx->d_scratch; a.status = ctx->d_ms_status; a.dp16_max_rows = ctx->sw.dp16_max_rows;
-    const mtr_status launched = dp_plan_launches(ctx, plan, a, (unsigned long long *)ctx->d_ms_counter, [&](int k, dim3 grid, dim3 block) {
-        a.work = { d_slots + (size_t)k * sS, d_firsts + (size_t)k * (sS + 1), (int32_t)l_slot[k].size(), l_first[k].back() };
-        DBG("search_motifs: list %d: %zu slots, %lld items, %d wavefronts of %zu bytes", k, l_slot[k].size(), (long long)l_first[k].back(), plan.waves[k], plan.per_wave[k]);
-        if (k < DP_LANE_BUCKETS) LAUNCH_BY_BUCKET(mtr_k_motif_lanes, dp_bucket_ub(k), grid, block, ctx->stream, a);
-        else hipLaunchKernelGGL(mtr_k_motif_waves, grid, block, 0, ctx->stream, a);
-    });
-    if (launched != MTR_OK) return launched;
-    // the status before the columns: a failed search writes nothing
-    int32_t dev = 0;
-    HIPCHK(copy_sync(ctx, &dev, ctx->d_ms_status, 4, hipMemcpyDeviceToHost));
-    if (dev == DEV_ERR_DP_TOO_LARGE) { ctx->err = "You need to increse the value of WrapDPsize. (a DP of the motif search exceeded it or its scratch)"; return MTR_ERR_DP_TOO_LARGE; }
-    if (dev != DEV_OK) { ctx->err = "the motif search failed on the device (status " + std::to_string(dev) + ")"; return MTR_ERR_HIP; }
-    const MotifHitsOut out = { dst->fields, dst->score, dst->ratio, dst->strand };
-    hipLaunchKernelGGL(mtr_k_motif_pack, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t *)ctx->d_ms_res, (int32_t)ns, H, out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
-
-// ---- known-motif locus search (motif_loci.hip.inc) ---------------------------------------------------------------------------------
-// Round by round: the host knows how many intervals a round has and their longest (LOCI_STATE, one small copy per round), sizes the round's
-// arrays and scratch from that, and enqueues its kernels; everything else - the bins, the work lists, the hits, the children - is made on the device.
-// at least `bytes`, with what the first `keep` bytes hold (the hit list grows from round to round)
-template <typename T>
-static hipError_t grow_keeping(mtr_ctx *ctx, DevBuf<T> &b, size_t keep, size_t bytes)
-{
-    if (b.p && bytes <= b.cap) return hipSuccess;
-    T *fresh = nullptr;
-    const size_t want = std::max<size_t>(bytes + bytes / 2, 256);
-    hipError_t e = hipMalloc((void **)&fresh, want);
-    if (e != hipSuccess) return e;
-    if (keep > 0 && b.p) e = copy_sync(ctx, fresh, b.p, keep, hipMemcpyDeviceToDevice);
-    b.release();
-    b.p = fresh; b.cap = want;
-    return e;
-}
-
-// One round's alignments: `tasks` tasks over a.iv (a.n_iv intervals of at most max_len bases), everything of `a` set but what one launch has of
-// its own.  Plans the launches as the search does, bins the tasks, enqueues the up to five DP launches.  counters: five item counters.  who: for MTR_DEBUG.
-static mtr_status loci_round(mtr_ctx *ctx, LociArgs &a, const LaneSlots &ls, int64_t tasks, int max_len, unsigned long long *counters, const char *who, int round)
-{
-    const size_t nb = (size_t)a.n_bins, nt = (size_t)tasks;
-    const DpLaunchPlan plan = dp_loci_plan(ls, tasks, max_len, a.lane_rows, DpPick{ ctx });
-    { mtr_status s = ensure_scratch(ctx, plan.scratch); if (s != MTR_OK) return s; }
-    a.scratch = ctx->d_scratch;
-    if (nb > 0) HIPCHK(hipMemsetAsync(a.hist, 0, nb * 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(counters, 0, 5 * 8, ctx->stream));
-    const dim3 per_task((unsigned)((nt + 255) / 256)), b256(256);
-    hipLaunchKernelGGL(mtr_k_loci_bin, per_task, b256, 0, ctx->stream, a);
-    if (nb > 0) {
-        hipLaunchKernelGGL(mtr_k_loci_groups, dim3((unsigned)((nb + 255) / 256)), b256, 0, ctx->stream, (const int32_t *)a.hist, (int32_t)nb, a.groups);
-        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.hist, (int64_t)nb, a.tfirst);
-        hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.groups, (int64_t)nb, a.gfirst);
-        hipLaunchKernelGGL(mtr_k_loci_scatter, per_task, b256, 0, ctx->stream, a);
-    }
-    HIPCHK(hipGetLastError());
-    return dp_plan_launches(ctx, plan, a, counters, [&](int k, dim3 grid, dim3 block) {
-        if (k < DP_LANE_BUCKETS) { a.bin0 = ls.q_first[k] * MLO_N_CLASSES; a.bin1 = ls.q_first[k + 1] * MLO_N_CLASSES; }
-        DBG("%s: round %d, %lld intervals of at most %d bases, launch %d: %d wavefronts of %zu bytes", who, round, (long long)a.n_iv, max_len, k, plan.waves[k], plan.per_wave[k]);
-        if (k < DP_LANE_BUCKETS) LAUNCH_BY_BUCKET(mtr_k_motif_loci_lanes, dp_bucket_ub(k), grid, block, ctx->stream, a);
-        else hipLaunchKernelGGL(mtr_k_motif_loci_waves, grid, block, 0, ctx->stream, a);
-    });
-}
-
-extern "C" mtr_status mtr_search_motif_loci_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, int32_t n_motifs, int32_t gain, int32_t mismatch,
-                                                   int32_t indel, int32_t both_strands, int32_t min_score, int32_t max_rounds, int64_t *out_pairs, int64_t *out_loci)
-{
-    if (!ctx || !out_pairs || !out_loci) return MTR_ERR_BAD_ARG;
-    *out_pairs = 0; *out_loci = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    ctx->ml_ready = false;                                                                             // whatever happens below, the loci kept before this call are gone
-    { mtr_status st = search_motifs_check_args(ctx, motifs, motif_off, n_motifs, gain, mismatch, indel); if (st != MTR_OK) return st; }
-    if (min_score < 1) { ctx->err = "min_score = " + std::to_string(min_score) + ": at least 1"; return MTR_ERR_BAD_ARG; }
-    if (max_rounds < 1 || max_rounds > MLO_MAX_ROUNDS) { ctx->err = "max_rounds = " + std::to_string(max_rounds) + " outside 1.." + std::to_string(MLO_MAX_ROUNDS); return MTR_ERR_BAD_ARG; }
-    { mtr_status st = search_motifs_check_size(ctx, motif_off, n_motifs); if (st != MTR_OK) return st; }
-    HIPCHK(hipSetDevice(ctx->device));
-    read_switches(ctx->sw);
-    const int lane_max = ctx->sw.motif_lane_max, lane_rows = ctx->sw.motif_lane_rows;
-    const int n = ctx->n_reads, ns = both_strands ? 2 : 1, S = n_motifs * ns, minlen = mlo_minlen(min_score, gain);
-    const int64_t P = (int64_t)n * n_motifs;
-    std::vector<uint8_t> units; std::vector<int32_t> unit_off; std::vector<uint64_t> bits;
-    motif_slots(motifs, motif_off, n_motifs, ns, units, unit_off, bits);
-    const LaneSlots ls = lane_slots(unit_off, S, lane_max);
-    const std::vector<int32_t> &slot_q = ls.slot_q, &q_slot = ls.q_slot;
-    const size_t sS = (size_t)S, nq = q_slot.size();
-    if ((int64_t)nq * MLO_N_CLASSES > (int64_t)INT32_MAX) { ctx->err = std::to_string(nq) + " short motifs are more than the bins take"; return MTR_ERR_OVERFLOW; }
-    const size_t nb = nq * MLO_N_CLASSES;
-    // device copies: d_ml_i32 = unit_off | slot_q | q_slot, d_ml_i64 = bits; the bins: d_ml_bin32 = hist | groups, d_ml_bin64 = tfirst | gfirst
-    HIPCHK(ctx->d_ml_i32.ensure((2 * sS + 1 + nq + 1) * 4)); HIPCHK(ctx->d_ml_i64.ensure(sS * 8)); HIPCHK(ctx->d_ml_units.ensure(units.size() + 16));
-    HIPCHK(ctx->d_ml_bin32.ensure((2 * nb + 1) * 4)); HIPCHK(ctx->d_ml_bin64.ensure(2 * (nb + 1) * 8));
-    HIPCHK(ctx->d_ml_state.ensure(LOCI_STATE * 4)); HIPCHK(ctx->d_ml_counter.ensure(5 * 8)); HIPCHK(ctx->d_ml_open.ensure((size_t)P));
-    int32_t *d_uoff = ctx->d_ml_i32, *d_slot_q = d_uoff + sS + 1, *d_q_slot = d_slot_q + sS;
-    HIPCHK(copy_sync(ctx, d_uoff, unit_off.data(), (sS + 1) * 4, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, d_slot_q, slot_q.data(), sS * 4, hipMemcpyHostToDevice));
-    if (nq > 0) HIPCHK(copy_sync(ctx, d_q_slot, q_slot.data(), nq * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(ctx, ctx->d_ml_i64, bits.data(), sS * 8, hipMemcpyHostToDevice)); HIPCHK(copy_sync(ctx, ctx->d_ml_units, units.data(), units.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(ctx->d_ml_state, 0, LOCI_STATE * 4, ctx->stream)); HIPCHK(hipMemsetAsync(ctx->d_ml_open, 0, (size_t)P, ctx->stream));
-    LociArgs a{};
-    a.b.packed = ctx->d_packed; a.b.woff = ctx->d_woff; a.b.lens = ctx->d_lens; a.b.order = nullptr; a.b.n_reads = n;
-    a.n_motifs = n_motifs; a.n_strands = ns; a.G = gain; a.MM = mismatch; a.D = indel; a.lane_rows = lane_rows;
-    a.units = ctx->d_ml_units; a.unit_off = d_uoff; a.bits = (const uint64_t *)(int64_t *)ctx->d_ml_i64; a.slot_q = d_slot_q; a.q_slot = d_q_slot;
-    a.hist = ctx->d_ml_bin32; a.groups = a.hist + nb; a.tfirst = ctx->d_ml_bin64; a.gfirst = a.tfirst + nb + 1; a.n_bins = (int32_t)nb;
-    a.state = ctx->d_ml_state; a.dp16_max_rows = ctx->sw.dp16_max_rows;
-    // round 0: every pair's whole read
-    HIPCHK(ctx->d_ml_iv[0].ensure((size_t)P * sizeof(LociIv)));
-    hipLaunchKernelGGL(mtr_k_loci_init, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t *)ctx->d_lens, n_motifs, (int32_t)P, (LociIv *)ctx->d_ml_iv[0]);
-    HIPCHK(hipGetLastError());
-    int64_t N = P, T = 0;
-    int max_len = ctx->Lmax;
-    for (int d = 0; d < max_rounds && N > 0; d++) {
-        const int64_t tasks = N * ns;
-        if (tasks > (int64_t)INT32_MAX || T + N > (int64_t)INT32_MAX) {
-            ctx->err = "round " + std::to_string(d) + ": " + std::to_string(tasks) + " alignments after " + std::to_string(T) + " loci are more than 2^31 - 1"; return MTR_ERR_OVERFLOW;
-        }
-        const size_t nt = (size_t)tasks;
-        LociIv *next = nullptr;
-        {   // the round's arrays: d_ml_task32 = tbin | trank | sorted | wlist; the next round holds at most two intervals per interval, the hit list one more hit
-            DevBuf<LociIv> &nx = ctx->d_ml_iv[(d + 1) & 1];
-            HIPCHK(ctx->d_ml_task32.ensure(4 * nt * 4)); HIPCHK(ctx->d_ml_res.ensure(nt * MS_RES * 4)); HIPCHK(nx.ensure(2 * (size_t)N * sizeof(LociIv)));
-            HIPCHK(grow_keeping(ctx, ctx->d_ml_hits, (size_t)T * LOCI_HIT * 4, (size_t)(T + N) * LOCI_HIT * 4));
-            next = nx;
-        }
-        a.iv = ctx->d_ml_iv[d & 1]; a.n_iv = (int32_t)N;
-        a.tbin = ctx->d_ml_task32; a.trank = a.tbin + nt; a.sorted = a.trank + nt; a.wlist = a.sorted + nt; a.res = ctx->d_ml_res;
-        HIPCHK(hipMemsetAsync(a.state + LOCI_NEXT, 0, (LOCI_STATE - LOCI_NEXT) * 4, ctx->stream));
-        { mtr_status s = loci_round(ctx, a, ls, tasks, max_len, (unsigned long long *)ctx->d_ml_counter, "search_motif_loci", d); if (s != MTR_OK) return s; }
-        const dim3 b256(256);
-        hipLaunchKernelGGL(mtr_k_loci_split, dim3((unsigned)((N + 255) / 256)), b256, 0, ctx->stream, a, min_score, (int32_t)minlen, max_rounds, (int32_t)d,
-                           next, (int32_t)std::min<int64_t>(2 * N, INT32_MAX), (int32_t *)ctx->d_ml_hits, (int32_t)(T + N), (uint8_t *)ctx->d_ml_open);
-        HIPCHK(hipGetLastError());
-        // the round's one look at the device: its verdict, the loci so far, the next round's intervals and their longest
-        int32_t st[LOCI_STATE];
-        HIPCHK(copy_sync(ctx, st, ctx->d_ml_state, sizeof st, hipMemcpyDeviceToHost));
-        if (st[LOCI_STATUS] == DEV_ERR_DP_TOO_LARGE) { ctx->err = "You need to increse the value of WrapDPsize. (a DP of the locus search exceeded it or its scratch)"; return MTR_ERR_DP_TOO_LARGE; }
-        if (st[LOCI_STATUS] != DEV_OK) { ctx->err = "the locus search failed on the device (status " + std::to_string(st[LOCI_STATUS]) + ", round " + std::to_string(d) + ")"; return MTR_ERR_HIP; }
-        if (st[LOCI_HITS] < T || st[LOCI_HITS] > T + N || st[LOCI_NEXT] < 0 || st[LOCI_NEXT] > 2 * N || st[LOCI_MAXLEN] > max_len) { ctx->err = "the locus search's lists are inconsistent"; return MTR_ERR_HIP; }
-        T = st[LOCI_HITS]; N = st[LOCI_NEXT]; max_len = st[LOCI_MAXLEN];
-    }
-    // the finish: per pair its loci counted, the offsets, every locus at its rank by start
-    const size_t np = (size_t)P, nl = std::max<size_t>((size_t)T, 1);
-    HIPCHK(ctx->d_ml_count.ensure(np * 4)); HIPCHK(ctx->d_ml_off.ensure((np + 1) * 8)); HIPCHK(ctx->d_ml_starts.ensure(nl * 4));
-    HIPCHK(ctx->d_ml_fields.ensure(nl * 32)); HIPCHK(ctx->d_ml_score.ensure(nl * 4)); HIPCHK(ctx->d_ml_ratio.ensure(nl * 4)); HIPCHK(ctx->d_ml_strand.ensure(nl));
-    HIPCHK(hipMemsetAsync(ctx->d_ml_count, 0, np * 4, ctx->stream));
-    const dim3 per_hit((unsigned)((nl + 255) / 256)), b256(256);
-    if (T > 0) hipLaunchKernelGGL(mtr_k_loci_count, per_hit, b256, 0, ctx->stream, (int32_t *)ctx->d_ml_hits, (int32_t)T, (int32_t *)ctx->d_ml_count);
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)ctx->d_ml_count, P, (int64_t *)ctx->d_ml_off);
-    if (T > 0) {
-        const MotifLociOut out = { ctx->d_ml_fields, ctx->d_ml_score, ctx->d_ml_ratio, ctx->d_ml_strand };
-        hipLaunchKernelGGL(mtr_k_loci_starts, per_hit, b256, 0, ctx->stream, (const int32_t *)ctx->d_ml_hits, (int32_t)T, (const int64_t *)ctx->d_ml_off, (int32_t *)ctx->d_ml_starts);
-        hipLaunchKernelGGL(mtr_k_loci_place, per_hit, b256, 0, ctx->stream, (const int32_t *)ctx->d_ml_hits, (int32_t)T, (const int64_t *)ctx->d_ml_off,
-                           (const int32_t *)ctx->d_ml_starts, out);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->ml_ready = true; ctx->ml_pairs = P; ctx->ml_loci = T;
-    *out_pairs = P; *out_loci = T;
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_motif_loci_copy_device(mtr_ctx *ctx, const mtr_motif_loci_dst *dst)
-{
-    if (!ctx) return MTR_ERR_BAD_ARG;
-    if (!ctx->ml_ready) { ctx->err = "no loci kept: mtr_search_motif_loci_device comes first (an upload discards what it kept)"; return MTR_ERR_BAD_ARG; }
-    if (!dst) { ctx->err = "dst is NULL"; return MTR_ERR_BAD_ARG; }
-    const int64_t P = ctx->ml_pairs, T = ctx->ml_loci;
-    if (dst->cap_pairs < P || dst->cap_loci < T) {
-        ctx->err = "destination holds " + std::to_string(dst->cap_pairs) + " pairs and " + std::to_string(dst->cap_loci) + " loci, " + std::to_string(P) + " and " + std::to_string(T) + " needed";
-        return MTR_ERR_OVERFLOW;
-    }
-    if (!dst->loci_off || !dst->open || (T > 0 && (!dst->fields || !dst->score || !dst->ratio || !dst->strand))) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
-    const size_t p = (size_t)P, t = (size_t)T;
-    HIPCHK(hipMemcpyAsync(dst->loci_off, ctx->d_ml_off, (p + 1) * 8, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->open, ctx->d_ml_open, p, dd, ctx->stream));
-    if (T > 0) {
-        HIPCHK(hipMemcpyAsync(dst->fields, ctx->d_ml_fields, t * 32, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->score, ctx->d_ml_score, t * 4, dd, ctx->stream));
-        HIPCHK(hipMemcpyAsync(dst->ratio, ctx->d_ml_ratio, t * 4, dd, ctx->stream)); HIPCHK(hipMemcpyAsync(dst->strand, ctx->d_ml_strand, t, dd, ctx->stream));
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
+#include "motif_host.hip.inc"
 
 #include "genotype_host.hip.inc"
 
-// ---- allele calls (allele_call.hip.inc) ------------------------------------------------------------------------------------------------
-// The arguments' checks, the count and the offsets, one look at the device (the status, S, the tiles), then the fill, the rank and the split
-// straight into the caller's columns.  No batch is needed and none is touched.
-// rows: the four input columns with R rows; row_read / row_locus: NULL for the dense layout (row = read * n_loci + locus), else the rows' own
-static mtr_status call_alleles_rows(mtr_ctx *ctx, const mtr_genotypes_dst *rows, int64_t R, int32_t n_loci, const int32_t *row_read, const int32_t *row_locus,
-                                    const mtr_allele_params *prm, void *wait_stream, const mtr_allele_calls_dst *dst, int64_t *out_support)
-{
-    if (prm->measure != MTR_ALLELE_COPIES && prm->measure != MTR_ALLELE_BASES) { ctx->err = "measure " + std::to_string(prm->measure) + " is neither MTR_ALLELE_COPIES nor MTR_ALLELE_BASES"; return MTR_ERR_BAD_ARG; }
-    if (!(prm->min_ratio >= 0.0f && prm->min_ratio <= 1.0f)) { ctx->err = "min_ratio " + std::to_string(prm->min_ratio) + " outside 0..1"; return MTR_ERR_BAD_ARG; }
-    if (prm->min_support < 1) { ctx->err = "min_support " + std::to_string(prm->min_support) + ": at least 1"; return MTR_ERR_BAD_ARG; }
-    if (prm->min_percent < 0 || prm->min_percent > 50) { ctx->err = "min_percent " + std::to_string(prm->min_percent) + " outside 0..50"; return MTR_ERR_BAD_ARG; }
-    if (prm->min_sep < 1) { ctx->err = "min_sep " + std::to_string(prm->min_sep) + ": at least 1"; return MTR_ERR_BAD_ARG; }
-    if (R > 0 && (!rows->spanning || !rows->window || !rows->fields || !rows->ratio)) { ctx->err = "an input column (spanning, window, fields, ratio) is NULL"; return MTR_ERR_BAD_ARG; }
-    if (rows->cap_rows < R) { ctx->err = "cap_rows " + std::to_string(rows->cap_rows) + " of the input is below " + std::to_string(R) + " rows"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    if (R > 0) {
-        { mtr_status st = check_device_ptr(ctx, rows->spanning, R, "rows->spanning", "the rows' bytes"); if (st != MTR_OK) return st; }
-        { mtr_status st = check_device_ptr(ctx, (const uint8_t *)rows->window, R * 8, "rows->window", "the rows' bytes"); if (st != MTR_OK) return st; }
-        { mtr_status st = check_device_ptr(ctx, (const uint8_t *)rows->fields, R * 32, "rows->fields", "the rows' bytes"); if (st != MTR_OK) return st; }
-        { mtr_status st = check_device_ptr(ctx, (const uint8_t *)rows->ratio, R * 4, "rows->ratio", "the rows' bytes"); if (st != MTR_OK) return st; }
-        if (row_locus) {
-            { mtr_status st = check_device_ptr(ctx, (const uint8_t *)row_read, R * 4, "row_read", "the rows' bytes"); if (st != MTR_OK) return st; }
-            { mtr_status st = check_device_ptr(ctx, (const uint8_t *)row_locus, R * 4, "row_locus", "the rows' bytes"); if (st != MTR_OK) return st; }
-        }
-    }
-    const size_t nl = (size_t)n_loci;
-    const size_t cstride = n_loci <= AL_SPREAD_LOCI ? AL_SPREAD : 1;
-    HIPCHK(ctx->d_ac_i32.ensure(2 * nl * cstride * 4)); HIPCHK(ctx->d_ac_i64.ensure((2 * (nl + 1) + AL_STATE) * 8));
-    AlleleArgs a{};
-    a.spanning = rows->spanning; a.window = rows->window; a.fields = rows->fields; a.ratio = rows->ratio;
-    a.row_read = R > 0 ? row_read : nullptr; a.row_locus = R > 0 ? row_locus : nullptr;
-    a.rows = R; a.n_loci = n_loci; a.measure = prm->measure; a.min_ratio = prm->min_ratio; a.rule = { prm->min_support, prm->min_percent, prm->min_sep };
-    a.count = ctx->d_ac_i32; a.cursor = a.count + nl * cstride; a.cstride = (int32_t)cstride; a.off = ctx->d_ac_i64; a.tile_off = a.off + nl + 1; a.state = a.tile_off + nl + 1;
-    // the rows come from the caller's stream: the kernels wait for it there, not for the whole device
-    if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(ctx->ev_text, (hipStream_t)wait_stream));
-    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
-    if (a.row_locus) {
-        // the index columns before anything else reads them: every locus in range, every (locus, read) once - the rank's keys are distinct by that
-        unsigned long long cap = 64; while (cap < 2 * (unsigned long long)R) cap <<= 1;
-        HIPCHK(ctx->d_ac_keys.ensure((size_t)(cap + 2) * 8));
-        unsigned long long *set = ctx->d_ac_keys, *bad = set + cap;
-        HIPCHK(hipMemsetAsync(set, 0xff, (size_t)(cap + 2) * 8, ctx->stream));
-        hipLaunchKernelGGL(mtr_k_cat_rows_check, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, ctx->stream, row_read, row_locus, R, n_loci, set, cap, bad);
-        HIPCHK(hipGetLastError());
-        unsigned long long found[2];
-        HIPCHK(copy_sync(ctx, found, bad, sizeof found, hipMemcpyDeviceToHost));
-        if (found[0] != ~0ull) {
-            int32_t rl[2] = { 0, 0 };
-            HIPCHK(copy_sync(ctx, &rl[0], row_read + found[0], 4, hipMemcpyDeviceToHost)); HIPCHK(copy_sync(ctx, &rl[1], row_locus + found[0], 4, hipMemcpyDeviceToHost));
-            ctx->err = "row " + std::to_string(found[0]) + ": read " + std::to_string(rl[0]) + " is negative or locus " + std::to_string(rl[1]) + " is outside 0.." + std::to_string(n_loci - 1);
-            return MTR_ERR_BAD_ARG;
-        }
-        if (found[1] != ~0ull) {
-            ctx->err = "(locus " + std::to_string(found[1] >> 32) + ", read " + std::to_string(found[1] & 0xffffffffull) + ") is given by more than one row";
-            return MTR_ERR_BAD_ARG;
-        }
-    }
-    HIPCHK(hipMemsetAsync(ctx->d_ac_i32, 0, 2 * nl * cstride * 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(a.state, 0xff, 8, ctx->stream));
-    const dim3 per_row((unsigned)((R + AL_BLOCK - 1) / AL_BLOCK)), blk(AL_BLOCK);
-    if (R > 0) hipLaunchKernelGGL(mtr_k_allele_count, per_row, blk, 0, ctx->stream, a);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(mtr_k_allele_offsets, dim3(1), dim3(64), 0, ctx->stream, a);
-    HIPCHK(hipGetLastError());
-    int64_t st[AL_STATE];
-    HIPCHK(copy_sync(ctx, st, a.state, 3 * 8, hipMemcpyDeviceToHost));
-    const int64_t S = st[AL_TOTAL], n_tiles = st[AL_TILES];
-    if (S < 0 || S > R || n_tiles < 0 || n_tiles > S) { ctx->err = "the allele calls' count failed on the device"; return MTR_ERR_HIP; }
-    *out_support = S;
-    if (st[AL_BAD] != -1) {
-        const int64_t p = st[AL_BAD];
-        int64_t rd = p / n_loci, l = p % n_loci;
-        if (a.row_locus) {
-            int32_t rl[2] = { 0, 0 };
-            HIPCHK(copy_sync(ctx, &rl[0], row_read + p, 4, hipMemcpyDeviceToHost)); HIPCHK(copy_sync(ctx, &rl[1], row_locus + p, 4, hipMemcpyDeviceToHost));
-            rd = rl[0]; l = rl[1];
-        }
-        ctx->err = "row " + std::to_string(p) + " (read " + std::to_string(rd) + ", locus " + std::to_string(l) + ") supports its locus with a negative value";
-        return MTR_ERR_BAD_ARG;
-    }
-    if (!dst) return MTR_OK;
-    if (dst->cap_loci < n_loci) { ctx->err = "destination holds " + std::to_string(dst->cap_loci) + " loci, " + std::to_string(n_loci) + " needed"; return MTR_ERR_OVERFLOW; }
-    if (dst->cap_support < S) { ctx->err = "destination holds " + std::to_string(dst->cap_support) + " supporting rows, " + std::to_string(S) + " needed"; return MTR_ERR_OVERFLOW; }
-    if (!dst->support_off || !dst->zygosity || !dst->call || !dst->call_support || !dst->cost || (S > 0 && (!dst->value || !dst->read || !dst->allele))) {
-        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
-    }
-    HIPCHK(ctx->d_ac_keys.ensure((size_t)std::max<int64_t>(S, 1) * 8)); HIPCHK(ctx->d_ac_prefix.ensure(((size_t)S + nl) * 8));
-    a.keys = ctx->d_ac_keys; a.prefix = ctx->d_ac_prefix;
-    a.value = dst->value; a.read = dst->read; a.allele = dst->allele; a.zygosity = dst->zygosity; a.call = dst->call; a.call_support = dst->call_support; a.cost = dst->cost;
-    if (S > 0) {
-        hipLaunchKernelGGL(mtr_k_allele_fill, per_row, blk, 0, ctx->stream, a);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(mtr_k_allele_rank, dim3((unsigned)std::min<int64_t>(n_tiles, AL_MAX_GRID)), dim3(AL_TILE), 0, ctx->stream, a, n_tiles);
-        HIPCHK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(mtr_k_allele_split, dim3((unsigned)std::min<int64_t>(n_loci, AL_MAX_GRID)), blk, 0, ctx->stream, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dst->support_off, a.off, (nl + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_call_alleles_device(mtr_ctx *ctx, const mtr_genotypes_dst *rows, int64_t n_reads, int32_t n_loci, const mtr_allele_params *prm,
-                                              void *wait_stream, const mtr_allele_calls_dst *dst, int64_t *out_support)
-{
-    if (!ctx || !out_support) return MTR_ERR_BAD_ARG;
-    *out_support = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    if (!rows || !prm) { ctx->err = "rows or prm is NULL"; return MTR_ERR_BAD_ARG; }
-    if (n_reads < 1) { ctx->err = "n_reads = " + std::to_string(n_reads) + ": at least one read is needed"; return MTR_ERR_BAD_ARG; }
-    if (n_loci < 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
-    if (n_reads > (int64_t)INT32_MAX / n_loci) { ctx->err = std::to_string(n_reads) + " reads x " + std::to_string(n_loci) + " loci are more than 2^31 - 1 rows"; return MTR_ERR_BAD_ARG; }
-    return call_alleles_rows(ctx, rows, n_reads * n_loci, n_loci, nullptr, nullptr, prm, wait_stream, dst, out_support);
-}
-
-extern "C" mtr_status mtr_call_alleles_rows_device(mtr_ctx *ctx, const mtr_genotypes_dst *rows, const int32_t *row_read, const int32_t *row_locus, int64_t n_rows,
-                                                   int32_t n_loci, const mtr_allele_params *prm, void *wait_stream, const mtr_allele_calls_dst *dst, int64_t *out_support)
-{
-    if (!ctx || !out_support) return MTR_ERR_BAD_ARG;
-    *out_support = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    if (!rows || !prm) { ctx->err = "rows or prm is NULL"; return MTR_ERR_BAD_ARG; }
-    if (n_rows < 0 || n_rows > (int64_t)INT32_MAX) { ctx->err = "n_rows = " + std::to_string(n_rows) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
-    if (n_loci < 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + ": at least one locus is needed"; return MTR_ERR_BAD_ARG; }
-    if (n_rows > 0 && (!row_read || !row_locus)) { ctx->err = "row_read or row_locus is NULL"; return MTR_ERR_BAD_ARG; }
-    return call_alleles_rows(ctx, rows, n_rows, n_loci, row_read, row_locus, prm, wait_stream, dst, out_support);
-}
-
-// ---- windows and allele consensus (consensus.hip.inc) ------------------------------------------------------------------------------------
-// the caller's stream before the context's, and the bad-input words set to "none"
-static mtr_status cons_begin(mtr_ctx *ctx, void *wait_stream)
-{
-    HIPCHK(ctx->d_co_state.ensure((CO_BAD + CO_STATE) * 8));
-    if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(ctx->ev_text, (hipStream_t)wait_stream));
-    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
-    HIPCHK(hipMemsetAsync(ctx->d_co_state, 0xff, CO_BAD * 8, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_co_state + CO_BAD, 0, CO_STATE * 8, ctx->stream));
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_extract_windows_device(mtr_ctx *ctx, const int32_t *row_read, const uint8_t *orientation, const int32_t *window, int64_t n_rows,
-                                                 void *wait_stream, const mtr_windows_dst *dst, int64_t *out_bases)
-{
-    if (!ctx || !out_bases) return MTR_ERR_BAD_ARG;
-    *out_bases = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
-    const int64_t R = n_rows;
-    if (R < 0 || R > (int64_t)INT32_MAX) { ctx->err = "n_rows = " + std::to_string(R) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
-    if (R > 0 && (!row_read || !orientation || !window)) { ctx->err = "row_read, orientation or window is NULL"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    if (R > 0) {
-        { mtr_status st = check_device_ptr(ctx, (const uint8_t *)row_read, R * 4, "row_read", "the rows' bytes"); if (st != MTR_OK) return st; }
-        { mtr_status st = check_device_ptr(ctx, orientation, R, "orientation", "the rows' bytes"); if (st != MTR_OK) return st; }
-        { mtr_status st = check_device_ptr(ctx, (const uint8_t *)window, R * 8, "window", "the rows' bytes"); if (st != MTR_OK) return st; }
-    }
-    const size_t nr = (size_t)R;
-    HIPCHK(ctx->d_co_i32.ensure(std::max<size_t>(nr, 1) * 4)); HIPCHK(ctx->d_co_i64.ensure((nr + 1) * 8));
-    { mtr_status st = cons_begin(ctx, wait_stream); if (st != MTR_OK) return st; }
-    unsigned long long *bad = ctx->d_co_state;
-    int32_t *len = ctx->d_co_i32; int64_t *off = ctx->d_co_i64;
-    if (R > 0) hipLaunchKernelGGL(mtr_k_win_len, dim3((unsigned)((R + CO_BLOCK - 1) / CO_BLOCK)), dim3(CO_BLOCK), 0, ctx->stream, row_read, window, R,
-                                  (const int32_t *)ctx->d_lens, (int32_t)ctx->n_reads, len, bad);
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)len, R, off);
-    HIPCHK(hipGetLastError());
-    unsigned long long found = 0; int64_t T = 0;
-    HIPCHK(hipMemcpyAsync(&T, off + R, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(copy_sync(ctx, &found, bad + 5, 8, hipMemcpyDeviceToHost));
-    if (found != ~0ull) {
-        int32_t v[3] = { 0, 0, 0 };
-        HIPCHK(copy_sync(ctx, &v[0], row_read + found, 4, hipMemcpyDeviceToHost)); HIPCHK(copy_sync(ctx, &v[1], window + 2 * found, 8, hipMemcpyDeviceToHost));
-        ctx->err = "row " + std::to_string(found) + ": read " + std::to_string(v[0]) + " is outside the batch of " + std::to_string(ctx->n_reads) + " reads, or its window " +
-                   std::to_string(v[1]) + ".." + std::to_string(v[2]) + " outside the read";
-        return MTR_ERR_BAD_ARG;
-    }
-    if (T < 0) { ctx->err = "the windows' scan failed on the device"; return MTR_ERR_HIP; }
-    *out_bases = T;
-    if (!dst) return MTR_OK;
-    if (dst->cap_rows < R) { ctx->err = "destination holds " + std::to_string(dst->cap_rows) + " rows, " + std::to_string(R) + " needed"; return MTR_ERR_OVERFLOW; }
-    if (dst->cap_bases < T) { ctx->err = "destination holds " + std::to_string(dst->cap_bases) + " bases, " + std::to_string(T) + " needed"; return MTR_ERR_OVERFLOW; }
-    if (!dst->win_off || (T > 0 && !dst->win_bases)) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
-    if (T > 0) {
-        hipLaunchKernelGGL(mtr_k_win_gather, dim3((unsigned)std::min<int64_t>(R, CO_MAX_GRID)), dim3(64), 0, ctx->stream, row_read, orientation, window, R,
-                           (const uint32_t *)ctx->d_packed, (const int64_t *)ctx->d_woff, (const int64_t *)off, dst->win_bases);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(dst->win_off, off, (nr + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
-
-// one bucket's alignments: the grid is bounded by the scratch it may take (each wavefront its own directions, sized by the bucket's longest task)
-template <int CPL>
-static mtr_status cons_align_bucket(mtr_ctx *ctx, const ConsArgs &a, int bucket, unsigned n_tasks, unsigned longest)
-{
-    if (n_tasks == 0) return MTR_OK;
-    const int64_t words = ((int64_t)(longest >> 4) + 1) * CPL * 64;
-    const int64_t cap_words = (int64_t)(std::min(ctx->sw.scratch_max_gb, 0.25) * (double)(1ll << 30) / 4.0);      // a quarter of a GB at the most, under the context's scratch cap
-    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_tasks, (int64_t)ctx->n_cu * 16), cap_words / words));
-    HIPCHK(ctx->d_co_dirs.ensure((size_t)(grid * words) * 4));
-    hipLaunchKernelGGL(mtr_k_cons_align<CPL>, dim3((unsigned)grid), dim3(64), 0, ctx->stream, a, bucket, n_tasks, (uint32_t *)ctx->d_co_dirs, words);
-    HIPCHK(hipGetLastError());
-    return MTR_OK;
-}
-
-extern "C" mtr_status mtr_allele_consensus_device(mtr_ctx *ctx, const mtr_consensus_src *src, int32_t band_extra, void *wait_stream,
-                                                  const mtr_consensus_dst *dst, int64_t *out_bases)
-{
-    if (!ctx || !out_bases) return MTR_ERR_BAD_ARG;
-    *out_bases = 0;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    if (!src) { ctx->err = "src is NULL"; return MTR_ERR_BAD_ARG; }
-    const int64_t R = src->n_rows, S = src->n_support, NB = src->n_bases; const int32_t n_loci = src->n_loci;
-    if (n_loci < 1 || n_loci > (1 << 30) - 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + " outside 1..2^30 - 1"; return MTR_ERR_BAD_ARG; }
-    if (R < 0 || R > (int64_t)INT32_MAX) { ctx->err = "n_rows = " + std::to_string(R) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
-    if (S < 0 || S > (int64_t)INT32_MAX) { ctx->err = "n_support = " + std::to_string(S) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
-    if (NB < 0 || NB > (int64_t)INT32_MAX) { ctx->err = "n_bases = " + std::to_string(NB) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
-    if (band_extra < 0 || band_extra > MTR_CONS_MAX_EXTRA) { ctx->err = "band_extra = " + std::to_string(band_extra) + " outside 0.." + std::to_string(MTR_CONS_MAX_EXTRA); return MTR_ERR_BAD_ARG; }
-    if (!src->win_off || !src->support_off || !src->zygosity || (R > 0 && (!src->row_read || !src->row_locus)) || (NB > 0 && !src->win_bases) ||
-        (S > 0 && (!src->read || !src->allele))) { ctx->err = "an input column is NULL"; return MTR_ERR_BAD_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    {
-        const struct { const void *p; int64_t bytes; const char *what; } cols[8] = {
-            { src->row_read, R * 4, "src->row_read" }, { src->row_locus, R * 4, "src->row_locus" }, { src->win_off, (R + 1) * 8, "src->win_off" }, { src->win_bases, NB, "src->win_bases" },
-            { src->support_off, ((int64_t)n_loci + 1) * 8, "src->support_off" }, { src->read, S * 4, "src->read" }, { src->allele, S, "src->allele" }, { src->zygosity, n_loci, "src->zygosity" } };
-        for (const auto &c : cols)
-            if (c.bytes > 0) { mtr_status st = check_device_ptr(ctx, (const uint8_t *)c.p, c.bytes, c.what, "the column's bytes"); if (st != MTR_OK) return st; }
-    }
-    read_switches(ctx->sw);
-    const size_t G = 2 * (size_t)n_loci, ns = (size_t)S;
-    HIPCHK(ctx->d_co_i32.ensure((ns + 9 * G) * 4)); HIPCHK(ctx->d_co_i64.ensure(2 * (G + 1) * 8)); HIPCHK(ctx->d_co_tasks.ensure(std::max<size_t>(2 * ns, 1) * sizeof(int4)));
-    { mtr_status st = cons_begin(ctx, wait_stream); if (st != MTR_OK) return st; }
-    ConsArgs a{};
-    a.row_read = src->row_read; a.row_locus = src->row_locus; a.R = R; a.win_off = src->win_off; a.win_bases = src->win_bases; a.n_bases = NB;
-    a.support_off = src->support_off; a.sup_read = src->read; a.sup_allele = src->allele; a.zygosity = src->zygosity; a.S = S; a.n_loci = n_loci; a.band_extra = band_extra;
-    int32_t *i32 = ctx->d_co_i32;
-    a.ent_row = i32; a.bb_ent = i32 + ns; a.bb_row = a.bb_ent + G; a.bb_read = a.bb_row + G; a.bb_len = a.bb_read + G; a.members = a.bb_len + G; a.aligned = a.members + G;
-    a.skipped = a.aligned + G; a.tab_len = a.skipped + G; a.cons_len = a.tab_len + G;
-    a.tab_off = ctx->d_co_i64; a.cons_off = a.tab_off + G + 1; a.tasks = ctx->d_co_tasks;
-    a.bad = ctx->d_co_state; a.state = (unsigned *)(a.bad + CO_BAD);
-    const auto blocks = [](int64_t n) { return dim3((unsigned)((std::max<int64_t>(n, 1) + CO_BLOCK - 1) / CO_BLOCK)); };
-    const dim3 blk(CO_BLOCK);
-    unsigned long long bad[CO_BAD];
-    hipLaunchKernelGGL(mtr_k_cons_check, blocks(std::max<int64_t>(R, n_loci)), blk, 0, ctx->stream, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(copy_sync(ctx, bad, a.bad, sizeof bad, hipMemcpyDeviceToHost));
-    if (bad[0] != ~0ull) { ctx->err = "row " + std::to_string(bad[0]) + " is out of order: the rows must ascend by (read, locus), each pair once, none negative"; return MTR_ERR_BAD_ARG; }
-    if (bad[1] != ~0ull) { ctx->err = "win_off at row " + std::to_string(bad[1]) + " does not ascend from 0 to n_bases, or the window is above 2^30 bases"; return MTR_ERR_BAD_ARG; }
-    if (bad[2] != ~0ull) { ctx->err = "locus " + std::to_string(bad[2]) + ": support_off does not ascend from 0 to n_support, or the zygosity is above 2"; return MTR_ERR_BAD_ARG; }
-    if (S > 0) {
-        hipLaunchKernelGGL(mtr_k_cons_members, blocks(S), blk, 0, ctx->stream, a);
-        HIPCHK(hipGetLastError());
-        HIPCHK(copy_sync(ctx, bad, a.bad, sizeof bad, hipMemcpyDeviceToHost));
-        if (bad[3] != ~0ull) {
-            int32_t rd = 0;
-            HIPCHK(copy_sync(ctx, &rd, src->read + bad[3], 4, hipMemcpyDeviceToHost));
-            ctx->err = "support entry " + std::to_string(bad[3]) + " (read " + std::to_string(rd) + ") has no row of its (read, locus)";
-            return MTR_ERR_BAD_ARG;
-        }
-        if (bad[4] != ~0ull) { ctx->err = "support entry " + std::to_string(bad[4]) + ": the allele column is not 0 .. 0 1 .. 1 within its locus"; return MTR_ERR_BAD_ARG; }
-    }
-    HIPCHK(hipMemsetAsync(a.aligned, 0, 2 * G * 4, ctx->stream));                                      // aligned | skipped
-    hipLaunchKernelGGL(mtr_k_cons_alleles, blocks((int64_t)G), blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.tab_len, (int64_t)G, a.tab_off);
-    if (S > 0) hipLaunchKernelGGL(mtr_k_cons_tasks, blocks(S), blk, 0, ctx->stream, a);
-    HIPCHK(hipGetLastError());
-    unsigned state[CO_STATE]; int64_t tab_positions = 0;
-    HIPCHK(hipMemcpyAsync(&tab_positions, a.tab_off + G, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(copy_sync(ctx, state, a.state, sizeof state, hipMemcpyDeviceToHost));
-    if (tab_positions < 0 || (int64_t)state[0] + state[1] > S || state[2] > 2 * BA_MAX_WINDOW || state[3] > 2 * BA_MAX_WINDOW) { ctx->err = "the consensus' task lists failed on the device"; return MTR_ERR_HIP; }
-    HIPCHK(ctx->d_co_tab.ensure(std::max<size_t>((size_t)tab_positions * BA_TAB, 1) * 4));
-    a.tab = ctx->d_co_tab;
-    if (tab_positions > 0) HIPCHK(hipMemsetAsync(a.tab, 0, (size_t)tab_positions * BA_TAB * 4, ctx->stream));
-    { mtr_status st = cons_align_bucket<1>(ctx, a, 0, state[0], state[2]); if (st != MTR_OK) return st; }
-    { mtr_status st = cons_align_bucket<2>(ctx, a, 1, state[1], state[3]); if (st != MTR_OK) return st; }
-    const dim3 per_allele((unsigned)std::min<int64_t>((int64_t)G, CO_MAX_GRID));
-    hipLaunchKernelGGL(mtr_k_cons_emit<0>, per_allele, blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.cons_len, (int64_t)G, a.cons_off);
-    HIPCHK(hipGetLastError());
-    int64_t T = 0;
-    HIPCHK(copy_sync(ctx, &T, a.cons_off + G, 8, hipMemcpyDeviceToHost));
-    if (T < 0) { ctx->err = "the consensus' emission lengths failed on the device"; return MTR_ERR_HIP; }
-    *out_bases = T;
-    if (!dst) return MTR_OK;
-    if (dst->cap_alleles < (int64_t)G) { ctx->err = "destination holds " + std::to_string(dst->cap_alleles) + " alleles, " + std::to_string(G) + " needed"; return MTR_ERR_OVERFLOW; }
-    if (dst->cap_bases < T) { ctx->err = "destination holds " + std::to_string(dst->cap_bases) + " bases, " + std::to_string(T) + " needed"; return MTR_ERR_OVERFLOW; }
-    if (!dst->cons_off || !dst->backbone_read || !dst->backbone_len || !dst->members || !dst->aligned || !dst->skipped || (T > 0 && (!dst->bases || !dst->votes))) {
-        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
-    }
-    a.bases = dst->bases; a.votes = dst->votes;
-    if (T > 0) { hipLaunchKernelGGL(mtr_k_cons_emit<1>, per_allele, blk, 0, ctx->stream, a); HIPCHK(hipGetLastError()); }
-    HIPCHK(hipMemcpyAsync(dst->cons_off, a.cons_off, (G + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    const struct { int32_t *to; const int32_t *from; } cols[5] = { { dst->backbone_read, a.bb_read }, { dst->backbone_len, a.bb_len }, { dst->members, a.members }, { dst->aligned, a.aligned },
-                                                                   { dst->skipped, a.skipped } };
-    for (const auto &c : cols) HIPCHK(hipMemcpyAsync(c.to, c.from, G * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
-
-// ---- the motif structure of windows (window_structure.hip.inc) ---------------------------------------------------------------------------
-template <int UB, bool WIDE>
-static void ws_launch_bin(mtr_ctx *ctx, const WsArgs &a, unsigned first, unsigned n_tasks)
-{
-    if (n_tasks > 0) hipLaunchKernelGGL((mtr_k_ws_lanes<UB, WIDE>), dim3((n_tasks + 63) / 64), dim3(64), 0, ctx->stream, a, first, n_tasks);
-}
-
-extern "C" mtr_status mtr_window_structure_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, const int32_t *struct_off, int32_t n_structs,
-                                                  const int64_t *win_off, const uint8_t *win_bases, const int32_t *win_struct, int64_t n_windows, int64_t n_bases,
-                                                  int32_t gain, int32_t mismatch, int32_t indel, void *wait_stream, const mtr_window_structure_dst *dst)
-{
-    if (!ctx) return MTR_ERR_BAD_ARG;
-    if (ctx->pending) { const mtr_status w = mtr_wait(ctx); if (w == MTR_ERR_HIP) return w; }        // a run in flight ends first; its verdict is its own
-    const int64_t N = n_windows;
-    const bool columns_null = !win_off || (N > 0 && !win_struct) || (n_bases > 0 && !win_bases) || !dst || (N > 0 && (!dst->seg || !dst->score || !dst->ratio || !dst->skipped));
-    if (!wsa_check(motifs, motif_off, struct_off, n_structs, columns_null, N, n_bases, gain, mismatch, indel, ctx->err)) return MTR_ERR_BAD_ARG;
-    HIPCHK(hipSetDevice(ctx->device));
-    {
-        const struct { const void *p; int64_t bytes; const char *what; } cols[3] = { { win_off, (N + 1) * 8, "win_off" }, { win_bases, n_bases, "win_bases" }, { win_struct, N * 4, "win_struct" } };
-        for (const auto &c : cols)
-            if (c.bytes > 0) { mtr_status st = check_device_ptr(ctx, (const uint8_t *)c.p, c.bytes, c.what, "the column's bytes"); if (st != MTR_OK) return st; }
-    }
-    std::vector<WsStruct> structs((size_t)n_structs);
-    for (int32_t k = 0; k < n_structs; k++) structs[(size_t)k] = wsa_struct(motifs, motif_off, struct_off, k);
-    const size_t nw = std::max<size_t>((size_t)N, 1);
-    const size_t state_bytes = WS_BAD * 8 + 2 * WS_KEYS * 4;
-    HIPCHK(ctx->d_ws_structs.ensure(structs.size() * sizeof(WsStruct))); HIPCHK(ctx->d_ws_i32.ensure(2 * nw * 4)); HIPCHK(ctx->d_ws_raw.ensure(nw * sizeof(WsRaw)));
-    HIPCHK(ctx->d_ws_state.ensure(state_bytes));
-    if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(ctx->ev_text, (hipStream_t)wait_stream));
-    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
-    HIPCHK(hipMemsetAsync(ctx->d_ws_state, 0xff, WS_BAD * 8, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_ws_state + WS_BAD, 0, 2 * WS_KEYS * 4, ctx->stream));
-    HIPCHK(copy_sync(ctx, ctx->d_ws_structs, structs.data(), structs.size() * sizeof(WsStruct), hipMemcpyHostToDevice));
-    WsArgs a{};
-    a.win_off = win_off; a.win_bases = win_bases; a.win_struct = win_struct; a.N = N; a.n_bases = n_bases; a.n_structs = n_structs; a.structs = ctx->d_ws_structs;
-    a.bad = ctx->d_ws_state; a.count = (unsigned *)(a.bad + WS_BAD); a.cursor = a.count + WS_KEYS;
-    a.key = ctx->d_ws_i32; a.tasks = a.key + nw; a.raw = ctx->d_ws_raw; a.G = gain; a.MM = mismatch; a.D = indel;
-    const dim3 per_window((unsigned)((nw + WS_BLOCK - 1) / WS_BLOCK)), blk(WS_BLOCK);
-    hipLaunchKernelGGL(mtr_k_ws_check, per_window, blk, 0, ctx->stream, a);
-    if (n_bases > 0) {
-        const int64_t words = (((int64_t)((uintptr_t)win_bases & 7) + n_bases - 1) >> 3) + 1;
-        hipLaunchKernelGGL(mtr_k_ws_bases, dim3((unsigned)std::min<int64_t>((words + WS_BLOCK - 1) / WS_BLOCK, 1 << 16)), blk, 0, ctx->stream, win_bases, n_bases, words, a.bad);
-    }
-    HIPCHK(hipGetLastError());
-    struct { unsigned long long bad[WS_BAD]; unsigned count[WS_KEYS]; } st;
-    static_assert(sizeof st == WS_BAD * 8 + WS_KEYS * 4, "the state's layout");
-    HIPCHK(copy_sync(ctx, &st, a.bad, sizeof st, hipMemcpyDeviceToHost));
-    if (st.bad[0] != ~0ull) { ctx->err = "win_off at window " + std::to_string(st.bad[0]) + " does not ascend from 0 to n_bases"; return MTR_ERR_BAD_ARG; }
-    if (st.bad[1] != ~0ull) {
-        int32_t k = 0;
-        HIPCHK(copy_sync(ctx, &k, win_struct + st.bad[1], 4, hipMemcpyDeviceToHost));
-        ctx->err = "window " + std::to_string(st.bad[1]) + ": win_struct " + std::to_string(k) + " outside 0.." + std::to_string(n_structs - 1); return MTR_ERR_BAD_ARG;
-    }
-    if (st.bad[2] != ~0ull) {
-        uint8_t c = 0;
-        HIPCHK(copy_sync(ctx, &c, win_bases + st.bad[2], 1, hipMemcpyDeviceToHost));
-        ctx->err = "win_bases at " + std::to_string(st.bad[2]) + ": code " + std::to_string((int)c) + " is above 3"; return MTR_ERR_BAD_ARG;
-    }
-    if (dst->cap_windows < N) { ctx->err = "destination holds " + std::to_string(dst->cap_windows) + " windows, " + std::to_string(N) + " needed"; return MTR_ERR_OVERFLOW; }
-    if (N == 0) return MTR_OK;
-    unsigned bin_first[WS_BINS + 1] = { 0 };
-    for (int b = 0; b < WS_BINS; b++) { unsigned n = 0; for (int k = 0; k < WS_CLASSES; k++) n += st.count[b * WS_CLASSES + k]; bin_first[b + 1] = bin_first[b] + n; }
-    if ((int64_t)bin_first[WS_BINS] > N) { ctx->err = "the window structure's task counts failed on the device"; return MTR_ERR_HIP; }
-    hipLaunchKernelGGL(mtr_k_ws_tasks, per_window, blk, 0, ctx->stream, a);
-    ws_launch_bin<8, false>(ctx, a, bin_first[0], bin_first[1] - bin_first[0]);
-    ws_launch_bin<16, false>(ctx, a, bin_first[1], bin_first[2] - bin_first[1]);
-    ws_launch_bin<32, false>(ctx, a, bin_first[2], bin_first[3] - bin_first[2]);
-    ws_launch_bin<8, true>(ctx, a, bin_first[3], bin_first[4] - bin_first[3]);
-    ws_launch_bin<16, true>(ctx, a, bin_first[4], bin_first[5] - bin_first[4]);
-    a.seg = dst->seg; a.score = dst->score; a.ratio = dst->ratio; a.skipped = dst->skipped;
-    hipLaunchKernelGGL(mtr_k_ws_output, per_window, blk, 0, ctx->stream, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MTR_OK;
-}
+#include "allele_host.hip.inc"
 
 // ---- a FASTA file in device memory (fasta.hip.inc) -----------------------------------------------------------------------------
 // Only the header count, the sizes and - for an upload - the reads' lengths, offsets and IDs come back to the host.
@@ -2625,10 +1864,7 @@ static mtr_status fasta_input(mtr_ctx *ctx, const uint8_t *d_file, int64_t n_byt
     }
     { mtr_status st = check_device_ptr(ctx, d_file, n_bytes, what, "n_bytes"); if (st != MTR_OK) return st; }
     HIPCHK(ctx->d_fa_event.ensure(8)); HIPCHK(ctx->d_fa_info.ensure(sizeof(mtr_fasta_info)));
-    // the file comes from the caller's stream: the kernels wait for it there, not for the whole device
-    if (!ctx->ev_text) HIPCHK(hipEventCreateWithFlags(&ctx->ev_text, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(ctx->ev_text, (hipStream_t)wait_stream));
-    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_text, 0));
+    { mtr_status st = wait_for_stream(ctx, wait_stream); if (st != MTR_OK) return st; }      // the file comes from the caller's stream
     HIPCHK(hipMemsetAsync(ctx->d_fa_event, 0xff, 8, ctx->stream));
     return MTR_OK;
 }

@@ -6,10 +6,13 @@
 //   the lane slots   against a brute-force construction, bucket by bucket.
 //   the five-launch plan   against the two formulas the hosts had before they shared it, restated here one statement after the other: the
 //                    search's (L_lane, L_first, l_umax) and loci_round's (lane_len, u_wave or u_all, tasks / 64 + slots * MLO_N_CLASSES).
+//   a round of the locus search   every buffer's bytes and every slice's place against the locus search's and the genotype's former statements, the
+//                    slices written through in heap buffers of exactly those bytes; the refusal where the bins outgrow an int32.
 #include "../mtr_amd/csrc/dp_task_plan.h"
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -188,6 +191,99 @@ static void check_both(const std::vector<int> &lens, const std::vector<int> &ule
     check_loci(ulen, lane_max, lane_rows, std::max<int64_t>(1, (int64_t)lens.size() / 3), std::max(1, L / 5));   // a later round: fewer, shorter windows
 }
 
+// ---- one round of the locus search ----
+// a buffer of exactly `bytes` on the heap (the address sanitizer watches its ends), every byte 0xff; a slice is written through element by element,
+// each found untouched (disjoint: nobody was here before) and read back at the end
+struct Heap {
+    uint8_t *p; size_t bytes, written = 0;
+    explicit Heap(size_t n) : p((uint8_t *)malloc(n)), bytes(n) { if (!p) { fprintf(stderr, "out of memory\n"); exit(1); } memset(p, 0xff, n); }
+    ~Heap() { free(p); }
+    Heap(const Heap &) = delete;
+    template <typename T> void slice(const std::string &what, size_t at, size_t n, int tag)
+    {
+        T *s = (T *)p + at;
+        hold(what + " is aligned to its elements", (uintptr_t)s % sizeof(T) == 0);
+        for (size_t i = 0; i < n; i++) { hold(what + " is written once", s[i] == (T)-1); s[i] = (T)(tag * 1000003 + (int)i); }
+        for (size_t i = 0; i < n; i++) same(what + " reads back", s[i], (T)(tag * 1000003 + (int)i));
+        written += n * sizeof(T);
+    }
+};
+// the two hosts before they shared the layout, one statement after the other: mtr_search_motif_loci_device over its d_ml_* buffers, then
+// genotype_align_tables over its d_gt_* (MS_RES = 9 ints a task, LOCI_STATE = 5 words, five counters)
+static void check_round(size_t sS, size_t nq, size_t nt)
+{
+    LociRoundLayout l; std::string err;
+    hold("the layout is given", loci_round_layout(sS, nq, nt, l, err) && err.empty());
+    const size_t nb = nq * 177;
+    same("bins", l.nb, nb); same("MLO_N_CLASSES", MLO_N_CLASSES, 177); same("ints a result", LOCI_RES_INTS, 9); same("state words", LOCI_STATE_INTS, 5);
+    // the locus search
+    const size_t ml_i32 = (2 * sS + 1 + nq + 1) * 4;
+    const size_t ml_i64 = sS * 8;
+    const size_t ml_bin32 = (2 * nb + 1) * 4;
+    const size_t ml_bin64 = 2 * (nb + 1) * 8;
+    const size_t ml_state = 5 * 4;
+    const size_t ml_counter = 5 * 8;
+    const size_t ml_slot_q = sS + 1;                                      // d_slot_q = d_uoff + sS + 1
+    const size_t ml_q_slot = ml_slot_q + sS;                              // d_q_slot = d_slot_q + sS
+    const size_t ml_groups = nb;                                          // a.groups = a.hist + nb
+    const size_t ml_gfirst = nb + 1;                                      // a.gfirst = a.tfirst + nb + 1
+    const size_t ml_task32 = 4 * nt * 4;
+    const size_t ml_res = nt * 9 * 4;
+    const size_t ml_trank = nt;                                           // a.trank = a.tbin + nt
+    const size_t ml_sorted = ml_trank + nt;                               // a.sorted = a.trank + nt
+    const size_t ml_wlist = ml_sorted + nt;                               // a.wlist = a.sorted + nt
+    // the genotype
+    const size_t gt_i32 = (3 * sS + 2) * 4;                               // the bound: q_slot's address is kept from before nq is known
+    const size_t gt_i64 = sS * 8;
+    const size_t gt_slot_q = sS + 1;
+    const size_t gt_q_slot = gt_slot_q + sS;
+    const size_t gt_bin32 = (2 * nb + 1) * 4;
+    const size_t gt_bin64 = 2 * (nb + 1) * 8;
+    const size_t gt_counter = 5 * 8;
+    const size_t gt_task32 = 4 * nt * 4;
+    const size_t gt_res = nt * 9 * 4;
+    const size_t gt_state = 5 * 4;
+    const size_t gt_groups = nb, gt_gfirst = nb + 1, gt_trank = nt, gt_sorted = gt_trank + nt, gt_wlist = gt_sorted + nt;
+    same("i32: the genotype's bound", l.i32_bytes, gt_i32);
+    hold("i32: the locus search's, grown by at most S - nq ints", l.i32_bytes >= ml_i32 && l.i32_bytes - ml_i32 <= (sS - nq) * 4);
+    same("i64 (locus search)", l.i64_bytes, ml_i64); same("i64 (genotype)", l.i64_bytes, gt_i64);
+    same("bin32 (locus search)", l.bin32_bytes, ml_bin32); same("bin32 (genotype)", l.bin32_bytes, gt_bin32);
+    same("bin64 (locus search)", l.bin64_bytes, ml_bin64); same("bin64 (genotype)", l.bin64_bytes, gt_bin64);
+    same("task32 (locus search)", l.task32_bytes, ml_task32); same("task32 (genotype)", l.task32_bytes, gt_task32);
+    same("res (locus search)", l.res_bytes, ml_res); same("res (genotype)", l.res_bytes, gt_res);
+    same("state (locus search)", l.state_bytes, ml_state); same("state (genotype)", l.state_bytes, gt_state);
+    same("counter (locus search)", l.counter_bytes, ml_counter); same("counter (genotype)", l.counter_bytes, gt_counter);
+    same("slot_q (locus search)", l.slot_q, ml_slot_q); same("slot_q (genotype)", l.slot_q, gt_slot_q);
+    same("q_slot (locus search)", l.q_slot, ml_q_slot); same("q_slot (genotype)", l.q_slot, gt_q_slot);
+    same("groups (locus search)", l.groups, ml_groups); same("groups (genotype)", l.groups, gt_groups);
+    same("gfirst (locus search)", l.gfirst, ml_gfirst); same("gfirst (genotype)", l.gfirst, gt_gfirst);
+    same("trank (locus search)", l.trank, ml_trank); same("trank (genotype)", l.trank, gt_trank);
+    same("sorted (locus search)", l.sorted, ml_sorted); same("sorted (genotype)", l.sorted, gt_sorted);
+    same("wlist (locus search)", l.wlist, ml_wlist); same("wlist (genotype)", l.wlist, gt_wlist);
+    const LociRoundLayout s0 = loci_slot_layout(sS);                      // what the genotype takes before it knows nq
+    same("the slots alone: i32", s0.i32_bytes, l.i32_bytes); same("the slots alone: i64", s0.i64_bytes, l.i64_bytes);
+    same("the slots alone: slot_q", s0.slot_q, l.slot_q); same("the slots alone: q_slot", s0.q_slot, l.q_slot);
+    // every slice written through, in buffers of exactly the layout's bytes
+    Heap i32(l.i32_bytes), i64(l.i64_bytes), bin32(l.bin32_bytes), bin64(l.bin64_bytes), task32(l.task32_bytes), res(l.res_bytes), state(l.state_bytes), counter(l.counter_bytes);
+    i32.slice<int32_t>("unit_off", 0, sS + 1, 1); i32.slice<int32_t>("slot_q", l.slot_q, sS, 2); i32.slice<int32_t>("q_slot", l.q_slot, nq, 3);
+    i64.slice<uint64_t>("bits", 0, sS, 4);
+    bin32.slice<int32_t>("hist", 0, nb, 5); bin32.slice<int32_t>("groups", l.groups, nb, 6);
+    bin64.slice<int64_t>("tfirst", 0, nb + 1, 7); bin64.slice<int64_t>("gfirst", l.gfirst, nb + 1, 8);
+    task32.slice<int32_t>("tbin", 0, nt, 9); task32.slice<int32_t>("trank", l.trank, nt, 10); task32.slice<int32_t>("sorted", l.sorted, nt, 11); task32.slice<int32_t>("wlist", l.wlist, nt, 12);
+    res.slice<int32_t>("res", 0, nt * 9, 13); state.slice<int32_t>("state", 0, 5, 14); counter.slice<unsigned long long>("counter", 0, 5, 15);
+    same("i32: room for q_slot up to S is all that is left", i32.bytes - i32.written, (sS - nq + 1) * 4);
+    same("bin32: one int over", bin32.bytes - bin32.written, 4);
+    for (const Heap *h : { &i64, &bin64, &task32, &res, &state, &counter }) same("the slices fill the buffer", h->written, h->bytes);
+}
+static void check_round_refusal()
+{
+    LociRoundLayout l; std::string err;
+    const size_t fits = (size_t)INT32_MAX / 177, over = fits + 1;          // 12 132 675 lane slots are the most whose bins an int32 counts
+    hold("the most lane slots that fit", loci_round_layout(fits, fits, 1, l, err) && err.empty() && l.nb == fits * 177);
+    hold("one more is refused", !loci_round_layout(over, over, 1, l, err));
+    hold("in the hosts' words", err == std::to_string(over) + " short motifs are more than the bins take");
+}
+
 static int g_named = 0;
 static void named(const std::string &name) { g_case = name; g_named++; }
 
@@ -215,6 +311,12 @@ int main(int argc, char **argv)
     named("lane rows split the reads"); check_both(reads70, { 3, 7, 12, 20, 40 }, 32, 100);
     named("one read, one motif"); check_both({ 1 }, { 1 }, 32, 16384);
     for (size_t cells : { (size_t)0, (size_t)1, (size_t)255, (size_t)256, (size_t)257, (size_t)200000000 }) { named("matrix of " + std::to_string(cells) + " cells"); check_matrix(cells); }
+    for (size_t S : { (size_t)1, (size_t)2, (size_t)3, (size_t)64, (size_t)65 })
+        for (size_t nq : S == 1 ? std::vector<size_t>{ 0, 1 } : std::vector<size_t>{ 0, 1, S })             // nq = 0, 1 and S
+            for (size_t nt : { (size_t)1, (size_t)63, (size_t)64, (size_t)65 }) {
+                named("a round of S = " + std::to_string(S) + ", nq = " + std::to_string(nq) + ", nt = " + std::to_string(nt)); check_round(S, nq, nt);
+            }
+    named("more short motifs than the bins take"); check_round_refusal();
     const int n_named = g_named;
     for (int r = 0; r < n_random; r++) {
         g_case = "random shape " + std::to_string(r);

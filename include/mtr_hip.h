@@ -901,6 +901,54 @@ mtr_status mtr_window_structure_device(mtr_ctx *ctx, const char *motifs, const i
                                        const int64_t *win_off, const uint8_t *win_bases, const int32_t *win_struct, int64_t n_windows, int64_t n_bases,
                                        int32_t gain, int32_t mismatch, int32_t indel, void *wait_stream, const mtr_window_structure_dst *dst);
 
+/* ---- window edits: each interruption by segment, copy and column ----------------------------------------------------------------------------------
+ * The window structure counts; it does not say WHICH copy of a segment deviates, at which motif base, or how - the CAA inside a CAG tract, the
+ * AGG inside CGG.  The window edits list it.  Structure, window, scores, cells, fixpoint, predecessor order and end are the window structure's,
+ * unchanged, and so are the limits: S <= 2 and W <= 32, or S <= 4 and W <= 16; n <= MTR_WS_MAX_WINDOW.  The predecessor order makes the
+ * alignment path a function of the window alone, so the list is too.  The definition:
+ *   path        the chain of predecessors from the end back to START, read FORWARD.  Every step lands on a cell (i, c), s = seg(c): a sub step
+ *               from (i-1, p), an up step from (i-1, c), a left step from (i, p)
+ *   copy index  k = (the number of steps up to and including this one that landed on first(s) by sub or left) - 1.  Only whole copies exist,
+ *               so every copy begins with such a landing and k runs over 0 .. copies[s] - 1 in window order.  An up step belongs to the copy
+ *               its column was last landed in (it lands on first(s) by neither sub nor left, so the count does not move)
+ *   edits       in path order: kind 0, substitution: a sub step with y[i-1] != m[c]; pos = i - 1, base = y[i-1].  kind 1, insertion: an up
+ *               step - a window base with no motif base, after motif base c of copy k; pos = i - 1, base = y[i-1].  kind 2, deletion: a left
+ *               step - a motif base with no window base; pos = i, base = m[c].  Matching subs are no edits, nor are the rows spent in START
+ *               before the first used segment
+ *   row         per edit int32 [6] (MTR_WE_FIELDS): pos, segment, copy, column (c - first(s)), kind, base
+ *   per window  seg, score and skipped as mtr_window_structure_device returns them for the same input, bit for bit.  An empty or a skipped
+ *               window has no edits
+ *   invariants  per window and segment s, since every copy lands on each of its U_s columns once by sub or left, and every row of a segment's
+ *               span is consumed by one sub or one up:
+ *                 copies * U_s == matches + #kind 0 + #kind 2          end - start == matches + #kind 0 + #kind 1
+ * Columns: off [N + 1] int64 (window w's edits are rows off[w] .. off[w + 1]), edits [T * 6] int32 with T = off[N], seg [N * 4 * 4], score [N],
+ * skipped [N].  None depends on where or in which order the device worked.
+ *
+ * mtr_window_edits_device computes into buffers of the context's own and keeps them (compute, then copy, as mtr_genotype_catalog_device and
+ * mtr_genotype_catalog_copy_device); nothing of a batch, a run or another call is touched.  Its arguments are mtr_window_structure_device's
+ * without dst, checked in the same order with the same words (out_edits counts among the columns that must not be NULL); *out_edits = T.  The
+ * decisions of every cell are kept only while a ROUND of windows is worked on: at most MTR_WE_SCRATCH_BYTES of them at a time (or one
+ * wavefront's 64 windows, if those alone need more) - up to 12 bytes a row and window.  The buffer that holds them is the context's, grown to the
+ * largest round it has had and kept, like its other buffers, until mtr_destroy: transient is what it holds, not the allocation.  mtr_window_edits_copy_device copies what the last
+ * successful call kept, device to device, into caller-owned DEVICE memory: MTR_ERR_BAD_ARG without such a call or with a NULL dst or column that
+ * would be written; cap_windows < N or cap_edits < T: MTR_ERR_OVERFLOW, and nothing is written.  The context's stream is synchronised before
+ * either returns.  MTR_ABI_VERSION is unchanged by these entries: look for them by symbol. */
+#define MTR_WE_FIELDS 6
+#define MTR_WE_SCRATCH_BYTES ((int64_t)1 << 29)
+typedef struct mtr_window_edits_dst {
+    int64_t *off;           /* [n_windows + 1] */
+    int32_t *edits;         /* [n_edits * 6]: pos, segment, copy, column, kind, base */
+    int32_t *seg;           /* [n_windows * 4 * 4] */
+    int32_t *score;         /* [n_windows] */
+    uint8_t *skipped;       /* [n_windows] */
+    int64_t  cap_windows;
+    int64_t  cap_edits;
+} mtr_window_edits_dst;   /* caller-owned DEVICE memory */
+mtr_status mtr_window_edits_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, const int32_t *struct_off, int32_t n_structs,
+                                   const int64_t *win_off, const uint8_t *win_bases, const int32_t *win_struct, int64_t n_windows, int64_t n_bases,
+                                   int32_t gain, int32_t mismatch, int32_t indel, void *wait_stream, int64_t *out_edits);
+mtr_status mtr_window_edits_copy_device(mtr_ctx *ctx, const mtr_window_edits_dst *dst);
+
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left
  * of handle_one_file.c:281-287's loop across GPUs is ONE exchange: the record tables travel to the process that chains and

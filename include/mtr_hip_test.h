@@ -166,6 +166,11 @@ mtr_status mtr_test_unit_motifs(mtr_ctx *ctx, int32_t n, const char *units, cons
  * mtr_get_kernel_times is the tail kernel (mtr_k_file_tail) of that upload: launches = 0 after a host upload or with no entry. */
 mtr_status mtr_test_file_tail(mtr_ctx *ctx, uint16_t **out_tail, int64_t **out_tail_off, uint8_t **out_after);
 
+/* The rounds the last successful mtr_window_edits_device call of the context took (0: no window had a DP).  MTR_TEST_WE_SCRATCH_BYTES=<bytes>,
+ * read per call, replaces MTR_WE_SCRATCH_BYTES as the cap on a round's stored decisions, so that small windows take several rounds; the edits do
+ * not depend on it.  MTR_ERR_BAD_ARG without such a call. */
+mtr_status mtr_test_window_edits_rounds(mtr_ctx *ctx, int32_t *rounds);
+
 /* Environment switches for tests, read once per launch next to MTR_TEST_STAGED_CAPS and MTR_TEST_STAGED_FLAGS (read_switches, mtr_abi.hip):
  *   MTR_TEST_WALK_SCREEN=0   the staged chain without its dead-range screen (mtr_k_walk_screen): every candidate range is an item of mtr_k_walks,
  *                            as before the screen existed.  Records and counters do not depend on it.  (A traced run, mtr_set_trace, never screens.)

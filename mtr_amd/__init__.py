@@ -58,7 +58,9 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_call_alleles_rows_device", "mtr_test_catalog_stats", "mtr_genotype_partial_catalog_device", "mtr_genotype_partial_catalog_copy_device",
            "mtr_test_partial_catalog_stats", "mtr_catalog_create", "mtr_catalog_destroy", "mtr_catalog_info_get", "mtr_genotype_catalog_prepared_device",
            "mtr_genotype_partial_catalog_prepared_device", "mtr_test_catalog_dump", "mtr_test_catalog_build_stats",
-           "mtr_extract_windows_device", "mtr_allele_consensus_device", "mtr_window_structure_device"]
+           "mtr_extract_windows_device", "mtr_allele_consensus_device", "mtr_window_structure_device",
+           "mtr_window_edits_device", "mtr_window_edits_copy_device", "mtr_test_window_edits_rounds"]
+WE_FIELDS = 6                                # MTR_WE_FIELDS: pos, segment, copy, column, kind, base of an edit of Engine.window_edits
 WS_MAX_SEGMENTS, WS_MAX_WINDOW = 4, 16384    # MTR_WS_*: the limits of Engine.window_structure
 CONS_MAX_WINDOW, CONS_MAX_BAND, CONS_INS_SLOTS, CONS_MAX_EXTRA = 16384, 256, 4, 64      # MTR_CONS_*: the limits of Engine.allele_consensus
 ALLELE_COPIES, ALLELE_BASES = 0, 1           # MTR_ALLELE_COPIES, MTR_ALLELE_BASES: the measure of Engine.call_alleles
@@ -495,6 +497,21 @@ class WindowStructure(NamedTuple):
     skipped: "object"  # uint8 [N]: 1 = the window is longer than WS_MAX_WINDOW and every other column of the row is 0
 
 
+class CWindowEditsDst(C.Structure):
+    """mtr_window_edits_dst: device pointers of the window edits' columns and their capacities"""
+    _fields_ = [("off", C.c_void_p), ("edits", C.c_void_p), ("seg", C.c_void_p), ("score", C.c_void_p), ("skipped", C.c_void_p), ("cap_windows", C.c_int64),
+                ("cap_edits", C.c_int64)]
+
+
+class WindowEdits(NamedTuple):
+    """What Engine.window_edits found, all on the engine's device.  include/mtr_hip.h ("window edits") defines every column."""
+    off: "object"      # int64 [N + 1]: window w's edits are rows off[w] .. off[w + 1] of edits
+    edits: "object"    # int32 [T, 6]: pos, segment, copy, column, kind (0 substitution, 1 insertion, 2 deletion), base - in path order
+    seg: "object"      # int32 [N, 4, 4]: Engine.window_structure's seg of the same input
+    score: "object"    # int32 [N]: its score
+    skipped: "object"  # uint8 [N]: its skipped; such a window has no edits
+
+
 class CFastaInfo(C.Structure):
     """mtr_fasta_info: what a FASTA file in device memory holds"""
     _fields_ = [("n_reads", C.c_int32), ("end", C.c_int32), ("bad_char", C.c_int32), ("reserved", C.c_int32),
@@ -671,6 +688,14 @@ def load_library(path: str = LIB_PATH):
         lib.mtr_window_structure_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, P(CWindowStructureDst)]
         lib.mtr_window_structure_device.restype = C.c_int
+    if hasattr(lib, "mtr_window_edits_device"):          # (likewise a build from before the window edits)
+        lib.mtr_window_edits_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p, P(C.c_int64)]
+        lib.mtr_window_edits_device.restype = C.c_int
+        lib.mtr_window_edits_copy_device.argtypes = [C.c_void_p, P(CWindowEditsDst)]
+        lib.mtr_window_edits_copy_device.restype = C.c_int
+        lib.mtr_test_window_edits_rounds.argtypes = [C.c_void_p, P(C.c_int32)]
+        lib.mtr_test_window_edits_rounds.restype = C.c_int
     lib.mtr_test_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
     lib.mtr_test_catalog_stats.restype = C.c_int
     lib.mtr_test_partial_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
@@ -1530,14 +1555,9 @@ class Engine:
         self._check(call(self.h, C.byref(src), int(band_extra), stream, C.byref(dst), C.byref(nb)), "mtr_allele_consensus_device")
         return cons
 
-    def window_structure(self, structures, off, bases, which, gain: int = 1, mismatch: int = 1, indel: int = 1) -> WindowStructure:
-        """The motif structure of windows (mtr_window_structure_device): window w = bases[off[w]:off[w + 1]] (codes 0..3) aligned globally to
-        structures[which[w]], an ordered list of motifs each repeated zero or more whole times; per segment its span, copies and matches.
-        structures: a sequence of structures, each a string (one motif) or a sequence of strings - at most 2 motifs of 32 bases in all, or 4 of
-        16.  off (int64 [N + 1]), bases (uint8 [T]) and which (int32 [N]) are tensors on this engine's device: genotype_windows' off and bases
-        with which = sg.locus, or allele_consensus' off and bases with which = arange(2 * n_loci) // 2.  A window above WS_MAX_WINDOW bases is
-        marked skipped.  Needs no upload and no run and changes nothing either left.  Returns a WindowStructure of fresh tensors on this
-        engine's device; stream handling as call_alleles'."""
+    def _window_args(self, structures, off, bases, which, gain, mismatch, indel):
+        """what window_structure and window_edits hand to the library for their common arguments, in the calls' order up to wait_stream: the
+        host arrays of the structures (kept alive by the caller through the returned tuple), the device columns, N, T, the scores, the stream"""
         import torch
 
         for name, v in (("gain", gain), ("mismatch", mismatch), ("indel", indel)):
@@ -1555,13 +1575,53 @@ class Engine:
         ptrs = [col(off, torch.int64, (N + 1,), "the windows' off"), col(bases, torch.uint8, (T,), "the windows' bases"), col(which, torch.int32, (N,), "the windows' structure")]
         dev = torch.device("cuda", self.device)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        keep = (data, motif_off, struct_off)
+        return keep, (data.ctypes.data, motif_off.ctypes.data, struct_off.ctypes.data, len(lists), *ptrs, N, T, int(gain), int(mismatch), int(indel), stream), N, dev
+
+    def window_structure(self, structures, off, bases, which, gain: int = 1, mismatch: int = 1, indel: int = 1) -> WindowStructure:
+        """The motif structure of windows (mtr_window_structure_device): window w = bases[off[w]:off[w + 1]] (codes 0..3) aligned globally to
+        structures[which[w]], an ordered list of motifs each repeated zero or more whole times; per segment its span, copies and matches.
+        structures: a sequence of structures, each a string (one motif) or a sequence of strings - at most 2 motifs of 32 bases in all, or 4 of
+        16.  off (int64 [N + 1]), bases (uint8 [T]) and which (int32 [N]) are tensors on this engine's device: genotype_windows' off and bases
+        with which = sg.locus, or allele_consensus' off and bases with which = arange(2 * n_loci) // 2.  A window above WS_MAX_WINDOW bases is
+        marked skipped.  Needs no upload and no run and changes nothing either left.  Returns a WindowStructure of fresh tensors on this
+        engine's device; stream handling as call_alleles'."""
+        import torch
+
+        keep, args, N, dev = self._window_args(structures, off, bases, which, gain, mismatch, indel)
         ws = WindowStructure(torch.empty((N, 4, 4), dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
                              torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.uint8, device=dev))
         torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
         dst = CWindowStructureDst(*[t.data_ptr() if t.numel() else None for t in ws], N)
-        self._check(self.lib.mtr_window_structure_device(self.h, data.ctypes.data, motif_off.ctypes.data, struct_off.ctypes.data, len(lists), *ptrs, N, T,
-                                                         int(gain), int(mismatch), int(indel), stream, C.byref(dst)), "mtr_window_structure_device")
+        self._check(self.lib.mtr_window_structure_device(self.h, *args, C.byref(dst)), "mtr_window_structure_device")
+        del keep
         return ws
+
+    def window_edits(self, structures, off, bases, which, gain: int = 1, mismatch: int = 1, indel: int = 1) -> WindowEdits:
+        """The edits of windows (mtr_window_edits_device, mtr_window_edits_copy_device): the alignment path of Engine.window_structure for the
+        same arguments, read out - every substitution, insertion and deletion with its window position, segment, copy of the segment's motif,
+        column of the motif and base, in path order, window w's at edits[off[w]:off[w + 1]].  seg, score and skipped are window_structure's.
+        The arguments and their limits are window_structure's.  Needs no upload and no run and changes nothing either left.  Returns a
+        WindowEdits of fresh tensors on this engine's device; stream handling as window_structure's."""
+        import torch
+
+        keep, args, N, dev = self._window_args(structures, off, bases, which, gain, mismatch, indel)
+        n_edits = C.c_int64(0)
+        self._check(self.lib.mtr_window_edits_device(self.h, *args, C.byref(n_edits)), "mtr_window_edits_device")
+        del keep
+        E = int(n_edits.value)
+        we = WindowEdits(torch.empty(N + 1, dtype=torch.int64, device=dev), torch.empty((E, WE_FIELDS), dtype=torch.int32, device=dev),
+                         torch.empty((N, 4, 4), dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.uint8, device=dev))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CWindowEditsDst(*[t.data_ptr() if t.numel() else None for t in we], N, E)
+        self._check(self.lib.mtr_window_edits_copy_device(self.h, C.byref(dst)), "mtr_window_edits_copy_device")
+        return we
+
+    def test_window_edits_rounds(self) -> int:
+        """mtr_test_window_edits_rounds: the rounds the last window_edits call took (MTR_TEST_WE_SCRATCH_BYTES caps a round's transient bytes)"""
+        rounds = C.c_int32(0)
+        self._check(self.lib.mtr_test_window_edits_rounds(self.h, C.byref(rounds)), "mtr_test_window_edits_rounds")
+        return int(rounds.value)
 
     def test_catalog_stats(self):
         """mtr_test_catalog_stats: what the last genotype_catalog call saw - (positions, passed by the filter, seed hits, candidates) and the
@@ -2343,6 +2403,40 @@ def format_window_structure(structures, ws: WindowStructure, names=None) -> byte
             start, end, copies, matches = (int(v) for v in seg[w, s])
             cols.append(f"{m.decode() if isinstance(m, bytes) else m}*{copies}[{start},{end}){matches}")
         out.append(head + "\t" + "\t".join(cols) + "\n")
+    return "".join(out).encode()
+
+
+def format_window_edits(structures, we: WindowEdits, names=None) -> bytes:
+    """The result of Engine.window_edits as text, one tab-separated line per window: its name (names[w], or its index), the number of its edits,
+    then one token per edit in path order; a skipped window's line is name, 0, "skipped".  structures: window w's structure at structures[w]
+    (the call's structures[which[w]]), or one structure for every window.  The token grammar:
+        token    = motif "#" copy ":" column change "@" pos
+        change   = motif_base ">" window_base      a substitution: the motif's base at that column, the window's base at pos
+                 | "+" window_base                 an insertion after that column: the window's base at pos has no motif base
+                 | "-" motif_base                  a deletion of that column before pos: the motif's base has no window base
+    motif is the segment's motif as given, copy and column count from 0, pos is the window position, bases are letters of ACGT: the CAA in
+    copy 10 of a CAG tract is CAG#10:2G>A@32."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    lists = [[st] if isinstance(st, (str, bytes)) else list(st) for st in structures]
+    off, edits, skipped = host(we.off).reshape(-1), host(we.edits).reshape(-1, WE_FIELDS), host(we.skipped).reshape(-1)
+    if len(lists) == 1:
+        lists = lists * len(skipped)
+    if not len(off) - 1 == len(skipped) == len(lists):
+        raise MtrError(f"{len(lists)} structures for {len(skipped)} windows")
+    out = []
+    for w in range(len(skipped)):
+        name = names[w] if names is not None else w
+        if skipped[w]:
+            out.append(f"{name}\t0\tskipped\n")
+            continue
+        tokens = []
+        for pos, s, copy, column, kind, base in (tuple(int(v) for v in row) for row in edits[off[w]:off[w + 1]]):
+            m = lists[w][s].decode() if isinstance(lists[w][s], bytes) else lists[w][s]
+            change = f"{m[column]}>{'ACGT'[base]}" if kind == 0 else f"+{'ACGT'[base]}" if kind == 1 else f"-{'ACGT'[base]}"
+            tokens.append(f"{m}#{copy}:{column}{change}@{pos}")
+        out.append("\t".join([str(name), str(len(tokens))] + tokens) + "\n")
     return "".join(out).encode()
 
 

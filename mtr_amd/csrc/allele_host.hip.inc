@@ -295,6 +295,35 @@ static void ws_launch_bin(mtr_ctx *ctx, const WsArgs &a, unsigned first, unsigne
     if (n_tasks > 0) hipLaunchKernelGGL((mtr_k_ws_lanes<UB, WIDE>), dim3((n_tasks + 63) / 64), dim3(64), 0, ctx->stream, a, first, n_tasks);
 }
 
+// The device's checks of the windows' columns, for the window structure and the window edits alike: the check and the base kernels on the call's
+// state (a.bad = WS_BAD words at ~0 | the keys' counts, zeroed), one look at it, the smallest offender of each kind refused in the one set of
+// words, and the keys' counts for the caller's bins.
+struct WsCounts { unsigned long long bad[WS_BAD]; unsigned count[WS_KEYS]; };
+static_assert(sizeof(WsCounts) == WS_BAD * 8 + WS_KEYS * 4, "the state's layout");
+static mtr_status ws_device_checks(mtr_ctx *ctx, const WsArgs &a, size_t nw, WsCounts &st)
+{
+    const dim3 per_window((unsigned)((nw + WS_BLOCK - 1) / WS_BLOCK)), blk(WS_BLOCK);
+    hipLaunchKernelGGL(mtr_k_ws_check, per_window, blk, 0, ctx->stream, a);
+    if (a.n_bases > 0) {
+        const int64_t words = (((int64_t)((uintptr_t)a.win_bases & 7) + a.n_bases - 1) >> 3) + 1;
+        hipLaunchKernelGGL(mtr_k_ws_bases, dim3((unsigned)std::min<int64_t>((words + WS_BLOCK - 1) / WS_BLOCK, 1 << 16)), blk, 0, ctx->stream, a.win_bases, a.n_bases, words, a.bad);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(ctx, &st, a.bad, sizeof st, hipMemcpyDeviceToHost));
+    if (st.bad[0] != ~0ull) { ctx->err = "win_off at window " + std::to_string(st.bad[0]) + " does not ascend from 0 to n_bases"; return MTR_ERR_BAD_ARG; }
+    if (st.bad[1] != ~0ull) {
+        int32_t k = 0;
+        HIPCHK(copy_sync(ctx, &k, a.win_struct + st.bad[1], 4, hipMemcpyDeviceToHost));
+        ctx->err = "window " + std::to_string(st.bad[1]) + ": win_struct " + std::to_string(k) + " outside 0.." + std::to_string(a.n_structs - 1); return MTR_ERR_BAD_ARG;
+    }
+    if (st.bad[2] != ~0ull) {
+        uint8_t c = 0;
+        HIPCHK(copy_sync(ctx, &c, a.win_bases + st.bad[2], 1, hipMemcpyDeviceToHost));
+        ctx->err = "win_bases at " + std::to_string(st.bad[2]) + ": code " + std::to_string((int)c) + " is above 3"; return MTR_ERR_BAD_ARG;
+    }
+    return MTR_OK;
+}
+
 extern "C" mtr_status mtr_window_structure_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, const int32_t *struct_off, int32_t n_structs,
                                                   const int64_t *win_off, const uint8_t *win_bases, const int32_t *win_struct, int64_t n_windows, int64_t n_bases,
                                                   int32_t gain, int32_t mismatch, int32_t indel, void *wait_stream, const mtr_window_structure_dst *dst)
@@ -318,26 +347,8 @@ extern "C" mtr_status mtr_window_structure_device(mtr_ctx *ctx, const char *moti
     a.bad = ctx->d_ws_state; a.count = (unsigned *)(a.bad + WS_BAD); a.cursor = a.count + WS_KEYS;
     a.key = ctx->d_ws_i32; a.tasks = a.key + nw; a.raw = ctx->d_ws_raw; a.G = gain; a.MM = mismatch; a.D = indel;
     const dim3 per_window((unsigned)((nw + WS_BLOCK - 1) / WS_BLOCK)), blk(WS_BLOCK);
-    hipLaunchKernelGGL(mtr_k_ws_check, per_window, blk, 0, ctx->stream, a);
-    if (n_bases > 0) {
-        const int64_t words = (((int64_t)((uintptr_t)win_bases & 7) + n_bases - 1) >> 3) + 1;
-        hipLaunchKernelGGL(mtr_k_ws_bases, dim3((unsigned)std::min<int64_t>((words + WS_BLOCK - 1) / WS_BLOCK, 1 << 16)), blk, 0, ctx->stream, win_bases, n_bases, words, a.bad);
-    }
-    HIPCHK(hipGetLastError());
-    struct { unsigned long long bad[WS_BAD]; unsigned count[WS_KEYS]; } st;
-    static_assert(sizeof st == WS_BAD * 8 + WS_KEYS * 4, "the state's layout");
-    HIPCHK(copy_sync(ctx, &st, a.bad, sizeof st, hipMemcpyDeviceToHost));
-    if (st.bad[0] != ~0ull) { ctx->err = "win_off at window " + std::to_string(st.bad[0]) + " does not ascend from 0 to n_bases"; return MTR_ERR_BAD_ARG; }
-    if (st.bad[1] != ~0ull) {
-        int32_t k = 0;
-        HIPCHK(copy_sync(ctx, &k, win_struct + st.bad[1], 4, hipMemcpyDeviceToHost));
-        ctx->err = "window " + std::to_string(st.bad[1]) + ": win_struct " + std::to_string(k) + " outside 0.." + std::to_string(n_structs - 1); return MTR_ERR_BAD_ARG;
-    }
-    if (st.bad[2] != ~0ull) {
-        uint8_t c = 0;
-        HIPCHK(copy_sync(ctx, &c, win_bases + st.bad[2], 1, hipMemcpyDeviceToHost));
-        ctx->err = "win_bases at " + std::to_string(st.bad[2]) + ": code " + std::to_string((int)c) + " is above 3"; return MTR_ERR_BAD_ARG;
-    }
+    WsCounts st;
+    { mtr_status rc = ws_device_checks(ctx, a, nw, st); if (rc != MTR_OK) return rc; }
     if (dst->cap_windows < N) { ctx->err = "destination holds " + std::to_string(dst->cap_windows) + " windows, " + std::to_string(N) + " needed"; return MTR_ERR_OVERFLOW; }
     if (N == 0) return MTR_OK;
     unsigned bin_first[WS_BINS + 1] = { 0 };
@@ -352,6 +363,158 @@ extern "C" mtr_status mtr_window_structure_device(mtr_ctx *ctx, const char *moti
     a.seg = dst->seg; a.score = dst->score; a.ratio = dst->ratio; a.skipped = dst->skipped;
     hipLaunchKernelGGL(mtr_k_ws_output, per_window, blk, 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- the edits of windows (window_edits.hip.inc) -----------------------------------------------------------------------------------------
+// The window structure's checks and task list on buffers of this call's own, then the groups' rows, one look at them, and the rounds: the groups
+// in task order whatever their bins, their slots side by side, as many as the transient cap holds (one at the least): the usual call is ONE round.
+// Count: per round the rows, then the walk that counts.  The offset
+// scan, one look at the total.  Emit: per round the walk that writes - after the rows once more when there was more than one round, since a
+// round's decisions are gone when the next has run.
+struct WeRound { int bin; unsigned g_first, groups; int round; };
+
+template <int UB, bool WIDE>
+static void we_launch_rows(mtr_ctx *ctx, const WeArgs &a, const WeRound &r)
+{
+    hipLaunchKernelGGL((mtr_k_we_rows<UB, WIDE>), dim3(r.groups), dim3(64), 0, ctx->stream, a, r.g_first);
+}
+static void we_rows_of(mtr_ctx *ctx, const WeArgs &a, const WeRound &r)
+{
+    switch (r.bin) {
+        case 0: we_launch_rows<8, false>(ctx, a, r); break;
+        case 1: we_launch_rows<16, false>(ctx, a, r); break;
+        case 2: we_launch_rows<32, false>(ctx, a, r); break;
+        case 3: we_launch_rows<8, true>(ctx, a, r); break;
+        default: we_launch_rows<16, true>(ctx, a, r); break;
+    }
+}
+
+extern "C" mtr_status mtr_window_edits_device(mtr_ctx *ctx, const char *motifs, const int64_t *motif_off, const int32_t *struct_off, int32_t n_structs,
+                                              const int64_t *win_off, const uint8_t *win_bases, const int32_t *win_struct, int64_t n_windows, int64_t n_bases,
+                                              int32_t gain, int32_t mismatch, int32_t indel, void *wait_stream, int64_t *out_edits)
+{
+    if (!ctx) return MTR_ERR_BAD_ARG;
+    ctx->we_ready = false;
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
+    const int64_t N = n_windows;
+    const bool columns_null = !win_off || (N > 0 && !win_struct) || (n_bases > 0 && !win_bases) || !out_edits;
+    if (!wsa_check(motifs, motif_off, struct_off, n_structs, columns_null, N, n_bases, gain, mismatch, indel, ctx->err)) return MTR_ERR_BAD_ARG;
+    *out_edits = 0;
+    HIPCHK(hipSetDevice(ctx->device));
+    const DeviceCol cols[3] = { { win_off, (N + 1) * 8, "win_off" }, { win_bases, n_bases, "win_bases" }, { win_struct, N * 4, "win_struct" } };
+    { mtr_status st = check_device_cols(ctx, cols, "the column's bytes"); if (st != MTR_OK) return st; }
+    std::vector<WsStruct> structs((size_t)n_structs);
+    for (int32_t k = 0; k < n_structs; k++) structs[(size_t)k] = wsa_struct(motifs, motif_off, struct_off, k);
+    const size_t nw = std::max<size_t>((size_t)N, 1), max_groups = nw / 64 + WS_BINS;
+    HIPCHK(ctx->d_we_structs.ensure(structs.size() * sizeof(WsStruct))); HIPCHK(ctx->d_we_i32.ensure((4 * nw + max_groups) * 4)); HIPCHK(ctx->d_we_raw.ensure(nw * sizeof(WsRaw)));
+    HIPCHK(ctx->d_we_cnt.ensure(nw * sizeof(WeCount))); HIPCHK(ctx->d_we_i64.ensure(max_groups * 8)); HIPCHK(ctx->d_we_off.ensure((nw + 1) * 8));
+    HIPCHK(ctx->d_we_seg.ensure(nw * 4 * WS_MAX_SEGMENTS * 4)); HIPCHK(ctx->d_we_score.ensure(nw * 4)); HIPCHK(ctx->d_we_skipped.ensure(nw));
+    { mtr_status st = columns_begin(ctx, wait_stream, ctx->d_we_state, WS_BAD, 2 * WS_KEYS * 4 + 8); if (st != MTR_OK) return st; }
+    HIPCHK(copy_sync(ctx, ctx->d_we_structs, structs.data(), structs.size() * sizeof(WsStruct), hipMemcpyHostToDevice));
+    WeArgs a{};
+    WsArgs &w = a.ws;
+    w.win_off = win_off; w.win_bases = win_bases; w.win_struct = win_struct; w.N = N; w.n_bases = n_bases; w.n_structs = n_structs; w.structs = ctx->d_we_structs;
+    w.bad = ctx->d_we_state; w.count = (unsigned *)(w.bad + WS_BAD); w.cursor = w.count + WS_KEYS; a.differs = (unsigned long long *)(w.cursor + WS_KEYS);       // the window structure's state | differs
+    HIPCHK(hipMemsetAsync(a.differs, 0xff, 8, ctx->stream));
+    w.key = ctx->d_we_i32; w.tasks = w.key + nw; a.end_id = w.tasks + nw; a.n_edits = a.end_id + nw; a.grows = a.n_edits + nw;
+    w.raw = ctx->d_we_raw; w.G = gain; w.MM = mismatch; w.D = indel;
+    a.cnt = ctx->d_we_cnt; a.gslot = ctx->d_we_i64; a.off = ctx->d_we_off; a.seg = ctx->d_we_seg; a.score = ctx->d_we_score; a.skipped = ctx->d_we_skipped;
+    const dim3 per_window((unsigned)((nw + WS_BLOCK - 1) / WS_BLOCK)), blk(WS_BLOCK);
+    WsCounts st;
+    { mtr_status rc = ws_device_checks(ctx, w, nw, st); if (rc != MTR_OK) return rc; }
+    ctx->we_rounds = 0;
+    if (N == 0) {
+        HIPCHK(hipMemsetAsync(ctx->d_we_off, 0, 8, ctx->stream)); HIPCHK(hipStreamSynchronize(ctx->stream));
+        ctx->we_ready = true; ctx->we_windows = 0; ctx->we_edits = 0;
+        return MTR_OK;
+    }
+    unsigned groups = 0;
+    for (int b = 0; b < WS_BINS; b++) {
+        unsigned n = 0; for (int k = 0; k < WS_CLASSES; k++) n += st.count[b * WS_CLASSES + k];
+        a.bin_first[b + 1] = a.bin_first[b] + n; a.grp_first[b] = groups; groups += (n + 63) / 64;
+    }
+    a.grp_first[WS_BINS] = groups;
+    if ((int64_t)a.bin_first[WS_BINS] > N || groups > max_groups) { ctx->err = "the window edits' task counts failed on the device"; return MTR_ERR_HIP; }
+    HIPCHK(hipMemsetAsync(a.n_edits, 0, nw * 4, ctx->stream));
+    hipLaunchKernelGGL(mtr_k_ws_tasks, per_window, blk, 0, ctx->stream, w);
+    std::vector<WeRound> parts;                                          // a round's groups of one bin; a round is the parts of one number
+    int n_rounds = 0;
+    size_t scratch_words = 1;
+    if (groups > 0) {
+        hipLaunchKernelGGL(mtr_k_we_groups, dim3(groups), dim3(64), 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        std::vector<int32_t> grows((size_t)groups);
+        HIPCHK(copy_sync(ctx, grows.data(), a.grows, (size_t)groups * 4, hipMemcpyDeviceToHost));
+        const char *e = getenv("MTR_TEST_WE_SCRATCH_BYTES");
+        const size_t cap_words = (size_t)std::max<long long>(e ? atoll(e) : (long long)MTR_WE_SCRATCH_BYTES, 4) / 4;
+        static const int bin_ub[WS_BINS] = { 8, 16, 32, 8, 16 };
+        std::vector<int64_t> gslot((size_t)groups);
+        size_t used = 0;
+        for (int b = 0; b < WS_BINS; b++)
+            for (unsigned g = a.grp_first[b]; g < a.grp_first[b + 1]; g++) {
+                if (grows[g] < 1 || grows[g] > WS_MAX_WINDOW + 1) { ctx->err = "the window edits' group rows failed on the device"; return MTR_ERR_HIP; }
+                const size_t words = (size_t)grows[g] * (size_t)we_row_words(bin_ub[b]) * 64;
+                if (g == 0 || used + words > cap_words) { n_rounds++; used = 0; }
+                if (parts.empty() || parts.back().round != n_rounds - 1 || parts.back().bin != b) parts.push_back(WeRound{ b, g, 0, n_rounds - 1 });
+                gslot[g] = (int64_t)used; used += words; parts.back().groups++;
+                scratch_words = std::max(scratch_words, used);
+            }
+        HIPCHK(ctx->d_we_scratch.ensure(scratch_words * 4));
+        HIPCHK(copy_sync(ctx, ctx->d_we_i64, gslot.data(), (size_t)groups * 8, hipMemcpyHostToDevice));
+    }
+    a.scratch = ctx->d_we_scratch;
+    // a round's groups are consecutive whatever their bins: the rows one launch per part, either walk one launch per round
+    const auto walk_round = [&](int round, bool rows, bool emit) {
+        unsigned g0 = 0, ng = 0;
+        for (const WeRound &r : parts) if (r.round == round) { if (ng == 0) g0 = r.g_first; ng += r.groups; if (rows) we_rows_of(ctx, a, r); }
+        if (emit) hipLaunchKernelGGL(mtr_k_we_emit, dim3(ng), dim3(64), 0, ctx->stream, a, g0);
+        else hipLaunchKernelGGL(mtr_k_we_count, dim3(ng), dim3(64), 0, ctx->stream, a, g0);
+    };
+    for (int k = 0; k < n_rounds; k++) walk_round(k, true, false);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.n_edits, N, ctx->d_we_off.p);
+    HIPCHK(hipGetLastError());
+    int64_t T = 0; unsigned long long differs = ~0ull;
+    HIPCHK(hipMemcpyAsync(&T, ctx->d_we_off + N, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(copy_sync(ctx, &differs, a.differs, 8, hipMemcpyDeviceToHost));
+    if (differs != ~0ull) {
+        WeCount k{}; WsRaw raw{}; int32_t end = 0;
+        HIPCHK(copy_sync(ctx, &k, a.cnt + differs, sizeof k, hipMemcpyDeviceToHost)); HIPCHK(copy_sync(ctx, &raw, w.raw + differs, sizeof raw, hipMemcpyDeviceToHost));
+        HIPCHK(copy_sync(ctx, &end, a.end_id + differs, 4, hipMemcpyDeviceToHost));
+        char buf[256];
+        snprintf(buf, sizeof buf, ": the stored decisions are not the path of its rows (end %d; entry, copies, matches walked %llx %llx %llx, carried %llx %llx %llx; %d edits, gave up %d)", end,
+                 (unsigned long long)k.entry, (unsigned long long)k.copies, (unsigned long long)k.matches, (unsigned long long)raw.entry, (unsigned long long)raw.copies, (unsigned long long)raw.matches, k.edits, k.bad);
+        ctx->err = "window " + std::to_string(differs) + buf; return MTR_ERR_HIP;
+    }
+    HIPCHK(ctx->d_we_edits.ensure((size_t)std::max<int64_t>(T, 1) * WE_FIELDS * 4));
+    a.edits = ctx->d_we_edits;
+    for (int k = 0; k < n_rounds; k++) walk_round(k, n_rounds > 1, true);
+    hipLaunchKernelGGL(mtr_k_we_output, per_window, blk, 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(ctx, &differs, a.differs, 8, hipMemcpyDeviceToHost));
+    if (differs != ~0ull) { ctx->err = "window " + std::to_string(differs) + ": the walk that writes is not the walk that counted"; return MTR_ERR_HIP; }
+    ctx->we_ready = true; ctx->we_windows = N; ctx->we_edits = T; ctx->we_rounds = n_rounds;
+    *out_edits = T;
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_window_edits_copy_device(mtr_ctx *ctx, const mtr_window_edits_dst *dst)
+{
+    if (!ctx) return MTR_ERR_BAD_ARG;
+    if (!ctx->we_ready) { ctx->err = "no edits kept: mtr_window_edits_device comes first"; return MTR_ERR_BAD_ARG; }
+    if (!dst) { ctx->err = "dst is NULL"; return MTR_ERR_BAD_ARG; }
+    const int64_t N = ctx->we_windows, T = ctx->we_edits;
+    if (dst->cap_windows < N) { ctx->err = "destination holds " + std::to_string(dst->cap_windows) + " windows, " + std::to_string(N) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (dst->cap_edits < T) { ctx->err = "destination holds " + std::to_string(dst->cap_edits) + " edits, " + std::to_string(T) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (!dst->off || (T > 0 && !dst->edits) || (N > 0 && (!dst->seg || !dst->score || !dst->skipped))) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const DeviceCol cols[5] = { { dst->off, (N + 1) * 8, "dst->off" }, { dst->edits, T * WE_FIELDS * 4, "dst->edits" }, { dst->seg, N * 4 * WS_MAX_SEGMENTS * 4, "dst->seg" },
+                                { dst->score, N * 4, "dst->score" }, { dst->skipped, N, "dst->skipped" } };
+    { mtr_status st = check_device_cols(ctx, cols, "the column's bytes"); if (st != MTR_OK) return st; }
+    const void *from[5] = { ctx->d_we_off.p, ctx->d_we_edits.p, ctx->d_we_seg.p, ctx->d_we_score.p, ctx->d_we_skipped.p };
+    for (int k = 0; k < 5; k++)
+        if (cols[k].bytes > 0) HIPCHK(hipMemcpyAsync(const_cast<void *>(cols[k].p), from[k], (size_t)cols[k].bytes, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
 }

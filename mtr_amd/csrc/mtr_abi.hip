@@ -54,6 +54,7 @@
 #include "consensus.hip.inc"
 #include "window_structure.hip.inc"
 #include "window_structure_args.h"
+#include "window_edits.hip.inc"
 #include "fasta.hip.inc"
 #include "fastq.hip.inc"
 #include "file_order.hip.inc"
@@ -282,6 +283,12 @@ struct mtr_ctx {
     // the window structure (window_structure.hip.inc), per call and nothing kept, buffers of its own: the structures as the lanes carry them, d_ws_i32 =
     // the windows' keys | the task list, the ends' carried fields, d_ws_state = the bad-input words | the keys' counts | their cursors
     DevBuf<WsStruct> d_ws_structs; DevBuf<int32_t> d_ws_i32; DevBuf<WsRaw> d_ws_raw; DevBuf<unsigned long long> d_ws_state;
+    // the window edits (window_edits.hip.inc): the same of its own, d_we_i32 = keys | tasks | the ends | the edit counts | the groups' rows, d_we_i64 = the
+    // groups' slots, the walk's counts, the stored decisions of a round (transient: at most the cap, or one group), and what the call KEEPS for
+    // mtr_window_edits_copy_device: off, edits, seg, score, skipped of we_windows windows and we_edits edits (we_ready)
+    DevBuf<WsStruct> d_we_structs; DevBuf<int32_t> d_we_i32, d_we_edits, d_we_seg, d_we_score; DevBuf<WsRaw> d_we_raw; DevBuf<unsigned long long> d_we_state;
+    DevBuf<int64_t> d_we_i64, d_we_off; DevBuf<WeCount> d_we_cnt; DevBuf<uint32_t> d_we_scratch; DevBuf<uint8_t> d_we_skipped;
+    bool we_ready = false; int64_t we_windows = 0, we_edits = 0; int32_t we_rounds = 0;
     long long wrap_dp_size = MTRC_WRAP_DP_SIZE;          // the WrapDPsize the kernels of this context's device test (MTR_TEST_WRAP_DP_SIZE)
     // a FASTA file in device memory (fasta.hip.inc), per call: the tiles' columns, the header windows' columns, the IDs' offsets, the stop, the sizes
     DevBuf<uint32_t> d_fa_tiles, d_fa_hbase; DevBuf<int32_t> d_fa_hpos, d_fa_hidlen; DevBuf<int64_t> d_fa_idoff;

@@ -519,3 +519,12 @@ extern "C" mtr_status mtr_test_revise(mtr_ctx *ctx, int32_t mode, int32_t n_grou
     }
     return check_status(ctx);
 }
+
+// ---- the rounds of the last window-edits call (mtr_window_edits_device, allele_host.hip.inc) ----
+extern "C" mtr_status mtr_test_window_edits_rounds(mtr_ctx *ctx, int32_t *rounds)
+{
+    if (!ctx || !rounds) return MTR_ERR_BAD_ARG;
+    if (!ctx->we_ready) { ctx->err = "no edits kept: mtr_window_edits_device comes first"; return MTR_ERR_BAD_ARG; }
+    *rounds = ctx->we_rounds;
+    return MTR_OK;
+}

@@ -949,6 +949,86 @@ mtr_status mtr_window_edits_device(mtr_ctx *ctx, const char *motifs, const int64
                                    int32_t gain, int32_t mismatch, int32_t indel, void *wait_stream, int64_t *out_edits);
 mtr_status mtr_window_edits_copy_device(mtr_ctx *ctx, const mtr_window_edits_dst *dst);
 
+/* ---- sequence allele calls: pairwise window distances, a two-medoid split ------------------------------------------------------------------------
+ * mtr_call_alleles_device splits a locus' reads by one integer, so two alleles of one length - (CAG)20 against (CAG)10(CAA)10, a pure CGG tract
+ * against one with AGG interruptions - are one allele to it, and the consensus votes them into a mixture.  This call splits by SEQUENCE: the
+ * edit distance between every two supporting reads' oriented windows, and an exact one- or two-medoid split over those distances.  The
+ * reference has nothing of this kind; the definition is this project's own.
+ * Input is mtr_consensus_src as mtr_allele_consensus_device takes it: the joined rows ascending by (read, locus), their windows, and
+ * support_off and read of a mtr_call_alleles_device result over the same rows - membership and min_ratio are decided there, the list order is
+ * ascending (value, read).  allele and zygosity of the src are not read and may be NULL.  value [n_support] (int32, DEVICE) holds the calls'
+ * values; it is carried along and never compared.  Parameters mtr_seq_params { max_dist K, min_support, min_percent, min_sep, min_gain }.
+ * The definition:
+ *   members     the members of locus l are its S_l entries in list order, t = 0 .. S_l - 1; each finds its row by bisection over (read, locus)
+ *               as in the consensus; W_t is its oriented window, n_t its length
+ *   distance    D(t, u) = min(lev(W_t, W_u), K + 1), lev the unit-cost edit distance: symmetric, D(t, t) = 0.  K in 0 .. MTR_SEQ_MAX_DIST = 254,
+ *               so a distance fits one byte.  By definition D = K + 1 when |n_t - n_u| > K, and when either window exceeds
+ *               MTR_CONS_MAX_WINDOW.  The definition does not depend on how it is computed: the kernels fill the band of diagonals
+ *               ba_band(n, m, (K - |m - n|) >> 1), at most K + 1 wide; a path of cost <= K cannot leave it, so the banded result clamped to
+ *               K + 1 is exactly D - unlike the consensus' band, which is part of its definition, this band is only the way there
+ *   skipped     a locus with S_l > MTR_SEQ_MAX_MEMBERS = 128: skipped[l] = 1, no pairs are computed, the entries keep list order and allele 0,
+ *               zygosity 0, call, call_support and cost zeros, medoid (-1, -1)
+ *   one medoid  cost(c) = sum over u of D(c, u); c* = the smallest c of least cost, cost1 = cost(c*)
+ *   two medoids for every pair c0 < c1: member u belongs to c0 iff D(c0, u) <= D(c1, u) (ties go to c0), else to c1; n0, n1 the two sizes;
+ *               cost2(c0, c1) = sum over u of min(D(c0, u), D(c1, u))
+ *   admissible  a pair is admissible iff min(n0, n1) >= min_support, min(n0, n1) * 100 >= min_percent * S_l (in int64), D(c0, c1) >= min_sep,
+ *               and cost2 * 100 <= cost1 * (100 - min_gain) (in int64)
+ *   S_l < min_support (S_l == 0 too)   zygosity 0, medoid (-1, -1), call, call_support and cost zeros; the entries keep list order, allele 0
+ *   no admissible pair                 zygosity 1, medoid (read of c*, -1), call (value[c*], value[c*]), call_support (S_l, 0), cost (cost1,
+ *                                      cost1); the entries keep list order, allele 0
+ *   an admissible pair exists          zygosity 2: the admissible pair of smallest cost2, ties to the smallest c0, then the smallest c1; medoid the
+ *                                      two reads, call their values, call_support (n0, n1), cost (cost1, cost2); the entries are the STABLE
+ *                                      PARTITION of the list - allele 0's members in list order, then allele 1's: the 0 .. 0 1 .. 1 column the
+ *                                      consensus requires
+ * Every output is an exact integer and none depends on the order in which the device worked.  Columns: support_off [n_loci + 1], a copy; value,
+ * read, allele, dist_to_medoid [S] each - the distance to the entry's own medoid, 0 under zygosity 0; zygosity [n_loci]; call, call_support,
+ * medoid [n_loci * 2] each; cost [n_loci * 2] int64; skipped [n_loci]; pair_off [n_loci + 1] int64 - locus l owns S_l (S_l - 1) / 2 pairs, none
+ * when skipped; dist [P] uint8, the upper triangle of D row-major: pair (t < u) at pair_off[l] + t * S_l - t (t + 1) / 2 + (u - t - 1).  The
+ * first eight are mtr_allele_calls_dst's columns: mtr_allele_consensus_device takes them as it takes mtr_call_alleles_device's.
+ *
+ * mtr_call_alleles_sequence_device computes into buffers of the context's own and keeps them (compute, then copy, as mtr_window_edits_device);
+ * it needs no uploaded batch and touches nothing that a batch, a run or another call keeps.  *out_support = S, *out_pairs = P.  Checked in this
+ * order, each MTR_ERR_BAD_ARG naming the offender: NULL ctx, out_support or out_pairs; NULL src or prm; n_loci < 1 or above 2^30 - 1, n_rows,
+ * n_support or n_bases outside 0..2^31 - 1; max_dist (0 .. MTR_SEQ_MAX_DIST), min_support (>= 1), min_percent (0..50), min_sep (>= 1), min_gain
+ * (0..100), in this order; a NULL input column that would be read (value among them); an input column that is not device memory of the
+ * context's GPU or runs past its allocation; then on the device the rows' order, the offset columns (ascending from 0 to n_bases /
+ * n_support, no window above 2^30 bases), an entry without a row.  More than 2^31 - 1 pairs are MTR_ERR_OVERFLOW.  wait_stream is the stream
+ * that wrote the columns, handled as mtr_upload_batch_device handles it.  mtr_call_alleles_sequence_copy_device copies what the last successful
+ * call kept, device to device, into caller-owned DEVICE memory: MTR_ERR_BAD_ARG without such a call or with a NULL dst or column that would be
+ * written (value, read, allele and dist_to_medoid may be NULL only when S == 0, dist only when P == 0); cap_loci < n_loci, cap_support < S or
+ * cap_pairs < P: MTR_ERR_OVERFLOW; a failure writes nothing.  The context's stream is synchronised before either returns.  MTR_ABI_VERSION is
+ * unchanged by these entries: look for them by symbol. */
+#define MTR_SEQ_MAX_DIST 254
+#define MTR_SEQ_MAX_MEMBERS 128
+typedef struct mtr_seq_params {
+    int32_t max_dist;      /* K: distances saturate at K + 1 */
+    int32_t min_support;   /* the fewest reads an allele needs */
+    int32_t min_percent;   /* the smaller allele's least share of the locus' supporting reads, in percent */
+    int32_t min_sep;       /* the least distance between the two medoids */
+    int32_t min_gain;      /* the least saving of cost2 against cost1, in percent */
+} mtr_seq_params;
+typedef struct mtr_seq_calls_dst {
+    int64_t *support_off;     /* [n_loci + 1] */
+    int32_t *value;           /* [S] */
+    int32_t *read;            /* [S] */
+    uint8_t *allele;          /* [S] */
+    uint8_t *zygosity;        /* [n_loci] */
+    int32_t *call;            /* [n_loci * 2] */
+    int32_t *call_support;    /* [n_loci * 2] */
+    int64_t *cost;            /* [n_loci * 2] cost1, cost2 */
+    int32_t *medoid;          /* [n_loci * 2] the medoids' reads, -1 without one */
+    int32_t *dist_to_medoid;  /* [S] */
+    uint8_t *skipped;         /* [n_loci] */
+    int64_t *pair_off;        /* [n_loci + 1] */
+    uint8_t *dist;            /* [P] */
+    int64_t  cap_loci;
+    int64_t  cap_support;
+    int64_t  cap_pairs;
+} mtr_seq_calls_dst;   /* caller-owned DEVICE memory */
+mtr_status mtr_call_alleles_sequence_device(mtr_ctx *ctx, const mtr_consensus_src *src, const int32_t *value, const mtr_seq_params *prm,
+                                            void *wait_stream, int64_t *out_support, int64_t *out_pairs);
+mtr_status mtr_call_alleles_sequence_copy_device(mtr_ctx *ctx, const mtr_seq_calls_dst *dst);
+
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left
  * of handle_one_file.c:281-287's loop across GPUs is ONE exchange: the record tables travel to the process that chains and

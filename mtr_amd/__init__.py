@@ -59,8 +59,10 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_test_partial_catalog_stats", "mtr_catalog_create", "mtr_catalog_destroy", "mtr_catalog_info_get", "mtr_genotype_catalog_prepared_device",
            "mtr_genotype_partial_catalog_prepared_device", "mtr_test_catalog_dump", "mtr_test_catalog_build_stats",
            "mtr_extract_windows_device", "mtr_allele_consensus_device", "mtr_window_structure_device",
-           "mtr_window_edits_device", "mtr_window_edits_copy_device", "mtr_test_window_edits_rounds"]
-WE_FIELDS = 6                                # MTR_WE_FIELDS: pos, segment, copy, column, kind, base of an edit of Engine.window_edits
+           "mtr_window_edits_device", "mtr_window_edits_copy_device", "mtr_test_window_edits_rounds",
+           "mtr_call_alleles_sequence_device", "mtr_call_alleles_sequence_copy_device"]
+SEQ_MAX_DIST, SEQ_MAX_MEMBERS = 254, 128     # MTR_SEQ_*: the limits of Engine.call_alleles_by_sequence
+WE_FIELDS = 6                               # MTR_WE_FIELDS: pos, segment, copy, column, kind, base of an edit of Engine.window_edits
 WS_MAX_SEGMENTS, WS_MAX_WINDOW = 4, 16384    # MTR_WS_*: the limits of Engine.window_structure
 CONS_MAX_WINDOW, CONS_MAX_BAND, CONS_INS_SLOTS, CONS_MAX_EXTRA = 16384, 256, 4, 64      # MTR_CONS_*: the limits of Engine.allele_consensus
 ALLELE_COPIES, ALLELE_BASES = 0, 1           # MTR_ALLELE_COPIES, MTR_ALLELE_BASES: the measure of Engine.call_alleles
@@ -512,6 +514,29 @@ class WindowEdits(NamedTuple):
     skipped: "object"  # uint8 [N]: its skipped; such a window has no edits
 
 
+class CSeqParams(C.Structure):
+    """mtr_seq_params: where the distances saturate and which medoid pairs are admissible"""
+    _fields_ = [("max_dist", C.c_int32), ("min_support", C.c_int32), ("min_percent", C.c_int32), ("min_sep", C.c_int32), ("min_gain", C.c_int32)]
+
+
+class CSeqCallsDst(C.Structure):
+    """mtr_seq_calls_dst: device pointers of the sequence calls' columns - mtr_allele_calls_dst's eight first - and their capacities"""
+    _fields_ = [("support_off", C.c_void_p), ("value", C.c_void_p), ("read", C.c_void_p), ("allele", C.c_void_p), ("zygosity", C.c_void_p),
+                ("call", C.c_void_p), ("call_support", C.c_void_p), ("cost", C.c_void_p), ("medoid", C.c_void_p), ("dist_to_medoid", C.c_void_p),
+                ("skipped", C.c_void_p), ("pair_off", C.c_void_p), ("dist", C.c_void_p), ("cap_loci", C.c_int64), ("cap_support", C.c_int64), ("cap_pairs", C.c_int64)]
+
+
+class SequenceCalls(NamedTuple):
+    """What Engine.call_alleles_by_sequence made of a locus' supporting reads' windows, all on the engine's device.  include/mtr_hip.h
+    ("sequence allele calls") defines every column."""
+    calls: AlleleCalls          # the split in call_alleles' shape: allele_consensus, format_allele_calls and partial_support take it unchanged
+    medoid: "object"            # int32 [m, 2]: the medoids' reads, -1 without one
+    dist_to_medoid: "object"    # int32 [S]: each entry's distance to its own allele's medoid
+    skipped: "object"           # uint8 [m]: 1 = more than SEQ_MAX_MEMBERS supporting reads, no pairs computed, zygosity 0
+    pair_off: "object"          # int64 [m + 1]: locus l owns S_l (S_l - 1) / 2 pairs, none when skipped
+    dist: "object"              # uint8 [P]: the upper triangle of D, row-major, pair (t < u) at pair_off[l] + t * S_l - t (t + 1) / 2 + (u - t - 1)
+
+
 class CFastaInfo(C.Structure):
     """mtr_fasta_info: what a FASTA file in device memory holds"""
     _fields_ = [("n_reads", C.c_int32), ("end", C.c_int32), ("bad_char", C.c_int32), ("reserved", C.c_int32),
@@ -696,6 +721,11 @@ def load_library(path: str = LIB_PATH):
         lib.mtr_window_edits_copy_device.restype = C.c_int
         lib.mtr_test_window_edits_rounds.argtypes = [C.c_void_p, P(C.c_int32)]
         lib.mtr_test_window_edits_rounds.restype = C.c_int
+    if hasattr(lib, "mtr_call_alleles_sequence_device"):          # (likewise a build from before the sequence calls)
+        lib.mtr_call_alleles_sequence_device.argtypes = [C.c_void_p, P(CConsensusSrc), C.c_void_p, P(CSeqParams), C.c_void_p, P(C.c_int64), P(C.c_int64)]
+        lib.mtr_call_alleles_sequence_device.restype = C.c_int
+        lib.mtr_call_alleles_sequence_copy_device.argtypes = [C.c_void_p, P(CSeqCallsDst)]
+        lib.mtr_call_alleles_sequence_copy_device.restype = C.c_int
     lib.mtr_test_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
     lib.mtr_test_catalog_stats.restype = C.c_int
     lib.mtr_test_partial_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
@@ -1555,6 +1585,50 @@ class Engine:
         self._check(call(self.h, C.byref(src), int(band_extra), stream, C.byref(dst), C.byref(nb)), "mtr_allele_consensus_device")
         return cons
 
+    def call_alleles_by_sequence(self, sg, windows: GenotypeWindows, calls: AlleleCalls, max_dist: int = 32, min_support: int = 2, min_percent: int = 20,
+                                 min_sep: int = 1, min_gain: int = 0) -> "SequenceCalls":
+        """Allele calls by sequence (mtr_call_alleles_sequence_device, mtr_call_alleles_sequence_copy_device).  sg, windows and calls are
+        allele_consensus' arguments; of calls only the support lists are read (support_off, value, read): which reads support a locus, in
+        which order.  Per locus the edit distance between every two supporting reads' oriented windows, saturated at max_dist + 1, and the
+        exact one- or two-medoid split over those distances: two alleles where a pair of medoids exists whose smaller side has min_support
+        reads and min_percent percent of them, whose medoids lie min_sep apart, and whose cost is at most (100 - min_gain) percent of one
+        medoid's - the pair of least cost.  A locus of more than SEQ_MAX_MEMBERS supporting reads is marked skipped.  Returns a
+        SequenceCalls of fresh tensors on this engine's device; .calls goes unchanged into allele_consensus, format_allele_calls and
+        partial_support.  Needs no upload and no run and changes nothing either left.  Stream handling as allele_consensus'."""
+        import torch
+
+        for name, v in (("max_dist", max_dist), ("min_support", min_support), ("min_percent", min_percent), ("min_sep", min_sep), ("min_gain", min_gain)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise MtrError(f"{name} must be an integer, got {v!r}")
+        if isinstance(sg.n_loci, bool) or not isinstance(sg.n_loci, (int, np.integer)) or sg.n_loci < 1:
+            raise MtrError(f"n_loci must be an integer >= 1, got {sg.n_loci!r}")
+        if not isinstance(sg.read, torch.Tensor) or sg.read.dim() != 1 or not isinstance(calls.read, torch.Tensor) or calls.read.dim() != 1:
+            raise MtrError("the rows' and the calls' read columns must be 1-D torch tensors")
+        if not isinstance(windows.bases, torch.Tensor) or windows.bases.dim() != 1:
+            raise MtrError("the windows' bases must be a 1-D torch tensor")
+        R, S, T, m = int(sg.read.numel()), int(calls.read.numel()), int(windows.bases.numel()), int(sg.n_loci)
+        col = self._gpu_column
+        src = CConsensusSrc(col(sg.read, torch.int32, (R,), "the rows' read"), col(sg.locus, torch.int32, (R,), "the rows' locus"),
+                            col(windows.off, torch.int64, (R + 1,), "the windows' off"), col(windows.bases, torch.uint8, (T,), "the windows' bases"),
+                            col(calls.support_off, torch.int64, (m + 1,), "the calls' support_off"), col(calls.read, torch.int32, (S,), "the calls' read"),
+                            None, None, R, T, S, m)
+        value = col(calls.value, torch.int32, (S,), "the calls' value")
+        prm = CSeqParams(int(max_dist), int(min_support), int(min_percent), int(min_sep), int(min_gain))
+        dev = torch.device("cuda", self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ns, npairs = C.c_int64(), C.c_int64()
+        self._check(self.lib.mtr_call_alleles_sequence_device(self.h, C.byref(src), value, C.byref(prm), stream, C.byref(ns), C.byref(npairs)),
+                    "mtr_call_alleles_sequence_device")
+        P = int(npairs.value)
+        new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)     # noqa: E731
+        ac = AlleleCalls(new(torch.int64, m + 1), new(torch.int32, S), new(torch.int32, S), new(torch.uint8, S), new(torch.uint8, m),
+                         new(torch.int32, m, 2), new(torch.int32, m, 2), new(torch.int64, m, 2))
+        sc = SequenceCalls(ac, new(torch.int32, m, 2), new(torch.int32, S), new(torch.uint8, m), new(torch.int64, m + 1), new(torch.uint8, P))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CSeqCallsDst(*[t.data_ptr() if t.numel() else None for t in (*ac, *sc[1:])], m, S, P)
+        self._check(self.lib.mtr_call_alleles_sequence_copy_device(self.h, C.byref(dst)), "mtr_call_alleles_sequence_copy_device")
+        return sc
+
     def _window_args(self, structures, off, bases, which, gain, mismatch, indel):
         """what window_structure and window_edits hand to the library for their common arguments, in the calls' order up to wait_stream: the
         host arrays of the structures (kept alive by the caller through the returned tuple), the device columns, N, T, the scores, the stream"""
@@ -2337,6 +2411,30 @@ def format_allele_calls(loci, calls: AlleleCalls) -> bytes:
         ends = (int(value[lo]), int(value[hi - 1])) if hi > lo else (0, 0)
         cols = [k, hi - lo, int(zyg[k]), int(call[k, 0]), int(call[k, 1]), int(sup[k, 0]), int(sup[k, 1]), int(cost[k, 0]), int(cost[k, 1]), *ends]
         out.append("\t".join(str(c) for c in cols).encode() + b"\t" + bmot[k] + b"\n")
+    return b"".join(out)
+
+
+def format_sequence_calls(loci, sc: SequenceCalls) -> bytes:
+    """The calls of Engine.call_alleles_by_sequence as text: format_allele_calls' line per locus, then for each of the two alleles its medoid's
+    read (-1 without one) and its members' mean distance to that medoid as the exact fraction sum/n (0/0 without members).
+    loci: what genotype_loci was given; sc: call_alleles_by_sequence's result (tensors or numpy)."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    lines = format_allele_calls(loci, sc.calls).split(b"\n")[:-1]
+    m = len(lines)
+    off, allele, dtm = host(sc.calls.support_off).reshape(-1), host(sc.calls.allele).reshape(-1), host(sc.dist_to_medoid).reshape(-1)
+    medoid, zyg = host(sc.medoid).reshape(-1, 2), host(sc.calls.zygosity).reshape(-1)
+    if len(medoid) != m or len(dtm) != len(allele):
+        raise MtrError(f"{len(medoid)} medoid pairs for {m} loci, {len(dtm)} distances for {len(allele)} entries")
+    out = []
+    for k in range(m):
+        lo, hi = int(off[k]), int(off[k + 1])
+        cols = []
+        for a in (0, 1):
+            mine = [int(d) for d, x in zip(dtm[lo:hi], allele[lo:hi]) if x == a] if a < int(zyg[k]) else []
+            cols += [str(int(medoid[k, a])), f"{sum(mine)}/{len(mine)}"]
+        out.append(lines[k] + b"\t" + "\t".join(cols).encode() + b"\n")
     return b"".join(out)
 
 

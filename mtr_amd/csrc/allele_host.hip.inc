@@ -518,3 +518,137 @@ extern "C" mtr_status mtr_window_edits_copy_device(mtr_ctx *ctx, const mtr_windo
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
 }
+
+// ---- the sequence allele calls (seq_calls.hip.inc) -------------------------------------------------------------------------------------------
+// The consensus' checks in its order, then the members' rows, the loci's pair counts and their scan, one look at P, the pairs' tasks, one look
+// at the buckets' counts, the distances bucket by bucket, the split.  Everything lands in buffers of the context's own, kept for the copy.
+static_assert(MTR_SEQ_MAX_DIST == SQ_MAX_DIST && MTR_SEQ_MAX_MEMBERS == SQ_MAX_MEMBERS, "the sequence calls' limits");
+static_assert(sizeof(mtr_seq_params) == sizeof(SqParams), "the sequence calls' parameters");
+
+template <int ROWS, int CPL>
+static void seq_dist_bucket(mtr_ctx *ctx, const SeqArgs &a, const int4 *tasks, int64_t step, unsigned n_tasks)
+{
+    if (n_tasks == 0) return;
+    const unsigned groups = (n_tasks + (unsigned)ROWS - 1u) / (unsigned)ROWS;
+    hipLaunchKernelGGL((mtr_k_seq_dist<ROWS, CPL>), dim3(std::min<unsigned>(groups, SQ_MAX_GRID)), dim3(64), 0, ctx->stream, a, tasks, step, n_tasks);
+}
+
+extern "C" mtr_status mtr_call_alleles_sequence_device(mtr_ctx *ctx, const mtr_consensus_src *src, const int32_t *value, const mtr_seq_params *prm,
+                                                       void *wait_stream, int64_t *out_support, int64_t *out_pairs)
+{
+    if (!ctx || !out_support || !out_pairs) return MTR_ERR_BAD_ARG;
+    *out_support = 0; *out_pairs = 0;
+    ctx->sq_ready = false;
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
+    if (!src || !prm) { ctx->err = "src or prm is NULL"; return MTR_ERR_BAD_ARG; }
+    const int64_t R = src->n_rows, S = src->n_support, NB = src->n_bases; const int32_t n_loci = src->n_loci;
+    if (n_loci < 1 || n_loci > (1 << 30) - 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + " outside 1..2^30 - 1"; return MTR_ERR_BAD_ARG; }
+    if (R < 0 || R > (int64_t)INT32_MAX) { ctx->err = "n_rows = " + std::to_string(R) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (S < 0 || S > (int64_t)INT32_MAX) { ctx->err = "n_support = " + std::to_string(S) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (NB < 0 || NB > (int64_t)INT32_MAX) { ctx->err = "n_bases = " + std::to_string(NB) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (prm->max_dist < 0 || prm->max_dist > MTR_SEQ_MAX_DIST) { ctx->err = "max_dist = " + std::to_string(prm->max_dist) + " outside 0.." + std::to_string(MTR_SEQ_MAX_DIST); return MTR_ERR_BAD_ARG; }
+    if (prm->min_support < 1) { ctx->err = "min_support " + std::to_string(prm->min_support) + ": at least 1"; return MTR_ERR_BAD_ARG; }
+    if (prm->min_percent < 0 || prm->min_percent > 50) { ctx->err = "min_percent " + std::to_string(prm->min_percent) + " outside 0..50"; return MTR_ERR_BAD_ARG; }
+    if (prm->min_sep < 1) { ctx->err = "min_sep " + std::to_string(prm->min_sep) + ": at least 1"; return MTR_ERR_BAD_ARG; }
+    if (prm->min_gain < 0 || prm->min_gain > 100) { ctx->err = "min_gain " + std::to_string(prm->min_gain) + " outside 0..100"; return MTR_ERR_BAD_ARG; }
+    if (!src->win_off || !src->support_off || (R > 0 && (!src->row_read || !src->row_locus)) || (NB > 0 && !src->win_bases) || (S > 0 && (!src->read || !value))) {
+        ctx->err = "an input column is NULL"; return MTR_ERR_BAD_ARG;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    {
+        const DeviceCol cols[7] = {
+            { src->row_read, R * 4, "src->row_read" }, { src->row_locus, R * 4, "src->row_locus" }, { src->win_off, (R + 1) * 8, "src->win_off" }, { src->win_bases, NB, "src->win_bases" },
+            { src->support_off, ((int64_t)n_loci + 1) * 8, "src->support_off" }, { src->read, S * 4, "src->read" }, { value, S * 4, "value" } };
+        { mtr_status st = check_device_cols(ctx, cols, "the column's bytes"); if (st != MTR_OK) return st; }
+    }
+    const size_t nl = (size_t)n_loci, ns = std::max<size_t>((size_t)S, 1);
+    HIPCHK(ctx->d_sq_i32.ensure((ns + nl) * 4)); HIPCHK(ctx->d_sq_pair_off.ensure((nl + 1) * 8)); HIPCHK(ctx->d_sq_off.ensure((nl + 1) * 8));
+    HIPCHK(ctx->d_sq_value.ensure(ns * 4)); HIPCHK(ctx->d_sq_read.ensure(ns * 4)); HIPCHK(ctx->d_sq_dtm.ensure(ns * 4)); HIPCHK(ctx->d_sq_allele.ensure(ns));
+    HIPCHK(ctx->d_sq_zyg.ensure(nl)); HIPCHK(ctx->d_sq_skipped.ensure(nl)); HIPCHK(ctx->d_sq_call.ensure(2 * nl * 4)); HIPCHK(ctx->d_sq_sup.ensure(2 * nl * 4));
+    HIPCHK(ctx->d_sq_medoid.ensure(2 * nl * 4)); HIPCHK(ctx->d_sq_cost.ensure(2 * nl * 8));
+    { mtr_status st = columns_begin(ctx, wait_stream, ctx->d_sq_state, CO_BAD, SQ_STATE * 4); if (st != MTR_OK) return st; }
+    SeqArgs a{};
+    ConsArgs &c = a.c;
+    c.row_read = src->row_read; c.row_locus = src->row_locus; c.R = R; c.win_off = src->win_off; c.win_bases = src->win_bases; c.n_bases = NB;
+    c.support_off = src->support_off; c.sup_read = src->read; c.S = S; c.n_loci = n_loci;
+    c.ent_row = ctx->d_sq_i32; c.bad = ctx->d_sq_state; c.state = (unsigned *)(c.bad + CO_BAD);
+    a.value = value; a.prm = { prm->max_dist, prm->min_support, prm->min_percent, prm->min_sep, prm->min_gain };
+    a.npairs = ctx->d_sq_i32 + ns; a.pair_off = ctx->d_sq_pair_off;
+    a.o_value = ctx->d_sq_value; a.o_read = ctx->d_sq_read; a.o_dtm = ctx->d_sq_dtm; a.o_allele = ctx->d_sq_allele; a.o_zyg = ctx->d_sq_zyg; a.o_skipped = ctx->d_sq_skipped;
+    a.o_call = ctx->d_sq_call; a.o_sup = ctx->d_sq_sup; a.o_medoid = ctx->d_sq_medoid; a.o_cost = ctx->d_sq_cost;
+    const auto blocks = [](int64_t n) { return dim3((unsigned)((std::max<int64_t>(n, 1) + SQ_BLOCK - 1) / SQ_BLOCK)); };
+    const dim3 blk(SQ_BLOCK);
+    unsigned long long bad[CO_BAD];
+    hipLaunchKernelGGL(mtr_k_seq_check, blocks(std::max<int64_t>(R, n_loci)), blk, 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(ctx, bad, c.bad, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad[0] != ~0ull) { ctx->err = "row " + std::to_string(bad[0]) + " is out of order: the rows must ascend by (read, locus), each pair once, none negative"; return MTR_ERR_BAD_ARG; }
+    if (bad[1] != ~0ull) { ctx->err = "win_off at row " + std::to_string(bad[1]) + " does not ascend from 0 to n_bases, or the window is above 2^30 bases"; return MTR_ERR_BAD_ARG; }
+    if (bad[2] != ~0ull) { ctx->err = "locus " + std::to_string(bad[2]) + ": support_off does not ascend from 0 to n_support"; return MTR_ERR_BAD_ARG; }
+    if (S > 0) {
+        hipLaunchKernelGGL(mtr_k_seq_members, blocks(S), blk, 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        HIPCHK(copy_sync(ctx, bad, c.bad, sizeof bad, hipMemcpyDeviceToHost));
+        if (bad[3] != ~0ull) {
+            int32_t rd = 0;
+            HIPCHK(copy_sync(ctx, &rd, src->read + bad[3], 4, hipMemcpyDeviceToHost));
+            ctx->err = "support entry " + std::to_string(bad[3]) + " (read " + std::to_string(rd) + ") has no row of its (read, locus)";
+            return MTR_ERR_BAD_ARG;
+        }
+    }
+    hipLaunchKernelGGL(mtr_k_seq_loci, blocks(n_loci), blk, 0, ctx->stream, a);
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.npairs, (int64_t)n_loci, a.pair_off);
+    HIPCHK(hipGetLastError());
+    int64_t P = 0;
+    HIPCHK(copy_sync(ctx, &P, a.pair_off + n_loci, 8, hipMemcpyDeviceToHost));
+    if (P < 0 || P > S * (SQ_MAX_MEMBERS - 1) / 2) { ctx->err = "the sequence calls' pair counts failed on the device"; return MTR_ERR_HIP; }
+    if (P > (int64_t)INT32_MAX) { ctx->err = std::to_string(P) + " pairs are more than 2^31 - 1"; return MTR_ERR_OVERFLOW; }
+    a.P = P;
+    HIPCHK(ctx->d_sq_dist.ensure(std::max<size_t>((size_t)P, 1))); HIPCHK(ctx->d_sq_tasks.ensure(std::max<size_t>(2 * (size_t)P, 1) * sizeof(int4)));
+    a.dist = ctx->d_sq_dist; a.tasks = ctx->d_sq_tasks;
+    if (P > 0) {
+        hipLaunchKernelGGL(mtr_k_seq_tasks, dim3((unsigned)std::min<int64_t>((P + SQ_BLOCK - 1) / SQ_BLOCK, SQ_MAX_GRID)), blk, 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        unsigned n[SQ_STATE];
+        HIPCHK(copy_sync(ctx, n, c.state, sizeof n, hipMemcpyDeviceToHost));
+        if ((int64_t)n[0] + n[1] > P || (int64_t)n[2] + n[3] > P) { ctx->err = "the sequence calls' task lists failed on the device"; return MTR_ERR_HIP; }
+        const char *e = getenv("MTR_TEST_SEQ_ROWS");
+        if (e && atoi(e) == 0) { seq_dist_bucket<1, 1>(ctx, a, a.tasks, 1, n[0]); seq_dist_bucket<1, 1>(ctx, a, a.tasks + P - 1, -1, n[1]); }
+        else { seq_dist_bucket<4, 1>(ctx, a, a.tasks, 1, n[0]); seq_dist_bucket<2, 1>(ctx, a, a.tasks + P - 1, -1, n[1]); }
+        seq_dist_bucket<1, 1>(ctx, a, a.tasks + P, 1, n[2]);
+        seq_dist_bucket<1, 2>(ctx, a, a.tasks + 2 * P - 1, -1, n[3]);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(mtr_k_seq_split, dim3((unsigned)std::min<int64_t>(n_loci, SQ_MAX_GRID)), dim3(64), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ctx->d_sq_off, src->support_off, (nl + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->sq_ready = true; ctx->sq_loci = n_loci; ctx->sq_support = S; ctx->sq_pairs = P;
+    *out_support = S; *out_pairs = P;
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_call_alleles_sequence_copy_device(mtr_ctx *ctx, const mtr_seq_calls_dst *dst)
+{
+    if (!ctx) return MTR_ERR_BAD_ARG;
+    if (!ctx->sq_ready) { ctx->err = "no sequence calls kept: mtr_call_alleles_sequence_device comes first"; return MTR_ERR_BAD_ARG; }
+    if (!dst) { ctx->err = "dst is NULL"; return MTR_ERR_BAD_ARG; }
+    const int64_t L = ctx->sq_loci, S = ctx->sq_support, P = ctx->sq_pairs;
+    if (dst->cap_loci < L) { ctx->err = "destination holds " + std::to_string(dst->cap_loci) + " loci, " + std::to_string(L) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (dst->cap_support < S) { ctx->err = "destination holds " + std::to_string(dst->cap_support) + " supporting rows, " + std::to_string(S) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (dst->cap_pairs < P) { ctx->err = "destination holds " + std::to_string(dst->cap_pairs) + " pairs, " + std::to_string(P) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (!dst->support_off || !dst->zygosity || !dst->call || !dst->call_support || !dst->medoid || !dst->cost || !dst->skipped || !dst->pair_off ||
+        (S > 0 && (!dst->value || !dst->read || !dst->allele || !dst->dist_to_medoid)) || (P > 0 && !dst->dist)) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const DeviceCol cols[13] = { { dst->support_off, (L + 1) * 8, "dst->support_off" }, { dst->value, S * 4, "dst->value" }, { dst->read, S * 4, "dst->read" }, { dst->allele, S, "dst->allele" },
+                                 { dst->dist_to_medoid, S * 4, "dst->dist_to_medoid" }, { dst->zygosity, L, "dst->zygosity" }, { dst->call, L * 8, "dst->call" },
+                                 { dst->call_support, L * 8, "dst->call_support" }, { dst->medoid, L * 8, "dst->medoid" }, { dst->cost, L * 16, "dst->cost" }, { dst->skipped, L, "dst->skipped" },
+                                 { dst->pair_off, (L + 1) * 8, "dst->pair_off" }, { dst->dist, P, "dst->dist" } };
+    { mtr_status st = check_device_cols(ctx, cols, "the column's bytes"); if (st != MTR_OK) return st; }
+    const void *from[13] = { ctx->d_sq_off.p, ctx->d_sq_value.p, ctx->d_sq_read.p, ctx->d_sq_allele.p, ctx->d_sq_dtm.p, ctx->d_sq_zyg.p, ctx->d_sq_call.p, ctx->d_sq_sup.p, ctx->d_sq_medoid.p,
+                             ctx->d_sq_cost.p, ctx->d_sq_skipped.p, ctx->d_sq_pair_off.p, ctx->d_sq_dist.p };
+    for (int k = 0; k < 13; k++)
+        if (cols[k].bytes > 0) HIPCHK(hipMemcpyAsync(const_cast<void *>(cols[k].p), from[k], (size_t)cols[k].bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}

@@ -42,6 +42,13 @@ DEVINL int32_t cons_locus(const ConsArgs &a, int64_t e)
     while (lo < hi) { const int32_t mid = (lo + hi + 1) >> 1; if (a.support_off[mid] <= e) lo = mid; else hi = mid - 1; }
     return lo;
 }
+// the row of (read, locus) by bisection over the rows' ascending keys, -1 without one
+DEVINL int32_t cons_row_of(const ConsArgs &a, unsigned long long key)
+{
+    int64_t lo = 0, hi = a.R;                                           // the first row whose key is not below the entry's
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (cons_key(a.row_read[mid], a.row_locus[mid]) < key) lo = mid + 1; else hi = mid; }
+    return lo < a.R && cons_key(a.row_read[lo], a.row_locus[lo]) == key ? (int32_t)lo : -1;
+}
 // the segment [lo, hi) of allele a of locus l within the locus' entries
 DEVINL void cons_segment(const ConsArgs &a, int32_t l, int al, int64_t &lo, int64_t &hi)
 {
@@ -99,12 +106,9 @@ __global__ __launch_bounds__(CO_BLOCK) void mtr_k_cons_members(ConsArgs a)
     const int64_t e = (int64_t)blockIdx.x * CO_BLOCK + threadIdx.x;
     if (e >= a.S) return;
     const int32_t l = cons_locus(a, e);
-    const unsigned long long key = cons_key(a.sup_read[e], l);
-    int64_t lo = 0, hi = a.R;                                           // the first row whose key is not below the entry's
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (cons_key(a.row_read[mid], a.row_locus[mid]) < key) lo = mid + 1; else hi = mid; }
-    const bool found = lo < a.R && cons_key(a.row_read[lo], a.row_locus[lo]) == key;
-    a.ent_row[e] = found ? (int32_t)lo : -1;
-    if (!found) atomicMin(&a.bad[3], (unsigned long long)e);
+    const int32_t row = cons_row_of(a, cons_key(a.sup_read[e], l));
+    a.ent_row[e] = row;
+    if (row < 0) atomicMin(&a.bad[3], (unsigned long long)e);
     if (a.sup_allele[e] > 1 || (e > a.support_off[l] && a.sup_allele[e] < a.sup_allele[e - 1])) atomicMin(&a.bad[4], (unsigned long long)e);
 }
 

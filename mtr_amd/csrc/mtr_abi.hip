@@ -55,6 +55,7 @@
 #include "window_structure.hip.inc"
 #include "window_structure_args.h"
 #include "window_edits.hip.inc"
+#include "seq_calls.hip.inc"
 #include "fasta.hip.inc"
 #include "fastq.hip.inc"
 #include "file_order.hip.inc"
@@ -289,6 +290,11 @@ struct mtr_ctx {
     DevBuf<WsStruct> d_we_structs; DevBuf<int32_t> d_we_i32, d_we_edits, d_we_seg, d_we_score; DevBuf<WsRaw> d_we_raw; DevBuf<unsigned long long> d_we_state;
     DevBuf<int64_t> d_we_i64, d_we_off; DevBuf<WeCount> d_we_cnt; DevBuf<uint32_t> d_we_scratch; DevBuf<uint8_t> d_we_skipped;
     bool we_ready = false; int64_t we_windows = 0, we_edits = 0; int32_t we_rounds = 0;
+    // the sequence allele calls (seq_calls.hip.inc), buffers of its own: d_sq_i32 = the entries' rows | the loci's pair counts, the tasks, the state, and what
+    // the call KEEPS for mtr_call_alleles_sequence_copy_device: the columns of sq_loci loci, sq_support entries and sq_pairs pairs (sq_ready)
+    DevBuf<int32_t> d_sq_i32, d_sq_value, d_sq_read, d_sq_dtm, d_sq_call, d_sq_sup, d_sq_medoid; DevBuf<uint8_t> d_sq_allele, d_sq_zyg, d_sq_skipped, d_sq_dist;
+    DevBuf<int64_t> d_sq_off, d_sq_pair_off, d_sq_cost; DevBuf<int4> d_sq_tasks; DevBuf<unsigned long long> d_sq_state;
+    bool sq_ready = false; int64_t sq_support = 0, sq_pairs = 0; int32_t sq_loci = 0;
     long long wrap_dp_size = MTRC_WRAP_DP_SIZE;          // the WrapDPsize the kernels of this context's device test (MTR_TEST_WRAP_DP_SIZE)
     // a FASTA file in device memory (fasta.hip.inc), per call: the tiles' columns, the header windows' columns, the IDs' offsets, the stop, the sizes
     DevBuf<uint32_t> d_fa_tiles, d_fa_hbase; DevBuf<int32_t> d_fa_hpos, d_fa_hidlen; DevBuf<int64_t> d_fa_idoff;

@@ -227,7 +227,8 @@ mtr_status mtr_fasta_index(const mtr_ctx *ctx, int32_t *lens, int64_t *id_off, c
  * Protocol, argument checks and stream handling are those of the FASTA entry points above, and info, dst, mtr_fasta_index mean
  * what they mean there: text = the reads' bases read after read, offsets their exclusive sum.  mtr_upload_fastq_device compacts
  * nothing: a sequence line is contiguous in the file, and the packing kernel of mtr_upload_batch_device reads the reads out of
- * d_fastq itself.  Multi-line FASTQ and the qualities as output are not supported. */
+ * d_fastq itself.  Multi-line FASTQ is not supported.  The qualities are no output of these calls; an upload keeps them with the
+ * batch when mtr_keep_qualities is on ("qualities of the resident batch", below). */
 #define MTR_FASTA_END_FORMAT 4
 mtr_status mtr_parse_fastq_device(mtr_ctx *ctx, const uint8_t *d_fastq, int64_t n_bytes, void *wait_stream,
                                   const mtr_fasta_dst *dst, mtr_fasta_info *info);
@@ -842,6 +843,59 @@ typedef struct mtr_consensus_dst {
 } mtr_consensus_dst;   /* caller-owned DEVICE memory */
 mtr_status mtr_allele_consensus_device(mtr_ctx *ctx, const mtr_consensus_src *src, int32_t band_extra, void *wait_stream,
                                        const mtr_consensus_dst *dst, int64_t *out_bases);
+
+/* ---- qualities of the resident batch, their windows, and the quality-weighted allele consensus ---------------------------------------------------
+ * The allele consensus gives every base one vote, whether the basecaller called it with Q3 or Q40.  These entries carry the FASTQ's own
+ * qualities from the file to the vote.  Stored qualities are Phred values 0..MTR_QUAL_MAX, one byte per base, in a buffer the context owns: read
+ * r's at the exclusive sum of the lengths of the reads before it.  They belong to the resident batch: every upload replaces or drops them.
+ *
+ * mtr_keep_qualities: a sticky option of the context, off by default (on != 0: on).  While it is on, mtr_upload_fastq_device, its _in_file and
+ * its _window form also gather each read's quality line, after the upload itself has succeeded: the stored value of a byte b is min(MTR_QUAL_MAX,
+ * max(0, b - 33)).  An upload made with the option off, and an upload of FASTA, text, codes or a packed image, leaves no qualities.
+ * mtr_attach_qualities_device: the caller's Phred values (NOT ASCII) for the resident batch, whatever uploaded it: read i's are d_qual[offsets[i]
+ * .. offsets[i] + lens[i]), d_qual DEVICE memory of n_bytes bytes, offsets [n_reads] on the HOST; a value above MTR_QUAL_MAX is stored as
+ * MTR_QUAL_MAX.  MTR_ERR_BAD_ARG naming the offender: no batch resident; d_qual or offsets NULL, d_qual not device memory of the context's GPU or
+ * n_bytes running past its allocation; a read whose span leaves 0..n_bytes (the smallest such read).  A refused call leaves the qualities as
+ * they were.  mtr_qualities_resident: *out_bytes = the stored bytes, 0 when there are none.
+ *
+ * mtr_extract_window_qualities_device: the byte-for-byte companion of mtr_extract_windows_device - the same arguments, the same checks in the
+ * same order (behind "no batch uploaded": no qualities resident, MTR_ERR_BAD_ARG "no qualities resident"), the same T.  Row r's values are
+ * dst_qual[win_off[r] .. win_off[r + 1]) with mtr_extract_windows_device's win_off: the read's values [lo, hi) for orientation 0, the same
+ * reversed - not complemented - for orientation 1, so that value k belongs to base k of the oriented window.  dst_qual == NULL: MTR_OK with T
+ * only; cap < T: MTR_ERR_OVERFLOW, nothing written.
+ *
+ * mtr_allele_consensus_quality_device: mtr_allele_consensus_device with weighted votes.  src and dst are its structs, win_qual [n_bases] is
+ * DEVICE memory aligned with src->win_bases, the outputs are its eight columns with votes holding weight sums.  The alleles, the backbone, the
+ * skip rule, the banded D and its directions, the tie rules, the protocol and the checks with their order are exactly its own: the alignment
+ * is not weighted.  Two refusals come behind band_extra: qual_cap outside 1..MTR_CONSQ_MAX_CAP, and n_support * qual_cap >= 2^31 (the sums are
+ * int32); a NULL win_qual with n_bases > 0 is a NULL input column, and its memory is checked behind win_bases'.
+ * The definition:
+ *   weights     w(q) = min(max(q, 1), qual_cap).  For a member with window W of n bases, omega[i] = w(the quality of W[i]); omegaB is the same
+ *               for the backbone.  The gap weight gamma(i) at boundary i of a window, 0 <= i <= n, is min(omega[i-1], omega[i]) where both exist,
+ *               the one that exists at the ends, 1 for an empty window; gammaB is the backbone's
+ *   the path    the walk from (n, m) to (0, 0) visits every column j = 0 .. m, in column j the rows lo_j .. hi_j: L_j = hi_j - lo_j is its run of up
+ *               steps there, which inserts W[lo_j .. hi_j) after backbone position j, and it leaves column j >= 1 from (lo_j, j) by diag or left
+ *   votes       of an aligned member: diag from (i, j): base[j][W[i-1]] += omega[i-1]; left from (i, j): del[j] += gamma(i); ins[j][k][W[lo_j + k]]
+ *               += omega[lo_j + k] for k < min(L_j, MTR_CONS_INS_SLOTS); and if L_j < MTR_CONS_INS_SLOTS: end[j][L_j] += gamma(hi_j) - the member
+ *               says "nothing more here from slot L_j on" with the weight of the boundary where that nothing is.  Of the backbone:
+ *               base[j][B[j-1]] += omegaB[j-1] for every j
+ *   emission    for j = 0 .. m: if j >= 1, c* = the base of the largest base[j] - among tied bases the backbone's if it is one of them, else the
+ *               lowest code - is emitted with votes = base[j][c*] unless del[j] > base[j][c*]; then the insertion slots k = 0, 1, .. after j: with
+ *               none_k = gammaB(j) + the sum of end[j][L] over L <= k, and mx the maximum over c of ins[j][k][c] (lowest code on a tie), slot k is
+ *               emitted with votes = mx iff mx > none_k; the first slot not emitted ends the junction
+ * Every output is an exact integer and none depends on the order in which the device worked.  With qual_cap = 1 every weight is 1, none_k is
+ * N - tot, and the result is mtr_allele_consensus_device's in all eight columns, whatever the qualities.  With one constant quality c <=
+ * qual_cap and no empty window among the members and backbones, the bases are the unweighted ones and votes c times the unweighted votes.
+ * MTR_ABI_VERSION is unchanged by these entries: look for them by symbol. */
+#define MTR_QUAL_MAX 93
+#define MTR_CONSQ_MAX_CAP 93
+mtr_status mtr_keep_qualities(mtr_ctx *ctx, int32_t on);
+mtr_status mtr_attach_qualities_device(mtr_ctx *ctx, const uint8_t *d_qual, int64_t n_bytes, const int64_t *offsets, void *wait_stream);
+mtr_status mtr_qualities_resident(const mtr_ctx *ctx, int64_t *out_bytes);
+mtr_status mtr_extract_window_qualities_device(mtr_ctx *ctx, const int32_t *row_read, const uint8_t *orientation, const int32_t *window, int64_t n_rows,
+                                               void *wait_stream, uint8_t *dst_qual, int64_t cap, int64_t *out_bases);
+mtr_status mtr_allele_consensus_quality_device(mtr_ctx *ctx, const mtr_consensus_src *src, const uint8_t *win_qual, int32_t band_extra, int32_t qual_cap,
+                                               void *wait_stream, const mtr_consensus_dst *dst, int64_t *out_bases);
 
 /* ---- window structure: compound loci counted segment by segment ---------------------------------------------------------------------------------
  * A genotype row's `copies` is one count for one motif, taken from a LOCAL alignment; a compound locus - HTT's (CAG)n CAACAG CCGCCA (CCG)m - and

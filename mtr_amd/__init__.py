@@ -60,7 +60,10 @@ EXPORTS = ["mtr_create", "mtr_destroy", "mtr_last_error", "mtr_abi_version", "mt
            "mtr_genotype_partial_catalog_prepared_device", "mtr_test_catalog_dump", "mtr_test_catalog_build_stats",
            "mtr_extract_windows_device", "mtr_allele_consensus_device", "mtr_window_structure_device",
            "mtr_window_edits_device", "mtr_window_edits_copy_device", "mtr_test_window_edits_rounds",
-           "mtr_call_alleles_sequence_device", "mtr_call_alleles_sequence_copy_device"]
+           "mtr_call_alleles_sequence_device", "mtr_call_alleles_sequence_copy_device",
+           "mtr_keep_qualities", "mtr_attach_qualities_device", "mtr_qualities_resident", "mtr_extract_window_qualities_device",
+           "mtr_allele_consensus_quality_device"]
+QUAL_MAX, CONSQ_MAX_CAP = 93, 93             # MTR_QUAL_MAX, MTR_CONSQ_MAX_CAP: the largest stored Phred value, the largest qual_cap of Engine.allele_consensus_quality
 SEQ_MAX_DIST, SEQ_MAX_MEMBERS = 254, 128     # MTR_SEQ_*: the limits of Engine.call_alleles_by_sequence
 WE_FIELDS = 6                               # MTR_WE_FIELDS: pos, segment, copy, column, kind, base of an edit of Engine.window_edits
 WS_MAX_SEGMENTS, WS_MAX_WINDOW = 4, 16384    # MTR_WS_*: the limits of Engine.window_structure
@@ -726,6 +729,14 @@ def load_library(path: str = LIB_PATH):
         lib.mtr_call_alleles_sequence_device.restype = C.c_int
         lib.mtr_call_alleles_sequence_copy_device.argtypes = [C.c_void_p, P(CSeqCallsDst)]
         lib.mtr_call_alleles_sequence_copy_device.restype = C.c_int
+    if hasattr(lib, "mtr_allele_consensus_quality_device"):       # (likewise a build from before the qualities)
+        lib.mtr_keep_qualities.argtypes = [C.c_void_p, C.c_int32]
+        lib.mtr_attach_qualities_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.mtr_qualities_resident.argtypes = [C.c_void_p, P(C.c_int64)]
+        lib.mtr_extract_window_qualities_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
+        lib.mtr_allele_consensus_quality_device.argtypes = [C.c_void_p, P(CConsensusSrc), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, P(CConsensusDst), P(C.c_int64)]
+        for name in ("mtr_keep_qualities", "mtr_attach_qualities_device", "mtr_qualities_resident", "mtr_extract_window_qualities_device", "mtr_allele_consensus_quality_device"):
+            getattr(lib, name).restype = C.c_int
     lib.mtr_test_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
     lib.mtr_test_catalog_stats.restype = C.c_int
     lib.mtr_test_partial_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
@@ -1060,11 +1071,40 @@ class Engine:
         front of end_pos are uploaded.  walk_fasta_device is the loop over a whole file."""
         return self._upload_file_device("mtr_upload_fasta_device", buf, file_state, more)
 
-    def upload_fastq_device(self, buf, file_state: "FileState | None" = None, more: bool = False) -> Fasta:
+    def upload_fastq_device(self, buf, file_state: "FileState | None" = None, more: bool = False, keep_quality: bool = False) -> Fasta:
         """mtr_upload_fastq_device(_in_file) + mtr_fasta_index: upload_fasta_device for the bytes of a FASTQ file.  Nothing is
         copied or compacted: the reads are packed out of buf itself, where each is one contiguous sequence line.
-        more=True (mtr_upload_fastq_device_window): buf is the beginning of a longer input, as in parse_fastq_device."""
-        return self._upload_file_device("mtr_upload_fastq_device", buf, file_state, more)
+        more=True (mtr_upload_fastq_device_window): buf is the beginning of a longer input, as in parse_fastq_device.
+        keep_quality=True (mtr_keep_qualities, for this call): the reads' quality lines stay with the batch as Phred values, for
+        genotype_window_qualities; any later upload replaces or drops them."""
+        if not keep_quality:
+            return self._upload_file_device("mtr_upload_fastq_device", buf, file_state, more)
+        self._check(self.lib.mtr_keep_qualities(self.h, 1), "mtr_keep_qualities")
+        try:
+            return self._upload_file_device("mtr_upload_fastq_device", buf, file_state, more)
+        finally:
+            self.lib.mtr_keep_qualities(self.h, 0)
+
+    def qualities_resident(self) -> int:
+        """mtr_qualities_resident: the Phred values kept with the resident batch, 0 when there are none"""
+        nb = C.c_int64()
+        self._check(self.lib.mtr_qualities_resident(self.h, C.byref(nb)), "mtr_qualities_resident")
+        return int(nb.value)
+
+    def attach_qualities(self, qual, offsets) -> None:
+        """mtr_attach_qualities_device: Phred values (not ASCII) for the resident batch, whatever uploaded it - upload_device for one.  qual: a
+        1-D uint8 tensor on this engine's device; offsets: per read of the batch where its values begin in qual (a host sequence of integers);
+        read i's values are qual[offsets[i]:offsets[i] + lens[i]].  Values above 93 are stored as 93."""
+        import torch
+
+        if not isinstance(qual, torch.Tensor) or qual.dim() != 1:
+            raise MtrError("qual must be a 1-D torch tensor")
+        ptr = self._gpu_column(qual, torch.uint8, (int(qual.numel()),), "qual")
+        offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+        if len(offs) != self.n_reads:
+            raise MtrError(f"{len(offs)} offsets for the resident batch of {self.n_reads} reads")
+        stream = C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+        self._check(self.lib.mtr_attach_qualities_device(self.h, ptr, int(qual.numel()), offs.ctypes.data, stream), "mtr_attach_qualities_device")
 
     def _upload_file_device(self, entry: str, buf, file_state, more: bool = False) -> Fasta:
         import torch
@@ -1111,10 +1151,13 @@ class Engine:
             } while (info.end == MTR_FASTA_END_MORE);"""
         return self._walk_file_device(self.upload_fasta_device, buf, window_bytes, file_state)
 
-    def walk_fastq_device(self, buf, window_bytes: int, file_state: "FileState | None" = None):
+    def walk_fastq_device(self, buf, window_bytes: int, file_state: "FileState | None" = None, keep_quality: bool = False):
         """walk_fasta_device for the bytes of a FASTQ file (upload_fastq_device, mtr_upload_fastq_device_window): a window's reads
-        are the records whose quality line's LF lies in it, and the next window starts behind the last such LF."""
-        return self._walk_file_device(self.upload_fastq_device, buf, window_bytes, file_state)
+        are the records whose quality line's LF lies in it, and the next window starts behind the last such LF.  keep_quality: as
+        upload_fastq_device's, for every batch of the walk."""
+        if not keep_quality:
+            return self._walk_file_device(self.upload_fastq_device, buf, window_bytes, file_state)
+        return self._walk_file_device(lambda part, fs, more: self.upload_fastq_device(part, fs, more, keep_quality=True), buf, window_bytes, file_state)
 
     def _walk_file_device(self, upload, buf, window_bytes, file_state):
         if isinstance(window_bytes, bool) or not isinstance(window_bytes, (int, np.integer)) or window_bytes < 1:
@@ -1548,6 +1591,43 @@ class Engine:
         self._check(self.lib.mtr_extract_windows_device(self.h, *ptrs, R, stream, C.byref(dst), C.byref(nb)), "mtr_extract_windows_device")
         return win
 
+    def genotype_window_qualities(self, sg):
+        """The Phred values of genotype_windows(sg)'s bases (mtr_extract_window_qualities_device): a uint8 tensor [T] aligned with its `bases`,
+        row r's at off[r]:off[r + 1], reversed - not complemented - where orientation is 1.  Needs the batch's qualities: an upload with
+        keep_quality=True, or attach_qualities.  Several batches' are joined by join_window_qualities."""
+        import torch
+
+        R = int(sg.read.numel()) if isinstance(sg.read, torch.Tensor) and sg.read.dim() == 1 else -1
+        if R < 0:
+            raise MtrError("the rows' read column must be a 1-D torch tensor")
+        ptrs = [self._gpu_column(sg.read, torch.int32, (R,), "the rows' read"), self._gpu_column(sg.orientation, torch.uint8, (R,), "the rows' orientation"),
+                self._gpu_column(sg.window, torch.int32, (R, 2), "the rows' window")]
+        dev = torch.device("cuda", self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        nb = C.c_int64()
+        call = self.lib.mtr_extract_window_qualities_device
+        self._check(call(self.h, *ptrs, R, stream, None, 0, C.byref(nb)), "mtr_extract_window_qualities_device")
+        T = int(nb.value)
+        qual = torch.empty(T, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the column on its own stream: torch's earlier use of the memory is done
+        if T:
+            self._check(call(self.h, *ptrs, R, stream, qual.data_ptr(), T, C.byref(nb)), "mtr_extract_window_qualities_device")
+        return qual
+
+    def allele_consensus_quality(self, sg, windows: GenotypeWindows, qual, calls: AlleleCalls, band_extra: int = 16, qual_cap: int = 40) -> AlleleConsensus:
+        """Quality-weighted allele consensus (mtr_allele_consensus_quality_device): allele_consensus - the same backbone, alignments, skip rule
+        and tie rules - with every vote weighted by its base's Phred value: a base of quality q weighs min(max(q, 1), qual_cap), a deletion or
+        the end of an insertion the lighter of the two bases beside it.  qual: the windows' qualities (genotype_window_qualities, or
+        join_window_qualities'), aligned with windows.bases.  `votes` holds weight sums; format_allele_consensus, window_structure and
+        window_edits take the result as they take allele_consensus'.  qual_cap = 1 is allele_consensus."""
+        import torch
+
+        if isinstance(qual_cap, bool) or not isinstance(qual_cap, (int, np.integer)):
+            raise MtrError(f"qual_cap must be an integer, got {qual_cap!r}")
+        if not isinstance(qual, torch.Tensor) or qual.dim() != 1:
+            raise MtrError("qual must be a 1-D torch tensor")
+        return self._allele_consensus(sg, windows, calls, band_extra, (qual, int(qual_cap)))
+
     def allele_consensus(self, sg, windows: GenotypeWindows, calls: AlleleCalls, band_extra: int = 16) -> AlleleConsensus:
         """Allele consensus (mtr_allele_consensus_device): each called allele's sequence by vote.  sg: the SparseGenotypes the calls were made of
         (one batch's, or join_sparse_genotypes'), sorted by (read, locus); windows: its rows' windows (genotype_windows, or join_windows'); calls:
@@ -1556,6 +1636,10 @@ class Engine:
         whose window, or the backbone's, exceeds 16384 bases is counted as skipped) and votes per backbone position for a base, a deletion or up
         to four inserted bases; the consensus is the plurality, ties to the backbone.  Needs no upload and no run and changes nothing either
         left.  Returns an AlleleConsensus of fresh tensors on this engine's device; stream handling as call_alleles'."""
+        return self._allele_consensus(sg, windows, calls, band_extra, None)
+
+    def _allele_consensus(self, sg, windows, calls, band_extra, weights):
+        """allele_consensus (weights None) and allele_consensus_quality (weights = (qual, qual_cap)): one argument list, one sizing call, one writing call"""
         import torch
 
         if isinstance(band_extra, bool) or not isinstance(band_extra, (int, np.integer)):
@@ -1575,14 +1659,20 @@ class Engine:
         dev = torch.device("cuda", self.device)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         nb = C.c_int64()
-        call = self.lib.mtr_allele_consensus_device
-        self._check(call(self.h, C.byref(src), int(band_extra), stream, None, C.byref(nb)), "mtr_allele_consensus_device")
+        if weights is None:
+            entry = "mtr_allele_consensus_device"
+            call = lambda s, extra, st, dst, out: self.lib.mtr_allele_consensus_device(self.h, s, extra, st, dst, out)      # noqa: E731
+        else:
+            entry = "mtr_allele_consensus_quality_device"
+            q, cap = col(weights[0], torch.uint8, (T,), "qual"), weights[1]
+            call = lambda s, extra, st, dst, out: self.lib.mtr_allele_consensus_quality_device(self.h, s, q, extra, cap, st, dst, out)      # noqa: E731
+        self._check(call(C.byref(src), int(band_extra), stream, None, C.byref(nb)), entry)
         L = int(nb.value)
         new = lambda dtype, n: torch.empty(n, dtype=dtype, device=dev)     # noqa: E731
         cons = AlleleConsensus(new(torch.int64, 2 * m + 1), new(torch.uint8, L), new(torch.int32, L), *[new(torch.int32, 2 * m) for _ in range(5)])
         torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
         dst = CConsensusDst(*[t.data_ptr() if t.numel() else None for t in cons], 2 * m, L)
-        self._check(call(self.h, C.byref(src), int(band_extra), stream, C.byref(dst), C.byref(nb)), "mtr_allele_consensus_device")
+        self._check(call(C.byref(src), int(band_extra), stream, C.byref(dst), C.byref(nb)), entry)
         return cons
 
     def call_alleles_by_sequence(self, sg, windows: GenotypeWindows, calls: AlleleCalls, max_dist: int = 32, min_support: int = 2, min_percent: int = 20,
@@ -2475,6 +2565,18 @@ def join_windows(parts) -> GenotypeWindows:
         offs.append((p.off if k == len(parts) - 1 else p.off[:-1]) + before)
         before += int(p.off[-1])
     return GenotypeWindows(_cat(offs), _cat([p.bases for p in parts]))
+
+
+def join_window_qualities(parts, windows: "GenotypeWindows | None" = None):
+    """Several batches' genotype_window_qualities, in the order of join_windows' parts, as one: concatenated.  windows: join_windows' result for
+    the same batches; given, the joined length must be its bases'.  Tensors or numpy arrays."""
+    parts = list(parts)
+    if not parts:
+        raise MtrError("nothing to join")
+    qual = _cat(parts)
+    if windows is not None and (len(qual) != int(windows.off[-1]) or len(qual) != len(windows.bases)):
+        raise MtrError(f"{len(qual)} qualities for windows of {int(windows.off[-1])} bases")
+    return qual
 
 
 def format_window_structure(structures, ws: WindowStructure, names=None) -> bytes:

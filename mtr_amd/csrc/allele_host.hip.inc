@@ -133,13 +133,15 @@ static mtr_status columns_begin(mtr_ctx *ctx, void *wait_stream, DevBuf<unsigned
     return MTR_OK;
 }
 
-extern "C" mtr_status mtr_extract_windows_device(mtr_ctx *ctx, const int32_t *row_read, const uint8_t *orientation, const int32_t *window, int64_t n_rows,
-                                                 void *wait_stream, const mtr_windows_dst *dst, int64_t *out_bases)
+// what the windows and their qualities share, up to the windows' offsets on the device (ctx->d_co_i64, [n_rows + 1]) and *out_bases = T
+static mtr_status windows_front(mtr_ctx *ctx, const int32_t *row_read, const uint8_t *orientation, const int32_t *window, int64_t n_rows, void *wait_stream, bool qualities,
+                                int64_t *out_bases)
 {
     if (!ctx || !out_bases) return MTR_ERR_BAD_ARG;
     *out_bases = 0;
     if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
     if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    if (qualities && ctx->qual_bytes <= 0) { ctx->err = "no qualities resident"; return MTR_ERR_BAD_ARG; }
     const int64_t R = n_rows;
     if (R < 0 || R > (int64_t)INT32_MAX) { ctx->err = "n_rows = " + std::to_string(R) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
     if (R > 0 && (!row_read || !orientation || !window)) { ctx->err = "row_read, orientation or window is NULL"; return MTR_ERR_BAD_ARG; }
@@ -167,13 +169,22 @@ extern "C" mtr_status mtr_extract_windows_device(mtr_ctx *ctx, const int32_t *ro
     }
     if (T < 0) { ctx->err = "the windows' scan failed on the device"; return MTR_ERR_HIP; }
     *out_bases = T;
+    return MTR_OK;
+}
+
+extern "C" mtr_status mtr_extract_windows_device(mtr_ctx *ctx, const int32_t *row_read, const uint8_t *orientation, const int32_t *window, int64_t n_rows,
+                                                 void *wait_stream, const mtr_windows_dst *dst, int64_t *out_bases)
+{
+    { mtr_status st = windows_front(ctx, row_read, orientation, window, n_rows, wait_stream, false, out_bases); if (st != MTR_OK) return st; }
+    const int64_t R = n_rows, T = *out_bases; const size_t nr = (size_t)R;
+    const int64_t *off = ctx->d_co_i64;
     if (!dst) return MTR_OK;
     if (dst->cap_rows < R) { ctx->err = "destination holds " + std::to_string(dst->cap_rows) + " rows, " + std::to_string(R) + " needed"; return MTR_ERR_OVERFLOW; }
     if (dst->cap_bases < T) { ctx->err = "destination holds " + std::to_string(dst->cap_bases) + " bases, " + std::to_string(T) + " needed"; return MTR_ERR_OVERFLOW; }
     if (!dst->win_off || (T > 0 && !dst->win_bases)) { ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG; }
     if (T > 0) {
         hipLaunchKernelGGL(mtr_k_win_gather, dim3((unsigned)std::min<int64_t>(R, CO_MAX_GRID)), dim3(64), 0, ctx->stream, row_read, orientation, window, R,
-                           (const uint32_t *)ctx->d_packed, (const int64_t *)ctx->d_woff, (const int64_t *)off, dst->win_bases);
+                           (const uint32_t *)ctx->d_packed, (const int64_t *)ctx->d_woff, off, dst->win_bases);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(dst->win_off, off, (nr + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
@@ -181,22 +192,96 @@ extern "C" mtr_status mtr_extract_windows_device(mtr_ctx *ctx, const int32_t *ro
     return MTR_OK;
 }
 
+extern "C" mtr_status mtr_extract_window_qualities_device(mtr_ctx *ctx, const int32_t *row_read, const uint8_t *orientation, const int32_t *window, int64_t n_rows,
+                                                          void *wait_stream, uint8_t *dst_qual, int64_t cap, int64_t *out_bases)
+{
+    { mtr_status st = windows_front(ctx, row_read, orientation, window, n_rows, wait_stream, true, out_bases); if (st != MTR_OK) return st; }
+    const int64_t R = n_rows, T = *out_bases;
+    if (!dst_qual) return MTR_OK;
+    if (cap < T) { ctx->err = "destination holds " + std::to_string(cap) + " bases, " + std::to_string(T) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (T > 0) {
+        hipLaunchKernelGGL(mtr_k_win_qual, dim3((unsigned)std::min<int64_t>(R, CO_MAX_GRID)), dim3(64), 0, ctx->stream, row_read, orientation, window, R,
+                           (const uint8_t *)ctx->d_qual, (const int64_t *)ctx->d_qual_off, (const int64_t *)ctx->d_co_i64, dst_qual);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}
+
+// ---- the batch's qualities from the caller (quality.hip.inc) ------------------------------------------------------------------------------------
+// the batch's place for them: d_qual_off = the exclusive sum of the resident lengths, d_qual sized for all (+ 4: the last aligned dword); enqueues
+static mtr_status qualities_layout(mtr_ctx *ctx, int64_t &total)
+{
+    const size_t n = (size_t)ctx->n_reads;
+    total = 0;
+    for (int32_t len : ctx->lens) total += len;
+    HIPCHK(ctx->d_qual.ensure((size_t)total + 4)); HIPCHK(ctx->d_qual_off.ensure((n + 1) * 8));
+    hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)ctx->d_lens, (int64_t)n, (int64_t *)ctx->d_qual_off);
+    HIPCHK(hipGetLastError());
+    return MTR_OK;
+}
+extern "C" mtr_status mtr_keep_qualities(mtr_ctx *ctx, int32_t on)
+{
+    if (!ctx) return MTR_ERR_BAD_ARG;
+    ctx->keep_qual = on != 0;
+    return MTR_OK;
+}
+extern "C" mtr_status mtr_qualities_resident(const mtr_ctx *ctx, int64_t *out_bytes)
+{
+    if (!ctx || !out_bytes) return MTR_ERR_BAD_ARG;
+    *out_bytes = ctx->n_reads > 0 ? ctx->qual_bytes : 0;
+    return MTR_OK;
+}
+extern "C" mtr_status mtr_attach_qualities_device(mtr_ctx *ctx, const uint8_t *d_qual, int64_t n_bytes, const int64_t *offsets, void *wait_stream)
+{
+    if (!ctx) return MTR_ERR_BAD_ARG;
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
+    if (ctx->n_reads <= 0) { ctx->err = "no batch uploaded"; return MTR_ERR_BAD_ARG; }
+    if (!d_qual || !offsets) { ctx->err = "d_qual or offsets is NULL"; return MTR_ERR_BAD_ARG; }
+    if (n_bytes <= 0) { ctx->err = "n_bytes " + std::to_string(n_bytes) + " <= 0"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    { mtr_status st = check_device_ptr(ctx, d_qual, n_bytes, "d_qual", "n_bytes"); if (st != MTR_OK) return st; }
+    const size_t n = (size_t)ctx->n_reads;
+    for (size_t i = 0; i < n; i++)
+        if (offsets[i] < 0 || offsets[i] > n_bytes - ctx->lens[i]) {
+            ctx->err = "read " + std::to_string(i) + ": values " + std::to_string(offsets[i]) + " .. +" + std::to_string(ctx->lens[i]) + " outside d_qual's " + std::to_string(n_bytes) + " bytes";
+            return MTR_ERR_BAD_ARG;
+        }
+    HIPCHK(ctx->d_toff.ensure(n * 8));
+    HIPCHK(copy_sync(ctx, ctx->d_toff, offsets, n * 8, hipMemcpyHostToDevice));
+    { mtr_status st = wait_for_stream(ctx, wait_stream); if (st != MTR_OK) return st; }               // the values come from the caller's stream
+    ctx->qual_bytes = 0;                                                                                // (what was there is being overwritten)
+    int64_t total = 0;
+    { mtr_status st = qualities_layout(ctx, total); if (st != MTR_OK) return st; }
+    hipLaunchKernelGGL(mtr_k_qual_gather<false>, dim3((unsigned)std::min<int64_t>(ctx->n_reads, QL_MAX_GRID)), dim3(64), 0, ctx->stream, d_qual, (const uint32_t *)nullptr,
+                       (const int64_t *)ctx->d_toff, (const int32_t *)ctx->d_lens, (const int64_t *)ctx->d_qual_off, (int32_t)ctx->n_reads, (uint8_t *)ctx->d_qual);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->qual_bytes = total;
+    return MTR_OK;
+}
+
 // one bucket's alignments: the grid is bounded by the scratch it may take (each wavefront its own directions, sized by the bucket's longest task)
+// qual: the weighted vote's two arguments, NULL for the unweighted one
+struct ConsWeights { const uint8_t *win_qual; int32_t qual_cap; };
 template <int CPL>
-static mtr_status cons_align_bucket(mtr_ctx *ctx, const ConsArgs &a, int bucket, unsigned n_tasks, unsigned longest)
+static mtr_status cons_align_bucket(mtr_ctx *ctx, const ConsArgs &a, const ConsWeights *qual, int bucket, unsigned n_tasks, unsigned longest)
 {
     if (n_tasks == 0) return MTR_OK;
     const int64_t words = ((int64_t)(longest >> 4) + 1) * CPL * 64;
     const int64_t cap_words = (int64_t)(std::min(ctx->sw.scratch_max_gb, 0.25) * (double)(1ll << 30) / 4.0);      // a quarter of a GB at the most, under the context's scratch cap
     const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_tasks, (int64_t)ctx->n_cu * 16), cap_words / words));
     HIPCHK(ctx->d_co_dirs.ensure((size_t)(grid * words) * 4));
-    hipLaunchKernelGGL(mtr_k_cons_align<CPL>, dim3((unsigned)grid), dim3(64), 0, ctx->stream, a, bucket, n_tasks, (uint32_t *)ctx->d_co_dirs, words);
+    if (qual) hipLaunchKernelGGL(mtr_k_cq_align<CPL>, dim3((unsigned)grid), dim3(64), 0, ctx->stream, ConsQArgs{ a, qual->win_qual, qual->qual_cap }, bucket, n_tasks, (uint32_t *)ctx->d_co_dirs, words);
+    else hipLaunchKernelGGL(mtr_k_cons_align<CPL>, dim3((unsigned)grid), dim3(64), 0, ctx->stream, a, bucket, n_tasks, (uint32_t *)ctx->d_co_dirs, words);
     HIPCHK(hipGetLastError());
     return MTR_OK;
 }
 
-extern "C" mtr_status mtr_allele_consensus_device(mtr_ctx *ctx, const mtr_consensus_src *src, int32_t band_extra, void *wait_stream,
-                                                  const mtr_consensus_dst *dst, int64_t *out_bases)
+// the allele consensus, unweighted (qual == NULL) or quality-weighted: the checks, the lists and the alignments' schedule are one; the votes' table
+// (BA_TAB or BAQ_TAB counters a position), the walk and the emission are the vote's own kernels
+static mtr_status allele_consensus(mtr_ctx *ctx, const mtr_consensus_src *src, const ConsWeights *qual, int32_t band_extra, void *wait_stream,
+                                   const mtr_consensus_dst *dst, int64_t *out_bases)
 {
     if (!ctx || !out_bases) return MTR_ERR_BAD_ARG;
     *out_bases = 0;
@@ -208,12 +293,17 @@ extern "C" mtr_status mtr_allele_consensus_device(mtr_ctx *ctx, const mtr_consen
     if (S < 0 || S > (int64_t)INT32_MAX) { ctx->err = "n_support = " + std::to_string(S) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
     if (NB < 0 || NB > (int64_t)INT32_MAX) { ctx->err = "n_bases = " + std::to_string(NB) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
     if (band_extra < 0 || band_extra > MTR_CONS_MAX_EXTRA) { ctx->err = "band_extra = " + std::to_string(band_extra) + " outside 0.." + std::to_string(MTR_CONS_MAX_EXTRA); return MTR_ERR_BAD_ARG; }
-    if (!src->win_off || !src->support_off || !src->zygosity || (R > 0 && (!src->row_read || !src->row_locus)) || (NB > 0 && !src->win_bases) ||
+    if (qual && (qual->qual_cap < 1 || qual->qual_cap > MTR_CONSQ_MAX_CAP)) { ctx->err = "qual_cap = " + std::to_string(qual->qual_cap) + " outside 1.." + std::to_string(MTR_CONSQ_MAX_CAP); return MTR_ERR_BAD_ARG; }
+    if (qual && S * qual->qual_cap >= (1ll << 31)) {
+        ctx->err = "n_support " + std::to_string(S) + " x qual_cap " + std::to_string(qual->qual_cap) + " reaches 2^31: the weight sums are int32"; return MTR_ERR_BAD_ARG;
+    }
+    if (!src->win_off || !src->support_off || !src->zygosity || (R > 0 && (!src->row_read || !src->row_locus)) || (NB > 0 && (!src->win_bases || (qual && !qual->win_qual))) ||
         (S > 0 && (!src->read || !src->allele))) { ctx->err = "an input column is NULL"; return MTR_ERR_BAD_ARG; }
     HIPCHK(hipSetDevice(ctx->device));
     {
-        const DeviceCol cols[8] = {
+        const DeviceCol cols[9] = {
             { src->row_read, R * 4, "src->row_read" }, { src->row_locus, R * 4, "src->row_locus" }, { src->win_off, (R + 1) * 8, "src->win_off" }, { src->win_bases, NB, "src->win_bases" },
+            { qual ? qual->win_qual : nullptr, qual ? NB : 0, "win_qual" },
             { src->support_off, ((int64_t)n_loci + 1) * 8, "src->support_off" }, { src->read, S * 4, "src->read" }, { src->allele, S, "src->allele" }, { src->zygosity, n_loci, "src->zygosity" } };
         { mtr_status st = check_device_cols(ctx, cols, "the column's bytes"); if (st != MTR_OK) return st; }
     }
@@ -259,13 +349,15 @@ extern "C" mtr_status mtr_allele_consensus_device(mtr_ctx *ctx, const mtr_consen
     HIPCHK(hipMemcpyAsync(&tab_positions, a.tab_off + G, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(copy_sync(ctx, state, a.state, sizeof state, hipMemcpyDeviceToHost));
     if (tab_positions < 0 || (int64_t)state[0] + state[1] > S || state[2] > 2 * BA_MAX_WINDOW || state[3] > 2 * BA_MAX_WINDOW) { ctx->err = "the consensus' task lists failed on the device"; return MTR_ERR_HIP; }
-    HIPCHK(ctx->d_co_tab.ensure(std::max<size_t>((size_t)tab_positions * BA_TAB, 1) * 4));
+    const size_t tab_ints = (size_t)tab_positions * (qual ? BAQ_TAB : BA_TAB);
+    HIPCHK(ctx->d_co_tab.ensure(std::max<size_t>(tab_ints, 1) * 4));
     a.tab = ctx->d_co_tab;
-    if (tab_positions > 0) HIPCHK(hipMemsetAsync(a.tab, 0, (size_t)tab_positions * BA_TAB * 4, ctx->stream));
-    { mtr_status st = cons_align_bucket<1>(ctx, a, 0, state[0], state[2]); if (st != MTR_OK) return st; }
-    { mtr_status st = cons_align_bucket<2>(ctx, a, 1, state[1], state[3]); if (st != MTR_OK) return st; }
+    if (tab_positions > 0) HIPCHK(hipMemsetAsync(a.tab, 0, tab_ints * 4, ctx->stream));
+    { mtr_status st = cons_align_bucket<1>(ctx, a, qual, 0, state[0], state[2]); if (st != MTR_OK) return st; }
+    { mtr_status st = cons_align_bucket<2>(ctx, a, qual, 1, state[1], state[3]); if (st != MTR_OK) return st; }
     const dim3 per_allele((unsigned)std::min<int64_t>((int64_t)G, CO_MAX_GRID));
-    hipLaunchKernelGGL(mtr_k_cons_emit<0>, per_allele, blk, 0, ctx->stream, a);
+    if (qual) hipLaunchKernelGGL(mtr_k_cq_emit<0>, per_allele, blk, 0, ctx->stream, ConsQArgs{ a, qual->win_qual, qual->qual_cap });
+    else hipLaunchKernelGGL(mtr_k_cons_emit<0>, per_allele, blk, 0, ctx->stream, a);
     hipLaunchKernelGGL(mtr_k_scan_offsets<int32_t>, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t *)a.cons_len, (int64_t)G, a.cons_off);
     HIPCHK(hipGetLastError());
     int64_t T = 0;
@@ -279,13 +371,29 @@ extern "C" mtr_status mtr_allele_consensus_device(mtr_ctx *ctx, const mtr_consen
         ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
     }
     a.bases = dst->bases; a.votes = dst->votes;
-    if (T > 0) { hipLaunchKernelGGL(mtr_k_cons_emit<1>, per_allele, blk, 0, ctx->stream, a); HIPCHK(hipGetLastError()); }
+    if (T > 0) {
+        if (qual) hipLaunchKernelGGL(mtr_k_cq_emit<1>, per_allele, blk, 0, ctx->stream, ConsQArgs{ a, qual->win_qual, qual->qual_cap });
+        else hipLaunchKernelGGL(mtr_k_cons_emit<1>, per_allele, blk, 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(hipMemcpyAsync(dst->cons_off, a.cons_off, (G + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
     const struct { int32_t *to; const int32_t *from; } cols[5] = { { dst->backbone_read, a.bb_read }, { dst->backbone_len, a.bb_len }, { dst->members, a.members }, { dst->aligned, a.aligned },
                                                                    { dst->skipped, a.skipped } };
     for (const auto &c : cols) HIPCHK(hipMemcpyAsync(c.to, c.from, G * 4, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
+}
+
+extern "C" mtr_status mtr_allele_consensus_device(mtr_ctx *ctx, const mtr_consensus_src *src, int32_t band_extra, void *wait_stream,
+                                                  const mtr_consensus_dst *dst, int64_t *out_bases)
+{
+    return allele_consensus(ctx, src, nullptr, band_extra, wait_stream, dst, out_bases);
+}
+extern "C" mtr_status mtr_allele_consensus_quality_device(mtr_ctx *ctx, const mtr_consensus_src *src, const uint8_t *win_qual, int32_t band_extra, int32_t qual_cap,
+                                                          void *wait_stream, const mtr_consensus_dst *dst, int64_t *out_bases)
+{
+    const ConsWeights qual = { win_qual, qual_cap };
+    return allele_consensus(ctx, src, &qual, band_extra, wait_stream, dst, out_bases);
 }
 
 // ---- the motif structure of windows (window_structure.hip.inc) ---------------------------------------------------------------------------

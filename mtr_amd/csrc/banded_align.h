@@ -151,3 +151,68 @@ BA_HD int ba_emit(const int32_t *t, int32_t j, int bb, int32_t N, uint8_t *sym, 
     }
     return has_base | (n_ins << 1);
 }
+
+// ---- the quality-weighted vote (include/mtr_hip.h, "quality-weighted allele consensus") --------------------------------------------------------
+// The alignment is the one above - band, D, directions, schedule -; only what a step of the walk adds to the table changes, and the table gets
+// one more kind of counter: end[L], the boundary weight of a member whose insertion run behind the position has exactly L < BA_INS_SLOTS bases.
+#define BAQ_MAX_CAP 93             // MTR_CONSQ_MAX_CAP
+#define BAQ_TAB (BA_TAB + BA_INS_SLOTS)     // int32 per backbone position 0 .. m: base[4], del, ins[slot][4], end[4]
+#define BAQ_TAB_END (BA_TAB_INS + 4 * BA_INS_SLOTS)
+
+// the weight of a base of quality q
+BA_HD int32_t baq_weight(int32_t q, int32_t cap) { return q < 1 ? 1 : q > cap ? cap : q; }
+// the gap weight at boundary i (0 .. n) of a window of n bases whose qualities are Q: the lighter of the two bases beside it, the one that exists
+// at the ends, 1 for an empty window
+BA_HD int32_t baq_gap(const uint8_t *Q, int32_t n, int32_t i, int32_t cap)
+{
+    if (n == 0) return 1;
+    const int32_t a = baq_weight(Q[i > 0 ? i - 1 : 0], cap), b = baq_weight(Q[i < n ? i : n - 1], cap);
+    return a < b ? a : b;
+}
+
+// the walk from (n, m) to (0, 0), column by column: in column j the path's rows are lo .. hi, its run of up steps inserts W[lo .. hi) behind
+// backbone position j, and it leaves column j >= 1 from (lo, j) by diag or left.  dir_at as for ba_walk; vote(x, w) adds w to counter x of the
+// backbone's table (position j's counters are x = j * BAQ_TAB ..).  Q: the qualities of W.
+template <class DirAt, class Vote>
+BA_HD void baq_walk(int32_t n, int32_t m, const uint8_t *W, const uint8_t *Q, int32_t cap, DirAt dir_at, Vote vote)
+{
+    int32_t i = n;
+    for (int32_t j = m; j >= 0; j--) {
+        const int32_t hi = i;
+        int d = BA_LEFT;                                                        // of (lo, j) once the run has ended above row 0
+        while (i > 0) { d = j == 0 ? BA_UP : dir_at(i, j); if (d != BA_UP) break; i--; }
+        const int64_t at = (int64_t)j * BAQ_TAB;
+        for (int32_t k = 0; k < BA_INS_SLOTS && i + k < hi; k++) vote(at + BA_TAB_INS + 4 * k + W[i + k], baq_weight(Q[i + k], cap));
+        if (hi - i < BA_INS_SLOTS) vote(at + BAQ_TAB_END + (hi - i), baq_gap(Q, n, hi, cap));
+        if (j == 0) break;
+        if (i > 0 && d == BA_DIAG) { vote(at + W[i - 1], baq_weight(Q[i - 1], cap)); i--; }
+        else vote(at + BA_TAB_DEL, baq_gap(Q, n, i, cap));
+    }
+}
+
+// what backbone position j (0 .. m) emits: t = its BAQ_TAB counters (the aligned members' weights), bb = B[j - 1] and wbb = its weight (any
+// values for j = 0), gap = the backbone's own gap weight at boundary j.  The backbone's votes are added here.  sym / votes and the result as
+// for ba_emit; votes are weight sums.
+BA_HD int baq_emit(const int32_t *t, int32_t j, int bb, int32_t wbb, int32_t gap, uint8_t *sym, int32_t *votes)
+{
+    int has_base = 0, n_ins = 0;
+    sym[0] = 0; votes[0] = 0;
+    if (j >= 1) {
+        int best = 0; int32_t bv = -1;
+        for (int c = 0; c < 4; c++) { const int32_t v = t[c] + (c == bb ? wbb : 0); if (v > bv) { bv = v; best = c; } }
+        if (t[bb] + wbb == bv) best = bb;                                       // a tie goes to the backbone's base
+        if (!(t[BA_TAB_DEL] > bv)) { sym[0] = (uint8_t)best; votes[0] = bv; has_base = 1; }
+    }
+    bool open = true;
+    int32_t none = gap;
+    for (int k = 0; k < BA_INS_SLOTS; k++) {
+        const int32_t *ins = t + BA_TAB_INS + 4 * k;
+        int best = 0; int32_t mx = -1;
+        for (int c = 0; c < 4; c++) if (ins[c] > mx) { mx = ins[c]; best = c; }
+        none += t[BAQ_TAB_END + k];
+        open = open && mx > none;                                               // the first slot not emitted ends the junction
+        sym[1 + k] = (uint8_t)best; votes[1 + k] = mx;
+        n_ins += open ? 1 : 0;
+    }
+    return has_base | (n_ins << 1);
+}

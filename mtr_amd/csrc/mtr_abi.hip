@@ -52,6 +52,8 @@
 #include "catalog_build.hip.inc"
 #include "allele_call.hip.inc"
 #include "consensus.hip.inc"
+#include "quality.hip.inc"
+#include "consensus_quality.hip.inc"
 #include "window_structure.hip.inc"
 #include "window_structure_args.h"
 #include "window_edits.hip.inc"
@@ -304,6 +306,9 @@ struct mtr_ctx {
     // mtr_upload_fasta_device: the parsed reads on the device, and the host copies of their index (mtr_fasta_index)
     DevBuf<uint8_t> d_fa_text, d_fa_ids; DevBuf<int64_t> d_fa_off; DevBuf<int32_t> d_fa_lens;
     bool fa_indexed = false; std::vector<int32_t> fa_lens; std::vector<int64_t> fa_idoff; std::vector<char> fa_ids;
+    // the qualities of the resident batch (quality.hip.inc): keep_qual = mtr_keep_qualities' option; qual_bytes > 0: d_qual holds that many Phred
+    // values, read r's at d_qual_off[r] (the exclusive sum of the lengths, [n_reads + 1]); free_batch drops them with the batch
+    bool keep_qual = false; int64_t qual_bytes = 0; DevBuf<uint8_t> d_qual; DevBuf<int64_t> d_qual_off;
     // test entry points
     DevBuf<int32_t> d_t_i32, d_t_out; DevBuf<uint8_t> d_t_units, d_t_text; DevBuf<int64_t> d_t_i64;
 };
@@ -383,7 +388,7 @@ static hipError_t copy_sync(mtr_ctx *ctx, void *dst, const void *src, size_t byt
 }
 
 // forget the resident batch (its buffers stay allocated for the next one)
-static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->mo_ready = false; ctx->ml_ready = false; ctx->gc.ready = false; ctx->pc.ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); }
+static void free_batch(mtr_ctx *ctx) { ctx->n_reads = 0; ctx->ran = false; ctx->rep_ready = false; ctx->ra_ready = false; ctx->rt_ready = false; ctx->mo_ready = false; ctx->ml_ready = false; ctx->gc.ready = false; ctx->pc.ready = false; ctx->run_status = MTR_OK; ctx->first_failed = -1; ctx->ovf_reads.clear(); ctx->qual_bytes = 0; }
 
 extern "C" int mtr_abi_version(void) { return MTR_ABI_VERSION; }
 
@@ -2034,6 +2039,19 @@ extern "C" mtr_status mtr_parse_fastq_device_window(mtr_ctx *ctx, const uint8_t 
     return parse_fasta(ctx, true, d_fastq, n_bytes, more_follows, wait_stream, dst, info);
 }
 
+// behind a successful FASTQ upload: read r's quality line, line 4r + 3 of the table the index left, becomes its stored values
+static mtr_status gather_fastq_qualities(mtr_ctx *ctx, const FastqArgs &q, const uint8_t *d_fastq)
+{
+    int64_t total = 0;
+    { mtr_status st = qualities_layout(ctx, total); if (st != MTR_OK) return st; }
+    hipLaunchKernelGGL(mtr_k_qual_gather<true>, dim3((unsigned)std::min<int64_t>(ctx->n_reads, QL_MAX_GRID)), dim3(64), 0, ctx->stream, d_fastq, (const uint32_t *)q.l_start,
+                       (const int64_t *)nullptr, (const int32_t *)ctx->d_lens, (const int64_t *)ctx->d_qual_off, (int32_t)ctx->n_reads, (uint8_t *)ctx->d_qual);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->qual_bytes = total;
+    return MTR_OK;
+}
+
 // fastq: the reads stay where they are, in the file - a sequence line is contiguous there -, and the packing kernel reads them from it
 static mtr_status upload_fasta(mtr_ctx *ctx, mtr_file_state *fs, bool fastq, const uint8_t *d_fasta, int64_t n_bytes, int32_t more, void *wait_stream,
                                mtr_fasta_info *info)
@@ -2069,6 +2087,7 @@ static mtr_status upload_fasta(mtr_ctx *ctx, mtr_file_state *fs, bool fastq, con
     const DeviceText dt = { fastq ? d_fasta : (const uint8_t *)ctx->d_fa_text, fastq ? n_bytes : f.n_bases, offs.data(), MTR_TEXT_ASCII, ctx->stream };
     const mtr_status st = upload_text(ctx, fs, dt, ctx->fa_lens.data(), f.n_reads);
     if (st != MTR_OK) ctx->fa_indexed = false;                    // as a refused mtr_upload_batch_device: no batch is left
+    if (st == MTR_OK && fastq && ctx->keep_qual) return gather_fastq_qualities(ctx, p.q, d_fasta);
     return st;
 }
 extern "C" mtr_status mtr_upload_fasta_device(mtr_ctx *ctx, const uint8_t *d_fasta, int64_t n_bytes, void *wait_stream, mtr_fasta_info *info)

@@ -1083,6 +1083,72 @@ mtr_status mtr_call_alleles_sequence_device(mtr_ctx *ctx, const mtr_consensus_sr
                                             void *wait_stream, int64_t *out_support, int64_t *out_pairs);
 mtr_status mtr_call_alleles_sequence_copy_device(mtr_ctx *ctx, const mtr_seq_calls_dst *dst);
 
+/* ---- genotype quality: each read scored against both allele sequences, the scores reduced to genotype likelihoods ------------------------------
+ * The calls say "two alleles, these"; the consensus says what they are.  This call says how sure that is: per read how much better it fits one
+ * allele's sequence than the other's, per locus the likelihoods of the genotypes 0/0, 0/1 and 1/1 on the Phred scale (a VCF's PL and GQ).  The
+ * reference has nothing of this kind; the definition is this project's own.  Every output is an exact integer and none depends on the order in
+ * which the device worked.
+ * Input, all DEVICE memory: mtr_consensus_src exactly as mtr_allele_consensus_device takes it - rows ascending by (read, locus), windows,
+ * support_off, read, allele, zygosity; win_qual [n_bases] aligned with win_bases, NULL meaning that every quality is qual_cap; the alleles'
+ * sequences cons_off [2 * n_loci + 1], cons_bases [n_cons] with the allele index A = 2 * locus + a, as the consensus writes them.  Parameters
+ * mtr_gq_params { band_extra 0..MTR_CONS_MAX_EXTRA, qual_cap 1..MTR_CONSQ_MAX_CAP, gap_cap 1..qual_cap, read_cap 1..MTR_GQ_MAX_READ_CAP = 2^20 }.
+ * The definition:
+ *   alleles     allele a of locus l exists iff zygosity[l] > a.  The spans of alleles that do not exist are not read
+ *   weights     omega[i] = min(max(q_i, 1), qual_cap) for the base of quality q_i; gamma(i), 0 <= i <= n, the gap weight of the quality-weighted
+ *               consensus: the lighter of the two bases beside boundary i, the one that exists at the ends, 1 for an empty window
+ *   score       s(e, a) of support entry e (window W of n bases, found by bisection over (read, locus) as in the consensus) against existing
+ *               allele a (sequence C of m bases): over the consensus' band - cells (i, j) exist iff dlo <= j - i <= dhi, dlo = min(0, m - n) -
+ *               band_extra, dhi = max(0, m - n) + band_extra; the band is part of the definition - D(0, 0) = 0, else D(i, j) is the minimum of
+ *               diag = D(i-1, j-1) + (W[i-1] != C[j-1] ? omega[i-1] : 0), up = D(i-1, j) + min(omega[i-1], gap_cap), left = D(i, j-1) +
+ *               min(gamma(i), gap_cap).  s = D(n, m), an int32: at most 32 768 steps of at most 93
+ *   scored      an entry is scored iff for every existing allele of its locus the consensus' skip rule (n or m above MTR_CONS_MAX_WINDOW, or
+ *               |m - n| + 2 * band_extra + 1 > MTR_CONS_MAX_BAND) is false.  An entry that is not scored has s = -1 against both alleles and
+ *               takes no part in any sum.  A locus of zygosity 0 scores nothing
+ *   per entry   score [S, 2] int32, -1 where there is none.  Zygosity 2 and scored: best [S] uint8 is 0 if s0 < s1, 1 if s1 < s0, the entry's own
+ *               allele on a tie; margin [S] int32 is |s0 - s1|.  Zygosity 1 and scored: best = 0, margin = 0.  Otherwise best is the entry's
+ *               allele, margin = 0
+ *   per locus   c(x) = min(x, read_cap), x0 = c(s0), x1 = c(s1); T = {3, 3, 2, 2, 1, 1, 1, 1, 1, 1}, T[d] = 0 for d >= 10 - 10 log10(1 +
+ *               10^(-d/10)) rounded, the integer form of a read drawn from either allele with probability one half; h = min(x0, x1) + 3 -
+ *               T[min(|x0 - x1|, 10)].  Zygosity 2: raw [n_loci, 3] int64 is the sum over the scored entries of (x0, h, x1), for the genotypes
+ *               0/0, 0/1 and 1/1; pl [n_loci, 3] int64 = raw - min(raw); gt [n_loci] uint8 is the genotype of least raw (0, 1, 2 in that
+ *               order of genotypes), ties in the order 0/1, 0/0, 1/1; gq [n_loci] int64 is the least pl among the other two.  Zygosity 1: raw =
+ *               (sum of x0, -1, -1), pl = (0, -1, -1), gt = 0, gq = -1.  Zygosity 0: raw and pl all -1, gt = 255, gq = -1.  scored and
+ *               unscored [n_loci] int32 count the locus' entries either way (both 0 under zygosity 0)
+ * With qual_cap = gap_cap = 1 every s is the consensus' unit-cost banded distance D(n, m), whatever the qualities.  With one constant quality c <=
+ * gap_cap and no empty window every s is c times that.
+ * All sizes follow from the input: one call, no size call.  Checked in this order, each MTR_ERR_BAD_ARG naming the offender: NULL ctx; NULL src,
+ * prm or dst; n_loci < 1 or above 2^30 - 1, n_rows, n_support, n_bases or n_cons outside 0..2^31 - 1; band_extra, qual_cap, gap_cap, read_cap in
+ * this order; a NULL input column that would be read (cons_off always, cons_bases with n_cons > 0; win_qual may be NULL); an input column that is
+ * not device memory of the context's GPU or runs past its allocation; then on the device the rows' order, the offset columns, a zygosity above
+ * 2, an entry without a row, an allele column that is not 0 .. 0 1 .. 1 within a locus, a cons_off that does not ascend from 0 to n_cons (the
+ * smallest such allele index is named).  Then cap_support < n_support or cap_loci < n_loci: MTR_ERR_OVERFLOW; a NULL destination column (score,
+ * best and margin may be NULL only when n_support == 0), or one that is not device memory: MTR_ERR_BAD_ARG.  A failed call writes nothing.  The
+ * context's stream is synchronised before the call returns; wait_stream is the stream that wrote the columns, handled as
+ * mtr_upload_batch_device handles it.  The call needs no upload and touches nothing that a batch, a run or another call keeps.
+ * MTR_ABI_VERSION is unchanged by this entry: look for it by symbol. */
+#define MTR_GQ_MAX_READ_CAP (1 << 20)
+typedef struct mtr_gq_params {
+    int32_t band_extra;    /* the consensus' band */
+    int32_t qual_cap;      /* where a base's weight saturates */
+    int32_t gap_cap;       /* where a gap step's cost saturates */
+    int32_t read_cap;      /* where one read's score saturates in the locus' sums */
+} mtr_gq_params;
+typedef struct mtr_gq_dst {
+    int32_t *score;       /* [S * 2] */
+    uint8_t *best;        /* [S] */
+    int32_t *margin;      /* [S] */
+    int64_t *raw;         /* [n_loci * 3] */
+    int64_t *pl;          /* [n_loci * 3] */
+    uint8_t *gt;          /* [n_loci] */
+    int64_t *gq;          /* [n_loci] */
+    int32_t *scored;      /* [n_loci] */
+    int32_t *unscored;    /* [n_loci] */
+    int64_t  cap_support;
+    int64_t  cap_loci;
+} mtr_gq_dst;   /* caller-owned DEVICE memory */
+mtr_status mtr_genotype_quality_device(mtr_ctx *ctx, const mtr_consensus_src *src, const uint8_t *win_qual, const int64_t *cons_off, const uint8_t *cons_bases,
+                                       int64_t n_cons, const mtr_gq_params *prm, void *wait_stream, const mtr_gq_dst *dst);
+
 /* ---- several GPUs in ONE process: the one exchange of the path (ABI 5) --------------------------------------------------
  * Reads shard over the GPUs of a node (isolated semantics make every read an independent unit); what is left
  * of handle_one_file.c:281-287's loop across GPUs is ONE exchange: the record tables travel to the process that chains and

@@ -540,6 +540,31 @@ class SequenceCalls(NamedTuple):
     dist: "object"              # uint8 [P]: the upper triangle of D, row-major, pair (t < u) at pair_off[l] + t * S_l - t (t + 1) / 2 + (u - t - 1)
 
 
+class CGqParams(C.Structure):
+    """mtr_gq_params: the band and where a base's weight, a gap's cost and a read's score saturate"""
+    _fields_ = [("band_extra", C.c_int32), ("qual_cap", C.c_int32), ("gap_cap", C.c_int32), ("read_cap", C.c_int32)]
+
+
+class CGqDst(C.Structure):
+    """mtr_gq_dst: device pointers of the genotype quality's nine columns and their capacities"""
+    _fields_ = [("score", C.c_void_p), ("best", C.c_void_p), ("margin", C.c_void_p), ("raw", C.c_void_p), ("pl", C.c_void_p), ("gt", C.c_void_p), ("gq", C.c_void_p),
+                ("scored", C.c_void_p), ("unscored", C.c_void_p), ("cap_support", C.c_int64), ("cap_loci", C.c_int64)]
+
+
+class GenotypeQuality(NamedTuple):
+    """What Engine.genotype_quality made of every supporting read's score against both allele sequences, all on the engine's device.
+    include/mtr_hip.h ("genotype quality") defines every column."""
+    score: "object"     # int32 [S, 2]: the entry's quality-weighted distance to allele 0's and allele 1's sequence, -1 where there is none
+    best: "object"      # uint8 [S]: the allele the entry fits better, its own on a tie or without scores
+    margin: "object"    # int32 [S]: |score 0 - score 1|, 0 without two scores
+    raw: "object"       # int64 [m, 3]: the Phred-scaled sums for the genotypes 0/0, 0/1, 1/1; -1 where there is no such genotype
+    pl: "object"        # int64 [m, 3]: raw less its minimum (a VCF's PL)
+    gt: "object"        # uint8 [m]: 0 = 0/0, 1 = 0/1, 2 = 1/1, 255 = no call
+    gq: "object"        # int64 [m]: the least pl of the two other genotypes (a VCF's GQ), -1 without two alleles
+    scored: "object"    # int32 [m]: the locus' entries that were scored
+    unscored: "object"  # int32 [m]: those that were not (a window, an allele or a band beyond the limits)
+
+
 class CFastaInfo(C.Structure):
     """mtr_fasta_info: what a FASTA file in device memory holds"""
     _fields_ = [("n_reads", C.c_int32), ("end", C.c_int32), ("bad_char", C.c_int32), ("reserved", C.c_int32),
@@ -737,6 +762,9 @@ def load_library(path: str = LIB_PATH):
         lib.mtr_allele_consensus_quality_device.argtypes = [C.c_void_p, P(CConsensusSrc), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, P(CConsensusDst), P(C.c_int64)]
         for name in ("mtr_keep_qualities", "mtr_attach_qualities_device", "mtr_qualities_resident", "mtr_extract_window_qualities_device", "mtr_allele_consensus_quality_device"):
             getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "mtr_genotype_quality_device"):               # (likewise a build from before the genotype quality)
+        lib.mtr_genotype_quality_device.argtypes = [C.c_void_p, P(CConsensusSrc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, P(CGqParams), C.c_void_p, P(CGqDst)]
+        lib.mtr_genotype_quality_device.restype = C.c_int
     lib.mtr_test_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
     lib.mtr_test_catalog_stats.restype = C.c_int
     lib.mtr_test_partial_catalog_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
@@ -1719,6 +1747,48 @@ class Engine:
         self._check(self.lib.mtr_call_alleles_sequence_copy_device(self.h, C.byref(dst)), "mtr_call_alleles_sequence_copy_device")
         return sc
 
+    def genotype_quality(self, sg, windows: GenotypeWindows, qual, calls: AlleleCalls, cons: AlleleConsensus, band_extra: int = 16, qual_cap: int = 40,
+                         gap_cap: int = 20, read_cap: int = 60) -> "GenotypeQuality":
+        """Genotype quality (mtr_genotype_quality_device).  sg, windows and calls are allele_consensus' arguments, qual the windows' qualities
+        (genotype_window_qualities; None: every base weighs qual_cap), cons the alleles' sequences (allele_consensus' or
+        allele_consensus_quality's result over the same calls).  Every supporting read's window is aligned to both allele sequences of its
+        locus inside the consensus' band with the read's qualities as costs - a substitution costs min(max(q, 1), qual_cap), a gap step at
+        most gap_cap -; per read the better allele and the margin, per locus the sums of the scores (one read's capped at read_cap) for the
+        genotypes 0/0, 0/1, 1/1, and from them pl, gt and gq as a VCF words them.  The defaults are policy, not measured on a basecaller's
+        output.  Returns a GenotypeQuality of fresh tensors on this engine's device.  Needs no upload and no run and changes nothing either
+        left.  Stream handling as allele_consensus'."""
+        import torch
+
+        for name, v in (("band_extra", band_extra), ("qual_cap", qual_cap), ("gap_cap", gap_cap), ("read_cap", read_cap)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise MtrError(f"{name} must be an integer, got {v!r}")
+        if isinstance(sg.n_loci, bool) or not isinstance(sg.n_loci, (int, np.integer)) or sg.n_loci < 1:
+            raise MtrError(f"n_loci must be an integer >= 1, got {sg.n_loci!r}")
+        if not isinstance(sg.read, torch.Tensor) or sg.read.dim() != 1 or not isinstance(calls.read, torch.Tensor) or calls.read.dim() != 1:
+            raise MtrError("the rows' and the calls' read columns must be 1-D torch tensors")
+        if not isinstance(windows.bases, torch.Tensor) or windows.bases.dim() != 1 or not isinstance(cons.bases, torch.Tensor) or cons.bases.dim() != 1:
+            raise MtrError("the windows' and the consensus' bases must be 1-D torch tensors")
+        if qual is not None and (not isinstance(qual, torch.Tensor) or qual.dim() != 1):
+            raise MtrError("qual must be a 1-D torch tensor or None")
+        R, S, T, m, L = int(sg.read.numel()), int(calls.read.numel()), int(windows.bases.numel()), int(sg.n_loci), int(cons.bases.numel())
+        col = self._gpu_column
+        src = CConsensusSrc(col(sg.read, torch.int32, (R,), "the rows' read"), col(sg.locus, torch.int32, (R,), "the rows' locus"),
+                            col(windows.off, torch.int64, (R + 1,), "the windows' off"), col(windows.bases, torch.uint8, (T,), "the windows' bases"),
+                            col(calls.support_off, torch.int64, (m + 1,), "the calls' support_off"), col(calls.read, torch.int32, (S,), "the calls' read"),
+                            col(calls.allele, torch.uint8, (S,), "the calls' allele"), col(calls.zygosity, torch.uint8, (m,), "the calls' zygosity"), R, T, S, m)
+        q = None if qual is None else col(qual, torch.uint8, (T,), "qual")
+        cons_off, cons_bases = col(cons.off, torch.int64, (2 * m + 1,), "the consensus' off"), col(cons.bases, torch.uint8, (L,), "the consensus' bases")
+        prm = CGqParams(int(band_extra), int(qual_cap), int(gap_cap), int(read_cap))
+        dev = torch.device("cuda", self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)     # noqa: E731
+        gq = GenotypeQuality(new(torch.int32, S, 2), new(torch.uint8, S), new(torch.int32, S), new(torch.int64, m, 3), new(torch.int64, m, 3), new(torch.uint8, m),
+                             new(torch.int64, m), new(torch.int32, m), new(torch.int32, m))
+        torch.cuda.current_stream(dev).synchronize()            # the library writes the columns on its own stream: torch's earlier use of the memory is done
+        dst = CGqDst(*[t.data_ptr() if t.numel() else None for t in gq], S, m)
+        self._check(self.lib.mtr_genotype_quality_device(self.h, C.byref(src), q, cons_off, cons_bases, L, C.byref(prm), stream, C.byref(dst)), "mtr_genotype_quality_device")
+        return gq
+
     def _window_args(self, structures, off, bases, which, gain, mismatch, indel):
         """what window_structure and window_edits hand to the library for their common arguments, in the calls' order up to wait_stream: the
         host arrays of the structures (kept alive by the caller through the returned tuple), the device columns, N, T, the scores, the stream"""
@@ -2526,6 +2596,55 @@ def format_sequence_calls(loci, sc: SequenceCalls) -> bytes:
             cols += [str(int(medoid[k, a])), f"{sum(mine)}/{len(mine)}"]
         out.append(lines[k] + b"\t" + "\t".join(cols).encode() + b"\n")
     return b"".join(out)
+
+
+def format_genotype_quality(loci, calls: AlleleCalls, gq: GenotypeQuality) -> bytes:
+    """The result of Engine.genotype_quality as text: format_allele_calls' line per locus, then the genotype (0/0, 0/1, 1/1, or ./. without a
+    call), gq, the three pl joined by commas, and scored/unscored.
+    loci: what genotype_loci was given; calls: the calls that were scored; gq: genotype_quality's result (tensors or numpy)."""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    lines = format_allele_calls(loci, calls).split(b"\n")[:-1]
+    m = len(lines)
+    gt, q, pl = host(gq.gt).reshape(-1), host(gq.gq).reshape(-1), host(gq.pl).reshape(-1, 3)
+    scored, unscored = host(gq.scored).reshape(-1), host(gq.unscored).reshape(-1)
+    if not (len(gt) == len(q) == len(pl) == len(scored) == len(unscored) == m):
+        raise MtrError(f"{len(gt)} genotypes for {m} loci")
+    names = {0: "0/0", 1: "0/1", 2: "1/1"}
+    out = []
+    for k in range(m):
+        cols = [names.get(int(gt[k]), "./."), str(int(q[k])), ",".join(str(int(v)) for v in pl[k]), f"{int(scored[k])}/{int(unscored[k])}"]
+        out.append(lines[k] + b"\t" + "\t".join(cols).encode() + b"\n")
+    return b"".join(out)
+
+
+def with_reassigned_alleles(calls: AlleleCalls, gq: GenotypeQuality) -> AlleleCalls:
+    """The calls with every read moved to the allele whose sequence it fits better (gq.best) - the input of a second consensus round.  It
+    applies to every locus of zygosity 2 whose best column leaves both sides non-empty: the entries are stably partitioned by best, allele =
+    best, call_support is recounted and call[a] is the value at position (n_a - 1) / 2 of allele a's list (the consensus' backbone rule); cost
+    is unchanged.  Every other locus is unchanged.  Torch ops only, on whatever device the tensors are on; allele_consensus takes the result
+    as it is."""
+    import torch
+
+    off, allele, zyg = calls.support_off, calls.allele, calls.zygosity
+    S, m = int(allele.numel()), int(zyg.numel())
+    if int(gq.best.numel()) != S or int(off.numel()) != m + 1:
+        raise MtrError(f"{int(gq.best.numel())} best alleles for {S} entries of {m} loci")
+    dev = allele.device
+    n = off[1:] - off[:-1]
+    locus = torch.searchsorted(off[1:].contiguous(), torch.arange(S, dtype=torch.int64, device=dev), right=True)        # the entry's locus
+    n1 = torch.zeros(m, dtype=torch.int64, device=dev).index_add_(0, locus, (gq.best == 1).to(torch.int64))
+    moved = (zyg == 2) & (n1 > 0) & (n1 < n)
+    new_allele = torch.where(moved[locus], gq.best, allele)
+    order = torch.sort(locus * 2 + torch.where(moved[locus], new_allele.to(torch.int64), torch.zeros_like(locus)), stable=True).indices
+    value, read, new_allele = calls.value[order], calls.read[order], new_allele[order]
+    n_a = torch.stack([n - n1, n1], dim=1)
+    first = torch.stack([off[:-1], off[:-1] + n - n1], dim=1)
+    at = torch.where(moved[:, None], first + (n_a - 1) // 2, torch.zeros_like(first))
+    call = torch.where(moved[:, None], value[at.reshape(-1)].reshape(m, 2) if S else calls.call, calls.call)
+    support = torch.where(moved[:, None], n_a.to(calls.call_support.dtype), calls.call_support)
+    return AlleleCalls(off, value, read, new_allele, zyg, call, support, calls.cost)
 
 
 def _cat(parts):

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmtr_hip.so")
 SOURCES = ["mtr_abi.hip", "quality.hip.inc", "consensus_quality.hip.inc", "mtr_common.h", "walk_screen.h", "polish_plan.h", "file_state.h", "loci_args.h", "revise_task.h", "dp_task_plan.h", "align_host.hip.inc", "test_entries.hip.inc", "motif_host.hip.inc", "genotype_host.hip.inc", "allele_host.hip.inc", "device_util.hip.inc", "k1_ranges.hip.inc", "k2_units.hip.inc", "k3_staged.hip.inc",
-           "dp_wrap.hip.inc", "dp_quad.hip.inc", "dp_test.hip.inc", "gather.hip.inc", "pack.hip.inc", "records.hip.inc", "chain.hip.inc", "report_align.hip.inc", "report_text.hip.inc", "report_motif.hip.inc", "unit_motif.h", "motif_search.hip.inc", "motif_dp.h", "motif_loci.hip.inc", "motif_loci.h", "flank_search.hip.inc", "flank_bv.h", "genotype.hip.inc", "catalog.hip.inc", "seed_index.h", "partial.hip.inc", "partial_catalog.hip.inc", "catalog_build.hip.inc", "catalog_build.h", "motif_ext.h", "allele_call.hip.inc", "allele_split.h", "consensus.hip.inc", "banded_align.h", "window_structure.hip.inc", "window_structure.h", "window_structure_args.h", "window_edits.hip.inc", "window_edits.h", "seq_calls.hip.inc", "seq_calls.h", "fasta.hip.inc", "fastq.hip.inc", "file_order.hip.inc", "min_missing_table.h", os.path.join("..", "..", "include", "mtr_hip.h")]
+           "dp_wrap.hip.inc", "dp_quad.hip.inc", "dp_test.hip.inc", "gather.hip.inc", "pack.hip.inc", "records.hip.inc", "chain.hip.inc", "report_align.hip.inc", "report_text.hip.inc", "report_motif.hip.inc", "unit_motif.h", "motif_search.hip.inc", "motif_dp.h", "motif_loci.hip.inc", "motif_loci.h", "flank_search.hip.inc", "flank_bv.h", "genotype.hip.inc", "catalog.hip.inc", "seed_index.h", "partial.hip.inc", "partial_catalog.hip.inc", "catalog_build.hip.inc", "catalog_build.h", "motif_ext.h", "allele_call.hip.inc", "allele_split.h", "consensus.hip.inc", "banded_align.h", "window_structure.hip.inc", "window_structure.h", "window_structure_args.h", "window_edits.hip.inc", "window_edits.h", "seq_calls.hip.inc", "seq_calls.h", "genotype_quality.hip.inc", "genotype_quality.h", "fasta.hip.inc", "fastq.hip.inc", "file_order.hip.inc", "min_missing_table.h", os.path.join("..", "..", "include", "mtr_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
          "-ffp-contract=off", "-fno-fast-math",      # fp64 DI values and float ratios must round exactly like the reference's C
          "-fhip-fp32-correctly-rounded-divide-sqrt",

@@ -760,3 +760,112 @@ extern "C" mtr_status mtr_call_alleles_sequence_copy_device(mtr_ctx *ctx, const 
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MTR_OK;
 }
+
+// ---- the genotype quality (genotype_quality.hip.inc) -----------------------------------------------------------------------------------------------
+// The consensus' checks in its order with its own list kernels, cons_off on the device, then the destination - every refusal comes before the
+// first kernel that is given dst -, the tasks, one look at the buckets' counts, the scores bucket by bucket, the loci.  Nothing is kept.
+static_assert(sizeof(mtr_gq_params) == sizeof(GqParams), "the genotype quality's parameters");
+
+template <int ROWS, int CPL>
+static void gq_score_bucket(mtr_ctx *ctx, const GqArgs &a, const int4 *tasks, int64_t step, unsigned n_tasks)
+{
+    if (n_tasks == 0) return;
+    const unsigned groups = (n_tasks + (unsigned)ROWS - 1u) / (unsigned)ROWS;
+    hipLaunchKernelGGL((mtr_k_gq_score<ROWS, CPL>), dim3(std::min<unsigned>(groups, GQ_MAX_GRID)), dim3(64), 0, ctx->stream, a, tasks, step, n_tasks);
+}
+
+extern "C" mtr_status mtr_genotype_quality_device(mtr_ctx *ctx, const mtr_consensus_src *src, const uint8_t *win_qual, const int64_t *cons_off, const uint8_t *cons_bases,
+                                                  int64_t n_cons, const mtr_gq_params *prm, void *wait_stream, const mtr_gq_dst *dst)
+{
+    if (!ctx) return MTR_ERR_BAD_ARG;
+    if (end_pending_run(ctx) != MTR_OK) return MTR_ERR_HIP;
+    if (!src || !prm || !dst) { ctx->err = "src, prm or dst is NULL"; return MTR_ERR_BAD_ARG; }
+    const int64_t R = src->n_rows, S = src->n_support, NB = src->n_bases, NC = n_cons; const int32_t n_loci = src->n_loci;
+    if (n_loci < 1 || n_loci > (1 << 30) - 1) { ctx->err = "n_loci = " + std::to_string(n_loci) + " outside 1..2^30 - 1"; return MTR_ERR_BAD_ARG; }
+    if (R < 0 || R > (int64_t)INT32_MAX) { ctx->err = "n_rows = " + std::to_string(R) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (S < 0 || S > (int64_t)INT32_MAX) { ctx->err = "n_support = " + std::to_string(S) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (NB < 0 || NB > (int64_t)INT32_MAX) { ctx->err = "n_bases = " + std::to_string(NB) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (NC < 0 || NC > (int64_t)INT32_MAX) { ctx->err = "n_cons = " + std::to_string(NC) + " outside 0..2^31 - 1"; return MTR_ERR_BAD_ARG; }
+    if (prm->band_extra < 0 || prm->band_extra > MTR_CONS_MAX_EXTRA) { ctx->err = "band_extra = " + std::to_string(prm->band_extra) + " outside 0.." + std::to_string(MTR_CONS_MAX_EXTRA); return MTR_ERR_BAD_ARG; }
+    if (prm->qual_cap < 1 || prm->qual_cap > MTR_CONSQ_MAX_CAP) { ctx->err = "qual_cap = " + std::to_string(prm->qual_cap) + " outside 1.." + std::to_string(MTR_CONSQ_MAX_CAP); return MTR_ERR_BAD_ARG; }
+    if (prm->gap_cap < 1 || prm->gap_cap > prm->qual_cap) { ctx->err = "gap_cap = " + std::to_string(prm->gap_cap) + " outside 1..qual_cap = " + std::to_string(prm->qual_cap); return MTR_ERR_BAD_ARG; }
+    if (prm->read_cap < 1 || prm->read_cap > MTR_GQ_MAX_READ_CAP) { ctx->err = "read_cap = " + std::to_string(prm->read_cap) + " outside 1.." + std::to_string(MTR_GQ_MAX_READ_CAP); return MTR_ERR_BAD_ARG; }
+    if (!src->win_off || !src->support_off || !src->zygosity || !cons_off || (R > 0 && (!src->row_read || !src->row_locus)) || (NB > 0 && !src->win_bases) || (NC > 0 && !cons_bases) ||
+        (S > 0 && (!src->read || !src->allele))) { ctx->err = "an input column is NULL"; return MTR_ERR_BAD_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t G = 2 * (int64_t)n_loci;
+    {
+        const DeviceCol cols[11] = {
+            { src->row_read, R * 4, "src->row_read" }, { src->row_locus, R * 4, "src->row_locus" }, { src->win_off, (R + 1) * 8, "src->win_off" }, { src->win_bases, NB, "src->win_bases" },
+            { win_qual, win_qual ? NB : 0, "win_qual" },
+            { src->support_off, ((int64_t)n_loci + 1) * 8, "src->support_off" }, { src->read, S * 4, "src->read" }, { src->allele, S, "src->allele" }, { src->zygosity, n_loci, "src->zygosity" },
+            { cons_off, (G + 1) * 8, "cons_off" }, { cons_bases, NC, "cons_bases" } };
+        { mtr_status st = check_device_cols(ctx, cols, "the column's bytes"); if (st != MTR_OK) return st; }
+    }
+    const size_t ns = std::max<size_t>((size_t)S, 1);
+    HIPCHK(ctx->d_gq_i32.ensure(ns * 4)); HIPCHK(ctx->d_gq_tasks.ensure(4 * ns * sizeof(int4)));
+    { mtr_status st = columns_begin(ctx, wait_stream, ctx->d_gq_state, CO_BAD, SQ_STATE * 4); if (st != MTR_OK) return st; }
+    GqArgs a{};
+    ConsArgs &c = a.c;
+    c.row_read = src->row_read; c.row_locus = src->row_locus; c.R = R; c.win_off = src->win_off; c.win_bases = src->win_bases; c.n_bases = NB;
+    c.support_off = src->support_off; c.sup_read = src->read; c.sup_allele = src->allele; c.zygosity = src->zygosity; c.S = S; c.n_loci = n_loci; c.band_extra = prm->band_extra;
+    c.ent_row = ctx->d_gq_i32; c.bad = ctx->d_gq_state; c.state = (unsigned *)(c.bad + CO_BAD);
+    a.win_qual = NB > 0 ? win_qual : nullptr; a.cons_off = cons_off; a.cons_bases = cons_bases; a.n_cons = NC;
+    a.prm = { prm->band_extra, prm->qual_cap, prm->gap_cap, prm->read_cap };
+    a.tasks = ctx->d_gq_tasks;
+    const auto blocks = [](int64_t n) { return dim3((unsigned)((std::max<int64_t>(n, 1) + GQ_BLOCK - 1) / GQ_BLOCK)); };
+    const dim3 blk(GQ_BLOCK);
+    static_assert(GQ_BLOCK == CO_BLOCK, "the consensus' list kernels are launched with this block");
+    unsigned long long bad[CO_BAD];
+    hipLaunchKernelGGL(mtr_k_cons_check, blocks(std::max<int64_t>(R, n_loci)), blk, 0, ctx->stream, c);
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(ctx, bad, c.bad, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad[0] != ~0ull) { ctx->err = "row " + std::to_string(bad[0]) + " is out of order: the rows must ascend by (read, locus), each pair once, none negative"; return MTR_ERR_BAD_ARG; }
+    if (bad[1] != ~0ull) { ctx->err = "win_off at row " + std::to_string(bad[1]) + " does not ascend from 0 to n_bases, or the window is above 2^30 bases"; return MTR_ERR_BAD_ARG; }
+    if (bad[2] != ~0ull) { ctx->err = "locus " + std::to_string(bad[2]) + ": support_off does not ascend from 0 to n_support, or the zygosity is above 2"; return MTR_ERR_BAD_ARG; }
+    if (S > 0) hipLaunchKernelGGL(mtr_k_cons_members, blocks(S), blk, 0, ctx->stream, c);
+    hipLaunchKernelGGL(mtr_k_gq_check, blocks(G), blk, 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(ctx, bad, c.bad, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad[3] != ~0ull) {
+        int32_t rd = 0;
+        HIPCHK(copy_sync(ctx, &rd, src->read + bad[3], 4, hipMemcpyDeviceToHost));
+        ctx->err = "support entry " + std::to_string(bad[3]) + " (read " + std::to_string(rd) + ") has no row of its (read, locus)";
+        return MTR_ERR_BAD_ARG;
+    }
+    if (bad[4] != ~0ull) { ctx->err = "support entry " + std::to_string(bad[4]) + ": the allele column is not 0 .. 0 1 .. 1 within its locus"; return MTR_ERR_BAD_ARG; }
+    if (bad[GQ_BAD_CONS] != ~0ull) {
+        ctx->err = "allele " + std::to_string(bad[GQ_BAD_CONS]) + " (locus " + std::to_string(bad[GQ_BAD_CONS] >> 1) + "): cons_off does not ascend from 0 to n_cons"; return MTR_ERR_BAD_ARG;
+    }
+    if (dst->cap_support < S) { ctx->err = "destination holds " + std::to_string(dst->cap_support) + " supporting rows, " + std::to_string(S) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (dst->cap_loci < n_loci) { ctx->err = "destination holds " + std::to_string(dst->cap_loci) + " loci, " + std::to_string(n_loci) + " needed"; return MTR_ERR_OVERFLOW; }
+    if (!dst->raw || !dst->pl || !dst->gt || !dst->gq || !dst->scored || !dst->unscored || (S > 0 && (!dst->score || !dst->best || !dst->margin))) {
+        ctx->err = "a destination column is NULL"; return MTR_ERR_BAD_ARG;
+    }
+    {
+        const int64_t L = n_loci;
+        const DeviceCol cols[9] = { { dst->score, S * 8, "dst->score" }, { dst->best, S, "dst->best" }, { dst->margin, S * 4, "dst->margin" }, { dst->raw, L * 24, "dst->raw" },
+                                    { dst->pl, L * 24, "dst->pl" }, { dst->gt, L, "dst->gt" }, { dst->gq, L * 8, "dst->gq" }, { dst->scored, L * 4, "dst->scored" },
+                                    { dst->unscored, L * 4, "dst->unscored" } };
+        { mtr_status st = check_device_cols(ctx, cols, "the column's bytes"); if (st != MTR_OK) return st; }
+    }
+    a.score = dst->score; a.best = dst->best; a.margin = dst->margin; a.raw = dst->raw; a.pl = dst->pl; a.gt = dst->gt; a.gq = dst->gq; a.scored = dst->scored; a.unscored = dst->unscored;
+    if (S > 0) {
+        const int64_t P = 2 * S;
+        hipLaunchKernelGGL(mtr_k_gq_tasks, dim3((unsigned)std::min<int64_t>((P + GQ_BLOCK - 1) / GQ_BLOCK, GQ_MAX_GRID)), blk, 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        unsigned n[SQ_STATE];
+        HIPCHK(copy_sync(ctx, n, c.state, sizeof n, hipMemcpyDeviceToHost));
+        if ((int64_t)n[0] + n[1] > P || (int64_t)n[2] + n[3] > P) { ctx->err = "the genotype quality's task lists failed on the device"; return MTR_ERR_HIP; }
+        const char *e = getenv("MTR_TEST_GQ_ROWS");
+        if (e && atoi(e) == 0) { gq_score_bucket<1, 1>(ctx, a, a.tasks, 1, n[0]); gq_score_bucket<1, 1>(ctx, a, a.tasks + P - 1, -1, n[1]); }
+        else { gq_score_bucket<4, 1>(ctx, a, a.tasks, 1, n[0]); gq_score_bucket<2, 1>(ctx, a, a.tasks + P - 1, -1, n[1]); }
+        gq_score_bucket<1, 1>(ctx, a, a.tasks + P, 1, n[2]);
+        gq_score_bucket<1, 2>(ctx, a, a.tasks + 2 * P - 1, -1, n[3]);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(mtr_k_gq_locus, dim3((unsigned)std::min<int64_t>(n_loci, GQ_MAX_GRID)), dim3(64), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MTR_OK;
+}

@@ -58,6 +58,7 @@
 #include "window_structure_args.h"
 #include "window_edits.hip.inc"
 #include "seq_calls.hip.inc"
+#include "genotype_quality.hip.inc"
 #include "fasta.hip.inc"
 #include "fastq.hip.inc"
 #include "file_order.hip.inc"
@@ -297,6 +298,8 @@ struct mtr_ctx {
     DevBuf<int32_t> d_sq_i32, d_sq_value, d_sq_read, d_sq_dtm, d_sq_call, d_sq_sup, d_sq_medoid; DevBuf<uint8_t> d_sq_allele, d_sq_zyg, d_sq_skipped, d_sq_dist;
     DevBuf<int64_t> d_sq_off, d_sq_pair_off, d_sq_cost; DevBuf<int4> d_sq_tasks; DevBuf<unsigned long long> d_sq_state;
     bool sq_ready = false; int64_t sq_support = 0, sq_pairs = 0; int32_t sq_loci = 0;
+    // the genotype quality (genotype_quality.hip.inc), per call and nothing kept, buffers of its own: the entries' rows, the tasks, the state
+    DevBuf<int32_t> d_gq_i32; DevBuf<int4> d_gq_tasks; DevBuf<unsigned long long> d_gq_state;
     long long wrap_dp_size = MTRC_WRAP_DP_SIZE;          // the WrapDPsize the kernels of this context's device test (MTR_TEST_WRAP_DP_SIZE)
     // a FASTA file in device memory (fasta.hip.inc), per call: the tiles' columns, the header windows' columns, the IDs' offsets, the stop, the sizes
     DevBuf<uint32_t> d_fa_tiles, d_fa_hbase; DevBuf<int32_t> d_fa_hpos, d_fa_hidlen; DevBuf<int64_t> d_fa_idoff;
